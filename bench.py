@@ -13,11 +13,16 @@ BASELINE.json configs[4], the rumination queue of `--batch` frames sharded over 
 (`--scaling strong`, the default: 1024 frames in all, 1024 / N per rank) or `--batch` frames PER rank (`--scaling weak`); each rank
 writes fixed-capacity per-frame records and the step ends with the queue's ONE all-gather of them.
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (per-stage device time from HIP events on the stream the
-kernels run on, every kernel alone on it); `cpu_baseline` is the CPU oracle (kind "port": the reference itself cannot be built in
-this image) timed single-threaded on a bounded sample of the same frames, rank 0, N = 1 only.  N = 1 also reports
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the `--steps` steps and prints the headline figure (`value`,
+`ms_per_step`).  Everything else is measured only with `--full`: `roofline` is for the dominant kernel (per-stage device time from
+HIP events on the stream the kernels run on, every kernel alone on it, in profiled passes of their own); `cpu_baseline` is the CPU
+oracle (kind "port": the reference itself cannot be built without its OpenCV / Eigen / ROS toolchain) timed single-threaded on a
+bounded sample of the same frames, rank 0, N = 1 only.  N = 1 with `--full` also reports
 `value_h2d_inclusive` (the same step with the frames starting in pinned HOST memory, transfers overlapped with the kernels),
 `single_frame_host_api_fps` (and `single_frame_c_call_fps`: the C entry alone on the pinned capture buffer), a `batch_sweep`, and the `lba` / `pose_opt` side legs.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0's frames) as DIR/<name>.npy, float32 / float64; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output (see `dump_outputs`).
 """
 import argparse
 import json
@@ -179,6 +184,38 @@ def make_frames(torch, np, dev, n, rank):
     return fr, host
 
 
+DUMP_MAX_FRAMES = 128          # per-frame arrays of --dump-outputs: a fixed, seeded sample of at most this many frames of the step
+DUMP_BUDGET_BYTES = 48 << 20   # ... and fewer when --nfeatures makes the per-frame arrays larger (every file together stays below 64 MB)
+
+
+def dump_outputs(d, out):
+    """--dump-outputs: the last timed step's (kp, desc, counts, matches), what the caller of the step receives, as .npy files in `d`.
+    counts.npy [F,2] f64 (n, monoIndex) for every frame of the step; sample_frames.npy [S] f64: the frames of the seeded sample, in order;
+    for those frames keypoints.npy [S,cap,7] f64 (x, y, size, angle, response, octave, class_id), descriptors.npy [S,cap,32] f32 (byte values),
+    match_best_idx / match_best_dist / match_second_dist.npy [S,cap] f64 (each frame against its successor).  Slots at and past a frame's
+    count are written as 0 (the buffers hold whatever an earlier step left there)."""
+    import numpy as np
+    import torch
+    kp, desc, counts, m = out
+    n, cap = int(kp.shape[0]), int(kp.shape[1])
+    per_frame = cap * (7 * 8 + 32 * 4 + 3 * 8)
+    s = max(1, min(n, DUMP_MAX_FRAMES, DUMP_BUDGET_BYTES // per_frame))
+    sel = np.sort(np.random.default_rng(0).choice(n, s, replace=False))
+    idx = torch.as_tensor(sel, device=kp.device)
+    cnt = counts.cpu().numpy()
+    valid = np.arange(cap)[None, :] < cnt[sel, 0:1]
+    rec = kp[idx].cpu().numpy()                               # f32 view of the 28-byte records: five floats, then octave and class_id as int32
+    kpo = np.concatenate([rec[..., :5].astype(np.float64), rec[..., 5:].view(np.int32).astype(np.float64)], axis=-1)
+    arrays = {"counts": cnt.astype(np.float64), "sample_frames": sel.astype(np.float64),
+              "keypoints": np.where(valid[..., None], kpo, 0.0),
+              "descriptors": np.where(valid[..., None], desc[idx].cpu().numpy().astype(np.float32), np.float32(0))}
+    for name, t in zip(("match_best_idx", "match_best_dist", "match_second_dist"), m):
+        arrays[name] = np.where(valid, t[idx].cpu().numpy().astype(np.float64), 0.0)
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def one_process_queue(args):
     """`bench.py --gpus N --one-process`: the reference is ONE C++ process (System.cc:193-240), so is this leg: rumi_queue_extract cuts the host
     queue into N contiguous blocks, one extractor per device, ONE ncclAllGather of the records (include/rumi_queue.h).  Extraction only."""
@@ -234,10 +271,18 @@ def main():
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong", help="N > 1: --batch frames in all (strong) or per rank (weak)")
     ap.add_argument("--nfeatures", type=int, default=1000)
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-oracle baseline leg")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline and the side legs (profiling runs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and the side legs (profiling runs)")
     ap.add_argument("--one-process", action="store_true", help="the queue over --gpus devices from ONE process through include/rumi_queue.h (RCCL all-gather inside the library) instead of one rank per GPU; "
                     "RUMI_BENCH_LOGICAL_SHARDS=1 aliases every shard to device 0 (a one-GPU box)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: per-stage profiled passes and the roofline, and (N = 1, "
+                    "unless --no-cpu) the host-memory, single-frame, sweep, CPU baseline, LBA, pose, tracking-frame and one-process queue legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, "
+                    "rank 0's frames; per-frame arrays of a fixed seeded sample of frames)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.one_process and args.dump_outputs:
+        ap.error("--dump-outputs is not supported with --one-process")
     if args.one_process:
         claim_stdout()
         return one_process_queue(args)
@@ -377,54 +422,28 @@ def main():
         return dt, out
 
     dt, out = timed(step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     n_kp = float(out[2][:, 0].float().mean().item())
 
-    # per-stage device time of one more (untimed) pass with every kernel ALONE on one stream in launches of up to 256 frames
-    # (rumi_orb_set_profiling: HIP events recorded by the library on the stream the kernels run on)
-    ext.set_resident_queue(False)
-    ext.extract_batch(frames, (0, 1000), cap=cap)           # (this mode's arenas and code paths warm)
-    torch.cuda.synchronize()
-    ext.set_profiling(True)
-    passes = []
-    for _ in range(5):
-        ext.extract_batch(frames, (0, 1000), cap=cap)
+    if args.full:
+        # per-stage device time of one more (untimed) pass with every kernel ALONE on one stream in launches of up to 256 frames
+        # (rumi_orb_set_profiling: HIP events recorded by the library on the stream the kernels run on)
+        ext.set_resident_queue(False)
+        ext.extract_batch(frames, (0, 1000), cap=cap)           # (this mode's arenas and code paths warm)
         torch.cuda.synchronize()
-        passes.append({k: float(v) for k, v in ext.stage_ms().items()})
-    stage = {k: sorted(p[k] for p in passes)[len(passes) // 2] for k in passes[0]}      # per stage: the median of five passes
-    ext.set_profiling(False)
-    ext.set_resident_queue(True)
+        ext.set_profiling(True)
+        passes = []
+        for _ in range(5):
+            ext.extract_batch(frames, (0, 1000), cap=cap)
+            torch.cuda.synchronize()
+            passes.append({k: float(v) for k, v in ext.stage_ms().items()})
+        stage = {k: sorted(p[k] for p in passes)[len(passes) // 2] for k in passes[0]}      # per stage: the median of five passes
+        ext.set_profiling(False)
+        ext.set_resident_queue(True)
 
     if rank == 0:
         fps = n_queue * args.steps / dt
-        ab = algorithmic_bytes_per_frame(n_kp)
-        # dominant kernel by device time; algorithmic bytes of that kernel per launch
-        # (pyramid: SURVEY.md section 8d's figure -- level 0 read once, levels 1-7 written once; the re-reads of levels 1-6 as sources are traffic, not algorithm)
-        kern_bytes = {"fast": ab["fast_read"], "pyramid": ab["read_l0"] + ab["write_levels"],
-                      "blur": ab["blur_rw"], "orient_desc": n_kp * ab["per_kp"], "quadtree": 0.0}
-        kern_ms = {k: stage[k] for k in kern_bytes}
-        dom = max(kern_ms, key=kern_ms.get)
-        per_launch = min(B, 256)
-        n_launch = (B + 255) // 256
-        achieved = kern_bytes[dom] * B / (kern_ms[dom] * 1e-3) / 1e9 if kern_ms[dom] > 0 else 0.0
-        kname = {"fast": "k_fast_cells", "blur": "k_blur", "orient_desc": "k_orient_desc", "quadtree": "k_octree", "pyramid": "k_resize"}[dom]
-        # HBM bytes per launch from the PMC counters: rocprofv3 cannot wrap this process from inside, so these two numbers are the committed
-        # results of separate --pmc passes of this command line (profiles/r04_pmc_*.json); `*_source` says so, and they are used only when
-        # taken at the same frames-per-launch.
-        traffic, valu = None, None
-        try:
-            pm = json.load(open(os.path.join(ROOT, "profiles", "r04_pmc_traffic.json")))
-            if pm.get("frames_per_launch") == per_launch and kname in pm["kernels"]:
-                traffic = pm["kernels"][kname]["hbm_bytes_per_launch"]
-        except Exception:
-            traffic = None
-        try:
-            sq = json.load(open(os.path.join(ROOT, "profiles", "r04_pmc_sq_counters.json")))["kernels"][kname]
-            if per_launch == 256:
-                valu = {"wave_insts_per_launch": int(sq["SQ_INSTS_VALU"]), "lds_insts_per_launch": int(sq.get("SQ_INSTS_LDS", 0)),
-                        "lds_bank_conflict_cycles": int(sq.get("SQ_LDS_BANK_CONFLICT", 0)),
-                        "note": "instruction classes issue at 2.4 (add/sub/logic/shift-right) or 4.2 (min/max, 3-operand, packed) cycles per wave and SIMD: profiles/r02_valu_issue_rates.txt"}
-        except Exception:
-            valu = None
         line = {
             "metric": "frames/sec ORB extract+match", "value": round(fps, 1), "unit": "frames/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -434,19 +453,51 @@ def main():
                        "frames_per_step": n_queue, "frames_per_step_per_gpu": B, "scaling": args.scaling if world > 1 else "n/a (one GPU)",
                        "mean_keypoints_per_frame": round(n_kp, 1),
                        "exchange": "one all_gather_into_tensor of %d-byte per-frame records over RCCL, overlapped with the next step" % rumination.record_bytes(cap) if world > 1 else "none"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                         "traffic_source": "committed profile profiles/r04_pmc_traffic.json (separate --pmc passes), not this run" if traffic else None,
-                         "algorithmic_bytes_per_launch": int(kern_bytes[dom] * per_launch), "frames_per_launch": per_launch,
-                         "launch_ms": round(kern_ms[dom] / n_launch, 4),
-                         "whole_path_GBps": round(ab["total"] * fps / 1e9, 2),
-                         "whole_path_frac": round(ab["total"] * fps / 1e9 / HBM_PEAK_GBS, 5), "valu": valu,
-                         "valu_source": "committed profile profiles/r04_pmc_sq_counters.json, not this run" if valu else None},
-            "valu_issue": whole_path_valu_issue(fps),
-            "stage_ms_per_step": {k: round(v, 3) for k, v in stage.items()},
-            "stage_ms_note": "five extra profiled steps (per stage the median): every kernel alone on ONE stream (RUMI_SERIAL-equivalent: the blur too), launches of up to 256 frames, summed over the step's launches",
         }
-        if world == 1 and not args.no_cpu:
+        if args.full:
+            ab = algorithmic_bytes_per_frame(n_kp)
+            # dominant kernel by device time; algorithmic bytes of that kernel per launch
+            # (pyramid: SURVEY.md section 8d's figure -- level 0 read once, levels 1-7 written once; the re-reads of levels 1-6 as sources are traffic, not algorithm)
+            kern_bytes = {"fast": ab["fast_read"], "pyramid": ab["read_l0"] + ab["write_levels"],
+                          "blur": ab["blur_rw"], "orient_desc": n_kp * ab["per_kp"], "quadtree": 0.0}
+            kern_ms = {k: stage[k] for k in kern_bytes}
+            dom = max(kern_ms, key=kern_ms.get)
+            per_launch = min(B, 256)
+            n_launch = (B + 255) // 256
+            achieved = kern_bytes[dom] * B / (kern_ms[dom] * 1e-3) / 1e9 if kern_ms[dom] > 0 else 0.0
+            kname = {"fast": "k_fast_cells", "blur": "k_blur", "orient_desc": "k_orient_desc", "quadtree": "k_octree", "pyramid": "k_resize"}[dom]
+            # HBM bytes per launch from the PMC counters: rocprofv3 cannot wrap this process from inside, so these two numbers are the committed
+            # results of separate --pmc passes of this command line (profiles/r04_pmc_*.json); `*_source` says so, and they are used only when
+            # taken at the same frames-per-launch.
+            traffic, valu = None, None
+            try:
+                pm = json.load(open(os.path.join(ROOT, "profiles", "r04_pmc_traffic.json")))
+                if pm.get("frames_per_launch") == per_launch and kname in pm["kernels"]:
+                    traffic = pm["kernels"][kname]["hbm_bytes_per_launch"]
+            except Exception:
+                traffic = None
+            try:
+                sq = json.load(open(os.path.join(ROOT, "profiles", "r04_pmc_sq_counters.json")))["kernels"][kname]
+                if per_launch == 256:
+                    valu = {"wave_insts_per_launch": int(sq["SQ_INSTS_VALU"]), "lds_insts_per_launch": int(sq.get("SQ_INSTS_LDS", 0)),
+                            "lds_bank_conflict_cycles": int(sq.get("SQ_LDS_BANK_CONFLICT", 0)),
+                            "note": "instruction classes issue at 2.4 (add/sub/logic/shift-right) or 4.2 (min/max, 3-operand, packed) cycles per wave and SIMD: profiles/r02_valu_issue_rates.txt"}
+            except Exception:
+                valu = None
+            line.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                             "traffic_source": "committed profile profiles/r04_pmc_traffic.json (separate --pmc passes), not this run" if traffic else None,
+                             "algorithmic_bytes_per_launch": int(kern_bytes[dom] * per_launch), "frames_per_launch": per_launch,
+                             "launch_ms": round(kern_ms[dom] / n_launch, 4),
+                             "whole_path_GBps": round(ab["total"] * fps / 1e9, 2),
+                             "whole_path_frac": round(ab["total"] * fps / 1e9 / HBM_PEAK_GBS, 5), "valu": valu,
+                             "valu_source": "committed profile profiles/r04_pmc_sq_counters.json, not this run" if valu else None},
+                "valu_issue": whole_path_valu_issue(fps),
+                "stage_ms_per_step": {k: round(v, 3) for k, v in stage.items()},
+                "stage_ms_note": "five extra profiled steps (per stage the median): every kernel alone on ONE stream (RUMI_SERIAL-equivalent: the blur too), launches of up to 256 frames, summed over the step's launches",
+            })
+        if args.full and world == 1 and not args.no_cpu:
             # ---- the same step with the frames starting in pinned HOST memory (the queue as the reference holds it), transfers overlapped ----
             hostq = frames.cpu().pin_memory()
 
@@ -578,7 +629,7 @@ def main():
             line["cpu_baseline"] = {"value": round(n / cdt, 2), "unit": "frames/s", "cores": 1, "kind": "port",
                                     "sample": "%d of the same synthetic frames (extract + brute-force match), oracle/ (g++ -O2, scalar, 1 thread), %.1f s" % (n, cdt)}
             line.update(side_legs(args))
-        if world == 1 and not args.no_cpu and hostq is not None:
+        if args.full and world == 1 and not args.no_cpu and hostq is not None:
             # (last of the N = 1 legs: RCCL's communicator leaves helper threads behind, and the one-frame host path measured after it ran at 2.8 k fps instead of 8 k)
             # ---- the queue behind the C ABI, ONE process (include/rumi_queue.h): host frames in, every shard's device holds the gathered records, host
             # records out.  One shard = this GPU (its exchange is RCCL's ncclAllGather on one rank); two LOGICAL shards on this GPU for the sharded code path.

@@ -49,7 +49,7 @@ for d, tmp in (("pmc_fetch", "/tmp/_pf"), ("pmc_write", "/tmp/_pw")):
     shutil.copy(newest(d + "/*/*counter_collection.csv"), tmp + "/x/")
 subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "pmc_summary.py"), "/tmp/_pf", "/tmp/_pw", os.path.join(P, TAG + "_pmc_traffic.json"), "256"],
                       stdout=subprocess.DEVNULL)
-out = {"command": "RUMI_SERIAL=1 rocprofv3 --kernel-trace --pmc <8 SQ counters> -- python3 bench.py --steps 2 --warmup 1 --batch 256 --no-cpu (two passes)",
+out = {"command": "RUMI_SERIAL=1 rocprofv3 --kernel-trace --pmc <8 SQ counters> -- python3 bench.py --full --steps 2 --warmup 1 --batch 256 --no-cpu (two passes)",
        "unit": "counter value per launch (256 frames), averaged over the sampled launches", "kernels": {}}
 for d in ("pmc_a", "pmc_b"):
     agg = collections.defaultdict(lambda: collections.defaultdict(list))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Turns two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; separate runs, as MI355X_MICROARCH.md §HBM prescribes) of
-`bench.py --steps 2 --warmup 1 --no-cpu` into profiles/<tag>_pmc_traffic.json: HBM bytes per launch and kernel,
+`bench.py --full --steps 2 --warmup 1 --no-cpu` into profiles/<tag>_pmc_traffic.json: HBM bytes per launch and kernel,
     bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024
 The factor 2 on the read side is the gfx950 correction of the guide, re-calibrated here with tools/pmc_calib.hip for BOTH
 16 B/lane and 4 B/lane coalesced streaming reads of 1 GiB (FETCH_SIZE * 1024 = 0.5000 x bytes read in both cases).
