@@ -12,7 +12,7 @@
 //                    round k queries 0..k-1 hold their sequential result, and a fix point is the sequential result
 //                    (induction on the query index), so the outcome equals the reference's loop bit for bit.
 //                    Then the rotation histogram / ComputeThreeMaxima filter and the result arrays.
-//   k_bruteforce     all-pairs best / second-best, queries in registers, train descriptors broadcast from LDS.
+//   k_bruteforce_mfma  all-pairs best / second-best as an int8 GEMM on the matrix cores (k_bruteforce: the VALU form, RUMI_BF_VALU=1).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1141,6 +1141,143 @@ __global__ __launch_bounds__(256) void k_bruteforce(const uint8_t *__restrict__ 
     }
 }
 
+// ---- brute force on the int8 matrix cores ----------------------------------------------------------------------------
+// With train bits t and query bits q (popcount pq): Ham(t, q) = pq + X, X = sum_k t_k (1 - 2 q_k), an exact int8 GEMM of
+// trains (A, 0/1 bytes) by queries (B, +1/-1 bytes) over K = 256 on v_mfma_i32_32x32x32_i8 (8 per 32 x 32 tile).  For one
+// query pq is a constant, so the running (best, second) are kept on X as SIGNED keys (X << 16 | train index) and pq is
+// added once at the end; min_i32 / med3_i32 then order them exactly as the VALU kernel orders (Ham << 16 | index).
+//
+// Fragment maps.  C/D of 32x32: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 h, h = lane >> 5.  A and B: lane l
+// holds row (A) / column (B) l & 31 and 16 k-values that depend only on (h, byte); the Hamming sum does not depend on the order
+// of k, so both operands take the same bit -> byte expansion and the hardware's k order never matters: k-step s, lane half h,
+// fragment dword i, byte j holds bit 8 j + s of descriptor dword 4 h + i.
+//
+// Workgroup: 8 waves, 32 queries each (the B fragments, 32 VGPRs, expanded once); train rows staged 64 at a time (two
+// tiles), expanded into LDS as ready A fragments [tile][s][lane] (16 B each: one conflict-free ds_read_b128 per MFMA),
+// double-buffered (2 x 16 KiB), one barrier per stage.  Per lane the 16 accumulator rows belong to ONE query, so the
+// reduction needs no cross-lane traffic until the end, where the two lane halves (lanes l and l + 32: same query) merge.
+// While looping a key carries the row WITHOUT the half's + 4 (a constant per lane keeps the argmin, and the index term is
+// then wave-uniform); the merge adds it.  Padded train rows of the last tile start their accumulator at 1024 (X >= 768:
+// never beats the initial distance 256); padded query columns are computed and not written.
+typedef int32_t bfm_v4i __attribute__((ext_vector_type(4)));
+typedef int32_t bfm_v16i __attribute__((ext_vector_type(16)));
+constexpr int kBfmWaves = 8, kBfmQueries = 32 * kBfmWaves, kBfmStage = 64;
+
+__device__ __forceinline__ uint32_t bfm_expand(uint32_t x, int s) { return (x >> s) & 0x01010101u; }
+__device__ __forceinline__ int32_t imed3(int32_t a, int32_t b, int32_t c) {
+    int32_t r;
+    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
+__global__ __launch_bounds__(512) void k_bruteforce_mfma(const uint8_t *__restrict__ qd, const int32_t *__restrict__ nqArr,
+                                                         const uint8_t *__restrict__ td, const int32_t *__restrict__ ntArr,
+                                                         int countStride, long long qStride, long long tStride, int cap, int32_t *__restrict__ bestIdx,
+                                                         int32_t *__restrict__ bestDist, int32_t *__restrict__ secondDist, int ring) {
+    __shared__ bfm_v4i frag[2][2 * 8 * 64];                           // [buffer][tile * 8 + s][lane]
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tb = ring > 0 ? (b + 1 == ring ? 0 : b + 1) : b;
+    const int nq = min(nqArr[(size_t)b * countStride], cap), nt = min(ntArr[(size_t)tb * countStride], cap);
+    const int q0 = blockIdx.x * kBfmQueries;
+    if (q0 >= nq) return;
+    const int qi = q0 + wave * 32 + (lane & 31);
+    const bool waveLive = q0 + wave * 32 < nq;
+
+    // the query: +1 / -1 bytes (1 - 2 q) of this lane's half, and its popcount over both halves
+    uint32_t qa[4] = {0, 0, 0, 0};
+    if (qi < nq) {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(qd + (size_t)b * qStride + (size_t)qi * 32) + 4 * h;   // 4-byte aligned only
+#pragma unroll
+        for (int i = 0; i < 4; i++) qa[i] = src[i];
+    }
+    int pq = __popc(qa[0]) + __popc(qa[1]) + __popc(qa[2]) + __popc(qa[3]);
+    pq += __shfl_xor(pq, 32);
+    bfm_v4i bq[8];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t x = qa[i];
+#pragma unroll
+        for (int s = 0; s < 8; s++) {
+            const uint32_t e = bfm_expand(x, s);
+            bq[s][i] = (int32_t)(((e << 8) - e) | 0x01010101u);       // e * 255 per byte (no carries): 0x00 / 0xFF, then | 1: +1 / -1
+        }
+    }
+    // X = 256 - pq is Ham = 256: the initial best (index 0) and second (index 0xFFFF) of the VALU kernel
+    int32_t best = (int32_t)((uint32_t)(256 - pq) << 16), second = best | 0xFFFF;
+
+    // staging: thread -> (tile tt of the stage, fragment lane sl, dword i); one source dword, eight expanded dwords
+    const int si = tid & 3, sl = (tid >> 2) & 63, stt = tid >> 8;
+    const int srow = stt * 32 + (sl & 31), sdw = 4 * (sl >> 5) + si;
+    const uint32_t *tsrc = reinterpret_cast<const uint32_t *>(td + (size_t)tb * tStride) + sdw;
+    auto load = [&](int r0) -> uint32_t { const int r = r0 + srow; return r < nt ? tsrc[(size_t)r * 8] : 0u; };
+    auto store = [&](int buf, uint32_t x) {
+        uint32_t *dst = reinterpret_cast<uint32_t *>(&frag[buf][stt * 8 * 64 + sl]) + si;
+#pragma unroll
+        for (int s = 0; s < 8; s++) dst[s * 64 * 4] = bfm_expand(x, s);
+    };
+    if (nt > 0) store(0, load(0));
+    __syncthreads();
+    for (int r0 = 0, buf = 0; r0 < nt; r0 += kBfmStage, buf ^= 1) {
+        const bool more = r0 + kBfmStage < nt;
+        const uint32_t next = more ? load(r0 + kBfmStage) : 0u;      // in flight under this stage's MFMAs
+        if (waveLive) {
+#pragma unroll
+            for (int tt = 0; tt < 2; tt++) {
+                const int t0 = r0 + tt * 32;
+                if (t0 >= nt) break;
+                auto tile = [&](const bfm_v16i &init) {
+                    bfm_v16i acc = init;
+#pragma unroll
+                    for (int s = 0; s < 8; s++) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(frag[buf][(tt * 8 + s) * 64 + lane], bq[s], acc, 0, 0, 0);
+#pragma unroll
+                    for (int g = 0; g < 16; g++) {
+                        // (plain code, not asm: the compiler pads the MFMA -> VALU read hazard; the index as one SGPR gives one v_lshl_or_b32)
+                        const uint32_t idx = __builtin_amdgcn_readfirstlane(t0 + (g & 3) + 8 * (g >> 2));
+                        const int32_t key = (int32_t)(((uint32_t)acc[g] << 16) | idx);
+                        second = imed3(best, second, key);
+                        best = min(best, key);
+                    }
+                };
+                if (t0 + 32 <= nt) {
+                    tile(bfm_v16i{});                                   // C = inline 0: no accumulator set-up
+                } else {
+                    bfm_v16i init;
+#pragma unroll
+                    for (int g = 0; g < 16; g++) init[g] = t0 + (g & 3) + 8 * (g >> 2) + 4 * h < nt ? 0 : 1024;
+                    tile(init);
+                }
+            }
+        }
+        if (more) store(buf ^ 1, next);
+        __syncthreads();
+    }
+    // merge the halves: lane l + 32 holds the same query over rows + 4
+    const int32_t ob = __shfl_xor(best, 32) + 4, os = __shfl_xor(second, 32);
+    if (h == 0 && qi < nq) {
+        const int32_t b2 = min(best, ob), s2 = min(min(second, os), max(best, ob));
+        const size_t o = (size_t)b * cap + qi;
+        const int d1 = (b2 >> 16) + pq;
+        bestIdx[o] = d1 < 256 ? (b2 & 0xFFFF) : -1;
+        bestDist[o] = d1; secondDist[o] = (s2 >> 16) + pq;
+    }
+}
+
+// RUMI_BF_VALU=1: the VALU kernel above in place of the matrix-core one (A/B measurements and tests in one build)
+static int launch_bruteforce(const void *qd, const void *nq, const void *td, const void *nt, int count_stride, long long q_stride, long long t_stride,
+                             int cap, int nrows, void *best_idx, void *best_dist, void *second_dist, int ring, hipStream_t st) {
+    static const bool valu = std::getenv("RUMI_BF_VALU") && std::atoi(std::getenv("RUMI_BF_VALU")) != 0;
+    const dim3 grid((cap + 255) / 256, nrows);
+    if (valu)
+        hipLaunchKernelGGL(k_bruteforce, grid, dim3(256), 0, st, (const uint8_t *)qd, (const int32_t *)nq, (const uint8_t *)td, (const int32_t *)nt, count_stride,
+                           q_stride, t_stride, cap, (int32_t *)best_idx, (int32_t *)best_dist, (int32_t *)second_dist, ring);
+    else
+        hipLaunchKernelGGL(k_bruteforce_mfma, grid, dim3(64 * kBfmWaves), 0, st, (const uint8_t *)qd, (const int32_t *)nq, (const uint8_t *)td, (const int32_t *)nt,
+                           count_stride, q_stride, t_stride, cap, (int32_t *)best_idx, (int32_t *)best_dist, (int32_t *)second_dist, ring);
+    HIP_TRY(hipGetLastError());
+    return RUMI_OK;
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // SearchByBoW(KF_k, F) for K candidate key-frames against ONE frame in one launch (Tracking::Relocalization walks the candidates of
@@ -1999,11 +2136,8 @@ extern "C" int rumi_match_bruteforce_batch_device_strided(const void *d_query, c
         query_stride < 32ll * cap || train_stride < 32ll * cap || (query_stride & 3) || (train_stride & 3) ||
         (reinterpret_cast<uintptr_t>(d_query) & 3) || (reinterpret_cast<uintptr_t>(d_train) & 3))
         return RUMI_E_INVALID;                                 // the kernel packs the train index into 16 bits next to the distance
-    hipLaunchKernelGGL(k_bruteforce, dim3((cap + 255) / 256, nbatch), dim3(256), 0, (hipStream_t)hip_stream, (const uint8_t *)d_query,
-                       (const int32_t *)d_nq, (const uint8_t *)d_train, (const int32_t *)d_nt, count_stride, (long long)query_stride, (long long)train_stride, cap,
-                       (int32_t *)d_best_idx, (int32_t *)d_best_dist, (int32_t *)d_second_dist, 0);
-    HIP_TRY(hipGetLastError());
-    return RUMI_OK;
+    return launch_bruteforce(d_query, d_nq, d_train, d_nt, count_stride, (long long)query_stride, (long long)train_stride, cap, nbatch, d_best_idx, d_best_dist,
+                             d_second_dist, 0, (hipStream_t)hip_stream);
 }
 
 extern "C" int rumi_match_bruteforce_ring_device(const void *d_desc, const void *d_n, int32_t count_stride, int64_t frame_stride, int32_t cap, int32_t nframes,
@@ -2011,11 +2145,8 @@ extern "C" int rumi_match_bruteforce_ring_device(const void *d_desc, const void 
     if (!d_desc || !d_n || !d_best_idx || !d_best_dist || !d_second_dist || cap < 1 || cap > 65535 || nframes < 1 || count_stride < 1 ||
         frame_stride < 32ll * cap || (frame_stride & 3) || (reinterpret_cast<uintptr_t>(d_desc) & 3))
         return RUMI_E_INVALID;
-    hipLaunchKernelGGL(k_bruteforce, dim3((cap + 255) / 256, nframes), dim3(256), 0, (hipStream_t)hip_stream, (const uint8_t *)d_desc, (const int32_t *)d_n,
-                       (const uint8_t *)d_desc, (const int32_t *)d_n, count_stride, (long long)frame_stride, (long long)frame_stride, cap, (int32_t *)d_best_idx,
-                       (int32_t *)d_best_dist, (int32_t *)d_second_dist, nframes);
-    HIP_TRY(hipGetLastError());
-    return RUMI_OK;
+    return launch_bruteforce(d_desc, d_n, d_desc, d_n, count_stride, (long long)frame_stride, (long long)frame_stride, cap, nframes, d_best_idx, d_best_dist,
+                             d_second_dist, nframes, (hipStream_t)hip_stream);
 }
 
 extern "C" int rumi_match_bruteforce_batch_device(const void *d_query, const void *d_nq, const void *d_train, const void *d_nt,
