@@ -32,8 +32,9 @@ inline int cv_round_host(double v) { return (int)std::lrint(v); }
 #endif
 RUMI_GEOM_HD unsigned magic_of(unsigned d) { return (1u << 20) / d + 1u; }
 RUMI_GEOM_HD int magic_div(int idx, unsigned M) { return (int)(((unsigned)idx * M) >> 20); }
-// plain 32-bit products: v_mul_lo_u32 issues at full rate on gfx950 (profiles/r01_valu_issue_rates.txt), and the 24-bit intrinsics cost an
-// extra mask per operand where the compiler cannot prove the range (measured: +0.8 % instructions in k_fast_cells)
+// plain 32-bit products: v_mul_lo_u32 issues at the rate of v_mul_u32_u24 on gfx950 (both ~4.2 cycles per wave64 instruction, the slow class:
+// profiles/r02_valu_issue_rates.txt, r06_valu_issue_rates_bytes.txt), and the 24-bit intrinsics cost an extra mask per operand where the
+// compiler cannot prove the range (measured: +0.8 % instructions in k_fast_cells)
 RUMI_GEOM_HD int mul24(int a, int b) { return a * b; }
 
 struct LevelGeom {

@@ -364,7 +364,8 @@ __device__ __forceinline__ void wave_lds_fence() {
 // The four families (pair x polarity) use b = 12..15, one v_bfi_b32 each merges them into ONE word per circle position, and the
 // "4 consecutive" rule (23 ANDs / ORs) runs once for all eight (pixel, polarity) combinations of the lane instead of four times.
 // Ring entries = tile offset of the pixel | polarity << 15; a pixel's darker entry always precedes its brighter one.
-constexpr int kRingCap = 640;        // linear: < 128 entries wait between steps, a step appends up to 512 (64 lanes x 4 pixels x 2 polarities)
+constexpr int kRingCap = 640;        // linear: < 128 entries wait between steps, a step appends up to 512 (64 lanes x 4 pixels x 2 polarities;
+                                     // the byte formulation below appends its up-to-1024 in two halves when they do not fit)
 constexpr int kScoredCap = 640;
 // (ring pixels q in [0, 255] travel as 0x4100 + q: positive normal f16 bit patterns of one exponent, ordered like the integers)
 
@@ -596,6 +597,151 @@ __device__ __forceinline__ int fast_score_cell(const uint8_t *tile, uint8_t *sc,
     return nScored;
 }
 
+// ---- quick test, fourth formulation (round 6): bytes, eight pixels a lane ---------------------------------------------------------
+// The same necessary condition as above (4 consecutive of the 8 even circle positions reach contrast T), computed on the pixel bytes as
+// they lie in LDS, four pixels per dword, two adjacent dwords (eight pixels) per lane.
+//   Circle dwords: the ring bytes of a 4-pixel group at (0, +-3) are the aligned dword of that row; the others are ONE v_alignbyte_b32 of
+//   two loaded dwords, and the two groups of a lane share the middle one of rows +-2 (10 alignbytes for 16 circle dwords).
+//   Compares: v_lerp_u8 computes (a + b + r) >> 1 per byte, so bit 7 of lerp(p, ~x, 0) is [p > x] and bit 7 of lerp(p, ~y, 1) is [p >= y]:
+//   four compares per instruction.  With x = sat(v + T) and y = sat(v - T) they are cv::FAST's strict tests: brighter = p > x, darker =
+//   NOT [p >= y] (saturation is exact: v + T > 255 admits no brighter pixel, v - T < 0 no darker one).  ~x and ~y come once per group
+//   from packed saturating 16-bit arithmetic on the centre bytes held in the HIGH byte of each half (the low byte never carries into it).
+//   Rule: per dword and polarity the "4 consecutive of 8" network of ten two- / three-input operations on the raw lerp words (only
+//   bit 7 of each byte is read); the not-darker words take its De Morgan dual.  Four networks cost less than merging the flag words first
+//   (a shift and a bit-field insert per word and position).
+//   Ring append: the four bit-7 words become ONE 16-bit mask in ring order (bit 2 i darker, 2 i + 1 brighter, pixel i = 0..7) by a mask
+//   and a multiplication per dword; a lane then writes its set bits lowest first.
+// Ring contract unchanged: entries in pixel order, darker before brighter within a pixel.
+__device__ __forceinline__ uint32_t pk_add_sat_u16(uint32_t a, uint32_t b) {
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_add_sat(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));      // v_pk_add_u16 clamp
+}
+__device__ __forceinline__ uint32_t pk_sub_sat_u16(uint32_t a, uint32_t b) {
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));      // v_pk_sub_u16 clamp
+}
+// per byte of the centre dword c: nb = ~sat(v + T), nd = ~sat(v - T) = sat(~v + T).  TT = T << 8 in both halves.
+__device__ __forceinline__ void fast_bytes_thresholds(uint32_t c, uint32_t TT, uint32_t &nb, uint32_t &nd) {
+    const uint32_t n = ~c, ne = n << 8;       // bytes 1, 3 (odd pixels) high in the halves of n, bytes 0, 2 (even pixels) in those of ne
+    nb = __builtin_amdgcn_perm(pk_sub_sat_u16(n, TT), pk_sub_sat_u16(ne, TT), 0x07030501u);
+    nd = __builtin_amdgcn_perm(pk_add_sat_u16(n, TT), pk_add_sat_u16(ne, TT), 0x07030501u);
+}
+// 4 consecutive of the 8 words set (circular), every bit on its own: the runs starting at even positions are p0 p2 | p2 p4 | p4 p6 | p6 p0
+// = (p0 | p4) & (p2 | p6) with p_k = f_k & f_k+1, the odd ones likewise -- ten operations instead of 16 (compiled to v_bitop3_b32, v_and_b32, v_or_b32 and a few v_and_or_b32)
+__device__ __forceinline__ uint32_t four_of_eight(const uint32_t (&f)[8]) {
+    const uint32_t te = (f[0] & f[1]) | (f[4] & f[5]), ue = (f[2] & f[3]) | (f[6] & f[7]);
+    const uint32_t to = (f[1] & f[2]) | (f[5] & f[6]), uo = (f[3] & f[4]) | (f[7] & f[0]);
+    return (te & ue) | (to & uo);
+}
+// the same rule for the complements: returns ~four_of_eight(~g)
+__device__ __forceinline__ uint32_t four_of_eight_dual(const uint32_t (&g)[8]) {
+    const uint32_t te = (g[0] | g[1]) & (g[4] | g[5]), ue = (g[2] | g[3]) & (g[6] | g[7]);
+    const uint32_t to = (g[1] | g[2]) & (g[5] | g[6]), uo = (g[3] | g[4]) & (g[7] | g[0]);
+    return (te | ue) & (to | uo);
+}
+// ring-order mask of one dword's four pixels in bits 24-31 (bit 24 + 2 q darker, 25 + 2 q brighter for byte q): brighter in bit 7 of
+// each byte of y, NOT darker in bit 7 of each byte of z.  The two flags of byte q sit at bits 8 q + 6, 7; the multiplier 2^18 + 2^12 +
+// 2^6 + 1 moves them to 24 + 2 q (every other product lands below bit 24 or above bit 31, and no two products overlap: no carries).
+__device__ __forceinline__ uint32_t fast_bytes_ringmask(uint32_t y, uint32_t z) {
+    const uint32_t f = ((y & 0x80808080u) | (~(z >> 1) & 0x40404040u));
+    return f * 0x41041u;
+}
+
+template <int CTP>
+__device__ __forceinline__ int fast_score_cell_bytes(const uint8_t *tile, uint8_t *sc, uint16_t *cl, uint16_t *sl, int tp, int dw, int dh, int tlow, int lane) {
+    const int TP = CTP ? CTP : tp;
+    const int ng = (dw + 7) >> 3;                         // 8-pixel items per row; the first starts at tile column 4
+    const int nItems = ng * dh;
+    const unsigned Mng = magic_of(ng);
+    const int scDelta = -2 * TP - 3;
+    const uint32_t mLast = 0xFFFFu >> (2 * (8 * ng - dw));   // ring mask of a row's last item: pixels from column dw on lie outside the region
+    const uint32_t TT = (uint32_t)tlow * 0x01000100u;
+    uint32_t *cl32 = reinterpret_cast<uint32_t *>(cl);
+    int pending = 0, nScored = 0;
+    // full batches of 128 leave the front of the ring; the entries still waiting move to the front (fewer than 128, from beyond them)
+    auto drain = [&]() {
+        int head = 0;
+        while (pending >= 128) {
+            wave_lds_fence();
+            fast_score_batch<CTP>(tile, sc, sl, nScored, cl + head, 128, tp, scDelta, tlow, lane);
+            head += 128;
+            pending -= 128;
+        }
+        if (head) {
+            wave_lds_fence();
+            const uint32_t q = cl32[(head >> 1) + lane];
+            wave_lds_fence();
+            if (2 * lane < pending) cl32[lane] = q;
+        }
+    };
+    for (int base = 0; base < nItems; base += 64) {
+        const int ip = base + lane;
+        const bool live = ip < nItems;
+        const int row = live ? magic_div(ip, Mng) : 0, gi = live ? ip - mul24(row, ng) : 0;
+        const int A = mul24(row + 3, TP) + 8 * gi + 4;                        // tile offset of the item's first pixel (a dword)
+        const uint8_t *t = tile + A;
+#define RUMI_DW(off) (*reinterpret_cast<const uint32_t *>(t + (off)))
+        // every read is an aligned dword inside the tile: columns 0 .. 8 ng + 7 of rows row .. row + 6 (a read past the row's last dword
+        // lands at the start of the next row, inside the tile; such bytes only reach pixels outside the region, which the mask drops)
+        const uint32_t M3a = RUMI_DW(-3 * TP), M3b = RUMI_DW(-3 * TP + 4), P3a = RUMI_DW(3 * TP), P3b = RUMI_DW(3 * TP + 4);
+        const uint32_t M2l = RUMI_DW(-2 * TP - 4), M2a = RUMI_DW(-2 * TP), M2b = RUMI_DW(-2 * TP + 4), M2r = RUMI_DW(-2 * TP + 8);
+        const uint32_t P2l = RUMI_DW(2 * TP - 4), P2a = RUMI_DW(2 * TP), P2b = RUMI_DW(2 * TP + 4), P2r = RUMI_DW(2 * TP + 8);
+        const uint32_t Cl = RUMI_DW(-4), Ca = RUMI_DW(0), Cb = RUMI_DW(4), Cr = RUMI_DW(8);
+#undef RUMI_DW
+        // rows -2 / +2 at column offsets -2, +2, +6 of the item
+        const uint32_t m0 = __builtin_amdgcn_alignbyte(M2a, M2l, 2), m1 = __builtin_amdgcn_alignbyte(M2b, M2a, 2), m2 = __builtin_amdgcn_alignbyte(M2r, M2b, 2);
+        const uint32_t p0 = __builtin_amdgcn_alignbyte(P2a, P2l, 2), p1 = __builtin_amdgcn_alignbyte(P2b, P2a, 2), p2 = __builtin_amdgcn_alignbyte(P2r, P2b, 2);
+        // even circle positions in circular order (0,+3) (+2,+2) (+3,0) (+2,-2) (0,-3) (-2,-2) (-3,0) (-2,+2), dword a then dword b
+        const uint32_t ra[8] = {P3a, p1, __builtin_amdgcn_alignbyte(Cb, Ca, 3), m1, M3a, m0, __builtin_amdgcn_alignbyte(Ca, Cl, 1), p0};
+        const uint32_t rb[8] = {P3b, p2, __builtin_amdgcn_alignbyte(Cr, Cb, 3), m2, M3b, m1, __builtin_amdgcn_alignbyte(Cb, Ca, 1), p1};
+        uint32_t nba, nda, nbb, ndb;
+        fast_bytes_thresholds(Ca, TT, nba, nda);
+        fast_bytes_thresholds(Cb, TT, nbb, ndb);
+        uint32_t ba[8], ga[8], bb[8], gb[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            ba[k] = __builtin_amdgcn_lerp(ra[k], nba, 0u);              // bit 7: brighter
+            ga[k] = __builtin_amdgcn_lerp(ra[k], nda, 0x01010101u);     // bit 7: NOT darker
+            bb[k] = __builtin_amdgcn_lerp(rb[k], nbb, 0u);
+            gb[k] = __builtin_amdgcn_lerp(rb[k], ndb, 0x01010101u);
+        }
+        // ring mask: bits 0-7 pixels 0-3 (dword a), bits 8-15 pixels 4-7 (dword b)
+        uint32_t m = __builtin_amdgcn_perm(fast_bytes_ringmask(four_of_eight(bb), four_of_eight_dual(gb)),
+                                           fast_bytes_ringmask(four_of_eight(ba), four_of_eight_dual(ga)), 0x0c0c0703u);
+        if (gi == ng - 1) m &= mLast;
+        if (!live) m = 0;
+        if (__ballot(m != 0) != 0) {
+            // ring positions: entries of lower lanes first; within a lane lowest bit first (pixel by pixel, darker before brighter)
+            const int cnt = __popc(m);
+            const int incl = wave_incl_scan(cnt);
+            const int total = __builtin_amdgcn_readlane(incl, 63);
+            auto append = [&](uint16_t *w) {
+                for (uint32_t r = m; r; r &= r - 1) {
+                    const uint32_t b = __builtin_ctz(r);
+                    *w++ = (uint16_t)(((uint32_t)A + (b >> 1)) | ((b & 1u) << 15));
+                }
+            };
+            // (pending is wave-uniform; readfirstlane keeps it, and the branches on it, on the scalar unit)
+            if (pending + total <= kRingCap) {
+                append(cl + pending + incl - cnt);
+                pending = __builtin_amdgcn_readfirstlane(pending + total);
+                drain();
+            } else {                                       // a step appends up to 1024 entries: then lanes 0-31 first, 32-63 after (at most 512 each)
+                const int half = __builtin_amdgcn_readlane(incl, 31);
+                if (lane < 32) append(cl + pending + incl - cnt);
+                pending = __builtin_amdgcn_readfirstlane(pending + half);
+                drain();
+                if (lane >= 32) append(cl + pending + incl - half - cnt);
+                pending = __builtin_amdgcn_readfirstlane(pending + total - half);
+                drain();
+            }
+        }
+    }
+    wave_lds_fence();
+    if (pending) fast_score_batch<CTP>(tile, sc, sl, nScored, cl, pending, tp, scDelta, tlow, lane);
+    return nScored;
+}
+
 // One cell's place in its frame.
 struct FastCell {
     const uint8_t *img;              // first staged byte: row iniY, column iniX - 1 (any alignment)
@@ -659,8 +805,9 @@ __device__ __forceinline__ void fast_cell_stage(const FastCell &g, uint8_t *tile
     }
 }
 
-// everything after the staging of one cell: score map, NMS, ordered emission
-template <int TPC>
+// everything after the staging of one cell: score map, NMS, ordered emission.  LEGACY: the round-3 quick test (fast_score_cell) instead of
+// the byte formulation (fast_score_cell_bytes); both fill the ring with the same entries in the same order
+template <int TPC, bool LEGACY>
 __device__ __forceinline__ void fast_cell_process(const DevParams *__restrict__ P, const FastLds &F, const FastCell &g, uint8_t *tile, uint8_t *sc,
                                                   uint32_t *__restrict__ cellBuf, int32_t *__restrict__ cellCnt, int lane) {
     const int TP = TPC ? TPC : F.tp;
@@ -681,7 +828,8 @@ __device__ __forceinline__ void fast_cell_process(const DevParams *__restrict__ 
     int found;
 #pragma nounroll
     for (int pass = 0;; pass++) {
-        const int nScored = fast_score_cell<TPC>(tile, sc, cl, sl, TP, dw, dh, thr, lane);
+        const int nScored = LEGACY ? fast_score_cell<TPC>(tile, sc, cl, sl, TP, dw, dh, thr, lane)
+                                   : fast_score_cell_bytes<TPC>(tile, sc, cl, sl, TP, dw, dh, thr, lane);
         wave_lds_fence();
         // NMS + emission in one sweep over the scored list (ascending pixel order = the row-major order cv::FAST emits in; every pixel at
         // most once); a cell with more than kScoredCap scored pixels scans its whole score map instead.  Two items per lane and sweep, all
@@ -736,7 +884,7 @@ __device__ __forceinline__ void fast_cell_process(const DevParams *__restrict__ 
 // TPC: tile pitch (= score-map pitch) as a compile-time constant: the circle offsets and the NMS neighbours then are immediate LDS
 // offsets instead of one address add each; 0 = run-time
 // (bx, gx): the workgroup's column and the columns of the FAST part of the launch (the whole grid, or its first gx columns in the fused launch)
-template <int TPC>
+template <int TPC, bool LEGACY>
 __device__ __forceinline__ void fast_cells_body(const DevParams *__restrict__ P, const ImgSrc &src, const FastLds &F, uint32_t *__restrict__ cellBuf,
                                                 int32_t *__restrict__ cellCnt, unsigned bx, unsigned gx) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fl[];
@@ -751,12 +899,12 @@ __device__ __forceinline__ void fast_cells_body(const DevParams *__restrict__ P,
     const FastCell gA = fast_cell_geom(P, src, cell, frame, cellCnt, lane);
     if (!gA.live) return;
     fast_cell_stage<TPC>(gA, tile, TP, lane);
-    fast_cell_process<TPC>(P, F, gA, tile, sc, cellBuf, cellCnt, lane);
+    fast_cell_process<TPC, LEGACY>(P, F, gA, tile, sc, cellBuf, cellCnt, lane);
 }
-template <int TPC>
+template <int TPC, bool LEGACY>
 __global__ __launch_bounds__(256) void k_fast_cells(const DevParams *__restrict__ P, ImgSrc src, FastLds F,
                                                     uint32_t *__restrict__ cellBuf, int32_t *__restrict__ cellCnt) {
-    fast_cells_body<TPC>(P, src, F, cellBuf, cellCnt, blockIdx.x, gridDim.x);
+    fast_cells_body<TPC, LEGACY>(P, src, F, cellBuf, cellCnt, blockIdx.x, gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -988,10 +1136,10 @@ __global__ __launch_bounds__(256) void k_blur(const DevParams *__restrict__ P, I
 // A few frames (the Tracking thread's call): FAST and the blur in ONE launch, the first gxFast workgroup columns FAST cells, the rest blur strips.
 // Both only read the pyramid; as two launches the blur goes to a side stream, and the event that forks it stalls the main queue for ~20 us on
 // this runtime (and the join for ~5): more than the blur takes.
-template <int TPC, int VARIANT>
+template <int TPC, int VARIANT, bool LEGACY>
 __global__ __launch_bounds__(256) void k_fast_blur(const DevParams *__restrict__ P, ImgSrc src, FastLds F, uint32_t *__restrict__ cellBuf,
                                                    int32_t *__restrict__ cellCnt, BlurGrid G, unsigned gxFast) {
-    if (blockIdx.x < gxFast) fast_cells_body<TPC>(P, src, F, cellBuf, cellCnt, blockIdx.x, gxFast);
+    if (blockIdx.x < gxFast) fast_cells_body<TPC, LEGACY>(P, src, F, cellBuf, cellCnt, blockIdx.x, gxFast);
     else blur_body<VARIANT, kBlurRowsSmall>(P, src, G, blockIdx.x - gxFast, gridDim.x - gxFast);
 }
 
@@ -1316,18 +1464,30 @@ static FastLds fast_lds_of(const DevParams &hP) {
     F.perWave = (F.tileBytes + F.scBytes + std::max(kRingCap * 2, F.maxIters * 8) + kScoredCap * 2 + 15) & ~15;
     return F;
 }
+// RUMI_FAST_LEGACY=1: the round-3 quick test in place of the byte formulation (A/B measurements and tests in one build; same results)
+static bool fast_legacy() {
+    static const bool legacy = std::getenv("RUMI_FAST_LEGACY") && std::atoi(std::getenv("RUMI_FAST_LEGACY")) != 0;
+    return legacy;
+}
 void launch_fast(const DevParams *dP, const DevParams &hP, ImgSrc src, uint32_t *cellBuf, int32_t *cellCnt, int nframes,
                  hipStream_t st) {
     const FastLds F = fast_lds_of(hP);
+    const bool legacy = fast_legacy();
     // tile pitches of the common image sizes as compile-time constants (cells up to 36 / 40 / 44 / 48 pixels wide: 44 / 48 / 52 / 56);
     // anything else takes the run-time instantiation
     const int wpg = 4;                                    // cells (= waves) per workgroup
     const dim3 grid((hP.totalCells + wpg - 1) / wpg, nframes);
     const size_t lds = (size_t)wpg * F.perWave;
-#define RUMI_FAST_CASE(T) if (F.tp == T) { hipLaunchKernelGGL((k_fast_cells<T>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt); return; }
+#define RUMI_FAST_CASE(T)                                                                                                  \
+    if (F.tp == T) {                                                                                                       \
+        if (legacy) hipLaunchKernelGGL((k_fast_cells<T, true>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt);  \
+        else hipLaunchKernelGGL((k_fast_cells<T, false>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt);        \
+        return;                                                                                                            \
+    }
     RUMI_FAST_CASE(48) RUMI_FAST_CASE(44) RUMI_FAST_CASE(52) RUMI_FAST_CASE(56)
 #undef RUMI_FAST_CASE
-    hipLaunchKernelGGL((k_fast_cells<0>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt);
+    if (legacy) hipLaunchKernelGGL((k_fast_cells<0, true>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt);
+    else hipLaunchKernelGGL((k_fast_cells<0, false>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt);
 }
 // workgroups per frame (each repeats the cheap scan and copies its share of the outputs: the copy is a chain of dependent LDS reads per
 // element, so one workgroup per frame is ~40 us of latency whatever the batch)
@@ -1376,8 +1536,11 @@ bool launch_fast_blur(const DevParams *dP, const DevParams &hP, ImgSrc src, uint
     const unsigned gxFast = (unsigned)((hP.totalCells + wpg - 1) / wpg);
     const dim3 grid(gxFast + (unsigned)run, nframes);
     const size_t lds = (size_t)wpg * F.perWave;
-    if (variant) hipLaunchKernelGGL((k_fast_blur<48, 1>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
-    else hipLaunchKernelGGL((k_fast_blur<48, 0>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
+    const bool legacy = fast_legacy();
+    if (variant && legacy) hipLaunchKernelGGL((k_fast_blur<48, 1, true>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
+    else if (variant) hipLaunchKernelGGL((k_fast_blur<48, 1, false>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
+    else if (legacy) hipLaunchKernelGGL((k_fast_blur<48, 0, true>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
+    else hipLaunchKernelGGL((k_fast_blur<48, 0, false>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
     return true;
 }
 void launch_blur(const DevParams *dP, const DevParams &hP, ImgSrc src, int nframes, int variant, hipStream_t st) {

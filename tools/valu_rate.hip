@@ -18,6 +18,11 @@
     asm volatile(INS " %0, %0, %4, %5\n\t" INS " %1, %1, %4, %5\n\t" INS " %2, %2, %4, %5\n\t" INS " %3, %3, %4, %5" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(e), "v"(f));
 #define CHAIN4_1(INS) \
     asm volatile(INS " %0, %0\n\t" INS " %1, %1\n\t" INS " %2, %2\n\t" INS " %3, %3" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+// with a trailing modifier (clamp, bitop3:...)
+#define CHAIN4_2M(INS, MOD) \
+    asm volatile(INS " %0, %0, %4 " MOD "\n\t" INS " %1, %1, %4 " MOD "\n\t" INS " %2, %2, %4 " MOD "\n\t" INS " %3, %3, %4 " MOD : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(e));
+#define CHAIN4_3M(INS, MOD) \
+    asm volatile(INS " %0, %0, %4, %5 " MOD "\n\t" INS " %1, %1, %4, %5 " MOD "\n\t" INS " %2, %2, %4, %5 " MOD "\n\t" INS " %3, %3, %4, %5 " MOD : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(e), "v"(f));
 // 64-bit register pairs (packed f32)
 #define CHAIN4_P3(INS) \
     asm volatile(INS " %0, %0, %4, %5\n\t" INS " %1, %1, %4, %5\n\t" INS " %2, %2, %4, %5\n\t" INS " %3, %3, %4, %5" : "+v"(A), "+v"(B), "+v"(C), "+v"(D) : "v"(E), "v"(F));
@@ -33,7 +38,7 @@ enum Op {
     FMA_F32, PK_FMA_F32, ADD_F32, PK_ADD_F32, MIN3_F32, MAX3_F32, MINIMUM3_F32, SUB_F32, CVT_F32_UBYTE0, CVT_F32_UBYTE3, CVT_U32_F32,
     ADD_U32, AND_B32, XOR_B32, LSHL_OR_B32, ADD3_U32, MIN_I32, MIN3_I32, MAX3_I32, MAD_I32_I24, MAD_U32_U24, MUL_LO_U32,
     PK_MIN_I16, PK_MAX_I16, PK_SUB_I16, PK_ADD_U16, MIN3_I16, PK_MINIMUM3_F16, PK_MAXIMUM3_F16, PK_MIN_F16, PK_ADD_F16,
-    DOT4_U32_U8, BCNT, PERM, ALIGNBYTE, SAD_U8, CNDMASK, CMP_GT_I32, MBCNT,
+    DOT4_U32_U8, BCNT, PERM, ALIGNBYTE, SAD_U8, LERP_U8, PK_ADD_U16_CLAMP, PK_SUB_U16_CLAMP, BITOP3, CNDMASK, CMP_GT_I32, MBCNT,
     OR_B32, SUB_U32, LSHLREV, LSHRREV, ASHRREV, MOV_B32, NOT_B32, MUL_F32, MAX_F32, MIN_F32, MAX_U32, MIN_U32, MAX_I32, MIN_U16, SUB_U16, MUL_U32_U24, FMAC_F32,
     BFE_U32, AND_OR_B32, OR3_B32, LSHL_ADD_U32, XAD_U32, BFI_B32, MED3_I32, MAX3_U32, MUL_HI_U32, CVT_F32_I32, CNDMASK_S, CMP_GT_U32_S, CMP_GT_F32,
     SDWA_SUB_U32_BYTES, SDWA_ADD_U32_W1, SDWA_AND_BYTE, SDWA_MIN_U16_BYTES, SDWA_MAX_I32_WORDS, SDWA_SUB_F32, SDWA_CVT_UBYTE, SDWA_MOV_W1, SDWA_CMP_BYTES, DPP_MOV_SHR1, DPP_ADD_SHR1, DPP_MOV_BCAST, READLANE,
@@ -94,6 +99,10 @@ template <int OP> __global__ __launch_bounds__(256) void k(unsigned *out, unsign
             if (OP == PERM) CHAIN4_3("v_perm_b32")
             if (OP == ALIGNBYTE) CHAIN4_3("v_alignbyte_b32")
             if (OP == SAD_U8) CHAIN4_3("v_sad_u8")
+            if (OP == LERP_U8) CHAIN4_3("v_lerp_u8")
+            if (OP == PK_ADD_U16_CLAMP) CHAIN4_2M("v_pk_add_u16", "clamp")
+            if (OP == PK_SUB_U16_CLAMP) CHAIN4_2M("v_pk_sub_u16", "clamp")
+            if (OP == BITOP3) CHAIN4_3M("v_bitop3_b32", "bitop3:0xc8")
             if (OP == CNDMASK) asm volatile("v_cndmask_b32 %0, %0, %4, vcc\n\tv_cndmask_b32 %1, %1, %4, vcc\n\tv_cndmask_b32 %2, %2, %4, vcc\n\tv_cndmask_b32 %3, %3, %4, vcc" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(e) : "vcc");
             if (OP == CMP_GT_I32) asm volatile("v_cmp_gt_i32 vcc, %0, %4\n\tv_cmp_gt_i32 vcc, %1, %4\n\tv_cmp_gt_i32 vcc, %2, %4\n\tv_cmp_gt_i32 vcc, %3, %4" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "v"(e) : "vcc");
             if (OP == MBCNT) CHAIN4("v_mbcnt_lo_u32_b32")
@@ -197,6 +206,13 @@ int main(int argc, char **argv) {
         std::printf("# tools/valu_rate.hip f64 on %s: cycles per wave64 instruction and SIMD at 1 / 2 / 4 / 8 resident waves per SIMD (four independent chains per lane; 'dep' = one chain)\n", p.gcnArchName);
         run<FMA_F32>("v_fma_f32 (control)"); run<FMA_F64>("v_fma_f64"); run<MUL_F64>("v_mul_f64"); run<ADD_F64>("v_add_f64"); run<FMA_F64_DEP>("v_fma_f64 dep");
         run<RSQ_F64>("v_rsq_f64"); run<RCP_F64>("v_rcp_f64");
+        return 0;
+    }
+    if (argc > 1 && std::string(argv[1]) == "bytes") {                      // the classes of k_fast_cells' byte quick test (round 6), with controls
+        std::printf("# tools/valu_rate.hip bytes on %s: cycles per wave64 instruction and SIMD at 1 / 2 / 4 / 8 resident waves per SIMD\n", p.gcnArchName);
+        run<ADD_U32>("v_add_u32 (control)"); run<AND_B32>("v_and_b32 (control)"); run<ALIGNBYTE>("v_alignbyte_b32 (control)"); run<PERM>("v_perm_b32 (control)");
+        run<LERP_U8>("v_lerp_u8"); run<PK_ADD_U16_CLAMP>("v_pk_add_u16 clamp"); run<PK_SUB_U16_CLAMP>("v_pk_sub_u16 clamp"); run<BITOP3>("v_bitop3_b32");
+        run<AND_OR_B32>("v_and_or_b32"); run<MUL_LO_U32>("v_mul_lo_u32");
         return 0;
     }
     std::printf("# tools/valu_rate.hip on %s (%s), %d CUs, clockRate %d kHz\n", p.name, p.gcnArchName, p.multiProcessorCount, p.clockRate);
