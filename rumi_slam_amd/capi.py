@@ -103,6 +103,42 @@ TRACK_SYMBOLS = ["rumi_track_create", "rumi_track_destroy", "rumi_track_frame", 
                  "rumi_track_reference_keyframe", "rumi_track_local", "rumi_track_image_buffer", "rumi_track_last_projections", "rumi_track_set_distortion", "rumi_track_undistorted"]
 QUEUE_SYMBOLS = ["rumi_queue_create", "rumi_queue_destroy", "rumi_queue_shards", "rumi_queue_record_bytes", "rumi_queue_block_capacity", "rumi_queue_row",
                  "rumi_queue_uses_rccl", "rumi_queue_extract", "rumi_queue_last_ms"]
+KFDB_SYMBOLS = ["rumi_kfdb_create", "rumi_kfdb_destroy", "rumi_kfdb_clear", "rumi_kfdb_size", "rumi_kfdb_next_seq", "rumi_kfdb_max_batch", "rumi_kfdb_add",
+                "rumi_kfdb_add_batch_device", "rumi_kfdb_bow", "rumi_kfdb_erase", "rumi_kfdb_clear_map", "rumi_kfdb_set_map_bad", "rumi_kfdb_set_maps",
+                "rumi_kfdb_set_bad", "rumi_kfdb_set_covisibles", "rumi_kfdb_score", "rumi_kfdb_scored", "rumi_kfdb_select_reloc", "rumi_kfdb_select_nbest"]
+
+
+def kfdb_lib():
+    """The key-frame database entries (include/rumi_kfdb.h) with their argument types."""
+    L = lib()
+    if getattr(L, "_kfdb_ready", False):
+        return L
+    vp, i32, i64, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
+    L.rumi_kfdb_create.argtypes = [vp, i32, i64, i32, C.POINTER(vp)]
+    L.rumi_kfdb_destroy.argtypes = [vp]
+    L.rumi_kfdb_destroy.restype = None
+    L.rumi_kfdb_clear.argtypes = [vp]
+    L.rumi_kfdb_size.argtypes = [vp]
+    L.rumi_kfdb_next_seq.argtypes = [vp]
+    L.rumi_kfdb_next_seq.restype = i64
+    L.rumi_kfdb_max_batch.argtypes = [vp]
+    L.rumi_kfdb_add.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.rumi_kfdb_add_batch_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp]
+    L.rumi_kfdb_bow.argtypes = [vp, u64, vp, vp, i32, C.POINTER(i32)]
+    L.rumi_kfdb_erase.argtypes = [vp, i32, vp]
+    L.rumi_kfdb_clear_map.argtypes = [vp, i32]
+    L.rumi_kfdb_set_map_bad.argtypes = [vp, i32, i32]
+    L.rumi_kfdb_set_maps.argtypes = [vp, i32, vp, vp]
+    L.rumi_kfdb_set_bad.argtypes = [vp, i32, vp, vp]
+    L.rumi_kfdb_set_covisibles.argtypes = [vp, i32, vp, vp]
+    L.rumi_kfdb_score.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rumi_kfdb_scored.argtypes = [vp, vp, vp]
+    L.rumi_kfdb_select_reloc.argtypes = [vp, vp, vp, i64]
+    L.rumi_kfdb_select_nbest.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L._kfdb_ready = True
+    return L
+
+
 HOOK_SYMBOLS = ["rumi_hook_sort_like_std", "rumi_hook_sort_device", "rumi_hook_std_sort", "rumi_hook_quadtree", "rumi_hook_sinf", "rumi_hook_cosf",
                 "rumi_hook_fast_atan2", "rumi_hook_cv_round", "rumi_hook_magic_div"]
 

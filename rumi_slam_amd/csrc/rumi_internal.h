@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+typedef struct RumiVocabulary RumiVocabulary;
+
 namespace rumi {
 
 // Correspondences the LDS instantiation of k_pose_opt holds (opt.hip).  The tracker (match.hip) launches ONLY that instantiation when it knows a
@@ -15,5 +17,8 @@ constexpr int kPoseLdsEdges = 1152;
 // instantiation is then not launched).  Enqueues on `st`, does not synchronise.
 int pose_opt_device(const int32_t *dStart, const float *dXw, const float *dObs, const float *dW, const float *dK4, const float *dTin, float *dTout,
                     uint8_t *dOutlier, int32_t *dNGood, uint8_t *dActive, double *dLastChi2, bool fitsLds, hipStream_t st);
+
+// Device, word count and the header's weighting / scoring types of a vocabulary (voc.hip), for the key-frame database (kfdb.hip).
+void voc_params(const RumiVocabulary *v, int *device, int *nWords, int *weighting, int *scoring);
 
 }  // namespace rumi

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "rumi_common.h"
+#include "rumi_internal.h"
 #include "rumi_voc.h"
 
 namespace rumi {
@@ -135,6 +136,10 @@ extern "C" void rumi_voc_destroy(RumiVocabulary *v) {
     delete v;
 }
 extern "C" int32_t rumi_voc_words(const RumiVocabulary *v) { return v ? v->nWords : 0; }
+// (rumi_internal.h) what the key-frame database (kfdb.hip) needs to know about a vocabulary
+void rumi::voc_params(const RumiVocabulary *v, int *device, int *nWords, int *weighting, int *scoring) {
+    *device = v->device; *nWords = v->nWords; *weighting = v->weighting; *scoring = v->scoring;
+}
 extern "C" int32_t rumi_voc_levels(const RumiVocabulary *v) { return v ? v->L : 0; }
 
 template <class T> static int upload(T **d, const std::vector<T> &h) {
