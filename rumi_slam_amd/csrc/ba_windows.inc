@@ -75,7 +75,7 @@ __device__ __forceinline__ double baw_fixed_sum(const double *p, int cnt, double
     return v[0];
 }
 
-// The head of a slot: the state of the LM loop after the previous slot.  levenberg.cpp:102-166 as k_lm_decide had it.
+// The head of a slot: the state of the LM loop after the previous slot.  levenberg.cpp:102-166 as ba_run's host loop has it.
 __device__ __forceinline__ LmCtl baw_head(const BAWin &W, int slot, double *red) {
     if (slot == 0) { LmCtl c0{}; c0.cur = W.cur0; c0.ni = 2; c0.lambda = -1; return c0; }      // a run starts from the table alone: nothing to upload
     LmCtl c = W.lm[slot & 1];

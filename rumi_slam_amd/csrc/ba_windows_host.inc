@@ -17,13 +17,14 @@ struct BawPrep {                         // what staging a window leaves behind
     bool ran = false;
 };
 
-static bool baw_eligible(int32_t nKF, const uint8_t *kf_fixed, int32_t nMP, int32_t nE) {
-    if (nKF < 1 || nKF > 512 || nE < 1 || nMP < 1 || !kf_fixed) return false;
+// Whether a window runs on this path (ba_run and rumi_local_ba_batch both ask here): up to 29 optimised key-frames (the tile solver), at most 512
+// key-frames (k_baw_system / k_baw_updchi cache every pose in LDS), and not on a profiled handle.  Everything else takes ba_run's host loop.
+static bool baw_eligible(const RumiOptimizer *o, int32_t nKF, const uint8_t *kf_fixed, int32_t nMP, int32_t nE) {
+    if (o->profiling || nKF < 1 || nKF > 512 || nE < 1 || nMP < 1 || !kf_fixed) return false;
     int nOpt = 0;
     for (int k = 0; k < nKF; k++) nOpt += kf_fixed[k] ? 0 : 1;
     const int n = 6 * nOpt, NT = (n + 1 + 15) / 16;
-    static const bool forceLegacy = std::getenv("RUMI_BA_LEGACY") != nullptr;
-    return n > 0 && NT <= kSolveTilesMax && !forceLegacy;
+    return n > 0 && NT <= kSolveTilesMax;
 }
 
 static int baw_arena_extras(RumiOptimizer *c) {

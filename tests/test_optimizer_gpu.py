@@ -79,6 +79,81 @@ def test_local_bundle_adjustment(opt, cfg):
     assert np.count_nonzero(er != er_ref) == 0, "erase flags"
 
 
+def _check_local_ba(b, got, ref):
+    stats, kp, mp, er = got
+    its_ref, kp_ref, mp_ref, er_ref = ref
+    assert stats[0] == its_ref, "number of LM iterations"
+    for k in range(len(kp)):
+        _pose_close(kp[k], kp_ref[k], f"key-frame {k}")
+    assert np.array_equal(kp[b["kf_fixed"] == 1], b["kf_pose"][b["kf_fixed"] == 1]), "fixed key-frames must not move"
+    scale = np.maximum(np.linalg.norm(mp_ref, axis=1), 1e-2)
+    assert (np.linalg.norm(mp - mp_ref, axis=1) <= RTOL * scale).all(), "landmarks"
+    assert np.count_nonzero(er != er_ref) == 0, "erase flags"
+
+
+def test_local_ba_profiled_tile_window():
+    """A window the tile solver takes, on a handle with profiling on: the host LM loop of ba_run over k_ba_solve_tiles instead of the window-batched
+    path, with the same results as the oracle."""
+    from rumi_slam_amd.optimizer import Optimizer
+    b = ba_problem(seed=3, n_opt=12, n_fixed=1, n_points=1500, outlier_frac=0.15)
+    a = (b["kf_pose"], b["kf_fixed"], b["mp_pos"], b["e_mp"], b["e_kf"], b["e_obs"], b["e_w"], b["K"])
+    prof = Optimizer()
+    try:
+        prof.set_profiling(True)
+        got = prof.LocalBundleAdjustment(*a)
+        assert prof.kernel_ms()["trials"] == got[0][1] > 0           # the profiled (host) loop ran every trial
+        _check_local_ba(b, got, O.local_ba(*a))
+    finally:
+        prof.close()
+
+
+def _wide_window(n_extra=500, per_kf=4):
+    """A tile-sized window (20 optimised key-frames) with more than 512 key-frames in all: BASELINE-like 20 + 5, plus n_extra fixed key-frames that
+    copy the poses of the original fixed ones and repeat per_kf of their observations each (edges kept grouped by landmark)."""
+    b = ba_problem(seed=0, n_opt=20, n_fixed=5, n_points=1500)
+    rng = np.random.default_rng(99)
+    n0 = len(b["kf_fixed"])
+    fixed_src = np.flatnonzero(b["kf_fixed"])
+    sel = [rng.choice(np.flatnonzero(b["e_kf"] == fixed_src[j % len(fixed_src)]), per_kf, replace=False) for j in range(n_extra)]
+    src_e = np.concatenate(sel)
+    new_kf = np.repeat(np.arange(n0, n0 + n_extra, dtype=np.int32), per_kf)
+    e_mp = np.concatenate([b["e_mp"], b["e_mp"][src_e]])
+    order = np.argsort(e_mp, kind="stable")
+    w = dict(b)
+    w["kf_pose"] = np.concatenate([b["kf_pose"], b["kf_pose"][fixed_src[np.arange(n_extra) % len(fixed_src)]]])
+    w["kf_fixed"] = np.concatenate([b["kf_fixed"], np.ones(n_extra, np.uint8)])
+    w["e_mp"] = e_mp[order]
+    w["e_kf"] = np.concatenate([b["e_kf"], new_kf])[order]
+    w["e_obs"] = np.concatenate([b["e_obs"], b["e_obs"][src_e]])[order]
+    w["e_w"] = np.concatenate([b["e_w"], b["e_w"][src_e]])[order]
+    return w
+
+
+def test_local_ba_tile_window_of_more_than_512_keyframes():
+    """At most 29 optimised key-frames but more than 512 key-frames in all: too many poses for the LDS cache of the window-batched kernels, so the
+    window takes ba_run's host loop, alone and inside rumi_local_ba_batch beside a window the batched path takes."""
+    from rumi_slam_amd.optimizer import Optimizer
+    b = _wide_window()
+    assert len(b["kf_fixed"]) > 512 and np.count_nonzero(b["kf_fixed"] == 0) == 20
+    a = (b["kf_pose"], b["kf_fixed"], b["mp_pos"], b["e_mp"], b["e_kf"], b["e_obs"], b["e_w"], b["K"])
+    ref = O.local_ba(*a)
+    small = ba_problem(seed=41, n_opt=7, n_fixed=2, n_points=300)
+    s = (small["kf_pose"], small["kf_fixed"], small["mp_pos"], small["e_mp"], small["e_kf"], small["e_obs"], small["e_w"], small["K"])
+    wide = Optimizer(max_kf=544)
+    try:
+        got = wide.LocalBundleAdjustment(*a)
+        print(f"LBA of {len(b['kf_fixed'])} key-frames: C call {wide.last_call_s * 1e3:.2f} ms, iterations {got[0][0]}, trials {got[0][1]}")
+        assert got[0][2] == 20
+        _check_local_ba(b, got, ref)
+        single_small = wide.LocalBundleAdjustment(*s)
+        got_b, got_s = wide.LocalBundleAdjustmentBatch([a, s], 2)
+        _check_local_ba(b, got_b, ref)
+        for x, y in zip(got_s, single_small):
+            assert np.array_equal(x, y), "the batched window beside it must equal its single call"
+    finally:
+        wide.close()
+
+
 def test_local_ba_stop_flag_and_no_fixed(opt):
     from rumi_slam_amd import capi
     b = ba_problem(seed=5, n_opt=4, n_fixed=2, n_points=200)

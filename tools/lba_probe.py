@@ -1,5 +1,5 @@
-"""Local BA of BASELINE configs[3] (20 + 5 key-frames x 3000 points): wall / device ms and per-kernel event times per trial, for both solve kernels
-(RUMI_BA_SOLVE_PANEL8=1 selects the older one in a fresh process)."""
+"""Local BA of BASELINE configs[3] (20 + 5 key-frames x 3000 points): wall / device ms per call, then batches of windows through
+rumi_local_ba_batch."""
 import sys, os, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
@@ -25,5 +25,5 @@ for R, workers in ((16, 1), (32, 1), (4, 1)):
     dts, cpu = [], []
     for _ in range(5):
         c0, t0 = time.process_time(), time.perf_counter(); opt.LocalBundleAdjustmentBatch([w] * R, workers); dts.append(time.perf_counter() - t0); cpu.append(time.process_time() - c0)
-    print("batch of %d windows (20 + 5 key-frames x 3000 points), %d workers: %.3f ms per window (best of 5; median %.3f); host cores busy %.2f (process CPU time / wall time, LM loop %s)" % (
-        R, workers, min(dts) * 1e3 / R, float(np.median(dts)) * 1e3 / R, float(np.median(cpu)) / float(np.median(dts)), "on the HOST (RUMI_BA_HOST_LM)" if os.environ.get("RUMI_BA_HOST_LM") else "on the device"))
+    print("batch of %d windows (20 + 5 key-frames x 3000 points), %d workers: %.3f ms per window (best of 5; median %.3f); host cores busy %.2f (process CPU time / wall time)" % (
+        R, workers, min(dts) * 1e3 / R, float(np.median(dts)) * 1e3 / R, float(np.median(cpu)) / float(np.median(dts))))
