@@ -12,7 +12,7 @@
 //                    round k queries 0..k-1 hold their sequential result, and a fix point is the sequential result
 //                    (induction on the query index), so the outcome equals the reference's loop bit for bit.
 //                    Then the rotation histogram / ComputeThreeMaxima filter and the result arrays.
-//   k_bruteforce_mfma  all-pairs best / second-best as an int8 GEMM on the matrix cores (k_bruteforce: the VALU form, RUMI_BF_VALU=1).
+//   k_bruteforce_mfma  all-pairs best / second-best as an int8 GEMM on the matrix cores.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1077,75 +1077,12 @@ __global__ __launch_bounds__(256) void k_tri_filter(int nq, const uint32_t *idx1
     if (tid == 0) *nmatches = sCount;
 }
 
-// ---- brute force ----------------------------------------------------------------------------------------------------
-// grid (ceil(cap/256), B); 256 queries per workgroup in registers; train descriptors staged 256 at a time in LDS and
-// read as broadcasts (every lane reads the same address: conflict-free).
-// popcount(x) + acc in one instruction (the compiler re-associates a sum of popcounts into popcounts + 3-input adds)
-__device__ __forceinline__ uint32_t popc_acc(uint32_t x, uint32_t acc) {
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
-__device__ __forceinline__ uint32_t umed3(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t r;
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
-__global__ __launch_bounds__(256) void k_bruteforce(const uint8_t *__restrict__ qd, const int32_t *__restrict__ nqArr,
-                                                    const uint8_t *__restrict__ td, const int32_t *__restrict__ ntArr,
-                                                    int countStride, long long qStride, long long tStride, int cap, int32_t *__restrict__ bestIdx,
-                                                    int32_t *__restrict__ bestDist, int32_t *__restrict__ secondDist, int ring) {
-    __shared__ uint4 tile[256 * 2];
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const int tb = ring > 0 ? (b + 1 == ring ? 0 : b + 1) : b;       // ring: frame b against its successor in the same buffer, the last against the first
-    const int nq = min(nqArr[(size_t)b * countStride], cap), nt = min(ntArr[(size_t)tb * countStride], cap);
-    const int qi = blockIdx.x * 256 + tid;
-    if (blockIdx.x * 256 >= nq) return;
-    uint32_t q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (qi < nq) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(qd + (size_t)b * qStride + (size_t)qi * 32);
-        const uint4 a = src[0], c = src[1];
-        q[0] = a.x; q[1] = a.y; q[2] = a.z; q[3] = a.w; q[4] = c.x; q[5] = c.y; q[6] = c.z; q[7] = c.w;
-    }
-    // best and second best as packed keys (distance << 16 | train index): "first minimum wins, a tie goes to the second place" is then
-    // best = min(best, key), second = med3(best, second, key) — three instructions per pair next to the 8 xor + 8 popcount-accumulate
-    uint32_t best = 256u << 16, second = (256u << 16) | 0xFFFFu;
-    for (int t0 = 0; t0 < nt; t0 += 256) {
-        const int m = min(256, nt - t0);
-        __syncthreads();
-        if (tid < m) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(td + (size_t)tb * tStride + (size_t)(t0 + tid) * 32);
-            tile[tid * 2] = src[0];
-            tile[tid * 2 + 1] = src[1];
-        }
-        __syncthreads();
-        auto step = [&](int j) {
-            const uint4 a = tile[j * 2], c = tile[j * 2 + 1];
-            uint32_t d = popc_acc(q[0] ^ a.x, 0u);
-            d = popc_acc(q[1] ^ a.y, d); d = popc_acc(q[2] ^ a.z, d); d = popc_acc(q[3] ^ a.w, d);
-            d = popc_acc(q[4] ^ c.x, d); d = popc_acc(q[5] ^ c.y, d); d = popc_acc(q[6] ^ c.z, d); d = popc_acc(q[7] ^ c.w, d);
-            const uint32_t key = (d << 16) | (uint32_t)(t0 + j);
-            second = umed3(best, second, key);
-            best = min(best, key);
-        };
-        int j = 0;
-        for (; j + 4 <= m; j += 4) { step(j); step(j + 1); step(j + 2); step(j + 3); }   // four independent popcount chains in flight
-        for (; j < m; j++) step(j);
-    }
-    if (qi < nq) {
-        const size_t o = (size_t)b * cap + qi;
-        const int b1 = (int)(best >> 16);
-        bestIdx[o] = b1 < 256 ? (int)(best & 0xFFFFu) : -1;     // a distance of 256 never beats the initial 256 (the reference's strict <)
-        bestDist[o] = b1; secondDist[o] = (int)(second >> 16);
-    }
-}
-
 // ---- brute force on the int8 matrix cores ----------------------------------------------------------------------------
 // With train bits t and query bits q (popcount pq): Ham(t, q) = pq + X, X = sum_k t_k (1 - 2 q_k), an exact int8 GEMM of
 // trains (A, 0/1 bytes) by queries (B, +1/-1 bytes) over K = 256 on v_mfma_i32_32x32x32_i8 (8 per 32 x 32 tile).  For one
 // query pq is a constant, so the running (best, second) are kept on X as SIGNED keys (X << 16 | train index) and pq is
-// added once at the end; min_i32 / med3_i32 then order them exactly as the VALU kernel orders (Ham << 16 | index).
+// added once at the end; min_i32 / med3_i32 then order them exactly as keys (Ham << 16 | index) would: "first minimum wins, a tie
+// goes to the second place" is best = min(best, key), second = med3(best, second, key).
 //
 // Fragment maps.  C/D of 32x32: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 h, h = lane >> 5.  A and B: lane l
 // holds row (A) / column (B) l & 31 and 16 k-values that depend only on (h, byte); the Hamming sum does not depend on the order
@@ -1177,7 +1114,7 @@ __global__ __launch_bounds__(512) void k_bruteforce_mfma(const uint8_t *__restri
     __shared__ bfm_v4i frag[2][2 * 8 * 64];                           // [buffer][tile * 8 + s][lane]
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tb = ring > 0 ? (b + 1 == ring ? 0 : b + 1) : b;
+    const int tb = ring > 0 ? (b + 1 == ring ? 0 : b + 1) : b;       // ring: frame b against its successor in the same buffer, the last against the first
     const int nq = min(nqArr[(size_t)b * countStride], cap), nt = min(ntArr[(size_t)tb * countStride], cap);
     const int q0 = blockIdx.x * kBfmQueries;
     if (q0 >= nq) return;
@@ -1263,17 +1200,11 @@ __global__ __launch_bounds__(512) void k_bruteforce_mfma(const uint8_t *__restri
     }
 }
 
-// RUMI_BF_VALU=1: the VALU kernel above in place of the matrix-core one (A/B measurements and tests in one build)
 static int launch_bruteforce(const void *qd, const void *nq, const void *td, const void *nt, int count_stride, long long q_stride, long long t_stride,
                              int cap, int nrows, void *best_idx, void *best_dist, void *second_dist, int ring, hipStream_t st) {
-    static const bool valu = std::getenv("RUMI_BF_VALU") && std::atoi(std::getenv("RUMI_BF_VALU")) != 0;
     const dim3 grid((cap + 255) / 256, nrows);
-    if (valu)
-        hipLaunchKernelGGL(k_bruteforce, grid, dim3(256), 0, st, (const uint8_t *)qd, (const int32_t *)nq, (const uint8_t *)td, (const int32_t *)nt, count_stride,
-                           q_stride, t_stride, cap, (int32_t *)best_idx, (int32_t *)best_dist, (int32_t *)second_dist, ring);
-    else
-        hipLaunchKernelGGL(k_bruteforce_mfma, grid, dim3(64 * kBfmWaves), 0, st, (const uint8_t *)qd, (const int32_t *)nq, (const uint8_t *)td, (const int32_t *)nt,
-                           count_stride, q_stride, t_stride, cap, (int32_t *)best_idx, (int32_t *)best_dist, (int32_t *)second_dist, ring);
+    hipLaunchKernelGGL(k_bruteforce_mfma, grid, dim3(64 * kBfmWaves), 0, st, (const uint8_t *)qd, (const int32_t *)nq, (const uint8_t *)td, (const int32_t *)nt,
+                       count_stride, q_stride, t_stride, cap, (int32_t *)best_idx, (int32_t *)best_dist, (int32_t *)second_dist, ring);
     HIP_TRY(hipGetLastError());
     return RUMI_OK;
 }

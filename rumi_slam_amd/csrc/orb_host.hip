@@ -38,6 +38,9 @@ extern "C" int rumi_device_count(void) {
 
 namespace {
 constexpr int kChunk = 256;  // frames per pass through the candidate / quadtree scratch arenas
+// Frames per sub-chunk of the resident queue.  256 since the end of round 3 (64 before): with the latency-bound kernels of a sub-chunk's chain
+// shortened (compaction, quadtree) larger launches win at every call size (1024-frame steps +3 %, 128-frame calls +5 %).
+constexpr int kResidentSub = 256;
 static int scratch_frames(int maxBatch) { return (std::min(kChunk, maxBatch) + 11) / 12 * 12; }
 
 template <class T> int dev_alloc(T **p, size_t n) {
@@ -66,7 +69,7 @@ struct RumiOrb {
     DevParams *dP = nullptr;
     int16_t *dCoef = nullptr;
     RowTap *dRowTab = nullptr; int capRowTab = 0;   // per level and output row: source rows and vertical taps of the resize
-    PyrTile *dPyrTiles[2] = {nullptr, nullptr}; int nPyrTiles[2] = {0, 0}, pyrBuf[2] = {0, 0}, pyrTab[2] = {0, 0};   // the one-launch pyramid (k_pyramid_tiles), [0] small tiles for calls of a few frames, [1] large tiles for batches: 0 tiles = not available for this geometry
+    PyrTile *dPyrTiles = nullptr; int nPyrTiles = 0, pyrBuf = 0, pyrTab = 0;   // the one-launch pyramid (k_pyramid_tiles) of calls of a few frames: 0 tiles = not available for this geometry
     // HBM arenas (sized for max_batch frames unless noted)
     uint8_t *dIn = nullptr;          // staging for the single-frame host API (1 frame, rows padded to a multiple of 4 bytes)
     uint8_t *dL0 = nullptr;          // staging for device frames whose base / pitch / frame stride is not 4-byte aligned (allocated on first use)
@@ -75,9 +78,8 @@ struct RumiOrb {
     uint8_t *dhOut1 = nullptr;        // the pinned block as the device addresses it: a one-frame call's kernels write counts, key-points and descriptors
     int32_t *dhErr = nullptr;         // straight into host memory (and k_assemble the final error word): no copy back, the call ends with its last kernel
     bool zeroCopyOut = false;         // set by rumi_orb_extract around its call
-    uint8_t *dhIn = nullptr;          // the pinned image as the device addresses it
-    bool hostImagePending = false;    // rumi_orb_extract: the frame of this call still sits in hIn (w x hgt, pitch wp): extract_async_impl either lets the
-                                      // one-launch pyramid read it over PCIe (and keep a copy as the arena's level 0) or copies it to dIn first
+    bool hostImagePending = false;    // rumi_orb_extract: the frame of this call still sits in hIn (w x hgt, pitch wp): extract_async_impl copies it to dIn
+                                      // on the call's stream
     uint8_t *dPyr = nullptr, *dBlur = nullptr;
     uint32_t *dCellBuf = nullptr;    // kChunk frames
     int32_t *dCellCnt = nullptr;
@@ -85,9 +87,6 @@ struct RumiOrb {
     int32_t *dLevelStart = nullptr;
     uint32_t *dSelPacked = nullptr, *dSelMeta = nullptr;   // kChunk frames x capSel
     int32_t *dSelCount = nullptr;
-    RumiKeyPoint *dKp = nullptr;     // outputs of the single-frame host API
-    uint8_t *dDesc = nullptr;
-    int32_t *dCounts = nullptr;
     uint16_t *dOwner = nullptr;      // kChunk frames x capCand: quadtree node id of every candidate
     uint32_t *dSelLevel = nullptr;   // kChunk frames x nlevels x selLevelCap: quadtree output per level
     int32_t *dSelLevelCnt = nullptr;
@@ -120,15 +119,19 @@ struct RumiOrb {
     int lastOutCap = 0;
     bool profiling = false;
     float stageMs[8] = {0};
-    // host entries with PINNED host destinations: every sub-chunk's output rows [frame0, frame0 + n) follow its kernels to the host on the sub-chunk's own
-    // stream, under the kernels of the sub-chunks behind it (one entry for the record layout, three for key-points / descriptors / counts)
-    struct Mirror { uint8_t *host; const uint8_t *dev; long long row; } mirror[3] = {{nullptr, nullptr, 0}, {nullptr, nullptr, 0}, {nullptr, nullptr, 0}};
+    // the record entry with a PINNED host destination: every sub-chunk's records [frame0, frame0 + n) follow its kernels to the host on the sub-chunk's
+    // own stream, under the kernels of the sub-chunks behind it
+    struct Mirror { uint8_t *host; const uint8_t *dev; long long row; } mirror = {nullptr, nullptr, 0};
     hipEvent_t ev[8] = {nullptr};
     // the blur only depends on the pyramid: it runs on a side stream next to FAST / quadtree and joins before rBRIEF
     hipStream_t sideStream = nullptr;
-    // a chunk's frames are split over the caller's stream and these, see Stage B
+    hipEvent_t evFork = nullptr, evJoin = nullptr;   // fork / join of the blur on sideStream
+    // a chunk's frames are split over the caller's stream and slots 1.. (slot 0 is the caller's stream except in the resident queue); the caller's
+    // stream waits for slot p's sub-chunks on slotJoin[p]
     static constexpr int kMaxParts = 8;
-    hipStream_t partStream[kMaxParts - 1] = {nullptr}, partSide[kMaxParts - 1] = {nullptr};   // partSide: the part's blur when the pyramid is split too
+    struct Lane { hipStream_t s, bs; hipEvent_t fork, join; };   // main stream, blur stream, fork / join of the blur
+    Lane slot[kMaxParts] = {};
+    hipEvent_t slotJoin[kMaxParts] = {nullptr};
     // rumi_orb_set_resident_queue: the frames of a call do not depend on work pending on the caller's stream, so sub-chunk 0 gets a stream of
     // its own too (with its blur stream) and no sub-chunk waits for the caller's stream: back-to-back calls then overlap like the sub-chunks of
     // one large call, only the caller's stream waits for each call's results
@@ -138,10 +141,7 @@ struct RumiOrb {
     int rot = 0;                     // slot of the next sub-chunk
     hipEvent_t userReady = nullptr;  // rumi_orb_wait_event: the sub-chunks of the next resident-queue call start behind it
     bool lastResident = false;       // the previous batched call ran in the resident-queue arrangement
-    hipStream_t part0Stream = nullptr, part0Side = nullptr;
-    hipEvent_t evPart0Join = nullptr, evSide0Fork = nullptr, evSide0Join = nullptr;
-    hipEvent_t evPartFork = nullptr, evPartJoin[kMaxParts - 1] = {nullptr}, evSideFork[kMaxParts - 1] = {nullptr}, evSideJoin[kMaxParts - 1] = {nullptr};
-    hipEvent_t evFork = nullptr, evJoin = nullptr, evB0 = nullptr, evB1 = nullptr;
+    hipEvent_t evPartFork = nullptr, evB0 = nullptr, evB1 = nullptr;
 };
 
 static int set_geometry(RumiOrb *h, int w, int hgt) {
@@ -208,11 +208,9 @@ static int set_geometry(RumiOrb *h, int w, int hgt) {
     // level l - 1 is the hull of what its region of level l reads (first tap column .. second tap column, first .. second source row) and of its
     // share of an even partition of level l - 1 (every pixel of every level belongs to some tile); x ranges are widened to multiples of 4 (the
     // kernels store dwords; the tables carry 4 padded columns).  Level 0's "region" is the window of the frame the tile reads.
-    // Two tile sets: small tiles (16 x 8 of the top level) for calls of a few frames, where the dependent chain is what counts (216 workgroups for
-    // one 640 x 480 frame); large tiles (RUMI_PYR_BATCH_TILE, default 48 x 16) for batches (opt-in, RUMI_PYRAMID_TILES=3: measured slower, see extract_async_impl), where the chip is full and what counts is the recomputed
-    // border (~1.2x the pixels instead of 1.8x) and the traffic: the frame is read once and every level written once, no level is read back.
-    auto build_tiles = [&](int kPyrTX, int kPyrTY, int set) -> int {
-        h->nPyrTiles[set] = 0; h->pyrBuf[set] = 0;
+    // Small tiles for calls of a few frames, where the dependent chain is what counts (216 workgroups for one 640 x 480 frame).
+    auto build_tiles = [&](int kPyrTX, int kPyrTY) -> int {
+        h->nPyrTiles = 0; h->pyrBuf = 0;
         if (P.nlevels < 2) return RUMI_OK;
         const int top = P.nlevels - 1;
         const int ntx = (P.lv[top].w + kPyrTX - 1) / kPyrTX, nty = (P.lv[top].h + kPyrTY - 1) / kPyrTY;
@@ -250,20 +248,14 @@ static int set_geometry(RumiOrb *h, int w, int hgt) {
             }
         bufMax = (bufMax + 15) & ~15;
         if (2 * bufMax + 8 * tabMax <= 60 * 1024 && tiles.size() <= 4096 && P.nlevels <= 8 && dimMax <= 256 && winRows <= 80 && winCols <= 256) {   // (the kernel's fixed shapes: orb_kernels.hip)
-            if (h->dPyrTiles[set]) { (void)hipFree(h->dPyrTiles[set]); h->dPyrTiles[set] = nullptr; }
-            HIP_TRY(hipMalloc((void **)&h->dPyrTiles[set], tiles.size() * sizeof(PyrTile)));
-            HIP_TRY(hipMemcpy(h->dPyrTiles[set], tiles.data(), tiles.size() * sizeof(PyrTile), hipMemcpyHostToDevice));
-            h->nPyrTiles[set] = (int)tiles.size(); h->pyrBuf[set] = bufMax; h->pyrTab[set] = tabMax;
+            if (h->dPyrTiles) { (void)hipFree(h->dPyrTiles); h->dPyrTiles = nullptr; }
+            HIP_TRY(hipMalloc((void **)&h->dPyrTiles, tiles.size() * sizeof(PyrTile)));
+            HIP_TRY(hipMemcpy(h->dPyrTiles, tiles.data(), tiles.size() * sizeof(PyrTile), hipMemcpyHostToDevice));
+            h->nPyrTiles = (int)tiles.size(); h->pyrBuf = bufMax; h->pyrTab = tabMax;
         }
         return RUMI_OK;
     };
-    {
-        int rcT = build_tiles(16, 8, 0);
-        if (rcT != RUMI_OK) return rcT;
-        int btx = 48, bty = 16;
-        if (const char *e = std::getenv("RUMI_PYR_BATCH_TILE")) { if (std::sscanf(e, "%dx%d", &btx, &bty) != 2 || btx < 4 || bty < 2) { btx = 48; bty = 16; } }
-        if ((rcT = build_tiles(btx, bty, 1)) != RUMI_OK) return rcT;
-    }
+    if (const int rcT = build_tiles(16, 8); rcT != RUMI_OK) return rcT;
     h->octLds = octree_lds_for(P);
     if (h->octLds > 160 * 1024) { g_lastError = "nfeatures too large for the LDS-resident quadtree node pool"; return RUMI_E_INVALID; }
     h->gw = w; h->gh = hgt;
@@ -289,27 +281,19 @@ extern "C" void rumi_orb_destroy(RumiOrb *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->pending) (void)hipStreamSynchronize(h->pendingStream);
-    void *dev[] = {h->dP, h->dCoef, h->dRowTab, h->dPyrTiles[0], h->dPyrTiles[1], h->dIn, h->dL0, h->dPyr, h->dBlur, h->dCellBuf, h->dCellCnt, h->dCand, h->dLevelStart,
-                   h->dSelPacked, h->dSelMeta, h->dSelCount, h->dKp, h->dDesc, h->dCounts,
-                   h->dOwner, h->dSelLevel, h->dSelLevelCnt, h->dErr};
+    void *dev[] = {h->dP, h->dCoef, h->dRowTab, h->dPyrTiles, h->dIn, h->dL0, h->dPyr, h->dBlur, h->dCellBuf, h->dCellCnt, h->dCand, h->dLevelStart,
+                   h->dSelPacked, h->dSelMeta, h->dSelCount, h->dOwner, h->dSelLevel, h->dSelLevelCnt, h->dErr};
     for (void *p : dev) if (p) (void)hipFree(p);
     void *pin[] = {h->hErr};
     for (void *p : pin) if (p) (void)hipHostFree(p);
     for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
-    if (h->evFork) (void)hipEventDestroy(h->evFork);
-    if (h->evJoin) (void)hipEventDestroy(h->evJoin);
-    if (h->evB0) (void)hipEventDestroy(h->evB0);
-    if (h->evB1) (void)hipEventDestroy(h->evB1);
+    for (hipEvent_t e : {h->evFork, h->evJoin, h->evB0, h->evB1, h->evPartFork}) if (e) (void)hipEventDestroy(e);
     if (h->sideStream) (void)hipStreamDestroy(h->sideStream);
-    for (auto &ps : h->partStream) if (ps) (void)hipStreamDestroy(ps);
-    for (auto &ps : h->partSide) if (ps) (void)hipStreamDestroy(ps);
-    for (auto &e : h->evPartJoin) if (e) (void)hipEventDestroy(e);
-    for (auto &e : h->evSideFork) if (e) (void)hipEventDestroy(e);
-    for (auto &e : h->evSideJoin) if (e) (void)hipEventDestroy(e);
-    if (h->evPartFork) (void)hipEventDestroy(h->evPartFork);
-    if (h->part0Stream) (void)hipStreamDestroy(h->part0Stream);
-    if (h->part0Side) (void)hipStreamDestroy(h->part0Side);
-    for (hipEvent_t e : {h->evPart0Join, h->evSide0Fork, h->evSide0Join}) if (e) (void)hipEventDestroy(e);
+    for (const auto &L : h->slot)
+        for (hipStream_t s : {L.s, L.bs}) if (s) (void)hipStreamDestroy(s);
+    for (const auto &L : h->slot)
+        for (hipEvent_t e : {L.fork, L.join}) if (e) (void)hipEventDestroy(e);
+    for (auto &e : h->slotJoin) if (e) (void)hipEventDestroy(e);
     if (h->dHostIn) (void)hipFree(h->dHostIn);
     for (auto &p : h->hFeed) if (p) (void)hipHostFree(p);
     for (auto &e : h->evFeed) if (e) (void)hipEventDestroy(e);
@@ -400,9 +384,6 @@ extern "C" int rumi_orb_create(const RumiOrbConfig *cfg, RumiOrb **out) {
     TRY_ALLOC(dev_alloc(&h->dRowTab, (size_t)std::max(h->capRowTab, 1)));
     TRY_ALLOC(dev_alloc(&h->dIn, (size_t)((cfg->max_width + 3) & ~3) * cfg->max_height));
     TRY_ALLOC(alloc_frame_arenas(h, C, B));
-    TRY_ALLOC(dev_alloc(&h->dKp, (size_t)h->capSel));
-    TRY_ALLOC(dev_alloc(&h->dDesc, (size_t)h->capSel * 32));
-    TRY_ALLOC(dev_alloc(&h->dCounts, 2));
     TRY_ALLOC(dev_alloc(&h->dOut1, (size_t)16 + (size_t)h->capSel * 60));
     if (hipHostMalloc((void **)&h->hIn, (size_t)((cfg->max_width + 3) & ~3) * cfg->max_height, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc((void **)&h->hOut1, (size_t)16 + (size_t)h->capSel * 60, hipHostMallocDefault) != hipSuccess) {
@@ -414,19 +395,21 @@ extern "C" int rumi_orb_create(const RumiOrbConfig *cfg, RumiOrb **out) {
         (void)hipGetLastError();
         h->dhOut1 = nullptr; h->dhErr = nullptr;            // (no device view of the pinned blocks: the copies stay)
     }
-    if (hipHostGetDevicePointer((void **)&h->dhIn, h->hIn, 0) != hipSuccess) { (void)hipGetLastError(); h->dhIn = nullptr; }
 #undef TRY_ALLOC
     for (auto &e : h->ev)
         if (hipEventCreate(&e) != hipSuccess) { rumi_orb_destroy(h); g_lastError = "hipEventCreate"; return RUMI_E_NO_DEVICE; }
-    for (int i = 0; i < RumiOrb::kMaxParts - 1; ++i)
-        if (hipStreamCreateWithFlags(&h->partStream[i], hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&h->partSide[i], hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&h->evSideFork[i], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->evSideJoin[i], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h->evPartJoin[i], hipEventDisableTiming) != hipSuccess) { rumi_orb_destroy(h); g_lastError = "part stream"; return RUMI_E_NO_DEVICE; }
-    if (hipEventCreateWithFlags(&h->evPartFork, hipEventDisableTiming) != hipSuccess) { rumi_orb_destroy(h); g_lastError = "part event"; return RUMI_E_NO_DEVICE; }
-    if (hipStreamCreateWithFlags(&h->part0Stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&h->part0Side, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&h->evPart0Join, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->evSide0Fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->evSide0Join, hipEventDisableTiming) != hipSuccess) { rumi_orb_destroy(h); g_lastError = "part stream 0"; return RUMI_E_NO_DEVICE; }
-    if (hipStreamCreateWithFlags(&h->sideStream, hipStreamNonBlocking) != hipSuccess ||
+    // slots 1 .. kMaxParts - 1 first, then slot 0, then the side stream: streams share the hardware queues in creation order
+    auto make_slot = [h](int p) {
+        RumiOrb::Lane &L = h->slot[p];
+        return hipStreamCreateWithFlags(&L.s, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&L.bs, hipStreamNonBlocking) == hipSuccess &&
+               hipEventCreateWithFlags(&L.fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&L.join, hipEventDisableTiming) == hipSuccess &&
+               hipEventCreateWithFlags(&h->slotJoin[p], hipEventDisableTiming) == hipSuccess;
+    };
+    bool slotsOk = true;
+    for (int p = 1; p < RumiOrb::kMaxParts && slotsOk; ++p) slotsOk = make_slot(p);
+    if (!slotsOk || !make_slot(0)) { rumi_orb_destroy(h); g_lastError = "slot stream"; return RUMI_E_NO_DEVICE; }
+    if (hipEventCreateWithFlags(&h->evPartFork, hipEventDisableTiming) != hipSuccess ||
+        hipStreamCreateWithFlags(&h->sideStream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->evFork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming) != hipSuccess || hipEventCreate(&h->evB0) != hipSuccess ||
         hipEventCreate(&h->evB1) != hipSuccess) { rumi_orb_destroy(h); g_lastError = "side stream"; return RUMI_E_NO_DEVICE; }
@@ -434,12 +417,6 @@ extern "C" int rumi_orb_create(const RumiOrbConfig *cfg, RumiOrb **out) {
     return RUMI_OK;
 }
 
-// Frames per sub-chunk of the resident queue.  256 since the end of round 3 (64 before): with the latency-bound kernels of a sub-chunk's chain
-// shortened (compaction, quadtree) larger launches win at every call size (1024-frame steps +3 %, 128-frame calls +5 %); RUMI_RESIDENT_SUB overrides.
-static int resident_sub_frames() {
-    static const int v = std::getenv("RUMI_RESIDENT_SUB") ? std::max(1, std::atoi(std::getenv("RUMI_RESIDENT_SUB"))) : 256;
-    return v;
-}
 extern "C" int rumi_orb_set_profiling(RumiOrb *h, int32_t on) {
     if (!h) return RUMI_E_INVALID;
     h->profiling = on != 0;
@@ -452,7 +429,7 @@ extern "C" int rumi_orb_set_resident_queue(RumiOrb *h, int32_t on) {
         // `on` slots (1: the default of four) of up to 256 frames each: their scratch ranges and their ranges of the pyramid / blur arenas
         const int slots = on == 1 ? 4 : std::min(std::max(on, 2), (int)RumiOrb::kMaxParts);
         h->residentSlots = slots;
-        const int need = (slots * std::min(resident_sub_frames(), h->cfg.max_batch) + 23) / 24 * 24;
+        const int need = (slots * std::min(kResidentSub, h->cfg.max_batch) + 23) / 24 * 24;
         if (h->scratchFrames < need || h->arenaFrames < need) {
             HIP_TRY(hipSetDevice(h->device));
             HIP_TRY(hipDeviceSynchronize());
@@ -550,40 +527,29 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
     // Batches of 64 frames and more are pipelined: sub-chunks of frames run pyramid -> FAST -> ... -> rBRIEF on up to 4 streams (sub-chunk j
     // on stream j % parts, in scratch slot j % parts), so the narrow launches of one sub-chunk (upper pyramid levels, compaction, quadtree:
     // latency-bound, few waves) sit beside the wide VALU-bound ones of the others.  Profiling and RUMI_SERIAL keep one stream.
-    static const int envParts = std::getenv("RUMI_PARTS") ? std::atoi(std::getenv("RUMI_PARTS")) : 4;
-    const int parts = (!prof && !serial) ? std::min(std::min(std::max(envParts, 1), (int)RumiOrb::kMaxParts), std::max(nframes / 32, 1)) : 1;
+    const int parts = (!prof && !serial) ? std::min(4, std::max(nframes / 32, 1)) : 1;
     // the call's error word starts at zero: a memset on the caller's stream, or -- a call that runs as one part on that stream (a handful of
     // frames: every dispatch counts) -- a store by the first pyramid kernel, which nothing that writes the word precedes
     bool clearInKernel = !h->pending && parts == 1 && !(h->residentQueue && !prof && !serial && !h->feed) && P.nlevels > 1;
     if (!h->pending && !clearInKernel) HIP_TRY(hipMemsetAsync(h->dErr, 0, sizeof(int32_t), st));
     if (h->userReady && !(h->residentQueue && !prof && !serial && !h->feed)) { HIP_TRY(hipStreamWaitEvent(st, h->userReady, 0)); h->userReady = nullptr; }
-    // the streams and events of one sub-chunk slot: main stream, blur stream, fork / join of the blur
-    struct Lane { hipStream_t s, bs; hipEvent_t fork, join; };
     const bool resident = h->residentQueue && !prof && !serial && !h->feed;
+    using Lane = RumiOrb::Lane;
     auto lane_of = [&](int slot) -> Lane {
-        if (slot) return {h->partStream[slot - 1], serial ? h->partStream[slot - 1] : h->partSide[slot - 1], h->evSideFork[slot - 1], h->evSideJoin[slot - 1]};
-        if (resident) return {h->part0Stream, h->part0Side, h->evSide0Fork, h->evSide0Join};      // (no slot runs on the caller's stream)
+        if (slot || resident) return h->slot[slot];      // (in the resident queue no slot runs on the caller's stream)
         return {st, serial || prof ? st : h->sideStream, h->evFork, h->evJoin};        // profiling: the blur on the call's stream too, so that every stage time is a stand-alone duration
     };
     // A few frames (the Tracking thread's call): FAST and the blur go out as ONE launch on the main stream (k_fast_blur).  As two launches the
     // blur runs on the side stream, and the event that forks it stalls the main queue for ~20 us on this runtime: more than the blur takes.
-    static const int envFuse = std::getenv("RUMI_FUSE_FAST_BLUR") ? std::atoi(std::getenv("RUMI_FUSE_FAST_BLUR")) : -1;
-    const bool fuseBlur = !prof && !serial && (envFuse >= 0 ? envFuse != 0 : nframes < 16) && fast_blur_fusable(P);
-    // A few frames: the pyramid in ONE launch (k_pyramid_tiles) instead of a launch per level
-    static const int envTiles = std::getenv("RUMI_PYRAMID_TILES") ? std::atoi(std::getenv("RUMI_PYRAMID_TILES")) : -1;
-    // RUMI_PYRAMID_TILES: unset = the small tiles for calls of up to 4 frames, a launch per level beyond; 0 = a launch per level for every call;
-    // 1 = the small tiles for every call; 3 = small tiles up to 4 frames and the LARGE ones beyond.  (3 was MEASURED for batches in round 4 and is
-    // not the default: 1024-frame steps run at 208-210 k fps with 32 x 16 / 48 x 16 top-level tiles against 234 k with the per-level launches -- a
+    const bool fuseBlur = !prof && !serial && nframes < 16 && fast_blur_fusable(P);
+    // Up to 4 frames: the pyramid in ONE launch (k_pyramid_tiles) instead of a launch per level.  (Batches keep the per-level launches: a
     // workgroup walks seven levels between barriers and its threads idle on the small ones, which costs more than the saved re-reads bring.)
-    const int tileSet = nframes <= 4 || envTiles == 1 ? 0 : 1;
-    const bool tilePyramid = !prof && h->nPyrTiles[tileSet] > 0 &&
-                             (tileSet == 0 ? (!serial && (envTiles >= 0 ? envTiles != 0 : true)) : envTiles == 3);
-    bool copyL0 = false;
+    const bool tilePyramid = !prof && !serial && nframes <= 4 && h->nPyrTiles > 0;
     auto stage_a = [&](const ImgSrc &ps, int n, const Lane &L) -> int {
         hipStream_t s = L.s;
         if (prof) HIP_TRY(hipEventRecord(h->ev[0], s));
         if (tilePyramid) {
-            launch_pyramid_tiles(h->dP, ps, h->dCoef, h->dRowTab, h->dPyrTiles[tileSet], h->nPyrTiles[tileSet], h->pyrBuf[tileSet], h->pyrTab[tileSet], n, s, clearInKernel ? h->dErr : nullptr, copyL0);
+            launch_pyramid_tiles(h->dP, ps, h->dCoef, h->dRowTab, h->dPyrTiles, h->nPyrTiles, h->pyrBuf, h->pyrTab, n, s, clearInKernel ? h->dErr : nullptr);
             clearInKernel = false;
         } else
         for (int l = 1; l < P.nlevels; l++) {
@@ -601,26 +567,15 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
         HIP_TRY(hipGetLastError());
         return RUMI_OK;
     };
-    // rumi_orb_extract's frame, still in pinned host memory: copied to dIn first.  (RUMI_ORB_ZERO_COPY_IN=1: read in place by the one-launch pyramid,
-    // which keeps a copy as the arena's level 0 for everything after it -- one dependent transfer less, but MEASURED SLOWER: the kernel's 550 KB of
-    // window reads over PCIe take 25 us more than the 13 us copy + queue latency they replace: 124.8 against 99.8 us per call.  Off by default.)
-    static const bool zcIn = std::getenv("RUMI_ORB_ZERO_COPY_IN") && std::atoi(std::getenv("RUMI_ORB_ZERO_COPY_IN")) != 0;
-    bool l0FromHost = false;
+    // rumi_orb_extract's frame, still in pinned host memory: copied to dIn first.  (Reading it over PCIe in the one-launch pyramid instead was
+    // measured slower: 124.8 against 99.8 us per call.)
     if (h->hostImagePending) {
         h->hostImagePending = false;
-        if (zcIn && h->dhIn && tilePyramid && parts == 1 && !resident && nframes == 1) { l0FromHost = true; src.l0 = h->dhIn; }
-        else HIP_TRY(hipMemcpyAsync(h->dIn, h->hIn, (size_t)stride * hgt, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(h->dIn, h->hIn, (size_t)stride * hgt, hipMemcpyHostToDevice, st));
     }
     if (parts == 1 && !resident) {
         if (h->feed && (rc = h->feed(nframes, st)) != RUMI_OK) return rc;
-        copyL0 = l0FromHost;
-        rc = stage_a(src, nframes, lane_of(0));
-        copyL0 = false;
-        if (rc != RUMI_OK) return rc;
-        if (l0FromHost) {                                    // from here on level 0 is the arena's copy
-            src.l0 = h->dPyr + P.lv[0].off; src.l0FrameStride = P.arenaStride; src.l0Pitch = P.lv[0].pitch;
-            frame_stride = P.arenaStride; stride = P.lv[0].pitch;
-        }
+        if ((rc = stage_a(src, nframes, lane_of(0))) != RUMI_OK) return rc;
     }
 
     // FAST -> compaction -> quadtree -> orientation + descriptors for the frames [frame0, frame0 + n) of the batch on stream s, in the scratch
@@ -648,8 +603,7 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
         if (timed) HIP_TRY(hipEventRecord(h->ev[5], s));
         launch_octree(h->dP, P, candp, lvStart, h->dOwner + (size_t)scr0 * P.totalCand, selLevel, selLevelCnt, h->selLevelCap, h->dErr, n, h->octLds, s);
         // a few frames: the slot assignment (k_assemble) inside the descriptor kernel's prologue, one launch less on the dependent chain
-        static const int envFuseA = std::getenv("RUMI_FUSE_ASSEMBLE") ? std::atoi(std::getenv("RUMI_FUSE_ASSEMBLE")) : -1;
-        const bool fuseAssemble = !timed && !serial && (envFuseA >= 0 ? envFuseA != 0 : n <= 4) && (long long)((h->capSel + 7) / 8) * n <= 2048;
+        const bool fuseAssemble = !timed && !serial && n <= 4 && (long long)((h->capSel + 7) / 8) * n <= 2048;
         int32_t *countsOut = (int32_t *)((uint8_t *)d_counts + (size_t)frame0 * out.countsStride);
         if (!fuseAssemble)
             launch_assemble(h->dP, selLevel, selLevelCnt, h->selLevelCap, lap0, lap1, selPacked, selMeta, h->dSelCount + scr0, h->capSel,
@@ -666,8 +620,8 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
                            (RumiKeyPoint *)((uint8_t *)d_kp + (size_t)frame0 * out.kpStride), out.kpStride,
                            (uint8_t *)d_desc + (size_t)frame0 * out.descStride, out.descStride, cap, n, s);
         if (timed) HIP_TRY(hipEventRecord(h->ev[7], s));
-        for (const auto &mr : h->mirror)
-            if (mr.host) HIP_TRY(hipMemcpyAsync(mr.host + (size_t)frame0 * mr.row, mr.dev + (size_t)frame0 * mr.row, (size_t)n * mr.row, hipMemcpyDeviceToHost, s));
+        const RumiOrb::Mirror &mr = h->mirror;
+        if (mr.host) HIP_TRY(hipMemcpyAsync(mr.host + (size_t)frame0 * mr.row, mr.dev + (size_t)frame0 * mr.row, (size_t)n * mr.row, hipMemcpyDeviceToHost, s));
         return RUMI_OK;
     };
     if (resident) {
@@ -678,7 +632,7 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
         constexpr int kMaxSlots = RumiOrb::kMaxParts;
         const int kSlots = h->residentSlots;
         const int slotFrames = h->scratchFrames / kSlots;
-        const int cap64 = std::min(resident_sub_frames(), slotFrames);
+        const int cap64 = std::min(kResidentSub, slotFrames);
         const int nsub = (nframes + cap64 - 1) / cap64, sub = (nframes + nsub - 1) / nsub;
         // (unaligned frames were staged into dL0 by copies queued on `st`: every slot stream this call touches waits for them.  The previous
         // call's readers of dL0 are behind `st` already: the caller's stream waited for that call's results at its end.)
@@ -700,16 +654,14 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
         // Join: the caller's stream waits for the results of every sub-chunk (an event per slot, taken after the slot's last sub-chunk)
         for (int p = 0; p < kSlots; p++)
             if (touched[p]) {
-                hipEvent_t e = p ? h->evPartJoin[p - 1] : h->evPart0Join;
-                HIP_TRY(hipEventRecord(e, lane_of(p).s));
-                HIP_TRY(hipStreamWaitEvent(st, e, 0));
+                HIP_TRY(hipEventRecord(h->slotJoin[p], h->slot[p].s));
+                HIP_TRY(hipStreamWaitEvent(st, h->slotJoin[p], 0));
             }
         HIP_TRY(hipGetLastError());
     } else if (parts > 1) {
         // equal sub-chunks: rounds of `parts` sub-chunks, as few rounds as the slots allow, no short tail
         const int slotFrames = h->scratchFrames / parts;
-        static const int envSub = std::getenv("RUMI_SUBMAX") ? std::atoi(std::getenv("RUMI_SUBMAX")) : 1 << 30;
-        const int subMax = std::max(1, std::min(std::min(slotFrames, 64), envSub));      // (64: the host path's transfer groups; the arenas may hold more since the resident queue grew them)
+        const int subMax = std::max(1, std::min(slotFrames, 64));      // (64: the host path's transfer groups; the arenas may hold more since the resident queue grew them)
         const int rounds = (nframes + parts * subMax - 1) / (parts * subMax), sub = (nframes + parts * rounds - 1) / (parts * rounds);
         HIP_TRY(hipEventRecord(h->evPartFork, st));
         int used = 0;
@@ -724,8 +676,8 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
             h->lastChunkBase = base; h->lastChunkFrames = n; h->lastChunkSlot = slot * slotFrames;
         }
         for (int p = 1; p < used; p++) {
-            HIP_TRY(hipEventRecord(h->evPartJoin[p - 1], h->partStream[p - 1]));
-            HIP_TRY(hipStreamWaitEvent(st, h->evPartJoin[p - 1], 0));
+            HIP_TRY(hipEventRecord(h->slotJoin[p], h->slot[p].s));
+            HIP_TRY(hipStreamWaitEvent(st, h->slotJoin[p], 0));
         }
         HIP_TRY(hipGetLastError());
     } else {
@@ -829,11 +781,10 @@ static int extract_batch_host_impl(RumiOrb *h, const uint8_t *const *imgs, int32
     }
     hipStream_t st = (hipStream_t)hip_stream;
     int fed = 0, group = 0;                                    // frames already on their way, groups enqueued
-    static const bool twoCopyStreams = std::getenv("RUMI_ONE_COPY_STREAM") == nullptr;
     h->feed = [&](int upto, hipStream_t s) -> int {
         while (fed < upto) {
             const int n = std::min(G, nframes - fed), slot = group % S;
-            hipStream_t cs = (twoCopyStreams && (group & 1)) ? h->copyStream2 : h->copyStream;
+            hipStream_t cs = (group & 1) ? h->copyStream2 : h->copyStream;
             if (group >= S) HIP_TRY(hipEventSynchronize(h->evFeed[slot]));       // the slot's previous group has left the pinned buffer / its event is free again
             bool dense = pinned && stride == wp;                               // one buffer, frames back to back: one transfer per group
             for (int f = 1; dense && f < n; f++) dense = imgs[fed + f] == imgs[fed] + (size_t)f * frameBytes;
@@ -860,7 +811,7 @@ static int extract_batch_host_impl(RumiOrb *h, const uint8_t *const *imgs, int32
         }
         // copies complete in order on each copy stream: waiting for the newest group of each covers every frame below `upto`
         HIP_TRY(hipStreamWaitEvent(s, h->evFeed[(group - 1) % S], 0));
-        if (twoCopyStreams && group >= 2) HIP_TRY(hipStreamWaitEvent(s, h->evFeed[(group - 2) % S], 0));
+        if (group >= 2) HIP_TRY(hipStreamWaitEvent(s, h->evFeed[(group - 2) % S], 0));
         return RUMI_OK;
     };
     rc = extract_async_impl(h, h->dHostIn, nframes, w, hgt, wp, (int64_t)frameBytes, lap0, lap1, out, cap, hip_stream);
@@ -874,29 +825,14 @@ extern "C" int rumi_orb_extract_batch_host(RumiOrb *h, const uint8_t *const *img
                                            int32_t lap0, int32_t lap1, void *d_kp, void *d_desc, void *d_counts, int32_t cap,
                                            RumiKeyPoint *h_kp, uint8_t *h_desc, int32_t *h_counts, void *hip_stream) {
     const OutLayout out{d_kp, (long long)cap * (long long)sizeof(RumiKeyPoint), d_desc, (long long)cap * 32, d_counts, 8};
-    // host arrays: one copy each at the end; optionally (pinned arrays) every sub-chunk's rows behind that sub-chunk's kernels (run_part)
-    // (MEASURED SLOWER for these three arrays, 4.4 MB per 64-frame sub-chunk: host frames in, everything out, 1024 frames a step: 101 k fps against 105-122 k
-    // with one copy each at the end -- the copies hold the sub-chunk streams while the uploads are the bottleneck.  Only with RUMI_ORB_MIRROR=2.  The record
-    // layout below gains 4 % from the same mechanism and has it by default.)
-    static const bool mirrorOn = std::getenv("RUMI_ORB_MIRROR") && std::atoi(std::getenv("RUMI_ORB_MIRROR")) == 2;
-    auto pinned = [](const void *p) {
-        hipPointerAttribute_t attr{};
-        const bool yes = mirrorOn && p && hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeHost;
-        (void)hipGetLastError();
-        return yes;
-    };
-    const bool pk = h && d_kp && pinned(h_kp), pd = h && d_desc && pinned(h_desc), pc = h && d_counts && pinned(h_counts);
-    if (pk) h->mirror[0] = {(uint8_t *)h_kp, (const uint8_t *)d_kp, out.kpStride};
-    if (pd) h->mirror[1] = {h_desc, (const uint8_t *)d_desc, out.descStride};
-    if (pc) h->mirror[2] = {(uint8_t *)h_counts, (const uint8_t *)d_counts, out.countsStride};
-    const int rc = extract_batch_host_impl(h, imgs, nframes, w, hgt, stride, lap0, lap1, out, cap, hip_stream, [&](hipStream_t st) -> int {
-        if (h_counts && !pc) HIP_TRY(hipMemcpyAsync(h_counts, d_counts, (size_t)nframes * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (h_kp && !pk) HIP_TRY(hipMemcpyAsync(h_kp, d_kp, (size_t)nframes * cap * sizeof(RumiKeyPoint), hipMemcpyDeviceToHost, st));
-        if (h_desc && !pd) HIP_TRY(hipMemcpyAsync(h_desc, d_desc, (size_t)nframes * cap * 32, hipMemcpyDeviceToHost, st));
+    // host arrays: one copy each at the end.  (Copies behind every sub-chunk, as the record layout below has them, were measured slower for these
+    // three arrays: they hold the sub-chunk streams while the uploads are the bottleneck.)
+    return extract_batch_host_impl(h, imgs, nframes, w, hgt, stride, lap0, lap1, out, cap, hip_stream, [&](hipStream_t st) -> int {
+        if (h_counts) HIP_TRY(hipMemcpyAsync(h_counts, d_counts, (size_t)nframes * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (h_kp) HIP_TRY(hipMemcpyAsync(h_kp, d_kp, (size_t)nframes * cap * sizeof(RumiKeyPoint), hipMemcpyDeviceToHost, st));
+        if (h_desc) HIP_TRY(hipMemcpyAsync(h_desc, d_desc, (size_t)nframes * cap * 32, hipMemcpyDeviceToHost, st));
         return RUMI_OK;
     });
-    if (h) for (auto &mr : h->mirror) mr = {nullptr, nullptr, 0};
-    return rc;
 }
 
 // The host-resident queue with ONE record per frame as output (the all-gather payload, rumi_orb_extract_batch_records_async's layout); h_records:
@@ -910,15 +846,14 @@ extern "C" int rumi_orb_extract_batch_host_records(RumiOrb *h, const uint8_t *co
     // a pinned destination takes the records sub-chunk by sub-chunk behind the kernels (run_part); a pageable one (whose "asynchronous" copy would hold
     // the enqueuing thread) gets them in one copy at the end
     hipPointerAttribute_t attr{};
-    static const bool mirrorOn = !(std::getenv("RUMI_ORB_MIRROR") && std::atoi(std::getenv("RUMI_ORB_MIRROR")) == 0);
-    const bool pinnedOut = mirrorOn && h && h_records && hipPointerGetAttributes(&attr, h_records) == hipSuccess && attr.type == hipMemoryTypeHost;
+    const bool pinnedOut = h && h_records && hipPointerGetAttributes(&attr, h_records) == hipSuccess && attr.type == hipMemoryTypeHost;
     (void)hipGetLastError();
-    if (pinnedOut) h->mirror[0] = {h_records, r, record_bytes};
+    if (pinnedOut) h->mirror = {h_records, r, record_bytes};
     const int rc = extract_batch_host_impl(h, imgs, nframes, w, hgt, stride, lap0, lap1, out, cap, hip_stream, [&](hipStream_t st) -> int {
         if (h_records && !pinnedOut) HIP_TRY(hipMemcpyAsync(h_records, d_records, (size_t)nframes * record_bytes, hipMemcpyDeviceToHost, st));
         return RUMI_OK;
     });
-    if (h) h->mirror[0] = {nullptr, nullptr, 0};
+    if (h) h->mirror = {nullptr, nullptr, 0};
     return rc;
 }
 
@@ -944,12 +879,11 @@ extern "C" int rumi_orb_extract(RumiOrb *h, const uint8_t *img, int32_t w, int32
     const int wp = (w + 3) & ~3;                                     // rows padded so that level 0 can be read as aligned dwords
     if (!(img == h->hIn && stride == wp))                    // (a caller that captured straight into rumi_orb_image_buffer's memory has nothing to stage)
         for (int y = 0; y < hgt; y++) std::memcpy(h->hIn + (size_t)y * wp, img + (size_t)y * stride, (size_t)w);
-    h->hostImagePending = true;                              // (extract_async_impl reads it in place or copies it: see there)
+    h->hostImagePending = true;                              // (extract_async_impl copies it to dIn on the call's stream)
     // Results straight into pinned host memory: the kernels' output pointers are the device's view of hOut1 (k_assemble writes the counts and the
     // final error word, k_orient_desc key-points and descriptors), so the call ends with its last kernel -- no copy back, no second copy for the
-    // error word (two dependent transfers of ~6 + 2 us with ~9 us of queue latency each).  RUMI_ORB_ZERO_COPY=0 keeps the copies (A/B measurements).
-    static const bool zc = !(std::getenv("RUMI_ORB_ZERO_COPY") && std::atoi(std::getenv("RUMI_ORB_ZERO_COPY")) == 0);
-    const bool zero = zc && h->dhOut1 && h->dhErr && !h->profiling;
+    // error word (two dependent transfers of ~6 + 2 us with ~9 us of queue latency each).  Profiling keeps the copies.
+    const bool zero = h->dhOut1 && h->dhErr && !h->profiling;
     uint8_t *ob = zero ? h->dhOut1 : h->dOut1;
     int32_t *dC = reinterpret_cast<int32_t *>(ob);
     RumiKeyPoint *dK = reinterpret_cast<RumiKeyPoint *>(ob + 16);

@@ -180,11 +180,9 @@ __global__ __launch_bounds__(256) void k_resize(const DevParams *__restrict__ P,
 // region is the source of level l's, the regions (PyrTile, from the host's resize tables) overlap by the taps' reach, and every workgroup
 // stores all it computed -- overlapping stores carry the same bytes.  The arithmetic per pixel is k_resize's general path, tap for tap.
 // ------------------------------------------------------------------------------------------------
-// copyL0: the caller's frame is PINNED HOST memory read over PCIe (a one-frame call without its host-to-device copy): the windows, which cover the frame,
-// are stored into the arena's level-0 slot as they pass through the registers, and every later kernel of the call reads level 0 there.
 __global__ __launch_bounds__(256) void k_pyramid_tiles(const DevParams *__restrict__ P, ImgSrc src, const int16_t *__restrict__ coef,
                                                        const RowTap *__restrict__ rowTab, const PyrTile *__restrict__ tiles, int bufBytes,
-                                                       int32_t *__restrict__ clearWord, int copyL0) {
+                                                       int32_t *__restrict__ clearWord) {
     // LDS: two image buffers of bufBytes (a level's region and the one computed from it), then the tile's slices of the resize tables
     // (per level and row: source rows relative to the buffer | vertical taps; per level and column: source column relative to the buffer, tap pair)
     extern __shared__ __attribute__((aligned(16))) uint8_t pyrLds[];
@@ -258,15 +256,6 @@ __global__ __launch_bounds__(256) void k_pyramid_tiles(const DevParams *__restri
             const int y = wy + 4 * k;
             if (y < ah && wx < aw) *reinterpret_cast<uint32_t *>(A + y * apitch + wx) = win[k];
         }
-        if (copyL0) {
-            const DevLevel &D0 = P->lv[0];
-            uint8_t *l0 = src.pyr + (long long)frame * P->arenaStride + D0.off;
-#pragma unroll
-            for (int k = 0; k < kPyrWinPasses; k++) {
-                const int y = wy + 4 * k;
-                if (y < ah && wx < aw && ax0 + wx + 4 <= D0.pitch) *reinterpret_cast<uint32_t *>(l0 + (long long)(ay0 + y) * D0.pitch + ax0 + wx) = win[k];
-            }
-        }
     }
     __syncthreads();
     int base = 0;
@@ -332,7 +321,6 @@ __global__ __launch_bounds__(256) void k_pyramid_tiles(const DevParams *__restri
 // pairs that get the exact score (fast_quick_pair / fast_score_polar).
 // ------------------------------------------------------------------------------------------------
 #include <algorithm>
-#include <cstdlib>
 __device__ __forceinline__ int min3i(int a, int b, int c) { return min(min(a, b), c); }
 __device__ __forceinline__ int max3i(int a, int b, int c) { return max(max(a, b), c); }
 
@@ -347,25 +335,20 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// ---- quick test and exact score, third formulation (round 3) --------------------------------------------------------------------
+// ---- quick test and exact score ---------------------------------------------------------------------------------------------------
 // Instruction classes on gfx950 (tools/valu_rate.hip, profiles/r02_valu_issue_rates.txt): plain add / sub / and / or / xor / right shift /
 // mov issue in ~2.4 cycles per wave once two waves share a SIMD; every min / max, three-operand, packed, SDWA and DPP form takes ~4.2.
 //
 // Tile.  Column c of the LDS tile is image column iniX - 1 + c: the detection region (cv::FAST's 3-px margin inside the sub-image)
 // ALWAYS starts at tile column 4, i.e. on a dword, whatever iniX is (the staging loads are unaligned 4-byte global loads).  A row of the
-// region then is ceil(dw / 4) aligned 4-pixel groups with no partial first group (round 2 staged aligned dwords and lost up to one
+// region then is made of aligned 4-pixel groups with no partial first group (round 2 staged aligned dwords and lost up to one
 // group per row to the shift).
 //
 // Quick test (necessary condition, per polarity): every arc of 9 contains 4 consecutive of the 8 EVEN circle positions, so a pixel can
 // reach contrast T on the darker-ring side only if 4 consecutive even positions all have v - p_k >= T (brighter ring: p_k - v >= T).
-// A lane takes the 4 pixels of one group; its operands come from 11 aligned dword reads of LDS.  Pixels (0, 2) and (1, 3) travel as
-// 16-bit halves of two registers ("even" / "odd" pair).  Adding 2^b - T to the centre before ONE 32-bit subtraction of the packed ring
-// pixels leaves "contrast >= T" in bit b of each half (the halves never borrow from each other: every half stays within 2^b +- 511).
-// The four families (pair x polarity) use b = 12..15, one v_bfi_b32 each merges them into ONE word per circle position, and the
-// "4 consecutive" rule (23 ANDs / ORs) runs once for all eight (pixel, polarity) combinations of the lane instead of four times.
 // Ring entries = tile offset of the pixel | polarity << 15; a pixel's darker entry always precedes its brighter one.
-constexpr int kRingCap = 640;        // linear: < 128 entries wait between steps, a step appends up to 512 (64 lanes x 4 pixels x 2 polarities;
-                                     // the byte formulation below appends its up-to-1024 in two halves when they do not fit)
+constexpr int kRingCap = 640;        // linear: < 128 entries wait between steps, a step appends up to 1024 (64 lanes x 8 pixels x 2 polarities)
+                                     // in two halves when they do not fit
 constexpr int kScoredCap = 640;
 // (ring pixels q in [0, 255] travel as 0x4100 + q: positive normal f16 bit patterns of one exponent, ordered like the integers)
 
@@ -390,23 +373,6 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
     return v;
 }
 
-// every bit position on its own: 4 consecutive of the 8 words have the bit set (circular)
-__device__ __forceinline__ uint32_t four_consecutive(const uint32_t (&f)[8]) {
-    uint32_t c[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) c[k] = f[k] & f[(k + 1) & 7];
-    uint32_t any = c[0] & c[2];
-#pragma unroll
-    for (int k = 1; k < 8; k++) any |= c[k] & c[(k + 2) & 7];
-    return any;
-}
-// (a & mask) | (b & ~mask) as ONE instruction.  Inline asm on purpose: written in C the compiler sees that only the masked bits are ever
-// used, distributes the masks through the AND / OR network below and ends up with the four separate networks again.
-__device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) {
-    uint32_t r;
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(mask), "v"(a), "v"(b));
-    return r;
-}
 
 typedef __attribute__((address_space(3))) const uint8_t lds_cu8;
 __device__ __forceinline__ uint32_t lds_addr(const uint8_t *p) { return (uint32_t)(uintptr_t)(lds_cu8 *)p; }
@@ -512,93 +478,8 @@ __device__ __forceinline__ void fast_score_batch(const uint8_t *tile, uint8_t *s
     nScored = total;
 }
 
-// score map of one cell (CTP != 0: compile-time tile pitch; the score map shares the tile's pitch, so a pixel's score byte sits at
-// its tile offset + scDelta).  Returns the number of scored-list appends.
-template <int CTP>
-__device__ __forceinline__ int fast_score_cell(const uint8_t *tile, uint8_t *sc, uint16_t *cl, uint16_t *sl, int tp, int dw, int dh, int tlow, int lane) {
-    const int TP = CTP ? CTP : tp;
-    const int ng = (dw + 3) >> 2;                         // aligned 4-pixel groups per row; the first starts at tile column 4
-    const int nItems = ng * dh;
-    const unsigned Mng = magic_of(ng);
-    const int scDelta = -2 * TP - 3;                      // tile offset (py + 3) * TP + px + 4  ->  score byte (py + 1) * TP + px + 1
-    // entry mask (2 bits per pixel) of a row's last group: pixels from column dw on lie outside the region
-    const uint32_t mLast = 0xFFu >> (2 * (4 * ng - dw));
-    const uint32_t T2 = (uint32_t)(tlow + 1);             // the contrast a circle pixel needs
-    // flag bit of each (pair, polarity) family: even-pair darker 12, even-pair brighter 13, odd-pair darker 14, odd-pair brighter 15 -- bit
-    // 2 i + polarity of (any >> 12) then belongs to pixel i of the group (pixel order 0, 1, 2, 3 = even.lo, odd.lo, even.hi, odd.hi)
-    const uint32_t kDe = (0x1000u - T2) * 0x10001u, kBe = (0x2000u - T2) * 0x10001u, kDo = (0x4000u - T2) * 0x10001u, kBo = (0x8000u - T2) * 0x10001u;
-    uint32_t *cl32 = reinterpret_cast<uint32_t *>(cl);
-    int pending = 0, nScored = 0;
-    for (int base = 0; base < nItems; base += 64) {
-        const int ip = base + lane;
-        const bool live = ip < nItems;
-        const int row = live ? magic_div(ip, Mng) : 0, gi = live ? ip - mul24(row, ng) : 0;
-        const int A = mul24(row + 3, TP) + 4 * (gi + 1);                      // tile offset of the group's first pixel
-        const uint8_t *t = tile + A;
-#define RUMI_DW(off) (*reinterpret_cast<const uint32_t *>(t + (off)))
-        const uint32_t cM3 = RUMI_DW(-3 * TP), cP3 = RUMI_DW(3 * TP);
-        const uint32_t l0 = RUMI_DW(-4), cc = RUMI_DW(0), r0 = RUMI_DW(4);
-        const uint32_t lM2 = RUMI_DW(-2 * TP - 4), cM2 = RUMI_DW(-2 * TP), rM2 = RUMI_DW(-2 * TP + 4);
-        const uint32_t lP2 = RUMI_DW(2 * TP - 4), cP2 = RUMI_DW(2 * TP), rP2 = RUMI_DW(2 * TP + 4);
-#undef RUMI_DW
-        // ring pixels of the (0, 2) pair ("e") and the (1, 3) pair ("o") as 16-bit halves, even circle positions in circular order:
-        // (0,+3) (+2,+2) (+3,0) (+2,-2) (0,-3) (-2,-2) (-3,0) (-2,+2).  v_perm_b32 over {right | centre} or {centre | left} picks a shifted
-        // pair in one instruction; the unshifted ones are an AND / shift + AND.
-        uint32_t pe[8], po[8];
-        pe[0] = cP3 & 0x00FF00FFu;                               po[0] = (cP3 >> 8) & 0x00FF00FFu;
-        pe[1] = __builtin_amdgcn_perm(rP2, cP2, 0x0c040c02u);    po[1] = __builtin_amdgcn_perm(rP2, cP2, 0x0c050c03u);
-        pe[2] = __builtin_amdgcn_perm(r0, cc, 0x0c050c03u);      po[2] = __builtin_amdgcn_perm(r0, cc, 0x0c060c04u);
-        pe[3] = __builtin_amdgcn_perm(rM2, cM2, 0x0c040c02u);    po[3] = __builtin_amdgcn_perm(rM2, cM2, 0x0c050c03u);
-        pe[4] = cM3 & 0x00FF00FFu;                               po[4] = (cM3 >> 8) & 0x00FF00FFu;
-        pe[5] = __builtin_amdgcn_perm(cM2, lM2, 0x0c040c02u);    po[5] = __builtin_amdgcn_perm(cM2, lM2, 0x0c050c03u);
-        pe[6] = __builtin_amdgcn_perm(cc, l0, 0x0c030c01u);      po[6] = __builtin_amdgcn_perm(cc, l0, 0x0c040c02u);
-        pe[7] = __builtin_amdgcn_perm(cP2, lP2, 0x0c040c02u);    po[7] = __builtin_amdgcn_perm(cP2, lP2, 0x0c050c03u);
-        const uint32_t ve = cc & 0x00FF00FFu, vo = (cc >> 8) & 0x00FF00FFu;
-        const uint32_t cDe = ve + kDe, cBe = kBe - ve, cDo = vo + kDo, cBo = kBo - vo;
-        uint32_t f[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-            f[k] = bfi(0x10001000u, cDe - pe[k], bfi(0x20002000u, pe[k] + cBe, bfi(0x40004000u, cDo - po[k], po[k] + cBo)));
-        const uint32_t any = four_consecutive(f);
-        // entry mask: bit 2 i + polarity for pixel i of the group
-        uint32_t m = ((any >> 12) & 0xFu) | ((any >> 24) & 0xF0u);
-        if (gi == ng - 1) m &= mLast;
-        if (!live) m = 0;
-        if (__ballot(m != 0) != 0) {
-            // ring positions: entries of lower lanes first; within a lane pixel by pixel, darker before brighter
-            const int cnt = __popc(m);
-            const int incl = wave_incl_scan(cnt);
-            uint16_t *w = cl + pending + incl - cnt;
-            uint32_t e = (uint32_t)A;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                if (m & (1u << (2 * i))) *w++ = (uint16_t)e;
-                if (m & (2u << (2 * i))) *w++ = (uint16_t)(e | 0x8000u);
-                e++;
-            }
-            pending += __builtin_amdgcn_readlane(incl, 63);
-            int head = 0;
-            while (pending >= 128) {                       // a full batch: score it exactly
-                wave_lds_fence();
-                fast_score_batch<CTP>(tile, sc, sl, nScored, cl + head, 128, tp, scDelta, tlow, lane);
-                head += 128;
-                pending -= 128;
-            }
-            if (head) {                                    // the entries still waiting move to the front (fewer than 128, from beyond them)
-                wave_lds_fence();
-                const uint32_t q = cl32[(head >> 1) + lane];
-                wave_lds_fence();
-                if (2 * lane < pending) cl32[lane] = q;
-            }
-        }
-    }
-    wave_lds_fence();
-    if (pending) fast_score_batch<CTP>(tile, sc, sl, nScored, cl, pending, tp, scDelta, tlow, lane);
-    return nScored;
-}
-
-// ---- quick test, fourth formulation (round 6): bytes, eight pixels a lane ---------------------------------------------------------
-// The same necessary condition as above (4 consecutive of the 8 even circle positions reach contrast T), computed on the pixel bytes as
+// ---- quick test on bytes, eight pixels a lane ---------------------------------------------------------------------------------------
+// The necessary condition above (4 consecutive of the 8 even circle positions reach contrast T), computed on the pixel bytes as
 // they lie in LDS, four pixels per dword, two adjacent dwords (eight pixels) per lane.
 //   Circle dwords: the ring bytes of a 4-pixel group at (0, +-3) are the aligned dword of that row; the others are ONE v_alignbyte_b32 of
 //   two loaded dwords, and the two groups of a lane share the middle one of rows +-2 (10 alignbytes for 16 circle dwords).
@@ -805,9 +686,8 @@ __device__ __forceinline__ void fast_cell_stage(const FastCell &g, uint8_t *tile
     }
 }
 
-// everything after the staging of one cell: score map, NMS, ordered emission.  LEGACY: the round-3 quick test (fast_score_cell) instead of
-// the byte formulation (fast_score_cell_bytes); both fill the ring with the same entries in the same order
-template <int TPC, bool LEGACY>
+// everything after the staging of one cell: score map, NMS, ordered emission
+template <int TPC>
 __device__ __forceinline__ void fast_cell_process(const DevParams *__restrict__ P, const FastLds &F, const FastCell &g, uint8_t *tile, uint8_t *sc,
                                                   uint32_t *__restrict__ cellBuf, int32_t *__restrict__ cellCnt, int lane) {
     const int TP = TPC ? TPC : F.tp;
@@ -828,8 +708,7 @@ __device__ __forceinline__ void fast_cell_process(const DevParams *__restrict__ 
     int found;
 #pragma nounroll
     for (int pass = 0;; pass++) {
-        const int nScored = LEGACY ? fast_score_cell<TPC>(tile, sc, cl, sl, TP, dw, dh, thr, lane)
-                                   : fast_score_cell_bytes<TPC>(tile, sc, cl, sl, TP, dw, dh, thr, lane);
+        const int nScored = fast_score_cell_bytes<TPC>(tile, sc, cl, sl, TP, dw, dh, thr, lane);
         wave_lds_fence();
         // NMS + emission in one sweep over the scored list (ascending pixel order = the row-major order cv::FAST emits in; every pixel at
         // most once); a cell with more than kScoredCap scored pixels scans its whole score map instead.  Two items per lane and sweep, all
@@ -884,7 +763,7 @@ __device__ __forceinline__ void fast_cell_process(const DevParams *__restrict__ 
 // TPC: tile pitch (= score-map pitch) as a compile-time constant: the circle offsets and the NMS neighbours then are immediate LDS
 // offsets instead of one address add each; 0 = run-time
 // (bx, gx): the workgroup's column and the columns of the FAST part of the launch (the whole grid, or its first gx columns in the fused launch)
-template <int TPC, bool LEGACY>
+template <int TPC>
 __device__ __forceinline__ void fast_cells_body(const DevParams *__restrict__ P, const ImgSrc &src, const FastLds &F, uint32_t *__restrict__ cellBuf,
                                                 int32_t *__restrict__ cellCnt, unsigned bx, unsigned gx) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fl[];
@@ -899,12 +778,12 @@ __device__ __forceinline__ void fast_cells_body(const DevParams *__restrict__ P,
     const FastCell gA = fast_cell_geom(P, src, cell, frame, cellCnt, lane);
     if (!gA.live) return;
     fast_cell_stage<TPC>(gA, tile, TP, lane);
-    fast_cell_process<TPC, LEGACY>(P, F, gA, tile, sc, cellBuf, cellCnt, lane);
+    fast_cell_process<TPC>(P, F, gA, tile, sc, cellBuf, cellCnt, lane);
 }
-template <int TPC, bool LEGACY>
+template <int TPC>
 __global__ __launch_bounds__(256) void k_fast_cells(const DevParams *__restrict__ P, ImgSrc src, FastLds F,
                                                     uint32_t *__restrict__ cellBuf, int32_t *__restrict__ cellCnt) {
-    fast_cells_body<TPC, LEGACY>(P, src, F, cellBuf, cellCnt, blockIdx.x, gridDim.x);
+    fast_cells_body<TPC>(P, src, F, cellBuf, cellCnt, blockIdx.x, gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1136,10 +1015,10 @@ __global__ __launch_bounds__(256) void k_blur(const DevParams *__restrict__ P, I
 // A few frames (the Tracking thread's call): FAST and the blur in ONE launch, the first gxFast workgroup columns FAST cells, the rest blur strips.
 // Both only read the pyramid; as two launches the blur goes to a side stream, and the event that forks it stalls the main queue for ~20 us on
 // this runtime (and the join for ~5): more than the blur takes.
-template <int TPC, int VARIANT, bool LEGACY>
+template <int TPC, int VARIANT>
 __global__ __launch_bounds__(256) void k_fast_blur(const DevParams *__restrict__ P, ImgSrc src, FastLds F, uint32_t *__restrict__ cellBuf,
                                                    int32_t *__restrict__ cellCnt, BlurGrid G, unsigned gxFast) {
-    if (blockIdx.x < gxFast) fast_cells_body<TPC, LEGACY>(P, src, F, cellBuf, cellCnt, blockIdx.x, gxFast);
+    if (blockIdx.x < gxFast) fast_cells_body<TPC>(P, src, F, cellBuf, cellCnt, blockIdx.x, gxFast);
     else blur_body<VARIANT, kBlurRowsSmall>(P, src, G, blockIdx.x - gxFast, gridDim.x - gxFast);
 }
 
@@ -1438,15 +1317,14 @@ __global__ __launch_bounds__(256, 7) void k_orient_desc(const DevParams *__restr
 // ---- launch wrappers (called from orb_host.hip) ----
 void launch_resize(const DevParams *dP, const DevParams &hP, ImgSrc src, const int16_t *coef, const RowTap *rowTab, int level, int nframes,
                    hipStream_t st, int32_t *clearWord) {
-    static const int envRows = std::getenv("RUMI_RESIZE_ROWS") ? std::atoi(std::getenv("RUMI_RESIZE_ROWS")) : 0;
-    const int rows = envRows ? envRows : (hP.lv[level].h >= 200 ? 8 : 4);
+    const int rows = hP.lv[level].h >= 200 ? 8 : 4;
     dim3 g((hP.lv[level].w + 255) / 256, (hP.lv[level].h + 4 * rows - 1) / (4 * rows), nframes);
     if (rows == 8) hipLaunchKernelGGL(k_resize<8>, g, dim3(256), 0, st, dP, src, coef, rowTab, level, clearWord);
     else hipLaunchKernelGGL(k_resize<4>, g, dim3(256), 0, st, dP, src, coef, rowTab, level, clearWord);
 }
 void launch_pyramid_tiles(const DevParams *dP, ImgSrc src, const int16_t *coef, const RowTap *rowTab, const PyrTile *tiles, int ntiles, int bufBytes,
-                          int tabEntries, int nframes, hipStream_t st, int32_t *clearWord, bool copyL0) {
-    hipLaunchKernelGGL(k_pyramid_tiles, dim3(ntiles, nframes), dim3(256), (size_t)2 * bufBytes + (size_t)tabEntries * 8, st, dP, src, coef, rowTab, tiles, bufBytes, clearWord, copyL0 ? 1 : 0);
+                          int tabEntries, int nframes, hipStream_t st, int32_t *clearWord) {
+    hipLaunchKernelGGL(k_pyramid_tiles, dim3(ntiles, nframes), dim3(256), (size_t)2 * bufBytes + (size_t)tabEntries * 8, st, dP, src, coef, rowTab, tiles, bufBytes, clearWord);
 }
 static FastLds fast_lds_of(const DevParams &hP) {
     // LDS per wave from the largest cell of this geometry
@@ -1464,37 +1342,26 @@ static FastLds fast_lds_of(const DevParams &hP) {
     F.perWave = (F.tileBytes + F.scBytes + std::max(kRingCap * 2, F.maxIters * 8) + kScoredCap * 2 + 15) & ~15;
     return F;
 }
-// RUMI_FAST_LEGACY=1: the round-3 quick test in place of the byte formulation (A/B measurements and tests in one build; same results)
-static bool fast_legacy() {
-    static const bool legacy = std::getenv("RUMI_FAST_LEGACY") && std::atoi(std::getenv("RUMI_FAST_LEGACY")) != 0;
-    return legacy;
-}
 void launch_fast(const DevParams *dP, const DevParams &hP, ImgSrc src, uint32_t *cellBuf, int32_t *cellCnt, int nframes,
                  hipStream_t st) {
     const FastLds F = fast_lds_of(hP);
-    const bool legacy = fast_legacy();
     // tile pitches of the common image sizes as compile-time constants (cells up to 36 / 40 / 44 / 48 pixels wide: 44 / 48 / 52 / 56);
     // anything else takes the run-time instantiation
     const int wpg = 4;                                    // cells (= waves) per workgroup
     const dim3 grid((hP.totalCells + wpg - 1) / wpg, nframes);
     const size_t lds = (size_t)wpg * F.perWave;
-#define RUMI_FAST_CASE(T)                                                                                                  \
-    if (F.tp == T) {                                                                                                       \
-        if (legacy) hipLaunchKernelGGL((k_fast_cells<T, true>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt);  \
-        else hipLaunchKernelGGL((k_fast_cells<T, false>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt);        \
-        return;                                                                                                            \
+#define RUMI_FAST_CASE(T)                                                                                      \
+    if (F.tp == T) {                                                                                           \
+        hipLaunchKernelGGL((k_fast_cells<T>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt);    \
+        return;                                                                                                \
     }
     RUMI_FAST_CASE(48) RUMI_FAST_CASE(44) RUMI_FAST_CASE(52) RUMI_FAST_CASE(56)
 #undef RUMI_FAST_CASE
-    if (legacy) hipLaunchKernelGGL((k_fast_cells<0, true>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt);
-    else hipLaunchKernelGGL((k_fast_cells<0, false>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt);
+    hipLaunchKernelGGL((k_fast_cells<0>), grid, dim3(64 * wpg), lds, st, dP, src, F, cellBuf, cellCnt);
 }
 // workgroups per frame (each repeats the cheap scan and copies its share of the outputs: the copy is a chain of dependent LDS reads per
 // element, so one workgroup per frame is ~40 us of latency whatever the batch)
-static int compactSlices(int nframes) {
-    static const int env = std::getenv("RUMI_COMPACT_SLICES") ? std::atoi(std::getenv("RUMI_COMPACT_SLICES")) : 0;
-    return env > 0 ? env : (nframes < 32 ? 32 : 8);
-}
+static int compactSlices(int nframes) { return nframes < 32 ? 32 : 8; }
 void launch_compact(const DevParams *dP, const DevParams &hP, const uint32_t *cellBuf, const int32_t *cellCnt,
                     uint32_t *cand, int32_t *levelStart, int32_t *errFlag, int nframes, hipStream_t st) {
     hipLaunchKernelGGL(k_compact, dim3(nframes, compactSlices(nframes)), dim3(kCompactThreads), (hP.totalCells + 1) * sizeof(int), st, dP, cellBuf, cellCnt,
@@ -1536,11 +1403,8 @@ bool launch_fast_blur(const DevParams *dP, const DevParams &hP, ImgSrc src, uint
     const unsigned gxFast = (unsigned)((hP.totalCells + wpg - 1) / wpg);
     const dim3 grid(gxFast + (unsigned)run, nframes);
     const size_t lds = (size_t)wpg * F.perWave;
-    const bool legacy = fast_legacy();
-    if (variant && legacy) hipLaunchKernelGGL((k_fast_blur<48, 1, true>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
-    else if (variant) hipLaunchKernelGGL((k_fast_blur<48, 1, false>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
-    else if (legacy) hipLaunchKernelGGL((k_fast_blur<48, 0, true>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
-    else hipLaunchKernelGGL((k_fast_blur<48, 0, false>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
+    if (variant) hipLaunchKernelGGL((k_fast_blur<48, 1>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
+    else hipLaunchKernelGGL((k_fast_blur<48, 0>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
     return true;
 }
 void launch_blur(const DevParams *dP, const DevParams &hP, ImgSrc src, int nframes, int variant, hipStream_t st) {

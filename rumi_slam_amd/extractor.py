@@ -150,7 +150,7 @@ class ORBextractor:
         desc = torch.empty((B, cap, 32), dtype=torch.uint8, device=dev)
         counts = torch.zeros((B, 2), dtype=torch.int32, device=dev)
         hk = hd = hc = None
-        if to_host == "pinned":             # pinned host arrays (with RUMI_ORB_MIRROR=2 every sub-chunk's rows come back behind its kernels; measured slower)
+        if to_host == "pinned":             # pinned host arrays (copied back once at the end of the call, like pageable ones)
             hk = torch.zeros((B, cap, 28), dtype=torch.uint8).pin_memory().numpy().view(KP_DTYPE).reshape(B, cap)
             hd, hc = torch.zeros((B, cap, 32), dtype=torch.uint8).pin_memory().numpy(), torch.zeros((B, 2), dtype=torch.int32).pin_memory().numpy()
         elif to_host:

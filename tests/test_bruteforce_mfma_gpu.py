@@ -1,10 +1,6 @@
 """The brute-force matcher on the int8 matrix cores (k_bruteforce_mfma) against the CPU oracle, bit for bit on best index, best
 distance and second distance: every tile edge, ties across lane halves and train tiles, single-bit descriptors (a wrong MFMA fragment
-map shows up as wrong distances), strided and ring layouts at 4 and 8 mod 16, extractor output, and the VALU kernel (RUMI_BF_VALU=1)."""
-import os
-import subprocess
-import sys
-
+map shows up as wrong distances), strided and ring layouts at 4 and 8 mod 16, extractor output, and near-ties in seeded batches."""
 import numpy as np
 import pytest
 
@@ -12,7 +8,6 @@ import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = [0, 1, 31, 32, 33, 255, 256, 257, 1000, 1096]
 
 
@@ -147,30 +142,22 @@ def test_ring_on_extractor_records():
     assert (rd[1, :int(c[1, 0])] < 40).sum() > 300
 
 
-_CHILD = r"""
-import sys, numpy as np, torch
-sys.path.insert(0, sys.argv[1])
-from rumi_slam_amd.matcher import bruteforce_batch, bruteforce_ring
-rng = np.random.default_rng(23)
-q = torch.from_numpy(rng.integers(0, 256, (6, 1096, 32), dtype=np.uint8)).cuda()
-t = q.clone(); t[:, ::3] ^= torch.from_numpy(rng.integers(0, 4, (6, 366, 32), dtype=np.uint8)).cuda()
-c = torch.from_numpy(np.stack([[1096, 1000, 0, 33, 257, 1005], [0] * 6], 1).astype(np.int32)).cuda()
-out = [x.cpu().numpy() for x in bruteforce_batch(q, c, t, c.flip(0).contiguous())] + [x.cpu().numpy() for x in bruteforce_ring(t, c)]
-np.savez(sys.argv[2], *out)
-"""
-
-
-def test_valu_switch_matches_default(tmp_path):
-    """RUMI_BF_VALU=1 (read once per process) selects the VALU kernel: one fresh child per path on the same seeded inputs, array for array."""
-    res = {}
-    for tag, valu in (("mfma", None), ("valu", "1")):
-        env = dict(os.environ)
-        env.pop("RUMI_BF_VALU", None)
-        if valu:
-            env["RUMI_BF_VALU"] = valu
-        path = str(tmp_path / (tag + ".npz"))
-        subprocess.run([sys.executable, "-c", _CHILD, ROOT, path], env=env, check=True, timeout=300)
-        z = np.load(path)
-        res[tag] = [z["arr_%d" % i] for i in range(6)]
-    for a, b in zip(res["mfma"], res["valu"]):
-        assert a.shape == b.shape and np.array_equal(a, b)
+def test_seeded_batch_and_ring_vs_oracle():
+    """Six frames of 1096 descriptors, every third train a few bits from its query (near-ties), counts (1096, 1000, 0, 33, 257, 1005)
+    against the flipped counts, and the ring launch over the trains."""
+    import torch
+    from rumi_slam_amd.matcher import bruteforce_ring
+    rng = np.random.default_rng(23)
+    q = rng.integers(0, 256, (6, 1096, 32), dtype=np.uint8)
+    t = q.copy()
+    t[:, ::3] ^= rng.integers(0, 4, (6, 366, 32), dtype=np.uint8)
+    c = _counts([1096, 1000, 0, 33, 257, 1005])
+    ct = np.ascontiguousarray(c[::-1])
+    got = _run_batch(q, c, t, ct)
+    for b in range(6):
+        _check([g[b] for g in got], q[b], int(c[b, 0]), t[b], int(ct[b, 0]), ("batch", b))
+    ri, rd, rs = [x.cpu().numpy() for x in bruteforce_ring(torch.from_numpy(t).cuda(), torch.from_numpy(c).cuda())]
+    torch.cuda.synchronize()
+    for b in range(6):
+        tb = (b + 1) % 6
+        _check((ri[b], rd[b], rs[b]), t[b], int(c[b, 0]), t[tb], int(c[tb, 0]), ("ring", b))

@@ -454,21 +454,30 @@ def test_threshold_pairs(ini, mn):
 
 
 @pytest.mark.gpu
-def test_one_launch_pyramid_equals_the_launch_per_level_chain(tmp_path):
+def test_one_launch_pyramid_equals_the_chain_on_padded_frames():
     """Calls of up to 4 frames compute the whole pyramid in one launch (k_pyramid_tiles: tiles of the top level, their regions of every level in
-    LDS); the chain of one launch per level must produce the same bytes: 9 geometries (sizes, scale factors 1.1 / 1.2 / 1.5, 2 to 8 levels), calls
-    of 1 and 3 frames, every level of every frame (tools/pyramid_tiles_check.py, once per path: the switch is read once per process)."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dumps = []
-    for tiles in ("0", "1"):
-        out = str(tmp_path / f"tiles{tiles}.npz")
-        subprocess.run([sys.executable, os.path.join(root, "tools", "pyramid_tiles_check.py"), out], check=True, env=dict(os.environ, RUMI_PYRAMID_TILES=tiles), timeout=600)
-        dumps.append(np.load(out))
-    a, b = dumps
-    assert set(a.files) == set(b.files) and len(a.files) > 150
-    bad = [k for k in a.files if not np.array_equal(a[k], b[k])]
-    assert not bad, f"levels differ: {bad[:8]}"
+    LDS); calls of 5 frames and more take the chain of one launch per level, which must produce the same bytes: 9 geometries (sizes, scale
+    factors 1.1 / 1.2 / 1.5, 2 to 8 levels), calls of 1 and 3 frames against the same frames padded to 5, every level of every real frame."""
+    import torch
+    from rumi_slam_amd.extractor import ORBextractor
+    rng = np.random.default_rng(11)
+    checked = 0
+    for (w, h, sf, nl) in ((640, 480, 1.2, 8), (752, 480, 1.2, 8), (600, 350, 1.2, 8), (320, 240, 1.2, 8), (641, 479, 1.2, 8), (640, 480, 1.1, 8),
+                           (640, 480, 1.5, 5), (1280, 720, 1.2, 8), (640, 480, 1.2, 2)):
+        for nb in (1, 3):
+            coarse = rng.integers(0, 256, (nb, h // 16 + 1, w // 16 + 1)).astype(np.int32)      # blocks of 16 x 16 plus a little noise: every byte matters to the resize, few corners
+            frames = np.clip(np.kron(coarse, np.ones((16, 16), np.int32))[:, :h, :w] + rng.integers(-3, 4, (nb, h, w)), 0, 255).astype(np.uint8)
+            padded = np.concatenate([frames, np.repeat(frames[:1], 5 - nb, 0)])
+            ext = ORBextractor(500, sf, nl, 20, 7, max_width=w, max_height=h, max_batch=5)
+            levels = []
+            for batch in (frames, padded):
+                ext.extract_batch(torch.from_numpy(batch).cuda(), (0, 1000))
+                levels.append([ext.pyramid_level(l, frame=f) for f in range(nb) for l in range(1, nl)])
+            tiles, chain = levels
+            for i, (a, b) in enumerate(zip(tiles, chain)):
+                assert np.array_equal(a, b), f"{w}x{h} sf {sf} nl {nl}, {nb} frames: level {1 + i % (nl - 1)} of frame {i // (nl - 1)} differs"
+            checked += len(tiles)
+    assert checked > 150
 
 
 @pytest.mark.gpu

@@ -1,14 +1,10 @@
-"""k_fast_cells' byte quick test (fast_score_cell_bytes, eight pixels a lane) against the CPU oracle and against the round-3 quick test
-(RUMI_FAST_LEGACY=1): candidate lists per level, key-points, descriptors.  Frames made to hit the edges of the byte arithmetic: centres
+"""k_fast_cells' byte quick test (fast_score_cell_bytes, eight pixels a lane) against the CPU oracle: candidate lists per level,
+key-points, descriptors.  Frames made to hit the edges of the byte arithmetic: centres
 near 0 and 255 (v +- T saturates), circle contrasts of exactly T and T + 1 (strict inequalities), dense noise, a ramp on which nearly
 every pixel passes the quick test in BOTH polarities (a 64-item step then appends more entries than the ring holds: the two-halves
 append; tests/test_fast_bytes_cpu.py counts on the CPU that its steps exceed the ring), featureless and saturated frames; thresholds (1, 1), (20, 7),
 (254, 1); 640 x 480 (cell widths 26-40, most not multiples of 8; one-frame calls and batches of fewer than 16 frames take the fused
 FAST + blur launch k_fast_blur, batches of 16 and more k_fast_cells) and 320 x 240 (tile pitch 68: the run-time-pitch instantiation)."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -17,7 +13,6 @@ from rumi_slam_amd.synth import synth_frame
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THRESHOLDS = [(1, 1), (20, 7), (254, 1)]
 KINDS = ["saturating", "contrast_t", "noise", "ramp", "synth", "flat", "white", "black"]
 RING_CAP = 640                        # kRingCap of orb_kernels.hip: entries the linear ring holds
@@ -87,8 +82,8 @@ def test_one_frame_vs_oracle(kind, ini, mn):
     _single(ini, mn, kind, 640, 480)
 
 
-@pytest.mark.parametrize("ini,mn", [(20, 7), (1, 1)])
-@pytest.mark.parametrize("kind", ["saturating", "contrast_t", "noise", "synth"])
+@pytest.mark.parametrize("ini,mn", THRESHOLDS)
+@pytest.mark.parametrize("kind", KINDS)
 def test_runtime_pitch_vs_oracle(kind, ini, mn):
     """320 x 240: the largest cell is 57 pixels wide, tile pitch 68, not one of the compile-time pitches."""
     _single(ini, mn, kind, 320, 240)
@@ -175,42 +170,3 @@ def test_split_append_vs_oracle():
     for f in range(16):
         _same(out[f], o.extract(frames[f], (0, 1000)), f"ramp batch frame {f}")
 
-
-def all_outputs():
-    """every case of this file on the current path, as one list of byte strings (for the A/B child processes)"""
-    res = []
-    for ini, mn in THRESHOLDS:
-        for w, h in ((640, 480), (320, 240)):
-            for kind in KINDS:
-                g, _ = _extractors(ini, mn, w, h)
-                m, k, d = g(make_frame(kind, w, h, seed=ini), None, (0, 1000))
-                res.append(np.int64(m).tobytes() + k.tobytes() + d.tobytes())
-                res.extend(g.stage_keypoints(l, 0).tobytes() for l in range(8))
-        _, out, _ = _batch_outputs(ini, mn, BATCH_KINDS)
-        res.extend(np.int64(m).tobytes() + k.tobytes() + d.tobytes() for m, k, d in out)
-    return res
-
-
-_CHILD = r"""
-import pickle, sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import test_fast_bytes_gpu as T
-pickle.dump(T.all_outputs(), open(sys.argv[2], "wb"))
-"""
-
-
-def test_legacy_switch_matches_default(tmp_path):
-    """RUMI_FAST_LEGACY=1 (read once per process) selects the round-3 quick test: one fresh child per path, every case byte for byte."""
-    import pickle
-    res = {}
-    for tag, legacy in (("bytes", None), ("legacy", "1")):
-        env = dict(os.environ)
-        env.pop("RUMI_FAST_LEGACY", None)
-        if legacy:
-            env["RUMI_FAST_LEGACY"] = legacy
-        path = str(tmp_path / (tag + ".pkl"))
-        subprocess.run([sys.executable, "-c", _CHILD, ROOT, path], env=env, check=True, timeout=600)
-        res[tag] = pickle.load(open(path, "rb"))
-    assert len(res["bytes"]) == len(res["legacy"])
-    bad = [i for i, (a, b) in enumerate(zip(res["bytes"], res["legacy"])) if a != b]
-    assert not bad, f"cases differ between the paths: {bad[:10]}"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Frames per second of device-resident extract (+ match) at small batch sizes: back-to-back asynchronous calls, one final sync.
-usage: batch_probe.py [nb ...]   (env: RUMI_PARTS, RUMI_SUBMAX)"""
+usage: batch_probe.py [nb ...]   (env: RUMI_RESIDENT)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -47,4 +47,4 @@ for nb in sizes:
             ext.sync(); torch.cuda.synchronize()
             best = max(best, nb * reps / (time.perf_counter() - t0))
         res[(nb, withm)] = best
-print("PARTS", os.environ.get("RUMI_PARTS"), "SUBMAX", os.environ.get("RUMI_SUBMAX"), "RESIDENT", os.environ.get("RUMI_RESIDENT"), " ".join(f"{nb}{'ems'[m]}={v/1e3:.1f}k" for (nb, m), v in res.items()))
+print("RESIDENT", os.environ.get("RUMI_RESIDENT"), " ".join(f"{nb}{'ems'[m]}={v/1e3:.1f}k" for (nb, m), v in res.items()))
