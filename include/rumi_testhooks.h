@@ -29,6 +29,13 @@ float rumi_hook_fast_atan2(float y, float x);   /* cv::fastAtan2, degrees */
 int rumi_hook_cv_round(float v);         /* cvRound */
 int rumi_hook_magic_div(int32_t idx, int32_t d);   /* divide-free idx / d used by the FAST cell kernel (orb_geom.h) */
 
+/* Stages 1 + 3 of the last rumi_create_new_map_points call on this matcher (rumi_mapping.h; needs a device): per neighbour k and feature i1 of
+ * the current key-frame, matches[k * n1 + i1] = the neighbour's feature SearchForTriangulation pairs it with when the loop reaches neighbour k
+ * (after the rotation histogram, before the triangulation gates), -1 = none.  n_neigh and n1 must be those of that call.  The call itself does
+ * not record this: the hook runs the replay kernel once more on the state the call left on the device. */
+struct RumiMatcher;
+int rumi_hook_newpts_matches(struct RumiMatcher *m, int32_t n_neigh, int32_t n1, int32_t *matches);
+
 #ifdef __cplusplus
 }
 #endif

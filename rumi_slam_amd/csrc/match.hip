@@ -23,6 +23,7 @@
 #include "rumi_internal.h"
 #include "rumi_common.h"
 #include "rumi_match.h"
+#include "match_device.h"
 
 namespace rumi {
 
@@ -51,22 +52,6 @@ struct FrameDev {
     const uint16_t *sortedIdx;   // features sorted by (cell, index)
     const int32_t *cellStart;    // [kGridCells + 1]
 };
-
-__device__ __forceinline__ int hamming256(const uint32_t q[8], const uint32_t *d) {
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) s += __popc(q[k] ^ d[k]);
-    return s;
-}
-
-// inclusive prefix sum over the lanes of a wave by DPP (row prefix, row_bcast:15, row_bcast:31); lane 63 holds the total
-__device__ __forceinline__ int wave_scan_incl_i32(int v) {
-#define RUMI_DPP_ADD(ctl, rows) v += __builtin_amdgcn_update_dpp(0, v, ctl, rows, 0xf, false)
-    RUMI_DPP_ADD(0x111, 0xf); RUMI_DPP_ADD(0x112, 0xf); RUMI_DPP_ADD(0x114, 0xf); RUMI_DPP_ADD(0x118, 0xf);
-    RUMI_DPP_ADD(0x142, 0xa); RUMI_DPP_ADD(0x143, 0xc);
-#undef RUMI_DPP_ADD
-    return v;
-}
 
 // ---- 1. grid -----------------------------------------------------------------------------------------------
 // Frame::AssignFeaturesToGrid as a counting sort by cell (cell = column-major ix*48+iy, the order GetFeaturesInArea walks),
@@ -664,15 +649,6 @@ struct ResolveArgs {
     int32_t *gIdx, *gStart, *gSnapshot;
 };
 
-__device__ __forceinline__ int rot_bin(float a, float b) {          // ORBmatcher.cc:1592-1599
-    const float factor = 1.0f / RUMI_HISTO_LENGTH;
-    float rot = a - b;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)__builtin_roundf(rot * factor);
-    if (bin == RUMI_HISTO_LENGTH) bin = 0;
-    return bin;
-}
-
 // Correspondences of Optimizer::PoseOptimization(Frame*) (Optimizer.cc:749-815, mono): the features with a map point, in feature order.
 // One workgroup of 1024 threads, ordered compaction (ballot + wave offsets through LDS, chunks of 1024 features).
 __device__ __forceinline__ void gather_correspondences(int n, const RumiKeyPoint *__restrict__ keys, const int32_t *featMp, const float *__restrict__ mpPos,
@@ -703,16 +679,6 @@ __device__ __forceinline__ void gather_correspondences(int n, const RumiKeyPoint
     }
     if (tid == 0) { start[0] = 0; start[1] = *sBase; }
 }
-
-// wave-wide maximum / sum of one 32-bit value by DPP (row prefix, row_bcast:15, row_bcast:31; the total sits in lane 63)
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#define RUMI_DPP_MAX(ctl, rows) v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctl, rows, 0xf, false))
-    RUMI_DPP_MAX(0x111, 0xf); RUMI_DPP_MAX(0x112, 0xf); RUMI_DPP_MAX(0x114, 0xf); RUMI_DPP_MAX(0x118, 0xf);
-    RUMI_DPP_MAX(0x142, 0xa); RUMI_DPP_MAX(0x143, 0xc);
-#undef RUMI_DPP_MAX
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ int wave_sum_i32(int v) { return __builtin_amdgcn_readlane(wave_scan_incl_i32(v), 63); }
 
 // One workgroup iterates "every query picks its best candidate among the features no EARLIER query holds" to its fixed point (the
 // result of the reference's sequential loop).  A round is latency, not work: what a round needs of a query -- count, the head of its
@@ -1358,8 +1324,16 @@ struct RumiMatcher {
     hipStream_t upStream = nullptr;        // where the next flush queues its copy and scatter (the caller orders its kernels behind them)
     bool gridPending = false; int gridN = 0; float gridMinX = 0, gridMinY = 0, gridWInv = 0, gridHInv = 0;
     const RumiKeyPoint *gridKeys = nullptr;      // key-points k_grid reads: dKeys, or a frame that already lies on the device (rumi_track_frame)
+    MatcherExt ext;                        // arenas of rumi_create_new_map_points (mapping.hip), released with the matcher
 };
 constexpr size_t kStageHeader = kMaxSegments * sizeof(Segment);
+
+namespace rumi {
+MatcherExt *matcher_ext(RumiMatcher *m, int *device, int *maxFeatures, int *maxQueries) {
+    *device = m->device; *maxFeatures = m->maxFeat; *maxQueries = m->maxQ;
+    return &m->ext;
+}
+}  // namespace rumi
 
 extern "C" int rumi_descriptor_distance(const uint8_t *a, const uint8_t *b) {
     uint64_t x[4], y[4];
@@ -1371,6 +1345,7 @@ extern "C" int rumi_descriptor_distance(const uint8_t *a, const uint8_t *b) {
 extern "C" void rumi_match_destroy(RumiMatcher *m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
+    if (m->ext.state && m->ext.destroy) m->ext.destroy(m->ext.state);
     void *p[] = {m->dKeys, m->dDesc, m->dScale, m->dSorted, m->dCellStart, m->dFvIdx, m->dQ, m->dQDesc, m->dCounts,
                  m->dOffsets, m->dLists, m->dOut, m->dU8a, m->dU8b, m->dF[0], m->dF[1], m->dF[2], m->dF[3],
                  m->dF[4], m->dF[5], m->dI[0], m->dI[1], m->dI[2], m->dI[3], m->dQKeys, m->dNodesA, m->dNodesB, m->dIdxA,

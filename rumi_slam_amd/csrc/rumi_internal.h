@@ -4,6 +4,7 @@
 #include <cstdint>
 
 typedef struct RumiVocabulary RumiVocabulary;
+typedef struct RumiMatcher RumiMatcher;
 
 namespace rumi {
 
@@ -20,5 +21,10 @@ int pose_opt_device(const int32_t *dStart, const float *dXw, const float *dObs, 
 
 // Device, word count and the header's weighting / scoring types of a vocabulary (voc.hip), for the key-frame database (kfdb.hip).
 void voc_params(const RumiVocabulary *v, int *device, int *nWords, int *weighting, int *scoring);
+
+// What another translation unit hangs on a RumiMatcher (match.hip): mapping.hip keeps the blocks of rumi_create_new_map_points here, so that they
+// live and die with the handle.  matcher_ext also reports the handle's device and the capacities it was created with.
+struct MatcherExt { void *state = nullptr; void (*destroy)(void *) = nullptr; };
+MatcherExt *matcher_ext(RumiMatcher *m, int *device, int *maxFeatures, int *maxQueries);
 
 }  // namespace rumi
