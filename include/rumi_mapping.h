@@ -7,6 +7,7 @@
  *   R/lib_src/KeyFrame.cc:947-978         KeyFrame::ComputeSceneMedianDepth(2)
  *   R/lib_src/GeometricTools.cc:47-66     GeometricTools::Triangulate
  *   R/lib_src/CameraModels/Pinhole.cpp:30-33,61-64   Pinhole::project / unprojectEig
+ *   R/lib_src/MapPoint.cc:353-427, 450-518   MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth (rumi_refresh_map_points, below)
  *
  * One call runs the whole neighbour loop: every neighbour's search, triangulation and gates in wide launches, then the only
  * order-dependent part (a feature that received a point from neighbour k is skipped for neighbour k + 1, ORBmatcher.cc:865) in
@@ -84,6 +85,79 @@ typedef struct RumiNewPoint {
 int rumi_create_new_map_points(RumiMatcher *m, const RumiNewPointsKF *cur, const RumiNewPointsKF *neigh, int32_t n_neigh,
                                const RumiNewPointsParams *p, RumiNewPoint *out, int32_t cap, int32_t *n_out,
                                int32_t *per_neigh_out, uint8_t *neigh_skipped_out);
+
+/* ---- MapPoint::ComputeDistinctiveDescriptors (R/lib_src/MapPoint.cc:353-427) and MapPoint::UpdateNormalAndDepth (:450-518) for a batch of
+ * points.  Neither member reads another MapPoint: a point's result depends on its own observation list, its position and reference
+ * key-frame, and the observing key-frames' descriptors, camera centres, bad flags and scale tables.  So the per-point calls a map-changing
+ * step ends with can be collected and issued as one call.  Monocular only: an observation carries a left index, so the right-camera branches
+ * (:383-385, 484-489, 501-506) cannot be asked for.
+ *
+ * Descriptor (RUMI_REFRESH_DESCRIPTOR).  Observations whose key-frame is bad are dropped (:376); N = the rest, in the caller's order.
+ * d[i][j] = Hamming distance of the 256-bit rows, d[i][i] = 0.  The median of row i is the element of rank (N-1)/2 of the ascending row,
+ * its own zero included (`vDists[0.5*(N-1)]`, :414, truncates).  The winner is the first i whose median is strictly smaller than all
+ * before it (:416).  best_obs is its position in the point's own observation list (the dropped entries count), best_median its median; both
+ * are -1 where the reference returns without writing (:367, :389: no observation, or every observing key-frame bad).
+ *
+ * Normal and depth (RUMI_REFRESH_NORMAL_DEPTH).  Bad key-frames are NOT dropped here (:471-490 has no isBad test).
+ * normal = sum over the list, in list order, of (Pos - Ow_i) / |Pos - Ow_i|, then divided by (float)n; dist = |Pos - Ow_ref|;
+ * max_distance = dist * scale[ref_level] (:514); min_distance = max_distance / scale[nLevels - 1] (:515).  updated = 0 and nothing else
+ * written where the reference returns early (:465, no observation).
+ * Parity with `Eigen::Vector3f::norm()` unpinned: Eigen is not available to this project's oracle, so the float evaluation order is DEFINED
+ * here and by tests/cpp/refresh_oracle.cc: differences per component, squared norm as (x*x + y*y) + z*z, IEEE sqrtf, true division per
+ * component (no reciprocal), no FMA contraction, all in float.
+ *
+ * The order of a point's observations decides the tie between equal medians and the order of the float sums.  The reference iterates a
+ * std::map<KeyFrame*, ...>, i.e. pointer order; the caller, who owns the pointers, supplies the pairs in that order. */
+#define RUMI_REFRESH_DESCRIPTOR 1
+#define RUMI_REFRESH_NORMAL_DEPTH 2
+/* Observations of one point (the whole list, bad key-frames included).  The reference has no cap; a point above this one makes the call
+ * return RUMI_E_CAPACITY with nothing written, never a truncated answer. */
+#define RUMI_REFRESH_MAX_OBS 2048
+
+/* What the two members read of a key-frame; each key-frame of the call once. */
+typedef struct RumiRefreshKF {
+    const uint8_t *desc;          /* mDescriptors, [n][32]; may be NULL without RUMI_REFRESH_DESCRIPTOR */
+    int32_t n;                    /* N */
+    int32_t nlevels;              /* mnScaleLevels */
+    const float *scale_factors;   /* mvScaleFactors, [nlevels] */
+    float Ow[3];                  /* GetCameraCenter() */
+    uint8_t is_bad;               /* isBad() */
+    uint8_t pad_[3];
+} RumiRefreshKF;
+
+typedef struct RumiRefreshPoint {
+    float pos[3];                 /* GetWorldPos() */
+    int32_t ref_kf;               /* GetReferenceKeyFrame(), index into the key-frame table */
+    int32_t ref_feature;          /* the left index `observations[pRefKF]` yields (:495; 0 where the map has no such entry) */
+    int32_t ref_level;            /* pRefKF->mvKeysUn[ref_feature].octave (:499) */
+    int32_t obs_begin, obs_end;   /* the point's observations: entries obs_begin .. obs_end - 1 of obs_kf / obs_feature */
+} RumiRefreshPoint;
+
+typedef struct RumiRefresh RumiRefresh;
+
+/* A handle owns the pinned upload block, the device blocks and the result block of its calls (grown on demand); not re-entrant, one per
+ * calling thread.  device < 0: the current one.  Creation does not touch the device; the first call with work does. */
+int rumi_refresh_create(int32_t device, RumiRefresh **out);
+void rumi_refresh_destroy(RumiRefresh *r);
+
+/* One batch.  kf [n_kf], pts [n_pts], obs_kf / obs_feature [n_obs] (key-frame index and feature index of every observation, the points'
+ * slices in any order and possibly sharing entries).  `what` = RUMI_REFRESH_DESCRIPTOR | RUMI_REFRESH_NORMAL_DEPTH, at least one.
+ * Outputs, one entry per point; the arrays of a mode that was not asked for are not touched and may be NULL:
+ *   best_obs, best_median [n_pts]                         RUMI_REFRESH_DESCRIPTOR
+ *   normal [n_pts][3], min_distance, max_distance, updated [n_pts]   RUMI_REFRESH_NORMAL_DEPTH
+ * The library gathers the observed descriptor rows of good key-frames into its upload block: one block goes up, one comes back.
+ * RUMI_E_INVALID, nothing written: a key-frame index outside the table, a feature index outside its key-frame, a slice outside
+ * 0..n_obs, or -- for a point that has observations -- ref_kf outside the table, ref_feature outside the reference key-frame, ref_level
+ * outside its scale table, nlevels < 1.  RUMI_E_CAPACITY, nothing written: a point with more than RUMI_REFRESH_MAX_OBS observations.
+ * All of this is checked on the host before anything reaches the device.  n_pts = 0 is RUMI_OK.  No floating-point atomics: two calls
+ * return the same bytes, and a point's result does not depend on its place in the batch. */
+int rumi_refresh_map_points(RumiRefresh *r, const RumiRefreshKF *kf, int32_t n_kf, const RumiRefreshPoint *pts, int32_t n_pts,
+                            const int32_t *obs_kf, const int32_t *obs_feature, int32_t n_obs, int32_t what, int32_t *best_obs,
+                            int32_t *best_median, float *normal, float *min_distance, float *max_distance, uint8_t *updated);
+
+/* Host wall-clock of the handle's last successful call with work, in ms: out3[0] validation and gather, out3[1] upload + kernels + download
+ * (the host waits for the device here), out3[2] writing the caller's arrays.  For tools/refresh_probe.py. */
+int rumi_refresh_stage_ms(const RumiRefresh *r, float *out3);
 
 #ifdef __cplusplus
 }

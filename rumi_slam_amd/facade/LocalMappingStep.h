@@ -27,9 +27,13 @@ public:
     // CheckNewKeyFrames is asked before every neighbour but the first (:398-399); when it answers true the points of the neighbours so far
     // stay and the rest are dropped, which is what the reference's early return leaves (the results of the first i neighbours do not depend
     // on later ones).  Returns the number of points created, -1 when the device call failed (reported through rumi_status.h).
+    // deferRefresh: when not NULL, the two per-point members (:639-641) are not called here; the created points are appended to it and the
+    // caller refreshes them in one batch (rumi_facade::RefreshMapPoints, MapPointRefresh.h) -- same results, as neither member reads
+    // another point.  NULL, the default, keeps the per-point calls.
     template <class MapPointT, class KeyFrameT, class AtlasT, class RecentListT, class CheckFn>
     int CreateNewMapPoints(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpNeighKFs, AtlasT *pAtlas, RecentListT &mlpRecentAddedMapPoints,
-                           bool bFarPoints, float thFarPoints, CheckFn CheckNewKeyFrames, bool bCoarse = false) {
+                           bool bFarPoints, float thFarPoints, CheckFn CheckNewKeyFrames, bool bCoarse = false,
+                           std::vector<MapPointT *> *deferRefresh = nullptr) {
         const int nn = (int)vpNeighKFs.size();
         if (nn == 0) return 0;
         if (nn > RUMI_NEWPTS_MAX_NEIGH) {
@@ -88,8 +92,11 @@ public:
                 pMP->AddObservation(pKF2, P.idx2);
                 pCurrentKF->AddMapPoint(pMP, P.idx1);
                 pKF2->AddMapPoint(pMP, P.idx2);
-                pMP->ComputeDistinctiveDescriptors();
-                pMP->UpdateNormalAndDepth();
+                if (deferRefresh) deferRefresh->push_back(pMP);
+                else {
+                    pMP->ComputeDistinctiveDescriptors();
+                    pMP->UpdateNormalAndDepth();
+                }
                 pAtlas->AddMapPoint(pMP);
                 mlpRecentAddedMapPoints.push_back(pMP);
                 created++;

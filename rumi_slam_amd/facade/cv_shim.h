@@ -42,6 +42,14 @@ public:
     uint8_t *ptr(int r) { return data + (size_t)r * step; }
     const uint8_t *ptr(int r) const { return data + (size_t)r * step; }
     Mat getMat() const { return *this; }
+    Mat row(int r) const { Mat m(1, cols, CV_8U, const_cast<uint8_t *>(ptr(r)), step); m.buf_ = buf_; return m; }   // a view, as cv::Mat::row
+    Mat clone() const {
+        Mat m;
+        if (empty()) return m;
+        m.create(rows, cols, CV_8U);
+        for (int r = 0; r < rows; r++) std::memcpy(m.ptr(r), ptr(r), (size_t)cols);
+        return m;
+    }
 private:
     std::shared_ptr<uint8_t> buf_;
 };

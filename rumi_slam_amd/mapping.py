@@ -1,5 +1,6 @@
 """Host-side mirror of ``LocalMapping::CreateNewMapPoints`` (R/lib_src/LocalMapping.cc:354-647, monocular pinhole) over the C ABI in
-include/rumi_mapping.h: one call for the current key-frame and all of its neighbours."""
+include/rumi_mapping.h: one call for the current key-frame and all of its neighbours; and of the map-point refresh
+(``MapPoint::ComputeDistinctiveDescriptors`` / ``UpdateNormalAndDepth``, R/lib_src/MapPoint.cc:353-427, 450-518) for a batch of points."""
 import ctypes as C
 
 import numpy as np
@@ -30,6 +31,11 @@ def _lib():
     vp, i32 = C.c_void_p, C.c_int32
     L.rumi_create_new_map_points.argtypes = [vp, vp, vp, i32, vp, vp, i32, C.POINTER(i32), vp, vp]
     L.rumi_hook_newpts_matches.argtypes = [vp, i32, i32, vp]
+    L.rumi_refresh_create.argtypes = [i32, C.POINTER(vp)]
+    L.rumi_refresh_destroy.argtypes = [vp]
+    L.rumi_refresh_destroy.restype = None
+    L.rumi_refresh_map_points.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.rumi_refresh_stage_ms.argtypes = [vp, vp]
     L._mapping_ready = True
     return L
 
@@ -88,3 +94,111 @@ def last_matches(matcher, n_neigh, n1):
     out = np.full((n_neigh, n1), -1, np.int32)
     capi.check(_lib().rumi_hook_newpts_matches(matcher._h, n_neigh, n1, capi.ptr(out)))
     return out
+
+
+# ---- map-point refresh ----
+REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH = 1, 2
+REFRESH_MAX_OBS = 2048
+
+REFRESH_POINT_DTYPE = np.dtype([("pos", "<f4", 3), ("ref_kf", "<i4"), ("ref_feature", "<i4"), ("ref_level", "<i4"), ("obs_begin", "<i4"),
+                                ("obs_end", "<i4")])
+assert REFRESH_POINT_DTYPE.itemsize == 32
+
+
+class RumiRefreshKF(C.Structure):
+    _fields_ = [("desc", C.c_void_p), ("n", C.c_int32), ("nlevels", C.c_int32), ("scale_factors", C.c_void_p), ("Ow", C.c_float * 3),
+                ("is_bad", C.c_uint8), ("pad_", C.c_uint8 * 3)]
+
+
+assert C.sizeof(RumiRefreshKF) == 40
+
+
+class RefreshBatch:
+    """The arguments of one rumi_refresh_map_points call, marshalled (keeps the arrays alive).  ``keyframes``: (mDescriptors [n, 32] uint8,
+    mvScaleFactors, camera centre, isBad) per key-frame; ``points``: (world position, reference key-frame index, ref_feature, ref_level,
+    [(key-frame index, feature index), ...] in the order the map iterates them) per point."""
+
+    def __init__(self, keyframes, points):
+        self._keep = []
+        self.n_kf = len(keyframes)
+        self.kf = (RumiRefreshKF * max(self.n_kf, 1))()
+        for k, (desc, sf, Ow, bad) in enumerate(keyframes):
+            desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+            sf = np.ascontiguousarray(sf, np.float32)
+            self._keep += [desc, sf]
+            c = self.kf[k]
+            c.desc, c.n, c.nlevels, c.scale_factors, c.is_bad = desc.ctypes.data, len(desc), len(sf), sf.ctypes.data, int(bool(bad))
+            c.Ow[:] = np.asarray(Ow, np.float32).tolist()
+        self.pts = np.zeros(max(len(points), 1), REFRESH_POINT_DTYPE)
+        self.n_pts = len(points)
+        okf, ofeat = [], []
+        for i, (pos, ref_kf, ref_feature, ref_level, obs) in enumerate(points):
+            self.pts[i] = (np.asarray(pos, np.float32), ref_kf, ref_feature, ref_level, len(okf), len(okf) + len(obs))
+            okf += [o[0] for o in obs]
+            ofeat += [o[1] for o in obs]
+        self.n_obs = len(okf)
+        self.obs_kf = np.array(okf + [0], np.int32)
+        self.obs_feature = np.array(ofeat + [0], np.int32)
+
+    def outputs(self, fill=0):
+        """Fresh output arrays, every byte ``fill``."""
+        n = max(self.n_pts, 1)
+        shapes = dict(best_obs=(n, np.int32), best_median=(n, np.int32), normal=((n, 3), np.float32), min_distance=(n, np.float32),
+                      max_distance=(n, np.float32), updated=(n, np.uint8))
+        out = {}
+        for k, (shape, dt) in shapes.items():
+            a = np.empty(shape, dt)
+            a.view(np.uint8).fill(fill)
+            out[k] = a
+        return out
+
+    def args(self, what, out):
+        """The argument tuple after the handle (the oracle of the tests takes the same)."""
+        return (C.byref(self.kf), self.n_kf, capi.ptr(self.pts), self.n_pts, capi.ptr(self.obs_kf), capi.ptr(self.obs_feature), self.n_obs, int(what),
+                capi.ptr(out["best_obs"]), capi.ptr(out["best_median"]), capi.ptr(out["normal"]), capi.ptr(out["min_distance"]),
+                capi.ptr(out["max_distance"]), capi.ptr(out["updated"]))
+
+
+class MapPointRefresher:
+    """A rumi_refresh handle (the blocks of its calls); one per calling thread."""
+
+    def __init__(self, device=-1):
+        self._lib = _lib()
+        h = C.c_void_p()
+        capi.check(self._lib.rumi_refresh_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            self._lib.rumi_refresh_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def stage_ms(self):
+        """(validation + gather, upload + kernels + download, write-out) of the last call, host wall-clock ms."""
+        out = np.zeros(3, np.float32)
+        capi.check(self._lib.rumi_refresh_stage_ms(self._h, capi.ptr(out)))
+        return out
+
+    def status(self, batch, what, out):
+        """The raw status of one call (outputs in ``out``)."""
+        return self._lib.rumi_refresh_map_points(self._h, *batch.args(what, out))
+
+
+_refresher = None
+
+
+def RefreshMapPoints(batch, what=REFRESH_DESCRIPTOR | REFRESH_NORMAL_DEPTH, refresher=None, out=None):
+    """ComputeDistinctiveDescriptors and / or UpdateNormalAndDepth for every point of ``batch`` in one device call.  Returns a dict of
+    best_obs, best_median (position in the point's own observation list of the descriptor to clone, -1 = leave the descriptor; its median),
+    normal [n, 3], min_distance, max_distance, updated; the arrays of a mode not asked for keep what ``out`` (or zeros) held."""
+    global _refresher
+    if refresher is None:
+        if _refresher is None:
+            _refresher = MapPointRefresher()
+        refresher = _refresher
+    out = batch.outputs() if out is None else out
+    capi.check(refresher.status(batch, what, out))
+    return {k: v[:batch.n_pts] for k, v in out.items()}
