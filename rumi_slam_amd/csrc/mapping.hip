@@ -14,11 +14,9 @@
 #include <cstring>
 #include <vector>
 
-#include "rumi_internal.h"
-#include "rumi_common.h"
 #include "rumi_mapping.h"
 #include "rumi_testhooks.h"
-#include "match_device.h"
+#include "match_host.h"
 
 namespace rumi {
 
@@ -465,8 +463,8 @@ extern "C" int rumi_create_new_map_points(RumiMatcher *m, const RumiNewPointsKF 
     const char *why = "";
     if (!kf_valid(*cur, false, &why)) { g_lastError = why; return RUMI_E_INVALID; }
     for (int k = 0; k < n_neigh; k++) if (!kf_valid(neigh[k], true, &why)) { g_lastError = why; return RUMI_E_INVALID; }
-    int device = 0, maxFeat = 0, maxQ = 0;
-    MatcherExt *ext = matcher_ext(m, &device, &maxFeat, &maxQ);
+    const int maxFeat = m->maxFeat, maxQ = m->maxQ;
+    MatcherExt *ext = &m->ext;
     const int n1 = cur->feat.n;
     auto entries = [](const RumiNewPointsKF &k) { return k.fv.n_nodes ? k.fv.offsets[k.fv.n_nodes] : 0; };
     bool fits = n1 <= std::min(std::min(maxFeat, maxQ), kMaxCur) && entries(*cur) <= std::min(maxFeat, maxQ) && cur->fv.n_nodes <= std::min(maxFeat, maxQ);
@@ -482,7 +480,7 @@ extern "C" int rumi_create_new_map_points(RumiMatcher *m, const RumiNewPointsKF 
     *n_out = 0;
     for (int k = 0; k < n_neigh; k++) { per_neigh_out[k] = 0; neigh_skipped_out[k] = 0; }
     if (n_neigh == 0) return RUMI_OK;
-    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(m->device));
     if (!ext->state) { ext->state = new NewPtsState(); ext->destroy = newpts_destroy; }
     NewPtsState *s = static_cast<NewPtsState *>(ext->state);
     s->lastNeigh = 0; s->lastN1 = 0;
@@ -548,14 +546,12 @@ extern "C" int rumi_create_new_map_points(RumiMatcher *m, const RumiNewPointsKF 
 
 extern "C" int rumi_hook_newpts_matches(RumiMatcher *m, int32_t n_neigh, int32_t n1, int32_t *matches) {
     if (!m || !matches) return RUMI_E_INVALID;
-    int device = 0, maxFeat = 0, maxQ = 0;
-    MatcherExt *ext = matcher_ext(m, &device, &maxFeat, &maxQ);
-    NewPtsState *s = static_cast<NewPtsState *>(ext->state);
+    NewPtsState *s = static_cast<NewPtsState *>(m->ext.state);
     if (!s || s->lastNeigh != n_neigh || s->lastN1 != n1 || (size_t)n_neigh * n1 == 0) {
         g_lastError = "rumi_hook_newpts_matches: no rumi_create_new_map_points call of that shape precedes";
         return RUMI_E_INVALID;
     }
-    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(m->device));
     // the last call's block, candidates, gates and skip flags are still on the device: the replay runs once more, this time recording its matches
     // (it rewrites the result block with the same bytes)
     const size_t pairs = (size_t)n_neigh * n1;

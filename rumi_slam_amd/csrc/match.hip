@@ -20,38 +20,11 @@
 #include <cstring>
 #include <vector>
 
-#include "rumi_internal.h"
-#include "rumi_common.h"
-#include "rumi_match.h"
-#include "match_device.h"
+#include "match_host.h"
 
 namespace rumi {
 
-constexpr int kGridCols = 64, kGridRows = 48, kGridCells = kGridCols * kGridRows;   // Frame.h:42-43
 constexpr int kMaxSortN = 16384;     // features per frame: the mono-initialisation extractor asks for 5 x nfeatures (Tracking.cc:581: 10 000 with TUM3.yaml)
-
-enum { MODE_MAPPOINTS = 0, MODE_FRAME = 1, MODE_BOW = 2, MODE_BOW_KF = 3, MODE_SIM3 = 4, MODE_RELOC = 5, MODE_INIT = 6, MODE_FUSE = 7 };
-
-struct Query {           // 48 bytes
-    float u, v, r;       // window centre / half-size (MODE_BOW: unused)
-    int32_t minLevel, maxLevel;
-    int32_t valid;
-    int32_t descId;      // row of the query descriptor in qDesc
-    int32_t mpId;        // map point id this query assigns
-    int32_t blocks;      // Observations() > 0: an assignment hides the feature from later queries
-    int32_t c0, c1;      // MODE_BOW: candidate range in the frame's FeatureVector indices
-    float angle;         // key-point angle on the query side (rotation histogram)
-};
-
-struct FrameDev {
-    int n;
-    const RumiKeyPoint *keys;
-    const uint8_t *desc;
-    float minX, minY, maxX, maxY, wInv, hInv;
-    const float *scale;          // mvScaleFactors
-    const uint16_t *sortedIdx;   // features sorted by (cell, index)
-    const int32_t *cellStart;    // [kGridCells + 1]
-};
 
 // ---- 1. grid -----------------------------------------------------------------------------------------------
 // Frame::AssignFeaturesToGrid as a counting sort by cell (cell = column-major ix*48+iy, the order GetFeaturesInArea walks),
@@ -118,21 +91,6 @@ __global__ __launch_bounds__(1024) void k_grid(int n, const RumiKeyPoint *__rest
 }
 
 // ---- 2. queries ----------------------------------------------------------------------------------------------
-// SearchByProjection(F, map points): ORBmatcher.cc:44-71
-__device__ __forceinline__ Query mappoint_query(int i, bool inView, float px, float py, int lvl, float viewCos, float depth, bool isBad, int obs,
-                                                const float *scaleFactors, float th, int farPoints, float thFar) {
-    Query o{};
-    o.valid = inView && !(farPoints && depth > thFar) && !isBad;
-    if (o.valid) {
-        float r = (double)viewCos > 0.998 ? 2.5f : 4.0f;      // RadiusByViewingCos (float vs double literal)
-        if ((double)th != 1.0) r *= th;
-        o.u = px; o.v = py;
-        o.r = r * scaleFactors[lvl];
-        o.minLevel = lvl - 1; o.maxLevel = lvl;
-    }
-    o.descId = i; o.mpId = i; o.blocks = obs > 0;
-    return o;
-}
 __global__ void k_queries_mappoints(int nmp, const uint8_t *trackInView, const float *projX, const float *projY,
                                     const int32_t *scaleLevel, const float *viewCos, const float *trackDepth,
                                     const uint8_t *isBad, const int32_t *mpObs, const float *scaleFactors, float th,
@@ -179,7 +137,7 @@ __global__ void k_queries_frame(int nlast, const RumiKeyPoint *lastKeys, const i
 // few nodes -- levelsup near L, small trees -- used to leave the work to a handful of threads walking a hundred entries each (84 us at 10 nodes).
 __global__ void k_queries_bow(int nnKF, const uint32_t *kfNodes, const int32_t *kfOff, const uint32_t *kfIdx,
                               const int32_t *kfMp, const uint8_t *mpBad, const RumiKeyPoint *kfKeys, int nnF,
-                              const uint32_t *fNodes, const int32_t *fOff, Query *q, const int32_t *nnFdev = nullptr) {
+                              const uint32_t *fNodes, const int32_t *fOff, Query *q, const int32_t *nnFdev) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (nnKF <= 0 || p >= kfOff[nnKF]) return;
     if (nnFdev) nnF = *nnFdev;                              // the frame's FeatureVector was built on the device (k_fv_build)
@@ -200,14 +158,6 @@ __global__ void k_queries_bow(int nnKF, const uint32_t *kfNodes, const int32_t *
     q[p] = o;
 }
 
-// MapPoint::PredictScale (MapPoint.cc:538-570); log in double (oracle/match_oracle.cc explains the choice)
-__device__ __forceinline__ int predict_scale(float maxDistance, float dist, float logScaleFactor, int nLevels) {
-    const float ratio = maxDistance / dist;
-    int nScale = (int)ceil(log((double)ratio) / (double)logScaleFactor);
-    if (nScale < 0) nScale = 0;
-    else if (nScale >= nLevels) nScale = nLevels - 1;
-    return nScale;
-}
 __device__ __forceinline__ void se3f_mul(const float *T, const float *p, float *o) {   // Sophus::SE3f * p (so3.hpp:358-367)
     const float qx = T[0], qy = T[1], qz = T[2], qw = T[3];
     float u0 = qy * p[2] - qz * p[1], u1 = qz * p[0] - qx * p[2], u2 = qx * p[1] - qy * p[0];
@@ -361,8 +311,6 @@ __global__ void k_is_in_frustum(int nmp, const float *pose /*Rcw9 tcw3 Ow3 K4*/,
 }
 
 // ---- uploads: one pinned block per call, scattered to the arrays on the device ---------------------------------------------
-struct Segment { void *dst; uint32_t off, bytes; };
-constexpr int kMaxSegments = 32;
 __global__ __launch_bounds__(256) void k_scatter(const uint8_t *__restrict__ mirror, int nseg) {
     const Segment sg = reinterpret_cast<const Segment *>(mirror)[blockIdx.y];
     if ((int)blockIdx.y >= nseg) return;
@@ -480,7 +428,6 @@ __device__ __forceinline__ void wave_bitonic_store(uint32_t *key, uint32_t *val,
 // PASS 0: count pass (counts[q]).  PASS 1: fill pass at the offsets a scan of the counts produced.  PASS 2: both in one launch, every query's list
 // in a fixed slot of `listCap` entries (offsets[q] = q * listCap written here): two dispatches (~4.5 us each) less per search; a query with more
 // candidates than a slot raises kFusedOverflow and the host repeats the search with passes 0 / scan / 1.
-constexpr int kFusedOverflow = -0x40000000;
 template <int PASS>
 __global__ __launch_bounds__(256) void k_candidates(int mode, int nq, const Query *__restrict__ q, FrameDev F,
                                                     const uint8_t *__restrict__ qDesc, const uint32_t *__restrict__ fvIdx,
@@ -626,60 +573,6 @@ __global__ __launch_bounds__(256) void k_scan(int n, const int32_t *__restrict__
 }
 
 // ---- 4. resolve ------------------------------------------------------------------------------------------------
-struct ResolveArgs {
-    int mode, nq, nfeat;
-    const Query *q;
-    const int32_t *counts, *offsets;
-    const uint32_t *lists;
-    const RumiKeyPoint *featKeys;   // angles of the frame's key-points (rotation histogram)
-    const int32_t *mpObs;           // Observations() per map point id (initial occupancy), may be null (BOW)
-    int32_t *featMp;                // in: initial frame_mp (MODE 0/1); out: final ids   [nfeat]
-    int32_t *assign;                // scratch [nq]: feature chosen by each query or -1
-    int32_t *nmatches;              // out
-    float nnratio;
-    int checkOri;
-    const uint8_t *featBlocked0;   // optional [nfeat]: feature unavailable from the start (overrides the featMp/mpObs rule)
-    float thrF;                    // MODE_SIM3: TH_LOW * ratioHamming
-    int thrI;                      // MODE_RELOC: ORBdist
-    const int32_t *overflow;       // set by the fill pass when the list arena is too small: nothing to resolve
-    // optional tail (the Tracking step): PoseOptimization's correspondences gathered from the vector this search leaves (k_track_gather's work,
-    // one launch less between the search and the optimisation); gXw == nullptr: none
-    const float *gMpPos, *gInvSigma2;
-    float *gXw, *gObs, *gW;
-    int32_t *gIdx, *gStart, *gSnapshot;
-};
-
-// Correspondences of Optimizer::PoseOptimization(Frame*) (Optimizer.cc:749-815, mono): the features with a map point, in feature order.
-// One workgroup of 1024 threads, ordered compaction (ballot + wave offsets through LDS, chunks of 1024 features).
-__device__ __forceinline__ void gather_correspondences(int n, const RumiKeyPoint *__restrict__ keys, const int32_t *featMp, const float *__restrict__ mpPos,
-                                                       const float *__restrict__ invSigma2, float *Xw, float *obs, float *w, int32_t *idx, int32_t *start,
-                                                       int32_t *snapshot, int *sWave /* [16] */, int *sBase) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (tid == 0) *sBase = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < n; c0 += 1024) {
-        const int i = c0 + tid;
-        const int mp = i < n ? featMp[i] : -1;
-        if (snapshot && i < n) snapshot[i] = mp;            // the frame's map-point vector as the search left it (the optimisation's outliers leave it next)
-        const unsigned long long b = __ballot(mp >= 0);
-        if (lane == 0) sWave[wave] = __popcll(b);
-        __syncthreads();
-        int off = *sBase;
-        for (int k = 0; k < wave; k++) off += sWave[k];
-        if (mp >= 0) {
-            const int c = off + __popcll(b & ((1ull << lane) - 1));
-            Xw[3 * c] = mpPos[3 * mp]; Xw[3 * c + 1] = mpPos[3 * mp + 1]; Xw[3 * c + 2] = mpPos[3 * mp + 2];
-            obs[2 * c] = keys[i].x; obs[2 * c + 1] = keys[i].y;
-            w[c] = invSigma2[keys[i].octave];
-            idx[c] = i;
-        }
-        __syncthreads();
-        if (tid == 0) { int t = *sBase; for (int k = 0; k < 16; k++) t += sWave[k]; *sBase = t; }
-        __syncthreads();
-    }
-    if (tid == 0) { start[0] = 0; start[1] = *sBase; }
-}
-
 // One workgroup iterates "every query picks its best candidate among the features no EARLIER query holds" to its fixed point (the
 // result of the reference's sequential loop).  A round is latency, not work: what a round needs of a query -- count, the head of its
 // candidate list, the blocks flag, its current pick -- is read once into registers (the first kResQ queries of a thread, i.e. up to
@@ -1294,47 +1187,6 @@ __global__ __launch_bounds__(256) void k_bow_batch_finish(BowBatch B) {
 using namespace rumi;
 
 // ================================================ host side =======================================================
-struct RumiMatcher {
-    int device = 0, maxFeat = 0, maxQ = 0;
-    size_t listCap = 0;
-    // frame (train) side
-    RumiKeyPoint *dKeys = nullptr; uint8_t *dDesc = nullptr; float *dScale = nullptr;
-    uint16_t *dSorted = nullptr; int32_t *dCellStart = nullptr;
-    uint32_t *dFvIdx = nullptr;      // frame FeatureVector indices (BoW)
-    // query side
-    Query *dQ = nullptr; uint8_t *dQDesc = nullptr; int32_t *dCounts = nullptr, *dOffsets = nullptr;
-    uint32_t *dLists = nullptr;
-    // results, one block so that one copy brings them back: [nmatches, list overflow, -, -][featMp maxFeat][assign maxQ]
-    int32_t *dOut = nullptr, *hOut = nullptr;
-    int32_t *dNmatches = nullptr, *dOverflow = nullptr, *dFeatMp = nullptr, *dAssign = nullptr;     // views into dOut
-    // raw inputs of the query builders
-    uint8_t *dU8a = nullptr, *dU8b = nullptr; float *dF[6] = {nullptr}; int32_t *dI[4] = {nullptr};
-    RumiKeyPoint *dQKeys = nullptr; uint32_t *dNodesA = nullptr, *dNodesB = nullptr, *dIdxA = nullptr;
-    int32_t *dOffA = nullptr, *dOffB = nullptr;
-    float *dPose = nullptr;
-    // uploads of one call: packed into a pinned block, copied once, scattered on the device (k_scatter)
-    uint8_t *hStage = nullptr, *dStage = nullptr;
-    size_t stageCap = 0, stageUsed = 0;
-    int nseg = 0;
-    // rumi_search_by_bow_batch: one pinned block up, one result block back (grown on demand)
-    uint8_t *hBow = nullptr, *dBow = nullptr; size_t bowCap = 0;
-    uint8_t *hBowOut = nullptr, *dBowOut = nullptr; size_t bowOutCap = 0;
-    // k_grid of the uploaded frame, launched by flush_uploads once the key-points are in place
-    const int32_t *gridNDev = nullptr;     // k_grid reads the count from the device (one call only: cleared by the flush)
-    hipStream_t upStream = nullptr;        // where the next flush queues its copy and scatter (the caller orders its kernels behind them)
-    bool gridPending = false; int gridN = 0; float gridMinX = 0, gridMinY = 0, gridWInv = 0, gridHInv = 0;
-    const RumiKeyPoint *gridKeys = nullptr;      // key-points k_grid reads: dKeys, or a frame that already lies on the device (rumi_track_frame)
-    MatcherExt ext;                        // arenas of rumi_create_new_map_points (mapping.hip), released with the matcher
-};
-constexpr size_t kStageHeader = kMaxSegments * sizeof(Segment);
-
-namespace rumi {
-MatcherExt *matcher_ext(RumiMatcher *m, int *device, int *maxFeatures, int *maxQueries) {
-    *device = m->device; *maxFeatures = m->maxFeat; *maxQueries = m->maxQ;
-    return &m->ext;
-}
-}  // namespace rumi
-
 extern "C" int rumi_descriptor_distance(const uint8_t *a, const uint8_t *b) {
     uint64_t x[4], y[4];
     std::memcpy(x, a, 32); std::memcpy(y, b, 32);
@@ -1358,12 +1210,6 @@ extern "C" void rumi_match_destroy(RumiMatcher *m) {
     if (m->dBow) (void)hipFree(m->dBow);
     if (m->dBowOut) (void)hipFree(m->dBowOut);
     delete m;
-}
-
-template <class T> static int dalloc(T **p, size_t n) {
-    *p = nullptr;
-    HIP_TRY(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
-    return RUMI_OK;
 }
 
 extern "C" int rumi_match_create(int32_t max_features, int32_t max_queries, int32_t device, RumiMatcher **out) {
@@ -1412,8 +1258,9 @@ extern "C" int rumi_match_create(int32_t max_features, int32_t max_queries, int3
     return RUMI_OK;
 }
 
-// Queue `bytes` of host data for the array `dst`; nothing moves until flush_uploads.
-static int stage_add(RumiMatcher *m, void *dst, const void *src, size_t bytes) {
+namespace rumi {
+
+int stage_add(RumiMatcher *m, void *dst, const void *src, size_t bytes) {
     if (bytes == 0) return RUMI_OK;
     const size_t off = (m->stageUsed + 15) & ~(size_t)15;
     if (m->nseg >= kMaxSegments || off + bytes > m->stageCap) {
@@ -1425,10 +1272,8 @@ static int stage_add(RumiMatcher *m, void *dst, const void *src, size_t bytes) {
     m->stageUsed = off + bytes;
     return RUMI_OK;
 }
-#define H2D(dst, src, n) do { const int rcS_ = stage_add(m, (dst), (src), (size_t)(n) * sizeof(*(dst))); if (rcS_ != RUMI_OK) return rcS_; } while (0)
 
-// One host-to-device copy for everything queued, the scatter, then the grid of the uploaded frame.
-static int flush_uploads(RumiMatcher *m) {
+int flush_uploads(RumiMatcher *m) {
     if (m->nseg > 0) {
         HIP_TRY(hipMemcpyAsync(m->dStage, m->hStage, m->stageUsed, hipMemcpyHostToDevice, m->upStream));
         hipLaunchKernelGGL(k_scatter, dim3(8, m->nseg), dim3(256), 0, m->upStream, m->dStage, m->nseg);
@@ -1443,12 +1288,10 @@ static int flush_uploads(RumiMatcher *m) {
     }
     return RUMI_OK;
 }
-#define FLUSH(m) do { const int rcF_ = flush_uploads(m); if (rcF_ != RUMI_OK) return rcF_; } while (0)
 
-// A call that fails between stage_add and flush must not leak its queue into the next one.
-static void reset_uploads(RumiMatcher *m) { m->nseg = 0; m->stageUsed = kStageHeader; m->gridPending = false; }
+void reset_uploads(RumiMatcher *m) { m->nseg = 0; m->stageUsed = kStageHeader; m->gridPending = false; }
 
-static int upload_frame(RumiMatcher *m, const RumiFrameFeatures *F, FrameDev *fd) {
+int upload_frame(RumiMatcher *m, const RumiFrameFeatures *F, FrameDev *fd) {
     reset_uploads(m);
     if (!F || F->n < 0 || F->n > m->maxFeat || F->nlevels < 1 || F->nlevels > 64 || !(F->max_x > F->min_x) || !(F->max_y > F->min_y)) {
         g_lastError = "bad RumiFrameFeatures (n, nlevels or bounds)";
@@ -1469,7 +1312,7 @@ static int upload_frame(RumiMatcher *m, const RumiFrameFeatures *F, FrameDev *fd
 
 // count pass, scan, fill pass.  The fill pass refuses to write past the list arena and raises the overflow word instead; the
 // caller sees it in the result block, grows the arena and repeats the call (run_search) — no mid-pipeline read-back.
-static int build_lists(RumiMatcher *m, int mode, int nq, const FrameDev &fd, const uint8_t *dQueryDesc, bool retry, bool fused) {
+int build_lists(RumiMatcher *m, int mode, int nq, const FrameDev &fd, const uint8_t *dQueryDesc, bool retry, bool fused) {
     FLUSH(m);
     if (retry) HIP_TRY(hipMemsetAsync(m->dOut, 0, 4 * sizeof(int32_t), nullptr));   // the first attempt's header was cleared with the frame upload
     if (nq > 0 && fused) {
@@ -1501,20 +1344,17 @@ static int grow_lists(RumiMatcher *m, size_t need) {
     return dalloc(&m->dLists, m->listCap);
 }
 
-// candidate lists, then the fix-point resolve
-static int run_search(RumiMatcher *m, int mode, int nq, const FrameDev &fd, const uint8_t *dQueryDesc, const int32_t *dMpObs,
-                      float nnratio, int checkOri, int32_t *hostFeatMp, int32_t *nmatchesOut, const uint8_t *dBlocked0 = nullptr,
-                      float thrF = 0.f, int thrI = 0, int32_t *hostAssign = nullptr) {
+int run_search(RumiMatcher *m, int mode, int nq, const FrameDev &fd, const uint8_t *dQueryDesc, const int32_t *dMpObs, float nnratio, int checkOri,
+               int32_t *hostFeatMp, int32_t *nmatchesOut, const uint8_t *dBlocked0, float thrF, int thrI, int32_t *hostAssign) {
     // first with every query's list in a fixed slot (one candidate launch); a query that does not fit falls back to count / scan / fill, which
     // sizes the lists exactly and grows the arena when needed
-    static const bool noFused = std::getenv("RUMI_MATCH_NO_FUSED") != nullptr;
-    bool fused = !noFused && nq > 0 && m->listCap / (size_t)nq >= 64;
+    bool fused = track_speculation().fused && nq > 0 && m->listCap / (size_t)nq >= 64;
     for (int attempt = 0, grown = 0; attempt < 4; attempt++) {
         const int rcl = build_lists(m, mode, nq, fd, dQueryDesc, attempt > 0, fused);
         if (rcl != RUMI_OK) return rcl;
         ResolveArgs A{mode, nq, fd.n, m->dQ, m->dCounts, m->dOffsets, m->dLists, fd.keys, dMpObs, m->dFeatMp, m->dAssign, m->dNmatches,
                       nnratio, checkOri, dBlocked0, thrF, thrI, m->dOverflow};
-        hipLaunchKernelGGL(k_resolve, dim3(1), dim3(1024), (size_t)std::max(fd.n, 1) * sizeof(int32_t), nullptr, A);
+        launch_resolve(A, nullptr);
         HIP_TRY(hipGetLastError());
         const int rcf = fetch_results(m, fd.n, nq, hostAssign != nullptr);
         if (rcf != RUMI_OK) return rcf;
@@ -1531,6 +1371,29 @@ static int run_search(RumiMatcher *m, int mode, int nq, const FrameDev &fd, cons
     if (nq > 0 && hostAssign) std::memcpy(hostAssign, m->hOut + 4 + m->maxFeat, (size_t)nq * sizeof(int32_t));
     return RUMI_OK;
 }
+
+const SearchSwitches &track_speculation() {
+    static const SearchSwitches sw = [] {
+        const char *spec = std::getenv("RUMI_TRACK_SPECULATE");
+        const bool fused = std::getenv("RUMI_MATCH_NO_FUSED") == nullptr;
+        return SearchSwitches{fused, fused && (spec ? std::atoi(spec) : 1) != 0};
+    }();
+    return sw;
+}
+
+void launch_queries_frame(RumiMatcher *m, const FrameDev &fd, int nlast, float th, hipStream_t st) {
+    hipLaunchKernelGGL(k_queries_frame, dim3((nlast + 255) / 256), dim3(256), 0, st, nlast, m->dQKeys, m->dI[0], m->dU8a, m->dF[0], m->dI[1], m->dPose,
+                       m->dPose + 7, m->dScale, th, fd.minX, fd.minY, fd.maxX, fd.maxY, m->dQ);
+}
+void launch_queries_bow(RumiMatcher *m, int nEntries, int nnKF, int nnF, const int32_t *nnFdev, hipStream_t st) {
+    hipLaunchKernelGGL(k_queries_bow, dim3((std::max(nEntries, 1) + 255) / 256), dim3(256), 0, st, nnKF, m->dNodesA, m->dOffA, m->dIdxA, m->dI[0], m->dU8a,
+                       m->dQKeys, nnF, m->dNodesB, m->dOffB, m->dQ, nnFdev);
+}
+void launch_resolve(const ResolveArgs &A, hipStream_t st) {
+    hipLaunchKernelGGL(k_resolve, dim3(1), dim3(1024), (size_t)std::max(A.nfeat, 1) * sizeof(int32_t), st, A);
+}
+
+}  // namespace rumi
 
 extern "C" int rumi_search_by_projection_mappoints(RumiMatcher *m, const RumiFrameFeatures *F, int32_t nmp,
                                                    const uint8_t *track_in_view, const float *proj_x, const float *proj_y,
@@ -1576,8 +1439,7 @@ extern "C" int rumi_search_by_projection_frame(RumiMatcher *m, const RumiFrameFe
     if (nlast > 0) {
         H2D(m->dQKeys, last_keys, nlast); H2D(m->dI[0], last_mp, nlast); H2D(m->dU8a, last_outlier, nlast);
         FLUSH(m);
-        hipLaunchKernelGGL(k_queries_frame, dim3((nlast + 255) / 256), dim3(256), 0, nullptr, nlast, m->dQKeys, m->dI[0], m->dU8a,
-                           m->dF[0], m->dI[1], m->dPose, m->dPose + 7, m->dScale, th, fd.minX, fd.minY, fd.maxX, fd.maxY, m->dQ);
+        launch_queries_frame(m, fd, nlast, th, nullptr);
     }
     return run_search(m, MODE_FRAME, nlast, fd, m->dQDesc, m->dI[1], 0.f, check_orientation, cur_mp, nmatches_out);
 }
@@ -1604,9 +1466,7 @@ extern "C" int rumi_search_by_bow(RumiMatcher *m, const RumiFrameFeatures *KF, c
     if (nfe > 0) H2D(m->dFvIdx, f_fv->indices, nfe);
     m->gridPending = false;                                 // candidates come from the FeatureVectors: the spatial grid is not read
     FLUSH(m);
-    if (kf_fv->n_nodes > 0)
-        hipLaunchKernelGGL(k_queries_bow, dim3((std::max(nqe, 1) + 255) / 256), dim3(256), 0, nullptr, kf_fv->n_nodes, m->dNodesA, m->dOffA,
-                           m->dIdxA, m->dI[0], m->dU8a, m->dQKeys, f_fv->n_nodes, m->dNodesB, m->dOffB, m->dQ);
+    if (kf_fv->n_nodes > 0) launch_queries_bow(m, nqe, kf_fv->n_nodes, f_fv->n_nodes, nullptr, nullptr);
     return run_search(m, MODE_BOW, nqe, fd, m->dQDesc, nullptr, nnratio, check_orientation, matches, nmatches_out);
 }
 
@@ -1736,9 +1596,7 @@ extern "C" int rumi_search_by_bow_kf(RumiMatcher *m, const RumiFrameFeatures *KF
     if (nfe > 0) H2D(m->dFvIdx, fv2->indices, nfe);
     m->gridPending = false;
     FLUSH(m);
-    if (fv1->n_nodes > 0)
-        hipLaunchKernelGGL(k_queries_bow, dim3((std::max(nqe, 1) + 255) / 256), dim3(256), 0, nullptr, fv1->n_nodes, m->dNodesA, m->dOffA, m->dIdxA,
-                           m->dI[0], m->dU8a, m->dQKeys, fv2->n_nodes, m->dNodesB, m->dOffB, m->dQ);
+    if (fv1->n_nodes > 0) launch_queries_bow(m, nqe, fv1->n_nodes, fv2->n_nodes, nullptr, nullptr);
     std::vector<int32_t> assign(std::max(nqe, 1), -1);
     rc = run_search(m, MODE_BOW_KF, nqe, fd, m->dQDesc, nullptr, nnratio, check_orientation, nullptr, nmatches_out, m->dU8b, 0.f, 0, assign.data());
     if (rc != RUMI_OK) return rc;
@@ -2060,1034 +1918,4 @@ extern "C" int rumi_match_bruteforce_batch_device(const void *d_query, const voi
                                                   void *d_best_dist, void *d_second_dist, void *hip_stream) {
     return rumi_match_bruteforce_batch_device_strided(d_query, d_nq, d_train, d_nt, count_stride, 32ll * cap, 32ll * cap, cap, nbatch, d_best_idx, d_best_dist,
                                                       d_second_dist, hip_stream);
-}
-
-// ==================================================================================================================
-// One device-resident Tracking step (include/rumi_track.h): the extractor's record, the matcher's grid and map-point vector (mvpMapPoints =
-// dFeatMp) and the pose optimiser's correspondence arrays never leave HBM between the five stages.  A dispatch costs about 4.5 us on the
-// device whatever it does, so the step is built from as few as the data flow allows: no device-to-device copies (the matcher reads the
-// extractor's record in place, results are produced inside the block that travels back), fills and bookkeeping folded into neighbouring kernels.
-// ==================================================================================================================
-namespace rumi {
-
-constexpr int kTrackLdsEdges = rumi::kPoseLdsEdges;     // (rumi_internal.h: one number for both files)
-struct TrackBlock {                  // the result block's header, device and pinned host alike (arrays follow at byte offsets of RumiTracker)
-    float Tout[14];                  // pose after the motion model | after the local map
-    float pose19[20];                // Rcw9 tcw3 Ow3 K4 of the first (Frame::UpdatePoseMatrices)
-    int32_t nGood[2];                // PoseOptimization return values
-    int32_t counters[2];             // nmatchesMap, mnMatchesInliers
-    int32_t start[2];                // correspondences of the optimisation in flight: {0, count}
-    int32_t spec[4];                 // speculative step: result header (matches, overflow word) of the motion search | of the local search
-};
-
-// fill(mvpMapPoints, NULL), cleared flags / counters, both poses = the prediction, result header of the search cleared
-__global__ void k_track_init(int n, int nmp, int full, int32_t *featMp, int32_t *searchHeader, uint8_t *seen, uint8_t *outF, int32_t *mpOut, const float *Tpred,
-                             TrackBlock *blk) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { featMp[i] = -1; if (full) { outF[i] = 0; mpOut[i] = -1; } }
-    if (full && i < nmp) seen[i] = 0;
-    if (i < 4) searchHeader[i] = 0;
-    if (full && i == 0) {
-        for (int k = 0; k < 7; k++) { blk->Tout[k] = Tpred[k]; blk->Tout[7 + k] = Tpred[k]; }
-        for (int k = 0; k < 20; k++) blk->pose19[k] = 0.f;
-        blk->nGood[0] = blk->nGood[1] = 0; blk->counters[0] = blk->counters[1] = 0; blk->start[0] = blk->start[1] = 0;
-    }
-}
-
-// (gather_correspondences as a launch of its own: the paths that do not end a search with it)
-__global__ __launch_bounds__(1024) void k_track_gather(int n, const RumiKeyPoint *__restrict__ keys, const int32_t *__restrict__ featMp,
-                                                       const float *__restrict__ mpPos, const float *__restrict__ invSigma2, float *Xw, float *obs,
-                                                       float *w, int32_t *idx, int32_t *start, int32_t *snapshot = nullptr) {
-    __shared__ int sWave[16], sBase;
-    gather_correspondences(n, keys, featMp, mpPos, invSigma2, Xw, obs, w, idx, start, snapshot, sWave, &sBase);
-}
-
-// Frame::UpdatePoseMatrices (Frame.cc:522-528) in Sophus' / Eigen's float arithmetic: Rcw = q.toRotationMatrix(), tcw, Ow = conj(q) * (-tcw)
-// (quaternion _transformVector), as [Rcw9 | tcw3 | Ow3 | K4] for the frustum test.
-__device__ __forceinline__ void pose_matrices19(const float *Tcw7, const float *K4, float *pose19) {
-    const float x = Tcw7[0], y = Tcw7[1], z = Tcw7[2], w = Tcw7[3];
-    const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z;
-    const float twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    pose19[0] = 1.f - (tyy + tzz); pose19[1] = txy - twz; pose19[2] = txz + twy;
-    pose19[3] = txy + twz; pose19[4] = 1.f - (txx + tzz); pose19[5] = tyz - twx;
-    pose19[6] = txz - twy; pose19[7] = tyz + twx; pose19[8] = 1.f - (txx + tyy);
-    const float t0 = Tcw7[4], t1 = Tcw7[5], t2 = Tcw7[6];
-    pose19[9] = t0; pose19[10] = t1; pose19[11] = t2;
-    const float qx = -x, qy = -y, qz = -z, v0 = t0 * -1.f, v1 = t1 * -1.f, v2 = t2 * -1.f;
-    float u0 = qy * v2 - qz * v1, u1 = qz * v0 - qx * v2, u2 = qx * v1 - qy * v0;
-    u0 += u0; u1 += u1; u2 += u2;
-    const float c0 = qy * u2 - qz * u1, c1 = qz * u0 - qx * u2, c2 = qx * u1 - qy * u0;
-    pose19[12] = (v0 + w * u0) + c0; pose19[13] = (v1 + w * u1) + c1; pose19[14] = (v2 + w * u2) + c2;
-    pose19[15] = K4[0]; pose19[16] = K4[1]; pose19[17] = K4[2]; pose19[18] = K4[3];
-}
-
-// "Discard outliers" of TrackWithMotionModel / TrackReferenceKeyFrame alone (Tracking.cc:2489-2508, 2349-2369): the outliers of the optimisation
-// leave the frame, the others count towards nmatchesMap when their point has observations.  (The step-wise entries: SearchLocalPoints' own
-// loops belong to rumi_track_local.)
-__global__ void k_track_discard(const int32_t *idx, const uint8_t *outlierC, int32_t *featMp, const int32_t *mpObs, TrackBlock *blk,
-                                const int32_t *searchHeader = nullptr) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c == 0 && searchHeader) { blk->spec[0] = searchHeader[0]; blk->spec[1] = searchHeader[1]; }
-    if (c >= blk->start[1]) return;
-    const int i = idx[c], mp = featMp[i];
-    if (outlierC[c]) { featMp[i] = -1; return; }
-    if (mpObs[mp] > 0) atomicAdd(&blk->counters[0], 1);
-}
-
-// rumi_track_local: the pose the stage starts from and its UpdatePoseMatrices, cleared outputs and counters (the frame's map-point vector and
-// the seen flags arrive with the stage's upload)
-__global__ void k_track_local_init(int n, const float *Tcw7, const float *K4, uint8_t *outF, int32_t *mpOut, int32_t *searchHeader, TrackBlock *blk) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { outF[i] = 0; mpOut[i] = -1; }
-    if (i < 4) searchHeader[i] = 0;
-    if (i == 0) {
-        for (int k = 0; k < 7; k++) { blk->Tout[k] = Tcw7[k]; blk->Tout[7 + k] = Tcw7[k]; }
-        pose_matrices19(Tcw7, K4, blk->pose19);
-        blk->nGood[0] = blk->nGood[1] = 0; blk->counters[0] = blk->counters[1] = 0; blk->start[0] = blk->start[1] = 0;
-    }
-}
-
-// The frame's DBoW2::FeatureVector on the device (TemplatedVocabulary.h:1147-1190, FeatureVector.cpp:31-45): the features with a positive word
-// weight grouped by their node id, nodes ascending, feature indices ascending inside a node, in the CSR form the BoW search reads.
-// ONE workgroup: 64-bit keys node << 32 | feature in LDS, bitonic sort, then the group boundaries by an ordered compaction.
-constexpr int kFvThreads = 1024;
-__global__ __launch_bounds__(kFvThreads) void k_fv_build(int n, int npad, const uint32_t *__restrict__ node, const double *__restrict__ weight,
-                                                         uint32_t *fvNodes, int32_t *fvOff, uint32_t *fvIdx, int32_t *nnOut) {
-    extern __shared__ unsigned long long fvKey[];          // npad keys (a power of two >= n)
-    __shared__ int sCnt[kFvThreads / 64], sBase, sValid;
-    const int tid = threadIdx.x;
-    for (int i = tid; i < npad; i += kFvThreads)
-        fvKey[i] = (i < n && weight[i] > 0.0) ? (((unsigned long long)node[i] << 32) | (unsigned)i) : ~0ull;       // stopped words and padding sort last
-    __syncthreads();
-    for (int k = 2; k <= npad; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < npad; i += kFvThreads) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long a = fvKey[i], b = fvKey[l];
-                    if ((a > b) == ((i & k) == 0)) { fvKey[i] = b; fvKey[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    if (tid == 0) { sBase = 0; sValid = 0; }
-    __syncthreads();
-    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    for (int c0 = 0; c0 < npad; c0 += kFvThreads) {
-        const int i = c0 + tid;
-        const unsigned long long key = i < npad ? fvKey[i] : ~0ull;
-        const bool valid = key != ~0ull;
-        const bool first = valid && (i == 0 || (uint32_t)(fvKey[i - 1] >> 32) != (uint32_t)(key >> 32));
-        if (valid) fvIdx[i] = (uint32_t)key;
-        const unsigned long long b = __ballot(first);
-        if (lane == 0) sCnt[wave] = __popcll(b);
-        if (valid) atomicMax(&sValid, i + 1);
-        __syncthreads();
-        int off = sBase;
-        for (int k = 0; k < wave; k++) off += sCnt[k];
-        if (first) { const int a = off + __popcll(b & ((1ull << lane) - 1)); fvNodes[a] = (uint32_t)(key >> 32); fvOff[a] = i; }
-        __syncthreads();
-        if (tid == 0) { int t = sBase; for (int k = 0; k < kFvThreads / 64; k++) t += sCnt[k]; sBase = t; }
-        __syncthreads();
-    }
-    if (tid == 0) { fvOff[sBase] = sValid; *nnOut = sBase; }
-}
-
-// After the first PoseOptimization (Tracking.cc:2489-2508) and the first loop of SearchLocalPoints (:2998-3010): every point the motion search
-// matched has been seen in this frame (inliers by SearchLocalPoints, outliers by the discard loop); outliers and bad points leave the frame.
-// Thread 0 also derives Frame::UpdatePoseMatrices (Frame.cc:522-528) of the optimised pose in Sophus' / Eigen's float arithmetic: Rcw =
-// q.toRotationMatrix(), tcw, Ow = conj(q) * (-tcw) (quaternion _transformVector), as [Rcw9 | tcw3 | Ow3 | K4] for k_is_in_frustum.
-__device__ __forceinline__ void after_motion_body(int c, const int32_t *idx, const uint8_t *outlierC, int32_t *featMp, const int32_t *mpObs, const uint8_t *mpBad,
-                                                  uint8_t *seen, const float *K4, TrackBlock *blk, const int32_t *searchHeader) {
-    if (c == 0) pose_matrices19(blk->Tout, K4, blk->pose19);
-    if (c == 0 && searchHeader) { blk->spec[0] = searchHeader[0]; blk->spec[1] = searchHeader[1]; }   // (the next search clears the header)
-    if (c >= blk->start[1]) return;
-    const int i = idx[c], mp = featMp[i];
-    seen[mp] = outlierC[c] ? 2 : 1;                        // 2: discarded as an outlier (k_track_frustum: its mbTrackInView may still be set from an earlier frame)
-    if (outlierC[c]) { featMp[i] = -1; return; }
-    if (mpObs[mp] > 0) atomicAdd(&blk->counters[0], 1);
-    if (mpBad[mp]) featMp[i] = -1;
-}
-__global__ void k_track_after_motion(const int32_t *idx, const uint8_t *outlierC, int32_t *featMp, const int32_t *mpObs, const uint8_t *mpBad, uint8_t *seen,
-                                     const float *K4, TrackBlock *blk, const int32_t *searchHeader) {
-    after_motion_body(blockIdx.x * blockDim.x + threadIdx.x, idx, outlierC, featMp, mpObs, mpBad, seen, K4, blk, searchHeader);
-}
-
-// Frame::isInFrustum of the local points SearchLocalPoints' second loop evaluates (not seen in this frame, not bad), writing the skip flag the query
-// builder reads as isBad; also clears the search's result header and keeps a copy of the frame's map-point vector
-struct FrustumArgs {
-    int nmp;
-    int n;
-    const int32_t *featMp;
-    int32_t *mpMotion;
-    const uint8_t *local;
-    const uint8_t *seen;
-    const uint8_t *bad;
-    uint8_t *skip;
-    int32_t *searchHeader;
-    const float *pose;
-    float minX;
-    float minY;
-    float maxX;
-    float maxY;
-    float logScaleFactor;
-    int nLevels;
-    float viewingCosLimit;
-    const float *mpPos;
-    const float *mpNormal;
-    const float *mpMinDist;
-    const float *mpMaxDist;
-    uint8_t *inView;
-    float *projX;
-    float *projY;
-    int32_t *scaleLevel;
-    float *viewCosOut;
-    float *trackDepth;
-    const int32_t *mpObs;
-    const float *scaleFactors;
-    float th;
-    int farPoints;
-    float thFar;
-    Query *q;
-    const uint8_t *staleIn;      // RumiTrackPoints.stale_in_view / stale_proj (nullptr: none)
-    const float *staleProj;
-};
-__device__ __forceinline__ void frustum_body(int i, const FrustumArgs &F) {
-    const auto nmp = F.nmp;
-    const auto n = F.n;
-    const auto featMp = F.featMp;
-    const auto mpMotion = F.mpMotion;
-    const auto local = F.local;
-    const auto seen = F.seen;
-    const auto bad = F.bad;
-    const auto skip = F.skip;
-    const auto searchHeader = F.searchHeader;
-    const auto pose = F.pose;
-    const auto minX = F.minX;
-    const auto minY = F.minY;
-    const auto maxX = F.maxX;
-    const auto maxY = F.maxY;
-    const auto logScaleFactor = F.logScaleFactor;
-    const auto nLevels = F.nLevels;
-    const auto viewingCosLimit = F.viewingCosLimit;
-    const auto mpPos = F.mpPos;
-    const auto mpNormal = F.mpNormal;
-    const auto mpMinDist = F.mpMinDist;
-    const auto mpMaxDist = F.mpMaxDist;
-    const auto inView = F.inView;
-    const auto projX = F.projX;
-    const auto projY = F.projY;
-    const auto scaleLevel = F.scaleLevel;
-    const auto viewCosOut = F.viewCosOut;
-    const auto trackDepth = F.trackDepth;
-    const auto mpObs = F.mpObs;
-    const auto scaleFactors = F.scaleFactors;
-    const auto th = F.th;
-    const auto farPoints = F.farPoints;
-    const auto thFar = F.thFar;
-    const auto q = F.q;
-    if (i < 4) searchHeader[i] = 0;
-    if (i < n) mpMotion[i] = featMp[i];                    // mvpMapPoints as TrackWithMotionModel leaves them (the local search may replace unobserved points)
-    if (i >= nmp) return;
-    // A discarded outlier (seen == 2) is not re-projected (mnLastFrameSeen == mnId) -- but a monocular frame's discard loop left its mbTrackInView
-    // as an earlier frame set it (Nleft = -1, Tracking.cc:2489-2508), and SearchByProjection searches it at that OLD projection (ORBmatcher.cc:46-60)
-    if (local[i] && !bad[i] && seen[i] == 2 && F.staleIn && F.staleIn[i]) {
-        const float *sp = F.staleProj + (size_t)i * 5;
-        skip[i] = 0;
-        inView[i] = 2; projX[i] = sp[0]; projY[i] = sp[1]; scaleLevel[i] = (int)sp[2]; viewCosOut[i] = sp[3]; trackDepth[i] = sp[4];
-        q[i] = mappoint_query(i, true, sp[0], sp[1], (int)sp[2], sp[3], sp[4], false, mpObs[i], scaleFactors, th, farPoints, thFar);
-        return;
-    }
-    const uint8_t sk = !local[i] || seen[i] || bad[i];
-    skip[i] = sk;
-    // (the search's query of this point is built here too: k_queries_mappoints' work on the values at hand, one launch less)
-    if (sk) {
-        inView[i] = 0; projX[i] = -1; projY[i] = -1; scaleLevel[i] = 0; viewCosOut[i] = 0; trackDepth[i] = 0;
-        q[i] = mappoint_query(i, false, -1.f, -1.f, 0, 0.f, 0.f, true, mpObs[i], scaleFactors, th, farPoints, thFar);
-        return;
-    }
-    const float *R = pose, *t = pose + 9, *Ow = pose + 12, *K = pose + 15;
-    const float *P = mpPos + (size_t)i * 3;
-    uint8_t in = 0;
-    float px = -1, py = -1, vc = 0, depth = 0;
-    int lvl = 0;
-    float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) Pc[r] = ((R[r * 3] * P[0] + R[r * 3 + 1] * P[1]) + R[r * 3 + 2] * P[2]) + t[r];
-    const float Pc_dist = sqrtf((Pc[0] * Pc[0] + Pc[1] * Pc[1]) + Pc[2] * Pc[2]);
-    if (!(Pc[2] < 0.0f)) {
-        const float u = K[0] * Pc[0] / Pc[2] + K[2], v = K[1] * Pc[1] / Pc[2] + K[3];
-        if (!(u < minX || u > maxX) && !(v < minY || v > maxY)) {
-            px = u; py = v;
-            const float maxD = 1.2f * mpMaxDist[i], minD = 0.8f * mpMinDist[i];
-            const float P0 = P[0] - Ow[0], P1 = P[1] - Ow[1], P2 = P[2] - Ow[2];
-            const float dist = sqrtf((P0 * P0 + P1 * P1) + P2 * P2);
-            if (!(dist < minD || dist > maxD)) {
-                const float *Pn = mpNormal + (size_t)i * 3;
-                const float viewCos = ((P0 * Pn[0] + P1 * Pn[1]) + P2 * Pn[2]) / dist;
-                if (!(viewCos < viewingCosLimit)) {
-                    lvl = predict_scale(mpMaxDist[i], dist, logScaleFactor, nLevels);
-                    in = 1; depth = Pc_dist; vc = viewCos;
-                }
-            }
-        }
-    }
-    inView[i] = in; projX[i] = px; projY[i] = py; scaleLevel[i] = lvl; viewCosOut[i] = vc; trackDepth[i] = depth;
-    q[i] = mappoint_query(i, in != 0, px, py, lvl, vc, depth, false, mpObs[i], scaleFactors, th, farPoints, thFar);
-}
-
-__global__ void k_track_frustum(FrustumArgs F) { frustum_body(blockIdx.x * blockDim.x + threadIdx.x, F); }
-
-// after the last PoseOptimization: mvpMapPoints and mvbOutlier per feature into the result block, mnMatchesInliers (Tracking.cc:2573-2586)
-__global__ void k_track_finish(const int32_t *idx, const uint8_t *outlierC, const int32_t *featMp, const int32_t *mpObs, uint8_t *outlierF, int32_t *mpOut,
-                               int countInliers, TrackBlock *blk, const int32_t *searchHeader) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c == 0 && searchHeader) { blk->spec[2] = searchHeader[0]; blk->spec[3] = searchHeader[1]; }
-    if (c >= blk->start[1]) return;
-    const int i = idx[c];
-    mpOut[i] = featMp[i];
-    if (countInliers) {
-        outlierF[i] = outlierC[c];
-        if (!outlierC[c] && mpObs[featMp[i]] > 0) atomicAdd(&blk->counters[1], 1);
-    }
-}
-
-}  // namespace rumi
-
-#include "rumi_internal.h"
-#include "rumi_orb.h"
-#include "rumi_track.h"
-#include "rumi_voc.h"
-
-// Frame::UndistortKeyPoints / ComputeImageBounds (R/lib_src/Frame.cc:770-826): cv::undistortPoints(mat, mat, K, mDistCoef, cv::Mat(), mK) per point,
-// in double, operation by operation as OpenCV 3.4's cvUndistortPointsInternal does it (not in the tree: restated from the published algorithm,
-// parity unpinned; oracle/frame_oracle.cc is the CPU statement the tests compare with): normalise, 5 fixed-point iterations of the inverse
-// radial-tangential model, project with P = K.  Terms that are zero for (k1, k2, p1, p2, k3) keep their place: 0 * r2 is not dropped.
-struct UndistortArgs { double fx, fy, cx, cy, ifx, ify, k1, k2, p1, p2, k3; };
-__host__ __device__ inline void undistort_point(const UndistortArgs &A, float u, float v, float *uo, float *vo) {
-    double x = u, y = v;
-    x = (x - A.cx) * A.ifx; y = (y - A.cy) * A.ify;
-    const double x0 = x, y0 = y;
-    for (int j = 0; j < 5; j++) {
-        const double r2 = x * x + y * y;
-        const double icdist = (1 + ((0 * r2 + 0) * r2 + 0) * r2) / (1 + ((A.k3 * r2 + A.k2) * r2 + A.k1) * r2);
-        const double deltaX = 2 * A.p1 * x * y + A.p2 * (r2 + 2 * x * x) + 0 * r2 + 0 * r2 * r2;
-        const double deltaY = A.p1 * (r2 + 2 * y * y) + 2 * A.p2 * x * y + 0 * r2 + 0 * r2 * r2;
-        x = (x0 - deltaX) * icdist;
-        y = (y0 - deltaY) * icdist;
-    }
-    const double xx = A.fx * x + 0 * y + A.cx, yy = 0 * x + A.fy * y + A.cy, ww = 1. / (0 * x + 0 * y + 1);
-    *uo = (float)(xx * ww); *vo = (float)(yy * ww);
-}
-// mvKeysUn: the extractor's key-points with pt replaced (Frame.cc:791-796); the count is read where the extractor left it (nDev) or given (n)
-__global__ void k_undistort_keys(const int32_t *nDev, int n, const RumiKeyPoint *__restrict__ keys, RumiKeyPoint *__restrict__ keysUn, UndistortArgs A) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (nDev ? *nDev : n)) return;
-    RumiKeyPoint k = keys[i];
-    undistort_point(A, k.x, k.y, &k.x, &k.y);
-    keysUn[i] = k;
-}
-
-struct RumiTracker {
-    int device = 0, cap = 0, maxPts = 0, nlevels = 0;
-    RumiOrbConfig cfg{};
-    RumiOrb *ext = nullptr;
-    RumiMatcher *m = nullptr;
-    uint8_t *dImage = nullptr; size_t imageBytes = 0;
-    hipStream_t upStream = nullptr;      // the step's uploads travel beside the extraction (rumi_track_frame)
-    hipEvent_t evUp = nullptr;
-    uint8_t *hImage = nullptr;           // pinned staging of the caller's (pageable) image: a plain memcpy + one asynchronous copy (the runtime's own
-                                         // staging of a pageable source serialises the call for ~0.1 ms)
-    // ONE device block [TrackBlock | mp cap*4 | mp after the motion model cap*4 | outlier cap | in_view maxPts | record 8 + 60 cap] and its pinned mirror: one copy brings a frame's results back
-    uint8_t *dBlk = nullptr, *hBlk = nullptr; size_t oMp = 0, oMpM = 0, oOut = 0, oView = 0, oRec = 0, blkBytes = 0, recordBytes = 0;
-    float *dInvSigma2 = nullptr, *dXw = nullptr, *dObs = nullptr, *dW = nullptr;
-    int32_t *dIdx = nullptr;
-    uint8_t *dOutC = nullptr, *dActive = nullptr, *dSeen = nullptr, *dBad = nullptr, *dLocal = nullptr, *dStaleIn = nullptr;
-    float *dStaleProj = nullptr;
-    size_t projN16 = 0; int projN = 0;       // the projection arrays the last SearchLocalPoints left in the matcher's staging block (rumi_track_last_projections)
-    double *dChi = nullptr;
-    float scale[64] = {0};
-    // the step-wise entries (rumi_track_extract / _motion / _reference_keyframe / _local): the frame that is resident, and its BoW transform
-    int curN = -1, curW = 0, curH = 0, curMono = -1;
-    // lens distortion (rumi_track_set_distortion): mvKeysUn of the resident frame and the undistorted image bounds (mnMinX .. mnMaxY)
-    bool distort = false;
-    UndistortArgs ua{};
-    RumiKeyPoint *dKeysUn = nullptr;
-    float bounds[4] = {0, 0, 0, 0};
-    // the frame's BoW transform: one block [weight f64 x cap | word u32 x cap | node u32 x cap] and its pinned mirror (one copy back)
-    uint8_t *dBow = nullptr, *hBow = nullptr;
-    uint32_t *dWord = nullptr, *dNode = nullptr; double *dWeight = nullptr; int32_t *dNN = nullptr;
-};
-
-namespace {
-void track_bounds(RumiTracker *t, int w, int h, RumiFrameFeatures *F);
-void track_undistort(RumiTracker *t);
-}  // namespace
-
-extern "C" void rumi_track_destroy(RumiTracker *t) {
-    if (!t) return;
-    (void)hipSetDevice(t->device);
-    rumi_orb_destroy(t->ext);
-    rumi_match_destroy(t->m);
-    void *p[] = {t->dImage, t->dBlk, t->dInvSigma2, t->dXw, t->dObs, t->dW, t->dIdx, t->dOutC, t->dActive, t->dSeen, t->dBad, t->dLocal, t->dChi, t->dBow, t->dNN, t->dStaleIn, t->dStaleProj, t->dKeysUn};
-    for (void *q : p) if (q) (void)hipFree(q);
-    if (t->hBlk) (void)hipHostFree(t->hBlk);
-    if (t->hBow) (void)hipHostFree(t->hBow);
-    if (t->hImage) (void)hipHostFree(t->hImage);
-    if (t->upStream) (void)hipStreamDestroy(t->upStream);
-    if (t->evUp) (void)hipEventDestroy(t->evUp);
-    delete t;
-}
-
-extern "C" int rumi_track_create(const RumiOrbConfig *cfg, int32_t max_points, int32_t device, RumiTracker **out) {
-    if (!out) return RUMI_E_INVALID;
-    *out = nullptr;
-    if (!cfg || max_points < 1 || cfg->nlevels < 1 || cfg->nlevels > 16) return RUMI_E_INVALID;
-    RumiTracker *t = new RumiTracker();
-    t->cfg = *cfg; t->cfg.max_batch = 1; t->cfg.device = device;
-    t->nlevels = cfg->nlevels;
-    t->cap = cfg->nfeatures + 4 * cfg->nlevels + 64;                // what the facade's ORBextractor::operator() reserves
-    t->maxPts = max_points;
-    int rc = rumi_orb_create(&t->cfg, &t->ext);
-    if (rc == RUMI_OK) rc = rumi_match_create(t->cap, std::max(max_points, t->cap), device, &t->m);
-    if (rc != RUMI_OK) { rumi_track_destroy(t); return rc; }
-    t->device = t->m->device;
-    const size_t C = t->cap, P = max_points;
-    auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-    t->imageBytes = (size_t)((cfg->max_width + 3) & ~3) * cfg->max_height;
-    t->recordBytes = 8 + 60 * C;
-    t->oMp = al(sizeof(TrackBlock)); t->oMpM = al(t->oMp + C * 4); t->oOut = al(t->oMpM + C * 4); t->oView = al(t->oOut + C); t->oRec = al(t->oView + P); t->blkBytes = al(t->oRec + t->recordBytes);
-#define TRYA(x) if ((rc = (x)) != RUMI_OK) { rumi_track_destroy(t); return rc; }
-    TRYA(dalloc(&t->dImage, t->imageBytes + 64)); TRYA(dalloc(&t->dBlk, t->blkBytes)); TRYA(dalloc(&t->dInvSigma2, 64));
-    TRYA(dalloc(&t->dXw, C * 3)); TRYA(dalloc(&t->dObs, C * 2)); TRYA(dalloc(&t->dW, C)); TRYA(dalloc(&t->dIdx, C));
-    TRYA(dalloc(&t->dOutC, C)); TRYA(dalloc(&t->dActive, C)); TRYA(dalloc(&t->dSeen, P)); TRYA(dalloc(&t->dBad, P)); TRYA(dalloc(&t->dLocal, P)); TRYA(dalloc(&t->dStaleIn, P)); TRYA(dalloc(&t->dStaleProj, P * 5)); TRYA(dalloc(&t->dChi, C));
-    TRYA(dalloc(&t->dBow, C * 16)); TRYA(dalloc(&t->dNN, 4));
-    t->dWeight = reinterpret_cast<double *>(t->dBow); t->dWord = reinterpret_cast<uint32_t *>(t->dBow + C * 8); t->dNode = t->dWord + C;
-#undef TRYA
-    if (hipHostMalloc((void **)&t->hBlk, t->blkBytes, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void **)&t->hBow, C * 16, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&t->hImage, t->imageBytes + 64, hipHostMallocDefault) != hipSuccess ||
-        hipStreamCreateWithFlags(&t->upStream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&t->evUp, hipEventDisableTiming) != hipSuccess) {
-        rumi_track_destroy(t); return RUMI_E_NO_DEVICE;
-    }
-    float inv2[64] = {0};
-    rumi_orb_tables(cfg, t->scale, nullptr, nullptr, inv2, nullptr, nullptr);
-    if (hipMemcpy(t->dInvSigma2, inv2, sizeof(inv2), hipMemcpyHostToDevice) != hipSuccess) { rumi_track_destroy(t); return RUMI_E_NO_DEVICE; }
-    *out = t;
-    return RUMI_OK;
-}
-
-extern "C" int rumi_track_frame(RumiTracker *t, const uint8_t *img, int32_t w, int32_t h, int32_t stride, const float *K4, const float *Tcw_pred7,
-                                const RumiKeyPoint *last_keys_un, int32_t nlast, const int32_t *last_mp, const uint8_t *last_outlier,
-                                const RumiTrackPoints *pts, float th_motion, float th_local, int32_t far_points, float th_far_points,
-                                RumiKeyPoint *keys_out, uint8_t *desc_out, int32_t cap, int32_t *frame_mp_motion, int32_t *frame_mp, uint8_t *outlier,
-                                uint8_t *in_view, RumiTrackResult *res) {
-    if (!t || !img || !K4 || !Tcw_pred7 || !pts || !res || !keys_out || !desc_out || !frame_mp_motion || !frame_mp || !outlier || nlast < 0 || pts->n < 0 ||
-        stride < w || (nlast > 0 && (!last_keys_un || !last_mp || !last_outlier)) ||
-        (pts->n > 0 && (!pts->pos || !pts->normal || !pts->min_dist || !pts->max_dist || !pts->desc || !pts->obs || !pts->bad || !pts->local || !in_view)))
-        return RUMI_E_INVALID;
-    if (w <= 0 || h <= 0) return RUMI_E_EMPTY;
-    if (w > t->cfg.max_width || h > t->cfg.max_height) { g_lastError = "rumi_track_frame: image larger than the tracker was created for"; return RUMI_E_CAPACITY; }
-    t->curN = -1;
-    RumiMatcher *m = t->m;
-    const int nmp = pts->n;
-    if (nlast > m->maxQ || nmp > t->maxPts || cap < t->cap) { g_lastError = "rumi_track_frame: more points / features than the tracker was created for, or cap too small"; return RUMI_E_CAPACITY; }
-    for (int i = 0; i < nlast; i++) if (last_mp[i] >= nmp) { g_lastError = "rumi_track_frame: last_mp index outside the point table"; return RUMI_E_INVALID; }
-    HIP_TRY(hipSetDevice(t->device));
-    std::memset(res, 0, sizeof(*res));
-    t->projN = 0;
-    res->mono_index = -1; res->th_motion = (int32_t)th_motion;
-    TrackBlock *dB = reinterpret_cast<TrackBlock *>(t->dBlk);
-    int32_t *dMpOut = reinterpret_cast<int32_t *>(t->dBlk + t->oMp), *dMpMotion = reinterpret_cast<int32_t *>(t->dBlk + t->oMpM);
-    uint8_t *dOutF = t->dBlk + t->oOut, *dView = t->dBlk + t->oView, *dRecord = t->dBlk + t->oRec;
-
-    // ---- stage 1: ORBextractor::operator() on the device; only the two counts come back (launch sizes need n)
-    const int wp = (w + 3) & ~3;
-    if (!(img == t->hImage && stride == wp))                // (a caller that captured straight into rumi_track_image_buffer's memory has nothing to stage)
-        for (int y = 0; y < h; y++) std::memcpy(t->hImage + (size_t)y * wp, img + (size_t)y * stride, (size_t)w);      // image -> pinned -> device (async)
-    HIP_TRY(hipMemcpyAsync(t->dImage, t->hImage, (size_t)wp * h, hipMemcpyHostToDevice, nullptr));
-    int rc = rumi_orb_extract_batch_records_async(t->ext, t->dImage, 1, w, h, wp, (int64_t)wp * h, 0, 1000, dRecord, (int64_t)t->recordBytes, t->cap, nullptr);
-    if (rc != RUMI_OK) return rc;
-    track_undistort(t);
-    // ---- uploads of the whole step: one pinned block, one copy, scattered on the device; the frame itself is read where the extractor left it.
-    // None of it depends on the extraction: the host fills the block while the extraction runs, and only then waits for the two counts.
-    RumiFrameFeatures F{};
-    F.n = 0;
-    F.nlevels = t->nlevels; F.scale_factors = t->scale;
-    track_bounds(t, w, h, &F);
-    FrameDev fd;
-    if ((rc = upload_frame(m, &F, &fd)) != RUMI_OK) return rc;
-    float pose[11];
-    std::memcpy(pose, Tcw_pred7, 7 * sizeof(float)); std::memcpy(pose + 7, K4, 4 * sizeof(float));
-    H2D(m->dPose, pose, 11);
-    if (nmp > 0) {
-        H2D(m->dF[0], pts->pos, (size_t)nmp * 3); H2D(m->dF[1], pts->normal, (size_t)nmp * 3); H2D(m->dF[2], pts->min_dist, nmp); H2D(m->dF[3], pts->max_dist, nmp);
-        H2D(m->dI[1], pts->obs, nmp); H2D(m->dQDesc, pts->desc, (size_t)nmp * 32); H2D(t->dBad, pts->bad, nmp); H2D(t->dLocal, pts->local, nmp);
-        if (pts->stale_in_view && pts->stale_proj) { H2D(t->dStaleIn, pts->stale_in_view, nmp); H2D(t->dStaleProj, pts->stale_proj, (size_t)nmp * 5); }
-    }
-    if (nlast > 0) { H2D(m->dQKeys, last_keys_un, nlast); H2D(m->dI[0], last_mp, nlast); H2D(m->dU8a, last_outlier, nlast); }
-    const bool gridWanted = m->gridPending;                 // (the grid needs the feature count: it is built below)
-    m->gridPending = false;
-    static const int envSpec = std::getenv("RUMI_TRACK_SPECULATE") ? std::atoi(std::getenv("RUMI_TRACK_SPECULATE")) : 1;
-    static const bool noFusedLists = std::getenv("RUMI_MATCH_NO_FUSED") != nullptr;
-    const size_t n16 = ((size_t)nmp + 15) & ~(size_t)15;
-    const float logSf = std::log(t->cfg.scale_factor);
-    const bool canSpec = envSpec && !noFusedLists && nlast > 0 && nmp > 0 && m->listCap / (size_t)std::max(nlast, nmp) >= 64 && n16 * 21 <= m->stageCap;
-    const int gC = std::max(1, (t->cap + 255) / 256);
-    m->upStream = t->upStream;                              // the copy and the scatter, on a stream of their own beside the extraction
-    const int rcUp = flush_uploads(m);
-    m->upStream = nullptr;
-    if (rcUp != RUMI_OK) return rcUp;
-    if (canSpec) {
-        // what the usual case (below) needs and the extraction does not feed: the cleared frame (sized by the capacity) and the motion-model queries
-        hipLaunchKernelGGL(k_track_init, dim3(std::max(1, (std::max(t->cap, nmp) + 255) / 256)), dim3(256), 0, t->upStream, t->cap, nmp, 1, m->dFeatMp, m->dOut, t->dSeen, dOutF,
-                           dMpOut, m->dPose, dB);
-        hipLaunchKernelGGL(k_queries_frame, dim3((nlast + 255) / 256), dim3(256), 0, t->upStream, nlast, m->dQKeys, m->dI[0], m->dU8a, m->dF[0], m->dI[1], m->dPose,
-                           m->dPose + 7, m->dScale, th_motion, fd.minX, fd.minY, fd.maxX, fd.maxY, m->dQ);
-    }
-    HIP_TRY(hipEventRecord(t->evUp, t->upStream));
-    HIP_TRY(hipStreamWaitEvent(nullptr, t->evUp, 0));      // (behind the extraction in the main queue: by then the event has long fired)
-    // ---- the usual case in ONE queue, no host round trip: the first search finds >= 20 matches and no candidate list overflows.  Every launch
-    // of stages 2-5 goes out back to back behind the extraction -- the feature count and the searches' counts stay on the device (launches are
-    // sized by their upper bounds), the searches' result headers are kept in the block -- the block comes back once, and only if a header says
-    // otherwise (fewer than 20 matches: the 2 th retry; a list overflow; no key-point at all) the step is redone stage by stage.
-    int n = t->cap;                                          // an upper bound until the two counts have been read
-    auto take_counts = [&](const int32_t *counts) {
-        n = counts[0];
-        res->n = n; res->mono_index = counts[1];
-        t->curN = n; t->curW = w; t->curH = h; t->curMono = counts[1];      // the frame is resident for the step-wise entries too
-    };
-    if (!canSpec) {
-        int32_t counts[2] = {0, -1};
-        HIP_TRY(hipMemcpy(counts, dRecord, 8, hipMemcpyDeviceToHost));
-        if ((rc = rumi_orb_sync(t->ext)) != RUMI_OK) return rc;
-        take_counts(counts);
-    }
-    const RumiKeyPoint *dKp = t->distort ? t->dKeysUn : reinterpret_cast<const RumiKeyPoint *>(dRecord + 8);      // mvKeysUn: what every stage below reads
-    const uint8_t *dDs = dRecord + 8 + (size_t)t->cap * sizeof(RumiKeyPoint);
-    fd.n = n; fd.keys = dKp; fd.desc = dDs;
-    m->gridN = n; m->gridKeys = dKp; m->gridNDev = canSpec ? reinterpret_cast<const int32_t *>(dRecord) : nullptr;
-    m->gridPending = gridWanted;
-    FLUSH(m);                                               // the grid of the resident frame
-    int gI = std::max(1, (std::max(std::max(n, nmp), 4) + 255) / 256);
-    if (!canSpec) hipLaunchKernelGGL(k_track_init, dim3(gI), dim3(256), 0, nullptr, n, nmp, 1, m->dFeatMp, m->dOut, t->dSeen, dOutF, dMpOut, m->dPose, dB);
-    bool small = n <= kTrackLdsEdges;                       // the frame's correspondences fit the LDS instantiation of k_pose_opt for sure
-    bool done = false;
-    if (canSpec) {
-        auto search = [&](int mode, int nq, float nnratio, int checkOri) -> int {
-            const int rcl = build_lists(m, mode, nq, fd, m->dQDesc, false, true);
-            if (rcl != RUMI_OK) return rcl;
-            // (the search ends with the gather of PoseOptimization's correspondences: k_resolve's tail)
-            ResolveArgs A{mode, nq, fd.n, m->dQ, m->dCounts, m->dOffsets, m->dLists, fd.keys, m->dI[1], m->dFeatMp, m->dAssign, m->dNmatches,
-                          nnratio, checkOri, nullptr, 0.f, 0, m->dOverflow, m->dF[0], t->dInvSigma2, t->dXw, t->dObs, t->dW, t->dIdx, dB->start, nullptr};
-            hipLaunchKernelGGL(k_resolve, dim3(1), dim3(1024), (size_t)std::max(fd.n, 1) * sizeof(int32_t), nullptr, A);
-            return RUMI_OK;
-        };
-        if ((rc = search(MODE_FRAME, nlast, 0.f, 1)) != RUMI_OK) return rc;      // (its queries were built beside the extraction, above)
-        if ((rc = rumi::pose_opt_device(dB->start, t->dXw, t->dObs, t->dW, m->dPose + 7, m->dPose, dB->Tout, t->dOutC, dB->nGood, t->dActive, t->dChi, small, nullptr)) != RUMI_OK) return rc;
-        uint8_t *dSkip = m->dU8b;
-        float *dX = reinterpret_cast<float *>(m->dStage + n16), *dY = dX + n16, *dC = dY + n16, *dD = dC + n16;
-        int32_t *dL = reinterpret_cast<int32_t *>(dD + n16);
-        { const FrustumArgs FA{nmp, n, m->dFeatMp, dMpMotion, t->dLocal, t->dSeen, t->dBad, dSkip, m->dOut, dB->pose19, fd.minX,
-                           fd.minY, fd.maxX, fd.maxY, logSf, t->nlevels, 0.5f, m->dF[0], m->dF[1], m->dF[2], m->dF[3], dView, dX, dY, dL, dC, dD,
-                           m->dI[1], m->dScale, th_local, far_points, th_far_points, m->dQ,
-                           (pts->stale_in_view && pts->stale_proj) ? t->dStaleIn : nullptr, (pts->stale_in_view && pts->stale_proj) ? t->dStaleProj : nullptr};
-          hipLaunchKernelGGL(k_track_after_motion, dim3(gC), dim3(256), 0, nullptr, t->dIdx, t->dOutC, m->dFeatMp, m->dI[1], t->dBad, t->dSeen, m->dPose + 7, dB, (const int32_t *)m->dOut);
-          // (both as ONE 1024-thread workgroup -- the frustum test reads the seen flags and the pose matrices the first half writes -- measured: 0.427-0.436 ms
-          // against 0.430-0.431 for the frame, no gain; not kept)
-          hipLaunchKernelGGL(k_track_frustum, dim3(gI), dim3(256), 0, nullptr, FA); t->projN16 = n16; t->projN = nmp; }
-        if ((rc = search(MODE_MAPPOINTS, nmp, 0.8f, 0)) != RUMI_OK) return rc;
-        if ((rc = rumi::pose_opt_device(dB->start, t->dXw, t->dObs, t->dW, m->dPose + 7, dB->Tout, dB->Tout + 7, t->dOutC, dB->nGood + 1, t->dActive, t->dChi, small, nullptr)) != RUMI_OK) return rc;
-        hipLaunchKernelGGL(k_track_finish, dim3(gC), dim3(256), 0, nullptr, t->dIdx, t->dOutC, m->dFeatMp, m->dI[1], dOutF, dMpOut, 1, dB, (const int32_t *)m->dOut);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(t->hBlk, t->dBlk, t->oRec + 8 + (size_t)t->cap * sizeof(RumiKeyPoint) + (size_t)n * 32, hipMemcpyDeviceToHost));
-        if ((rc = rumi_orb_sync(t->ext)) != RUMI_OK) return rc;
-        take_counts(reinterpret_cast<const int32_t *>(t->hBlk + t->oRec));
-        const TrackBlock *hS = reinterpret_cast<const TrackBlock *>(t->hBlk);
-        if (n > 0 && hS->spec[0] >= 20 && hS->spec[1] == 0 && hS->spec[3] == 0) {
-            res->nmatches_motion = hS->spec[0];
-            res->nmatches_local = hS->spec[2];
-            done = true;
-        } else {
-            // not the usual case: start over from the cleared frame (the staged inputs and the frame's grid are still on the device)
-            fd.n = n; m->gridN = n;
-            gI = std::max(1, (std::max(std::max(n, nmp), 4) + 255) / 256);
-            small = n <= kTrackLdsEdges;
-            hipLaunchKernelGGL(k_track_init, dim3(gI), dim3(256), 0, nullptr, n, nmp, 1, m->dFeatMp, m->dOut, t->dSeen, dOutF, dMpOut, m->dPose, dB);
-        }
-    }
-    bool localRan = done;
-    if (!done) {
-    // ---- stage 2: SearchByProjection(Cur, Last, th, mono), once more with 2 * th below 20 matches (Tracking.cc:2466-2474)
-    int nm = 0;
-    std::vector<int32_t> tmpMp((size_t)std::max(n, 1));
-    for (int attempt = 0; attempt < 2 && n > 0 && nlast > 0 && nmp > 0; attempt++) {
-        const float th = attempt == 0 ? th_motion : 2 * th_motion;
-        if (attempt == 1) hipLaunchKernelGGL(k_track_init, dim3(gI), dim3(256), 0, nullptr, n, nmp, 0, m->dFeatMp, m->dOut, t->dSeen, dOutF, dMpOut, m->dPose, dB);
-        hipLaunchKernelGGL(k_queries_frame, dim3((nlast + 255) / 256), dim3(256), 0, nullptr, nlast, m->dQKeys, m->dI[0], m->dU8a, m->dF[0], m->dI[1], m->dPose,
-                           m->dPose + 7, m->dScale, th, fd.minX, fd.minY, fd.maxX, fd.maxY, m->dQ);
-        if ((rc = run_search(m, MODE_FRAME, nlast, fd, m->dQDesc, m->dI[1], 0.f, 1, tmpMp.data(), &nm)) != RUMI_OK) return rc;
-        res->th_motion = (int32_t)th;
-        if (nm >= 20) break;
-    }
-    res->nmatches_motion = nm;
-    if (nm >= 20) {
-        // ---- stage 3: PoseOptimization on the matches, outliers leave the frame
-        hipLaunchKernelGGL(k_track_gather, dim3(1), dim3(1024), 0, nullptr, n, dKp, m->dFeatMp, m->dF[0], t->dInvSigma2, t->dXw, t->dObs, t->dW, t->dIdx, dB->start);
-        if ((rc = rumi::pose_opt_device(dB->start, t->dXw, t->dObs, t->dW, m->dPose + 7, m->dPose, dB->Tout, t->dOutC, dB->nGood, t->dActive, t->dChi, small, nullptr)) != RUMI_OK) return rc;
-        hipLaunchKernelGGL(k_track_after_motion, dim3(gC), dim3(256), 0, nullptr, t->dIdx, t->dOutC, m->dFeatMp, m->dI[1], t->dBad, t->dSeen, m->dPose + 7, dB, (const int32_t *)nullptr);
-        // ---- stage 4: SearchLocalPoints with the optimised pose
-        if (n16 * 21 > m->stageCap) { g_lastError = "rumi_track_frame: point table exceeds the staging block"; return RUMI_E_CAPACITY; }
-        uint8_t *dSkip = m->dU8b;
-        float *dX = reinterpret_cast<float *>(m->dStage + n16), *dY = dX + n16, *dC = dY + n16, *dD = dC + n16;
-        int32_t *dL = reinterpret_cast<int32_t *>(dD + n16);
-        { const FrustumArgs FA{nmp, n, m->dFeatMp, dMpMotion, t->dLocal, t->dSeen, t->dBad, dSkip, m->dOut, dB->pose19, fd.minX,
-                           fd.minY, fd.maxX, fd.maxY, logSf, t->nlevels, 0.5f, m->dF[0], m->dF[1], m->dF[2], m->dF[3], dView, dX, dY, dL, dC, dD,
-                           m->dI[1], m->dScale, th_local, far_points, th_far_points, m->dQ,
-                           (pts->stale_in_view && pts->stale_proj) ? t->dStaleIn : nullptr, (pts->stale_in_view && pts->stale_proj) ? t->dStaleProj : nullptr};
-          hipLaunchKernelGGL(k_track_frustum, dim3(gI), dim3(256), 0, nullptr, FA); t->projN16 = n16; t->projN = nmp; }
-        int nmLocal = 0;
-        if ((rc = run_search(m, MODE_MAPPOINTS, nmp, fd, m->dQDesc, m->dI[1], 0.8f, 0, tmpMp.data(), &nmLocal)) != RUMI_OK) return rc;
-        res->nmatches_local = nmLocal;
-        localRan = true;
-        // ---- stage 5: PoseOptimization on everything the frame now holds
-        hipLaunchKernelGGL(k_track_gather, dim3(1), dim3(1024), 0, nullptr, n, dKp, m->dFeatMp, m->dF[0], t->dInvSigma2, t->dXw, t->dObs, t->dW, t->dIdx, dB->start);
-        if ((rc = rumi::pose_opt_device(dB->start, t->dXw, t->dObs, t->dW, m->dPose + 7, dB->Tout, dB->Tout + 7, t->dOutC, dB->nGood + 1, t->dActive, t->dChi, small, nullptr)) != RUMI_OK) return rc;
-        hipLaunchKernelGGL(k_track_finish, dim3(gC), dim3(256), 0, nullptr, t->dIdx, t->dOutC, m->dFeatMp, m->dI[1], dOutF, dMpOut, 1, dB, (const int32_t *)nullptr);
-    } else if (nm > 0) {                                       // fewer than 20 matches: the frame keeps them (the caller falls back to TrackReferenceKeyFrame)
-        hipLaunchKernelGGL(k_track_gather, dim3(1), dim3(1024), 0, nullptr, n, dKp, m->dFeatMp, m->dF[0], t->dInvSigma2, t->dXw, t->dObs, t->dW, t->dIdx, dB->start);
-        hipLaunchKernelGGL(k_track_finish, dim3(gC), dim3(256), 0, nullptr, t->dIdx, t->dOutC, m->dFeatMp, m->dI[1], dOutF, dMpOut, 0, dB, (const int32_t *)nullptr);
-    }
-    // ---- one copy back: header, mvpMapPoints, mvbOutlier, mbTrackInView and the extractor's record
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(t->hBlk, t->dBlk, t->oRec + 8 + (size_t)t->cap * sizeof(RumiKeyPoint) + (size_t)n * 32, hipMemcpyDeviceToHost));
-    }
-    const TrackBlock *hB = reinterpret_cast<const TrackBlock *>(t->hBlk);
-    std::memcpy(res->Tcw_motion, hB->Tout, 28); std::memcpy(res->Tcw, hB->Tout + 7, 28);
-    std::memcpy(res->Rcw, hB->pose19, 36); std::memcpy(res->tcw, hB->pose19 + 9, 12); std::memcpy(res->Ow, hB->pose19 + 12, 12);
-    res->ngood_motion = hB->nGood[0]; res->ngood_local = hB->nGood[1]; res->nmatches_map = hB->counters[0]; res->matches_inliers = hB->counters[1];
-    if (n > 0) {
-        std::memcpy(frame_mp, t->hBlk + t->oMp, (size_t)n * 4); std::memcpy(outlier, t->hBlk + t->oOut, (size_t)n);
-        std::memcpy(keys_out, t->hBlk + t->oRec + 8, (size_t)n * sizeof(RumiKeyPoint));
-        std::memcpy(desc_out, t->hBlk + t->oRec + 8 + (size_t)t->cap * sizeof(RumiKeyPoint), (size_t)n * 32);
-    }
-    int nTo = 0;
-    if (nmp > 0) {
-        if (localRan) std::memcpy(in_view, t->hBlk + t->oView, (size_t)nmp); else std::memset(in_view, 0, (size_t)nmp);
-        for (int j = 0; j < nmp; j++) nTo += in_view[j] == 1;         // (2: a stale flag of an earlier frame, not an isInFrustum of this one)
-    }
-    res->n_to_match = nTo;
-    if (n > 0) std::memcpy(frame_mp_motion, localRan ? t->hBlk + t->oMpM : t->hBlk + t->oMp, (size_t)n * 4);
-    return RUMI_OK;
-}
-
-// ==================================================================================================================
-// The same stages one member function of Tracking at a time (include/rumi_track.h, "step-wise entries"): the frame extracted by
-// rumi_track_extract stays on the device -- key-points, descriptors, grid, FeatureVector -- while the host runs the reference's own control
-// flow between the calls (the decisions of TrackWithMotionModel / TrackReferenceKeyFrame, UpdateLocalMap).
-// ==================================================================================================================
-namespace {
-// Frame::ComputeImageBounds (Frame.cc:799-826): the image rectangle, or the undistorted corners' hull with lens distortion
-void track_bounds(RumiTracker *t, int w, int h, RumiFrameFeatures *F) {
-    if (!t->distort) { t->bounds[0] = 0; t->bounds[1] = 0; t->bounds[2] = (float)w; t->bounds[3] = (float)h; }
-    else {
-        const float c[8] = {0, 0, (float)w, 0, 0, (float)h, (float)w, (float)h};
-        float u[8];
-        for (int i = 0; i < 4; i++) undistort_point(t->ua, c[2 * i], c[2 * i + 1], &u[2 * i], &u[2 * i + 1]);
-        t->bounds[0] = std::min(u[0], u[4]); t->bounds[2] = std::max(u[2], u[6]);
-        t->bounds[1] = std::min(u[1], u[3]); t->bounds[3] = std::max(u[5], u[7]);
-    }
-    F->min_x = t->bounds[0]; F->min_y = t->bounds[1]; F->max_x = t->bounds[2]; F->max_y = t->bounds[3];
-}
-// mvKeysUn of the frame the extractor has just been asked for (same queue, behind the extraction)
-void track_undistort(RumiTracker *t) {
-    if (!t->distort) return;
-    const uint8_t *dRecord = t->dBlk + t->oRec;
-    hipLaunchKernelGGL(k_undistort_keys, dim3((t->cap + 255) / 256), dim3(256), 0, nullptr, reinterpret_cast<const int32_t *>(dRecord), t->cap,
-                       reinterpret_cast<const RumiKeyPoint *>(dRecord + 8), t->dKeysUn, t->ua);
-}
-// the resident frame as the matcher's kernels address it (upload_frame of an empty frame queues the scale table and the cleared result header)
-int track_frame_dev(RumiTracker *t, FrameDev *fd) {
-    RumiMatcher *m = t->m;
-    RumiFrameFeatures F{};
-    F.n = 0; F.nlevels = t->nlevels; F.scale_factors = t->scale;
-    track_bounds(t, t->curW, t->curH, &F);
-    const int rc = upload_frame(m, &F, fd);
-    if (rc != RUMI_OK) return rc;
-    const uint8_t *dRecord = t->dBlk + t->oRec;
-    fd->n = t->curN;
-    fd->keys = t->distort ? t->dKeysUn : reinterpret_cast<const RumiKeyPoint *>(dRecord + 8);
-    fd->desc = dRecord + 8 + (size_t)t->cap * sizeof(RumiKeyPoint);
-    m->gridN = t->curN; m->gridKeys = fd->keys;
-    return RUMI_OK;
-}
-int track_check_points(const RumiTrackPoints *pts, bool needFrustum) {
-    if (!pts || pts->n < 0) return RUMI_E_INVALID;
-    if (pts->n > 0 && (!pts->pos || !pts->desc || !pts->obs || !pts->bad)) return RUMI_E_INVALID;
-    if (pts->n > 0 && needFrustum && (!pts->normal || !pts->min_dist || !pts->max_dist || !pts->local)) return RUMI_E_INVALID;
-    return RUMI_OK;
-}
-}  // namespace
-
-// The tracker's pinned staging buffer for a w x h frame, for a caller that lets its camera driver / decoder write the frame there (e.g. a
-// cv::Mat constructed on this memory): rumi_track_frame / rumi_track_extract called with this pointer and stride skip their staging copy.
-extern "C" int rumi_track_image_buffer(RumiTracker *t, int32_t w, int32_t h, uint8_t **buf, int32_t *stride) {
-    if (!t || !buf || !stride) return RUMI_E_INVALID;
-    if (w <= 0 || h <= 0 || w > t->cfg.max_width || h > t->cfg.max_height) { g_lastError = "rumi_track_image_buffer: frame larger than the tracker was created for"; return RUMI_E_CAPACITY; }
-    *buf = t->hImage; *stride = (w + 3) & ~3;
-    return RUMI_OK;
-}
-
-extern "C" int rumi_track_extract(RumiTracker *t, const uint8_t *img, int32_t w, int32_t h, int32_t stride, RumiKeyPoint *keys_out, uint8_t *desc_out,
-                                  int32_t cap, int32_t *n_out, int32_t *mono_out) {
-    if (!t || !img || !keys_out || !desc_out || !n_out || !mono_out || stride < w) return RUMI_E_INVALID;
-    *n_out = 0; *mono_out = -1;
-    if (w <= 0 || h <= 0) return RUMI_E_EMPTY;
-    if (w > t->cfg.max_width || h > t->cfg.max_height || cap < t->cap) { g_lastError = "rumi_track_extract: image larger than the tracker was created for, or cap too small"; return RUMI_E_CAPACITY; }
-    HIP_TRY(hipSetDevice(t->device));
-    t->curN = -1;
-    uint8_t *dRecord = t->dBlk + t->oRec;
-    const int wp = (w + 3) & ~3;
-    if (!(img == t->hImage && stride == wp))                // (a caller that captured straight into rumi_track_image_buffer's memory has nothing to stage)
-        for (int y = 0; y < h; y++) std::memcpy(t->hImage + (size_t)y * wp, img + (size_t)y * stride, (size_t)w);      // image -> pinned -> device (async)
-    HIP_TRY(hipMemcpyAsync(t->dImage, t->hImage, (size_t)wp * h, hipMemcpyHostToDevice, nullptr));
-    int rc = rumi_orb_extract_batch_records_async(t->ext, t->dImage, 1, w, h, wp, (int64_t)wp * h, 0, 1000, dRecord, (int64_t)t->recordBytes, t->cap, nullptr);
-    if (rc != RUMI_OK) return rc;
-    track_undistort(t);
-    int32_t counts[2] = {0, -1};
-    HIP_TRY(hipMemcpy(counts, dRecord, 8, hipMemcpyDeviceToHost));
-    if ((rc = rumi_orb_sync(t->ext)) != RUMI_OK) return rc;
-    const int n = counts[0];
-    if (n > 0) {
-        HIP_TRY(hipMemcpyAsync(t->hBlk + t->oRec + 8, dRecord + 8, (size_t)n * sizeof(RumiKeyPoint), hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(hipMemcpy(t->hBlk + t->oRec + 8 + (size_t)t->cap * sizeof(RumiKeyPoint), dRecord + 8 + (size_t)t->cap * sizeof(RumiKeyPoint), (size_t)n * 32, hipMemcpyDeviceToHost));
-        std::memcpy(keys_out, t->hBlk + t->oRec + 8, (size_t)n * sizeof(RumiKeyPoint));
-        std::memcpy(desc_out, t->hBlk + t->oRec + 8 + (size_t)t->cap * sizeof(RumiKeyPoint), (size_t)n * 32);
-    }
-    t->curN = n; t->curW = w; t->curH = h; t->curMono = counts[1];
-    { RumiFrameFeatures Fb{}; track_bounds(t, w, h, &Fb); }    // mnMinX .. mnMaxY of this frame (rumi_track_undistorted)
-    *n_out = n; *mono_out = counts[1];
-    return RUMI_OK;
-}
-
-extern "C" int rumi_track_motion(RumiTracker *t, const float *K4, const float *Tcw_pred7, const RumiKeyPoint *last_keys_un, int32_t nlast,
-                                 const int32_t *last_mp, const uint8_t *last_outlier, const RumiTrackPoints *pts, float th_motion, int32_t *frame_mp,
-                                 int32_t *discarded, RumiTrackResult *res) {
-    if (!t || !K4 || !Tcw_pred7 || !res || !frame_mp || !discarded || nlast < 0 || (nlast > 0 && (!last_keys_un || !last_mp || !last_outlier)) ||
-        track_check_points(pts, false) != RUMI_OK)
-        return RUMI_E_INVALID;
-    if (t->curN < 0) { g_lastError = "rumi_track_motion: no frame is resident (rumi_track_extract first)"; return RUMI_E_INVALID; }
-    RumiMatcher *m = t->m;
-    const int n = t->curN, nmp = pts->n;
-    if (nlast > m->maxQ || nmp > t->maxPts) { g_lastError = "rumi_track_motion: more points / features than the tracker was created for"; return RUMI_E_CAPACITY; }
-    for (int i = 0; i < nlast; i++) if (last_mp[i] >= nmp) { g_lastError = "rumi_track_motion: last_mp index outside the point table"; return RUMI_E_INVALID; }
-    HIP_TRY(hipSetDevice(t->device));
-    std::memset(res, 0, sizeof(*res));
-    t->projN = 0;
-    res->n = n; res->mono_index = t->curMono; res->th_motion = (int32_t)th_motion;
-    std::memcpy(res->Tcw_motion, Tcw_pred7, 28); std::memcpy(res->Tcw, Tcw_pred7, 28);
-    for (int i = 0; i < n; i++) { frame_mp[i] = -1; discarded[i] = -1; }
-    TrackBlock *dB = reinterpret_cast<TrackBlock *>(t->dBlk);
-    int32_t *dMpOut = reinterpret_cast<int32_t *>(t->dBlk + t->oMp);
-    uint8_t *dOutF = t->dBlk + t->oOut;
-    FrameDev fd;
-    int rc = track_frame_dev(t, &fd);
-    if (rc != RUMI_OK) return rc;
-    float pose[11];
-    std::memcpy(pose, Tcw_pred7, 7 * sizeof(float)); std::memcpy(pose + 7, K4, 4 * sizeof(float));
-    H2D(m->dPose, pose, 11);
-    if (nmp > 0) { H2D(m->dF[0], pts->pos, (size_t)nmp * 3); H2D(m->dI[1], pts->obs, nmp); H2D(m->dQDesc, pts->desc, (size_t)nmp * 32); }
-    if (nlast > 0) { H2D(m->dQKeys, last_keys_un, nlast); H2D(m->dI[0], last_mp, nlast); H2D(m->dU8a, last_outlier, nlast); }
-    FLUSH(m);
-    const int gI = std::max(1, (std::max(std::max(n, nmp), 4) + 255) / 256), gC = std::max(1, (t->cap + 255) / 256);
-    hipLaunchKernelGGL(k_track_init, dim3(gI), dim3(256), 0, nullptr, n, nmp, 1, m->dFeatMp, m->dOut, t->dSeen, dOutF, dMpOut, m->dPose, dB);
-    const bool small = n <= kTrackLdsEdges;
-    // the usual case (>= 20 matches at th, no list overflow) in one queue, as in rumi_track_frame: the search's result header and the map-point
-    // vector it leaves travel back with the results; anything else is redone stage by stage below
-    static const int envSpec = std::getenv("RUMI_TRACK_SPECULATE") ? std::atoi(std::getenv("RUMI_TRACK_SPECULATE")) : 1;
-    static const bool noFusedLists = std::getenv("RUMI_MATCH_NO_FUSED") != nullptr;
-    if (envSpec && !noFusedLists && n > 0 && nlast > 0 && nmp > 0 && m->listCap / (size_t)nlast >= 64) {
-        int32_t *dSnap = reinterpret_cast<int32_t *>(t->dBlk + t->oMpM);
-        hipLaunchKernelGGL(k_queries_frame, dim3((nlast + 255) / 256), dim3(256), 0, nullptr, nlast, m->dQKeys, m->dI[0], m->dU8a, m->dF[0], m->dI[1], m->dPose,
-                           m->dPose + 7, m->dScale, th_motion, fd.minX, fd.minY, fd.maxX, fd.maxY, m->dQ);
-        if ((rc = build_lists(m, MODE_FRAME, nlast, fd, m->dQDesc, false, true)) != RUMI_OK) return rc;
-        ResolveArgs A{MODE_FRAME, nlast, fd.n, m->dQ, m->dCounts, m->dOffsets, m->dLists, fd.keys, m->dI[1], m->dFeatMp, m->dAssign, m->dNmatches,
-                      0.f, 1, nullptr, 0.f, 0, m->dOverflow, m->dF[0], t->dInvSigma2, t->dXw, t->dObs, t->dW, t->dIdx, dB->start, dSnap};   // (ends with the gather)
-        hipLaunchKernelGGL(k_resolve, dim3(1), dim3(1024), (size_t)std::max(fd.n, 1) * sizeof(int32_t), nullptr, A);
-        if ((rc = rumi::pose_opt_device(dB->start, t->dXw, t->dObs, t->dW, m->dPose + 7, m->dPose, dB->Tout, t->dOutC, dB->nGood, t->dActive, t->dChi, small, nullptr)) != RUMI_OK) return rc;
-        hipLaunchKernelGGL(k_track_discard, dim3(gC), dim3(256), 0, nullptr, t->dIdx, t->dOutC, m->dFeatMp, m->dI[1], dB, (const int32_t *)m->dOut);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(t->hBlk + t->oMp, m->dFeatMp, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(hipMemcpyAsync(t->hBlk + t->oMpM, dSnap, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
-        HIP_TRY(hipMemcpy(t->hBlk, t->dBlk, sizeof(TrackBlock), hipMemcpyDeviceToHost));
-        const TrackBlock *hS = reinterpret_cast<const TrackBlock *>(t->hBlk);
-        if (hS->spec[0] >= 20 && hS->spec[1] == 0) {
-            res->nmatches_motion = hS->spec[0];
-            std::memcpy(res->Tcw_motion, hS->Tout, 28); std::memcpy(res->Tcw, hS->Tout, 28);
-            res->ngood_motion = hS->nGood[0]; res->nmatches_map = hS->counters[0];
-            const int32_t *before = reinterpret_cast<const int32_t *>(t->hBlk + t->oMpM), *after = reinterpret_cast<const int32_t *>(t->hBlk + t->oMp);
-            for (int i = 0; i < n; i++) { if (before[i] >= 0 && after[i] < 0) discarded[i] = before[i]; frame_mp[i] = after[i]; }
-            return RUMI_OK;
-        }
-        hipLaunchKernelGGL(k_track_init, dim3(gI), dim3(256), 0, nullptr, n, nmp, 1, m->dFeatMp, m->dOut, t->dSeen, dOutF, dMpOut, m->dPose, dB);
-    }
-    int nm = 0;
-    std::vector<int32_t> searched((size_t)std::max(n, 1), -1);
-    for (int attempt = 0; attempt < 2 && n > 0 && nlast > 0 && nmp > 0; attempt++) {      // Tracking.cc:2466-2474
-        const float th = attempt == 0 ? th_motion : 2 * th_motion;
-        if (attempt == 1) hipLaunchKernelGGL(k_track_init, dim3(gI), dim3(256), 0, nullptr, n, nmp, 0, m->dFeatMp, m->dOut, t->dSeen, dOutF, dMpOut, m->dPose, dB);
-        hipLaunchKernelGGL(k_queries_frame, dim3((nlast + 255) / 256), dim3(256), 0, nullptr, nlast, m->dQKeys, m->dI[0], m->dU8a, m->dF[0], m->dI[1], m->dPose,
-                           m->dPose + 7, m->dScale, th, fd.minX, fd.minY, fd.maxX, fd.maxY, m->dQ);
-        if ((rc = run_search(m, MODE_FRAME, nlast, fd, m->dQDesc, m->dI[1], 0.f, 1, searched.data(), &nm)) != RUMI_OK) return rc;
-        res->th_motion = (int32_t)th;
-        if (nm >= 20) break;
-    }
-    res->nmatches_motion = nm;
-    if (n > 0) std::memcpy(frame_mp, searched.data(), (size_t)n * 4);
-    if (nm < 20) return RUMI_OK;                                  // TrackWithMotionModel returns false here (:2476-2483): nothing else has happened to the frame
-    hipLaunchKernelGGL(k_track_gather, dim3(1), dim3(1024), 0, nullptr, n, fd.keys, m->dFeatMp, m->dF[0], t->dInvSigma2, t->dXw, t->dObs, t->dW, t->dIdx, dB->start);
-    if ((rc = rumi::pose_opt_device(dB->start, t->dXw, t->dObs, t->dW, m->dPose + 7, m->dPose, dB->Tout, t->dOutC, dB->nGood, t->dActive, t->dChi, small, nullptr)) != RUMI_OK) return rc;
-    hipLaunchKernelGGL(k_track_discard, dim3(gC), dim3(256), 0, nullptr, t->dIdx, t->dOutC, m->dFeatMp, m->dI[1], dB);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(t->hBlk + t->oMp, m->dFeatMp, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpy(t->hBlk, t->dBlk, sizeof(TrackBlock), hipMemcpyDeviceToHost));
-    const TrackBlock *hB = reinterpret_cast<const TrackBlock *>(t->hBlk);
-    std::memcpy(res->Tcw_motion, hB->Tout, 28); std::memcpy(res->Tcw, hB->Tout, 28);
-    res->ngood_motion = hB->nGood[0]; res->nmatches_map = hB->counters[0];
-    const int32_t *after = reinterpret_cast<const int32_t *>(t->hBlk + t->oMp);
-    for (int i = 0; i < n; i++) { if (searched[i] >= 0 && after[i] < 0) discarded[i] = searched[i]; frame_mp[i] = after[i]; }
-    return RUMI_OK;
-}
-
-extern "C" int rumi_track_reference_keyframe(RumiTracker *t, RumiVocabulary *voc, int32_t levelsup, const float *K4, const float *Tcw_init7,
-                                             const RumiFrameFeatures *KF, const RumiFeatureVector *kf_fv, const int32_t *kf_mp,
-                                             const RumiTrackPoints *pts, float nnratio, int32_t check_orientation, uint32_t *word_id, double *word_weight,
-                                             uint32_t *node_id, int32_t *frame_mp, int32_t *discarded, RumiTrackResult *res) {
-    if (!t || !voc || !K4 || !Tcw_init7 || !KF || !kf_fv || !res || !frame_mp || !discarded || !word_id || !word_weight || !node_id || KF->n < 0 ||
-        kf_fv->n_nodes < 0 || (KF->n > 0 && (!kf_mp || !KF->keys_un || !KF->desc)) || track_check_points(pts, false) != RUMI_OK)
-        return RUMI_E_INVALID;
-    if (t->curN < 0) { g_lastError = "rumi_track_reference_keyframe: no frame is resident (rumi_track_extract first)"; return RUMI_E_INVALID; }
-    RumiMatcher *m = t->m;
-    const int n = t->curN, nmp = pts->n;
-    const int nqe = kf_fv->n_nodes > 0 ? kf_fv->offsets[kf_fv->n_nodes] : 0;
-    if (KF->n > m->maxQ || nqe > m->maxQ || nmp > t->maxPts || nmp > m->maxQ || kf_fv->n_nodes > m->maxQ) {
-        g_lastError = "rumi_track_reference_keyframe: sizes exceed the tracker's capacities"; return RUMI_E_CAPACITY;
-    }
-    for (int i = 0; i < KF->n; i++) if (kf_mp[i] >= nmp) { g_lastError = "rumi_track_reference_keyframe: kf_mp index outside the point table"; return RUMI_E_INVALID; }
-    HIP_TRY(hipSetDevice(t->device));
-    std::memset(res, 0, sizeof(*res));
-    t->projN = 0;
-    res->n = n; res->mono_index = t->curMono;
-    std::memcpy(res->Tcw_motion, Tcw_init7, 28); std::memcpy(res->Tcw, Tcw_init7, 28);
-    for (int i = 0; i < n; i++) { frame_mp[i] = -1; discarded[i] = -1; }
-    if (n == 0) return RUMI_OK;
-    TrackBlock *dB = reinterpret_cast<TrackBlock *>(t->dBlk);
-    int32_t *dMpOut = reinterpret_cast<int32_t *>(t->dBlk + t->oMp);
-    uint8_t *dOutF = t->dBlk + t->oOut;
-    const uint8_t *dRecord = t->dBlk + t->oRec;
-    // ---- Frame::ComputeBoW (Frame.cc:763-768): the tree descent of every descriptor, then the FeatureVector, both on the device
-    int rc = rumi_voc_transform_batch_device(voc, dRecord + 8 + (size_t)t->cap * sizeof(RumiKeyPoint), dRecord, 1, t->cap, levelsup, t->dWord, t->dWeight, t->dNode, nullptr);
-    if (rc != RUMI_OK) return rc;
-    int npad = 1;
-    while (npad < n) npad <<= 1;
-    const size_t fvLds = (size_t)npad * sizeof(unsigned long long);
-    if (fvLds > 64 * 1024) HIP_TRY(raise_lds_limit(reinterpret_cast<const void *>(k_fv_build), fvLds));
-    hipLaunchKernelGGL(k_fv_build, dim3(1), dim3(kFvThreads), fvLds, nullptr, n, npad, t->dNode, t->dWeight, m->dNodesB, m->dOffB, m->dFvIdx, t->dNN);
-    // ---- SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:198-370): the key-frame side comes from the host, the frame side is resident
-    FrameDev fd;
-    if ((rc = track_frame_dev(t, &fd)) != RUMI_OK) return rc;
-    float pose[11];
-    std::memcpy(pose, Tcw_init7, 7 * sizeof(float)); std::memcpy(pose + 7, K4, 4 * sizeof(float));
-    H2D(m->dPose, pose, 11);
-    if (KF->n > 0) { H2D(m->dQKeys, KF->keys_un, KF->n); H2D(m->dQDesc, KF->desc, (size_t)KF->n * 32); H2D(m->dI[0], kf_mp, KF->n); }
-    if (nmp > 0) { H2D(m->dU8a, pts->bad, nmp); H2D(m->dF[0], pts->pos, (size_t)nmp * 3); H2D(m->dI[1], pts->obs, nmp); }
-    if (kf_fv->n_nodes > 0) { H2D(m->dNodesA, kf_fv->node_ids, kf_fv->n_nodes); H2D(m->dOffA, kf_fv->offsets, kf_fv->n_nodes + 1); }
-    if (nqe > 0) H2D(m->dIdxA, kf_fv->indices, nqe);
-    m->gridPending = false;                                 // candidates come from the FeatureVectors: the spatial grid is not read
-    FLUSH(m);
-    const int gI = std::max(1, (std::max(std::max(n, nmp), 4) + 255) / 256), gC = std::max(1, (t->cap + 255) / 256);
-    hipLaunchKernelGGL(k_track_init, dim3(gI), dim3(256), 0, nullptr, n, nmp, 1, m->dFeatMp, m->dOut, t->dSeen, dOutF, dMpOut, m->dPose, dB);
-    if (kf_fv->n_nodes > 0)
-        hipLaunchKernelGGL(k_queries_bow, dim3((std::max(nqe, 1) + 255) / 256), dim3(256), 0, nullptr, kf_fv->n_nodes, m->dNodesA, m->dOffA,
-                           m->dIdxA, m->dI[0], m->dU8a, m->dQKeys, 0, m->dNodesB, m->dOffB, m->dQ, t->dNN);
-    int nm = 0;
-    std::vector<int32_t> searched((size_t)n, -1);
-    if ((rc = run_search(m, MODE_BOW, nqe, fd, m->dQDesc, nullptr, nnratio, check_orientation, searched.data(), &nm)) != RUMI_OK) return rc;
-    res->nmatches_motion = nm;
-    std::memcpy(frame_mp, searched.data(), (size_t)n * 4);
-    // the per-feature transform for the host's mBowVec / mFeatVec (assembled there in feature order: rumi_voc_assemble): ONE copy of the block into
-    // pinned memory, queued BEHIND the pose chain (three copies into the caller's pageable arrays sat between the search and PoseOptimization)
-    const size_t C = (size_t)t->cap;
-    auto bow_out = [&]() {
-        std::memcpy(word_weight, t->hBow, (size_t)n * 8); std::memcpy(word_id, t->hBow + C * 8, (size_t)n * 4); std::memcpy(node_id, t->hBow + C * 12, (size_t)n * 4);
-    };
-    if (nm < 15) {                                          // TrackReferenceKeyFrame returns false here (:2335-2338)
-        HIP_TRY(hipMemcpy(t->hBow, t->dBow, C * 16, hipMemcpyDeviceToHost));
-        bow_out();
-        return RUMI_OK;
-    }
-    const bool small = n <= kTrackLdsEdges;
-    hipLaunchKernelGGL(k_track_gather, dim3(1), dim3(1024), 0, nullptr, n, fd.keys, m->dFeatMp, m->dF[0], t->dInvSigma2, t->dXw, t->dObs, t->dW, t->dIdx, dB->start);
-    if ((rc = rumi::pose_opt_device(dB->start, t->dXw, t->dObs, t->dW, m->dPose + 7, m->dPose, dB->Tout, t->dOutC, dB->nGood, t->dActive, t->dChi, small, nullptr)) != RUMI_OK) return rc;
-    hipLaunchKernelGGL(k_track_discard, dim3(gC), dim3(256), 0, nullptr, t->dIdx, t->dOutC, m->dFeatMp, m->dI[1], dB);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(t->hBow, t->dBow, C * 16, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpyAsync(t->hBlk + t->oMp, m->dFeatMp, (size_t)n * 4, hipMemcpyDeviceToHost, nullptr));
-    HIP_TRY(hipMemcpy(t->hBlk, t->dBlk, sizeof(TrackBlock), hipMemcpyDeviceToHost));
-    bow_out();
-    const TrackBlock *hB = reinterpret_cast<const TrackBlock *>(t->hBlk);
-    std::memcpy(res->Tcw_motion, hB->Tout, 28); std::memcpy(res->Tcw, hB->Tout, 28);
-    res->ngood_motion = hB->nGood[0]; res->nmatches_map = hB->counters[0];
-    const int32_t *after = reinterpret_cast<const int32_t *>(t->hBlk + t->oMp);
-    for (int i = 0; i < n; i++) { if (searched[i] >= 0 && after[i] < 0) discarded[i] = searched[i]; frame_mp[i] = after[i]; }
-    return RUMI_OK;
-}
-
-extern "C" int rumi_track_local(RumiTracker *t, const float *K4, const float *Tcw7, const int32_t *frame_mp_in, const RumiTrackPoints *pts,
-                                const uint8_t *seen_in, float th_local, int32_t far_points, float th_far_points, int32_t *frame_mp, uint8_t *outlier,
-                                uint8_t *in_view, RumiTrackResult *res) {
-    if (!t || !K4 || !Tcw7 || !res || !frame_mp || !outlier || !frame_mp_in || track_check_points(pts, true) != RUMI_OK || (pts->n > 0 && !in_view))
-        return RUMI_E_INVALID;
-    if (t->curN < 0) { g_lastError = "rumi_track_local: no frame is resident (rumi_track_extract first)"; return RUMI_E_INVALID; }
-    RumiMatcher *m = t->m;
-    const int n = t->curN, nmp = pts->n;
-    if (nmp > t->maxPts) { g_lastError = "rumi_track_local: more points than the tracker was created for"; return RUMI_E_CAPACITY; }
-    for (int i = 0; i < n; i++) if (frame_mp_in[i] >= nmp) { g_lastError = "rumi_track_local: frame_mp_in index outside the point table"; return RUMI_E_INVALID; }
-    HIP_TRY(hipSetDevice(t->device));
-    std::memset(res, 0, sizeof(*res));
-    t->projN = 0;
-    res->n = n; res->mono_index = t->curMono;
-    std::memcpy(res->Tcw_motion, Tcw7, 28); std::memcpy(res->Tcw, Tcw7, 28);
-    // SearchLocalPoints, first loop (Tracking.cc:2998-3010), on the host while the arrays are being staged: a bad point leaves the frame, the
-    // others are "seen in this frame"; seen_in carries the points the caller's discard loop has marked (mnLastFrameSeen == mCurrentFrame.mnId)
-    std::vector<int32_t> mpIn((size_t)std::max(n, 1), -1);
-    std::vector<uint8_t> seen((size_t)std::max(nmp, 1), 0);
-    if (seen_in) for (int j = 0; j < nmp; j++) seen[j] = seen_in[j] ? 2 : 0;       // the caller's discard loop: 2 (k_track_frustum tells them from the frame's own points)
-    for (int i = 0; i < n; i++) {
-        const int mp = frame_mp_in[i];
-        if (mp < 0) continue;
-        if (pts->bad[mp]) continue;
-        mpIn[i] = mp; seen[mp] = 1;
-    }
-    TrackBlock *dB = reinterpret_cast<TrackBlock *>(t->dBlk);
-    int32_t *dMpOut = reinterpret_cast<int32_t *>(t->dBlk + t->oMp), *dMpMotion = reinterpret_cast<int32_t *>(t->dBlk + t->oMpM);
-    uint8_t *dOutF = t->dBlk + t->oOut, *dView = t->dBlk + t->oView;
-    FrameDev fd;
-    int rc = track_frame_dev(t, &fd);
-    if (rc != RUMI_OK) return rc;
-    float pose[11];
-    std::memcpy(pose, Tcw7, 7 * sizeof(float)); std::memcpy(pose + 7, K4, 4 * sizeof(float));
-    H2D(m->dPose, pose, 11);
-    if (n > 0) H2D(m->dFeatMp, mpIn.data(), n);
-    if (nmp > 0) {
-        H2D(m->dF[0], pts->pos, (size_t)nmp * 3); H2D(m->dF[1], pts->normal, (size_t)nmp * 3); H2D(m->dF[2], pts->min_dist, nmp); H2D(m->dF[3], pts->max_dist, nmp);
-        H2D(m->dI[1], pts->obs, nmp); H2D(m->dQDesc, pts->desc, (size_t)nmp * 32); H2D(t->dBad, pts->bad, nmp); H2D(t->dLocal, pts->local, nmp);
-        if (pts->stale_in_view && pts->stale_proj) { H2D(t->dStaleIn, pts->stale_in_view, nmp); H2D(t->dStaleProj, pts->stale_proj, (size_t)nmp * 5); }
-        H2D(t->dSeen, seen.data(), nmp);
-    }
-    FLUSH(m);
-    const int gI = std::max(1, (std::max(std::max(n, nmp), 4) + 255) / 256), gC = std::max(1, (t->cap + 255) / 256);
-    hipLaunchKernelGGL(k_track_local_init, dim3(gI), dim3(256), 0, nullptr, n, m->dPose, m->dPose + 7, dOutF, dMpOut, m->dOut, dB);
-    int nmLocal = 0;
-    bool speculate = false;
-    std::vector<int32_t> tmpMp((size_t)std::max(n, 1));
-    if (nmp > 0 && n > 0) {
-        const size_t n16 = ((size_t)nmp + 15) & ~(size_t)15;
-        if (n16 * 21 > m->stageCap) { g_lastError = "rumi_track_local: point table exceeds the staging block"; return RUMI_E_CAPACITY; }
-        uint8_t *dSkip = m->dU8b;
-        float *dX = reinterpret_cast<float *>(m->dStage + n16), *dY = dX + n16, *dC = dY + n16, *dD = dC + n16;
-        int32_t *dL = reinterpret_cast<int32_t *>(dD + n16);
-        const float logSf = std::log(t->cfg.scale_factor);
-        { const FrustumArgs FA{nmp, n, m->dFeatMp, dMpMotion, t->dLocal, t->dSeen, t->dBad, dSkip, m->dOut, dB->pose19, fd.minX,
-                           fd.minY, fd.maxX, fd.maxY, logSf, t->nlevels, 0.5f, m->dF[0], m->dF[1], m->dF[2], m->dF[3], dView, dX, dY, dL, dC, dD,
-                           m->dI[1], m->dScale, th_local, far_points, th_far_points, m->dQ,
-                           (pts->stale_in_view && pts->stale_proj) ? t->dStaleIn : nullptr, (pts->stale_in_view && pts->stale_proj) ? t->dStaleProj : nullptr};
-          hipLaunchKernelGGL(k_track_frustum, dim3(gI), dim3(256), 0, nullptr, FA); t->projN16 = n16; t->projN = nmp; }
-        // the search's counts are not needed before the end: one queue, the result header travels in the block (a list overflow -- the resolve
-        // did not run then, the frame's vector is untouched -- sends the stage through the sizing path)
-        static const int envSpec = std::getenv("RUMI_TRACK_SPECULATE") ? std::atoi(std::getenv("RUMI_TRACK_SPECULATE")) : 1;
-        static const bool noFusedLists = std::getenv("RUMI_MATCH_NO_FUSED") != nullptr;
-        speculate = envSpec && !noFusedLists && m->listCap / (size_t)nmp >= 64;
-        if (speculate) {
-            if ((rc = build_lists(m, MODE_MAPPOINTS, nmp, fd, m->dQDesc, false, true)) != RUMI_OK) return rc;
-            ResolveArgs A{MODE_MAPPOINTS, nmp, fd.n, m->dQ, m->dCounts, m->dOffsets, m->dLists, fd.keys, m->dI[1], m->dFeatMp, m->dAssign, m->dNmatches,
-                          0.8f, 0, nullptr, 0.f, 0, m->dOverflow};
-            hipLaunchKernelGGL(k_resolve, dim3(1), dim3(1024), (size_t)std::max(fd.n, 1) * sizeof(int32_t), nullptr, A);
-        } else if ((rc = run_search(m, MODE_MAPPOINTS, nmp, fd, m->dQDesc, m->dI[1], 0.8f, 0, tmpMp.data(), &nmLocal)) != RUMI_OK) return rc;
-    }
-    res->nmatches_local = nmLocal;
-    const bool small = n <= kTrackLdsEdges;
-    const TrackBlock *hB = reinterpret_cast<const TrackBlock *>(t->hBlk);
-    for (int pass = 0; pass < 2; pass++) {
-        hipLaunchKernelGGL(k_track_gather, dim3(1), dim3(1024), 0, nullptr, n, fd.keys, m->dFeatMp, m->dF[0], t->dInvSigma2, t->dXw, t->dObs, t->dW, t->dIdx, dB->start);
-        if ((rc = rumi::pose_opt_device(dB->start, t->dXw, t->dObs, t->dW, m->dPose + 7, dB->Tout, dB->Tout + 7, t->dOutC, dB->nGood + 1, t->dActive, t->dChi, small, nullptr)) != RUMI_OK) return rc;
-        hipLaunchKernelGGL(k_track_finish, dim3(gC), dim3(256), 0, nullptr, t->dIdx, t->dOutC, m->dFeatMp, m->dI[1], dOutF, dMpOut, 1, dB, speculate ? (const int32_t *)m->dOut : (const int32_t *)nullptr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(t->hBlk, t->dBlk, t->oRec, hipMemcpyDeviceToHost));       // header, mvpMapPoints, mvbOutlier, mbTrackInView
-        if (!speculate) break;
-        if (hB->spec[3] == 0) { res->nmatches_local = hB->spec[2]; break; }
-        // a candidate list overflowed: the search again with exact list sizes, then the optimisation on its result
-        speculate = false;
-        hipLaunchKernelGGL(k_track_local_init, dim3(gI), dim3(256), 0, nullptr, n, m->dPose, m->dPose + 7, dOutF, dMpOut, m->dOut, dB);
-        if ((rc = run_search(m, MODE_MAPPOINTS, nmp, fd, m->dQDesc, m->dI[1], 0.8f, 0, tmpMp.data(), &nmLocal)) != RUMI_OK) return rc;
-        res->nmatches_local = nmLocal;
-    }
-    std::memcpy(res->Tcw, hB->Tout + 7, 28);
-    std::memcpy(res->Rcw, hB->pose19, 36); std::memcpy(res->tcw, hB->pose19 + 9, 12); std::memcpy(res->Ow, hB->pose19 + 12, 12);
-    res->ngood_local = hB->nGood[1]; res->matches_inliers = hB->counters[1];
-    if (n > 0) { std::memcpy(frame_mp, t->hBlk + t->oMp, (size_t)n * 4); std::memcpy(outlier, t->hBlk + t->oOut, (size_t)n); }
-    int nTo = 0;
-    if (nmp > 0) {
-        if (n > 0) std::memcpy(in_view, t->hBlk + t->oView, (size_t)nmp); else std::memset(in_view, 0, (size_t)nmp);
-        for (int j = 0; j < nmp; j++) nTo += in_view[j] == 1;         // (2: a stale flag of an earlier frame, not an isInFrustum of this one)
-    }
-    res->n_to_match = nTo;
-    return RUMI_OK;
-}
-
-/* mTrackProjX, mTrackProjY, mnTrackScaleLevel, mTrackViewCos, mTrackDepth of every table point as the SearchLocalPoints of the LAST rumi_track_frame /
- * rumi_track_local call left them (Frame::isInFrustum writes them into the MapPoint, Frame.cc:558-630; the values of a point that is not in view are
- * not meaningful).  They are still in the matcher's staging block: one more copy brings them.  Valid until the next rumi_track_* call. */
-extern "C" int rumi_track_last_projections(RumiTracker *t, int32_t n_points, float *proj5_out) {
-    if (!t || !proj5_out || n_points < 0) return RUMI_E_INVALID;
-    if (t->projN <= 0 || n_points != t->projN) { g_lastError = "rumi_track_last_projections: no SearchLocalPoints result of that size is resident"; return RUMI_E_INVALID; }
-    HIP_TRY(hipSetDevice(t->device));
-    RumiMatcher *m = t->m;
-    const size_t n16 = t->projN16;
-    std::vector<float> h(5 * n16);
-    HIP_TRY(hipMemcpy(h.data(), m->dStage + n16, 5 * n16 * sizeof(float), hipMemcpyDeviceToHost));
-    const float *X = h.data(), *Y = X + n16, *Cc = Y + n16, *D = Cc + n16;
-    const int32_t *L = reinterpret_cast<const int32_t *>(D + n16);
-    for (int i = 0; i < n_points; i++) { float *o = proj5_out + (size_t)i * 5; o[0] = X[i]; o[1] = Y[i]; o[2] = (float)L[i]; o[3] = Cc[i]; o[4] = D[i]; }
-    return RUMI_OK;
-}
-
-/* Lens distortion of the camera (Frame::UndistortKeyPoints / ComputeImageBounds, R/lib_src/Frame.cc:770-826; R/config/euroc_ori.yaml:23-31 has
- * k1 = -0.283): K4 = fx, fy, cx, cy of mK, dist5 = mDistCoef (k1, k2, p1, p2, k3).  From the next rumi_track_extract / rumi_track_frame on the
- * resident frame carries mvKeysUn (the grid, every search and PoseOptimization read those) and the undistorted image bounds; keys_out of those calls
- * stays mvKeys, as ExtractORB returns them.  dist5 == NULL or dist5[0] == 0: none (mvKeysUn = mvKeys, the reference's own test, Frame.cc:771). */
-extern "C" int rumi_track_set_distortion(RumiTracker *t, const float *K4, const float *dist5) {
-    if (!t) return RUMI_E_INVALID;
-    if (!dist5 || dist5[0] == 0.0f) { t->distort = false; return RUMI_OK; }
-    if (!K4 || !(K4[0] != 0.0f) || !(K4[1] != 0.0f)) { g_lastError = "rumi_track_set_distortion: camera matrix"; return RUMI_E_INVALID; }
-    HIP_TRY(hipSetDevice(t->device));
-    if (!t->dKeysUn) HIP_TRY(hipMalloc((void **)&t->dKeysUn, (size_t)t->cap * sizeof(RumiKeyPoint)));
-    UndistortArgs &A = t->ua;
-    A.fx = K4[0]; A.fy = K4[1]; A.cx = K4[2]; A.cy = K4[3]; A.ifx = 1. / A.fx; A.ify = 1. / A.fy;
-    A.k1 = dist5[0]; A.k2 = dist5[1]; A.p1 = dist5[2]; A.p2 = dist5[3]; A.k3 = dist5[4];
-    t->distort = true;
-    t->curN = -1;                                          // a frame extracted under other coefficients is not this camera's
-    return RUMI_OK;
-}
-/* mvKeysUn of the resident frame (keys_un_out [cap >= n]) and {mnMinX, mnMinY, mnMaxX, mnMaxY} (bounds4); either may be NULL. */
-extern "C" int rumi_track_undistorted(RumiTracker *t, RumiKeyPoint *keys_un_out, int32_t cap, float *bounds4) {
-    if (!t) return RUMI_E_INVALID;
-    if (t->curN < 0) { g_lastError = "rumi_track_undistorted: no frame is resident"; return RUMI_E_INVALID; }
-    if (bounds4) std::memcpy(bounds4, t->bounds, 16);
-    if (keys_un_out && t->curN > 0) {
-        if (cap < t->curN) return RUMI_E_CAPACITY;
-        HIP_TRY(hipSetDevice(t->device));
-        const RumiKeyPoint *src = t->distort ? t->dKeysUn : reinterpret_cast<const RumiKeyPoint *>(t->dBlk + t->oRec + 8);
-        HIP_TRY(hipMemcpy(keys_un_out, src, (size_t)t->curN * sizeof(RumiKeyPoint), hipMemcpyDeviceToHost));
-    }
-    return RUMI_OK;
 }

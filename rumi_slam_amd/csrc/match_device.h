@@ -1,4 +1,4 @@
-// Device helpers the matcher kernels (match.hip) and the mapping kernels (mapping.hip) share.
+// Device helpers the matcher kernels (match.hip), the Tracking step (track.hip) and the mapping kernels (mapping.hip) share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -41,5 +41,91 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 __device__ __forceinline__ int wave_sum_i32(int v) { return __builtin_amdgcn_readlane(wave_scan_incl_i32(v), 63); }
+
+struct Query {           // 48 bytes
+    float u, v, r;       // window centre / half-size (MODE_BOW: unused)
+    int32_t minLevel, maxLevel;
+    int32_t valid;
+    int32_t descId;      // row of the query descriptor in qDesc
+    int32_t mpId;        // map point id this query assigns
+    int32_t blocks;      // Observations() > 0: an assignment hides the feature from later queries
+    int32_t c0, c1;      // MODE_BOW: candidate range in the frame's FeatureVector indices
+    float angle;         // key-point angle on the query side (rotation histogram)
+};
+
+// SearchByProjection(F, map points): ORBmatcher.cc:44-71
+__device__ __forceinline__ Query mappoint_query(int i, bool inView, float px, float py, int lvl, float viewCos, float depth, bool isBad, int obs,
+                                                const float *scaleFactors, float th, int farPoints, float thFar) {
+    Query o{};
+    o.valid = inView && !(farPoints && depth > thFar) && !isBad;
+    if (o.valid) {
+        float r = (double)viewCos > 0.998 ? 2.5f : 4.0f;      // RadiusByViewingCos (float vs double literal)
+        if ((double)th != 1.0) r *= th;
+        o.u = px; o.v = py;
+        o.r = r * scaleFactors[lvl];
+        o.minLevel = lvl - 1; o.maxLevel = lvl;
+    }
+    o.descId = i; o.mpId = i; o.blocks = obs > 0;
+    return o;
+}
+
+// MapPoint::PredictScale (MapPoint.cc:538-570); log in double (oracle/match_oracle.cc explains the choice)
+__device__ __forceinline__ int predict_scale(float maxDistance, float dist, float logScaleFactor, int nLevels) {
+    const float ratio = maxDistance / dist;
+    int nScale = (int)ceil(log((double)ratio) / (double)logScaleFactor);
+    if (nScale < 0) nScale = 0;
+    else if (nScale >= nLevels) nScale = nLevels - 1;
+    return nScale;
+}
+
+// Correspondences of Optimizer::PoseOptimization(Frame*) (Optimizer.cc:749-815, mono): the features with a map point, in feature order.
+// One workgroup of 1024 threads, ordered compaction (ballot + wave offsets through LDS, chunks of 1024 features).
+__device__ __forceinline__ void gather_correspondences(int n, const RumiKeyPoint *__restrict__ keys, const int32_t *featMp, const float *__restrict__ mpPos,
+                                                       const float *__restrict__ invSigma2, float *Xw, float *obs, float *w, int32_t *idx, int32_t *start,
+                                                       int32_t *snapshot, int *sWave /* [16] */, int *sBase) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid == 0) *sBase = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < n; c0 += 1024) {
+        const int i = c0 + tid;
+        const int mp = i < n ? featMp[i] : -1;
+        if (snapshot && i < n) snapshot[i] = mp;            // the frame's map-point vector as the search left it (the optimisation's outliers leave it next)
+        const unsigned long long b = __ballot(mp >= 0);
+        if (lane == 0) sWave[wave] = __popcll(b);
+        __syncthreads();
+        int off = *sBase;
+        for (int k = 0; k < wave; k++) off += sWave[k];
+        if (mp >= 0) {
+            const int c = off + __popcll(b & ((1ull << lane) - 1));
+            Xw[3 * c] = mpPos[3 * mp]; Xw[3 * c + 1] = mpPos[3 * mp + 1]; Xw[3 * c + 2] = mpPos[3 * mp + 2];
+            obs[2 * c] = keys[i].x; obs[2 * c + 1] = keys[i].y;
+            w[c] = invSigma2[keys[i].octave];
+            idx[c] = i;
+        }
+        __syncthreads();
+        if (tid == 0) { int t = *sBase; for (int k = 0; k < 16; k++) t += sWave[k]; *sBase = t; }
+        __syncthreads();
+    }
+    if (tid == 0) { start[0] = 0; start[1] = *sBase; }
+}
+
+// Frame::UpdatePoseMatrices (Frame.cc:522-528) in Sophus' / Eigen's float arithmetic: Rcw = q.toRotationMatrix(), tcw, Ow = conj(q) * (-tcw)
+// (quaternion _transformVector), as [Rcw9 | tcw3 | Ow3 | K4] for the frustum test.
+__device__ __forceinline__ void pose_matrices19(const float *Tcw7, const float *K4, float *pose19) {
+    const float x = Tcw7[0], y = Tcw7[1], z = Tcw7[2], w = Tcw7[3];
+    const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z;
+    const float twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    pose19[0] = 1.f - (tyy + tzz); pose19[1] = txy - twz; pose19[2] = txz + twy;
+    pose19[3] = txy + twz; pose19[4] = 1.f - (txx + tzz); pose19[5] = tyz - twx;
+    pose19[6] = txz - twy; pose19[7] = tyz + twx; pose19[8] = 1.f - (txx + tyy);
+    const float t0 = Tcw7[4], t1 = Tcw7[5], t2 = Tcw7[6];
+    pose19[9] = t0; pose19[10] = t1; pose19[11] = t2;
+    const float qx = -x, qy = -y, qz = -z, v0 = t0 * -1.f, v1 = t1 * -1.f, v2 = t2 * -1.f;
+    float u0 = qy * v2 - qz * v1, u1 = qz * v0 - qx * v2, u2 = qx * v1 - qy * v0;
+    u0 += u0; u1 += u1; u2 += u2;
+    const float c0 = qy * u2 - qz * u1, c1 = qz * u0 - qx * u2, c2 = qx * u1 - qy * u0;
+    pose19[12] = (v0 + w * u0) + c0; pose19[13] = (v1 + w * u1) + c1; pose19[14] = (v2 + w * u2) + c2;
+    pose19[15] = K4[0]; pose19[16] = K4[1]; pose19[17] = K4[2]; pose19[18] = K4[3];
+}
 
 }  // namespace rumi

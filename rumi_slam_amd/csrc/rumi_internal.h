@@ -8,7 +8,7 @@ typedef struct RumiMatcher RumiMatcher;
 
 namespace rumi {
 
-// Correspondences the LDS instantiation of k_pose_opt holds (opt.hip).  The tracker (match.hip) launches ONLY that instantiation when it knows a
+// Correspondences the LDS instantiation of k_pose_opt holds (opt.hip).  The tracker (track.hip) launches ONLY that instantiation when it knows a
 // frame cannot have more (nfeatures 1000 + the extractor's slack of 96 fits), so both files take the number from here.
 constexpr int kPoseLdsEdges = 1152;
 
@@ -22,9 +22,8 @@ int pose_opt_device(const int32_t *dStart, const float *dXw, const float *dObs, 
 // Device, word count and the header's weighting / scoring types of a vocabulary (voc.hip), for the key-frame database (kfdb.hip).
 void voc_params(const RumiVocabulary *v, int *device, int *nWords, int *weighting, int *scoring);
 
-// What another translation unit hangs on a RumiMatcher (match.hip): mapping.hip keeps the blocks of rumi_create_new_map_points here, so that they
-// live and die with the handle.  matcher_ext also reports the handle's device and the capacities it was created with.
+// What another translation unit hangs on a RumiMatcher (match_host.h): mapping.hip keeps the blocks of rumi_create_new_map_points here, so that
+// they live and die with the handle.
 struct MatcherExt { void *state = nullptr; void (*destroy)(void *) = nullptr; };
-MatcherExt *matcher_ext(RumiMatcher *m, int *device, int *maxFeatures, int *maxQueries);
 
 }  // namespace rumi
