@@ -8,6 +8,7 @@
  *   R/lib_src/GeometricTools.cc:47-66     GeometricTools::Triangulate
  *   R/lib_src/CameraModels/Pinhole.cpp:30-33,61-64   Pinhole::project / unprojectEig
  *   R/lib_src/MapPoint.cc:353-427, 450-518   MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth (rumi_refresh_map_points, below)
+ *   R/lib_src/LocalMapping.cc:953-1079, 820-951   LocalMapping::KeyFrameCulling / CloudKeyFrameCulling (rumi_keyframe_culling, below)
  *
  * One call runs the whole neighbour loop: every neighbour's search, triangulation and gates in wide launches, then the only
  * order-dependent part (a feature that received a point from neighbour k is skipped for neighbour k + 1, ORBmatcher.cc:865) in
@@ -158,6 +159,89 @@ int rumi_refresh_map_points(RumiRefresh *r, const RumiRefreshKF *kf, int32_t n_k
 /* Host wall-clock of the handle's last successful call with work, in ms: out3[0] validation and gather, out3[1] upload + kernels + download
  * (the host waits for the device here), out3[2] writing the caller's arrays.  For tools/refresh_probe.py. */
 int rumi_refresh_stage_ms(const RumiRefresh *r, float *out3);
+
+/* ---- LocalMapping::KeyFrameCulling (R/lib_src/LocalMapping.cc:953-1079) and CloudKeyFrameCulling (:820-951) for the whole covisible list in
+ * one call.  Non-inertial, monocular: the inertial branch (:1045-1070), the stereo depth gate (:1001-1004) and the NLeft != -1 octave
+ * selection (:1008, :1020-1028) cannot be asked for -- the tables below carry no mPrevKF / mvDepth / right index.
+ *
+ * The loop takes the candidates in order.  `count` is incremented for every candidate, skipped ones included (:986).  A cloud candidate
+ * (cloud variant only, :857), then the initial key-frame or a bad one (:989) is skipped by `continue`, which also skips the break test at the
+ * loop's end.  For the others nMPs = the non-bad points of the key-frame (:1006); a point is redundant when Observations() > 3 (:1007) and
+ * more than 3 OTHER observing key-frames see it at octave <= own octave + 1 (:1030-1037; the iteration order and the early break :1032 do
+ * not change that).  The verdict is (float)nRedundant > 0.9f * (float)nMPs (:1044): one float multiply and one compare, no contraction.
+ * After the verdict the loop breaks when count > 100, or count > 20 && abort_ba (:1075).
+ *
+ * A positive verdict calls KeyFrame::SetBadFlag() (:1072).  For a not_erase key-frame that only marks mbToBeErased (KeyFrame.cc:783):
+ * status RUMI_CULL_TO_BE_ERASED, the map is unchanged and the key-frame is not bad.  Otherwise every point of the key-frame loses this
+ * observation and nObs-- (MapPoint.cc:192-225); a point whose nObs is then <= 2 turns bad, drops all observations and leaves every
+ * key-frame (MapPoint.cc:240-263).  So the state the loop carries is the set S of key-frames culled so far: a point's nObs is n_obs_count
+ * minus its observers in S, it is bad when it was bad at the call or when it has an observer in S and that value is <= 2 (monotone), and the
+ * observer count ignores observers in S.  A candidate listed twice is `skipped bad` the second time once culled.
+ *
+ * The map must be consistent, as KeyFrame::AddMapPoint / MapPoint::AddObservation keep it: mp[i] = p exactly when point p lists
+ * (key-frame, i), and a point lists a key-frame at most once (its observations are a std::map).  MapPoint::SetBadFlag clears key-frame
+ * slots BY INDEX (KeyFrame::EraseMapPointMatch(idx)), so with a dangling observation the result would depend on state outside S; such
+ * tables are RUMI_E_INVALID, in both directions.
+ *
+ * abort_ba is sampled ONCE, at the call: the reference reads mbAbortBA anew at every candidate, from a flag another thread sets.  This is
+ * the one deliberate difference. */
+#define RUMI_CULL_CLOUD 1      /* flags: CloudKeyFrameCulling -- is_cloud candidates are skipped before anything else (:857) */
+#define RUMI_CULL_ABORT_BA 2   /* flags: mbAbortBA */
+
+#define RUMI_CULL_NOT_REACHED 0    /* the loop broke before this candidate */
+#define RUMI_CULL_SKIPPED_CLOUD 1
+#define RUMI_CULL_SKIPPED_INIT 2
+#define RUMI_CULL_SKIPPED_BAD 3
+#define RUMI_CULL_KEPT 4
+#define RUMI_CULL_CULLED 5         /* SetBadFlag() went through: listed in culled[] */
+#define RUMI_CULL_TO_BE_ERASED 6   /* positive verdict on a not_erase key-frame */
+
+/* Key-frames of one call: the replay kernel keeps one bit each in LDS.  More is RUMI_E_CAPACITY. */
+#define RUMI_CULL_MAX_KEYFRAMES 65536
+
+/* Every key-frame that appears in an observation list, each once. */
+typedef struct RumiCullKF {
+    const int32_t *octave;   /* [n] mvKeysUn[i].octave, 0..127 */
+    const int32_t *mp;       /* [n] GetMapPointMatches(): index into pts, -1 = NULL */
+    int32_t n;
+    uint8_t is_bad;          /* isBad() */
+    uint8_t is_init;         /* mnId == GetMap()->GetInitKFid() */
+    uint8_t not_erase;       /* mbNotErase */
+    uint8_t is_cloud;        /* isCloud() */
+} RumiCullKF;
+
+typedef struct RumiCullPoint {
+    int32_t obs_begin, obs_end;   /* entries obs_begin .. obs_end - 1 of obs_kf / obs_feature */
+    int32_t n_obs_count;          /* Observations(): nObs, carried separately from the list length */
+    uint8_t is_bad;               /* isBad() */
+    uint8_t pad_[3];
+} RumiCullPoint;
+
+typedef struct RumiCull RumiCull;
+
+/* A handle owns the pinned upload block, the device block and the result block of its calls (grown on demand); not re-entrant, one per
+ * calling thread.  device < 0: the current one.  Creation does not touch the device; the first call with work does. */
+int rumi_cull_create(int32_t device, RumiCull **out);
+void rumi_cull_destroy(RumiCull *c);
+
+/* One pass of the culling loop.  kfs [n_kf]; cand [n_cand] = GetVectorCovisibleKeyFrames() after UpdateBestCovisibles(), in its order, as
+ * indices into kfs; pts [n_pts]; obs_kf / obs_feature [n_obs].  flags = RUMI_CULL_CLOUD | RUMI_CULL_ABORT_BA or 0.
+ * Outputs: status, n_mps, n_redundant [n_cand] (the counts are 0 where the candidate was skipped or not reached); culled [n_cand] the
+ * candidates (positions in cand) with status RUMI_CULL_CULLED in loop order, *n_culled their number.  Calling SetBadFlag() on them in that
+ * order reproduces the reference's map; the RUMI_CULL_TO_BE_ERASED ones take SetBadFlag() too (it only sets mbToBeErased), at any time.
+ * One pinned block goes up, one comes back.  Integer arithmetic but for the verdict; no floating-point atomics: two calls return the same
+ * bytes, and the outputs do not depend on the order of pts or of the observations.
+ * RUMI_E_INVALID, nothing written: an index outside its table (cand, mp, obs_kf, obs_feature), a slice outside 0..n_obs, an octave
+ * outside 0..127, an mp[i] whose point does not list that (key-frame, feature) pair, an observation whose key-frame slot does not hold
+ * the point, a point that lists a key-frame twice.  RUMI_E_CAPACITY, nothing written: a point above RUMI_REFRESH_MAX_OBS observations, or
+ * n_kf above RUMI_CULL_MAX_KEYFRAMES.  All checked on the host before anything reaches the device.  n_cand = 0 is RUMI_OK (*n_culled = 0). */
+int rumi_keyframe_culling(RumiCull *c, const RumiCullKF *kfs, int32_t n_kf, const int32_t *cand, int32_t n_cand, const RumiCullPoint *pts,
+                          int32_t n_pts, const int32_t *obs_kf, const int32_t *obs_feature, int32_t n_obs, int32_t flags, int32_t *status,
+                          int32_t *n_mps, int32_t *n_redundant, int32_t *culled, int32_t *n_culled);
+
+/* Host wall-clock of the handle's last successful call with work, in ms: out3[0] validation and pack, out3[1] upload + kernels + download,
+ * out3[2] writing the caller's arrays.  For tools/culling_probe.py. */
+int rumi_cull_stage_ms(const RumiCull *c, float *out3);
 
 #ifdef __cplusplus
 }

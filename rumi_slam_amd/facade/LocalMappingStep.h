@@ -8,7 +8,16 @@
 //     step.CreateNewMapPoints<MapPoint>(mpCurrentKeyFrame, vpNeighKFs, mpAtlas, mlpRecentAddedMapPoints, mbFarPoints, mThFarPoints,
 //                                       [this] { return CheckNewKeyFrames(); }, bCoarse);
 // (the neighbour list, its inertial extension :362-371 and bCoarse :423 stay the caller's).
+//
+// LocalMapping::KeyFrameCulling (:953-1079) and CloudKeyFrameCulling (:820-951) become
+//     step.KeyFrameCulling(mpCurrentKeyFrame, mbInertial, mbMonocular, mbAbortBA);
+//     step.CloudKeyFrameCulling(mpCurrentKeyFrame, mbInertial, mbMonocular, mbAbortBA);
+// one device call judges the whole covisible list (rumi_keyframe_culling); SetBadFlag() is then applied in the returned order.
 #pragma once
+#include <map>
+#include <tuple>
+#include <type_traits>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -104,8 +113,133 @@ public:
         }
         return created;
     }
+#endif  // RUMI_HAVE_SOPHUS
+
+    // The reference's loop over GetVectorCovisibleKeyFrames() after UpdateBestCovisibles(), non-inertial and monocular.  mbAbortBA is read once,
+    // here (the reference reads it at every candidate).  Returns the number of key-frames culled (SetBadFlag() went through), -1 when no
+    // key-frame or point was touched: mbInertial or !mbMonocular (the inertial branch :1045-1070 and the stereo depth gate :1001-1004 are not
+    // built; refused before anything is called), a stereo observation or key-frame (NLeft != -1), or the device call failed -- all reported
+    // through rumi_status.h.  The last two are found while the covisible list is read, so UpdateBestCovisibles() (:959) has run by then, as it
+    // has at the top of the reference's member the caller falls back to.
+    // KeyFrame needs one getter the reference lacks: bool GetNotErase() { return mbNotErase; }.
+    template <class KeyFrameT> int KeyFrameCulling(KeyFrameT *pCurrentKF, bool bInertial, bool bMonocular, bool bAbortBA) {
+        return culling(pCurrentKF, bInertial, bMonocular, bAbortBA, false);
+    }
+    template <class KeyFrameT> int CloudKeyFrameCulling(KeyFrameT *pCurrentKF, bool bInertial, bool bMonocular, bool bAbortBA) {
+        return culling(pCurrentKF, bInertial, bMonocular, bAbortBA, true);
+    }
 
 protected:
+    // One culling handle per calling thread (handles are not re-entrant), destroyed with its blocks when the thread ends.
+    struct CullHandle {
+        RumiCull *h = nullptr;
+        CullHandle() = default;
+        CullHandle(const CullHandle &) = delete;
+        CullHandle &operator=(const CullHandle &) = delete;
+        ~CullHandle() { rumi_cull_destroy(h); }
+    };
+    static RumiCull *cull_handle() {
+        thread_local CullHandle holder;
+        if (!holder.h) {
+            const int rc = rumi_cull_create(-1, &holder.h);
+            if (rc != RUMI_OK) { rumi_facade::report("LocalMappingStep::KeyFrameCulling: handle", rc); holder.h = nullptr; }
+        }
+        return holder.h;
+    }
+
+    template <class KeyFrameT> int culling(KeyFrameT *pCurrentKF, bool bInertial, bool bMonocular, bool bAbortBA, bool cloudVariant) {
+        static const char *where = "LocalMappingStep::KeyFrameCulling";
+        if (bInertial || !bMonocular) {
+            rumi_facade::report(where, RUMI_E_INVALID, "mbInertial or a non-monocular sensor: only the non-inertial monocular loop is built; no key-frame was culled");
+            return -1;
+        }
+        pCurrentKF->UpdateBestCovisibles();                                     // :959
+        const auto vpLocalKeyFrames = pCurrentKF->GetVectorCovisibleKeyFrames();   // :960
+        using KFPtr = typename std::decay<decltype(vpLocalKeyFrames)>::type::value_type;
+        using MPPtr = typename std::decay<decltype(vpLocalKeyFrames[0]->GetMapPointMatches())>::type::value_type;
+        std::vector<KFPtr> kfs;
+        std::unordered_map<const void *, int32_t> kfIndex, mpIndex;
+        std::vector<MPPtr> mps;
+        auto kf_of = [&](KFPtr pKF) {
+            auto it = kfIndex.find(pKF);
+            if (it != kfIndex.end()) return it->second;
+            kfs.push_back(pKF);
+            return kfIndex[pKF] = (int32_t)kfs.size() - 1;
+        };
+        // the candidates, all of their points, and every key-frame those points list
+        std::vector<int32_t> cand;
+        for (KFPtr pKF : vpLocalKeyFrames) cand.push_back(kf_of(pKF));
+        const size_t nCandKF = kfs.size();
+        std::vector<std::vector<int32_t>> mp(nCandKF), octave;
+        for (size_t k = 0; k < nCandKF; k++) {
+            const auto vpMapPoints = kfs[k]->GetMapPointMatches();              // :991
+            mp[k].assign(vpMapPoints.size(), -1);
+            for (size_t i = 0; i < vpMapPoints.size(); i++) {
+                MPPtr pMP = vpMapPoints[i];
+                if (!pMP) continue;
+                auto it = mpIndex.find(pMP);
+                if (it == mpIndex.end()) { mps.push_back(pMP); it = mpIndex.emplace(pMP, (int32_t)mps.size() - 1).first; }
+                mp[k][i] = it->second;
+            }
+        }
+        std::vector<RumiCullPoint> pts(mps.size());
+        std::vector<int32_t> obsKf, obsFeature;
+        for (size_t p = 0; p < mps.size(); p++) {
+            const auto observations = mps[p]->GetObservations();               // std::map: the order :1011 iterates in
+            pts[p].obs_begin = (int32_t)obsKf.size();
+            for (const auto &o : observations) {
+                const int leftIndex = std::get<0>(o.second), rightIndex = std::get<1>(o.second);
+                if (rightIndex != -1 || leftIndex == -1 || o.first->NLeft != -1) {
+                    rumi_facade::report(where, RUMI_E_INVALID, "a stereo observation (right index or NLeft != -1): only the monocular loop is built; no key-frame was culled");
+                    return -1;
+                }
+                const int32_t k = kf_of(o.first);
+                if ((size_t)k >= mp.size()) mp.resize((size_t)k + 1);
+                if (mp[k].empty()) mp[k].assign(o.first->mvKeysUn.size(), -1);
+                // a key-frame outside the covisible list is never culled: of its slots only those the table's points name matter
+                if ((size_t)k >= nCandKF && leftIndex < (int)mp[k].size() && o.first->GetMapPoint(leftIndex) == mps[p]) mp[k][leftIndex] = (int32_t)p;
+                obsKf.push_back(k);
+                obsFeature.push_back(leftIndex);
+            }
+            pts[p].obs_end = (int32_t)obsKf.size();
+            pts[p].n_obs_count = mps[p]->Observations();
+            pts[p].is_bad = mps[p]->isBad();
+            pts[p].pad_[0] = pts[p].pad_[1] = pts[p].pad_[2] = 0;
+        }
+        mp.resize(kfs.size());
+        octave.resize(kfs.size());
+        std::vector<RumiCullKF> table(kfs.size());
+        for (size_t k = 0; k < kfs.size(); k++) {
+            KFPtr pKF = kfs[k];
+            if (pKF->NLeft != -1) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a key-frame with NLeft != -1: only the monocular loop is built; no key-frame was culled");
+                return -1;
+            }
+            mp[k].resize(pKF->mvKeysUn.size(), -1);
+            octave[k].resize(pKF->mvKeysUn.size());
+            for (size_t i = 0; i < octave[k].size(); i++) octave[k][i] = pKF->mvKeysUn[i].octave;   // :1008, :1019
+            RumiCullKF &o = table[k];
+            o.octave = octave[k].data(); o.mp = mp[k].data(); o.n = (int32_t)octave[k].size();
+            o.is_bad = pKF->isBad(); o.is_init = pKF->mnId == pKF->GetMap()->GetInitKFid();
+            o.not_erase = pKF->GetNotErase(); o.is_cloud = pKF->isCloud();
+        }
+        const int nc = (int)cand.size();
+        std::vector<int32_t> status(nc), nMPs(nc), nRedundant(nc), culled(nc);
+        int32_t nCulled = 0;
+        RumiCull *h = cull_handle();
+        if (!h) return -1;
+        const int flags = (cloudVariant ? RUMI_CULL_CLOUD : 0) | (bAbortBA ? RUMI_CULL_ABORT_BA : 0);
+        if (RUMI_GUARDED("LocalMappingStep / rumi_keyframe_culling", &rumi_facade::no_growth,
+                         rumi_keyframe_culling(h, table.data(), (int32_t)table.size(), cand.data(), nc, pts.data(), (int32_t)pts.size(), obsKf.data(),
+                                               obsFeature.data(), (int32_t)obsKf.size(), flags, status.data(), nMPs.data(), nRedundant.data(),
+                                               culled.data(), &nCulled)) != RUMI_OK)
+            return -1;
+        for (int c = 0; c < nc; c++)                                            // :1072, in the loop's order; a not_erase key-frame only gets mbToBeErased
+            if (status[c] == RUMI_CULL_CULLED || status[c] == RUMI_CULL_TO_BE_ERASED) vpLocalKeyFrames[c]->SetBadFlag();
+        return nCulled;
+    }
+
+#ifdef RUMI_HAVE_SOPHUS
     struct Marshalled { Csr fv; std::vector<int32_t> mp; std::vector<float> pos; };
 
     template <class KeyFrameT> static bool has_stereo(KeyFrameT *pKF) {

@@ -1,6 +1,7 @@
 """Host-side mirror of ``LocalMapping::CreateNewMapPoints`` (R/lib_src/LocalMapping.cc:354-647, monocular pinhole) over the C ABI in
-include/rumi_mapping.h: one call for the current key-frame and all of its neighbours; and of the map-point refresh
-(``MapPoint::ComputeDistinctiveDescriptors`` / ``UpdateNormalAndDepth``, R/lib_src/MapPoint.cc:353-427, 450-518) for a batch of points."""
+include/rumi_mapping.h: one call for the current key-frame and all of its neighbours; of the map-point refresh
+(``MapPoint::ComputeDistinctiveDescriptors`` / ``UpdateNormalAndDepth``, R/lib_src/MapPoint.cc:353-427, 450-518) for a batch of points; and of
+``LocalMapping::KeyFrameCulling`` / ``CloudKeyFrameCulling`` (R/lib_src/LocalMapping.cc:953-1079, 820-951) for the whole covisible list."""
 import ctypes as C
 
 import numpy as np
@@ -36,6 +37,11 @@ def _lib():
     L.rumi_refresh_destroy.restype = None
     L.rumi_refresh_map_points.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.rumi_refresh_stage_ms.argtypes = [vp, vp]
+    L.rumi_cull_create.argtypes = [i32, C.POINTER(vp)]
+    L.rumi_cull_destroy.argtypes = [vp]
+    L.rumi_cull_destroy.restype = None
+    L.rumi_keyframe_culling.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.rumi_cull_stage_ms.argtypes = [vp, vp]
     L._mapping_ready = True
     return L
 
@@ -202,3 +208,118 @@ def RefreshMapPoints(batch, what=REFRESH_DESCRIPTOR | REFRESH_NORMAL_DEPTH, refr
     out = batch.outputs() if out is None else out
     capi.check(refresher.status(batch, what, out))
     return {k: v[:batch.n_pts] for k, v in out.items()}
+
+
+# ---- key-frame culling ----
+CULL_CLOUD, CULL_ABORT_BA = 1, 2
+CULL_NOT_REACHED, CULL_SKIPPED_CLOUD, CULL_SKIPPED_INIT, CULL_SKIPPED_BAD, CULL_KEPT, CULL_CULLED, CULL_TO_BE_ERASED = range(7)
+CULL_MAX_KEYFRAMES = 65536
+
+CULL_POINT_DTYPE = np.dtype([("obs_begin", "<i4"), ("obs_end", "<i4"), ("n_obs_count", "<i4"), ("is_bad", "u1"), ("pad_", "u1", 3)])
+assert CULL_POINT_DTYPE.itemsize == 16
+
+
+class RumiCullKF(C.Structure):
+    _fields_ = [("octave", C.c_void_p), ("mp", C.c_void_p), ("n", C.c_int32), ("is_bad", C.c_uint8), ("is_init", C.c_uint8),
+                ("not_erase", C.c_uint8), ("is_cloud", C.c_uint8)]
+
+
+assert C.sizeof(RumiCullKF) == 24
+
+
+class CullBatch:
+    """The arguments of one rumi_keyframe_culling call, marshalled (keeps the arrays alive).  ``keyframes``: (octave [n], mp [n] as indices
+    into ``points`` or -1, isBad, is the initial key-frame, mbNotErase, isCloud) per key-frame; ``cand``: the covisible list as indices into
+    ``keyframes``; ``points``: (isBad, Observations(), [(key-frame index, feature index), ...]) per point."""
+
+    def __init__(self, keyframes, cand, points):
+        self._keep = []
+        self.n_kf = len(keyframes)
+        self.kf = (RumiCullKF * max(self.n_kf, 1))()
+        for k, (octave, mp, bad, init, not_erase, cloud) in enumerate(keyframes):
+            octave = np.ascontiguousarray(octave, np.int32)
+            mp = np.ascontiguousarray(mp, np.int32)
+            assert len(octave) == len(mp)
+            self._keep += [octave, mp]
+            c = self.kf[k]
+            c.octave, c.mp, c.n = octave.ctypes.data, mp.ctypes.data, len(mp)
+            c.is_bad, c.is_init, c.not_erase, c.is_cloud = int(bool(bad)), int(bool(init)), int(bool(not_erase)), int(bool(cloud))
+        self.n_cand = len(cand)
+        self.cand = np.array(list(cand) + [0], np.int32)
+        self.n_pts = len(points)
+        self.pts = np.zeros(max(self.n_pts, 1), CULL_POINT_DTYPE)
+        okf, ofeat = [], []
+        for i, (bad, n_obs_count, obs) in enumerate(points):
+            self.pts[i] = (len(okf), len(okf) + len(obs), n_obs_count, int(bool(bad)), 0)
+            okf += [o[0] for o in obs]
+            ofeat += [o[1] for o in obs]
+        self.n_obs = len(okf)
+        self.obs_kf = np.array(okf + [0], np.int32)
+        self.obs_feature = np.array(ofeat + [0], np.int32)
+
+    def outputs(self, fill=0):
+        """Fresh output arrays, every byte ``fill``."""
+        n = max(self.n_cand, 1)
+        out = {}
+        for k, m in (("status", n), ("n_mps", n), ("n_redundant", n), ("culled", n), ("n_culled", 1)):
+            a = np.empty(m, np.int32)
+            a.view(np.uint8).fill(fill)
+            out[k] = a
+        return out
+
+    def args(self, flags, out):
+        """The argument tuple after the handle (the oracle of the tests takes the same, and more)."""
+        return (C.byref(self.kf), self.n_kf, capi.ptr(self.cand), self.n_cand, capi.ptr(self.pts), self.n_pts, capi.ptr(self.obs_kf),
+                capi.ptr(self.obs_feature), self.n_obs, int(flags), capi.ptr(out["status"]), capi.ptr(out["n_mps"]), capi.ptr(out["n_redundant"]),
+                capi.ptr(out["culled"]), capi.ptr(out["n_culled"]))
+
+
+class KeyFrameCuller:
+    """A rumi_cull handle (the blocks of its calls); one per calling thread."""
+
+    def __init__(self, device=-1):
+        self._lib = _lib()
+        h = C.c_void_p()
+        capi.check(self._lib.rumi_cull_create(device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if self._h:
+            self._lib.rumi_cull_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def stage_ms(self):
+        """(validation + pack, upload + kernels + download, write-out) of the last call, host wall-clock ms."""
+        out = np.zeros(3, np.float32)
+        capi.check(self._lib.rumi_cull_stage_ms(self._h, capi.ptr(out)))
+        return out
+
+    def status(self, batch, flags, out):
+        """The raw status of one call (outputs in ``out``)."""
+        return self._lib.rumi_keyframe_culling(self._h, *batch.args(flags, out))
+
+
+_culler = None
+
+
+def trim(batch, out):
+    """The outputs cut to their lengths: status, n_mps, n_redundant [n_cand], culled [n_culled]."""
+    n = int(out["n_culled"][0])
+    return dict(status=out["status"][:batch.n_cand], n_mps=out["n_mps"][:batch.n_cand], n_redundant=out["n_redundant"][:batch.n_cand],
+                culled=out["culled"][:n])
+
+
+def keyframe_culling(batch, cloud=False, abort_ba=False, culler=None, out=None):
+    """KeyFrameCulling (``cloud``: CloudKeyFrameCulling) over ``batch`` in one device call.  Returns a dict of status (CULL_*), n_mps,
+    n_redundant per candidate and culled, the positions in the covisible list to call SetBadFlag() on, in order."""
+    global _culler
+    if culler is None:
+        if _culler is None:
+            _culler = KeyFrameCuller()
+        culler = _culler
+    out = batch.outputs() if out is None else out
+    capi.check(culler.status(batch, (CULL_CLOUD if cloud else 0) | (CULL_ABORT_BA if abort_ba else 0), out))
+    return trim(batch, out)
