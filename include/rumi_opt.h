@@ -170,6 +170,42 @@ int rumi_optimize_sim3(RumiOptimizer *o, int32_t n, const int32_t *pair_of, int3
                        const float *inv_sigma2_2, const uint8_t *skip12, const uint8_t *skip21, const float *K4_1, const float *K4_2, float th2,
                        int32_t fix_scale, int32_t robust_first_pass, double *S_io8, uint8_t *status_out, int32_t *result3);
 
+/* Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale) —
+ * R/lib_src/Optimizer.cc:1357-1623 (LoopClosing::CorrectLoop) and its merge overload (pCurKF, vpFixedKFs, vpFixedCorrectedKFs, vpNonFixedKFs,
+ * vpNonCorrectedMPs) — :1625-1918: the Sim3 pose graph, Levenberg-Marquardt with setUserLambdaInit(1e-16) over g2o::VertexSim3Expmap vertices
+ * and g2o::EdgeSim3 edges with numeric Jacobians (G/core/base_binary_edge.hpp, central differences, delta 1e-9) and identity information.
+ *   S_io8      n_v x 8 in/out  vertex estimates (qx qy qz qw tx ty tz s); fixed vertices and vertices without an active edge are not written
+ *   fixed      n_v             1 = fixed vertex
+ *   fix_scale  n_v             g2o's _fix_scale: the seventh update component is zeroed in oplusImpl (and with it that Jacobian column)
+ *   edges      n_e: e_v0 / e_v1 = g2o's vertex 0 / vertex 1, meas8 n_e x 8 = the measurement C; error log(C * S_v0 * S_v1^-1)
+ *   n_iterations  optimize(n) (20 upstream); stop_flag as for rumi_local_ba (may be NULL)
+ *   stats[4]   LM iterations run, LM trials in total, vertices that took rows, how it ended: 0 ran all iterations, 1 trial limit or rho == 0,
+ *              2 three iterations in a row with (iniChi - currentChi) * 1e3 < iniChi, 3 stop flag
+ *   chi2_trace n_iterations + 1: the active chi2 before the first iteration (always, also with n_iterations = 0 or a raised stop flag) and
+ *              after each one; entries not reached are NaN
+ * Active sets as SparseOptimizer::initializeOptimization builds them: an edge whose two vertices are both fixed is NOT active (it adds
+ * nothing to chi2), a vertex without an active edge takes no rows and comes back unchanged; a graph without active edges returns RUMI_OK with
+ * stats = 0 and an all-NaN trace.  A graph without a fixed vertex is accepted (free gauge, result unpinned).
+ * The linear system of every trial is dense: 7 x 7 blocks in vertex order, blocked Cholesky; the matrix ((7 * rows)^2 doubles) is allocated by the
+ * first call.  RUMI_E_CAPACITY: n_v above the handle's max_kf or n_e above its max_edges.  Arguments
+ * are validated on the host before anything is uploaded (indices, v0 != v1, finite numbers, unit quaternions to 1e-3, positive scales):
+ * RUMI_E_INVALID leaves every output untouched.  A HIP error during the run (RUMI_E_NO_DEVICE) leaves S_io8 and stats untouched and
+ * chi2_trace partly written (the entries reached, NaN after them).  Two calls on the same input return the same bytes.  Parity against the reference is
+ * unpinned: upstream factors with Eigen's sparse Cholesky under a fill-reducing order. */
+int rumi_essential_graph(RumiOptimizer *o, int32_t n_v, double *S_io8, const uint8_t *fixed, const uint8_t *fix_scale, int32_t n_e,
+                         const int32_t *e_v0, const int32_t *e_v1, const double *meas8, int32_t n_iterations,
+                         const volatile uint8_t *stop_flag, int32_t *stats, double *chi2_trace);
+
+/* The map-point correction that ends both overloads.  X n x 3 float in/out; ref[n] = index of the point's reference vertex, -1 = leave the
+ * point alone; two per-vertex transform tables of n_v entries.
+ *   mode 0 (Optimizer.cc:1611-1616): tab_a = Srw (vScw), tab_b = correctedSwr (vCorrectedSwc), Sim3 as 8 doubles;
+ *           X <- float(correctedSwr.map(Srw.map(double(X))))
+ *   mode 1 (Optimizer.cc:1907-1911): tab_a = Twr (GetPoseInverse after the write-back), tab_b = TNonCorrectedwr (mTwcBefMerge), SE(3) as 7
+ *           floats (qx qy qz qw tx ty tz); X <- (Twr * TNonCorrectedwr^-1) * X in float, associated as written there
+ * Same validation rules as above; n within the handle's max_mp. */
+int rumi_sim3_correct_points(RumiOptimizer *o, int32_t mode, int32_t n, float *X, const int32_t *ref, int32_t n_v, const void *tab_a,
+                             const void *tab_b);
+
 #ifdef __cplusplus
 }
 #endif

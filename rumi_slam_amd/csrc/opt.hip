@@ -1980,6 +1980,7 @@ __device__ __forceinline__ double wave_allreduce_max(double v) {
 }
 
 #include "ba_windows.inc"
+#include "essential.inc"
 
 }  // namespace rumi
 
@@ -2026,6 +2027,8 @@ struct RumiOptimizer {
     bool profiling = false;
     hipEvent_t evK[6] = {nullptr};
     float kernelMs[4] = {0};          // hpp, syrk, solve (ms over the call), trials
+    // essential graph (essential_host.inc): the dense matrix and one block for the rest, allocated by the first rumi_essential_graph call
+    uint8_t *dEgA = nullptr, *dEg = nullptr; size_t egACap = 0, egCap = 0;
 };
 
 template <class T> static int oalloc(T **p, size_t n) {
@@ -2045,6 +2048,8 @@ extern "C" void rumi_opt_destroy(RumiOptimizer *o) {
                  o->dAglob, o->dErase, o->dEOff, o->dYt, o->dG, o->dLp, o->dW, o->dColOf};
     for (void *q : p) if (q) (void)hipFree(q);
     if (o->dPairs) (void)hipFree(o->dPairs);
+    if (o->dEgA) (void)hipFree(o->dEgA);
+    if (o->dEg) (void)hipFree(o->dEg);
     { void *q[] = {o->dGpart, o->dGw, o->dChiPart, o->dSclPart, o->dWinSmall, o->dLmCtl, o->dWinTab, o->dSorted}; for (void *x : q) if (x) (void)hipFree(x); }
     if (o->hLmCtl) (void)hipHostFree(o->hLmCtl);
     if (o->hWm) (void)hipHostFree((void *)o->hWm);
@@ -2187,7 +2192,25 @@ extern "C" int rumi_pose_optimization(RumiOptimizer *o, const float *Xw, const f
     return rumi_pose_optimization_batch(o, 1, start, Xw, obs, inv_sigma2, K4, Tcw7, outlier_out, n_good_out);
 }
 
+// The eight scalars of o->dScal -> o->hScal without a runtime synchronisation (see k_ba_publish); falls back to one if the stream has drained
+// without the sequence number arriving (a failed launch).  Shared by the bundle adjustments and the essential graph.
+static int fetch_published_scalars(RumiOptimizer *o, hipStream_t st) {
+    const unsigned long long seq = ++o->pubSeq;
+    hipLaunchKernelGGL(k_ba_publish, dim3(1), dim3(64), 0, st, o->dScal, o->dhScal, seq);
+    HIP_TRY(hipGetLastError());
+    volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(o->hScal + 8);
+    for (unsigned spin = 0; *flag != seq; spin++) {
+        if ((spin & 0xFFFF) == 0xFFFF && hipStreamQuery(st) != hipErrorNotReady) {
+            HIP_TRY(hipStreamSynchronize(st));
+            if (*flag != seq) { HIP_TRY(hipMemcpyAsync(o->hScal, o->dScal, 8 * sizeof(double), hipMemcpyDeviceToHost, st)); HIP_TRY(hipStreamSynchronize(st)); break; }
+        }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return RUMI_OK;
+}
+
 #include "ba_windows_host.inc"
+#include "essential_host.inc"
 
 // mode 0: Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*, ...) — one optimize(10) with Huber(sqrt(5.991)).
 // mode 1: Optimizer::LocalBundleAdjustment(KeyFrame *pMainKF, vpAdjustKF, vpFixedKF, bool*) (merge window, Optimizer.cc:3768-4183) —
@@ -2377,20 +2400,7 @@ static int ba_run(RumiOptimizer *o, int mode, int32_t nKF, float *kf_pose7, cons
     const int nSlices = 64;
     // the eight scalars of o->dScal -> o->hScal, without a runtime synchronisation (see k_ba_publish); falls back to one if the stream has
     // drained without the number arriving (a failed launch)
-    auto fetch_scalars = [&]() -> int {
-        const unsigned long long seq = ++o->pubSeq;
-        hipLaunchKernelGGL(k_ba_publish, dim3(1), dim3(64), 0, st, o->dScal, o->dhScal, seq);
-        HIP_TRY(hipGetLastError());
-        volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(o->hScal + 8);
-        for (unsigned spin = 0; *flag != seq; spin++) {
-            if ((spin & 0xFFFF) == 0xFFFF && hipStreamQuery(st) != hipErrorNotReady) {
-                HIP_TRY(hipStreamSynchronize(st));
-                if (*flag != seq) { HIP_TRY(hipMemcpyAsync(o->hScal, o->dScal, 8 * sizeof(double), hipMemcpyDeviceToHost, st)); HIP_TRY(hipStreamSynchronize(st)); break; }
-            }
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        return RUMI_OK;
-    };
+    auto fetch_scalars = [&]() -> int { return fetch_published_scalars(o, st); };
     auto chi2_of = [&](int which, double *out) -> int {
         HIP_TRY(hipMemsetAsync(o->dScal, 0, sizeof(double), st));
         hipLaunchKernelGGL(k_ba_chi2, dim3(gE), dim3(256), 0, st, B, o->dT[which], o->dX[which]);

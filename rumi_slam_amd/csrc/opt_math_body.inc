@@ -272,6 +272,55 @@ RUMI_HD DSim3 sim3_exp(const double u[7]) {
     S.s = s;
     return S;
 }
+// Sim3::log(): (omega, upsilon, sigma)                                            sim3.h:148-230
+// The rotation part is read off the rotation matrix (deltaR, with acos of the half trace away from the identity), upsilon solves
+// W upsilon = t with the same W as the exponential; upstream solves by a pivoted LU, here: elimination with row pivoting, written with
+// fixed indices (no runtime-indexed arrays on the device).
+RUMI_HD void sim3_log(const DSim3 &S, double out[7]) {
+    const double s = S.s, sigma = log(s), eps = 0.00001;
+    double R[3][3];
+    quat_to_matrix(S.r, R);
+    const double d = 0.5 * (R[0][0] + R[1][1] + R[2][2] - 1);
+    const bool smallT = d > 1 - eps;
+    double theta = 0, k = 0.5;
+    if (!smallT) { theta = acos(d); k = theta / (2 * sqrt(1 - d * d)); }
+    const double wx = k * (R[2][1] - R[1][2]), wy = k * (R[0][2] - R[2][0]), wz = k * (R[1][0] - R[0][1]);
+    double A, B, C;
+    if (fabs(sigma) < eps) {
+        C = 1;
+        if (smallT) { A = 1. / 2.; B = 1. / 6.; }
+        else { const double theta2 = theta * theta; A = (1 - cos(theta)) / theta2; B = (theta - sin(theta)) / (theta2 * theta); }
+    } else {
+        C = (s - 1) / sigma;
+        if (smallT) { const double sigma2 = sigma * sigma; A = ((sigma - 1) * s + 1) / sigma2; B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma); }
+        else {
+            const double a = s * sin(theta), b = s * cos(theta), theta2 = theta * theta, c = theta2 + sigma * sigma;
+            A = (a * sigma + (1 - b) * theta) / (theta * c);
+            B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
+        }
+    }
+    const double O[3][3] = {{0, -wz, wy}, {wz, 0, -wx}, {-wy, wx, 0}};
+    double m0[4], m1[4], m2[4];
+    {
+        double W[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                const double o2 = O[i][0] * O[0][j] + O[i][1] * O[1][j] + O[i][2] * O[2][j];
+                W[i][j] = (A * O[i][j] + B * o2) + (i == j ? C : 0.0);
+            }
+        for (int j = 0; j < 3; j++) { m0[j] = W[0][j]; m1[j] = W[1][j]; m2[j] = W[2][j]; }
+        m0[3] = S.t.x; m1[3] = S.t.y; m2[3] = S.t.z;
+    }
+#define RUMI_SWAP_ROWS(a, b) for (int j_ = 0; j_ < 4; j_++) { const double t_ = a[j_]; a[j_] = b[j_]; b[j_] = t_; }
+    if (fabs(m1[0]) > fabs(m0[0])) RUMI_SWAP_ROWS(m0, m1)
+    if (fabs(m2[0]) > fabs(m0[0])) RUMI_SWAP_ROWS(m0, m2)
+    { const double f1 = m1[0] / m0[0], f2 = m2[0] / m0[0]; for (int j = 1; j < 4; j++) { m1[j] -= f1 * m0[j]; m2[j] -= f2 * m0[j]; } }
+    if (fabs(m2[1]) > fabs(m1[1])) RUMI_SWAP_ROWS(m1, m2)
+    { const double f2 = m2[1] / m1[1]; for (int j = 2; j < 4; j++) m2[j] -= f2 * m1[j]; }
+#undef RUMI_SWAP_ROWS
+    const double u2 = m2[3] / m2[2], u1 = (m1[3] - m1[2] * u2) / m1[1], u0 = (m0[3] - m0[1] * u1 - m0[2] * u2) / m0[0];
+    out[0] = wx; out[1] = wy; out[2] = wz; out[3] = u0; out[4] = u1; out[5] = u2; out[6] = sigma;
+}
 
 
 // Cholesky solve of the N x N system (H + lambda I) x = b, H given by its upper triangle packed row-major.

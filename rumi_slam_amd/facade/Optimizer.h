@@ -3,6 +3,7 @@
 // graph gathering (Optimizer.cc:763-897, :1011-1271), locking (MapPoint::mGlobalMutex, Map::mMutexMapUpdate) and the
 // write-back / observation erasing (:993-1000, :1325-1354) stay here on the host; the arithmetic runs on the GPU.
 #pragma once
+#include <algorithm>
 #include <cstdio>
 #include <list>
 #include <map>
@@ -485,6 +486,323 @@ public:
         if (res[2]) return 0;                                                          // :2437-2438
         mAcumHessian.setZero();                                                        // :2446
         return (float)res[0] / (float)g.n();                                           // :2468
+    }
+    // ---- Optimizer::OptimizeEssentialGraph, both overloads (Optimizer.cc:1357-1623, :1625-1918), over rumi_essential_graph and
+    //      rumi_sim3_correct_points.  The graph is gathered as upstream gathers it, measurements are formed in double on the host. ----
+    struct EssentialGraphFlat {                 // the flattened graph; vertex k is key-frame id[k]
+        std::vector<unsigned long> id;
+        std::vector<double> S, meas;
+        std::vector<uint8_t> fixed, fix_scale;
+        std::vector<int32_t> v0, v1;
+        int32_t stats[4] = {0, 0, 0, 0};
+        int add_vertex(unsigned long kfId, const double *S8, bool fix, bool fs) {
+            id.push_back(kfId); S.insert(S.end(), S8, S8 + 8); fixed.push_back(fix); fix_scale.push_back(fs);
+            return (int)id.size() - 1;
+        }
+        void add_edge(int i, int j, const double *Sji) { v0.push_back(i); v1.push_back(j); meas.insert(meas.end(), Sji, Sji + 8); }   // setVertex(0, i), setVertex(1, j)
+    };
+    // tests set this to receive a copy of the graph the next call gathers (per thread)
+    static EssentialGraphFlat *&essential_graph_record() { thread_local EssentialGraphFlat *r = nullptr; return r; }
+
+private:
+    // g2o::Sim3 on (qx qy qz qw tx ty tz s) doubles: operator* (sim3.h:266-272), inverse (:233-236), Sim3(q, t, 1.0) of a float pose
+    static void eg_rot(const double *q, const double *v, double *o) {
+        const double ux = 2 * (q[1] * v[2] - q[2] * v[1]), uy = 2 * (q[2] * v[0] - q[0] * v[2]), uz = 2 * (q[0] * v[1] - q[1] * v[0]);
+        o[0] = v[0] + q[3] * ux + (q[1] * uz - q[2] * uy); o[1] = v[1] + q[3] * uy + (q[2] * ux - q[0] * uz); o[2] = v[2] + q[3] * uz + (q[0] * uy - q[1] * ux);
+    }
+    static void eg_mul(const double *a, const double *b, double *o) {
+        double r[3];
+        eg_rot(a, b + 4, r);
+        const double q[4] = {a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1], a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2],
+                             a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0], a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2]};
+        for (int k = 0; k < 4; k++) o[k] = q[k];
+        for (int k = 0; k < 3; k++) o[4 + k] = a[7] * r[k] + a[4 + k];
+        o[7] = a[7] * b[7];
+    }
+    static void eg_inv(const double *a, double *o) {
+        const double c[4] = {-a[0], -a[1], -a[2], a[3]}, k = -1. / a[7], t[3] = {k * a[4], k * a[5], k * a[6]};
+        double r[3];
+        eg_rot(c, t, r);
+        for (int i = 0; i < 4; i++) o[i] = c[i];
+        for (int i = 0; i < 3; i++) o[4 + i] = r[i];
+        o[7] = 1. / a[7];
+    }
+    static void eg_identity(double *o) { o[0] = o[1] = o[2] = 0; o[3] = 1; o[4] = o[5] = o[6] = 0; o[7] = 1; }
+    template <class SE3T> static void eg_from_pose(const SE3T &T, double *o) {          // Tcw.cast<double>() -> g2o::Sim3(q, t, 1.0)
+        const auto q = T.unit_quaternion(); const auto t = T.translation();
+        o[0] = q.x(); o[1] = q.y(); o[2] = q.z(); o[3] = q.w(); o[4] = t(0); o[5] = t(1); o[6] = t(2); o[7] = 1.0;
+    }
+    template <class SE3T> static void eg_pose7(const SE3T &T, float *o) {
+        const auto q = T.unit_quaternion(); const auto t = T.translation();
+        o[0] = q.x(); o[1] = q.y(); o[2] = q.z(); o[3] = q.w(); o[4] = t(0); o[5] = t(1); o[6] = t(2);
+    }
+    static bool eg_solve(EssentialGraphFlat &g, const char *where) {
+        if (EssentialGraphFlat *r = essential_graph_record()) *r = g;
+        std::vector<double> trace(21);
+        const int rc = RUMI_GUARDED(where, &Optimizer::grow_arena, rumi_essential_graph(arena(), (int32_t)g.id.size(), g.S.data(), g.fixed.data(), g.fix_scale.data(),
+                                    (int32_t)g.v0.size(), g.v0.data(), g.v1.data(), g.meas.data(), 20, nullptr, g.stats, trace.data()));
+        if (EssentialGraphFlat *r = essential_graph_record()) for (int k = 0; k < 4; k++) r->stats[k] = g.stats[k];
+        return rc == RUMI_OK;
+    }
+
+public:
+    // void static OptimizeEssentialGraph(Map *pMap, KeyFrame *pLoopKF, KeyFrame *pCurKF, const LoopClosing::KeyFrameAndPose &NonCorrectedSim3,
+    //                                    const LoopClosing::KeyFrameAndPose &CorrectedSim3, const map<KeyFrame *, set<KeyFrame *>> &LoopConnections,
+    //                                    const bool &bFixScale)                                                  Optimizer.cc:1357-1623
+    // Bad key-frames get no vertex (:1390) and, unlike upstream (which would dereference a null vertex), are passed over wherever they would
+    // be an edge's end.  The inertial edge of :1550-1565 is not built: a key-frame with bImu and mPrevKF is reported and goes without it.
+    template <class MapT, class KeyFrameT, class PoseMapT, class ConnT>
+    static void OptimizeEssentialGraph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const PoseMapT &NonCorrectedSim3, const PoseMapT &CorrectedSim3,
+                                       const ConnT &LoopConnections, const bool &bFixScale) {
+        const auto vpKFs = pMap->GetAllKeyFrames();
+        const auto vpMPs = pMap->GetAllMapPoints();
+        const int minFeat = 100;
+        EssentialGraphFlat g;
+        std::map<unsigned long, int> vertexOf;
+        for (size_t i = 0; i < vpKFs.size(); i++) {                                   // :1387-1419
+            KeyFrameT *pKF = vpKFs[i];
+            if (pKF->isBad()) continue;
+            double S[8];
+            const auto it = CorrectedSim3.find(pKF);
+            if (it != CorrectedSim3.end()) sim3_to8(it->second, S); else eg_from_pose(pKF->GetPose(), S);
+            vertexOf[pKF->mnId] = g.add_vertex(pKF->mnId, S, (long)pKF->mnId == (long)pMap->GetInitKFid(), bFixScale);
+        }
+        const std::vector<double> vScw = g.S;                                          // vScw[nIDi], by vertex
+        auto vertex = [&](KeyFrameT *p) { const auto f = vertexOf.find(p->mnId); return f == vertexOf.end() ? -1 : f->second; };
+        auto non_corrected = [&](KeyFrameT *p, int v, double *o) {                     // NonCorrectedSim3 if it holds the key-frame, else vScw
+            const auto f = NonCorrectedSim3.find(p);
+            if (f != NonCorrectedSim3.end()) sim3_to8(f->second, o); else for (int k = 0; k < 8; k++) o[k] = vScw[8 * (size_t)v + k];
+        };
+        std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+        for (auto mit = LoopConnections.begin(); mit != LoopConnections.end(); ++mit) {   // loop edges, :1425-1463
+            KeyFrameT *pKF = mit->first;
+            const int vi = vertex(pKF);
+            if (vi < 0) continue;
+            const unsigned long nIDi = pKF->mnId;
+            double Swi[8], Sji[8];
+            eg_inv(&vScw[8 * (size_t)vi], Swi);
+            for (auto sit = mit->second.begin(); sit != mit->second.end(); ++sit) {
+                const unsigned long nIDj = (*sit)->mnId;
+                if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(*sit) < minFeat) continue;
+                const int vj = vertex(*sit);
+                if (vj < 0) continue;
+                eg_mul(&vScw[8 * (size_t)vj], Swi, Sji);
+                g.add_edge(vi, vj, Sji);
+                sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+            }
+        }
+        bool inertial = false;
+        for (size_t i = 0; i < vpKFs.size(); i++) {                                   // normal edges, :1465-1566
+            KeyFrameT *pKF = vpKFs[i];
+            const int vi = vertex(pKF);
+            if (vi < 0 || pKF->isBad()) continue;
+            double Siw[8], Swi[8], Sjw[8], Sji[8];
+            non_corrected(pKF, vi, Siw);
+            eg_inv(Siw, Swi);
+            KeyFrameT *pParentKF = pKF->GetParent();
+            if (pParentKF && vertex(pParentKF) >= 0) {                                 // spanning tree
+                const int vj = vertex(pParentKF);
+                non_corrected(pParentKF, vj, Sjw);
+                eg_mul(Sjw, Swi, Sji);
+                g.add_edge(vi, vj, Sji);
+            }
+            const auto sLoopEdges = pKF->GetLoopEdges();                               // earlier loop edges
+            for (auto sit = sLoopEdges.begin(); sit != sLoopEdges.end(); ++sit) {
+                KeyFrameT *pLKF = *sit;
+                const int vl = vertex(pLKF);
+                if (pLKF->mnId < pKF->mnId && vl >= 0) {
+                    non_corrected(pLKF, vl, Sjw);
+                    eg_mul(Sjw, Swi, Sji);
+                    g.add_edge(vi, vl, Sji);
+                }
+            }
+            const auto vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);           // covisibility graph
+            for (auto vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); ++vit) {
+                KeyFrameT *pKFn = *vit;
+                if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn)) {
+                    if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                        if (sInsertedEdges.count(std::make_pair(std::min<unsigned long>(pKF->mnId, pKFn->mnId), std::max<unsigned long>(pKF->mnId, pKFn->mnId)))) continue;
+                        const int vn = vertex(pKFn);
+                        if (vn < 0) continue;
+                        non_corrected(pKFn, vn, Sjw);
+                        eg_mul(Sjw, Swi, Sji);
+                        g.add_edge(vi, vn, Sji);
+                    }
+                }
+            }
+            if (pKF->bImu && pKF->mPrevKF) inertial = true;
+        }
+        if (inertial) rumi_facade::report("Optimizer::OptimizeEssentialGraph", RUMI_E_INVALID, "key-frames with bImu and mPrevKF: the inertial edge (Optimizer.cc:1550-1565) is not built and was left out (DESIGN.md section 7)");
+        if (!eg_solve(g, "Optimizer / rumi_essential_graph")) return;
+        std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+        const int nV = (int)g.id.size();
+        std::vector<double> vCorrectedSwc((size_t)nV * 8);
+        for (size_t i = 0; i < vpKFs.size(); i++) {                                   // SE3 pose recovering, :1575-1587: [sR t; 0 1] -> [R t/s; 0 1]
+            KeyFrameT *pKFi = vpKFs[i];
+            const int v = vertex(pKFi);
+            if (v < 0) continue;
+            const double *S = &g.S[8 * (size_t)v];
+            eg_inv(S, &vCorrectedSwc[8 * (size_t)v]);
+            const float s = (float)S[7];
+            pKFi->SetPose(Sophus::SE3f(Eigen::Quaternionf((float)S[3], (float)S[0], (float)S[1], (float)S[2]),
+                                       Eigen::Vector3f((float)S[4] / s, (float)S[5] / s, (float)S[6] / s)));
+        }
+        std::vector<float> X;                                                          // correct points, :1590-1619
+        std::vector<int32_t> ref;
+        std::vector<size_t> which;
+        for (size_t i = 0; i < vpMPs.size(); i++) {
+            auto *pMP = vpMPs[i];
+            if (pMP->isBad()) continue;
+            long nIDr;
+            if (pMP->mnCorrectedByKF == pCurKF->mnId) nIDr = (long)pMP->mnCorrectedReference;
+            else {
+                KeyFrameT *pRefKF = pMP->GetReferenceKeyFrame();
+                if (!pRefKF) continue;
+                nIDr = (long)pRefKF->mnId;
+            }
+            const auto f = vertexOf.find((unsigned long)nIDr);
+            if (f == vertexOf.end()) continue;
+            const auto P = pMP->GetWorldPos();
+            X.push_back(P(0)); X.push_back(P(1)); X.push_back(P(2));
+            ref.push_back(f->second); which.push_back(i);
+        }
+        if (!which.empty()) {
+            if (RUMI_GUARDED("Optimizer / rumi_sim3_correct_points", &Optimizer::grow_arena, rumi_sim3_correct_points(arena(), 0, (int32_t)which.size(), X.data(), ref.data(), nV, vScw.data(), vCorrectedSwc.data())) != RUMI_OK) return;
+            for (size_t k = 0; k < which.size(); k++) {
+                auto *pMP = vpMPs[which[k]];
+                pMP->SetWorldPos(Eigen::Vector3f(X[3 * k], X[3 * k + 1], X[3 * k + 2]));
+                pMP->UpdateNormalAndDepth();
+            }
+        }
+        pMap->IncreaseChangeIndex();
+    }
+
+    // void static OptimizeEssentialGraph(KeyFrame *pCurKF, vector<KeyFrame *> &vpFixedKFs, vector<KeyFrame *> &vpFixedCorrectedKFs,
+    //                                    vector<KeyFrame *> &vpNonFixedKFs, vector<MapPoint *> &vpNonCorrectedMPs)      Optimizer.cc:1625-1918
+    // Three vertex groups (:1654-1746): fixed (good pose, _fix_scale), fixed and corrected (good and bad pose: the estimate is the corrected pose,
+    // vScw the one before the merge), free (bad pose).  An edge exists where both ends have a good pose (measured from the corrected poses)
+    // or else both a bad one (from the poses before the merge) (:1757-1859).  A key-frame listed twice is visited twice, as upstream.
+    template <class KeyFrameT, class MapPointT>
+    static void OptimizeEssentialGraph(KeyFrameT *pCurKF, std::vector<KeyFrameT *> &vpFixedKFs, std::vector<KeyFrameT *> &vpFixedCorrectedKFs,
+                                       std::vector<KeyFrameT *> &vpNonFixedKFs, std::vector<MapPointT *> &vpNonCorrectedMPs) {
+        auto *pMap = pCurKF->GetMap();
+        const int minFeat = 100;
+        EssentialGraphFlat g;
+        std::map<unsigned long, int> vertexOf;
+        std::vector<double> vScw, vCorrectedSwc;                                       // by vertex; a default g2o::Sim3 where upstream never assigns
+        std::vector<uint8_t> good, bad;
+        auto push = [&](KeyFrameT *pKFi, const double *Siw, bool fix, bool fs, const double *Scw, const double *Swc, bool isGood, bool isBad) {
+            vertexOf[pKFi->mnId] = g.add_vertex(pKFi->mnId, Siw, fix, fs);
+            double I[8];
+            eg_identity(I);
+            vScw.insert(vScw.end(), Scw ? Scw : I, (Scw ? Scw : I) + 8);
+            vCorrectedSwc.insert(vCorrectedSwc.end(), Swc ? Swc : I, (Swc ? Swc : I) + 8);
+            good.push_back(isGood); bad.push_back(isBad);
+        };
+        for (KeyFrameT *pKFi : vpFixedKFs) {
+            if (pKFi->isBad()) continue;
+            double Siw[8], Swi[8];
+            eg_from_pose(pKFi->GetPose(), Siw); eg_inv(Siw, Swi);
+            push(pKFi, Siw, true, true, nullptr, Swi, true, false);
+        }
+        std::set<unsigned long> sIdKF;
+        for (KeyFrameT *pKFi : vpFixedCorrectedKFs) {
+            if (pKFi->isBad()) continue;
+            double Siw[8], Swi[8], Sbef[8];
+            eg_from_pose(pKFi->GetPose(), Siw); eg_inv(Siw, Swi); eg_from_pose(pKFi->mTcwBefMerge, Sbef);
+            push(pKFi, Siw, true, false, Sbef, Swi, true, true);
+            sIdKF.insert(pKFi->mnId);
+        }
+        for (KeyFrameT *pKFi : vpNonFixedKFs) {
+            if (pKFi->isBad()) continue;
+            if (sIdKF.count(pKFi->mnId)) continue;
+            double Siw[8];
+            eg_from_pose(pKFi->GetPose(), Siw);
+            push(pKFi, Siw, false, false, Siw, nullptr, false, true);
+            sIdKF.insert(pKFi->mnId);
+        }
+        std::vector<KeyFrameT *> vpKFs;
+        vpKFs.insert(vpKFs.end(), vpFixedKFs.begin(), vpFixedKFs.end());
+        vpKFs.insert(vpKFs.end(), vpFixedCorrectedKFs.begin(), vpFixedCorrectedKFs.end());
+        vpKFs.insert(vpKFs.end(), vpNonFixedKFs.begin(), vpNonFixedKFs.end());
+        const std::set<KeyFrameT *> spKFs(vpKFs.begin(), vpKFs.end());
+        auto vertex = [&](KeyFrameT *p) { const auto f = vertexOf.find(p->mnId); return f == vertexOf.end() ? -1 : f->second; };
+        // the relation rule of :1772-1779 and its two repeats: the other end's pose as the measurement takes it, or false
+        auto relation = [&](int vi, int vj, double *Sjw) {
+            if (good[vi] && good[vj]) { eg_inv(&vCorrectedSwc[8 * (size_t)vj], Sjw); return true; }
+            if (bad[vi] && bad[vj]) { for (int k = 0; k < 8; k++) Sjw[k] = vScw[8 * (size_t)vj + k]; return true; }
+            return false;
+        };
+        for (KeyFrameT *pKFi : vpKFs) {
+            const int vi = vertex(pKFi);
+            if (vi < 0) continue;
+            double Swi[8], Sjw[8], Sji[8];
+            eg_identity(Swi);
+            if (bad[vi]) eg_inv(&vScw[8 * (size_t)vi], Swi);
+            KeyFrameT *pParentKFi = pKFi->GetParent();
+            if (pParentKFi && spKFs.find(pParentKFi) != spKFs.end() && vertex(pParentKFi) >= 0) {
+                const int vj = vertex(pParentKFi);
+                if (relation(vi, vj, Sjw)) { eg_mul(Sjw, Swi, Sji); g.add_edge(vi, vj, Sji); }
+            }
+            const auto sLoopEdges = pKFi->GetLoopEdges();
+            for (auto sit = sLoopEdges.begin(); sit != sLoopEdges.end(); ++sit) {
+                KeyFrameT *pLKF = *sit;
+                if (spKFs.find(pLKF) != spKFs.end() && pLKF->mnId < pKFi->mnId && vertex(pLKF) >= 0) {
+                    const int vl = vertex(pLKF);
+                    if (relation(vi, vl, Sjw)) { eg_mul(Sjw, Swi, Sji); g.add_edge(vi, vl, Sji); }
+                }
+            }
+            const auto vpConnectedKFs = pKFi->GetCovisiblesByWeight(minFeat);
+            for (auto vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); ++vit) {
+                KeyFrameT *pKFn = *vit;
+                if (pKFn && pKFn != pParentKFi && !pKFi->hasChild(pKFn) && !sLoopEdges.count(pKFn) && spKFs.find(pKFn) != spKFs.end()) {
+                    if (!pKFn->isBad() && pKFn->mnId < pKFi->mnId && vertex(pKFn) >= 0) {
+                        const int vn = vertex(pKFn);
+                        if (relation(vi, vn, Sjw)) { eg_mul(Sjw, Swi, Sji); g.add_edge(vi, vn, Sji); }
+                    }
+                }
+            }
+        }
+        if (!eg_solve(g, "Optimizer / rumi_essential_graph (merge)")) return;
+        std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+        for (KeyFrameT *pKFi : vpNonFixedKFs) {                                        // :1873-1888
+            if (pKFi->isBad()) continue;
+            const int v = vertex(pKFi);
+            if (v < 0) continue;
+            const double *S = &g.S[8 * (size_t)v], s = S[7];
+            pKFi->mTcwBefMerge = pKFi->GetPose();
+            pKFi->mTwcBefMerge = pKFi->GetPoseInverse();
+            pKFi->SetPose(Sophus::SE3f(Eigen::Quaternionf((float)S[3], (float)S[0], (float)S[1], (float)S[2]),
+                                       Eigen::Vector3f((float)(S[4] / s), (float)(S[5] / s), (float)(S[6] / s))));
+        }
+        const int nV = (int)g.id.size();
+        std::vector<float> tabA((size_t)nV * 7, 0.f), tabB((size_t)nV * 7, 0.f), X;
+        for (int v = 0; v < nV; v++) tabA[7 * (size_t)v + 3] = tabB[7 * (size_t)v + 3] = 1.f;
+        std::vector<uint8_t> tabSet((size_t)nV, 0);
+        std::vector<int32_t> ref;
+        std::vector<size_t> which;
+        bool foreign = false;
+        for (size_t i = 0; i < vpNonCorrectedMPs.size(); i++) {                       // :1891-1916
+            MapPointT *pMPi = vpNonCorrectedMPs[i];
+            if (pMPi->isBad()) continue;
+            KeyFrameT *pRefKF = pMPi->GetReferenceKeyFrame();
+            while (pRefKF && pRefKF->isBad()) { pMPi->EraseObservation(pRefKF); pRefKF = pMPi->GetReferenceKeyFrame(); }
+            if (!pRefKF) continue;
+            const int v = vertex(pRefKF);
+            if (v < 0 || !bad[v]) { foreign = true; continue; }                        // "MapPoint has a reference KF from another map"
+            if (!tabSet[v]) { eg_pose7(pRefKF->GetPoseInverse(), &tabA[7 * (size_t)v]); eg_pose7(pRefKF->mTwcBefMerge, &tabB[7 * (size_t)v]); tabSet[v] = 1; }
+            const auto P = pMPi->GetWorldPos();
+            X.push_back(P(0)); X.push_back(P(1)); X.push_back(P(2));
+            ref.push_back(v); which.push_back(i);
+        }
+        if (foreign) std::fprintf(stderr, "[rumi] Optimizer::OptimizeEssentialGraph: map points whose reference key-frame has no pose from before the merge were left alone\n");
+        if (which.empty()) return;
+        if (RUMI_GUARDED("Optimizer / rumi_sim3_correct_points (merge)", &Optimizer::grow_arena, rumi_sim3_correct_points(arena(), 1, (int32_t)which.size(), X.data(), ref.data(), nV, tabA.data(), tabB.data())) != RUMI_OK) return;
+        for (size_t k = 0; k < which.size(); k++) {
+            MapPointT *pMPi = vpNonCorrectedMPs[which[k]];
+            pMPi->SetWorldPos(Eigen::Vector3f(X[3 * k], X[3 * k + 1], X[3 * k + 2]));
+            pMPi->UpdateNormalAndDepth();
+        }
     }
 #endif
 };

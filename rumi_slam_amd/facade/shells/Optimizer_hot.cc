@@ -1,6 +1,7 @@
 // Definitions of the hot members of the reference's all-static ORB_SLAM3::Optimizer, with the reference's exact signatures
 // (include/cloud_edge_slam_lib/Optimizer.h:45-92), each a forward to the MI355X facade templates (../Optimizer.h).  The reference's
-// Optimizer.cc keeps every other member (inertial, essential graph, ...): build this file NEXT TO lib_src/Optimizer.cc and remove (or put
+// Optimizer.cc keeps every other member (inertial, OptimizeEssentialGraph4DoF, ...; the two OptimizeEssentialGraph overloads are in
+// Optimizer_essential.cc): build this file NEXT TO lib_src/Optimizer.cc and remove (or put
 // under #ifndef RUMI_HIP) the reference's own definitions of
 //   BundleAdjustment (:54-351), GlobalBundleAdjustemnt (:48-52), PoseOptimization (:723-1001), LocalBundleAdjustment (:1003-1355),
 //   OptimizeSim3 (:1920-2167), OptimizeCloudSim3 (:2169-2471), LocalBundleAdjustment for the welding window (:3768-4183).

@@ -14,7 +14,8 @@ class RumiSim3ScoreSet(C.Structure):
 
 
 OPT_SYMBOLS = ["rumi_opt_create", "rumi_opt_destroy", "rumi_pose_optimization", "rumi_pose_optimization_batch", "rumi_local_ba", "rumi_merge_ba", "rumi_bundle_adjustment", "rumi_sim3_inliers",
-               "rumi_optimize_sim3", "rumi_sim3_ransac", "rumi_opt_stage_ms", "rumi_opt_set_profiling", "rumi_opt_kernel_ms"]
+               "rumi_optimize_sim3", "rumi_sim3_ransac", "rumi_opt_stage_ms", "rumi_opt_set_profiling", "rumi_opt_kernel_ms",
+               "rumi_essential_graph", "rumi_sim3_correct_points"]
 
 
 def _lib():
@@ -37,6 +38,8 @@ def _lib():
     L.rumi_opt_kernel_ms.argtypes = [vp, vp]
     L.rumi_sim3_ransac.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.rumi_optimize_sim3.argtypes = [vp, i32, vp, i32] + [vp] * 12 + [C.c_float, i32, i32, vp, vp, vp]
+    L.rumi_essential_graph.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]
+    L.rumi_sim3_correct_points.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp]
     L._opt_ready = True
     return L
 
@@ -202,6 +205,33 @@ class Optimizer:
         capi.check(self._lib.rumi_optimize_sim3(self._h, n, P(po), len(A) if world else 0, P(A), P(B), P(P1c), P(P2c), P(obs1), P(obs2), P(w1), P(w2),
                                                 P(s12), P(s21), P(K1), P(K2), float(th2), int(fix_scale), int(robust_first_pass), P(S), P(status), P(res)))
         return int(res[0]), int(res[1]), bool(res[2]), S, status[:n]
+
+    def essential_graph(self, S8, fixed, fix_scale, e_v0, e_v1, meas8, n_iterations=20, stop_flag=None):
+        """Optimizer::OptimizeEssentialGraph on the flattened Sim3 pose graph (include/rumi_opt.h, rumi_essential_graph).
+        Returns (S8 [n_v,8], stats[4], chi2_trace[n_iterations + 1])."""
+        S = np.ascontiguousarray(S8, np.float64).reshape(-1, 8).copy()
+        fx = np.ascontiguousarray(fixed, np.uint8); fs = np.ascontiguousarray(fix_scale, np.uint8)
+        v0 = np.ascontiguousarray(e_v0, np.int32); v1 = np.ascontiguousarray(e_v1, np.int32)
+        M = np.ascontiguousarray(meas8, np.float64).reshape(-1, 8)
+        if len(fx) != len(S) or len(fs) != len(S) or len(v1) != len(v0) or len(M) != len(v0):
+            raise ValueError("essential_graph: array lengths disagree")
+        stats = np.zeros(4, np.int32); trace = np.full(max(int(n_iterations), 0) + 1, np.nan)
+        sp = capi.ptr(stop_flag) if stop_flag is not None else None
+        rc = self._lib.rumi_essential_graph(self._h, len(S), capi.ptr(S), capi.ptr(fx), capi.ptr(fs), len(v0), capi.ptr(v0), capi.ptr(v1), capi.ptr(M),
+                                            int(n_iterations), sp, capi.ptr(stats), capi.ptr(trace))
+        capi.check(rc)
+        return S, stats, trace
+
+    def correct_points(self, X, ref, tab_a, tab_b, mode=0):
+        """The point correction that ends both overloads (rumi_sim3_correct_points).  mode 0: Sim3 tables [n_v,8] double (Srw, correctedSwr);
+        mode 1: SE(3) tables [n_v,7] float (Twr, TNonCorrectedwr).  Returns X [n,3] float32."""
+        X = np.ascontiguousarray(X, np.float32).reshape(-1, 3).copy(); ref = np.ascontiguousarray(ref, np.int32)
+        dt, w = (np.float64, 8) if mode == 0 else (np.float32, 7)
+        A = np.ascontiguousarray(tab_a, dt).reshape(-1, w); B = np.ascontiguousarray(tab_b, dt).reshape(-1, w)
+        if len(ref) != len(X) or len(A) != len(B):
+            raise ValueError("correct_points: array lengths disagree")
+        capi.check(self._lib.rumi_sim3_correct_points(self._h, int(mode), len(X), capi.ptr(X), capi.ptr(ref), len(A), capi.ptr(A), capi.ptr(B)))
+        return X
 
     def set_profiling(self, on=True):
         capi.check(self._lib.rumi_opt_set_profiling(self._h, int(on)))
