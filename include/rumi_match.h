@@ -215,6 +215,9 @@ int rumi_match_bruteforce_batch_device_strided(const void *d_query, const void *
  * outputs [nframes][cap] int32 each (row i = the matches of frame i in its successor). */
 int rumi_match_bruteforce_ring_device(const void *d_desc, const void *d_n, int32_t count_stride, int64_t frame_stride, int32_t cap, int32_t nframes,
                                       void *d_best_idx, void *d_best_dist, void *d_second_dist, void *hip_stream);
+/* The blocking of the brute-force kernel, for tests that place cases on its edges: out3 = {queries per wave, queries per workgroup,
+ * train rows per LDS stage}.  Needs no device. */
+void rumi_match_bruteforce_shape(int32_t *out3);
 
 #ifdef __cplusplus
 }

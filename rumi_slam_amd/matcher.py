@@ -23,7 +23,7 @@ class RumiFeatureVector(C.Structure):
 MATCH_SYMBOLS = ["rumi_descriptor_distance", "rumi_match_create", "rumi_match_destroy", "rumi_search_by_projection_mappoints",
                  "rumi_search_by_projection_frame", "rumi_search_by_bow", "rumi_search_by_bow_kf", "rumi_search_by_projection_sim3",
                  "rumi_search_by_projection_reloc", "rumi_search_for_initialization", "rumi_search_for_triangulation", "rumi_fuse_candidates", "rumi_search_by_sim3", "rumi_frame_is_in_frustum", "rumi_search_by_bow_batch", "rumi_match_bruteforce_batch_device",
-                 "rumi_match_bruteforce_batch_device_strided", "rumi_match_bruteforce_ring_device"]
+                 "rumi_match_bruteforce_batch_device_strided", "rumi_match_bruteforce_ring_device", "rumi_match_bruteforce_shape"]
 
 
 def _lib():
@@ -55,6 +55,8 @@ def _lib():
     L.rumi_search_by_bow_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp]
     L.rumi_match_bruteforce_batch_device_strided.argtypes = [vp, vp, vp, vp, i32, C.c_int64, C.c_int64, i32, i32, vp, vp, vp, vp]
     L.rumi_match_bruteforce_ring_device.argtypes = [vp, vp, i32, C.c_int64, i32, i32, vp, vp, vp, vp]
+    L.rumi_match_bruteforce_shape.argtypes = [vp]
+    L.rumi_match_bruteforce_shape.restype = None
     L._match_ready = True
     return L
 
@@ -333,3 +335,10 @@ def bruteforce_ring(desc, counts, stream=None, out=None):
     capi.check(_lib().rumi_match_bruteforce_ring_device(desc.data_ptr(), counts.data_ptr(), counts.stride(0), desc.stride(0) if B > 1 else 32 * cap, cap, B,
                                                         out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), st.cuda_stream))
     return out
+
+
+def bruteforce_shape():
+    """(queries per wave, queries per workgroup, train rows per LDS stage) of the brute-force kernel; needs no GPU."""
+    out = (C.c_int32 * 3)()
+    _lib().rumi_match_bruteforce_shape(out)
+    return tuple(int(x) for x in out)

@@ -16,3 +16,6 @@ F="-O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics --offload-arch=gfx
 # k_baw_system (-DRUMI_BAW_STAMP: workgroups 1 and 5 of window 0 print their phases at the third LM trial): ... && python tools/with_lib.py tools/bin/librumi_hip_baw_stamp.so tools/prof_lba_batch.py 0 1
 /opt/rocm/bin/hipcc $F -DRUMI_BAW_STAMP -c opt.hip -o /tmp/opt_baw_stamp.o
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $R/tools/bin/librumi_hip_baw_stamp.so /tmp/opt_baw_stamp.o $(ls *.o | grep -v -e '^opt.o') -lpthread
+# k_bruteforce_mfma (-DRUMI_BFM_STAMP: wave 0 of the first workgroup of pair 0 prints its phases; the int8 kernel it replaced: tools/bfm_stamp_int8.patch): ... && python tools/with_lib.py tools/bin/librumi_hip_bfm_stamp.so tools/bfm_stamp.py
+/opt/rocm/bin/hipcc $F -DRUMI_BFM_STAMP -c match.hip -o /tmp/match_bfm_stamp.o
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $R/tools/bin/librumi_hip_bfm_stamp.so /tmp/match_bfm_stamp.o $(ls *.o | grep -v -e '^match.o') -lpthread
