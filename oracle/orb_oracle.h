@@ -13,8 +13,8 @@
 //
 // PARITY STATUS: "parity unpinned" for every OpenCV-owned step — OpenCV is not vendored in the
 // reference, is absent from this image, and the reference holds no tests / golden vectors for
-// this path.  The in-tree arithmetic (octree, rBRIEF sampling, ordering) is
-// pinned by source only.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg
+// this path.  The in-tree arithmetic (cell grid, octree, IC_Angle, rBRIEF sampling,
+// ordering) is pinned by the constructed cases of tests/extract_cases.py.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg
 // may use this library.
 #pragma once
 #include <cstddef>
