@@ -29,6 +29,15 @@ float rumi_hook_fast_atan2(float y, float x);   /* cv::fastAtan2, degrees */
 int rumi_hook_cv_round(float v);         /* cvRound */
 int rumi_hook_magic_div(int32_t idx, int32_t d);   /* divide-free idx / d used by the FAST cell kernel (orb_geom.h) */
 
+/* Lane packing of the batch launches (orb_geom.h: LanePack / lane_slot, the code the kernels and the launch wrappers use): for a w x h frame,
+ * the pyramid rule (scale, nlevels) and a launch of nframes frames, the mapping of every lane of kernel 0 = the resize launch that writes `level`
+ * (1 .. nlevels - 1) or kernel 1 = the batch blur's part for `level` (0 .. nlevels - 1).  force_g = 0: the frames per group the launch code
+ * picks; > 0: that many.  info[8] = {level width, lanes per frame row, G, waves per group row, groups, lanes a wave advances by, non-producing
+ * columns at the row's end, level height}.  slots: groups x waves x 64 entries of {frame (-1: the lane maps to no frame), dword column, flags}
+ * with flags 1 = produces, 2 = first dword of its frame's row, 4 = last column of its frame's row; n_out = entries (RUMI_E_CAPACITY if > cap). */
+int rumi_hook_lane_packing(int32_t w, int32_t h, float scale, int32_t nlevels, int32_t nframes, int32_t kernel, int32_t level, int32_t force_g,
+                           int32_t *info, int32_t *slots, int32_t cap, int32_t *n_out);
+
 /* Stages 1 + 3 of the last rumi_create_new_map_points call on this matcher (rumi_mapping.h; needs a device): per neighbour k and feature i1 of
  * the current key-frame, matches[k * n1 + i1] = the neighbour's feature SearchForTriangulation pairs it with when the loop reaches neighbour k
  * (after the rotation histogram, before the triangulation gates), -1 = none.  n_neigh and n1 must be those of that call.  The call itself does

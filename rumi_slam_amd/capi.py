@@ -143,7 +143,7 @@ def kfdb_lib():
 
 
 HOOK_SYMBOLS = ["rumi_hook_sort_like_std", "rumi_hook_sort_device", "rumi_hook_std_sort", "rumi_hook_quadtree", "rumi_hook_sinf", "rumi_hook_cosf",
-                "rumi_hook_fast_atan2", "rumi_hook_cv_round", "rumi_hook_magic_div", "rumi_hook_newpts_matches"]
+                "rumi_hook_fast_atan2", "rumi_hook_cv_round", "rumi_hook_magic_div", "rumi_hook_newpts_matches", "rumi_hook_lane_packing"]
 
 
 def hooks():
@@ -163,5 +163,6 @@ def hooks():
     L.rumi_hook_fast_atan2.argtypes = [C.c_float, C.c_float]
     L.rumi_hook_cv_round.argtypes = [C.c_float]
     L.rumi_hook_magic_div.argtypes = [i32, i32]
+    L.rumi_hook_lane_packing.argtypes = [i32, i32, C.c_float, i32, i32, i32, i32, i32, vp, vp, i32, C.POINTER(i32)]
     L._hooks_ready = True
     return L

@@ -127,6 +127,74 @@ inline bool make_geometry(const OrbTables &t, int w, int h, std::vector<LevelGeo
     return true;
 }
 
+// ---- Lane packing of the batch launches of k_resize and k_blur ----
+// Both kernels give a lane one dword (4 pixels) of a row and a wave one stretch of a row; a wave that hangs over the row's end issues its
+// instructions for lanes that own nothing.  The row state (row index, source rows, vertical taps, mirrored rows) is the same for every frame
+// of a launch, so the launch lays the same rows of G consecutive frames side by side: a group's row is G * lpr virtual lanes long, a wave
+// takes 64 consecutive ones, and a lane derives (frame in group, dword column) once in its prologue.  Only a lane's ADDRESS depends on its
+// frame.  k_resize: lpr = ceil(w / 4), a wave advances by 64 lanes (G = 1 is the mapping of a launch per frame).  k_blur: a frame's row gets
+// one more column, the dword beyond the row's last one (all mirrored bytes: the right halo of the last producing lane), and a wave advances
+// by 62: its lanes 0 and 63 repeat the neighbour waves' lanes and only hand their dword to lanes 1 and 62, so no lane fetches a halo dword
+// from memory and a frame's seam may fall anywhere in a wave.
+struct LanePack {
+    int lpr;        // virtual lanes per frame row
+    int halo;       // of these, the last `halo` (0 or 1) produce nothing
+    int G;          // frames per group
+    int step, lead; // a wave advances by `step` virtual lanes and starts `lead` lanes before its first producing one (64, 0 or 62, 1)
+    int waves;      // waves along a group's row
+    unsigned M;     // floor(2^32 / lpr) + 1: v / lpr == (v * M) >> 32 while v * lpr < 2^32
+};
+struct LaneSlot {
+    int frame, col; // frame inside the group, dword column inside the frame's row (col == lpr - 1 with halo: the mirrored dword)
+    bool live;      // the lane maps into the group (frame < G)
+    bool produce;   // ... and stores its column
+    bool first;     // col == 0: the left neighbour lane belongs to another frame
+    bool last;      // col == lpr - 1: the right neighbour lane belongs to another frame
+};
+RUMI_GEOM_HD int lane_pack_waves(int lpr, int G, int step) { return (G * lpr + step - 1) / step; }
+RUMI_GEOM_HD LaneSlot lane_slot(const LanePack &K, int wave, int lane) {
+    const int v = wave * K.step - K.lead + lane;
+    const unsigned vv = v < 0 ? 0u : (unsigned)v;
+    LaneSlot s;
+    s.frame = (int)(((unsigned long long)vv * K.M) >> 32);
+    s.col = (int)vv - s.frame * K.lpr;
+    s.live = v >= 0 && s.frame < K.G;
+    s.produce = s.live && lane >= K.lead && lane < K.lead + K.step && s.col < K.lpr - K.halo;
+    s.first = s.col == 0;
+    s.last = s.col == K.lpr - 1;
+    return s;
+}
+// the lane's frame in a launch of `nframes` frames (group `group` of the launch), -1: beyond the group or the launch's last frame
+RUMI_GEOM_HD int lane_frame(const LanePack &K, const LaneSlot &s, int group, int nframes) {
+    const int f = group * K.G + s.frame;
+    return s.live && f < nframes ? f : -1;
+}
+constexpr int kLanePackMaxG = 8;   // a handful of frames: neighbouring workgroups still share a frame's cache lines
+// Frames per group for a launch of `nframes` frames: the G <= kLanePackMaxG with the fewest issued waves (the partial last group counted; ties
+// go to the smaller G).  `spanBytes`: bytes from a frame to the next (the larger of source and destination, 0: not packable): the kernels add
+// the frame to a 32-bit per-lane offset against the base of the group's first frame, so a group's span must fit.
+inline LanePack lane_pack_choose(int lpr, int halo, int step, int lead, int nframes, int maxG, long long spanBytes) {
+    LanePack K{lpr, halo, 1, step, lead, lane_pack_waves(lpr, 1, step), (unsigned)((1ull << 32) / (unsigned)lpr) + 1u};
+    long long best = (long long)nframes * K.waves;
+    for (int G = 2; G <= std::min(std::min(maxG, kLanePackMaxG), nframes); G++) {
+        if (spanBytes <= 0 || (long long)G * spanBytes >= (1ll << 31)) break;
+        if (((long long)G * lpr + 64) * lpr >= (1ll << 32)) break;
+        const int waves = lane_pack_waves(lpr, G, step);
+        const long long issued = (long long)((nframes + G - 1) / G) * waves;
+        if (issued < best) { best = issued; K.G = G; K.waves = waves; }
+    }
+    return K;
+}
+RUMI_GEOM_HD int resize_lanes_per_row(int w) { return (w + 3) >> 2; }
+RUMI_GEOM_HD int blur_lanes_per_row(int w) { return ((w + 3) >> 2) + 1; }
+constexpr int kPackMinFrames = 16;   // launches of fewer frames keep a launch per frame (G = 1) and the strip blur: they do not fill the device
+inline LanePack resize_pack_of(int w, int nframes, long long spanBytes) {
+    return lane_pack_choose(resize_lanes_per_row(w), 0, 64, 0, nframes, nframes >= kPackMinFrames ? kLanePackMaxG : 1, spanBytes);
+}
+inline LanePack blur_pack_of(int w, int nframes, long long spanBytes) {
+    return lane_pack_choose(blur_lanes_per_row(w), 1, 62, 1, nframes, kLanePackMaxG, spanBytes);
+}
+
 // cv::resize INTER_LINEAR 8UC1 coefficient tables for one axis: ofs[d] and the two 11-bit taps.
 // Horizontal axis (clampX = true): the source index is clamped and the tap zeroed as cv does, and
 // `maxOut` receives xmax (first destination index whose second tap would fall outside the source:

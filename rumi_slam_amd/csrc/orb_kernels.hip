@@ -62,23 +62,28 @@ __device__ __forceinline__ int reflect101(int i, int n) {
 // level 1 straight from the caller's frame.  A lane produces 4 horizontally adjacent pixels of kResizeRows consecutive rows and stores
 // one dword per row: the column tables are loaded once and the 2 x kResizeRows source-row loads are issued back to back.
 // No border pixels are written: the blur mirrors at the edges itself.
+// Frames: blockIdx.z counts GROUPS of K.G consecutive frames whose rows lie side by side along x (LanePack, orb_geom.h); the row state below
+// is the same for every frame, so it stays scalar, and the lane's frame only enters its 32-bit address offsets (the host checks the span).
 // ------------------------------------------------------------------------------------------------
 // (kResizeRows: 4 for the small levels, 8 for levels of 200 rows and more -- launch_resize)
 template <int kResizeRows>
 __global__ __launch_bounds__(256) void k_resize(const DevParams *__restrict__ P, ImgSrc src,
-                                                const int16_t *__restrict__ coef, const RowTap *__restrict__ rowTab, int level, int32_t *__restrict__ clearWord) {
+                                                const int16_t *__restrict__ coef, const RowTap *__restrict__ rowTab, int level, int32_t *__restrict__ clearWord,
+                                                LanePack K, int nframes) {
     if (clearWord && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) *clearWord = 0;    // the call's error word (orb_host.hip)
     const DevLevel &D = P->lv[level];
     const DevLevel &S = P->lv[level - 1];
     const unsigned wg = xcd_swizzle((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, gridDim.x * gridDim.y * gridDim.z);
-    const int bx = wg % gridDim.x, by = (wg / gridDim.x) % gridDim.y, frame = wg / (gridDim.x * gridDim.y);
-    const int ox = (bx * 64 + (threadIdx.x & 63)) * 4;
+    const int bx = wg % gridDim.x, by = (wg / gridDim.x) % gridDim.y, group = wg / (gridDim.x * gridDim.y), frame0 = group * K.G;
+    const LaneSlot slot = lane_slot(K, bx, threadIdx.x & 63);
+    const int ox = slot.col * 4;
     // (the wave index as a scalar: the row table entries, the source-row pointers and the vertical taps then live in scalar registers)
     const int oyBase = (by * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * kResizeRows;
-    if (ox >= D.w || oyBase >= D.h) return;
+    if (lane_frame(K, slot, group, nframes) < 0 || oyBase >= D.h) return;
     int sp;
-    const uint8_t *sb = level_base(src, P, level - 1, frame, &sp);
-    uint8_t *dbase = src.pyr + (long long)frame * P->arenaStride + D.off + ox;
+    const uint8_t *sb = level_base(src, P, level - 1, frame0, &sp);
+    const uint32_t fo = (uint32_t)slot.frame * (uint32_t)(level == 1 ? src.l0FrameStride : P->arenaStride);      // my frame's source, from the group's first
+    uint8_t *dbase = src.pyr + (long long)frame0 * P->arenaStride + D.off + ((uint32_t)slot.frame * (uint32_t)P->arenaStride + (uint32_t)ox);
     const int16_t *xofs = coef + D.coefX, *xa = coef + D.coefXT;
     // per output row: the two source rows and the vertical taps come ready from a host-built table (the clamps are the same for every
     // lane of every frame)
@@ -100,6 +105,7 @@ __global__ __launch_bounds__(256) void k_resize(const DevParams *__restrict__ P,
         // the 4 outputs read source bytes sx0 .. sx0+7 of two rows -> two (unaligned) 8-byte loads per row; offsets and taps
         // come as one 8-byte and one 16-byte table load.  The window never leaves the source row (the last lanes slide it left).
         const int wx0 = min(sx0, S.w - 8);
+        const uint32_t wo = fo + (uint32_t)wx0;
         const uint64_t ofs = reinterpret_cast<const U64 *>(xofs + ox)->v;
         const U64 *t8 = reinterpret_cast<const U64 *>(xa + 2 * ox);
         const uint64_t ta = t8[0].v, tb = t8[1].v;
@@ -109,8 +115,8 @@ __global__ __launch_bounds__(256) void k_resize(const DevParams *__restrict__ P,
 #pragma unroll
         for (int r = 0; r < kResizeRows; r++) {
             s0[r] = 0;
-            if (!shared[r]) s0[r] = reinterpret_cast<const U64 *>(r0p[r] + wx0)->v;
-            s1[r] = reinterpret_cast<const U64 *>(r1p[r] + wx0)->v;
+            if (!shared[r]) s0[r] = reinterpret_cast<const U64 *>(r0p[r] + wo)->v;
+            s1[r] = reinterpret_cast<const U64 *>(r1p[r] + wo)->v;
         }
         // horizontal pass as a 2-element dot product: the two source bytes of an output are adjacent, v_perm_b32 spreads them into
         // 16-bit halves and v_dot2_u32_u16 multiplies by the (non-negative, <= 2048) tap pair as it lies in the table
@@ -156,7 +162,7 @@ __global__ __launch_bounds__(256) void k_resize(const DevParams *__restrict__ P,
             uint32_t packed = 0;
             for (int i = 0; i < 4 && ox + i < D.w; i++) {
                 const int dx = ox + i;
-                const int sx = xofs[dx];
+                const uint32_t sx = fo + (uint32_t)xofs[dx];
                 int q0, q1;
                 if (dx < D.xmax) {
                     const int a0 = xa[dx * 2], a1 = xa[dx * 2 + 1];
@@ -877,6 +883,11 @@ constexpr int kBlurRowsSmall = 16, kBlurRowsBatch = 64;
 
 // all levels in one launch: workgroup `lin` of a frame belongs to the level whose [base, base + gx * gy) range holds it
 struct BlurGrid { int base[kMaxLevels + 1]; int gx[kMaxLevels]; int bw[kMaxLevels]; };   // bw: pixels a wave's strips cover (256, or less: see launch_blur)
+// Batches (kPacked): the rows of G[l] consecutive frames side by side (LanePack, orb_geom.h) in a ONE-dimensional grid, level after level:
+// level l owns the workgroups [base[l], base[l + 1]), group-major, then row block, then the gx[l] waves along the group's row.  The strips
+// and the outer lanes' halo loads above are gone: a wave's lanes 0 and 63 only hold the dwords lanes 1 and 62 need, every seam and edge
+// is a per-lane predicate, and nothing but the lane's address offset knows its frame.
+struct BlurPack { int base[kMaxLevels + 1]; int gx[kMaxLevels], gy[kMaxLevels], G[kMaxLevels]; unsigned M[kMaxLevels]; int nframes; };
 // a * b + c on 24-bit operands as ONE v_mad_u32_u24 (the compiler splits the C expression into a multiply and a 3-input add)
 __device__ __forceinline__ uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c) {
     uint32_t r;
@@ -885,24 +896,42 @@ __device__ __forceinline__ uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c) 
 }
 // VARIANT: RumiOrbConfig.blur_variant -- 0: taps {18,34,48,56,..}/256 of the fixed-point GaussianBlur of OpenCV >= 3.4.2; 1: the integer-scaled float
 // kernel {18,34,49,55,..}/256 of 3.4.0 / 3.4.1 (sum 257: the result is saturated)
-template <int VARIANT, int kBlurRows>
-__device__ __forceinline__ void blur_body(const DevParams *__restrict__ P, const ImgSrc &src, const BlurGrid &G, unsigned bxg, unsigned gxg) {
+template <int VARIANT, int kBlurRows, bool kPacked, typename Grid>
+__device__ __forceinline__ void blur_body(const DevParams *__restrict__ P, const ImgSrc &src, const Grid &G, unsigned bxg, unsigned gxg) {
     constexpr uint32_t kT2 = VARIANT ? 49u : 48u, kT3 = VARIANT ? 55u : 56u;      // taps at distance 1 and 0 (18 and 34 are common)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (scalar: the row walk is scalar arithmetic)
-    const unsigned wg = xcd_swizzle(blockIdx.y * gxg + bxg, gxg * gridDim.y);
-    const int frame = wg / gxg, lin = wg % gxg;
+    const unsigned wg = kPacked ? xcd_swizzle(bxg, gxg) : xcd_swizzle(blockIdx.y * gxg + bxg, gxg * gridDim.y);
+    const int lin = kPacked ? wg : wg % gxg;
+    int frame = kPacked ? 0 : wg / gxg;                          // (packed: the first frame of the wave's group)
     int level = 0;
     for (int l = 1; l < P->nlevels; l++)
         if (lin >= G.base[l]) level = l;
     const DevLevel &L = P->lv[level];
-    const int bx = (lin - G.base[level]) % G.gx[level], by = (lin - G.base[level]) / G.gx[level];
-    const int bw = G.bw[level];
-    const int xa = bx * bw + lane * 4;                           // first pixel of my strip (lanes from bw / 4 on only feed their left neighbour's halo)
+    int bx, by, bw, xa;
+    uint32_t fsrc = 0, fdst = 0;                                 // packed: my frame's byte offset from the group's first frame, source and blurred arena
+    bool produce, first = false;
+    if constexpr (kPacked) {
+        const int per = G.gx[level] * G.gy[level], idx = lin - G.base[level], group = idx / per;
+        bx = (idx - group * per) % G.gx[level]; by = (idx - group * per) / G.gx[level];
+        frame = group * G.G[level];
+        const LanePack K{blur_lanes_per_row(L.w), 1, G.G[level], 62, 1, G.gx[level], G.M[level]};
+        const LaneSlot slot = lane_slot(K, bx, lane);
+        // lanes beyond the group's last frame (or, in the launch's last group, beyond the last frame) walk along on frame 0 of the group and store nothing
+        const bool mine = lane_frame(K, slot, group, G.nframes) >= 0;
+        const uint32_t f = mine ? (uint32_t)slot.frame : 0u;
+        fsrc = f * (uint32_t)(level == 0 ? src.l0FrameStride : P->arenaStride); fdst = f * (uint32_t)P->arenaStride;
+        bw = 256; xa = slot.col * 4;
+        produce = mine && slot.produce; first = slot.first;
+    } else {
+        bx = (lin - G.base[level]) % G.gx[level]; by = (lin - G.base[level]) / G.gx[level];
+        bw = G.bw[level];
+        xa = bx * bw + lane * 4;                                 // first pixel of my strip (lanes from bw / 4 on only feed their left neighbour's halo)
+    }
     const int y0 = (by * 4 + wave) * kBlurRows;
     if (y0 >= L.h) return;                                       // whole wave (wave-uniform)
     int pitch;
     const uint8_t *img = level_base(src, P, level, frame, &pitch);
-    uint8_t *out = src.blur + (long long)frame * P->arenaStride + L.off;
+    uint8_t *out = src.blur + (long long)frame * P->arenaStride + L.off + fdst;
     const int w = L.w, h = L.h;
     // Right edge.  The dword that holds column w - 1 may be partial and the one after it lies wholly beyond the row, yet both feed the
     // halos of the last strips: their missing bytes are the mirrored columns 2 (w - 1) - x, which sit in the same lane or one / two lanes to
@@ -912,8 +941,11 @@ __device__ __forceinline__ void blur_body(const DevParams *__restrict__ P, const
     const int xLast = (w - 1) & ~3;                              // last dword that holds a pixel of the row
     const int xl = min(xa, xLast);
     const bool firstBlock = bx == 0;
-    const bool edgeWave = bx * bw + bw + 4 > w;                  // a dword of this wave (its right halo included) reaches column w or beyond (wave-uniform)
-    const bool produce = lane * 4 < bw && xa < w;
+    // a dword of this wave (its right halo included) reaches column w or beyond (wave-uniform); packed: a frame's right edge may lie anywhere
+    // in the wave, and so may a frame's first dword
+    const bool edgeWave = kPacked ? __builtin_amdgcn_ballot_w64(xa + 3 >= w) != 0 : bx * bw + bw + 4 > w;
+    const bool seamWave = kPacked && __builtin_amdgcn_ballot_w64(first) != 0;
+    if constexpr (!kPacked) produce = lane * 4 < bw && xa < w;
     uint32_t selA = 0x03020100u, selB = 0x07060504u;             // identity: keep my own four bytes
     if (edgeWave && xa + 3 >= w && xa <= xLast + 4) {
 #pragma unroll
@@ -938,7 +970,7 @@ __device__ __forceinline__ void blur_body(const DevParams *__restrict__ P, const
     uint8_t *orow = out + (long long)(y0 - 6) * L.pitch + xa - L.pitch;
     // the halo dword of the wave's outer lanes: lane 0 reads the dword left of its own (but in the first strip block, where it is the mirrored
     // bytes of its own), lane 63 of a 256-pixel wave the one to the right
-    const int haloOff = lane == 0 ? (firstBlock ? 0 : -4) : (lane == 63 && !edgeWave && bw == 256 ? 4 : 0);
+    const int haloOff = kPacked ? 0 : lane == 0 ? (firstBlock ? 0 : -4) : (lane == 63 && !edgeWave && bw == 256 ? 4 : 0);
     // the source rows of the NEXT seven are fetched while the current seven are filtered (a wave's walk is otherwise a chain of
     // load -> filter -> load; rows past the walk's end re-read its last row).  256 frames alone on the device: 260 -> 192 us at 83 registers
     // (5 waves a SIMD); forced to 80 registers / 6 waves (one spill) 217 us, held at 4 waves 207 us, two register sets taking turns 88 registers
@@ -946,10 +978,11 @@ __device__ __forceinline__ void blur_body(const DevParams *__restrict__ P, const
     auto fetch = [&](int r, uint32_t &C, uint32_t &H) {
         const int rc = min(r, rEnd - 1);
         const int rr = rc < 0 ? -rc : (rc >= h ? 2 * (h - 1) - rc : rc);        // rows -3..-1 and h..h+2 mirror into the level
-        const uint8_t *row = img + (long long)rr * pitch + xl;
+        const uint8_t *row = img + (long long)rr * pitch;           // (scalar)
+        if constexpr (kPacked) row += fsrc + (uint32_t)xl; else row += xl;
         C = *reinterpret_cast<const uint32_t *>(row);
         H = 0;
-        if (haloOff) H = *reinterpret_cast<const uint32_t *>(row + haloOff);
+        if (!kPacked && haloOff) H = *reinterpret_cast<const uint32_t *>(row + haloOff);
     };
 #pragma unroll
     for (int j = 0; j < 7; j++) fetch(y0 - 3 + j, Cn[j], Hn[j]);
@@ -966,8 +999,14 @@ __device__ __forceinline__ void blur_body(const DevParams *__restrict__ P, const
                 C = __builtin_amdgcn_perm(C, __builtin_amdgcn_perm(c1, c2, selA), selB);
             }
             uint32_t Lw = __shfl_up(C, 1), Rw = __shfl_down(C, 1);
-            if (lane == 0) Lw = firstBlock ? __builtin_amdgcn_perm(C, C, 0x01020300u) : Hc[j];
-            if (lane == 63 && !edgeWave && bw == 256) Rw = Hc[j];   // (only a 256-pixel wave has a producing lane 63)
+            if constexpr (kPacked) {
+                // no shuffled dword crosses a seam into a producing lane: a frame's first dword mirrors its own bytes, its last producing
+                // dword has the frame's rebuilt halo dword to its right
+                if (seamWave && first) Lw = __builtin_amdgcn_perm(C, C, 0x01020300u);
+            } else {
+                if (lane == 0) Lw = firstBlock ? __builtin_amdgcn_perm(C, C, 0x01020300u) : Hc[j];
+                if (lane == 63 && !edgeWave && bw == 256) Rw = Hc[j];   // (only a 256-pixel wave has a producing lane 63)
+            }
             // row pass on packed bytes: output i needs the 7 bytes S[i+1 .. i+7] of the 12-byte run {Lw, C, Rw}; two byte-dot-products
             // (v_dot4_u32_u8) against the taps {18,34,48,56} and {48,34,18,0} give the exact integer sum (<= 65 280)
             constexpr uint32_t tA = 18u | (34u << 8) | (kT2 << 16) | (kT3 << 24), tB = kT2 | (34u << 8) | (18u << 16);
@@ -1010,7 +1049,11 @@ __device__ __forceinline__ void blur_body(const DevParams *__restrict__ P, const
 }
 template <int VARIANT, int kBlurRows>
 __global__ __launch_bounds__(256) void k_blur(const DevParams *__restrict__ P, ImgSrc src, BlurGrid G) {
-    blur_body<VARIANT, kBlurRows>(P, src, G, blockIdx.x, gridDim.x);
+    blur_body<VARIANT, kBlurRows, false>(P, src, G, blockIdx.x, gridDim.x);
+}
+template <int VARIANT>
+__global__ __launch_bounds__(256) void k_blur_packed(const DevParams *__restrict__ P, ImgSrc src, BlurPack G) {
+    blur_body<VARIANT, kBlurRowsBatch, true>(P, src, G, blockIdx.x, gridDim.x);
 }
 // A few frames (the Tracking thread's call): FAST and the blur in ONE launch, the first gxFast workgroup columns FAST cells, the rest blur strips.
 // Both only read the pyramid; as two launches the blur goes to a side stream, and the event that forks it stalls the main queue for ~20 us on
@@ -1019,7 +1062,7 @@ template <int TPC, int VARIANT>
 __global__ __launch_bounds__(256) void k_fast_blur(const DevParams *__restrict__ P, ImgSrc src, FastLds F, uint32_t *__restrict__ cellBuf,
                                                    int32_t *__restrict__ cellCnt, BlurGrid G, unsigned gxFast) {
     if (blockIdx.x < gxFast) fast_cells_body<TPC>(P, src, F, cellBuf, cellCnt, blockIdx.x, gxFast);
-    else blur_body<VARIANT, kBlurRowsSmall>(P, src, G, blockIdx.x - gxFast, gridDim.x - gxFast);
+    else blur_body<VARIANT, kBlurRowsSmall, false>(P, src, G, blockIdx.x - gxFast, gridDim.x - gxFast);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1315,12 +1358,19 @@ __global__ __launch_bounds__(256, 7) void k_orient_desc(const DevParams *__restr
 }
 
 // ---- launch wrappers (called from orb_host.hip) ----
+// bytes from a frame to the next for the lane packing's 32-bit frame offsets: the arena's, and the caller's frames' where level 0 is read
+// (0: not packable -- a caller's stride that is not positive)
+static long long pack_span(const DevParams &hP, const ImgSrc &src, bool readsLevel0) {
+    if (readsLevel0 && src.l0FrameStride <= 0) return 0;
+    return readsLevel0 ? std::max(hP.arenaStride, src.l0FrameStride) : hP.arenaStride;
+}
 void launch_resize(const DevParams *dP, const DevParams &hP, ImgSrc src, const int16_t *coef, const RowTap *rowTab, int level, int nframes,
                    hipStream_t st, int32_t *clearWord) {
     const int rows = hP.lv[level].h >= 200 ? 8 : 4;
-    dim3 g((hP.lv[level].w + 255) / 256, (hP.lv[level].h + 4 * rows - 1) / (4 * rows), nframes);
-    if (rows == 8) hipLaunchKernelGGL(k_resize<8>, g, dim3(256), 0, st, dP, src, coef, rowTab, level, clearWord);
-    else hipLaunchKernelGGL(k_resize<4>, g, dim3(256), 0, st, dP, src, coef, rowTab, level, clearWord);
+    const LanePack K = resize_pack_of(hP.lv[level].w, nframes, pack_span(hP, src, level == 1));
+    dim3 g(K.waves, (hP.lv[level].h + 4 * rows - 1) / (4 * rows), (nframes + K.G - 1) / K.G);
+    if (rows == 8) hipLaunchKernelGGL(k_resize<8>, g, dim3(256), 0, st, dP, src, coef, rowTab, level, clearWord, K, nframes);
+    else hipLaunchKernelGGL(k_resize<4>, g, dim3(256), 0, st, dP, src, coef, rowTab, level, clearWord, K, nframes);
 }
 void launch_pyramid_tiles(const DevParams *dP, ImgSrc src, const int16_t *coef, const RowTap *rowTab, const PyrTile *tiles, int ntiles, int bufBytes,
                           int tabEntries, int nframes, hipStream_t st, int32_t *clearWord) {
@@ -1407,18 +1457,33 @@ bool launch_fast_blur(const DevParams *dP, const DevParams &hP, ImgSrc src, uint
     else hipLaunchKernelGGL((k_fast_blur<48, 0>), grid, dim3(256), lds, st, dP, src, F, cellBuf, cellCnt, G, gxFast);
     return true;
 }
-void launch_blur(const DevParams *dP, const DevParams &hP, ImgSrc src, int nframes, int variant, hipStream_t st) {
-    const bool small = nframes < 16;
-    const int rows = small ? kBlurRowsSmall : kBlurRowsBatch;
+// the packed grid of a batch (k_blur_packed); the same G for every level would tie the levels' group counts together for no gain
+static BlurPack blur_pack_grid(const DevParams &hP, int nframes, long long span, int *total) {
+    BlurPack G{};
     int run = 0;
-    const BlurGrid G = blur_grid_of(hP, rows, &run);
-    if (small) {
-        if (variant) hipLaunchKernelGGL((k_blur<1, kBlurRowsSmall>), dim3(run, nframes), dim3(256), 0, st, dP, src, G);
-        else hipLaunchKernelGGL((k_blur<0, kBlurRowsSmall>), dim3(run, nframes), dim3(256), 0, st, dP, src, G);
-    } else {
-        if (variant) hipLaunchKernelGGL((k_blur<1, kBlurRowsBatch>), dim3(run, nframes), dim3(256), 0, st, dP, src, G);
-        else hipLaunchKernelGGL((k_blur<0, kBlurRowsBatch>), dim3(run, nframes), dim3(256), 0, st, dP, src, G);
+    for (int l = 0; l < hP.nlevels; l++) {
+        const LanePack K = blur_pack_of(hP.lv[l].w, nframes, span);
+        G.gx[l] = K.waves; G.gy[l] = (hP.lv[l].h + 4 * kBlurRowsBatch - 1) / (4 * kBlurRowsBatch); G.G[l] = K.G; G.M[l] = K.M;
+        G.base[l] = run;
+        run += G.gx[l] * G.gy[l] * ((nframes + K.G - 1) / K.G);
     }
+    G.base[hP.nlevels] = run;
+    G.nframes = nframes;
+    *total = run;
+    return G;
+}
+void launch_blur(const DevParams *dP, const DevParams &hP, ImgSrc src, int nframes, int variant, hipStream_t st) {
+    if (nframes >= kPackMinFrames) {
+        int run = 0;
+        const BlurPack G = blur_pack_grid(hP, nframes, pack_span(hP, src, true), &run);
+        if (variant) hipLaunchKernelGGL((k_blur_packed<1>), dim3(run), dim3(256), 0, st, dP, src, G);
+        else hipLaunchKernelGGL((k_blur_packed<0>), dim3(run), dim3(256), 0, st, dP, src, G);
+        return;
+    }
+    int run = 0;
+    const BlurGrid G = blur_grid_of(hP, kBlurRowsSmall, &run);
+    if (variant) hipLaunchKernelGGL((k_blur<1, kBlurRowsSmall>), dim3(run, nframes), dim3(256), 0, st, dP, src, G);
+    else hipLaunchKernelGGL((k_blur<0, kBlurRowsSmall>), dim3(run, nframes), dim3(256), 0, st, dP, src, G);
 }
 void launch_orient_desc(const DevParams *dP, ImgSrc src, const uint32_t *selPacked, const uint32_t *selMeta,
                         const int32_t *selCount, int selCap, int maxSel, RumiKeyPoint *kpOut, long long kpStride, uint8_t *descOut,

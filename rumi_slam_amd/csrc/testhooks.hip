@@ -54,3 +54,34 @@ extern "C" float rumi_hook_cosf(float x) { return cosf_glibc(x); }
 extern "C" float rumi_hook_fast_atan2(float y, float x) { return fast_atan2_deg(y, x); }
 extern "C" int rumi_hook_cv_round(float v) { return cv_round_f(v); }
 extern "C" int rumi_hook_magic_div(int32_t idx, int32_t d) { return magic_div(idx, magic_of((unsigned)d)); }
+
+// the lane packing of the batch resize / blur launches: the launch code's choice of G and the kernels' lane_slot, evaluated on the host
+extern "C" int rumi_hook_lane_packing(int32_t w, int32_t h, float scale, int32_t nlevels, int32_t nframes, int32_t kernel, int32_t level,
+                                      int32_t force_g, int32_t *info, int32_t *slots, int32_t cap, int32_t *n_out) {
+    if (!info || !n_out || nframes < 1 || nlevels < 1 || nlevels > kMaxLevels || kernel < 0 || kernel > 1 || level < (kernel ? 0 : 1) || level >= nlevels ||
+        force_g < 0 || force_g > nframes)
+        return RUMI_E_INVALID;
+    const OrbTables t = make_tables(1000, scale, nlevels);
+    std::vector<LevelGeom> g;
+    long long arena = 0;
+    int cells, cand, cellCand;
+    if (!make_geometry(t, w, h, g, &arena, &cells, &cand, &cellCand)) return RUMI_E_INVALID;
+    const long long span = std::max(arena, (long long)w * h);
+    LanePack K = kernel ? blur_pack_of(g[level].w, nframes, span) : resize_pack_of(g[level].w, nframes, span);
+    if (force_g) { K.G = force_g; K.waves = lane_pack_waves(K.lpr, K.G, K.step); }
+    const int groups = (nframes + K.G - 1) / K.G;
+    const int32_t inf[8] = {g[level].w, K.lpr, K.G, K.waves, groups, K.step, K.halo, g[level].h};
+    std::copy(inf, inf + 8, info);
+    const long long n = (long long)groups * K.waves * 64;
+    *n_out = (int32_t)std::min<long long>(n, INT32_MAX);
+    if (n > cap || !slots) return RUMI_E_CAPACITY;
+    int32_t *o = slots;
+    for (int grp = 0; grp < groups; grp++)
+        for (int wv = 0; wv < K.waves; wv++)
+            for (int lane = 0; lane < 64; lane++, o += 3) {
+                const LaneSlot s = lane_slot(K, wv, lane);
+                const int f = lane_frame(K, s, grp, nframes);
+                o[0] = f; o[1] = s.col; o[2] = (f >= 0 && s.produce ? 1 : 0) | (s.first ? 2 : 0) | (s.last ? 4 : 0);
+            }
+    return RUMI_OK;
+}
