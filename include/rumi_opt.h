@@ -28,7 +28,23 @@ extern "C" {
 typedef struct RumiOptimizer RumiOptimizer;
 
 /* Scratch arenas: pose problems of up to max_pose_edges correspondences in total per call (all problems of a batch),
- * BA problems of up to max_kf key-frame vertices, max_mp points, max_edges observations. */
+ * BA problems of up to max_kf key-frame vertices, max_mp points, max_edges observations.
+ *
+ * What a handle allocates, in bytes, with PE = max_pose_edges, PB = max_pose_batch, K = max_kf, M = max_mp, E = max_edges and
+ * NP = min(6 K + 1 rounded up to 16, 256), the padded width of the dense Schur panel:
+ *   device, at creation
+ *     34 PE + 64 PB                    pose optimisation: transfer blocks, active flags, last chi2
+ *     377 E                            per observation: H_pl 144, pose panel rows 128, chi2 8, level flag 1, two transfer blocks of 48 each
+ *     (352 + 24 NP) M                  per point: H_ll, D^-1, L, b_l, two states, update, two transfer blocks; 24 NP M is the panel Y
+ *                                      (6 KiB a point once NP = 256: from K = 40 on)
+ *     768 K + 8 (6 K + 2)^2 + 8 NP^2   per key-frame: states, H_pp, b_p, update; the dense reduced system of the large-window path and of
+ *                                      the essential graph (85 MB at K = 544); the Gram matrix of the panel
+ *   pinned host memory, at creation    48 E + 32 M + 80 K (one transfer block) and 25 PE + 64 PB
+ *   device, on first use and kept      large-window BA: 148 E and the co-observation pair lists of the largest window seen;
+ *                                      window-batched local BA (rumi_local_ba, rumi_local_ba_batch): 26 MB of Gram partials whatever the sizes,
+ *                                      about 33 E + 16 M for the sorted graph; essential graph: its own matrix and one block, by problem size
+ * rumi_local_ba_batch creates child handles with the parent's K, M, E and PE (PB = 1) on first use and keeps them: one per window of a
+ * launch group and three runners, up to 35. */
 int rumi_opt_create(int32_t max_pose_edges, int32_t max_pose_batch, int32_t max_kf, int32_t max_mp, int32_t max_edges,
                     int32_t device, RumiOptimizer **out);
 void rumi_opt_destroy(RumiOptimizer *o);

@@ -50,7 +50,7 @@ static int baw_arena_extras(RumiOptimizer *c) {
     return RUMI_OK;
 }
 
-// Stages window `a` into arena `c` on stream `st` and fills its descriptor.  The two host passes over the edges are ba_run's.
+// Stages window `a` into arena `c` on stream `st` and fills its descriptor (the structure is derived on the device: k_baws_*).
 static int baw_stage(RumiOptimizer *c, hipStream_t st, int mode, const BawArgs &a, int gbaRobust, BAWin &Wd, BawPrep &P, int slicesWanted) {
     const int nKF = a.nKF, nMP = a.nMP, nE = a.nE;
     if (nKF > c->maxKF || nMP > c->maxMP || nE > c->maxE) { g_lastError = "local BA: problem larger than the optimiser's arenas"; return RUMI_E_CAPACITY; }
@@ -58,20 +58,14 @@ static int baw_stage(RumiOptimizer *c, hipStream_t st, int mode, const BawArgs &
     int nOpt = 0;
     for (int k = 0; k < nKF; k++) nOpt += a.kf_fixed[k] ? 0 : 1;
     const int n = 6 * nOpt;
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
     // ONE pinned block up: the caller's arrays as they came (the structure -- g2o's buildStructure -- is derived on the device, k_baws_*), the
     // initial poses as doubles, the column blocks
-    const size_t oT = 0, oX = al(oT + (size_t)nKF * 64), oPC = al(oX + (size_t)nMP * 12), oEM = al(oPC + (size_t)nKF * 4), oEK = al(oEM + (size_t)nE * 4),
-                 oOb = al(oEK + (size_t)nE * 4), oIn = al(oOb + (size_t)nE * 8), upBytes = al(oIn + (size_t)nE * 4);
+    const size_t oT = 0, oX = al16(oT + (size_t)nKF * 64), oPC = al16(oX + (size_t)nMP * 12), oEM = al16(oPC + (size_t)nKF * 4), oEK = al16(oEM + (size_t)nE * 4),
+                 oOb = al16(oEK + (size_t)nE * 4), oIn = al16(oOb + (size_t)nE * 8), upBytes = al16(oIn + (size_t)nE * 4);
     if (upBytes > c->baStageCap) { g_lastError = "local BA: upload block larger than the optimiser's arenas"; return RUMI_E_CAPACITY; }
     uint8_t *hs = c->hBa;
+    ba_stage_poses(nKF, a.kf_pose7, reinterpret_cast<double *>(hs + oT));
     {
-        double *T0 = reinterpret_cast<double *>(hs + oT);
-        for (int k = 0; k < nKF; k++) {
-            const DSE3 Q = se3_from_float7(a.kf_pose7 + (size_t)k * 7);
-            double *t = T0 + (size_t)k * 8;
-            t[0] = Q.r.x; t[1] = Q.r.y; t[2] = Q.r.z; t[3] = Q.r.w; t[4] = Q.t.x; t[5] = Q.t.y; t[6] = Q.t.z; t[7] = 0;
-        }
         int32_t *poseCol = reinterpret_cast<int32_t *>(hs + oPC);
         int cc = 0;
         for (int k = 0; k < nKF; k++) poseCol[k] = a.kf_fixed[k] ? -1 : cc++;
@@ -89,7 +83,7 @@ static int baw_stage(RumiOptimizer *c, hipStream_t st, int mode, const BawArgs &
     Wd.nUpd = (nMP * kLmLanes + 255) / 256;
     Wd.robust = mode == 2 ? (gbaRobust ? 1 : 0) : 1;
     Wd.useLast = 1;
-    Wd.delta = mode == 0 ? (double)(float)std::sqrt(5.991) : (double)(float)std::sqrt(5.99);   // thHuberMono = sqrt(5.991) / thHuber2D = sqrt(5.99)
+    Wd.delta = ba_huber_delta(mode);
     Wd.dsqr = Wd.delta * Wd.delta;
     Wd.cam = DCam{a.K4[0], a.K4[1], a.K4[2], a.K4[3]};
     Wd.poseCol = (const int32_t *)(c->dBa + oPC); Wd.rawMP = (const int32_t *)(c->dBa + oEM); Wd.rawKF = (const int32_t *)(c->dBa + oEK);
@@ -116,7 +110,7 @@ static int baw_stage(RumiOptimizer *c, hipStream_t st, int mode, const BawArgs &
     Wd.stopSeen = reinterpret_cast<int32_t *>(c->dWinSmall + 16);
     Wd.lm = c->dLmCtl; Wd.mirror = c->dhWm; Wd.stopWord = c->dhStop;
     P.arena = c; P.nOpt = nOpt; P.n = n; P.NP = NP; P.NT = NT;
-    P.rT = 0; P.rX = al(P.rT + (size_t)nKF * 64); P.rE = al(P.rX + (size_t)nMP * 24); P.rErr = al(P.rE + (size_t)nE); P.dnBytes = al(P.rErr + 16);
+    P.rT = 0; P.rX = al16(P.rT + (size_t)nKF * 64); P.rE = al16(P.rX + (size_t)nMP * 24); P.rErr = al16(P.rE + (size_t)nE); P.dnBytes = al16(P.rErr + 16);
     Wd.outT = reinterpret_cast<double *>(c->dBaOut + P.rT); Wd.outX = reinterpret_cast<double *>(c->dBaOut + P.rX); Wd.erase = c->dBaOut + P.rE;
     Wd.errOut = reinterpret_cast<int32_t *>(c->dBaOut + P.rErr);
     return RUMI_OK;
@@ -146,7 +140,6 @@ struct BawGroup {
     bool anyRun = false;
     double tStage = 0, tLm0 = 0, tLm1 = 0;
 
-    static double now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
     hipStream_t st() const { return run->stream; }
     BAWin *tab() const { return run->hWinTab; }
 
@@ -157,24 +150,21 @@ struct BawGroup {
             if (hipHostMalloc((void **)&o->hWinTab, sizeof(BAWin) * kBawMaxWindows, hipHostMallocDefault) != hipSuccess ||
                 hipMalloc((void **)&o->dWinTab, sizeof(BAWin) * kBawMaxWindows) != hipSuccess) return RUMI_E_NO_DEVICE;
         }
-        const double tA = now();
+        const double tA = ba_now_us();
         prep.assign((size_t)nW, BawPrep{});
         static const int envSlices = std::getenv("RUMI_BAW_SLICES") ? std::atoi(std::getenv("RUMI_BAW_SLICES")) : 0;
         const int slicesWanted = envSlices > 0 ? envSlices : std::max(8, std::min(kBawMaxSlices, 512 / std::max(nW, 1)));
         for (int i = 0; i < nW; i++) {
             const BawArgs &a = args[i];
             status[i] = RUMI_OK;
-            if (a.stats) a.stats[0] = a.stats[1] = a.stats[2] = a.stats[3] = 0;
-            int nFixed = 0;
-            for (int k = 0; k < a.nKF; k++) nFixed += a.kf_fixed[k] ? 1 : 0;
-            if (nFixed == 0 && mode == 0) { g_lastError = "LM-LBA: There are 0 fixed KF in the optimizations, LBA aborted"; status[i] = worst = RUMI_E_INVALID; continue; }   // Optimizer.cc:1057-1060
-            if (mode != 2 && a.stop_flag && *a.stop_flag) { if (a.stats) a.stats[3] = 1; continue; }                                         // :1274-1276 / :3982-3984
+            int rcExit;
+            if (ba_early_exit(mode, a.nKF, a.kf_fixed, a.stop_flag, a.stats, &rcExit)) { if (rcExit != RUMI_OK) status[i] = worst = rcExit; continue; }
             const int rc = baw_stage(arenas[i], st(), mode, a, gbaRobust, tab()[live.size()], prep[i], slicesWanted);
             if (rc != RUMI_OK) { status[i] = worst = rc; continue; }
             live.push_back(i);
         }
         L = (int)live.size();
-        tStage = now() - tA;
+        tStage = ba_now_us() - tA;
         if (L == 0) { phase = kDone; return RUMI_OK; }
         HIP_TRY(hipEventRecord(o->ev[0], st()));
         int maxE = 1, maxMP = 1, maxBlk = 1;
@@ -205,7 +195,7 @@ struct BawGroup {
         hipLaunchKernelGGL(k_baws_kfscan, dim3(L), dim3(1024), 0, st(), dTab);
         hipLaunchKernelGGL(k_baws_rowslot, dim3(maxBlk, L), dim3(256), 0, st(), dTab);
         HIP_TRY(hipGetLastError());
-        tLm0 = now();
+        tLm0 = ba_now_us();
         const int firstIt = mode == 0 ? 10 : mode == 1 ? 5 : gbaIterations;     // (mode 2 with the stop flag already up or no iteration goes the single-window path, ba_run)
         return start_pass(firstIt);
     }
@@ -298,7 +288,7 @@ struct BawGroup {
     }
     int finish_enqueue() {                 // results: [T | X | erase | err] per window, gathered by one launch, one copy each
         RumiOptimizer *o = run;
-        tLm1 = now();
+        tLm1 = ba_now_us();
         // every window's block [T | X | erase | err] into ONE buffer of the group: one copy back instead of one per window
         size_t total = 0;
         for (int j = 0; j < L; j++) { prep[live[j]].outOff = total; total += (prep[live[j]].dnBytes + 255) & ~(size_t)255; }
@@ -330,30 +320,24 @@ struct BawGroup {
         RumiOptimizer *o = run;
         HIP_TRY(hipStreamSynchronize(st()));
         HIP_TRY(hipEventElapsedTime(&o->stageMs[5], o->ev[0], o->ev[1]));
-        const double tD = now();
+        const double tD = ba_now_us();
         for (int j = 0; j < L; j++) {
             const int i = live[j];
             const BawArgs &a = args[i];
             const BawPrep &P = prep[i];
             const uint8_t *hb = o->hGroupOut + P.outOff;
-            const double *T1 = reinterpret_cast<const double *>(hb + P.rT), *X1 = reinterpret_cast<const double *>(hb + P.rX);
             const int32_t err = *reinterpret_cast<const int32_t *>(hb + P.rErr);
             if (err) {                                      // nothing of this window is written back
                 g_lastError = (err & 1) ? "local BA: edge index out of range" : "local BA: a map point is observed twice by one key-frame";
                 status[i] = worst = RUMI_E_INVALID;
                 continue;
             }
-            if (a.nE > 0) std::memcpy(a.erase_out, hb + P.rE, (size_t)a.nE);
-            for (int k = 0; k < a.nKF; k++) {
-                if (a.kf_fixed[k]) continue;
-                const double *t = T1 + (size_t)k * 8;
-                se3_to_float7(DSE3{{t[0], t[1], t[2], t[3]}, {t[4], t[5], t[6]}}, a.kf_pose7 + (size_t)k * 7);
-            }
-            for (size_t q = 0; q < (size_t)a.nMP * 3; q++) a.mp_pos3[q] = (float)X1[q];
-            if (a.stats) { a.stats[0] = mode == 1 ? P.itersFirst : P.iters; a.stats[1] = P.trials; a.stats[2] = P.nOpt; a.stats[3] = mode == 1 ? P.iters - P.itersFirst : 0; }
+            ba_unpack(a.nKF, a.kf_fixed, a.nMP, a.nE, reinterpret_cast<const double *>(hb + P.rT), reinterpret_cast<const double *>(hb + P.rX), hb + P.rE,
+                      a.kf_pose7, a.mp_pos3, a.erase_out);
+            ba_write_stats(mode, P.iters, P.itersFirst, P.trials, P.nOpt, a.stats);
         }
         static const bool hostDbg = std::getenv("RUMI_HOSTDBG") != nullptr;
-        if (hostDbg) fprintf(stderr, "baw host us (%d windows): staging %.1f lm %.1f finalize+copy %.1f unpack %.1f\n", L, tStage, tLm1 - tLm0, tD - tLm1, now() - tD);
+        if (hostDbg) fprintf(stderr, "baw host us (%d windows): staging %.1f lm %.1f finalize+copy %.1f unpack %.1f\n", L, tStage, tLm1 - tLm0, tD - tLm1, ba_now_us() - tD);
         phase = kDone;
         return RUMI_OK;
     }

@@ -60,7 +60,10 @@ def test_pose_optimization_batch(opt):
                                  dict(seed=11, n_opt=8, n_fixed=2, n_points=400), dict(seed=12, n_opt=16, n_fixed=2, n_points=600),
                                  dict(seed=13, n_opt=24, n_fixed=3, n_points=700), dict(seed=14, n_opt=3, n_fixed=2, n_points=300),
                                  dict(seed=15, n_opt=27, n_fixed=2, n_points=700), dict(seed=16, n_opt=29, n_fixed=2, n_points=700),
-                                 dict(seed=17, n_opt=30, n_fixed=2, n_points=700)])
+                                 dict(seed=17, n_opt=30, n_fixed=2, n_points=700),
+                                 # the last window the one-workgroup panel solver takes (252 unknowns: all four unknowns per lane of its backward
+                                 # substitution in use) and the first window of the large path (258 unknowns: a partial last panel of 64)
+                                 dict(seed=18, n_opt=42, n_fixed=2, n_points=600), dict(seed=19, n_opt=43, n_fixed=2, n_points=600)])
 def test_local_bundle_adjustment(opt, cfg):
     b = ba_problem(**cfg)
     t0 = time.time()
