@@ -1,4 +1,5 @@
-// Device helpers the matcher kernels (match.hip), the Tracking step (track.hip) and the mapping kernels (mapping.hip) share.
+// Device helpers the matcher kernels (match.hip and its match_*.inc parts: queries, candidates, resolve, tri, bow_batch), the Tracking step (track.hip)
+// and the mapping kernels (mapping.hip) share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -1,10 +1,12 @@
-// The matcher's host side as the other translation units of librumi_hip.so drive it (track.hip, mapping.hip): the handle, the upload queue,
-// the candidate-list / resolve pipeline and host launchers of the matcher kernels they need.  Definitions: match.hip.  Not part of the C ABI.
+// The matcher's host side as the other translation units of librumi_hip.so drive it (track.hip, mapping.hip): the handle, the upload queue and
+// the stagers that fill it, the candidate-list / resolve pipeline and host launchers of the matcher kernels they need.  Definitions: match.hip
+// (handle, queue, launchers) and match_search.inc (build_lists, run_search), which match.hip includes.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 
 #include "rumi_internal.h"
 #include "rumi_common.h"
@@ -72,7 +74,7 @@ struct RumiMatcher {
     int32_t *dOut = nullptr, *hOut = nullptr;
     int32_t *dNmatches = nullptr, *dOverflow = nullptr, *dFeatMp = nullptr, *dAssign = nullptr;     // views into dOut
     // raw inputs of the query builders
-    uint8_t *dU8a = nullptr, *dU8b = nullptr; float *dF[6] = {nullptr}; int32_t *dI[4] = {nullptr};
+    uint8_t *dU8a = nullptr, *dU8b = nullptr; float *dF[4] = {nullptr}; int32_t *dI[2] = {nullptr};
     RumiKeyPoint *dQKeys = nullptr; uint32_t *dNodesA = nullptr, *dNodesB = nullptr, *dIdxA = nullptr;
     int32_t *dOffA = nullptr, *dOffB = nullptr;
     float *dPose = nullptr;
@@ -112,9 +114,67 @@ int build_lists(RumiMatcher *m, int mode, int nq, const FrameDev &fd, const uint
 // candidate lists, then the fix-point resolve; brings the results to the host (and synchronises the null stream)
 int run_search(RumiMatcher *m, int mode, int nq, const FrameDev &fd, const uint8_t *dQueryDesc, const int32_t *dMpObs, float nnratio, int checkOri,
                int32_t *hostFeatMp, int32_t *nmatchesOut, const uint8_t *dBlocked0 = nullptr, float thrF = 0.f, int thrI = 0, int32_t *hostAssign = nullptr);
-// (`m` is the matcher in scope; both return from the calling function on failure)
-#define H2D(dst, src, n) do { const int rcS_ = rumi::stage_add(m, (dst), (src), (size_t)(n) * sizeof(*(dst))); if (rcS_ != RUMI_OK) return rcS_; } while (0)
-#define FLUSH(m) do { const int rcF_ = rumi::flush_uploads(m); if (rcF_ != RUMI_OK) return rcF_; } while (0)
+// (`m` is the matcher in scope; all three return from the calling function on failure)
+#define RC_TRY(call) do { const int rcT_ = (call); if (rcT_ != RUMI_OK) return rcT_; } while (0)
+#define H2D(dst, src, n) RC_TRY(rumi::stage_add(m, (dst), (src), (size_t)(n) * sizeof(*(dst))))
+#define FLUSH(m) RC_TRY(rumi::flush_uploads(m))
+
+// ---- stagers: these only queue into the matcher's upload block; the order of the segments fixes the offsets inside the staged block ----
+// The three pose packs of the query builders and the frustum test, into dPose.
+inline int stage_pose(RumiMatcher *m, const float *Tcw7, const float *K4) {                                       // Tcw7 | K4
+    float pose[11];
+    std::memcpy(pose, Tcw7, 28); std::memcpy(pose + 7, K4, 16);
+    H2D(m->dPose, pose, 11);
+    return RUMI_OK;
+}
+inline int stage_pose_ow(RumiMatcher *m, const float *Tcw7, const float *K4, const float *Ow3) {                  // Tcw7 | K4 | Ow3
+    float pose[14];
+    std::memcpy(pose, Tcw7, 28); std::memcpy(pose + 7, K4, 16); std::memcpy(pose + 11, Ow3, 12);
+    H2D(m->dPose, pose, 14);
+    return RUMI_OK;
+}
+inline int stage_pose_matrices(RumiMatcher *m, const float *Rcw9, const float *tcw3, const float *Ow3, const float *K4) {   // Rcw9 | tcw3 | Ow3 | K4
+    float pose[19];
+    std::memcpy(pose, Rcw9, 36); std::memcpy(pose + 9, tcw3, 12); std::memcpy(pose + 12, Ow3, 12); std::memcpy(pose + 15, K4, 16);
+    H2D(m->dPose, pose, 19);
+    return RUMI_OK;
+}
+// the last frame of k_queries_frame
+inline int stage_last_frame(RumiMatcher *m, const RumiKeyPoint *last_keys_un, int nlast, const int32_t *last_mp, const uint8_t *last_outlier) {
+    if (nlast > 0) { H2D(m->dQKeys, last_keys_un, nlast); H2D(m->dI[0], last_mp, nlast); H2D(m->dU8a, last_outlier, nlast); }
+    return RUMI_OK;
+}
+// The key-frame on the query side of the FeatureVector searches (k_queries_bow, k_tri_match): its features, then (behind whatever the entry queues in
+// between) its FeatureVector in CSR form; and the FeatureVector of the frame side.  nEntries = offsets[n_nodes], 0 without nodes.
+inline int stage_query_keyframe(RumiMatcher *m, const RumiFrameFeatures *KF, const int32_t *kf_mp) {
+    if (KF->n > 0) { H2D(m->dQKeys, KF->keys_un, KF->n); H2D(m->dQDesc, KF->desc, (size_t)KF->n * 32); H2D(m->dI[0], kf_mp, KF->n); }
+    return RUMI_OK;
+}
+inline int stage_fv(RumiMatcher *m, const RumiFeatureVector *fv, int nEntries, uint32_t *dNodes, int32_t *dOff, uint32_t *dIdx) {
+    if (fv->n_nodes > 0) { H2D(dNodes, fv->node_ids, fv->n_nodes); H2D(dOff, fv->offsets, fv->n_nodes + 1); }
+    if (nEntries > 0) H2D(dIdx, fv->indices, nEntries);
+    return RUMI_OK;
+}
+inline int stage_fv_query(RumiMatcher *m, const RumiFeatureVector *fv, int nEntries) { return stage_fv(m, fv, nEntries, m->dNodesA, m->dOffA, m->dIdxA); }
+inline int stage_fv_frame(RumiMatcher *m, const RumiFeatureVector *fv, int nEntries) { return stage_fv(m, fv, nEntries, m->dNodesB, m->dOffB, m->dFvIdx); }
+
+// The result block of the frustum test for nmp points, as k_is_in_frustum and k_track_frustum write it into dStage (its uploads have been scattered
+// by then) and as one copy brings it to hStage: [inView u8 | X | Y | cos | depth f32 | level i32], every array n16 = nmp rounded up to 16 entries
+// long, 21 bytes a point.
+struct FrustumBlock {
+    size_t n16, bytes;
+    uint8_t *inView; float *x, *y, *viewCos, *depth; int32_t *level;
+    FrustumBlock(uint8_t *base, int nmp)
+        : n16(((size_t)nmp + 15) & ~(size_t)15), bytes(n16 * 21), inView(base), x(reinterpret_cast<float *>(base + n16)), y(reinterpret_cast<float *>(base + n16 * 5)),
+          viewCos(reinterpret_cast<float *>(base + n16 * 9)), depth(reinterpret_cast<float *>(base + n16 * 13)), level(reinterpret_cast<int32_t *>(base + n16 * 17)) {}
+    // a host copy into the caller's arrays
+    void unpack(int nmp, uint8_t *inViewOut, float *xOut, float *yOut, int32_t *levelOut, float *cosOut, float *depthOut) const {
+        std::memcpy(inViewOut, inView, (size_t)nmp);
+        std::memcpy(xOut, x, (size_t)nmp * 4); std::memcpy(yOut, y, (size_t)nmp * 4); std::memcpy(cosOut, viewCos, (size_t)nmp * 4);
+        std::memcpy(depthOut, depth, (size_t)nmp * 4); std::memcpy(levelOut, level, (size_t)nmp * 4);
+    }
+};
+inline bool frustum_fits(const RumiMatcher *m, int nmp) { return FrustumBlock(m->dStage, nmp).bytes <= m->stageCap; }
 
 // The two environment switches of the search pipeline, read once per process.  fused: every query's list in a fixed slot (RUMI_MATCH_NO_FUSED set:
 // count / scan / fill).  speculate: the Tracking entries queue a whole step without reading a count back (RUMI_TRACK_SPECULATE=0 or not fused: no).

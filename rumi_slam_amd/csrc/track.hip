@@ -2,7 +2,8 @@
 // map-point vector (mvpMapPoints = dFeatMp) and the pose optimiser's correspondence arrays never leave HBM between the five stages.  A dispatch
 // costs about 4.5 us on the device whatever it does, so the step is built from as few as the data flow allows: no device-to-device copies (the
 // matcher reads the extractor's record in place, results are produced inside the block that travels back), fills and bookkeeping folded into
-// neighbouring kernels.  The matcher is driven through match_host.h; its kernels are launched by match.hip's launchers.
+// neighbouring kernels.  The matcher is driven through match_host.h (upload queue and stagers, the frustum result block, run_search); its kernels are
+// launched by match.hip's launchers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -288,7 +289,7 @@ struct RumiTracker {
     int32_t *dIdx = nullptr;
     uint8_t *dOutC = nullptr, *dActive = nullptr, *dSeen = nullptr, *dBad = nullptr, *dLocal = nullptr, *dStaleIn = nullptr;
     float *dStaleProj = nullptr;
-    size_t projN16 = 0; int projN = 0;       // the projection arrays the last SearchLocalPoints left in the matcher's staging block (rumi_track_last_projections)
+    int projN = 0;                           // the projection arrays the last SearchLocalPoints left in the matcher's staging block (rumi_track_last_projections)
     double *dChi = nullptr;
     float scale[64] = {0};
     // the step-wise entries (rumi_track_extract / _motion / _reference_keyframe / _local): the frame that is resident, and its BoW transform
@@ -369,7 +370,6 @@ enum TrackTail { TAIL_AFTER_MOTION, TAIL_DISCARD, TAIL_FINISH };       // the ke
 int grid_of(int n) { return std::max(1, (n + 255) / 256); }
 int grid_items(int n, int nmp) { return grid_of(std::max(std::max(n, nmp), 4)); }     // features, table points and the 4-word result header
 bool has_stale(const RumiTrackPoints *pts) { return pts->stale_in_view && pts->stale_proj; }
-bool frustum_fits(const RumiMatcher *m, int nmp) { return (((size_t)nmp + 15) & ~(size_t)15) * 21 <= m->stageCap; }
 const RumiKeyPoint *resident_keys(const RumiTracker *t) {               // mvKeysUn: what every stage reads
     return t->distort ? t->dKeysUn : reinterpret_cast<const RumiKeyPoint *>(t->d.record + 8);
 }
@@ -432,13 +432,8 @@ int track_check_points(const RumiTrackPoints *pts, bool needFrustum) {
     return RUMI_OK;
 }
 
-// These three only queue into the matcher's upload block; the order of the segments fixes the offsets inside the staged block.
-int stage_pose(RumiMatcher *m, const float *Tcw7, const float *K4) {
-    float pose[11];
-    std::memcpy(pose, Tcw7, 7 * sizeof(float)); std::memcpy(pose + 7, K4, 4 * sizeof(float));
-    H2D(m->dPose, pose, 11);
-    return RUMI_OK;
-}
+// The point table into the matcher's upload block (like match_host.h's stagers it only queues; the order of the segments fixes the offsets
+// inside the staged block)
 int stage_points(RumiTracker *t, const RumiTrackPoints *pts, bool withFrustumFields) {
     RumiMatcher *m = t->m;
     const int nmp = pts->n;
@@ -450,10 +445,6 @@ int stage_points(RumiTracker *t, const RumiTrackPoints *pts, bool withFrustumFie
         H2D(t->dBad, pts->bad, nmp); H2D(t->dLocal, pts->local, nmp);
         if (has_stale(pts)) { H2D(t->dStaleIn, pts->stale_in_view, nmp); H2D(t->dStaleProj, pts->stale_proj, (size_t)nmp * 5); }
     }
-    return RUMI_OK;
-}
-int stage_last_frame(RumiMatcher *m, const RumiKeyPoint *last_keys_un, int nlast, const int32_t *last_mp, const uint8_t *last_outlier) {
-    if (nlast > 0) { H2D(m->dQKeys, last_keys_un, nlast); H2D(m->dI[0], last_mp, nlast); H2D(m->dU8a, last_outlier, nlast); }
     return RUMI_OK;
 }
 
@@ -504,16 +495,14 @@ int local_search(RumiTracker *t, const FrameDev &fd, int nmp, int32_t *hostMp, R
 int launch_frustum(RumiTracker *t, const FrameDev &fd, const RumiTrackPoints *pts, int n, float th_local, int far_points, float th_far_points, const char *entry) {
     RumiMatcher *m = t->m;
     const int nmp = pts->n;
-    const size_t n16 = ((size_t)nmp + 15) & ~(size_t)15;
     if (!frustum_fits(m, nmp)) { g_lastError = std::string(entry) + ": point table exceeds the staging block"; return RUMI_E_CAPACITY; }
-    float *dX = reinterpret_cast<float *>(m->dStage + n16), *dY = dX + n16, *dC = dY + n16, *dD = dC + n16;
-    int32_t *dL = reinterpret_cast<int32_t *>(dD + n16);
+    const FrustumBlock fb(m->dStage, nmp);                  // (its flag array stays unused: mbTrackInView goes into the tracker's block)
     const FrustumArgs FA{nmp, n, m->dFeatMp, t->d.mpMotion, t->dLocal, t->dSeen, t->dBad, /*skip*/ m->dU8b, m->dOut, t->d.blk->pose19, fd.minX,
-                         fd.minY, fd.maxX, fd.maxY, std::log(t->cfg.scale_factor), t->nlevels, 0.5f, m->dF[0], m->dF[1], m->dF[2], m->dF[3], t->d.view, dX, dY, dL, dC, dD,
+                         fd.minY, fd.maxX, fd.maxY, std::log(t->cfg.scale_factor), t->nlevels, 0.5f, m->dF[0], m->dF[1], m->dF[2], m->dF[3], t->d.view, fb.x, fb.y, fb.level, fb.viewCos, fb.depth,
                          m->dI[1], m->dScale, th_local, far_points, th_far_points, m->dQ,
                          has_stale(pts) ? t->dStaleIn : nullptr, has_stale(pts) ? t->dStaleProj : nullptr};
     hipLaunchKernelGGL(k_track_frustum, dim3(grid_items(n, nmp)), dim3(256), 0, nullptr, FA);
-    t->projN16 = n16; t->projN = nmp;
+    t->projN = nmp;
     return RUMI_OK;
 }
 
@@ -818,10 +807,9 @@ extern "C" int rumi_track_reference_keyframe(RumiTracker *t, RumiVocabulary *voc
     // ---- SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:198-370): the key-frame side comes from the host, the frame side is resident
     FrameDev fd;
     if ((rc = track_frame_dev(t, &fd)) != RUMI_OK || (rc = stage_pose(m, Tcw_init7, K4)) != RUMI_OK) return rc;
-    if (KF->n > 0) { H2D(m->dQKeys, KF->keys_un, KF->n); H2D(m->dQDesc, KF->desc, (size_t)KF->n * 32); H2D(m->dI[0], kf_mp, KF->n); }
+    if ((rc = stage_query_keyframe(m, KF, kf_mp)) != RUMI_OK) return rc;
     if (nmp > 0) { H2D(m->dU8a, pts->bad, nmp); H2D(m->dF[0], pts->pos, (size_t)nmp * 3); H2D(m->dI[1], pts->obs, nmp); }
-    if (kf_fv->n_nodes > 0) { H2D(m->dNodesA, kf_fv->node_ids, kf_fv->n_nodes); H2D(m->dOffA, kf_fv->offsets, kf_fv->n_nodes + 1); }
-    if (nqe > 0) H2D(m->dIdxA, kf_fv->indices, nqe);
+    if ((rc = stage_fv_query(m, kf_fv, nqe)) != RUMI_OK) return rc;
     m->gridPending = false;                                 // candidates come from the FeatureVectors: the spatial grid is not read
     FLUSH(m);
     track_init(t, n, nmp, 1, nullptr);
@@ -917,12 +905,9 @@ extern "C" int rumi_track_last_projections(RumiTracker *t, int32_t n_points, flo
     if (t->projN <= 0 || n_points != t->projN) { g_lastError = "rumi_track_last_projections: no SearchLocalPoints result of that size is resident"; return RUMI_E_INVALID; }
     HIP_TRY(hipSetDevice(t->device));
     RumiMatcher *m = t->m;
-    const size_t n16 = t->projN16;
-    std::vector<float> h(5 * n16);
-    HIP_TRY(hipMemcpy(h.data(), m->dStage + n16, 5 * n16 * sizeof(float), hipMemcpyDeviceToHost));
-    const float *X = h.data(), *Y = X + n16, *Cc = Y + n16, *D = Cc + n16;
-    const int32_t *L = reinterpret_cast<const int32_t *>(D + n16);
-    for (int i = 0; i < n_points; i++) { float *o = proj5_out + (size_t)i * 5; o[0] = X[i]; o[1] = Y[i]; o[2] = (float)L[i]; o[3] = Cc[i]; o[4] = D[i]; }
+    const FrustumBlock fb(m->dStage, n_points), h(m->hStage, n_points);
+    HIP_TRY(hipMemcpy(h.x, fb.x, 5 * fb.n16 * sizeof(float), hipMemcpyDeviceToHost));        // the five word arrays; the flags are not wanted
+    for (int i = 0; i < n_points; i++) { float *o = proj5_out + (size_t)i * 5; o[0] = h.x[i]; o[1] = h.y[i]; o[2] = (float)h.level[i]; o[3] = h.viewCos[i]; o[4] = h.depth[i]; }
     return RUMI_OK;
 }
 

@@ -373,6 +373,40 @@ def test_search_for_initialization(matcher, seed, ratio, ori, window):
     assert n_gpu2 == n_ref2 and np.array_equal(m12b, m_ref2) and np.array_equal(pmb, pm_ref2)
 
 
+def test_search_for_initialization_grows_the_arena():
+    """The initialisation entry's own grow-and-retry: 64 queries whose windows each hold all 1500 key-points of F2 list 96000 candidates, more than
+    the 64 * 256 + 65536 = 81920 entries a matcher of 64 queries starts with.  The second call runs in the grown arena."""
+    from rumi_slam_amd.matcher import FrameView, ORBmatcher
+    rng = np.random.default_rng(77)
+    sf = np.float32(1.2) ** np.arange(8, dtype=np.float32)
+    n1, n2, window, ratio = 64, 1500, 100, 0.9
+    keys2, desc2 = _random_frame(rng, n2)
+    keys2["x"], keys2["y"] = 320 + rng.normal(0, 5, n2), 240 + rng.normal(0, 5, n2)
+    keys2["octave"] = 0
+    keys1, desc1 = _random_frame(rng, n1)
+    keys1["x"], keys1["y"] = 320 + rng.normal(0, 5, n1), 240 + rng.normal(0, 5, n1)
+    keys1["octave"] = 0
+    twin = rng.choice(n2, n1, replace=False)        # every F1 descriptor is one of F2's with at most 8 bits flipped, at its twin's angle
+    bits = np.unpackbits(desc2[twin], axis=1)
+    for i in range(n1):
+        bits[i, rng.choice(256, rng.integers(0, 9), replace=False)] ^= 1
+    desc1 = np.packbits(bits, axis=1)
+    keys1["angle"] = keys2["angle"][twin]
+    pm0 = np.stack([keys1["x"], keys1["y"]], 1).astype(np.float32)
+    # the overflow by construction: every F2 key-point lies inside the window of every F1 key-point (Frame::GetFeaturesInArea's |dx| < r, |dy| < r)
+    assert np.all(np.abs(keys2["x"][None, :] - pm0[:, :1]) < window) and np.all(np.abs(keys2["y"][None, :] - pm0[:, 1:]) < window)
+    assert n1 * n2 > n1 * 256 + 65536
+    m = ORBmatcher(ratio, True, max_features=2048, max_queries=n1)
+    F1, F2 = FrameView(keys1, desc1, 640, 480, sf), FrameView(keys2, desc2, 640, 480, sf)
+    n_ref, m_ref, pm_ref = O.search_for_initialization(keys1, desc1, keys2, desc2, 640, 480, pm0, window, ratio, True)
+    assert n_ref >= 32
+    n_gpu, m12, pm = m.SearchForInitialization(F1, F2, pm0, window)
+    assert n_gpu == n_ref and np.array_equal(m12, m_ref) and np.array_equal(pm, pm_ref)
+    n_ref2, m_ref2, pm_ref2 = O.search_for_initialization(keys1, desc1, keys2, desc2, 640, 480, pm_ref, window, ratio, True)
+    n_gpu2, m12b, pmb = m.SearchForInitialization(F1, F2, pm, window)
+    assert n_gpu2 == n_ref2 and np.array_equal(m12b, m_ref2) and np.array_equal(pmb, pm_ref2)
+
+
 @pytest.mark.parametrize("seed,coarse,ori", [(0, False, True), (1, False, False), (2, True, True), (3, False, True)])
 def test_search_for_triangulation(matcher, seed, coarse, ori):
     """LocalMapping::CreateNewMapPoints matcher: BoW node walk + epipole / epipolar-line tests, pairs identical to the oracle."""
