@@ -11,6 +11,7 @@
  *   R/lib_src/ORBmatcher.cc:682-804     SearchByBoW(KeyFrame*, KeyFrame*, vector<MapPoint*>&)
  *   R/lib_src/ORBmatcher.cc:1830-1844   DescriptorDistance
  *   R/lib_src/Frame.cc:441-466,695-761  AssignFeaturesToGrid / GetFeaturesInArea / PosInGrid (candidate order)
+ *   R/lib_src/CloudMerging.cc:503-551   the key-point match of ComputeSubmapSim3 (rumi_submap_match)
  * The facade marshals Frame / KeyFrame / MapPoint pointers into the flat views below: a MapPoint* becomes an
  * int32 id into caller-side arrays, NULL becomes -1.  Mono branches only (the node hard-codes MONOCULAR,
  * R/src/cloud_edge_main.cpp:267).  Results are bit-identical to the reference's sequential loops, including
@@ -218,6 +219,32 @@ int rumi_match_bruteforce_ring_device(const void *d_desc, const void *d_n, int32
 /* The blocking of the brute-force kernel, for tests that place cases on its edges: out3 = {queries per wave, queries per workgroup,
  * train rows per LDS stage}.  Needs no device. */
 void rumi_match_bruteforce_shape(int32_t *out3);
+
+/* The key-point match of CloudMerging::ComputeSubmapSim3 (R/lib_src/CloudMerging.cc:503-551) for ALL matched key-frame pairs in one call.  For every
+ * key-point i1 of key-frame 1: KeyFrame::GetFeaturesInArea(mvKeys1[i1].pt, tolerance) in key-frame 2 (KeyFrame.cc:887-925, mono: the gate reads key-frame
+ * 2's mvKeysUn), then the nearest candidate by (float)sqrt(pow(u1 - u2, 2) + pow(v1 - v2, 2)) over the two mvKeys, strictly below a running best that
+ * starts at `tolerance`, among the candidates where both slots hold a map point; the first candidate in the reference's order wins equal distances,
+ * and two key-points of key-frame 1 may keep the same key-point of key-frame 2.  The frames carry no descriptors.
+ * One frame of the table: its grid is rebuilt from keys_un_xy by the Frame::PosInGrid rule with min_x, min_y and the two inverse cell sizes
+ * (mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv; 64 x 48 cells), which is mGrid for a key-frame built from a Frame. */
+typedef struct RumiSubmapFrame {
+    int32_t n;                /* at most 16384 */
+    const float *keys_xy;     /* mvKeys[i].pt, n x 2 */
+    const float *keys_un_xy;  /* mvKeysUn[i].pt, n x 2 (NULL = same as keys_xy) */
+    const uint8_t *has_mp;    /* GetMapPointMatches()[i] != NULL */
+    float min_x, min_y, grid_w_inv, grid_h_inv;
+    int32_t on_device;        /* the three arrays are device pointers (e.g. views of the queue's gathered records), used in place */
+} RumiSubmapFrame;
+
+/* frames [n_frames]: the table; a frame that occurs in several pairs is uploaded once and gets one grid.  Pair p = (pair_f1[p], pair_f2[p]), indices
+ * into the table, in the order the reference walks mKfMatch12.  Outputs, with Q = the sum of n over the pairs' key-frames 1:
+ *   best2 [Q]                    pair after pair: the key-point of key-frame 2 kept by every key-point of key-frame 1, -1 = none
+ *   pair_start [n_pairs + 1]     pair p's matches are matches[pair_start[p] .. pair_start[p + 1])  (matchNum = the difference)
+ *   matches [pair_start[n_pairs]][2]   (i1, i2) in ascending i1: vpMatchedKeyPoints12 = vpValidMatchedKeyPoints12; room for Q entries
+ * RUMI_E_INVALID, with nothing written and no device work: n above 16384 or negative, a pair index outside the table, tolerance <= 0 or not
+ * finite, bounds that are not finite, a NULL array. */
+int rumi_submap_match(RumiMatcher *m, int32_t n_frames, const RumiSubmapFrame *frames, int32_t n_pairs, const int32_t *pair_f1,
+                      const int32_t *pair_f2, float tolerance, int32_t *best2, int32_t *pair_start, int32_t *matches);
 
 #ifdef __cplusplus
 }

@@ -25,9 +25,11 @@
 //   match_tri.inc         k_tri_match, k_tri_filter (TriArgs) and rumi_search_for_triangulation
 //   match_bruteforce.inc  k_bruteforce_mfma with its derivation, launch_bruteforce, rumi_match_bruteforce_*
 //   match_bow_batch.inc   k_bow_batch_match, k_bow_batch_finish (BowKF, BowBatch) and rumi_search_by_bow_batch
+//   match_submap.inc      k_grid_batch, k_submap_match, k_submap_compact (SubFrame, SubPair) and rumi_submap_match
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -138,9 +140,10 @@ extern "C" void rumi_match_destroy(RumiMatcher *m) {
     if (m->ext.state && m->ext.destroy) m->ext.destroy(m->ext.state);
     void *p[] = {m->dKeys, m->dDesc, m->dScale, m->dSorted, m->dCellStart, m->dFvIdx, m->dQ, m->dQDesc, m->dCounts,
                  m->dOffsets, m->dLists, m->dOut, m->dU8a, m->dU8b, m->dF[0], m->dF[1], m->dF[2], m->dF[3],
-                 m->dI[0], m->dI[1], m->dQKeys, m->dNodesA, m->dNodesB, m->dIdxA, m->dOffA, m->dOffB, m->dPose, m->dStage, m->dBow, m->dBowOut};
+                 m->dI[0], m->dI[1], m->dQKeys, m->dNodesA, m->dNodesB, m->dIdxA, m->dOffA, m->dOffB, m->dPose, m->dStage, m->dBow, m->dBowOut,
+                 m->dSub, m->dSubOut};
     for (void *q : p) if (q) (void)hipFree(q);
-    void *h[] = {m->hStage, m->hOut, m->hBow, m->hBowOut};
+    void *h[] = {m->hStage, m->hOut, m->hBow, m->hBowOut, m->hSubOut};
     for (void *q : h) if (q) (void)hipHostFree(q);
     delete m;
 }
@@ -193,16 +196,22 @@ extern "C" int rumi_match_create(int32_t max_features, int32_t max_queries, int3
 
 namespace rumi {
 
-int stage_add(RumiMatcher *m, void *dst, const void *src, size_t bytes) {
-    if (bytes == 0) return RUMI_OK;
+uint8_t *stage_reserve(RumiMatcher *m, void *dst, size_t bytes) {
     const size_t off = (m->stageUsed + 15) & ~(size_t)15;
     if (m->nseg >= kMaxSegments || off + bytes > m->stageCap) {
         g_lastError = "matcher upload block exhausted (raise max_features / max_queries)";
-        return RUMI_E_CAPACITY;
+        return nullptr;
     }
-    std::memcpy(m->hStage + off, src, bytes);
     reinterpret_cast<Segment *>(m->hStage)[m->nseg++] = Segment{dst, (uint32_t)off, (uint32_t)bytes};
     m->stageUsed = off + bytes;
+    return m->hStage + off;
+}
+
+int stage_add(RumiMatcher *m, void *dst, const void *src, size_t bytes) {
+    if (bytes == 0) return RUMI_OK;
+    uint8_t *h = stage_reserve(m, dst, bytes);
+    if (!h) return RUMI_E_CAPACITY;
+    std::memcpy(h, src, bytes);
     return RUMI_OK;
 }
 
@@ -270,3 +279,4 @@ void launch_resolve(const ResolveArgs &A, hipStream_t st) {
 #include "match_tri.inc"
 #include "match_bruteforce.inc"
 #include "match_bow_batch.inc"
+#include "match_submap.inc"

@@ -85,6 +85,9 @@ struct RumiMatcher {
     // rumi_search_by_bow_batch: one pinned block up, one result block back (grown on demand)
     uint8_t *hBow = nullptr, *dBow = nullptr; size_t bowCap = 0;
     uint8_t *hBowOut = nullptr, *dBowOut = nullptr; size_t bowOutCap = 0;
+    // rumi_submap_match: frame / pair tables, uploaded key-points, grids and block counts in dSub; one result block back (grown on demand)
+    uint8_t *dSub = nullptr; size_t subCap = 0;
+    uint8_t *hSubOut = nullptr, *dSubOut = nullptr; size_t subOutCap = 0;
     // k_grid of the uploaded frame, launched by flush_uploads once the key-points are in place
     const int32_t *gridNDev = nullptr;     // k_grid reads the count from the device (one call only: cleared by the flush)
     hipStream_t upStream = nullptr;        // where the next flush queues its copy and scatter (the caller orders its kernels behind them)
@@ -103,6 +106,8 @@ template <class T> int dalloc(T **p, size_t n) {
 
 // Queue `bytes` of host data for the array `dst`; nothing moves until flush_uploads.
 int stage_add(RumiMatcher *m, void *dst, const void *src, size_t bytes);
+// The same for a caller that packs the bytes itself: the place in the pinned block that will land on `dst`, or nullptr when the block is full.
+uint8_t *stage_reserve(RumiMatcher *m, void *dst, size_t bytes);
 // One host-to-device copy for everything queued, the scatter, then the grid of the uploaded frame.
 int flush_uploads(RumiMatcher *m);
 // A call that fails between stage_add and flush must not leak its queue into the next one.
