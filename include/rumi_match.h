@@ -220,6 +220,21 @@ int rumi_match_bruteforce_ring_device(const void *d_desc, const void *d_n, int32
  * train rows per LDS stage}.  Needs no device. */
 void rumi_match_bruteforce_shape(int32_t *out3);
 
+/* One pair, latency form: train rows split into `slices` slices (0 = chosen from nt and cap; forced values are for tests) that run on
+ * different workgroups.  Results equal rumi_match_bruteforce_batch_device's for nbatch = 1, bit for bit, whatever the slice count or
+ * arrival order.  d_scratch: rumi_match_bruteforce_pair_scratch_bytes(cap) bytes, 16-byte aligned, zeroed ONCE by the caller after
+ * allocation; calls that share a scratch must be ordered on one stream.  d_nq / d_nt: one int32 each, on the device (where an extraction
+ * leaves them); outputs [cap] int32 each, rows at or past the query count are left untouched.
+ * A slice is a whole number of the stages of rumi_match_bruteforce_shape; at most min(stages in cap, 64) slices.  RUMI_E_INVALID: what the
+ * strided entry refuses (null pointers, cap outside 1..65535, descriptors not 4-byte aligned), slices < 0 or above that maximum. */
+int64_t rumi_match_bruteforce_pair_scratch_bytes(int32_t cap);                         /* host only; 0 for a cap outside 1..65535 */
+/* host only: out2 = {slices used, rows per slice} for a train count of at most nt (the device entry, which cannot read the count, uses
+ * nt = cap); {0, 0} where the device entry would refuse `slices`. */
+void rumi_match_bruteforce_pair_shape(int32_t cap, int32_t nt, int32_t slices, int32_t *out2);
+int rumi_match_bruteforce_pair_device(const void *d_query, const void *d_nq, const void *d_train, const void *d_nt, int32_t cap,
+                                      int32_t slices, void *d_scratch, void *d_best_idx, void *d_best_dist, void *d_second_dist,
+                                      void *hip_stream);
+
 /* The key-point match of CloudMerging::ComputeSubmapSim3 (R/lib_src/CloudMerging.cc:503-551) for ALL matched key-frame pairs in one call.  For every
  * key-point i1 of key-frame 1: KeyFrame::GetFeaturesInArea(mvKeys1[i1].pt, tolerance) in key-frame 2 (KeyFrame.cc:887-925, mono: the gate reads key-frame
  * 2's mvKeysUn), then the nearest candidate by (float)sqrt(pow(u1 - u2, 2) + pow(v1 - v2, 2)) over the two mvKeys, strictly below a running best that

@@ -86,6 +86,28 @@ int rumi_orb_extract(RumiOrb *h, const uint8_t *img, int32_t w, int32_t hgt, int
  * and stride to rumi_orb_extract saves its staging copy (~20 us for 640 x 480). */
 int rumi_orb_image_buffer(RumiOrb *h, int32_t w, int32_t hgt, uint8_t **buf, int32_t *stride);
 
+/* Streaming front-end (a Tracking-style caller: one frame at a time from a camera).  A stream keeps the previous frame's key-points and
+ * descriptors resident on the device; a push extracts the frame exactly as rumi_orb_extract does (same staging rules, status codes, RUMI_E_EMPTY
+ * and the rumi_orb_image_buffer shortcut) and brute-force matches it -- this frame as query, the previous one as train, first train index wins
+ * ties: rumi_match_bruteforce_pair_device (rumi_match.h) -- in the same call, with one synchronisation.  The first push, a push after a reset
+ * and a push after a frame without key-points match against n_prev = 0: every best_idx = -1, both distances 256.  A failing push leaves the
+ * previous frame as it was.  The stream owns its device slots: rumi_orb_extract or batched calls on the same RumiOrb between two pushes (same
+ * thread) do not disturb it.  Not concurrent with any other use of `h`; destroy the stream before `h`. */
+typedef struct RumiOrbStream RumiOrbStream;
+typedef struct RumiStreamFrame {           /* pointers into the stream's pinned block, valid until the next push / reset / destroy */
+    int32_t n, mono, n_prev;               /* key-points of this frame, operator()'s return value, key-points of the frame matched against */
+    const RumiKeyPoint *kp; const uint8_t *desc;                       /* [n], [n][32] */
+    const int32_t *best_idx, *best_dist, *second_dist;                 /* [n]: this frame (query) against the previous one (train) */
+} RumiStreamFrame;
+int rumi_orb_stream_create(RumiOrb *h, RumiOrbStream **out);          /* two resident slots of h's capacity, scratch, pinned block */
+void rumi_orb_stream_destroy(RumiOrbStream *s);
+int rumi_orb_stream_reset(RumiOrbStream *s);                          /* forget the previous frame */
+int rumi_orb_stream_push(RumiOrbStream *s, const uint8_t *img, int32_t w, int32_t hgt, int32_t stride, int32_t lap0, int32_t lap1,
+                         RumiStreamFrame *out);
+/* The current (last successfully pushed) frame on the device: key-points [cap], descriptors [cap][32], counts {n, monoIndex};
+ * cap = nfeatures + 4 * nlevels + 64.  RUMI_E_INVALID before the first push. */
+int rumi_orb_stream_resident(RumiOrbStream *s, void **d_kp, void **d_desc, void **d_counts);
+
 /* Batched form for the rumination queue (CloudImageSampler.cc:148-170 collects the frames; KFDSample.cc:113
  * runs the same extractor on them).  All pointers are DEVICE pointers; frames are `frame_stride`
  * bytes apart.  Outputs: d_kp [nframes][cap], d_desc [nframes][cap][32], d_counts [nframes][2] =

@@ -25,6 +25,11 @@ class RumiOrbConfig(C.Structure):
                 ("host_threads", C.c_int32), ("blur_variant", C.c_int32)]
 
 
+class RumiStreamFrame(C.Structure):
+    _fields_ = [("n", C.c_int32), ("mono", C.c_int32), ("n_prev", C.c_int32), ("kp", C.c_void_p), ("desc", C.c_void_p),
+                ("best_idx", C.c_void_p), ("best_dist", C.c_void_p), ("second_dist", C.c_void_p)]
+
+
 class RumiError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"rumi status {code}: {msg}")
@@ -37,7 +42,8 @@ _lib = None
 ORB_SYMBOLS = ["rumi_last_error", "rumi_device_count", "rumi_orb_create", "rumi_orb_destroy", "rumi_orb_tables",
                "rumi_orb_extract", "rumi_orb_image_buffer", "rumi_orb_extract_batch_device", "rumi_orb_extract_batch_device_async", "rumi_orb_sync", "rumi_orb_set_resident_queue", "rumi_orb_wait_event", "rumi_orb_extract_batch_records_async", "rumi_orb_extract_batch_host", "rumi_orb_extract_batch_host_records",
                "rumi_orb_pyramid_level",
-               "rumi_orb_stage_keypoints", "rumi_orb_set_profiling", "rumi_orb_stage_ms"]
+               "rumi_orb_stage_keypoints", "rumi_orb_set_profiling", "rumi_orb_stage_ms",
+               "rumi_orb_stream_create", "rumi_orb_stream_destroy", "rumi_orb_stream_reset", "rumi_orb_stream_push", "rumi_orb_stream_resident"]
 
 
 def lib():
@@ -77,6 +83,12 @@ def lib():
     L.rumi_orb_set_resident_queue.argtypes = [vp, i32]
     L.rumi_orb_wait_event.argtypes = [vp, vp]
     L.rumi_orb_stage_ms.argtypes = [vp, vp]
+    L.rumi_orb_stream_create.argtypes = [vp, C.POINTER(vp)]
+    L.rumi_orb_stream_destroy.argtypes = [vp]
+    L.rumi_orb_stream_destroy.restype = None
+    L.rumi_orb_stream_reset.argtypes = [vp]
+    L.rumi_orb_stream_push.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(RumiStreamFrame)]
+    L.rumi_orb_stream_resident.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     _lib = L
     return L
 
@@ -92,7 +104,8 @@ def ptr(a):
 
 MATCH_SYMBOLS = ["rumi_descriptor_distance", "rumi_match_create", "rumi_match_destroy", "rumi_search_by_projection_mappoints",
                  "rumi_search_by_projection_frame", "rumi_search_by_bow", "rumi_search_by_bow_kf", "rumi_search_by_projection_sim3",
-                 "rumi_search_by_projection_reloc", "rumi_search_for_initialization", "rumi_search_for_triangulation", "rumi_fuse_candidates", "rumi_search_by_sim3", "rumi_frame_is_in_frustum", "rumi_search_local_points", "rumi_search_by_bow_batch", "rumi_match_bruteforce_batch_device", "rumi_match_bruteforce_batch_device_strided", "rumi_match_bruteforce_ring_device", "rumi_match_bruteforce_shape", "rumi_submap_match"]
+                 "rumi_search_by_projection_reloc", "rumi_search_for_initialization", "rumi_search_for_triangulation", "rumi_fuse_candidates", "rumi_search_by_sim3", "rumi_frame_is_in_frustum", "rumi_search_local_points", "rumi_search_by_bow_batch", "rumi_match_bruteforce_batch_device", "rumi_match_bruteforce_batch_device_strided", "rumi_match_bruteforce_ring_device", "rumi_match_bruteforce_shape", "rumi_submap_match",
+                 "rumi_match_bruteforce_pair_scratch_bytes", "rumi_match_bruteforce_pair_shape", "rumi_match_bruteforce_pair_device"]
 
 OPT_SYMBOLS = ["rumi_opt_create", "rumi_opt_destroy", "rumi_pose_optimization", "rumi_pose_optimization_batch", "rumi_local_ba", "rumi_local_ba_batch", "rumi_merge_ba", "rumi_bundle_adjustment", "rumi_sim3_inliers",
                "rumi_optimize_sim3", "rumi_sim3_ransac", "rumi_opt_stage_ms", "rumi_opt_set_profiling", "rumi_opt_kernel_ms",

@@ -24,6 +24,8 @@
 //                         rumi_fuse_candidates, rumi_frame_is_in_frustum
 //   match_tri.inc         k_tri_match, k_tri_filter (TriArgs) and rumi_search_for_triangulation
 //   match_bruteforce.inc  k_bruteforce_mfma with its derivation, launch_bruteforce, rumi_match_bruteforce_*
+//   match_bruteforce_pair.inc  k_bruteforce_pair (one pair, train rows split over workgroups, last-arriver merge), launch_bruteforce_pair,
+//                         rumi_match_bruteforce_pair_*
 //   match_bow_batch.inc   k_bow_batch_match, k_bow_batch_finish (BowKF, BowBatch) and rumi_search_by_bow_batch
 //   match_submap.inc      k_grid_batch, k_submap_match, k_submap_compact (SubFrame, SubPair) and rumi_submap_match
 #include <hip/hip_runtime.h>
@@ -278,5 +280,6 @@ void launch_resolve(const ResolveArgs &A, hipStream_t st) {
 #include "match_search.inc"
 #include "match_tri.inc"
 #include "match_bruteforce.inc"
+#include "match_bruteforce_pair.inc"
 #include "match_bow_batch.inc"
 #include "match_submap.inc"

@@ -26,4 +26,13 @@ void voc_params(const RumiVocabulary *v, int *device, int *nWords, int *weightin
 // they live and die with the handle.
 struct MatcherExt { void *state = nullptr; void (*destroy)(void *) = nullptr; };
 
+// k_bruteforce_pair (match.hip, match_bruteforce_pair.inc) for the streaming front-end (orb_host.hip): rumi_match_bruteforce_pair_device with the
+// caller's bound on the train count (the slice rule sees min(nt_bound, cap) rows) and, when `mirror` is set, a second copy of the query frame and
+// of the results written by the same launch: counts {n, monoIndex, n_prev} (d_nq then points at the extractor's {n, monoIndex} pair), the query's
+// key-points (from kp_src) and descriptors (desc 16-byte aligned) and the three result rows -- the device's view of a pinned host block.
+// The arguments are not checked.  Enqueues on `st`, does not synchronise.
+struct PairMirrorArgs { void *counts; const void *kp_src; void *kp, *desc, *best_idx, *best_dist, *second_dist; };
+int launch_bruteforce_pair(const void *qd, const void *nq, const void *td, const void *nt, int cap, int nt_bound, int slices, void *scratch, void *best_idx,
+                           void *best_dist, void *second_dist, const PairMirrorArgs *mirror, hipStream_t st);
+
 }  // namespace rumi

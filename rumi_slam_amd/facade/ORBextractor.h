@@ -36,6 +36,10 @@ public:
 
     // facade-only: the constructor arguments as the C ABI takes them (rumi_facade::TrackFrame creates its tracker from the frame's extractor)
     RumiOrbConfig rumiConfig(int width, int height) const;
+    // facade-only: the C handle, created or re-created (larger) for frames of width x height as operator() would (rumi_facade::FrameStream hangs its
+    // stream on it); nullptr, reported, when that fails.  rumiHandleFits: such a frame needs no re-creation.
+    RumiOrb *rumiHandle(int width, int height) { ensureHandle(width, height); return handle_; }
+    bool rumiHandleFits(int width, int height) const { return handle_ && width <= capW_ && height <= capH_; }
 
     // Filled after every call when keepPyramid is true (stereo matching reads it, Frame.cc:834,918-932); each level is a
     // view with the reference's 19-px BORDER_REFLECT_101 frame around it.  Mono tracking never reads it: set false there.

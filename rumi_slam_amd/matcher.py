@@ -23,7 +23,8 @@ class RumiFeatureVector(C.Structure):
 MATCH_SYMBOLS = ["rumi_descriptor_distance", "rumi_match_create", "rumi_match_destroy", "rumi_search_by_projection_mappoints",
                  "rumi_search_by_projection_frame", "rumi_search_by_bow", "rumi_search_by_bow_kf", "rumi_search_by_projection_sim3",
                  "rumi_search_by_projection_reloc", "rumi_search_for_initialization", "rumi_search_for_triangulation", "rumi_fuse_candidates", "rumi_search_by_sim3", "rumi_frame_is_in_frustum", "rumi_search_by_bow_batch", "rumi_match_bruteforce_batch_device",
-                 "rumi_match_bruteforce_batch_device_strided", "rumi_match_bruteforce_ring_device", "rumi_match_bruteforce_shape"]
+                 "rumi_match_bruteforce_batch_device_strided", "rumi_match_bruteforce_ring_device", "rumi_match_bruteforce_shape",
+                 "rumi_match_bruteforce_pair_scratch_bytes", "rumi_match_bruteforce_pair_shape", "rumi_match_bruteforce_pair_device"]
 
 
 def _lib():
@@ -57,6 +58,11 @@ def _lib():
     L.rumi_match_bruteforce_ring_device.argtypes = [vp, vp, i32, C.c_int64, i32, i32, vp, vp, vp, vp]
     L.rumi_match_bruteforce_shape.argtypes = [vp]
     L.rumi_match_bruteforce_shape.restype = None
+    L.rumi_match_bruteforce_pair_scratch_bytes.argtypes = [i32]
+    L.rumi_match_bruteforce_pair_scratch_bytes.restype = C.c_int64
+    L.rumi_match_bruteforce_pair_shape.argtypes = [i32, i32, i32, vp]
+    L.rumi_match_bruteforce_pair_shape.restype = None
+    L.rumi_match_bruteforce_pair_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L._match_ready = True
     return L
 
@@ -342,3 +348,39 @@ def bruteforce_shape():
     out = (C.c_int32 * 3)()
     _lib().rumi_match_bruteforce_shape(out)
     return tuple(int(x) for x in out)
+
+
+def bruteforce_pair_scratch_bytes(cap):
+    """Bytes of scratch rumi_match_bruteforce_pair_device wants for descriptor blocks of `cap` rows (0: cap outside 1..65535); needs no GPU."""
+    return int(_lib().rumi_match_bruteforce_pair_scratch_bytes(int(cap)))
+
+
+def bruteforce_pair_shape(cap, nt=None, slices=0):
+    """(slices used, train rows per slice) of the one-pair kernel for at most nt train rows (None: cap, what bruteforce_pair uses, which cannot
+    read the count); (0, 0) where the entry refuses `slices`.  Needs no GPU."""
+    out = (C.c_int32 * 2)()
+    _lib().rumi_match_bruteforce_pair_shape(int(cap), int(cap if nt is None else nt), int(slices), out)
+    return int(out[0]), int(out[1])
+
+
+def bruteforce_pair_scratch(cap, device):
+    """A zeroed scratch for bruteforce_pair; reusable by every later call on the same stream without clearing."""
+    import torch
+    return torch.zeros(bruteforce_pair_scratch_bytes(cap), dtype=torch.uint8, device=device)
+
+
+def bruteforce_pair(desc_q, n_q, desc_t, n_t, slices=0, scratch=None, stream=None, out=None):
+    """One pair, latency form (k_bruteforce_pair): desc_*: torch u8 CUDA [cap,32]; n_*: torch i32 CUDA, the count in element 0 (e.g. the
+    extractor's {n, monoIndex} pair).  slices: 0 = automatic, else forced.  scratch: from bruteforce_pair_scratch (None: a fresh one).
+    Returns best_idx, best, second [cap] int32 (out: three preallocated tensors; rows at or past the query count are left as they are)."""
+    import torch
+    cap = desc_q.shape[0]
+    assert desc_q.shape == desc_t.shape and desc_q.stride(0) == 32 and desc_q.stride(1) == 1 and desc_t.stride(0) == 32 and desc_t.stride(1) == 1
+    if scratch is None:
+        scratch = bruteforce_pair_scratch(cap, desc_q.device)
+    if out is None:
+        out = [torch.empty((cap,), dtype=torch.int32, device=desc_q.device) for _ in range(3)]
+    st = stream if stream is not None else torch.cuda.current_stream(desc_q.device)
+    capi.check(_lib().rumi_match_bruteforce_pair_device(desc_q.data_ptr(), n_q.data_ptr(), desc_t.data_ptr(), n_t.data_ptr(), cap, int(slices),
+                                                        scratch.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), st.cuda_stream))
+    return out
