@@ -146,7 +146,7 @@ static int ba_big_prepare(RumiOptimizer *o, hipStream_t st, const BaLayout &L, i
     if (!blk.empty()) HIP_TRY(hipMemcpyAsync(o->dPairs, blk.data(), blk.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(o->dPairs + blk.size(), pairs.data(), pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));                 // blk / pairs are temporaries
-    if (!o->dW) { int rcw = oalloc(&o->dW, (size_t)o->maxE * 18); if (rcw == RUMI_OK) rcw = oalloc(&o->dColOf, (size_t)o->maxE); if (rcw != RUMI_OK) return rcw; }
+    if (!o->dW) { int rcw = dev_alloc(&o->dW, (size_t)o->maxE * 18); if (rcw == RUMI_OK) rcw = dev_alloc(&o->dColOf, (size_t)o->maxE); if (rcw != RUMI_OK) return rcw; }
     // more than 64 KiB of dynamic LDS needs the opt-in; the limit is process state and only grows (rumi_common.h: raise_lds_limit), so that the
     // worker threads of rumi_local_ba_batch and the facade's per-thread arenas cannot lower it under each other
     if ((size_t)n * 8 > 16 * 1024) HIP_TRY(raise_lds_limit(reinterpret_cast<const void *>(k_chol_backsub), (size_t)n * 8));

@@ -138,13 +138,6 @@ __global__ __launch_bounds__(kReplayThreads) void k_cull_replay(CullArgs a) {
     if (tid == 0) *head = make_int4(nCulled, reached, 0, 0);
 }
 
-template <class T> int regrow(T **p, size_t bytes, bool pinned) {
-    if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); *p = nullptr; }
-    if (pinned) HIP_TRY(hipHostMalloc((void **)p, bytes, hipHostMallocDefault));
-    else HIP_TRY(hipMalloc((void **)p, bytes));
-    return RUMI_OK;
-}
-
 }  // namespace
 }  // namespace rumi
 

@@ -389,13 +389,6 @@ static void newpts_destroy(void *p) {
     delete s;
 }
 
-template <class T> static int regrow(T **p, size_t bytes, bool pinned) {
-    if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); *p = nullptr; }
-    if (pinned) HIP_TRY(hipHostMalloc((void **)p, bytes, hipHostMallocDefault));
-    else HIP_TRY(hipMalloc((void **)p, bytes));
-    return RUMI_OK;
-}
-
 static bool kf_valid(const RumiNewPointsKF &k, bool neighbour, const char **why) {
     const RumiFrameFeatures &f = k.feat;
     const RumiFeatureVector &v = k.fv;

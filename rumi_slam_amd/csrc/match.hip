@@ -170,20 +170,20 @@ extern "C" int rumi_match_create(int32_t max_features, int32_t max_queries, int3
     const size_t F = max_features, Q = max_queries;
     int rc;
 #define TRYA(x) if ((rc = (x)) != RUMI_OK) { rumi_match_destroy(m); return rc; }
-    TRYA(dalloc(&m->dKeys, F)); TRYA(dalloc(&m->dDesc, F * 32)); TRYA(dalloc(&m->dScale, 64));
-    TRYA(dalloc(&m->dSorted, F)); TRYA(dalloc(&m->dCellStart, kGridCells + 2));
-    TRYA(dalloc(&m->dFvIdx, F));
-    TRYA(dalloc(&m->dQ, Q)); TRYA(dalloc(&m->dQDesc, Q * 32)); TRYA(dalloc(&m->dCounts, Q + 1)); TRYA(dalloc(&m->dOffsets, Q + 1));
-    TRYA(dalloc(&m->dLists, m->listCap));
-    TRYA(dalloc(&m->dOut, 4 + F + Q));
+    TRYA(dev_alloc(&m->dKeys, F)); TRYA(dev_alloc(&m->dDesc, F * 32)); TRYA(dev_alloc(&m->dScale, 64));
+    TRYA(dev_alloc(&m->dSorted, F)); TRYA(dev_alloc(&m->dCellStart, kGridCells + 2));
+    TRYA(dev_alloc(&m->dFvIdx, F));
+    TRYA(dev_alloc(&m->dQ, Q)); TRYA(dev_alloc(&m->dQDesc, Q * 32)); TRYA(dev_alloc(&m->dCounts, Q + 1)); TRYA(dev_alloc(&m->dOffsets, Q + 1));
+    TRYA(dev_alloc(&m->dLists, m->listCap));
+    TRYA(dev_alloc(&m->dOut, 4 + F + Q));
     m->dNmatches = m->dOut; m->dOverflow = m->dOut + 1; m->dFeatMp = m->dOut + 4; m->dAssign = m->dOut + 4 + F;
-    TRYA(dalloc(&m->dU8a, Q)); TRYA(dalloc(&m->dU8b, std::max(Q, F)));
-    for (auto &f : m->dF) TRYA(dalloc(&f, Q * 3));
-    for (auto &i : m->dI) TRYA(dalloc(&i, Q + 1));
-    TRYA(dalloc(&m->dQKeys, Q)); TRYA(dalloc(&m->dNodesA, Q)); TRYA(dalloc(&m->dNodesB, F)); TRYA(dalloc(&m->dIdxA, Q));
-    TRYA(dalloc(&m->dOffA, Q + 1)); TRYA(dalloc(&m->dOffB, F + 1)); TRYA(dalloc(&m->dPose, 32));
+    TRYA(dev_alloc(&m->dU8a, Q)); TRYA(dev_alloc(&m->dU8b, std::max(Q, F)));
+    for (auto &f : m->dF) TRYA(dev_alloc(&f, Q * 3));
+    for (auto &i : m->dI) TRYA(dev_alloc(&i, Q + 1));
+    TRYA(dev_alloc(&m->dQKeys, Q)); TRYA(dev_alloc(&m->dNodesA, Q)); TRYA(dev_alloc(&m->dNodesB, F)); TRYA(dev_alloc(&m->dIdxA, Q));
+    TRYA(dev_alloc(&m->dOffA, Q + 1)); TRYA(dev_alloc(&m->dOffB, F + 1)); TRYA(dev_alloc(&m->dPose, 32));
     m->stageCap = kStageHeader + F * 112 + Q * 224 + 65536;
-    TRYA(dalloc(&m->dStage, m->stageCap));
+    TRYA(dev_alloc(&m->dStage, m->stageCap));
     if (hipHostMalloc((void **)&m->hStage, m->stageCap, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc((void **)&m->hOut, (4 + F + Q) * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
         g_lastError = "rumi_match_create: pinned host allocation failed";

@@ -98,12 +98,6 @@ struct RumiMatcher {
 
 namespace rumi {
 
-template <class T> int dalloc(T **p, size_t n) {
-    *p = nullptr;
-    HIP_TRY(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
-    return RUMI_OK;
-}
-
 // Queue `bytes` of host data for the array `dst`; nothing moves until flush_uploads.
 int stage_add(RumiMatcher *m, void *dst, const void *src, size_t bytes);
 // The same for a caller that packs the bytes itself: the place in the pinned block that will land on `dst`, or nullptr when the block is full.

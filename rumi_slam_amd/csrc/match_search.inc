@@ -33,7 +33,7 @@ static int grow_lists(RumiMatcher *m, size_t need) {
     (void)hipFree(m->dLists);
     m->dLists = nullptr;
     m->listCap = need * 2;
-    return dalloc(&m->dLists, m->listCap);
+    return dev_alloc(&m->dLists, m->listCap);
 }
 
 // Candidate lists, the resolve (`resolve()` launches it on the arrays as they are at that moment: the arena may have moved) and the results, until

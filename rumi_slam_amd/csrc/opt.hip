@@ -94,11 +94,6 @@ struct RumiOptimizer {
 };
 
 static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }   // offsets inside the transfer blocks
-template <class T> static int oalloc(T **p, size_t n) {
-    *p = nullptr;
-    HIP_TRY(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
-    return RUMI_OK;
-}
 
 extern "C" void rumi_opt_destroy(RumiOptimizer *o) {
     if (!o) return;
@@ -148,14 +143,14 @@ extern "C" int rumi_opt_create(int32_t max_pose_edges, int32_t max_pose_batch, i
     const size_t PE = max_pose_edges, PB = max_pose_batch, K = max_kf, M = max_mp, E = max_edges, N = 6 * K;
     int rc;
 #define TRYA(x) if ((rc = (x)) != RUMI_OK) { rumi_opt_destroy(o); return rc; }
-    TRYA(oalloc(&o->dActive, PE)); TRYA(oalloc(&o->dLastChi2, PE));
-    for (int i = 0; i < 2; i++) { TRYA(oalloc(&o->dT[i], K * 8)); TRYA(oalloc(&o->dX[i], M * 3)); }
-    TRYA(oalloc(&o->dHll, M * 9)); TRYA(oalloc(&o->dBl, M * 3)); TRYA(oalloc(&o->dHpl, E * 18)); TRYA(oalloc(&o->dPanel, E * 16 + 64));
-    TRYA(oalloc(&o->dHpp, K * 36)); TRYA(oalloc(&o->dBp, N)); TRYA(oalloc(&o->dDinv, M * 9));
-    TRYA(oalloc(&o->dXv, N + M * 3)); TRYA(oalloc(&o->dChi, E)); TRYA(oalloc(&o->dScal, 8));
+    TRYA(dev_alloc(&o->dActive, PE)); TRYA(dev_alloc(&o->dLastChi2, PE));
+    for (int i = 0; i < 2; i++) { TRYA(dev_alloc(&o->dT[i], K * 8)); TRYA(dev_alloc(&o->dX[i], M * 3)); }
+    TRYA(dev_alloc(&o->dHll, M * 9)); TRYA(dev_alloc(&o->dBl, M * 3)); TRYA(dev_alloc(&o->dHpl, E * 18)); TRYA(dev_alloc(&o->dPanel, E * 16 + 64));
+    TRYA(dev_alloc(&o->dHpp, K * 36)); TRYA(dev_alloc(&o->dBp, N)); TRYA(dev_alloc(&o->dDinv, M * 9));
+    TRYA(dev_alloc(&o->dXv, N + M * 3)); TRYA(dev_alloc(&o->dChi, E)); TRYA(dev_alloc(&o->dScal, 8));
     o->npCap = (int)std::min<size_t>((N + 1 + 15) / 16 * 16, 256);
-    TRYA(oalloc(&o->dAglob, (N + 2) * (N + 2) + 2 * N)); TRYA(oalloc(&o->dEOff, E));
-    TRYA(oalloc(&o->dYt, 3 * M * (size_t)o->npCap)); TRYA(oalloc(&o->dG, (size_t)o->npCap * o->npCap)); TRYA(oalloc(&o->dLp, M * 6));
+    TRYA(dev_alloc(&o->dAglob, (N + 2) * (N + 2) + 2 * N)); TRYA(dev_alloc(&o->dEOff, E));
+    TRYA(dev_alloc(&o->dYt, 3 * M * (size_t)o->npCap)); TRYA(dev_alloc(&o->dG, (size_t)o->npCap * o->npCap)); TRYA(dev_alloc(&o->dLp, M * 6));
 #undef TRYA
     if (hipHostMalloc((void **)&o->hScal, 16 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostGetDevicePointer((void **)&o->dhScal, o->hScal, 0) != hipSuccess) { rumi_opt_destroy(o); return RUMI_E_NO_DEVICE; }

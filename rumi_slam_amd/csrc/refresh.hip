@@ -163,13 +163,6 @@ __global__ __launch_bounds__(256) void k_refresh_normal(const PtDev *__restrict_
     out[p].updated = 1;
 }
 
-template <class T> int regrow(T **p, size_t bytes, bool pinned) {
-    if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); *p = nullptr; }
-    if (pinned) HIP_TRY(hipHostMalloc((void **)p, bytes, hipHostMallocDefault));
-    else HIP_TRY(hipMalloc((void **)p, bytes));
-    return RUMI_OK;
-}
-
 }  // namespace
 }  // namespace rumi
 

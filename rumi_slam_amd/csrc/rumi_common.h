@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <functional>
 #include <map>
@@ -41,3 +42,25 @@ inline hipError_t raise_lds_limit(const void *fn, size_t bytes) {
             return RUMI_E_NO_DEVICE;                                                           \
         }                                                                                      \
     } while (0)
+
+namespace rumi {
+// The allocation helpers of the C-ABI translation units: a failure ends the caller through HIP_TRY's message and RUMI_E_NO_DEVICE.
+// n elements of T (at least one) in device / pinned host memory; *p is null on failure
+template <class T> int dev_alloc(T **p, size_t n) {
+    *p = nullptr;
+    HIP_TRY(hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)));
+    return RUMI_OK;
+}
+template <class T> int pin_alloc(T **p, size_t n) {
+    *p = nullptr;
+    HIP_TRY(hipHostMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault));
+    return RUMI_OK;
+}
+// a block grown on demand: the old one is released, `bytes` of device or pinned host memory take its place (the contents are not kept)
+template <class T> int regrow(T **p, size_t bytes, bool pinned) {
+    if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); *p = nullptr; }
+    if (pinned) HIP_TRY(hipHostMalloc((void **)p, bytes, hipHostMallocDefault));
+    else HIP_TRY(hipMalloc((void **)p, bytes));
+    return RUMI_OK;
+}
+}  // namespace rumi

@@ -340,10 +340,10 @@ extern "C" int rumi_track_create(const RumiOrbConfig *cfg, int32_t max_points, i
     const size_t oMp = al(sizeof(TrackBlock)), oMpM = al(oMp + C * 4), oOut = al(oMpM + C * 4), oView = al(oOut + C);
     t->oRec = al(oView + P); t->blkBytes = al(t->oRec + t->recordBytes);
 #define TRYA(x) if ((rc = (x)) != RUMI_OK) { rumi_track_destroy(t); return rc; }
-    TRYA(dalloc(&t->dImage, t->imageBytes + 64)); TRYA(dalloc(&t->dBlk, t->blkBytes)); TRYA(dalloc(&t->dInvSigma2, 64));
-    TRYA(dalloc(&t->dXw, C * 3)); TRYA(dalloc(&t->dObs, C * 2)); TRYA(dalloc(&t->dW, C)); TRYA(dalloc(&t->dIdx, C));
-    TRYA(dalloc(&t->dOutC, C)); TRYA(dalloc(&t->dActive, C)); TRYA(dalloc(&t->dSeen, P)); TRYA(dalloc(&t->dBad, P)); TRYA(dalloc(&t->dLocal, P)); TRYA(dalloc(&t->dStaleIn, P)); TRYA(dalloc(&t->dStaleProj, P * 5)); TRYA(dalloc(&t->dChi, C));
-    TRYA(dalloc(&t->dBow, C * 16)); TRYA(dalloc(&t->dNN, 4));
+    TRYA(dev_alloc(&t->dImage, t->imageBytes + 64)); TRYA(dev_alloc(&t->dBlk, t->blkBytes)); TRYA(dev_alloc(&t->dInvSigma2, 64));
+    TRYA(dev_alloc(&t->dXw, C * 3)); TRYA(dev_alloc(&t->dObs, C * 2)); TRYA(dev_alloc(&t->dW, C)); TRYA(dev_alloc(&t->dIdx, C));
+    TRYA(dev_alloc(&t->dOutC, C)); TRYA(dev_alloc(&t->dActive, C)); TRYA(dev_alloc(&t->dSeen, P)); TRYA(dev_alloc(&t->dBad, P)); TRYA(dev_alloc(&t->dLocal, P)); TRYA(dev_alloc(&t->dStaleIn, P)); TRYA(dev_alloc(&t->dStaleProj, P * 5)); TRYA(dev_alloc(&t->dChi, C));
+    TRYA(dev_alloc(&t->dBow, C * 16)); TRYA(dev_alloc(&t->dNN, 4));
     t->dWeight = reinterpret_cast<double *>(t->dBow); t->dWord = reinterpret_cast<uint32_t *>(t->dBow + C * 8); t->dNode = t->dWord + C;
 #undef TRYA
     if (hipHostMalloc((void **)&t->hBlk, t->blkBytes, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void **)&t->hBow, C * 16, hipHostMallocDefault) != hipSuccess ||

@@ -1,5 +1,5 @@
 """The extractor kernels against the constructed cases of extract_cases.py (and against the oracle), through the stage taps and the final
-records.  Which kernels a call launches depends on the geometry and on the number of frames (csrc/orb_host.hip):
+records.  Which kernels a call launches depends on the geometry and on the number of frames (csrc/orb_schedule.inc):
 
   * FAST and blur: geometries whose widest cell is 37..40 px (tile pitch 48, as at 640 x 480) run the fused k_fast_blur in calls of fewer than 16
     frames and k_fast_cells<48> + the blur kernel from 16 frames on.  Families A, C, most of D and the 181 / 183 px wide B cases are on such
@@ -36,7 +36,7 @@ _ext, _orc = {}, {}
 
 
 def fused(c):
-    """True when the geometry's widest cell gives the tile pitch 48 that k_fast_blur is instantiated for (fast_lds_of, csrc/orb_kernels.hip)."""
+    """True when the geometry's widest cell gives the tile pitch 48 that k_fast_blur is instantiated for (fast_lds_of, csrc/orb_fast.inc)."""
     h, w = c.frame.shape
     inv = [np.float32(1.0) / s for s in EC.scale_table(c.ctor[1], c.ctor[2])]
     wmax = max(EC.grid(int(np.rint(np.float32(w) * i)), int(np.rint(np.float32(h) * i)))[2] for i in inv)

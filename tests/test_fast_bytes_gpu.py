@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 THRESHOLDS = [(1, 1), (20, 7), (254, 1)]
 KINDS = ["saturating", "contrast_t", "noise", "ramp", "synth", "flat", "white", "black"]
-RING_CAP = 640                        # kRingCap of orb_kernels.hip: entries the linear ring holds
+RING_CAP = 640                        # kRingCap of orb_fast.inc: entries the linear ring holds
 
 
 def make_frame(kind, w=640, h=480, seed=0):
