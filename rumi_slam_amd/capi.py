@@ -122,6 +122,29 @@ KFDB_SYMBOLS = ["rumi_kfdb_create", "rumi_kfdb_destroy", "rumi_kfdb_clear", "rum
                 "rumi_kfdb_set_bad", "rumi_kfdb_set_covisibles", "rumi_kfdb_score", "rumi_kfdb_scored", "rumi_kfdb_select_reloc", "rumi_kfdb_select_nbest"]
 MAPPING_SYMBOLS = ["rumi_create_new_map_points", "rumi_refresh_create", "rumi_refresh_destroy", "rumi_refresh_map_points", "rumi_refresh_stage_ms",
                    "rumi_cull_create", "rumi_cull_destroy", "rumi_keyframe_culling", "rumi_cull_stage_ms"]
+KFD_SYMBOLS = ["rumi_kfd_create", "rumi_kfd_destroy", "rumi_kfd_set_pd", "rumi_kfd_reset", "rumi_kfd_step", "rumi_kfd_track"]
+
+
+class RumiKfdStep(C.Structure):
+    _fields_ = [("selected", C.c_int32), ("n_tracked", C.c_int32), ("n_good", C.c_int32), ("moptf", C.c_float), ("pd_out", C.c_float), ("th", C.c_float),
+                ("next", C.c_void_p), ("status", C.c_void_p), ("n", C.c_int32), ("mono", C.c_int32), ("kp", C.c_void_p), ("desc", C.c_void_p)]
+
+
+def kfd_lib():
+    """The PD frame selector's entries (include/rumi_kfd.h) with their argument types."""
+    L = lib()
+    if getattr(L, "_kfd_ready", False):
+        return L
+    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
+    L.rumi_kfd_create.argtypes = [vp, C.POINTER(vp)]
+    L.rumi_kfd_destroy.argtypes = [vp]
+    L.rumi_kfd_destroy.restype = None
+    L.rumi_kfd_set_pd.argtypes = [vp, f32, f32, f32]
+    L.rumi_kfd_reset.argtypes = [vp]
+    L.rumi_kfd_step.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, C.POINTER(RumiKfdStep)]
+    L.rumi_kfd_track.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
+    L._kfd_ready = True
+    return L
 
 
 def kfdb_lib():

@@ -9,6 +9,7 @@
 //   orb_host_batch.inc  extract_batch_host_impl (the feeder of host-resident batches) and its two entries
 //   orb_single.inc      rumi_orb_image_buffer, rumi_orb_extract, RumiOrbStream and the rumi_orb_stream_* entries
 //   orb_taps.inc        rumi_orb_pyramid_level, fetch_taps, rumi_orb_stage_keypoints
+//   orb_kfd.inc         RumiKfd and the rumi_kfd_* entries (include/rumi_kfd.h): the PD frame selector, whose selected frames go through this extractor
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -22,10 +23,12 @@
 #include <thread>
 #include <vector>
 
+#include "flow_device.h"
 #include "orb_device.h"
 #include "orb_octree.h"
 #include "rumi_common.h"
 #include "rumi_internal.h"
+#include "rumi_kfd.h"
 #include "rumi_match.h"
 
 using namespace rumi;
@@ -339,3 +342,4 @@ extern "C" int rumi_orb_sync(RumiOrb *h) {
 #include "orb_host_batch.inc"
 #include "orb_single.inc"
 #include "orb_taps.inc"
+#include "orb_kfd.inc"

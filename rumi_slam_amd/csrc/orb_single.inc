@@ -17,18 +17,10 @@ static void stage_host_frame(RumiOrb *h, const uint8_t *img, int w, int hgt, int
     for (int y = 0; y < hgt; y++) std::memcpy(h->hIn + (size_t)y * wp, img + (size_t)y * stride, (size_t)w);
 }
 
-extern "C" int rumi_orb_extract(RumiOrb *h, const uint8_t *img, int32_t w, int32_t hgt, int32_t stride, int32_t lap0,
-                                int32_t lap1, RumiKeyPoint *kp_out, uint8_t *desc_out, int32_t cap, int32_t *n_out,
-                                int32_t *mono_out) {
-    if (n_out) *n_out = 0;
-    if (mono_out) *mono_out = -1;
-    if (!h || !n_out || !mono_out) return RUMI_E_INVALID;
-    if (!img || w <= 0 || hgt <= 0) return RUMI_E_EMPTY;            // operator() returns -1 on an empty image
-    if (stride < w || w > h->cfg.max_width || hgt > h->cfg.max_height) { g_lastError = "image size"; return RUMI_E_INVALID; }
-    HIP_TRY(hipSetDevice(h->device));
-    // image -> pinned -> device (async), kernels, [counts | key-points | descriptors] -> pinned: one synchronisation in all
-    const int wp = (w + 3) & ~3;
-    stage_host_frame(h, img, w, hgt, stride, wp);
+// One frame, already staged in hIn (fromStaging: it is copied to dIn on the call's stream) or already resident at `dImg` (rows wp bytes apart), through the
+// extractor into the handle's pinned result block hOut1 = [counts {n, monoIndex} | key-points capSel x 28 at +16 | descriptors capSel x 32]: one
+// synchronisation in all.
+static int extract_one_to_pinned(RumiOrb *h, const uint8_t *dImg, int w, int hgt, int wp, int lap0, int lap1, bool fromStaging) {
     // Results straight into pinned host memory: the kernels' output pointers are the device's view of hOut1 (k_assemble writes the counts and the
     // final error word, k_orient_desc key-points and descriptors), so the call ends with its last kernel -- no copy back, no second copy for the
     // error word (two dependent transfers of ~6 + 2 us with ~9 us of queue latency each).  Profiling keeps the copies.
@@ -38,9 +30,24 @@ extern "C" int rumi_orb_extract(RumiOrb *h, const uint8_t *img, int32_t w, int32
     RumiKeyPoint *dK = reinterpret_cast<RumiKeyPoint *>(ob + 16);
     uint8_t *dD = ob + 16 + (size_t)h->capSel * sizeof(RumiKeyPoint);
     CallOpts opts;
-    opts.hostImagePending = true; opts.zeroCopyOut = zero; opts.out1Bytes = zero ? 0 : (size_t)16 + (size_t)h->capSel * 60;
+    opts.hostImagePending = fromStaging; opts.zeroCopyOut = zero; opts.out1Bytes = zero ? 0 : (size_t)16 + (size_t)h->capSel * 60;
     if (zero) *h->hErr = 0;
-    const int rc = end_call(h, extract_async_impl(h, h->dIn, 1, w, hgt, wp, (int64_t)wp * hgt, lap0, lap1, three_array_layout(dK, dD, dC, h->capSel), h->capSel, nullptr, opts));
+    return end_call(h, extract_async_impl(h, dImg, 1, w, hgt, wp, (int64_t)wp * hgt, lap0, lap1, three_array_layout(dK, dD, dC, h->capSel), h->capSel, nullptr, opts));
+}
+
+extern "C" int rumi_orb_extract(RumiOrb *h, const uint8_t *img, int32_t w, int32_t hgt, int32_t stride, int32_t lap0,
+                                int32_t lap1, RumiKeyPoint *kp_out, uint8_t *desc_out, int32_t cap, int32_t *n_out,
+                                int32_t *mono_out) {
+    if (n_out) *n_out = 0;
+    if (mono_out) *mono_out = -1;
+    if (!h || !n_out || !mono_out) return RUMI_E_INVALID;
+    if (!img || w <= 0 || hgt <= 0) return RUMI_E_EMPTY;            // operator() returns -1 on an empty image
+    if (stride < w || w > h->cfg.max_width || hgt > h->cfg.max_height) { g_lastError = "image size"; return RUMI_E_INVALID; }
+    HIP_TRY(hipSetDevice(h->device));
+    // image -> pinned -> device (async), kernels, [counts | key-points | descriptors] -> pinned
+    const int wp = (w + 3) & ~3;
+    stage_host_frame(h, img, w, hgt, stride, wp);
+    const int rc = extract_one_to_pinned(h, h->dIn, w, hgt, wp, lap0, lap1, true);
     if (rc != RUMI_OK) return rc;
     const int32_t *counts = reinterpret_cast<const int32_t *>(h->hOut1);
     *n_out = counts[0];
