@@ -1,0 +1,91 @@
+/* rumi_covis.h — C ABI of the MI355X covisibility store: KeyFrame::UpdateConnections for a batch, Tracking::UpdateLocalMap for a frame.
+ *
+ * Replaces the two members of the reference that histogram key-frames over observation lists:
+ *   KeyFrame::UpdateConnections / UpdateCloudConnections   R/lib_src/KeyFrame.cc:487-574, :576+   (the counting and the two orderings)
+ *   Tracking::UpdateLocalKeyFrames + UpdateLocalPoints     R/lib_src/Tracking.cc:3067-3210        (monocular, IMU not initialised)
+ *
+ * The handle keeps, on the device and between calls, what those members read and nothing else.  A key-frame is a slot 0 .. max_kf-1 chosen
+ * by the caller, a map point an id 0 .. max_points-1.
+ *   per key-frame slot: mp[n] (GetMapPointMatches as point ids, -1 = NULL), is_bad, map_id, order_key, best[10]
+ *                       (GetBestCovisibilityKeyFrames(10) as slots, -1 padded), parent slot or -1, the children as a slot list
+ *   per point:          is_bad, the observers (the key-frame slots of GetObservations(); feature indices are not kept)
+ *
+ * order_key restates pointer order.  Every ordered walk in the two members is a walk of a std::map<KeyFrame*, ..> or a
+ * std::set<KeyFrame*>, and every tie of sort(vPairs) is broken by the KeyFrame*: "pointer order" here is ascending order_key, distinct per
+ * live slot and unrelated to slot numbers.  A C++ host passes the pointer value.
+ *
+ * Edits (rumi_covis_set_*) are validated, then staged on the host; the next query uploads them in one block whose size follows what
+ * changed, not the map.  A slot is live once rumi_covis_set_keyframes has named it, and stays live.  Every slot a call names (observers,
+ * best, parent, children, the batch) must be live, or become live in the same rumi_covis_set_keyframes call.  A refused call
+ * (RUMI_E_INVALID, RUMI_E_CAPACITY) leaves the state and every output untouched.
+ *
+ * Both queries are integer-only: two calls on the same state return the same bytes.  They work on the default (null) stream and return
+ * when their results are on the host.  Status codes as in rumi_orb.h.  No CPU fallback. */
+#ifndef RUMI_COVIS_H
+#define RUMI_COVIS_H
+#include <stdint.h>
+
+#include "rumi_orb.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct RumiCovis RumiCovis;
+
+#define RUMI_COVIS_MAX_KEYFRAMES 8192 /* slots: one 32-bit LDS counter each (32 KiB of a workgroup's LDS), see DESIGN 4o */
+#define RUMI_COVIS_MAX_FEATURES 65536 /* longest mp row, and the most points a frame passes */
+#define RUMI_COVIS_NBEST 10           /* GetBestCovisibilityKeyFrames(10) */
+#define RUMI_COVIS_TH 15              /* KeyFrame.cc:524 */
+#define RUMI_COVIS_LOCAL_LIMIT 80     /* Tracking.cc:3150 */
+
+enum { RUMI_COVIS_CONNECTED = 0, RUMI_COVIS_EMPTY = 1 }; /* EMPTY: the early return at KeyFrame.cc:519, the host writes nothing */
+
+/* max_kf <= RUMI_COVIS_MAX_KEYFRAMES (RUMI_E_CAPACITY above).  arena_entries: first size of the row arena in 32-bit entries (0: a default);
+ * it is compacted when full and doubled when the live rows fill more than three quarters of it. */
+int rumi_covis_create(int32_t max_kf, int32_t max_points, int64_t arena_entries, int32_t device, RumiCovis **out);
+void rumi_covis_destroy(RumiCovis *c);
+
+/* n key-frames, each slot at most once: mp row of entry i = mp[mp_off[i] .. mp_off[i+1]), children = children[child_off[i] .. child_off[i+1])
+ * (distinct slots, never the key-frame itself), best [n][10], parent [n].  order_keys distinct among the live slots after the call.
+ * map_ids, is_bad as they are now. */
+int rumi_covis_set_keyframes(RumiCovis *c, int32_t n, const int32_t *slots, const uint64_t *order_keys, const int32_t *map_ids, const uint8_t *is_bad,
+                             const int32_t *mp_off, const int32_t *mp, const int32_t *best, const int32_t *parent, const int32_t *child_off,
+                             const int32_t *children);
+/* n points, each id at most once: observers of entry i = obs[obs_off[i] .. obs_off[i+1]), distinct live slots. */
+int rumi_covis_set_points(RumiCovis *c, int32_t n, const int32_t *ids, const uint8_t *is_bad, const int32_t *obs_off, const int32_t *obs);
+/* KeyFrame::isBad of n_kf live slots and MapPoint::isBad of n_pt points. */
+int rumi_covis_set_bad(RumiCovis *c, int32_t n_kf, const int32_t *slots, const uint8_t *kf_bad, int32_t n_pt, const int32_t *ids, const uint8_t *pt_bad);
+/* KeyFrame::GetMap of n live slots changed (map merge). */
+int rumi_covis_set_maps(RumiCovis *c, int32_t n, const int32_t *slots, const int32_t *map_ids);
+
+/* KeyFrame::UpdateConnections for the key-frames batch[0 .. B), live slots in this order; a slot may repeat.  Per entry b:
+ *   status[b]                                                  RUMI_COVIS_CONNECTED or RUMI_COVIS_EMPTY (both lists empty then)
+ *   (conn_slot, conn_count)[conn_off[b] .. conn_off[b+1])      KFcounter = mConnectedKeyFrameWeights, in key order
+ *   (ord_slot, ord_weight)[ord_off[b] .. ord_off[b+1])         mvpOrderedConnectedKeyFrames / mvOrderedWeights: the entries with count >= 15,
+ *                                                              or the single (pKFmax, nmax); weight descending, key descending among equals
+ * The counting reads no connection state, so the B results do not depend on each other; the host replays AddConnection, the member writes
+ * and the parent choice in batch order.  conn_cap / ord_cap: capacities of the caller's arrays; RUMI_E_CAPACITY, nothing written, when a
+ * list does not fit. */
+int rumi_covis_update_connections(RumiCovis *c, int32_t B, const int32_t *batch, int32_t *status, int32_t *conn_off, int32_t *conn_slot,
+                                  int32_t *conn_count, int64_t conn_cap, int32_t *ord_off, int32_t *ord_slot, int32_t *ord_weight, int64_t ord_cap);
+
+/* Tracking::UpdateLocalKeyFrames + UpdateLocalPoints for one frame.  frame_points [n]: mCurrentFrame.mvpMapPoints as point ids, -1 = NULL.
+ *   frame_point_bad [n]     1 where the point is bad: it gave no vote and the caller NULLs it (Tracking.cc:3102)
+ *   local_kf [n_local_kf]   mvpLocalKeyFrames; the first n_k1 are the voted key-frames in key order
+ *   ref_kf                  pKFmax, or -1 (mpReferenceKF stays)
+ *   local_points            mvpLocalMapPoints
+ * mnTrackReferenceForFrame of key-frames and points is the de-duplication of this call and nothing else: the coincidence of frame id 0
+ * with the stamp's initial value is not reproduced.  RUMI_E_CAPACITY, nothing written, when kf_cap or pt_cap is too small. */
+int rumi_covis_local_map(RumiCovis *c, int32_t n, const int32_t *frame_points, uint8_t *frame_point_bad, int32_t *local_kf, int32_t kf_cap,
+                         int32_t *n_k1, int32_t *n_local_kf, int32_t *ref_kf, int32_t *local_points, int32_t pt_cap, int32_t *n_local_points);
+
+/* The last query, in ms: validation + staging | upload, kernels, download | write-out. */
+int rumi_covis_stage_ms(const RumiCovis *c, float *out3);
+/* out7: arena capacity, tail, live entries (all in 32-bit entries), rows re-placed at the tail, compactions, growths, bytes of the last upload. */
+int rumi_covis_stats(const RumiCovis *c, int64_t *out7);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,7 +1,7 @@
 /* C ABI of one device-resident Tracking step: ORBextractor::operator() -> ORBmatcher::SearchByProjection(Cur, Last) -> Optimizer::PoseOptimization
  * -> Tracking::SearchLocalPoints (Frame::isInFrustum + SearchByProjection(Cur, local points)) -> Optimizer::PoseOptimization, i.e. the data path of
  *   Tracking::TrackWithMotionModel   R/lib_src/Tracking.cc:2441-2530   (monocular, no IMU)
- *   Tracking::TrackLocalMap          R/lib_src/Tracking.cc:2545-2607   (the part after UpdateLocalMap, which stays on the host)
+ *   Tracking::TrackLocalMap          R/lib_src/Tracking.cc:2545-2607   (the part after UpdateLocalMap: the host's, or rumi_covis_local_map of rumi_covis.h)
  *   Tracking::SearchLocalPoints      R/lib_src/Tracking.cc:2996-3055
  * in ONE call: the frame's key-points, descriptors, grid and map-point vector (mvpMapPoints) stay in HBM between the five stages; the host
  * stages its inputs once and reads the results once (plus three 16-byte-to-4-KB reads where the reference's control flow needs a number:

@@ -122,6 +122,8 @@ KFDB_SYMBOLS = ["rumi_kfdb_create", "rumi_kfdb_destroy", "rumi_kfdb_clear", "rum
                 "rumi_kfdb_set_bad", "rumi_kfdb_set_covisibles", "rumi_kfdb_score", "rumi_kfdb_scored", "rumi_kfdb_select_reloc", "rumi_kfdb_select_nbest"]
 MAPPING_SYMBOLS = ["rumi_create_new_map_points", "rumi_refresh_create", "rumi_refresh_destroy", "rumi_refresh_map_points", "rumi_refresh_stage_ms",
                    "rumi_cull_create", "rumi_cull_destroy", "rumi_keyframe_culling", "rumi_cull_stage_ms"]
+COVIS_SYMBOLS = ["rumi_covis_create", "rumi_covis_destroy", "rumi_covis_set_keyframes", "rumi_covis_set_points", "rumi_covis_set_bad", "rumi_covis_set_maps",
+                 "rumi_covis_update_connections", "rumi_covis_local_map", "rumi_covis_stage_ms", "rumi_covis_stats"]
 KFD_SYMBOLS = ["rumi_kfd_create", "rumi_kfd_destroy", "rumi_kfd_set_pd", "rumi_kfd_reset", "rumi_kfd_step", "rumi_kfd_track"]
 
 
@@ -175,6 +177,27 @@ def kfdb_lib():
     L.rumi_kfdb_select_reloc.argtypes = [vp, vp, vp, i64]
     L.rumi_kfdb_select_nbest.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L._kfdb_ready = True
+    return L
+
+
+def covis_lib():
+    """The covisibility store's entries (include/rumi_covis.h) with their argument types."""
+    L = lib()
+    if getattr(L, "_covis_ready", False):
+        return L
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.rumi_covis_create.argtypes = [i32, i32, i64, i32, C.POINTER(vp)]
+    L.rumi_covis_destroy.argtypes = [vp]
+    L.rumi_covis_destroy.restype = None
+    L.rumi_covis_set_keyframes.argtypes = [vp, i32] + [vp] * 10
+    L.rumi_covis_set_points.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.rumi_covis_set_bad.argtypes = [vp, i32, vp, vp, i32, vp, vp]
+    L.rumi_covis_set_maps.argtypes = [vp, i32, vp, vp]
+    L.rumi_covis_update_connections.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64]
+    L.rumi_covis_local_map.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]
+    L.rumi_covis_stage_ms.argtypes = [vp, vp]
+    L.rumi_covis_stats.argtypes = [vp, vp]
+    L._covis_ready = True
     return L
 
 

@@ -1,0 +1,810 @@
+// The covisibility store (include/rumi_covis.h): KeyFrame::UpdateConnections for a batch of key-frames (R/lib_src/KeyFrame.cc:487-574) and
+// Tracking::UpdateLocalKeyFrames + UpdateLocalPoints for one frame (R/lib_src/Tracking.cc:3067-3210), over tables that stay on the device.
+//
+// Resident state, all of it 32-bit words so that one scatter kernel applies every staged edit:
+//   kf     [max_kf][20]     mp row (offset, length), children row (offset, length), flags (bit 0 bad, bit 1 live), map, parent, -, order_key
+//                           (two words), best[10]
+//   pt     [max_points][4]  observer row (offset, length), bad, -
+//   arena                   every row: mp rows, children rows, observer rows.  A row that outgrows its place moves to the tail; a full arena is
+//                           rebuilt on the host (compacted, and doubled when the live rows fill more than three quarters of it) and sent whole.
+//   tag    [max_points]     64-bit stamps of the local-point selection, (call epoch << 32) | priority
+// The host keeps a mirror of the three tables; an edit writes the mirror and notes (table, offset, words).  The next query packs the noted
+// ranges and its own input into one pinned block, sends it with one copy, and k_covis_apply scatters it.
+//
+//   k_covis_count<false>  a workgroup per batch key-frame: a lane per feature slot walks its point's observer row and counts into a histogram
+//                         over slots in LDS (32-bit atomics); the non-zero slots are compacted by ballot + popcount, sorted by order_key
+//                         (bitonic, slots in LDS, keys read through the cache) and written as KFcounter; the entries under the threshold are
+//                         then replaced by a sentinel and the same array sorted by (weight, key) descending.
+//   k_covis_count<true>   the vote of UpdateLocalKeyFrames: the same kernel with one row (the frame's points) and the observer filters off;
+//                         its first wave then walks the expansion loop (:3148-3188) over an included-bitset in LDS.
+//   k_covis_local<1,2,3>  UpdateLocalPoints over (rank from the end, feature) candidates: a 64-bit atomicMax of the candidate's priority on
+//                         tag[point], the count of the winners per workgroup, and their write at the prefix offsets.
+// Integer arithmetic only; no float atomics, and every sum is independent of arrival order.
+#include <climits>
+#include <cstring>
+#include <unordered_map>
+#include <vector>
+
+#include "rumi_common.h"
+#include "rumi_covis.h"
+
+namespace rumi {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int KFW = 20, PTW = 4;                       // words per key-frame / point record
+constexpr int K_MPOFF = 0, K_MPLEN = 1, K_CHOFF = 2, K_CHLEN = 3, K_FLAGS = 4, K_MAP = 5, K_PARENT = 6, K_KEY = 8, K_BEST = 10;
+constexpr int T_KF = 0, T_PT = 1, T_ARENA = 2;
+constexpr uint16_t kNone = 0xFFFF;                     // sorts last; slots stay below RUMI_COVIS_MAX_KEYFRAMES
+constexpr int kPosBits = 13;
+static_assert((1 << kPosBits) == RUMI_COVIS_MAX_KEYFRAMES, "position bits of the packed maximum");
+static_assert((int64_t)RUMI_COVIS_MAX_FEATURES << kPosBits < (1ll << 31), "count << 13 | position fits 32 bits");
+static_assert((int64_t)RUMI_COVIS_MAX_KEYFRAMES * RUMI_COVIS_MAX_FEATURES <= (1ll << 32), "rank * features + feature fits 32 bits");
+
+struct CovisTables {
+    const int32_t *kf, *pt, *arena;
+    int hiSlot;                    // highest live slot + 1
+};
+
+struct CountArgs {
+    CovisTables t;
+    const int32_t *rows;           // batch slots [B], or the frame's points [nFrame]
+    int nFrame;
+    // update_connections
+    int4 *head;                    // [B] status, first pair, KFcounter entries, ordered entries
+    int2 *pairs;
+    uint32_t *cursor;
+    uint32_t pairsCap;
+    // local_map
+    int4 *lmHead;                  // K1, local key-frames, reference key-frame, local points
+    uint8_t *outBad;               // [nFrame]
+    int32_t *outKf;                // [hiSlot]
+};
+
+struct LocalArgs {
+    CovisTables t;
+    unsigned long long *tag;
+    int4 *lmHead;
+    const int32_t *outKf;
+    int32_t *counts;               // [gridDim.x * gridDim.y]
+    int32_t *outPts;
+    int ptsCap;
+    uint32_t epoch;
+};
+
+struct ApplyArgs {
+    int32_t *base[3];
+    const int4 *recs;              // table, first word there, first word of the payload, words
+    const int32_t *payload;
+};
+
+__global__ __launch_bounds__(64) void k_covis_apply(ApplyArgs a) {
+    const int4 r = a.recs[blockIdx.x];
+    int32_t *dst = a.base[r.x] + r.y;
+    const int32_t *src = a.payload + r.z;
+    for (int i = threadIdx.x; i < r.w; i += 64) dst[i] = src[i];
+}
+
+__device__ __forceinline__ uint64_t key_of(const int32_t *kf, int s) { return *reinterpret_cast<const uint64_t *>(kf + s * KFW + K_KEY); }
+
+template <class Before> __device__ __forceinline__ void bitonic_sort(uint16_t *a, int npad, int tid, Before before) {
+    for (int k = 2; k <= npad; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < npad; i += kThreads) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const uint16_t x = a[i], y = a[l];
+                    if ((i & k) == 0 ? before(y, x) : before(x, y)) { a[i] = y; a[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+template <bool VOTE> __global__ __launch_bounds__(kThreads) void k_covis_count(CountArgs a) {
+    __shared__ uint32_t sHist[RUMI_COVIS_MAX_KEYFRAMES];
+    __shared__ uint16_t sIdx[RUMI_COVIS_MAX_KEYFRAMES];
+    __shared__ uint32_t sIncl[RUMI_COVIS_MAX_KEYFRAMES / 32];
+    __shared__ int sN, sOrd;
+    __shared__ uint32_t sMax, sStart;
+    const int tid = threadIdx.x, b = blockIdx.x, hi = a.t.hiSlot;
+    const int32_t *kf = a.t.kf, *arena = a.t.arena;
+    for (int s = tid; s < hi; s += kThreads) sHist[s] = 0;
+    if (VOTE) for (int w = tid; w < RUMI_COVIS_MAX_KEYFRAMES / 32; w += kThreads) sIncl[w] = 0;
+    if (tid == 0) { sN = 0; sOrd = 0; sMax = 0; }
+    __syncthreads();
+
+    // ---- the histogram: KFcounter[observer]++ (KeyFrame.cc:500-514), keyframeCounter[observer]++ (Tracking.cc:3093-3105)
+    int self = -1, myMap = 0, rowLen;
+    const int32_t *row;
+    if (VOTE) { row = a.rows; rowLen = a.nFrame; }
+    else {
+        self = a.rows[b];
+        const int32_t *K = kf + self * KFW;
+        row = arena + K[K_MPOFF]; rowLen = K[K_MPLEN]; myMap = K[K_MAP];
+    }
+    for (int i = tid; i < rowLen; i += kThreads) {
+        const int p = row[i];
+        int bad = 0;
+        if (p >= 0) {
+            const int4 P = *reinterpret_cast<const int4 *>(a.t.pt + p * PTW);
+            if (P.z & 1) bad = 1;
+            else
+                for (int o = P.x, e = P.x + P.y; o < e; o++) {
+                    const int k = arena[o];
+                    if (!VOTE) {
+                        if (k == self) continue;
+                        const int32_t *O = kf + k * KFW;
+                        if ((O[K_FLAGS] & 1) || O[K_MAP] != myMap) continue;
+                    }
+                    atomicAdd(&sHist[k], 1u);
+                }
+        }
+        if (VOTE) a.outBad[i] = (uint8_t)bad;
+    }
+    __syncthreads();
+
+    // ---- the counted slots, compacted (the vote drops bad key-frames here: :3135)
+    for (int base = 0; base < hi; base += kThreads) {
+        const int s = base + tid;
+        bool nz = s < hi && sHist[s] > 0;
+        if (VOTE && nz) nz = !(kf[s * KFW + K_FLAGS] & 1);
+        const unsigned long long mask = __ballot(nz);
+        int wbase = 0;
+        if ((tid & 63) == 0 && mask) wbase = atomicAdd(&sN, __popcll(mask));
+        wbase = __shfl(wbase, 0);
+        if (nz) sIdx[wbase + __popcll(mask & ((1ull << (tid & 63)) - 1ull))] = (uint16_t)s;
+    }
+    __syncthreads();
+    const int n = sN;
+    if (n == 0) {                                                    // KeyFrame.cc:519; an empty keyframeCounter
+        if (tid == 0) {
+            if (VOTE) *a.lmHead = make_int4(0, 0, -1, 0);
+            else a.head[b] = make_int4(RUMI_COVIS_EMPTY, 0, 0, 0);
+        }
+        return;
+    }
+    int npad = 1;
+    while (npad < n) npad <<= 1;
+    for (int i = n + tid; i < npad; i += kThreads) sIdx[i] = kNone;
+    __syncthreads();
+    bitonic_sort(sIdx, npad, tid, [&](uint16_t x, uint16_t y) { return x != kNone && (y == kNone || key_of(kf, x) < key_of(kf, y)); });
+
+    // ---- the first entry in key order with a strictly greater count (:529-532, :3137-3140), and how many reach the threshold
+    for (int i = tid; i < n; i += kThreads) {
+        const uint32_t c = sHist[sIdx[i]];
+        atomicMax(&sMax, (c << kPosBits) | (uint32_t)(RUMI_COVIS_MAX_KEYFRAMES - 1 - i));
+        if (!VOTE && c >= RUMI_COVIS_TH) atomicAdd(&sOrd, 1);
+    }
+    __syncthreads();
+    const int nmax = (int)(sMax >> kPosBits), slotMax = sIdx[RUMI_COVIS_MAX_KEYFRAMES - 1 - (int)(sMax & (RUMI_COVIS_MAX_KEYFRAMES - 1))];
+
+    if (!VOTE) {
+        const int nOrd = sOrd > 0 ? sOrd : 1;
+        if (tid == 0) sStart = atomicAdd(a.cursor, (uint32_t)(n + nOrd));
+        __syncthreads();
+        const uint32_t start = sStart;
+        if ((uint64_t)start + (uint32_t)(n + nOrd) > a.pairsCap) {   // the host sizes the buffer for the bound; never taken
+            if (tid == 0) a.head[b] = make_int4(-1, 0, 0, 0);
+            return;
+        }
+        for (int i = tid; i < n; i += kThreads) a.pairs[start + i] = make_int2(sIdx[i], (int)sHist[sIdx[i]]);
+        if (sOrd == 0) {
+            if (tid == 0) a.pairs[start + n] = make_int2(slotMax, nmax);                      // :543-547
+        } else {
+            __syncthreads();
+            for (int i = tid; i < n; i += kThreads)
+                if (sHist[sIdx[i]] < RUMI_COVIS_TH) sIdx[i] = kNone;
+            __syncthreads();
+            // sort ascending on (weight, key), then push_front: weight descending, key descending among equal weights (:549-555)
+            bitonic_sort(sIdx, npad, tid, [&](uint16_t x, uint16_t y) {
+                if (x == kNone) return false;
+                if (y == kNone) return true;
+                const uint32_t wx = sHist[x], wy = sHist[y];
+                return wx > wy || (wx == wy && key_of(kf, x) > key_of(kf, y));
+            });
+            for (int i = tid; i < nOrd; i += kThreads) a.pairs[start + n + i] = make_int2(sIdx[i], (int)sHist[sIdx[i]]);
+        }
+        if (tid == 0) a.head[b] = make_int4(RUMI_COVIS_CONNECTED, (int)start, n, nOrd);
+        return;
+    }
+
+    // ---- the expansion (Tracking.cc:3148-3188): one wave, the included set as bits in LDS, the list in sIdx behind K1
+    for (int i = tid; i < n; i += kThreads) atomicOr(&sIncl[sIdx[i] >> 5], 1u << (sIdx[i] & 31));
+    __syncthreads();
+    if (tid >= 64) return;
+    const int lane = tid;
+    int size = n;
+    auto included = [&](int s) { return (sIncl[s >> 5] >> (s & 31)) & 1u; };
+    auto is_bad = [&](int s) { return kf[s * KFW + K_FLAGS] & 1; };
+    auto add = [&](int s) {                                          // uniform over the wave
+        if (lane == 0) { sIdx[size] = (uint16_t)s; sIncl[s >> 5] |= 1u << (s & 31); }
+        size++;
+        __threadfence_block();
+    };
+    for (int m = 0; m < n; m++) {                                    // the end iterator is K1's (:3148)
+        if (size > RUMI_COVIS_LOCAL_LIMIT) break;                    // :3150
+        const int32_t *K = kf + (int)sIdx[m] * KFW;
+        const int bs = lane < RUMI_COVIS_NBEST ? K[K_BEST + lane] : -1;
+        const unsigned long long okBest = __ballot(bs >= 0 && !is_bad(bs) && !included(bs));
+        if (okBest) add(__shfl(bs, __ffsll((long long)okBest) - 1)); // :3157-3166: the first that is not bad and not included
+        uint64_t bestKey = 0;
+        int bestSlot = -1;
+        for (int j = lane, e = K[K_CHLEN]; j < e; j += 64) {         // :3168-3178: the first child in key order
+            const int c = arena[K[K_CHOFF] + j];
+            if (is_bad(c) || included(c)) continue;
+            const uint64_t key = key_of(kf, c);
+            if (bestSlot < 0 || key < bestKey) { bestKey = key; bestSlot = c; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t lo = __shfl_xor((uint32_t)bestKey, o), hi32 = __shfl_xor((uint32_t)(bestKey >> 32), o);
+            const int os = __shfl_xor(bestSlot, o);
+            const uint64_t ok = ((uint64_t)hi32 << 32) | lo;
+            if (os >= 0 && (bestSlot < 0 || ok < bestKey)) { bestKey = ok; bestSlot = os; }
+        }
+        if (bestSlot >= 0) add(bestSlot);
+        const int par = K[K_PARENT];
+        if (par >= 0 && !included(par)) { add(par); break; }        // :3180-3187: the break leaves the loop; isBad() is not asked
+    }
+    for (int i = lane; i < size; i += 64) a.outKf[i] = sIdx[i];
+    if (lane == 0) *a.lmHead = make_int4(n, size, slotMax, 0);
+}
+
+// UpdateLocalPoints (:3067-3087).  Workgroup (r, y): features y * 256 .. of the key-frame r places from the end of the list.
+template <int PASS> __global__ __launch_bounds__(kThreads) void k_covis_local(LocalArgs a) {
+    __shared__ int sWave[kThreads / 64];
+    __shared__ int sPrefix;
+    const int tid = threadIdx.x, r = blockIdx.x, nLocal = a.lmHead->y;
+    if (r >= nLocal) return;
+    const int32_t *K = a.t.kf + a.outKf[nLocal - 1 - r] * KFW;
+    const int i = (int)blockIdx.y * kThreads + tid;
+    int p = -1;
+    if (i < K[K_MPLEN]) {
+        p = a.t.arena[K[K_MPOFF] + i];
+        if (p >= 0 && (a.t.pt[p * PTW + 2] & 1)) p = -1;
+    }
+    const unsigned long long value = ((unsigned long long)a.epoch << 32) | (0xFFFFFFFFu - ((uint32_t)r * RUMI_COVIS_MAX_FEATURES + (uint32_t)i));
+    if (PASS == 1) {
+        if (p >= 0) atomicMax(&a.tag[p], value);
+        return;
+    }
+    const bool win = p >= 0 && a.tag[p] == value;
+    const unsigned long long mask = __ballot(win);
+    if ((tid & 63) == 0) sWave[tid >> 6] = __popcll(mask);
+    const int blk = r * (int)gridDim.y + (int)blockIdx.y;
+    if (PASS == 3 && tid == 0) sPrefix = 0;
+    __syncthreads();
+    if (PASS == 2) {
+        if (tid == 0) a.counts[blk] = sWave[0] + sWave[1] + sWave[2] + sWave[3];
+        return;
+    }
+    int part = 0;
+    for (int j = tid; j < blk; j += kThreads) part += a.counts[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+    if ((tid & 63) == 0 && part) atomicAdd(&sPrefix, part);
+    __syncthreads();
+    int off = sPrefix;
+    for (int w = 0; w < (tid >> 6); w++) off += sWave[w];
+    off += __popcll(mask & ((1ull << (tid & 63)) - 1ull));
+    if (win && off < a.ptsCap) a.outPts[off] = p;
+    if (tid == 0 && r == nLocal - 1 && blockIdx.y == gridDim.y - 1) a.lmHead->w = sPrefix + sWave[0] + sWave[1] + sWave[2] + sWave[3];
+}
+
+}  // namespace
+}  // namespace rumi
+
+using namespace rumi;
+
+struct RumiCovis {
+    int device = -1;
+    bool bound = false;
+    int32_t maxKf = 0, maxPts = 0;
+    // host mirrors of the device tables
+    std::vector<int32_t> kf, pt, arena;
+    std::vector<int32_t> capMp, capCh, capObs;       // places of the rows in the arena (entries); 0 = never placed
+    int64_t tail = 0, live = 0;
+    int64_t replaced = 0, compactions = 0, growths = 0, lastUpload = 0;
+    std::unordered_map<uint64_t, int32_t> keyToSlot;
+    int32_t nLive = 0, hiSlot = 0, maxRow = 0;
+    std::vector<int32_t> kfStamp, ptStamp;           // validation marks
+    int32_t stampKf = 0, stampPt = 0;
+    // staged edits
+    std::vector<int4> recs;                          // table, first word, -, words
+    bool full[3] = {true, true, true};
+    // device
+    int32_t *dKf = nullptr, *dPt = nullptr, *dArena = nullptr;
+    size_t dArenaCap = 0;
+    unsigned long long *dTag = nullptr;
+    uint32_t epoch = 0;
+    uint8_t *hStage = nullptr, *dStage = nullptr; size_t stageCap = 0;
+    uint8_t *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;
+    float stageMs[3] = {0.f, 0.f, 0.f};
+};
+
+namespace {
+
+inline int32_t row_cap(int32_t n) { return n + (n >> 2) + 2; }
+inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+void note(RumiCovis *h, int table, int64_t off, int64_t words) {
+    if (words > 0 && !h->full[table]) h->recs.push_back(make_int4(table, (int)off, 0, (int)words));
+}
+
+// Rebuilds the arena with every row at cap(len): in place when the rows and `need` more entries fill at most three quarters, else doubled.
+void rebuild_arena(RumiCovis *h, int64_t need) {
+    int64_t total = 0;
+    for (int s = 0; s < h->hiSlot; s++) {
+        if (h->capMp[s]) total += row_cap(h->kf[(size_t)s * KFW + K_MPLEN]);
+        if (h->capCh[s]) total += row_cap(h->kf[(size_t)s * KFW + K_CHLEN]);
+    }
+    for (int p = 0; p < h->maxPts; p++)
+        if (h->capObs[p]) total += row_cap(h->pt[(size_t)p * PTW + 1]);
+    size_t cap = h->arena.size();
+    if ((total + need) * 4 > (int64_t)cap * 3) {
+        while ((total + need) * 4 > (int64_t)cap * 3) cap *= 2;
+        h->growths++;
+    } else h->compactions++;
+    std::vector<int32_t> nv(cap, 0);
+    int64_t t = 0;
+    auto move = [&](int32_t &off, int32_t len, int32_t &c) {
+        if (!c) return;
+        if (len > 0) std::memcpy(nv.data() + t, h->arena.data() + off, (size_t)len * 4);
+        off = (int32_t)t; c = row_cap(len); t += c;
+    };
+    for (int s = 0; s < h->hiSlot; s++) {
+        int32_t *K = h->kf.data() + (size_t)s * KFW;
+        move(K[K_MPOFF], K[K_MPLEN], h->capMp[s]);
+        move(K[K_CHOFF], K[K_CHLEN], h->capCh[s]);
+    }
+    for (int p = 0; p < h->maxPts; p++) move(h->pt[(size_t)p * PTW], h->pt[(size_t)p * PTW + 1], h->capObs[p]);
+    h->arena.swap(nv);
+    h->tail = h->live = t;
+    h->full[T_KF] = h->full[T_PT] = h->full[T_ARENA] = true;
+    h->recs.clear();
+}
+
+// Row (off, len) of place c takes src[0 .. n): in place when it fits, else at the tail.
+void set_row(RumiCovis *h, int32_t &off, int32_t &len, int32_t &c, const int32_t *src, int32_t n) {
+    if (n > c) {
+        const int32_t nc = row_cap(n);
+        if (h->tail + nc > (int64_t)h->arena.size()) rebuild_arena(h, nc);     // moves this row too, with its old contents
+        if (n > c) {
+            if (c) h->replaced++;
+            h->live += nc - c;
+            off = (int32_t)h->tail; h->tail += nc; c = nc;
+        }
+    }
+    len = n;
+    if (n > 0) std::memcpy(h->arena.data() + off, src, (size_t)n * 4);
+    note(h, T_ARENA, off, n);
+}
+
+int bind_device(RumiCovis *h) {
+    if (h->bound) return hipSetDevice(h->device) == hipSuccess ? RUMI_OK : RUMI_E_NO_DEVICE;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        g_lastError = "no HIP device visible: librumi_hip has no CPU fallback";
+        return RUMI_E_NO_DEVICE;
+    }
+    if (h->device < 0 && hipGetDevice(&h->device) != hipSuccess) h->device = 0;
+    HIP_TRY(hipSetDevice(h->device));
+    int rc;
+    if ((rc = dev_alloc(&h->dKf, (size_t)h->maxKf * KFW)) != RUMI_OK || (rc = dev_alloc(&h->dPt, (size_t)h->maxPts * PTW)) != RUMI_OK ||
+        (rc = dev_alloc(&h->dTag, (size_t)h->maxPts)) != RUMI_OK)
+        return rc;
+    HIP_TRY(hipMemsetAsync(h->dTag, 0, (size_t)h->maxPts * 8, nullptr));
+    h->bound = true;
+    return RUMI_OK;
+}
+
+// Sends the staged edits and `extra` (the query's input) in one block; *dExtra is where the input lies on the device.
+int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) {
+    int rc;
+    if ((rc = bind_device(h)) != RUMI_OK) return rc;
+    if (h->recs.size() > (1u << 16)) { h->full[0] = h->full[1] = h->full[2] = true; }
+    if (h->arena.size() > h->dArenaCap) {
+        h->dArenaCap = 0;
+        if ((rc = regrow(&h->dArena, h->arena.size() * 4, false)) != RUMI_OK) return rc;
+        h->dArenaCap = h->arena.size();
+        h->full[T_ARENA] = true;
+    }
+    int32_t *dBase[3] = {h->dKf, h->dPt, h->dArena};
+    const std::vector<int32_t> *mirror[3] = {&h->kf, &h->pt, &h->arena};
+    size_t words = 0, nRec = 0;
+    for (int4 &r : h->recs)
+        if (!h->full[r.x]) { r.z = (int)words; words += (size_t)r.w; h->recs[nRec++] = r; }
+    h->recs.resize(nRec);
+    const size_t offPay = up16(nRec * 16), offExtra = offPay + up16(words * 4), bytes = offExtra + up16(extraBytes);
+    if (bytes > h->stageCap) {
+        const size_t want = bytes + bytes / 4 + 4096;
+        h->stageCap = 0;
+        if ((rc = regrow(&h->hStage, want, true)) != RUMI_OK || (rc = regrow(&h->dStage, want, false)) != RUMI_OK) return rc;
+        h->stageCap = want;
+    }
+    h->lastUpload = (int64_t)bytes;
+    for (int t = 0; t < 3; t++)
+        if (h->full[t]) {
+            const size_t n = t == T_ARENA ? (size_t)h->tail : mirror[t]->size();
+            if (n) HIP_TRY(hipMemcpyAsync(dBase[t], mirror[t]->data(), n * 4, hipMemcpyHostToDevice, nullptr));
+            h->lastUpload += (int64_t)n * 4;
+        }
+    if (nRec) std::memcpy(h->hStage, h->recs.data(), nRec * 16);
+    int32_t *pay = reinterpret_cast<int32_t *>(h->hStage + offPay);
+    for (const int4 &r : h->recs) std::memcpy(pay + r.z, mirror[r.x]->data() + r.y, (size_t)r.w * 4);
+    if (extraBytes) std::memcpy(h->hStage + offExtra, extra, extraBytes);
+    if (bytes) HIP_TRY(hipMemcpyAsync(h->dStage, h->hStage, bytes, hipMemcpyHostToDevice, nullptr));
+    if (nRec) {
+        ApplyArgs a;
+        for (int t = 0; t < 3; t++) a.base[t] = dBase[t];
+        a.recs = reinterpret_cast<const int4 *>(h->dStage);
+        a.payload = reinterpret_cast<const int32_t *>(h->dStage + offPay);
+        hipLaunchKernelGGL(k_covis_apply, dim3((unsigned)nRec), dim3(64), 0, nullptr, a);
+    }
+    h->recs.clear();
+    h->full[0] = h->full[1] = h->full[2] = false;
+    *dExtra = h->dStage + offExtra;
+    return RUMI_OK;
+}
+
+int grow_out(RumiCovis *h, size_t bytes) {
+    if (bytes <= h->outCap) return RUMI_OK;
+    int rc;
+    const size_t want = bytes + bytes / 4;
+    h->outCap = 0;
+    if ((rc = regrow(&h->hOut, want, true)) != RUMI_OK || (rc = regrow(&h->dOut, want, false)) != RUMI_OK) return rc;
+    h->outCap = want;
+    return RUMI_OK;
+}
+
+inline bool is_live(const RumiCovis *h, int32_t s) { return s >= 0 && s < h->maxKf && (h->kf[(size_t)s * KFW + K_FLAGS] & 2); }
+
+void set_ms(RumiCovis *h, std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1, std::chrono::steady_clock::time_point t2) {
+    const auto t3 = std::chrono::steady_clock::now();
+    h->stageMs[0] = std::chrono::duration<float, std::milli>(t1 - t0).count();
+    h->stageMs[1] = std::chrono::duration<float, std::milli>(t2 - t1).count();
+    h->stageMs[2] = std::chrono::duration<float, std::milli>(t3 - t2).count();
+}
+
+}  // namespace
+
+extern "C" int rumi_covis_create(int32_t max_kf, int32_t max_points, int64_t arena_entries, int32_t device, RumiCovis **out) {
+    if (!out || max_kf <= 0 || max_points <= 0 || arena_entries < 0 || arena_entries > (1ll << 30) || max_points > (1 << 28)) {
+        g_lastError = "rumi_covis_create: missing handle pointer or a size outside its range";
+        return RUMI_E_INVALID;
+    }
+    if (max_kf > RUMI_COVIS_MAX_KEYFRAMES) {
+        g_lastError = "rumi_covis_create: more than RUMI_COVIS_MAX_KEYFRAMES slots (one LDS counter each)";
+        return RUMI_E_CAPACITY;
+    }
+    RumiCovis *h = new RumiCovis();
+    h->device = device; h->maxKf = max_kf; h->maxPts = max_points;
+    h->kf.assign((size_t)max_kf * KFW, 0);
+    h->pt.assign((size_t)max_points * PTW, 0);
+    h->arena.assign(arena_entries ? (size_t)std::max<int64_t>(arena_entries, 16) : (size_t)1 << 20, 0);
+    h->capMp.assign(max_kf, 0); h->capCh.assign(max_kf, 0); h->capObs.assign(max_points, 0);
+    h->kfStamp.assign(max_kf, 0); h->ptStamp.assign(max_points, 0);
+    for (int s = 0; s < max_kf; s++) {
+        int32_t *K = h->kf.data() + (size_t)s * KFW;
+        K[K_PARENT] = -1;
+        for (int j = 0; j < RUMI_COVIS_NBEST; j++) K[K_BEST + j] = -1;
+    }
+    *out = h;
+    return RUMI_OK;
+}
+
+extern "C" void rumi_covis_destroy(RumiCovis *h) {
+    if (!h) return;
+    if (h->bound) (void)hipSetDevice(h->device);
+    if (h->hStage) (void)hipHostFree(h->hStage);
+    if (h->hOut) (void)hipHostFree(h->hOut);
+    for (void *p : {(void *)h->dKf, (void *)h->dPt, (void *)h->dArena, (void *)h->dTag, (void *)h->dStage, (void *)h->dOut})
+        if (p) (void)hipFree(p);
+    delete h;
+}
+
+extern "C" int rumi_covis_set_keyframes(RumiCovis *h, int32_t n, const int32_t *slots, const uint64_t *order_keys, const int32_t *map_ids,
+                                        const uint8_t *is_bad, const int32_t *mp_off, const int32_t *mp, const int32_t *best,
+                                        const int32_t *parent, const int32_t *child_off, const int32_t *children) {
+    if (!h || n < 0 || (n > 0 && (!slots || !order_keys || !map_ids || !is_bad || !mp_off || !best || !parent || !child_off))) {
+        g_lastError = "rumi_covis_set_keyframes: missing argument or negative count";
+        return RUMI_E_INVALID;
+    }
+    if (n == 0) return RUMI_OK;
+    // ---- validation, all of it before anything is staged
+    if (h->stampKf > INT32_MAX - 4) { std::fill(h->kfStamp.begin(), h->kfStamp.end(), 0); h->stampKf = 0; }
+    const int32_t inCall = ++h->stampKf;
+    for (int i = 0; i < n; i++) {
+        if (slots[i] < 0 || slots[i] >= h->maxKf || h->kfStamp[slots[i]] == inCall) {
+            g_lastError = "rumi_covis_set_keyframes: a slot outside 0..max_kf-1, or named twice";
+            return RUMI_E_INVALID;
+        }
+        h->kfStamp[slots[i]] = inCall;
+    }
+    {
+        std::unordered_map<uint64_t, int32_t> seen;
+        for (int i = 0; i < n; i++) {
+            const auto it = h->keyToSlot.find(order_keys[i]);
+            if (!seen.emplace(order_keys[i], slots[i]).second || (it != h->keyToSlot.end() && h->kfStamp[it->second] != inCall)) {
+                g_lastError = "rumi_covis_set_keyframes: an order_key that another live slot holds";
+                return RUMI_E_INVALID;
+            }
+        }
+    }
+    auto known = [&](int32_t s) { return s >= 0 && s < h->maxKf && (h->kfStamp[s] == inCall || (h->kf[(size_t)s * KFW + K_FLAGS] & 2)); };
+    if (mp_off[0] < 0 || child_off[0] < 0) { g_lastError = "rumi_covis_set_keyframes: a negative offset"; return RUMI_E_INVALID; }
+    int64_t need = 0;
+    for (int i = 0; i < n; i++) {
+        const int64_t nm = (int64_t)mp_off[i + 1] - mp_off[i], nc = (int64_t)child_off[i + 1] - child_off[i];
+        if (nm < 0 || nc < 0 || nm > RUMI_COVIS_MAX_FEATURES || nc > h->maxKf || (nm > 0 && !mp) || (nc > 0 && !children)) {
+            g_lastError = "rumi_covis_set_keyframes: a row slice that runs backwards, is longer than its limit, or has no array";
+            return RUMI_E_INVALID;
+        }
+        need += row_cap((int32_t)nm) + row_cap((int32_t)nc);
+        for (int64_t j = mp_off[i]; j < mp_off[i + 1]; j++)
+            if (mp[j] < -1 || mp[j] >= h->maxPts) { g_lastError = "rumi_covis_set_keyframes: an mp entry outside -1..max_points-1"; return RUMI_E_INVALID; }
+        for (int j = 0; j < RUMI_COVIS_NBEST; j++) {
+            const int32_t b = best[(size_t)i * RUMI_COVIS_NBEST + j];
+            if (b != -1 && !known(b)) { g_lastError = "rumi_covis_set_keyframes: a best entry that is neither -1 nor a live slot"; return RUMI_E_INVALID; }
+        }
+        if (parent[i] != -1 && (!known(parent[i]) || parent[i] == slots[i])) {
+            g_lastError = "rumi_covis_set_keyframes: a parent that is neither -1 nor another live slot";
+            return RUMI_E_INVALID;
+        }
+    }
+    {   // children: distinct live slots, never the key-frame itself
+        std::vector<int32_t> mark(h->maxKf, -1);
+        for (int i = 0; i < n; i++)
+            for (int64_t j = child_off[i]; j < child_off[i + 1]; j++) {
+                const int32_t c = children[j];
+                if (!known(c) || c == slots[i] || mark[c] == i) {
+                    g_lastError = "rumi_covis_set_keyframes: a child that is not a live slot, is the key-frame itself, or is listed twice";
+                    return RUMI_E_INVALID;
+                }
+                mark[c] = i;
+            }
+    }
+    if (h->live + need > (1ll << 29)) { g_lastError = "rumi_covis_set_keyframes: the row arena would pass 2^29 entries"; return RUMI_E_CAPACITY; }
+    // ---- apply to the mirror, note what changed
+    for (int i = 0; i < n; i++) {
+        const int32_t *K = h->kf.data() + (size_t)slots[i] * KFW;
+        if (K[K_FLAGS] & 2) { uint64_t old; std::memcpy(&old, K + K_KEY, 8); h->keyToSlot.erase(old); }
+    }
+    for (int i = 0; i < n; i++) {
+        const int32_t s = slots[i];
+        int32_t *K = h->kf.data() + (size_t)s * KFW;
+        if (!(K[K_FLAGS] & 2)) { h->nLive++; h->hiSlot = std::max(h->hiSlot, s + 1); }
+        K[K_FLAGS] = 2 | (is_bad[i] ? 1 : 0);
+        const int32_t nm = mp_off[i + 1] - mp_off[i], nc = child_off[i + 1] - child_off[i];
+        // set_row works on the mirror's own words: a rebuild of the arena rewrites the offsets there
+        set_row(h, K[K_MPOFF], K[K_MPLEN], h->capMp[s], nm ? mp + mp_off[i] : nullptr, nm);
+        set_row(h, K[K_CHOFF], K[K_CHLEN], h->capCh[s], nc ? children + child_off[i] : nullptr, nc);
+        K[K_MAP] = map_ids[i];
+        K[K_PARENT] = parent[i];
+        std::memcpy(K + K_KEY, &order_keys[i], 8);
+        std::memcpy(K + K_BEST, best + (size_t)i * RUMI_COVIS_NBEST, RUMI_COVIS_NBEST * 4);
+        h->keyToSlot[order_keys[i]] = s;
+        h->maxRow = std::max(h->maxRow, nm);
+        note(h, T_KF, (int64_t)s * KFW, KFW);
+    }
+    return RUMI_OK;
+}
+
+extern "C" int rumi_covis_set_points(RumiCovis *h, int32_t n, const int32_t *ids, const uint8_t *is_bad, const int32_t *obs_off, const int32_t *obs) {
+    if (!h || n < 0 || (n > 0 && (!ids || !is_bad || !obs_off))) {
+        g_lastError = "rumi_covis_set_points: missing argument or negative count";
+        return RUMI_E_INVALID;
+    }
+    if (n == 0) return RUMI_OK;
+    if (h->stampPt > INT32_MAX - 4) { std::fill(h->ptStamp.begin(), h->ptStamp.end(), 0); h->stampPt = 0; }
+    const int32_t inCall = ++h->stampPt;
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= h->maxPts || h->ptStamp[ids[i]] == inCall) {
+            g_lastError = "rumi_covis_set_points: a point id outside 0..max_points-1, or named twice";
+            return RUMI_E_INVALID;
+        }
+        h->ptStamp[ids[i]] = inCall;
+    }
+    if (obs_off[0] < 0) { g_lastError = "rumi_covis_set_points: a negative offset"; return RUMI_E_INVALID; }
+    int64_t need = 0;
+    std::vector<int32_t> mark(h->maxKf, -1);
+    for (int i = 0; i < n; i++) {
+        const int64_t no = (int64_t)obs_off[i + 1] - obs_off[i];
+        if (no < 0 || no > h->maxKf || (no > 0 && !obs)) {
+            g_lastError = "rumi_covis_set_points: an observer slice that runs backwards, is longer than max_kf, or has no array";
+            return RUMI_E_INVALID;
+        }
+        need += row_cap((int32_t)no);
+        for (int64_t j = obs_off[i]; j < obs_off[i + 1]; j++) {
+            if (!is_live(h, obs[j]) || mark[obs[j]] == i) {
+                g_lastError = "rumi_covis_set_points: an observer that is not a live slot, or is listed twice";
+                return RUMI_E_INVALID;
+            }
+            mark[obs[j]] = i;
+        }
+    }
+    if (h->live + need > (1ll << 29)) { g_lastError = "rumi_covis_set_points: the row arena would pass 2^29 entries"; return RUMI_E_CAPACITY; }
+    for (int i = 0; i < n; i++) {
+        const int32_t p = ids[i], no = obs_off[i + 1] - obs_off[i];
+        set_row(h, h->pt[(size_t)p * PTW], h->pt[(size_t)p * PTW + 1], h->capObs[p], no ? obs + obs_off[i] : nullptr, no);
+        h->pt[(size_t)p * PTW + 2] = is_bad[i] ? 1 : 0;
+        note(h, T_PT, (int64_t)p * PTW, PTW);
+    }
+    return RUMI_OK;
+}
+
+extern "C" int rumi_covis_set_bad(RumiCovis *h, int32_t n_kf, const int32_t *slots, const uint8_t *kf_bad, int32_t n_pt, const int32_t *ids,
+                                  const uint8_t *pt_bad) {
+    if (!h || n_kf < 0 || n_pt < 0 || (n_kf > 0 && (!slots || !kf_bad)) || (n_pt > 0 && (!ids || !pt_bad))) {
+        g_lastError = "rumi_covis_set_bad: missing argument or negative count";
+        return RUMI_E_INVALID;
+    }
+    for (int i = 0; i < n_kf; i++)
+        if (!is_live(h, slots[i])) { g_lastError = "rumi_covis_set_bad: a key-frame slot that is not live"; return RUMI_E_INVALID; }
+    for (int i = 0; i < n_pt; i++)
+        if (ids[i] < 0 || ids[i] >= h->maxPts) { g_lastError = "rumi_covis_set_bad: a point id outside 0..max_points-1"; return RUMI_E_INVALID; }
+    for (int i = 0; i < n_kf; i++) {
+        h->kf[(size_t)slots[i] * KFW + K_FLAGS] = 2 | (kf_bad[i] ? 1 : 0);
+        note(h, T_KF, (int64_t)slots[i] * KFW + K_FLAGS, 1);
+    }
+    for (int i = 0; i < n_pt; i++) {
+        h->pt[(size_t)ids[i] * PTW + 2] = pt_bad[i] ? 1 : 0;
+        note(h, T_PT, (int64_t)ids[i] * PTW + 2, 1);
+    }
+    return RUMI_OK;
+}
+
+extern "C" int rumi_covis_set_maps(RumiCovis *h, int32_t n, const int32_t *slots, const int32_t *map_ids) {
+    if (!h || n < 0 || (n > 0 && (!slots || !map_ids))) {
+        g_lastError = "rumi_covis_set_maps: missing argument or negative count";
+        return RUMI_E_INVALID;
+    }
+    for (int i = 0; i < n; i++)
+        if (!is_live(h, slots[i])) { g_lastError = "rumi_covis_set_maps: a key-frame slot that is not live"; return RUMI_E_INVALID; }
+    for (int i = 0; i < n; i++) {
+        h->kf[(size_t)slots[i] * KFW + K_MAP] = map_ids[i];
+        note(h, T_KF, (int64_t)slots[i] * KFW + K_MAP, 1);
+    }
+    return RUMI_OK;
+}
+
+extern "C" int rumi_covis_update_connections(RumiCovis *h, int32_t B, const int32_t *batch, int32_t *status, int32_t *conn_off, int32_t *conn_slot,
+                                             int32_t *conn_count, int64_t conn_cap, int32_t *ord_off, int32_t *ord_slot, int32_t *ord_weight,
+                                             int64_t ord_cap) {
+    if (!h || B < 0 || conn_cap < 0 || ord_cap < 0 || !conn_off || !ord_off || (B > 0 && (!batch || !status)) ||
+        (conn_cap > 0 && (!conn_slot || !conn_count)) || (ord_cap > 0 && (!ord_slot || !ord_weight))) {
+        g_lastError = "rumi_covis_update_connections: missing argument or negative count";
+        return RUMI_E_INVALID;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int b = 0; b < B; b++)
+        if (!is_live(h, batch[b])) { g_lastError = "rumi_covis_update_connections: a batch entry that is not a live slot"; return RUMI_E_INVALID; }
+    if (B == 0) { conn_off[0] = ord_off[0] = 0; return RUMI_OK; }
+    const uint64_t pairsCap = (uint64_t)B * 2u * (uint64_t)h->nLive;            // KFcounter and the ordered list hold at most every live slot
+    if (pairsCap * 8 > (1ull << 30)) {
+        g_lastError = "rumi_covis_update_connections: the batch times the live key-frames passes the result buffer (1 GiB); split the batch";
+        return RUMI_E_CAPACITY;
+    }
+    int rc;
+    uint8_t *dBatch = nullptr;
+    if ((rc = flush(h, batch, (size_t)B * 4, &dBatch)) != RUMI_OK) return rc;
+    const size_t offHead = 16, offPairs = offHead + (size_t)B * 16, outBytes = offPairs + (size_t)pairsCap * 8;
+    if ((rc = grow_out(h, outBytes)) != RUMI_OK) return rc;
+    const auto t1 = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemsetAsync(h->dOut, 0, 16, nullptr));
+    CountArgs a{};
+    a.t = CovisTables{h->dKf, h->dPt, h->dArena, h->hiSlot};
+    a.rows = reinterpret_cast<const int32_t *>(dBatch);
+    a.head = reinterpret_cast<int4 *>(h->dOut + offHead);
+    a.pairs = reinterpret_cast<int2 *>(h->dOut + offPairs);
+    a.cursor = reinterpret_cast<uint32_t *>(h->dOut);
+    a.pairsCap = (uint32_t)pairsCap;
+    hipLaunchKernelGGL(k_covis_count<false>, dim3(B), dim3(kThreads), 0, nullptr, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(h->hOut, h->dOut, offPairs, hipMemcpyDeviceToHost));
+    const uint32_t used = *reinterpret_cast<const uint32_t *>(h->hOut);
+    const int4 *head = reinterpret_cast<const int4 *>(h->hOut + offHead);
+    int64_t nConn = 0, nOrd = 0;
+    for (int b = 0; b < B; b++) {
+        if (head[b].x < 0 || used > pairsCap) { g_lastError = "rumi_covis_update_connections: the result buffer overflowed (internal error)"; return RUMI_E_INVALID; }
+        nConn += head[b].z; nOrd += head[b].w;
+    }
+    if (nConn > conn_cap || nOrd > ord_cap || nConn > INT32_MAX) {
+        g_lastError = "rumi_covis_update_connections: conn_cap or ord_cap is too small for the lists";
+        return RUMI_E_CAPACITY;
+    }
+    if (used) HIP_TRY(hipMemcpy(h->hOut + offPairs, h->dOut + offPairs, (size_t)used * 8, hipMemcpyDeviceToHost));
+    const auto t2 = std::chrono::steady_clock::now();
+    const int2 *pairs = reinterpret_cast<const int2 *>(h->hOut + offPairs);
+    int32_t co = 0, oo = 0;
+    for (int b = 0; b < B; b++) {
+        status[b] = head[b].x;
+        conn_off[b] = co; ord_off[b] = oo;
+        const int2 *src = pairs + head[b].y;
+        for (int i = 0; i < head[b].z; i++) { conn_slot[co] = src[i].x; conn_count[co++] = src[i].y; }
+        src += head[b].z;
+        for (int i = 0; i < head[b].w; i++) { ord_slot[oo] = src[i].x; ord_weight[oo++] = src[i].y; }
+    }
+    conn_off[B] = co; ord_off[B] = oo;
+    set_ms(h, t0, t1, t2);
+    return RUMI_OK;
+}
+
+extern "C" int rumi_covis_local_map(RumiCovis *h, int32_t n, const int32_t *frame_points, uint8_t *frame_point_bad, int32_t *local_kf, int32_t kf_cap,
+                                    int32_t *n_k1, int32_t *n_local_kf, int32_t *ref_kf, int32_t *local_points, int32_t pt_cap,
+                                    int32_t *n_local_points) {
+    if (!h || n < 0 || n > RUMI_COVIS_MAX_FEATURES || kf_cap < 0 || pt_cap < 0 || !n_k1 || !n_local_kf || !ref_kf || !n_local_points ||
+        (n > 0 && (!frame_points || !frame_point_bad)) || (kf_cap > 0 && !local_kf) || (pt_cap > 0 && !local_points)) {
+        g_lastError = "rumi_covis_local_map: missing argument, negative count, or more than RUMI_COVIS_MAX_FEATURES frame points";
+        return RUMI_E_INVALID;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < n; i++)
+        if (frame_points[i] < -1 || frame_points[i] >= h->maxPts) {
+            g_lastError = "rumi_covis_local_map: a frame point outside -1..max_points-1";
+            return RUMI_E_INVALID;
+        }
+    int rc;
+    uint8_t *dFrame = nullptr;
+    if ((rc = flush(h, frame_points, (size_t)n * 4, &dFrame)) != RUMI_OK) return rc;
+    const int gx = h->nLive, gy = (h->maxRow + kThreads - 1) / kThreads;
+    const size_t offBad = 16, offKf = offBad + up16((size_t)n), offCounts = offKf + up16((size_t)h->hiSlot * 4),
+                 offPts = offCounts + up16((size_t)gx * gy * 4), outBytes = offPts + (size_t)h->maxPts * 4;
+    if ((rc = grow_out(h, outBytes)) != RUMI_OK) return rc;
+    if (++h->epoch == 0) {                                           // once every 2^32 calls: stale tags could meet a reused epoch
+        HIP_TRY(hipMemsetAsync(h->dTag, 0, (size_t)h->maxPts * 8, nullptr));
+        h->epoch = 1;
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    CountArgs a{};
+    a.t = CovisTables{h->dKf, h->dPt, h->dArena, h->hiSlot};
+    a.rows = reinterpret_cast<const int32_t *>(dFrame);
+    a.nFrame = n;
+    a.lmHead = reinterpret_cast<int4 *>(h->dOut);
+    a.outBad = h->dOut + offBad;
+    a.outKf = reinterpret_cast<int32_t *>(h->dOut + offKf);
+    hipLaunchKernelGGL(k_covis_count<true>, dim3(1), dim3(kThreads), 0, nullptr, a);
+    if (gx > 0 && gy > 0) {
+        LocalArgs l{};
+        l.t = a.t;
+        l.tag = h->dTag;
+        l.lmHead = a.lmHead;
+        l.outKf = a.outKf;
+        l.counts = reinterpret_cast<int32_t *>(h->dOut + offCounts);
+        l.outPts = reinterpret_cast<int32_t *>(h->dOut + offPts);
+        l.ptsCap = h->maxPts;
+        l.epoch = h->epoch;
+        hipLaunchKernelGGL(k_covis_local<1>, dim3(gx, gy), dim3(kThreads), 0, nullptr, l);
+        hipLaunchKernelGGL(k_covis_local<2>, dim3(gx, gy), dim3(kThreads), 0, nullptr, l);
+        hipLaunchKernelGGL(k_covis_local<3>, dim3(gx, gy), dim3(kThreads), 0, nullptr, l);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(h->hOut, h->dOut, offCounts, hipMemcpyDeviceToHost));
+    const int4 head = *reinterpret_cast<const int4 *>(h->hOut);
+    if (head.y > kf_cap || head.w > pt_cap) {
+        g_lastError = "rumi_covis_local_map: kf_cap or pt_cap is too small for the lists";
+        return RUMI_E_CAPACITY;
+    }
+    if (head.w > 0) HIP_TRY(hipMemcpy(h->hOut + offPts, h->dOut + offPts, (size_t)head.w * 4, hipMemcpyDeviceToHost));
+    const auto t2 = std::chrono::steady_clock::now();
+    if (n > 0) std::memcpy(frame_point_bad, h->hOut + offBad, (size_t)n);
+    if (head.y > 0) std::memcpy(local_kf, h->hOut + offKf, (size_t)head.y * 4);
+    if (head.w > 0) std::memcpy(local_points, h->hOut + offPts, (size_t)head.w * 4);
+    *n_k1 = head.x; *n_local_kf = head.y; *ref_kf = head.z; *n_local_points = head.w;
+    set_ms(h, t0, t1, t2);
+    return RUMI_OK;
+}
+
+extern "C" int rumi_covis_stage_ms(const RumiCovis *h, float *out3) {
+    if (!h || !out3) return RUMI_E_INVALID;
+    std::memcpy(out3, h->stageMs, sizeof h->stageMs);
+    return RUMI_OK;
+}
+
+extern "C" int rumi_covis_stats(const RumiCovis *h, int64_t *out7) {
+    if (!h || !out7) return RUMI_E_INVALID;
+    const int64_t v[7] = {(int64_t)h->arena.size(), h->tail, h->live, h->replaced, h->compactions, h->growths, h->lastUpload};
+    std::memcpy(out7, v, sizeof v);
+    return RUMI_OK;
+}
