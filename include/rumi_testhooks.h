@@ -29,6 +29,12 @@ float rumi_hook_fast_atan2(float y, float x);   /* cv::fastAtan2, degrees */
 int rumi_hook_cv_round(float v);         /* cvRound */
 int rumi_hook_magic_div(int32_t idx, int32_t d);   /* divide-free idx / d used by the FAST cell kernel (orb_geom.h) */
 
+/* IC_Angle (ORBextractor.cc:73-97) as k_disc_angle computes it: rows = 31 rows of 36 bytes of the level from (x - 15) & ~3 on, so column u = -15 of
+ * the disc sits in byte s = (x - 15) & 3 = 0..3 of a row; the kernel's two lanes of a row load the 2 x 16 bytes from there.  umax16 = the
+ * extractor's umax table.  m01 / m10: the moments, by the kernel's own chunk function (orb_math.h) summed over the rows.  W / M (31 x 8 dwords
+ * each, may be null): the per-row weight and mask vectors the launch code builds from umax16 (orb_geom.h). */
+int rumi_hook_disc_moments(const uint8_t *rows, int32_t s, const int32_t *umax16, int32_t *m01, int32_t *m10, uint32_t *W, uint32_t *M);
+
 /* Lane packing of the batch launches (orb_geom.h: LanePack / lane_slot, the code the kernels and the launch wrappers use): for a w x h frame,
  * the pyramid rule (scale, nlevels) and a launch of nframes frames, the mapping of every lane of kernel 0 = the resize launch that writes `level`
  * (1 .. nlevels - 1) or kernel 1 = the batch blur's part for `level` (0 .. nlevels - 1).  force_g = 0: the frames per group the launch code

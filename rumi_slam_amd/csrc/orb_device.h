@@ -59,9 +59,16 @@ bool launch_fast_blur(const DevParams *dP, const DevParams &hP, ImgSrc src, uint
 void launch_compact(const DevParams *dP, const DevParams &hP, const uint32_t *cellBuf, const int32_t *cellCnt,
                     uint32_t *cand, int32_t *levelStart, int32_t *errFlag, int nframes, hipStream_t st);
 void launch_blur(const DevParams *dP, const DevParams &hP, ImgSrc src, int nframes, int variant, hipStream_t st);
+// Batches take IC_Angle and the trigonometry in a kernel of their own (launch_disc_angle) and the descriptor kernel without them; every call the
+// fused kernel fills the device with keeps it.  THE rule, asked once per sub-chunk by the scheduler.
+inline bool orient_desc_split(int maxSel, int nframes) { return (long long)((maxSel + 7) / 8) * nframes > 2048; }
+// trig: null = the fused kernel; else the {angle, cos, sin, 0} array (indexed like selMeta) launch_disc_angle has filled on the same stream
 void launch_orient_desc(const DevParams *dP, ImgSrc src, const uint32_t *selPacked, const uint32_t *selMeta,
                         const int32_t *selCount, int selCap, int maxSel, RumiKeyPoint *kpOut, long long kpStride, uint8_t *descOut,
-                        long long descStride, int outCap, int nframes, hipStream_t st);   // strides: bytes from one frame's outputs to the next
+                        long long descStride, int outCap, int nframes, hipStream_t st, const float4 *trig);   // strides: bytes from one frame's outputs to the next
+// discVec: make_disc_vectors' table on the device.  Reads the un-blurred levels only.
+void launch_disc_angle(const DevParams *dP, ImgSrc src, const uint32_t *selPacked, const uint32_t *selMeta, const int32_t *selCount, int selCap,
+                       int maxSel, const uint32_t *discVec, float4 *trig, int nframes, hipStream_t st);
 
 void launch_assemble_orient_desc(const DevParams *dP, ImgSrc src, const uint32_t *selLevel, const int32_t *selLevelCnt, int selLevelCap, int lap0, int lap1,
                                  int32_t *counts, long long countsStride, int32_t *errFlag, int32_t *errMirror, uint32_t *selPacked, uint32_t *selMeta,

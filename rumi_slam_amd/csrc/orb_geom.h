@@ -6,6 +6,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 namespace rumi {
@@ -89,6 +90,22 @@ inline OrbTables make_tables(int nfeatures, float scaleFactorArg, int nlevels) {
         ++v0;
     }
     return t;
+}
+
+// k_disc_angle's constant vectors (disc_chunk_moments, orb_math.h), from the umax table: row v = r - 15 of the disc, r = 0..30, gets 16 dwords
+// at out[16 r]: eight of column weights (byte j = j where |j - 15| <= umax[|v|], else 0), eight of the mask (1 in the same bytes); a row's two lanes
+// take a half of each.  Byte 31 and the whole of row 31 (the lanes left over) are zero.
+constexpr int kDiscVecLanes = 32, kDiscVecLaneDwords = 16;
+inline void make_disc_vectors(const int *umax, uint32_t *out) {
+    std::fill(out, out + kDiscVecLanes * kDiscVecLaneDwords, 0u);
+    for (int r = 0; r < kPatchSize; r++) {
+        const int v = r - kHalfPatch, um = umax[v < 0 ? -v : v];
+        for (int j = 0; j < kPatchSize; j++) {
+            if (std::abs(j - kHalfPatch) > um) continue;
+            out[r * kDiscVecLaneDwords + j / 4] |= (uint32_t)j << (8 * (j % 4));
+            out[r * kDiscVecLaneDwords + 8 + j / 4] |= 1u << (8 * (j % 4));
+        }
+    }
 }
 
 // Level sizes (ComputePyramid :1095-1096) and FAST cell grids (:729-746) for a w x h frame.

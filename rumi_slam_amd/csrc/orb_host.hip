@@ -86,6 +86,8 @@ struct RumiOrb {
     int32_t *dLevelStart = nullptr;
     uint32_t *dSelPacked = nullptr, *dSelMeta = nullptr;   // kChunk frames x capSel
     int32_t *dSelCount = nullptr;
+    float4 *dSelTrig = nullptr;      // kChunk frames x capSel: {angle, cos, sin, 0} of k_disc_angle (batches)
+    uint32_t *dDiscVec = nullptr;    // k_disc_angle's per-row weight and mask vectors (make_disc_vectors of tab.umax)
     uint16_t *dOwner = nullptr;      // kChunk frames x capCand: quadtree node id of every candidate
     uint32_t *dSelLevel = nullptr;   // kChunk frames x nlevels x selLevelCap: quadtree output per level
     int32_t *dSelLevelCnt = nullptr;
@@ -143,14 +145,14 @@ struct RumiOrb {
 // The per-frame device arrays (alloc_frame_arenas sizes them), named once: released and forgotten.
 static void free_frame_arenas(RumiOrb *h) {
     auto drop = [](auto *&...p) { (((p ? (void)hipFree(p) : (void)0), p = nullptr), ...); };
-    drop(h->dPyr, h->dBlur, h->dCellBuf, h->dCellCnt, h->dCand, h->dLevelStart, h->dSelPacked, h->dSelMeta, h->dSelCount, h->dOwner, h->dSelLevel, h->dSelLevelCnt);
+    drop(h->dPyr, h->dBlur, h->dCellBuf, h->dCellCnt, h->dCand, h->dLevelStart, h->dSelPacked, h->dSelMeta, h->dSelTrig, h->dSelCount, h->dOwner, h->dSelLevel, h->dSelLevelCnt);
 }
 
 extern "C" void rumi_orb_destroy(RumiOrb *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->pending) (void)hipStreamSynchronize(h->pendingStream);
-    void *dev[] = {h->dP, h->dCoef, h->dRowTab, h->dPyrTiles, h->dIn, h->dL0, h->dErr};
+    void *dev[] = {h->dP, h->dCoef, h->dRowTab, h->dPyrTiles, h->dIn, h->dL0, h->dErr, h->dDiscVec};
     for (void *p : dev) if (p) (void)hipFree(p);
     free_frame_arenas(h);
     void *pin[] = {h->hErr};
@@ -190,6 +192,7 @@ static int alloc_frame_arenas(RumiOrb *h, size_t scratch, size_t arena) {
     TRY_A(dev_alloc(&h->dLevelStart, C * (kMaxLevels + 1)));
     TRY_A(dev_alloc(&h->dSelPacked, C * h->capSel));
     TRY_A(dev_alloc(&h->dSelMeta, C * h->capSel));
+    TRY_A(dev_alloc(&h->dSelTrig, C * h->capSel));
     TRY_A(dev_alloc(&h->dSelCount, C));
     TRY_A(dev_alloc(&h->dOwner, C * h->capCand));
     TRY_A(dev_alloc(&h->dSelLevel, C * h->cfg.nlevels * h->selLevelCap));
@@ -256,6 +259,12 @@ extern "C" int rumi_orb_create(const RumiOrbConfig *cfg, RumiOrb **out) {
         rumi_orb_destroy(h); g_lastError = "pinned staging"; return RUMI_E_NO_DEVICE;
     }
     TRY_ALLOC(dev_alloc(&h->dErr, 1));
+    {
+        uint32_t vec[kDiscVecLanes * kDiscVecLaneDwords];
+        make_disc_vectors(h->tab.umax.data(), vec);
+        TRY_ALLOC(dev_alloc(&h->dDiscVec, sizeof vec / sizeof vec[0]));
+        if (hipMemcpy(h->dDiscVec, vec, sizeof vec, hipMemcpyHostToDevice) != hipSuccess) { rumi_orb_destroy(h); g_lastError = "disc vectors"; return RUMI_E_NO_DEVICE; }
+    }
     TRY_ALLOC(pin_alloc(&h->hErr, 1));
     if (hipHostGetDevicePointer((void **)&h->dhOut1, h->hOut1, 0) != hipSuccess || hipHostGetDevicePointer((void **)&h->dhErr, h->hErr, 0) != hipSuccess) {
         (void)hipGetLastError();

@@ -8,6 +8,7 @@
 //   k_compact       concatenation of the cell results in cell order      R/lib_src/ORBextractor.cc:796-803
 //   k_blur          cv::GaussianBlur 7x7 sigma 2, REFLECT_101             R/lib_src/ORBextractor.cc:1057-1058
 //   k_orient_desc   IC_Angle + computeOrbDescriptor + output assembly    R/lib_src/ORBextractor.cc:73-143,1067-1088
+//   k_disc_angle    IC_Angle and the angle's cos / sin for batches         R/lib_src/ORBextractor.cc:73-97,101-104
 //
 // One translation unit (the library is built without relocatable device code, so a kernel is launched from the unit that defines it).  This file
 // holds what the parts share -- the rBRIEF pattern, xcd_swizzle, U32 / U64, level_base, reflect101, pack_span -- and includes the kernels by job,
@@ -17,7 +18,7 @@
 //   orb_fast.inc         FastLds, quick test, exact score, ring, k_fast_cells, k_compact; fast_lds_of, launch_fast, launch_compact
 //   orb_blur.inc         BlurGrid / BlurPack, blur_body, k_blur, k_blur_packed, k_fast_blur; the grid builders, launch_blur, launch_fast_blur,
 //                        fast_blur_fusable
-//   orb_orient_desc.inc  k_orient_desc (AssembleArgs); launch_orient_desc, launch_assemble_orient_desc
+//   orb_orient_desc.inc  k_orient_desc (AssembleArgs), k_disc_angle; launch_orient_desc, launch_disc_angle, launch_assemble_orient_desc
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -91,4 +91,29 @@ RUMI_HD float eval(float y, int isCos) {
 RUMI_HD float sinf_glibc(float x) { return sincosf_impl::eval(x, 0); }
 RUMI_HD float cosf_glibc(float x) { return sincosf_impl::eval(x, 1); }
 
+// ---- IC_Angle (ORBextractor.cc:73-97) by rows: the two moments' share of one 16-byte half of ONE row v of the radius-15 disc ----
+// acc + the dot product of the four unsigned bytes of a and b (v_dot4_u32_u8)
+RUMI_HD uint32_t dot4_u8(uint32_t a, uint32_t b, uint32_t acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_udot4(a, b, acc, false);
+#else
+    for (int i = 0; i < 4; i++) acc += ((a >> (8 * i)) & 0xFF) * ((b >> (8 * i)) & 0xFF);
+    return acc;
+#endif
+}
+constexpr int kDiscChunkDwords = 4, kDiscRowChunks = 2;
+// d: 16 bytes of row v, columns u = -15 .. 0 (chunk 0) or 1 .. 16 (chunk 1), read from x - 15 on.  W / M (make_disc_vectors, orb_geom.h): the chunk's
+// four dwords of the row's vectors, whose byte u + 15 holds u + 15 / 1 where |u| <= umax[|v|], else 0 (byte 31, u = 16: 0).  With S = sum of the
+// chunk's pixels inside the disc and Wt = sum of (u + 15) * pixel: m10 += Wt - 15 S, m01 += v S.  Integers throughout: Wt <= 16 * 30 * 255.
+RUMI_HD void disc_chunk_moments(const uint32_t *d, const uint32_t *W, const uint32_t *M, int v, int &m01, int &m10) {
+    uint32_t S = 0, Wt = 0;
+#pragma unroll
+    for (int i = 0; i < kDiscChunkDwords; i++) {
+        S = dot4_u8(d[i], M[i], S);
+        Wt = dot4_u8(d[i], W[i], Wt);
+    }
+    m10 = (int)Wt - 15 * (int)S;
+    m01 = v * (int)S;
+}
+
 }  // namespace rumi

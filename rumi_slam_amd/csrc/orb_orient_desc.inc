@@ -1,10 +1,13 @@
-// Orientation, rBRIEF and output assembly: k_orient_desc (with k_assemble's work in its prologue for calls of a few frames) and its launch wrappers.
+// Orientation, rBRIEF and output assembly: k_orient_desc (with k_assemble's work in its prologue for calls of a few frames), the two kernels batches
+// take instead (k_disc_angle: IC_Angle and the trigonometry, a key-point per lane; k_orient_desc<2, false, true>: rBRIEF and the output) and the
+// launch wrappers.
 namespace rumi {
 
 // ------------------------------------------------------------------------------------------------
 // Orientation + descriptor + output assembly: one HALF wave (32 lanes) per selected key-point, eight key-points per workgroup.
 //   The arithmetic that is the same for every lane of a key-point (fastAtan2, the libm sinf / cosf restatement in double precision, the
-//   record) is a third of the kernel: with two key-points per wave an instruction serves both.
+//   record) is a third of the fused kernel: with two key-points per wave an instruction serves both.  Batches (orient_desc_split) leave it and
+//   IC_Angle to k_disc_angle, where a lane IS a key-point for it, and run the descriptor part alone (kSplit).
 //   IC_Angle: integer moments over the radius-15 disc of the UN-blurred level, lane = disc column;
 //   rBRIEF:   lane l evaluates test pairs l, l+32, ... l+224; __ballot packs 32 bits per key-point at a time, which
 //             is exactly the descriptor's little-endian bit order (bit k of byte i = pair 8i+k).
@@ -28,7 +31,8 @@ __device__ __forceinline__ int wave_sum(int v) {
 
 constexpr int kDiscP = 48, kPatchP = 48;       // LDS row pitches: 36 and 40 staged bytes per row (31 / 37 + alignment slack), rows 16-byte aligned for b128 stores
 constexpr int kKpPerWg = 8;                    // half waves of a workgroup
-// kKpGroups: key-points a half wave handles one after the other (the next one's pixels are in flight meanwhile).  Two for batches: with four,
+constexpr int kPatchRows = 37, kPatchRowPieces = 5, kPatchTrips = (kPatchRows * kPatchRowPieces + 31) / 32;   // the patch as 8-byte pieces: 185 in six trips of a half wave
+// kKpGroups: key-points a half wave handles one after the other (the next one's pixels are in flight meanwhile).  Two for batches (kSplit): with four,
 // the workgroups resident on an XCD span five frames instead of two and a half, their pyramids no longer fit its L2 and the kernel fetches
 // 1.7x the bytes (FETCH_SIZE).  One for a handful of frames: there are not enough workgroups to fill the chip otherwise.
 
@@ -41,13 +45,15 @@ struct AssembleArgs {
     int32_t *counts; long long countsStride; int32_t *errFlag, *errMirror;
     uint32_t *selPackedOut, *selMetaOut; int32_t *selCountOut;      // k_assemble's arrays are still written (the parity taps read them)
 };
-template <int kKpGroups, bool kAssemble>
-__global__ __launch_bounds__(256, 7) void k_orient_desc(const DevParams *__restrict__ P, ImgSrc src,
+// kSplit (batches): the angle and its cosine / sine come from k_disc_angle's array (indexed like selMeta); no disc is fetched or staged here.
+template <int kKpGroups, bool kAssemble, bool kSplit>
+__global__ __launch_bounds__(256, kSplit ? 8 : 7) void k_orient_desc(const DevParams *__restrict__ P, ImgSrc src,
                                                      const uint32_t *__restrict__ selPacked,
                                                      const uint32_t *__restrict__ selMeta,
                                                      const int32_t *__restrict__ selCount, int selCap,
                                                      RumiKeyPoint *__restrict__ kpOut, long long kpStride, uint8_t *__restrict__ descOut,
-                                                     long long descStride, int outCap, AssembleArgs A) {
+                                                     long long descStride, int outCap, AssembleArgs A, const float4 *__restrict__ trig) {
+    static_assert(!(kSplit && kAssemble), "the split form reads k_assemble's arrays");
     // per key-point: the 31-row disc neighbourhood of the un-blurred level, THEN (in the same LDS: the moments are done with the disc before the
     // descriptor wants the patch) the 37-row patch of the blurred level, staged by the half wave that owns the key-point and read by nobody else:
     // no workgroup barrier anywhere past the pattern table's.  18 KB per workgroup: seven workgroups per CU (30 KB with both resident: five)
@@ -149,7 +155,15 @@ __global__ __launch_bounds__(256, 7) void k_orient_desc(const DevParams *__restr
     struct __attribute__((packed, aligned(4))) Q8 { uint32_t x, y; };
     auto ld16 = [](const uint8_t *q) { const Q16 t = *reinterpret_cast<const Q16 *>(q); return make_uint4(t.x, t.y, t.z, t.w); };
     auto ld8 = [](const uint8_t *q) { const Q8 t = *reinterpret_cast<const Q8 *>(q); return make_uint2(t.x, t.y); };
-    struct Staged { uint4 d0, d1, p0, p1, q0, q1; uint2 p2, q2; uint32_t d2; };
+    struct Staged { uint4 d0, d1, p0, p1, q0, q1; uint2 p2, q2; uint32_t d2; uint2 c[kPatchTrips]; };
+    // kSplit: the patch by 8-byte pieces, five a row, piece q = lane + 32 t of the half wave in trip t: the pieces of a row sit in neighbouring
+    // lanes of ONE load instruction, which then asks for six or seven cache lines instead of a line per lane (0.105 -> 0.096 ms per 256 frames
+    // against the row form in this kernel).  The same bytes as the row form's, to the same LDS addresses.
+    int pcRow[kPatchTrips], pcCol[kPatchTrips];
+    if constexpr (kSplit) {
+#pragma unroll
+        for (int t = 0; t < kPatchTrips; t++) { const int q = lane + 32 * t; pcRow[t] = q / kPatchRowPieces; pcCol[t] = (q % kPatchRowPieces) * 8; }
+    }
     const bool dRow = lane < 31, qRow = lane < 5;
     const uint8_t *frame0 = src.l0 + (long long)frame * src.l0FrameStride, *framePyr = src.pyr + (long long)frame * P->arenaStride,
                   *frameBlur = src.blur + (long long)frame * P->arenaStride;
@@ -166,6 +180,13 @@ __global__ __launch_bounds__(256, 7) void k_orient_desc(const DevParams *__restr
         if (!live) return;
         const int level = meta & 0xFF, x = (int)(pk & 0xFFF) + kBorder, y = (int)((pk >> 12) & 0xFFF) + kBorder;
         const int4 lv = sLv[level];
+        if constexpr (kSplit) {
+            const uint8_t *b0 = frameBlur + (lv.z + (y - 18) * lv.w + ((x - 18) & ~3));
+#pragma unroll
+            for (int t = 0; t < kPatchTrips; t++)
+                if (pcRow[t] < kPatchRows) S.c[t] = ld8(b0 + (pcRow[t] * lv.w + pcCol[t]));
+            return;
+        }
         const uint8_t *br = frameBlur + (lv.z + (y - 18 + lane) * lv.w + ((x - 18) & ~3)), *br2 = br + 32 * lv.w;
         S.p0 = ld16(br); S.p1 = ld16(br + 16); S.p2 = ld8(br + 32);
         if (qRow) { S.q0 = ld16(br2); S.q1 = ld16(br2 + 16); S.q2 = ld8(br2 + 32); }
@@ -177,6 +198,12 @@ __global__ __launch_bounds__(256, 7) void k_orient_desc(const DevParams *__restr
     };
     auto stage_patch = [&](bool live, const Staged &S) {
         if (!live) return;
+        if constexpr (kSplit) {
+#pragma unroll
+            for (int t = 0; t < kPatchTrips; t++)
+                if (pcRow[t] < kPatchRows) *reinterpret_cast<uint2 *>(&sWin[hw][pcRow[t] * kPatchP + pcCol[t]]) = S.c[t];
+            return;
+        }
         {
             uint8_t *dst = &sWin[hw][lane * kPatchP];
             *reinterpret_cast<uint4 *>(dst) = S.p0; *reinterpret_cast<uint4 *>(dst + 16) = S.p1; *reinterpret_cast<uint2 *>(dst + 32) = S.p2;
@@ -210,14 +237,17 @@ __global__ __launch_bounds__(256, 7) void k_orient_desc(const DevParams *__restr
         OD_STAMP(4);
         return fast_atan2_deg((float)m01, (float)m10);
     };
-    auto describe = [&](uint32_t pk, uint32_t meta, float angle) {
+    auto describe = [&](uint32_t pk, uint32_t meta, float angle, float cosA, float sinA) {
         const int level = meta & 0xFF, slot = (int)(meta >> 8);
         const int x = (int)(pk & 0xFFF) + kBorder, y = (int)((pk >> 12) & 0xFFF) + kBorder, score = (int)(pk >> 24);
         const int xp = (x - 18) & ~3;
         // computeOrbDescriptor (ORBextractor.cc:99-143) on the blurred level
-        const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
-        const float ang = angle * factorPI;
-        const float a = cosf_glibc(ang), b = sinf_glibc(ang);
+        float a = cosA, b = sinA;
+        if constexpr (!kSplit) {
+            const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
+            const float ang = angle * factorPI;
+            a = cosf_glibc(ang); b = sinf_glibc(ang);
+        }
         const uint8_t *bc = &sWin[hw][18 * kPatchP + (x - xp)];
         uint32_t w = 0;                                                   // lane j of the half wave ends up with descriptor word j
         OD_STAMP(5);
@@ -253,58 +283,155 @@ __global__ __launch_bounds__(256, 7) void k_orient_desc(const DevParams *__restr
     };
 
     const uint32_t *selP = selPacked + (long long)frame * selCap, *selM = selMeta + (long long)frame * selCap;
-    auto key_rec = [&](int k, uint32_t &pk, uint32_t &mt) {     // key-point k of the frame: from k_assemble's arrays, or from this workgroup's own prologue
+    const float4 *selT = kSplit ? trig + (long long)frame * selCap : nullptr;
+    auto key_rec = [&](int k, uint32_t &pk, uint32_t &mt, float4 &tg) {     // key-point k of the frame: from k_assemble's arrays, or from this workgroup's own prologue
         if constexpr (kAssemble) { const int j = k - (kb - hw); pk = sOwnPk[j]; mt = sOwnMt[j]; }
         else { pk = selP[k]; mt = selM[k]; }
+        if constexpr (kSplit) tg = selT[k];                                 // {angle, cos, sin, 0} of k_disc_angle
     };
     bool liveC = kb < cnt, liveN = kb + kKpPerWg < cnt;
     uint32_t pkC = 0, mtC = 0, pkN = 0, mtN = 0;
-    if (liveC) key_rec(kb, pkC, mtC);
-    if (liveN && kKpGroups > 1) key_rec(kb + kKpPerWg, pkN, mtN);
+    float4 tgC = make_float4(0.f, 0.f, 0.f, 0.f), tgN = tgC;
+    if (liveC) key_rec(kb, pkC, mtC, tgC);
+    if (liveN && kKpGroups > 1) key_rec(kb + kKpPerWg, pkN, mtN, tgN);
     if (kKpGroups == 1) liveN = false;
     Staged S;
-    fetch_disc(pkC, mtC, liveC, S);
+    if constexpr (!kSplit) fetch_disc(pkC, mtC, liveC, S);
     fetch_patch(pkC, mtC, liveC, S);
 #pragma unroll
     for (int g = 0; g < kKpGroups; g++) {
         if (!__any(liveC)) break;                                         // (key-points of a half wave come in ascending k: nothing further)
         OD_STAMP(0);
-        stage_disc(liveC, S);
+        if constexpr (!kSplit) stage_disc(liveC, S);
         OD_STAMP(1);
         // the key-point after this one: its pixels travel while this one is computed (the disc behind this one's disc store, the patch behind
         // this one's patch store: the registers are free then); the one after that: its record
         const int k2 = kb + (g + 2) * kKpPerWg;
         const bool liveNN = g + 2 < kKpGroups && k2 < cnt;
         uint32_t pkNN = 0, mtNN = 0;
-        if (liveNN) key_rec(k2, pkNN, mtNN);
-        if (g + 1 < kKpGroups) fetch_disc(pkN, mtN, liveN, S);
+        float4 tgNN = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (liveNN) key_rec(k2, pkNN, mtNN, tgNN);
+        if constexpr (!kSplit) if (g + 1 < kKpGroups) fetch_disc(pkN, mtN, liveN, S);
         OD_STAMP(2);
-        float angle = 0.f;
-        if (liveC) angle = orientation(pkC);
+        float angle = tgC.x;
+        if constexpr (!kSplit) if (liveC) angle = orientation(pkC);
         stage_patch(liveC, S);                                            // (the same LDS rows: the moments above have read the disc)
         if (g + 1 < kKpGroups) fetch_patch(pkN, mtN, liveN, S);
-        if (liveC) describe(pkC, mtC, angle);
+        if (liveC) describe(pkC, mtC, angle, tgC.y, tgC.z);
         OD_STAMP(3);
-        pkC = pkN; mtC = mtN; liveC = liveN;
-        pkN = pkNN; mtN = mtNN; liveN = liveNN;
+        pkC = pkN; mtC = mtN; tgC = tgN; liveC = liveN;
+        pkN = pkNN; mtN = mtNN; tgN = tgNN; liveN = liveNN;
     }
 #ifdef RUMI_OD_STAMP
     if (threadIdx.x == 0 && (blockIdx.x % 8) == 0 && blockIdx.y == 0) printf("od wg %d: loop-head %lld stage(wait loads) %lld issue-next %lld | IC_Angle %lld trig %lld rBRIEF %lld store %lld\n", (int)blockIdx.x, st[0], st[1], st[2], st[4], st[5], st[6], st[3]);
 #endif
 }
+// ------------------------------------------------------------------------------------------------
+// IC_Angle and the trigonometry of a batch (orient_desc_split): one WAVE per key-point and round, 16 key-points per workgroup in four rounds,
+// then ONE wave with a key-point per lane for fastAtan2 and the sinf / cosf restatement -- the same functions on the same moments as the fused
+// kernel's, so the same bits.
+//   Lanes 2r and 2r + 1 own row v = r - 15 of the disc: ONE 16-byte load each, of columns u = -15..0 and 1..16, straight from x - 15 (no
+//   alignment: bytes inside the fused kernel's 36-byte row from (x - 15) & ~3), a load instruction per key-point and no byte shifts.  The
+//   kernel is bound by what it fetches (a frame's whole un-blurred pyramid, 117 MB per 256 frames), not by its vector instructions (15.6 M):
+//   78 us per 256 frames; with a row per lane and the fused kernel's three loads a row, one round in flight and 64 key-points a workgroup it
+//   took 87 us (profiles/orient_split_*).
+//   The bytes stay in registers: disc_chunk_moments (orb_math.h) takes the masked sum and the column-weighted one with v_dot4_u32_u8 against
+//   the lane's two constant vectors.  The disc is symmetric (|u| <= umax[|v|]  <=>  |v| <= umax[|u|]), so the row formulation sums the same
+//   pixels as the fused kernel's column one.  The bytes of the next three rounds are requested before this round's arithmetic.  Reads only the
+//   un-blurred levels: it runs before the blur joins.
+// ------------------------------------------------------------------------------------------------
+// sum over the 64 lanes of a wave: half_wave_sum's DPP adds, then row_bcast:31 carries the lower half's total into the upper one
+__device__ __forceinline__ int wave_sum_dpp(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);          // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);          // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);          // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);          // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);          // row_bcast:15 -> rows 1 and 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);          // row_bcast:31 -> rows 2 and 3
+    return __builtin_amdgcn_readlane(v, 63);
+}
+// 16 key-points a workgroup, as in the descriptor kernel: with 64 the workgroups resident on an XCD span fifteen frames instead of four, their
+// pyramids no longer fit its L2 and the kernel fetches 194 MB per 256 frames (FETCH_SIZE) where the descriptor kernel fetches 122 MB
+constexpr int kAngleKpPerWg = 16, kAngleWaves = 4, kAngleRounds = kAngleKpPerWg / kAngleWaves, kAngleAhead = 3;
+__global__ __launch_bounds__(256) void k_disc_angle(const DevParams *__restrict__ P, ImgSrc src, const uint32_t *__restrict__ selPacked,
+                                                    const uint32_t *__restrict__ selMeta, const int32_t *__restrict__ selCount, int selCap,
+                                                    const uint4 *__restrict__ discVec, float4 *__restrict__ trig) {
+    __shared__ int2 sLv[kMaxLevels];              // per level: offset and pitch of the un-blurred image (level 0 = the caller's frame)
+    __shared__ int2 sMom[kAngleKpPerWg];          // {m01, m10} of the workgroup's key-points
+    if (threadIdx.x < (unsigned)P->nlevels) {
+        const DevLevel &Lv = P->lv[threadIdx.x];
+        sLv[threadIdx.x] = threadIdx.x == 0 ? make_int2(0, src.l0Pitch) : make_int2((int)Lv.off, Lv.pitch);
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned wg = xcd_swizzle(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);   // a frame's key-points share one L2
+    const int kbase = (wg % gridDim.x) * kAngleKpPerWg, frame = wg / gridDim.x;
+    const int cnt = selCount[frame];
+    if (kbase >= cnt) return;                                             // (the whole workgroup)
+    __syncthreads();
+    // lanes 62 and 63 are left over: they repeat row 15's loads with the zero vectors of table row 31
+    const int r = lane >> 1, chunk = lane & 1, row = r < kPatchSize ? r : kPatchSize - 1;
+    const uint4 w = discVec[r * 4 + chunk], m = discVec[r * 4 + kDiscRowChunks + chunk];
+    const uint32_t W[kDiscChunkDwords] = {w.x, w.y, w.z, w.w}, M[kDiscChunkDwords] = {m.x, m.y, m.z, m.w};   // column weights u + 15 and the 0 / 1 mask, both inside the disc only
+    struct __attribute__((packed)) Q16 { uint32_t x, y, z, w; };          // (a 16-byte load at any byte address)
+    struct Chunk { uint32_t d[kDiscChunkDwords]; };
+    const uint8_t *frame0 = src.l0 + (long long)frame * src.l0FrameStride, *framePyr = src.pyr + (long long)frame * P->arenaStride;
+    const uint32_t *selP = selPacked + (long long)frame * selCap, *selM = selMeta + (long long)frame * selCap;
+    // the records of the wave's four key-points in one load (lane j: round j's), so that no round's pixel load waits for a record load
+    uint32_t pkL = 0, mtL = 0;
+    if (lane < kAngleRounds && kbase + lane * kAngleWaves + wv < cnt) { pkL = selP[kbase + lane * kAngleWaves + wv]; mtL = selM[kbase + lane * kAngleWaves + wv]; }
+    auto fetch = [&](int rd, Chunk &R) {                                  // (rd: a constant after unrolling; the record is wave-uniform)
+        if (kbase + rd * kAngleWaves + wv >= cnt) return;
+        const uint32_t pk = (uint32_t)__builtin_amdgcn_readlane((int)pkL, rd), meta = (uint32_t)__builtin_amdgcn_readlane((int)mtL, rd);
+        const int level = meta & 0xFF, x = (int)(pk & 0xFFF) + kBorder, y = (int)((pk >> 12) & 0xFFF) + kBorder;
+        const int2 lv = sLv[level];                                       // (a frame's arena is far below 2 GB: 32-bit offsets)
+        const uint8_t *cr = (level == 0 ? frame0 : framePyr) + (lv.x + (y - kHalfPatch + row) * lv.y + (x - kHalfPatch) + 16 * chunk);
+        const Q16 t = *reinterpret_cast<const Q16 *>(cr);
+        R.d[0] = t.x; R.d[1] = t.y; R.d[2] = t.z; R.d[3] = t.w;
+    };
+    Chunk B[kAngleAhead + 1] = {};                                        // kAngleAhead rounds' bytes in flight behind the one being summed
+#pragma unroll
+    for (int rd = 0; rd < kAngleAhead; rd++) fetch(rd, B[rd]);
+#pragma unroll
+    for (int rd = 0; rd < kAngleRounds; rd++) {
+        if (kbase + rd * kAngleWaves >= cnt) break;                       // (key-points come in ascending k: nothing further for the workgroup)
+        if (rd + kAngleAhead < kAngleRounds) fetch(rd + kAngleAhead, B[(rd + kAngleAhead) % (kAngleAhead + 1)]);
+        int m01, m10;
+        disc_chunk_moments(B[rd % (kAngleAhead + 1)].d, W, M, r - kHalfPatch, m01, m10);
+        m10 = wave_sum_dpp(m10);
+        m01 = wave_sum_dpp(m01);
+        if (lane == 0) sMom[rd * kAngleWaves + wv] = make_int2(m01, m10);
+    }
+    __syncthreads();
+    const int k = kbase + (int)threadIdx.x;
+    if (threadIdx.x < kAngleKpPerWg && k < cnt) {                         // wave 0: a key-point per lane
+        const int2 mo = sMom[threadIdx.x];
+        const float angle = fast_atan2_deg((float)mo.x, (float)mo.y);
+        const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
+        const float ang = angle * factorPI;
+        trig[(long long)frame * selCap + k] = make_float4(angle, cosf_glibc(ang), sinf_glibc(ang), 0.f);
+    }
+}
 // ---- launch wrappers (called from orb_schedule.inc) ----
+// trig: null = the fused kernel (the caller guarantees ceil(maxSel / 8) * nframes <= 2048 workgroups: !orient_desc_split), else the array
+// launch_disc_angle has filled on the same stream
 void launch_orient_desc(const DevParams *dP, ImgSrc src, const uint32_t *selPacked, const uint32_t *selMeta,
                         const int32_t *selCount, int selCap, int maxSel, RumiKeyPoint *kpOut, long long kpStride, uint8_t *descOut,
-                        long long descStride, int outCap, int nframes, hipStream_t st) {
+                        long long descStride, int outCap, int nframes, hipStream_t st, const float4 *trig) {
     if (maxSel <= 0) return;
     const int wg1 = (maxSel + kKpPerWg - 1) / kKpPerWg;
     const AssembleArgs none{};
-    if ((long long)wg1 * nframes <= 2048)
-        hipLaunchKernelGGL((k_orient_desc<1, false>), dim3(wg1, nframes), dim3(256), 0, st, dP, src, selPacked, selMeta, selCount, selCap, kpOut, kpStride, descOut,
-                           descStride, outCap, none);
+    if (!trig)
+        hipLaunchKernelGGL((k_orient_desc<1, false, false>), dim3(wg1, nframes), dim3(256), 0, st, dP, src, selPacked, selMeta, selCount, selCap, kpOut, kpStride, descOut,
+                           descStride, outCap, none, trig);
     else
-        hipLaunchKernelGGL((k_orient_desc<2, false>), dim3((wg1 + 1) / 2, nframes), dim3(256), 0, st, dP, src, selPacked, selMeta, selCount, selCap, kpOut, kpStride,
-                           descOut, descStride, outCap, none);
+        hipLaunchKernelGGL((k_orient_desc<2, false, true>), dim3((wg1 + 1) / 2, nframes), dim3(256), 0, st, dP, src, selPacked, selMeta, selCount, selCap, kpOut, kpStride,
+                           descOut, descStride, outCap, none, trig);
+}
+void launch_disc_angle(const DevParams *dP, ImgSrc src, const uint32_t *selPacked, const uint32_t *selMeta, const int32_t *selCount, int selCap,
+                       int maxSel, const uint32_t *discVec, float4 *trig, int nframes, hipStream_t st) {
+    if (maxSel <= 0) return;
+    hipLaunchKernelGGL(k_disc_angle, dim3((maxSel + kAngleKpPerWg - 1) / kAngleKpPerWg, nframes), dim3(256), 0, st, dP, src, selPacked, selMeta, selCount, selCap,
+                       reinterpret_cast<const uint4 *>(discVec), trig);
 }
 // k_assemble + k_orient_desc in ONE launch, for calls of a few frames (the caller guarantees (maxSel / 8) * nframes <= 2048 workgroups)
 void launch_assemble_orient_desc(const DevParams *dP, ImgSrc src, const uint32_t *selLevel, const int32_t *selLevelCnt, int selLevelCap, int lap0, int lap1,
@@ -314,8 +441,8 @@ void launch_assemble_orient_desc(const DevParams *dP, ImgSrc src, const uint32_t
     if (maxSel <= 0) return;
     const int wg1 = (maxSel + kKpPerWg - 1) / kKpPerWg;
     const AssembleArgs A{selLevel, selLevelCnt, selLevelCap, lap0, lap1, counts, countsStride, errFlag, nframes == 1 ? errMirror : nullptr, selPacked, selMeta, selCount};
-    hipLaunchKernelGGL((k_orient_desc<1, true>), dim3(wg1, nframes), dim3(256), 0, st, dP, src, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                       (const int32_t *)nullptr, selCap, kpOut, kpStride, descOut, descStride, outCap, A);
+    hipLaunchKernelGGL((k_orient_desc<1, true, false>), dim3(wg1, nframes), dim3(256), 0, st, dP, src, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
+                       (const int32_t *)nullptr, selCap, kpOut, kpStride, descOut, descStride, outCap, A, (const float4 *)nullptr);
 }
 
 }  // namespace rumi

@@ -152,6 +152,9 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
             launch_assemble(h->dP, selLevel, selLevelCnt, h->selLevelCap, lap0, lap1, selPacked, selMeta, h->dSelCount + scr0, h->capSel,
                             countsOut, out.countsStride, h->dErr, n, s, opts.zeroCopyOut ? h->dhErr : nullptr);
         if (timed) HIP_TRY(hipEventRecord(h->ev[6], s));
+        // batches: IC_Angle and the trigonometry in a kernel of their own, BEFORE the join (it reads the un-blurred levels only)
+        float4 *trig = !fuseAssemble && orient_desc_split(h->capSel, n) ? h->dSelTrig + (size_t)scr0 * h->capSel : nullptr;
+        if (trig) launch_disc_angle(h->dP, ps, selPacked, selMeta, h->dSelCount + scr0, h->capSel, h->capSel, h->dDiscVec, trig, n, s);
         if (!fuseBlur) HIP_TRY(hipStreamWaitEvent(s, L.join, 0));   // join: rBRIEF reads the blurred levels
         if (fuseAssemble)
             launch_assemble_orient_desc(h->dP, ps, selLevel, selLevelCnt, h->selLevelCap, lap0, lap1, countsOut, out.countsStride, h->dErr,
@@ -161,7 +164,7 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
         else
         launch_orient_desc(h->dP, ps, selPacked, selMeta, h->dSelCount + scr0, h->capSel, h->capSel,
                            (RumiKeyPoint *)((uint8_t *)d_kp + (size_t)frame0 * out.kpStride), out.kpStride,
-                           (uint8_t *)d_desc + (size_t)frame0 * out.descStride, out.descStride, cap, n, s);
+                           (uint8_t *)d_desc + (size_t)frame0 * out.descStride, out.descStride, cap, n, s, trig);
         if (timed) HIP_TRY(hipEventRecord(h->ev[7], s));
         const CallOpts::Mirror &mr = opts.mirror;
         if (mr.host) HIP_TRY(hipMemcpyAsync(mr.host + (size_t)frame0 * mr.row, mr.dev + (size_t)frame0 * mr.row, (size_t)n * mr.row, hipMemcpyDeviceToHost, s));

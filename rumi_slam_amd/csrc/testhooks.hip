@@ -55,6 +55,30 @@ extern "C" float rumi_hook_fast_atan2(float y, float x) { return fast_atan2_deg(
 extern "C" int rumi_hook_cv_round(float v) { return cv_round_f(v); }
 extern "C" int rumi_hook_magic_div(int32_t idx, int32_t d) { return magic_div(idx, magic_of((unsigned)d)); }
 
+// IC_Angle by rows: the vectors the launch code builds from umax and the kernel's own chunk function (disc_chunk_moments) on the 2 x 16 bytes a
+// row's two lanes load from byte s of the staged row on, summed over the 31 rows
+extern "C" int rumi_hook_disc_moments(const uint8_t *rows, int32_t s, const int32_t *umax16, int32_t *m01, int32_t *m10, uint32_t *W, uint32_t *M) {
+    if (!rows || !umax16 || !m01 || !m10 || s < 0 || s > 3) return RUMI_E_INVALID;
+    for (int i = 0; i <= kHalfPatch; i++) if (umax16[i] < 0 || umax16[i] > kHalfPatch) return RUMI_E_INVALID;
+    uint32_t vec[kDiscVecLanes * kDiscVecLaneDwords];
+    make_disc_vectors(umax16, vec);
+    int s01 = 0, s10 = 0;
+    for (int r = 0; r < kPatchSize; r++) {
+        const uint32_t *w = vec + r * kDiscVecLaneDwords, *m = w + kDiscRowChunks * kDiscChunkDwords;
+        for (int c = 0; c < kDiscRowChunks; c++) {
+            uint32_t d[kDiscChunkDwords];
+            std::memcpy(d, rows + r * 36 + s + 16 * c, sizeof d);
+            int a, b;
+            disc_chunk_moments(d, w + c * kDiscChunkDwords, m + c * kDiscChunkDwords, r - kHalfPatch, a, b);
+            s01 += a; s10 += b;
+        }
+        if (W) std::copy(w, w + 8, W + r * 8);
+        if (M) std::copy(m, m + 8, M + r * 8);
+    }
+    *m01 = s01; *m10 = s10;
+    return RUMI_OK;
+}
+
 // the lane packing of the batch resize / blur launches: the launch code's choice of G and the kernels' lane_slot, evaluated on the host
 extern "C" int rumi_hook_lane_packing(int32_t w, int32_t h, float scale, int32_t nlevels, int32_t nframes, int32_t kernel, int32_t level,
                                       int32_t force_g, int32_t *info, int32_t *slots, int32_t cap, int32_t *n_out) {
