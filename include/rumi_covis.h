@@ -8,7 +8,11 @@
  * by the caller, a map point an id 0 .. max_points-1.
  *   per key-frame slot: mp[n] (GetMapPointMatches as point ids, -1 = NULL), is_bad, map_id, order_key, best[10]
  *                       (GetBestCovisibilityKeyFrames(10) as slots, -1 padded), parent slot or -1, the children as a slot list
- *   per point:          is_bad, the observers (the key-frame slots of GetObservations(); feature indices are not kept)
+ *   per point:          is_bad, the observers (the key-frame slots of GetObservations(); feature indices are not kept), and optionally the
+ *                       attributes TrackLocalMap reads: GetWorldPos, GetNormal, mfMinDistance, mfMaxDistance, GetDescriptor, and a "has
+ *                       attributes" bit.  Observations() is not a field: for the monocular model it is the length of the observer row.
+ *                       isBad() is the bit rumi_covis_set_points / rumi_covis_set_bad maintain.  rumi_track_local_map (rumi_track.h) builds
+ *                       its point table from these on the device.
  *
  * order_key restates pointer order.  Every ordered walk in the two members is a walk of a std::map<KeyFrame*, ..> or a
  * std::set<KeyFrame*>, and every tie of sort(vPairs) is broken by the KeyFrame*: "pointer order" here is ascending order_key, distinct per
@@ -54,6 +58,11 @@ int rumi_covis_set_keyframes(RumiCovis *c, int32_t n, const int32_t *slots, cons
                              const int32_t *children);
 /* n points, each id at most once: observers of entry i = obs[obs_off[i] .. obs_off[i+1]), distinct live slots. */
 int rumi_covis_set_points(RumiCovis *c, int32_t n, const int32_t *ids, const uint8_t *is_bad, const int32_t *obs_off, const int32_t *obs);
+/* The attributes of n points, each id at most once: pos / normal [n][3], min_dist / max_dist [n] (raw: isInFrustum applies 0.8 and 1.2),
+ * desc [n][32].  To be called where the reference calls SetWorldPos, UpdateNormalAndDepth and ComputeDistinctiveDescriptors.  Staged like every
+ * edit: the next query uploads the changed records.  A point keeps its attributes until they are set again. */
+int rumi_covis_set_point_attributes(RumiCovis *c, int32_t n, const int32_t *ids, const float *pos, const float *normal, const float *min_dist,
+                                    const float *max_dist, const uint8_t *desc);
 /* KeyFrame::isBad of n_kf live slots and MapPoint::isBad of n_pt points. */
 int rumi_covis_set_bad(RumiCovis *c, int32_t n_kf, const int32_t *slots, const uint8_t *kf_bad, int32_t n_pt, const int32_t *ids, const uint8_t *pt_bad);
 /* KeyFrame::GetMap of n live slots changed (map merge). */
@@ -82,7 +91,8 @@ int rumi_covis_local_map(RumiCovis *c, int32_t n, const int32_t *frame_points, u
 
 /* The last query, in ms: validation + staging | upload, kernels, download | write-out. */
 int rumi_covis_stage_ms(const RumiCovis *c, float *out3);
-/* out7: arena capacity, tail, live entries (all in 32-bit entries), rows re-placed at the tail, compactions, growths, bytes of the last upload. */
+/* out7: arena capacity, tail, live entries (all in 32-bit entries), rows re-placed at the tail, compactions, growths, bytes of the last upload
+ * (attribute edits included). */
 int rumi_covis_stats(const RumiCovis *c, int64_t *out7);
 
 #ifdef __cplusplus

@@ -11,6 +11,7 @@
  */
 #ifndef RUMI_TRACK_H
 #define RUMI_TRACK_H
+#include "rumi_covis.h"
 #include "rumi_match.h"
 #include "rumi_orb.h"
 #include "rumi_voc.h"
@@ -127,6 +128,29 @@ int rumi_track_reference_keyframe(RumiTracker *t, RumiVocabulary *voc, int32_t l
 int rumi_track_local(RumiTracker *t, const float *K4, const float *Tcw7, const int32_t *frame_mp_in, const RumiTrackPoints *pts,
                      const uint8_t *seen_in, float th_local, int32_t far_points, float th_far_points, int32_t *frame_mp, uint8_t *outlier,
                      uint8_t *in_view, RumiTrackResult *res);
+
+/* Tracking::UpdateLocalMap + Tracking::TrackLocalMap in one call, on a covisibility store (rumi_covis.h) that holds the map points' attributes
+ * (rumi_covis_set_point_attributes).  The first half is rumi_covis_local_map on frame_points; the local point list stays on the device, where
+ * kernels build the point table rumi_track_local would be given:
+ *   rows 0 .. n_local_points)   mvpLocalMapPoints in their order, local = 1
+ *   then                        the frame's points that are not bad and not in the local list, each once, in order of their first feature, local = 0
+ *   then                        the discarded ids that have no row yet, in list order, local = 0
+ * position, normal, distances and descriptor come from the attribute records, Observations() is the length of the point's observer row, isBad
+ * the store's flag.  A bad frame point gets no row and its feature enters the search as -1 (SearchLocalPoints' first loop).  Rows the frame
+ * holds are seen in this frame; rows named in discarded_ids [n_discarded] (distinct ids: the points the previous function's "discard outliers"
+ * loop dropped) are seen as discarded outliers, and discarded_in_view [n_discarded] / discarded_proj5 [n_discarded][5] (both or neither) are
+ * their RumiTrackPoints.stale_in_view / stale_proj.  From there on the call is rumi_track_local.
+ * frame_points [n]: mCurrentFrame.mvpMapPoints as point ids, -1 = NULL, n = the resident frame's feature count.
+ * Outputs: frame_point_bad [n], local_kf [kf_cap], n_k1, n_local_kf, ref_kf, n_local_points as rumi_covis_local_map; table_ids [table_cap]: the
+ * point id of every row, n_table of them; frame_mp [n] as point ids, outlier [n], in_view [table_cap] per row and res as rumi_track_local.
+ * rumi_track_last_projections works afterwards with n_points = n_table.
+ * RUMI_E_INVALID: no frame is resident; the two handles live on different devices; a local or frame point has no attributes (counted on the
+ * device, the message names how many).  RUMI_E_CAPACITY: kf_cap, table_cap or the tracker's max_points is too small.  No output is written then. */
+int rumi_track_local_map(RumiTracker *t, RumiCovis *c, const float *K4, const float *Tcw7, const int32_t *frame_points, int32_t n_discarded,
+                         const int32_t *discarded_ids, const uint8_t *discarded_in_view, const float *discarded_proj5, float th_local,
+                         int32_t far_points, float th_far_points, uint8_t *frame_point_bad, int32_t *local_kf, int32_t kf_cap, int32_t *n_k1,
+                         int32_t *n_local_kf, int32_t *ref_kf, int32_t *table_ids, int32_t table_cap, int32_t *n_local_points, int32_t *n_table,
+                         int32_t *frame_mp, uint8_t *outlier, uint8_t *in_view, RumiTrackResult *res);
 
 /* Lens distortion (Frame::UndistortKeyPoints, Frame::ComputeImageBounds: R/lib_src/Frame.cc:770-826, cv::undistortPoints(mat, mat, K, mDistCoef,
  * cv::Mat(), mK): 5 fixed-point iterations of the inverse radial-tangential model in double, then P = K; OpenCV's arithmetic restated, parity

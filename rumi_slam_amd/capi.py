@@ -114,7 +114,7 @@ OPT_SYMBOLS = ["rumi_opt_create", "rumi_opt_destroy", "rumi_pose_optimization", 
 VOC_SYMBOLS = ["rumi_voc_create", "rumi_voc_load_text", "rumi_voc_destroy", "rumi_voc_words", "rumi_voc_levels", "rumi_voc_set_levels", "rumi_voc_assemble", "rumi_voc_transform_features",
                "rumi_voc_transform_batch_device", "rumi_voc_transform"]
 TRACK_SYMBOLS = ["rumi_track_create", "rumi_track_destroy", "rumi_track_frame", "rumi_track_extract", "rumi_track_motion",
-                 "rumi_track_reference_keyframe", "rumi_track_local", "rumi_track_image_buffer", "rumi_track_last_projections", "rumi_track_set_distortion", "rumi_track_undistorted"]
+                 "rumi_track_reference_keyframe", "rumi_track_local", "rumi_track_local_map", "rumi_track_image_buffer", "rumi_track_last_projections", "rumi_track_set_distortion", "rumi_track_undistorted"]
 QUEUE_SYMBOLS = ["rumi_queue_create", "rumi_queue_destroy", "rumi_queue_shards", "rumi_queue_record_bytes", "rumi_queue_block_capacity", "rumi_queue_row",
                  "rumi_queue_uses_rccl", "rumi_queue_extract", "rumi_queue_last_ms"]
 KFDB_SYMBOLS = ["rumi_kfdb_create", "rumi_kfdb_destroy", "rumi_kfdb_clear", "rumi_kfdb_size", "rumi_kfdb_next_seq", "rumi_kfdb_max_batch", "rumi_kfdb_add",
@@ -122,7 +122,8 @@ KFDB_SYMBOLS = ["rumi_kfdb_create", "rumi_kfdb_destroy", "rumi_kfdb_clear", "rum
                 "rumi_kfdb_set_bad", "rumi_kfdb_set_covisibles", "rumi_kfdb_score", "rumi_kfdb_scored", "rumi_kfdb_select_reloc", "rumi_kfdb_select_nbest"]
 MAPPING_SYMBOLS = ["rumi_create_new_map_points", "rumi_refresh_create", "rumi_refresh_destroy", "rumi_refresh_map_points", "rumi_refresh_stage_ms",
                    "rumi_cull_create", "rumi_cull_destroy", "rumi_keyframe_culling", "rumi_cull_stage_ms"]
-COVIS_SYMBOLS = ["rumi_covis_create", "rumi_covis_destroy", "rumi_covis_set_keyframes", "rumi_covis_set_points", "rumi_covis_set_bad", "rumi_covis_set_maps",
+COVIS_SYMBOLS = ["rumi_covis_create", "rumi_covis_destroy", "rumi_covis_set_keyframes", "rumi_covis_set_points", "rumi_covis_set_point_attributes",
+                 "rumi_covis_set_bad", "rumi_covis_set_maps",
                  "rumi_covis_update_connections", "rumi_covis_local_map", "rumi_covis_stage_ms", "rumi_covis_stats"]
 KFD_SYMBOLS = ["rumi_kfd_create", "rumi_kfd_destroy", "rumi_kfd_set_pd", "rumi_kfd_reset", "rumi_kfd_step", "rumi_kfd_track"]
 
@@ -191,6 +192,7 @@ def covis_lib():
     L.rumi_covis_destroy.restype = None
     L.rumi_covis_set_keyframes.argtypes = [vp, i32] + [vp] * 10
     L.rumi_covis_set_points.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.rumi_covis_set_point_attributes.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.rumi_covis_set_bad.argtypes = [vp, i32, vp, vp, i32, vp, vp]
     L.rumi_covis_set_maps.argtypes = [vp, i32, vp, vp]
     L.rumi_covis_update_connections.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64]

@@ -65,6 +65,14 @@ class Covisibility:
         oo, ob = _csr(list(observers))
         return self._ret(self._lib.rumi_covis_set_points(self._h, len(ids), _p(ids), _p(bad), _p(oo), _p(ob)), check)
 
+    def set_point_attributes(self, ids, pos, normal, min_dist, max_dist, desc, check=True):
+        """GetWorldPos / GetNormal [n, 3], mfMinDistance / mfMaxDistance [n] (raw), GetDescriptor [n, 32] of the points `ids`."""
+        ids = np.ascontiguousarray(ids, _i32); n = len(ids)
+        pos = np.ascontiguousarray(pos, np.float32).reshape(n, 3); normal = np.ascontiguousarray(normal, np.float32).reshape(n, 3)
+        mn = np.ascontiguousarray(min_dist, np.float32).reshape(n); mx = np.ascontiguousarray(max_dist, np.float32).reshape(n)
+        desc = np.ascontiguousarray(desc, _u8).reshape(n, 32)
+        return self._ret(self._lib.rumi_covis_set_point_attributes(self._h, n, _p(ids), _p(pos), _p(normal), _p(mn), _p(mx), _p(desc)), check)
+
     def set_bad(self, kf_slots=(), kf_bad=(), pt_ids=(), pt_bad=(), check=True):
         ks = np.ascontiguousarray(kf_slots, _i32); kb = np.ascontiguousarray(kf_bad, _u8)
         ps = np.ascontiguousarray(pt_ids, _i32); pb = np.ascontiguousarray(pt_bad, _u8)

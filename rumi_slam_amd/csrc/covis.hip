@@ -4,11 +4,15 @@
 // Resident state, all of it 32-bit words so that one scatter kernel applies every staged edit:
 //   kf     [max_kf][20]     mp row (offset, length), children row (offset, length), flags (bit 0 bad, bit 1 live), map, parent, -, order_key
 //                           (two words), best[10]
-//   pt     [max_points][4]  observer row (offset, length), bad, -
+//   pt     [max_points][4]  observer row (offset, length), bad, has attributes
+//   attr   [max_points][16] position, normal, mfMinDistance, mfMaxDistance (eight floats), then the 32 descriptor bytes: a 64-byte record whose
+//                           two halves are 16-byte aligned, so a gather may read either as two uint4 or as eight dwords over eight lanes.
+//                           Allocated with the first rumi_covis_set_point_attributes; the tracker's table gather reads it (track_local_map.inc)
 //   arena                   every row: mp rows, children rows, observer rows.  A row that outgrows its place moves to the tail; a full arena is
 //                           rebuilt on the host (compacted, and doubled when the live rows fill more than three quarters of it) and sent whole.
 //   tag    [max_points]     64-bit stamps of the local-point selection, (call epoch << 32) | priority
-// The host keeps a mirror of the three tables; an edit writes the mirror and notes (table, offset, words).  The next query packs the noted
+//   rowOf  [max_points]     64-bit stamps of the same epoch for rumi_track_local_map's id -> table row map (allocated with its first call)
+// The host keeps a mirror of kf, pt, attr and the arena; an edit writes the mirror and notes (table, offset, words).  The next query packs the noted
 // ranges and its own input into one pinned block, sends it with one copy, and k_covis_apply scatters it.
 //
 //   k_covis_count<false>  a workgroup per batch key-frame: a lane per feature slot walks its point's observer row and counts into a histogram
@@ -27,14 +31,15 @@
 
 #include "rumi_common.h"
 #include "rumi_covis.h"
+#include "rumi_internal.h"
 
 namespace rumi {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int KFW = 20, PTW = 4;                       // words per key-frame / point record
+constexpr int KFW = 20, PTW = kCovisPointWords, ATW = kCovisAttrWords;     // words per key-frame / point / attribute record
 constexpr int K_MPOFF = 0, K_MPLEN = 1, K_CHOFF = 2, K_CHLEN = 3, K_FLAGS = 4, K_MAP = 5, K_PARENT = 6, K_KEY = 8, K_BEST = 10;
-constexpr int T_KF = 0, T_PT = 1, T_ARENA = 2;
+constexpr int T_KF = 0, T_PT = 1, T_ARENA = 2, T_ATTR = 3, kTables = 4;
 constexpr uint16_t kNone = 0xFFFF;                     // sorts last; slots stay below RUMI_COVIS_MAX_KEYFRAMES
 constexpr int kPosBits = 13;
 static_assert((1 << kPosBits) == RUMI_COVIS_MAX_KEYFRAMES, "position bits of the packed maximum");
@@ -73,7 +78,7 @@ struct LocalArgs {
 };
 
 struct ApplyArgs {
-    int32_t *base[3];
+    int32_t *base[kTables];
     const int4 *recs;              // table, first word there, first word of the payload, words
     const int32_t *payload;
 };
@@ -302,7 +307,8 @@ struct RumiCovis {
     bool bound = false;
     int32_t maxKf = 0, maxPts = 0;
     // host mirrors of the device tables
-    std::vector<int32_t> kf, pt, arena;
+    std::vector<int32_t> kf, pt, arena, attr;        // attr: empty until the first rumi_covis_set_point_attributes
+    int32_t hiAttr = 0;                              // highest point id with attributes + 1
     std::vector<int32_t> capMp, capCh, capObs;       // places of the rows in the arena (entries); 0 = never placed
     int64_t tail = 0, live = 0;
     int64_t replaced = 0, compactions = 0, growths = 0, lastUpload = 0;
@@ -312,9 +318,12 @@ struct RumiCovis {
     int32_t stampKf = 0, stampPt = 0;
     // staged edits
     std::vector<int4> recs;                          // table, first word, -, words
-    bool full[3] = {true, true, true};
+    bool full[kTables] = {true, true, true, true};
     // device
-    int32_t *dKf = nullptr, *dPt = nullptr, *dArena = nullptr;
+    int32_t *dKf = nullptr, *dPt = nullptr, *dArena = nullptr, *dAttr = nullptr;
+    unsigned long long *dRowOf = nullptr;
+    std::vector<uint8_t> extra;                      // the input block of rumi_track_local_map: frame points and the discarded outliers
+    std::chrono::steady_clock::time_point tq[2];     // start of the query in flight, and of its device part
     size_t dArenaCap = 0;
     unsigned long long *dTag = nullptr;
     uint32_t epoch = 0;
@@ -362,7 +371,7 @@ void rebuild_arena(RumiCovis *h, int64_t need) {
     h->arena.swap(nv);
     h->tail = h->live = t;
     h->full[T_KF] = h->full[T_PT] = h->full[T_ARENA] = true;
-    h->recs.clear();
+    h->recs.erase(std::remove_if(h->recs.begin(), h->recs.end(), [](const int4 &r) { return r.x != T_ATTR; }), h->recs.end());
 }
 
 // Row (off, len) of place c takes src[0 .. n): in place when it fits, else at the tail.
@@ -403,15 +412,19 @@ int bind_device(RumiCovis *h) {
 int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) {
     int rc;
     if ((rc = bind_device(h)) != RUMI_OK) return rc;
-    if (h->recs.size() > (1u << 16)) { h->full[0] = h->full[1] = h->full[2] = true; }
+    if (h->recs.size() > (1u << 16)) { std::fill(h->full, h->full + kTables, true); }
     if (h->arena.size() > h->dArenaCap) {
         h->dArenaCap = 0;
         if ((rc = regrow(&h->dArena, h->arena.size() * 4, false)) != RUMI_OK) return rc;
         h->dArenaCap = h->arena.size();
         h->full[T_ARENA] = true;
     }
-    int32_t *dBase[3] = {h->dKf, h->dPt, h->dArena};
-    const std::vector<int32_t> *mirror[3] = {&h->kf, &h->pt, &h->arena};
+    if (h->hiAttr > 0 && !h->dAttr) {
+        if ((rc = dev_alloc(&h->dAttr, (size_t)h->maxPts * ATW)) != RUMI_OK) return rc;
+        h->full[T_ATTR] = true;
+    }
+    int32_t *dBase[kTables] = {h->dKf, h->dPt, h->dArena, h->dAttr};
+    const std::vector<int32_t> *mirror[kTables] = {&h->kf, &h->pt, &h->arena, &h->attr};
     size_t words = 0, nRec = 0;
     for (int4 &r : h->recs)
         if (!h->full[r.x]) { r.z = (int)words; words += (size_t)r.w; h->recs[nRec++] = r; }
@@ -424,9 +437,9 @@ int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) 
         h->stageCap = want;
     }
     h->lastUpload = (int64_t)bytes;
-    for (int t = 0; t < 3; t++)
+    for (int t = 0; t < kTables; t++)
         if (h->full[t]) {
-            const size_t n = t == T_ARENA ? (size_t)h->tail : mirror[t]->size();
+            const size_t n = t == T_ARENA ? (size_t)h->tail : t == T_ATTR ? (size_t)h->hiAttr * ATW : mirror[t]->size();
             if (n) HIP_TRY(hipMemcpyAsync(dBase[t], mirror[t]->data(), n * 4, hipMemcpyHostToDevice, nullptr));
             h->lastUpload += (int64_t)n * 4;
         }
@@ -437,13 +450,13 @@ int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) 
     if (bytes) HIP_TRY(hipMemcpyAsync(h->dStage, h->hStage, bytes, hipMemcpyHostToDevice, nullptr));
     if (nRec) {
         ApplyArgs a;
-        for (int t = 0; t < 3; t++) a.base[t] = dBase[t];
+        for (int t = 0; t < kTables; t++) a.base[t] = dBase[t];
         a.recs = reinterpret_cast<const int4 *>(h->dStage);
         a.payload = reinterpret_cast<const int32_t *>(h->dStage + offPay);
         hipLaunchKernelGGL(k_covis_apply, dim3((unsigned)nRec), dim3(64), 0, nullptr, a);
     }
     h->recs.clear();
-    h->full[0] = h->full[1] = h->full[2] = false;
+    std::fill(h->full, h->full + kTables, false);
     *dExtra = h->dStage + offExtra;
     return RUMI_OK;
 }
@@ -499,7 +512,7 @@ extern "C" void rumi_covis_destroy(RumiCovis *h) {
     if (h->bound) (void)hipSetDevice(h->device);
     if (h->hStage) (void)hipHostFree(h->hStage);
     if (h->hOut) (void)hipHostFree(h->hOut);
-    for (void *p : {(void *)h->dKf, (void *)h->dPt, (void *)h->dArena, (void *)h->dTag, (void *)h->dStage, (void *)h->dOut})
+    for (void *p : {(void *)h->dKf, (void *)h->dPt, (void *)h->dArena, (void *)h->dAttr, (void *)h->dTag, (void *)h->dRowOf, (void *)h->dStage, (void *)h->dOut})
         if (p) (void)hipFree(p);
     delete h;
 }
@@ -669,6 +682,40 @@ extern "C" int rumi_covis_set_maps(RumiCovis *h, int32_t n, const int32_t *slots
     return RUMI_OK;
 }
 
+extern "C" int rumi_covis_set_point_attributes(RumiCovis *h, int32_t n, const int32_t *ids, const float *pos, const float *normal, const float *min_dist,
+                                               const float *max_dist, const uint8_t *desc) {
+    if (!h || n < 0 || (n > 0 && (!ids || !pos || !normal || !min_dist || !max_dist || !desc))) {
+        g_lastError = "rumi_covis_set_point_attributes: missing argument or negative count";
+        return RUMI_E_INVALID;
+    }
+    if (n == 0) return RUMI_OK;
+    if (h->maxPts > (1 << 26)) {                                     // a staged edit addresses its table by a 32-bit word offset
+        g_lastError = "rumi_covis_set_point_attributes: the attribute table holds at most 2^26 points";
+        return RUMI_E_CAPACITY;
+    }
+    if (h->stampPt > INT32_MAX - 4) { std::fill(h->ptStamp.begin(), h->ptStamp.end(), 0); h->stampPt = 0; }
+    const int32_t inCall = ++h->stampPt;
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= h->maxPts || h->ptStamp[ids[i]] == inCall) {
+            g_lastError = "rumi_covis_set_point_attributes: a point id outside 0..max_points-1, or named twice";
+            return RUMI_E_INVALID;
+        }
+        h->ptStamp[ids[i]] = inCall;
+    }
+    if (h->attr.empty()) h->attr.assign((size_t)h->maxPts * ATW, 0);
+    for (int i = 0; i < n; i++) {
+        const int32_t p = ids[i];
+        int32_t *A = h->attr.data() + (size_t)p * ATW;
+        std::memcpy(A, pos + (size_t)i * 3, 12); std::memcpy(A + 3, normal + (size_t)i * 3, 12);
+        std::memcpy(A + 6, min_dist + i, 4); std::memcpy(A + 7, max_dist + i, 4);
+        std::memcpy(A + 8, desc + (size_t)i * 32, 32);
+        h->hiAttr = std::max(h->hiAttr, p + 1);
+        note(h, T_ATTR, (int64_t)p * ATW, ATW);
+        if (!h->pt[(size_t)p * PTW + 3]) { h->pt[(size_t)p * PTW + 3] = 1; note(h, T_PT, (int64_t)p * PTW + 3, 1); }
+    }
+    return RUMI_OK;
+}
+
 extern "C" int rumi_covis_update_connections(RumiCovis *h, int32_t B, const int32_t *batch, int32_t *status, int32_t *conn_off, int32_t *conn_slot,
                                              int32_t *conn_count, int64_t conn_cap, int32_t *ord_off, int32_t *ord_slot, int32_t *ord_weight,
                                              int64_t ord_cap) {
@@ -731,32 +778,71 @@ extern "C" int rumi_covis_update_connections(RumiCovis *h, int32_t B, const int3
     return RUMI_OK;
 }
 
-extern "C" int rumi_covis_local_map(RumiCovis *h, int32_t n, const int32_t *frame_points, uint8_t *frame_point_bad, int32_t *local_kf, int32_t kf_cap,
-                                    int32_t *n_k1, int32_t *n_local_kf, int32_t *ref_kf, int32_t *local_points, int32_t pt_cap,
-                                    int32_t *n_local_points) {
-    if (!h || n < 0 || n > RUMI_COVIS_MAX_FEATURES || kf_cap < 0 || pt_cap < 0 || !n_k1 || !n_local_kf || !ref_kf || !n_local_points ||
-        (n > 0 && (!frame_points || !frame_point_bad)) || (kf_cap > 0 && !local_kf) || (pt_cap > 0 && !local_points)) {
-        g_lastError = "rumi_covis_local_map: missing argument, negative count, or more than RUMI_COVIS_MAX_FEATURES frame points";
+// The launch sequence of Tracking::UpdateLocalMap, nothing read back: k_covis_count<true>, k_covis_local<1..3>.  With `d` (rumi_track_local_map)
+// the discarded outliers travel in the same block behind the frame's points, and the second header is cleared for the table kernels.
+int rumi::covis_local_map_launch(RumiCovis *h, int n, const int32_t *frame_points, const CovisDiscarded *d, int wantDevice, const char *entry,
+                                 CovisLocalView *view) {
+    h->tq[0] = std::chrono::steady_clock::now();
+    if (n < 0 || n > RUMI_COVIS_MAX_FEATURES || (n > 0 && !frame_points)) {
+        g_lastError = std::string(entry) + ": missing argument, negative count, or more than RUMI_COVIS_MAX_FEATURES frame points";
         return RUMI_E_INVALID;
     }
-    const auto t0 = std::chrono::steady_clock::now();
     for (int i = 0; i < n; i++)
         if (frame_points[i] < -1 || frame_points[i] >= h->maxPts) {
-            g_lastError = "rumi_covis_local_map: a frame point outside -1..max_points-1";
+            g_lastError = std::string(entry) + ": a frame point outside -1..max_points-1";
             return RUMI_E_INVALID;
         }
+    const int nd = d ? d->n : 0;
+    const bool stale = d && d->inView && d->proj5;
+    if (d) {
+        if (nd < 0 || nd > RUMI_COVIS_MAX_FEATURES || (nd > 0 && !d->ids)) {
+            g_lastError = std::string(entry) + ": missing discarded ids, negative count, or more than RUMI_COVIS_MAX_FEATURES of them";
+            return RUMI_E_INVALID;
+        }
+        if (h->stampPt > INT32_MAX - 4) { std::fill(h->ptStamp.begin(), h->ptStamp.end(), 0); h->stampPt = 0; }
+        const int32_t inCall = ++h->stampPt;
+        for (int k = 0; k < nd; k++) {
+            if (d->ids[k] < 0 || d->ids[k] >= h->maxPts || h->ptStamp[d->ids[k]] == inCall) {
+                g_lastError = std::string(entry) + ": a discarded id outside 0..max_points-1, or named twice";
+                return RUMI_E_INVALID;
+            }
+            h->ptStamp[d->ids[k]] = inCall;
+        }
+    }
     int rc;
+    if ((rc = bind_device(h)) != RUMI_OK) return rc;
+    if (wantDevice >= 0 && h->device != wantDevice) {
+        g_lastError = std::string(entry) + ": the store and the tracker are on different devices";
+        return RUMI_E_INVALID;
+    }
+    // the input block: frame points | discarded ids | their mbTrackInView | their projections, each part 16-byte aligned
+    const size_t offIds = up16((size_t)n * 4), offIn = offIds + up16((size_t)nd * 4), offProj = offIn + up16(stale ? (size_t)nd : 0),
+                 inBytes = d ? offProj + (stale ? (size_t)nd * 20 : 0) : (size_t)n * 4;
+    const void *in = frame_points;
+    if (d) {
+        h->extra.assign(inBytes, 0);
+        if (n > 0) std::memcpy(h->extra.data(), frame_points, (size_t)n * 4);
+        if (nd > 0) std::memcpy(h->extra.data() + offIds, d->ids, (size_t)nd * 4);
+        if (stale && nd > 0) { std::memcpy(h->extra.data() + offIn, d->inView, (size_t)nd); std::memcpy(h->extra.data() + offProj, d->proj5, (size_t)nd * 20); }
+        in = h->extra.data();
+    }
     uint8_t *dFrame = nullptr;
-    if ((rc = flush(h, frame_points, (size_t)n * 4, &dFrame)) != RUMI_OK) return rc;
+    if ((rc = flush(h, in, inBytes, &dFrame)) != RUMI_OK) return rc;
     const int gx = h->nLive, gy = (h->maxRow + kThreads - 1) / kThreads;
-    const size_t offBad = 16, offKf = offBad + up16((size_t)n), offCounts = offKf + up16((size_t)h->hiSlot * 4),
+    const size_t offBad = 2 * 16, offKf = offBad + up16((size_t)n), offCounts = offKf + up16((size_t)h->hiSlot * 4),
                  offPts = offCounts + up16((size_t)gx * gy * 4), outBytes = offPts + (size_t)h->maxPts * 4;
     if ((rc = grow_out(h, outBytes)) != RUMI_OK) return rc;
-    if (++h->epoch == 0) {                                           // once every 2^32 calls: stale tags could meet a reused epoch
-        HIP_TRY(hipMemsetAsync(h->dTag, 0, (size_t)h->maxPts * 8, nullptr));
-        h->epoch = 1;
+    bool clearStamps = ++h->epoch == 0;                              // once every 2^32 calls: stale tags could meet a reused epoch
+    if (d && !h->dRowOf) {
+        if ((rc = dev_alloc(&h->dRowOf, (size_t)h->maxPts)) != RUMI_OK) return rc;
+        clearStamps = true;
     }
-    const auto t1 = std::chrono::steady_clock::now();
+    if (clearStamps) {
+        if (h->epoch == 0) { HIP_TRY(hipMemsetAsync(h->dTag, 0, (size_t)h->maxPts * 8, nullptr)); h->epoch = 1; }
+        if (h->dRowOf) HIP_TRY(hipMemsetAsync(h->dRowOf, 0, (size_t)h->maxPts * 8, nullptr));
+    }
+    if (d) HIP_TRY(hipMemsetAsync(h->dOut + 16, 0, 16, nullptr));
+    h->tq[1] = std::chrono::steady_clock::now();
     CountArgs a{};
     a.t = CovisTables{h->dKf, h->dPt, h->dArena, h->hiSlot};
     a.rows = reinterpret_cast<const int32_t *>(dFrame);
@@ -780,19 +866,57 @@ extern "C" int rumi_covis_local_map(RumiCovis *h, int32_t n, const int32_t *fram
         hipLaunchKernelGGL(k_covis_local<3>, dim3(gx, gy), dim3(kThreads), 0, nullptr, l);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(h->hOut, h->dOut, offCounts, hipMemcpyDeviceToHost));
-    const int4 head = *reinterpret_cast<const int4 *>(h->hOut);
-    if (head.y > kf_cap || head.w > pt_cap) {
+    CovisLocalView &v = *view;
+    v = CovisLocalView{};
+    v.device = h->device; v.maxPoints = h->maxPts; v.nFrame = n; v.nDiscarded = nd; v.epoch = h->epoch;
+    v.pt = h->dPt; v.attr = h->dAttr; v.rowOf = h->dRowOf;
+    v.head = reinterpret_cast<int32_t *>(h->dOut);
+    v.localPts = reinterpret_cast<const int32_t *>(h->dOut + offPts);
+    v.framePts = reinterpret_cast<const int32_t *>(dFrame);
+    if (d) {
+        v.discIds = reinterpret_cast<const int32_t *>(dFrame + offIds);
+        if (stale) { v.discInView = dFrame + offIn; v.discProj = reinterpret_cast<const float *>(dFrame + offProj); }
+    }
+    v.offBad = offBad; v.offKf = offKf; v.offPts = offPts; v.headBytes = offCounts;
+    return RUMI_OK;
+}
+
+// The one read in the middle of the query: both headers, the frame's bad flags and the local key-frames, into the pinned block.
+int rumi::covis_local_map_read(RumiCovis *h, const CovisLocalView &v, const int32_t **head8, const uint8_t **frameBad, const int32_t **localKf) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(h->hOut, h->dOut, v.headBytes, hipMemcpyDeviceToHost));
+    *head8 = reinterpret_cast<const int32_t *>(h->hOut);
+    *frameBad = h->hOut + v.offBad;
+    *localKf = reinterpret_cast<const int32_t *>(h->hOut + v.offKf);
+    set_ms(h, h->tq[0], h->tq[1], std::chrono::steady_clock::now());
+    return RUMI_OK;
+}
+
+extern "C" int rumi_covis_local_map(RumiCovis *h, int32_t n, const int32_t *frame_points, uint8_t *frame_point_bad, int32_t *local_kf, int32_t kf_cap,
+                                    int32_t *n_k1, int32_t *n_local_kf, int32_t *ref_kf, int32_t *local_points, int32_t pt_cap,
+                                    int32_t *n_local_points) {
+    if (!h || n < 0 || n > RUMI_COVIS_MAX_FEATURES || kf_cap < 0 || pt_cap < 0 || !n_k1 || !n_local_kf || !ref_kf || !n_local_points ||
+        (n > 0 && (!frame_points || !frame_point_bad)) || (kf_cap > 0 && !local_kf) || (pt_cap > 0 && !local_points)) {
+        g_lastError = "rumi_covis_local_map: missing argument, negative count, or more than RUMI_COVIS_MAX_FEATURES frame points";
+        return RUMI_E_INVALID;
+    }
+    int rc;
+    CovisLocalView v;
+    const int32_t *head, *kfs;
+    const uint8_t *bad;
+    if ((rc = covis_local_map_launch(h, n, frame_points, nullptr, -1, "rumi_covis_local_map", &v)) != RUMI_OK) return rc;
+    if ((rc = covis_local_map_read(h, v, &head, &bad, &kfs)) != RUMI_OK) return rc;
+    if (head[1] > kf_cap || head[3] > pt_cap) {
         g_lastError = "rumi_covis_local_map: kf_cap or pt_cap is too small for the lists";
         return RUMI_E_CAPACITY;
     }
-    if (head.w > 0) HIP_TRY(hipMemcpy(h->hOut + offPts, h->dOut + offPts, (size_t)head.w * 4, hipMemcpyDeviceToHost));
+    if (head[3] > 0) HIP_TRY(hipMemcpy(h->hOut + v.offPts, h->dOut + v.offPts, (size_t)head[3] * 4, hipMemcpyDeviceToHost));
     const auto t2 = std::chrono::steady_clock::now();
-    if (n > 0) std::memcpy(frame_point_bad, h->hOut + offBad, (size_t)n);
-    if (head.y > 0) std::memcpy(local_kf, h->hOut + offKf, (size_t)head.y * 4);
-    if (head.w > 0) std::memcpy(local_points, h->hOut + offPts, (size_t)head.w * 4);
-    *n_k1 = head.x; *n_local_kf = head.y; *ref_kf = head.z; *n_local_points = head.w;
-    set_ms(h, t0, t1, t2);
+    if (n > 0) std::memcpy(frame_point_bad, bad, (size_t)n);
+    if (head[1] > 0) std::memcpy(local_kf, kfs, (size_t)head[1] * 4);
+    if (head[3] > 0) std::memcpy(local_points, h->hOut + v.offPts, (size_t)head[3] * 4);
+    *n_k1 = head[0]; *n_local_kf = head[1]; *ref_kf = head[2]; *n_local_points = head[3];
+    set_ms(h, h->tq[0], h->tq[1], t2);
     return RUMI_OK;
 }
 

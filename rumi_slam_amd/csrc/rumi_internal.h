@@ -5,8 +5,34 @@
 
 typedef struct RumiVocabulary RumiVocabulary;
 typedef struct RumiMatcher RumiMatcher;
+typedef struct RumiCovis RumiCovis;
 
 namespace rumi {
+
+// ---- the covisibility store (covis.hip) as the tracker's rumi_track_local_map drives it (track.hip, track_local_map.inc) ----
+constexpr int kCovisPointWords = 4;    // pt record: observer row (offset, length), flags (bit 0 bad), has attributes
+constexpr int kCovisAttrWords = 16;    // attr record: position 3, normal 3, min distance, max distance (f32), descriptor 8 words
+// The discarded outliers of the previous Tracking function: ids (distinct), and optionally what an earlier frame left in them.
+struct CovisDiscarded { int n; const int32_t *ids; const uint8_t *inView; const float *proj5; };
+// Where the store's tables and the lists of the local-map kernels lie on the device after covis_local_map_launch.
+struct CovisLocalView {
+    int device, maxPoints, nFrame, nDiscarded;
+    uint32_t epoch;                    // of this query: the stamp of tag and rowOf
+    const int32_t *pt, *attr;          // [max_points][kCovisPointWords], [max_points][kCovisAttrWords] (null: no point has attributes)
+    unsigned long long *rowOf;         // [max_points] (epoch << 32) | value, see track_local_map.inc (null without CovisDiscarded)
+    int32_t *head;                     // {n_k1, n_local_kf, ref_kf, n_local_points} {n_table, rows without attributes, -, -}
+    const int32_t *localPts;           // mvpLocalMapPoints [n_local_points]
+    const int32_t *framePts, *discIds; // the query's input as uploaded: [nFrame], [nDiscarded]
+    const uint8_t *discInView;         // [nDiscarded] or null
+    const float *discProj;             // [nDiscarded][5] or null
+    size_t offBad, offKf, offPts, headBytes;      // byte offsets inside the store's output block (covis_local_map_read)
+};
+// Validates, uploads the staged edits and the input, launches k_covis_count<true> and k_covis_local<1..3> on the null stream and returns
+// without reading anything back.  d: the table entry's discarded outliers (null: rumi_covis_local_map).  wantDevice >= 0: refused with
+// RUMI_E_INVALID when the store lives on another device.
+int covis_local_map_launch(RumiCovis *c, int n, const int32_t *frame_points, const CovisDiscarded *d, int wantDevice, const char *entry, CovisLocalView *view);
+// Both headers, the frame's bad flags [nFrame] and the local key-frames, as host pointers into the store's pinned block (synchronises).
+int covis_local_map_read(RumiCovis *c, const CovisLocalView &v, const int32_t **head8, const uint8_t **frameBad, const int32_t **localKf);
 
 // Correspondences the LDS instantiation of k_pose_opt holds (opt.hip).  The tracker (track.hip) launches ONLY that instantiation when it knows a
 // frame cannot have more (nfeatures 1000 + the extractor's slack of 96 fits), so both files take the number from here.

@@ -219,6 +219,8 @@ __device__ __forceinline__ void frustum_body(int i, const FrustumArgs &F) {
 
 __global__ void k_track_frustum(FrustumArgs F) { frustum_body(blockIdx.x * blockDim.x + threadIdx.x, F); }
 
+#include "track_local_map.inc"
+
 // after the last PoseOptimization: mvpMapPoints and mvbOutlier per feature into the result block, mnMatchesInliers (Tracking.cc:2573-2586)
 __global__ void k_track_finish(const int32_t *idx, const uint8_t *outlierC, const int32_t *featMp, const int32_t *mpObs, uint8_t *outlierF, int32_t *mpOut,
                                int countInliers, TrackBlock *blk, const int32_t *searchHeader) {
@@ -270,6 +272,7 @@ struct TrackViews {                      // the arrays behind the TrackBlock hea
     TrackBlock *blk;
     int32_t *mpOut, *mpMotion;           // mvpMapPoints at the end | after the motion model
     uint8_t *outF, *view, *record;       // mvbOutlier, mbTrackInView, the extractor's record [n, mono | keys cap | descriptors]
+    int32_t *tableIds;                   // rumi_track_local_map: the point id of every table row, behind the record
 };
 
 struct RumiTracker {
@@ -282,8 +285,8 @@ struct RumiTracker {
     hipEvent_t evUp = nullptr;
     uint8_t *hImage = nullptr;           // pinned staging of the caller's (pageable) image: a plain memcpy + one asynchronous copy (the runtime's own
                                          // staging of a pageable source serialises the call for ~0.1 ms)
-    // ONE device block [TrackBlock | mp cap*4 | mp after the motion model cap*4 | outlier cap | in_view maxPts | record 8 + 60 cap] and its pinned mirror: one copy brings a frame's results back
-    uint8_t *dBlk = nullptr, *hBlk = nullptr; size_t oRec = 0, oDesc = 0, blkBytes = 0, recordBytes = 0;     // oDesc: the descriptors inside the record
+    // ONE device block [TrackBlock | mp cap*4 | mp after the motion model cap*4 | outlier cap | in_view maxPts | record 8 + 60 cap | table ids maxPts*4] and its pinned mirror: one copy brings a frame's results back
+    uint8_t *dBlk = nullptr, *hBlk = nullptr; size_t oRec = 0, oDesc = 0, oIds = 0, blkBytes = 0, recordBytes = 0;     // oDesc: the descriptors inside the record
     TrackViews d{}, h{};
     float *dInvSigma2 = nullptr, *dXw = nullptr, *dObs = nullptr, *dW = nullptr;
     int32_t *dIdx = nullptr;
@@ -338,7 +341,7 @@ extern "C" int rumi_track_create(const RumiOrbConfig *cfg, int32_t max_points, i
     t->recordBytes = 8 + 60 * C;
     t->oDesc = 8 + C * sizeof(RumiKeyPoint);
     const size_t oMp = al(sizeof(TrackBlock)), oMpM = al(oMp + C * 4), oOut = al(oMpM + C * 4), oView = al(oOut + C);
-    t->oRec = al(oView + P); t->blkBytes = al(t->oRec + t->recordBytes);
+    t->oRec = al(oView + P); t->oIds = al(t->oRec + t->recordBytes); t->blkBytes = al(t->oIds + P * 4);
 #define TRYA(x) if ((rc = (x)) != RUMI_OK) { rumi_track_destroy(t); return rc; }
     TRYA(dev_alloc(&t->dImage, t->imageBytes + 64)); TRYA(dev_alloc(&t->dBlk, t->blkBytes)); TRYA(dev_alloc(&t->dInvSigma2, 64));
     TRYA(dev_alloc(&t->dXw, C * 3)); TRYA(dev_alloc(&t->dObs, C * 2)); TRYA(dev_alloc(&t->dW, C)); TRYA(dev_alloc(&t->dIdx, C));
@@ -352,7 +355,7 @@ extern "C" int rumi_track_create(const RumiOrbConfig *cfg, int32_t max_points, i
         rumi_track_destroy(t); return RUMI_E_NO_DEVICE;
     }
     auto views = [&](uint8_t *b) {
-        return TrackViews{reinterpret_cast<TrackBlock *>(b), reinterpret_cast<int32_t *>(b + oMp), reinterpret_cast<int32_t *>(b + oMpM), b + oOut, b + oView, b + t->oRec};
+        return TrackViews{reinterpret_cast<TrackBlock *>(b), reinterpret_cast<int32_t *>(b + oMp), reinterpret_cast<int32_t *>(b + oMpM), b + oOut, b + oView, b + t->oRec, reinterpret_cast<int32_t *>(b + t->oIds)};
     };
     t->d = views(t->dBlk); t->h = views(t->hBlk);
     float inv2[64] = {0};
@@ -369,7 +372,7 @@ enum TrackTail { TAIL_AFTER_MOTION, TAIL_DISCARD, TAIL_FINISH };       // the ke
 
 int grid_of(int n) { return std::max(1, (n + 255) / 256); }
 int grid_items(int n, int nmp) { return grid_of(std::max(std::max(n, nmp), 4)); }     // features, table points and the 4-word result header
-bool has_stale(const RumiTrackPoints *pts) { return pts->stale_in_view && pts->stale_proj; }
+bool has_stale(const RumiTrackPoints *pts) { return pts && pts->stale_in_view && pts->stale_proj; }
 const RumiKeyPoint *resident_keys(const RumiTracker *t) {               // mvKeysUn: what every stage reads
     return t->distort ? t->dKeysUn : reinterpret_cast<const RumiKeyPoint *>(t->d.record + 8);
 }
@@ -492,15 +495,14 @@ int local_search(RumiTracker *t, const FrameDev &fd, int nmp, int32_t *hostMp, R
 
 // SearchLocalPoints' second loop with the pose in the block: isInFrustum of the table's points and their queries.  The six per-point fields go
 // into the matcher's (by then scattered) staging block, where rumi_track_last_projections finds them.
-int launch_frustum(RumiTracker *t, const FrameDev &fd, const RumiTrackPoints *pts, int n, float th_local, int far_points, float th_far_points, const char *entry) {
+int launch_frustum(RumiTracker *t, const FrameDev &fd, int nmp, bool stale, int n, float th_local, int far_points, float th_far_points, const char *entry) {
     RumiMatcher *m = t->m;
-    const int nmp = pts->n;
     if (!frustum_fits(m, nmp)) { g_lastError = std::string(entry) + ": point table exceeds the staging block"; return RUMI_E_CAPACITY; }
     const FrustumBlock fb(m->dStage, nmp);                  // (its flag array stays unused: mbTrackInView goes into the tracker's block)
     const FrustumArgs FA{nmp, n, m->dFeatMp, t->d.mpMotion, t->dLocal, t->dSeen, t->dBad, /*skip*/ m->dU8b, m->dOut, t->d.blk->pose19, fd.minX,
                          fd.minY, fd.maxX, fd.maxY, std::log(t->cfg.scale_factor), t->nlevels, 0.5f, m->dF[0], m->dF[1], m->dF[2], m->dF[3], t->d.view, fb.x, fb.y, fb.level, fb.viewCos, fb.depth,
                          m->dI[1], m->dScale, th_local, far_points, th_far_points, m->dQ,
-                         has_stale(pts) ? t->dStaleIn : nullptr, has_stale(pts) ? t->dStaleProj : nullptr};
+                         stale ? t->dStaleIn : nullptr, stale ? t->dStaleProj : nullptr};
     hipLaunchKernelGGL(k_track_frustum, dim3(grid_items(n, nmp)), dim3(256), 0, nullptr, FA);
     t->projN = nmp;
     return RUMI_OK;
@@ -566,6 +568,38 @@ void unpack_in_view(const RumiTracker *t, int nmp, bool localRan, uint8_t *in_vi
         for (int j = 0; j < nmp; j++) nTo += in_view[j] == 1;         // (2: a stale flag of an earlier frame, not an isInFrustum of this one)
     }
     res->n_to_match = nTo;
+}
+
+// TrackLocalMap from the point where the table, the frame's vector and the seen flags lie on the device: SearchLocalPoints' second loop, the
+// search (speculative, or sized after a list overflow), PoseOptimization and the statistics loop.  Ends with the block in the pinned mirror.
+int track_local_body(RumiTracker *t, const FrameDev &fd, int n, int nmp, bool stale, float th_local, int far_points, float th_far_points, const char *entry,
+                     RumiTrackResult *res) {
+    RumiMatcher *m = t->m;
+    int rc;
+    track_local_init(t, n, nmp);
+    bool speculate = false;
+    std::vector<int32_t> tmpMp((size_t)std::max(n, 1));
+    if (nmp > 0 && n > 0) {
+        if ((rc = launch_frustum(t, fd, nmp, stale, n, th_local, far_points, th_far_points, entry)) != RUMI_OK) return rc;
+        // the search's counts are not needed before the end: one queue, the result header travels in the block (a list overflow -- the resolve
+        // did not run then, the frame's vector is untouched -- sends the stage through the sizing path)
+        speculate = track_speculation().speculate && m->listCap / (size_t)nmp >= 64;
+        if ((rc = speculate ? speculative_search(t, MODE_MAPPOINTS, nmp, fd, 0.8f, 0, false, nullptr) : local_search(t, fd, nmp, tmpMp.data(), res)) != RUMI_OK) return rc;
+    }
+    const TrackBlock *hB = t->h.blk;
+    for (int pass = 0; pass < 2; pass++) {
+        if ((rc = pose_stage(t, fd, SLOT_LOCAL, true, TAIL_FINISH, speculate ? m->dOut : nullptr)) != RUMI_OK) return rc;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(t->hBlk, t->dBlk, t->oRec, hipMemcpyDeviceToHost));       // header, mvpMapPoints, mvbOutlier, mbTrackInView
+        if (!speculate) break;
+        if (hB->spec[3] == 0) { res->nmatches_local = hB->spec[2]; break; }
+        // a candidate list overflowed: the search again with exact list sizes, then the optimisation on its result
+        speculate = false;
+        track_local_init(t, n, nmp);
+        if ((rc = local_search(t, fd, nmp, tmpMp.data(), res)) != RUMI_OK) return rc;
+    }
+    unpack_local_pose(res, hB);
+    return RUMI_OK;
 }
 }  // namespace
 
@@ -642,7 +676,7 @@ extern "C" int rumi_track_frame(RumiTracker *t, const uint8_t *img, int32_t w, i
         if ((rc = pose_stage(t, fd, SLOT_MOTION, false, TAIL_AFTER_MOTION, header)) != RUMI_OK) return rc;
         // (k_track_after_motion and k_track_frustum as ONE 1024-thread workgroup -- the frustum test reads the seen flags and the pose matrices the
         // first half writes -- measured: 0.427-0.436 ms against 0.430-0.431 for the frame, no gain; not kept)
-        if ((rc = launch_frustum(t, fd, pts, n, th_local, far_points, th_far_points, "rumi_track_frame")) != RUMI_OK) return rc;
+        if ((rc = launch_frustum(t, fd, nmp, has_stale(pts), n, th_local, far_points, th_far_points, "rumi_track_frame")) != RUMI_OK) return rc;
         if ((rc = speculative_search(t, MODE_MAPPOINTS, nmp, fd, 0.8f, 0, true, nullptr)) != RUMI_OK) return rc;
         if ((rc = pose_stage(t, fd, SLOT_LOCAL, false, TAIL_FINISH, header)) != RUMI_OK) return rc;
         if ((rc = fetch_frame_block(t, n)) != RUMI_OK || (rc = rumi_orb_sync(t->ext)) != RUMI_OK) return rc;
@@ -666,7 +700,7 @@ extern "C" int rumi_track_frame(RumiTracker *t, const uint8_t *img, int32_t w, i
             // ---- stage 3: PoseOptimization on the matches, outliers leave the frame
             if ((rc = pose_stage(t, fd, SLOT_MOTION, true, TAIL_AFTER_MOTION, nullptr)) != RUMI_OK) return rc;
             // ---- stage 4: SearchLocalPoints with the optimised pose
-            if ((rc = launch_frustum(t, fd, pts, n, th_local, far_points, th_far_points, "rumi_track_frame")) != RUMI_OK) return rc;
+            if ((rc = launch_frustum(t, fd, nmp, has_stale(pts), n, th_local, far_points, th_far_points, "rumi_track_frame")) != RUMI_OK) return rc;
             if ((rc = local_search(t, fd, nmp, tmpMp.data(), res)) != RUMI_OK) return rc;
             localRan = true;
             // ---- stage 5: PoseOptimization on everything the frame now holds
@@ -869,31 +903,76 @@ extern "C" int rumi_track_local(RumiTracker *t, const float *K4, const float *Tc
     if ((rc = stage_points(t, pts, true)) != RUMI_OK) return rc;
     if (nmp > 0) H2D(t->dSeen, seen.data(), nmp);
     FLUSH(m);
-    track_local_init(t, n, nmp);
-    bool speculate = false;
-    std::vector<int32_t> tmpMp((size_t)std::max(n, 1));
-    if (nmp > 0 && n > 0) {
-        if ((rc = launch_frustum(t, fd, pts, n, th_local, far_points, th_far_points, "rumi_track_local")) != RUMI_OK) return rc;
-        // the search's counts are not needed before the end: one queue, the result header travels in the block (a list overflow -- the resolve
-        // did not run then, the frame's vector is untouched -- sends the stage through the sizing path)
-        speculate = track_speculation().speculate && m->listCap / (size_t)nmp >= 64;
-        if ((rc = speculate ? speculative_search(t, MODE_MAPPOINTS, nmp, fd, 0.8f, 0, false, nullptr) : local_search(t, fd, nmp, tmpMp.data(), res)) != RUMI_OK) return rc;
-    }
-    const TrackBlock *hB = t->h.blk;
-    for (int pass = 0; pass < 2; pass++) {
-        if ((rc = pose_stage(t, fd, SLOT_LOCAL, true, TAIL_FINISH, speculate ? m->dOut : nullptr)) != RUMI_OK) return rc;
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(t->hBlk, t->dBlk, t->oRec, hipMemcpyDeviceToHost));       // header, mvpMapPoints, mvbOutlier, mbTrackInView
-        if (!speculate) break;
-        if (hB->spec[3] == 0) { res->nmatches_local = hB->spec[2]; break; }
-        // a candidate list overflowed: the search again with exact list sizes, then the optimisation on its result
-        speculate = false;
-        track_local_init(t, n, nmp);
-        if ((rc = local_search(t, fd, nmp, tmpMp.data(), res)) != RUMI_OK) return rc;
-    }
-    unpack_local_pose(res, hB);
+    if ((rc = track_local_body(t, fd, n, nmp, has_stale(pts), th_local, far_points, th_far_points, "rumi_track_local", res)) != RUMI_OK) return rc;
     if (n > 0) { std::memcpy(frame_mp, t->h.mpOut, (size_t)n * 4); std::memcpy(outlier, t->h.outF, (size_t)n); }
     unpack_in_view(t, nmp, n > 0, in_view, res);
+    return RUMI_OK;
+}
+
+// Tracking::UpdateLocalMap + TrackLocalMap in one call: the store's local-map kernels, the table kernels of track_local_map.inc behind them in
+// the same queue, one read of the two headers (the later launches are sized by n_table), then rumi_track_local's stages on the table the
+// device built.  Nothing is written to the caller before the last stage has come back.
+extern "C" int rumi_track_local_map(RumiTracker *t, RumiCovis *c, const float *K4, const float *Tcw7, const int32_t *frame_points, int32_t n_discarded,
+                                    const int32_t *discarded_ids, const uint8_t *discarded_in_view, const float *discarded_proj5, float th_local,
+                                    int32_t far_points, float th_far_points, uint8_t *frame_point_bad, int32_t *local_kf, int32_t kf_cap, int32_t *n_k1,
+                                    int32_t *n_local_kf, int32_t *ref_kf, int32_t *table_ids, int32_t table_cap, int32_t *n_local_points, int32_t *n_table,
+                                    int32_t *frame_mp, uint8_t *outlier, uint8_t *in_view, RumiTrackResult *res) {
+    const char *entry = "rumi_track_local_map";
+    if (!t || !c || !K4 || !Tcw7 || !res || !n_k1 || !n_local_kf || !ref_kf || !n_local_points || !n_table || kf_cap < 0 || table_cap < 0 || n_discarded < 0 ||
+        (n_discarded > 0 && !discarded_ids) || (kf_cap > 0 && !local_kf) || (table_cap > 0 && (!table_ids || !in_view))) {
+        g_lastError = std::string(entry) + ": missing argument or negative count";
+        return RUMI_E_INVALID;
+    }
+    if (t->curN < 0) { g_lastError = std::string(entry) + ": no frame is resident (rumi_track_extract first)"; return RUMI_E_INVALID; }
+    RumiMatcher *m = t->m;
+    const int n = t->curN;
+    if (n > 0 && (!frame_points || !frame_point_bad || !frame_mp || !outlier)) { g_lastError = std::string(entry) + ": missing per-feature array"; return RUMI_E_INVALID; }
+    HIP_TRY(hipSetDevice(t->device));
+    RumiTrackResult r;
+    begin_entry(t, &r, Tcw7);
+    FrameDev fd;
+    int rc;
+    if ((rc = track_frame_dev(t, &fd)) != RUMI_OK || (rc = stage_pose(m, Tcw7, K4)) != RUMI_OK) return rc;
+    FLUSH(m);
+    // ---- UpdateLocalMap: the store's kernels; the lists stay on the device
+    const bool stale = discarded_in_view && discarded_proj5;
+    const CovisDiscarded disc{n_discarded, discarded_ids, stale ? discarded_in_view : nullptr, stale ? discarded_proj5 : nullptr};
+    CovisLocalView v;
+    if ((rc = covis_local_map_launch(c, n, frame_points, &disc, t->device, entry, &v)) != RUMI_OK) return rc;
+    // ---- the table: id -> row, the frame's extras and the discarded outliers in order, then the gather into the stages' arrays
+    const int rowCap = std::min(t->maxPts, table_cap);
+    const TableArgs TA{v, rowCap, m->dF[0], m->dF[1], m->dF[2], m->dF[3], m->dI[1], reinterpret_cast<uint32_t *>(m->dQDesc), t->dBad, t->dLocal, t->dSeen,
+                       t->dStaleIn, t->dStaleProj, m->dFeatMp, t->d.tableIds};
+    const int gRows = std::min(std::max(grid_of(rowCap), 1), 256);
+    hipLaunchKernelGGL(k_table_mark, dim3(gRows), dim3(256), 0, nullptr, TA);
+    if (n + n_discarded > 0) hipLaunchKernelGGL(k_table_claim, dim3(grid_of(n + n_discarded)), dim3(256), 0, nullptr, TA);
+    hipLaunchKernelGGL(k_table_extras, dim3(1), dim3(kTableThreads), 0, nullptr, TA);
+    hipLaunchKernelGGL(k_table_gather, dim3(gRows), dim3(256), 0, nullptr, TA);
+    const int32_t *head, *kfs;
+    const uint8_t *bad;
+    if ((rc = covis_local_map_read(c, v, &head, &bad, &kfs)) != RUMI_OK) return rc;
+    const int nK1 = head[0], nKf = head[1], refKf = head[2], nLocal = head[3], nmp = head[4], nMissing = head[5];
+    if (nMissing > 0) {
+        g_lastError = std::string(entry) + ": " + std::to_string(nMissing) + " local or frame point(s) without attributes (rumi_covis_set_point_attributes)";
+        return RUMI_E_INVALID;
+    }
+    if (nKf > kf_cap || nmp > table_cap || nmp > t->maxPts) {
+        g_lastError = std::string(entry) + ": kf_cap, table_cap or the tracker's max_points is too small for the lists";
+        return RUMI_E_CAPACITY;
+    }
+    // ---- TrackLocalMap on that table
+    // (the row ids travel behind the stages and are on the host when the body's copy of the result block returns)
+    if (nmp > 0) HIP_TRY(hipMemcpyAsync(t->h.tableIds, t->d.tableIds, (size_t)nmp * 4, hipMemcpyDeviceToHost, nullptr));
+    if ((rc = track_local_body(t, fd, n, nmp, stale, th_local, far_points, th_far_points, entry, &r)) != RUMI_OK) return rc;
+    // ---- write-out
+    if (n > 0) std::memcpy(frame_point_bad, bad, (size_t)n);
+    if (nKf > 0) std::memcpy(local_kf, kfs, (size_t)nKf * 4);
+    *n_k1 = nK1; *n_local_kf = nKf; *ref_kf = refKf; *n_local_points = nLocal; *n_table = nmp;
+    if (nmp > 0) std::memcpy(table_ids, t->h.tableIds, (size_t)nmp * 4);
+    for (int i = 0; i < n; i++) { const int row = t->h.mpOut[i]; frame_mp[i] = row >= 0 ? t->h.tableIds[row] : -1; }
+    if (n > 0) std::memcpy(outlier, t->h.outF, (size_t)n);
+    unpack_in_view(t, nmp, n > 0, in_view, &r);
+    *res = r;
     return RUMI_OK;
 }
 

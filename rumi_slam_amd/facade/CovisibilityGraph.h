@@ -13,6 +13,10 @@
 //   UpdateLocalMap(frame, ..) one device call; writes the frame's NULLed points, mvpLocalKeyFrames, mvpLocalMapPoints, mpReferenceKF and the
 //                             mnTrackReferenceForFrame stamps.  The inertial branches (Tracking.cc:3106-3123, :3190-3204) are refused with
 //                             a report: the ABI does not express them.
+//   SyncAttributes(points)    stages position, normal, distances and descriptor of the listed points (rumi_covis_set_point_attributes): what
+//                             rumi_facade::TrackLocalMapResident (TrackingStep.h) builds its point table from on the device.  MarkDirty(p)
+//                             notes a point whose SetWorldPos / UpdateNormalAndDepth / ComputeDistinctiveDescriptors has run (any thread's
+//                             caller serialises, as for Sync); FlushDirty() stages the noted points, once each, before the frame's query.
 // Errors follow rumi_status.h: reported, never thrown; the member returns without having written anything.
 #pragma once
 #include <cstdint>
@@ -41,6 +45,57 @@ template <class KeyFrameT, class MapPointT> class CovisibilityGraph {
     template <class MapT> int SyncAll(MapT *pMap) {
         const int rc = sync_keyframes(pMap->GetAllKeyFrames());
         return rc != RUMI_OK ? rc : sync_points(pMap->GetAllMapPoints());
+    }
+
+    // ---- the attributes TrackLocalMap reads (GetWorldPos, GetNormal, GetMinDistance, GetMaxDistance, GetDescriptor)
+    int SyncAttributes(const std::vector<MapPointT *> &vpMPs) {
+        if (!h_) return RUMI_E_INVALID;
+        std::vector<MapPointT *> unseen;
+        std::set<MapPointT *> in;
+        std::vector<int32_t> ids;
+        std::vector<float> pos, nrm, mn, mx;
+        std::vector<uint8_t> desc;
+        for (MapPointT *p : vpMPs)
+            if (p && in.insert(p).second && !id_.count(p)) unseen.push_back(p);
+        int rc;
+        if (!unseen.empty() && (rc = sync_points(unseen)) != RUMI_OK) return rc;
+        for (MapPointT *p : in) {
+            ids.push_back(id_[p]);
+            const auto P = p->GetWorldPos(), N = p->GetNormal();
+            for (int c = 0; c < 3; c++) { pos.push_back(P(c)); nrm.push_back(N(c)); }
+            mn.push_back(p->GetMinDistance()); mx.push_back(p->GetMaxDistance());
+            const auto d = p->GetDescriptor();
+            desc.insert(desc.end(), d.ptr(0), d.ptr(0) + 32);
+            dirty_.erase(p);
+        }
+        if (ids.empty()) return RUMI_OK;
+        rc = rumi_covis_set_point_attributes(h_, (int32_t)ids.size(), ids.data(), pos.data(), nrm.data(), mn.data(), mx.data(), desc.data());
+        if (rc != RUMI_OK) rumi_facade::report("CovisibilityGraph::SyncAttributes", rc);
+        return rc;
+    }
+    void MarkDirty(MapPointT *pMP) { if (pMP) dirty_.insert(pMP); }
+    size_t DirtyCount() const { return dirty_.size(); }
+    int FlushDirty() {
+        if (dirty_.empty()) return RUMI_OK;
+        return SyncAttributes(std::vector<MapPointT *>(dirty_.begin(), dirty_.end()));
+    }
+
+    // ---- for the callers that drive the store themselves (TrackingStep.h): the handle, and objects <-> slots and ids
+    RumiCovis *handle() const { return h_; }
+    int KeyFrameCount() const { return (int)kfs_.size(); }
+    int PointCount() const { return (int)pts_.size(); }
+    KeyFrameT *KeyFrameAt(int slot) const { return kfs_[slot]; }
+    MapPointT *PointAt(int id) const { return pts_[id]; }
+    // the id of a point, staging it first when the store has not seen it (-1 on failure)
+    int IdOf(MapPointT *pMP) {
+        auto it = id_.find(pMP);
+        if (it != id_.end()) return it->second;
+        if (sync_points(std::vector<MapPointT *>{pMP}) != RUMI_OK) return -1;
+        return id_[pMP];
+    }
+    int64_t LastUploadBytes() const {
+        int64_t v[7] = {0, 0, 0, 0, 0, 0, 0};
+        return h_ && rumi_covis_stats(h_, v) == RUMI_OK ? v[6] : -1;
     }
 
     // KeyFrame::UpdateConnections for every key-frame of the list, in this order.  cloud: UpdateCloudConnections (the parent is the first of
@@ -142,6 +197,7 @@ template <class KeyFrameT, class MapPointT> class CovisibilityGraph {
     std::unordered_map<MapPointT *, int32_t> id_;
     std::vector<KeyFrameT *> kfs_;
     std::vector<MapPointT *> pts_;
+    std::set<MapPointT *> dirty_;
 
     int32_t slot_of(KeyFrameT *k, std::vector<KeyFrameT *> &work) {                      // a key-frame the store has not seen joins the call
         auto it = slot_.find(k);

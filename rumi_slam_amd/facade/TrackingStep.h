@@ -392,6 +392,90 @@ int TrackLocalMap(FrameT &Cur, const std::vector<MapPointT *> &vpLocalMapPoints,
     return r.matches_inliers;
 }
 
+// Tracking::UpdateLocalMap() + Tracking::TrackLocalMap() in ONE device call (rumi_track_local_map) on a CovisibilityGraph (CovisibilityGraph.h)
+// whose points carry their attributes: the graph's dirty points are flushed, the device votes, builds the local map and the point table, and
+// runs SearchLocalPoints, PoseOptimization and the statistics loop on it.  The host then replays what the two members write: the frame's
+// NULLed bad points, mvpLocalKeyFrames, mvpLocalMapPoints, mpReferenceKF and the mnTrackReferenceForFrame stamps (UpdateLocalMap), then the
+// loops of TrackLocalMap above, on the table rows the device reports.  The discarded outliers of the previous function are the points with
+// mnLastFrameSeen == Cur.mnId that the frame does not hold; the caller passes them (TrackWithMotionModel's / TrackReferenceKeyFrame's replay
+// stamps them) as vpDiscarded -- the store cannot enumerate MapPoints by a member's value.  Returns mnMatchesInliers (-1: error, nothing written).
+template <class FrameT, class GraphT, class KeyFrameT, class MapPointT>
+int TrackLocalMapResident(FrameT &Cur, GraphT &graph, const std::vector<MapPointT *> &vpDiscarded, std::vector<KeyFrameT *> &vpLocalKeyFrames,
+                          std::vector<MapPointT *> &vpLocalMapPoints, KeyFrameT *&pReferenceKF, float thLocal, bool bFarPoints, float thFarPoints, TrackStep *out) {
+    const char *where = "TrackLocalMapResident";
+    TrackStep st = out ? *out : TrackStep();
+    RumiTracker *t = tracker_slot();
+    if (!t || !graph.ok()) { report("TrackLocalMapResident: ExtractFrame has not run on this thread, or no store", RUMI_E_INVALID); return -1; }
+    int rc;
+    if ((rc = graph.FlushDirty()) != RUMI_OK) return -1;
+    std::vector<int32_t> fp(Cur.N > 0 ? Cur.N : 1, -1);
+    for (int i = 0; i < Cur.N; i++)
+        if (Cur.mvpMapPoints[i] && (fp[i] = graph.IdOf(Cur.mvpMapPoints[i])) < 0) return -1;
+    std::vector<int32_t> disc;
+    std::vector<uint8_t> discIn;
+    std::vector<float> discProj;
+    for (MapPointT *p : vpDiscarded) {
+        if (!p || p->mnLastFrameSeen != Cur.mnId) continue;
+        const int id = graph.IdOf(p);
+        if (id < 0) return -1;
+        if (std::find(disc.begin(), disc.end(), id) != disc.end()) continue;
+        disc.push_back(id); discIn.push_back(p->mbTrackInView ? 1 : 0);
+        const float sp[5] = {p->mTrackProjX, p->mTrackProjY, (float)p->mnTrackScaleLevel, p->mTrackViewCos, p->mTrackDepth};
+        discProj.insert(discProj.end(), sp, sp + 5);
+    }
+    const int kfCap = graph.KeyFrameCount() + 1, cap = std::min(graph.PointCount() + 1, tracker_points());
+    std::vector<uint8_t> bad(fp.size(), 0), outl(fp.size(), 0), inView(cap, 0);
+    std::vector<int32_t> lk(kfCap), ids(cap), mp(fp.size(), -1);
+    int32_t nK1 = 0, nK = 0, ref = -1, nLocal = 0, np = 0;
+    float T7[7];
+    track_detail::get_pose(Cur, T7);
+    const float K4[4] = {Cur.fx, Cur.fy, Cur.cx, Cur.cy};
+    RumiTrackResult r;
+    rc = rumi_track_local_map(t, graph.handle(), K4, T7, fp.data(), (int32_t)disc.size(), disc.data(), discIn.data(), discProj.data(), thLocal, bFarPoints ? 1 : 0,
+                              thFarPoints, bad.data(), lk.data(), kfCap, &nK1, &nK, &ref, ids.data(), cap, &nLocal, &np, mp.data(), outl.data(), inView.data(), &r);
+    if (rc != RUMI_OK) { report(where, rc); return -1; }
+    // ---- UpdateLocalMap's writes (Tracking.cc:3067-3210)
+    for (int i = 0; i < Cur.N; i++)
+        if (bad[i]) Cur.mvpMapPoints[i] = nullptr;                                           // :3102
+    vpLocalKeyFrames.clear();
+    for (int i = 0; i < nK; i++) { vpLocalKeyFrames.push_back(graph.KeyFrameAt(lk[i])); graph.KeyFrameAt(lk[i])->mnTrackReferenceForFrame = Cur.mnId; }
+    vpLocalMapPoints.clear();
+    for (int j = 0; j < nLocal; j++) { vpLocalMapPoints.push_back(graph.PointAt(ids[j])); graph.PointAt(ids[j])->mnTrackReferenceForFrame = Cur.mnId; }
+    if (ref >= 0) { pReferenceKF = graph.KeyFrameAt(ref); Cur.mpReferenceKF = pReferenceKF; }
+    // ---- TrackLocalMap's loops over Frame and MapPoint objects, in their order (as TrackLocalMap above)
+    for (int i = 0; i < Cur.N; i++) {                        // SearchLocalPoints, first loop (:2998-3010)
+        MapPointT *p = Cur.mvpMapPoints[i];
+        if (!p) continue;
+        if (p->isBad()) { Cur.mvpMapPoints[i] = nullptr; continue; }
+        p->IncreaseVisible(); p->mnLastFrameSeen = Cur.mnId; p->mbTrackInView = false;
+    }
+    std::vector<float> pr((size_t)(np > 0 ? np : 1) * 5);
+    if (np > 0 && Cur.N > 0 && (rc = rumi_track_last_projections(t, np, pr.data())) != RUMI_OK) report("rumi_track_last_projections", rc);
+    for (int j = 0; j < nLocal; j++) {                       // second loop (:3015-3030)
+        MapPointT *p = graph.PointAt(ids[j]);
+        if (p->mnLastFrameSeen == Cur.mnId || p->isBad()) continue;
+        p->mbTrackInView = inView[j] != 0;
+        if (inView[j]) p->IncreaseVisible();
+    }
+    if (rc == RUMI_OK && Cur.N > 0)
+        for (int j = 0; j < np; j++) {                       // Frame::isInFrustum's writes into the points it accepted
+            if (inView[j] != 1) continue;
+            MapPointT *p = graph.PointAt(ids[j]);
+            const float *sp = &pr[(size_t)j * 5];
+            p->mTrackProjX = sp[0]; p->mTrackProjY = sp[1]; p->mnTrackScaleLevel = (int)sp[2]; p->mTrackViewCos = sp[3]; p->mTrackDepth = sp[4];
+        }
+    for (int i = 0; i < Cur.N; i++) {                        // TrackLocalMap (:2573-2586)
+        Cur.mvpMapPoints[i] = mp[i] >= 0 ? graph.PointAt(mp[i]) : nullptr;
+        Cur.mvbOutlier[i] = mp[i] >= 0 && outl[i] != 0;
+        if (mp[i] >= 0 && !outl[i]) graph.PointAt(mp[i])->IncreaseFound();
+    }
+    track_detail::set_pose(Cur, r.Tcw);
+    st.nToMatch = r.n_to_match; st.nmatchesLocal = r.nmatches_local; st.ngoodLocal = r.ngood_local; st.mnMatchesInliers = r.matches_inliers; st.ranLocal = true;
+    std::memcpy(st.Tcw, r.Tcw, 28);
+    if (out) *out = st;
+    return r.matches_inliers;
+}
+
 // The fused form: extraction, TrackWithMotionModel and TrackLocalMap in ONE device call, for a caller that supplies the local set ITSELF --
 // vpLocalMapPoints must not be the result of an UpdateLocalMap() on this (still empty) frame; the local map of the previous frame's
 // TrackLocalMap is the natural choice (the reference rebuilds it from the new matches, which mostly re-elects the same key-frames).

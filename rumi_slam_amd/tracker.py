@@ -47,6 +47,8 @@ def _bind(L):
     L.rumi_track_reference_keyframe.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, C.POINTER(RumiTrackPoints), f32, i32, vp, vp, vp, vp, vp,
                                                 C.POINTER(RumiTrackResult)]
     L.rumi_track_local.argtypes = [vp, vp, vp, vp, C.POINTER(RumiTrackPoints), vp, f32, i32, f32, vp, vp, vp, C.POINTER(RumiTrackResult)]
+    L.rumi_track_local_map.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, f32, i32, f32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp,
+                                       C.POINTER(RumiTrackResult)]
     L.rumi_track_last_projections.argtypes = [vp, i32, vp]
     L.rumi_track_set_distortion.argtypes = [vp, vp, vp]
     L.rumi_track_undistorted.argtypes = [vp, vp, i32, vp]
@@ -63,6 +65,7 @@ class Tracker:
         self._lib = _bind(capi.lib())
         self.cfg = RumiOrbConfig(nfeatures, scale_factor, nlevels, ini_th, min_th, max_width, max_height, 1, device, 0, blur_variant)
         self.cap = nfeatures + 4 * nlevels + 64
+        self.max_points = int(max_points)
         self._h = C.c_void_p()
         capi.check(self._lib.rumi_track_create(C.byref(self.cfg), int(max_points), int(device), C.byref(self._h)))
 
@@ -205,4 +208,50 @@ class Tracker:
                                               float(th_local), int(far_points), float(th_far_points), capi.ptr(mp), capi.ptr(outl), capi.ptr(in_view), C.byref(res)))
         out = self._result(res, ("n", "n_to_match", "nmatches_local", "ngood_local", "matches_inliers", "Tcw", "Rcw", "tcw", "Ow"))
         out.update(frame_mp=mp[:res.n].copy(), outlier=outl[:res.n].copy(), in_view=in_view[:n].copy())
+        return out
+
+    @staticmethod
+    def local_map_outputs(n, kf_cap, table_cap, fill=0):
+        """The output arrays of local_map_into, every byte = fill."""
+        f = lambda m, dt=np.int32: np.frombuffer(bytes([fill]) * (max(int(m), 1) * np.dtype(dt).itemsize), dt).copy()
+        return dict(frame_point_bad=f(n, np.uint8), local_kf=f(kf_cap), n_k1=f(1), n_local_kf=f(1), ref_kf=f(1), table_ids=f(table_cap), n_local_points=f(1),
+                    n_table=f(1), frame_mp=f(n), outlier=f(n, np.uint8), in_view=f(table_cap, np.uint8), res=f(C.sizeof(RumiTrackResult), np.uint8))
+
+    def local_map_into(self, cov, K4, Tcw7, frame_points, out, kf_cap, table_cap, discarded=None, discarded_in_view=None, discarded_proj=None, th_local=1.0,
+                       far_points=False, th_far_points=50.0):
+        """The raw rumi_track_local_map call: status code; results in `out` (local_map_outputs)."""
+        K4 = np.ascontiguousarray(K4, np.float32); T = np.ascontiguousarray(Tcw7, np.float32)
+        fp = np.ascontiguousarray(frame_points, np.int32)
+        assert getattr(self, "_n", None) is None or len(fp) >= self._n, f"frame_points has {len(fp)} entries, the resident frame {self._n} features"
+        di = np.ascontiguousarray(discarded if discarded is not None else [], np.int32)
+        dv = np.ascontiguousarray(discarded_in_view, np.uint8) if discarded_in_view is not None else None
+        dp = np.ascontiguousarray(discarded_proj, np.float32).reshape(-1, 5) if discarded_proj is not None else None
+        assert (dv is None) == (dp is None) and (dv is None or len(dv) == len(dp) == len(di))
+        o = out
+        return self._lib.rumi_track_local_map(self._h, cov._h, capi.ptr(K4), capi.ptr(T), capi.ptr(fp), len(di), capi.ptr(di), capi.ptr(dv) if dv is not None else None,
+                                              capi.ptr(dp) if dp is not None else None, float(th_local), int(far_points), float(th_far_points),
+                                              capi.ptr(o["frame_point_bad"]), capi.ptr(o["local_kf"]), int(kf_cap), capi.ptr(o["n_k1"]), capi.ptr(o["n_local_kf"]),
+                                              capi.ptr(o["ref_kf"]), capi.ptr(o["table_ids"]), int(table_cap), capi.ptr(o["n_local_points"]), capi.ptr(o["n_table"]),
+                                              capi.ptr(o["frame_mp"]), capi.ptr(o["outlier"]), capi.ptr(o["in_view"]),
+                                              C.cast(capi.ptr(o["res"]), C.POINTER(RumiTrackResult)))
+
+    def local_map(self, cov, K4, Tcw7, frame_points, discarded=None, discarded_in_view=None, discarded_proj=None, th_local=1.0, far_points=False,
+                  th_far_points=50.0, kf_cap=None, table_cap=None):
+        """rumi_track_local_map: Tracking::UpdateLocalMap + TrackLocalMap on the resident frame and the covisibility store `cov`
+        (rumi_slam_amd.covis.Covisibility, its points carrying attributes).  frame_points: point ids, -1 = NULL; discarded: the ids the previous
+        function discarded as outliers, discarded_in_view / discarded_proj their stale mbTrackInView and projections.
+        -> the dict of Covisibility.local_map (local_points = the first rows of the table) and of Tracker.local (frame_mp in point ids,
+        in_view per table row), plus table_ids."""
+        kf_cap = cov.max_kf if kf_cap is None else kf_cap
+        table_cap = min(cov.max_points, self.max_points) if table_cap is None else table_cap
+        n = len(frame_points)
+        o = self.local_map_outputs(n, kf_cap, table_cap)
+        capi.check(self.local_map_into(cov, K4, Tcw7, frame_points, o, kf_cap, table_cap, discarded, discarded_in_view, discarded_proj, th_local, far_points,
+                                       th_far_points))
+        res = RumiTrackResult.from_buffer_copy(o["res"].tobytes())
+        nt, nl = int(o["n_table"][0]), int(o["n_local_points"][0])
+        out = self._result(res, ("n", "n_to_match", "nmatches_local", "ngood_local", "matches_inliers", "Tcw", "Rcw", "tcw", "Ow"))
+        out.update(frame_point_bad=o["frame_point_bad"][:n], local_kf=o["local_kf"][:int(o["n_local_kf"][0])], n_k1=int(o["n_k1"][0]), ref_kf=int(o["ref_kf"][0]),
+                   local_points=o["table_ids"][:nl].copy(), table_ids=o["table_ids"][:nt], frame_mp=o["frame_mp"][:res.n], outlier=o["outlier"][:res.n],
+                   in_view=o["in_view"][:nt])
         return out
