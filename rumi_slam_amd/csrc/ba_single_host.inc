@@ -136,15 +136,11 @@ static int ba_big_prepare(RumiOptimizer *o, hipStream_t st, const BaLayout &L, i
     for_pairs([&](size_t key, int ia, int ib) { const int64_t at = cnt[key]++; pairs[2 * at] = ptEdge[ia]; pairs[2 * at + 1] = ptEdge[ib]; });
     *nBlocksOut = (int)(blk.size() / 4);
     const size_t need = (blk.size() + pairs.size()) * sizeof(int32_t);
-    if (need > o->pairCap) {
-        if (o->dPairs) (void)hipFree(o->dPairs);
-        o->dPairs = nullptr; o->pairCap = 0;
-        HIP_TRY(hipMalloc((void **)&o->dPairs, need + need / 4));
-        o->pairCap = need + need / 4;
-    }
+    { const int rcp = o->pairs.reserve(need, need + need / 4); if (rcp != RUMI_OK) return rcp; }
+    int32_t *dPairs = reinterpret_cast<int32_t *>(o->pairs.p);
     o->pairOff = blk.size();
-    if (!blk.empty()) HIP_TRY(hipMemcpyAsync(o->dPairs, blk.data(), blk.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(o->dPairs + blk.size(), pairs.data(), pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (!blk.empty()) HIP_TRY(hipMemcpyAsync(dPairs, blk.data(), blk.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dPairs + blk.size(), pairs.data(), pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));                 // blk / pairs are temporaries
     if (!o->dW) { int rcw = dev_alloc(&o->dW, (size_t)o->maxE * 18); if (rcw == RUMI_OK) rcw = dev_alloc(&o->dColOf, (size_t)o->maxE); if (rcw != RUMI_OK) return rcw; }
     // more than 64 KiB of dynamic LDS needs the opt-in; the limit is process state and only grows (rumi_common.h: raise_lds_limit), so that the
@@ -166,7 +162,8 @@ static int ba_solve_big(RumiOptimizer *o, hipStream_t st, const BADev &B, const 
         hipLaunchKernelGGL(k_ba_dinv, dim3((nMP + 255) / 256), dim3(256), 0, st, Bz, lambda, o->dYt, 1, o->dLp);
         if (nE > 0) {
             hipLaunchKernelGGL(k_big_w, dim3(P.gE), dim3(256), 0, st, B, o->dLp, o->dW, o->dColOf);
-            if (P.nBlocks > 0) hipLaunchKernelGGL(k_big_schur, dim3((P.nBlocks + 3) / 4), dim3(256), 0, st, B, o->dPairs, P.nBlocks, o->dPairs + o->pairOff, o->dW, o->dYt, A, ld);
+            const int32_t *dPairs = reinterpret_cast<const int32_t *>(o->pairs.p);
+            if (P.nBlocks > 0) hipLaunchKernelGGL(k_big_schur, dim3((P.nBlocks + 3) / 4), dim3(256), 0, st, B, dPairs, P.nBlocks, dPairs + o->pairOff, o->dW, o->dYt, A, ld);
         }
     }
     for (int j0 = 0; j0 < n; j0 += kNB) {

@@ -292,19 +292,12 @@ struct BawGroup {
         // every window's block [T | X | erase | err] into ONE buffer of the group: one copy back instead of one per window
         size_t total = 0;
         for (int j = 0; j < L; j++) { prep[live[j]].outOff = total; total += (prep[live[j]].dnBytes + 255) & ~(size_t)255; }
-        if (total > o->groupOutCap) {
-            if (o->dGroupOut) (void)hipFree(o->dGroupOut);
-            if (o->hGroupOut) (void)hipHostFree(o->hGroupOut);
-            o->dGroupOut = nullptr; o->hGroupOut = nullptr; o->groupOutCap = 0;
-            const size_t cap = total + total / 2;
-            if (hipMalloc((void **)&o->dGroupOut, cap) != hipSuccess || hipHostMalloc((void **)&o->hGroupOut, cap, hipHostMallocDefault) != hipSuccess) return RUMI_E_NO_DEVICE;
-            o->groupOutCap = cap;
-        }
+        { const int rcg = o->groupOut.reserve(total, total + total / 2); if (rcg != RUMI_OK) return rcg; }
         for (int j = 0; j < L; j++) {
             const BawPrep &P = prep[live[j]];
             BAWin &Wd = tab()[j];
             Wd.useLast = P.ran ? 1 : 0; Wd.cur0 = P.cur;
-            uint8_t *base = o->dGroupOut + P.outOff;
+            uint8_t *base = o->groupOut.d + P.outOff;
             Wd.outT = reinterpret_cast<double *>(base + P.rT); Wd.outX = reinterpret_cast<double *>(base + P.rX); Wd.erase = base + P.rE;
             Wd.errOut = reinterpret_cast<int32_t *>(base + P.rErr);
         }
@@ -312,7 +305,7 @@ struct BawGroup {
         hipLaunchKernelGGL(k_baw_finalize, dim3(maxF, L), dim3(256), 0, st(), o->dWinTab);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(o->ev[1], st()));
-        HIP_TRY(hipMemcpyAsync(o->hGroupOut, o->dGroupOut, total, hipMemcpyDeviceToHost, st()));
+        HIP_TRY(hipMemcpyAsync(o->groupOut.h, o->groupOut.d, total, hipMemcpyDeviceToHost, st()));
         phase = kFinalWait;
         return RUMI_OK;
     }
@@ -325,7 +318,7 @@ struct BawGroup {
             const int i = live[j];
             const BawArgs &a = args[i];
             const BawPrep &P = prep[i];
-            const uint8_t *hb = o->hGroupOut + P.outOff;
+            const uint8_t *hb = o->groupOut.h + P.outOff;
             const int32_t err = *reinterpret_cast<const int32_t *>(hb + P.rErr);
             if (err) {                                      // nothing of this window is written back
                 g_lastError = (err & 1) ? "local BA: edge index out of range" : "local BA: a map point is observed twice by one key-frame";

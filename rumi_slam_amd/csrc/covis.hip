@@ -303,8 +303,7 @@ template <int PASS> __global__ __launch_bounds__(kThreads) void k_covis_local(Lo
 using namespace rumi;
 
 struct RumiCovis {
-    int device = -1;
-    bool bound = false;
+    DeviceBinding dev;
     int32_t maxKf = 0, maxPts = 0;
     // host mirrors of the device tables
     std::vector<int32_t> kf, pt, arena, attr;        // attr: empty until the first rumi_covis_set_point_attributes
@@ -320,15 +319,12 @@ struct RumiCovis {
     std::vector<int4> recs;                          // table, first word, -, words
     bool full[kTables] = {true, true, true, true};
     // device
-    int32_t *dKf = nullptr, *dPt = nullptr, *dArena = nullptr, *dAttr = nullptr;
-    unsigned long long *dRowOf = nullptr;
+    DevBuf<int32_t> dKf, dPt, dArena, dAttr;         // dKf, dPt, dTag: with the first bind; dAttr, dRowOf: with their first use; dArena follows the mirror
+    DevBuf<unsigned long long> dTag, dRowOf;
     std::vector<uint8_t> extra;                      // the input block of rumi_track_local_map: frame points and the discarded outliers
-    std::chrono::steady_clock::time_point tq[2];     // start of the query in flight, and of its device part
-    size_t dArenaCap = 0;
-    unsigned long long *dTag = nullptr;
+    StageClock clock;                                // of the query in flight (the local-map query is launched and read in two calls)
     uint32_t epoch = 0;
-    uint8_t *hStage = nullptr, *dStage = nullptr; size_t stageCap = 0;
-    uint8_t *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;
+    MirrorBuf<uint8_t> stage, out;
     float stageMs[3] = {0.f, 0.f, 0.f};
 };
 
@@ -390,21 +386,16 @@ void set_row(RumiCovis *h, int32_t &off, int32_t &len, int32_t &c, const int32_t
     note(h, T_ARENA, off, n);
 }
 
+// The store's device, and with the first bind its fixed tables; bound only once they are in place.
 int bind_device(RumiCovis *h) {
-    if (h->bound) return hipSetDevice(h->device) == hipSuccess ? RUMI_OK : RUMI_E_NO_DEVICE;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        g_lastError = "no HIP device visible: librumi_hip has no CPU fallback";
-        return RUMI_E_NO_DEVICE;
-    }
-    if (h->device < 0 && hipGetDevice(&h->device) != hipSuccess) h->device = 0;
-    HIP_TRY(hipSetDevice(h->device));
-    int rc;
-    if ((rc = dev_alloc(&h->dKf, (size_t)h->maxKf * KFW)) != RUMI_OK || (rc = dev_alloc(&h->dPt, (size_t)h->maxPts * PTW)) != RUMI_OK ||
-        (rc = dev_alloc(&h->dTag, (size_t)h->maxPts)) != RUMI_OK)
+    bool first;
+    int rc = h->dev.bind(&first);
+    if (rc != RUMI_OK || !first) return rc;
+    const size_t nKf = (size_t)h->maxKf * KFW, nPt = (size_t)h->maxPts * PTW, nTag = (size_t)h->maxPts;
+    if ((rc = h->dKf.reserve(nKf, nKf)) != RUMI_OK || (rc = h->dPt.reserve(nPt, nPt)) != RUMI_OK || (rc = h->dTag.reserve(nTag, nTag)) != RUMI_OK)
         return rc;
-    HIP_TRY(hipMemsetAsync(h->dTag, 0, (size_t)h->maxPts * 8, nullptr));
-    h->bound = true;
+    HIP_TRY(hipMemsetAsync(h->dTag.p, 0, (size_t)h->maxPts * 8, nullptr));
+    h->dev.bound = true;
     return RUMI_OK;
 }
 
@@ -413,29 +404,22 @@ int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) 
     int rc;
     if ((rc = bind_device(h)) != RUMI_OK) return rc;
     if (h->recs.size() > (1u << 16)) { std::fill(h->full, h->full + kTables, true); }
-    if (h->arena.size() > h->dArenaCap) {
-        h->dArenaCap = 0;
-        if ((rc = regrow(&h->dArena, h->arena.size() * 4, false)) != RUMI_OK) return rc;
-        h->dArenaCap = h->arena.size();
+    if (h->arena.size() > h->dArena.cap) {
+        if ((rc = h->dArena.reserve(h->arena.size(), h->arena.size())) != RUMI_OK) return rc;
         h->full[T_ARENA] = true;
     }
-    if (h->hiAttr > 0 && !h->dAttr) {
-        if ((rc = dev_alloc(&h->dAttr, (size_t)h->maxPts * ATW)) != RUMI_OK) return rc;
+    if (h->hiAttr > 0 && !h->dAttr.p) {
+        if ((rc = h->dAttr.reserve((size_t)h->maxPts * ATW, (size_t)h->maxPts * ATW)) != RUMI_OK) return rc;
         h->full[T_ATTR] = true;
     }
-    int32_t *dBase[kTables] = {h->dKf, h->dPt, h->dArena, h->dAttr};
+    int32_t *dBase[kTables] = {h->dKf.p, h->dPt.p, h->dArena.p, h->dAttr.p};
     const std::vector<int32_t> *mirror[kTables] = {&h->kf, &h->pt, &h->arena, &h->attr};
     size_t words = 0, nRec = 0;
     for (int4 &r : h->recs)
         if (!h->full[r.x]) { r.z = (int)words; words += (size_t)r.w; h->recs[nRec++] = r; }
     h->recs.resize(nRec);
     const size_t offPay = up16(nRec * 16), offExtra = offPay + up16(words * 4), bytes = offExtra + up16(extraBytes);
-    if (bytes > h->stageCap) {
-        const size_t want = bytes + bytes / 4 + 4096;
-        h->stageCap = 0;
-        if ((rc = regrow(&h->hStage, want, true)) != RUMI_OK || (rc = regrow(&h->dStage, want, false)) != RUMI_OK) return rc;
-        h->stageCap = want;
-    }
+    if ((rc = h->stage.reserve(bytes, bytes + bytes / 4 + 4096)) != RUMI_OK) return rc;
     h->lastUpload = (int64_t)bytes;
     for (int t = 0; t < kTables; t++)
         if (h->full[t]) {
@@ -443,42 +427,25 @@ int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) 
             if (n) HIP_TRY(hipMemcpyAsync(dBase[t], mirror[t]->data(), n * 4, hipMemcpyHostToDevice, nullptr));
             h->lastUpload += (int64_t)n * 4;
         }
-    if (nRec) std::memcpy(h->hStage, h->recs.data(), nRec * 16);
-    int32_t *pay = reinterpret_cast<int32_t *>(h->hStage + offPay);
+    if (nRec) std::memcpy(h->stage.h, h->recs.data(), nRec * 16);
+    int32_t *pay = reinterpret_cast<int32_t *>(h->stage.h + offPay);
     for (const int4 &r : h->recs) std::memcpy(pay + r.z, mirror[r.x]->data() + r.y, (size_t)r.w * 4);
-    if (extraBytes) std::memcpy(h->hStage + offExtra, extra, extraBytes);
-    if (bytes) HIP_TRY(hipMemcpyAsync(h->dStage, h->hStage, bytes, hipMemcpyHostToDevice, nullptr));
+    if (extraBytes) std::memcpy(h->stage.h + offExtra, extra, extraBytes);
+    if (bytes) HIP_TRY(hipMemcpyAsync(h->stage.d, h->stage.h, bytes, hipMemcpyHostToDevice, nullptr));
     if (nRec) {
         ApplyArgs a;
         for (int t = 0; t < kTables; t++) a.base[t] = dBase[t];
-        a.recs = reinterpret_cast<const int4 *>(h->dStage);
-        a.payload = reinterpret_cast<const int32_t *>(h->dStage + offPay);
+        a.recs = reinterpret_cast<const int4 *>(h->stage.d);
+        a.payload = reinterpret_cast<const int32_t *>(h->stage.d + offPay);
         hipLaunchKernelGGL(k_covis_apply, dim3((unsigned)nRec), dim3(64), 0, nullptr, a);
     }
     h->recs.clear();
     std::fill(h->full, h->full + kTables, false);
-    *dExtra = h->dStage + offExtra;
-    return RUMI_OK;
-}
-
-int grow_out(RumiCovis *h, size_t bytes) {
-    if (bytes <= h->outCap) return RUMI_OK;
-    int rc;
-    const size_t want = bytes + bytes / 4;
-    h->outCap = 0;
-    if ((rc = regrow(&h->hOut, want, true)) != RUMI_OK || (rc = regrow(&h->dOut, want, false)) != RUMI_OK) return rc;
-    h->outCap = want;
+    *dExtra = h->stage.d + offExtra;
     return RUMI_OK;
 }
 
 inline bool is_live(const RumiCovis *h, int32_t s) { return s >= 0 && s < h->maxKf && (h->kf[(size_t)s * KFW + K_FLAGS] & 2); }
-
-void set_ms(RumiCovis *h, std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1, std::chrono::steady_clock::time_point t2) {
-    const auto t3 = std::chrono::steady_clock::now();
-    h->stageMs[0] = std::chrono::duration<float, std::milli>(t1 - t0).count();
-    h->stageMs[1] = std::chrono::duration<float, std::milli>(t2 - t1).count();
-    h->stageMs[2] = std::chrono::duration<float, std::milli>(t3 - t2).count();
-}
 
 }  // namespace
 
@@ -492,7 +459,7 @@ extern "C" int rumi_covis_create(int32_t max_kf, int32_t max_points, int64_t are
         return RUMI_E_CAPACITY;
     }
     RumiCovis *h = new RumiCovis();
-    h->device = device; h->maxKf = max_kf; h->maxPts = max_points;
+    h->dev.device = device; h->maxKf = max_kf; h->maxPts = max_points;
     h->kf.assign((size_t)max_kf * KFW, 0);
     h->pt.assign((size_t)max_points * PTW, 0);
     h->arena.assign(arena_entries ? (size_t)std::max<int64_t>(arena_entries, 16) : (size_t)1 << 20, 0);
@@ -509,11 +476,7 @@ extern "C" int rumi_covis_create(int32_t max_kf, int32_t max_points, int64_t are
 
 extern "C" void rumi_covis_destroy(RumiCovis *h) {
     if (!h) return;
-    if (h->bound) (void)hipSetDevice(h->device);
-    if (h->hStage) (void)hipHostFree(h->hStage);
-    if (h->hOut) (void)hipHostFree(h->hOut);
-    for (void *p : {(void *)h->dKf, (void *)h->dPt, (void *)h->dArena, (void *)h->dAttr, (void *)h->dTag, (void *)h->dRowOf, (void *)h->dStage, (void *)h->dOut})
-        if (p) (void)hipFree(p);
+    if (h->dev.bound) (void)hipSetDevice(h->dev.device);
     delete h;
 }
 
@@ -724,7 +687,7 @@ extern "C" int rumi_covis_update_connections(RumiCovis *h, int32_t B, const int3
         g_lastError = "rumi_covis_update_connections: missing argument or negative count";
         return RUMI_E_INVALID;
     }
-    const auto t0 = std::chrono::steady_clock::now();
+    h->clock.start();
     for (int b = 0; b < B; b++)
         if (!is_live(h, batch[b])) { g_lastError = "rumi_covis_update_connections: a batch entry that is not a live slot"; return RUMI_E_INVALID; }
     if (B == 0) { conn_off[0] = ord_off[0] = 0; return RUMI_OK; }
@@ -737,21 +700,21 @@ extern "C" int rumi_covis_update_connections(RumiCovis *h, int32_t B, const int3
     uint8_t *dBatch = nullptr;
     if ((rc = flush(h, batch, (size_t)B * 4, &dBatch)) != RUMI_OK) return rc;
     const size_t offHead = 16, offPairs = offHead + (size_t)B * 16, outBytes = offPairs + (size_t)pairsCap * 8;
-    if ((rc = grow_out(h, outBytes)) != RUMI_OK) return rc;
-    const auto t1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemsetAsync(h->dOut, 0, 16, nullptr));
+    if ((rc = h->out.reserve(outBytes, outBytes + outBytes / 4)) != RUMI_OK) return rc;
+    h->clock.mark();
+    HIP_TRY(hipMemsetAsync(h->out.d, 0, 16, nullptr));
     CountArgs a{};
-    a.t = CovisTables{h->dKf, h->dPt, h->dArena, h->hiSlot};
+    a.t = CovisTables{h->dKf.p, h->dPt.p, h->dArena.p, h->hiSlot};
     a.rows = reinterpret_cast<const int32_t *>(dBatch);
-    a.head = reinterpret_cast<int4 *>(h->dOut + offHead);
-    a.pairs = reinterpret_cast<int2 *>(h->dOut + offPairs);
-    a.cursor = reinterpret_cast<uint32_t *>(h->dOut);
+    a.head = reinterpret_cast<int4 *>(h->out.d + offHead);
+    a.pairs = reinterpret_cast<int2 *>(h->out.d + offPairs);
+    a.cursor = reinterpret_cast<uint32_t *>(h->out.d);
     a.pairsCap = (uint32_t)pairsCap;
     hipLaunchKernelGGL(k_covis_count<false>, dim3(B), dim3(kThreads), 0, nullptr, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(h->hOut, h->dOut, offPairs, hipMemcpyDeviceToHost));
-    const uint32_t used = *reinterpret_cast<const uint32_t *>(h->hOut);
-    const int4 *head = reinterpret_cast<const int4 *>(h->hOut + offHead);
+    HIP_TRY(hipMemcpy(h->out.h, h->out.d, offPairs, hipMemcpyDeviceToHost));
+    const uint32_t used = *reinterpret_cast<const uint32_t *>(h->out.h);
+    const int4 *head = reinterpret_cast<const int4 *>(h->out.h + offHead);
     int64_t nConn = 0, nOrd = 0;
     for (int b = 0; b < B; b++) {
         if (head[b].x < 0 || used > pairsCap) { g_lastError = "rumi_covis_update_connections: the result buffer overflowed (internal error)"; return RUMI_E_INVALID; }
@@ -761,9 +724,9 @@ extern "C" int rumi_covis_update_connections(RumiCovis *h, int32_t B, const int3
         g_lastError = "rumi_covis_update_connections: conn_cap or ord_cap is too small for the lists";
         return RUMI_E_CAPACITY;
     }
-    if (used) HIP_TRY(hipMemcpy(h->hOut + offPairs, h->dOut + offPairs, (size_t)used * 8, hipMemcpyDeviceToHost));
-    const auto t2 = std::chrono::steady_clock::now();
-    const int2 *pairs = reinterpret_cast<const int2 *>(h->hOut + offPairs);
+    if (used) HIP_TRY(hipMemcpy(h->out.h + offPairs, h->out.d + offPairs, (size_t)used * 8, hipMemcpyDeviceToHost));
+    h->clock.mark();
+    const int2 *pairs = reinterpret_cast<const int2 *>(h->out.h + offPairs);
     int32_t co = 0, oo = 0;
     for (int b = 0; b < B; b++) {
         status[b] = head[b].x;
@@ -774,7 +737,7 @@ extern "C" int rumi_covis_update_connections(RumiCovis *h, int32_t B, const int3
         for (int i = 0; i < head[b].w; i++) { ord_slot[oo] = src[i].x; ord_weight[oo++] = src[i].y; }
     }
     conn_off[B] = co; ord_off[B] = oo;
-    set_ms(h, t0, t1, t2);
+    h->clock.finish(h->stageMs);
     return RUMI_OK;
 }
 
@@ -782,7 +745,7 @@ extern "C" int rumi_covis_update_connections(RumiCovis *h, int32_t B, const int3
 // the discarded outliers travel in the same block behind the frame's points, and the second header is cleared for the table kernels.
 int rumi::covis_local_map_launch(RumiCovis *h, int n, const int32_t *frame_points, const CovisDiscarded *d, int wantDevice, const char *entry,
                                  CovisLocalView *view) {
-    h->tq[0] = std::chrono::steady_clock::now();
+    h->clock.start();
     if (n < 0 || n > RUMI_COVIS_MAX_FEATURES || (n > 0 && !frame_points)) {
         g_lastError = std::string(entry) + ": missing argument, negative count, or more than RUMI_COVIS_MAX_FEATURES frame points";
         return RUMI_E_INVALID;
@@ -811,7 +774,7 @@ int rumi::covis_local_map_launch(RumiCovis *h, int n, const int32_t *frame_point
     }
     int rc;
     if ((rc = bind_device(h)) != RUMI_OK) return rc;
-    if (wantDevice >= 0 && h->device != wantDevice) {
+    if (wantDevice >= 0 && h->dev.device != wantDevice) {
         g_lastError = std::string(entry) + ": the store and the tracker are on different devices";
         return RUMI_E_INVALID;
     }
@@ -831,34 +794,34 @@ int rumi::covis_local_map_launch(RumiCovis *h, int n, const int32_t *frame_point
     const int gx = h->nLive, gy = (h->maxRow + kThreads - 1) / kThreads;
     const size_t offBad = 2 * 16, offKf = offBad + up16((size_t)n), offCounts = offKf + up16((size_t)h->hiSlot * 4),
                  offPts = offCounts + up16((size_t)gx * gy * 4), outBytes = offPts + (size_t)h->maxPts * 4;
-    if ((rc = grow_out(h, outBytes)) != RUMI_OK) return rc;
+    if ((rc = h->out.reserve(outBytes, outBytes + outBytes / 4)) != RUMI_OK) return rc;
     bool clearStamps = ++h->epoch == 0;                              // once every 2^32 calls: stale tags could meet a reused epoch
-    if (d && !h->dRowOf) {
-        if ((rc = dev_alloc(&h->dRowOf, (size_t)h->maxPts)) != RUMI_OK) return rc;
+    if (d && !h->dRowOf.p) {
+        if ((rc = h->dRowOf.reserve((size_t)h->maxPts, (size_t)h->maxPts)) != RUMI_OK) return rc;
         clearStamps = true;
     }
     if (clearStamps) {
-        if (h->epoch == 0) { HIP_TRY(hipMemsetAsync(h->dTag, 0, (size_t)h->maxPts * 8, nullptr)); h->epoch = 1; }
-        if (h->dRowOf) HIP_TRY(hipMemsetAsync(h->dRowOf, 0, (size_t)h->maxPts * 8, nullptr));
+        if (h->epoch == 0) { HIP_TRY(hipMemsetAsync(h->dTag.p, 0, (size_t)h->maxPts * 8, nullptr)); h->epoch = 1; }
+        if (h->dRowOf.p) HIP_TRY(hipMemsetAsync(h->dRowOf.p, 0, (size_t)h->maxPts * 8, nullptr));
     }
-    if (d) HIP_TRY(hipMemsetAsync(h->dOut + 16, 0, 16, nullptr));
-    h->tq[1] = std::chrono::steady_clock::now();
+    if (d) HIP_TRY(hipMemsetAsync(h->out.d + 16, 0, 16, nullptr));
+    h->clock.mark();
     CountArgs a{};
-    a.t = CovisTables{h->dKf, h->dPt, h->dArena, h->hiSlot};
+    a.t = CovisTables{h->dKf.p, h->dPt.p, h->dArena.p, h->hiSlot};
     a.rows = reinterpret_cast<const int32_t *>(dFrame);
     a.nFrame = n;
-    a.lmHead = reinterpret_cast<int4 *>(h->dOut);
-    a.outBad = h->dOut + offBad;
-    a.outKf = reinterpret_cast<int32_t *>(h->dOut + offKf);
+    a.lmHead = reinterpret_cast<int4 *>(h->out.d);
+    a.outBad = h->out.d + offBad;
+    a.outKf = reinterpret_cast<int32_t *>(h->out.d + offKf);
     hipLaunchKernelGGL(k_covis_count<true>, dim3(1), dim3(kThreads), 0, nullptr, a);
     if (gx > 0 && gy > 0) {
         LocalArgs l{};
         l.t = a.t;
-        l.tag = h->dTag;
+        l.tag = h->dTag.p;
         l.lmHead = a.lmHead;
         l.outKf = a.outKf;
-        l.counts = reinterpret_cast<int32_t *>(h->dOut + offCounts);
-        l.outPts = reinterpret_cast<int32_t *>(h->dOut + offPts);
+        l.counts = reinterpret_cast<int32_t *>(h->out.d + offCounts);
+        l.outPts = reinterpret_cast<int32_t *>(h->out.d + offPts);
         l.ptsCap = h->maxPts;
         l.epoch = h->epoch;
         hipLaunchKernelGGL(k_covis_local<1>, dim3(gx, gy), dim3(kThreads), 0, nullptr, l);
@@ -868,10 +831,10 @@ int rumi::covis_local_map_launch(RumiCovis *h, int n, const int32_t *frame_point
     HIP_TRY(hipGetLastError());
     CovisLocalView &v = *view;
     v = CovisLocalView{};
-    v.device = h->device; v.maxPoints = h->maxPts; v.nFrame = n; v.nDiscarded = nd; v.epoch = h->epoch;
-    v.pt = h->dPt; v.attr = h->dAttr; v.rowOf = h->dRowOf;
-    v.head = reinterpret_cast<int32_t *>(h->dOut);
-    v.localPts = reinterpret_cast<const int32_t *>(h->dOut + offPts);
+    v.device = h->dev.device; v.maxPoints = h->maxPts; v.nFrame = n; v.nDiscarded = nd; v.epoch = h->epoch;
+    v.pt = h->dPt.p; v.attr = h->dAttr.p; v.rowOf = h->dRowOf.p;
+    v.head = reinterpret_cast<int32_t *>(h->out.d);
+    v.localPts = reinterpret_cast<const int32_t *>(h->out.d + offPts);
     v.framePts = reinterpret_cast<const int32_t *>(dFrame);
     if (d) {
         v.discIds = reinterpret_cast<const int32_t *>(dFrame + offIds);
@@ -884,11 +847,12 @@ int rumi::covis_local_map_launch(RumiCovis *h, int n, const int32_t *frame_point
 // The one read in the middle of the query: both headers, the frame's bad flags and the local key-frames, into the pinned block.
 int rumi::covis_local_map_read(RumiCovis *h, const CovisLocalView &v, const int32_t **head8, const uint8_t **frameBad, const int32_t **localKf) {
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(h->hOut, h->dOut, v.headBytes, hipMemcpyDeviceToHost));
-    *head8 = reinterpret_cast<const int32_t *>(h->hOut);
-    *frameBad = h->hOut + v.offBad;
-    *localKf = reinterpret_cast<const int32_t *>(h->hOut + v.offKf);
-    set_ms(h, h->tq[0], h->tq[1], std::chrono::steady_clock::now());
+    HIP_TRY(hipMemcpy(h->out.h, h->out.d, v.headBytes, hipMemcpyDeviceToHost));
+    *head8 = reinterpret_cast<const int32_t *>(h->out.h);
+    *frameBad = h->out.h + v.offBad;
+    *localKf = reinterpret_cast<const int32_t *>(h->out.h + v.offKf);
+    h->clock.mark();
+    h->clock.finish(h->stageMs);
     return RUMI_OK;
 }
 
@@ -910,13 +874,13 @@ extern "C" int rumi_covis_local_map(RumiCovis *h, int32_t n, const int32_t *fram
         g_lastError = "rumi_covis_local_map: kf_cap or pt_cap is too small for the lists";
         return RUMI_E_CAPACITY;
     }
-    if (head[3] > 0) HIP_TRY(hipMemcpy(h->hOut + v.offPts, h->dOut + v.offPts, (size_t)head[3] * 4, hipMemcpyDeviceToHost));
-    const auto t2 = std::chrono::steady_clock::now();
+    if (head[3] > 0) HIP_TRY(hipMemcpy(h->out.h + v.offPts, h->out.d + v.offPts, (size_t)head[3] * 4, hipMemcpyDeviceToHost));
+    h->clock.mark();                                                 // the list is part of the device stage
     if (n > 0) std::memcpy(frame_point_bad, bad, (size_t)n);
     if (head[1] > 0) std::memcpy(local_kf, kfs, (size_t)head[1] * 4);
-    if (head[3] > 0) std::memcpy(local_points, h->hOut + v.offPts, (size_t)head[3] * 4);
+    if (head[3] > 0) std::memcpy(local_points, h->out.h + v.offPts, (size_t)head[3] * 4);
     *n_k1 = head[0]; *n_local_kf = head[1]; *ref_kf = head[2]; *n_local_points = head[3];
-    set_ms(h, h->tq[0], h->tq[1], t2);
+    h->clock.finish(h->stageMs);
     return RUMI_OK;
 }
 

@@ -95,6 +95,8 @@ __global__ __launch_bounds__(kReplayThreads) void k_cull_replay(CullArgs a) {
         const int4 cd = a.cands[c];
         int st = cd.w & 0xff;
         if (st == 0 && ((sCulled[cd.x >> 5] >> (cd.x & 31)) & 1)) st = RUMI_CULL_SKIPPED_BAD;   // culled earlier in this loop (:989)
+        __syncthreads();                                             // every wave has read S before this candidate's verdict may add to it: a wave
+                                                                     // that read the bit of its own candidate would skip the cull the others apply
         if (st != 0) {                                               // `continue`: no break test
             if (tid == 0) a.out[c] = make_int4(st, 0, 0, 0);
             continue;
@@ -144,29 +146,24 @@ __global__ __launch_bounds__(kReplayThreads) void k_cull_replay(CullArgs a) {
 using namespace rumi;
 
 struct RumiCull {
-    int device = -1;
-    bool bound = false;
-    uint8_t *hBlk = nullptr, *dBlk = nullptr; size_t blkCap = 0;
-    uint8_t *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;
+    DeviceBinding dev;
+    MirrorBuf<uint8_t> blk, out;
     std::vector<int32_t> stamp, slots, octOff;
     std::vector<int4> cands;
+    StageClock clock;
     float stageMs[3] = {0.f, 0.f, 0.f};   // the last call: validation + pack | upload, kernels, download | write-out
 };
 
 extern "C" int rumi_cull_create(int32_t device, RumiCull **out) {
     if (!out) return RUMI_E_INVALID;
     *out = new RumiCull();
-    (*out)->device = device;
+    (*out)->dev.device = device;
     return RUMI_OK;
 }
 
 extern "C" void rumi_cull_destroy(RumiCull *c) {
     if (!c) return;
-    if (c->bound) (void)hipSetDevice(c->device);
-    if (c->hBlk) (void)hipHostFree(c->hBlk);
-    if (c->hOut) (void)hipHostFree(c->hOut);
-    if (c->dBlk) (void)hipFree(c->dBlk);
-    if (c->dOut) (void)hipFree(c->dOut);
+    if (c->dev.bound) (void)hipSetDevice(c->dev.device);
     delete c;
 }
 
@@ -179,7 +176,7 @@ extern "C" int rumi_keyframe_culling(RumiCull *h, const RumiCullKF *kfs, int32_t
         g_lastError = "rumi_keyframe_culling: missing argument, negative count or unknown flag";
         return RUMI_E_INVALID;
     }
-    const auto t0 = std::chrono::steady_clock::now();
+    h->clock.start();
     // ---- validation, all of it before anything is written or uploaded
     h->octOff.resize((size_t)n_kf + 1);
     h->slots.assign(n_pts, 0);
@@ -208,19 +205,10 @@ extern "C" int rumi_keyframe_culling(RumiCull *h, const RumiCullKF *kfs, int32_t
             g_lastError = "rumi_keyframe_culling: a candidate outside the key-frame table";
             return RUMI_E_INVALID;
         }
-    for (int o = 0; o < n_obs; o++)
-        if (obs_kf[o] < 0 || obs_kf[o] >= n_kf || obs_feature[o] < 0 || obs_feature[o] >= kfs[obs_kf[o]].n) {
-            g_lastError = "rumi_keyframe_culling: an observation names a key-frame outside the table or a feature outside its key-frame";
-            return RUMI_E_INVALID;
-        }
     h->stamp.assign(n_kf, -1);
     bool tooMany = false;
-    for (int p = 0; p < n_pts; p++) {
+    auto slots_agree = [&](int p) -> int {                                // every observation of p names a slot that holds p, and no slot is left over
         const RumiCullPoint &P = pts[p];
-        if (P.obs_begin < 0 || P.obs_end < P.obs_begin || P.obs_end > n_obs) {
-            g_lastError = "rumi_keyframe_culling: a point's observation slice lies outside 0..n_obs";
-            return RUMI_E_INVALID;
-        }
         for (int o = P.obs_begin; o < P.obs_end; o++) {
             const int k = obs_kf[o];
             if (kfs[k].mp[obs_feature[o]] != p || h->stamp[k] == p) {
@@ -233,8 +221,11 @@ extern "C" int rumi_keyframe_culling(RumiCull *h, const RumiCullKF *kfs, int32_t
             g_lastError = "rumi_keyframe_culling: an mp entry whose point does not list that (key-frame, feature) pair";
             return RUMI_E_INVALID;
         }
-        tooMany = tooMany || P.obs_end - P.obs_begin > RUMI_REFRESH_MAX_OBS;
-    }
+        return RUMI_OK;
+    };
+    int rc = check_observation_table("rumi_keyframe_culling", n_kf, [&](int k) { return kfs[k].n; }, pts, n_pts, obs_kf, obs_feature, n_obs,
+                                     RUMI_REFRESH_MAX_OBS, &tooMany, slots_agree);
+    if (rc != RUMI_OK) return rc;
     if (tooMany || n_kf > RUMI_CULL_MAX_KEYFRAMES) {
         g_lastError = "rumi_keyframe_culling: a point has more than RUMI_REFRESH_MAX_OBS observations, or more than RUMI_CULL_MAX_KEYFRAMES key-frames";
         return RUMI_E_CAPACITY;
@@ -265,30 +256,10 @@ extern "C" int rumi_keyframe_culling(RumiCull *h, const RumiCullKF *kfs, int32_t
                  offRows = offOctOff + up(((size_t)n_kf + 1) * 4), offObsKf = offRows + up(nRows * 4), offObsF = offObsKf + up((size_t)n_obs * 4),
                  offOct = offObsF + up((size_t)n_obs * 4), upBytes = offOct + up((size_t)nOct), blkBytes = upBytes + up(nRows);
     const size_t outBytes = ((size_t)nUp + 1) * 16 + up((size_t)nUp * 4);
-    if (!h->bound) {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-            g_lastError = "no HIP device visible: librumi_hip has no CPU fallback";
-            return RUMI_E_NO_DEVICE;
-        }
-        if (h->device < 0 && hipGetDevice(&h->device) != hipSuccess) h->device = 0;
-        h->bound = true;
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    int rc;
-    if (blkBytes > h->blkCap) {
-        const size_t want = blkBytes + blkBytes / 4;
-        h->blkCap = 0;
-        if ((rc = regrow(&h->hBlk, want, true)) != RUMI_OK || (rc = regrow(&h->dBlk, want, false)) != RUMI_OK) return rc;
-        h->blkCap = want;
-    }
-    if (outBytes > h->outCap) {
-        const size_t want = outBytes + outBytes / 4;
-        h->outCap = 0;
-        if ((rc = regrow(&h->hOut, want, true)) != RUMI_OK || (rc = regrow(&h->dOut, want, false)) != RUMI_OK) return rc;
-        h->outCap = want;
-    }
-    uint8_t *b = h->hBlk;
+    if ((rc = h->dev.bind()) != RUMI_OK || (rc = h->blk.reserve(blkBytes, blkBytes + blkBytes / 4)) != RUMI_OK ||
+        (rc = h->out.reserve(outBytes, outBytes + outBytes / 4)) != RUMI_OK)
+        return rc;
+    uint8_t *b = h->blk.h;
     int4 *hPts = reinterpret_cast<int4 *>(b + offPts);
     for (int p = 0; p < n_pts; p++) hPts[p] = make_int4(pts[p].obs_begin, pts[p].obs_end - pts[p].obs_begin, pts[p].n_obs_count, pts[p].is_bad ? 1 : 0);
     std::memcpy(b + offCand, h->cands.data(), (size_t)nUp * 16);
@@ -304,30 +275,30 @@ extern "C" int rumi_keyframe_culling(RumiCull *h, const RumiCullKF *kfs, int32_t
         uint8_t *dst = hOct + h->octOff[k];
         for (int i = 0; i < kfs[k].n; i++) dst[i] = (uint8_t)src[i];
     }
-    const auto t1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(h->dBlk, h->hBlk, upBytes, hipMemcpyHostToDevice, nullptr));
+    h->clock.mark();
+    HIP_TRY(hipMemcpyAsync(h->blk.d, h->blk.h, upBytes, hipMemcpyHostToDevice, nullptr));
 
     // ---- the two launches
     CullArgs a;
-    a.pts = reinterpret_cast<int4 *>(h->dBlk + offPts);
-    a.cands = reinterpret_cast<const int4 *>(h->dBlk + offCand);
-    a.counts = reinterpret_cast<int2 *>(h->dBlk + offCount);
-    a.rows = reinterpret_cast<const int32_t *>(h->dBlk + offRows);
-    a.first = h->dBlk + upBytes;
-    a.obsKf = reinterpret_cast<const int32_t *>(h->dBlk + offObsKf);
-    a.obsFeature = reinterpret_cast<const int32_t *>(h->dBlk + offObsF);
-    a.octOff = reinterpret_cast<const int32_t *>(h->dBlk + offOctOff);
-    a.oct = h->dBlk + offOct;
-    a.out = reinterpret_cast<int4 *>(h->dOut);
+    a.pts = reinterpret_cast<int4 *>(h->blk.d + offPts);
+    a.cands = reinterpret_cast<const int4 *>(h->blk.d + offCand);
+    a.counts = reinterpret_cast<int2 *>(h->blk.d + offCount);
+    a.rows = reinterpret_cast<const int32_t *>(h->blk.d + offRows);
+    a.first = h->blk.d + upBytes;
+    a.obsKf = reinterpret_cast<const int32_t *>(h->blk.d + offObsKf);
+    a.obsFeature = reinterpret_cast<const int32_t *>(h->blk.d + offObsF);
+    a.octOff = reinterpret_cast<const int32_t *>(h->blk.d + offOctOff);
+    a.oct = h->blk.d + offOct;
+    a.out = reinterpret_cast<int4 *>(h->out.d);
     a.nUp = nUp; a.limit = limit;
     if (maxN > 0) hipLaunchKernelGGL(k_cull_first, dim3(nUp, (maxN + kFirstThreads - 1) / kFirstThreads), dim3(kFirstThreads), 0, nullptr, a);
     hipLaunchKernelGGL(k_cull_replay, dim3(1), dim3(kReplayThreads), 0, nullptr, a);
     HIP_TRY(hipGetLastError());
 
     // ---- one block back
-    HIP_TRY(hipMemcpy(h->hOut, h->dOut, outBytes, hipMemcpyDeviceToHost));
-    const auto t2 = std::chrono::steady_clock::now();
-    const int4 *res = reinterpret_cast<const int4 *>(h->hOut);
+    HIP_TRY(hipMemcpy(h->out.h, h->out.d, outBytes, hipMemcpyDeviceToHost));
+    h->clock.mark();
+    const int4 *res = reinterpret_cast<const int4 *>(h->out.h);
     const int nCulled = res[nUp].x, reached = res[nUp].y;
     const int32_t *list = reinterpret_cast<const int32_t *>(res + nUp + 1);
     for (int c = 0; c < n_cand; c++) {
@@ -338,10 +309,7 @@ extern "C" int rumi_keyframe_culling(RumiCull *h, const RumiCullKF *kfs, int32_t
     }
     for (int i = 0; i < nCulled; i++) culled[i] = list[i];
     *n_culled = nCulled;
-    const auto t3 = std::chrono::steady_clock::now();
-    h->stageMs[0] = std::chrono::duration<float, std::milli>(t1 - t0).count();
-    h->stageMs[1] = std::chrono::duration<float, std::milli>(t2 - t1).count();
-    h->stageMs[2] = std::chrono::duration<float, std::milli>(t3 - t2).count();
+    h->clock.finish(h->stageMs);
     return RUMI_OK;
 }
 

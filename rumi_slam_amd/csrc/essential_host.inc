@@ -1,14 +1,5 @@
 // Host side of rumi_essential_graph / rumi_sim3_correct_points (kernels: essential.inc).  Included by opt.hip after RumiOptimizer.
 
-static int eg_grow(uint8_t **p, size_t *cap, size_t need) {
-    if (need <= *cap) return RUMI_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    HIP_TRY(hipMalloc((void **)p, need));
-    *cap = need;
-    return RUMI_OK;
-}
-
 static bool eg_sim3_ok(const double *S) {
     for (int k = 0; k < 8; k++) if (!std::isfinite(S[k])) return false;
     const double nq = std::sqrt(S[0] * S[0] + S[1] * S[1] + S[2] * S[2] + S[3] * S[3]);
@@ -66,14 +57,14 @@ extern "C" int rumi_essential_graph(RumiOptimizer *o, int32_t n_v, double *S_io8
     hipStream_t st = o->stream;
     // ---- device arenas: the dense matrix [(n + 1) x n | n reciprocal pivots] and one block for everything else, grown on demand ----
     const size_t aBytes = ((size_t)(n + 1) * n + n) * sizeof(double);
-    { const int rcg = eg_grow(&o->dEgA, &o->egACap, aBytes); if (rcg != RUMI_OK) return rcg; }
+    { const int rcg = o->egA.reserve(aBytes, aBytes); if (rcg != RUMI_OK) return rcg; }
     auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
     const size_t oS = 0, oM = al(oS + (size_t)n_v * 8 * 8), oV0 = al(oM + (size_t)nE * 8 * 8), oV1 = al(oV0 + (size_t)nE * 4), oCol = al(oV1 + (size_t)nE * 4),
                  oRow = al(oCol + (size_t)n_v * 4), oInc = al(oRow + (size_t)(nR + 1) * 4), oFix = al(oInc + inc.size() * 4), oFs = al(oFix + (size_t)n_v),
                  upBytes = al(oFs + (size_t)n_v);
     const size_t oS1 = upBytes, oEB = al(oS1 + (size_t)n_v * 8 * 8), oChi = al(oEB + (size_t)nE * kEgStride * 8), oB = al(oChi + (size_t)nE * 8),
                  oX = al(oB + (size_t)n * 8), oPart = al(oX + (size_t)n * 8), total = al(oPart + (size_t)nR * 8);
-    { const int rcg = eg_grow(&o->dEg, &o->egCap, total); if (rcg != RUMI_OK) return rcg; }
+    { const int rcg = o->eg.reserve(total, total); if (rcg != RUMI_OK) return rcg; }
     std::vector<uint8_t> up(upBytes, 0);
     std::memcpy(up.data() + oS, S_io8, (size_t)n_v * 64);
     std::memcpy(up.data() + oM, actM.data(), (size_t)nE * 64);
@@ -83,10 +74,10 @@ extern "C" int rumi_essential_graph(RumiOptimizer *o, int32_t n_v, double *S_io8
     std::memcpy(up.data() + oRow, rowStart.data(), (size_t)(nR + 1) * 4);
     std::memcpy(up.data() + oInc, inc.data(), inc.size() * 4);
     for (int v = 0; v < n_v; v++) { up[oFix + v] = fixed[v] != 0; up[oFs + v] = fix_scale[v] != 0; }
-    HIP_TRY(hipMemcpyAsync(o->dEg, up.data(), upBytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o->eg.p, up.data(), upBytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
-    uint8_t *d = o->dEg;
-    double *A = (double *)o->dEgA, *rdg = A + (size_t)(n + 1) * n, *dS[2] = {(double *)(d + oS), (double *)(d + oS1)};
+    uint8_t *d = o->eg.p;
+    double *A = (double *)o->egA.p, *rdg = A + (size_t)(n + 1) * n, *dS[2] = {(double *)(d + oS), (double *)(d + oS1)};
     const EGDev G{n_v, nE, nR, n, (const int32_t *)(d + oV0), (const int32_t *)(d + oV1), (const double *)(d + oM), d + oFix, d + oFs,
                   (const int32_t *)(d + oCol), (const int32_t *)(d + oRow), (const int32_t *)(d + oInc), (double *)(d + oEB), (double *)(d + oChi), A,
                   (double *)(d + oB), (double *)(d + oX), (double *)(d + oPart), o->dScal};
@@ -190,15 +181,15 @@ extern "C" int rumi_sim3_correct_points(RumiOptimizer *o, int32_t mode, int32_t 
     hipStream_t st = o->stream;
     auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
     const size_t tb = (size_t)n_v * (mode == 0 ? 64 : 28), oX = 0, oR = al(oX + (size_t)n * 12), oA = al(oR + (size_t)n * 4), oB = al(oA + tb), total = al(oB + tb);
-    { const int rcg = eg_grow(&o->dEg, &o->egCap, total); if (rcg != RUMI_OK) return rcg; }
+    { const int rcg = o->eg.reserve(total, total); if (rcg != RUMI_OK) return rcg; }
     std::vector<uint8_t> up(total, 0);
     std::memcpy(up.data() + oX, X, (size_t)n * 12); std::memcpy(up.data() + oR, ref, (size_t)n * 4);
     std::memcpy(up.data() + oA, tab_a, tb); std::memcpy(up.data() + oB, tab_b, tb);
-    HIP_TRY(hipMemcpyAsync(o->dEg, up.data(), total, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_sim3_correct_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mode, n, (float *)(o->dEg + oX), (const int32_t *)(o->dEg + oR),
-                       (const void *)(o->dEg + oA), (const void *)(o->dEg + oB));
+    HIP_TRY(hipMemcpyAsync(o->eg.p, up.data(), total, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_sim3_correct_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mode, n, (float *)(o->eg.p + oX), (const int32_t *)(o->eg.p + oR),
+                       (const void *)(o->eg.p + oA), (const void *)(o->eg.p + oB));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(up.data(), o->dEg + oX, (size_t)n * 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(up.data(), o->eg.p + oX, (size_t)n * 12, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     std::memcpy(X, up.data(), (size_t)n * 12);
     return RUMI_OK;

@@ -428,26 +428,14 @@ __global__ __launch_bounds__(256) void k_q_nbest(QDev Q, const int32_t *__restri
     nMerge[q] = nm;
 }
 
-template <class T> struct DBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return RUMI_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        const size_t c = std::max<size_t>(n, 64);
-        HIP_TRY(hipMalloc((void **)&p, c * sizeof(T)));
-        cap = c;
-        return RUMI_OK;
-    }
-    int put(const T *h, size_t n) {
-        int rc = ensure(n);
-        if (rc != RUMI_OK) return rc;
-        if (n) HIP_TRY(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice));
-        return RUMI_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
+// The query arrays are DevBufs of at least 64 elements, so that the small ones stop growing early.
+template <class T> int ensure(DevBuf<T> &b, size_t n) { return b.reserve(n, std::max<size_t>(n, 64)); }
+template <class T> int put(DevBuf<T> &b, const T *h, size_t n) {
+    const int rc = ensure(b, n);
+    if (rc != RUMI_OK) return rc;
+    if (n) HIP_TRY(hipMemcpy(b.p, h, n * sizeof(T), hipMemcpyHostToDevice));
+    return RUMI_OK;
+}
 
 inline int blocks(size_t n, int t) { return (int)((n + t - 1) / t); }
 
@@ -486,9 +474,9 @@ struct RumiKFDatabase {
     int32_t *wCount = nullptr; uint32_t *wRank = nullptr; float *wVal = nullptr; int32_t *wList = nullptr; uint64_t *wKey = nullptr; float *wSi = nullptr;
     float *wAcc = nullptr; int32_t *wBest = nullptr; int32_t *wOrder = nullptr;
     int32_t *qSmall = nullptr;                    // maxc, minc, nsc, scOff [tileQ + 1], outN, nLoop, nMerge, nCand
-    DBuf<uint64_t> qId; DBuf<int32_t> qMap; DBuf<int64_t> qVb; DBuf<int32_t> qBowOff, qOfWord, connQ, connS, flatSlot, outSlot, loopS, mergeS, badM, tmpI;
-    DBuf<uint32_t> qW; DBuf<double> qV; DBuf<float> flatSi; DBuf<NewKF> newKF;
-    DBuf<uint64_t> asmKey; DBuf<int32_t> asmOrder, asmN; DBuf<uint32_t> asmW; DBuf<double> asmV;
+    DevBuf<uint64_t> qId; DevBuf<int32_t> qMap; DevBuf<int64_t> qVb; DevBuf<int32_t> qBowOff, qOfWord, connQ, connS, flatSlot, outSlot, loopS, mergeS, badM, tmpI;
+    DevBuf<uint32_t> qW; DevBuf<double> qV; DevBuf<float> flatSi; DevBuf<NewKF> newKF;
+    DevBuf<uint64_t> asmKey; DevBuf<int32_t> asmOrder, asmN; DevBuf<uint32_t> asmW; DevBuf<double> asmV;
     // pending query
     int pendKind = -1, pendNq = 0;
     std::vector<int32_t> pendScOff;
@@ -501,10 +489,6 @@ void kfdb_free(RumiKFDatabase *d) {
                  d->dTileSums, d->dGrand, d->dPSlot[0], d->dPSlot[1], d->dPWord[0], d->dPWord[1], d->wCount, d->wRank, d->wVal, d->wList, d->wKey,
                  d->wSi, d->wAcc, d->wBest, d->wOrder, d->qSmall};
     for (void *q : p) if (q) (void)hipFree(q);
-    d->qId.release(); d->qMap.release(); d->qVb.release(); d->qBowOff.release(); d->qOfWord.release(); d->connQ.release(); d->connS.release();
-    d->flatSlot.release(); d->outSlot.release(); d->loopS.release(); d->mergeS.release(); d->badM.release(); d->tmpI.release(); d->qW.release();
-    d->qV.release(); d->flatSi.release(); d->newKF.release(); d->asmKey.release(); d->asmOrder.release(); d->asmN.release(); d->asmW.release();
-    d->asmV.release();
 }
 
 int fail(const char *msg, int code) { g_lastError = msg; return code; }
@@ -513,7 +497,7 @@ int fail(const char *msg, int code) { g_lastError = msg; return code; }
 int rebuild(RumiKFDatabase *d, const std::vector<int32_t> &newSlots) {
     const int nw1 = d->nWords + 1;
     HIP_TRY(hipMemset(d->dFill, 0, (size_t)nw1 * 4));
-    int rc = d->tmpI.put(newSlots.data(), newSlots.size());
+    int rc = put(d->tmpI, newSlots.data(), newSlots.size());
     if (rc != RUMI_OK) return rc;
     if (d->T > 0) hipLaunchKernelGGL(k_count_old, dim3(blocks(d->T, 256)), dim3(256), 0, nullptr, (int)d->T, d->dPSlot[d->cur], d->dPWord[d->cur], d->dLive, d->dFill);
     if (!newSlots.empty()) hipLaunchKernelGGL(k_count_new, dim3((unsigned)newSlots.size()), dim3(256), 0, nullptr, d->tmpI.p, d->dBowOff, d->dBowN, d->dPoolW, d->dFill);
@@ -543,8 +527,8 @@ int compact_pool(RumiKFDatabase *d) {
         hipMalloc((void **)&v2, (size_t)std::max<int64_t>(d->maxEntries, 1) * 8) != hipSuccess)
         return drop(fail("rumi_kfdb: entry pool compaction: device allocation failed", RUMI_E_NO_DEVICE));
     if (!slots.empty()) {
-        int rc = d->tmpI.put(slots.data(), slots.size());
-        if (rc == RUMI_OK) rc = d->flatSlot.put(newOff.data(), newOff.size());
+        int rc = put(d->tmpI, slots.data(), slots.size());
+        if (rc == RUMI_OK) rc = put(d->flatSlot, newOff.data(), newOff.size());
         if (rc != RUMI_OK) return drop(rc);
         hipLaunchKernelGGL(k_pool_gather, dim3((unsigned)slots.size()), dim3(256), 0, nullptr, d->tmpI.p, d->flatSlot.p, d->dBowOff, d->dBowN, d->dPoolW, d->dPoolV, w2, v2);
         hipLaunchKernelGGL(k_set_at<int32_t>, dim3(blocks(slots.size(), 256)), dim3(256), 0, nullptr, d->tmpI.p, d->flatSlot.p, (int)slots.size(), 1, d->dBowOff);
@@ -574,7 +558,7 @@ NewKF new_kf(RumiKFDatabase *d, int slot, uint64_t id, int32_t map, int32_t n) {
 }
 
 int upload_new(RumiKFDatabase *d, const std::vector<NewKF> &ks) {
-    int rc = d->newKF.put(ks.data(), ks.size());
+    int rc = put(d->newKF, ks.data(), ks.size());
     if (rc != RUMI_OK) return rc;
     hipLaunchKernelGGL(k_new_meta, dim3(blocks(ks.size(), 256)), dim3(256), 0, nullptr, d->newKF.p, (int)ks.size(), d->maxKf, d->dSeq, d->dMap, d->dLive, d->dBad,
                        d->dBowOff, d->dBowN, d->dCov, d->dLastQ, d->dLastS);
@@ -629,9 +613,9 @@ int remove_slots(RumiKFDatabase *d, const std::vector<int32_t> &slots) {
         d->liveEntries -= d->bowNH[s];
         d->nLive--;
     }
-    int rc = d->tmpI.put(slots.data(), slots.size());
+    int rc = put(d->tmpI, slots.data(), slots.size());
     if (rc != RUMI_OK) return rc;
-    rc = d->badM.ensure(slots.size());
+    rc = ensure(d->badM, slots.size());
     if (rc != RUMI_OK) return rc;
     HIP_TRY(hipMemcpy(d->badM.p, zeros.data(), zeros.size(), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_set_at<uint8_t>, dim3(blocks(slots.size(), 256)), dim3(256), 0, nullptr, d->tmpI.p, (const uint8_t *)d->badM.p, (int)slots.size(), 1, d->dLive);
@@ -665,8 +649,7 @@ extern "C" int rumi_kfdb_create(const RumiVocabulary *voc, int32_t max_kf, int64
     voc_params(voc, &vdev, &nWords, &weighting, &scoring);
     if (scoring != 0) return fail("rumi_kfdb_create: only L1_NORM scoring is implemented (the vocabulary's ScoringType is another)", RUMI_E_INVALID);
     if (nWords < 1) return fail("rumi_kfdb_create: the vocabulary has no words", RUMI_E_INVALID);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail("no HIP device visible: librumi_hip has no CPU fallback", RUMI_E_NO_DEVICE);
+    if (const int rc = require_device(); rc != RUMI_OK) return rc;
     RumiKFDatabase *d = new RumiKFDatabase();
     d->device = device >= 0 ? device : vdev;
     d->nWords = nWords; d->weighting = weighting; d->maxKf = max_kf; d->maxEntries = max_entries;
@@ -734,7 +717,7 @@ extern "C" int rumi_kfdb_add_batch_device(RumiKFDatabase *d, int32_t nf, const u
     HIP_TRY(hipSetDevice(d->device));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     const size_t cells = (size_t)nf * cap;
-    if ((rc = d->asmKey.ensure(cells)) || (rc = d->asmOrder.ensure(cells)) || (rc = d->asmW.ensure(cells)) || (rc = d->asmV.ensure(cells)) || (rc = d->asmN.ensure(nf)))
+    if ((rc = ensure(d->asmKey, cells)) || (rc = ensure(d->asmOrder, cells)) || (rc = ensure(d->asmW, cells)) || (rc = ensure(d->asmV, cells)) || (rc = ensure(d->asmN, nf)))
         return rc;
     const int tf = d->weighting == 0 || d->weighting == 1;
     hipLaunchKernelGGL(k_bow_assemble, dim3(nf), dim3(256), 0, nullptr, (const uint32_t *)d_word, (const double *)d_weight, (const int32_t *)d_counts, cap, tf,
@@ -757,7 +740,7 @@ extern "C" int rumi_kfdb_add_batch_device(RumiKFDatabase *d, int32_t nf, const u
         ks.push_back(k);
     }
     d->liveEntries += ne;
-    if ((rc = d->tmpI.put(frameOf.data(), nf)) || (rc = d->flatSlot.put(dst.data(), nf))) return rc;
+    if ((rc = put(d->tmpI, frameOf.data(), nf)) || (rc = put(d->flatSlot, dst.data(), nf))) return rc;
     hipLaunchKernelGGL(k_bow_place, dim3(nf), dim3(256), 0, nullptr, d->tmpI.p, d->flatSlot.p, d->asmN.p, cap, d->asmW.p, d->asmV.p, d->dPoolW, d->dPoolV);
     HIP_TRY(hipGetLastError());
     if ((rc = upload_new(d, ks)) != RUMI_OK) return rc;
@@ -843,12 +826,10 @@ template <class T> int set_per_kf(RumiKFDatabase *d, int n, const uint64_t *ids,
     }
     if (slots.empty()) return RUMI_OK;
     HIP_TRY(hipSetDevice(d->device));
-    DBuf<T> tmp;
-    if ((rc = d->tmpI.put(slots.data(), slots.size())) != RUMI_OK || (rc = tmp.put(v.data(), v.size())) != RUMI_OK) { tmp.release(); return rc; }
+    DevBuf<T> tmp;                                                   // released when the function returns, behind the synchronisation
+    if ((rc = put(d->tmpI, slots.data(), slots.size())) != RUMI_OK || (rc = put(tmp, v.data(), v.size())) != RUMI_OK) return rc;
     hipLaunchKernelGGL(k_set_at<T>, dim3(blocks(slots.size(), 256)), dim3(256), 0, nullptr, d->tmpI.p, tmp.p, (int)slots.size(), stride, dst);
-    const hipError_t e = hipDeviceSynchronize();
-    tmp.release();
-    HIP_TRY(e);
+    HIP_TRY(hipDeviceSynchronize());
     return RUMI_OK;
 }
 }  // namespace
@@ -929,9 +910,9 @@ extern "C" int rumi_kfdb_score(RumiKFDatabase *d, int32_t kind, int32_t nq, cons
                 if (it != d->slotOf.end()) { cq.push_back(q); cs.push_back(it->second); }
             }
     }
-    if ((rc = d->qId.put(qid, nq)) || (rc = d->qMap.put(qmap, nq)) || (rc = d->qVb.put(vbs.data(), nq)) || (rc = d->qBowOff.put(boff.data(), nq + 1)) ||
-        (rc = d->qOfWord.put(qow.data(), nwt)) || (rc = d->qW.put(bow_w ? bow_w + bow_off[0] : nullptr, nwt)) ||
-        (rc = d->qV.put(bow_v ? bow_v + bow_off[0] : nullptr, nwt)) || (rc = d->connQ.put(cq.data(), cq.size())) || (rc = d->connS.put(cs.data(), cs.size())))
+    if ((rc = put(d->qId, qid, nq)) || (rc = put(d->qMap, qmap, nq)) || (rc = put(d->qVb, vbs.data(), nq)) || (rc = put(d->qBowOff, boff.data(), nq + 1)) ||
+        (rc = put(d->qOfWord, qow.data(), nwt)) || (rc = put(d->qW, bow_w ? bow_w + bow_off[0] : nullptr, nwt)) ||
+        (rc = put(d->qV, bow_v ? bow_v + bow_off[0] : nullptr, nwt)) || (rc = put(d->connQ, cq.data(), cq.size())) || (rc = put(d->connS, cs.data(), cs.size())))
         return rc;
     d->pendKind = kind; d->pendNq = nq;
     QDev Q = qdev(d);
@@ -957,7 +938,7 @@ extern "C" int rumi_kfdb_score(RumiKFDatabase *d, int32_t kind, int32_t nq, cons
     for (int q = 0; q < nq; q++) d->pendScOff[q + 1] = d->pendScOff[q] + nsc[q];
     const int total = d->pendScOff[nq];
     HIP_TRY(hipMemcpy(Q.scOff, d->pendScOff.data(), (size_t)(nq + 1) * 4, hipMemcpyHostToDevice));
-    if ((rc = d->flatSlot.ensure(total)) || (rc = d->flatSi.ensure(total))) return rc;
+    if ((rc = ensure(d->flatSlot, total)) || (rc = ensure(d->flatSi, total))) return rc;
     if (total > 0)
         hipLaunchKernelGGL(k_q_si, dim3(blocks(total, 4)), dim3(256), 0, nullptr, Q, total, d->dBowOff, d->dBowN, d->dPoolW, d->dPoolV, d->flatSlot.p, d->flatSi.p);
     HIP_TRY(hipGetLastError());
@@ -1003,7 +984,7 @@ extern "C" int rumi_kfdb_select_reloc(RumiKFDatabase *d, int32_t *cand_off, uint
     cand_off[0] = 0;
     if (nq == 0) return RUMI_OK;
     if (total == 0 || d->hi == 0) { for (int q = 0; q <= nq; q++) cand_off[q] = 0; return RUMI_OK; }
-    if ((rc = d->outSlot.ensure(total)) != RUMI_OK) return rc;
+    if ((rc = ensure(d->outSlot, total)) != RUMI_OK) return rc;
     hipLaunchKernelGGL(k_q_reloc, dim3(nq), dim3(256), 0, nullptr, Q, d->dMap, d->outSlot.p, q_outN(d));
     HIP_TRY(hipGetLastError());
     std::vector<int32_t> n(nq), slots(total);
@@ -1030,7 +1011,7 @@ extern "C" int rumi_kfdb_select_nbest(RumiKFDatabase *d, const int32_t *n_cand, 
     for (int q = 0; q < nq; q++) { n_loop[q] = 0; n_merge[q] = 0; }
     if (nq == 0 || total == 0 || d->hi == 0 || stride == 0) return RUMI_OK;
     std::vector<int32_t> bm(d->badMaps.begin(), d->badMaps.end());
-    if ((rc = d->loopS.ensure((size_t)nq * stride)) || (rc = d->mergeS.ensure((size_t)nq * stride)) || (rc = d->badM.put(bm.data(), bm.size()))) return rc;
+    if ((rc = ensure(d->loopS, (size_t)nq * stride)) || (rc = ensure(d->mergeS, (size_t)nq * stride)) || (rc = put(d->badM, bm.data(), bm.size()))) return rc;
     HIP_TRY(hipMemcpy(q_nCand(d), n_cand, (size_t)nq * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_q_nbest, dim3(nq), dim3(256), 0, nullptr, Q, d->dMap, d->dBad, d->badM.p, (int)bm.size(), q_nCand(d), stride, d->loopS.p, q_nLoop(d),
                        d->mergeS.p, q_nMerge(d));

@@ -374,20 +374,12 @@ __global__ __launch_bounds__(1024) void k_newpts_replay(const uint8_t *__restric
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
 struct NewPtsState {
-    uint8_t *hBlk = nullptr, *dBlk = nullptr; size_t blkCap = 0;
-    int32_t *dCand = nullptr, *dMatched = nullptr; size_t matchedCap = 0; uint8_t *dGate = nullptr; float *dX3D = nullptr; size_t pairCap = 0;
-    NewPtsResult *hRes = nullptr, *dRes = nullptr; size_t resCap = 0;
+    MirrorBuf<uint8_t> blk, res;                             // the upload block; the result block, a NewPtsResult and its points
+    DevBuf<int32_t> cand, matched; DevBuf<uint8_t> gate; DevBuf<float> x3D;      // a candidate, a gate and a point (three floats) per (neighbour, feature) pair
     int lastNeigh = 0, lastN1 = 0, lastOri = 0;              // the last call, whose device state rumi_hook_newpts_matches replays
 };
 
-static void newpts_destroy(void *p) {
-    NewPtsState *s = static_cast<NewPtsState *>(p);
-    if (s->hBlk) (void)hipHostFree(s->hBlk);
-    if (s->hRes) (void)hipHostFree(s->hRes);
-    void *d[] = {s->dBlk, s->dCand, s->dMatched, s->dGate, s->dX3D, s->dRes};
-    for (void *q : d) if (q) (void)hipFree(q);
-    delete s;
-}
+static void newpts_destroy(void *p) { delete static_cast<NewPtsState *>(p); }     // rumi_match_destroy has made the matcher's device current
 
 static bool kf_valid(const RumiNewPointsKF &k, bool neighbour, const char **why) {
     const RumiFrameFeatures &f = k.feat;
@@ -482,51 +474,39 @@ extern "C" int rumi_create_new_map_points(RumiMatcher *m, const RumiNewPointsKF 
     size_t blkBytes = (size_t)(n_neigh + 1) * sizeof(KFDev) + kf_bytes(*cur);
     for (int k = 0; k < n_neigh; k++) blkBytes += kf_bytes(neigh[k]);
     int rc;
-    if (blkBytes > s->blkCap) {
-        const size_t want = blkBytes + blkBytes / 4;
-        s->blkCap = 0;
-        if ((rc = regrow(&s->hBlk, want, true)) != RUMI_OK || (rc = regrow(&s->dBlk, want, false)) != RUMI_OK) return rc;
-        s->blkCap = want;
-    }
     const size_t pairs = (size_t)n_neigh * std::max(n1, 1);
-    if (pairs > s->pairCap) {
-        s->pairCap = 0;
-        if ((rc = regrow(&s->dCand, pairs * 4, false)) != RUMI_OK ||
-            (rc = regrow(&s->dGate, pairs, false)) != RUMI_OK || (rc = regrow(&s->dX3D, pairs * 12, false)) != RUMI_OK) return rc;
-        s->pairCap = pairs;
-    }
     const size_t resBytes = sizeof(NewPtsResult) + (size_t)n1 * sizeof(RumiNewPoint);
-    if (resBytes > s->resCap) {
-        s->resCap = 0;
-        if ((rc = regrow(&s->hRes, resBytes, true)) != RUMI_OK || (rc = regrow(&s->dRes, resBytes, false)) != RUMI_OK) return rc;
-        s->resCap = resBytes;
-    }
+    if ((rc = s->blk.reserve(blkBytes, blkBytes + blkBytes / 4)) != RUMI_OK || (rc = s->cand.reserve(pairs, pairs)) != RUMI_OK ||
+        (rc = s->gate.reserve(pairs, pairs)) != RUMI_OK || (rc = s->x3D.reserve(pairs * 3, pairs * 3)) != RUMI_OK ||
+        (rc = s->res.reserve(resBytes, resBytes)) != RUMI_OK)
+        return rc;
+    NewPtsResult *dRes = reinterpret_cast<NewPtsResult *>(s->res.d);
 
     // ---- one block up
     size_t used = (size_t)(n_neigh + 1) * sizeof(KFDev);
-    KFDev *tab = reinterpret_cast<KFDev *>(s->hBlk);
-    kf_pack(*cur, false, s->hBlk, &used, &tab[0]);
-    for (int k = 0; k < n_neigh; k++) kf_pack(neigh[k], true, s->hBlk, &used, &tab[1 + k]);
-    HIP_TRY(hipMemcpyAsync(s->dBlk, s->hBlk, used, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemsetAsync(s->dCand, 0xFF, pairs * 4, nullptr));
-    HIP_TRY(hipMemsetAsync(s->dRes, 0, sizeof(NewPtsResult), nullptr));
+    KFDev *tab = reinterpret_cast<KFDev *>(s->blk.h);
+    kf_pack(*cur, false, s->blk.h, &used, &tab[0]);
+    for (int k = 0; k < n_neigh; k++) kf_pack(neigh[k], true, s->blk.h, &used, &tab[1 + k]);
+    HIP_TRY(hipMemcpyAsync(s->blk.d, s->blk.h, used, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemsetAsync(s->cand.p, 0xFF, pairs * 4, nullptr));
+    HIP_TRY(hipMemsetAsync(dRes, 0, sizeof(NewPtsResult), nullptr));
 
     // ---- four launches
-    hipLaunchKernelGGL(k_newpts_depth, dim3((maxN2 + 255) / 256, n_neigh), dim3(256), 0, nullptr, s->dBlk, s->dRes->skipped);
+    hipLaunchKernelGGL(k_newpts_depth, dim3((maxN2 + 255) / 256, n_neigh), dim3(256), 0, nullptr, s->blk.d, dRes->skipped);
     if (n1 > 0) {
         if (cur->fv.n_nodes > 0)
-            hipLaunchKernelGGL(k_newpts_match, dim3((cur->fv.n_nodes + 3) / 4, n_neigh), dim3(256), 0, nullptr, s->dBlk, p->coarse, s->dCand);
-        hipLaunchKernelGGL(k_newpts_triangulate, dim3((n1 + 255) / 256, n_neigh), dim3(256), 0, nullptr, s->dBlk, s->dCand, p->far_points,
-                           p->th_far_points, p->ratio_factor, s->dGate, s->dX3D);
+            hipLaunchKernelGGL(k_newpts_match, dim3((cur->fv.n_nodes + 3) / 4, n_neigh), dim3(256), 0, nullptr, s->blk.d, p->coarse, s->cand.p);
+        hipLaunchKernelGGL(k_newpts_triangulate, dim3((n1 + 255) / 256, n_neigh), dim3(256), 0, nullptr, s->blk.d, s->cand.p, p->far_points,
+                           p->th_far_points, p->ratio_factor, s->gate.p, s->x3D.p);
     }
-    hipLaunchKernelGGL(k_newpts_replay, dim3(1), dim3(1024), 0, nullptr, s->dBlk, n_neigh, p->check_orientation, s->dCand, s->dGate, s->dX3D,
-                       s->dRes, (int32_t *)nullptr);
+    hipLaunchKernelGGL(k_newpts_replay, dim3(1), dim3(1024), 0, nullptr, s->blk.d, n_neigh, p->check_orientation, s->cand.p, s->gate.p, s->x3D.p,
+                       dRes, (int32_t *)nullptr);
     HIP_TRY(hipGetLastError());
 
     // ---- one block back
-    HIP_TRY(hipMemcpy(s->hRes, s->dRes, resBytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(s->res.h, dRes, resBytes, hipMemcpyDeviceToHost));
     s->lastNeigh = n_neigh; s->lastN1 = n1; s->lastOri = p->check_orientation;
-    const NewPtsResult *r = s->hRes;
+    const NewPtsResult *r = reinterpret_cast<const NewPtsResult *>(s->res.h);
     *n_out = r->nOut;
     for (int k = 0; k < n_neigh; k++) { per_neigh_out[k] = r->perNeigh[k]; neigh_skipped_out[k] = (uint8_t)r->skipped[k]; }
     if (std::min(r->nOut, cap) > 0) std::memcpy(out, r->pts, (size_t)std::min(r->nOut, cap) * sizeof(RumiNewPoint));
@@ -548,14 +528,10 @@ extern "C" int rumi_hook_newpts_matches(RumiMatcher *m, int32_t n_neigh, int32_t
     // the last call's block, candidates, gates and skip flags are still on the device: the replay runs once more, this time recording its matches
     // (it rewrites the result block with the same bytes)
     const size_t pairs = (size_t)n_neigh * n1;
-    if (pairs > s->matchedCap) {
-        s->matchedCap = 0;
-        const int rc = regrow(&s->dMatched, pairs * 4, false);
-        if (rc != RUMI_OK) return rc;
-        s->matchedCap = pairs;
-    }
-    hipLaunchKernelGGL(k_newpts_replay, dim3(1), dim3(1024), 0, nullptr, s->dBlk, n_neigh, s->lastOri, s->dCand, s->dGate, s->dX3D, s->dRes, s->dMatched);
+    const int rc = s->matched.reserve(pairs, pairs);
+    if (rc != RUMI_OK) return rc;
+    hipLaunchKernelGGL(k_newpts_replay, dim3(1), dim3(1024), 0, nullptr, s->blk.d, n_neigh, s->lastOri, s->cand.p, s->gate.p, s->x3D.p, reinterpret_cast<NewPtsResult *>(s->res.d), s->matched.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(matches, s->dMatched, pairs * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(matches, s->matched.p, pairs * 4, hipMemcpyDeviceToHost));
     return RUMI_OK;
 }

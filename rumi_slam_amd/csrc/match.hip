@@ -141,12 +141,10 @@ extern "C" void rumi_match_destroy(RumiMatcher *m) {
     (void)hipSetDevice(m->device);
     if (m->ext.state && m->ext.destroy) m->ext.destroy(m->ext.state);
     void *p[] = {m->dKeys, m->dDesc, m->dScale, m->dSorted, m->dCellStart, m->dFvIdx, m->dQ, m->dQDesc, m->dCounts,
-                 m->dOffsets, m->dLists, m->dOut, m->dU8a, m->dU8b, m->dF[0], m->dF[1], m->dF[2], m->dF[3],
-                 m->dI[0], m->dI[1], m->dQKeys, m->dNodesA, m->dNodesB, m->dIdxA, m->dOffA, m->dOffB, m->dPose, m->dStage, m->dBow, m->dBowOut,
-                 m->dSub, m->dSubOut};
+                 m->dOffsets, m->dOut, m->dU8a, m->dU8b, m->dF[0], m->dF[1], m->dF[2], m->dF[3],
+                 m->dI[0], m->dI[1], m->dQKeys, m->dNodesA, m->dNodesB, m->dIdxA, m->dOffA, m->dOffB, m->dPose};
     for (void *q : p) if (q) (void)hipFree(q);
-    void *h[] = {m->hStage, m->hOut, m->hBow, m->hBowOut, m->hSubOut};
-    for (void *q : h) if (q) (void)hipHostFree(q);
+    if (m->hOut) (void)hipHostFree(m->hOut);
     delete m;
 }
 
@@ -157,24 +155,20 @@ extern "C" int rumi_match_create(int32_t max_features, int32_t max_queries, int3
         g_lastError = "rumi_match_create: max_features must be in 1..16384, max_queries >= 1";
         return RUMI_E_INVALID;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        g_lastError = "no HIP device visible: librumi_hip has no CPU fallback";
-        return RUMI_E_NO_DEVICE;
-    }
+    int rc = require_device();
+    if (rc != RUMI_OK) return rc;
     RumiMatcher *m = new RumiMatcher();
     if (device >= 0) m->device = device; else if (hipGetDevice(&m->device) != hipSuccess) m->device = 0;
     if (hipSetDevice(m->device) != hipSuccess) { delete m; return RUMI_E_NO_DEVICE; }
     m->maxFeat = max_features; m->maxQ = max_queries;
-    m->listCap = (size_t)max_queries * 256 + 65536;     // grown on demand
     const size_t F = max_features, Q = max_queries;
-    int rc;
 #define TRYA(x) if ((rc = (x)) != RUMI_OK) { rumi_match_destroy(m); return rc; }
     TRYA(dev_alloc(&m->dKeys, F)); TRYA(dev_alloc(&m->dDesc, F * 32)); TRYA(dev_alloc(&m->dScale, 64));
     TRYA(dev_alloc(&m->dSorted, F)); TRYA(dev_alloc(&m->dCellStart, kGridCells + 2));
     TRYA(dev_alloc(&m->dFvIdx, F));
     TRYA(dev_alloc(&m->dQ, Q)); TRYA(dev_alloc(&m->dQDesc, Q * 32)); TRYA(dev_alloc(&m->dCounts, Q + 1)); TRYA(dev_alloc(&m->dOffsets, Q + 1));
-    TRYA(dev_alloc(&m->dLists, m->listCap));
+    const size_t listCap = (size_t)max_queries * 256 + 65536;     // grown on demand
+    TRYA(m->lists.reserve(listCap, listCap));
     TRYA(dev_alloc(&m->dOut, 4 + F + Q));
     m->dNmatches = m->dOut; m->dOverflow = m->dOut + 1; m->dFeatMp = m->dOut + 4; m->dAssign = m->dOut + 4 + F;
     TRYA(dev_alloc(&m->dU8a, Q)); TRYA(dev_alloc(&m->dU8b, std::max(Q, F)));
@@ -182,10 +176,9 @@ extern "C" int rumi_match_create(int32_t max_features, int32_t max_queries, int3
     for (auto &i : m->dI) TRYA(dev_alloc(&i, Q + 1));
     TRYA(dev_alloc(&m->dQKeys, Q)); TRYA(dev_alloc(&m->dNodesA, Q)); TRYA(dev_alloc(&m->dNodesB, F)); TRYA(dev_alloc(&m->dIdxA, Q));
     TRYA(dev_alloc(&m->dOffA, Q + 1)); TRYA(dev_alloc(&m->dOffB, F + 1)); TRYA(dev_alloc(&m->dPose, 32));
-    m->stageCap = kStageHeader + F * 112 + Q * 224 + 65536;
-    TRYA(dev_alloc(&m->dStage, m->stageCap));
-    if (hipHostMalloc((void **)&m->hStage, m->stageCap, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc((void **)&m->hOut, (4 + F + Q) * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+    const size_t stageBytes = kStageHeader + F * 112 + Q * 224 + 65536;
+    TRYA(m->stage.reserve(stageBytes, stageBytes));
+    if (hipHostMalloc((void **)&m->hOut, (4 + F + Q) * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
         g_lastError = "rumi_match_create: pinned host allocation failed";
         rumi_match_destroy(m);
         return RUMI_E_NO_DEVICE;
@@ -200,13 +193,13 @@ namespace rumi {
 
 uint8_t *stage_reserve(RumiMatcher *m, void *dst, size_t bytes) {
     const size_t off = (m->stageUsed + 15) & ~(size_t)15;
-    if (m->nseg >= kMaxSegments || off + bytes > m->stageCap) {
+    if (m->nseg >= kMaxSegments || off + bytes > m->stage.cap) {
         g_lastError = "matcher upload block exhausted (raise max_features / max_queries)";
         return nullptr;
     }
-    reinterpret_cast<Segment *>(m->hStage)[m->nseg++] = Segment{dst, (uint32_t)off, (uint32_t)bytes};
+    reinterpret_cast<Segment *>(m->stage.h)[m->nseg++] = Segment{dst, (uint32_t)off, (uint32_t)bytes};
     m->stageUsed = off + bytes;
-    return m->hStage + off;
+    return m->stage.h + off;
 }
 
 int stage_add(RumiMatcher *m, void *dst, const void *src, size_t bytes) {
@@ -219,8 +212,8 @@ int stage_add(RumiMatcher *m, void *dst, const void *src, size_t bytes) {
 
 int flush_uploads(RumiMatcher *m) {
     if (m->nseg > 0) {
-        HIP_TRY(hipMemcpyAsync(m->dStage, m->hStage, m->stageUsed, hipMemcpyHostToDevice, m->upStream));
-        hipLaunchKernelGGL(k_scatter, dim3(8, m->nseg), dim3(256), 0, m->upStream, m->dStage, m->nseg);
+        HIP_TRY(hipMemcpyAsync(m->stage.d, m->stage.h, m->stageUsed, hipMemcpyHostToDevice, m->upStream));
+        hipLaunchKernelGGL(k_scatter, dim3(8, m->nseg), dim3(256), 0, m->upStream, m->stage.d, m->nseg);
         m->nseg = 0;
         m->stageUsed = kStageHeader;
     }

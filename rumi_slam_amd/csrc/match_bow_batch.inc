@@ -115,18 +115,6 @@ __global__ __launch_bounds__(256) void k_bow_batch_finish(BowBatch B) {
 }
 
 // ---- host side: layout, pack, launch, unpack or fallback ----
-// a pinned block and its device twin, grown together to hold at least `need` bytes
-static int grow_pinned_pair(uint8_t **h, uint8_t **d, size_t *cap, size_t need) {
-    if (need <= *cap) return RUMI_OK;
-    if (*h) HIP_TRY(hipHostFree(*h));
-    if (*d) HIP_TRY(hipFree(*d));
-    *h = nullptr; *d = nullptr; *cap = 0;
-    HIP_TRY(hipHostMalloc((void **)h, need * 2, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)d, need * 2));
-    *cap = need * 2;
-    return RUMI_OK;
-}
-
 // Byte offsets inside the upload block: [frame arrays | key-frame table | key-frame arrays], every array on a 16-byte boundary.  Results:
 // [matches K nf | nmatch K | err 1 | hist K 32 | rotBin K nf bytes]; the first part (outInts words) comes back.
 struct BowLayout {
@@ -182,12 +170,12 @@ static void bow_pack(uint8_t *h, const BowLayout &L, int K, const RumiFrameFeatu
 
 // the block up, cleared results, both kernels, the first part of the results back (synchronises)
 static int bow_launch(RumiMatcher *m, const BowLayout &L, int K, int nf, int nnF, float nnratio, int checkOri) {
-    HIP_TRY(hipMemcpyAsync(m->dBow, m->hBow, L.used, hipMemcpyHostToDevice, nullptr));
-    int32_t *dOut = reinterpret_cast<int32_t *>(m->dBowOut);
+    HIP_TRY(hipMemcpyAsync(m->bow.d, m->bow.h, L.used, hipMemcpyHostToDevice, nullptr));
+    int32_t *dOut = reinterpret_cast<int32_t *>(m->bowOut.d);
     HIP_TRY(hipMemsetAsync(dOut, 0xFF, (size_t)K * nf * 4, nullptr));                              // matches = -1
     HIP_TRY(hipMemsetAsync(dOut + (size_t)K * nf, 0, ((size_t)K + 1 + (size_t)K * 32) * 4, nullptr));   // counts, error word, histograms
     BowBatch B;
-    B.blk = reinterpret_cast<const uint32_t *>(m->dBow);
+    B.blk = reinterpret_cast<const uint32_t *>(m->bow.d);
     B.K = K; B.nf = nf; B.nnF = nnF;
     B.fAngle = (int)(L.oFA / 4); B.fDesc = (int)(L.oFD / 4); B.fNodes = (int)(L.oFN / 4); B.fOff = (int)(L.oFO / 4); B.fIdx = (int)(L.oFI / 4); B.kfTable = (int)(L.oT / 4);
     B.matches = dOut; B.nmatch = dOut + (size_t)K * nf; B.err = B.nmatch + K; B.hist = B.err + 1;
@@ -196,7 +184,7 @@ static int bow_launch(RumiMatcher *m, const BowLayout &L, int K, int nf, int nnF
     if (L.maxNodes > 0) hipLaunchKernelGGL(k_bow_batch_match, dim3((L.maxNodes + 15) / 16, K), dim3(256), 0, nullptr, B);
     hipLaunchKernelGGL(k_bow_batch_finish, dim3(K), dim3(256), 0, nullptr, B);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(m->hBowOut, dOut, L.outInts * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(m->bowOut.h, dOut, L.outInts * 4, hipMemcpyDeviceToHost));
     return RUMI_OK;
 }
 
@@ -216,11 +204,11 @@ extern "C" int rumi_search_by_bow_batch(RumiMatcher *m, int32_t K, const RumiFra
     for (size_t i = 0; i < (size_t)K * std::max(nf, 0); i++) matches[i] = -1;
     if (nf == 0 || nnF == 0) return RUMI_OK;
     const BowLayout L = bow_layout(K, KFs, kf_fvs, nf, nnF, nfe);
-    RC_TRY(grow_pinned_pair(&m->hBow, &m->dBow, &m->bowCap, L.used));
-    RC_TRY(grow_pinned_pair(&m->hBowOut, &m->dBowOut, &m->bowOutCap, L.outBytes));
-    bow_pack(m->hBow, L, K, KFs, kf_fvs, kf_mp, nmp, mp_bad, F, f_fv, nfe);
+    RC_TRY(m->bow.reserve(L.used, L.used * 2));
+    RC_TRY(m->bowOut.reserve(L.outBytes, L.outBytes * 2));
+    bow_pack(m->bow.h, L, K, KFs, kf_fvs, kf_mp, nmp, mp_bad, F, f_fv, nfe);
     RC_TRY(bow_launch(m, L, K, nf, nnF, nnratio, check_orientation));
-    const int32_t *ho = reinterpret_cast<const int32_t *>(m->hBowOut);
+    const int32_t *ho = reinterpret_cast<const int32_t *>(m->bowOut.h);
     if (ho[(size_t)K * nf + K] & 1) {
         // a FeatureVector node of the frame holds more than 512 features (k_bow_batch_match keeps a node's "taken" flags in one 32-bit mask per
         // lane of a 16-lane group): shallow vocabularies or levelsup near L.  The results must still be those of K single searches, so run them.

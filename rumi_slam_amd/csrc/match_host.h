@@ -62,14 +62,13 @@ struct ResolveArgs {
 
 struct RumiMatcher {
     int device = 0, maxFeat = 0, maxQ = 0;
-    size_t listCap = 0;
     // frame (train) side
     RumiKeyPoint *dKeys = nullptr; uint8_t *dDesc = nullptr; float *dScale = nullptr;
     uint16_t *dSorted = nullptr; int32_t *dCellStart = nullptr;
     uint32_t *dFvIdx = nullptr;      // frame FeatureVector indices (BoW)
     // query side
     rumi::Query *dQ = nullptr; uint8_t *dQDesc = nullptr; int32_t *dCounts = nullptr, *dOffsets = nullptr;
-    uint32_t *dLists = nullptr;
+    rumi::DevBuf<uint32_t> lists;    // the candidate lists of every query: sized by rumi_match_create, grown once by a search that overflows it
     // results, one block so that one copy brings them back: [nmatches, list overflow, -, -][featMp maxFeat][assign maxQ]
     int32_t *dOut = nullptr, *hOut = nullptr;
     int32_t *dNmatches = nullptr, *dOverflow = nullptr, *dFeatMp = nullptr, *dAssign = nullptr;     // views into dOut
@@ -79,15 +78,14 @@ struct RumiMatcher {
     int32_t *dOffA = nullptr, *dOffB = nullptr;
     float *dPose = nullptr;
     // uploads of one call: packed into a pinned block, copied once, scattered on the device (k_scatter)
-    uint8_t *hStage = nullptr, *dStage = nullptr;
-    size_t stageCap = 0, stageUsed = 0;
+    rumi::MirrorBuf<uint8_t> stage;          // sized by rumi_match_create; rumi_submap_match grows it for its one block
+    size_t stageUsed = 0;
     int nseg = 0;
     // rumi_search_by_bow_batch: one pinned block up, one result block back (grown on demand)
-    uint8_t *hBow = nullptr, *dBow = nullptr; size_t bowCap = 0;
-    uint8_t *hBowOut = nullptr, *dBowOut = nullptr; size_t bowOutCap = 0;
+    rumi::MirrorBuf<uint8_t> bow, bowOut;
     // rumi_submap_match: frame / pair tables, uploaded key-points, grids and block counts in dSub; one result block back (grown on demand)
-    uint8_t *dSub = nullptr; size_t subCap = 0;
-    uint8_t *hSubOut = nullptr, *dSubOut = nullptr; size_t subOutCap = 0;
+    rumi::DevBuf<uint8_t> sub;
+    rumi::MirrorBuf<uint8_t> subOut;
     // k_grid of the uploaded frame, launched by flush_uploads once the key-points are in place
     const int32_t *gridNDev = nullptr;     // k_grid reads the count from the device (one call only: cleared by the flush)
     hipStream_t upStream = nullptr;        // where the next flush queues its copy and scatter (the caller orders its kernels behind them)
@@ -173,7 +171,7 @@ struct FrustumBlock {
         std::memcpy(depthOut, depth, (size_t)nmp * 4); std::memcpy(levelOut, level, (size_t)nmp * 4);
     }
 };
-inline bool frustum_fits(const RumiMatcher *m, int nmp) { return FrustumBlock(m->dStage, nmp).bytes <= m->stageCap; }
+inline bool frustum_fits(const RumiMatcher *m, int nmp) { return FrustumBlock(m->stage.d, nmp).bytes <= m->stage.cap; }
 
 // The two environment switches of the search pipeline, read once per process.  fused: every query's list in a fixed slot (RUMI_MATCH_NO_FUSED set:
 // count / scan / fill).  speculate: the Tracking entries queue a whole step without reading a count back (RUMI_TRACK_SPECULATE=0 or not fused: no).

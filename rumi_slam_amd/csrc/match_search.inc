@@ -9,15 +9,15 @@ int build_lists(RumiMatcher *m, int mode, int nq, const FrameDev &fd, const uint
     if (retry) HIP_TRY(hipMemsetAsync(m->dOut, 0, 4 * sizeof(int32_t), nullptr));   // the first attempt's header was cleared with the frame upload
     if (nq > 0 && fused) {
         // one launch: every query's list in a fixed slot of the arena (k_candidates<2>)
-        const int slot = (int)std::min<size_t>(m->listCap / (size_t)nq, 0x7FFFFFFF / (size_t)nq);
+        const int slot = (int)std::min<size_t>(m->lists.cap / (size_t)nq, 0x7FFFFFFF / (size_t)nq);
         hipLaunchKernelGGL(k_candidates<2>, dim3((nq + 3) / 4), dim3(256), 0, nullptr, mode, nq, m->dQ, fd, dQueryDesc, m->dFvIdx,
-                           m->dCounts, m->dOffsets, m->dLists, slot, m->dOverflow);
+                           m->dCounts, m->dOffsets, m->lists.p, slot, m->dOverflow);
     } else if (nq > 0) {
         hipLaunchKernelGGL(k_candidates<0>, dim3((nq + 3) / 4), dim3(256), 0, nullptr, mode, nq, m->dQ, fd, dQueryDesc, m->dFvIdx,
-                           m->dCounts, m->dOffsets, m->dLists, 0, m->dOverflow);
+                           m->dCounts, m->dOffsets, m->lists.p, 0, m->dOverflow);
         hipLaunchKernelGGL(k_scan, dim3(1), dim3(256), 0, nullptr, nq, m->dCounts, m->dOffsets);
         hipLaunchKernelGGL(k_candidates<1>, dim3((nq + 3) / 4), dim3(256), 0, nullptr, mode, nq, m->dQ, fd, dQueryDesc, m->dFvIdx,
-                           m->dCounts, m->dOffsets, m->dLists, (int)std::min<size_t>(m->listCap, 0x7FFFFFFF), m->dOverflow);
+                           m->dCounts, m->dOffsets, m->lists.p, (int)std::min<size_t>(m->lists.cap, 0x7FFFFFFF), m->dOverflow);
     }
     return RUMI_OK;
 }
@@ -27,13 +27,6 @@ static int fetch_results(RumiMatcher *m, int nfeat, int nq, bool wantAssign) {
     const size_t ints = wantAssign ? (size_t)4 + m->maxFeat + std::max(nq, 0) : (size_t)4 + std::max(nfeat, 0);
     HIP_TRY(hipMemcpy(m->hOut, m->dOut, ints * sizeof(int32_t), hipMemcpyDeviceToHost));
     return RUMI_OK;
-}
-
-static int grow_lists(RumiMatcher *m, size_t need) {
-    (void)hipFree(m->dLists);
-    m->dLists = nullptr;
-    m->listCap = need * 2;
-    return dev_alloc(&m->dLists, m->listCap);
 }
 
 // Candidate lists, the resolve (`resolve()` launches it on the arrays as they are at that moment: the arena may have moved) and the results, until
@@ -50,7 +43,7 @@ static int search_loop(RumiMatcher *m, int mode, int nq, const FrameDev &fd, con
         if (m->hOut[1] == kFusedOverflow) { fused = false; continue; }      // the resolve did not run; repeat with exact list sizes
         // list arena too small: the resolve did not run and the frame's map-point vector is untouched
         if (grown) { g_lastError = "candidate list arena overflow after growing"; return RUMI_E_CAPACITY; }
-        RC_TRY(grow_lists(m, (size_t)m->hOut[1]));
+        RC_TRY(m->lists.reserve((size_t)m->hOut[1], (size_t)m->hOut[1] * 2));
         grown = 1;
     }
     return RUMI_OK;
@@ -58,9 +51,9 @@ static int search_loop(RumiMatcher *m, int mode, int nq, const FrameDev &fd, con
 
 int run_search(RumiMatcher *m, int mode, int nq, const FrameDev &fd, const uint8_t *dQueryDesc, const int32_t *dMpObs, float nnratio, int checkOri,
                int32_t *hostFeatMp, int32_t *nmatchesOut, const uint8_t *dBlocked0, float thrF, int thrI, int32_t *hostAssign) {
-    const bool fused = track_speculation().fused && nq > 0 && m->listCap / (size_t)nq >= 64;
+    const bool fused = track_speculation().fused && nq > 0 && m->lists.cap / (size_t)nq >= 64;
     RC_TRY(search_loop(m, mode, nq, fd, dQueryDesc, fused, hostAssign != nullptr, [&] {
-        const ResolveArgs A{mode, nq, fd.n, m->dQ, m->dCounts, m->dOffsets, m->dLists, fd.keys, dMpObs, m->dFeatMp, m->dAssign, m->dNmatches,
+        const ResolveArgs A{mode, nq, fd.n, m->dQ, m->dCounts, m->dOffsets, m->lists.p, fd.keys, dMpObs, m->dFeatMp, m->dAssign, m->dNmatches,
                             nnratio, checkOri, dBlocked0, thrF, thrI, m->dOverflow};
         launch_resolve(A, nullptr);
     }));
@@ -305,7 +298,7 @@ extern "C" int rumi_search_for_initialization(RumiMatcher *m, const RumiFrameFea
     FLUSH(m);
     hipLaunchKernelGGL(k_queries_init, dim3((n1 + 255) / 256), dim3(256), 0, nullptr, n1, m->dQKeys, m->dF[0], (float)window_size, m->dQ);
     RC_TRY(search_loop(m, MODE_INIT, n1, fd, m->dQDesc, false, true, [&] {          // (never the fused candidate pass)
-        const InitArgs A{n1, fd.n, m->dQ, m->dCounts, m->dOffsets, m->dLists, fd.keys, m->dAssign, m->dF[0], m->dNmatches, nnratio, check_orientation,
+        const InitArgs A{n1, fd.n, m->dQ, m->dCounts, m->dOffsets, m->lists.p, fd.keys, m->dAssign, m->dF[0], m->dNmatches, nnratio, check_orientation,
                          m->dOverflow};
         hipLaunchKernelGGL(k_resolve_init, dim3(1), dim3(64), (size_t)std::max(fd.n, 1) * 2 * sizeof(int32_t), nullptr, A);
     }));
@@ -331,13 +324,13 @@ extern "C" int rumi_frame_is_in_frustum(RumiMatcher *m, const float *Rcw9, const
     H2D(m->dF[0], mp_pos, (size_t)nmp * 3); H2D(m->dF[1], mp_normal, (size_t)nmp * 3); H2D(m->dF[2], mp_min_dist, nmp); H2D(m->dF[3], mp_max_dist, nmp);
     // outputs are packed into the upload mirror (its contents have been scattered by then) and come back with one copy
     if (!frustum_fits(m, nmp)) { g_lastError = "isInFrustum: result block exceeds the staging block"; return RUMI_E_CAPACITY; }
-    const FrustumBlock fb(m->dStage, nmp);
+    const FrustumBlock fb(m->stage.d, nmp);
     FLUSH(m);
     hipLaunchKernelGGL(k_is_in_frustum, dim3((nmp + 255) / 256), dim3(256), 0, nullptr, nmp, m->dPose, min_x, min_y, max_x, max_y, log_scale_factor,
                        nlevels, viewing_cos_limit, m->dF[0], m->dF[1], m->dF[2], m->dF[3], fb.inView, fb.x, fb.y, fb.level, fb.viewCos, fb.depth);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(m->hStage, m->dStage, fb.bytes, hipMemcpyDeviceToHost));
-    FrustumBlock(m->hStage, nmp).unpack(nmp, track_in_view, proj_x, proj_y, scale_level, view_cos, track_depth);
+    HIP_TRY(hipMemcpy(m->stage.h, m->stage.d, fb.bytes, hipMemcpyDeviceToHost));
+    FrustumBlock(m->stage.h, nmp).unpack(nmp, track_in_view, proj_x, proj_y, scale_level, view_cos, track_depth);
     return RUMI_OK;
 }
 
@@ -365,16 +358,16 @@ extern "C" int rumi_search_local_points(RumiMatcher *m, const RumiFrameFeatures 
     // the frustum test writes the six per-point fields into the (by then scattered) upload mirror; the query kernel reads them there and the
     // same block travels back to the host for the facade's write-back: no host round trip between isInFrustum and SearchByProjection
     if (!frustum_fits(m, nmp)) { g_lastError = "SearchLocalPoints: result block exceeds the staging block"; return RUMI_E_CAPACITY; }
-    const FrustumBlock fb(m->dStage, nmp);
+    const FrustumBlock fb(m->stage.d, nmp);
     FLUSH(m);
     hipLaunchKernelGGL(k_is_in_frustum, dim3((nmp + 255) / 256), dim3(256), 0, nullptr, nmp, m->dPose, fd.minX, fd.minY, fd.maxX, fd.maxY, log_scale_factor,
                        nlevels, viewing_cos_limit, m->dF[0], m->dF[1], m->dF[2], m->dF[3], fb.inView, fb.x, fb.y, fb.level, fb.viewCos, fb.depth, m->dU8b);
-    HIP_TRY(hipMemcpyAsync(m->hStage, m->dStage, fb.bytes, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpyAsync(m->stage.h, m->stage.d, fb.bytes, hipMemcpyDeviceToHost, nullptr));
     // is_bad of SearchByProjection = skip: a skipped point is never in view, so the flag is only read for points that are not bad
     hipLaunchKernelGGL(k_queries_mappoints, dim3((nmp + 255) / 256), dim3(256), 0, nullptr, nmp, fb.inView, fb.x, fb.y, fb.level, fb.viewCos, fb.depth, m->dU8b, m->dI[1],
                        m->dScale, th, far_points, th_far_points, m->dQ);
     RC_TRY(run_search(m, MODE_MAPPOINTS, nmp, fd, m->dQDesc, m->dI[1], nnratio, 0, frame_mp, nmatches_out));
-    FrustumBlock(m->hStage, nmp).unpack(nmp, track_in_view, proj_x, proj_y, scale_level, view_cos, track_depth);      // complete: run_search synchronised the stream
+    FrustumBlock(m->stage.h, nmp).unpack(nmp, track_in_view, proj_x, proj_y, scale_level, view_cos, track_depth);      // complete: run_search synchronised the stream
     int nTo = 0;
     for (int i = 0; i < nmp; i++) nTo += track_in_view[i];
     *n_to_match_out = nTo;

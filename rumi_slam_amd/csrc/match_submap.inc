@@ -1,5 +1,4 @@
 // The key-point match of CloudMerging::ComputeSubmapSim3 (CloudMerging.cc:503-551) for every matched key-frame pair in one call: rumi_submap_match.
-// (Included by match.hip after match_bow_batch.inc, whose grow_pinned_pair it uses.)
 //
 // The reference: for every key-point i1 of key-frame 1, KeyFrame::GetFeaturesInArea(mvKeys1[i1], 3) in key-frame 2 (KeyFrame.cc:887-925, mono),
 // then the nearest candidate by the pixel distance of the two mvKeys, among the candidates whose slot and the query's slot both hold a map point.
@@ -218,22 +217,17 @@ extern "C" int rumi_submap_match(RumiMatcher *m, int32_t n_frames, const RumiSub
     const size_t oCell = up, oSorted = sub_align(oCell + gridList.size() * (kGridCells + 1) * sizeof(int32_t));
     const size_t oBlocks = sub_align(oSorted + sumGridN * sizeof(uint16_t)), total = oBlocks + (size_t)n_pairs * gx * sizeof(int32_t);
     const size_t outInts = (size_t)n_pairs + 1 + 3 * sumQ;              // [pair_start P + 1 | best2 sumQ | matches 2 sumQ]
-    if (total > m->subCap) {
-        if (m->dSub) HIP_TRY(hipFree(m->dSub));
-        m->dSub = nullptr; m->subCap = 0;
-        HIP_TRY(hipMalloc((void **)&m->dSub, total * 2));
-        m->subCap = total * 2;
-    }
-    RC_TRY(grow_pinned_pair(&m->hSubOut, &m->dSubOut, &m->subOutCap, outInts * sizeof(int32_t)));
+    RC_TRY(m->sub.reserve(total, total * 2));
+    RC_TRY(m->subOut.reserve(outInts * sizeof(int32_t), outInts * sizeof(int32_t) * 2));
     reset_uploads(m);
     constexpr int kChunks = 24;                                          // segments of the one block: k_scatter gives each eight workgroups
-    RC_TRY(grow_pinned_pair(&m->hStage, &m->dStage, &m->stageCap, kStageHeader + up + 16 * (kChunks + 1)));
+    { const size_t stageBytes = kStageHeader + up + 16 * (kChunks + 1); RC_TRY(m->stage.reserve(stageBytes, stageBytes * 2)); }
 
     // ---- pack the upload straight into the pinned mirror, in chunks that k_scatter copies side by side ----
     const size_t chunk = sub_align((up + kChunks - 1) / kChunks);
     uint8_t *h0 = nullptr;
     for (size_t o = 0; o < up; o += chunk) {
-        uint8_t *h = stage_reserve(m, m->dSub + o, std::min(chunk, up - o));
+        uint8_t *h = stage_reserve(m, m->sub.p + o, std::min(chunk, up - o));
         if (!h) { reset_uploads(m); return RUMI_E_CAPACITY; }
         if (!h0) h0 = h;                                                 // every chunk is a multiple of 16 bytes: the chunks are contiguous in the mirror
     }
@@ -244,9 +238,9 @@ extern "C" int rumi_submap_match(RumiMatcher *m, int32_t n_frames, const RumiSub
         D.keys = D.keysUn = nullptr; D.hasMp = nullptr;
         if (!side[f] || F.n == 0) continue;
         if (F.on_device) { D.keys = F.keys_xy; D.keysUn = F.keys_un_xy ? F.keys_un_xy : F.keys_xy; D.hasMp = F.has_mp; continue; }
-        D.keys = reinterpret_cast<const float *>(m->dSub + oKeys[f]);
-        D.keysUn = oUn[f] ? reinterpret_cast<const float *>(m->dSub + oUn[f]) : D.keys;
-        D.hasMp = m->dSub + oMp[f];
+        D.keys = reinterpret_cast<const float *>(m->sub.p + oKeys[f]);
+        D.keysUn = oUn[f] ? reinterpret_cast<const float *>(m->sub.p + oUn[f]) : D.keys;
+        D.hasMp = m->sub.p + oMp[f];
         std::memcpy(h0 + oKeys[f], F.keys_xy, (size_t)F.n * 8);
         if (oUn[f]) std::memcpy(h0 + oUn[f], F.keys_un_xy, (size_t)F.n * 8);
         std::memcpy(h0 + oMp[f], F.has_mp, (size_t)F.n);
@@ -259,21 +253,21 @@ extern "C" int rumi_submap_match(RumiMatcher *m, int32_t n_frames, const RumiSub
     FLUSH(m);
 
     // ---- the three launches, one copy back ----
-    const SubFrame *dFrames = reinterpret_cast<const SubFrame *>(m->dSub);
-    const SubPair *dPairs = reinterpret_cast<const SubPair *>(m->dSub + oPairs);
-    int32_t *dCell = reinterpret_cast<int32_t *>(m->dSub + oCell), *dBlocks = reinterpret_cast<int32_t *>(m->dSub + oBlocks);
-    uint16_t *dSorted = reinterpret_cast<uint16_t *>(m->dSub + oSorted);
-    int32_t *dPairStart = reinterpret_cast<int32_t *>(m->dSubOut), *dBest = dPairStart + n_pairs + 1, *dMatches = dBest + sumQ;
-    hipLaunchKernelGGL(k_grid_batch, dim3((unsigned)gridList.size()), dim3(1024), 0, nullptr, dFrames, reinterpret_cast<const int32_t *>(m->dSub + oGridList), dSorted, dCell);
+    const SubFrame *dFrames = reinterpret_cast<const SubFrame *>(m->sub.p);
+    const SubPair *dPairs = reinterpret_cast<const SubPair *>(m->sub.p + oPairs);
+    int32_t *dCell = reinterpret_cast<int32_t *>(m->sub.p + oCell), *dBlocks = reinterpret_cast<int32_t *>(m->sub.p + oBlocks);
+    uint16_t *dSorted = reinterpret_cast<uint16_t *>(m->sub.p + oSorted);
+    int32_t *dPairStart = reinterpret_cast<int32_t *>(m->subOut.d), *dBest = dPairStart + n_pairs + 1, *dMatches = dBest + sumQ;
+    hipLaunchKernelGGL(k_grid_batch, dim3((unsigned)gridList.size()), dim3(1024), 0, nullptr, dFrames, reinterpret_cast<const int32_t *>(m->sub.p + oGridList), dSorted, dCell);
     hipLaunchKernelGGL(k_submap_match, dim3(gx, n_pairs), dim3(256), 0, nullptr, dFrames, dPairs, dSorted, dCell, tolerance, dBest, dBlocks);
     hipLaunchKernelGGL(k_submap_compact, dim3(gx, n_pairs), dim3(256), 0, nullptr, dFrames, dPairs, dBest, dBlocks, dPairStart, dMatches);
     HIP_TRY(hipGetLastError());
     // pair_start and best2 first; the list is as long as pair_start says
-    HIP_TRY(hipMemcpy(m->hSubOut, m->dSubOut, ((size_t)n_pairs + 1 + sumQ) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    const int32_t *ho = reinterpret_cast<const int32_t *>(m->hSubOut);
+    HIP_TRY(hipMemcpy(m->subOut.h, m->subOut.d, ((size_t)n_pairs + 1 + sumQ) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int32_t *ho = reinterpret_cast<const int32_t *>(m->subOut.h);
     const size_t nm = (size_t)ho[n_pairs];
     if (nm > sumQ) { g_lastError = "rumi_submap_match: the device reports more matches than queries"; return RUMI_E_NO_DEVICE; }
-    int32_t *hm = reinterpret_cast<int32_t *>(m->hSubOut) + n_pairs + 1 + sumQ;
+    int32_t *hm = reinterpret_cast<int32_t *>(m->subOut.h) + n_pairs + 1 + sumQ;
     if (nm > 0) HIP_TRY(hipMemcpy(hm, dMatches, nm * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
     std::memcpy(matches, hm, nm * 2 * sizeof(int32_t));
     std::memcpy(pair_start, ho, ((size_t)n_pairs + 1) * sizeof(int32_t));

@@ -64,7 +64,7 @@ struct RumiOptimizer {
     int npCap = 0;
     double *dW = nullptr;            // H_pl L per edge, allocated by the first large-window call
     int32_t *dColOf = nullptr;       // column block of every edge's key-frame (-1 fixed), same
-    int32_t *dPairs = nullptr; size_t pairCap = 0, pairOff = 0;   // Schur block descriptors + observation pairs of the large-window path
+    DevBuf<uint8_t> pairs; size_t pairOff = 0;   // Schur block descriptors + observation pairs (int32) of the large-window path; pairOff: where the pairs begin
     double *hScal = nullptr;         // fine-grained pinned: [0..7] the trial's scalars, [8] sequence number of the last publication (k_ba_publish)
     double *dhScal = nullptr;        // the same memory as the device sees it
     unsigned long long pubSeq = 0;
@@ -76,7 +76,7 @@ struct RumiOptimizer {
     rumi::WinMirror *hWm = nullptr, *dhWm = nullptr;
     rumi::BAWin *hWinTab = nullptr, *dWinTab = nullptr;
     unsigned bawRun = 0;
-    uint8_t *dGroupOut = nullptr, *hGroupOut = nullptr; size_t groupOutCap = 0;     // results of a launch group, gathered for one copy back
+    MirrorBuf<uint8_t> groupOut;     // results of a launch group, gathered for one copy back
     hipStream_t stream = nullptr;    // bundle adjustments of this handle (created non-blocking)
     std::vector<RumiOptimizer *> workers;   // rumi_local_ba_batch: one child handle per worker thread, created on first use
     uint8_t *hPose = nullptr, *hPoseOut = nullptr, *dPoseIn = nullptr, *dPoseOut = nullptr;   // PoseOptimization transfer blocks
@@ -90,7 +90,7 @@ struct RumiOptimizer {
     hipEvent_t evK[6] = {nullptr};
     float kernelMs[4] = {0};          // hpp, syrk, solve (ms over the call), trials
     // essential graph (essential_host.inc): the dense matrix and one block for the rest, allocated by the first rumi_essential_graph call
-    uint8_t *dEgA = nullptr, *dEg = nullptr; size_t egACap = 0, egCap = 0;
+    DevBuf<uint8_t> egA, eg;
 };
 
 static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }   // offsets inside the transfer blocks
@@ -105,15 +105,10 @@ extern "C" void rumi_opt_destroy(RumiOptimizer *o) {
                  o->dX[1], o->dHll, o->dBl, o->dHpl, o->dPanel, o->dHpp, o->dBp, o->dDinv, o->dXv, o->dChi, o->dScal,
                  o->dAglob, o->dEOff, o->dYt, o->dG, o->dLp, o->dW, o->dColOf};
     for (void *q : p) if (q) (void)hipFree(q);
-    if (o->dPairs) (void)hipFree(o->dPairs);
-    if (o->dEgA) (void)hipFree(o->dEgA);
-    if (o->dEg) (void)hipFree(o->dEg);
     { void *q[] = {o->dGpart, o->dGw, o->dChiPart, o->dSclPart, o->dWinSmall, o->dLmCtl, o->dWinTab, o->dSorted}; for (void *x : q) if (x) (void)hipFree(x); }
     if (o->hLmCtl) (void)hipHostFree(o->hLmCtl);
     if (o->hWm) (void)hipHostFree((void *)o->hWm);
     if (o->hWinTab) (void)hipHostFree(o->hWinTab);
-    if (o->dGroupOut) (void)hipFree(o->dGroupOut);
-    if (o->hGroupOut) (void)hipHostFree(o->hGroupOut);
     if (o->hScal) (void)hipHostFree(o->hScal);
     if (o->hStop) (void)hipHostFree(o->hStop);
     if (o->hPose) (void)hipHostFree(o->hPose);
@@ -133,15 +128,14 @@ extern "C" int rumi_opt_create(int32_t max_pose_edges, int32_t max_pose_batch, i
     if (!out) return RUMI_E_INVALID;
     *out = nullptr;
     if (max_pose_edges < 1 || max_pose_batch < 1 || max_kf < 1 || max_mp < 1 || max_edges < 1) { g_lastError = "rumi_opt_create: sizes must be >= 1"; return RUMI_E_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { g_lastError = "no HIP device visible: librumi_hip has no CPU fallback"; return RUMI_E_NO_DEVICE; }
+    int rc = require_device();
+    if (rc != RUMI_OK) return rc;
     RumiOptimizer *o = new RumiOptimizer();
     if (device >= 0) o->device = device; else if (hipGetDevice(&o->device) != hipSuccess) o->device = 0;
     if (hipSetDevice(o->device) != hipSuccess) { delete o; return RUMI_E_NO_DEVICE; }
     o->maxPoseEdges = max_pose_edges; o->maxPoseBatch = max_pose_batch; o->maxKF = max_kf; o->maxMP = max_mp; o->maxE = max_edges;
     if (hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking) != hipSuccess) { delete o; return RUMI_E_NO_DEVICE; }
     const size_t PE = max_pose_edges, PB = max_pose_batch, K = max_kf, M = max_mp, E = max_edges, N = 6 * K;
-    int rc;
 #define TRYA(x) if ((rc = (x)) != RUMI_OK) { rumi_opt_destroy(o); return rc; }
     TRYA(dev_alloc(&o->dActive, PE)); TRYA(dev_alloc(&o->dLastChi2, PE));
     for (int i = 0; i < 2; i++) { TRYA(dev_alloc(&o->dT[i], K * 8)); TRYA(dev_alloc(&o->dX[i], M * 3)); }

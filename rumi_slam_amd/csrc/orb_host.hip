@@ -94,7 +94,7 @@ struct RumiOrb {
     int32_t *dErr = nullptr;         // device error word (bit 0/1/2/3: roots, node pool, level cap, selection cap; bit 4: FAST candidate capacity);
                                      // sticky over the asynchronous calls since the last rumi_orb_sync
     // host-resident batches (rumi_orb_extract_batch_host): device landing arena, pinned staging slots, copy streams
-    uint8_t *dHostIn = nullptr; size_t dHostInBytes = 0;
+    DevBuf<uint8_t> hostIn;
     static constexpr int kFeedSlots = 4, kFeedFrames = 64;
     uint8_t *hFeed[kFeedSlots] = {nullptr}; size_t hFeedBytes = 0;
     hipEvent_t evFeed[kFeedSlots] = {nullptr};
@@ -165,7 +165,6 @@ extern "C" void rumi_orb_destroy(RumiOrb *h) {
     for (const auto &L : h->slot)
         for (hipEvent_t e : {L.fork, L.join}) if (e) (void)hipEventDestroy(e);
     for (auto &e : h->slotJoin) if (e) (void)hipEventDestroy(e);
-    if (h->dHostIn) (void)hipFree(h->dHostIn);
     for (auto &p : h->hFeed) if (p) (void)hipHostFree(p);
     for (auto &e : h->evFeed) if (e) (void)hipEventDestroy(e);
     if (h->copyStream) (void)hipStreamDestroy(h->copyStream);
@@ -210,11 +209,7 @@ extern "C" int rumi_orb_create(const RumiOrbConfig *cfg, RumiOrb **out) {
         g_lastError = "invalid RumiOrbConfig";
         return RUMI_E_INVALID;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        g_lastError = "no HIP device visible: librumi_hip has no CPU fallback";
-        return RUMI_E_NO_DEVICE;
-    }
+    if (const int rc = require_device(); rc != RUMI_OK) return rc;
     RumiOrb *h = new RumiOrb();
     h->cfg = *cfg;
     if (cfg->device >= 0) { h->device = cfg->device; }

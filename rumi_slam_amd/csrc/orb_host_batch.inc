@@ -18,12 +18,7 @@ static int extract_batch_host_impl(RumiOrb *h, const uint8_t *const *imgs, int32
     if (h->pending && (rc = rumi_orb_sync(h)) != RUMI_OK) return rc;
     const int wp = (w + 3) & ~3;
     const size_t frameBytes = (size_t)wp * hgt;
-    if (h->dHostInBytes < frameBytes * nframes) {
-        if (h->dHostIn) HIP_TRY(hipFree(h->dHostIn));
-        h->dHostIn = nullptr; h->dHostInBytes = 0;
-        HIP_TRY(hipMalloc((void **)&h->dHostIn, frameBytes * h->cfg.max_batch));
-        h->dHostInBytes = frameBytes * h->cfg.max_batch;
-    }
+    if ((rc = h->hostIn.reserve(frameBytes * nframes, frameBytes * h->cfg.max_batch)) != RUMI_OK) return rc;
     if (!h->copyStream) {
         HIP_TRY(hipStreamCreateWithFlags(&h->copyStream, hipStreamNonBlocking));
         HIP_TRY(hipStreamCreateWithFlags(&h->copyStream2, hipStreamNonBlocking));
@@ -49,10 +44,10 @@ static int extract_batch_host_impl(RumiOrb *h, const uint8_t *const *imgs, int32
             bool dense = pinned && stride == wp;                               // one buffer, frames back to back: one transfer per group
             for (int f = 1; dense && f < n; f++) dense = imgs[fed + f] == imgs[fed] + (size_t)f * frameBytes;
             if (dense) {
-                HIP_TRY(hipMemcpyAsync(h->dHostIn + (size_t)fed * frameBytes, imgs[fed], frameBytes * n, hipMemcpyHostToDevice, cs));
+                HIP_TRY(hipMemcpyAsync(h->hostIn.p + (size_t)fed * frameBytes, imgs[fed], frameBytes * n, hipMemcpyHostToDevice, cs));
             } else if (pinned) {
                 for (int f = 0; f < n; f++)
-                    HIP_TRY(hipMemcpy2DAsync(h->dHostIn + (size_t)(fed + f) * frameBytes, wp, imgs[fed + f], stride, w, hgt, hipMemcpyHostToDevice, cs));
+                    HIP_TRY(hipMemcpy2DAsync(h->hostIn.p + (size_t)(fed + f) * frameBytes, wp, imgs[fed + f], stride, w, hgt, hipMemcpyHostToDevice, cs));
             } else {
                 uint8_t *dst = h->hFeed[slot];
                 const int nt = std::max(1, std::min(h->hostThreads, n));
@@ -64,7 +59,7 @@ static int extract_batch_host_impl(RumiOrb *h, const uint8_t *const *imgs, int32
                 for (int t = 1; t < nt; t++) th.emplace_back(work, t);
                 work(0);
                 for (auto &x : th) x.join();
-                HIP_TRY(hipMemcpyAsync(h->dHostIn + (size_t)fed * frameBytes, dst, frameBytes * n, hipMemcpyHostToDevice, cs));
+                HIP_TRY(hipMemcpyAsync(h->hostIn.p + (size_t)fed * frameBytes, dst, frameBytes * n, hipMemcpyHostToDevice, cs));
             }
             HIP_TRY(hipEventRecord(h->evFeed[slot], cs));
             fed += n; group++;
@@ -74,7 +69,7 @@ static int extract_batch_host_impl(RumiOrb *h, const uint8_t *const *imgs, int32
         if (group >= 2) HIP_TRY(hipStreamWaitEvent(s, h->evFeed[(group - 2) % S], 0));
         return RUMI_OK;
     };
-    rc = extract_async_impl(h, h->dHostIn, nframes, w, hgt, wp, (int64_t)frameBytes, lap0, lap1, out, cap, hip_stream, opts);
+    rc = extract_async_impl(h, h->hostIn.p, nframes, w, hgt, wp, (int64_t)frameBytes, lap0, lap1, out, cap, hip_stream, opts);
     if (rc == RUMI_OK && tail) rc = tail(st);
     return end_call(h, rc);
 }

@@ -14,7 +14,7 @@ struct RumiKfd {
     int frameCap = 0, derivCap = 0;               // bytes / elements of a slot, for the extractor's largest frame
     uint8_t *dFrames[2] = {nullptr, nullptr};
     uint32_t *dDeriv[2] = {nullptr, nullptr};
-    uint8_t *hBgr = nullptr, *dBgr = nullptr;     // a BGR frame on its way to level 0 (allocated with the first one)
+    MirrorBuf<uint8_t> bgr;                       // a BGR frame on its way to level 0 (allocated with the first one)
     float *hOld = nullptr, *dOld = nullptr;       // the tracked points, pinned and on the device
     uint8_t *hOut = nullptr, *dOut = nullptr;     // [next n x 2 float | status n]
     int prevSlot = 0, nOld = 0;
@@ -26,8 +26,8 @@ struct RumiKfd {
 extern "C" void rumi_kfd_destroy(RumiKfd *s) {
     if (!s) return;
     if (s->h) { (void)hipSetDevice(s->h->device); (void)hipStreamSynchronize(nullptr); }
-    for (void *p : {(void *)s->dFrames[0], (void *)s->dFrames[1], (void *)s->dDeriv[0], (void *)s->dDeriv[1], (void *)s->dBgr, (void *)s->dOld, (void *)s->dOut}) if (p) (void)hipFree(p);
-    for (void *p : {(void *)s->hBgr, (void *)s->hOld, (void *)s->hOut}) if (p) (void)hipHostFree(p);
+    for (void *p : {(void *)s->dFrames[0], (void *)s->dFrames[1], (void *)s->dDeriv[0], (void *)s->dDeriv[1], (void *)s->dOld, (void *)s->dOut}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)s->hOld, (void *)s->hOut}) if (p) (void)hipHostFree(p);
     delete s;
 }
 
@@ -86,14 +86,11 @@ extern "C" int rumi_kfd_step(RumiKfd *s, const uint8_t *img, int32_t w, int32_t 
         HIP_TRY(hipMemcpyAsync(frame + g.off[0], h->hIn, (size_t)wp * hgt, hipMemcpyHostToDevice, nullptr));
     } else {
         const size_t row = (size_t)w * 3, bytes = row * hgt;
-        if (!s->hBgr) {
-            const size_t most = (size_t)h->cfg.max_width * 3 * h->cfg.max_height;
-            if (int rc = pin_alloc(&s->hBgr, most); rc != RUMI_OK) return rc;
-            if (int rc = dev_alloc(&s->dBgr, most); rc != RUMI_OK) { (void)hipHostFree(s->hBgr); s->hBgr = nullptr; return rc; }
-        }
-        for (int y = 0; y < hgt; y++) std::memcpy(s->hBgr + (size_t)y * row, img + (size_t)y * stride, row);
-        HIP_TRY(hipMemcpyAsync(s->dBgr, s->hBgr, bytes, hipMemcpyHostToDevice, nullptr));
-        flow_launch_grey(s->dBgr, (int)row, frame, g, nullptr);
+        const size_t most = (size_t)h->cfg.max_width * 3 * h->cfg.max_height;
+        if (int rc = s->bgr.reserve(most, most); rc != RUMI_OK) return rc;
+        for (int y = 0; y < hgt; y++) std::memcpy(s->bgr.h + (size_t)y * row, img + (size_t)y * stride, row);
+        HIP_TRY(hipMemcpyAsync(s->bgr.d, s->bgr.h, bytes, hipMemcpyHostToDevice, nullptr));
+        flow_launch_grey(s->bgr.d, (int)row, frame, g, nullptr);
     }
     flow_launch_prepare(frame, s->dDeriv[cur], g, nullptr);
 

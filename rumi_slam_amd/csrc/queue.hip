@@ -86,7 +86,7 @@ extern "C" int rumi_queue_create(const RumiOrbConfig *cfg, const int32_t *device
     *out = nullptr;
     if (!cfg || !devices || n_devices < 1 || n_devices > 64 || cap < 1 || cfg->max_batch < 1) { g_lastError = "rumi_queue_create: bad argument"; return RUMI_E_INVALID; }
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { g_lastError = "no HIP device visible: librumi_hip has no CPU fallback"; return RUMI_E_NO_DEVICE; }
+    if (const int rc = rumi::require_device(&ndev); rc != RUMI_OK) return rc;
     bool distinct = true;
     for (int i = 0; i < n_devices; i++) {
         if (devices[i] < 0 || devices[i] >= ndev) { g_lastError = "rumi_queue_create: device ordinal out of range"; return RUMI_E_INVALID; }

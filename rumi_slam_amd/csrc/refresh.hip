@@ -169,29 +169,24 @@ __global__ __launch_bounds__(256) void k_refresh_normal(const PtDev *__restrict_
 using namespace rumi;
 
 struct RumiRefresh {
-    int device = -1;
-    bool bound = false;
-    uint8_t *hBlk = nullptr, *dBlk = nullptr; size_t blkCap = 0;
-    OutDev *hOut = nullptr, *dOut = nullptr; size_t outCap = 0;
+    DeviceBinding dev;
+    MirrorBuf<uint8_t> blk, out;          // the upload block; the results, an OutDev a point
     std::vector<PtDev> pt;
     std::vector<int32_t> bins[4];
+    StageClock clock;
     float stageMs[3] = {0.f, 0.f, 0.f};   // the last call: validation + gather | upload, kernels, download | write-out
 };
 
 extern "C" int rumi_refresh_create(int32_t device, RumiRefresh **out) {
     if (!out) return RUMI_E_INVALID;
     *out = new RumiRefresh();
-    (*out)->device = device;
+    (*out)->dev.device = device;
     return RUMI_OK;
 }
 
 extern "C" void rumi_refresh_destroy(RumiRefresh *r) {
     if (!r) return;
-    if (r->bound) (void)hipSetDevice(r->device);
-    if (r->hBlk) (void)hipHostFree(r->hBlk);
-    if (r->hOut) (void)hipHostFree(r->hOut);
-    if (r->dBlk) (void)hipFree(r->dBlk);
-    if (r->dOut) (void)hipFree(r->dOut);
+    if (r->dev.bound) (void)hipSetDevice(r->dev.device);
     delete r;
 }
 
@@ -206,33 +201,27 @@ extern "C" int rumi_refresh_map_points(RumiRefresh *r, const RumiRefreshKF *kf, 
         g_lastError = "rumi_refresh_map_points: missing argument, negative count, or `what` without a known mode bit";
         return RUMI_E_INVALID;
     }
-    const auto t0 = std::chrono::steady_clock::now();
+    r->clock.start();
     // ---- validation, all of it before anything is written or uploaded
     for (int k = 0; k < n_kf; k++)
         if (kf[k].n < 0 || (wantDesc && kf[k].n > 0 && !kf[k].desc)) {
             g_lastError = "rumi_refresh_map_points: a key-frame with a negative feature count or without descriptors";
             return RUMI_E_INVALID;
         }
-    for (int o = 0; o < n_obs; o++)
-        if (obs_kf[o] < 0 || obs_kf[o] >= n_kf || obs_feature[o] < 0 || obs_feature[o] >= kf[obs_kf[o]].n) {
-            g_lastError = "rumi_refresh_map_points: an observation names a key-frame outside the table or a feature outside its key-frame";
-            return RUMI_E_INVALID;
-        }
     bool tooMany = false;
-    for (int i = 0; i < n_pts; i++) {
+    auto reference_ok = [&](int i) -> int {
         const RumiRefreshPoint &P = pts[i];
-        if (P.obs_begin < 0 || P.obs_end < P.obs_begin || P.obs_end > n_obs) {
-            g_lastError = "rumi_refresh_map_points: a point's observation slice lies outside 0..n_obs";
-            return RUMI_E_INVALID;
-        }
-        if (P.obs_end == P.obs_begin) continue;                  // both members return before they read the reference key-frame
+        if (P.obs_end == P.obs_begin) return RUMI_OK;            // both members return before they read the reference key-frame
         if (P.ref_kf < 0 || P.ref_kf >= n_kf || P.ref_feature < 0 || P.ref_feature >= kf[P.ref_kf].n || kf[P.ref_kf].nlevels < 1 ||
             !kf[P.ref_kf].scale_factors || P.ref_level < 0 || P.ref_level >= kf[P.ref_kf].nlevels) {
             g_lastError = "rumi_refresh_map_points: reference key-frame outside the table, ref_feature outside it, or ref_level outside its scale table";
             return RUMI_E_INVALID;
         }
-        tooMany = tooMany || P.obs_end - P.obs_begin > RUMI_REFRESH_MAX_OBS;
-    }
+        return RUMI_OK;
+    };
+    int rc = check_observation_table("rumi_refresh_map_points", n_kf, [&](int k) { return kf[k].n; }, pts, n_pts, obs_kf, obs_feature, n_obs,
+                                     RUMI_REFRESH_MAX_OBS, &tooMany, reference_ok);
+    if (rc != RUMI_OK) return rc;
     if (tooMany) {
         g_lastError = "rumi_refresh_map_points: a point has more than RUMI_REFRESH_MAX_OBS observations";
         return RUMI_E_CAPACITY;
@@ -273,30 +262,12 @@ extern "C" int rumi_refresh_map_points(RumiRefresh *r, const RumiRefreshKF *kf, 
                  offList = offObs + up(wantNormal ? (size_t)n_obs * 4 : 0), offPos = offList + up(nBinned * 4), offDesc = offPos + up(nGoodAll * 4),
                  blkBytes = offDesc + nGoodAll * 32;
     const size_t outBytes = (size_t)n_pts * sizeof(OutDev);
-    if (!r->bound) {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-            g_lastError = "no HIP device visible: librumi_hip has no CPU fallback";
-            return RUMI_E_NO_DEVICE;
-        }
-        if (r->device < 0 && hipGetDevice(&r->device) != hipSuccess) r->device = 0;
-        r->bound = true;
-    }
-    HIP_TRY(hipSetDevice(r->device));
-    int rc;
-    if (blkBytes > r->blkCap) {
-        const size_t want = blkBytes + blkBytes / 4;
-        r->blkCap = 0;
-        if ((rc = regrow(&r->hBlk, want, true)) != RUMI_OK || (rc = regrow(&r->dBlk, want, false)) != RUMI_OK) return rc;
-        r->blkCap = want;
-    }
-    if (outBytes > r->outCap) {
-        const size_t want = outBytes + outBytes / 4;
-        r->outCap = 0;
-        if ((rc = regrow(&r->hOut, want, true)) != RUMI_OK || (rc = regrow(&r->dOut, want, false)) != RUMI_OK) return rc;
-        r->outCap = want;
-    }
-    uint8_t *h = r->hBlk;
+    if ((rc = r->dev.bind()) != RUMI_OK || (rc = r->blk.reserve(blkBytes, blkBytes + blkBytes / 4)) != RUMI_OK ||
+        (rc = r->out.reserve(outBytes, outBytes + outBytes / 4)) != RUMI_OK)
+        return rc;
+    OutDev *dOut = reinterpret_cast<OutDev *>(r->out.d);
+    const OutDev *hOut = reinterpret_cast<const OutDev *>(r->out.h);
+    uint8_t *h = r->blk.h;
     std::memcpy(h + offPts, r->pt.data(), (size_t)n_pts * sizeof(PtDev));
     float *hOw = reinterpret_cast<float *>(h + offOw);
     for (int k = 0; k < n_kf; k++) std::memcpy(hOw + 3 * k, kf[k].Ow, 12);
@@ -321,34 +292,34 @@ extern "C" int rumi_refresh_map_points(RumiRefresh *r, const RumiRefreshKF *kf, 
                 g++;
             }
     }
-    const auto t1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(r->dBlk, r->hBlk, blkBytes, hipMemcpyHostToDevice, nullptr));
+    r->clock.mark();
+    HIP_TRY(hipMemcpyAsync(r->blk.d, r->blk.h, blkBytes, hipMemcpyHostToDevice, nullptr));
 
     // ---- the launches
-    const PtDev *dPts = reinterpret_cast<const PtDev *>(r->dBlk + offPts);
-    const int32_t *dList = reinterpret_cast<const int32_t *>(r->dBlk + offList), *dPos = reinterpret_cast<const int32_t *>(r->dBlk + offPos);
-    const uint4 *dDesc = reinterpret_cast<const uint4 *>(r->dBlk + offDesc);
+    const PtDev *dPts = reinterpret_cast<const PtDev *>(r->blk.d + offPts);
+    const int32_t *dList = reinterpret_cast<const int32_t *>(r->blk.d + offList), *dPos = reinterpret_cast<const int32_t *>(r->blk.d + offPos);
+    const uint4 *dDesc = reinterpret_cast<const uint4 *>(r->blk.d + offDesc);
     if (wantDesc) {
         const int n0 = (int)r->bins[0].size(), n1 = (int)r->bins[1].size(), n2 = (int)r->bins[2].size(), n3 = (int)r->bins[3].size();
-        if (n0) hipLaunchKernelGGL(k_refresh_desc_group<16>, dim3((n0 + 15) / 16), dim3(256), 0, nullptr, dPts, dList + binOff[0], n0, dDesc, dPos, r->dOut);
-        if (n1) hipLaunchKernelGGL(k_refresh_desc_group<32>, dim3((n1 + 7) / 8), dim3(256), 0, nullptr, dPts, dList + binOff[1], n1, dDesc, dPos, r->dOut);
-        if (n2) hipLaunchKernelGGL(k_refresh_desc_group<64>, dim3((n2 + 3) / 4), dim3(256), 0, nullptr, dPts, dList + binOff[2], n2, dDesc, dPos, r->dOut);
+        if (n0) hipLaunchKernelGGL(k_refresh_desc_group<16>, dim3((n0 + 15) / 16), dim3(256), 0, nullptr, dPts, dList + binOff[0], n0, dDesc, dPos, dOut);
+        if (n1) hipLaunchKernelGGL(k_refresh_desc_group<32>, dim3((n1 + 7) / 8), dim3(256), 0, nullptr, dPts, dList + binOff[1], n1, dDesc, dPos, dOut);
+        if (n2) hipLaunchKernelGGL(k_refresh_desc_group<64>, dim3((n2 + 3) / 4), dim3(256), 0, nullptr, dPts, dList + binOff[2], n2, dDesc, dPos, dOut);
         if (n3) {
             const size_t lds = (size_t)maxGood * 32 + 4 * kHistStride * sizeof(int);     // at most 64 KiB + 4224 bytes
             if (lds > 64 * 1024) HIP_TRY(raise_lds_limit(reinterpret_cast<const void *>(k_refresh_desc_block), lds));
-            hipLaunchKernelGGL(k_refresh_desc_block, dim3(n3), dim3(256), lds, nullptr, dPts, dList + binOff[3], maxGood, dDesc, dPos, r->dOut);
+            hipLaunchKernelGGL(k_refresh_desc_block, dim3(n3), dim3(256), lds, nullptr, dPts, dList + binOff[3], maxGood, dDesc, dPos, dOut);
         }
     }
     if (wantNormal)
-        hipLaunchKernelGGL(k_refresh_normal, dim3((n_pts + 255) / 256), dim3(256), 0, nullptr, dPts, n_pts, reinterpret_cast<const float *>(r->dBlk + offOw),
-                           reinterpret_cast<const int32_t *>(r->dBlk + offObs), r->dOut);
+        hipLaunchKernelGGL(k_refresh_normal, dim3((n_pts + 255) / 256), dim3(256), 0, nullptr, dPts, n_pts, reinterpret_cast<const float *>(r->blk.d + offOw),
+                           reinterpret_cast<const int32_t *>(r->blk.d + offObs), dOut);
     HIP_TRY(hipGetLastError());
 
     // ---- one block back; only the arrays of the modes asked for are written
-    HIP_TRY(hipMemcpy(r->hOut, r->dOut, outBytes, hipMemcpyDeviceToHost));
-    const auto t2 = std::chrono::steady_clock::now();
+    HIP_TRY(hipMemcpy(r->out.h, r->out.d, outBytes, hipMemcpyDeviceToHost));
+    r->clock.mark();
     for (int i = 0; i < n_pts; i++) {
-        const OutDev &o = r->hOut[i];
+        const OutDev &o = hOut[i];
         if (wantDesc) {
             const bool has = r->pt[i].nGood > 0;                 // :367, :389: nothing is written for a point without a good observation
             best_obs[i] = has ? o.bestObs : -1;
@@ -362,10 +333,7 @@ extern "C" int rumi_refresh_map_points(RumiRefresh *r, const RumiRefreshKF *kf, 
             }
         }
     }
-    const auto t3 = std::chrono::steady_clock::now();
-    r->stageMs[0] = std::chrono::duration<float, std::milli>(t1 - t0).count();
-    r->stageMs[1] = std::chrono::duration<float, std::milli>(t2 - t1).count();
-    r->stageMs[2] = std::chrono::duration<float, std::milli>(t3 - t2).count();
+    r->clock.finish(r->stageMs);
     return RUMI_OK;
 }
 

@@ -1,4 +1,4 @@
-// Error plumbing shared by the C-ABI translation units.
+// Error and host plumbing shared by the C-ABI translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -56,11 +56,120 @@ template <class T> int pin_alloc(T **p, size_t n) {
     HIP_TRY(hipHostMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault));
     return RUMI_OK;
 }
-// a block grown on demand: the old one is released, `bytes` of device or pinned host memory take its place (the contents are not kept)
-template <class T> int regrow(T **p, size_t bytes, bool pinned) {
-    if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); *p = nullptr; }
-    if (pinned) HIP_TRY(hipHostMalloc((void **)p, bytes, hipHostMallocDefault));
-    else HIP_TRY(hipMalloc((void **)p, bytes));
+
+// ---- host plumbing of the handles ("Host plumbing"): a new entry point uses these instead of writing its own ----
+
+// "Is there a device": the one check and the one message of a library without a CPU path.  *count: how many there are.
+inline int require_device(int *count = nullptr) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        g_lastError = "no HIP device visible: librumi_hip has no CPU fallback";
+        return RUMI_E_NO_DEVICE;
+    }
+    if (count) *count = ndev;
+    return RUMI_OK;
+}
+
+// A device block grown on demand.  reserve(need, want): nothing when `need` elements fit, else the old block is released (its contents are not
+// kept) and `want` elements take its place.  After a failed allocation p is null and cap is 0, so the next call allocates again and nothing
+// writes through a stale block.  An empty buffer makes no HIP call, in release() or in the destructor.
+template <class T> struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;                 // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    int reserve(size_t need, size_t want) {
+        if (need <= cap) return RUMI_OK;
+        release();
+        const int rc = dev_alloc(&p, want);
+        if (rc == RUMI_OK) cap = want;
+        return rc;
+    }
+};
+
+// A pinned host block and its device twin behind one capacity, with DevBuf's rules: after a failure of either half both are null and cap is 0.
+template <class T> struct MirrorBuf {
+    T *h = nullptr, *d = nullptr;
+    size_t cap = 0;                 // elements
+    MirrorBuf() = default;
+    MirrorBuf(const MirrorBuf &) = delete;
+    MirrorBuf &operator=(const MirrorBuf &) = delete;
+    ~MirrorBuf() { release(); }
+    void release() {
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+        h = d = nullptr; cap = 0;
+    }
+    int reserve(size_t need, size_t want) {
+        if (need <= cap) return RUMI_OK;
+        release();
+        int rc = pin_alloc(&h, want);
+        if (rc == RUMI_OK) rc = dev_alloc(&d, want);
+        if (rc == RUMI_OK) cap = want; else release();
+        return rc;
+    }
+};
+
+// The device of a handle that binds at its first call past validation, so that creating one, its argument checks and its destruction run on a
+// machine without a GPU: an unbound handle has made no HIP call.  bind(): require_device, the current device when none was named, hipSetDevice;
+// on later calls hipSetDevice only.  With `first` the caller has allocations of its own to make when *first comes back true, and sets `bound`
+// itself once they are in place.  A destroy function makes the device current before its `delete` only when `bound`.
+struct DeviceBinding {
+    int device = -1;
+    bool bound = false;
+    int bind(bool *first = nullptr) {
+        if (first) *first = !bound;
+        if (!bound) {
+            const int rc = require_device();
+            if (rc != RUMI_OK) return rc;
+            if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
+        }
+        HIP_TRY(hipSetDevice(device));
+        if (!first) bound = true;
+        return RUMI_OK;
+    }
+};
+
+// The wall clock of a call in three stages: start(), a mark() at each of the two boundaries, finish() at the end writes the three differences
+// in milliseconds.  A third mark() moves the second boundary (the local-map query of covis.hip reads in two steps).
+struct StageClock {
+    std::chrono::steady_clock::time_point t[3];
+    int n = 0;
+    void start() { t[0] = std::chrono::steady_clock::now(); n = 1; }
+    void mark() { t[n < 3 ? n++ : 2] = std::chrono::steady_clock::now(); }
+    void finish(float ms[3]) const {
+        const auto end = std::chrono::steady_clock::now();
+        ms[0] = std::chrono::duration<float, std::milli>(t[1] - t[0]).count();
+        ms[1] = std::chrono::duration<float, std::milli>(t[2] - t[1]).count();
+        ms[2] = std::chrono::duration<float, std::milli>(end - t[2]).count();
+    }
+};
+
+// The observation table of the twin entries of rumi_mapping.h (rumi_keyframe_culling, rumi_refresh_map_points): every (obs_kf, obs_feature)
+// pair inside the key-frame table (nOf(k): the feature count of key-frame k), then every point's slice inside 0..n_obs, followed at once by the
+// entry's own check of that point (each(p): RUMI_OK, or its code with the message set).  *tooMany: a slice longer than maxObs.
+template <class Point, class FeatCount, class EachPoint>
+int check_observation_table(const char *entry, int n_kf, FeatCount nOf, const Point *pts, int n_pts, const int32_t *obs_kf, const int32_t *obs_feature,
+                            int n_obs, int maxObs, bool *tooMany, EachPoint each) {
+    for (int o = 0; o < n_obs; o++)
+        if (obs_kf[o] < 0 || obs_kf[o] >= n_kf || obs_feature[o] < 0 || obs_feature[o] >= nOf(obs_kf[o])) {
+            g_lastError = std::string(entry) + ": an observation names a key-frame outside the table or a feature outside its key-frame";
+            return RUMI_E_INVALID;
+        }
+    *tooMany = false;
+    for (int p = 0; p < n_pts; p++) {
+        const Point &P = pts[p];
+        if (P.obs_begin < 0 || P.obs_end < P.obs_begin || P.obs_end > n_obs) {
+            g_lastError = std::string(entry) + ": a point's observation slice lies outside 0..n_obs";
+            return RUMI_E_INVALID;
+        }
+        const int rc = each(p);
+        if (rc != RUMI_OK) return rc;
+        *tooMany = *tooMany || P.obs_end - P.obs_begin > maxObs;
+    }
     return RUMI_OK;
 }
 }  // namespace rumi

@@ -466,7 +466,7 @@ int speculative_search(RumiTracker *t, int mode, int nq, const FrameDev &fd, flo
     RumiMatcher *m = t->m;
     const int rc = build_lists(m, mode, nq, fd, m->dQDesc, false, true);
     if (rc != RUMI_OK) return rc;
-    ResolveArgs A{mode, nq, fd.n, m->dQ, m->dCounts, m->dOffsets, m->dLists, fd.keys, m->dI[1], m->dFeatMp, m->dAssign, m->dNmatches,
+    ResolveArgs A{mode, nq, fd.n, m->dQ, m->dCounts, m->dOffsets, m->lists.p, fd.keys, m->dI[1], m->dFeatMp, m->dAssign, m->dNmatches,
                   nnratio, checkOri, nullptr, 0.f, 0, m->dOverflow};
     if (withGather) { A.gMpPos = m->dF[0]; A.gInvSigma2 = t->dInvSigma2; A.gXw = t->dXw; A.gObs = t->dObs; A.gW = t->dW; A.gIdx = t->dIdx; A.gStart = t->d.blk->start; A.gSnapshot = snap; }
     launch_resolve(A, nullptr);
@@ -498,7 +498,7 @@ int local_search(RumiTracker *t, const FrameDev &fd, int nmp, int32_t *hostMp, R
 int launch_frustum(RumiTracker *t, const FrameDev &fd, int nmp, bool stale, int n, float th_local, int far_points, float th_far_points, const char *entry) {
     RumiMatcher *m = t->m;
     if (!frustum_fits(m, nmp)) { g_lastError = std::string(entry) + ": point table exceeds the staging block"; return RUMI_E_CAPACITY; }
-    const FrustumBlock fb(m->dStage, nmp);                  // (its flag array stays unused: mbTrackInView goes into the tracker's block)
+    const FrustumBlock fb(m->stage.d, nmp);                  // (its flag array stays unused: mbTrackInView goes into the tracker's block)
     const FrustumArgs FA{nmp, n, m->dFeatMp, t->d.mpMotion, t->dLocal, t->dSeen, t->dBad, /*skip*/ m->dU8b, m->dOut, t->d.blk->pose19, fd.minX,
                          fd.minY, fd.maxX, fd.maxY, std::log(t->cfg.scale_factor), t->nlevels, 0.5f, m->dF[0], m->dF[1], m->dF[2], m->dF[3], t->d.view, fb.x, fb.y, fb.level, fb.viewCos, fb.depth,
                          m->dI[1], m->dScale, th_local, far_points, th_far_points, m->dQ,
@@ -583,7 +583,7 @@ int track_local_body(RumiTracker *t, const FrameDev &fd, int n, int nmp, bool st
         if ((rc = launch_frustum(t, fd, nmp, stale, n, th_local, far_points, th_far_points, entry)) != RUMI_OK) return rc;
         // the search's counts are not needed before the end: one queue, the result header travels in the block (a list overflow -- the resolve
         // did not run then, the frame's vector is untouched -- sends the stage through the sizing path)
-        speculate = track_speculation().speculate && m->listCap / (size_t)nmp >= 64;
+        speculate = track_speculation().speculate && m->lists.cap / (size_t)nmp >= 64;
         if ((rc = speculate ? speculative_search(t, MODE_MAPPOINTS, nmp, fd, 0.8f, 0, false, nullptr) : local_search(t, fd, nmp, tmpMp.data(), res)) != RUMI_OK) return rc;
     }
     const TrackBlock *hB = t->h.blk;
@@ -635,7 +635,7 @@ extern "C" int rumi_track_frame(RumiTracker *t, const uint8_t *img, int32_t w, i
         return rc;
     const bool gridWanted = m->gridPending;                 // (the grid needs the feature count: it is built below)
     m->gridPending = false;
-    const bool canSpec = track_speculation().speculate && nlast > 0 && nmp > 0 && m->listCap / (size_t)std::max(nlast, nmp) >= 64 && frustum_fits(m, nmp);
+    const bool canSpec = track_speculation().speculate && nlast > 0 && nmp > 0 && m->lists.cap / (size_t)std::max(nlast, nmp) >= 64 && frustum_fits(m, nmp);
     m->upStream = t->upStream;                              // the copy and the scatter, on a stream of their own beside the extraction
     const int rcUp = flush_uploads(m);
     m->upStream = nullptr;
@@ -787,7 +787,7 @@ extern "C" int rumi_track_motion(RumiTracker *t, const float *K4, const float *T
     track_init(t, n, nmp, 1, nullptr);
     // the usual case (>= 20 matches at th, no list overflow) in one queue, as in rumi_track_frame: the search's result header and the map-point
     // vector it leaves travel back with the results; anything else is redone stage by stage below
-    if (track_speculation().speculate && n > 0 && nlast > 0 && nmp > 0 && m->listCap / (size_t)nlast >= 64) {
+    if (track_speculation().speculate && n > 0 && nlast > 0 && nmp > 0 && m->lists.cap / (size_t)nlast >= 64) {
         launch_queries_frame(m, fd, nlast, th_motion, nullptr);
         if ((rc = speculative_search(t, MODE_FRAME, nlast, fd, 0.f, 1, true, t->d.mpMotion)) != RUMI_OK) return rc;
         if ((rc = pose_stage(t, fd, SLOT_MOTION, false, TAIL_DISCARD, m->dOut)) != RUMI_OK) return rc;
@@ -984,7 +984,7 @@ extern "C" int rumi_track_last_projections(RumiTracker *t, int32_t n_points, flo
     if (t->projN <= 0 || n_points != t->projN) { g_lastError = "rumi_track_last_projections: no SearchLocalPoints result of that size is resident"; return RUMI_E_INVALID; }
     HIP_TRY(hipSetDevice(t->device));
     RumiMatcher *m = t->m;
-    const FrustumBlock fb(m->dStage, n_points), h(m->hStage, n_points);
+    const FrustumBlock fb(m->stage.d, n_points), h(m->stage.h, n_points);
     HIP_TRY(hipMemcpy(h.x, fb.x, 5 * fb.n16 * sizeof(float), hipMemcpyDeviceToHost));        // the five word arrays; the flags are not wanted
     for (int i = 0; i < n_points; i++) { float *o = proj5_out + (size_t)i * 5; o[0] = h.x[i]; o[1] = h.y[i]; o[2] = (float)h.level[i]; o[3] = h.viewCos[i]; o[4] = h.depth[i]; }
     return RUMI_OK;

@@ -124,14 +124,13 @@ struct RumiVocabulary {
     int32_t *dChildOff = nullptr; uint32_t *dChildIds = nullptr; uint8_t *dDesc = nullptr; double *dWeight = nullptr; uint32_t *dWordId = nullptr;
     uint2 *dRange = nullptr;         // children as id ranges, when the tree allows it (k_voc_descend_ranges)
     // scratch of the host-array entry points
-    int cap = 0;
-    uint8_t *dQ = nullptr; uint32_t *dWord = nullptr, *dNode = nullptr; double *dW = nullptr;
+    DevBuf<uint8_t> q; DevBuf<uint32_t> word, node; DevBuf<double> w;     // descriptors (32 bytes each) and the three results of n features
 };
 
 extern "C" void rumi_voc_destroy(RumiVocabulary *v) {
     if (!v) return;
     (void)hipSetDevice(v->device);
-    void *p[] = {v->dChildOff, v->dChildIds, v->dDesc, v->dWeight, v->dWordId, v->dQ, v->dWord, v->dNode, v->dW, v->dRange};
+    void *p[] = {v->dChildOff, v->dChildIds, v->dDesc, v->dWeight, v->dWordId, v->dRange};
     for (void *q : p) if (q) (void)hipFree(q);
     delete v;
 }
@@ -157,11 +156,8 @@ extern "C" int rumi_voc_create(int32_t n_nodes, const int32_t *parent, const uin
         g_lastError = "rumi_voc_create: bad argument";
         return RUMI_E_INVALID;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        g_lastError = "no HIP device visible: librumi_hip has no CPU fallback";
-        return RUMI_E_NO_DEVICE;
-    }
+    int rc = require_device();
+    if (rc != RUMI_OK) return rc;
     // children lists in file order (m_nodes[pid].children.push_back(nid), TemplatedVocabulary.h:1389-1390), word ids in file order (:1408-1413)
     std::vector<int32_t> off(n_nodes + 1, 0), depth(n_nodes, 0);
     for (int i = 1; i < n_nodes; i++) {
@@ -195,7 +191,6 @@ extern "C" int rumi_voc_create(int32_t n_nodes, const int32_t *parent, const uin
         for (int c = c0 + 1; c < c1; c++) if (ids[c] != ids[c - 1] + 1) { consecutive = false; break; }
     }
     static const bool noRanges = std::getenv("RUMI_VOC_NO_RANGES") != nullptr;     // (A/B measurements and tests of the general kernel)
-    int rc;
     if (consecutive && !noRanges && (rc = upload(&v->dRange, range)) != RUMI_OK) { rumi_voc_destroy(v); return rc; }
     if ((rc = upload(&v->dChildOff, off)) != RUMI_OK || (rc = upload(&v->dChildIds, ids)) != RUMI_OK || (rc = upload(&v->dDesc, d)) != RUMI_OK ||
         (rc = upload(&v->dWeight, w)) != RUMI_OK || (rc = upload(&v->dWordId, wid)) != RUMI_OK) {
@@ -283,20 +278,16 @@ extern "C" int rumi_voc_transform_features(RumiVocabulary *v, const uint8_t *des
     if (!v || n < 0 || (n > 0 && (!desc || !word_id || !weight || !node_id))) return RUMI_E_INVALID;
     if (n == 0) return RUMI_OK;
     HIP_TRY(hipSetDevice(v->device));
-    if (n > v->cap) {
-        for (void *p : {(void *)v->dQ, (void *)v->dWord, (void *)v->dNode, (void *)v->dW}) if (p) (void)hipFree(p);
-        v->dQ = nullptr; v->dWord = nullptr; v->dNode = nullptr; v->dW = nullptr; v->cap = 0;
-        const size_t c = (size_t)n * 2;
-        HIP_TRY(hipMalloc((void **)&v->dQ, c * 32)); HIP_TRY(hipMalloc((void **)&v->dWord, c * 4));
-        HIP_TRY(hipMalloc((void **)&v->dNode, c * 4)); HIP_TRY(hipMalloc((void **)&v->dW, c * 8));
-        v->cap = (int)c;
-    }
-    HIP_TRY(hipMemcpyAsync(v->dQ, desc, (size_t)n * 32, hipMemcpyHostToDevice, nullptr));
-    const int rc = launch_descend(v, v->dQ, nullptr, 0, n, levelsup, v->dWord, v->dW, v->dNode, nullptr);
-    if (rc != RUMI_OK) return rc;
-    HIP_TRY(hipMemcpy(word_id, v->dWord, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(weight, v->dW, (size_t)n * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(node_id, v->dNode, (size_t)n * 4, hipMemcpyDeviceToHost));
+    const size_t N = (size_t)n;
+    int rc;
+    if ((rc = v->q.reserve(N * 32, N * 64)) != RUMI_OK || (rc = v->word.reserve(N, N * 2)) != RUMI_OK || (rc = v->node.reserve(N, N * 2)) != RUMI_OK ||
+        (rc = v->w.reserve(N, N * 2)) != RUMI_OK)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(v->q.p, desc, N * 32, hipMemcpyHostToDevice, nullptr));
+    if ((rc = launch_descend(v, v->q.p, nullptr, 0, n, levelsup, v->word.p, v->w.p, v->node.p, nullptr)) != RUMI_OK) return rc;
+    HIP_TRY(hipMemcpy(word_id, v->word.p, N * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(weight, v->w.p, N * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(node_id, v->node.p, N * 4, hipMemcpyDeviceToHost));
     return RUMI_OK;
 }
 

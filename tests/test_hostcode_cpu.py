@@ -39,6 +39,44 @@ def test_create_without_gpu_fails_loudly():
     assert L.rumi_orb_create(C.byref(cfg), C.byref(h)) == capi.RUMI_E_NO_DEVICE
     assert b"no CPU fallback" in L.rumi_last_error()
 
+    # every other handle that allocates when it is created refuses the same way.  (rumi_kfdb_create takes a vocabulary handle, which cannot
+    # exist without a device: its check is out of reach here.)
+    from rumi_slam_amd.matcher import ORBmatcher
+    from rumi_slam_amd.optimizer import Optimizer
+    from rumi_slam_amd.queue import RuminationQueue
+    from rumi_slam_amd.vocabulary import ORBVocabulary
+    from voc_scene import synthetic_vocabulary
+    eager = {"matcher": lambda: ORBmatcher(max_features=64, max_queries=64), "optimizer": lambda: Optimizer(64, 4, 4, 64, 64),
+             "vocabulary": lambda: ORBVocabulary(*synthetic_vocabulary(0, k=2, L=1)), "queue": lambda: RuminationQueue(1000, 1.2, 8, 20, 7, [0], 1)}
+    for name, create in eager.items():
+        with pytest.raises(capi.RumiError) as e:
+            create()
+        assert e.value.code == capi.RUMI_E_NO_DEVICE and "no CPU fallback" in str(e.value), name
+
+    # a handle that binds its device at the first call is created fine, refuses its first well-formed call and the next one alike, and is
+    # destroyed without having touched a device
+    from covis_scene import World
+    from culling_scene import small_batch
+    from refresh_scene import capacity_batch
+    from rumi_slam_amd.mapping import REFRESH_DESCRIPTOR, REFRESH_NORMAL_DEPTH, KeyFrameCuller, MapPointRefresher
+    cull, cb = KeyFrameCuller(), small_batch()
+    refresh, rb = MapPointRefresher(), capacity_batch(6)
+    w = World(8, 16)
+    for s in range(4):
+        w.add_kf(s, 10 + s, mp=[s, s + 1, -1], best=[(s + 1) % 4], parent=(s + 3) % 4, children=[(s + 1) % 4])
+    for p in range(6):
+        w.add_pt(p, [p % 4, (p + 1) % 4])
+    store = w.handle()                                               # the edits only write the host mirror
+    lazy = {"culler": lambda: cull.status(cb, 0, cb.outputs()),
+            "refresher": lambda: refresh.status(rb, REFRESH_DESCRIPTOR | REFRESH_NORMAL_DEPTH, rb.outputs()),
+            "covis update_connections": lambda: store.update_connections_into([0, 1], store.connection_outputs(2, 16, 16), 16, 16),
+            "covis local_map": lambda: store.local_map_into([0, 1, -1], store.local_map_outputs(3, 8, 16), 8, 16)}
+    for name, call in lazy.items():
+        for attempt in range(2):
+            assert call() == capi.RUMI_E_NO_DEVICE, (name, attempt)
+            assert b"no CPU fallback" in L.rumi_last_error(), (name, attempt)
+    cull.close(); refresh.close(); store.close()
+
 
 def test_invalid_config_rejected():
     L = capi.lib()
