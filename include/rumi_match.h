@@ -12,6 +12,7 @@
  *   R/lib_src/ORBmatcher.cc:1830-1844   DescriptorDistance
  *   R/lib_src/Frame.cc:441-466,695-761  AssignFeaturesToGrid / GetFeaturesInArea / PosInGrid (candidate order)
  *   R/lib_src/CloudMerging.cc:503-551   the key-point match of ComputeSubmapSim3 (rumi_submap_match)
+ *   R/lib_src/LoopClosing.cc:576-651    the BoW stage of DetectCommonRegionsFromBoW, all candidates (rumi_common_regions_bow)
  * The facade marshals Frame / KeyFrame / MapPoint pointers into the flat views below: a MapPoint* becomes an
  * int32 id into caller-side arrays, NULL becomes -1.  Mono branches only (the node hard-codes MONOCULAR,
  * R/src/cloud_edge_main.cpp:267).  Results are bit-identical to the reference's sequential loops, including
@@ -260,6 +261,40 @@ typedef struct RumiSubmapFrame {
  * finite, bounds that are not finite, a NULL array. */
 int rumi_submap_match(RumiMatcher *m, int32_t n_frames, const RumiSubmapFrame *frames, int32_t n_pairs, const int32_t *pair_f1,
                       const int32_t *pair_f2, float tolerance, int32_t *best2, int32_t *pair_start, int32_t *matches);
+
+/* The BoW stage of LoopClosing::DetectCommonRegionsFromBoW (R/lib_src/LoopClosing.cc:576-651; the same text at CloudMerging.cc:1019-1094) for ALL
+ * candidates of a key-frame in one call: SearchByBoW(mpCurrentKF, vpCovKFi[j], vvpMatchedMPs[j]) for every member j of every candidate's group
+ * (:622-633) and, per group, the fold of the match vectors into vpMatchedPoints / vpKeyFrameMatchedMP through the set of map points (:635-651).
+ * One member key-frame of the table; a key-frame that is a covisible of several candidates is listed (and uploaded) once. */
+typedef struct RumiBowKeyFrame {
+    RumiFrameFeatures feat;   /* n, keys_un (the angle is read) and desc; bounds, scale_factors and nlevels are not read */
+    RumiFeatureVector fv;     /* mFeatVec */
+    const int32_t *mp;        /* [n] GetMapPointMatches() as ids into ONE numbering shared by all members, negative = NULL */
+} RumiBowKeyFrame;
+
+/* Cur / cur_fv: the current key-frame; cur_good[i]: its feature i holds a map point that is not bad (ORBmatcher.cc:717-721).  kfs [n_kfs]: the
+ * table; mp_bad [nmp]: isBad() of the shared numbering.  Group g = one candidate that the caller did not skip or abort (:577, :593-605): members
+ * member_kf[group_start[g] .. group_start[g + 1]) index the table in vpCovKFi order (candidate first, the displaced covisible last, :583-591),
+ * bad or NULL members left out (:623).  Outputs, with M = group_start[n_groups] and n = Cur->n:
+ *   matches12 [M][n]        the member FEATURE matched to every current feature, -1 none: what rumi_search_by_bow_kf returns for that pair
+ *   nmatches [M]            the reference's return values
+ *   matched_point [G][n]    vpMatchedPoints as map-point ids, -1 NULL
+ *   matched_member [G][n]   vpKeyFrameMatchedMP as the member's position j inside its group, -1 NULL
+ *   num_bow_matches [G]     numBoWMatches
+ *   most_matches [G][2]     nIndexMostBoWMatchesKF, nMostBoWNumMatches (strictly greater, :628: the first j wins a tie; 0, 0 without matches)
+ * Exact: every result equals the literal loop's.  A member FeatureVector node with more than 512 features does not fit the batch kernel; the entry then
+ * runs rumi_search_by_bow_kf member by member and the union on the host for that call, with the same results (the handle's max_features /
+ * max_queries then apply).  RUMI_E_INVALID, with nothing written and no device work: a NULL array, group_start not ascending from 0, a member
+ * index outside the table, a map-point id >= nmp, a FeatureVector whose offsets descend, whose node ids do not ascend or that names a feature
+ * outside its key-frame. */
+int rumi_common_regions_bow(RumiMatcher *m, const RumiFrameFeatures *Cur, const RumiFeatureVector *cur_fv, const uint8_t *cur_good, int32_t n_kfs,
+                            const RumiBowKeyFrame *kfs, int32_t nmp, const uint8_t *mp_bad, int32_t n_groups, const int32_t *group_start,
+                            const int32_t *member_kf, float nnratio, int32_t check_orientation, int32_t *matches12, int32_t *nmatches,
+                            int32_t *matched_point, int32_t *matched_member, int32_t *num_bow_matches, int32_t *most_matches);
+
+/* enable != 0: later rumi_common_regions_bow calls on this handle time themselves with events.  ms5 (may be NULL) receives the last call's
+ * [host pack, upload and table clears, match kernel, finish and union kernels, copy back] in milliseconds (zeros for a call that was not timed). */
+int rumi_common_regions_bow_profile(RumiMatcher *m, int32_t enable, float *ms5);
 
 #ifdef __cplusplus
 }

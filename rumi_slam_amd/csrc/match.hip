@@ -27,10 +27,12 @@
 //   match_bruteforce_pair.inc  k_bruteforce_pair (one pair, train rows split over workgroups, last-arriver merge), launch_bruteforce_pair,
 //                         rumi_match_bruteforce_pair_*
 //   match_bow_batch.inc   k_bow_batch_match, k_bow_batch_finish (BowKF, BowBatch) and rumi_search_by_bow_batch
+//   match_bow_kf_batch.inc  k_crb_match, k_crb_finish, k_crb_union (CrKF, CrArgs) and rumi_common_regions_bow
 //   match_submap.inc      k_grid_batch, k_submap_match, k_submap_compact (SubFrame, SubPair) and rumi_submap_match
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -275,4 +277,5 @@ void launch_resolve(const ResolveArgs &A, hipStream_t st) {
 #include "match_bruteforce.inc"
 #include "match_bruteforce_pair.inc"
 #include "match_bow_batch.inc"
+#include "match_bow_kf_batch.inc"
 #include "match_submap.inc"

@@ -86,6 +86,10 @@ struct RumiMatcher {
     // rumi_submap_match: frame / pair tables, uploaded key-points, grids and block counts in dSub; one result block back (grown on demand)
     rumi::DevBuf<uint8_t> sub;
     rumi::MirrorBuf<uint8_t> subOut;
+    // rumi_common_regions_bow: one pinned block up, one result block back (grown on demand); the last call's event times when profiling is on
+    rumi::MirrorBuf<uint8_t> crb, crbOut;
+    bool crbProfile = false;
+    float crbMs[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     // k_grid of the uploaded frame, launched by flush_uploads once the key-points are in place
     const int32_t *gridNDev = nullptr;     // k_grid reads the count from the device (one call only: cleared by the flush)
     hipStream_t upStream = nullptr;        // where the next flush queues its copy and scatter (the caller orders its kernels behind them)

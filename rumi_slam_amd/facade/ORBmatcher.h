@@ -28,6 +28,10 @@ public:
     static const int TH_HIGH = RUMI_TH_HIGH;
     static const int HISTO_LENGTH = RUMI_HISTO_LENGTH;
 
+    // what the matcher was constructed with, for the batched stages that run its searches in one call (LoopClosingStep.h)
+    float NNRatio() const { return mfNNratio; }
+    bool CheckOrientation() const { return mbCheckOrientation; }
+
     // Computes the Hamming distance between two ORB descriptors
     static int DescriptorDistance(const cv::Mat &a, const cv::Mat &b) { return rumi_descriptor_distance(a.ptr(0), b.ptr(0)); }
 

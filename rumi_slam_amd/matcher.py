@@ -20,9 +20,13 @@ class RumiFeatureVector(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("node_ids", C.c_void_p), ("offsets", C.c_void_p), ("indices", C.c_void_p)]
 
 
+class RumiBowKeyFrame(C.Structure):
+    _fields_ = [("feat", RumiFrameFeatures), ("fv", RumiFeatureVector), ("mp", C.c_void_p)]
+
+
 MATCH_SYMBOLS = ["rumi_descriptor_distance", "rumi_match_create", "rumi_match_destroy", "rumi_search_by_projection_mappoints",
                  "rumi_search_by_projection_frame", "rumi_search_by_bow", "rumi_search_by_bow_kf", "rumi_search_by_projection_sim3",
-                 "rumi_search_by_projection_reloc", "rumi_search_for_initialization", "rumi_search_for_triangulation", "rumi_fuse_candidates", "rumi_search_by_sim3", "rumi_frame_is_in_frustum", "rumi_search_by_bow_batch", "rumi_match_bruteforce_batch_device",
+                 "rumi_search_by_projection_reloc", "rumi_search_for_initialization", "rumi_search_for_triangulation", "rumi_fuse_candidates", "rumi_search_by_sim3", "rumi_frame_is_in_frustum", "rumi_search_by_bow_batch", "rumi_common_regions_bow", "rumi_common_regions_bow_profile", "rumi_match_bruteforce_batch_device",
                  "rumi_match_bruteforce_batch_device_strided", "rumi_match_bruteforce_ring_device", "rumi_match_bruteforce_shape",
                  "rumi_match_bruteforce_pair_scratch_bytes", "rumi_match_bruteforce_pair_shape", "rumi_match_bruteforce_pair_device"]
 
@@ -54,6 +58,8 @@ def _lib():
     L.rumi_frame_is_in_frustum.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rumi_match_bruteforce_batch_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     L.rumi_search_by_bow_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp]
+    L.rumi_common_regions_bow.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp]
+    L.rumi_common_regions_bow_profile.argtypes = [vp, i32, vp]
     L.rumi_match_bruteforce_batch_device_strided.argtypes = [vp, vp, vp, vp, i32, C.c_int64, C.c_int64, i32, i32, vp, vp, vp, vp]
     L.rumi_match_bruteforce_ring_device.argtypes = [vp, vp, i32, C.c_int64, i32, i32, vp, vp, vp, vp]
     L.rumi_match_bruteforce_shape.argtypes = [vp]
@@ -211,6 +217,59 @@ def SearchByBoW_batch(m, KFs, kf_fvs, kf_mps, mp_bads, F, f_fv):
     capi.check(m._lib.rumi_search_by_bow_batch(m._h, K, kfa, fva, mpp, capi.ptr(nmp), bdp, C.byref(F.c), C.byref(f_fv.c), m.mfNNratio,
                                                int(m.mbCheckOrientation), capi.ptr(matches), capi.ptr(nm)))
     return nm, matches
+
+
+def CommonRegionsBoW_status(m, Cur, cur_fv, cur_good, kfs, mp_bad, groups, nnratio=None, check_ori=None, fill=-1):
+    """``rumi_common_regions_bow`` with its status code instead of an exception (m may be None: the entry then refuses for want of a handle, after
+    every check of the arguments).  An argument given as None goes in as a NULL pointer (a table with a count of 1).  The outputs start out filled with ``fill``.
+    Returns (rc, matches12, nmatches, matched_point, matched_member, num_bow_matches, most_matches)."""
+    L = _lib()
+    n = Cur.n if Cur is not None else 0
+    good = None if cur_good is None else _u8(cur_good)
+    bad = None if mp_bad is None else _u8(mp_bad)
+    mps = [None if k[2] is None else np.ascontiguousarray(k[2], np.int32) for k in (kfs or [])]
+    table = None
+    if kfs is not None:
+        table = (RumiBowKeyFrame * max(len(kfs), 1))()
+        for t, (F, fv, _), a in zip(table, kfs, mps):
+            t.feat, t.fv, t.mp = F.c, fv.c, (None if a is None else a.ctypes.data)
+    start = member = None
+    if groups is not None:
+        if isinstance(groups, tuple):                          # (group_start, member_kf) as given, for a caller that wants them malformed
+            start, member = np.ascontiguousarray(groups[0], np.int32), np.ascontiguousarray(groups[1], np.int32)
+        else:
+            start = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int32)
+            member = np.array([k for g in groups for k in g], np.int32)
+    G = 0 if start is None else len(start) - 1
+    M = 0 if member is None else len(member)
+    out = [np.full((M, n), fill, np.int32), np.full(M, fill, np.int32), np.full((G, n), fill, np.int32), np.full((G, n), fill, np.int32),
+           np.full(G, fill, np.int32), np.full((G, 2), fill, np.int32)]
+    p = lambda a: None if a is None else capi.ptr(a)
+    rc = L.rumi_common_regions_bow(m._h if m is not None else None, None if Cur is None else C.addressof(Cur.c), None if cur_fv is None else C.addressof(cur_fv.c),
+                                   p(good), 1 if kfs is None else len(kfs), None if table is None else C.addressof(table), 1 if bad is None else len(bad), p(bad),
+                                   G, p(start), p(member), float(m.mfNNratio if nnratio is None else nnratio),
+                                   int(m.mbCheckOrientation if check_ori is None else check_ori), *[capi.ptr(a) for a in out])
+    return (rc, *out)
+
+
+def CommonRegionsBoW(m, Cur, cur_fv, cur_good, kfs, mp_bad, groups, nnratio=None, check_ori=None):
+    """The BoW stage of LoopClosing::DetectCommonRegionsFromBoW (LoopClosing.cc:576-651) for every candidate in one call.  Cur / cur_fv: the current
+    key-frame (FrameView, FeatureVector); cur_good[i]: its feature i holds a map point that is not bad.  kfs: the distinct member key-frames as
+    (FrameView, FeatureVector, mp) with mp[i] an id into ONE numbering shared by all members (-1 NULL); mp_bad: isBad() over that numbering.
+    groups: one list per candidate of indices into kfs, in vpCovKFi order.  nnratio / check_ori default to the handle's.
+    Returns (matches12 [M, n], nmatches [M], matched_point [G, n], matched_member [G, n], num_bow_matches [G], most_matches [G, 2])."""
+    r = CommonRegionsBoW_status(m, Cur, cur_fv, cur_good, kfs, mp_bad, groups, nnratio, check_ori)
+    capi.check(r[0])
+    return r[1:]
+
+
+def CommonRegionsBoW_times(m, enable=None):
+    """The last CommonRegionsBoW call's [host pack, upload and clears, match kernel, finish and union kernels, copy back] in ms; enable: switch the event
+    timing of later calls on or off."""
+    ms = np.zeros(5, np.float32)
+    on = m._crb_profile = bool(getattr(m, "_crb_profile", False) if enable is None else enable)
+    capi.check(_lib().rumi_common_regions_bow_profile(m._h, int(on), capi.ptr(ms)))
+    return ms
 
 
 def _f32(a):
