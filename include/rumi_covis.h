@@ -7,7 +7,8 @@
  * The handle keeps, on the device and between calls, what those members read and nothing else.  A key-frame is a slot 0 .. max_kf-1 chosen
  * by the caller, a map point an id 0 .. max_points-1.
  *   per key-frame slot: mp[n] (GetMapPointMatches as point ids, -1 = NULL), is_bad, map_id, order_key, best[10]
- *                       (GetBestCovisibilityKeyFrames(10) as slots, -1 padded), parent slot or -1, the children as a slot list
+ *                       (GetBestCovisibilityKeyFrames(10) as slots, -1 padded), parent slot or -1, the children as a slot list; and
+ *                       optionally its features (rumi_covis_set_keyframe_features, below), which the two members above do not read
  *   per point:          is_bad, the observers (the key-frame slots of GetObservations(); feature indices are not kept), and optionally the
  *                       attributes TrackLocalMap reads: GetWorldPos, GetNormal, mfMinDistance, mfMaxDistance, GetDescriptor, and a "has
  *                       attributes" bit.  Observations() is not a field: for the monocular model it is the length of the observer row.
@@ -29,6 +30,7 @@
 #define RUMI_COVIS_H
 #include <stdint.h>
 
+#include "rumi_match.h"
 #include "rumi_orb.h"
 
 #ifdef __cplusplus
@@ -67,6 +69,25 @@ int rumi_covis_set_point_attributes(RumiCovis *c, int32_t n, const int32_t *ids,
 int rumi_covis_set_bad(RumiCovis *c, int32_t n_kf, const int32_t *slots, const uint8_t *kf_bad, int32_t n_pt, const int32_t *ids, const uint8_t *pt_bad);
 /* KeyFrame::GetMap of n live slots changed (map merge). */
 int rumi_covis_set_maps(RumiCovis *c, int32_t n, const int32_t *slots, const int32_t *map_ids);
+
+/* ---- Key-frame features: what never changes after the key-frame is built -- mvKeysUn (whole RumiKeyPoint records, angle included),
+ * mDescriptors, mvScaleFactors, mFeatVec (CSR) and fx fy cx cy -- kept on the device once per key-frame, so that a consumer names slots
+ * instead of uploading key-frames (rumi_create_new_map_points_resident, rumi_mapping.h).  The host keeps no copy of the feature bytes, only
+ * where each block lies.
+ *
+ * slot must be live.  Setting a slot again replaces its features.  Validated like rumi_create_new_map_points validates a key-frame (sizes,
+ * octaves inside nlevels, FeatureVector offsets and indices in range, node ids strictly ascending, no feature listed twice; the same
+ * messages), and at most RUMI_COVIS_MAX_FEATURES features (RUMI_E_CAPACITY).  Staged like every edit: the call makes no device call, the
+ * next consumer sends what is staged.  A refused call leaves the store untouched. */
+int rumi_covis_set_keyframe_features(RumiCovis *c, int32_t slot, const RumiFrameFeatures *feat, const RumiFeatureVector *fv, const float *K4);
+/* n slots inside 0..max_kf-1; a slot without features is not an error.  The blocks become free space that later key-frames reuse. */
+int rumi_covis_drop_keyframe_features(RumiCovis *c, int32_t n, const int32_t *slots);
+/* First size of the feature arena in bytes (0: a default); before the first rumi_covis_set_keyframe_features, RUMI_E_INVALID afterwards.
+ * The arena doubles when a block fits neither a free block nor the tail; growth copies device to device. */
+int rumi_covis_reserve_features(RumiCovis *c, int64_t bytes);
+/* out6: arena capacity, bytes in use, slots that hold features, growths, compactions (0: freed blocks are reused through a free list),
+ * bytes of feature data in the last upload. */
+int rumi_covis_feature_stats(const RumiCovis *c, int64_t *out6);
 
 /* KeyFrame::UpdateConnections for the key-frames batch[0 .. B), live slots in this order; a slot may repeat.  Per entry b:
  *   status[b]                                                  RUMI_COVIS_CONNECTED or RUMI_COVIS_EMPTY (both lists empty then)

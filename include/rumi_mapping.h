@@ -30,6 +30,7 @@
 
 #include <stdint.h>
 
+#include "rumi_covis.h"
 #include "rumi_match.h"
 
 #ifdef __cplusplus
@@ -86,6 +87,31 @@ typedef struct RumiNewPoint {
 int rumi_create_new_map_points(RumiMatcher *m, const RumiNewPointsKF *cur, const RumiNewPointsKF *neigh, int32_t n_neigh,
                                const RumiNewPointsParams *p, RumiNewPoint *out, int32_t cap, int32_t *n_out,
                                int32_t *per_neigh_out, uint8_t *neigh_skipped_out);
+
+/* ---- The same member over key-frames that are resident in a covisibility store (rumi_covis.h): the caller names slots, and only what a
+ * bundle adjustment changes travels per call. */
+typedef struct RumiNewPointsPose {
+    float Tcw[12], Ow[3];            /* as in RumiNewPointsKF */
+    float F12[9], epipole2[2];       /* neighbours only, formed as for rumi_create_new_map_points */
+} RumiNewPointsPose;
+
+/* rumi_create_new_map_points with every key-frame read where the store keeps it: outputs and statuses are those of that entry on the same
+ * data, byte for byte (the same kernels, instantiated over another view of the data).
+ *   feat, fv, K4      the slot's features (rumi_covis_set_keyframe_features)
+ *   kf_mp[i] >= 0     mp[i] >= 0 of the slot's map-point row, read in place
+ *   mp_pos[i]         the position in point mp[i]'s attribute record (rumi_covis_set_point_attributes); neighbours only
+ * Host to device per call: the store's staged edits and staged features, and a table of n_neigh + 1 pose records.
+ * RUMI_E_INVALID, nothing written: a slot that is not live or holds no features; a slot named twice, cur_slot among the neighbours; a slot
+ * whose feature count differs from the length of its map-point row; matcher and store on different devices; a neighbour entry >= 0 whose
+ * point has no attributes (found on the device; the message names how many).  RUMI_E_CAPACITY as for rumi_create_new_map_points.
+ * n_neigh == 0: RUMI_OK, *n_out = 0, no device call.  rumi_hook_newpts_matches does not replay a resident call (RUMI_E_INVALID). */
+int rumi_create_new_map_points_resident(RumiMatcher *m, RumiCovis *c, int32_t cur_slot, const RumiNewPointsPose *cur_pose,
+                                        const int32_t *neigh_slots, const RumiNewPointsPose *neigh_pose, int32_t n_neigh,
+                                        const RumiNewPointsParams *p, RumiNewPoint *out, int32_t cap, int32_t *n_out,
+                                        int32_t *per_neigh_out, uint8_t *neigh_skipped_out);
+
+/* The last call of either entry on this matcher, in ms: validation + packing | upload, kernels, download | write-out. */
+int rumi_newpts_stage_ms(const RumiMatcher *m, float *out3);
 
 /* ---- MapPoint::ComputeDistinctiveDescriptors (R/lib_src/MapPoint.cc:353-427) and MapPoint::UpdateNormalAndDepth (:450-518) for a batch of
  * points.  Neither member reads another MapPoint: a point's result depends on its own observation list, its position and reference

@@ -82,6 +82,26 @@ class Covisibility:
         s = np.ascontiguousarray(slots, _i32); m = np.ascontiguousarray(maps, _i32)
         return self._ret(self._lib.rumi_covis_set_maps(self._h, len(s), _p(s), _p(m)), check)
 
+    # ---- key-frame features: uploaded once per key-frame, read in place by mapping.CreateNewMapPointsResident ----
+    def set_keyframe_features(self, slot, frame, fv, K4, check=True):
+        """mvKeysUn, mDescriptors, mvScaleFactors (``frame``: a matcher.FrameView), mFeatVec (``fv``: a matcher.FeatureVector) and fx fy cx cy
+        of a live slot; setting a slot again replaces them.  Staged: the next consumer uploads them."""
+        K4 = np.ascontiguousarray(K4, np.float32).reshape(4)
+        return self._ret(self._lib.rumi_covis_set_keyframe_features(self._h, int(slot), C.byref(frame.c), C.byref(fv.c), _p(K4)), check)
+
+    def drop_keyframe_features(self, slots, check=True):
+        s = np.ascontiguousarray(slots, _i32).reshape(-1)
+        return self._ret(self._lib.rumi_covis_drop_keyframe_features(self._h, len(s), _p(s)), check)
+
+    def reserve_features(self, nbytes, check=True):
+        """First size of the feature arena (0: the default); before the first set_keyframe_features."""
+        return self._ret(self._lib.rumi_covis_reserve_features(self._h, int(nbytes)), check)
+
+    def feature_stats(self):
+        v = np.zeros(6, np.int64)
+        capi.check(self._lib.rumi_covis_feature_stats(self._h, _p(v)))
+        return dict(zip(("capacity", "used", "slots", "growths", "compactions", "last_upload_bytes"), (int(x) for x in v)))
+
     # ---- queries ----
     @staticmethod
     def connection_outputs(B, conn_cap, ord_cap, fill=0):

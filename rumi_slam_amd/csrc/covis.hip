@@ -12,6 +12,7 @@
 //                           rebuilt on the host (compacted, and doubled when the live rows fill more than three quarters of it) and sent whole.
 //   tag    [max_points]     64-bit stamps of the local-point selection, (call epoch << 32) | priority
 //   rowOf  [max_points]     64-bit stamps of the same epoch for rumi_track_local_map's id -> table row map (allocated with its first call)
+//   feat                    the key-frames' constant part, a byte arena of its own with no host mirror (covis_features.inc)
 // The host keeps a mirror of kf, pt, attr and the arena; an edit writes the mirror and notes (table, offset, words).  The next query packs the noted
 // ranges and its own input into one pinned block, sends it with one copy, and k_covis_apply scatters it.
 //
@@ -25,6 +26,7 @@
 //                         tag[point], the count of the winners per workgroup, and their write at the prefix offsets.
 // Integer arithmetic only; no float atomics, and every sum is independent of arrival order.
 #include <climits>
+#include <cstdlib>
 #include <cstring>
 #include <unordered_map>
 #include <vector>
@@ -32,6 +34,7 @@
 #include "rumi_common.h"
 #include "rumi_covis.h"
 #include "rumi_internal.h"
+#include "keyframe_features.h"
 
 namespace rumi {
 namespace {
@@ -302,8 +305,32 @@ template <int PASS> __global__ __launch_bounds__(kThreads) void k_covis_local(Lo
 
 using namespace rumi;
 
+// The key-frame features (covis_features.inc): where each slot's block lies, the free blocks, what is staged.  No feature byte stays on the
+// host once it is on the device.
+struct FeatPlace { int64_t off = -1, stageOff = -1; CovisFeatRec rec{}; };       // off: in the arena; stageOff >= 0: still in the staging block
+struct FeatureStore {
+    std::vector<FeatPlace> place;                                // [max_kf], with the first set
+    std::vector<std::pair<int64_t, int64_t>> freeList;           // (offset, bytes) ascending, neighbours merged, none touching the tail
+    int64_t cap = 0, firstCap = 0, tail = 0, used = 0, slots = 0, growths = 0, compactions = 0, lastUpload = 0;
+    uint8_t *stage = nullptr;                                    // ordinary memory until the store has a device, pinned from then on
+    size_t stageCap = 0, stageUsed = 0;
+    bool stagePinned = false;
+    std::vector<std::pair<int32_t, int64_t>> staged;             // (slot, stageOff) in staging order; stale when the slot's stageOff differs
+    DevBuf<uint8_t> arena;
+    int64_t onDevice = 0;                                        // the device arena holds what lies below
+    FeatureStore() = default;
+    FeatureStore(const FeatureStore &) = delete;
+    FeatureStore &operator=(const FeatureStore &) = delete;
+    ~FeatureStore() { release_stage(); }
+    void release_stage() {
+        if (stage) { if (stagePinned) (void)hipHostFree(stage); else std::free(stage); }
+        stage = nullptr; stageCap = 0;
+    }
+};
+
 struct RumiCovis {
     DeviceBinding dev;
+    FeatureStore feat;
     int32_t maxKf = 0, maxPts = 0;
     // host mirrors of the device tables
     std::vector<int32_t> kf, pt, arena, attr;        // attr: empty until the first rumi_covis_set_point_attributes
@@ -883,6 +910,8 @@ extern "C" int rumi_covis_local_map(RumiCovis *h, int32_t n, const int32_t *fram
     h->clock.finish(h->stageMs);
     return RUMI_OK;
 }
+
+#include "covis_features.inc"
 
 extern "C" int rumi_covis_stage_ms(const RumiCovis *h, float *out3) {
     if (!h || !out3) return RUMI_E_INVALID;

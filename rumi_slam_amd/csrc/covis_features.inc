@@ -1,0 +1,228 @@
+// The key-frame features of the covisibility store (include/rumi_covis.h; part of covis.hip): mvKeysUn, mDescriptors, mvScaleFactors, mFeatVec
+// and the intrinsics of every slot, uploaded once and read where they lie by rumi_create_new_map_points_resident (mapping.hip).
+//
+//   block   CovisFeatRec (64 bytes: sizes, K4, where each array lies behind the record), keys, desc, scale, node ids, offsets, indices; every
+//           array 16-byte aligned, padding zeroed.  The record travels with its arrays, so a key-frame is one contiguous copy and a consumer
+//           needs one 64-bit block offset per key-frame.
+//   arena   one device allocation.  A block goes to the first free block that holds it (first fit; the rest of the free block stays free), else
+//           to the tail; when the tail would pass the capacity, the capacity doubles until it fits.  Growth allocates the new arena, copies
+//           the old one device to device and releases it: nothing is uploaded twice.  A dropped or replaced block joins the free list, merged
+//           with free neighbours; a free block at the tail pulls the tail back.  Offsets are 64-bit.
+//   staging rumi_covis_set_keyframe_features validates, places the block (host arithmetic only) and writes it into the staging block; the next
+//           consumer sends the staging block with one copy per run of blocks that are neighbours in both places (one key-frame, or any number
+//           appended at the tail: one copy).  The staging block is empty afterwards.
+
+namespace {
+
+constexpr int64_t kFeatDefaultCap = 32ll << 20;
+constexpr int64_t kFeatLimit = 1ll << 38;              // far above any device; keeps the doubling below 2^63
+
+// The record of a validated key-frame; false when the block would pass 2 GiB (the record's 32-bit offsets).
+bool feat_layout(const RumiFrameFeatures &f, const RumiFeatureVector &v, const float *K4, CovisFeatRec *r) {
+    const uint64_t n = (uint64_t)f.n, nn = (uint64_t)v.n_nodes, ne = nn ? (uint64_t)v.offsets[nn] : 0;
+    uint64_t at = sizeof(CovisFeatRec);
+    auto put = [&](uint64_t bytes) { const uint64_t o = at; at = up16(at + bytes); return o; };
+    const uint64_t keys = put(n * sizeof(RumiKeyPoint)), desc = put(n * 32), scale = put((uint64_t)f.nlevels * 4), nodes = put(nn * 4),
+                   off = put((nn + 1) * 4), idx = put(ne * 4);
+    if (at >= (1ull << 31)) return false;
+    r->n = (int32_t)n; r->nn = (int32_t)nn; r->ne = (int32_t)ne; r->nlevels = f.nlevels;
+    std::memcpy(r->K, K4, 16);
+    r->keys = (uint32_t)keys; r->desc = (uint32_t)desc; r->scale = (uint32_t)scale; r->nodes = (uint32_t)nodes; r->off = (uint32_t)off; r->idx = (uint32_t)idx;
+    r->bytes = (uint32_t)at; r->pad = 0;
+    return true;
+}
+
+void feat_free(FeatureStore &F, int64_t off, int64_t bytes) {
+    auto it = std::lower_bound(F.freeList.begin(), F.freeList.end(), std::make_pair(off, (int64_t)0));
+    it = F.freeList.insert(it, {off, bytes});
+    if (it + 1 != F.freeList.end() && it->first + it->second == (it + 1)->first) { it->second += (it + 1)->second; F.freeList.erase(it + 1); }
+    if (it != F.freeList.begin() && (it - 1)->first + (it - 1)->second == it->first) { (it - 1)->second += it->second; it = F.freeList.erase(it) - 1; }
+    if (it->first + it->second == F.tail) { F.tail = it->first; F.freeList.erase(it); }
+}
+
+int64_t feat_alloc(FeatureStore &F, int64_t bytes) {
+    for (auto it = F.freeList.begin(); it != F.freeList.end(); ++it)
+        if (it->second >= bytes) {
+            const int64_t off = it->first;
+            if (it->second == bytes) F.freeList.erase(it); else { it->first += bytes; it->second -= bytes; }
+            return off;
+        }
+    if (F.cap == 0) F.cap = F.firstCap ? F.firstCap : kFeatDefaultCap;
+    if (F.tail + bytes > F.cap) {
+        while (F.tail + bytes > F.cap) F.cap *= 2;
+        F.growths++;
+    }
+    const int64_t off = F.tail;
+    F.tail += bytes;
+    return off;
+}
+
+// Room for `need` bytes in the staging block, what it holds kept.  Pinned once the store has a device (a set_ call on a machine without one
+// must still succeed, so that refusals can be tested there); feat_flush re-houses an unpinned block.
+int feat_stage_reserve(RumiCovis *h, size_t need, bool pinned) {
+    FeatureStore &F = h->feat;
+    if (need <= F.stageCap && (F.stagePinned || !pinned)) return RUMI_OK;
+    const size_t cap = std::max(need + need / 2, (size_t)1 << 20);
+    uint8_t *p = nullptr;
+    if (pinned) {
+        HIP_TRY(hipSetDevice(h->dev.device));
+        const int rc = pin_alloc(&p, cap);
+        if (rc != RUMI_OK) return rc;
+    } else if (!(p = static_cast<uint8_t *>(std::malloc(cap)))) {
+        g_lastError = "rumi_covis_set_keyframe_features: out of host memory for the staging block";
+        return RUMI_E_CAPACITY;
+    }
+    if (F.stageUsed) std::memcpy(p, F.stage, F.stageUsed);
+    F.release_stage();
+    F.stage = p; F.stageCap = cap; F.stagePinned = pinned;
+    return RUMI_OK;
+}
+
+void feat_remove(FeatureStore &F, int32_t slot) {
+    FeatPlace &P = F.place[slot];
+    if (P.off < 0) return;
+    feat_free(F, P.off, P.rec.bytes);
+    F.used -= P.rec.bytes; F.slots--;
+    P = FeatPlace{};
+}
+
+// Grows the device arena to the capacity the placements assume (device to device), then sends what is staged.
+int feat_flush(RumiCovis *h) {
+    FeatureStore &F = h->feat;
+    F.lastUpload = 0;
+    if (F.cap > 0 && (int64_t)F.arena.cap < F.cap) {
+        DevBuf<uint8_t> grown;
+        const int rc = grown.reserve((size_t)F.cap, (size_t)F.cap);
+        if (rc != RUMI_OK) return rc;
+        if (F.arena.p && F.onDevice > 0) HIP_TRY(hipMemcpyAsync(grown.p, F.arena.p, (size_t)F.onDevice, hipMemcpyDeviceToDevice, nullptr));
+        std::swap(grown.p, F.arena.p); std::swap(grown.cap, F.arena.cap);        // `grown` releases the old arena; hipFree waits for the copy
+    }
+    if (!F.staged.empty() && !F.stagePinned) {
+        const int rc = feat_stage_reserve(h, F.stageUsed, true);
+        if (rc != RUMI_OK) return rc;
+    }
+    int64_t src = -1, dst = -1, len = 0;                                         // the run being collected
+    auto send = [&]() -> hipError_t {
+        const hipError_t e = len ? hipMemcpyAsync(F.arena.p + dst, F.stage + src, (size_t)len, hipMemcpyHostToDevice, nullptr) : hipSuccess;
+        F.lastUpload += len; len = 0;
+        return e;
+    };
+    for (const auto &st : F.staged) {
+        FeatPlace &P = F.place[st.first];
+        if (P.off < 0 || P.stageOff != st.second) continue;                      // dropped or replaced since
+        if (len && (src + len != P.stageOff || dst + len != P.off)) HIP_TRY(send());
+        if (!len) { src = P.stageOff; dst = P.off; }
+        len += P.rec.bytes;
+        P.stageOff = -1;
+    }
+    HIP_TRY(send());
+    F.staged.clear(); F.stageUsed = 0;
+    F.onDevice = F.tail;
+    return RUMI_OK;
+}
+
+}  // namespace
+
+extern "C" int rumi_covis_reserve_features(RumiCovis *h, int64_t bytes) {
+    if (!h || bytes < 0 || bytes > kFeatLimit) { g_lastError = "rumi_covis_reserve_features: missing handle, or a size outside 0..2^38"; return RUMI_E_INVALID; }
+    if (h->feat.cap != 0) { g_lastError = "rumi_covis_reserve_features: the feature arena is in use; its first size is set before the first key-frame"; return RUMI_E_INVALID; }
+    h->feat.firstCap = bytes ? (int64_t)up16((size_t)std::max<int64_t>(bytes, 4096)) : 0;
+    return RUMI_OK;
+}
+
+extern "C" int rumi_covis_set_keyframe_features(RumiCovis *h, int32_t slot, const RumiFrameFeatures *feat, const RumiFeatureVector *fv, const float *K4) {
+    if (!h || !feat || !fv || !K4) { g_lastError = "rumi_covis_set_keyframe_features: missing argument"; return RUMI_E_INVALID; }
+    if (!is_live(h, slot)) { g_lastError = "rumi_covis_set_keyframe_features: a slot that is not live"; return RUMI_E_INVALID; }
+    if (feat->n > RUMI_COVIS_MAX_FEATURES) {                                     // before any array is read
+        g_lastError = "rumi_covis_set_keyframe_features: more than RUMI_COVIS_MAX_FEATURES features";
+        return RUMI_E_CAPACITY;
+    }
+    const char *why = "";
+    if (!keyframe_features_valid(*feat, *fv, &why)) { g_lastError = why; return RUMI_E_INVALID; }
+    FeatureStore &F = h->feat;
+    CovisFeatRec rec;
+    if (!feat_layout(*feat, *fv, K4, &rec) || F.tail + (int64_t)rec.bytes > kFeatLimit) {
+        g_lastError = "rumi_covis_set_keyframe_features: the key-frame's block or the feature arena would pass its size limit";
+        return RUMI_E_CAPACITY;
+    }
+    const int rc = feat_stage_reserve(h, F.stageUsed + rec.bytes, h->dev.bound);
+    if (rc != RUMI_OK) return rc;
+    // ---- nothing refuses from here on
+    if (F.place.empty()) F.place.resize((size_t)h->maxKf);
+    feat_remove(F, slot);
+    FeatPlace &P = F.place[slot];
+    P.rec = rec;
+    P.off = feat_alloc(F, rec.bytes);
+    P.stageOff = (int64_t)F.stageUsed;
+    F.used += rec.bytes; F.slots++;
+    uint8_t *b = F.stage + F.stageUsed;
+    std::memset(b, 0, rec.bytes);
+    std::memcpy(b, &rec, sizeof rec);
+    const size_t n = (size_t)rec.n, nn = (size_t)rec.nn;
+    if (n) { std::memcpy(b + rec.keys, feat->keys_un, n * sizeof(RumiKeyPoint)); std::memcpy(b + rec.desc, feat->desc, n * 32); }
+    std::memcpy(b + rec.scale, feat->scale_factors, (size_t)rec.nlevels * 4);
+    if (nn) {
+        std::memcpy(b + rec.nodes, fv->node_ids, nn * 4); std::memcpy(b + rec.off, fv->offsets, (nn + 1) * 4);
+        if (rec.ne) std::memcpy(b + rec.idx, fv->indices, (size_t)rec.ne * 4);
+    }
+    F.staged.push_back({slot, P.stageOff});
+    F.stageUsed += rec.bytes;
+    return RUMI_OK;
+}
+
+extern "C" int rumi_covis_drop_keyframe_features(RumiCovis *h, int32_t n, const int32_t *slots) {
+    if (!h || n < 0 || (n > 0 && !slots)) { g_lastError = "rumi_covis_drop_keyframe_features: missing argument or negative count"; return RUMI_E_INVALID; }
+    for (int i = 0; i < n; i++)
+        if (slots[i] < 0 || slots[i] >= h->maxKf) { g_lastError = "rumi_covis_drop_keyframe_features: a slot outside 0..max_kf-1"; return RUMI_E_INVALID; }
+    if (!h->feat.place.empty())
+        for (int i = 0; i < n; i++) feat_remove(h->feat, slots[i]);
+    return RUMI_OK;
+}
+
+extern "C" int rumi_covis_feature_stats(const RumiCovis *h, int64_t *out6) {
+    if (!h || !out6) return RUMI_E_INVALID;
+    const FeatureStore &F = h->feat;
+    const int64_t v[6] = {F.cap, F.used, F.slots, F.growths, F.compactions, F.lastUpload};
+    std::memcpy(out6, v, sizeof v);
+    return RUMI_OK;
+}
+
+int rumi::covis_features_check(RumiCovis *h, int n, const int32_t *slots, int wantDevice, const char *entry, CovisSlotFeatures *info) {
+    const FeatureStore &F = h->feat;
+    if (h->stampKf > INT32_MAX - 4) { std::fill(h->kfStamp.begin(), h->kfStamp.end(), 0); h->stampKf = 0; }
+    const int32_t inCall = ++h->stampKf;
+    for (int i = 0; i < n; i++) {
+        const int32_t s = slots[i];
+        if (!is_live(h, s) || F.place.empty() || F.place[s].off < 0) {
+            g_lastError = std::string(entry) + ": a slot that is not live or holds no features (rumi_covis_set_keyframe_features)";
+            return RUMI_E_INVALID;
+        }
+        if (h->kfStamp[s] == inCall) { g_lastError = std::string(entry) + ": a slot named twice (the current key-frame is not its own neighbour)"; return RUMI_E_INVALID; }
+        h->kfStamp[s] = inCall;
+        const int32_t *K = h->kf.data() + (size_t)s * KFW;
+        if (F.place[s].rec.n != K[K_MPLEN]) {
+            g_lastError = std::string(entry) + ": a slot whose feature count differs from the length of its map-point row";
+            return RUMI_E_INVALID;
+        }
+    }
+    if (wantDevice >= 0) {
+        if (!h->dev.bound && h->dev.device < 0) h->dev.device = wantDevice;      // a store without a device takes the consumer's
+        const int rc = bind_device(h);
+        if (rc != RUMI_OK) return rc;
+        if (h->dev.device != wantDevice) { g_lastError = std::string(entry) + ": the store and the matcher are on different devices"; return RUMI_E_INVALID; }
+    }
+    for (int i = 0; i < n; i++) {                        // rows move when an edit is staged (set_row), never in a query
+        const FeatPlace &P = F.place[slots[i]];
+        const int32_t *K = h->kf.data() + (size_t)slots[i] * KFW;
+        info[i] = CovisSlotFeatures{P.rec.n, P.rec.nn, P.rec.ne, K[K_MPOFF], K[K_MPLEN], P.off};
+    }
+    return RUMI_OK;
+}
+
+int rumi::covis_features_flush(RumiCovis *h, CovisFeatureView *view) {
+    int rc;
+    uint8_t *unused = nullptr;
+    if ((rc = flush(h, nullptr, 0, &unused)) != RUMI_OK || (rc = feat_flush(h)) != RUMI_OK) return rc;
+    *view = CovisFeatureView{h->dArena.p, h->dPt.p, h->dAttr.p, h->feat.arena.p};
+    return RUMI_OK;
+}

@@ -11,11 +11,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "rumi_mapping.h"
 #include "rumi_testhooks.h"
+#include "keyframe_features.h"
 #include "match_host.h"
 
 namespace rumi {
@@ -36,6 +40,72 @@ enum { GATE_OK = 0, GATE_PARALLAX, GATE_W0, GATE_Z1, GATE_Z2, GATE_REPROJ1, GATE
 
 template <class T> __device__ __forceinline__ const T *at(const uint8_t *blk, uint32_t off) { return reinterpret_cast<const T *>(blk + off); }
 
+// ---- views --------------------------------------------------------------------------------------------------------------------------------
+// The four kernels below read a key-frame through a view: view.kf(i) is key-frame i of the call (0 = the current one), and what it returns
+// names every array and small matrix.  The kernels hold the arithmetic once; the two entries differ only in where the bytes lie.
+//   BlockView     rumi_create_new_map_points: everything inside the call's upload block, arrays at blk + offset.
+//   ResidentView  rumi_create_new_map_points_resident: features in the store's feature arena (a CovisFeatRec and its arrays), the map-point
+//                 row where the covisibility store keeps it, positions in the scratch k_newpts_gather filled, poses in the call's table.
+struct BlockView {
+    const uint8_t *blk;
+    struct KF {
+        const uint8_t *blk; const KFDev *d;
+        __device__ __forceinline__ int n() const { return d->n; }
+        __device__ __forceinline__ int nn() const { return d->nn; }
+        __device__ __forceinline__ const RumiKeyPoint *keys() const { return at<RumiKeyPoint>(blk, d->keys); }
+        __device__ __forceinline__ const uint8_t *desc() const { return blk + d->desc; }
+        __device__ __forceinline__ const float *scale() const { return at<float>(blk, d->scale); }
+        __device__ __forceinline__ const uint32_t *nodes() const { return at<uint32_t>(blk, d->nodes); }
+        __device__ __forceinline__ const int32_t *off() const { return at<int32_t>(blk, d->off); }
+        __device__ __forceinline__ const uint32_t *idx() const { return at<uint32_t>(blk, d->idx); }
+        __device__ __forceinline__ const int32_t *mp() const { return at<int32_t>(blk, d->mp); }
+        __device__ __forceinline__ const float *pos() const { return at<float>(blk, d->pos); }
+        __device__ __forceinline__ const float *K() const { return d->K; }
+        __device__ __forceinline__ const float *T() const { return d->T; }
+        __device__ __forceinline__ const float *Ow() const { return d->Ow; }
+        __device__ __forceinline__ const float *F12() const { return d->F12; }
+        __device__ __forceinline__ const float *ep() const { return d->ep; }
+    };
+    __device__ __forceinline__ KF kf(int i) const { return KF{blk, reinterpret_cast<const KFDev *>(blk) + i}; }
+};
+
+// One key-frame of a resident call: where its block, its row and its positions lie, and the pose by value.
+struct ResKF {
+    int64_t block;                     // byte offset of the CovisFeatRec in the feature arena
+    int32_t mpOff;                     // first entry of the mp row in the row arena
+    uint32_t posOff;                   // first float of its positions in the gather scratch (neighbours)
+    float T[12], Ow[3], F12[9], ep[2];
+    int32_t pad[2];
+};
+static_assert(sizeof(ResKF) == 128, "a pose record");
+
+struct ResidentView {
+    const ResKF *tab; const uint8_t *feat; const int32_t *rows; const float *pos;
+    struct KF {
+        const ResKF *p; const CovisFeatRec *r; const int32_t *row; const float *xyz;
+        template <class T> __device__ __forceinline__ const T *arr(uint32_t o) const { return reinterpret_cast<const T *>(reinterpret_cast<const uint8_t *>(r) + o); }
+        __device__ __forceinline__ int n() const { return r->n; }
+        __device__ __forceinline__ int nn() const { return r->nn; }
+        __device__ __forceinline__ const RumiKeyPoint *keys() const { return arr<RumiKeyPoint>(r->keys); }
+        __device__ __forceinline__ const uint8_t *desc() const { return arr<uint8_t>(r->desc); }
+        __device__ __forceinline__ const float *scale() const { return arr<float>(r->scale); }
+        __device__ __forceinline__ const uint32_t *nodes() const { return arr<uint32_t>(r->nodes); }
+        __device__ __forceinline__ const int32_t *off() const { return arr<int32_t>(r->off); }
+        __device__ __forceinline__ const uint32_t *idx() const { return arr<uint32_t>(r->idx); }
+        __device__ __forceinline__ const int32_t *mp() const { return row; }
+        __device__ __forceinline__ const float *pos() const { return xyz; }
+        __device__ __forceinline__ const float *K() const { return r->K; }
+        __device__ __forceinline__ const float *T() const { return p->T; }
+        __device__ __forceinline__ const float *Ow() const { return p->Ow; }
+        __device__ __forceinline__ const float *F12() const { return p->F12; }
+        __device__ __forceinline__ const float *ep() const { return p->ep; }
+    };
+    __device__ __forceinline__ KF kf(int i) const {
+        const ResKF *p = tab + i;
+        return KF{p, reinterpret_cast<const CovisFeatRec *>(feat + p->block), rows + p->mpOff, pos + p->posOff};
+    }
+};
+
 // ---- 1. search --------------------------------------------------------------------------------------------------------------------------
 // One wavefront per (neighbour, node of the current key-frame's FeatureVector).  Lanes hold the candidates of the neighbour's node (descriptor,
 // key-point, epipole test: loaded once per 64 candidates); the node's current features go by one at a time, wave-uniform, and each is reduced
@@ -43,24 +113,24 @@ template <class T> __device__ __forceinline__ const T *at(const uint8_t *blk, ui
 // (`dist > bestDist` rejects, ORBmatcher.cc:905).  Lane j keeps the running key of the tile's feature j, so nodes of more than 64
 // candidates need no memory between chunks.  A wave rather than half of one: a node at levelsup = 4 holds ~20 features a side, and the
 // cost is the 20 uniform steps, not the idle lanes; two nodes a wave would double the steps' register state for no shorter chain.
-__global__ __launch_bounds__(256) void k_newpts_match(const uint8_t *__restrict__ blk, int coarse, int32_t *__restrict__ cand) {
-    const KFDev *kf = reinterpret_cast<const KFDev *>(blk);
+template <class View> __global__ __launch_bounds__(256) void k_newpts_match(const View view, int coarse, int32_t *__restrict__ cand) {
     const int lane = threadIdx.x & 63;
     const int a = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), k = blockIdx.y;
-    const KFDev &C = kf[0], &N = kf[1 + k];
-    if (a >= C.nn) return;
-    const uint32_t *nodes2 = at<uint32_t>(blk, N.nodes);
-    const uint32_t id = at<uint32_t>(blk, C.nodes)[a];
-    int lo = 0, hi = N.nn;
+    const typename View::KF C = view.kf(0), N = view.kf(1 + k);
+    const int nn1 = C.nn(), nn2 = N.nn(), n1 = C.n();
+    if (a >= nn1) return;
+    const uint32_t *nodes2 = N.nodes();
+    const uint32_t id = C.nodes()[a];
+    int lo = 0, hi = nn2;
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (nodes2[mid] < id) lo = mid + 1; else hi = mid; }
-    if (lo >= N.nn || nodes2[lo] != id) return;
-    const int32_t *off1 = at<int32_t>(blk, C.off), *off2 = at<int32_t>(blk, N.off), *mp1 = at<int32_t>(blk, C.mp), *mp2 = at<int32_t>(blk, N.mp);
-    const uint32_t *idx1 = at<uint32_t>(blk, C.idx), *idx2 = at<uint32_t>(blk, N.idx);
-    const RumiKeyPoint *keys1 = at<RumiKeyPoint>(blk, C.keys), *keys2 = at<RumiKeyPoint>(blk, N.keys);
-    const uint8_t *desc1 = blk + C.desc, *desc2 = blk + N.desc;
-    const float *scale2 = at<float>(blk, N.scale);
-    const float *F = N.F12;
-    const float epx = N.ep[0], epy = N.ep[1];
+    if (lo >= nn2 || nodes2[lo] != id) return;
+    const int32_t *off1 = C.off(), *off2 = N.off(), *mp1 = C.mp(), *mp2 = N.mp();
+    const uint32_t *idx1 = C.idx(), *idx2 = N.idx();
+    const RumiKeyPoint *keys1 = C.keys(), *keys2 = N.keys();
+    const uint8_t *desc1 = C.desc(), *desc2 = N.desc();
+    const float *scale2 = N.scale();
+    const float *F = N.F12();
+    const float epx = N.ep()[0], epy = N.ep()[1];
     const int p0 = off1[a], p1 = off1[a + 1], c0 = off2[lo], c1 = off2[lo + 1];
     for (int pt = p0; pt < p1; pt += 64) {
         uint32_t mine = 0;                                   // running key of feature pt + lane
@@ -102,7 +172,7 @@ __global__ __launch_bounds__(256) void k_newpts_match(const uint8_t *__restrict_
             }
         }
         const int p = pt + lane;
-        if (p < pe && mine != 0) cand[(size_t)k * C.n + idx1[p]] = (int32_t)idx2[0xffff - (~mine & 0xffff)];
+        if (p < pe && mine != 0) cand[(size_t)k * n1 + idx1[p]] = (int32_t)idx2[0xffff - (~mine & 0xffff)];
     }
 }
 
@@ -162,20 +232,20 @@ __device__ __forceinline__ float dot3(float a0, float a1, float a2, float b0, fl
 __device__ __forceinline__ float norm3(float x, float y, float z) { return __builtin_sqrtf((x * x + y * y) + z * z); }
 
 // One lane per (neighbour, feature of the current key-frame) that has a candidate: LocalMapping.cc:506-626 in float, in the reference's order.
-__global__ __launch_bounds__(256) void k_newpts_triangulate(const uint8_t *__restrict__ blk, const int32_t *__restrict__ cand, int farPoints,
+template <class View>
+__global__ __launch_bounds__(256) void k_newpts_triangulate(const View view, const int32_t *__restrict__ cand, int farPoints,
                                                             float thFar, float ratioFactor, uint8_t *__restrict__ gate, float *__restrict__ x3Dout) {
-    const KFDev *kf = reinterpret_cast<const KFDev *>(blk);
-    const KFDev &C = kf[0], &N = kf[1 + blockIdx.y];
-    const int i1 = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i1 >= C.n) return;
-    const size_t slot = (size_t)blockIdx.y * C.n + i1;
+    const typename View::KF C = view.kf(0), N = view.kf(1 + blockIdx.y);
+    const int i1 = blockIdx.x * blockDim.x + threadIdx.x, n1 = C.n();
+    if (i1 >= n1) return;
+    const size_t slot = (size_t)blockIdx.y * n1 + i1;
     const int i2 = cand[slot];
     if (i2 < 0) return;
-    const RumiKeyPoint kp1 = at<RumiKeyPoint>(blk, C.keys)[i1], kp2 = at<RumiKeyPoint>(blk, N.keys)[i2];
-    const float *T1 = C.T, *T2 = N.T;
+    const RumiKeyPoint kp1 = C.keys()[i1], kp2 = N.keys()[i2];
+    const float *T1 = C.T(), *T2 = N.T(), *K1 = C.K(), *K2 = N.K(), *Ow1 = C.Ow(), *Ow2 = N.Ow();
     // :507-512  unprojectEig (Pinhole.cpp:61-64), rays, parallax
-    const float xn1[3] = {(kp1.x - C.K[2]) / C.K[0], (kp1.y - C.K[3]) / C.K[1], 1.f};
-    const float xn2[3] = {(kp2.x - N.K[2]) / N.K[0], (kp2.y - N.K[3]) / N.K[1], 1.f};
+    const float xn1[3] = {(kp1.x - K1[2]) / K1[0], (kp1.y - K1[3]) / K1[1], 1.f};
+    const float xn2[3] = {(kp2.x - K2[2]) / K2[0], (kp2.y - K2[3]) / K2[1], 1.f};
     float ray1[3], ray2[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) {                            // Rwc = Rcw^T
@@ -211,16 +281,16 @@ __global__ __launch_bounds__(256) void k_newpts_triangulate(const uint8_t *__res
         if (z1 <= 0) g = GATE_Z1;
         else if (z2 <= 0) g = GATE_Z2;
         else {
-            const float sf1 = at<float>(blk, C.scale)[kp1.octave], sf2 = at<float>(blk, N.scale)[kp2.octave];
+            const float sf1 = C.scale()[kp1.octave], sf2 = N.scale()[kp2.octave];
             const float sig1 = sf1 * sf1, sig2 = sf2 * sf2;
             const float x1 = dot3(T1[0], T1[1], T1[2], x3D[0], x3D[1], x3D[2]) + T1[3];          // :563-574
             const float y1 = dot3(T1[4], T1[5], T1[6], x3D[0], x3D[1], x3D[2]) + T1[7];
-            const float eX1 = (C.K[0] * x1 / z1 + C.K[2]) - kp1.x, eY1 = (C.K[1] * y1 / z1 + C.K[3]) - kp1.y;
+            const float eX1 = (K1[0] * x1 / z1 + K1[2]) - kp1.x, eY1 = (K1[1] * y1 / z1 + K1[3]) - kp1.y;
             const float x2 = dot3(T2[0], T2[1], T2[2], x3D[0], x3D[1], x3D[2]) + T2[3];          // :588-597
             const float y2 = dot3(T2[4], T2[5], T2[6], x3D[0], x3D[1], x3D[2]) + T2[7];
-            const float eX2 = (N.K[0] * x2 / z2 + N.K[2]) - kp2.x, eY2 = (N.K[1] * y2 / z2 + N.K[3]) - kp2.y;
-            const float dist1 = norm3(x3D[0] - C.Ow[0], x3D[1] - C.Ow[1], x3D[2] - C.Ow[2]);      // :610-626
-            const float dist2 = norm3(x3D[0] - N.Ow[0], x3D[1] - N.Ow[1], x3D[2] - N.Ow[2]);
+            const float eX2 = (K2[0] * x2 / z2 + K2[2]) - kp2.x, eY2 = (K2[1] * y2 / z2 + K2[3]) - kp2.y;
+            const float dist1 = norm3(x3D[0] - Ow1[0], x3D[1] - Ow1[1], x3D[2] - Ow1[2]);          // :610-626
+            const float dist2 = norm3(x3D[0] - Ow2[0], x3D[1] - Ow2[1], x3D[2] - Ow2[2]);
             const float ratioDist = dist2 / dist1, ratioOctave = sf1 / sf2;
             if ((double)(eX1 * eX1 + eY1 * eY1) > 5.991 * (double)sig1) g = GATE_REPROJ1;
             else if ((double)(eX2 * eX2 + eY2 * eY2) > 5.991 * (double)sig2) g = GATE_REPROJ2;
@@ -241,17 +311,16 @@ __global__ __launch_bounds__(256) void k_newpts_triangulate(const uint8_t *__res
 // recomputes the depths tile by tile into LDS (cheaper than a pass through memory and a second launch), each thread ranks one feature, and
 // the one thread that holds the median applies the baseline test.
 constexpr int kDepthTile = 2048;
-__global__ __launch_bounds__(256) void k_newpts_depth(const uint8_t *__restrict__ blk, int32_t *__restrict__ skipped) {
+template <class View> __global__ __launch_bounds__(256) void k_newpts_depth(const View view, int32_t *__restrict__ skipped) {
     __shared__ __attribute__((aligned(16))) float sZ[kDepthTile];
     __shared__ int sCount;
-    const KFDev *kf = reinterpret_cast<const KFDev *>(blk);
-    const KFDev &C = kf[0], &N = kf[1 + blockIdx.y];
-    const int tid = threadIdx.x, n = N.n, i = blockIdx.x * 256 + tid;
+    const typename View::KF C = view.kf(0), N = view.kf(1 + blockIdx.y);
+    const int tid = threadIdx.x, n = N.n(), i = blockIdx.x * 256 + tid;
     if (blockIdx.x > 0 && (int)blockIdx.x * 256 >= n) return;
-    const int32_t *mp = at<int32_t>(blk, N.mp);
-    const float *pos = at<float>(blk, N.pos);
+    const int32_t *mp = N.mp();
+    const float *pos = N.pos(), *T2 = N.T();
     auto depth = [&](int j) {                                 // :964-971, NaN where the feature holds no point
-        return j < n && mp[j] >= 0 ? dot3(N.T[8], N.T[9], N.T[10], pos[3 * j], pos[3 * j + 1], pos[3 * j + 2]) + N.T[11] : __builtin_nanf("");
+        return j < n && mp[j] >= 0 ? dot3(T2[8], T2[9], T2[10], pos[3 * j], pos[3 * j + 1], pos[3 * j + 2]) + T2[11] : __builtin_nanf("");
     };
     if (tid == 0) sCount = 0;
     const float zi = depth(i);
@@ -277,7 +346,8 @@ __global__ __launch_bounds__(256) void k_newpts_depth(const uint8_t *__restrict_
     const bool holder = m > 0 ? (zi == zi && rank == (m - 1) / 2) : (i == 0);
     if (holder) {
         const float median = m > 0 ? zi : -1.0f;
-        const float baseline = norm3(N.Ow[0] - C.Ow[0], N.Ow[1] - C.Ow[1], N.Ow[2] - C.Ow[2]);
+        const float *Ow1 = C.Ow(), *Ow2 = N.Ow();
+        const float baseline = norm3(Ow2[0] - Ow1[0], Ow2[1] - Ow1[1], Ow2[2] - Ow1[2]);
         const float ratio = baseline / median;
         skipped[blockIdx.y] = (double)ratio < 0.01 ? 1 : 0;
     }
@@ -295,16 +365,16 @@ struct NewPtsResult {
 // One workgroup walks the neighbours in order.  Feature i belongs to thread i % 1024 in every pass, so a free flag is only ever touched by
 // its own thread; the histogram uses integer LDS atomics (order-free), the emission is an ordered compaction (ballot, wave totals, running base).
 // matched (may be null: only rumi_hook_newpts_matches passes it) receives stages 1 + 3 per neighbour.
-__global__ __launch_bounds__(1024) void k_newpts_replay(const uint8_t *__restrict__ blk, int nNeigh, int checkOri, const int32_t *__restrict__ cand,
+template <class View>
+__global__ __launch_bounds__(1024) void k_newpts_replay(const View view, int nNeigh, int checkOri, const int32_t *__restrict__ cand,
                                                         const uint8_t *__restrict__ gate, const float *__restrict__ x3D, NewPtsResult *__restrict__ res,
                                                         int32_t *__restrict__ matched) {
     __shared__ uint8_t sFree[kMaxCur];
     __shared__ int sHist[RUMI_HISTO_LENGTH], sKeep[RUMI_HISTO_LENGTH], sWave[16], sBase;
-    const KFDev *kf = reinterpret_cast<const KFDev *>(blk);
-    const KFDev &C = kf[0];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), n1 = C.n;
-    const RumiKeyPoint *keys1 = at<RumiKeyPoint>(blk, C.keys);
-    const int32_t *mp1 = at<int32_t>(blk, C.mp);
+    const typename View::KF C = view.kf(0);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), n1 = C.n();
+    const RumiKeyPoint *keys1 = C.keys();
+    const int32_t *mp1 = C.mp();
     for (int i = tid; i < n1; i += 1024) sFree[i] = mp1[i] < 0;
     if (tid == 0) sBase = 0;
     __syncthreads();
@@ -317,7 +387,7 @@ __global__ __launch_bounds__(1024) void k_newpts_replay(const uint8_t *__restric
             if (tid == 0) res->perNeigh[k] = 0;
             continue;
         }
-        const RumiKeyPoint *keys2 = at<RumiKeyPoint>(blk, kf[1 + k].keys);
+        const RumiKeyPoint *keys2 = view.kf(1 + k).keys();
         if (tid < RUMI_HISTO_LENGTH) { sHist[tid] = 0; sKeep[tid] = 1; }
         __syncthreads();
         if (checkOri) {                                      // ORBmatcher.cc:964-1001 over the pairs the sequential search finds
@@ -372,36 +442,41 @@ __global__ __launch_bounds__(1024) void k_newpts_replay(const uint8_t *__restric
     if (tid == 0) res->nOut = sBase;
 }
 
+// ---- 0. the resident entry's gather -----------------------------------------------------------------------------------------------------
+// One lane per (neighbour, feature): the feature's entry in the neighbour's mp row, and where it names a point, the 12 position bytes of the
+// point's 64-byte attribute record (covis.hip) into pos[posOff + 3 i]: what the block entry gets as mp_pos.  An entry whose point has no
+// attributes is counted (integer atomic; the order does not matter) and the host refuses the call.  The current key-frame's positions
+// are not read, as with mp_pos == NULL.
+__global__ __launch_bounds__(256) void k_newpts_gather(const ResKF *__restrict__ tab, const uint8_t *__restrict__ feat, const int32_t *__restrict__ rows,
+                                                       const int32_t *__restrict__ pt, const int32_t *__restrict__ attr, int32_t *__restrict__ pos,
+                                                       int32_t *__restrict__ missing) {
+    const ResKF &N = tab[1 + blockIdx.y];
+    const int n = reinterpret_cast<const CovisFeatRec *>(feat + N.block)->n, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int p = rows[N.mpOff + i];
+    if (p < 0) return;
+    if (!attr || !pt[(size_t)p * kCovisPointWords + 3]) { atomicAdd(missing, 1); return; }
+    const int32_t *A = attr + (size_t)p * kCovisAttrWords;
+    int32_t *o = pos + N.posOff + 3 * (size_t)i;
+    o[0] = A[0]; o[1] = A[1]; o[2] = A[2];
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
 struct NewPtsState {
     MirrorBuf<uint8_t> blk, res;                             // the upload block; the result block, a NewPtsResult and its points
     DevBuf<int32_t> cand, matched; DevBuf<uint8_t> gate; DevBuf<float> x3D;      // a candidate, a gate and a point (three floats) per (neighbour, feature) pair
-    int lastNeigh = 0, lastN1 = 0, lastOri = 0;              // the last call, whose device state rumi_hook_newpts_matches replays
+    MirrorBuf<uint8_t> tab; DevBuf<int32_t> pos;             // the resident entry: its table of ResKF, the gathered positions
+    int lastNeigh = 0, lastN1 = 0, lastOri = 0;              // the last block call, whose device state rumi_hook_newpts_matches replays
+    StageClock clock;
+    float stageMs[3] = {0.f, 0.f, 0.f};
 };
 
 static void newpts_destroy(void *p) { delete static_cast<NewPtsState *>(p); }     // rumi_match_destroy has made the matcher's device current
 
 static bool kf_valid(const RumiNewPointsKF &k, bool neighbour, const char **why) {
-    const RumiFrameFeatures &f = k.feat;
-    const RumiFeatureVector &v = k.fv;
-    *why = "RumiNewPointsKF: bad sizes or missing arrays";
-    if (f.n < 0 || f.nlevels < 1 || f.nlevels > 64 || !f.scale_factors || v.n_nodes < 0) return false;
-    if (f.n > 0 && (!f.keys_un || !f.desc || !k.kf_mp)) return false;
-    if (v.n_nodes > 0 && (!v.node_ids || !v.offsets || !v.indices)) return false;
-    if (neighbour && f.n > 0 && !k.mp_pos) return false;
-    *why = "RumiNewPointsKF: key-point octave outside mvScaleFactors";
-    for (int i = 0; i < f.n; i++) if (f.keys_un[i].octave < 0 || f.keys_un[i].octave >= f.nlevels) return false;
-    *why = "RumiNewPointsKF: FeatureVector offsets or indices out of range";
-    if (v.n_nodes > 0) {
-        if (v.offsets[0] != 0) return false;
-        for (int a = 0; a < v.n_nodes; a++) if (v.offsets[a + 1] < v.offsets[a]) return false;
-        for (int p = 0; p < v.offsets[v.n_nodes]; p++) if (v.indices[p] >= (uint32_t)f.n) return false;
-        *why = "RumiNewPointsKF: FeatureVector node ids not strictly ascending, or a feature listed twice";
-        for (int a = 1; a < v.n_nodes; a++) if (v.node_ids[a] <= v.node_ids[a - 1]) return false;      // the kernels search the ids by bisection
-        std::vector<uint8_t> seen((size_t)f.n, 0);                                                      // one writer per cand[k][i1]
-        for (int p = 0; p < v.offsets[v.n_nodes]; p++) { if (seen[v.indices[p]]) return false; seen[v.indices[p]] = 1; }
-    }
-    return true;
+    *why = "key-frame features: bad sizes or missing arrays";
+    if (k.feat.n > 0 && (!k.kf_mp || (neighbour && !k.mp_pos))) return false;
+    return keyframe_features_valid(k.feat, k.fv, why);
 }
 
 static size_t kf_bytes(const RumiNewPointsKF &k) {
@@ -433,6 +508,51 @@ static void kf_pack(const RumiNewPointsKF &k, bool neighbour, uint8_t *blk, size
     d->pad[0] = d->pad[1] = 0;
 }
 
+// ---- what both entries share behind their uploads
+static int newpts_reserve(NewPtsState *s, int n_neigh, int n1) {
+    const size_t pairs = (size_t)n_neigh * std::max(n1, 1), resBytes = sizeof(NewPtsResult) + (size_t)n1 * sizeof(RumiNewPoint);
+    int rc;
+    if ((rc = s->cand.reserve(pairs, pairs)) != RUMI_OK || (rc = s->gate.reserve(pairs, pairs)) != RUMI_OK ||
+        (rc = s->x3D.reserve(pairs * 3, pairs * 3)) != RUMI_OK || (rc = s->res.reserve(resBytes, resBytes)) != RUMI_OK)
+        return rc;
+    return RUMI_OK;
+}
+
+// The four launches over `view` and the result block back into s->res.h.  The block entry clears the result block's header here; the
+// resident entry has cleared it before its gather, which counts into it.
+template <class View> static int newpts_run(NewPtsState *s, const View &view, int n_neigh, int n1, int nNodes1, int maxN2, const RumiNewPointsParams *p) {
+    const size_t pairs = (size_t)n_neigh * std::max(n1, 1), resBytes = sizeof(NewPtsResult) + (size_t)n1 * sizeof(RumiNewPoint);
+    NewPtsResult *dRes = reinterpret_cast<NewPtsResult *>(s->res.d);
+    HIP_TRY(hipMemsetAsync(s->cand.p, 0xFF, pairs * 4, nullptr));
+    if (std::is_same<View, BlockView>::value) HIP_TRY(hipMemsetAsync(dRes, 0, sizeof(NewPtsResult), nullptr));
+    hipLaunchKernelGGL(k_newpts_depth<View>, dim3((maxN2 + 255) / 256, n_neigh), dim3(256), 0, nullptr, view, dRes->skipped);
+    if (n1 > 0) {
+        if (nNodes1 > 0)
+            hipLaunchKernelGGL(k_newpts_match<View>, dim3((nNodes1 + 3) / 4, n_neigh), dim3(256), 0, nullptr, view, p->coarse, s->cand.p);
+        hipLaunchKernelGGL(k_newpts_triangulate<View>, dim3((n1 + 255) / 256, n_neigh), dim3(256), 0, nullptr, view, s->cand.p, p->far_points,
+                           p->th_far_points, p->ratio_factor, s->gate.p, s->x3D.p);
+    }
+    hipLaunchKernelGGL(k_newpts_replay<View>, dim3(1), dim3(1024), 0, nullptr, view, n_neigh, p->check_orientation, s->cand.p, s->gate.p, s->x3D.p,
+                       dRes, (int32_t *)nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(s->res.h, dRes, resBytes, hipMemcpyDeviceToHost));      // one block back
+    s->clock.mark();
+    return RUMI_OK;
+}
+
+static int newpts_write_out(NewPtsState *s, int n_neigh, RumiNewPoint *out, int32_t cap, int32_t *n_out, int32_t *per_neigh_out, uint8_t *neigh_skipped_out) {
+    const NewPtsResult *r = reinterpret_cast<const NewPtsResult *>(s->res.h);
+    *n_out = r->nOut;
+    for (int k = 0; k < n_neigh; k++) { per_neigh_out[k] = r->perNeigh[k]; neigh_skipped_out[k] = (uint8_t)r->skipped[k]; }
+    if (std::min(r->nOut, cap) > 0) std::memcpy(out, r->pts, (size_t)std::min(r->nOut, cap) * sizeof(RumiNewPoint));
+    s->clock.finish(s->stageMs);
+    if (r->nOut > cap) {
+        g_lastError = "CreateNewMapPoints: more points than the output list holds (cap)";
+        return RUMI_E_CAPACITY;
+    }
+    return RUMI_OK;
+}
+
 }  // namespace rumi
 
 using namespace rumi;
@@ -445,6 +565,7 @@ extern "C" int rumi_create_new_map_points(RumiMatcher *m, const RumiNewPointsKF 
         g_lastError = "rumi_create_new_map_points: missing argument, or n_neigh outside 0..RUMI_NEWPTS_MAX_NEIGH";
         return RUMI_E_INVALID;
     }
+    const auto t0 = std::chrono::steady_clock::now();
     const char *why = "";
     if (!kf_valid(*cur, false, &why)) { g_lastError = why; return RUMI_E_INVALID; }
     for (int k = 0; k < n_neigh; k++) if (!kf_valid(neigh[k], true, &why)) { g_lastError = why; return RUMI_E_INVALID; }
@@ -469,51 +590,101 @@ extern "C" int rumi_create_new_map_points(RumiMatcher *m, const RumiNewPointsKF 
     if (!ext->state) { ext->state = new NewPtsState(); ext->destroy = newpts_destroy; }
     NewPtsState *s = static_cast<NewPtsState *>(ext->state);
     s->lastNeigh = 0; s->lastN1 = 0;
+    s->clock.start(); s->clock.t[0] = t0;                    // the validation above belongs to the host stage
 
     // ---- arenas (grown on demand, like the BoW batch blocks of the matcher)
     size_t blkBytes = (size_t)(n_neigh + 1) * sizeof(KFDev) + kf_bytes(*cur);
     for (int k = 0; k < n_neigh; k++) blkBytes += kf_bytes(neigh[k]);
     int rc;
-    const size_t pairs = (size_t)n_neigh * std::max(n1, 1);
-    const size_t resBytes = sizeof(NewPtsResult) + (size_t)n1 * sizeof(RumiNewPoint);
-    if ((rc = s->blk.reserve(blkBytes, blkBytes + blkBytes / 4)) != RUMI_OK || (rc = s->cand.reserve(pairs, pairs)) != RUMI_OK ||
-        (rc = s->gate.reserve(pairs, pairs)) != RUMI_OK || (rc = s->x3D.reserve(pairs * 3, pairs * 3)) != RUMI_OK ||
-        (rc = s->res.reserve(resBytes, resBytes)) != RUMI_OK)
-        return rc;
-    NewPtsResult *dRes = reinterpret_cast<NewPtsResult *>(s->res.d);
+    if ((rc = s->blk.reserve(blkBytes, blkBytes + blkBytes / 4)) != RUMI_OK || (rc = newpts_reserve(s, n_neigh, n1)) != RUMI_OK) return rc;
 
     // ---- one block up
     size_t used = (size_t)(n_neigh + 1) * sizeof(KFDev);
     KFDev *tab = reinterpret_cast<KFDev *>(s->blk.h);
     kf_pack(*cur, false, s->blk.h, &used, &tab[0]);
     for (int k = 0; k < n_neigh; k++) kf_pack(neigh[k], true, s->blk.h, &used, &tab[1 + k]);
+    s->clock.mark();
     HIP_TRY(hipMemcpyAsync(s->blk.d, s->blk.h, used, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemsetAsync(s->cand.p, 0xFF, pairs * 4, nullptr));
-    HIP_TRY(hipMemsetAsync(dRes, 0, sizeof(NewPtsResult), nullptr));
-
-    // ---- four launches
-    hipLaunchKernelGGL(k_newpts_depth, dim3((maxN2 + 255) / 256, n_neigh), dim3(256), 0, nullptr, s->blk.d, dRes->skipped);
-    if (n1 > 0) {
-        if (cur->fv.n_nodes > 0)
-            hipLaunchKernelGGL(k_newpts_match, dim3((cur->fv.n_nodes + 3) / 4, n_neigh), dim3(256), 0, nullptr, s->blk.d, p->coarse, s->cand.p);
-        hipLaunchKernelGGL(k_newpts_triangulate, dim3((n1 + 255) / 256, n_neigh), dim3(256), 0, nullptr, s->blk.d, s->cand.p, p->far_points,
-                           p->th_far_points, p->ratio_factor, s->gate.p, s->x3D.p);
-    }
-    hipLaunchKernelGGL(k_newpts_replay, dim3(1), dim3(1024), 0, nullptr, s->blk.d, n_neigh, p->check_orientation, s->cand.p, s->gate.p, s->x3D.p,
-                       dRes, (int32_t *)nullptr);
-    HIP_TRY(hipGetLastError());
-
-    // ---- one block back
-    HIP_TRY(hipMemcpy(s->res.h, dRes, resBytes, hipMemcpyDeviceToHost));
+    if ((rc = newpts_run(s, BlockView{s->blk.d}, n_neigh, n1, cur->fv.n_nodes, maxN2, p)) != RUMI_OK) return rc;
     s->lastNeigh = n_neigh; s->lastN1 = n1; s->lastOri = p->check_orientation;
-    const NewPtsResult *r = reinterpret_cast<const NewPtsResult *>(s->res.h);
-    *n_out = r->nOut;
-    for (int k = 0; k < n_neigh; k++) { per_neigh_out[k] = r->perNeigh[k]; neigh_skipped_out[k] = (uint8_t)r->skipped[k]; }
-    if (std::min(r->nOut, cap) > 0) std::memcpy(out, r->pts, (size_t)std::min(r->nOut, cap) * sizeof(RumiNewPoint));
-    if (r->nOut > cap) {
-        g_lastError = "CreateNewMapPoints: more points than the output list holds (cap)";
+    return newpts_write_out(s, n_neigh, out, cap, n_out, per_neigh_out, neigh_skipped_out);
+}
+
+extern "C" int rumi_create_new_map_points_resident(RumiMatcher *m, RumiCovis *c, int32_t cur_slot, const RumiNewPointsPose *cur_pose,
+                                                   const int32_t *neigh_slots, const RumiNewPointsPose *neigh_pose, int32_t n_neigh,
+                                                   const RumiNewPointsParams *p, RumiNewPoint *out, int32_t cap, int32_t *n_out,
+                                                   int32_t *per_neigh_out, uint8_t *neigh_skipped_out) {
+    static const char *entry = "rumi_create_new_map_points_resident";
+    if (!m || !c || !cur_pose || !p || !n_out || n_neigh < 0 || n_neigh > RUMI_NEWPTS_MAX_NEIGH || cap < 0 || (cap > 0 && !out) ||
+        (n_neigh > 0 && (!neigh_slots || !neigh_pose || !per_neigh_out || !neigh_skipped_out))) {
+        g_lastError = std::string(entry) + ": missing argument, or n_neigh outside 0..RUMI_NEWPTS_MAX_NEIGH";
+        return RUMI_E_INVALID;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    int32_t slots[RUMI_NEWPTS_MAX_NEIGH + 1];
+    CovisSlotFeatures info[RUMI_NEWPTS_MAX_NEIGH + 1];
+    slots[0] = cur_slot;
+    for (int k = 0; k < n_neigh; k++) slots[1 + k] = neigh_slots[k];
+    int rc;
+    if ((rc = covis_features_check(c, n_neigh + 1, slots, n_neigh > 0 ? m->device : -1, entry, info)) != RUMI_OK) return rc;
+    const int lim = std::min(m->maxFeat, m->maxQ), n1 = info[0].n;
+    bool fits = n1 <= std::min(lim, kMaxCur) && info[0].ne <= lim && info[0].nn <= lim;
+    int maxN2 = 1;
+    size_t posFloats = 0;
+    for (int k = 1; k <= n_neigh; k++) {
+        fits = fits && info[k].n <= m->maxFeat && info[k].ne <= m->maxFeat && info[k].nn <= m->maxFeat;
+        maxN2 = std::max(maxN2, info[k].n);
+        posFloats += 3 * (size_t)info[k].n;
+    }
+    if (!fits) {
+        g_lastError = "CreateNewMapPoints: a key-frame exceeds the matcher's capacities (max_features / max_queries)";
         return RUMI_E_CAPACITY;
     }
+    if (n_neigh == 0) { *n_out = 0; return RUMI_OK; }
+    HIP_TRY(hipSetDevice(m->device));
+    MatcherExt *ext = &m->ext;
+    if (!ext->state) { ext->state = new NewPtsState(); ext->destroy = newpts_destroy; }
+    NewPtsState *s = static_cast<NewPtsState *>(ext->state);
+    s->lastNeigh = 0; s->lastN1 = 0;                         // the hook replays the block path's state, which this call overwrites
+    s->clock.start(); s->clock.t[0] = t0;
+
+    const size_t tabBytes = (size_t)(n_neigh + 1) * sizeof(ResKF);
+    if ((rc = s->tab.reserve(tabBytes, (RUMI_NEWPTS_MAX_NEIGH + 1) * sizeof(ResKF))) != RUMI_OK ||
+        (rc = s->pos.reserve(posFloats, posFloats + posFloats / 4)) != RUMI_OK || (rc = newpts_reserve(s, n_neigh, n1)) != RUMI_OK)
+        return rc;
+    // ---- the table of poses: all that travels for this call, besides what the store had staged
+    ResKF *tab = reinterpret_cast<ResKF *>(s->tab.h);
+    uint32_t posOff = 0;
+    for (int k = 0; k <= n_neigh; k++) {
+        const RumiNewPointsPose &P = k ? neigh_pose[k - 1] : *cur_pose;
+        ResKF &R = tab[k];
+        R.block = info[k].block; R.mpOff = info[k].mpOff; R.posOff = k ? posOff : 0;
+        std::memcpy(R.T, P.Tcw, 48); std::memcpy(R.Ow, P.Ow, 12); std::memcpy(R.F12, P.F12, 36); std::memcpy(R.ep, P.epipole2, 8);
+        R.pad[0] = R.pad[1] = 0;
+        if (k) posOff += 3u * (uint32_t)info[k].n;
+    }
+    s->clock.mark();
+    CovisFeatureView fv;
+    if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(s->tab.d, s->tab.h, tabBytes, hipMemcpyHostToDevice, nullptr));
+    NewPtsResult *dRes = reinterpret_cast<NewPtsResult *>(s->res.d);
+    HIP_TRY(hipMemsetAsync(dRes, 0, sizeof(NewPtsResult), nullptr));
+    const ResKF *dTab = reinterpret_cast<const ResKF *>(s->tab.d);
+    hipLaunchKernelGGL(k_newpts_gather, dim3((maxN2 + 255) / 256, n_neigh), dim3(256), 0, nullptr, dTab, fv.feat, fv.rows, fv.pt, fv.attr, s->pos.p,
+                       &dRes->pad[0]);
+    if ((rc = newpts_run(s, ResidentView{dTab, fv.feat, fv.rows, reinterpret_cast<const float *>(s->pos.p)}, n_neigh, n1, info[0].nn, maxN2, p)) != RUMI_OK)
+        return rc;
+    const int missing = reinterpret_cast<const NewPtsResult *>(s->res.h)->pad[0];
+    if (missing) {
+        g_lastError = std::string(entry) + ": " + std::to_string(missing) + " neighbour map point(s) without attributes (rumi_covis_set_point_attributes)";
+        return RUMI_E_INVALID;
+    }
+    return newpts_write_out(s, n_neigh, out, cap, n_out, per_neigh_out, neigh_skipped_out);
+}
+
+extern "C" int rumi_newpts_stage_ms(const RumiMatcher *m, float *out3) {
+    if (!m || !out3 || !m->ext.state) { g_lastError = "rumi_newpts_stage_ms: no CreateNewMapPoints call precedes on this matcher"; return RUMI_E_INVALID; }
+    std::memcpy(out3, static_cast<const NewPtsState *>(m->ext.state)->stageMs, 12);
     return RUMI_OK;
 }
 
@@ -530,7 +701,7 @@ extern "C" int rumi_hook_newpts_matches(RumiMatcher *m, int32_t n_neigh, int32_t
     const size_t pairs = (size_t)n_neigh * n1;
     const int rc = s->matched.reserve(pairs, pairs);
     if (rc != RUMI_OK) return rc;
-    hipLaunchKernelGGL(k_newpts_replay, dim3(1), dim3(1024), 0, nullptr, s->blk.d, n_neigh, s->lastOri, s->cand.p, s->gate.p, s->x3D.p, reinterpret_cast<NewPtsResult *>(s->res.d), s->matched.p);
+    hipLaunchKernelGGL(k_newpts_replay<BlockView>, dim3(1), dim3(1024), 0, nullptr, BlockView{s->blk.d}, n_neigh, s->lastOri, s->cand.p, s->gate.p, s->x3D.p, reinterpret_cast<NewPtsResult *>(s->res.d), s->matched.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(matches, s->matched.p, pairs * 4, hipMemcpyDeviceToHost));
     return RUMI_OK;

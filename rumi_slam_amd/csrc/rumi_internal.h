@@ -34,6 +34,28 @@ int covis_local_map_launch(RumiCovis *c, int n, const int32_t *frame_points, con
 // Both headers, the frame's bad flags [nFrame] and the local key-frames, as host pointers into the store's pinned block (synchronises).
 int covis_local_map_read(RumiCovis *c, const CovisLocalView &v, const int32_t **head8, const uint8_t **frameBad, const int32_t **localKf);
 
+// ---- the store's key-frame features (covis_features.inc) as rumi_create_new_map_points_resident reads them (mapping.hip) ----
+// A key-frame's block in the feature arena starts with this record; every array lies `its field` bytes behind the record's own address,
+// 16-byte aligned: RumiKeyPoint keys [n], desc [n][32], scale [nlevels], then mFeatVec as node ids [nn], offsets [nn + 1], indices [ne].
+struct CovisFeatRec {
+    int32_t n, nn, ne, nlevels;
+    float K[4];                        // fx fy cx cy
+    uint32_t keys, desc, scale, nodes, off, idx;
+    uint32_t bytes, pad;               // of the whole block, record included
+};
+static_assert(sizeof(CovisFeatRec) == 64, "the arrays behind the record start 16-byte aligned");
+// What the host knows of a slot without asking the device.
+struct CovisSlotFeatures { int32_t n, nn, ne, mpOff, mpLen; int64_t block; };     // mp row in the row arena (entries); block in the feature arena (bytes)
+struct CovisFeatureView {
+    const int32_t *rows, *pt, *attr;   // the row arena, [max_points][kCovisPointWords], [max_points][kCovisAttrWords] (null: no point has attributes)
+    const uint8_t *feat;               // the feature arena
+};
+// Host only: every slot live, with features, named once, feature count == length of its mp row; with wantDevice >= 0 the store on that
+// device (a store without a device yet takes it).  Refused with RUMI_E_INVALID and the message set.
+int covis_features_check(RumiCovis *c, int n, const int32_t *slots, int wantDevice, const char *entry, CovisSlotFeatures *info);
+// Sends the staged edits and the staged features; where the tables lie afterwards.  Enqueues on the null stream, does not synchronise.
+int covis_features_flush(RumiCovis *c, CovisFeatureView *view);
+
 // Correspondences the LDS instantiation of k_pose_opt holds (opt.hip).  The tracker (track.hip) launches ONLY that instantiation when it knows a
 // frame cannot have more (nfeatures 1000 + the extractor's slack of 96 fits), so both files take the number from here.
 constexpr int kPoseLdsEdges = 1152;

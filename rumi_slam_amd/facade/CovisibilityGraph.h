@@ -80,6 +80,47 @@ template <class KeyFrameT, class MapPointT> class CovisibilityGraph {
         return SyncAttributes(std::vector<MapPointT *>(dirty_.begin(), dirty_.end()));
     }
 
+    // ---- the key-frame's constant part (mvKeysUn, mDescriptors, mvScaleFactors, mFeatVec, fx fy cx cy): rumi_covis_set_keyframe_features.
+    // SyncFeatures is called once, where the key-frame enters the graph (after ComputeBoW: mFeatVec must be final); DropFeatures from
+    // KeyFrame::SetBadFlag.  rumi::LocalMappingStep::CreateNewMapPointsResident then names slots instead of uploading key-frames.
+    int SyncFeatures(KeyFrameT *pKF) {
+        if (!h_ || !pKF) return RUMI_E_INVALID;
+        int rc;
+        if (!slot_.count(pKF) && (rc = sync_keyframes(std::vector<KeyFrameT *>{pKF})) != RUMI_OK) return rc;
+        RumiFrameFeatures f;
+        f.n = pKF->N;
+        f.keys_un = reinterpret_cast<const RumiKeyPoint *>(pKF->mvKeysUn.data());
+        f.desc = pKF->mDescriptors.ptr(0);
+        f.min_x = pKF->mnMinX; f.min_y = pKF->mnMinY; f.max_x = pKF->mnMaxX; f.max_y = pKF->mnMaxY;
+        f.scale_factors = pKF->mvScaleFactors.data();
+        f.nlevels = (int32_t)pKF->mvScaleFactors.size();
+        std::vector<uint32_t> nodes, idx;
+        std::vector<int32_t> off{0};
+        for (const auto &kv : pKF->mFeatVec) {                                           // std::map order: node ids ascending
+            nodes.push_back((uint32_t)kv.first);
+            for (unsigned i : kv.second) idx.push_back(i);
+            off.push_back((int32_t)idx.size());
+        }
+        const RumiFeatureVector fv{(int32_t)nodes.size(), nodes.data(), off.data(), idx.data()};
+        const float K4[4] = {pKF->fx, pKF->fy, pKF->cx, pKF->cy};
+        rc = rumi_covis_set_keyframe_features(h_, slot_[pKF], &f, &fv, K4);
+        if (rc != RUMI_OK) { rumi_facade::report("CovisibilityGraph::SyncFeatures", rc); return rc; }
+        featured_.insert(pKF);
+        return RUMI_OK;
+    }
+    int DropFeatures(KeyFrameT *pKF) {
+        auto it = slot_.find(pKF);
+        if (!h_ || it == slot_.end()) return RUMI_OK;                                    // never seen: nothing to drop
+        const int32_t s = it->second;
+        const int rc = rumi_covis_drop_keyframe_features(h_, 1, &s);
+        if (rc != RUMI_OK) rumi_facade::report("CovisibilityGraph::DropFeatures", rc);
+        featured_.erase(pKF);
+        return rc;
+    }
+    bool HasFeatures(KeyFrameT *pKF) const { return featured_.count(pKF) > 0; }
+    // the slot of a key-frame the store has seen, else -1
+    int SlotOf(KeyFrameT *pKF) const { auto it = slot_.find(pKF); return it == slot_.end() ? -1 : it->second; }
+
     // ---- for the callers that drive the store themselves (TrackingStep.h): the handle, and objects <-> slots and ids
     RumiCovis *handle() const { return h_; }
     int KeyFrameCount() const { return (int)kfs_.size(); }
@@ -198,6 +239,7 @@ template <class KeyFrameT, class MapPointT> class CovisibilityGraph {
     std::vector<KeyFrameT *> kfs_;
     std::vector<MapPointT *> pts_;
     std::set<MapPointT *> dirty_;
+    std::set<KeyFrameT *> featured_;                                                     // key-frames whose features the store holds
 
     int32_t slot_of(KeyFrameT *k, std::vector<KeyFrameT *> &work) {                      // a key-frame the store has not seen joins the call
         auto it = slot_.find(k);

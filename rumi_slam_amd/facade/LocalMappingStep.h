@@ -88,30 +88,82 @@ public:
                          rumi_create_new_map_points(arena(), &kf[0], &kf[1], nn, &prm, pts.data(), (int32_t)pts.size(), &nOut, per.data(),
                                                     skipped.data())) != RUMI_OK)
             return -1;
-        // :628-644 for every returned point, in the returned order, neighbour by neighbour
-        int created = 0, next = 0;
-        for (int i = 0; i < nn; i++) {
-            if (i > 0 && CheckNewKeyFrames()) return created;                   // :398-399
-            KeyFrameT *pKF2 = vpNeighKFs[i];
-            for (int j = 0; j < per[i]; j++, next++) {
-                const RumiNewPoint &P = pts[next];
-                const Eigen::Vector3f x3D(P.x3D[0], P.x3D[1], P.x3D[2]);
-                MapPointT *pMP = new MapPointT(x3D, pCurrentKF, pAtlas->GetCurrentMap());
-                pMP->AddObservation(pCurrentKF, P.idx1);
-                pMP->AddObservation(pKF2, P.idx2);
-                pCurrentKF->AddMapPoint(pMP, P.idx1);
-                pKF2->AddMapPoint(pMP, P.idx2);
-                if (deferRefresh) deferRefresh->push_back(pMP);
-                else {
-                    pMP->ComputeDistinctiveDescriptors();
-                    pMP->UpdateNormalAndDepth();
-                }
-                pAtlas->AddMapPoint(pMP);
-                mlpRecentAddedMapPoints.push_back(pMP);
-                created++;
-            }
+        return replay<MapPointT>(pCurrentKF, vpNeighKFs, pAtlas, mlpRecentAddedMapPoints, CheckNewKeyFrames, pts, per, deferRefresh, nullptr);
+    }
+
+    // The same member over key-frames resident in a CovisibilityGraph (CovisibilityGraph.h): every key-frame's features were staged once by
+    // graph.SyncFeatures, its map-point row and the points' positions are what graph.Sync / MarkDirty keep current, so only the poses travel
+    // (rumi_create_new_map_points_resident).  FlushDirty() runs first.  A key-frame without resident features is refused with a report -- it
+    // is not uploaded behind the caller's back.  The host replay is CreateNewMapPoints'; afterwards the touched key-frames and the created
+    // points are staged again (Sync, MarkDirty), so the graph is current when the member returns.  `created`: as deferRefresh above.
+    template <class MapPointT, class GraphT, class KeyFrameT, class AtlasT, class RecentListT, class CheckFn>
+    int CreateNewMapPointsResident(GraphT &graph, KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpNeighKFs, AtlasT *pAtlas,
+                                   RecentListT &mlpRecentAddedMapPoints, bool bFarPoints, float thFarPoints, CheckFn CheckNewKeyFrames,
+                                   bool bCoarse = false, std::vector<MapPointT *> *created = nullptr) {
+        static const char *where = "LocalMappingStep::CreateNewMapPointsResident";
+        const int nn = (int)vpNeighKFs.size();
+        if (nn == 0) return 0;
+        if (nn > RUMI_NEWPTS_MAX_NEIGH) {
+            rumi_facade::report(where, RUMI_E_INVALID, "more neighbours than RUMI_NEWPTS_MAX_NEIGH; no point was created");
+            return -1;
         }
-        return created;
+        if (!graph.ok()) { rumi_facade::report(where, RUMI_E_INVALID, "no store; no point was created"); return -1; }
+        std::vector<int32_t> slots(nn);
+        for (int k = -1; k < nn; k++) {
+            KeyFrameT *pKF = k < 0 ? pCurrentKF : vpNeighKFs[k];
+            if (has_stereo(pKF)) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a key-frame has stereo key-points (mvuRight >= 0): only the monocular branch is built; no point was created");
+                return -1;
+            }
+            if (!graph.HasFeatures(pKF)) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a key-frame without resident features (CovisibilityGraph::SyncFeatures was never called for it); no point was created");
+                return -1;
+            }
+            if (k >= 0) slots[k] = graph.SlotOf(pKF);
+        }
+        if (graph.FlushDirty() != RUMI_OK) return -1;
+        std::vector<RumiNewPointsPose> pose(nn + 1);
+        pose_of(pCurrentKF, pose[0]);
+        const Sophus::SE3f T1w = pCurrentKF->GetPose();
+        const Eigen::Vector3f Cw = pCurrentKF->GetCameraCenter();
+        const Eigen::Matrix3f K1 = pCurrentKF->mpCamera->toK_();
+        for (int k = 0; k < nn; k++) {                                          // F12 and the epipole: the expressions of CreateNewMapPoints above
+            KeyFrameT *pKF2 = vpNeighKFs[k];
+            pose_of(pKF2, pose[1 + k]);
+            const Sophus::SE3f T2w = pKF2->GetPose(), Tw2 = pKF2->GetPoseInverse();
+            const Eigen::Vector3f C2 = T2w * Cw;
+            const Eigen::Vector2f ep = pKF2->mpCamera->project(C2);
+            const Sophus::SE3f T12 = T1w * Tw2;
+            const Eigen::Matrix3f R12 = T12.rotationMatrix();
+            const Eigen::Vector3f t12 = T12.translation();
+            const Eigen::Matrix3f t12x = Sophus::SO3f::hat(t12);
+            const Eigen::Matrix3f K2 = pKF2->mpCamera->toK_();
+            const Eigen::Matrix3f F12 = K1.transpose().inverse() * t12x * R12 * K2.inverse();
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) pose[1 + k].F12[r * 3 + c] = F12(r, c);
+            pose[1 + k].epipole2[0] = ep(0); pose[1 + k].epipole2[1] = ep(1);
+        }
+        RumiNewPointsParams prm;
+        prm.coarse = bCoarse; prm.check_orientation = mbCheckOrientation; prm.far_points = bFarPoints; prm.th_far_points = thFarPoints;
+        prm.ratio_factor = 1.5f * pCurrentKF->mfScaleFactor;                    // :391
+        std::vector<RumiNewPoint> pts((size_t)(pCurrentKF->N > 0 ? pCurrentKF->N : 1));
+        std::vector<int32_t> per(nn);
+        std::vector<uint8_t> skipped(nn);
+        int32_t nOut = 0;
+        if (RUMI_GUARDED("LocalMappingStep / rumi_create_new_map_points_resident", &ORBmatcher::grow_arena,
+                         rumi_create_new_map_points_resident(arena(), graph.handle(), graph.SlotOf(pCurrentKF), &pose[0], slots.data(), &pose[1], nn, &prm,
+                                                             pts.data(), (int32_t)pts.size(), &nOut, per.data(), skipped.data())) != RUMI_OK)
+            return -1;
+        std::vector<MapPointT *> made;
+        const int n = replay<MapPointT>(pCurrentKF, vpNeighKFs, pAtlas, mlpRecentAddedMapPoints, CheckNewKeyFrames, pts, per, created, &made);
+        if (!made.empty()) {                                                    // rows of the touched key-frames, observers and attributes of the new points
+            std::vector<KeyFrameT *> touched{pCurrentKF};
+            for (MapPointT *p : made) graph.MarkDirty(p);
+            for (int i = 0, next = 0; i < nn && next < (int)made.size(); next += per[i++])
+                if (per[i] > 0) touched.push_back(vpNeighKFs[i]);
+            for (KeyFrameT *k : touched)
+                if (graph.Sync(k) != RUMI_OK) break;
+        }
+        return n;
     }
 #endif  // RUMI_HAVE_SOPHUS
 
@@ -241,6 +293,47 @@ protected:
 
 #ifdef RUMI_HAVE_SOPHUS
     struct Marshalled { Csr fv; std::vector<int32_t> mp; std::vector<float> pos; };
+
+    // :628-644 for every returned point, in the returned order, neighbour by neighbour; stops where CheckNewKeyFrames answers true (:398-399).
+    // made: when not NULL, every point created here.
+    template <class MapPointT, class KeyFrameT, class AtlasT, class RecentListT, class CheckFn>
+    static int replay(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpNeighKFs, AtlasT *pAtlas, RecentListT &mlpRecentAddedMapPoints,
+                      CheckFn &CheckNewKeyFrames, const std::vector<RumiNewPoint> &pts, const std::vector<int32_t> &per,
+                      std::vector<MapPointT *> *deferRefresh, std::vector<MapPointT *> *made) {
+        int created = 0, next = 0;
+        for (int i = 0; i < (int)vpNeighKFs.size(); i++) {
+            if (i > 0 && CheckNewKeyFrames()) return created;                   // :398-399
+            KeyFrameT *pKF2 = vpNeighKFs[i];
+            for (int j = 0; j < per[i]; j++, next++) {
+                const RumiNewPoint &P = pts[next];
+                const Eigen::Vector3f x3D(P.x3D[0], P.x3D[1], P.x3D[2]);
+                MapPointT *pMP = new MapPointT(x3D, pCurrentKF, pAtlas->GetCurrentMap());
+                pMP->AddObservation(pCurrentKF, P.idx1);
+                pMP->AddObservation(pKF2, P.idx2);
+                pCurrentKF->AddMapPoint(pMP, P.idx1);
+                pKF2->AddMapPoint(pMP, P.idx2);
+                if (deferRefresh) deferRefresh->push_back(pMP);
+                else {
+                    pMP->ComputeDistinctiveDescriptors();
+                    pMP->UpdateNormalAndDepth();
+                }
+                pAtlas->AddMapPoint(pMP);
+                mlpRecentAddedMapPoints.push_back(pMP);
+                if (made) made->push_back(pMP);
+                created++;
+            }
+        }
+        return created;
+    }
+
+    template <class KeyFrameT> static void pose_of(KeyFrameT *pKF, RumiNewPointsPose &o) {
+        const Sophus::SE3f Tcw = pKF->GetPose();                                // as marshal() below
+        const Eigen::Matrix3f R = Tcw.rotationMatrix();
+        const Eigen::Vector3f t = Tcw.translation(), Ow = pKF->GetCameraCenter();
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) o.Tcw[r * 4 + c] = R(r, c); o.Tcw[r * 4 + 3] = t(r); o.Ow[r] = Ow(r); }
+        for (float &f : o.F12) f = 0.f;
+        o.epipole2[0] = o.epipole2[1] = 0.f;
+    }
 
     template <class KeyFrameT> static bool has_stereo(KeyFrameT *pKF) {
         for (float u : pKF->mvuRight) if (u >= 0) return true;

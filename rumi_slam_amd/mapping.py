@@ -10,6 +10,7 @@ from . import capi
 from .matcher import FeatureVector, FrameView, RumiFeatureVector, RumiFrameFeatures
 
 MAX_NEIGH = 64
+MAX_FEATURES = 16384
 
 NEWPOINT_DTYPE = np.dtype([("neigh", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("x3D", "<f4", 3)])
 assert NEWPOINT_DTYPE.itemsize == 24
@@ -31,6 +32,8 @@ def _lib():
         return L
     vp, i32 = C.c_void_p, C.c_int32
     L.rumi_create_new_map_points.argtypes = [vp, vp, vp, i32, vp, vp, i32, C.POINTER(i32), vp, vp]
+    L.rumi_create_new_map_points_resident.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, C.POINTER(i32), vp, vp]
+    L.rumi_newpts_stage_ms.argtypes = [vp, vp]
     L.rumi_hook_newpts_matches.argtypes = [vp, i32, i32, vp]
     L.rumi_refresh_create.argtypes = [i32, C.POINTER(vp)]
     L.rumi_refresh_destroy.argtypes = [vp]
@@ -93,6 +96,59 @@ def CreateNewMapPoints(matcher, cur, neighbours, ratio_factor, coarse=False, far
     capi.check(L.rumi_create_new_map_points(matcher._h, C.byref(c), C.byref(arr) if n else None, n, C.byref(prm), capi.ptr(out), cap, C.byref(n_out),
                                             capi.ptr(per), capi.ptr(skipped)))
     return out[:n_out.value], per[:n], skipped[:n]
+
+
+class RumiNewPointsPose(C.Structure):
+    _fields_ = [("Tcw", C.c_float * 12), ("Ow", C.c_float * 3), ("F12", C.c_float * 9), ("epipole2", C.c_float * 2)]
+
+
+assert C.sizeof(RumiNewPointsPose) == 104
+
+
+def pose(Tcw, Ow, F12=None, epipole2=None):
+    """What changes with every bundle adjustment, by value: a KeyFrameView's Tcw / Ow / F12 / epipole2 as one RumiNewPointsPose."""
+    p = RumiNewPointsPose()
+    p.Tcw[:] = np.asarray(Tcw, np.float32).reshape(12).tolist()
+    p.Ow[:] = np.asarray(Ow, np.float32).reshape(3).tolist()
+    if F12 is not None:
+        p.F12[:] = np.asarray(F12, np.float32).reshape(9).tolist()
+    if epipole2 is not None:
+        p.epipole2[:] = np.asarray(epipole2, np.float32).reshape(2).tolist()
+    return p
+
+
+def pack_poses(cur_pose, neigh_poses):
+    """(RumiNewPointsPose, array of RumiNewPointsPose) for the C entry."""
+    arr = (RumiNewPointsPose * max(len(neigh_poses), 1))(*neigh_poses)
+    return cur_pose, arr
+
+
+def CreateNewMapPointsResident(matcher, store, cur_slot, cur_pose, neigh_slots, neigh_poses, ratio_factor, coarse=False, far_points=False,
+                               th_far_points=0.0, cap=None):
+    """CreateNewMapPoints over key-frames resident in ``store`` (a covis.Covisibility whose slots hold features, map-point rows and point
+    attributes).  ``cur_pose`` / ``neigh_poses``: RumiNewPointsPose (see ``pose``).  Returns what CreateNewMapPoints returns."""
+    L = _lib()
+    n = len(neigh_slots)
+    assert len(neigh_poses) == n
+    slots = np.ascontiguousarray(neigh_slots, np.int32).reshape(-1)
+    cp, arr = pack_poses(cur_pose, list(neigh_poses))
+    prm = RumiNewPointsParams(int(coarse), int(matcher.mbCheckOrientation), int(far_points), float(th_far_points), float(ratio_factor))
+    cap = MAX_FEATURES if cap is None else int(cap)          # a list never needs more entries than the current key-frame has features
+    out = np.zeros(max(cap, 1), NEWPOINT_DTYPE)
+    per = np.zeros(max(n, 1), np.int32)
+    skipped = np.zeros(max(n, 1), np.uint8)
+    n_out = C.c_int32()
+    capi.check(L.rumi_create_new_map_points_resident(matcher._h, store._h, int(cur_slot), C.byref(cp), capi.ptr(slots) if n else None,
+                                                     C.byref(arr) if n else None, n, C.byref(prm), capi.ptr(out), cap, C.byref(n_out),
+                                                     capi.ptr(per), capi.ptr(skipped)))
+    return out[:n_out.value], per[:n], skipped[:n]
+
+
+def stage_ms(matcher):
+    """(validation + packing, upload + kernels + download, write-out) of the matcher's last CreateNewMapPoints call of either kind, ms."""
+    out = np.zeros(3, np.float32)
+    capi.check(_lib().rumi_newpts_stage_ms(matcher._h, capi.ptr(out)))
+    return out
 
 
 def last_matches(matcher, n_neigh, n1):
