@@ -44,6 +44,13 @@ int rumi_hook_disc_moments(const uint8_t *rows, int32_t s, const int32_t *umax16
 int rumi_hook_lane_packing(int32_t w, int32_t h, float scale, int32_t nlevels, int32_t nframes, int32_t kernel, int32_t level, int32_t force_g,
                            int32_t *info, int32_t *slots, int32_t cap, int32_t *n_out);
 
+/* Stream plan of the resident queue (orb_geom.h: stream_plan, what rumi_orb_set_resident_queue asks): for requested_slots slots and hw_queues
+ * hardware queues (<= 0: GPU_MAX_HW_QUEUES as the library read it, 4 when unset or unparsable), the slot streams it drives and whether a
+ * slot's blur runs on the slot's own stream; reserve (may be null) = the queues the rule leaves to the caller's stream.
+ * rumi_hook_parse_hw_queues: the library's reading of a GPU_MAX_HW_QUEUES value (null = unset). */
+int rumi_hook_stream_plan(int32_t requested_slots, int32_t hw_queues, int32_t *streams, int32_t *blur_inline, int32_t *reserve);
+int rumi_hook_parse_hw_queues(const char *value);
+
 /* Stages 1 + 3 of the last rumi_create_new_map_points call on this matcher (rumi_mapping.h; needs a device): per neighbour k and feature i1 of
  * the current key-frame, matches[k * n1 + i1] = the neighbour's feature SearchForTriangulation pairs it with when the loop reaches neighbour k
  * (after the rotation histogram, before the triangulation gates), -1 = none.  n_neigh and n1 must be those of that call.  The call itself does

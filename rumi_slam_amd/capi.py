@@ -209,7 +209,8 @@ def covis_lib():
 
 
 HOOK_SYMBOLS = ["rumi_hook_sort_like_std", "rumi_hook_sort_device", "rumi_hook_std_sort", "rumi_hook_quadtree", "rumi_hook_sinf", "rumi_hook_cosf",
-                "rumi_hook_fast_atan2", "rumi_hook_cv_round", "rumi_hook_magic_div", "rumi_hook_newpts_matches", "rumi_hook_lane_packing", "rumi_hook_disc_moments"]
+                "rumi_hook_fast_atan2", "rumi_hook_cv_round", "rumi_hook_magic_div", "rumi_hook_newpts_matches", "rumi_hook_lane_packing", "rumi_hook_disc_moments",
+                "rumi_hook_stream_plan", "rumi_hook_parse_hw_queues"]
 
 
 def hooks():
@@ -231,5 +232,7 @@ def hooks():
     L.rumi_hook_magic_div.argtypes = [i32, i32]
     L.rumi_hook_lane_packing.argtypes = [i32, i32, C.c_float, i32, i32, i32, i32, i32, vp, vp, i32, C.POINTER(i32)]
     L.rumi_hook_disc_moments.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.rumi_hook_stream_plan.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.rumi_hook_parse_hw_queues.argtypes = [C.c_char_p]
     L._hooks_ready = True
     return L

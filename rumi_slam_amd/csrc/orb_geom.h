@@ -212,6 +212,32 @@ inline LanePack blur_pack_of(int w, int nframes, long long spanBytes) {
     return lane_pack_choose(blur_lanes_per_row(w), 1, 62, 1, nframes, kLanePackMaxG, spanBytes);
 }
 
+// Stream plan of the resident queue.  A process has `hwQueues` hardware queues (GPU_MAX_HW_QUEUES, 4 unless set) and a hardware queue runs its
+// packets in order whichever stream they came from, so streams beyond the queues do not add concurrency: they couple unrelated slots (a slot's
+// blur stream lands on the queue of ANOTHER slot's main stream and waits behind its kernels).  The plan drives
+//   streams = min(requestedSlots, max(2, hwQueues - reserve))
+// slot streams, and runs a slot's blur on the slot's own stream (`blurInline`) whenever slot + blur streams + reserve would not fit the queues.
+// reserve: queues left to the caller's stream (the matcher); kStreamReserve is the measured choice.
+constexpr int kStreamReserve = 1;
+constexpr int kDefaultHwQueues = 4;
+struct StreamPlan { int streams; bool blurInline; };
+inline StreamPlan stream_plan(int requestedSlots, int hwQueues, int reserve = kStreamReserve) {
+    const int streams = std::min(requestedSlots, std::max(2, hwQueues - reserve));
+    return StreamPlan{streams, 2 * streams + reserve > hwQueues};
+}
+// GPU_MAX_HW_QUEUES as the runtime reads it: a positive decimal integer; unset (null) or anything else = the default of 4
+inline int parse_hw_queues(const char *v) {
+    if (!v || !*v) return kDefaultHwQueues;
+    char *end = nullptr;
+    const long q = std::strtol(v, &end, 10);
+    return (*end || q < 1 || q > 4096) ? kDefaultHwQueues : (int)q;
+}
+// ... read once per process; the library only reads the variable
+inline int hw_queues_env() {
+    static const int q = parse_hw_queues(std::getenv("GPU_MAX_HW_QUEUES"));
+    return q;
+}
+
 // cv::resize INTER_LINEAR 8UC1 coefficient tables for one axis: ofs[d] and the two 11-bit taps.
 // Horizontal axis (clampX = true): the source index is clamped and the tap zeroed as cv does, and
 // `maxOut` receives xmax (first destination index whose second tap would fall outside the source:

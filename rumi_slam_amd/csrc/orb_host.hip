@@ -120,19 +120,23 @@ struct RumiOrb {
     float stageMs[8] = {0};
     hipEvent_t ev[8] = {nullptr};
     // the blur only depends on the pyramid: it runs on a side stream next to FAST / quadtree and joins before rBRIEF
-    hipStream_t sideStream = nullptr;
+    hipStream_t sideStream = nullptr;                // (made at the first call that forks the blur: ensure_side)
     hipEvent_t evFork = nullptr, evJoin = nullptr;   // fork / join of the blur on sideStream
     // a chunk's frames are split over the caller's stream and slots 1.. (slot 0 is the caller's stream except in the resident queue); the caller's
     // stream waits for slot p's sub-chunks on slotJoin[p]
     static constexpr int kMaxParts = 8;
-    struct Lane { hipStream_t s, bs; hipEvent_t fork, join; };   // main stream, blur stream, fork / join of the blur
+    // A slot's streams exist from the first arrangement that drives them (ensure_lanes): every stream a handle creates holds a reference on one
+    // of the process's few hardware queues, and the runtime places the next stream on the least-referenced queue, so idle streams only push
+    // the driven ones together.
+    struct Lane { hipStream_t s, bs; hipEvent_t fork, join; };   // main stream, blur stream (bs == s: the blur in line, no fork / join), fork / join of the blur
     Lane slot[kMaxParts] = {};
     hipEvent_t slotJoin[kMaxParts] = {nullptr};
     // rumi_orb_set_resident_queue: the frames of a call do not depend on work pending on the caller's stream, so sub-chunk 0 gets a stream of
     // its own too (with its blur stream) and no sub-chunk waits for the caller's stream: back-to-back calls then overlap like the sub-chunks of
     // one large call, only the caller's stream waits for each call's results
     bool residentQueue = false;
-    int residentSlots = 4;                    // slots of the resident queue (2 .. kMaxParts)
+    int residentSlots = 4;                    // slots the caller asked for (2 .. kMaxParts): calls in flight, and what the arenas are sized for
+    StreamPlan plan{4, true};                 // ... and what of them is driven: plan.streams slot streams, the blur in line or on blur streams (orb_geom.h: stream_plan)
     int scratchFrames = 0, arenaFrames = 0;   // frames the scratch arrays / the pyramid and blur arenas hold
     int rot = 0;                     // slot of the next sub-chunk
     hipEvent_t userReady = nullptr;  // rumi_orb_wait_event: the sub-chunks of the next resident-queue call start behind it
@@ -268,25 +272,32 @@ extern "C" int rumi_orb_create(const RumiOrbConfig *cfg, RumiOrb **out) {
 #undef TRY_ALLOC
     for (auto &e : h->ev)
         if (hipEventCreate(&e) != hipSuccess) { rumi_orb_destroy(h); g_lastError = "hipEventCreate"; return RUMI_E_NO_DEVICE; }
-    // slots 1 .. kMaxParts - 1 first, then slot 0, then the side stream: streams share the hardware queues in creation order
-    auto make_slot = [h](int p) {
-        RumiOrb::Lane &L = h->slot[p];
-        return hipStreamCreateWithFlags(&L.s, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&L.bs, hipStreamNonBlocking) == hipSuccess &&
-               hipEventCreateWithFlags(&L.fork, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&L.join, hipEventDisableTiming) == hipSuccess &&
-               hipEventCreateWithFlags(&h->slotJoin[p], hipEventDisableTiming) == hipSuccess;
-    };
-    bool slotsOk = true;
-    for (int p = 1; p < RumiOrb::kMaxParts && slotsOk; ++p) slotsOk = make_slot(p);
-    if (!slotsOk || !make_slot(0)) { rumi_orb_destroy(h); g_lastError = "slot stream"; return RUMI_E_NO_DEVICE; }
     if (hipEventCreateWithFlags(&h->evPartFork, hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithFlags(&h->sideStream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->evFork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming) != hipSuccess || hipEventCreate(&h->evB0) != hipSuccess ||
-        hipEventCreate(&h->evB1) != hipSuccess) { rumi_orb_destroy(h); g_lastError = "side stream"; return RUMI_E_NO_DEVICE; }
+        hipEventCreate(&h->evB1) != hipSuccess) { rumi_orb_destroy(h); g_lastError = "hipEventCreate"; return RUMI_E_NO_DEVICE; }
     *out = h;
     return RUMI_OK;
 }
 
+// The streams and events of slots [p0, p1), made when an arrangement first drives them (rumi_orb_set_resident_queue, the first call of equal
+// sub-chunks); blurStreams: with a blur stream and its fork / join events each.  rumi_orb_destroy frees what exists.
+static int ensure_lanes(RumiOrb *h, int p0, int p1, bool blurStreams) {
+    for (int p = p0; p < p1; ++p) {
+        RumiOrb::Lane &L = h->slot[p];
+        if (!L.s) HIP_TRY(hipStreamCreateWithFlags(&L.s, hipStreamNonBlocking));
+        if (!h->slotJoin[p]) HIP_TRY(hipEventCreateWithFlags(&h->slotJoin[p], hipEventDisableTiming));
+        if (!blurStreams) continue;
+        if (!L.bs) HIP_TRY(hipStreamCreateWithFlags(&L.bs, hipStreamNonBlocking));
+        if (!L.fork) HIP_TRY(hipEventCreateWithFlags(&L.fork, hipEventDisableTiming));
+        if (!L.join) HIP_TRY(hipEventCreateWithFlags(&L.join, hipEventDisableTiming));
+    }
+    return RUMI_OK;
+}
+static int ensure_side(RumiOrb *h) {
+    if (!h->sideStream) HIP_TRY(hipStreamCreateWithFlags(&h->sideStream, hipStreamNonBlocking));
+    return RUMI_OK;
+}
 extern "C" int rumi_orb_set_profiling(RumiOrb *h, int32_t on) {
     if (!h) return RUMI_E_INVALID;
     h->profiling = on != 0;
@@ -299,6 +310,9 @@ extern "C" int rumi_orb_set_resident_queue(RumiOrb *h, int32_t on) {
         // `on` slots (1: the default of four) of up to 256 frames each: their scratch ranges and their ranges of the pyramid / blur arenas
         const int slots = on == 1 ? 4 : std::min(std::max(on, 2), (int)RumiOrb::kMaxParts);
         h->residentSlots = slots;
+        h->plan = stream_plan(slots, hw_queues_env());
+        HIP_TRY(hipSetDevice(h->device));
+        if (const int rc = ensure_lanes(h, 0, h->plan.streams, !h->plan.blurInline); rc != RUMI_OK) return rc;
         const int need = (slots * std::min(kResidentSub, h->cfg.max_batch) + 23) / 24 * 24;
         if (h->scratchFrames < need || h->arenaFrames < need) {
             HIP_TRY(hipSetDevice(h->device));

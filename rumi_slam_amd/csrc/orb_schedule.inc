@@ -81,6 +81,7 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
     if (h->userReady && !resident) { HIP_TRY(hipStreamWaitEvent(st, h->userReady, 0)); h->userReady = nullptr; }
     using Lane = RumiOrb::Lane;
     auto lane_of = [&](int slot) -> Lane {
+        if (resident && h->plan.blurInline) return {h->slot[slot].s, h->slot[slot].s, nullptr, nullptr};   // the blur in line: behind the pyramid on the slot's own stream
         if (slot || resident) return h->slot[slot];      // (in the resident queue no slot runs on the caller's stream)
         return {st, serial || prof ? st : h->sideStream, h->evFork, h->evJoin};        // profiling: the blur on the call's stream too, so that every stage time is a stand-alone duration
     };
@@ -90,6 +91,11 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
     // Up to 4 frames: the pyramid in ONE launch (k_pyramid_tiles) instead of a launch per level.  (Batches keep the per-level launches: a
     // workgroup walks seven levels between barriers and its threads idle on the small ones, which costs more than the saved re-reads bring.)
     const bool tilePyramid = !prof && !serial && nframes <= 4 && h->nPyrTiles > 0;
+    // the streams this call's arrangement drives (made at its first use: ensure_lanes)
+    if (resident) rc = ensure_lanes(h, 0, h->plan.streams, !h->plan.blurInline);
+    else if (parts > 1) rc = ensure_lanes(h, 1, parts, true);
+    if (rc == RUMI_OK && !resident && !serial && !prof && !fuseBlur) rc = ensure_side(h);
+    if (rc != RUMI_OK) return rc;
     auto stage_a = [&](const ImgSrc &ps, int n, const Lane &L) -> int {
         hipStream_t s = L.s;
         if (prof) HIP_TRY(hipEventRecord(h->ev[0], s));
@@ -103,12 +109,15 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
         }
         if (prof) HIP_TRY(hipEventRecord(h->ev[1], s));
         if (fuseBlur) return RUMI_OK;
-        HIP_TRY(hipEventRecord(L.fork, s));
-        HIP_TRY(hipStreamWaitEvent(L.bs, L.fork, 0));
+        const bool forked = L.bs != s;           // (in line -- the resident queue's plan, RUMI_SERIAL, profiling -- stream order is the fork and the join)
+        if (forked) {
+            HIP_TRY(hipEventRecord(L.fork, s));
+            HIP_TRY(hipStreamWaitEvent(L.bs, L.fork, 0));
+        }
         if (prof) HIP_TRY(hipEventRecord(h->evB0, L.bs));
         launch_blur(h->dP, P, ps, n, h->cfg.blur_variant, L.bs);
         if (prof) HIP_TRY(hipEventRecord(h->evB1, L.bs));
-        HIP_TRY(hipEventRecord(L.join, L.bs));
+        if (forked) HIP_TRY(hipEventRecord(L.join, L.bs));
         HIP_TRY(hipGetLastError());
         return RUMI_OK;
     };
@@ -155,7 +164,7 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
         // batches: IC_Angle and the trigonometry in a kernel of their own, BEFORE the join (it reads the un-blurred levels only)
         float4 *trig = !fuseAssemble && orient_desc_split(h->capSel, n) ? h->dSelTrig + (size_t)scr0 * h->capSel : nullptr;
         if (trig) launch_disc_angle(h->dP, ps, selPacked, selMeta, h->dSelCount + scr0, h->capSel, h->capSel, h->dDiscVec, trig, n, s);
-        if (!fuseBlur) HIP_TRY(hipStreamWaitEvent(s, L.join, 0));   // join: rBRIEF reads the blurred levels
+        if (!fuseBlur && L.bs != s) HIP_TRY(hipStreamWaitEvent(s, L.join, 0));   // join: rBRIEF reads the blurred levels
         if (fuseAssemble)
             launch_assemble_orient_desc(h->dP, ps, selLevel, selLevelCnt, h->selLevelCap, lap0, lap1, countsOut, out.countsStride, h->dErr,
                                         opts.zeroCopyOut ? h->dhErr : nullptr, selPacked, selMeta, h->dSelCount + scr0, h->capSel, h->capSel,
@@ -171,12 +180,21 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
         return RUMI_OK;
     };
     if (resident) {
-        // Resident queue: FOUR fixed slots (stream, blur stream, scratch range, pyramid / blur arena range), sub-chunks of at most 256 frames
-        // dealt to the slots round-robin ACROSS calls (a 64-frame call takes one slot, the next call the next one).  Everything a sub-chunk
+        // Resident queue: the plan's fixed slots (stream, scratch range, pyramid / blur arena range; a blur stream only where the hardware
+        // queues have room for it), sub-chunks of at most 256 frames dealt to the slots round-robin ACROSS calls (a 64-frame call takes one
+        // slot, the next call the next one).  The plan may drive fewer slots than the caller asked for (orb_geom.h: stream_plan): a call
+        // then puts consecutive sub-chunks on one stream, which stream order covers like consecutive calls.  Everything a sub-chunk
         // touches on the device belongs to its slot, so stream order alone keeps consecutive users of a slot apart: no sub-chunk waits for
         // the caller's stream or for another slot -- except after a rumi_orb_sync, whose reset of the error word is queued on `st`.
+        // With the blur in line a slot has ONE stream and both arena hazards rest on its order, nothing else:
+        //   - a sub-chunk's blur writes the slot's blurred arena, which the previous sub-chunk's k_orient_desc on that slot read: the blur
+        //     is enqueued behind it on the same stream;
+        //   - a sub-chunk's pyramid overwrites the levels the previous sub-chunk's k_disc_angle and k_fast_cells read (and its blur):
+        //     all of them precede it on the same stream.
+        // (With blur streams the second hazard has a gap the join closes: the blur stream's join is waited for before k_orient_desc, so
+        // the previous blur has ended before the slot's next pyramid starts.)
         constexpr int kMaxSlots = RumiOrb::kMaxParts;
-        const int kSlots = h->residentSlots;
+        const int kSlots = h->plan.streams;
         const int slotFrames = h->scratchFrames / kSlots;
         const int cap64 = std::min(kResidentSub, slotFrames);
         const int nsub = (nframes + cap64 - 1) / cap64, sub = (nframes + nsub - 1) / nsub;

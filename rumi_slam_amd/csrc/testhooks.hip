@@ -109,3 +109,13 @@ extern "C" int rumi_hook_lane_packing(int32_t w, int32_t h, float scale, int32_t
             }
     return RUMI_OK;
 }
+
+// the stream plan of the resident queue (orb_geom.h: stream_plan, the function rumi_orb_set_resident_queue asks)
+extern "C" int rumi_hook_stream_plan(int32_t requested_slots, int32_t hw_queues, int32_t *streams, int32_t *blur_inline, int32_t *reserve) {
+    if (!streams || !blur_inline || requested_slots < 1) return RUMI_E_INVALID;
+    const StreamPlan p = stream_plan(requested_slots, hw_queues > 0 ? hw_queues : hw_queues_env());
+    *streams = p.streams; *blur_inline = p.blurInline ? 1 : 0;
+    if (reserve) *reserve = kStreamReserve;
+    return RUMI_OK;
+}
+extern "C" int rumi_hook_parse_hw_queues(const char *value) { return parse_hw_queues(value); }
