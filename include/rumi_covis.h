@@ -9,8 +9,9 @@
  *   per key-frame slot: mp[n] (GetMapPointMatches as point ids, -1 = NULL), is_bad, map_id, order_key, best[10]
  *                       (GetBestCovisibilityKeyFrames(10) as slots, -1 padded), parent slot or -1, the children as a slot list; and
  *                       optionally its features (rumi_covis_set_keyframe_features, below), which the two members above do not read
- *   per point:          is_bad, the observers (the key-frame slots of GetObservations(); feature indices are not kept), and optionally the
- *                       attributes TrackLocalMap reads: GetWorldPos, GetNormal, mfMinDistance, mfMaxDistance, GetDescriptor, and a "has
+ *   per point:          is_bad, the observers (the key-frame slots of GetObservations(), and with rumi_covis_set_point_observations the
+ *                       feature index of each, plus a "has observation features" bit: rumi_keyframe_culling_resident reads the observer's
+ *                       octave through it), and optionally the attributes TrackLocalMap reads: GetWorldPos, GetNormal, mfMinDistance, mfMaxDistance, GetDescriptor, and a "has
  *                       attributes" bit.  Observations() is not a field: for the monocular model it is the length of the observer row.
  *                       isBad() is the bit rumi_covis_set_points / rumi_covis_set_bad maintain.  rumi_track_local_map (rumi_track.h) builds
  *                       its point table from these on the device.
@@ -60,6 +61,12 @@ int rumi_covis_set_keyframes(RumiCovis *c, int32_t n, const int32_t *slots, cons
                              const int32_t *children);
 /* n points, each id at most once: observers of entry i = obs[obs_off[i] .. obs_off[i+1]), distinct live slots. */
 int rumi_covis_set_points(RumiCovis *c, int32_t n, const int32_t *ids, const uint8_t *is_bad, const int32_t *obs_off, const int32_t *obs);
+/* rumi_covis_set_points, and per observer the feature index GetObservations() holds for it (get<0> of the tuple).
+ * obs_feature[j] in 0 .. RUMI_COVIS_MAX_FEATURES-1.  A point set through this entry "has observation features"; a point set
+ * later through rumi_covis_set_points loses them again.  Same checks and messages as rumi_covis_set_points, plus the feature range.  Whether
+ * (slot, feature) agrees with the slot's map-point row is checked by the query that reads it, not here. */
+int rumi_covis_set_point_observations(RumiCovis *c, int32_t n, const int32_t *ids, const uint8_t *is_bad, const int32_t *obs_off, const int32_t *obs_slot,
+                                      const int32_t *obs_feature);
 /* The attributes of n points, each id at most once: pos / normal [n][3], min_dist / max_dist [n] (raw: isInFrustum applies 0.8 and 1.2),
  * desc [n][32].  To be called where the reference calls SetWorldPos, UpdateNormalAndDepth and ComputeDistinctiveDescriptors.  Staged like every
  * edit: the next query uploads the changed records.  A point keeps its attributes until they are set again. */

@@ -265,8 +265,25 @@ int rumi_keyframe_culling(RumiCull *c, const RumiCullKF *kfs, int32_t n_kf, cons
                           int32_t n_pts, const int32_t *obs_kf, const int32_t *obs_feature, int32_t n_obs, int32_t flags, int32_t *status,
                           int32_t *n_mps, int32_t *n_redundant, int32_t *culled, int32_t *n_culled);
 
-/* Host wall-clock of the handle's last successful call with work, in ms: out3[0] validation and pack, out3[1] upload + kernels + download,
- * out3[2] writing the caller's arrays.  For tools/culling_probe.py. */
+/* The same loop over a covisibility store (rumi_covis.h): nothing of the map travels but the store's staged edits.  A candidate is a slot;
+ * is_init, not_erase and is_cloud as in RumiCullKF.  isBad() of key-frames and points are the store's bits, a candidate's row is its map-point
+ * row, Observations() the length of a point's observer row, and an observer's octave is keys[feature].octave of that slot's resident
+ * features (rumi_covis_set_keyframe_features), with the feature index rumi_covis_set_point_observations stored.  Outputs and statuses are
+ * those of rumi_keyframe_culling on the same map, byte for byte; the same kernels run over a view of the store.  A query: the store is not
+ * changed.  The caller applies SetBadFlag() in the returned order and stages its edits for the next call.
+ * RUMI_E_INVALID, nothing written: a missing argument or unknown flag; a candidate slot that is not live; a candidate that will be
+ * evaluated and holds no features, or whose feature count differs from the length of its row; a point in such a row without observation
+ * features (checked on the store's host mirror, with the count); the handle and the store on different devices; and, counted on the device
+ * among the rows of the evaluated candidates, their points and those points' observers: an observer slot without resident features, an
+ * observation (k, f) with f outside k's row or row_k[f] != p, a candidate slot i holding p where p does not list (candidate, i).  The check
+ * happens at the query because the store is legitimately inconsistent between two staged edits.  RUMI_E_CAPACITY, nothing written: a point
+ * of those rows above RUMI_REFRESH_MAX_OBS observers.  n_cand = 0 is RUMI_OK (*n_culled = 0) and makes no device call. */
+typedef struct RumiCullCandidate { int32_t slot; uint8_t is_init, not_erase, is_cloud, pad_; } RumiCullCandidate;
+int rumi_keyframe_culling_resident(RumiCull *h, RumiCovis *c, const RumiCullCandidate *cand, int32_t n_cand, int32_t flags, int32_t *status,
+                                   int32_t *n_mps, int32_t *n_redundant, int32_t *culled, int32_t *n_culled);
+
+/* Host wall-clock of the handle's last successful call with work (either entry), in ms: out3[0] validation and pack, out3[1] upload +
+ * kernels + download, out3[2] writing the caller's arrays.  For tools/culling_probe.py. */
 int rumi_cull_stage_ms(const RumiCull *c, float *out3);
 
 #ifdef __cplusplus

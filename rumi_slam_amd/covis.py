@@ -65,6 +65,13 @@ class Covisibility:
         oo, ob = _csr(list(observers))
         return self._ret(self._lib.rumi_covis_set_points(self._h, len(ids), _p(ids), _p(bad), _p(oo), _p(ob)), check)
 
+    def set_point_observations(self, ids, bad, observations, check=True):
+        """set_points with the feature index of every observer: observations[i] = [(slot, feature), ...] of point ids[i]."""
+        ids = np.ascontiguousarray(ids, _i32); bad = np.ascontiguousarray(bad, _u8)
+        oo, ob = _csr([[o[0] for o in r] for r in observations])
+        _, of = _csr([[o[1] for o in r] for r in observations])
+        return self._ret(self._lib.rumi_covis_set_point_observations(self._h, len(ids), _p(ids), _p(bad), _p(oo), _p(ob), _p(of)), check)
+
     def set_point_attributes(self, ids, pos, normal, min_dist, max_dist, desc, check=True):
         """GetWorldPos / GetNormal [n, 3], mfMinDistance / mfMaxDistance [n] (raw), GetDescriptor [n, 32] of the points `ids`."""
         ids = np.ascontiguousarray(ids, _i32); n = len(ids)

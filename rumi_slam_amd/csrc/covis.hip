@@ -4,7 +4,9 @@
 // Resident state, all of it 32-bit words so that one scatter kernel applies every staged edit:
 //   kf     [max_kf][20]     mp row (offset, length), children row (offset, length), flags (bit 0 bad, bit 1 live), map, parent, -, order_key
 //                           (two words), best[10]
-//   pt     [max_points][4]  observer row (offset, length), bad, has attributes
+//   pt     [max_points][4]  observer row (offset, length), flags (bit 0 bad, bit 1 has observation features), has attributes.  An observer
+//                           entry is slot | feature << 13 (kCovisObsSlotMask): the feature index GetObservations() holds, 0 where the
+//                           point was set without them (rumi_covis_set_points)
 //   attr   [max_points][16] position, normal, mfMinDistance, mfMaxDistance (eight floats), then the 32 descriptor bytes: a 64-byte record whose
 //                           two halves are 16-byte aligned, so a gather may read either as two uint4 or as eight dwords over eight lanes.
 //                           Allocated with the first rumi_covis_set_point_attributes; the tracker's table gather reads it (track_local_map.inc)
@@ -13,6 +15,8 @@
 //   tag    [max_points]     64-bit stamps of the local-point selection, (call epoch << 32) | priority
 //   rowOf  [max_points]     64-bit stamps of the same epoch for rumi_track_local_map's id -> table row map (allocated with its first call)
 //   feat                    the key-frames' constant part, a byte arena of its own with no host mirror (covis_features.inc)
+//   featTab [max_kf][4]     where a slot's key-points lie in feat (64-bit byte offset, -1: no features), its feature count, -: what a kernel
+//                           needs to read the octave of an observation it meets in an observer row (culling.hip)
 // The host keeps a mirror of kf, pt, attr and the arena; an edit writes the mirror and notes (table, offset, words).  The next query packs the noted
 // ranges and its own input into one pinned block, sends it with one copy, and k_covis_apply scatters it.
 //
@@ -42,10 +46,14 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int KFW = 20, PTW = kCovisPointWords, ATW = kCovisAttrWords;     // words per key-frame / point / attribute record
 constexpr int K_MPOFF = 0, K_MPLEN = 1, K_CHOFF = 2, K_CHLEN = 3, K_FLAGS = 4, K_MAP = 5, K_PARENT = 6, K_KEY = 8, K_BEST = 10;
-constexpr int T_KF = 0, T_PT = 1, T_ARENA = 2, T_ATTR = 3, kTables = 4;
+constexpr int T_KF = 0, T_PT = 1, T_ARENA = 2, T_ATTR = 3, T_FEAT = 4, kTables = 5;
+constexpr int FTW = kCovisFeatTabWords;
 constexpr uint16_t kNone = 0xFFFF;                     // sorts last; slots stay below RUMI_COVIS_MAX_KEYFRAMES
 constexpr int kPosBits = 13;
 static_assert((1 << kPosBits) == RUMI_COVIS_MAX_KEYFRAMES, "position bits of the packed maximum");
+static_assert((1 << kCovisObsSlotBits) == RUMI_COVIS_MAX_KEYFRAMES && ((int64_t)RUMI_COVIS_MAX_FEATURES << kCovisObsSlotBits) <= (1ll << 31),
+              "slot | feature << 13 is a non-negative 32-bit word");
+static_assert(KFW == kCovisKfWords && K_MPOFF == kCovisKfMpOff && K_MPLEN == kCovisKfMpLen, "the kf record as culling.hip reads it");
 static_assert((int64_t)RUMI_COVIS_MAX_FEATURES << kPosBits < (1ll << 31), "count << 13 | position fits 32 bits");
 static_assert((int64_t)RUMI_COVIS_MAX_KEYFRAMES * RUMI_COVIS_MAX_FEATURES <= (1ll << 32), "rank * features + feature fits 32 bits");
 
@@ -139,7 +147,7 @@ template <bool VOTE> __global__ __launch_bounds__(kThreads) void k_covis_count(C
             if (P.z & 1) bad = 1;
             else
                 for (int o = P.x, e = P.x + P.y; o < e; o++) {
-                    const int k = arena[o];
+                    const int k = arena[o] & kCovisObsSlotMask;
                     if (!VOTE) {
                         if (k == self) continue;
                         const int32_t *O = kf + k * KFW;
@@ -318,6 +326,9 @@ struct FeatureStore {
     std::vector<std::pair<int32_t, int64_t>> staged;             // (slot, stageOff) in staging order; stale when the slot's stageOff differs
     DevBuf<uint8_t> arena;
     int64_t onDevice = 0;                                        // the device arena holds what lies below
+    DevBuf<uint8_t> oct;                                         // [max_kf][octStride] keys[i].octave, device only (covis_features.inc)
+    int32_t octStride = 0, maxN = 0;                             // maxN: the longest key-frame ever set
+    std::vector<int32_t> octPending;                             // slots whose features changed since the table was brought up to date
     FeatureStore() = default;
     FeatureStore(const FeatureStore &) = delete;
     FeatureStore &operator=(const FeatureStore &) = delete;
@@ -334,6 +345,7 @@ struct RumiCovis {
     int32_t maxKf = 0, maxPts = 0;
     // host mirrors of the device tables
     std::vector<int32_t> kf, pt, arena, attr;        // attr: empty until the first rumi_covis_set_point_attributes
+    std::vector<int32_t> featTab;                    // [max_kf][FTW]
     int32_t hiAttr = 0;                              // highest point id with attributes + 1
     std::vector<int32_t> capMp, capCh, capObs;       // places of the rows in the arena (entries); 0 = never placed
     int64_t tail = 0, live = 0;
@@ -344,9 +356,9 @@ struct RumiCovis {
     int32_t stampKf = 0, stampPt = 0;
     // staged edits
     std::vector<int4> recs;                          // table, first word, -, words
-    bool full[kTables] = {true, true, true, true};
+    bool full[kTables] = {true, true, true, true, true};
     // device
-    DevBuf<int32_t> dKf, dPt, dArena, dAttr;         // dKf, dPt, dTag: with the first bind; dAttr, dRowOf: with their first use; dArena follows the mirror
+    DevBuf<int32_t> dKf, dPt, dArena, dAttr, dFeatTab;         // dKf, dPt, dTag: with the first bind; dAttr, dRowOf: with their first use; dArena follows the mirror
     DevBuf<unsigned long long> dTag, dRowOf;
     std::vector<uint8_t> extra;                      // the input block of rumi_track_local_map: frame points and the discarded outliers
     StageClock clock;                                // of the query in flight (the local-map query is launched and read in two calls)
@@ -394,7 +406,7 @@ void rebuild_arena(RumiCovis *h, int64_t need) {
     h->arena.swap(nv);
     h->tail = h->live = t;
     h->full[T_KF] = h->full[T_PT] = h->full[T_ARENA] = true;
-    h->recs.erase(std::remove_if(h->recs.begin(), h->recs.end(), [](const int4 &r) { return r.x != T_ATTR; }), h->recs.end());
+    h->recs.erase(std::remove_if(h->recs.begin(), h->recs.end(), [](const int4 &r) { return r.x != T_ATTR && r.x != T_FEAT; }), h->recs.end());
 }
 
 // Row (off, len) of place c takes src[0 .. n): in place when it fits, else at the tail.
@@ -418,8 +430,8 @@ int bind_device(RumiCovis *h) {
     bool first;
     int rc = h->dev.bind(&first);
     if (rc != RUMI_OK || !first) return rc;
-    const size_t nKf = (size_t)h->maxKf * KFW, nPt = (size_t)h->maxPts * PTW, nTag = (size_t)h->maxPts;
-    if ((rc = h->dKf.reserve(nKf, nKf)) != RUMI_OK || (rc = h->dPt.reserve(nPt, nPt)) != RUMI_OK || (rc = h->dTag.reserve(nTag, nTag)) != RUMI_OK)
+    const size_t nKf = (size_t)h->maxKf * KFW, nPt = (size_t)h->maxPts * PTW, nTag = (size_t)h->maxPts, nFt = (size_t)h->maxKf * FTW;
+    if ((rc = h->dKf.reserve(nKf, nKf)) != RUMI_OK || (rc = h->dFeatTab.reserve(nFt, nFt)) != RUMI_OK || (rc = h->dPt.reserve(nPt, nPt)) != RUMI_OK || (rc = h->dTag.reserve(nTag, nTag)) != RUMI_OK)
         return rc;
     HIP_TRY(hipMemsetAsync(h->dTag.p, 0, (size_t)h->maxPts * 8, nullptr));
     h->dev.bound = true;
@@ -439,8 +451,8 @@ int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) 
         if ((rc = h->dAttr.reserve((size_t)h->maxPts * ATW, (size_t)h->maxPts * ATW)) != RUMI_OK) return rc;
         h->full[T_ATTR] = true;
     }
-    int32_t *dBase[kTables] = {h->dKf.p, h->dPt.p, h->dArena.p, h->dAttr.p};
-    const std::vector<int32_t> *mirror[kTables] = {&h->kf, &h->pt, &h->arena, &h->attr};
+    int32_t *dBase[kTables] = {h->dKf.p, h->dPt.p, h->dArena.p, h->dAttr.p, h->dFeatTab.p};
+    const std::vector<int32_t> *mirror[kTables] = {&h->kf, &h->pt, &h->arena, &h->attr, &h->featTab};
     size_t words = 0, nRec = 0;
     for (int4 &r : h->recs)
         if (!h->full[r.x]) { r.z = (int)words; words += (size_t)r.w; h->recs[nRec++] = r; }
@@ -489,6 +501,8 @@ extern "C" int rumi_covis_create(int32_t max_kf, int32_t max_points, int64_t are
     h->dev.device = device; h->maxKf = max_kf; h->maxPts = max_points;
     h->kf.assign((size_t)max_kf * KFW, 0);
     h->pt.assign((size_t)max_points * PTW, 0);
+    h->featTab.assign((size_t)max_kf * FTW, 0);
+    for (int s = 0; s < max_kf; s++) h->featTab[(size_t)s * FTW] = h->featTab[(size_t)s * FTW + 1] = -1;
     h->arena.assign(arena_entries ? (size_t)std::max<int64_t>(arena_entries, 16) : (size_t)1 << 20, 0);
     h->capMp.assign(max_kf, 0); h->capCh.assign(max_kf, 0); h->capObs.assign(max_points, 0);
     h->kfStamp.assign(max_kf, 0); h->ptStamp.assign(max_points, 0);
@@ -594,9 +608,12 @@ extern "C" int rumi_covis_set_keyframes(RumiCovis *h, int32_t n, const int32_t *
     return RUMI_OK;
 }
 
-extern "C" int rumi_covis_set_points(RumiCovis *h, int32_t n, const int32_t *ids, const uint8_t *is_bad, const int32_t *obs_off, const int32_t *obs) {
+// rumi_covis_set_points (obs_feature null) and rumi_covis_set_point_observations: one validation, one staging.
+static int set_points_impl(RumiCovis *h, const char *entry, int32_t n, const int32_t *ids, const uint8_t *is_bad, const int32_t *obs_off, const int32_t *obs,
+                           const int32_t *obs_feature, bool withFeatures) {
+    const std::string E(entry);
     if (!h || n < 0 || (n > 0 && (!ids || !is_bad || !obs_off))) {
-        g_lastError = "rumi_covis_set_points: missing argument or negative count";
+        g_lastError = E + ": missing argument or negative count";
         return RUMI_E_INVALID;
     }
     if (n == 0) return RUMI_OK;
@@ -604,37 +621,59 @@ extern "C" int rumi_covis_set_points(RumiCovis *h, int32_t n, const int32_t *ids
     const int32_t inCall = ++h->stampPt;
     for (int i = 0; i < n; i++) {
         if (ids[i] < 0 || ids[i] >= h->maxPts || h->ptStamp[ids[i]] == inCall) {
-            g_lastError = "rumi_covis_set_points: a point id outside 0..max_points-1, or named twice";
+            g_lastError = E + ": a point id outside 0..max_points-1, or named twice";
             return RUMI_E_INVALID;
         }
         h->ptStamp[ids[i]] = inCall;
     }
-    if (obs_off[0] < 0) { g_lastError = "rumi_covis_set_points: a negative offset"; return RUMI_E_INVALID; }
+    if (obs_off[0] < 0) { g_lastError = E + ": a negative offset"; return RUMI_E_INVALID; }
     int64_t need = 0;
+    int32_t longest = 0;
     std::vector<int32_t> mark(h->maxKf, -1);
     for (int i = 0; i < n; i++) {
         const int64_t no = (int64_t)obs_off[i + 1] - obs_off[i];
-        if (no < 0 || no > h->maxKf || (no > 0 && !obs)) {
-            g_lastError = "rumi_covis_set_points: an observer slice that runs backwards, is longer than max_kf, or has no array";
+        if (no < 0 || no > h->maxKf || (no > 0 && (!obs || (withFeatures && !obs_feature)))) {
+            g_lastError = E + ": an observer slice that runs backwards, is longer than max_kf, or has no array";
             return RUMI_E_INVALID;
         }
         need += row_cap((int32_t)no);
+        longest = std::max(longest, (int32_t)no);
         for (int64_t j = obs_off[i]; j < obs_off[i + 1]; j++) {
             if (!is_live(h, obs[j]) || mark[obs[j]] == i) {
-                g_lastError = "rumi_covis_set_points: an observer that is not a live slot, or is listed twice";
+                g_lastError = E + ": an observer that is not a live slot, or is listed twice";
                 return RUMI_E_INVALID;
             }
             mark[obs[j]] = i;
+            if (withFeatures && (obs_feature[j] < 0 || obs_feature[j] >= RUMI_COVIS_MAX_FEATURES)) {
+                g_lastError = E + ": a feature index outside 0..RUMI_COVIS_MAX_FEATURES-1";
+                return RUMI_E_INVALID;
+            }
         }
     }
-    if (h->live + need > (1ll << 29)) { g_lastError = "rumi_covis_set_points: the row arena would pass 2^29 entries"; return RUMI_E_CAPACITY; }
+    if (h->live + need > (1ll << 29)) { g_lastError = E + ": the row arena would pass 2^29 entries"; return RUMI_E_CAPACITY; }
+    std::vector<int32_t> packed;
+    if (withFeatures) packed.resize((size_t)longest);
     for (int i = 0; i < n; i++) {
         const int32_t p = ids[i], no = obs_off[i + 1] - obs_off[i];
-        set_row(h, h->pt[(size_t)p * PTW], h->pt[(size_t)p * PTW + 1], h->capObs[p], no ? obs + obs_off[i] : nullptr, no);
-        h->pt[(size_t)p * PTW + 2] = is_bad[i] ? 1 : 0;
+        const int32_t *src = no ? obs + obs_off[i] : nullptr;
+        if (withFeatures && no) {
+            for (int j = 0; j < no; j++) packed[j] = src[j] | (obs_feature[obs_off[i] + j] << kCovisObsSlotBits);
+            src = packed.data();
+        }
+        set_row(h, h->pt[(size_t)p * PTW], h->pt[(size_t)p * PTW + 1], h->capObs[p], src, no);
+        h->pt[(size_t)p * PTW + 2] = (is_bad[i] ? 1 : 0) | (withFeatures ? kCovisPointHasObsFeatures : 0);
         note(h, T_PT, (int64_t)p * PTW, PTW);
     }
     return RUMI_OK;
+}
+
+extern "C" int rumi_covis_set_points(RumiCovis *h, int32_t n, const int32_t *ids, const uint8_t *is_bad, const int32_t *obs_off, const int32_t *obs) {
+    return set_points_impl(h, "rumi_covis_set_points", n, ids, is_bad, obs_off, obs, nullptr, false);
+}
+
+extern "C" int rumi_covis_set_point_observations(RumiCovis *h, int32_t n, const int32_t *ids, const uint8_t *is_bad, const int32_t *obs_off,
+                                                 const int32_t *obs_slot, const int32_t *obs_feature) {
+    return set_points_impl(h, "rumi_covis_set_point_observations", n, ids, is_bad, obs_off, obs_slot, obs_feature, true);
 }
 
 extern "C" int rumi_covis_set_bad(RumiCovis *h, int32_t n_kf, const int32_t *slots, const uint8_t *kf_bad, int32_t n_pt, const int32_t *ids,
@@ -652,7 +691,8 @@ extern "C" int rumi_covis_set_bad(RumiCovis *h, int32_t n_kf, const int32_t *slo
         note(h, T_KF, (int64_t)slots[i] * KFW + K_FLAGS, 1);
     }
     for (int i = 0; i < n_pt; i++) {
-        h->pt[(size_t)ids[i] * PTW + 2] = pt_bad[i] ? 1 : 0;
+        int32_t &f = h->pt[(size_t)ids[i] * PTW + 2];
+        f = (f & ~1) | (pt_bad[i] ? 1 : 0);
         note(h, T_PT, (int64_t)ids[i] * PTW + 2, 1);
     }
     return RUMI_OK;

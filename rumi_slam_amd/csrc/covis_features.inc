@@ -8,6 +8,10 @@
 //           to the tail; when the tail would pass the capacity, the capacity doubles until it fits.  Growth allocates the new arena, copies
 //           the old one device to device and releases it: nothing is uploaded twice.  A dropped or replaced block joins the free list, merged
 //           with free neighbours; a free block at the tail pulls the tail back.  Offsets are 64-bit.
+//   octaves a device-only byte table [max_kf][stride] of keys[i].octave, for the consumer that reads one octave per observation it meets
+//           (rumi_keyframe_culling_resident): the key-points of 140 key-frames of 2000 features are 7.8 MB, their octaves 280 KB, and that
+//           consumer's walks are latency-bound.  Filled from the arena by k_covis_octaves when that consumer flushes, for the slots whose
+//           features changed since; the stride is the power of two that holds the longest key-frame seen (a longer one rebuilds the table).
 //   staging rumi_covis_set_keyframe_features validates, places the block (host arithmetic only) and writes it into the staging block; the next
 //           consumer sends the staging block with one copy per run of blocks that are neighbours in both places (one key-frame, or any number
 //           appended at the tail: one copy).  The staging block is empty afterwards.
@@ -16,6 +20,42 @@ namespace {
 
 constexpr int64_t kFeatDefaultCap = 32ll << 20;
 constexpr int64_t kFeatLimit = 1ll << 38;              // far above any device; keeps the doubling below 2^63
+
+// Slot `slot0 + blockIdx.y` of the octave table, from its key-points where they lie.  One slot (slot0 = the slot, gridDim.y = 1) or every slot
+// below gridDim.y; a slot without features is left alone.
+__global__ __launch_bounds__(256) void k_covis_octaves(const int32_t *featTab, const uint8_t *feat, uint8_t *oct, int stride, int slot0) {
+    const int s = slot0 + (int)blockIdx.y, i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const int32_t *T = featTab + s * FTW;
+    const long long keys = *reinterpret_cast<const long long *>(T);
+    if (keys < 0 || i >= T[2] || i >= stride) return;
+    oct[(size_t)s * stride + i] = (uint8_t)reinterpret_cast<const RumiKeyPoint *>(feat + keys)[i].octave;
+}
+
+// Brings the octave table up to date with the arena and featTab on the device (both flushed before): the pending slots one launch each,
+// or every slot in one launch when there are many or the table is new.
+int oct_flush(RumiCovis *h) {
+    FeatureStore &F = h->feat;
+    int stride = 256;
+    while (stride < F.maxN) stride *= 2;
+    bool all = F.octPending.size() > 8;
+    if (!F.oct.p || stride > F.octStride) {
+        const size_t bytes = (size_t)h->maxKf * stride;
+        const int rc = F.oct.reserve(bytes, bytes);
+        if (rc != RUMI_OK) return rc;
+        F.octStride = stride;
+        all = true;
+    }
+    if (F.arena.p && h->hiSlot > 0) {
+        const int gx = (F.octStride + 255) / 256;
+        if (all) hipLaunchKernelGGL(k_covis_octaves, dim3(gx, h->hiSlot), dim3(256), 0, nullptr, h->dFeatTab.p, F.arena.p, F.oct.p, F.octStride, 0);
+        else
+            for (int32_t s : F.octPending)
+                hipLaunchKernelGGL(k_covis_octaves, dim3(gx, 1), dim3(256), 0, nullptr, h->dFeatTab.p, F.arena.p, F.oct.p, F.octStride, s);
+        HIP_TRY(hipGetLastError());
+    }
+    F.octPending.clear();
+    return RUMI_OK;
+}
 
 // The record of a validated key-frame; false when the block would pass 2 GiB (the record's 32-bit offsets).
 bool feat_layout(const RumiFrameFeatures &f, const RumiFeatureVector &v, const float *K4, CovisFeatRec *r) {
@@ -76,6 +116,16 @@ int feat_stage_reserve(RumiCovis *h, size_t need, bool pinned) {
     F.release_stage();
     F.stage = p; F.stageCap = cap; F.stagePinned = pinned;
     return RUMI_OK;
+}
+
+// The slot's record of featTab follows its place in the arena.
+void feat_tab_set(RumiCovis *h, int32_t slot) {
+    const FeatPlace &P = h->feat.place[slot];
+    const int64_t keys = P.off < 0 ? -1 : P.off + (int64_t)P.rec.keys;
+    int32_t *T = h->featTab.data() + (size_t)slot * FTW;
+    std::memcpy(T, &keys, 8);
+    T[2] = P.off < 0 ? 0 : P.rec.n;
+    note(h, T_FEAT, (int64_t)slot * FTW, FTW);
 }
 
 void feat_remove(FeatureStore &F, int32_t slot) {
@@ -167,6 +217,9 @@ extern "C" int rumi_covis_set_keyframe_features(RumiCovis *h, int32_t slot, cons
     }
     F.staged.push_back({slot, P.stageOff});
     F.stageUsed += rec.bytes;
+    F.maxN = std::max(F.maxN, rec.n);
+    F.octPending.push_back(slot);
+    feat_tab_set(h, slot);
     return RUMI_OK;
 }
 
@@ -175,7 +228,7 @@ extern "C" int rumi_covis_drop_keyframe_features(RumiCovis *h, int32_t n, const 
     for (int i = 0; i < n; i++)
         if (slots[i] < 0 || slots[i] >= h->maxKf) { g_lastError = "rumi_covis_drop_keyframe_features: a slot outside 0..max_kf-1"; return RUMI_E_INVALID; }
     if (!h->feat.place.empty())
-        for (int i = 0; i < n; i++) feat_remove(h->feat, slots[i]);
+        for (int i = 0; i < n; i++) { feat_remove(h->feat, slots[i]); feat_tab_set(h, slots[i]); }
     return RUMI_OK;
 }
 
@@ -224,5 +277,36 @@ int rumi::covis_features_flush(RumiCovis *h, CovisFeatureView *view) {
     uint8_t *unused = nullptr;
     if ((rc = flush(h, nullptr, 0, &unused)) != RUMI_OK || (rc = feat_flush(h)) != RUMI_OK) return rc;
     *view = CovisFeatureView{h->dArena.p, h->dPt.p, h->dAttr.p, h->feat.arena.p};
+    return RUMI_OK;
+}
+
+void rumi::covis_cull_slot(const RumiCovis *h, int32_t slot, CovisCullSlot *out) {
+    *out = CovisCullSlot{0, 0, -1, 0, 0};
+    if (!is_live(h, slot)) return;
+    const int32_t *K = h->kf.data() + (size_t)slot * KFW;
+    const FeatureStore &F = h->feat;
+    *out = CovisCullSlot{1, K[K_FLAGS] & 1, F.place.empty() || F.place[slot].off < 0 ? -1 : F.place[slot].rec.n, K[K_MPOFF], K[K_MPLEN]};
+}
+
+void rumi::covis_cull_row_points(const RumiCovis *h, int32_t mpOff, int32_t mpLen, int32_t *without, int32_t *longest) {
+    const int32_t *row = h->arena.data() + mpOff;
+    int32_t w = 0, l = 0;
+    for (int i = 0; i < mpLen; i++) {
+        if (row[i] < 0) continue;
+        const int32_t *P = h->pt.data() + (size_t)row[i] * PTW;
+        w += !(P[2] & kCovisPointHasObsFeatures);
+        l = std::max(l, P[1]);
+    }
+    *without = w; *longest = l;
+}
+
+int rumi::covis_cull_flush(RumiCovis *h, int wantDevice, const char *entry, CovisCullView *view) {
+    if (!h->dev.bound && h->dev.device < 0) h->dev.device = wantDevice;          // a store without a device takes the consumer's
+    int rc = bind_device(h);
+    if (rc != RUMI_OK) return rc;
+    if (h->dev.device != wantDevice) { g_lastError = std::string(entry) + ": the handle and the store are on different devices"; return RUMI_E_INVALID; }
+    uint8_t *unused = nullptr;
+    if ((rc = flush(h, nullptr, 0, &unused)) != RUMI_OK || (rc = feat_flush(h)) != RUMI_OK || (rc = oct_flush(h)) != RUMI_OK) return rc;
+    *view = CovisCullView{h->dKf.p, h->dPt.p, h->dArena.p, h->dFeatTab.p, h->feat.oct.p, h->feat.octStride, h->maxKf, h->maxPts, h->dev.device};
     return RUMI_OK;
 }

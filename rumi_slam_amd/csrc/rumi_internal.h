@@ -10,8 +10,12 @@ typedef struct RumiCovis RumiCovis;
 namespace rumi {
 
 // ---- the covisibility store (covis.hip) as the tracker's rumi_track_local_map drives it (track.hip, track_local_map.inc) ----
-constexpr int kCovisPointWords = 4;    // pt record: observer row (offset, length), flags (bit 0 bad), has attributes
+constexpr int kCovisPointWords = 4;    // pt record: observer row (offset, length), flags (bit 0 bad, bit 1 has observation features), has attributes
 constexpr int kCovisAttrWords = 16;    // attr record: position 3, normal 3, min distance, max distance (f32), descriptor 8 words
+constexpr int kCovisPointHasObsFeatures = 2;           // in the flags word
+constexpr int kCovisObsSlotBits = 13, kCovisObsSlotMask = (1 << kCovisObsSlotBits) - 1;   // an observer entry: slot | feature << 13
+constexpr int kCovisKfWords = 20, kCovisKfMpOff = 0, kCovisKfMpLen = 1;                   // kf record: where its mp row lies in the row arena
+constexpr int kCovisFeatTabWords = 4;  // featTab record: byte offset of the slot's key-points in the feature arena (64-bit, -1: none), feature count, -
 // The discarded outliers of the previous Tracking function: ids (distinct), and optionally what an earlier frame left in them.
 struct CovisDiscarded { int n; const int32_t *ids; const uint8_t *inView; const float *proj5; };
 // Where the store's tables and the lists of the local-map kernels lie on the device after covis_local_map_launch.
@@ -55,6 +59,22 @@ struct CovisFeatureView {
 int covis_features_check(RumiCovis *c, int n, const int32_t *slots, int wantDevice, const char *entry, CovisSlotFeatures *info);
 // Sends the staged edits and the staged features; where the tables lie afterwards.  Enqueues on the null stream, does not synchronise.
 int covis_features_flush(RumiCovis *c, CovisFeatureView *view);
+
+// ---- the store as rumi_keyframe_culling_resident reads it (culling.hip) ----
+struct CovisCullView {
+    const int32_t *kf, *pt, *rows, *featTab;   // [max_kf][kCovisKfWords], [max_points][kCovisPointWords], the row arena, [max_kf][kCovisFeatTabWords]
+    const uint8_t *oct;                        // [max_kf][octStride] keys[i].octave of every slot that holds features
+    int octStride;
+    int maxKf, maxPoints, device;
+};
+// Host only, from the store's mirror: is the slot live, its bad bit, its feature count (-1: no features), its mp row.
+struct CovisCullSlot { int32_t live, bad, nFeat, mpOff, mpLen; };
+void covis_cull_slot(const RumiCovis *c, int32_t slot, CovisCullSlot *out);
+// Host only: the points of the row [mpOff, mpOff + mpLen): how many lack observation features, the longest observer row among them.
+void covis_cull_row_points(const RumiCovis *c, int32_t mpOff, int32_t mpLen, int32_t *without, int32_t *longest);
+// Binds the store (wantDevice as above), sends the staged edits and features, brings the octave table up to date; where the tables lie.
+// Does not synchronise.
+int covis_cull_flush(RumiCovis *c, int wantDevice, const char *entry, CovisCullView *view);
 
 // Correspondences the LDS instantiation of k_pose_opt holds (opt.hip).  The tracker (track.hip) launches ONLY that instantiation when it knows a
 // frame cannot have more (nfeatures 1000 + the extractor's slack of 96 fits), so both files take the number from here.

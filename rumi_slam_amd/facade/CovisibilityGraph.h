@@ -17,11 +17,14 @@
 //                             rumi_facade::TrackLocalMapResident (TrackingStep.h) builds its point table from on the device.  MarkDirty(p)
 //                             notes a point whose SetWorldPos / UpdateNormalAndDepth / ComputeDistinctiveDescriptors has run (any thread's
 //                             caller serialises, as for Sync); FlushDirty() stages the noted points, once each, before the frame's query.
+//   Sync(MapPoint*)           stages the feature index of every observation with its observer (rumi_covis_set_point_observations), which is
+//                             what rumi::LocalMappingStep::KeyFrameCullingResident reads an observer's octave through.
 // Errors follow rumi_status.h: reported, never thrown; the member returns without having written anything.
 #pragma once
 #include <cstdint>
 #include <map>
 #include <set>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -290,16 +293,22 @@ template <class KeyFrameT, class MapPointT> class CovisibilityGraph {
     template <class List> int sync_points(const List &list) {
         if (!h_) return RUMI_E_INVALID;
         std::vector<KeyFrameT *> newKfs;
-        std::vector<int32_t> ids, off{0}, obs;
+        std::vector<int32_t> ids, off{0}, obs, feat;
         std::vector<uint8_t> bad;
         std::set<MapPointT *> in;
+        bool leftOnly = true;                                                            // every observation has a left index the store can keep
         for (MapPointT *p : list) {
             if (!p || !in.insert(p).second) continue;
             auto it = id_.find(p);
             if (it == id_.end()) { it = id_.emplace(p, (int32_t)pts_.size()).first; pts_.push_back(p); }
             ids.push_back(it->second);
             bad.push_back(p->isBad() ? 1 : 0);
-            for (const auto &o : p->GetObservations()) obs.push_back(slot_of(o.first, newKfs));
+            for (const auto &o : p->GetObservations()) {
+                obs.push_back(slot_of(o.first, newKfs));
+                const int left = std::get<0>(o.second);                                  // the feature index KeyFrameCullingResident reads the octave through
+                feat.push_back(left);
+                leftOnly = leftOnly && left >= 0 && left < RUMI_COVIS_MAX_FEATURES;
+            }
             off.push_back((int32_t)obs.size());
         }
         if (ids.empty()) return RUMI_OK;
@@ -308,7 +317,10 @@ template <class KeyFrameT, class MapPointT> class CovisibilityGraph {
             for (KeyFrameT *k : newKfs) { kfs_.pop_back(); slot_.erase(k); }             // sync_keyframes assigns the same slots again
             if ((rc = sync_keyframes(newKfs)) != RUMI_OK) return rc;
         }
-        rc = rumi_covis_set_points(h_, (int32_t)ids.size(), ids.data(), bad.data(), off.data(), obs.data());
+        // a right-only (stereo) observation has no left index: those points go without observation features, and the resident culling,
+        // which is monocular, refuses a call that reads one of them
+        rc = leftOnly ? rumi_covis_set_point_observations(h_, (int32_t)ids.size(), ids.data(), bad.data(), off.data(), obs.data(), feat.data())
+                      : rumi_covis_set_points(h_, (int32_t)ids.size(), ids.data(), bad.data(), off.data(), obs.data());
         if (rc != RUMI_OK) rumi_facade::report("CovisibilityGraph::Sync(MapPoint)", rc);
         return rc;
     }

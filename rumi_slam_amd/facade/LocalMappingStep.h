@@ -13,6 +13,8 @@
 //     step.KeyFrameCulling(mpCurrentKeyFrame, mbInertial, mbMonocular, mbAbortBA);
 //     step.CloudKeyFrameCulling(mpCurrentKeyFrame, mbInertial, mbMonocular, mbAbortBA);
 // one device call judges the whole covisible list (rumi_keyframe_culling); SetBadFlag() is then applied in the returned order.
+// With a CovisibilityGraph that holds the map, step.KeyFrameCullingResident(graph, ...) / CloudKeyFrameCullingResident(graph, ...) send the
+// candidates' slots instead of the neighbourhood's tables (rumi_keyframe_culling_resident).
 #pragma once
 #include <map>
 #include <tuple>
@@ -181,6 +183,18 @@ public:
         return culling(pCurrentKF, bInertial, bMonocular, bAbortBA, true);
     }
 
+    // The same two members over a CovisibilityGraph (CovisibilityGraph.h) that holds the map: the candidates travel as slots with their three
+    // flags, everything else is read where it lies on the device (rumi_keyframe_culling_resident).  The graph must be current: graph.Sync of
+    // the key-frames and points the mutators touched, graph.SyncFeatures of every key-frame that observes a point of a candidate.  SetBadFlag()
+    // is applied in the returned order; its Sync hooks stage the edits for the next query.  Refuses what the members above
+    // refuse, and a candidate the graph has never seen: nothing is staged or uploaded on the caller's behalf.  Returns as above.
+    template <class GraphT, class KeyFrameT> int KeyFrameCullingResident(GraphT &graph, KeyFrameT *pCurrentKF, bool bInertial, bool bMonocular, bool bAbortBA) {
+        return culling_resident(graph, pCurrentKF, bInertial, bMonocular, bAbortBA, false);
+    }
+    template <class GraphT, class KeyFrameT> int CloudKeyFrameCullingResident(GraphT &graph, KeyFrameT *pCurrentKF, bool bInertial, bool bMonocular, bool bAbortBA) {
+        return culling_resident(graph, pCurrentKF, bInertial, bMonocular, bAbortBA, true);
+    }
+
 protected:
     // One culling handle per calling thread (handles are not re-entrant), destroyed with its blocks when the thread ends.
     struct CullHandle {
@@ -285,6 +299,50 @@ protected:
                          rumi_keyframe_culling(h, table.data(), (int32_t)table.size(), cand.data(), nc, pts.data(), (int32_t)pts.size(), obsKf.data(),
                                                obsFeature.data(), (int32_t)obsKf.size(), flags, status.data(), nMPs.data(), nRedundant.data(),
                                                culled.data(), &nCulled)) != RUMI_OK)
+            return -1;
+        for (int c = 0; c < nc; c++)                                            // :1072, in the loop's order; a not_erase key-frame only gets mbToBeErased
+            if (status[c] == RUMI_CULL_CULLED || status[c] == RUMI_CULL_TO_BE_ERASED) vpLocalKeyFrames[c]->SetBadFlag();
+        return nCulled;
+    }
+
+    template <class GraphT, class KeyFrameT>
+    int culling_resident(GraphT &graph, KeyFrameT *pCurrentKF, bool bInertial, bool bMonocular, bool bAbortBA, bool cloudVariant) {
+        static const char *where = "LocalMappingStep::KeyFrameCullingResident";
+        if (bInertial || !bMonocular) {
+            rumi_facade::report(where, RUMI_E_INVALID, "mbInertial or a non-monocular sensor: only the non-inertial monocular loop is built; no key-frame was culled");
+            return -1;
+        }
+        if (!graph.ok()) { rumi_facade::report(where, RUMI_E_INVALID, "no store; no key-frame was culled"); return -1; }
+        pCurrentKF->UpdateBestCovisibles();                                     // :959
+        const auto vpLocalKeyFrames = pCurrentKF->GetVectorCovisibleKeyFrames();   // :960
+        const int nc = (int)vpLocalKeyFrames.size();
+        std::vector<RumiCullCandidate> cand(nc);
+        for (int c = 0; c < nc; c++) {
+            auto pKF = vpLocalKeyFrames[c];
+            if (pKF->NLeft != -1) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a key-frame with NLeft != -1: only the monocular loop is built; no key-frame was culled");
+                return -1;
+            }
+            const int slot = graph.SlotOf(pKF);
+            if (slot < 0) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a candidate the graph has never seen (graph.Sync, graph.SyncFeatures); nothing was uploaded, no key-frame was culled");
+                return -1;
+            }
+            cand[c].slot = slot;
+            cand[c].is_init = pKF->mnId == pKF->GetMap()->GetInitKFid();
+            cand[c].not_erase = pKF->GetNotErase();
+            cand[c].is_cloud = pKF->isCloud();
+            cand[c].pad_ = 0;
+        }
+        if (nc == 0) return 0;
+        std::vector<int32_t> status(nc), nMPs(nc), nRedundant(nc), culled(nc);
+        int32_t nCulled = 0;
+        RumiCull *h = cull_handle();
+        if (!h) return -1;
+        const int flags = (cloudVariant ? RUMI_CULL_CLOUD : 0) | (bAbortBA ? RUMI_CULL_ABORT_BA : 0);
+        if (RUMI_GUARDED("LocalMappingStep / rumi_keyframe_culling_resident", &rumi_facade::no_growth,
+                         rumi_keyframe_culling_resident(h, graph.handle(), cand.data(), nc, flags, status.data(), nMPs.data(), nRedundant.data(),
+                                                        culled.data(), &nCulled)) != RUMI_OK)
             return -1;
         for (int c = 0; c < nc; c++)                                            // :1072, in the loop's order; a not_erase key-frame only gets mbToBeErased
             if (status[c] == RUMI_CULL_CULLED || status[c] == RUMI_CULL_TO_BE_ERASED) vpLocalKeyFrames[c]->SetBadFlag();

@@ -45,6 +45,7 @@ def _lib():
     L.rumi_cull_destroy.restype = None
     L.rumi_keyframe_culling.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.rumi_cull_stage_ms.argtypes = [vp, vp]
+    L.rumi_keyframe_culling_resident.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L._mapping_ready = True
     return L
 
@@ -356,6 +357,55 @@ class KeyFrameCuller:
     def status(self, batch, flags, out):
         """The raw status of one call (outputs in ``out``)."""
         return self._lib.rumi_keyframe_culling(self._h, *batch.args(flags, out))
+
+
+    def status_resident(self, store, candidates, flags, out):
+        """The raw status of one rumi_keyframe_culling_resident call (outputs in ``out``)."""
+        return cull_resident_status(self, store, candidates, flags, out)
+
+
+CULL_CANDIDATE_DTYPE = np.dtype([("slot", "<i4"), ("is_init", "u1"), ("not_erase", "u1"), ("is_cloud", "u1"), ("pad_", "u1")])
+assert CULL_CANDIDATE_DTYPE.itemsize == 8
+
+
+def cull_candidates(candidates):
+    """(slot, is_init, not_erase, is_cloud) tuples, or an array of CULL_CANDIDATE_DTYPE -> the records of one call."""
+    if isinstance(candidates, np.ndarray) and candidates.dtype == CULL_CANDIDATE_DTYPE:
+        return np.ascontiguousarray(candidates)
+    rec = np.zeros(len(candidates), CULL_CANDIDATE_DTYPE)
+    for i, (slot, init, not_erase, cloud) in enumerate(candidates):
+        rec[i] = (int(slot), int(bool(init)), int(bool(not_erase)), int(bool(cloud)), 0)
+    return rec
+
+
+def cull_outputs(n_cand, fill=0):
+    """Fresh output arrays of a culling call over n_cand candidates, every byte ``fill``."""
+    out = {}
+    for k, m in (("status", max(n_cand, 1)), ("n_mps", max(n_cand, 1)), ("n_redundant", max(n_cand, 1)), ("culled", max(n_cand, 1)), ("n_culled", 1)):
+        a = np.empty(m, np.int32)
+        a.view(np.uint8).fill(fill)
+        out[k] = a
+    return out
+
+
+def cull_resident_status(cull, store, candidates, flags, out):
+    """The raw call; ``cull`` a KeyFrameCuller or None, ``store`` a covis.Covisibility or None (a missing handle is the library's to refuse)."""
+    rec = cull_candidates(candidates)
+    h = cull._h if cull is not None else None
+    s = store._h if store is not None else None
+    return _lib().rumi_keyframe_culling_resident(h, s, capi.ptr(rec) if len(rec) else None, len(rec), int(flags), capi.ptr(out["status"]),
+                                                 capi.ptr(out["n_mps"]), capi.ptr(out["n_redundant"]), capi.ptr(out["culled"]), capi.ptr(out["n_culled"]))
+
+
+def KeyFrameCullingResident(cull, store, candidates, flags=0):
+    """KeyFrameCulling (flags & CULL_CLOUD: CloudKeyFrameCulling) over the key-frames ``candidates`` names by slot in ``store`` (a
+    covis.Covisibility whose points were set through set_point_observations and whose key-frames hold features): only the store's staged
+    edits and the candidate records travel.  Returns what keyframe_culling returns."""
+    rec = cull_candidates(candidates)
+    out = cull_outputs(len(rec))
+    capi.check(cull_resident_status(cull, store, rec, flags, out))
+    n = int(out["n_culled"][0])
+    return dict(status=out["status"][:len(rec)], n_mps=out["n_mps"][:len(rec)], n_redundant=out["n_redundant"][:len(rec)], culled=out["culled"][:n])
 
 
 _culler = None

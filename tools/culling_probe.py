@@ -4,7 +4,10 @@ member, which copies a std::map per point.  Two workloads (tests/culling_scene.p
 observations a point; (b) 100 candidates x 2000 features, 4..40 observations, a handful of culls.  The C entries are timed with their
 arguments already marshalled; warm-up, then the median of repeated calls.  The outputs are asserted equal to the oracle's before a time is
 reported.
-    python tools/culling_probe.py [--reps 30] [--only device] [--out FILE]"""
+--resident times rumi_keyframe_culling_resident on the same two maps, loaded once into a covisibility store (tests/culling_resident_scene.py),
+next to the block entry in the same process: on a steady state with nothing staged, and with the edits of one culled key-frame (its record,
+its row, the observer rows of its points) staged before every call.  Each line carries the three-way split of both entries.
+    python tools/culling_probe.py [--reps 30] [--only device] [--resident] [--workloads ab] [--out FILE]"""
 import argparse
 import json
 import os
@@ -60,10 +63,75 @@ def walk_stats(b):
             "walks_to_the_end": round(full / max(walks, 1), 3)}
 
 
+def resident_times(r, b, block_out, reps):
+    """The resident entry on the map of batch ``b``: outputs equal to the block entry's (already equal to the oracle's), then the medians."""
+    import culling_resident_scene as rs
+    from culling_scene import same_bytes
+    from rumi_slam_amd import capi
+    from rumi_slam_amd.covis import Covisibility
+    from rumi_slam_amd.mapping import CULL_CULLED, cull_candidates, cull_outputs
+    m = rs.MapMirror.from_batch(b)
+    store = Covisibility(m.n_kf, m.n_pts + 8)
+    t0 = time.perf_counter()
+    m.load(store)
+    load_ms = (time.perf_counter() - t0) * 1e3
+    cand = b.cand[:b.n_cand].tolist()
+    rec = cull_candidates(m.candidates(cand))
+    out = cull_outputs(len(rec))
+    args = (r._h, store._h, capi.ptr(rec), len(rec), 0, capi.ptr(out["status"]), capi.ptr(out["n_mps"]), capi.ptr(out["n_redundant"]),
+            capi.ptr(out["culled"]), capi.ptr(out["n_culled"]))
+
+    def resident_call():
+        capi.check(r._lib.rumi_keyframe_culling_resident(*args))
+    resident_call()
+    first_upload = store.stats()["last_upload_bytes"] + store.feature_stats()["last_upload_bytes"]
+    assert same_bytes(out, block_out) == [], same_bytes(out, block_out)
+
+    def split(call, before=lambda: None):
+        total, stages = [], []
+        for i in range(reps + 5):
+            before()
+            t0 = time.perf_counter()
+            call()
+            dt = (time.perf_counter() - t0) * 1e3
+            if i >= 5:
+                total.append(dt)
+                stages.append(r.stage_ms())
+        return [round(float(x), 4) for x in (np.median(total), np.min(total), *np.median(np.array(stages), axis=0))]
+
+    res = {"resident_equal_to_block": True, "store_load_ms": round(load_ms, 2), "first_upload_bytes": int(first_upload)}
+    res["resident_steady_ms"], res["resident_steady_min_ms"], *res["resident_steady_split_ms"] = split(resident_call)
+    res["resident_steady_upload_bytes"] = store.stats()["last_upload_bytes"]
+    # what SetBadFlag() of one culled key-frame touches, staged again with the values the map holds: the same bytes travel, the state stays
+    hit = np.nonzero(out["status"][:len(cand)] == CULL_CULLED)[0]
+    k = cand[int(hit[0]) if len(hit) else 0]
+    pts = sorted({int(p) for p in m.mp[k] if p >= 0})
+    stage_ms = []
+
+    def stage():
+        t0 = time.perf_counter()
+        m.set_keyframes(store, [k])
+        m.set_points(store, pts)
+        stage_ms.append((time.perf_counter() - t0) * 1e3)
+    res["resident_staged_ms"], res["resident_staged_min_ms"], *res["resident_staged_split_ms"] = split(resident_call, stage)
+    res["resident_staged_upload_bytes"] = store.stats()["last_upload_bytes"]
+    res["staged_points"], res["staging_python_ms"] = len(pts), round(float(np.median(stage_ms)), 4)
+    assert same_bytes(out, block_out) == []
+    block_args = b.args(0, block_out)
+
+    def block_call():
+        capi.check(r._lib.rumi_keyframe_culling(r._h, *block_args))
+    res["block_again_ms"], res["block_again_min_ms"], *res["block_again_split_ms"] = split(block_call)
+    store.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--only", default="", help="'device': time the device call alone (for a kernel trace)")
+    ap.add_argument("--resident", action="store_true", help="also time rumi_keyframe_culling_resident on the same maps")
+    ap.add_argument("--workloads", default="ab")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch  # noqa: F401
@@ -74,6 +142,8 @@ def main():
     r = KeyFrameCuller()
     lines = []
     for name, (n_cand, n_feat, obs_range, seed) in WORKLOADS.items():
+        if name not in a.workloads:
+            continue
         b = probe_batch(n_cand, n_feat, obs_range, seed)
         out, ref = b.outputs(), b.outputs()
         args_dev, args_ref = b.args(0, out), b.args(0, ref) + (None,) * 6
@@ -100,6 +170,8 @@ def main():
         if a.only != "device":
             res["oracle_loop_ms"], res["oracle_loop_min_ms"] = [round(x, 4) for x in median_ms(oracle_loop, a.reps, 2)]
             res["speedup_vs_oracle_loop"] = round(res["oracle_loop_ms"] / res["device_call_ms"], 2)
+        if a.resident:
+            res.update(resident_times(r, b, out, a.reps))
         lines.append(json.dumps(res))
         print(lines[-1], flush=True)
     r.close()
