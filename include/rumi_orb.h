@@ -191,6 +191,13 @@ int rumi_orb_stage_keypoints(RumiOrb *h, int32_t frame, int32_t level, int32_t s
 int rumi_orb_set_profiling(RumiOrb *h, int32_t on);
 int rumi_orb_stage_ms(RumiOrb *h, float ms[8]);
 
+/* The batch quadtree of the batched calls since the handle was last idle (one call, for a caller that waits for each), as of the last
+ * rumi_orb_sync: trees[0] = (frame, level) trees finished from the candidate histogram alone, trees[1] = trees that outgrew the count
+ * tables and were redone from their keys.  Both 0 for calls of so few frames that they keep their keys in registers.  The counters reach the
+ * host with a batched call's error word: the one-frame host entry (rumi_orb_extract, rumi_orb_stream_push) does not fetch them, so trees it
+ * runs through the batch kernels (only with RUMI_OCT_REGS=0) are counted into the next batched call's figure. */
+int rumi_orb_octree_stats(RumiOrb *h, int32_t trees[2]);
+
 #ifdef __cplusplus
 }
 #endif

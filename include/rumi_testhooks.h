@@ -23,6 +23,19 @@ int rumi_hook_std_sort(uint32_t *keys, uint16_t *ids, int32_t n);
 int rumi_hook_quadtree(const uint32_t *cand, int32_t n, int32_t minX, int32_t maxX, int32_t minY, int32_t maxY,
                        int32_t N, int32_t *out_idx, int32_t cap, int32_t *n_out);
 
+/* The coordinate tables of the batch quadtree (orb_octree.h: the per-coordinate halves of a key's depth-D path, built on the host by the rule the
+ * kernels share) for `level` of a w x h frame: info[6] = {W, H of the level's key-point area, roots, table depth D, cells of depth D (0: the
+ * level has no tables), features wanted on the level}; bins = the x half (W + 1 entries: root << 2 D | bit 2 (D - 1 - d) = right side taken
+ * at depth d), then the y half (H + 1 entries: bit 2 (D - 1 - d) + 1 = lower side); n_out = entries (RUMI_E_CAPACITY if > cap). */
+int rumi_hook_octree_bins(int32_t w, int32_t h, int32_t nfeatures, float scale, int32_t nlevels, int32_t level, int32_t *info, uint16_t *bins,
+                          int32_t cap, int32_t *n_out);
+
+/* k_compact's LDS for the batch quadtree of a w x h geometry: info[4] = {FAST cells of a frame (the kernel's prefix has one dword more),
+ * depth-D cells of a frame's histogram row (every level's count rounded up to even), bytes of the kernel's count table in LDS -- 0 when
+ * prefix + table + static LDS would pass the 64 KiB a launch gets without an opt-in: such a geometry keeps the one-launch quadtree --, the
+ * bound on the kernel's static LDS the rule uses}. */
+int rumi_hook_compact_hist_lds(int32_t w, int32_t h, int32_t nfeatures, float scale, int32_t nlevels, int32_t *info);
+
 float rumi_hook_sinf(float x);           /* restated glibc sinf  (orb_math.h) */
 float rumi_hook_cosf(float x);           /* restated glibc cosf  (orb_math.h) */
 float rumi_hook_fast_atan2(float y, float x);   /* cv::fastAtan2, degrees */

@@ -42,7 +42,7 @@ _lib = None
 ORB_SYMBOLS = ["rumi_last_error", "rumi_device_count", "rumi_orb_create", "rumi_orb_destroy", "rumi_orb_tables",
                "rumi_orb_extract", "rumi_orb_image_buffer", "rumi_orb_extract_batch_device", "rumi_orb_extract_batch_device_async", "rumi_orb_sync", "rumi_orb_set_resident_queue", "rumi_orb_wait_event", "rumi_orb_extract_batch_records_async", "rumi_orb_extract_batch_host", "rumi_orb_extract_batch_host_records",
                "rumi_orb_pyramid_level",
-               "rumi_orb_stage_keypoints", "rumi_orb_set_profiling", "rumi_orb_stage_ms",
+               "rumi_orb_stage_keypoints", "rumi_orb_set_profiling", "rumi_orb_stage_ms", "rumi_orb_octree_stats",
                "rumi_orb_stream_create", "rumi_orb_stream_destroy", "rumi_orb_stream_reset", "rumi_orb_stream_push", "rumi_orb_stream_resident"]
 
 
@@ -83,6 +83,7 @@ def lib():
     L.rumi_orb_set_resident_queue.argtypes = [vp, i32]
     L.rumi_orb_wait_event.argtypes = [vp, vp]
     L.rumi_orb_stage_ms.argtypes = [vp, vp]
+    L.rumi_orb_octree_stats.argtypes = [vp, vp]
     L.rumi_orb_stream_create.argtypes = [vp, C.POINTER(vp)]
     L.rumi_orb_stream_destroy.argtypes = [vp]
     L.rumi_orb_stream_destroy.restype = None
@@ -212,7 +213,7 @@ def covis_lib():
 
 HOOK_SYMBOLS = ["rumi_hook_sort_like_std", "rumi_hook_sort_device", "rumi_hook_std_sort", "rumi_hook_quadtree", "rumi_hook_sinf", "rumi_hook_cosf",
                 "rumi_hook_fast_atan2", "rumi_hook_cv_round", "rumi_hook_magic_div", "rumi_hook_newpts_matches", "rumi_hook_lane_packing", "rumi_hook_disc_moments",
-                "rumi_hook_stream_plan", "rumi_hook_parse_hw_queues"]
+                "rumi_hook_stream_plan", "rumi_hook_parse_hw_queues", "rumi_hook_octree_bins", "rumi_hook_compact_hist_lds"]
 
 
 def hooks():
@@ -236,5 +237,7 @@ def hooks():
     L.rumi_hook_disc_moments.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.rumi_hook_stream_plan.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.rumi_hook_parse_hw_queues.argtypes = [C.c_char_p]
+    L.rumi_hook_octree_bins.argtypes = [i32, i32, i32, C.c_float, i32, i32, vp, vp, i32, C.POINTER(i32)]
+    L.rumi_hook_compact_hist_lds.argtypes = [i32, i32, i32, C.c_float, i32, vp]
     L._hooks_ready = True
     return L

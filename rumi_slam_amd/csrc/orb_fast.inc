@@ -485,10 +485,14 @@ __global__ __launch_bounds__(256) void k_fast_cells(const DevParams *__restrict_
 // ------------------------------------------------------------------------------------------------
 // 256 threads (a 1024-thread workgroup waits for a CU with sixteen free wave slots beside the other streams' kernels: 0.42 ms per 256-frame launch
 // in the pipelined step against 0.03 ms alone -- without costing the step anything measurable; one frame: 6.7 -> ~3 us)
+// hist != null (batches: the quadtree pipeline of orb_octree_kernel.hip): every candidate is also counted in the depth-D quadtree cell of its
+// level, hist[frame][level's cells], 16-bit counts two to a dword -- the table the quadtree kernel used to fill by a pass of its own over the
+// keys.  The cell comes from the host-built coordinate tables (bins).
 constexpr int kCompactThreads = 256;
 __global__ __launch_bounds__(kCompactThreads) void k_compact(const DevParams *__restrict__ P, const uint32_t *__restrict__ cellBuf,
                                                  const int32_t *__restrict__ cellCnt, uint32_t *__restrict__ cand,
-                                                 int32_t *__restrict__ levelStart, int32_t *__restrict__ errFlag) {
+                                                 int32_t *__restrict__ levelStart, int32_t *__restrict__ errFlag,
+                                                 uint32_t *__restrict__ hist, const uint16_t *__restrict__ bins) {
     extern __shared__ int sStart[];          // totalCells + 1 exclusive prefix
     __shared__ int part[kCompactThreads];
     const int tid = threadIdx.x, frame = blockIdx.x;
@@ -540,13 +544,62 @@ __global__ __launch_bounds__(kCompactThreads) void k_compact(const DevParams *__
     // lane has an independent load in flight instead of a wave walking its cells one round trip at a time
     const int nOut = min(sStart[nc], P->totalCand);
     const uint32_t *inBase = cellBuf + (long long)frame * nc * P->maxCellCand;
-    for (int j = blockIdx.y * kCompactThreads + tid; j < nOut; j += kCompactThreads * gridDim.y) {
-        int lo = 0, hi = nc;                       // invariant: sStart[lo] <= j < sStart[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (sStart[mid] <= j) lo = mid; else hi = mid;
+    if (!hist) {
+        for (int j = blockIdx.y * kCompactThreads + tid; j < nOut; j += kCompactThreads * gridDim.y) {
+            int lo = 0, hi = nc;                       // invariant: sStart[lo] <= j < sStart[hi]
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (sStart[mid] <= j) lo = mid; else hi = mid;
+            }
+            out[j] = inBase[(long long)lo * P->maxCellCand + (j - sStart[lo])];
         }
-        out[j] = inBase[(long long)lo * P->maxCellCand + (j - sStart[lo])];
+        return;
+    }
+    // ... and the count of the candidate's quadtree cell; whole waves walk the loop (wave_run_add looks at the neighbour lanes)
+    __shared__ int sLevCell[kMaxLevels];           // first FAST cell of the level
+    __shared__ int4 sLev[kMaxLevels];              // {its coordinate tables, its first entry in the frame's row (-1: none), W, H}
+    if (tid < P->nlevels) {
+        const DevLevel &L = P->lv[tid];
+        sLevCell[tid] = L.cellBase;
+        sLev[tid] = make_int4(L.octBin, L.octCells > 0 ? L.octCell : -1, L.maxBX - kBorder, L.maxBY - kBorder);
+    }
+    static_assert(sizeof(part) + sizeof(sLevCell) + sizeof(sLev) + 64 <= kCompactStaticLds, "oct_hist_lds_bytes sizes the launch with this bound");
+    // The workgroup counts into a table of its own in LDS (behind the cell prefix; oct_hist_lds_bytes: a geometry whose table does not fit has
+    // no pipeline) and adds what is not zero to the frame's row at the end -- the candidates of a FAST cell's row rarely fill a run, so
+    // counting straight into HBM / L2 was one atomic per candidate or two (measured: 106 us alone against 48).  A workgroup takes a
+    // CONTIGUOUS share of the candidates, so its counts fall into a share of the cells
+    const int nl = P->nlevels, hw = P->octCellStride / 2;
+    uint32_t *hf = hist + (size_t)frame * (size_t)hw;
+    uint32_t *sh = reinterpret_cast<uint32_t *>(sStart + nc + 1);
+    for (int i = tid; i < hw; i += kCompactThreads) sh[i] = 0u;
+    __syncthreads();
+    const int per = ((nOut + (int)gridDim.y - 1) / (int)gridDim.y + kCompactThreads - 1) / kCompactThreads * kCompactThreads;
+    const int jBeg = min(nOut, (int)blockIdx.y * per), jEnd = min(nOut, jBeg + per);
+    for (int j0 = jBeg; j0 < jEnd; j0 += kCompactThreads) {
+        const int j = j0 + tid;
+        int entry = -1;                            // the cell's entry in the frame's row: equal for equal (level, cell)
+        if (j < jEnd) {
+            int lo = 0, hi = nc;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (sStart[mid] <= j) lo = mid; else hi = mid;
+            }
+            const uint32_t ck = inBase[(long long)lo * P->maxCellCand + (j - sStart[lo])];
+            out[j] = ck;
+            int l = 0;
+            for (int k = 1; k < nl; k++) l += sLevCell[k] <= lo;
+            const int4 L = sLev[l];
+            if (L.y >= 0) {
+                const uint16_t *xbin = bins + L.x, *ybin = xbin + L.z + 1;
+                entry = L.y + ((int)xbin[min((int)(ck & 0xFFFu), L.z)] | (int)ybin[min((int)((ck >> 12) & 0xFFFu), L.w)]);
+            }
+        }
+        wave_run_add(entry, sh + ((entry < 0 ? 0 : entry) >> 1), 1u << (16 * (entry & 1)));
+    }
+    __syncthreads();
+    for (int i = tid; i < hw; i += kCompactThreads) {
+        const uint32_t w = sh[i];
+        if (w) atomicAdd(hf + i, w);
     }
 }
 // ---- launch wrappers (called from orb_schedule.inc) ----
@@ -587,9 +640,11 @@ void launch_fast(const DevParams *dP, const DevParams &hP, ImgSrc src, uint32_t 
 // element, so one workgroup per frame is ~40 us of latency whatever the batch)
 static int compactSlices(int nframes) { return nframes < 32 ? 32 : 8; }
 void launch_compact(const DevParams *dP, const DevParams &hP, const uint32_t *cellBuf, const int32_t *cellCnt,
-                    uint32_t *cand, int32_t *levelStart, int32_t *errFlag, int nframes, hipStream_t st) {
-    hipLaunchKernelGGL(k_compact, dim3(nframes, compactSlices(nframes)), dim3(kCompactThreads), (hP.totalCells + 1) * sizeof(int), st, dP, cellBuf, cellCnt,
-                       cand, levelStart, errFlag);
+                    uint32_t *cand, int32_t *levelStart, int32_t *errFlag, int nframes, hipStream_t st, uint32_t *hist, const uint16_t *bins) {
+    // with a histogram: the workgroup's own count table behind the prefix (640 x 480, 8 levels: 4 KB); set_geometry has checked that it fits
+    const size_t histBytes = hist ? (size_t)oct_hist_lds_bytes(hP.totalCells, hP.octCellStride) : 0;
+    hipLaunchKernelGGL(k_compact, dim3(nframes, compactSlices(nframes)), dim3(kCompactThreads), (hP.totalCells + 1) * sizeof(int) + histBytes, st, dP, cellBuf,
+                       cellCnt, cand, levelStart, errFlag, hist, bins);
 }
 
 }  // namespace rumi

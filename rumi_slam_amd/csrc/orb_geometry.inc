@@ -40,6 +40,25 @@ static void make_level_tables(const std::vector<LevelGeom> &g, DevParams &P, std
     }
 }
 
+// The batch quadtree's tables of a geometry (orb_octree.h): per level the coordinate halves of a key's depth-D path -- x half, then y half, by
+// the rule the kernels share (oct_coord_bin) -- and where the level's depth-D cells lie in a frame's histogram / rank row.  A level whose
+// aspect ratio gives no or too many roots has neither (its trees go to the kernel that reports that).
+static void make_octree_tables(DevParams &P, std::vector<uint16_t> &bins) {
+    bins.clear();
+    int cells = 0;
+    for (int l = 0; l < P.nlevels; l++) {
+        DevLevel &D = P.lv[l];
+        const int W = D.maxBX - kBorder, Hh = D.maxBY - kBorder;
+        const OctLevelTabs T = oct_level_tabs(W, Hh, D.nfeat);
+        D.octBin = (int)bins.size(); D.octCell = cells; D.octCells = T.cells;
+        if (T.cells == 0) continue;
+        bins.resize(bins.size() + (size_t)(W + 1 + Hh + 1));
+        oct_make_bins(W, Hh, T, bins.data() + D.octBin);
+        cells += oct_row_entries(T.cells);
+    }
+    P.octCellStride = cells;
+}
+
 // Step 2 of set_geometry: regions of the one-launch pyramid (k_pyramid_tiles): an even partition of the TOP level into tiles of about kPyrTX x kPyrTY pixels (16 x 8: 14.3 us for one 640 x 480 frame; 32 x 16: 19.4, 16 x 16: 16.5, 8 x 8: 15.1); going down, a tile's region of
 // level l - 1 is the hull of what its region of level l reads (first tap column .. second tap column, first .. second source row) and of its
 // share of an even partition of level l - 1 (every pixel of every level belongs to some tile); x ranges are widened to multiples of 4 (the
@@ -117,13 +136,19 @@ static int set_geometry(RumiOrb *h, int w, int hgt) {
     std::vector<RowTap> rowTab;
     make_level_tables(g, P, coef, rowTab);
     if ((int)coef.size() > h->capCoef) { g_lastError = "resize table capacity"; return RUMI_E_CAPACITY; }
+    std::vector<uint16_t> octBins;
+    make_octree_tables(P, octBins);
+    if ((int)octBins.size() > h->capOctBins) { g_lastError = "quadtree coordinate table capacity"; return RUMI_E_CAPACITY; }
+    // no room for this geometry's cell tables in the handle's arrays, or for k_compact's count table in LDS: its batches keep the one-launch quadtree
+    if (P.octCellStride > h->capOctCells || oct_hist_lds_bytes(P.totalCells, P.octCellStride) == 0) P.octCellStride = 0;
+    if (!octBins.empty()) HIP_TRY(hipMemcpy(h->dOctBins, octBins.data(), octBins.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->dP, &P, sizeof P, hipMemcpyHostToDevice));
     if ((int)rowTab.size() > h->capRowTab) { g_lastError = "resize row table capacity"; return RUMI_E_CAPACITY; }
     if (!coef.empty()) HIP_TRY(hipMemcpy(h->dCoef, coef.data(), coef.size() * sizeof(int16_t), hipMemcpyHostToDevice));
     if (!rowTab.empty()) HIP_TRY(hipMemcpy(h->dRowTab, rowTab.data(), rowTab.size() * sizeof(RowTap), hipMemcpyHostToDevice));
     if (const int rcT = build_pyramid_tiles(h, coef, rowTab); rcT != RUMI_OK) return rcT;
-    h->octLds = octree_lds_for(P);
-    if (h->octLds > 160 * 1024) { g_lastError = "nfeatures too large for the LDS-resident quadtree node pool"; return RUMI_E_INVALID; }
+    h->octLds = octree_lds_for(P, h->selLevelCap);
+    if (h->octLds.wide > 160 * 1024) { g_lastError = "nfeatures too large for the LDS-resident quadtree node pool"; return RUMI_E_INVALID; }
     h->gw = w; h->gh = hgt;
     return RUMI_OK;
 }

@@ -92,7 +92,16 @@ struct RumiOrb {
     uint32_t *dSelLevel = nullptr;   // kChunk frames x nlevels x selLevelCap: quadtree output per level
     int32_t *dSelLevelCnt = nullptr;
     int32_t *dErr = nullptr;         // device error word (bit 0/1/2/3: roots, node pool, level cap, selection cap; bit 4: FAST candidate capacity);
-                                     // sticky over the asynchronous calls since the last rumi_orb_sync
+                                     // sticky over the asynchronous calls since the last rumi_orb_sync.  Words 1, 2: the batch quadtree's
+                                     // cumulative {trees finished by k_octree_narrow, trees redone}; they travel to hErr with the error word
+    // batch quadtree pipeline (orb_device.h: OctNarrow): coordinate tables of the current geometry; per scratch frame the cell histogram and the
+    // cell -> rank table (capOctCells 16-bit entries each), per (frame, level) the list length, per slot range the redo list and its counters
+    uint16_t *dOctBins = nullptr; int capOctBins = 0, capOctCells = 0;
+    uint32_t *dOctHist = nullptr, *dOctRank = nullptr;
+    int32_t *dOctM = nullptr, *dOctRedo = nullptr, *dOctCtl = nullptr;
+    uint32_t octStatBase[2] = {0, 0};        // the (wrapping) counters when the handle was last idle
+    int32_t octStat[2] = {0, 0};             // the calls since, as of the last rumi_orb_sync
+    bool octDirty = false;                   // a call returned between launch_compact and launch_octree: histogram / counters are not zero
     // host-resident batches (rumi_orb_extract_batch_host): device landing arena, pinned staging slots, copy streams
     DevBuf<uint8_t> hostIn;
     static constexpr int kFeedSlots = 4, kFeedFrames = 64;
@@ -102,7 +111,7 @@ struct RumiOrb {
     bool pending = false;            // an asynchronous call has been enqueued and not yet waited for
     hipStream_t pendingStream = nullptr;
     int selLevelCap = 0;
-    size_t octLds = 0;
+    OctLdsSizes octLds{0, 0, 0};
     // pinned host words
     int32_t *hErr = nullptr;
     // host copies fetched lazily by the stage taps
@@ -150,13 +159,14 @@ struct RumiOrb {
 static void free_frame_arenas(RumiOrb *h) {
     auto drop = [](auto *&...p) { (((p ? (void)hipFree(p) : (void)0), p = nullptr), ...); };
     drop(h->dPyr, h->dBlur, h->dCellBuf, h->dCellCnt, h->dCand, h->dLevelStart, h->dSelPacked, h->dSelMeta, h->dSelTrig, h->dSelCount, h->dOwner, h->dSelLevel, h->dSelLevelCnt);
+    drop(h->dOctHist, h->dOctRank, h->dOctM, h->dOctRedo, h->dOctCtl);
 }
 
 extern "C" void rumi_orb_destroy(RumiOrb *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->pending) (void)hipStreamSynchronize(h->pendingStream);
-    void *dev[] = {h->dP, h->dCoef, h->dRowTab, h->dPyrTiles, h->dIn, h->dL0, h->dErr, h->dDiscVec};
+    void *dev[] = {h->dP, h->dCoef, h->dRowTab, h->dOctBins, h->dPyrTiles, h->dIn, h->dL0, h->dErr, h->dDiscVec};
     for (void *p : dev) if (p) (void)hipFree(p);
     free_frame_arenas(h);
     void *pin[] = {h->hErr};
@@ -177,6 +187,15 @@ extern "C" void rumi_orb_destroy(RumiOrb *h) {
     if (h->hOut1) (void)hipHostFree(h->hOut1);
     if (h->dOut1) (void)hipFree(h->dOut1);
     delete h;
+}
+
+// The state the batch quadtree pipeline keeps zero between launches: every frame's cell histogram and every slot range's redo counters.
+static int zero_octree_state(RumiOrb *h) {
+    const size_t C = (size_t)h->scratchFrames;
+    HIP_TRY(hipMemset(h->dOctHist, 0, std::max<size_t>(C * (h->capOctCells / 2), 1) * sizeof(uint32_t)));
+    HIP_TRY(hipMemset(h->dOctCtl, 0, std::max<size_t>(C * 4, 1) * sizeof(int32_t)));
+    h->octDirty = false;
+    return RUMI_OK;
 }
 
 // The per-frame device arrays: candidate / quadtree scratch for `scratch` frames, pyramid and blurred levels for `arena` frames.  Called by
@@ -200,8 +219,15 @@ static int alloc_frame_arenas(RumiOrb *h, size_t scratch, size_t arena) {
     TRY_A(dev_alloc(&h->dOwner, C * h->capCand));
     TRY_A(dev_alloc(&h->dSelLevel, C * h->cfg.nlevels * h->selLevelCap));
     TRY_A(dev_alloc(&h->dSelLevelCnt, C * h->cfg.nlevels));
+    TRY_A(dev_alloc(&h->dOctHist, C * (h->capOctCells / 2)));
+    TRY_A(dev_alloc(&h->dOctRank, C * (h->capOctCells / 2)));
+    TRY_A(dev_alloc(&h->dOctM, C * h->cfg.nlevels));
+    TRY_A(dev_alloc(&h->dOctRedo, C * h->cfg.nlevels));
+    TRY_A(dev_alloc(&h->dOctCtl, C * 4));
 #undef TRY_A
     h->scratchFrames = (int)scratch; h->arenaFrames = (int)arena;
+    // zeroed once: k_octree_narrow clears what it reads of the histogram, k_octree_redo's last workgroup its counters
+    if (const int rz = zero_octree_state(h); rz != RUMI_OK) { h->scratchFrames = 0; h->arenaFrames = 0; return rz; }
     return RUMI_OK;
 }
 
@@ -243,6 +269,13 @@ extern "C" int rumi_orb_create(const RumiOrbConfig *cfg, RumiOrb **out) {
     int maxN = 0;
     for (int l = 0; l < cfg->nlevels; l++) maxN = std::max(maxN, h->tab.featuresPerLevel[l]);
     h->selLevelCap = maxN + 4 * 16 + 8;
+    // batch quadtree tables: a level's coordinate tables are shorter than its width + height; twice the depth-D cells of the largest geometry
+    // (another aspect ratio has other root counts), at most 4096 per level -- a geometry that wants more keeps the one-launch kernel
+    for (int l = 0; l < cfg->nlevels; l++) {
+        h->capOctBins += g[l].w + g[l].h;
+        h->capOctCells += 2 * oct_level_tabs(g[l].maxBX - kBorder, g[l].maxBY - kBorder, h->tab.featuresPerLevel[l]).cells;
+    }
+    h->capOctCells = std::min(std::max(h->capOctCells, 512), 4096 * cfg->nlevels);
     // scratch arenas: frames of one pass, rounded up to a multiple of 12 so that 2, 3 or 4 equal slots hold ceil(frames / parts) each
     const size_t B = (size_t)cfg->max_batch, C = (size_t)scratch_frames(cfg->max_batch);
     int rc = RUMI_OK;
@@ -250,6 +283,7 @@ extern "C" int rumi_orb_create(const RumiOrbConfig *cfg, RumiOrb **out) {
     TRY_ALLOC(dev_alloc(&h->dP, 1));
     TRY_ALLOC(dev_alloc(&h->dCoef, (size_t)h->capCoef));
     TRY_ALLOC(dev_alloc(&h->dRowTab, (size_t)std::max(h->capRowTab, 1)));
+    TRY_ALLOC(dev_alloc(&h->dOctBins, (size_t)h->capOctBins));
     TRY_ALLOC(dev_alloc(&h->dIn, (size_t)((cfg->max_width + 3) & ~3) * cfg->max_height));
     TRY_ALLOC(alloc_frame_arenas(h, C, B));
     TRY_ALLOC(dev_alloc(&h->dOut1, (size_t)16 + (size_t)h->capSel * 60));
@@ -257,14 +291,16 @@ extern "C" int rumi_orb_create(const RumiOrbConfig *cfg, RumiOrb **out) {
         hipHostMalloc((void **)&h->hOut1, (size_t)16 + (size_t)h->capSel * 60, hipHostMallocDefault) != hipSuccess) {
         rumi_orb_destroy(h); g_lastError = "pinned staging"; return RUMI_E_NO_DEVICE;
     }
-    TRY_ALLOC(dev_alloc(&h->dErr, 1));
+    TRY_ALLOC(dev_alloc(&h->dErr, 4));
+    if (hipMemset(h->dErr, 0, 4 * sizeof(int32_t)) != hipSuccess) { rumi_orb_destroy(h); g_lastError = "error word"; return RUMI_E_NO_DEVICE; }
     {
         uint32_t vec[kDiscVecLanes * kDiscVecLaneDwords];
         make_disc_vectors(h->tab.umax.data(), vec);
         TRY_ALLOC(dev_alloc(&h->dDiscVec, sizeof vec / sizeof vec[0]));
         if (hipMemcpy(h->dDiscVec, vec, sizeof vec, hipMemcpyHostToDevice) != hipSuccess) { rumi_orb_destroy(h); g_lastError = "disc vectors"; return RUMI_E_NO_DEVICE; }
     }
-    TRY_ALLOC(pin_alloc(&h->hErr, 1));
+    TRY_ALLOC(pin_alloc(&h->hErr, 4));
+    std::memset(h->hErr, 0, 4 * sizeof(int32_t));
     if (hipHostGetDevicePointer((void **)&h->dhOut1, h->hOut1, 0) != hipSuccess || hipHostGetDevicePointer((void **)&h->dhErr, h->hErr, 0) != hipSuccess) {
         (void)hipGetLastError();
         h->dhOut1 = nullptr; h->dhErr = nullptr;            // (no device view of the pinned blocks: the copies stay)
@@ -342,12 +378,19 @@ extern "C" int rumi_orb_stage_ms(RumiOrb *h, float ms[8]) {
     return RUMI_OK;
 }
 
+extern "C" int rumi_orb_octree_stats(RumiOrb *h, int32_t trees[2]) {
+    if (!h || !trees) return RUMI_E_INVALID;
+    trees[0] = h->octStat[0]; trees[1] = h->octStat[1];
+    return RUMI_OK;
+}
+
 extern "C" int rumi_orb_sync(RumiOrb *h) {
     if (!h) return RUMI_E_INVALID;
     if (!h->pending) return RUMI_OK;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->pendingStream));
     h->pending = false;
+    for (int i = 0; i < 2; i++) h->octStat[i] = (int32_t)((uint32_t)h->hErr[1 + i] - h->octStatBase[i]);   // (unsigned: the device counters wrap)
     const int err = *h->hErr;
     if (err & 16) { g_lastError = "FAST candidate capacity exceeded (more than 65535 in one level)"; return RUMI_E_CAPACITY; }
     if (err & 1) { g_lastError = "aspect ratio gives 0 or more than 16 quadtree roots"; return RUMI_E_INVALID; }

@@ -25,6 +25,7 @@
 
 #include "orb_device.h"
 #include "orb_math.h"
+#include "orb_octree.h"
 
 namespace rumi {
 

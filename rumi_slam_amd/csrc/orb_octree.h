@@ -283,6 +283,80 @@ RUMI_HD int cand_x(uint32_t c) { return (int)(c & 0xFFFu); }
 RUMI_HD int cand_y(uint32_t c) { return (int)((c >> 12) & 0xFFFu); }
 RUMI_HD int cand_score(uint32_t c) { return (int)(c >> 24); }
 
+// ---- count tables and the coordinate halves of a key's path (shared by the kernels and by set_geometry) ----------------------------
+constexpr int kMaxRoots = 16;
+RUMI_HD int octree_pool_cap(int N, int nIni) { return 2 * (N > nIni ? N : nIni) + 16 + nIni; }
+// Count tables: the key populations of EVERY cell of the first D subdivision levels, T_d[P] with P = path of the cell (root index,
+// then two bits per level: P_{d+1} = 4 P_d + quadrant), d = 0 .. D.  One pass over the keys fills T_D, a sum pyramid gives the rest; after
+// that a node of depth d < D is born with its quadrant counts (T_{d+1}[4 P .. 4 P + 3]) and the rounds need no pass over the keys at all.
+// Level d starts at a multiple of four entries, so the four counts of a cell are one aligned 8-byte LDS read.
+// D grows with the number of nodes wanted (the coarse passes stop near 4^depth = N), within 4096 cells of depth D.
+RUMI_HD int oct_tab_depth(int nIni, int N) {
+    int D = N <= 256 ? 4 : N <= 1024 ? 5 : N <= 1152 ? 6 : 5;   // (beyond that the node pool needs the LDS)
+    while (D > 1 && (nIni << (2 * D)) > 4096) D--;
+    return D;
+}
+RUMI_HD int oct_tab_off(int d, int nIni) { return d == 0 ? 0 : 16 + nIni * (((1 << (2 * d)) - 4) / 3); }
+RUMI_HD int oct_tab_entries(int nIni, int D) { return oct_tab_off(D + 1, nIni); }
+RUMI_HD int oct_leaf_entries(int nIni, int D) { return nIni << (2 * D); }
+// lNodes' initial size (:544): round(W / H) roots over the level's key-point area W x H
+RUMI_HD int oct_roots(int W, int Hh) { return (int)__builtin_roundf((float)W / (float)Hh); }
+RUMI_HD float oct_root_width(int W, int nIni) { return (float)W / nIni; }
+// THE rule of the per-coordinate halves of a key's depth-D path.  The x comparisons DivideNode makes on the way down (:471-511) depend on x
+// alone (the root is a function of x) and the y comparisons on y alone.  x half (isX, v = 0 .. W): root << 2 D | bit 2 (D - 1 - d) = side
+// taken at depth d; y half (v = 0 .. H): bit 2 (D - 1 - d) + 1.  The cell of a key is xbin[x] | ybin[y].
+RUMI_HD uint16_t oct_coord_bin(bool isX, int v, float hX, int Hh, int nIni, int D) {
+    const int r = isX ? ((int)((float)v / hX) < nIni - 1 ? (int)((float)v / hX) : nIni - 1) : 0;   // (v = W itself is not a key position)
+    int lo = isX ? (int)(hX * (float)r) : 0, hi = isX ? (int)(hX * (float)(r + 1)) : Hh;
+    int bits = 0;
+    for (int d = 0; d < D; d++) {
+        const int mid = lo + ((hi - lo + 1) >> 1);
+        const bool q = v >= mid;
+        lo = q ? mid : lo; hi = q ? hi : mid;
+        bits = bits * 4 + (q ? 1 : 0);
+    }
+    return isX ? (uint16_t)((r << (2 * D)) | bits) : (uint16_t)(bits << 1);
+}
+// What the host keeps per pyramid level for the batch quadtree: roots, table depth and the cells of depth D (0: the level's aspect ratio gives
+// no or too many roots -- the kernels report that -- and it has no tables), and its W + 1 + H + 1 table entries (x half, then y half).
+struct OctLevelTabs { int nIni, D, cells; };
+inline OctLevelTabs oct_level_tabs(int W, int Hh, int N) {
+    const int nIni = W > 0 && Hh > 0 ? oct_roots(W, Hh) : 0;
+    if (nIni <= 0 || nIni > kMaxRoots) return OctLevelTabs{nIni, 0, 0};
+    const int D = oct_tab_depth(nIni, N);
+    return OctLevelTabs{nIni, D, oct_leaf_entries(nIni, D)};
+}
+// a level's cells in a frame's histogram / rank row start at an even entry (two 16-bit entries to a dword)
+inline int oct_row_entries(int cells) { return (cells + 1) & ~1; }
+// k_compact counts the histogram in a table of its own in LDS, behind its prefix of totalCells + 1 cell starts: the bytes of that table for
+// a frame row of `rowEntries` cells, or 0 when prefix + table + the kernel's static LDS (kCompactStaticLds: an upper bound, held by a
+// static_assert beside the kernel) would pass the 64 KiB a launch gets without an opt-in.  Such a geometry keeps the one-launch quadtree.
+constexpr int kCompactStaticLds = 2048, kLdsNoOptIn = 64 * 1024;
+inline int oct_hist_lds_bytes(int totalCells, int rowEntries) {
+    const long long prefix = ((long long)totalCells + 1) * 4, table = (long long)rowEntries * 2;
+    return rowEntries > 0 && prefix + table + kCompactStaticLds <= kLdsNoOptIn ? (int)table : 0;
+}
+inline void oct_make_bins(int W, int Hh, const OctLevelTabs &T, uint16_t *bins) {
+    const float hX = oct_root_width(W, T.nIni);
+    for (int v = 0; v <= W; v++) bins[v] = oct_coord_bin(true, v, hX, Hh, T.nIni, T.D);
+    for (int v = 0; v <= Hh; v++) bins[W + 1 + v] = oct_coord_bin(false, v, hX, Hh, T.nIni, T.D);
+}
+#if defined(__HIPCC__)
+// Counting keys that arrive in RUNS (the cells of a level in raster order, the keys of a cell row by row: neighbouring lanes fall into the
+// same cell of the subdivision): the first lane of every run of equal keys adds the length of its run.  No loop, one atomic per run (LDS in
+// the quadtree kernels, HBM / L2 in k_compact).  Every lane of the wave calls it; key < 0: the lane has nothing to add; lanes with equal keys
+// pass the same word and the same increment.
+__device__ __forceinline__ void wave_run_add(int key, unsigned int *word, unsigned int one) {
+    const int lane = threadIdx.x & 63;
+    const int before = __shfl_up(key, 1);
+    const bool head = lane == 0 || key != before;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
+    const int len = rest ? __ffsll((long long)rest) : 64 - lane;
+    if (head && key >= 0) atomicAdd(word, one * (unsigned int)len);
+}
+#endif
+
 // Host driver of the same state machine (used by the CPU tests of the
 // replayed sort / list logic).  out receives indices into cand in the reference's result order.
 inline int octree_host(const uint32_t *cand, int n, int minX, int maxX, int minY, int maxY, int N,

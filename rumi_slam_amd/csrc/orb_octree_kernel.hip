@@ -7,6 +7,9 @@
 //               round (a 16-bit owner id per key then, owner[]).  The list passes (divide, push children to the front, erase parents) are
 //               prefix sums + scatters -- on one wave without barriers while the list is short -- and std::sort is replayed exactly
 //               (wave_sort_like_libstdcxx up to 64 entries, wg_sort_like_libstdcxx beyond), so the result ORDER equals the reference's.
+//   k_octree_narrow, k_octree_redo, k_oct_select   batches: the same trees with ONE wave each, from the cell histogram k_compact counts; the keys
+//               are read once, by k_oct_select; a tree that outgrows the count tables is redone by k_octree's keys-in-memory form (below,
+//               "the batch pipeline")
 //   k_assemble  one workgroup per frame: concatenates the levels and assigns the output slot of every key-point
 //               by the lapping-area rule of operator() (:1067-1088) with a block scan (the reference walks them
 //               serially with monoIndex++ / stereoIndex--).
@@ -22,26 +25,12 @@
 
 namespace rumi {
 
-constexpr int kMaxRoots = 16;
 constexpr int kOctThreads = 512;
 
-__host__ __device__ inline int octree_pool_cap(int N, int nIni) { return 2 * (N > nIni ? N : nIni) + 16 + nIni; }
-// Count tables (round 3): the key populations of EVERY cell of the first D subdivision levels, T_d[P] with P = path of the cell (root index,
-// then two bits per level: P_{d+1} = 4 P_d + quadrant), d = 0 .. D.  One pass over the keys fills T_D, a sum pyramid gives the rest; after
-// that a node of depth d < D is born with its quadrant counts (T_{d+1}[4 P .. 4 P + 3]) and the rounds need no pass over the keys at all.
-// Level d starts at a multiple of four entries, so the four counts of a cell are one aligned 8-byte LDS read.
-// D grows with the number of nodes wanted (the coarse passes stop near 4^depth = N), within 4096 cells of depth D.
-__host__ __device__ inline int oct_tab_depth(int nIni, int N) {
-    int D = N <= 256 ? 4 : N <= 1024 ? 5 : N <= 1152 ? 6 : 5;   // (beyond that the node pool needs the LDS)
-    while (D > 1 && (nIni << (2 * D)) > 4096) D--;
-    return D;
-}
-__host__ __device__ inline int oct_tab_off(int d, int nIni) { return d == 0 ? 0 : 16 + nIni * (((1 << (2 * d)) - 4) / 3); }
-__host__ __device__ inline int oct_tab_entries(int nIni, int D) { return oct_tab_off(D + 1, nIni); }
-__host__ __device__ inline int oct_leaf_entries(int nIni, int D) { return nIni << (2 * D); }
+// (pool size, count tables and the per-coordinate path rule: orb_octree.h, shared with set_geometry)
 // LDS bytes of one k_octree workgroup for a pool of `cap` nodes: nodes, open + sort arrays, free stack, split stack, two list arrays,
 // two SortSeg work lists, the count tables and the cell -> leaf table
-// (W, H: the level's key-point area; the two per-coordinate path tables have W + 1 and H + 1 entries)
+// (W, H: the level's key-point area; the two per-coordinate path tables have W + 1 and H + 1 entries; the narrow kernel has none: -1, -1)
 __host__ __device__ inline size_t octree_lds_bytes(int cap, int nIni, int D, int W, int H) {
     return (size_t)cap * (sizeof(OctNode) + 2 * sizeof(OctEntry) + 4 * sizeof(uint16_t)) + 2 * (size_t)(cap / 16 + 2) * 8 + 64 +
            ((size_t)(oct_tab_entries(nIni, D) + oct_leaf_entries(nIni, D) + W + H + 4) * sizeof(uint16_t) + 16);
@@ -172,17 +161,7 @@ __device__ __forceinline__ void wave_agg_add(int key, unsigned int *word, unsign
     }
 }
 
-// The same for keys that arrive in RUNS (the cells of a level in raster order, the keys of a cell row by row: neighbouring lanes fall into the
-// same cell of the subdivision): the first lane of every run of equal keys adds the length of its run.  No loop, one LDS atomic per run.
-__device__ __forceinline__ void wave_run_add(int key, unsigned int *word, unsigned int one) {
-    const int lane = threadIdx.x & 63;
-    const int before = __shfl_up(key, 1);
-    const bool head = lane == 0 || key != before;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
-    const int len = rest ? __ffsll((long long)rest) : 64 - lane;
-    if (head && key >= 0) atomicAdd(word, one * (unsigned int)len);
-}
+// (wave_run_add, the same for keys that arrive in RUNS: orb_octree.h -- k_compact counts with it too)
 
 // inclusive prefix sum over the wave in six DPP steps (no LDS round trips: __shfl_up is a ds_bpermute each)
 __device__ __forceinline__ unsigned int wave_scan_incl(unsigned int v) {
@@ -203,11 +182,15 @@ __device__ __forceinline__ unsigned int wave_scan_incl(unsigned int v) {
         const int v2 = __builtin_amdgcn_update_dpp(0, (int)v, 0x110 + S_, 0xF, 0xF, false); \
         if (o2 == oo) v = max(v, (uint32_t)v2);                                            \
     }
-__device__ __forceinline__ void wave_run_max(OctNode *nodes, int owner, bool valid, uint32_t v) {
+// best0 + owner * strideWords: the owner's word (the nodes' `best` fields in k_octree, a plain array by list rank in k_oct_select)
+__device__ __forceinline__ void wave_run_max(uint32_t *best0, int strideWords, int owner, bool valid, uint32_t v) {
     const int oo = valid ? owner : -1;
     RUMI_RUN_MAX_STEP(1) RUMI_RUN_MAX_STEP(2) RUMI_RUN_MAX_STEP(4) RUMI_RUN_MAX_STEP(8)
     const int after = __builtin_amdgcn_update_dpp(-2, oo, 0x101, 0xF, 0xF, false);          // row_shl:1 = the next lane's owner
-    if (valid && after != oo) atomicMax(&nodes[owner].best, v);
+    if (valid && after != oo) atomicMax(best0 + owner * strideWords, v);
+}
+__device__ __forceinline__ void wave_run_max(OctNode *nodes, int owner, bool valid, uint32_t v) {
+    wave_run_max(&nodes[0].best, (int)(sizeof(OctNode) / sizeof(uint32_t)), owner, valid, v);
 }
 #undef RUMI_RUN_MAX_STEP
 
@@ -270,18 +253,33 @@ struct OctKeys {
     }
 };
 
-template <bool REG, int NT>
+// Where the tree of one (frame, level) gets its keys' cells from.  kKeysMem / kKeysReg: two passes over the keys (in memory / in registers), the
+// kernel selects the best key of every node itself.  kKeysHist (k_octree_narrow): the keys are never touched -- T_D arrives counted (k_compact's
+// histogram, cleared as it is read) and the result is the list length and the cell -> list rank table k_oct_select picks the keys by; a tree
+// that outgrows the count tables is handed to k_octree_redo.
+enum { kKeysMem = 0, kKeysReg = 1, kKeysHist = 2 };
+
+template <int MODE, int NT>
 __device__ __forceinline__ void octree_level(const DevParams *__restrict__ P, const uint32_t *__restrict__ cand,
                                              const int32_t *__restrict__ levelStart, uint16_t *__restrict__ owner,
                                              uint32_t *__restrict__ selLevel, int32_t *__restrict__ selLevelCnt,
-                                             int selLevelCap, int32_t *__restrict__ errFlag, unsigned char *lds) {
+                                             int selLevelCap, int32_t *__restrict__ errFlag, unsigned char *lds, int level, int frame,
+                                             const OctNarrow &Q) {
+    constexpr bool REG = MODE == kKeysReg, HIST = MODE == kKeysHist;
     __shared__ int sPhase, sM, sNOpen, sNFree, sNSplit, sOverflow, sDeep, sSolo;
     __shared__ unsigned long long sWave[NT / 64];
     __shared__ int sSortCount[2];
 
-    const int tid = threadIdx.x, level = blockIdx.x, frame = blockIdx.y;
+    const int tid = threadIdx.x;
     const DevLevel &L = P->lv[level];
     const int32_t *ls = levelStart + (long long)frame * (kMaxLevels + 1);
+    // kKeysHist: this tree is k_octree_redo's (its list entry is the only thing written)
+    [[maybe_unused]] auto redo = [&]() {
+        if (tid == 0) {
+            Q.m[frame * P->nlevels + level] = kOctRedo;
+            Q.redoList[atomicAdd(&Q.ctl[0], 1)] = frame * kMaxLevels + level;
+        }
+    };
     OctKeys<REG, NT> keys;
     keys.n = ls[level + 1] - ls[level];
     keys.c = cand + (long long)frame * P->totalCand + ls[level];
@@ -291,13 +289,17 @@ __device__ __forceinline__ void octree_level(const DevParams *__restrict__ P, co
     uint32_t *out = selLevel + ((long long)frame * P->nlevels + level) * selLevelCap;
     int32_t *outCnt = selLevelCnt + (long long)frame * P->nlevels + level;
     if (n <= 0) {
-        if (tid == 0) *outCnt = 0;
+        if (tid == 0) {
+            *outCnt = 0;
+            if constexpr (HIST) Q.m[frame * P->nlevels + level] = 0;
+        }
         return;
     }
     const int N = L.nfeat;
     const int W = L.maxBX - kBorder, Hh = L.maxBY - kBorder;
-    const int nIni = uni((int)__builtin_roundf((float)W / (float)Hh));   // (float arithmetic is per-lane: everything derived from it would be too)
+    const int nIni = uni(oct_roots(W, Hh));        // (float arithmetic is per-lane: everything derived from it would be too)
     if (nIni <= 0 || nIni > kMaxRoots) {           // the reference divides by zero / we do not stage that many roots
+        if constexpr (HIST) { redo(); return; }    // (such a level has no histogram: nothing to clear)
         if (tid == 0) { *outCnt = 0; atomicOr(errFlag, 1); }
         return;
     }
@@ -308,7 +310,7 @@ __device__ __forceinline__ void octree_level(const DevParams *__restrict__ P, co
 #define OCT_STAMP(k) do { } while (0)
 #endif
     keys.load();
-    const float hX = __int_as_float(uni(__float_as_int((float)W / nIni)));
+    const float hX = __int_as_float(uni(__float_as_int(oct_root_width(W, nIni))));
     const int cap = octree_pool_cap(N, nIni);
 
     OctLds S;
@@ -332,22 +334,24 @@ __device__ __forceinline__ void octree_level(const DevParams *__restrict__ P, co
 
     // free stack: ids cap-1 .. nIni (top of the stack = smallest id); roots take ids 0 .. nIni-1
     for (int i = tid; i < cap - nIni; i += NT) S.freeIds[i] = (uint16_t)(cap - 1 - i);
-    for (int i = tid; i < (nIni << (2 * D)) / 2; i += NT) reinterpret_cast<uint32_t *>(S.tab + offD)[i] = 0u;
     if (tid == 0) { sNFree = cap - nIni; sNSplit = 0; sOverflow = 0; sPhase = 0; sNOpen = 0; sDeep = 0; }
-    for (int i = tid; i <= W + Hh + 1; i += NT) {  // per-coordinate halves of the path: bit 2 (D-1-d) (x) / 2 (D-1-d) + 1 (y) = side taken at depth d
-        const bool isX = i <= W;
-        const int v = isX ? i : i - (W + 1);
-        const int r = isX ? min((int)((float)v / hX), nIni - 1) : 0;   // (v = W itself is not a key position)
-        int lo = isX ? (int)(hX * (float)r) : 0, hi = isX ? (int)(hX * (float)(r + 1)) : Hh;
-        int bits = 0;
-        for (int d = 0; d < D; d++) {
-            const int mid = lo + ((hi - lo + 1) >> 1);
-            const bool q = v >= mid;
-            lo = q ? mid : lo; hi = q ? hi : mid;
-            bits = bits * 4 + (q ? 1 : 0);
+    if constexpr (HIST) {
+        // T_D as k_compact counted it; what is read is cleared, so the next call's k_compact finds zeros without a memset launch
+        uint32_t *hg = Q.hist + (size_t)frame * (size_t)(P->octCellStride / 2) + L.octCell / 2;
+        for (int i = tid; i < (nIni << (2 * D)) / 2; i += NT) {
+            const uint32_t w = hg[i];
+            reinterpret_cast<uint32_t *>(S.tab + offD)[i] = w;
+            if (w) hg[i] = 0u;
         }
-        if (isX) S.xbin[v] = (uint16_t)((r << (2 * D)) | bits);
-        else S.ybin[v] = (uint16_t)(bits << 1);
+    } else {
+        for (int i = tid; i < (nIni << (2 * D)) / 2; i += NT) reinterpret_cast<uint32_t *>(S.tab + offD)[i] = 0u;
+        for (int i = tid; i <= W + Hh + 1; i += NT) {  // per-coordinate halves of the path, this workgroup's own copy of the tables of set_geometry
+            const bool isX = i <= W;
+            const int v = isX ? i : i - (W + 1);
+            const uint16_t b = oct_coord_bin(isX, v, hX, Hh, nIni, D);
+            if (isX) S.xbin[v] = b;
+            else S.ybin[v] = b;
+        }
     }
     __syncthreads();
     OCT_STAMP(7);
@@ -355,16 +359,18 @@ __device__ __forceinline__ void octree_level(const DevParams *__restrict__ P, co
     // The x comparisons of a path depend on x alone (the root is a function of x) and the y comparisons on y alone, so the two halves of
     // the path come from two small tables by coordinate.  A key keeps the path of its cell (its "owner" until the tree outgrows the
     // tables); T_D counts the keys of every cell.
-    auto cell_of = [&](uint32_t ck) { return (int)S.xbin[min(cand_x(ck), W)] | (int)S.ybin[min(cand_y(ck), Hh)]; };
-    keys.template for_each<1>([&](int, bool valid, uint32_t ck, int &o) {      // (keys in memory: the cell is looked up again when it is needed)
-        int P = -1;
-        if (valid) {
-            P = cell_of(ck);
-            o = P;
-        }
-        wave_run_add(P, reinterpret_cast<unsigned int *>(S.tab + offD) + ((P < 0 ? 0 : P) >> 1), 1u << (16 * (P & 1)));
-    });
-    __syncthreads();
+    [[maybe_unused]] auto cell_of = [&](uint32_t ck) { return (int)S.xbin[min(cand_x(ck), W)] | (int)S.ybin[min(cand_y(ck), Hh)]; };
+    if constexpr (!HIST) {
+        keys.template for_each<1>([&](int, bool valid, uint32_t ck, int &o) {      // (keys in memory: the cell is looked up again when it is needed)
+            int P = -1;
+            if (valid) {
+                P = cell_of(ck);
+                o = P;
+            }
+            wave_run_add(P, reinterpret_cast<unsigned int *>(S.tab + offD) + ((P < 0 ? 0 : P) >> 1), 1u << (16 * (P & 1)));
+        });
+        __syncthreads();
+    }
     OCT_STAMP(8);
     for (int d = D - 1; d >= 0; d--) {             // sum pyramid
         const uint16_t *src = S.tab + oct_tab_off(d + 1, nIni);
@@ -395,6 +401,7 @@ __device__ __forceinline__ void octree_level(const DevParams *__restrict__ P, co
     bool table = true;                             // uniform: the count tables still cover every open node
     // leaf[cell of depth D] = the node of `list` that covers it; the cells of a node are consecutive paths.  One thread per node writes up
     // to 16 cells itself; the few shallower nodes (64, 256 cells: sparse levels) are filled by their wave, lane per cell.
+    // kKeysHist: the table holds the node's RANK in the list instead (k_oct_select has no node pool).
     auto fill_leaf = [&](const uint16_t *list, int len) {
         for (int r0 = 0; r0 < len; r0 += NT) {
             const int r = r0 + tid;
@@ -404,6 +411,7 @@ __device__ __forceinline__ void octree_level(const DevParams *__restrict__ P, co
                 OctNode &nd = nodes[id];
                 span = 1 << (2 * (D - (int)node_depth(nd)));
                 base = (int)node_path(nd) * span;
+                if constexpr (HIST) id = r;
                 if (span <= 16)
                     for (int cI = 0; cI < span; cI++) S.leaf[base + cI] = (uint16_t)id;
             }
@@ -592,6 +600,7 @@ __device__ __forceinline__ void octree_level(const DevParams *__restrict__ P, co
             // every key moves from its cell to the node that covers the cell now, the keys of those deepest nodes are counted, and the
             // rounds after this one relabel and count as they go (below).
             if (uni(sDeep)) {
+                if constexpr (HIST) { redo(); return; }     // the tree outgrows the count tables: the rest needs the keys
                 fill_leaf(A, m2);
                 __syncthreads();
                 keys.template for_each<2>([&](int, bool valid, uint32_t ck, int &o) {
@@ -634,6 +643,16 @@ __device__ __forceinline__ void octree_level(const DevParams *__restrict__ P, co
     // :705-721  best key of every node, nodes in list order; the keys of the nodes divided in the last round move to their
     // children on the way (best shares its word with the quadrant counts of the surviving nodes, hence the clearing first)
     const int m = uni(sM);
+    if constexpr (HIST) {
+        // the errors of the old kernel are the old kernel's to report; otherwise: the list length and, by cell, the rank of the node that covers it
+        if (uni(sOverflow) || m > selLevelCap) { redo(); return; }
+        fill_leaf(A, m);                           // (the count tables covered every round: every node is at most D deep)
+        __syncthreads();
+        uint32_t *rg = Q.rank + (size_t)frame * (size_t)(P->octCellStride / 2) + L.octCell / 2;
+        for (int i = tid; i < (nIni << (2 * D)) / 2; i += NT) rg[i] = reinterpret_cast<const uint32_t *>(S.leaf)[i];
+        if (tid == 0) Q.m[frame * P->nlevels + level] = m;
+        return;
+    }
     if (tid == 0 && sOverflow) atomicOr(errFlag, 2);
     if (table) fill_leaf(A, m);                    // every node of the final list is at most D deep here
     for (int r = tid; r < m; r += NT) nodes[A[r]].best = 0;
@@ -674,41 +693,148 @@ __global__ __launch_bounds__(NT, REGS ? 1 : 4) void k_octree(const DevParams *__
                                                         uint32_t *__restrict__ selLevel, int32_t *__restrict__ selLevelCnt,
                                                         int selLevelCap, int32_t *__restrict__ errFlag) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const OctNarrow none{};
     if constexpr (REGS) {
         const int32_t *ls = levelStart + (long long)blockIdx.y * (kMaxLevels + 1);
         if (ls[blockIdx.x + 1] - ls[blockIdx.x] <= kKeysPerLane * NT) {
-            octree_level<true, NT>(P, cand, levelStart, owner, selLevel, selLevelCnt, selLevelCap, errFlag, lds);
+            octree_level<kKeysReg, NT>(P, cand, levelStart, owner, selLevel, selLevelCnt, selLevelCap, errFlag, lds, blockIdx.x, blockIdx.y, none);
             return;
         }
     }
-    octree_level<false, NT>(P, cand, levelStart, owner, selLevel, selLevelCnt, selLevelCap, errFlag, lds);
+    octree_level<kKeysMem, NT>(P, cand, levelStart, owner, selLevel, selLevelCnt, selLevelCap, errFlag, lds, blockIdx.x, blockIdx.y, none);
 }
 
+// ---- the batch pipeline: k_compact's histogram -> k_octree_narrow -> k_octree_redo -> k_oct_select ------------------------------------
+// A k_octree<false, 256> workgroup wants a 128-register slot on all four SIMDs of a CU at once plus 29 KB of LDS, and beside the other slot
+// streams' kernels (small waves that fill the SIMDs) it waits for that: 330 us in the overlapped step against 80 us alone.  Most of the
+// footprint idles -- the list phases run on wave 0 while three waves sit at barriers.  So a tree gets ONE wave (NT = 64: every barrier of
+// the rounds is gone) and the two data-parallel passes over the keys move into wide, light kernels: the count of every depth-D cell into
+// k_compact (it has each key in a register anyway), the choice of the best key of every node into k_oct_select.
+template <int NT>
+__global__ __launch_bounds__(NT, 4) void k_octree_narrow(const DevParams *__restrict__ P, const int32_t *__restrict__ levelStart,
+                                                         int32_t *__restrict__ selLevelCnt, int selLevelCap, OctNarrow Q) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    octree_level<kKeysHist, NT>(P, nullptr, levelStart, nullptr, nullptr, selLevelCnt, selLevelCap, nullptr, lds, blockIdx.x, blockIdx.y, Q);
+}
+
+// The trees k_octree_narrow handed on (the count tables ended before the tree did, or one of the reported errors), by the keys-in-memory
+// kernel as it is: it counts from the keys again, so its results are k_octree<false, NT>'s by construction.  A fixed grid strides over the
+// list and is gone at once when the list is empty; the last workgroup to finish adds the launch to the handle's statistic and clears the
+// list's counter for the slot range's next launch.  No workgroup waits for another.
+// (32 workgroups: each of them, empty list or not, waits for the 128-register, 29 KB slot the pipeline exists to avoid -- 256 of them
+// took 45 us beside the other streams' kernels with nothing to do)
+constexpr int kRedoGrid = 32;
+template <int NT>
+__global__ __launch_bounds__(NT, 4) void k_octree_redo(const DevParams *__restrict__ P, const uint32_t *__restrict__ cand,
+                                                       const int32_t *__restrict__ levelStart, uint16_t *__restrict__ owner,
+                                                       uint32_t *__restrict__ selLevel, int32_t *__restrict__ selLevelCnt,
+                                                       int selLevelCap, int32_t *__restrict__ errFlag, OctNarrow Q, int ntrees) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ int sCnt;
+    if (threadIdx.x == 0) sCnt = Q.ctl[0];
+    __syncthreads();
+    const int cnt = uni(sCnt);
+    for (int t = blockIdx.x; t < cnt; t += gridDim.x) {
+        const int e = uni(Q.redoList[t]);
+        octree_level<kKeysMem, NT>(P, cand, levelStart, owner, selLevel, selLevelCnt, selLevelCap, errFlag, lds, e % kMaxLevels, e / kMaxLevels, Q);
+        __syncthreads();                            // (the next tree's set-up overwrites what this one's last pass reads)
+    }
+    if (threadIdx.x == 0 && atomicAdd(&Q.ctl[1], 1) == (int)gridDim.x - 1) {   // every workgroup has read the counter before its ticket
+        atomicAdd(&Q.stat[0], ntrees - cnt);
+        atomicAdd(&Q.stat[1], cnt);
+        Q.ctl[0] = 0; Q.ctl[1] = 0;
+    }
+}
+
+// The best key of every node of the final list (:705-721: largest response, first in candidate order on ties) for the trees
+// k_octree_narrow finished: a key's node is rank[cell of the key], its cell comes from the host-built coordinate tables.
+constexpr int kSelectThreads = 256;
+__global__ __launch_bounds__(kSelectThreads) void k_oct_select(const DevParams *__restrict__ P, const uint32_t *__restrict__ cand,
+                                                               const int32_t *__restrict__ levelStart, uint32_t *__restrict__ selLevel,
+                                                               int32_t *__restrict__ selLevelCnt, int selLevelCap, OctNarrow Q) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t sel[];     // cell -> rank (16 bit each) | best [m]
+    const int tid = threadIdx.x, level = blockIdx.x, frame = blockIdx.y;
+    const int m = uni(Q.m[frame * P->nlevels + level]);
+    if (m <= 0) return;                            // no keys (the count is written), or the tree is k_octree_redo's (kOctRedo)
+    const DevLevel &L = P->lv[level];
+    const int32_t *ls = levelStart + (long long)frame * (kMaxLevels + 1);
+    const int n = ls[level + 1] - ls[level];
+    const uint32_t *c = cand + (long long)frame * P->totalCand + ls[level];
+    const int W = L.maxBX - kBorder, Hh = L.maxBY - kBorder;
+    const uint16_t *xbin = Q.bins + L.octBin, *ybin = xbin + W + 1;
+    const uint16_t *rank = reinterpret_cast<const uint16_t *>(sel);
+    uint32_t *best = sel + L.octCells / 2;
+    const uint32_t *rg = Q.rank + (size_t)frame * (size_t)(P->octCellStride / 2) + L.octCell / 2;
+    for (int i = tid; i < L.octCells / 2; i += kSelectThreads) sel[i] = rg[i];
+    for (int r = tid; r < m; r += kSelectThreads) best[r] = 0u;
+    __syncthreads();
+    for (int i0 = 0; i0 < n; i0 += kSelectThreads) {
+        const int i = i0 + tid;
+        const bool valid = i < n;
+        const uint32_t ck = valid ? c[i] : 0u;
+        const int r = valid ? (int)rank[(int)xbin[min(cand_x(ck), W)] | (int)ybin[min(cand_y(ck), Hh)]] : 0;
+        wave_run_max(best, 1, r, valid, ((uint32_t)cand_score(ck) << 16) | (uint32_t)(0xFFFF - i));
+    }
+    __syncthreads();
+    uint32_t *out = selLevel + ((long long)frame * P->nlevels + level) * selLevelCap;
+    for (int r = tid; r < m; r += kSelectThreads) out[r] = c[min(0xFFFF - (int)(best[r] & 0xFFFF), n - 1)];   // (every node of the list has a key)
+    if (tid == 0) selLevelCnt[(long long)frame * P->nlevels + level] = m;
+}
+
+// 0: the keys-in-registers kernel (at most one workgroup per CU); 1: the keys-in-memory kernel in one launch; 2: the batch pipeline.
+// RUMI_OCT_REGS and RUMI_OCT_NARROW are read once per process.
+int octree_plan(const DevParams &hP, int nframes) {
+    static const int forced = [] { const char *e = getenv("RUMI_OCT_REGS"); return e ? atoi(e) : -1; }();
+    static const bool narrow = [] { const char *e = getenv("RUMI_OCT_NARROW"); return !e || atoi(e) != 0; }();
+    const bool regs = forced >= 0 ? forced != 0 : hP.nlevels * nframes <= 256;   // at most one workgroup per CU
+    if (regs) return 0;
+    return narrow && hP.octCellStride > 0 ? 2 : 1;
+}
+
+// One wave per tree: 256 threads per tree were measured too (93 us against 61 us per 256-frame launch in the overlapped step)
+constexpr int kNarrowThreads = 64;
 void launch_octree(const DevParams *dP, const DevParams &hP, const uint32_t *cand, const int32_t *levelStart,
                    uint16_t *owner, uint32_t *selLevel, int32_t *selLevelCnt, int selLevelCap, int32_t *errFlag,
-                   int nframes, size_t ldsBytes, hipStream_t st) {
-    static const int forced = [] { const char *e = getenv("RUMI_OCT_REGS"); return e ? atoi(e) : -1; }();
-    const bool regs = forced >= 0 ? forced != 0 : hP.nlevels * nframes <= 256;   // at most one workgroup per CU
+                   int nframes, const OctLdsSizes &lds, const OctNarrow &Q, hipStream_t st) {
+    const int plan = octree_plan(hP, nframes);
     auto go = [&](auto kern, int threads) {
         // > 64 KiB of dynamic LDS needs the opt-in (process state that only grows: rumi_common.h)
-        (void)raise_lds_limit(reinterpret_cast<const void *>(kern), ldsBytes);
-        hipLaunchKernelGGL(kern, dim3(hP.nlevels, nframes), dim3(threads), ldsBytes, st, dP, cand, levelStart, owner, selLevel, selLevelCnt, selLevelCap,
+        (void)raise_lds_limit(reinterpret_cast<const void *>(kern), lds.wide);
+        hipLaunchKernelGGL(kern, dim3(hP.nlevels, nframes), dim3(threads), lds.wide, st, dP, cand, levelStart, owner, selLevel, selLevelCnt, selLevelCap,
                            errFlag);
     };
-    if (regs) go(k_octree<true, kOctThreads>, kOctThreads);
-    else if (hP.lv[0].nfeat <= 260) go(k_octree<false, 256>, 256);             // level 0 of 1200 features at scale 1.2, 8 levels
-    else go(k_octree<false, kOctThreads>, kOctThreads);
+    const bool small = hP.lv[0].nfeat <= 260;                                   // level 0 of 1200 features at scale 1.2, 8 levels
+    if (plan == 0) { go(k_octree<true, kOctThreads>, kOctThreads); return; }
+    if (plan == 1) {
+        if (small) go(k_octree<false, 256>, 256);
+        else go(k_octree<false, kOctThreads>, kOctThreads);
+        return;
+    }
+    const dim3 grid(hP.nlevels, nframes);
+    (void)raise_lds_limit(reinterpret_cast<const void *>(k_octree_narrow<kNarrowThreads>), lds.narrow);
+    hipLaunchKernelGGL(k_octree_narrow<kNarrowThreads>, grid, dim3(kNarrowThreads), lds.narrow, st, dP, levelStart, selLevelCnt, selLevelCap, Q);
+    auto redo = [&](auto kern, int threads) {
+        (void)raise_lds_limit(reinterpret_cast<const void *>(kern), lds.wide);
+        hipLaunchKernelGGL(kern, dim3(kRedoGrid), dim3(threads), lds.wide, st, dP, cand, levelStart, owner, selLevel, selLevelCnt, selLevelCap, errFlag,
+                           Q, hP.nlevels * nframes);
+    };
+    if (small) redo(k_octree_redo<256>, 256);
+    else redo(k_octree_redo<kOctThreads>, kOctThreads);
+    hipLaunchKernelGGL(k_oct_select, grid, dim3(kSelectThreads), lds.select, st, dP, cand, levelStart, selLevel, selLevelCnt, selLevelCap, Q);
 }
-size_t octree_lds_for(const DevParams &hP) {
-    size_t mx = 0;
+OctLdsSizes octree_lds_for(const DevParams &hP, int selLevelCap) {
+    OctLdsSizes s{0, 0, 0};
     for (int l = 0; l < hP.nlevels; l++) {
         const int W = hP.lv[l].maxBX - kBorder, Hh = hP.lv[l].maxBY - kBorder;
-        int nIni = (int)__builtin_roundf((float)W / (float)Hh);
+        int nIni = oct_roots(W, Hh);
         if (nIni < 1) nIni = 1;
         const int nr = nIni > kMaxRoots ? kMaxRoots : nIni;
-        mx = std::max(mx, octree_lds_bytes(octree_pool_cap(hP.lv[l].nfeat, nIni), nr, oct_tab_depth(nr, hP.lv[l].nfeat), W, Hh));
+        const int cap = octree_pool_cap(hP.lv[l].nfeat, nIni), D = oct_tab_depth(nr, hP.lv[l].nfeat);
+        s.wide = std::max(s.wide, octree_lds_bytes(cap, nr, D, W, Hh));
+        s.narrow = std::max(s.narrow, octree_lds_bytes(cap, nr, D, -1, -1));
+        s.select = std::max(s.select, (size_t)hP.lv[l].octCells * sizeof(uint16_t) + (size_t)selLevelCap * sizeof(uint32_t));
     }
-    return mx;
+    return s;
 }
 
 }  // namespace rumi

@@ -48,6 +48,12 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
     // calls not yet waited for share the scratch arenas in stream order: another stream (or the profiled path) waits for them first
     if (h->pending && (st != h->pendingStream || h->profiling)) { rc = rumi_orb_sync(h); if (rc != RUMI_OK) return rc; }
     const DevParams &P = h->hP;
+    if (!h->pending) { h->octStatBase[0] = (uint32_t)h->hErr[1]; h->octStatBase[1] = (uint32_t)h->hErr[2]; }   // rumi_orb_octree_stats counts from an idle handle
+    if (h->octDirty) {           // an earlier call failed between its compaction and its quadtree launch: the pipeline's zero state is restored first
+        HIP_TRY(hipDeviceSynchronize());
+        if (const int rz = zero_octree_state(h); rz != RUMI_OK) return rz;
+        h->octDirty = false;
+    }
     // Level 0 is read where the caller has it, as aligned dwords.  Frames whose base, pitch or frame stride is not a multiple of 4 are
     // first copied into an aligned staging arena (the only case that costs a copy).
     bool stagedL0 = false;       // the frames were copied on `st`: the slot streams of a resident call must then wait for `st` (below)
@@ -151,9 +157,19 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
         if (fuseBlur) (void)launch_fast_blur(h->dP, P, ps, cellBuf, cellCnt, n, h->cfg.blur_variant, s);
         else launch_fast(h->dP, P, ps, cellBuf, cellCnt, n, s);
         if (timed) HIP_TRY(hipEventRecord(h->ev[4], s));
-        launch_compact(h->dP, P, cellBuf, cellCnt, candp, lvStart, h->dErr, n, s);
+        // batches: the quadtree pipeline starts from the cell histogram the compaction counts (this slot range's blocks)
+        const bool octPipe = octree_plan(P, n) > 1;
+        const size_t octRow = (size_t)scr0 * (size_t)(h->capOctCells / 2);
+        const OctNarrow Q{h->dOctHist + octRow, h->dOctRank + octRow, h->dOctM + (size_t)scr0 * P.nlevels, h->dOctRedo + (size_t)scr0 * P.nlevels,
+                          h->dOctCtl + (size_t)scr0 * 4, h->dErr + 1, h->dOctBins};
+        // INVARIANT of the pipeline: the histogram rows and the redo counters are zero between launches (k_octree_narrow clears what it reads).
+        // A return between the compaction and the quadtree launch would leave counted cells behind and every later tree of the handle wrong,
+        // so the handle is marked until the quadtree is queued; a marked handle zeroes both before its next call (below, octDirty).
+        if (octPipe) h->octDirty = true;
+        launch_compact(h->dP, P, cellBuf, cellCnt, candp, lvStart, h->dErr, n, s, octPipe ? Q.hist : nullptr, h->dOctBins);
         if (timed) HIP_TRY(hipEventRecord(h->ev[5], s));
-        launch_octree(h->dP, P, candp, lvStart, h->dOwner + (size_t)scr0 * P.totalCand, selLevel, selLevelCnt, h->selLevelCap, h->dErr, n, h->octLds, s);
+        launch_octree(h->dP, P, candp, lvStart, h->dOwner + (size_t)scr0 * P.totalCand, selLevel, selLevelCnt, h->selLevelCap, h->dErr, n, h->octLds, Q, s);
+        h->octDirty = false;
         // a few frames: the slot assignment (k_assemble) inside the descriptor kernel's prologue, one launch less on the dependent chain
         const bool fuseAssemble = !timed && !serial && n <= 4 && (long long)((h->capSel + 7) / 8) * n <= 2048;
         int32_t *countsOut = (int32_t *)((uint8_t *)d_counts + (size_t)frame0 * out.countsStride);
@@ -265,7 +281,7 @@ static int extract_async_impl(RumiOrb *h, const void *d_imgs, int32_t nframes, i
     // The call's error word (and, for the single-frame host API, its result block) follow the kernels on the stream; rumi_orb_sync waits
     // for them.  Nothing here blocks, so a caller can queue the next batch while this one runs.
     if (opts.out1Bytes) HIP_TRY(hipMemcpyAsync(h->hOut1, h->dOut1, opts.out1Bytes, hipMemcpyDeviceToHost, st));
-    if (!opts.zeroCopyOut) HIP_TRY(hipMemcpyAsync(h->hErr, h->dErr, sizeof(int32_t), hipMemcpyDeviceToHost, st));       // (zero-copy: k_assemble has published it)
+    if (!opts.zeroCopyOut) HIP_TRY(hipMemcpyAsync(h->hErr, h->dErr, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));   // with the quadtree's counters (zero-copy: k_assemble has published the error word)
     h->pending = true; h->pendingStream = st;
     if (prof) {
         float ms;

@@ -49,6 +49,39 @@ extern "C" int rumi_hook_quadtree(const uint32_t *cand, int32_t n, int32_t minX,
     return RUMI_OK;
 }
 
+// the batch quadtree's coordinate tables of one level, by the functions set_geometry builds them with (oct_level_tabs, oct_make_bins)
+extern "C" int rumi_hook_octree_bins(int32_t w, int32_t h, int32_t nfeatures, float scale, int32_t nlevels, int32_t level, int32_t *info,
+                                     uint16_t *bins, int32_t cap, int32_t *n_out) {
+    if (!info || !n_out || nfeatures < 1 || nlevels < 1 || nlevels > kMaxLevels || level < 0 || level >= nlevels) return RUMI_E_INVALID;
+    const OrbTables t = make_tables(nfeatures, scale, nlevels);
+    std::vector<LevelGeom> g;
+    long long arena = 0;
+    int cells, cand, cellCand;
+    if (!make_geometry(t, w, h, g, &arena, &cells, &cand, &cellCand)) return RUMI_E_INVALID;
+    const int W = g[level].maxBX - kBorder, Hh = g[level].maxBY - kBorder;
+    const OctLevelTabs T = oct_level_tabs(W, Hh, g[level].nfeat);
+    const int32_t inf[6] = {W, Hh, T.nIni, T.D, T.cells, g[level].nfeat};
+    std::copy(inf, inf + 6, info);
+    *n_out = T.cells ? W + 1 + Hh + 1 : 0;
+    if (*n_out > cap || (*n_out && !bins)) return RUMI_E_CAPACITY;
+    if (T.cells) oct_make_bins(W, Hh, T, bins);
+    return RUMI_OK;
+}
+
+// k_compact's LDS sizing for the batch quadtree of a geometry, by the functions set_geometry and launch_compact use (oct_row_entries, oct_hist_lds_bytes)
+extern "C" int rumi_hook_compact_hist_lds(int32_t w, int32_t h, int32_t nfeatures, float scale, int32_t nlevels, int32_t *info) {
+    if (!info || nfeatures < 1 || nlevels < 1 || nlevels > kMaxLevels) return RUMI_E_INVALID;
+    const OrbTables t = make_tables(nfeatures, scale, nlevels);
+    std::vector<LevelGeom> g;
+    long long arena = 0;
+    int cells, cand, cellCand;
+    if (!make_geometry(t, w, h, g, &arena, &cells, &cand, &cellCand)) return RUMI_E_INVALID;
+    int row = 0;
+    for (int l = 0; l < nlevels; l++) row += oct_row_entries(oct_level_tabs(g[l].maxBX - kBorder, g[l].maxBY - kBorder, g[l].nfeat).cells);
+    info[0] = cells; info[1] = row; info[2] = oct_hist_lds_bytes(cells, row); info[3] = kCompactStaticLds;
+    return RUMI_OK;
+}
+
 extern "C" float rumi_hook_sinf(float x) { return sinf_glibc(x); }
 extern "C" float rumi_hook_cosf(float x) { return cosf_glibc(x); }
 extern "C" float rumi_hook_fast_atan2(float y, float x) { return fast_atan2_deg(y, x); }

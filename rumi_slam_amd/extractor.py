@@ -199,6 +199,12 @@ class ORBextractor:
     def set_profiling(self, on=True):
         capi.check(self._lib.rumi_orb_set_profiling(self._h, int(on)))
 
+    def octree_stats(self):
+        """(trees finished from the candidate histogram, trees redone from their keys) of the batched calls since the handle was last idle."""
+        t = np.zeros(2, np.int32)
+        capi.check(self._lib.rumi_orb_octree_stats(self._h, capi.ptr(t)))
+        return int(t[0]), int(t[1])
+
     def stage_ms(self):
         ms = np.zeros(8, np.float32)
         capi.check(self._lib.rumi_orb_stage_ms(self._h, capi.ptr(ms)))
