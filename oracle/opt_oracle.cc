@@ -173,6 +173,13 @@ struct LMProblem {
     virtual bool terminate() { return false; }
 };
 
+// What the last optimiser call decided (orc_opt_last_trace): the LM control's counts and how close any chi2 came to the threshold it was compared with.
+// Every orc_* optimiser entry resets it; the tests use it to keep their inputs away from decisions a float rounding could flip.
+struct OptTrace { int32_t trials, rejected, endedQmax, endedRho0, maxRejectedRun; double minMargin, minGain; };
+static thread_local OptTrace g_trace = {0, 0, 0, 0, 0, std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity()};
+static inline void trace_reset() { g_trace = OptTrace{0, 0, 0, 0, 0, std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity()}; }
+static inline void trace_threshold(double chi2, double th) { g_trace.minMargin = std::min(g_trace.minMargin, std::fabs(chi2 - th) / th); }
+
 static int lm_optimize(LMProblem &P, int iterations) {
     double lambda = -1, ni = 2;
     int nBad = 0, done = 0;
@@ -183,7 +190,7 @@ static int lm_optimize(LMProblem &P, int iterations) {
         P.build();
         if (it == 0) { lambda = tau * P.max_diag(); ni = 2; nBad = 0; }
         double rho = 0;
-        int qmax = 0;
+        int qmax = 0, rejectedRun = 0;
         do {
             P.push();
             const bool ok2 = P.solve(lambda);
@@ -191,6 +198,7 @@ static int lm_optimize(LMProblem &P, int iterations) {
             tempChi = P.robust_chi2();
             if (!ok2) tempChi = std::numeric_limits<double>::max();
             rho = currentChi - tempChi;
+            if (ok2) g_trace.minGain = std::min(g_trace.minGain, std::fabs(rho) / (currentChi > 0 ? currentChi : 1.));
             double sc = P.scale(lambda);
             sc += 1e-3;
             rho /= sc;
@@ -205,10 +213,14 @@ static int lm_optimize(LMProblem &P, int iterations) {
                 lambda *= ni;
                 ni *= 2;
                 P.pop();
+                g_trace.rejected++;
+                g_trace.maxRejectedRun = std::max(g_trace.maxRejectedRun, ++rejectedRun);
             }
             qmax++;
+            g_trace.trials++;
         } while (rho < 0 && qmax < 10 && !P.terminate());
         done++;
+        if (qmax == 10) g_trace.endedQmax++; else if (rho == 0) g_trace.endedRho0++;
         if (qmax == 10 || rho == 0) break;                 // Terminate
         if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
         if (nBad >= 3) break;
@@ -567,6 +579,7 @@ extern "C" {
 // (qx qy qz qw tx ty tz), outlier: n u8 out.  Returns nInitialCorrespondences - nBad (0 and no change if n < 3).
 int orc_pose_optimization(const float *Xw, const float *obs, const float *invSigma2, int n, const float *K4, float *Tcw7,
                           uint8_t *outlier) {
+    trace_reset();
     for (int i = 0; i < n; i++) outlier[i] = 0;
     if (n < 3) return 0;
     std::vector<V3> X(n);
@@ -596,6 +609,7 @@ int orc_pose_optimization(const float *Xw, const float *obs, const float *invSig
             // keep the error of the LAST computeActiveErrors(), which after 10 rejected trials is the rejected state.
             double e[2];
             const float chi2 = (float)(outlier[i] ? P.edge_chi2(i, e) : P.lastChi2[i]);
+            trace_threshold(chi2, chi2Mono[it]);
             if (chi2 > chi2Mono[it]) { outlier[i] = 1; active[i] = 0; nBad++; }
             else { outlier[i] = 0; active[i] = 1; }
         }
@@ -613,6 +627,7 @@ int orc_pose_optimization(const float *Xw, const float *obs, const float *invSig
 int orc_local_ba(int nKF, float *kfPose, const uint8_t *kfFixed, int nMP, float *mpPos, int nE, const int32_t *eMP,
                  const int32_t *eKF, const float *eObs, const float *eInvSigma2, const float *K4, const volatile uint8_t *stop,
                  uint8_t *eraseOut) {
+    trace_reset();
     if (stop && *stop) return -1;
     BAProblem P;
     P.nKF = nKF; P.nMP = nMP; P.nE = nE; P.fixedKF = kfFixed; P.eMP = eMP; P.eKF = eKF; P.stop = stop;
@@ -632,6 +647,7 @@ int orc_local_ba(int nKF, float *kfPose, const uint8_t *kfFixed, int nMP, float 
         V3 pc;
         P.edge_err(e, r, &pc);                                            // isDepthPositive() uses the current estimates
         const double chi2 = its > 0 ? P.lastChi2[e] : P.edge_err(e, r);   // e->chi2() = error of the last computeActiveErrors()
+        trace_threshold(chi2, 5.991);
         eraseOut[e] = (chi2 > 5.991 || !(pc.z > 0.0)) ? 1 : 0;
     }
     for (int k = 0; k < nKF; k++) if (!kfFixed[k]) se3_to_float7(P.T[k], kfPose + 7 * k);
@@ -644,6 +660,7 @@ int orc_local_ba(int nKF, float *kfPose, const uint8_t *kfFixed, int nMP, float 
 // of the two optimize() calls.  Returns -1 when the stop flag is already set (:3982-3984).
 int orc_merge_ba(int nKF, float *kfPose, const uint8_t *kfFixed, int nMP, float *mpPos, int nE, const int32_t *eMP, const int32_t *eKF,
                  const float *eObs, const float *eInvSigma2, const float *K4, const volatile uint8_t *stop, uint8_t *eraseOut, int32_t *its2) {
+    trace_reset();
     if (its2) its2[0] = its2[1] = 0;
     if (stop && *stop) return -1;
     BAProblem P;
@@ -667,6 +684,7 @@ int orc_merge_ba(int nKF, float *kfPose, const uint8_t *kfFixed, int nMP, float 
             V3 pc;
             P.edge_err(e, r, &pc);
             const double chi2 = its1 > 0 ? P.lastChi2[e] : P.edge_err(e, r);
+            trace_threshold(chi2, 5.991);
             if (chi2 > 5.991 || !(pc.z > 0.0)) P.level1[e] = 1;           // e->setLevel(1)
         }
         P.robust = false;                                                 // e->setRobustKernel(0)
@@ -678,6 +696,7 @@ int orc_merge_ba(int nKF, float *kfPose, const uint8_t *kfFixed, int nMP, float 
         V3 pc;
         P.edge_err(e, r, &pc);
         const double chi2 = its > 0 ? P.lastChi2[e] : P.edge_err(e, r);
+        trace_threshold(chi2, 5.991);
         eraseOut[e] = (chi2 > 5.991 || !(pc.z > 0.0)) ? 1 : 0;
     }
     for (int k = 0; k < nKF; k++) if (!kfFixed[k]) se3_to_float7(P.T[k], kfPose + 7 * k);
@@ -691,6 +710,7 @@ int orc_merge_ba(int nKF, float *kfPose, const uint8_t *kfFixed, int nMP, float 
 // optimize(nIterations), Huber(sqrt(5.99)) on every edge when bRobust.  Returns the LM iterations run.
 int orc_bundle_adjustment(int nKF, float *kfPose, const uint8_t *kfFixed, int nMP, float *mpPos, int nE, const int32_t *eMP, const int32_t *eKF,
                           const float *eObs, const float *eInvSigma2, const float *K4, const volatile uint8_t *stop, int nIterations, int bRobust) {
+    trace_reset();
     BAProblem P;
     P.nKF = nKF; P.nMP = nMP; P.nE = nE; P.fixedKF = kfFixed; P.eMP = eMP; P.eKF = eKF; P.stop = stop;
     P.T.resize(nKF); P.X.resize(nMP);
@@ -708,6 +728,17 @@ int orc_bundle_adjustment(int nKF, float *kfPose, const uint8_t *kfFixed, int nM
     for (int k = 0; k < nKF; k++) if (!kfFixed[k]) se3_to_float7(P.T[k], kfPose + 7 * k);
     for (int p = 0; p < nMP; p++) { mpPos[3 * p] = (float)P.X[p].x; mpPos[3 * p + 1] = (float)P.X[p].y; mpPos[3 * p + 2] = (float)P.X[p].z; }
     return its;
+}
+
+// The decisions of the last orc_pose_optimization / orc_local_ba / orc_merge_ba / orc_bundle_adjustment call of this thread:
+// counts[5] = LM trials run, rejected trials, iterations ended by qmax == 10, iterations ended by rho == 0, the most rejections in a row
+// inside one iteration (from the second on, the growth of ni decides the next lambda); margins[0] = the smallest
+// |chi2 - th| / th over every threshold comparison of the call (the four re-classification rounds of the pose optimisation, the level-1
+// marking and the erase test of the merge BA, the erase test of the local BA), infinity when it compared nothing; margins[1] = the smallest
+// |chi2 before - chi2 after| / chi2 before over the LM trials: how far the closest accept / reject decision was from a tie.
+void orc_opt_last_trace(int32_t *counts, double *margins) {
+    counts[0] = g_trace.trials; counts[1] = g_trace.rejected; counts[2] = g_trace.endedQmax; counts[3] = g_trace.endedRho0; counts[4] = g_trace.maxRejectedRun;
+    margins[0] = g_trace.minMargin; margins[1] = g_trace.minGain;
 }
 
 // Sim3Solver::ComputeInliersNum (R/lib_src/Sim3Solver.cc:564-664) on flat arrays (layout: include/rumi_opt.h, rumi_sim3_inliers).
@@ -886,6 +917,7 @@ void orc_sim3_ransac(int n, const float *X1, const float *X2, const float *sigma
 int orc_optimize_sim3(int n, const int32_t *pairOf, const double *Sc1w, const double *Sc2w, const float *P1c, const float *P2c,
                       const float *obs1, const float *obs2, const float *w1, const float *w2, const uint8_t *skip12, const uint8_t *skip21,
                       const float *K1, const float *K2, float th2, int fixScale, int robustFirst, double *S8, uint8_t *status, int32_t *res) {
+    trace_reset();                                                  // (LM counts only: the Sim3 threshold tests are not traced)
     Sim3Problem P;
     P.n = n; P.pairOf = pairOf; P.Sc1w = Sc1w; P.Sc2w = Sc2w; P.P1c = P1c; P.P2c = P2c; P.obs1 = obs1; P.obs2 = obs2; P.w1 = w1; P.w2 = w2;
     P.on12.resize(n); P.on21.resize(n); P.chi12.assign(n, 0.); P.chi21.assign(n, 0.);

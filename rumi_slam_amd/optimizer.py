@@ -104,9 +104,10 @@ class Optimizer:
         capi.check(rc)
         return stats, kp, mp, erase[:len(em)]
 
-    def LocalBundleAdjustmentBatch(self, windows, n_workers=4):
+    def LocalBundleAdjustmentBatch(self, windows, n_workers=4, return_status=False):
         """rumi_local_ba_batch: `windows` = list of (kf_pose, kf_fixed, mp_pos, e_mp, e_kf, e_obs, e_inv_sigma2, K4) tuples; returns one
-        (stats[4], kf_pose, mp_pos, erase[nE]) per window, as LocalBundleAdjustment does."""
+        (stats[4], kf_pose, mp_pos, erase[nE]) per window, as LocalBundleAdjustment does.  Any failure raises, unless return_status: then the
+        call returns (results, the batch's status, the status of every window) and a failed window's arrays are what the C entry left of them."""
         arr = (RumiBaWindow * len(windows))()
         keep = []
         for W, w in zip(arr, windows):
@@ -123,8 +124,10 @@ class Optimizer:
         t0 = time.perf_counter()
         rc = self._lib.rumi_local_ba_batch(self._h, len(windows), C.cast(arr, C.c_void_p), int(n_workers))
         self.last_call_s = time.perf_counter() - t0         # the C entry alone (the mirror above copies every array of every window)
-        capi.check(rc)
-        return [(np.array(W.stats, np.int32), k[0], k[2], k[8][:len(k[3])]) for W, k in zip(arr, keep)]
+        if not return_status:
+            capi.check(rc)
+        res = [(np.array(W.stats, np.int32), k[0], k[2], k[8][:len(k[3])]) for W, k in zip(arr, keep)]
+        return (res, int(rc), [int(W.status) for W in arr]) if return_status else res
 
     def BundleAdjustment(self, kf_pose, kf_fixed, mp_pos, e_mp, e_kf, e_obs, e_inv_sigma2, K4, n_iterations=5, robust=True, stop_flag=None):
         """Optimizer::BundleAdjustment (global BA): returns (stats[4], kf_pose, mp_pos)."""

@@ -313,6 +313,20 @@ def merge_ba(kf_pose, kf_fixed, mp_pos, e_mp, e_kf, e_obs, e_inv_sigma2, K4, sto
     return its2, kp, mp, erase
 
 
+def opt_last_trace():
+    """What the last pose_optimization / local_ba / merge_ba / bundle_adjustment call on this thread decided: dict(trials, rejected, ended_qmax,
+    ended_rho0, rejected_run, margin) -- LM trials run, rejected trials, iterations that ended by qmax == 10 and by rho == 0, the most rejections in a
+    row inside one iteration, the smallest
+    |chi2 - th| / th over every threshold comparison the call made (inf when it made none), and as `gain` the smallest relative change of chi2 any
+    trial made: how far the closest accept / reject decision was from a tie."""
+    L = _olib()
+    L.orc_opt_last_trace.restype = None
+    L.orc_opt_last_trace.argtypes = [C.c_void_p, C.c_void_p]
+    counts = np.zeros(5, np.int32); margin = np.zeros(2, np.float64)
+    L.orc_opt_last_trace(_p(counts), _p(margin))
+    return dict(trials=int(counts[0]), rejected=int(counts[1]), ended_qmax=int(counts[2]), ended_rho0=int(counts[3]), rejected_run=int(counts[4]), margin=float(margin[0]), gain=float(margin[1]))
+
+
 def search_by_bow_kf(k1, d1, mp1, fv1, k2, d2, mp2, fv2, mp_bad, nnratio, check_ori):
     k1 = np.ascontiguousarray(k1, KP_DTYPE); d1 = np.ascontiguousarray(d1, np.uint8); m1 = np.ascontiguousarray(mp1, np.int32)
     k2 = np.ascontiguousarray(k2, KP_DTYPE); d2 = np.ascontiguousarray(d2, np.uint8); m2 = np.ascontiguousarray(mp2, np.int32)
