@@ -72,6 +72,9 @@ int rumi_covis_set_point_observations(RumiCovis *c, int32_t n, const int32_t *id
  * edit: the next query uploads the changed records.  A point keeps its attributes until they are set again. */
 int rumi_covis_set_point_attributes(RumiCovis *c, int32_t n, const int32_t *ids, const float *pos, const float *normal, const float *min_dist,
                                     const float *max_dist, const uint8_t *desc);
+/* The length of a live slot's map-point row as the last rumi_covis_set_keyframes left it (host only, no device call); -1 for a slot that is
+ * not live or a missing handle.  For callers that size an output by it (rumi_search_in_neighbors_resident, rumi_mapping.h). */
+int32_t rumi_covis_row_length(const RumiCovis *c, int32_t slot);
 /* KeyFrame::isBad of n_kf live slots and MapPoint::isBad of n_pt points. */
 int rumi_covis_set_bad(RumiCovis *c, int32_t n_kf, const int32_t *slots, const uint8_t *kf_bad, int32_t n_pt, const int32_t *ids, const uint8_t *pt_bad);
 /* KeyFrame::GetMap of n live slots changed (map merge). */

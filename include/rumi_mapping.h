@@ -9,6 +9,7 @@
  *   R/lib_src/CameraModels/Pinhole.cpp:30-33,61-64   Pinhole::project / unprojectEig
  *   R/lib_src/MapPoint.cc:353-427, 450-518   MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth (rumi_refresh_map_points, below)
  *   R/lib_src/LocalMapping.cc:953-1079, 820-951   LocalMapping::KeyFrameCulling / CloudKeyFrameCulling (rumi_keyframe_culling, below)
+ *   R/lib_src/LocalMapping.cc:649-743, ORBmatcher.cc:1058-1161   the searches of LocalMapping::SearchInNeighbors (rumi_search_in_neighbors_resident, below)
  *
  * One call runs the whole neighbour loop: every neighbour's search, triangulation and gates in wide launches, then the only
  * order-dependent part (a feature that received a point from neighbour k is skipped for neighbour k + 1, ORBmatcher.cc:865) in
@@ -112,6 +113,49 @@ int rumi_create_new_map_points_resident(RumiMatcher *m, RumiCovis *c, int32_t cu
 
 /* The last call of either entry on this matcher, in ms: validation + packing | upload, kernels, download | write-out. */
 int rumi_newpts_stage_ms(const RumiMatcher *m, float *out3);
+
+/* ---- The search half of LocalMapping::SearchInNeighbors (R/lib_src/LocalMapping.cc:649-743) for every target key-frame in one call, over
+ * key-frames and points resident in a covisibility store.  ORBmatcher::Fuse (ORBmatcher.cc:1037-1174) first searches, then mutates; the index
+ * it finds for a (key-frame, point) pair reads the point's position, normal, distance range and descriptor and the key-frame's pose,
+ * key-points, descriptors, scale table and bounds.  Of these the member changes one before its final refresh (:730): MapPoint::Replace ends
+ * with ComputeDistinctiveDescriptors() on the surviving point (MapPoint.cc:321).  The forward gates (NULL, isBad, IsInKeyFrame) only ever
+ * close during the member, and every point the reverse pass searches stood in a target row at the call.  So the device answers both passes
+ * from the store as it stands, and the caller replays AddObservation / AddMapPoint / Replace in the reference's order, re-evaluating each
+ * gate when its turn comes.
+ * WHAT THE CALLER MUST DO BESIDES: compare GetDescriptor() of the survivor before and after every Replace of the forward pass.  A point
+ * of the current key-frame whose descriptor changed no longer has valid answers in fwd_best for the targets that follow: search it again
+ * for each of them (rumi_fuse_candidates with the live descriptor) before its turn.  Without that the map can differ from the reference's.
+ * The reverse answers need no second look: a forward survivor is in the current key-frame by then and is skipped, and a reverse survivor
+ * has been searched already.  facade/LocalMappingStep.h SearchInNeighborsResident does all of this.  Monocular, non-inertial. */
+#define RUMI_FUSE_MAX_TARGETS 640   /* 30 + 30 * 20 (LocalMapping.cc:651-677), rounded up */
+typedef struct RumiFuseKF {   /* what a bundle adjustment changes, and what the store does not keep */
+    float Tcw7[7];            /* as rumi_fuse_candidates takes it: qx qy qz qw tx ty tz of GetPose() */
+    float Ow[3];              /* GetCameraCenter() */
+    float bounds[4];          /* mnMinX, mnMinY, mnMaxX, mnMaxY */
+    float log_scale_factor;   /* mfLogScaleFactor */
+} RumiFuseKF;
+
+/* fwd_best [n_targets][n_cur], n_cur = the length of cur_slot's map-point row (= its feature count): the feature of target t that the point
+ * in entry i of that row fuses with: best_idx of rumi_fuse_candidates(..., check_reprojection = 1) on that target's features, pose and
+ * bounds, K4 from the store, and that point's attributes, byte for byte.  -1 where the search finds none, where the entry is -1, where the
+ * point is bad in the store, or where the point's observer row lists target_slots[t].
+ * rev_point / rev_best [rev_cap]: one entry per distinct point that stands in some target's row, is not bad and does not list cur_slot: its
+ * id and the feature of the current key-frame it fuses with (-1: none), in order of first occurrence with the targets walked in list order
+ * and their rows in ascending feature order (what LocalMapping.cc:710-724 produces on the unmutated map).  *n_rev their number.  rev_cap <
+ * *n_rev: RUMI_E_CAPACITY, fwd_best and *n_rev valid, the first rev_cap entries written.  The sum of the targets' feature counts always
+ * suffices.
+ * Host to device per call: the store's staged edits and staged features, and n_targets + 1 records of 60 bytes.  A query: the store is not
+ * changed.  Integer atomics only: two calls on the same state return the same bytes.
+ * RUMI_E_INVALID, nothing written: a missing argument; th <= 0; a pose, centre, bound or scale factor that is not finite, or empty bounds; a
+ * slot that is not live or holds no features; a slot named twice, cur_slot among the targets; a slot whose feature count differs from the
+ * length of its map-point row; matcher and store on different devices; a point that would be searched but has no attributes (found on the
+ * device; the message names how many).  RUMI_E_CAPACITY, nothing written: n_targets > RUMI_FUSE_MAX_TARGETS; a key-frame above the matcher's
+ * max_features.  n_targets == 0: RUMI_OK, *n_rev = 0, no device call. */
+int rumi_search_in_neighbors_resident(RumiMatcher *m, RumiCovis *c, int32_t cur_slot, const RumiFuseKF *cur, const int32_t *target_slots,
+                                      const RumiFuseKF *targets, int32_t n_targets, float th, int32_t *fwd_best, int32_t *rev_point,
+                                      int32_t *rev_best, int32_t rev_cap, int32_t *n_rev);
+/* The last call on this matcher, in ms: validation + table | upload, kernels, download | write-out. */
+int rumi_search_in_neighbors_stage_ms(const RumiMatcher *m, float *out3);
 
 /* ---- MapPoint::ComputeDistinctiveDescriptors (R/lib_src/MapPoint.cc:353-427) and MapPoint::UpdateNormalAndDepth (:450-518) for a batch of
  * points.  Neither member reads another MapPoint: a point's result depends on its own observation list, its position and reference

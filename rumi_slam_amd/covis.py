@@ -60,6 +60,10 @@ class Covisibility:
         return self._ret(self._lib.rumi_covis_set_keyframes(self._h, n, _p(slots), _p(keys), _p(maps), _p(bad), _p(mo), _p(mp), _p(b), _p(parents),
                                                             _p(co), _p(ch)), check)
 
+    def row_length(self, slot):
+        """Length of a live slot's map-point row as the store holds it; -1 for a slot that is not live."""
+        return int(self._lib.rumi_covis_row_length(self._h, int(slot)))
+
     def set_points(self, ids, bad, observers, check=True):
         ids = np.ascontiguousarray(ids, _i32); bad = np.ascontiguousarray(bad, _u8)
         oo, ob = _csr(list(observers))

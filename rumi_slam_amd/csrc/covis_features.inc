@@ -232,6 +232,10 @@ extern "C" int rumi_covis_drop_keyframe_features(RumiCovis *h, int32_t n, const 
     return RUMI_OK;
 }
 
+extern "C" int32_t rumi_covis_row_length(const RumiCovis *h, int32_t slot) {
+    return h && is_live(h, slot) ? h->kf[(size_t)slot * KFW + K_MPLEN] : -1;
+}
+
 extern "C" int rumi_covis_feature_stats(const RumiCovis *h, int64_t *out6) {
     if (!h || !out6) return RUMI_E_INVALID;
     const FeatureStore &F = h->feat;
@@ -276,7 +280,7 @@ int rumi::covis_features_flush(RumiCovis *h, CovisFeatureView *view) {
     int rc;
     uint8_t *unused = nullptr;
     if ((rc = flush(h, nullptr, 0, &unused)) != RUMI_OK || (rc = feat_flush(h)) != RUMI_OK) return rc;
-    *view = CovisFeatureView{h->dArena.p, h->dPt.p, h->dAttr.p, h->feat.arena.p};
+    *view = CovisFeatureView{h->dArena.p, h->dPt.p, h->dAttr.p, h->feat.arena.p, h->maxKf, h->maxPts};
     return RUMI_OK;
 }
 

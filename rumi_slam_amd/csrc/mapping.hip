@@ -8,10 +8,13 @@
 //   gate[k][i1]  whether (i1, cand[k][i1]) triangulates and passes every test depends on the two key-frames alone.
 //   replay       for k = 0, 1, ...: baseline skip; the pairs whose i1 is still free; the rotation histogram over exactly those; survivors
 //                with gate == 0 create a point and take i1 out.
+//
+// The searches of LocalMapping::SearchInNeighbors over the same store: search_in_neighbors.inc, included at the end of this file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <type_traits>
@@ -21,6 +24,7 @@
 #include "rumi_testhooks.h"
 #include "keyframe_features.h"
 #include "match_host.h"
+#include "match_grid.h"
 
 namespace rumi {
 
@@ -462,6 +466,9 @@ __global__ __launch_bounds__(256) void k_newpts_gather(const ResKF *__restrict__
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
+struct SinState;                                             // the blocks of rumi_search_in_neighbors_resident (search_in_neighbors.inc)
+static void sin_destroy(SinState *s);
+
 struct NewPtsState {
     MirrorBuf<uint8_t> blk, res;                             // the upload block; the result block, a NewPtsResult and its points
     DevBuf<int32_t> cand, matched; DevBuf<uint8_t> gate; DevBuf<float> x3D;      // a candidate, a gate and a point (three floats) per (neighbour, feature) pair
@@ -469,9 +476,14 @@ struct NewPtsState {
     int lastNeigh = 0, lastN1 = 0, lastOri = 0;              // the last block call, whose device state rumi_hook_newpts_matches replays
     StageClock clock;
     float stageMs[3] = {0.f, 0.f, 0.f};
+    SinState *sin = nullptr;                                 // with the first SearchInNeighbors call
 };
 
-static void newpts_destroy(void *p) { delete static_cast<NewPtsState *>(p); }     // rumi_match_destroy has made the matcher's device current
+static void newpts_destroy(void *p) {                        // rumi_match_destroy has made the matcher's device current
+    NewPtsState *s = static_cast<NewPtsState *>(p);
+    if (s->sin) sin_destroy(s->sin);
+    delete s;
+}
 
 static bool kf_valid(const RumiNewPointsKF &k, bool neighbour, const char **why) {
     *why = "key-frame features: bad sizes or missing arrays";
@@ -706,3 +718,5 @@ extern "C" int rumi_hook_newpts_matches(RumiMatcher *m, int32_t n_neigh, int32_t
     HIP_TRY(hipMemcpy(matches, s->matched.p, pairs * 4, hipMemcpyDeviceToHost));
     return RUMI_OK;
 }
+
+#include "search_in_neighbors.inc"

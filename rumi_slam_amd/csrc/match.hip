@@ -29,6 +29,7 @@
 //   match_bow_batch.inc   k_bow_batch_match, k_bow_batch_finish (BowKF, BowBatch) and rumi_search_by_bow_batch
 //   match_bow_kf_batch.inc  k_crb_match, k_crb_finish, k_crb_union (CrKF, CrArgs) and rumi_common_regions_bow
 //   match_submap.inc      k_grid_batch, k_submap_match, k_submap_compact (SubFrame, SubPair) and rumi_submap_match
+//   match_grid.h          grid_build_xy, the one-workgroup grid of k_grid_batch (shared with mapping.hip's k_sin_grid)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,10 +40,9 @@
 #include <vector>
 
 #include "match_host.h"
+#include "match_grid.h"
 
 namespace rumi {
-
-constexpr int kMaxSortN = 16384;     // features per frame: the mono-initialisation extractor asks for 5 x nfeatures (Tracking.cc:581: 10 000 with TUM3.yaml)
 
 // ---- 1. grid -----------------------------------------------------------------------------------------------
 // Frame::AssignFeaturesToGrid as a counting sort by cell (cell = column-major ix*48+iy, the order GetFeaturesInArea walks),

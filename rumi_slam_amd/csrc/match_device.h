@@ -79,6 +79,47 @@ __device__ __forceinline__ int predict_scale(float maxDistance, float dist, floa
     return nScale;
 }
 
+__device__ __forceinline__ void se3f_mul(const float *T, const float *p, float *o) {   // Sophus::SE3f * p (so3.hpp:358-367)
+    const float qx = T[0], qy = T[1], qz = T[2], qw = T[3];
+    float u0 = qy * p[2] - qz * p[1], u1 = qz * p[0] - qx * p[2], u2 = qx * p[1] - qy * p[0];
+    u0 += u0; u1 += u1; u2 += u2;
+    const float c0 = qy * u2 - qz * u1, c1 = qz * u0 - qx * u2, c2 = qx * u1 - qy * u0;
+    o[0] = ((p[0] + qw * u0) + c0) + T[4]; o[1] = ((p[1] + qw * u1) + c1) + T[5]; o[2] = ((p[2] + qw * u2) + c2) + T[6];
+}
+
+// The projection and gates of one point for SearchByProjection(KeyFrame*, Sim3f&, points, ...) (ORBmatcher.cc:389-436, variant 0; :491-539,
+// variant 1) and Fuse (:1058-1112): depth, KeyFrame::IsInImage, the distance range, the viewing angle, the predicted level and the window.
+// One body for k_queries_sim3 (match_queries.inc) and the SearchInNeighbors kernels (search_in_neighbors.inc): their results are compared
+// byte for byte.  The caller fills descId, mpId, blocks and c0.
+__device__ __forceinline__ Query sim3_query(const float *p3Dw, const float *Pn, float minDist, float maxDist, const float *Tcw, const float *K,
+                                            const float *Ow, const float *scaleFactors, int nLevels, float logScaleFactor, float th, int variant,
+                                            float minX, float minY, float maxX, float maxY) {
+    Query o{};
+    float pc[3];
+    se3f_mul(Tcw, p3Dw, pc);
+    if (!(pc[2] < 0.0f)) {
+        float u, v;
+        if (variant == 0) { u = K[0] * pc[0] / pc[2] + K[2]; v = K[1] * pc[1] / pc[2] + K[3]; }
+        else { const float invz = 1 / pc[2]; const float x = pc[0] * invz, y = pc[1] * invz; u = K[0] * x + K[2]; v = K[1] * y + K[3]; }
+        if (u >= minX && u < maxX && v >= minY && v < maxY) {                       // KeyFrame::IsInImage
+            const float maxD = 1.2f * maxDist, minD = 0.8f * minDist;
+            const float P0 = p3Dw[0] - Ow[0], P1 = p3Dw[1] - Ow[1], P2 = p3Dw[2] - Ow[2];
+            const float dist = sqrtf((P0 * P0 + P1 * P1) + P2 * P2);
+            if (!(dist < minD || dist > maxD) && !((double)((P0 * Pn[0] + P1 * Pn[1]) + P2 * Pn[2]) < 0.5 * (double)dist)) {
+                const int lvl = predict_scale(maxDist, dist, logScaleFactor, nLevels);
+                o.valid = 1; o.u = u; o.v = v; o.r = th * scaleFactors[lvl];
+                o.minLevel = lvl - 1; o.maxLevel = lvl;                              // the level test of :445-448 / :553-556
+            }
+        }
+    }
+    return o;
+}
+
+// A 16-byte load that asks for 4-byte alignment only (the extractor's descriptor kernel loads its rows the same way, orb_orient_desc.inc):
+// one wide instruction where the address happens to be aligned, never a fault where a row is not.
+struct __attribute__((packed, aligned(4))) Dword4 { uint32_t x, y, z, w; };
+__device__ __forceinline__ uint4 ld16_dword(const void *q) { const Dword4 t = *reinterpret_cast<const Dword4 *>(q); return make_uint4(t.x, t.y, t.z, t.w); }
+
 // Correspondences of Optimizer::PoseOptimization(Frame*) (Optimizer.cc:749-815, mono): the features with a map point, in feature order.
 // One workgroup of 1024 threads, ordered compaction (ballot + wave offsets through LDS, chunks of 1024 features).
 __device__ __forceinline__ void gather_correspondences(int n, const RumiKeyPoint *__restrict__ keys, const int32_t *featMp, const float *__restrict__ mpPos,

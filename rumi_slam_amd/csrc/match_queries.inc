@@ -67,15 +67,7 @@ __global__ void k_queries_bow(int nnKF, const uint32_t *kfNodes, const int32_t *
     q[p] = o;
 }
 
-__device__ __forceinline__ void se3f_mul(const float *T, const float *p, float *o) {   // Sophus::SE3f * p (so3.hpp:358-367)
-    const float qx = T[0], qy = T[1], qz = T[2], qw = T[3];
-    float u0 = qy * p[2] - qz * p[1], u1 = qz * p[0] - qx * p[2], u2 = qx * p[1] - qy * p[0];
-    u0 += u0; u1 += u1; u2 += u2;
-    const float c0 = qy * u2 - qz * u1, c1 = qz * u0 - qx * u2, c2 = qx * u1 - qy * u0;
-    o[0] = ((p[0] + qw * u0) + c0) + T[4]; o[1] = ((p[1] + qw * u1) + c1) + T[5]; o[2] = ((p[2] + qw * u2) + c2) + T[6];
-}
-
-// SearchByProjection(KeyFrame*, Sim3f&, points, ...): ORBmatcher.cc:389-436 (variant 0) / :491-539 (variant 1)
+// SearchByProjection(KeyFrame*, Sim3f&, points, ...): ORBmatcher.cc:389-436 (variant 0) / :491-539 (variant 1); the arithmetic is sim3_query's (match_device.h)
 __global__ void k_queries_sim3(int nmp, const uint8_t *skip, const float *mpPos, const float *mpNormal, const float *mpMinDist,
                                const float *mpMaxDist, const float *pose /*Tcw7, K4, Ow3*/, const float *scaleFactors, int nLevels,
                                float logScaleFactor, float th, int variant, int blocks, int checkReproj, float minX, float minY, float maxX, float maxY,
@@ -83,29 +75,10 @@ __global__ void k_queries_sim3(int nmp, const uint8_t *skip, const float *mpPos,
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nmp) return;
     Query o{};
+    if (!skip[i])
+        o = sim3_query(mpPos + (size_t)i * 3, mpNormal + (size_t)i * 3, mpMinDist[i], mpMaxDist[i], pose, pose + 7, pose + 11, scaleFactors, nLevels,
+                       logScaleFactor, th, variant, minX, minY, maxX, maxY);
     o.descId = i; o.mpId = i; o.blocks = blocks; o.c0 = checkReproj;
-    const float *Tcw = pose, *K = pose + 7, *Ow = pose + 11;
-    if (!skip[i]) {
-        const float *p3Dw = mpPos + (size_t)i * 3;
-        float pc[3];
-        se3f_mul(Tcw, p3Dw, pc);
-        if (!(pc[2] < 0.0f)) {
-            float u, v;
-            if (variant == 0) { u = K[0] * pc[0] / pc[2] + K[2]; v = K[1] * pc[1] / pc[2] + K[3]; }
-            else { const float invz = 1 / pc[2]; const float x = pc[0] * invz, y = pc[1] * invz; u = K[0] * x + K[2]; v = K[1] * y + K[3]; }
-            if (u >= minX && u < maxX && v >= minY && v < maxY) {                       // KeyFrame::IsInImage
-                const float maxD = 1.2f * mpMaxDist[i], minD = 0.8f * mpMinDist[i];
-                const float P0 = p3Dw[0] - Ow[0], P1 = p3Dw[1] - Ow[1], P2 = p3Dw[2] - Ow[2];
-                const float dist = sqrtf((P0 * P0 + P1 * P1) + P2 * P2);
-                const float *Pn = mpNormal + (size_t)i * 3;
-                if (!(dist < minD || dist > maxD) && !((double)((P0 * Pn[0] + P1 * Pn[1]) + P2 * Pn[2]) < 0.5 * (double)dist)) {
-                    const int lvl = predict_scale(mpMaxDist[i], dist, logScaleFactor, nLevels);
-                    o.valid = 1; o.u = u; o.v = v; o.r = th * scaleFactors[lvl];
-                    o.minLevel = lvl - 1; o.maxLevel = lvl;                              // the level test of :445-448 / :553-556
-                }
-            }
-        }
-    }
     q[i] = o;
 }
 

@@ -21,70 +21,10 @@ struct SubFrame {
 };
 struct SubPair { int32_t f1, f2, qStart, pad; };
 
-// Frame::AssignFeaturesToGrid for one frame by one workgroup of 1024: k_grid's counting sort by cell (column-major, ascending key-point index inside a
-// cell), restated here over x, y pairs.  (Giving k_grid and this kernel one body moved k_grid's LDS arrays and rescheduled its scan; k_grid stays as it is.)
-__device__ __forceinline__ void grid_build_xy(int n, const float *__restrict__ xy, float minX, float minY, float wInv, float hInv, uint16_t *__restrict__ sortedIdx,
-                                           int32_t *__restrict__ cellStart) {
-    __shared__ int32_t sCnt[kGridCells + 1];
-    __shared__ uint16_t sCell[kMaxSortN], sOut[kMaxSortN];
-    __shared__ int32_t sWave[16];
-    const int tid = threadIdx.x;
-    for (int c = tid; c <= kGridCells; c += 1024) sCnt[c] = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += 1024) {
-        // Frame::PosInGrid: round() of the float expression, dropped when outside the grid
-        const int px = (int)__builtin_roundf((xy[2 * i] - minX) * wInv);
-        const int py = (int)__builtin_roundf((xy[2 * i + 1] - minY) * hInv);
-        uint16_t cell = 0xFFFF;
-        if (px >= 0 && px < kGridCols && py >= 0 && py < kGridRows) { cell = (uint16_t)(px * kGridRows + py); atomicAdd(&sCnt[cell], 1); }
-        sCell[i] = cell;
-    }
-    __syncthreads();
-    // exclusive scan of the 3072 counts: 3 cells per thread, a DPP scan inside each wave, the 16 wave totals through LDS (one barrier)
-    constexpr int kPer = (kGridCells + 1023) / 1024;
-    int loc[kPer], sum = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; k++) { const int c = tid * kPer + k; loc[k] = c < kGridCells ? sCnt[c] : 0; sum += loc[k]; }
-    const int incl = wave_scan_incl_i32(sum);
-    if ((tid & 63) == 63) sWave[tid >> 6] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) { const int t = sWave[w]; total += t; if (w < (tid >> 6)) before += t; }
-    int run = before + incl - sum;
-#pragma unroll
-    for (int k = 0; k < kPer; k++) {
-        const int c = tid * kPer + k;
-        if (c < kGridCells) { cellStart[c] = run; sCnt[c] = run; run += loc[k]; }
-    }
-    if (tid == 1023) cellStart[kGridCells] = total;
-    __syncthreads();
-    for (int i = tid; i < n; i += 1024) {
-        const uint16_t cell = sCell[i];
-        if (cell != 0xFFFF) sOut[atomicAdd(&sCnt[cell], 1)] = (uint16_t)i;
-    }
-    __syncthreads();
-    // sCnt[c] is now the END of cell c; its start is the end of cell c-1 (or 0)
-#pragma unroll
-    for (int k = 0; k < kPer; k++) {
-        const int c = tid * kPer + k;
-        if (c >= kGridCells) continue;
-        const int e = sCnt[c], b0 = e - loc[k];
-        for (int i = b0 + 1; i < e; i++) {
-            const uint16_t v = sOut[i];
-            int j = i - 1;
-            while (j >= b0 && sOut[j] > v) { sOut[j + 1] = sOut[j]; j--; }
-            sOut[j + 1] = v;
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < total; i += 1024) sortedIdx[i] = sOut[i];
-}
-
 __global__ __launch_bounds__(1024) void k_grid_batch(const SubFrame *__restrict__ frames, const int32_t *__restrict__ gridFrames, uint16_t *__restrict__ sorted,
                                                      int32_t *__restrict__ cellStart) {
     const SubFrame F = frames[gridFrames[blockIdx.x]];
-    grid_build_xy(F.n, F.keysUn, F.minX, F.minY, F.wInv, F.hInv, sorted + F.sortedOff, cellStart + (size_t)blockIdx.x * (kGridCells + 1));
+    grid_build_xy<2>(F.n, F.keysUn, F.minX, F.minY, F.wInv, F.hInv, sorted + F.sortedOff, cellStart + (size_t)blockIdx.x * (kGridCells + 1));
 }
 
 // The number of set predicates in the workgroup (256 threads) in front of this thread, and the workgroup's total.

@@ -53,6 +53,7 @@ struct CovisSlotFeatures { int32_t n, nn, ne, mpOff, mpLen; int64_t block; };   
 struct CovisFeatureView {
     const int32_t *rows, *pt, *attr;   // the row arena, [max_points][kCovisPointWords], [max_points][kCovisAttrWords] (null: no point has attributes)
     const uint8_t *feat;               // the feature arena
+    int maxKf, maxPoints;              // slots and point ids the tables hold
 };
 // Host only: every slot live, with features, named once, feature count == length of its mp row; with wantDevice >= 0 the store on that
 // device (a store without a device yet takes it).  Refused with RUMI_E_INVALID and the message set.

@@ -13,16 +13,23 @@
 //     step.KeyFrameCulling(mpCurrentKeyFrame, mbInertial, mbMonocular, mbAbortBA);
 //     step.CloudKeyFrameCulling(mpCurrentKeyFrame, mbInertial, mbMonocular, mbAbortBA);
 // one device call judges the whole covisible list (rumi_keyframe_culling); SetBadFlag() is then applied in the returned order.
+//
+// LocalMapping::SearchInNeighbors (:649-743), with a CovisibilityGraph that holds the map, becomes
+//     step.SearchInNeighborsResident<MapPoint>(graph, mpCurrentKeyFrame, mbMonocular, mbInertial, mbAbortBA);
+// one device call answers every search of both passes (rumi_search_in_neighbors_resident); the reference's own objects replay the mutations.
 // With a CovisibilityGraph that holds the map, step.KeyFrameCullingResident(graph, ...) / CloudKeyFrameCullingResident(graph, ...) send the
 // candidates' slots instead of the neighbourhood's tables (rumi_keyframe_culling_resident).
 #pragma once
+#include <cstring>
 #include <map>
+#include <set>
 #include <tuple>
 #include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <vector>
 
+#include "MapPointRefresh.h"
 #include "ORBmatcher.h"
 #include "rumi_mapping.h"
 
@@ -167,6 +174,144 @@ public:
         }
         return n;
     }
+
+    // LocalMapping::SearchInNeighbors (R/lib_src/LocalMapping.cc:649-743), monocular and non-inertial, over a CovisibilityGraph that holds
+    // the map.  The target list is built as :651-677 builds it (stamps, isBad skips, the mbAbortBA break); FlushDirty(); ONE device call
+    // answers every search of the forward and of the reverse pass from the store as it stands (rumi_search_in_neighbors_resident); then the
+    // reference's own objects replay both passes in order, every gate re-evaluated at its turn, as Fuse above does for one target.
+    // MapPoint::Replace ends with ComputeDistinctiveDescriptors() on the survivor (MapPoint.cc:321): a point of the current key-frame whose
+    // GetDescriptor() a Replace changed is searched again, on its live descriptor, for every target that follows (one small
+    // rumi_fuse_candidates call per such target; *nSearchedAgain counts the pairs).  A reverse candidate that is not bad, not in the current
+    // key-frame and missing from the call's table contradicts the store: reported (RUMI_E_INVALID, counted) and skipped, never searched on
+    // the host.  Then RefreshKeyFramePoints (:730-739) and graph.UpdateConnections({current}) (:742).  The touched key-frames and points are
+    // staged again (Sync, MarkDirty), so the graph is current when the member returns.
+    // Returns the two passes' nFused together, or -1 with a report and nothing mutated: mbInertial (the temporal extension :680-691),
+    // NLeft != -1 on any key-frame, a key-frame the graph has never seen or without SyncFeatures, more targets than RUMI_FUSE_MAX_TARGETS,
+    // a failed device call.  The caller keeps the reference's member for those.
+    template <class MapPointT, class GraphT, class KeyFrameT>
+    int SearchInNeighborsResident(GraphT &graph, KeyFrameT *pCurrentKF, bool bMonocular, bool bInertial, const volatile bool &bAbortBA,
+                                  int *nSearchedAgain = nullptr, int *nContradictions = nullptr) {
+        static const char *where = "LocalMappingStep::SearchInNeighborsResident";
+        if (nSearchedAgain) *nSearchedAgain = 0;
+        if (nContradictions) *nContradictions = 0;
+        if (bInertial) {
+            rumi_facade::report(where, RUMI_E_INVALID, "mbInertial: the temporal extension (LocalMapping.cc:680-691) is not built; nothing was fused");
+            return -1;
+        }
+        if (!graph.ok()) { rumi_facade::report(where, RUMI_E_INVALID, "no store; nothing was fused"); return -1; }
+        // ---- 1. the targets (:651-677).  The stamps are written once nothing can refuse any more; until then `in` stands for them.
+        std::vector<KeyFrameT *> vpTargetKFs;
+        std::set<KeyFrameT *> in;
+        auto taken = [&](KeyFrameT *k) { return k->isBad() || k->mnFuseTargetForKF == pCurrentKF->mnId || in.count(k) > 0; };
+        for (KeyFrameT *pKFi : pCurrentKF->GetBestCovisibilityKeyFrames(bMonocular ? 30 : 10)) {
+            if (taken(pKFi)) continue;
+            vpTargetKFs.push_back(pKFi); in.insert(pKFi);
+        }
+        for (int i = 0, imax = (int)vpTargetKFs.size(); i < imax; i++) {
+            for (KeyFrameT *pKFi2 : vpTargetKFs[i]->GetBestCovisibilityKeyFrames(20)) {
+                if (taken(pKFi2) || pKFi2->mnId == pCurrentKF->mnId) continue;
+                vpTargetKFs.push_back(pKFi2); in.insert(pKFi2);
+            }
+            if (bAbortBA) break;
+        }
+        const int nT = (int)vpTargetKFs.size();
+        if (nT > RUMI_FUSE_MAX_TARGETS) { rumi_facade::report(where, RUMI_E_INVALID, "more targets than RUMI_FUSE_MAX_TARGETS; nothing was fused"); return -1; }
+        std::vector<int32_t> slots(nT > 0 ? nT : 1);
+        for (int k = -1; k < nT; k++) {
+            KeyFrameT *pKF = k < 0 ? pCurrentKF : vpTargetKFs[k];
+            if (pKF->NLeft != -1) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a key-frame with NLeft != -1: only the monocular Fuse is built; nothing was fused");
+                return -1;
+            }
+            if (graph.SlotOf(pKF) < 0 || !graph.HasFeatures(pKF)) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a key-frame the graph has never seen or without resident features (graph.Sync, graph.SyncFeatures); nothing was uploaded, nothing was fused");
+                return -1;
+            }
+            if (k >= 0) slots[k] = graph.SlotOf(pKF);
+        }
+        // ---- 2., 3. one call
+        if (graph.FlushDirty() != RUMI_OK) return -1;
+        std::vector<RumiFuseKF> rec(nT + 1);
+        size_t revCap = 0;
+        for (int k = 0; k <= nT; k++) {
+            KeyFrameT *pKF = k ? vpTargetKFs[k - 1] : pCurrentKF;
+            fuse_pose(pKF, rec[k].Tcw7, rec[k].Ow);
+            rec[k].bounds[0] = pKF->mnMinX; rec[k].bounds[1] = pKF->mnMinY; rec[k].bounds[2] = pKF->mnMaxX; rec[k].bounds[3] = pKF->mnMaxY;
+            rec[k].log_scale_factor = pKF->mfLogScaleFactor;
+            if (k) revCap += (size_t)pKF->N;
+        }
+        const int nCur = pCurrentKF->N;
+        const float th = 3.0f;                                                  // Fuse's default, as :699 and :726 call it
+        std::vector<int32_t> fwd((size_t)nT * nCur + 1), revPoint(revCap + 1), revBest(revCap + 1);
+        int32_t nRev = 0;
+        if (RUMI_GUARDED("LocalMappingStep / rumi_search_in_neighbors_resident", &ORBmatcher::grow_arena,
+                         rumi_search_in_neighbors_resident(arena(), graph.handle(), graph.SlotOf(pCurrentKF), &rec[0], slots.data(), rec.data() + 1, nT, th,
+                                                           fwd.data(), revPoint.data(), revBest.data(), (int32_t)revCap, &nRev)) != RUMI_OK)
+            return -1;
+        for (KeyFrameT *pKFi : vpTargetKFs) pKFi->mnFuseTargetForKF = pCurrentKF->mnId;
+        // ---- 4. the forward pass (:694-701)
+        FuseTouched<KeyFrameT, MapPointT> touched;
+        const std::vector<MapPointT *> vpMapPointMatches = pCurrentKF->GetMapPointMatches();   // copied once (:695)
+        int nFused = 0;
+        bool failed = false;
+        for (int t = 0; t < nT && !failed; t++) {
+            KeyFrameT *pKFi = vpTargetKFs[t];
+            std::vector<int32_t> best(fwd.begin() + (size_t)t * nCur, fwd.begin() + (size_t)(t + 1) * nCur);
+            if (!touched.changed.empty()) {                                     // survivors whose descriptor a Replace changed: their answers are stale
+                std::vector<int> at;
+                std::vector<MapPointT *> again;
+                for (int i = 0; i < nCur && i < (int)vpMapPointMatches.size(); i++) {
+                    MapPointT *p = vpMapPointMatches[i];
+                    if (p && touched.changed.count(p) && !p->isBad() && !p->IsInKeyFrame(pKFi)) { at.push_back(i); again.push_back(p); }
+                }
+                if (!again.empty()) {
+                    float T7[7], Ow[3];
+                    fuse_pose(pKFi, T7, Ow);
+                    std::vector<int32_t> sub;
+                    if (!fuse_search(pKFi, T7, Ow, again, [](MapPointT *) { return false; }, th, 1, sub)) { failed = true; break; }
+                    for (size_t j = 0; j < at.size(); j++) best[at[j]] = sub[j];
+                    if (nSearchedAgain) *nSearchedAgain += (int)at.size();
+                }
+            }
+            nFused += fuse_replay(pKFi, vpMapPointMatches, best, touched);
+        }
+        // ---- 5. (:703), and a second search that failed: what was replayed stays, as it does when the reference returns here
+        if (failed || bAbortBA) { touched.stage(graph); return failed ? -1 : nFused; }
+        // ---- 6. the reverse candidates (:706-724), on the map as the forward pass left it
+        std::vector<MapPointT *> vpFuseCandidates;
+        for (KeyFrameT *pKFi : vpTargetKFs)
+            for (MapPointT *pMP : pKFi->GetMapPointMatches()) {
+                if (!pMP) continue;
+                if (pMP->isBad() || pMP->mnFuseCandidateForKF == pCurrentKF->mnId) continue;
+                pMP->mnFuseCandidateForKF = pCurrentKF->mnId;
+                vpFuseCandidates.push_back(pMP);
+            }
+        // ---- 7. the reverse pass (:726) from the call's table
+        std::unordered_map<int32_t, int32_t> table;
+        for (int j = 0; j < nRev; j++) table[revPoint[j]] = revBest[j];
+        std::vector<int32_t> best(vpFuseCandidates.size(), -1);
+        int contradictions = 0;
+        for (size_t i = 0; i < vpFuseCandidates.size(); i++) {
+            MapPointT *pMP = vpFuseCandidates[i];
+            if (pMP->isBad() || pMP->IsInKeyFrame(pCurrentKF)) continue;        // Fuse skips it whatever the table says
+            auto it = table.find(graph.IdOf(pMP));
+            if (it != table.end()) best[i] = it->second;
+            else contradictions++;                                              // not searched at the call: skipped, not searched here
+        }
+        if (contradictions) {
+            rumi_facade::report(where, RUMI_E_INVALID, "reverse candidates that the store did not hold in a target row at the call (graph.Sync missing somewhere); they were skipped");
+            if (nContradictions) *nContradictions = contradictions;
+        }
+        nFused += fuse_replay(pCurrentKF, vpFuseCandidates, best, touched);
+        // ---- 8. Update points (:730-739)
+        rumi_facade::RefreshKeyFramePoints(pCurrentKF);
+        for (MapPointT *pMP : pCurrentKF->GetMapPointMatches())
+            if (pMP && !pMP->isBad()) graph.MarkDirty(pMP);
+        // ---- 9. (:742)
+        touched.stage(graph);
+        graph.UpdateConnections(std::vector<KeyFrameT *>{pCurrentKF}, false);
+        return nFused;
+    }
 #endif  // RUMI_HAVE_SOPHUS
 
     // The reference's loop over GetVectorCovisibleKeyFrames() after UpdateBestCovisibles(), non-inertial and monocular.  mbAbortBA is read once,
@@ -196,6 +341,63 @@ public:
     }
 
 protected:
+#ifdef RUMI_HAVE_SOPHUS
+    // What the replay of Fuse changed: key-frames whose rows and points whose observers or bad flag the store must see again, and the
+    // survivors of a Replace whose descriptor it changed.
+    template <class KeyFrameT, class MapPointT> struct FuseTouched {
+        std::set<KeyFrameT *> kfs;
+        std::set<MapPointT *> pts, changed;
+        template <class GraphT> void stage(GraphT &graph) {
+            for (KeyFrameT *k : kfs) graph.Sync(k);
+            for (MapPointT *p : pts) graph.Sync(p);
+            for (MapPointT *p : changed) graph.MarkDirty(p);
+            kfs.clear(); pts.clear();
+        }
+    };
+
+    template <class KeyFrameT> static void fuse_pose(KeyFrameT *pKF, float *T7, float *Ow) {      // as Fuse (ORBmatcher.h) forms them
+        const auto Tcw = pKF->GetPose();
+        const auto q = Tcw.unit_quaternion();
+        const auto t = Tcw.translation();
+        T7[0] = q.x(); T7[1] = q.y(); T7[2] = q.z(); T7[3] = q.w(); T7[4] = t(0); T7[5] = t(1); T7[6] = t(2);
+        const Eigen::Vector3f c = pKF->GetCameraCenter();
+        Ow[0] = c(0); Ow[1] = c(1); Ow[2] = c(2);
+    }
+
+    // ORBmatcher.cc:1045-1056 and :1162-1174 over `pts` with the search's answers in `best`: the loop of Fuse (ORBmatcher.h), which also notes
+    // what it touched and compares the survivor's descriptor around every Replace.
+    template <class KeyFrameT, class MapPointT>
+    static int fuse_replay(KeyFrameT *pKF, const std::vector<MapPointT *> &pts, const std::vector<int32_t> &best, FuseTouched<KeyFrameT, MapPointT> &touched) {
+        int nFused = 0;
+        for (size_t i = 0; i < pts.size() && i < best.size(); i++) {
+            MapPointT *pMP = pts[i];
+            if (!pMP) continue;
+            if (pMP->isBad()) continue;
+            else if (pMP->IsInKeyFrame(pKF)) continue;
+            if (best[i] < 0) continue;
+            MapPointT *pMPinKF = pKF->GetMapPoint(best[i]);
+            if (pMPinKF) {
+                if (!pMPinKF->isBad()) {
+                    const bool keepInKF = pMPinKF->Observations() > pMP->Observations();
+                    MapPointT *gone = keepInKF ? pMP : pMPinKF, *stays = keepInKF ? pMPinKF : pMP;
+                    for (const auto &o : gone->GetObservations()) touched.kfs.insert(o.first);
+                    const cv::Mat before = stays->GetDescriptor().clone();
+                    gone->Replace(stays);
+                    const cv::Mat after = stays->GetDescriptor();
+                    if (std::memcmp(before.ptr(0), after.ptr(0), 32) != 0) touched.changed.insert(stays);     // (after the forward pass only MarkDirty reads it)
+                    touched.pts.insert(gone); touched.pts.insert(stays);
+                }
+            } else {
+                pMP->AddObservation(pKF, best[i]);
+                pKF->AddMapPoint(pMP, best[i]);
+                touched.kfs.insert(pKF); touched.pts.insert(pMP);
+            }
+            nFused++;
+        }
+        return nFused;
+    }
+#endif
+
     // One culling handle per calling thread (handles are not re-entrant), destroyed with its blocks when the thread ends.
     struct CullHandle {
         RumiCull *h = nullptr;

@@ -1,7 +1,8 @@
 """Host-side mirror of ``LocalMapping::CreateNewMapPoints`` (R/lib_src/LocalMapping.cc:354-647, monocular pinhole) over the C ABI in
 include/rumi_mapping.h: one call for the current key-frame and all of its neighbours; of the map-point refresh
 (``MapPoint::ComputeDistinctiveDescriptors`` / ``UpdateNormalAndDepth``, R/lib_src/MapPoint.cc:353-427, 450-518) for a batch of points; and of
-``LocalMapping::KeyFrameCulling`` / ``CloudKeyFrameCulling`` (R/lib_src/LocalMapping.cc:953-1079, 820-951) for the whole covisible list."""
+``LocalMapping::KeyFrameCulling`` / ``CloudKeyFrameCulling`` (R/lib_src/LocalMapping.cc:953-1079, 820-951) for the whole covisible list; and of
+the searches of ``LocalMapping::SearchInNeighbors`` (R/lib_src/LocalMapping.cc:649-743) for every target key-frame in one call."""
 import ctypes as C
 
 import numpy as np
@@ -34,6 +35,8 @@ def _lib():
     L.rumi_create_new_map_points.argtypes = [vp, vp, vp, i32, vp, vp, i32, C.POINTER(i32), vp, vp]
     L.rumi_create_new_map_points_resident.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, C.POINTER(i32), vp, vp]
     L.rumi_newpts_stage_ms.argtypes = [vp, vp]
+    L.rumi_search_in_neighbors_resident.argtypes = [vp, vp, i32, vp, vp, vp, i32, C.c_float, vp, vp, vp, i32, C.POINTER(i32)]
+    L.rumi_search_in_neighbors_stage_ms.argtypes = [vp, vp]
     L.rumi_hook_newpts_matches.argtypes = [vp, i32, i32, vp]
     L.rumi_refresh_create.argtypes = [i32, C.POINTER(vp)]
     L.rumi_refresh_destroy.argtypes = [vp]
@@ -156,6 +159,62 @@ def last_matches(matcher, n_neigh, n1):
     """Test hook: [n_neigh, n1] the neighbour feature each current feature was paired with when the loop reached that neighbour (-1 none)."""
     out = np.full((n_neigh, n1), -1, np.int32)
     capi.check(_lib().rumi_hook_newpts_matches(matcher._h, n_neigh, n1, capi.ptr(out)))
+    return out
+
+
+# ---- SearchInNeighbors ----
+FUSE_MAX_TARGETS = 640
+
+
+class RumiFuseKF(C.Structure):
+    _fields_ = [("Tcw7", C.c_float * 7), ("Ow", C.c_float * 3), ("bounds", C.c_float * 4), ("log_scale_factor", C.c_float)]
+
+
+assert C.sizeof(RumiFuseKF) == 60
+
+
+def fuse_kf(Tcw7, Ow, bounds, log_sf):
+    """What SearchInNeighbors needs of a key-frame besides what the store keeps: the pose as qx qy qz qw tx ty tz, the camera centre, the image
+    bounds (mnMinX, mnMinY, mnMaxX, mnMaxY) and mfLogScaleFactor, as one RumiFuseKF."""
+    k = RumiFuseKF()
+    k.Tcw7[:] = np.asarray(Tcw7, np.float32).reshape(7).tolist()
+    k.Ow[:] = np.asarray(Ow, np.float32).reshape(3).tolist()
+    k.bounds[:] = np.asarray(bounds, np.float32).reshape(4).tolist()
+    k.log_scale_factor = float(log_sf)
+    return k
+
+
+def SearchInNeighborsResident(matcher, store, cur_slot, cur, target_slots, targets, th=3.0, rev_cap=None):
+    """The search half of LocalMapping::SearchInNeighbors over key-frames and points resident in ``store``: one device call for every target.
+    ``cur`` / ``targets``: RumiFuseKF (see ``fuse_kf``).  Returns (fwd_best [n_targets, n_cur], rev_point, rev_best): the target feature each
+    point of the current key-frame fuses with, and for every distinct point of the targets' rows that is not bad and not in the current
+    key-frame its id and the current key-frame's feature (-1: none).  ``rev_cap``: entries of the reverse lists (default: all that can occur)."""
+    L = _lib()
+    n = len(target_slots)
+    assert len(targets) == n
+    slots = np.ascontiguousarray(target_slots, np.int32).reshape(-1)
+    arr = (RumiFuseKF * max(n, 1))(*targets)
+    lengths = [store.row_length(int(s)) for s in [cur_slot] + slots.tolist()]
+    if min(lengths) < 0:
+        raise ValueError("SearchInNeighborsResident: slot %d is not live in the store" % ([cur_slot] + slots.tolist())[lengths.index(min(lengths))])
+    n_cur = lengths[0]
+    if rev_cap is None:
+        rev_cap = sum(lengths[1:])
+    rev_cap = int(rev_cap)
+    fwd = np.full((n, max(n_cur, 0)), -1, np.int32)
+    rev_point = np.full(max(rev_cap, 1), -1, np.int32)
+    rev_best = np.full(max(rev_cap, 1), -1, np.int32)
+    n_rev = C.c_int32()
+    capi.check(L.rumi_search_in_neighbors_resident(matcher._h, store._h, int(cur_slot), C.byref(cur), capi.ptr(slots) if n else None,
+                                                   C.byref(arr) if n else None, n, float(th), capi.ptr(fwd if fwd.size else np.zeros(1, np.int32)),
+                                                   capi.ptr(rev_point), capi.ptr(rev_best), rev_cap, C.byref(n_rev)))
+    return fwd, rev_point[:n_rev.value], rev_best[:n_rev.value]
+
+
+def search_in_neighbors_stage_ms(matcher):
+    """(validation + table, upload + kernels + download, write-out) of the matcher's last SearchInNeighborsResident call, ms."""
+    out = np.zeros(3, np.float32)
+    capi.check(_lib().rumi_search_in_neighbors_stage_ms(matcher._h, capi.ptr(out)))
     return out
 
 
