@@ -72,6 +72,13 @@ int rumi_covis_set_point_observations(RumiCovis *c, int32_t n, const int32_t *id
  * edit: the next query uploads the changed records.  A point keeps its attributes until they are set again. */
 int rumi_covis_set_point_attributes(RumiCovis *c, int32_t n, const int32_t *ids, const float *pos, const float *normal, const float *min_dist,
                                     const float *max_dist, const uint8_t *desc);
+/* GetCameraCenter() of n live slots, each at most once, Ow [n][3] finite.  To be called where the reference calls SetPose.  A slot set here
+ * "has a centre" from then on.  Staged like every edit: 16 bytes a key-frame go up with the next query.  Read by
+ * rumi_refresh_map_points_resident (rumi_mapping.h) and by nothing else. */
+int rumi_covis_set_keyframe_centres(RumiCovis *c, int32_t n, const int32_t *slots, const float *Ow);
+/* GetReferenceKeyFrame() of n points as a live slot, -1 clears it; ids each at most once and inside 0..max_points-1.  To be called wherever
+ * SetReferenceKeyFrame or EraseObservation changes mpRefKF.  Staged like every edit, one word a point. */
+int rumi_covis_set_point_reference(RumiCovis *c, int32_t n, const int32_t *ids, const int32_t *ref_slots);
 /* The length of a live slot's map-point row as the last rumi_covis_set_keyframes left it (host only, no device call); -1 for a slot that is
  * not live or a missing handle.  For callers that size an output by it (rumi_search_in_neighbors_resident, rumi_mapping.h). */
 int32_t rumi_covis_row_length(const RumiCovis *c, int32_t slot);
@@ -123,7 +130,7 @@ int rumi_covis_local_map(RumiCovis *c, int32_t n, const int32_t *frame_points, u
 /* The last query, in ms: validation + staging | upload, kernels, download | write-out. */
 int rumi_covis_stage_ms(const RumiCovis *c, float *out3);
 /* out7: arena capacity, tail, live entries (all in 32-bit entries), rows re-placed at the tail, compactions, growths, bytes of the last upload
- * (attribute edits included). */
+ * (attribute, centre and reference edits included). */
 int rumi_covis_stats(const RumiCovis *c, int64_t *out7);
 
 #ifdef __cplusplus

@@ -226,9 +226,49 @@ int rumi_refresh_map_points(RumiRefresh *r, const RumiRefreshKF *kf, int32_t n_k
                             const int32_t *obs_kf, const int32_t *obs_feature, int32_t n_obs, int32_t what, int32_t *best_obs,
                             int32_t *best_median, float *normal, float *min_distance, float *max_distance, uint8_t *updated);
 
-/* Host wall-clock of the handle's last successful call with work, in ms: out3[0] validation and gather, out3[1] upload + kernels + download
- * (the host waits for the device here), out3[2] writing the caller's arrays.  For tools/refresh_probe.py. */
+/* The same two members over a covisibility store (rumi_covis.h): a list of point ids goes up and one 64-byte record a point comes back.
+ * The outputs are those of rumi_refresh_map_points on the same map, byte for byte, with
+ *   observation list of a point    its observer row, IN THE ORDER THE ROW IS STORED (rumi_covis_set_point_observations)
+ *   is_bad of a key-frame          the slot's bit
+ *   desc, n, nlevels, scale_factors   the slot's resident features (rumi_covis_set_keyframe_features)
+ *   Ow                             the slot's centre (rumi_covis_set_keyframe_centres)
+ *   pos                            the position in the point's attribute record (rumi_covis_set_point_attributes)
+ *   ref_kf                         the point's reference slot (rumi_covis_set_point_reference)
+ *   ref_feature                    the feature the row stores for that slot, 0 where the row does not list it (MapPoint.cc:495)
+ *   ref_level                      the octave of that feature in the reference slot's resident key-points
+ * The stored row order decides equal medians and the order of the float sums.  The reference iterates GetObservations(), a
+ * std::map<KeyFrame*, ...>: pointer order.  facade/CovisibilityGraph::Sync(MapPoint*) stores the rows in that order; any other caller must too.
+ * desc [n_pts][32]: the winning row's bytes, written where best_obs >= 0.  The point's own bad bit is not read (the members return for bad
+ * points; the caller skips them).  Float rules as above; no floating-point atomics.
+ *
+ * flags = 0: a query, the store is unchanged.  RUMI_REFRESH_WRITE_BACK: when the call succeeds, each point's attribute record takes the
+ * new descriptor where best_obs >= 0 and the new normal and distance range where updated, on the device and in the store's host mirror; the
+ * position is untouched and no edit is staged.  rumi_track_local_map, rumi_search_in_neighbors_resident and
+ * rumi_create_new_map_points_resident then read the new values without another upload.  Staged edits, these points' included, go up before
+ * the kernels, so the write-back wins over an older staged value.
+ *
+ * RUMI_E_INVALID, nothing written (neither the outputs nor the store), on the host before any device call: a missing argument; an unknown
+ * `what` or `flags` bit, or no mode; an id outside the store or named twice; the handle and the store on different devices (a handle created
+ * with device < 0 learns its device by asking for the current one, which is then the only device call made before this refusal); a point with
+ * observers but without observation features; a point without attributes when RUMI_REFRESH_NORMAL_DEPTH or the write-back is asked for.
+ * RUMI_E_INVALID, nothing written, counted on the device among what the call reads, the counts in the message (the store is legitimately
+ * inconsistent between two staged edits, so the check is at the query): an observer slot without resident features (descriptor mode, good
+ * observers); an observer feature outside its slot's feature count; an observer or reference slot without a centre (normal mode); for a point
+ * with observers no reference slot, a reference slot without features, a reference octave outside its scale table (kept as a guard of the
+ * kernel's table index: rumi_covis_set_keyframe_features refuses such key-points, so no caller of this ABI can meet it).
+ * RUMI_E_CAPACITY, nothing written: a row above RUMI_REFRESH_MAX_OBS (known from the mirror).  n_pts = 0 is RUMI_OK and makes no device call.
+ * A point with an empty row: best_obs = best_median = -1, updated = 0, nothing of it written back. */
+#define RUMI_REFRESH_WRITE_BACK 1
+struct RumiCovis;
+int rumi_refresh_map_points_resident(RumiRefresh *r, struct RumiCovis *c, const int32_t *ids, int32_t n_pts, int32_t what, int32_t flags,
+                                     int32_t *best_obs, int32_t *best_median, uint8_t *desc /*[n_pts][32]*/, float *normal, float *min_distance,
+                                     float *max_distance, uint8_t *updated);
+
+/* Host wall-clock of the handle's last successful call with work (either entry), in ms: out3[0] validation and gather, out3[1] upload +
+ * kernels + download (the host waits for the device here), out3[2] writing the caller's arrays.  For tools/refresh_probe.py. */
 int rumi_refresh_stage_ms(const RumiRefresh *r, float *out3);
+/* Kernels the handle's last successful rumi_refresh_map_points_resident launched itself (the store's scatter of staged edits not counted). */
+int32_t rumi_refresh_last_launches(const RumiRefresh *r);
 
 /* ---- LocalMapping::KeyFrameCulling (R/lib_src/LocalMapping.cc:953-1079) and CloudKeyFrameCulling (:820-951) for the whole covisible list in
  * one call.  Non-inertial, monocular: the inertial branch (:1045-1070), the stereo depth gate (:1001-1004) and the NLeft != -1 octave

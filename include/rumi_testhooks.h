@@ -71,6 +71,13 @@ int rumi_hook_parse_hw_queues(const char *value);
 struct RumiMatcher;
 int rumi_hook_newpts_matches(struct RumiMatcher *m, int32_t n_neigh, int32_t n1, int32_t *matches);
 
+/* The 64-byte attribute records of n points of a covisibility store (rumi_covis.h: position, normal, min and max distance, descriptor), from
+ * the device copy (from_device != 0; waits for the device) or from the host mirror.  Uploads nothing: staged edits stay staged.
+ * RUMI_E_INVALID for an id outside the store or when that side holds no attribute table yet.  For the write-back tests of
+ * rumi_refresh_map_points_resident. */
+struct RumiCovis;
+int rumi_hook_covis_read_attributes(struct RumiCovis *c, int32_t n, const int32_t *ids, uint8_t *out, int32_t from_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,10 +121,10 @@ QUEUE_SYMBOLS = ["rumi_queue_create", "rumi_queue_destroy", "rumi_queue_shards",
 KFDB_SYMBOLS = ["rumi_kfdb_create", "rumi_kfdb_destroy", "rumi_kfdb_clear", "rumi_kfdb_size", "rumi_kfdb_next_seq", "rumi_kfdb_max_batch", "rumi_kfdb_add",
                 "rumi_kfdb_add_batch_device", "rumi_kfdb_bow", "rumi_kfdb_erase", "rumi_kfdb_clear_map", "rumi_kfdb_set_map_bad", "rumi_kfdb_set_maps",
                 "rumi_kfdb_set_bad", "rumi_kfdb_set_covisibles", "rumi_kfdb_score", "rumi_kfdb_scored", "rumi_kfdb_select_reloc", "rumi_kfdb_select_nbest"]
-MAPPING_SYMBOLS = ["rumi_create_new_map_points", "rumi_create_new_map_points_resident", "rumi_newpts_stage_ms", "rumi_search_in_neighbors_resident", "rumi_search_in_neighbors_stage_ms", "rumi_refresh_create", "rumi_refresh_destroy", "rumi_refresh_map_points", "rumi_refresh_stage_ms",
+MAPPING_SYMBOLS = ["rumi_create_new_map_points", "rumi_create_new_map_points_resident", "rumi_newpts_stage_ms", "rumi_search_in_neighbors_resident", "rumi_search_in_neighbors_stage_ms", "rumi_refresh_create", "rumi_refresh_destroy", "rumi_refresh_map_points", "rumi_refresh_stage_ms", "rumi_refresh_map_points_resident", "rumi_refresh_last_launches",
                    "rumi_cull_create", "rumi_cull_destroy", "rumi_keyframe_culling", "rumi_keyframe_culling_resident", "rumi_cull_stage_ms"]
 COVIS_SYMBOLS = ["rumi_covis_create", "rumi_covis_destroy", "rumi_covis_set_keyframes", "rumi_covis_set_points", "rumi_covis_set_point_observations",
-                 "rumi_covis_set_point_attributes",
+                 "rumi_covis_set_point_attributes", "rumi_covis_set_keyframe_centres", "rumi_covis_set_point_reference",
                  "rumi_covis_set_bad", "rumi_covis_set_maps", "rumi_covis_set_keyframe_features", "rumi_covis_drop_keyframe_features",
                  "rumi_covis_reserve_features", "rumi_covis_feature_stats", "rumi_covis_row_length",
                  "rumi_covis_update_connections", "rumi_covis_local_map", "rumi_covis_stage_ms", "rumi_covis_stats"]
@@ -197,6 +197,8 @@ def covis_lib():
     L.rumi_covis_set_points.argtypes = [vp, i32, vp, vp, vp, vp]
     L.rumi_covis_set_point_observations.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.rumi_covis_set_point_attributes.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.rumi_covis_set_keyframe_centres.argtypes = [vp, i32, vp, vp]
+    L.rumi_covis_set_point_reference.argtypes = [vp, i32, vp, vp]
     L.rumi_covis_set_bad.argtypes = [vp, i32, vp, vp, i32, vp, vp]
     L.rumi_covis_set_maps.argtypes = [vp, i32, vp, vp]
     L.rumi_covis_update_connections.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64]
@@ -215,7 +217,7 @@ def covis_lib():
 
 HOOK_SYMBOLS = ["rumi_hook_sort_like_std", "rumi_hook_sort_device", "rumi_hook_std_sort", "rumi_hook_quadtree", "rumi_hook_sinf", "rumi_hook_cosf",
                 "rumi_hook_fast_atan2", "rumi_hook_cv_round", "rumi_hook_magic_div", "rumi_hook_newpts_matches", "rumi_hook_lane_packing", "rumi_hook_disc_moments",
-                "rumi_hook_stream_plan", "rumi_hook_parse_hw_queues", "rumi_hook_octree_bins", "rumi_hook_compact_hist_lds"]
+                "rumi_hook_stream_plan", "rumi_hook_parse_hw_queues", "rumi_hook_octree_bins", "rumi_hook_compact_hist_lds", "rumi_hook_covis_read_attributes"]
 
 
 def hooks():
@@ -241,5 +243,6 @@ def hooks():
     L.rumi_hook_parse_hw_queues.argtypes = [C.c_char_p]
     L.rumi_hook_octree_bins.argtypes = [i32, i32, i32, C.c_float, i32, i32, vp, vp, i32, C.POINTER(i32)]
     L.rumi_hook_compact_hist_lds.argtypes = [i32, i32, i32, C.c_float, i32, vp]
+    L.rumi_hook_covis_read_attributes.argtypes = [vp, i32, vp, vp, i32]
     L._hooks_ready = True
     return L

@@ -84,6 +84,29 @@ class Covisibility:
         desc = np.ascontiguousarray(desc, _u8).reshape(n, 32)
         return self._ret(self._lib.rumi_covis_set_point_attributes(self._h, n, _p(ids), _p(pos), _p(normal), _p(mn), _p(mx), _p(desc)), check)
 
+    def set_keyframe_centres(self, slots, Ow, check=True):
+        """GetCameraCenter() [n, 3] of the live slots ``slots`` (where the reference calls SetPose); read by mapping.RefreshMapPointsResident."""
+        s = np.ascontiguousarray(slots, _i32).reshape(-1)
+        Ow = np.ascontiguousarray(Ow, np.float32).reshape(len(s), 3)
+        return self._ret(self._lib.rumi_covis_set_keyframe_centres(self._h, len(s), _p(s), _p(Ow)), check)
+
+    def set_point_reference(self, ids, ref_slots, check=True):
+        """GetReferenceKeyFrame() of the points ``ids`` as live slots; -1 clears it."""
+        ids = np.ascontiguousarray(ids, _i32).reshape(-1); ref = np.ascontiguousarray(ref_slots, _i32).reshape(-1)
+        assert len(ids) == len(ref)
+        return self._ret(self._lib.rumi_covis_set_point_reference(self._h, len(ids), _p(ids), _p(ref)), check)
+
+    def read_attributes(self, ids, from_device=False, check=True):
+        """Test hook: the 64-byte attribute records [n, 64] of ``ids`` from the device copy or the host mirror; uploads nothing.  With
+        check=False -> (status, records)."""
+        ids = np.ascontiguousarray(ids, _i32).reshape(-1)
+        out = np.zeros((len(ids), 64), _u8)
+        rc = capi.hooks().rumi_hook_covis_read_attributes(self._h, len(ids), _p(ids), _p(out), int(bool(from_device)))
+        if check:
+            capi.check(rc)
+            return out
+        return rc, out
+
     def set_bad(self, kf_slots=(), kf_bad=(), pt_ids=(), pt_bad=(), check=True):
         ks = np.ascontiguousarray(kf_slots, _i32); kb = np.ascontiguousarray(kf_bad, _u8)
         ps = np.ascontiguousarray(pt_ids, _i32); pb = np.ascontiguousarray(pt_bad, _u8)

@@ -15,6 +15,9 @@
 //   tag    [max_points]     64-bit stamps of the local-point selection, (call epoch << 32) | priority
 //   rowOf  [max_points]     64-bit stamps of the same epoch for rumi_track_local_map's id -> table row map (allocated with its first call)
 //   feat                    the key-frames' constant part, a byte arena of its own with no host mirror (covis_features.inc)
+//   centre [max_kf][4]      GetCameraCenter() and a "has centre" word (rumi_covis_set_keyframe_centres); allocated with the first such call
+//   ref    [max_points]     GetReferenceKeyFrame() as slot + 1, 0 = none (rumi_covis_set_point_reference); allocated with the first such call.
+//                           Both are read by rumi_refresh_map_points_resident (refresh_resident.inc) and by nothing else
 //   featTab [max_kf][4]     where a slot's key-points lie in feat (64-bit byte offset, -1: no features), its feature count, -: what a kernel
 //                           needs to read the octave of an observation it meets in an observer row (culling.hip)
 // The host keeps a mirror of kf, pt, attr and the arena; an edit writes the mirror and notes (table, offset, words).  The next query packs the noted
@@ -46,7 +49,8 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int KFW = 20, PTW = kCovisPointWords, ATW = kCovisAttrWords;     // words per key-frame / point / attribute record
 constexpr int K_MPOFF = 0, K_MPLEN = 1, K_CHOFF = 2, K_CHLEN = 3, K_FLAGS = 4, K_MAP = 5, K_PARENT = 6, K_KEY = 8, K_BEST = 10;
-constexpr int T_KF = 0, T_PT = 1, T_ARENA = 2, T_ATTR = 3, T_FEAT = 4, kTables = 5;
+constexpr int T_KF = 0, T_PT = 1, T_ARENA = 2, T_ATTR = 3, T_FEAT = 4, T_CENTRE = 5, T_REF = 6, kTables = 7;
+constexpr int CTW = kCovisCentreWords;
 constexpr int FTW = kCovisFeatTabWords;
 constexpr uint16_t kNone = 0xFFFF;                     // sorts last; slots stay below RUMI_COVIS_MAX_KEYFRAMES
 constexpr int kPosBits = 13;
@@ -54,6 +58,7 @@ static_assert((1 << kPosBits) == RUMI_COVIS_MAX_KEYFRAMES, "position bits of the
 static_assert((1 << kCovisObsSlotBits) == RUMI_COVIS_MAX_KEYFRAMES && ((int64_t)RUMI_COVIS_MAX_FEATURES << kCovisObsSlotBits) <= (1ll << 31),
               "slot | feature << 13 is a non-negative 32-bit word");
 static_assert(KFW == kCovisKfWords && K_MPOFF == kCovisKfMpOff && K_MPLEN == kCovisKfMpLen, "the kf record as culling.hip reads it");
+static_assert(K_FLAGS == kCovisKfFlags, "the kf record as refresh_resident.inc reads it");
 static_assert((int64_t)RUMI_COVIS_MAX_FEATURES << kPosBits < (1ll << 31), "count << 13 | position fits 32 bits");
 static_assert((int64_t)RUMI_COVIS_MAX_KEYFRAMES * RUMI_COVIS_MAX_FEATURES <= (1ll << 32), "rank * features + feature fits 32 bits");
 
@@ -346,6 +351,8 @@ struct RumiCovis {
     // host mirrors of the device tables
     std::vector<int32_t> kf, pt, arena, attr;        // attr: empty until the first rumi_covis_set_point_attributes
     std::vector<int32_t> featTab;                    // [max_kf][FTW]
+    std::vector<int32_t> centre, ref;                // [max_kf][CTW], [max_points]: empty until their first edit
+    int32_t hiRef = 0;                               // highest point id whose reference was ever set + 1
     int32_t hiAttr = 0;                              // highest point id with attributes + 1
     std::vector<int32_t> capMp, capCh, capObs;       // places of the rows in the arena (entries); 0 = never placed
     int64_t tail = 0, live = 0;
@@ -356,9 +363,9 @@ struct RumiCovis {
     int32_t stampKf = 0, stampPt = 0;
     // staged edits
     std::vector<int4> recs;                          // table, first word, -, words
-    bool full[kTables] = {true, true, true, true, true};
+    bool full[kTables] = {true, true, true, true, true, true, true};
     // device
-    DevBuf<int32_t> dKf, dPt, dArena, dAttr, dFeatTab;         // dKf, dPt, dTag: with the first bind; dAttr, dRowOf: with their first use; dArena follows the mirror
+    DevBuf<int32_t> dKf, dPt, dArena, dAttr, dFeatTab, dCentre, dRef;       // dKf, dPt, dTag: with the first bind; dAttr, dRowOf: with their first use; dArena follows the mirror
     DevBuf<unsigned long long> dTag, dRowOf;
     std::vector<uint8_t> extra;                      // the input block of rumi_track_local_map: frame points and the discarded outliers
     StageClock clock;                                // of the query in flight (the local-map query is launched and read in two calls)
@@ -406,7 +413,7 @@ void rebuild_arena(RumiCovis *h, int64_t need) {
     h->arena.swap(nv);
     h->tail = h->live = t;
     h->full[T_KF] = h->full[T_PT] = h->full[T_ARENA] = true;
-    h->recs.erase(std::remove_if(h->recs.begin(), h->recs.end(), [](const int4 &r) { return r.x != T_ATTR && r.x != T_FEAT; }), h->recs.end());
+    h->recs.erase(std::remove_if(h->recs.begin(), h->recs.end(), [](const int4 &r) { return r.x == T_KF || r.x == T_PT || r.x == T_ARENA; }), h->recs.end());
 }
 
 // Row (off, len) of place c takes src[0 .. n): in place when it fits, else at the tail.
@@ -451,8 +458,17 @@ int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) 
         if ((rc = h->dAttr.reserve((size_t)h->maxPts * ATW, (size_t)h->maxPts * ATW)) != RUMI_OK) return rc;
         h->full[T_ATTR] = true;
     }
-    int32_t *dBase[kTables] = {h->dKf.p, h->dPt.p, h->dArena.p, h->dAttr.p, h->dFeatTab.p};
-    const std::vector<int32_t> *mirror[kTables] = {&h->kf, &h->pt, &h->arena, &h->attr, &h->featTab};
+    if (!h->centre.empty() && !h->dCentre.p) {
+        if ((rc = h->dCentre.reserve(h->centre.size(), h->centre.size())) != RUMI_OK) return rc;
+        h->full[T_CENTRE] = true;
+    }
+    if (!h->ref.empty() && !h->dRef.p) {
+        if ((rc = h->dRef.reserve(h->ref.size(), h->ref.size())) != RUMI_OK) return rc;
+        HIP_TRY(hipMemsetAsync(h->dRef.p, 0, h->ref.size() * 4, nullptr));     // ids above hiRef: no reference
+        h->full[T_REF] = true;
+    }
+    int32_t *dBase[kTables] = {h->dKf.p, h->dPt.p, h->dArena.p, h->dAttr.p, h->dFeatTab.p, h->dCentre.p, h->dRef.p};
+    const std::vector<int32_t> *mirror[kTables] = {&h->kf, &h->pt, &h->arena, &h->attr, &h->featTab, &h->centre, &h->ref};
     size_t words = 0, nRec = 0;
     for (int4 &r : h->recs)
         if (!h->full[r.x]) { r.z = (int)words; words += (size_t)r.w; h->recs[nRec++] = r; }
@@ -462,7 +478,7 @@ int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) 
     h->lastUpload = (int64_t)bytes;
     for (int t = 0; t < kTables; t++)
         if (h->full[t]) {
-            const size_t n = t == T_ARENA ? (size_t)h->tail : t == T_ATTR ? (size_t)h->hiAttr * ATW : mirror[t]->size();
+            const size_t n = t == T_ARENA ? (size_t)h->tail : t == T_ATTR ? (size_t)h->hiAttr * ATW : t == T_REF ? (size_t)h->hiRef : mirror[t]->size();
             if (n) HIP_TRY(hipMemcpyAsync(dBase[t], mirror[t]->data(), n * 4, hipMemcpyHostToDevice, nullptr));
             h->lastUpload += (int64_t)n * 4;
         }
@@ -952,6 +968,7 @@ extern "C" int rumi_covis_local_map(RumiCovis *h, int32_t n, const int32_t *fram
 }
 
 #include "covis_features.inc"
+#include "covis_refresh.inc"
 
 extern "C" int rumi_covis_stage_ms(const RumiCovis *h, float *out3) {
     if (!h || !out3) return RUMI_E_INVALID;

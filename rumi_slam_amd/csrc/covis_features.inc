@@ -57,14 +57,15 @@ int oct_flush(RumiCovis *h) {
     return RUMI_OK;
 }
 
-// The record of a validated key-frame; false when the block would pass 2 GiB (the record's 32-bit offsets).
+// The record of a validated key-frame; false when the block would pass 2 GiB (the record's 32-bit offsets), or if the key-points did not
+// follow the record at once (kCovisFeatKeysOffset, rumi_internal.h).
 bool feat_layout(const RumiFrameFeatures &f, const RumiFeatureVector &v, const float *K4, CovisFeatRec *r) {
     const uint64_t n = (uint64_t)f.n, nn = (uint64_t)v.n_nodes, ne = nn ? (uint64_t)v.offsets[nn] : 0;
-    uint64_t at = sizeof(CovisFeatRec);
+    uint64_t at = sizeof(CovisFeatRec);                // the key-points follow the record at once: refresh_resident.inc finds the record from featTab's offset
     auto put = [&](uint64_t bytes) { const uint64_t o = at; at = up16(at + bytes); return o; };
     const uint64_t keys = put(n * sizeof(RumiKeyPoint)), desc = put(n * 32), scale = put((uint64_t)f.nlevels * 4), nodes = put(nn * 4),
                    off = put((nn + 1) * 4), idx = put(ne * 4);
-    if (at >= (1ull << 31)) return false;
+    if (at >= (1ull << 31) || keys != kCovisFeatKeysOffset) return false;
     r->n = (int32_t)n; r->nn = (int32_t)nn; r->ne = (int32_t)ne; r->nlevels = f.nlevels;
     std::memcpy(r->K, K4, 16);
     r->keys = (uint32_t)keys; r->desc = (uint32_t)desc; r->scale = (uint32_t)scale; r->nodes = (uint32_t)nodes; r->off = (uint32_t)off; r->idx = (uint32_t)idx;

@@ -13,12 +13,14 @@
 // sorted.  Rows are visited in ascending order and a median replaces the best only when strictly smaller (:416).
 // k_refresh_normal: a lane a point walks the point's observations in list order -- the order of the float sum is part of the definition, so
 // nothing is reduced across lanes.  Integer LDS atomics only (the count), no float atomics: the same bytes on every run.
+// rumi_refresh_map_points_resident (refresh_resident.inc) runs the same two walks over rows it fetches from the covisibility store in place.
 #include <algorithm>
 #include <climits>
 #include <cstring>
 #include <vector>
 
 #include "rumi_common.h"
+#include "rumi_internal.h"
 #include "rumi_mapping.h"
 
 namespace rumi {
@@ -45,6 +47,33 @@ __device__ __forceinline__ int hamming(const uint4 &a0, const uint4 &a1, const u
            __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
+// The walk of a group of G lanes over its point's N rows (rows: the group's rows in LDS; a0, a1: row `sub` in registers, zero from N on):
+// best = the smallest median, bestIdx = the first row that has it.  Both entries' group kernels end in this walk.
+template <int G>
+__device__ __forceinline__ void desc_group_best(const uint4 &a0, const uint4 &a1, const uint4 *rows, int N, int sub, int lane, int &best, int &bestIdx) {
+    const int gbase = lane & ~(G - 1);
+    const unsigned long long gmask = G == 64 ? ~0ull : (1ull << (G & 63)) - 1;
+    const int rank = (N - 1) >> 1;                               // vDists[0.5*(N-1)], :414
+    int nmax = 0;
+    for (int k = 0; k < 64; k += G) nmax = max(nmax, __shfl(N, k));
+    nmax = __builtin_amdgcn_readfirstlane(nmax);
+    best = INT_MAX; bestIdx = 0;
+    for (int i = 0; i < nmax; i++) {                             // wave-uniform trip count: the ballots below see every lane
+        const int ii = i < N ? i : 0;
+        const int d = hamming(a0, a1, rows[2 * ii], rows[2 * ii + 1]);
+        bool cand = sub < N;
+        int r = rank, med = 0;
+#pragma unroll
+        for (int bit = 8; bit >= 0; bit--) {                     // the value of rank r among the candidates, from the top bit down
+            const bool zero = ((d >> bit) & 1) == 0;
+            const int zeros = __popcll((__ballot(cand && zero) >> gbase) & gmask);
+            if (r < zeros) cand = cand && zero;
+            else { r -= zeros; med |= 1 << bit; cand = cand && !zero; }
+        }
+        if (i < N && med < best) { best = med; bestIdx = i; }    // :416
+    }
+}
+
 // Points of 1..G rows, a group of G lanes each (G = 16, 32, 64; 256 / G points a workgroup).  list [nList] = the points of this bin.
 template <int G>
 __global__ __launch_bounds__(256) void k_refresh_desc_group(const PtDev *__restrict__ pts, const int32_t *__restrict__ list, int nList,
@@ -60,48 +89,18 @@ __global__ __launch_bounds__(256) void k_refresh_desc_group(const PtDev *__restr
     if (sub < N) { a0 = desc[2 * (size_t)(off + sub)]; a1 = desc[2 * (size_t)(off + sub) + 1]; }
     sRow[2 * tid] = a0; sRow[2 * tid + 1] = a1;
     __syncthreads();
-    const uint4 *rows = sRow + 2 * (tid - sub);                  // the group's rows
-    const int gbase = lane & ~(G - 1);
-    const unsigned long long gmask = G == 64 ? ~0ull : (1ull << (G & 63)) - 1;
-    const int rank = (N - 1) >> 1;                               // vDists[0.5*(N-1)], :414
-    int nmax = 0;
-    for (int k = 0; k < 64; k += G) nmax = max(nmax, __shfl(N, k));
-    nmax = __builtin_amdgcn_readfirstlane(nmax);
-    int best = INT_MAX, bestIdx = 0;
-    for (int i = 0; i < nmax; i++) {                             // wave-uniform trip count: the ballots below see every lane
-        const int ii = i < N ? i : 0;
-        const int d = hamming(a0, a1, rows[2 * ii], rows[2 * ii + 1]);
-        bool cand = sub < N;
-        int r = rank, med = 0;
-#pragma unroll
-        for (int bit = 8; bit >= 0; bit--) {                     // the value of rank r among the candidates, from the top bit down
-            const bool zero = ((d >> bit) & 1) == 0;
-            const int zeros = __popcll((__ballot(cand && zero) >> gbase) & gmask);
-            if (r < zeros) cand = cand && zero;
-            else { r -= zeros; med |= 1 << bit; cand = cand && !zero; }
-        }
-        if (i < N && med < best) { best = med; bestIdx = i; }    // :416
-    }
+    int best, bestIdx;
+    desc_group_best<G>(a0, a1, sRow + 2 * (tid - sub), N, sub, lane, best, bestIdx);
     if (live && sub == 0) { out[p].bestObs = goodPos[off + bestIdx]; out[p].bestMedian = best; }
 }
 
-// Points of more than 64 rows: a workgroup a point.  Dynamic LDS: nAlloc rows of 32 bytes (nAlloc >= every N of the launch), then a 257-bin
-// count per wave.
-__global__ __launch_bounds__(256) void k_refresh_desc_block(const PtDev *__restrict__ pts, const int32_t *__restrict__ list, int nAlloc,
-                                                            const uint4 *__restrict__ desc, const int32_t *__restrict__ goodPos,
-                                                            OutDev *__restrict__ out) {
-    extern __shared__ uint4 smem[];
-    __shared__ int sBest[4], sBestIdx[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int p = list[blockIdx.x];
-    const int N = min(pts[p].nGood, nAlloc), off = pts[p].descOff;
-    uint4 *sRow = smem;
-    int *hist = reinterpret_cast<int *>(smem + 2 * (size_t)nAlloc) + wave * kHistStride;
-    for (int j = tid; j < 2 * N; j += 256) sRow[j] = desc[2 * (size_t)off + j];
-    for (int k = lane; k < kHistStride; k += 64) hist[k] = 0;
-    __syncthreads();
+// The walk of a workgroup of four waves over its point's N rows in LDS, a wave a row, against a 257-bin count per wave (hist: this wave's,
+// zeroed, and a barrier passed since).  On thread 0: best = the smallest median, bestIdx = the first row that has it.  Both entries'
+// workgroup kernels end in this walk.
+__device__ __forceinline__ void desc_block_best(const uint4 *sRow, int *hist, int N, int tid, int lane, int wave, int *sBest, int *sBestIdx, int &best,
+                                                int &bestIdx) {
     const int rank = (N - 1) >> 1;
-    int best = INT_MAX, bestIdx = 0;
+    best = INT_MAX; bestIdx = 0;
     for (int i = wave; i < N; i += 4) {                          // ascending within the wave
         const uint4 r0 = sRow[2 * i], r1 = sRow[2 * i + 1];
         for (int j = lane; j < N; j += 64) atomicAdd(&hist[hamming(r0, r1, sRow[2 * j], sRow[2 * j + 1])], 1);
@@ -131,11 +130,29 @@ __global__ __launch_bounds__(256) void k_refresh_desc_block(const PtDev *__restr
     }
     if (lane == 0) { sBest[wave] = best; sBestIdx[wave] = bestIdx; }
     __syncthreads();
-    if (tid == 0) {                                              // the first row of the smallest median over the four interleaved walks
+    if (tid == 0)                                                // the first row of the smallest median over the four interleaved walks
         for (int w = 1; w < 4; w++)
             if (sBest[w] < best || (sBest[w] == best && sBestIdx[w] < bestIdx)) { best = sBest[w]; bestIdx = sBestIdx[w]; }
-        out[p].bestObs = goodPos[off + bestIdx]; out[p].bestMedian = best;
-    }
+}
+
+// Points of more than 64 rows: a workgroup a point.  Dynamic LDS: nAlloc rows of 32 bytes (nAlloc >= every N of the launch), then a 257-bin
+// count per wave.
+__global__ __launch_bounds__(256) void k_refresh_desc_block(const PtDev *__restrict__ pts, const int32_t *__restrict__ list, int nAlloc,
+                                                            const uint4 *__restrict__ desc, const int32_t *__restrict__ goodPos,
+                                                            OutDev *__restrict__ out) {
+    extern __shared__ uint4 smem[];
+    __shared__ int sBest[4], sBestIdx[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int p = list[blockIdx.x];
+    const int N = min(pts[p].nGood, nAlloc), off = pts[p].descOff;
+    uint4 *sRow = smem;
+    int *hist = reinterpret_cast<int *>(smem + 2 * (size_t)nAlloc) + wave * kHistStride;
+    for (int j = tid; j < 2 * N; j += 256) sRow[j] = desc[2 * (size_t)off + j];
+    for (int k = lane; k < kHistStride; k += 64) hist[k] = 0;
+    __syncthreads();
+    int best, bestIdx;
+    desc_block_best(sRow, hist, N, tid, lane, wave, sBest, sBestIdx, best, bestIdx);
+    if (tid == 0) { out[p].bestObs = goodPos[off + bestIdx]; out[p].bestMedian = best; }
 }
 
 // The operation order rumi_mapping.h defines: differences per component, (x*x + y*y) + z*z, IEEE sqrtf, true division (the library is built
@@ -173,6 +190,8 @@ struct RumiRefresh {
     MirrorBuf<uint8_t> blk, out;          // the upload block; the results, an OutDev a point
     std::vector<PtDev> pt;
     std::vector<int32_t> bins[4];
+    std::vector<int32_t> rowLen;          // the resident entry: the observer-row length of every point of the call
+    int launches = 0;                     // kernels of the last resident call
     StageClock clock;
     float stageMs[3] = {0.f, 0.f, 0.f};   // the last call: validation + gather | upload, kernels, download | write-out
 };
@@ -342,3 +361,5 @@ extern "C" int rumi_refresh_stage_ms(const RumiRefresh *r, float *out3) {
     std::memcpy(out3, r->stageMs, sizeof r->stageMs);
     return RUMI_OK;
 }
+
+#include "refresh_resident.inc"

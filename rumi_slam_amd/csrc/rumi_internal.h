@@ -48,6 +48,9 @@ struct CovisFeatRec {
     uint32_t bytes, pad;               // of the whole block, record included
 };
 static_assert(sizeof(CovisFeatRec) == 64, "the arrays behind the record start 16-byte aligned");
+// The key-points are the first array behind the record (feat_layout refuses any other placement): a kernel that holds featTab's key-point
+// offset finds the slot's record this many bytes before it (refresh_resident.inc).
+constexpr uint32_t kCovisFeatKeysOffset = sizeof(CovisFeatRec);
 // What the host knows of a slot without asking the device.
 struct CovisSlotFeatures { int32_t n, nn, ne, mpOff, mpLen; int64_t block; };     // mp row in the row arena (entries); block in the feature arena (bytes)
 struct CovisFeatureView {
@@ -76,6 +79,35 @@ void covis_cull_row_points(const RumiCovis *c, int32_t mpOff, int32_t mpLen, int
 // Binds the store (wantDevice as above), sends the staged edits and features, brings the octave table up to date; where the tables lie.
 // Does not synchronise.
 int covis_cull_flush(RumiCovis *c, int wantDevice, const char *entry, CovisCullView *view);
+
+// ---- the store as rumi_refresh_map_points_resident reads and writes it (refresh.hip, refresh_resident.inc; covis_refresh.inc) ----
+constexpr int kCovisKfFlags = 4;       // kf record: the flags word (bit 0 bad, bit 1 live)
+constexpr int kCovisCentreWords = 4;   // centre record: GetCameraCenter() (3 x f32), has centre
+struct CovisRefreshView {
+    const int32_t *kf, *pt, *rows, *featTab;   // as CovisCullView
+    const int32_t *centre, *ref;               // [max_kf][kCovisCentreWords], [max_points] slot + 1 (0: none); null: never set
+    int32_t *attr;                             // [max_points][kCovisAttrWords], written by the write-back; null: no point has attributes
+    const uint8_t *feat;                       // the feature arena (a slot's CovisFeatRec lies kCovisFeatKeysOffset bytes before its key-points)
+    int device;
+};
+// One point's results as the kernels leave them and the host reads them back.
+struct CovisRefreshOut {
+    int32_t bestObs, bestMedian;
+    float normal[3], minD, maxD;
+    int32_t updated;
+    uint32_t desc[8];                          // the winning row, where bestObs >= 0
+};
+static_assert(sizeof(CovisRefreshOut) == 64, "one record a point comes back");
+// Host only, from the store's mirror, O(1) per id: every id in range and named once; rowLen[i] = the length of its observer row; a point with
+// observers has observation features; with needAttr every point has attributes; with both devices known they are the same.  Refused with
+// RUMI_E_INVALID and the message set.
+int covis_refresh_check(RumiCovis *c, int n, const int32_t *ids, bool needAttr, int wantDevice, const char *entry, int32_t *rowLen);
+// wantDevice: the consumer's device, resolved.  A store on another device is refused before the store makes any device call; a store without a
+// device takes the consumer's.  Then binds the store, sends the staged edits and features; where the tables lie.  Does not synchronise.
+int covis_refresh_flush(RumiCovis *c, int wantDevice, const char *entry, CovisRefreshView *view);
+// The host half of the write-back: the mirror's attribute records take what the device's took (descriptor where bestObs >= 0, normal and
+// distance range where updated; a point with an empty row is skipped).  No edit is staged.
+void covis_refresh_write_mirror(RumiCovis *c, int n, const int32_t *ids, const int32_t *rowLen, const CovisRefreshOut *out, bool desc, bool normal);
 
 // Correspondences the LDS instantiation of k_pose_opt holds (opt.hip).  The tracker (track.hip) launches ONLY that instantiation when it knows a
 // frame cannot have more (nfeatures 1000 + the extractor's slack of 96 fits), so both files take the number from here.

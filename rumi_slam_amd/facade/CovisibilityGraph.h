@@ -19,6 +19,9 @@
 //                             caller serialises, as for Sync); FlushDirty() stages the noted points, once each, before the frame's query.
 //   Sync(MapPoint*)           stages the feature index of every observation with its observer (rumi_covis_set_point_observations), which is
 //                             what rumi::LocalMappingStep::KeyFrameCullingResident reads an observer's octave through.
+//   SyncCentres(kfs)          stages GetCameraCenter() of the listed key-frames, SyncReferences(points) GetReferenceKeyFrame() of the listed
+//                             points: with those, rumi_facade::RefreshMapPointsResident (MapPointRefresh.h) refreshes points by id, and its
+//                             write-back leaves their attributes current in the store without a SyncAttributes.
 // Errors follow rumi_status.h: reported, never thrown; the member returns without having written anything.
 #pragma once
 #include <cstdint>
@@ -81,6 +84,55 @@ template <class KeyFrameT, class MapPointT> class CovisibilityGraph {
     int FlushDirty() {
         if (dirty_.empty()) return RUMI_OK;
         return SyncAttributes(std::vector<MapPointT *>(dirty_.begin(), dirty_.end()));
+    }
+
+    // ---- what rumi_facade::RefreshMapPointsResident (MapPointRefresh.h) reads beside features, observers and attributes: GetCameraCenter()
+    // of the key-frames (rumi_covis_set_keyframe_centres; after SetPose) and GetReferenceKeyFrame() of the points
+    // (rumi_covis_set_point_reference; wherever mpRefKF changes).  Objects the store has not seen are staged first.
+    int SyncCentres(const std::vector<KeyFrameT *> &vpKFs) {
+        if (!h_) return RUMI_E_INVALID;
+        std::vector<KeyFrameT *> unseen;
+        std::set<KeyFrameT *> in;
+        for (KeyFrameT *k : vpKFs)
+            if (k && in.insert(k).second && !slot_.count(k)) unseen.push_back(k);
+        int rc;
+        if (!unseen.empty() && (rc = sync_keyframes(unseen)) != RUMI_OK) return rc;
+        std::vector<int32_t> slots;
+        std::vector<float> Ow;
+        for (KeyFrameT *k : in) {
+            slots.push_back(slot_[k]);
+            const auto C = k->GetCameraCenter();
+            for (int c = 0; c < 3; c++) Ow.push_back(C(c));
+        }
+        if (slots.empty()) return RUMI_OK;
+        rc = rumi_covis_set_keyframe_centres(h_, (int32_t)slots.size(), slots.data(), Ow.data());
+        if (rc != RUMI_OK) rumi_facade::report("CovisibilityGraph::SyncCentres", rc);
+        return rc;
+    }
+    int SyncReferences(const std::vector<MapPointT *> &vpMPs) {
+        if (!h_) return RUMI_E_INVALID;
+        std::vector<MapPointT *> unseen;
+        std::vector<KeyFrameT *> unseenKfs;
+        std::set<MapPointT *> in;
+        for (MapPointT *p : vpMPs) {
+            if (!p || !in.insert(p).second) continue;
+            if (!id_.count(p)) unseen.push_back(p);
+            KeyFrameT *ref = p->GetReferenceKeyFrame();
+            if (ref && !slot_.count(ref)) unseenKfs.push_back(ref);
+        }
+        int rc;
+        if (!unseenKfs.empty() && (rc = sync_keyframes(unseenKfs)) != RUMI_OK) return rc;
+        if (!unseen.empty() && (rc = sync_points(unseen)) != RUMI_OK) return rc;
+        std::vector<int32_t> ids, refs;
+        for (MapPointT *p : in) {
+            KeyFrameT *ref = p->GetReferenceKeyFrame();
+            ids.push_back(id_[p]);
+            refs.push_back(ref ? slot_[ref] : -1);
+        }
+        if (ids.empty()) return RUMI_OK;
+        rc = rumi_covis_set_point_reference(h_, (int32_t)ids.size(), ids.data(), refs.data());
+        if (rc != RUMI_OK) rumi_facade::report("CovisibilityGraph::SyncReferences", rc);
+        return rc;
     }
 
     // ---- the key-frame's constant part (mvKeysUn, mDescriptors, mvScaleFactors, mFeatVec, fx fy cx cy): rumi_covis_set_keyframe_features.

@@ -10,7 +10,9 @@
 // MapPoint needs two one-line setters the reference lacks: SetDescriptor(const cv::Mat&) and
 // SetDistanceRange(float min, float max); SetNormalVector exists.
 #pragma once
+#include <cstring>
 #include <map>
+#include <set>
 #include <tuple>
 #include <type_traits>
 #include <unordered_map>
@@ -138,6 +140,81 @@ template <class KeyFrameT, class RecentListT> int AssociateAndRefresh(KeyFrameT 
 // LocalMapping::SearchInNeighbors, the "Update points" loop (LocalMapping.cc:730-739).
 template <class KeyFrameT> int RefreshKeyFramePoints(KeyFrameT *pCurrentKF) {
     return RefreshMapPoints(pCurrentKF->GetMapPointMatches());
+}
+// The same refresh over a CovisibilityGraph that holds the map (rumi_refresh_map_points_resident): the points go to the device as ids, the
+// observer rows, descriptors, centres, positions and reference key-frames are read where the store keeps them, and the write-back leaves the
+// store's attribute records current, so that a later TrackLocalMapResident / SearchInNeighborsResident / CreateNewMapPointsResident needs no
+// SyncAttributes for these points.  The store must be current for them: Sync(MapPoint*) after the observations changed, SyncFeatures of every
+// observer, SyncCentres after SetPose, SyncReferences where mpRefKF changed, SyncAttributes (or MarkDirty + FlushDirty) after SetWorldPos
+// (INTEGRATION.md).  NULL, isBad() and repeated points are skipped.  Stereo observations are refused as RefreshMapPoints refuses them, with
+// nothing written.  Returns the number of points refreshed, -1 when nothing was written.
+template <class GraphT, class MapPointT>
+int RefreshMapPointsResident(GraphT &graph, const std::vector<MapPointT *> &vpMPs, int what = RUMI_REFRESH_DESCRIPTOR | RUMI_REFRESH_NORMAL_DEPTH) {
+    static const char *where = "MapPointRefresh::RefreshMapPointsResident";
+    std::vector<MapPointT *> live;
+    std::set<MapPointT *> in;
+    for (MapPointT *pMP : vpMPs) {
+        if (!pMP || pMP->isBad() || !in.insert(pMP).second) continue;
+        const auto observations = pMP->GetObservations();
+        for (const auto &o : observations)
+            if (std::get<1>(o.second) != -1 || std::get<0>(o.second) == -1 || o.first->NLeft != -1) {
+                report(where, RUMI_E_INVALID, "a stereo observation (right index or NLeft != -1): only the monocular branches are built; no point was refreshed");
+                return -1;
+            }
+        if (!observations.empty() && pMP->GetReferenceKeyFrame()->NLeft != -1) {
+            report(where, RUMI_E_INVALID, "a stereo reference key-frame (NLeft != -1): only the monocular branches are built; no point was refreshed");
+            return -1;
+        }
+        live.push_back(pMP);
+    }
+    const int n = (int)live.size();
+    if (n == 0) return 0;
+    std::vector<int32_t> ids(n);
+    for (int i = 0; i < n; i++)
+        if ((ids[i] = graph.IdOf(live[i])) < 0) return -1;
+    std::vector<int32_t> bestObs(n), bestMedian(n);
+    std::vector<uint8_t> desc((size_t)n * 32), updated(n);
+    std::vector<float> normal((size_t)n * 3), minD(n), maxD(n);
+    RumiRefresh *h = refresh_handle();
+    if (!h) return -1;
+    if (RUMI_GUARDED("MapPointRefresh / rumi_refresh_map_points_resident", &no_growth,
+                     rumi_refresh_map_points_resident(h, graph.handle(), ids.data(), n, what, RUMI_REFRESH_WRITE_BACK, bestObs.data(), bestMedian.data(),
+                                                      desc.data(), normal.data(), minD.data(), maxD.data(), updated.data())) != RUMI_OK)
+        return -1;
+    for (int i = 0; i < n; i++) {
+        MapPointT *pMP = live[i];
+        if ((what & RUMI_REFRESH_DESCRIPTOR) && bestObs[i] >= 0) {                       // :425
+            cv::Mat d;
+            d.create(1, 32, CV_8U);
+            std::memcpy(d.ptr(0), desc.data() + 32 * (size_t)i, 32);
+            pMP->SetDescriptor(d);
+        }
+        if ((what & RUMI_REFRESH_NORMAL_DEPTH) && updated[i]) {                          // :512-517
+            pMP->SetDistanceRange(minD[i], maxD[i]);
+            pMP->SetNormalVector(Eigen::Vector3f(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]));
+        }
+    }
+    return n;
+}
+
+// The association loop of ProcessNewKeyFrame over the graph: every touched point's new observer row is staged, then one resident refresh.
+template <class GraphT, class KeyFrameT, class RecentListT> int AssociateAndRefreshResident(GraphT &graph, KeyFrameT *pCurrentKF, RecentListT &mlpRecentAddedMapPoints) {
+    const auto vpMapPointMatches = pCurrentKF->GetMapPointMatches();
+    std::vector<typename std::decay<decltype(vpMapPointMatches)>::type::value_type> touched;
+    for (size_t i = 0; i < vpMapPointMatches.size(); i++) {
+        auto pMP = vpMapPointMatches[i];
+        if (!pMP || pMP->isBad()) continue;
+        if (!pMP->IsInKeyFrame(pCurrentKF)) { pMP->AddObservation(pCurrentKF, (int)i); touched.push_back(pMP); }
+        else mlpRecentAddedMapPoints.push_back(pMP);
+    }
+    for (auto pMP : touched)
+        if (graph.Sync(pMP) != RUMI_OK) return -1;
+    return RefreshMapPointsResident(graph, touched);
+}
+
+// The "Update points" loop of SearchInNeighbors over the graph (the member's Fuse calls have staged what they changed).
+template <class GraphT, class KeyFrameT> int RefreshKeyFramePointsResident(GraphT &graph, KeyFrameT *pCurrentKF) {
+    return RefreshMapPointsResident(graph, pCurrentKF->GetMapPointMatches());
 }
 #endif  // RUMI_HAVE_SOPHUS
 

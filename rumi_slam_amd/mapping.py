@@ -43,6 +43,8 @@ def _lib():
     L.rumi_refresh_destroy.restype = None
     L.rumi_refresh_map_points.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.rumi_refresh_stage_ms.argtypes = [vp, vp]
+    L.rumi_refresh_map_points_resident.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.rumi_refresh_last_launches.argtypes = [vp]
     L.rumi_cull_create.argtypes = [i32, C.POINTER(vp)]
     L.rumi_cull_destroy.argtypes = [vp]
     L.rumi_cull_destroy.restype = None
@@ -307,6 +309,44 @@ class MapPointRefresher:
     def status(self, batch, what, out):
         """The raw status of one call (outputs in ``out``)."""
         return self._lib.rumi_refresh_map_points(self._h, *batch.args(what, out))
+
+
+    def status_resident(self, store, ids, what, flags, out):
+        """The raw status of one rumi_refresh_map_points_resident call (outputs in ``out``, see refresh_resident_outputs)."""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        return self._lib.rumi_refresh_map_points_resident(self._h, store._h, capi.ptr(ids), len(ids), int(what), int(flags), capi.ptr(out["best_obs"]),
+                                                          capi.ptr(out["best_median"]), capi.ptr(out["desc"]), capi.ptr(out["normal"]),
+                                                          capi.ptr(out["min_distance"]), capi.ptr(out["max_distance"]), capi.ptr(out["updated"]))
+
+    def last_launches(self):
+        """Kernels the last resident call launched itself."""
+        return int(self._lib.rumi_refresh_last_launches(self._h))
+
+
+REFRESH_WRITE_BACK = 1
+
+
+def refresh_resident_outputs(n_pts, fill=0):
+    """Fresh output arrays of the resident entry, every byte ``fill``: those of RefreshBatch.outputs and desc [n, 32]."""
+    n = max(int(n_pts), 1)
+    shapes = dict(best_obs=(n, np.int32), best_median=(n, np.int32), desc=((n, 32), np.uint8), normal=((n, 3), np.float32),
+                  min_distance=(n, np.float32), max_distance=(n, np.float32), updated=(n, np.uint8))
+    out = {}
+    for k, (shape, dt) in shapes.items():
+        a = np.empty(shape, dt)
+        a.view(np.uint8).fill(fill)
+        out[k] = a
+    return out
+
+
+def RefreshMapPointsResident(refresher, store, ids, what=REFRESH_DESCRIPTOR | REFRESH_NORMAL_DEPTH, write_back=True, out=None):
+    """ComputeDistinctiveDescriptors and / or UpdateNormalAndDepth of the points ``ids`` of a covis.Covisibility store, read where the store
+    keeps them; with ``write_back`` the store's attribute records take the results.  Returns the dict of RefreshMapPoints plus desc [n, 32]
+    (the winning row where best_obs >= 0)."""
+    ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    out = refresh_resident_outputs(len(ids)) if out is None else out
+    capi.check(refresher.status_resident(store, ids, what, REFRESH_WRITE_BACK if write_back else 0, out))
+    return {k: v[:len(ids)] for k, v in out.items()}
 
 
 _refresher = None
