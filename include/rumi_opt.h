@@ -30,21 +30,43 @@ typedef struct RumiOptimizer RumiOptimizer;
 /* Scratch arenas: pose problems of up to max_pose_edges correspondences in total per call (all problems of a batch),
  * BA problems of up to max_kf key-frame vertices, max_mp points, max_edges observations.
  *
- * What a handle allocates, in bytes, with PE = max_pose_edges, PB = max_pose_batch, K = max_kf, M = max_mp, E = max_edges and
- * NP = min(6 K + 1 rounded up to 16, 256), the padded width of the dense Schur panel:
- *   device, at creation
- *     34 PE + 64 PB                    pose optimisation: transfer blocks, active flags, last chi2
- *     377 E                            per observation: H_pl 144, pose panel rows 128, chi2 8, level flag 1, two transfer blocks of 48 each
- *     (352 + 24 NP) M                  per point: H_ll, D^-1, L, b_l, two states, update, two transfer blocks; 24 NP M is the panel Y
- *                                      (6 KiB a point once NP = 256: from K = 40 on)
- *     768 K + 8 (6 K + 2)^2 + 8 NP^2   per key-frame: states, H_pp, b_p, update; the dense reduced system of the large-window path and of
- *                                      the essential graph (85 MB at K = 544); the Gram matrix of the panel
- *   pinned host memory, at creation    48 E + 32 M + 80 K (one transfer block) and 25 PE + 64 PB
- *   device, on first use and kept      large-window BA: 148 E and the co-observation pair lists of the largest window seen;
- *                                      window-batched local BA (rumi_local_ba, rumi_local_ba_batch): 26 MB of Gram partials whatever the sizes,
- *                                      about 33 E + 16 M for the sorted graph; essential graph: its own matrix and one block, by problem size
- * rumi_local_ba_batch creates child handles with the parent's K, M, E and PE (PB = 1) on first use and keeps them: one per window of a
- * launch group and three runners, up to 35. */
+ * What a handle owns, in bytes (rumi_opt_footprint returns the two sums; every block has one owner, so the expressions are exact).
+ * PE = max_pose_edges, PB = max_pose_batch, K = max_kf, M = max_mp, E = max_edges; r16(x), r256(x) = x rounded up to a multiple of 16, 256;
+ * NP = min(r16(6 K + 1), 256), the padded width of the dense Schur panel.  Integer arithmetic throughout ("/" rounds down).
+ *   pose blocks          device  34 PE + 64 PB + 532          transfer blocks in and out, active flags 1, last chi2 8 per correspondence
+ *                        pinned  25 PE + 64 PB + 532          the two transfer blocks
+ *   window part  W       device  233 E + 232 M + 672 K + 2560 one window's state as the window-batched kernels use it: two transfer blocks
+ *                                                             of S = 48 E + 32 M + 80 K + 1024 each, pose panel rows 128 E, chi2 8 E, level
+ *                                                             flags E; per point D^-1, b_l, two states, update; per key-frame two states,
+ *                                                             H_pp, b_p, update
+ *                        pinned  S + 64                       the upload block and the stop word
+ *   host-loop part  H    device  144 E + (120 + 24 NP) M + 8 NP^2 + 8 (6 K + 2)^2 + 96 K + 64
+ *                                                             what only the single-window LM loop driven from the host reads: H_pl 144 E; H_ll, L
+ *                                                             and the panel Y (24 NP M: 6 KiB a point once NP = 256, from K = 40 on); its
+ *                                                             Gram matrix; the dense reduced system of the large-window path (85 MB at
+ *                                                             K = 544); the trial's scalars
+ *                        pinned  128                          the published scalars
+ *   batch extras  X      device  26088000 + 16 max(192, (M + 31) / 32) + 2 r256(4 M + 4) + 6 r256(4 E) + r256(8 E) + r256(E)
+ *                                + r256(128 (M / 16 + 2))     Gram partials of the tile solver (26 MB whatever the sizes), chi2 / scale
+ *                                                             partials, the graph sorted by landmark, LM control
+ *                        pinned  24                           the word a window reports through
+ *   runner  R            device  15616 + 32 r256(r16(r16(r16(64 K) + 24 M) + E) + 16)
+ *                        pinned  the same                     what a chain of launches needs: the window table of a launch group (32 x 488)
+ *                                                             and the block its results come back in, sized for 32 windows of K, M, E;
+ *                                                             a stream and two events
+ * rumi_opt_create allocates the pose blocks, W + H (the handle's own window) and R; nothing else.
+ * First use, kept until rumi_opt_destroy:
+ *   rumi_local_ba / rumi_merge_ba / rumi_bundle_adjustment: X, the first time a window of up to 29 optimised key-frames (and at most 512
+ *     key-frames, handle not profiled) runs; 148 E and the co-observation pair lists of the largest window seen (growing by a quarter), the first
+ *     time a window of more than 42 optimised key-frames runs.
+ *   rumi_essential_graph / rumi_sim3_correct_points: the dense matrix and one block for the rest, by problem size.
+ *   rumi_local_ba_batch with n such small windows: batch arenas A = W + X, one per window of a launch wave: min(n, 32) of them (X when a
+ *     window is first staged in the arena; a window that ends before staging leaves it at W); batch runners R: one per launch group after the
+ *     first, which the handle's own runner drives: none below 8 windows in a wave, 1 from 8, 2 from 12 (RUMI_BAW_GROUPS = g: g - 1, at most 3).
+ *     Every other window of the batch (30 or more optimised key-frames, more than 512 key-frames, a profiled handle) runs in a worker context
+ *     W + H + R, one per worker thread: min(n_workers, number of such windows, 16) of them; a worker context takes X and the large-window
+ *     blocks as the handle's own window does.
+ * A later call with no more windows of either kind than an earlier one allocates nothing. */
 int rumi_opt_create(int32_t max_pose_edges, int32_t max_pose_batch, int32_t max_kf, int32_t max_mp, int32_t max_edges,
                     int32_t device, RumiOptimizer **out);
 void rumi_opt_destroy(RumiOptimizer *o);
@@ -77,10 +99,11 @@ int rumi_local_ba(RumiOptimizer *o, int32_t nKF, float *kf_pose7, const uint8_t 
                   const float *K4, const volatile uint8_t *stop_flag, uint8_t *erase_out, int32_t *stats);
 
 /* R independent windows of Optimizer::LocalBundleAdjustment (Optimizer.cc:1003-1355) in one call.  A window does not shard over GPUs or
- * workgroups ("replicas only"), but windows are independent: n_workers host threads, each with its own child handle
- * (stream + arenas, created on the first call and kept by `o`), take the windows from a shared counter, so the kernels of one window run while
- * another window's thread waits for the scalars of its LM trial.  Per window: the arguments of rumi_local_ba, stats[4] and the status of its
- * own run.  Returns the worst status. */
+ * workgroups ("replicas only"), but windows are independent.  Windows of up to 29 optimised key-frames are a batch
+ * dimension of the kernels: the calling thread drives all of them, each in a batch arena of the handle.  The others run one by one in worker
+ * contexts on n_workers host threads that take them from a shared counter, so the kernels of one window run while another window's thread
+ * waits for the scalars of its LM trial.  What the handle allocates for either kind: the paragraph above rumi_opt_create.  Per window: the
+ * arguments of rumi_local_ba, stats[4] and the status of its own run.  Returns the worst status. */
 typedef struct RumiBaWindow {
     int32_t n_kf; float *kf_pose7; const uint8_t *kf_fixed;
     int32_t n_mp; float *mp_pos3;
@@ -112,6 +135,10 @@ int rumi_opt_stage_ms(RumiOptimizer *o, float ms[8]);
  * reduced solve of every LM trial; rumi_opt_kernel_ms returns their sums in ms and the trial count: [0] hpp, [1] syrk, [2] solve, [3] trials. */
 int rumi_opt_set_profiling(RumiOptimizer *o, int32_t on);
 int rumi_opt_kernel_ms(RumiOptimizer *o, float ms[4]);
+
+/* out2 = {device bytes, pinned host bytes} the handle owns right now: the sum of the capacities of its blocks, batch arenas, batch runners
+ * and worker contexts included (the expressions above rumi_opt_create). */
+int rumi_opt_footprint(const RumiOptimizer *o, int64_t out2[2]);
 
 /* Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust) — R/lib_src/Optimizer.cc:54-351, monocular edges: the
  * full BA behind GlobalBundleAdjustemnt (map initialisation, Tracking.cc CreateInitialMapMonocular: 2 key-frames, 20 iterations; loop /

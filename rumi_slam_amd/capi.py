@@ -109,7 +109,7 @@ MATCH_SYMBOLS = ["rumi_descriptor_distance", "rumi_match_create", "rumi_match_de
                  "rumi_match_bruteforce_pair_scratch_bytes", "rumi_match_bruteforce_pair_shape", "rumi_match_bruteforce_pair_device"]
 
 OPT_SYMBOLS = ["rumi_opt_create", "rumi_opt_destroy", "rumi_pose_optimization", "rumi_pose_optimization_batch", "rumi_local_ba", "rumi_local_ba_batch", "rumi_merge_ba", "rumi_bundle_adjustment", "rumi_sim3_inliers",
-               "rumi_optimize_sim3", "rumi_sim3_ransac", "rumi_opt_stage_ms", "rumi_opt_set_profiling", "rumi_opt_kernel_ms",
+               "rumi_optimize_sim3", "rumi_sim3_ransac", "rumi_opt_stage_ms", "rumi_opt_set_profiling", "rumi_opt_kernel_ms", "rumi_opt_footprint",
                "rumi_essential_graph", "rumi_sim3_correct_points"]
 
 VOC_SYMBOLS = ["rumi_voc_create", "rumi_voc_load_text", "rumi_voc_destroy", "rumi_voc_words", "rumi_voc_levels", "rumi_voc_set_levels", "rumi_voc_assemble", "rumi_voc_transform_features",

@@ -10,7 +10,6 @@ struct BawArgs {                         // one window as the C ABI hands it ove
     const volatile uint8_t *stop_flag; uint8_t *erase_out; int32_t *stats;
 };
 struct BawPrep {                         // what staging a window leaves behind
-    RumiOptimizer *arena = nullptr;
     int nOpt = 0, n = 0, NP = 0, NT = 0;
     size_t rT = 0, rX = 0, rE = 0, rErr = 0, dnBytes = 0, outOff = 0;
     int cur = 0, iters = 0, trials = 0, itersFirst = 0;
@@ -19,42 +18,19 @@ struct BawPrep {                         // what staging a window leaves behind
 
 // Whether a window runs on this path (ba_run and rumi_local_ba_batch both ask here): up to 29 optimised key-frames (the tile solver), at most 512
 // key-frames (k_baw_system / k_baw_updchi cache every pose in LDS), and not on a profiled handle.  Everything else takes ba_run's host loop.
-static bool baw_eligible(const RumiOptimizer *o, int32_t nKF, const uint8_t *kf_fixed, int32_t nMP, int32_t nE) {
-    if (o->profiling || nKF < 1 || nKF > 512 || nE < 1 || nMP < 1 || !kf_fixed) return false;
+static bool baw_eligible(bool profiled, int32_t nKF, const uint8_t *kf_fixed, int32_t nMP, int32_t nE) {
+    if (profiled || nKF < 1 || nKF > 512 || nE < 1 || nMP < 1 || !kf_fixed) return false;
     int nOpt = 0;
     for (int k = 0; k < nKF; k++) nOpt += kf_fixed[k] ? 0 : 1;
     const int n = 6 * nOpt, NT = (n + 1 + 15) / 16;
     return n > 0 && NT <= kSolveTilesMax;
 }
 
-static int baw_arena_extras(RumiOptimizer *c) {
-    if (c->dGpart) return RUMI_OK;
-    const size_t nTmax = (size_t)kSolveTilesMax * (kSolveTilesMax + 1) / 2;
-    HIP_TRY(hipMalloc((void **)&c->dGpart, (size_t)kBawMaxSlices * nTmax * 256 * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&c->dGw, nTmax * 256 * sizeof(double)));
-    const size_t parts = std::max<size_t>(kBawMaxSlices, ((size_t)c->maxMP + 31) / 32) + 8;
-    HIP_TRY(hipMalloc((void **)&c->dChiPart, parts * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&c->dSclPart, parts * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&c->dWinSmall, 64));        // [0] solveOk (f64), [1] maxDiag (u64), [2] stopSeen, cur (2 x i32), [3] err (i32)
-    {   // the graph in landmark order, built by the k_baws_* kernels, and their scratch
-        const size_t E = (size_t)c->maxE, M = (size_t)c->maxMP;
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        c->sortedBytes = al((M + 1) * 4) * 2 + al(64 * 4) + al(E * 4) * 6 + al(E * 8) + al(E) + al((M / 16 + 2) * 32 * 4);
-        HIP_TRY(hipMalloc((void **)&c->dSorted, c->sortedBytes));
-    }
-    HIP_TRY(hipMalloc((void **)&c->dLmCtl, 2 * sizeof(LmCtl)));
-    if (hipHostMalloc((void **)&c->hWm, sizeof(WinMirror), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&c->dhWm, c->hWm, 0) != hipSuccess ||
-        hipHostMalloc((void **)&c->hLmCtl, 2 * sizeof(LmCtl) + 64, hipHostMallocDefault) != hipSuccess) return RUMI_E_NO_DEVICE;
-    std::memset((void *)c->hWm, 0, sizeof(WinMirror));
-    return RUMI_OK;
-}
-
 // Stages window `a` into arena `c` on stream `st` and fills its descriptor (the structure is derived on the device: k_baws_*).
-static int baw_stage(RumiOptimizer *c, hipStream_t st, int mode, const BawArgs &a, int gbaRobust, BAWin &Wd, BawPrep &P, int slicesWanted) {
+static int baw_stage(BaArena *c, hipStream_t st, int mode, const BawArgs &a, int gbaRobust, BAWin &Wd, BawPrep &P, int slicesWanted) {
     const int nKF = a.nKF, nMP = a.nMP, nE = a.nE;
     if (nKF > c->maxKF || nMP > c->maxMP || nE > c->maxE) { g_lastError = "local BA: problem larger than the optimiser's arenas"; return RUMI_E_CAPACITY; }
-    { const int rc = baw_arena_extras(c); if (rc != RUMI_OK) return rc; }
+    { const int rc = c->extras(); if (rc != RUMI_OK) return rc; }
     int nOpt = 0;
     for (int k = 0; k < nKF; k++) nOpt += a.kf_fixed[k] ? 0 : 1;
     const int n = 6 * nOpt;
@@ -62,8 +38,8 @@ static int baw_stage(RumiOptimizer *c, hipStream_t st, int mode, const BawArgs &
     // initial poses as doubles, the column blocks
     const size_t oT = 0, oX = al16(oT + (size_t)nKF * 64), oPC = al16(oX + (size_t)nMP * 12), oEM = al16(oPC + (size_t)nKF * 4), oEK = al16(oEM + (size_t)nE * 4),
                  oOb = al16(oEK + (size_t)nE * 4), oIn = al16(oOb + (size_t)nE * 8), upBytes = al16(oIn + (size_t)nE * 4);
-    if (upBytes > c->baStageCap) { g_lastError = "local BA: upload block larger than the optimiser's arenas"; return RUMI_E_CAPACITY; }
-    uint8_t *hs = c->hBa;
+    if (upBytes > c->stage.cap) { g_lastError = "local BA: upload block larger than the optimiser's arenas"; return RUMI_E_CAPACITY; }
+    uint8_t *hs = c->stage.h;
     ba_stage_poses(nKF, a.kf_pose7, reinterpret_cast<double *>(hs + oT));
     {
         int32_t *poseCol = reinterpret_cast<int32_t *>(hs + oPC);
@@ -73,7 +49,7 @@ static int baw_stage(RumiOptimizer *c, hipStream_t st, int mode, const BawArgs &
     std::memcpy(hs + oX, a.mp_pos3, (size_t)nMP * 12);
     std::memcpy(hs + oEM, a.e_mp, (size_t)nE * 4); std::memcpy(hs + oEK, a.e_kf, (size_t)nE * 4);
     std::memcpy(hs + oOb, a.e_obs, (size_t)nE * 8); std::memcpy(hs + oIn, a.e_inv_sigma2, (size_t)nE * 4);
-    HIP_TRY(hipMemcpyAsync(c->dBa, hs, upBytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->stage.d, hs, upBytes, hipMemcpyHostToDevice, st));
     const int NP = (n + 1 + 15) / 16 * 16, NT = NP / 16;
     Wd = BAWin{};
     Wd.nKF = nKF; Wd.nMP = nMP; Wd.nE = nE; Wd.nOpt = nOpt; Wd.n = n; Wd.NP = NP; Wd.NT = NT; Wd.nT = NT * (NT + 1) / 2;
@@ -86,12 +62,12 @@ static int baw_stage(RumiOptimizer *c, hipStream_t st, int mode, const BawArgs &
     Wd.delta = ba_huber_delta(mode);
     Wd.dsqr = Wd.delta * Wd.delta;
     Wd.cam = DCam{a.K4[0], a.K4[1], a.K4[2], a.K4[3]};
-    Wd.poseCol = (const int32_t *)(c->dBa + oPC); Wd.rawMP = (const int32_t *)(c->dBa + oEM); Wd.rawKF = (const int32_t *)(c->dBa + oEK);
-    Wd.rawObs = (const float *)(c->dBa + oOb); Wd.rawInfo = (const float *)(c->dBa + oIn); Wd.rawX = (const float *)(c->dBa + oX);
-    Wd.rawT = (const double *)(c->dBa + oT);
+    Wd.poseCol = (const int32_t *)(c->stage.d + oPC); Wd.rawMP = (const int32_t *)(c->stage.d + oEM); Wd.rawKF = (const int32_t *)(c->stage.d + oEK);
+    Wd.rawObs = (const float *)(c->stage.d + oOb); Wd.rawInfo = (const float *)(c->stage.d + oIn); Wd.rawX = (const float *)(c->stage.d + oX);
+    Wd.rawT = (const double *)(c->stage.d + oT);
     {
         auto alS = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        uint8_t *q = c->dSorted;
+        uint8_t *q = c->sorted.p;
         auto take = [&](size_t bytes) { uint8_t *r = q; q += alS(bytes); return r; };
         Wd.ptStart = (int32_t *)take((size_t)(nMP + 1) * 4); Wd.cursor = (int32_t *)take((size_t)(nMP + 1) * 4); Wd.kfRowStart = (int32_t *)take(64 * 4);
         Wd.sMP = (int32_t *)take((size_t)nE * 4); Wd.sKF = (int32_t *)take((size_t)nE * 4); Wd.sEdge = (int32_t *)take((size_t)nE * 4);
@@ -99,20 +75,20 @@ static int baw_stage(RumiOptimizer *c, hipStream_t st, int mode, const BawArgs &
         Wd.obs = (float *)take((size_t)nE * 8); Wd.rank8 = take((size_t)nE);
         Wd.nBlk = (nMP + 15) / 16;
         Wd.blkCnt = (int32_t *)take((size_t)Wd.nBlk * 32 * 4);
-        if ((size_t)(q - c->dSorted) > c->sortedBytes) { g_lastError = "local BA: structure arena too small"; return RUMI_E_CAPACITY; }
+        if ((size_t)(q - c->sorted.p) > c->sorted.cap) { g_lastError = "local BA: structure arena too small"; return RUMI_E_CAPACITY; }
     }
-    Wd.err = reinterpret_cast<int32_t *>(c->dWinSmall + 24);
-    Wd.off = c->dEOff;
-    Wd.T[0] = c->dT[0]; Wd.T[1] = c->dT[1]; Wd.X[0] = c->dX[0]; Wd.X[1] = c->dX[1];
-    Wd.panel = c->dPanel; Wd.Dinv = c->dDinv; Wd.bl = c->dBl; Wd.Hpp = c->dHpp; Wd.bp = c->dBp; Wd.x = c->dXv; Wd.lastChi2 = c->dChi;
-    Wd.Gpart = c->dGpart; Wd.G = c->dGw; Wd.chiPart = c->dChiPart; Wd.sclPart = c->dSclPart;
-    Wd.solveOk = reinterpret_cast<double *>(c->dWinSmall); Wd.maxDiag = reinterpret_cast<unsigned long long *>(c->dWinSmall + 8);
-    Wd.stopSeen = reinterpret_cast<int32_t *>(c->dWinSmall + 16);
-    Wd.lm = c->dLmCtl; Wd.mirror = c->dhWm; Wd.stopWord = c->dhStop;
-    P.arena = c; P.nOpt = nOpt; P.n = n; P.NP = NP; P.NT = NT;
+    Wd.err = reinterpret_cast<int32_t *>(c->winSmall.p + 24);
+    Wd.off = c->eOff.p;
+    Wd.T[0] = c->T[0].p; Wd.T[1] = c->T[1].p; Wd.X[0] = c->X[0].p; Wd.X[1] = c->X[1].p;
+    Wd.panel = c->panel.p; Wd.Dinv = c->Dinv.p; Wd.bl = c->bl.p; Wd.Hpp = c->Hpp.p; Wd.bp = c->bp.p; Wd.x = c->xv.p; Wd.lastChi2 = c->chi.p;
+    Wd.Gpart = c->Gpart.p; Wd.G = c->Gw.p; Wd.chiPart = c->chiPart.p; Wd.sclPart = c->sclPart.p;
+    Wd.solveOk = reinterpret_cast<double *>(c->winSmall.p); Wd.maxDiag = reinterpret_cast<unsigned long long *>(c->winSmall.p + 8);
+    Wd.stopSeen = reinterpret_cast<int32_t *>(c->winSmall.p + 16);
+    Wd.lm = c->lmCtl.p; Wd.mirror = c->wm.d; Wd.stopWord = c->stop.d;
+    P.nOpt = nOpt; P.n = n; P.NP = NP; P.NT = NT;
     P.rT = 0; P.rX = al16(P.rT + (size_t)nKF * 64); P.rE = al16(P.rX + (size_t)nMP * 24); P.rErr = al16(P.rE + (size_t)nE); P.dnBytes = al16(P.rErr + 16);
-    Wd.outT = reinterpret_cast<double *>(c->dBaOut + P.rT); Wd.outX = reinterpret_cast<double *>(c->dBaOut + P.rX); Wd.erase = c->dBaOut + P.rE;
-    Wd.errOut = reinterpret_cast<int32_t *>(c->dBaOut + P.rErr);
+    Wd.outT = reinterpret_cast<double *>(c->stageOut.p + P.rT); Wd.outX = reinterpret_cast<double *>(c->stageOut.p + P.rX); Wd.erase = c->stageOut.p + P.rE;
+    Wd.errOut = reinterpret_cast<int32_t *>(c->stageOut.p + P.rErr);
     return RUMI_OK;
 }
 
@@ -121,10 +97,10 @@ static int baw_stage(RumiOptimizer *c, hipStream_t st, int mode, const BawArgs &
 // copy back): a batch is cut into two groups, so that the transfers, the one-workgroup-per-window solve and the launch tails of one group run
 // beside the wide kernels of the other.
 struct BawGroup {
-    RumiOptimizer *run = nullptr;          // lends its stream, events and window table
+    BaRunner *run = nullptr;               // stream, events, window table, result block
     int mode = 0, nW = 0, gbaIterations = 0, gbaRobust = 1;
     const BawArgs *args = nullptr;
-    RumiOptimizer *const *arenas = nullptr;
+    BaArena *arenas = nullptr;             // window i of the group runs in arenas[i]
     int32_t *status = nullptr;
     std::vector<BawPrep> prep;
     std::vector<int> live;
@@ -141,15 +117,10 @@ struct BawGroup {
     double tStage = 0, tLm0 = 0, tLm1 = 0;
 
     hipStream_t st() const { return run->stream; }
-    BAWin *tab() const { return run->hWinTab; }
+    BAWin *tab() const { return run->winTab.h; }
 
     int begin() {                          // stage every window, derive the structure on the device, start the first pass
-        RumiOptimizer *o = run;
         if (nW > kBawMaxWindows) { g_lastError = "local BA batch: too many windows in one launch group"; return RUMI_E_CAPACITY; }
-        if (!o->hWinTab) {
-            if (hipHostMalloc((void **)&o->hWinTab, sizeof(BAWin) * kBawMaxWindows, hipHostMallocDefault) != hipSuccess ||
-                hipMalloc((void **)&o->dWinTab, sizeof(BAWin) * kBawMaxWindows) != hipSuccess) return RUMI_E_NO_DEVICE;
-        }
         const double tA = ba_now_us();
         prep.assign((size_t)nW, BawPrep{});
         static const int envSlices = std::getenv("RUMI_BAW_SLICES") ? std::atoi(std::getenv("RUMI_BAW_SLICES")) : 0;
@@ -159,14 +130,14 @@ struct BawGroup {
             status[i] = RUMI_OK;
             int rcExit;
             if (ba_early_exit(mode, a.nKF, a.kf_fixed, a.stop_flag, a.stats, &rcExit)) { if (rcExit != RUMI_OK) status[i] = worst = rcExit; continue; }
-            const int rc = baw_stage(arenas[i], st(), mode, a, gbaRobust, tab()[live.size()], prep[i], slicesWanted);
+            const int rc = baw_stage(&arenas[i], st(), mode, a, gbaRobust, tab()[live.size()], prep[i], slicesWanted);
             if (rc != RUMI_OK) { status[i] = worst = rc; continue; }
             live.push_back(i);
         }
         L = (int)live.size();
         tStage = ba_now_us() - tA;
         if (L == 0) { phase = kDone; return RUMI_OK; }
-        HIP_TRY(hipEventRecord(o->ev[0], st()));
+        HIP_TRY(hipEventRecord(run->ev[0], st()));
         int maxE = 1, maxMP = 1, maxBlk = 1;
         for (int j = 0; j < L; j++) {                       // launch geometry: the maxima over the live windows
             const BAWin &Wd = tab()[j];
@@ -184,8 +155,8 @@ struct BawGroup {
         if (ldsSys > 48 * 1024) HIP_TRY(raise_lds_limit(reinterpret_cast<const void *>(sysK), ldsSys));
         if (ldsTiles > 48 * 1024) HIP_TRY(raise_lds_limit(reinterpret_cast<const void *>(k_baw_solve), ldsTiles));
         // the structure of every window: seven small launches for the whole group
-        const BAWin *dTab = o->dWinTab;
-        HIP_TRY(hipMemcpyAsync(o->dWinTab, tab(), sizeof(BAWin) * L, hipMemcpyHostToDevice, st()));
+        const BAWin *dTab = run->winTab.d;
+        HIP_TRY(hipMemcpyAsync(run->winTab.d, tab(), sizeof(BAWin) * L, hipMemcpyHostToDevice, st()));
         const int gE2 = (maxE + 255) / 256;
         hipLaunchKernelGGL(k_baws_zero, dim3((std::max(maxE, maxMP + 1) + 255) / 256, L), dim3(256), 0, st(), dTab);
         hipLaunchKernelGGL(k_baws_count, dim3(gE2, L), dim3(256), 0, st(), dTab);
@@ -200,27 +171,26 @@ struct BawGroup {
         return start_pass(firstIt);
     }
     int start_pass(int maxIt) {            // a pass starts from the table alone: the head of slot 0 makes the control block
-        RumiOptimizer *o = run;
         passMaxIt = maxIt;
         for (int j = 0; j < L; j++) {
             tab()[j].maxIt = maxIt;
             tab()[j].cur0 = prep[live[j]].cur;
-            *arenas[live[j]]->hStop = 0;
+            *arenas[live[j]].stop.h = 0;
         }
-        HIP_TRY(hipMemcpyAsync(o->dWinTab, tab(), sizeof(BAWin) * L, hipMemcpyHostToDevice, st()));
-        runId = ++o->bawRun;
+        HIP_TRY(hipMemcpyAsync(run->winTab.d, tab(), sizeof(BAWin) * L, hipMemcpyHostToDevice, st()));
+        runId = ++run->bawRun;
         maxSlots = maxIt * 10 + 2;                          // init, the trials, and the head that takes the last decision
         enq = 0; naps = 0;
         phase = kPass;
         return RUMI_OK;
     }
-    void report(RumiOptimizer *c, int *slotSeen, bool *done) const {
-        const unsigned long long w = __atomic_load_n(const_cast<const unsigned long long *>(&c->hWm->word), __ATOMIC_ACQUIRE);
+    void report(const BaArena *c, int *slotSeen, bool *done) const {
+        const unsigned long long w = __atomic_load_n(const_cast<const unsigned long long *>(&c->wm.h->word), __ATOMIC_ACQUIRE);
         if ((unsigned)(w >> 32) != runId) { *slotSeen = -1; *done = false; return; }
         *slotSeen = (int)((w & 0xFFFFFFFFull) >> 1) - 1; *done = (w & 1) != 0;
     }
     void enqueue_slot(int slot) {
-        const BAWin *dTab = run->dWinTab;
+        const BAWin *dTab = run->winTab.d;
         hipLaunchKernelGGL(sysK, dim3(maxS, L), dim3(256), ldsSys, st(), dTab, slot, runId);
         if (maxS > 64) hipLaunchKernelGGL((k_baw_reduce<16>), dim3(4 * maxT + maxOpt, L), dim3(1024), 0, st(), dTab, slot, 4 * maxT);
         else hipLaunchKernelGGL((k_baw_reduce<4>), dim3(4 * maxT + maxOpt, L), dim3(256), 0, st(), dTab, slot, 4 * maxT);
@@ -236,12 +206,12 @@ struct BawGroup {
             int seen = 1 << 30;
             bool allDone = true;
             for (int j = 0; j < L; j++) {
-                RumiOptimizer *c = arenas[live[j]];
+                BaArena *c = &arenas[live[j]];
                 int sl; bool dn;
                 report(c, &sl, &dn);
                 if (!dn) { allDone = false; seen = std::min(seen, sl); }
                 const volatile uint8_t *sf = args[live[j]].stop_flag;
-                if (sf && *sf) *c->hStop = 1;
+                if (sf && *sf) *c->stop.h = 1;
             }
             if (!allDone) {
                 if (enq < maxSlots && (enq <= 1 || enq <= seen + 1)) {
@@ -251,16 +221,16 @@ struct BawGroup {
                 } else if ((++naps & 0x3FF) == 0 && hipStreamQuery(st()) != hipErrorNotReady) {
                     HIP_TRY(hipStreamSynchronize(st()));
                     bool ok = true;
-                    for (int j = 0; j < L; j++) { int sl; bool dn; report(arenas[live[j]], &sl, &dn); ok &= dn; }
+                    for (int j = 0; j < L; j++) { int sl; bool dn; report(&arenas[live[j]], &sl, &dn); ok &= dn; }
                     if (!ok && enq >= maxSlots) { g_lastError = "local BA: the device-side LM loop stalled"; return RUMI_E_NO_DEVICE; }
                 }
                 return RUMI_OK;
             }
             __atomic_thread_fence(__ATOMIC_ACQUIRE);
             for (int j = 0; j < L; j++) {
-                RumiOptimizer *c = arenas[live[j]];
+                BaArena *c = &arenas[live[j]];
                 BawPrep &P = prep[live[j]];
-                P.cur = c->hWm->cur; P.iters += c->hWm->iters; P.trials += c->hWm->trials; P.ran = true;
+                P.cur = c->wm.h->cur; P.iters += c->wm.h->iters; P.trials += c->wm.h->trials; P.ran = true;
             }
             anyRun = true;
             *worked = true;
@@ -271,7 +241,7 @@ struct BawGroup {
                 if (!stopped) {
                     int gM = 1;
                     for (int j = 0; j < L; j++) gM = std::max(gM, (tab()[j].nE + 255) / 256);
-                    hipLaunchKernelGGL(k_baw_mark, dim3(gM, L), dim3(256), 0, st(), run->dWinTab);     // (reads the table of the first pass: same arrays)
+                    hipLaunchKernelGGL(k_baw_mark, dim3(gM, L), dim3(256), 0, st(), run->winTab.d);     // (reads the table of the first pass: same arrays)
                     for (int j = 0; j < L; j++) tab()[j].robust = 0;
                     passNo = 1;
                     return start_pass(10);
@@ -287,38 +257,36 @@ struct BawGroup {
         return RUMI_OK;
     }
     int finish_enqueue() {                 // results: [T | X | erase | err] per window, gathered by one launch, one copy each
-        RumiOptimizer *o = run;
         tLm1 = ba_now_us();
         // every window's block [T | X | erase | err] into ONE buffer of the group: one copy back instead of one per window
         size_t total = 0;
         for (int j = 0; j < L; j++) { prep[live[j]].outOff = total; total += (prep[live[j]].dnBytes + 255) & ~(size_t)255; }
-        { const int rcg = o->groupOut.reserve(total, total + total / 2); if (rcg != RUMI_OK) return rcg; }
+        if (total > run->groupOut.cap) { g_lastError = "local BA: result block larger than the runner's"; return RUMI_E_CAPACITY; }   // (cannot happen: every window passed baw_stage's limits)
         for (int j = 0; j < L; j++) {
             const BawPrep &P = prep[live[j]];
             BAWin &Wd = tab()[j];
             Wd.useLast = P.ran ? 1 : 0; Wd.cur0 = P.cur;
-            uint8_t *base = o->groupOut.d + P.outOff;
+            uint8_t *base = run->groupOut.d + P.outOff;
             Wd.outT = reinterpret_cast<double *>(base + P.rT); Wd.outX = reinterpret_cast<double *>(base + P.rX); Wd.erase = base + P.rE;
             Wd.errOut = reinterpret_cast<int32_t *>(base + P.rErr);
         }
-        HIP_TRY(hipMemcpyAsync(o->dWinTab, tab(), sizeof(BAWin) * L, hipMemcpyHostToDevice, st()));
-        hipLaunchKernelGGL(k_baw_finalize, dim3(maxF, L), dim3(256), 0, st(), o->dWinTab);
+        HIP_TRY(hipMemcpyAsync(run->winTab.d, tab(), sizeof(BAWin) * L, hipMemcpyHostToDevice, st()));
+        hipLaunchKernelGGL(k_baw_finalize, dim3(maxF, L), dim3(256), 0, st(), run->winTab.d);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(o->ev[1], st()));
-        HIP_TRY(hipMemcpyAsync(o->groupOut.h, o->groupOut.d, total, hipMemcpyDeviceToHost, st()));
+        HIP_TRY(hipEventRecord(run->ev[1], st()));
+        HIP_TRY(hipMemcpyAsync(run->groupOut.h, run->groupOut.d, total, hipMemcpyDeviceToHost, st()));
         phase = kFinalWait;
         return RUMI_OK;
     }
     int finish() {
-        RumiOptimizer *o = run;
         HIP_TRY(hipStreamSynchronize(st()));
-        HIP_TRY(hipEventElapsedTime(&o->stageMs[5], o->ev[0], o->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&run->stageMs[5], run->ev[0], run->ev[1]));
         const double tD = ba_now_us();
         for (int j = 0; j < L; j++) {
             const int i = live[j];
             const BawArgs &a = args[i];
             const BawPrep &P = prep[i];
-            const uint8_t *hb = o->groupOut.h + P.outOff;
+            const uint8_t *hb = run->groupOut.h + P.outOff;
             const int32_t err = *reinterpret_cast<const int32_t *>(hb + P.rErr);
             if (err) {                                      // nothing of this window is written back
                 g_lastError = (err & 1) ? "local BA: edge index out of range" : "local BA: a map point is observed twice by one key-frame";
@@ -336,21 +304,26 @@ struct BawGroup {
     }
 };
 
-// nW windows (each already known to be eligible) from ONE thread; arenas[i] holds window i's arrays; runners[g] lends group g its stream and table.
-static int baw_run(RumiOptimizer *o, int mode, int nW, const BawArgs *args, RumiOptimizer *const *arenas, int gbaIterations, int gbaRobust, int32_t *status,
-                   RumiOptimizer *const *runners = nullptr, int nRunners = 1) {
-    HIP_TRY(hipSetDevice(o->device));
+// Launch groups of a batch of nW windows when nRunners runners can be had.  Every group is a chain of dependent launches (system -> reduce -> solve
+// -> update per trial) that leaves most of the device idle; chains of different groups fill each other's gaps.  16 windows of BASELINE configs[3]:
+// 0.147 ms per window as one group, 0.127-0.135 as two, 0.120-0.124 as three, 0.144-0.152 as four (the one host thread then is the limit); 12 windows
+// 0.155 / 0.135-0.145 / 0.129-0.132; 8 windows 0.174 / 0.166 / 0.166
+static int baw_groups(int nW, int nRunners) {
     static const int envGroups = std::getenv("RUMI_BAW_GROUPS") ? std::atoi(std::getenv("RUMI_BAW_GROUPS")) : 0;
-    // launch groups: every group is a chain of dependent launches (system -> reduce -> solve -> update per trial) that leaves most of the device idle;
-    // chains of different groups fill each other's gaps.  16 windows of BASELINE configs[3]: 0.147 ms per window as one group, 0.127-0.135 as two,
-    // 0.120-0.124 as three, 0.144-0.152 as four (the one host thread then is the limit); 12 windows 0.155 / 0.135-0.145 / 0.129-0.132; 8 windows 0.174 / 0.166 / 0.166
-    int G = envGroups > 0 ? envGroups : (nW >= 12 ? 3 : nW >= 8 ? 2 : 1);
-    G = std::max(1, std::min(std::min(G, nRunners), nW));
+    const int G = envGroups > 0 ? envGroups : (nW >= 12 ? 3 : nW >= 8 ? 2 : 1);
+    return std::max(1, std::min(std::min(G, nRunners), nW));
+}
+
+// nW windows (each already known to be eligible) from ONE thread; window i runs in arenas[i]; runners[g] drives group g (baw_groups(nW, nRunners) of them).
+static int baw_run(int mode, int nW, const BawArgs *args, BaArena *arenas, int gbaIterations, int gbaRobust, int32_t *status,
+                   BaRunner *const *runners, int nRunners) {
+    HIP_TRY(hipSetDevice(runners[0]->device));
+    const int G = baw_groups(nW, nRunners);
     std::vector<BawGroup> grp((size_t)G);
     for (int g = 0, i0 = 0; g < G; g++) {
         const int cnt = (nW - i0 + (G - g) - 1) / (G - g);
         BawGroup &B = grp[g];
-        B.run = runners ? runners[g] : o; B.mode = mode; B.nW = cnt; B.args = args + i0; B.arenas = arenas + i0; B.status = status + i0;
+        B.run = runners[g]; B.mode = mode; B.nW = cnt; B.args = args + i0; B.arenas = arenas + i0; B.status = status + i0;
         B.gbaIterations = gbaIterations; B.gbaRobust = gbaRobust;
         i0 += cnt;
     }

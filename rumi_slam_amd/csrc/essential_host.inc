@@ -12,7 +12,7 @@ extern "C" int rumi_essential_graph(RumiOptimizer *o, int32_t n_v, double *S_io8
     // ---- validation: nothing below this block sees an unchecked index or a non-finite number ----
     if (!o || !S_io8 || !fixed || !fix_scale || !stats || !chi2_trace || n_v < 1 || n_e < 0 || n_iterations < 0) { g_lastError = "rumi_essential_graph: null argument or negative size"; return RUMI_E_INVALID; }
     if (n_e > 0 && (!e_v0 || !e_v1 || !meas8)) { g_lastError = "rumi_essential_graph: edges without arrays"; return RUMI_E_INVALID; }
-    if (n_v > o->maxKF || n_e > o->maxE) { g_lastError = "rumi_essential_graph: graph larger than the optimiser's arenas"; return RUMI_E_CAPACITY; }
+    if (n_v > o->ba.arena.maxKF || n_e > o->ba.arena.maxE) { g_lastError = "rumi_essential_graph: graph larger than the optimiser's arenas"; return RUMI_E_CAPACITY; }
     for (int v = 0; v < n_v; v++) if (!eg_sim3_ok(S_io8 + (size_t)v * 8)) { g_lastError = "rumi_essential_graph: vertex estimate not finite, not a unit quaternion or scale <= 0"; return RUMI_E_INVALID; }
     for (int e = 0; e < n_e; e++) {
         if (e_v0[e] < 0 || e_v0[e] >= n_v || e_v1[e] < 0 || e_v1[e] >= n_v) { g_lastError = "rumi_essential_graph: edge vertex index out of range"; return RUMI_E_INVALID; }
@@ -54,7 +54,9 @@ extern "C" int rumi_essential_graph(RumiOptimizer *o, int32_t n_v, double *S_io8
         }
     }
     HIP_TRY(hipSetDevice(o->device));
-    hipStream_t st = o->stream;
+    BaRunner &run = o->ba.run;                       // the handle's own stream, events and stage times
+    BaArena::HostLoop &sc = o->ba.arena.solo;        // ... and published scalars
+    hipStream_t st = run.stream;
     // ---- device arenas: the dense matrix [(n + 1) x n | n reciprocal pivots] and one block for everything else, grown on demand ----
     const size_t aBytes = ((size_t)(n + 1) * n + n) * sizeof(double);
     { const int rcg = o->egA.reserve(aBytes, aBytes); if (rcg != RUMI_OK) return rcg; }
@@ -80,15 +82,15 @@ extern "C" int rumi_essential_graph(RumiOptimizer *o, int32_t n_v, double *S_io8
     double *A = (double *)o->egA.p, *rdg = A + (size_t)(n + 1) * n, *dS[2] = {(double *)(d + oS), (double *)(d + oS1)};
     const EGDev G{n_v, nE, nR, n, (const int32_t *)(d + oV0), (const int32_t *)(d + oV1), (const double *)(d + oM), d + oFix, d + oFs,
                   (const int32_t *)(d + oCol), (const int32_t *)(d + oRow), (const int32_t *)(d + oInc), (double *)(d + oEB), (double *)(d + oChi), A,
-                  (double *)(d + oB), (double *)(d + oX), (double *)(d + oPart), o->dScal};
+                  (double *)(d + oB), (double *)(d + oX), (double *)(d + oPart), sc.scal.p};
     const unsigned gE = (unsigned)((nE + 255) / 256), gV = (unsigned)((n_v + 255) / 256);
     auto chi2_of = [&](const double *S, int withScale, double *chi, double *scale) -> int {
         hipLaunchKernelGGL(k_eg_chi2, dim3(gE), dim3(256), 0, st, G, S);
         hipLaunchKernelGGL(k_eg_reduce, dim3(1), dim3(256), 0, st, G, withScale);
-        const int rcf = fetch_published_scalars(o, st);
+        const int rcf = fetch_published_scalars(sc, st);
         if (rcf != RUMI_OK) return rcf;
-        *chi = o->hScal[0];
-        if (scale) *scale = o->hScal[1];
+        *chi = sc.pub.h[0];
+        if (scale) *scale = sc.pub.h[1];
         return RUMI_OK;
     };
     for (int i = 0; i <= n_iterations; i++) chi2_trace[i] = kNaN;
@@ -109,23 +111,23 @@ extern "C" int rumi_essential_graph(RumiOptimizer *o, int32_t n_v, double *S_io8
             const int trial = cur ^ 1;
             HIP_TRY(hipMemsetAsync(A, 0, (size_t)(n + 1) * n * sizeof(double), st));
             hipLaunchKernelGGL(k_eg_assemble, dim3((unsigned)((nR + 3) / 4)), dim3(256), 0, st, G, lambda);
-            HIP_TRY(hipEventRecord(o->ev[0], st));
+            HIP_TRY(hipEventRecord(run.ev[0], st));
             for (int j0 = 0; j0 < n; j0 += kNB) {
                 const int w = std::min(kNB, n - j0), rows = n + 1 - (j0 + w);
-                hipLaunchKernelGGL(k_chol_diag, dim3(1), dim3(256), 0, st, A, n, n, j0, rdg, o->dScal);
+                hipLaunchKernelGGL(k_chol_diag, dim3(1), dim3(256), 0, st, A, n, n, j0, rdg, sc.scal.p);
                 if (rows > 0) {
                     const int T = (rows + 63) / 64;
                     hipLaunchKernelGGL(k_chol_trsm, dim3(T), dim3(256), 0, st, A, n, n, j0, rdg);
                     if (j0 + w < n) hipLaunchKernelGGL(k_chol_syrk, dim3(T, T), dim3(256), 0, st, A, n, n, j0);
                 }
             }
-            hipLaunchKernelGGL(k_eg_backsub, dim3(1), dim3(1024), 0, st, A, n, n, rdg, G.x, o->dScal);
-            HIP_TRY(hipEventRecord(o->ev[1], st));
+            hipLaunchKernelGGL(k_eg_backsub, dim3(1), dim3(1024), 0, st, A, n, n, rdg, G.x, sc.scal.p);
+            HIP_TRY(hipEventRecord(run.ev[1], st));
             hipLaunchKernelGGL(k_eg_update, dim3(gV), dim3(256), 0, st, G, lambda, dS[cur], dS[trial]);
             HIP_TRY(hipGetLastError());
             double tempChi = 0, scale = 0;
             if ((rc = chi2_of(dS[trial], 1, &tempChi, &scale)) != RUMI_OK) return rc;
-            if (o->hScal[3] == 0.0) tempChi = std::numeric_limits<double>::max();     // the factorisation failed: g2o's solve() returned false
+            if (sc.pub.h[3] == 0.0) tempChi = std::numeric_limits<double>::max();     // the factorisation failed: g2o's solve() returned false
             rho = (currentChi - tempChi) / (scale + 1e-3);
             if (rho > 0 && std::isfinite(tempChi)) {
                 double alpha = 1. - std::pow((2 * rho - 1), 3);
@@ -153,16 +155,16 @@ extern "C" int rumi_essential_graph(RumiOptimizer *o, int32_t n_v, double *S_io8
     HIP_TRY(hipStreamSynchronize(st));
     for (int v = 0; v < n_v; v++) if (col[v] >= 0) std::memcpy(S_io8 + (size_t)v * 8, out.data() + (size_t)v * 8, 64);
     stats[0] = iters; stats[1] = trials; stats[2] = nR; stats[3] = how;
-    for (auto &m : o->stageMs) m = 0.f;
-    if (trials > 0) HIP_TRY(hipEventElapsedTime(&o->stageMs[3], o->ev[0], o->ev[1]));      // factorisation + back-substitution of the last trial
-    o->stageMs[5] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (auto &m : run.stageMs) m = 0.f;
+    if (trials > 0) HIP_TRY(hipEventElapsedTime(&run.stageMs[3], run.ev[0], run.ev[1]));      // factorisation + back-substitution of the last trial
+    run.stageMs[5] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return RUMI_OK;
 }
 
 extern "C" int rumi_sim3_correct_points(RumiOptimizer *o, int32_t mode, int32_t n, float *X, const int32_t *ref, int32_t n_v, const void *tab_a,
                                         const void *tab_b) {
     if (!o || (mode != 0 && mode != 1) || n < 0 || n_v < 1 || !tab_a || !tab_b || (n > 0 && (!X || !ref))) { g_lastError = "rumi_sim3_correct_points: null argument, negative size or unknown mode"; return RUMI_E_INVALID; }
-    if (n_v > o->maxKF || n > o->maxMP) { g_lastError = "rumi_sim3_correct_points: more vertices or points than the optimiser's arenas"; return RUMI_E_CAPACITY; }
+    if (n_v > o->ba.arena.maxKF || n > o->ba.arena.maxMP) { g_lastError = "rumi_sim3_correct_points: more vertices or points than the optimiser's arenas"; return RUMI_E_CAPACITY; }
     for (int i = 0; i < n; i++) {
         if (ref[i] < -1 || ref[i] >= n_v) { g_lastError = "rumi_sim3_correct_points: reference vertex index out of range"; return RUMI_E_INVALID; }
         if (!std::isfinite(X[3 * i]) || !std::isfinite(X[3 * i + 1]) || !std::isfinite(X[3 * i + 2])) { g_lastError = "rumi_sim3_correct_points: point not finite"; return RUMI_E_INVALID; }
@@ -178,7 +180,7 @@ extern "C" int rumi_sim3_correct_points(RumiOptimizer *o, int32_t mode, int32_t 
     }
     if (n == 0) return RUMI_OK;
     HIP_TRY(hipSetDevice(o->device));
-    hipStream_t st = o->stream;
+    hipStream_t st = o->ba.run.stream;
     auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
     const size_t tb = (size_t)n_v * (mode == 0 ? 64 : 28), oX = 0, oR = al(oX + (size_t)n * 12), oA = al(oR + (size_t)n * 4), oB = al(oA + tb), total = al(oB + tb);
     { const int rcg = o->eg.reserve(total, total); if (rcg != RUMI_OK) return rcg; }

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <mutex>
@@ -111,6 +112,58 @@ template <class T> struct MirrorBuf {
         if (rc == RUMI_OK) cap = want; else release();
         return rc;
     }
+};
+
+// A mapped, coherent pinned block that kernels read and write in place (a stop word, published scalars), with the address the device uses for
+// it.  MirrorBuf's rules; a new block comes back zeroed.
+template <class T> struct MappedBuf {
+    T *h = nullptr, *d = nullptr;   // one memory, as the host and as the device see it
+    size_t cap = 0;                 // elements
+    MappedBuf() = default;
+    MappedBuf(const MappedBuf &) = delete;
+    MappedBuf &operator=(const MappedBuf &) = delete;
+    ~MappedBuf() { release(); }
+    void release() { if (h) (void)hipHostFree((void *)h); h = d = nullptr; cap = 0; }
+    int reserve(size_t need, size_t want) {
+        if (need <= cap) return RUMI_OK;
+        release();
+        hipError_t e = hipHostMalloc((void **)&h, std::max<size_t>(want, 1) * sizeof(T), hipHostMallocMapped | hipHostMallocCoherent);
+        if (e != hipSuccess) h = nullptr;
+        else e = hipHostGetDevicePointer((void **)&d, (void *)h, 0);
+        if (e != hipSuccess) { release(); HIP_TRY(e); }
+        std::memset((void *)h, 0, std::max<size_t>(want, 1) * sizeof(T));
+        cap = want;
+        return RUMI_OK;
+    }
+};
+
+// A stream (non-blocking) and an event that are destroyed with their owner; empty until create(), which does nothing the second time.
+struct StreamHold {
+    hipStream_t s = nullptr;
+    StreamHold() = default;
+    StreamHold(const StreamHold &) = delete;
+    StreamHold &operator=(const StreamHold &) = delete;
+    ~StreamHold() { if (s) (void)hipStreamDestroy(s); }
+    int create() { if (!s) HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return RUMI_OK; }
+    operator hipStream_t() const { return s; }
+};
+struct EventHold {
+    hipEvent_t e = nullptr;
+    EventHold() = default;
+    EventHold(const EventHold &) = delete;
+    EventHold &operator=(const EventHold &) = delete;
+    ~EventHold() { if (e) (void)hipEventDestroy(e); }
+    int create() { if (!e) HIP_TRY(hipEventCreate(&e)); return RUMI_OK; }
+    operator hipEvent_t() const { return e; }
+};
+
+// What a set of owning buffers holds right now, in bytes: device memory and pinned host memory.
+struct Footprint {
+    int64_t dev = 0, pin = 0;
+    template <class T> void one(const DevBuf<T> &b) { dev += (int64_t)(b.cap * sizeof(T)); }
+    template <class T> void one(const MirrorBuf<T> &b) { dev += (int64_t)(b.cap * sizeof(T)); pin += (int64_t)(b.cap * sizeof(T)); }
+    template <class T> void one(const MappedBuf<T> &b) { pin += (int64_t)(b.cap * sizeof(T)); }
+    template <class... B> void add(const B &...b) { (one(b), ...); }
 };
 
 // The device of a handle that binds at its first call past validation, so that creating one, its argument checks and its destruction run on a

@@ -18,8 +18,8 @@ extern "C" int rumi_sim3_inliers(RumiOptimizer *o, int32_t n_pairs, const int32_
         const size_t oP = 0, oA = al16(oP + (size_t)total * 4), oB = al16(oA + (size_t)n_pairs * 64), oK = al16(oB + (size_t)n_pairs * 64), oX1 = al16(oK + 32),
                      oX2 = al16(oX1 + (size_t)total * 12), oK1 = al16(oX2 + (size_t)total * 12), oK2 = al16(oK1 + (size_t)total * 8), oS1 = al16(oK2 + (size_t)total * 8),
                      oS2 = al16(oS1 + (size_t)total * 4), oE1 = al16(oS2 + (size_t)total * 4), oE2 = al16(oE1 + (size_t)total), bytes = al16(oE2 + (size_t)total);
-        if (bytes > o->baStageCap || (size_t)total > o->baStageCap) { g_lastError = "Sim3 inliers: more matches than the optimiser's arenas hold"; return RUMI_E_CAPACITY; }
-        uint8_t *h = o->hBa;
+        if (bytes > o->ba.arena.stage.cap || (size_t)total > o->ba.arena.stage.cap) { g_lastError = "Sim3 inliers: more matches than the optimiser's arenas hold"; return RUMI_E_CAPACITY; }
+        uint8_t *h = o->ba.arena.stage.h;
         int32_t *pairOf = reinterpret_cast<int32_t *>(h + oP);
         for (int p = 0; p < n_pairs; p++) for (int i = pair_start[p]; i < pair_start[p + 1]; i++) pairOf[i] = p;
         std::memcpy(h + oA, S_c1w2, (size_t)n_pairs * 64); std::memcpy(h + oB, S_c2w1, (size_t)n_pairs * 64);
@@ -28,13 +28,13 @@ extern "C" int rumi_sim3_inliers(RumiOptimizer *o, int32_t n_pairs, const int32_
         std::memcpy(h + oK1, kp1, (size_t)total * 8); std::memcpy(h + oK2, kp2, (size_t)total * 8);
         std::memcpy(h + oS1, sigma2_1, (size_t)total * 4); std::memcpy(h + oS2, sigma2_2, (size_t)total * 4);
         std::memcpy(h + oE1, edge1, (size_t)total); std::memcpy(h + oE2, edge2, (size_t)total);
-        HIP_TRY(hipMemcpyAsync(o->dBa, h, bytes, hipMemcpyHostToDevice, nullptr));
-        uint8_t *d = o->dBa;
+        HIP_TRY(hipMemcpyAsync(o->ba.arena.stage.d, h, bytes, hipMemcpyHostToDevice, nullptr));
+        uint8_t *d = o->ba.arena.stage.d;
         hipLaunchKernelGGL(k_sim3_inliers, dim3((total + 255) / 256), dim3(256), 0, nullptr, total, (const int32_t *)(d + oP), (const double *)(d + oA),
                            (const double *)(d + oB), (const float *)(d + oK), (const float *)(d + oK + 16), (const float *)(d + oX1), (const float *)(d + oX2),
-                           (const float *)(d + oK1), (const float *)(d + oK2), (const float *)(d + oS1), (const float *)(d + oS2), d + oE1, d + oE2, o->dBaOut);
+                           (const float *)(d + oK1), (const float *)(d + oK2), (const float *)(d + oS1), (const float *)(d + oS2), d + oE1, d + oE2, o->ba.arena.stageOut.p);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(inlier_out, o->dBaOut, (size_t)total, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(inlier_out, o->ba.arena.stageOut.p, (size_t)total, hipMemcpyDeviceToHost));
     }
     for (int p = 0; p < n_pairs; p++) {                                       // :643-646
         int nIn = 0;
@@ -71,8 +71,8 @@ extern "C" int rumi_sim3_ransac(RumiOptimizer *o, int32_t n, const float *X3Dc1,
                  sK2 = al16(sK1 + T * 8), sS1 = al16(sK2 + T * 8), sS2 = al16(sS1 + T * 4), sE1 = al16(sS2 + T * 4), sE2 = al16(sE1 + T), inBytes = al16(sE2 + T);
     const size_t rT = 0, rN = al16(rT + H * 64), rC = al16(rN + H * 4), rI = al16(rC + H * NP * 4), outBytes = al16(rI + (inlier_out ? H * N : 0)),
                  rComp = outBytes, scratchEnd = al16(rComp + H * NP * 128);
-    if (inBytes > o->baStageCap || scratchEnd > o->baStageCap) { g_lastError = "rumi_sim3_ransac: more correspondences / hypotheses than the optimiser's arenas hold"; return RUMI_E_CAPACITY; }
-    uint8_t *h = o->hBa;
+    if (inBytes > o->ba.arena.stage.cap || scratchEnd > o->ba.arena.stage.cap) { g_lastError = "rumi_sim3_ransac: more correspondences / hypotheses than the optimiser's arenas hold"; return RUMI_E_CAPACITY; }
+    uint8_t *h = o->ba.arena.stage.h;
     std::memcpy(h + oX1, X3Dc1, N * 12); std::memcpy(h + oX2, X3Dc2, N * 12);
     float *t1 = reinterpret_cast<float *>(h + oT1), *t2 = reinterpret_cast<float *>(h + oT2);
     for (int i = 0; i < n; i++) {        // mvnMaxError1/2 are vector<size_t> upstream (Sim3Solver.h:77-78): 9.210 * sigma2 truncated, compared as float
@@ -95,8 +95,8 @@ extern "C" int rumi_sim3_ransac(RumiOptimizer *o, int32_t n, const float *X3Dc1,
             std::memcpy(h + sS1, score->sigma2_1, T * 4); std::memcpy(h + sS2, score->sigma2_2, T * 4); std::memcpy(h + sE1, score->edge1, T); std::memcpy(h + sE2, score->edge2, T);
         }
     }
-    HIP_TRY(hipMemcpyAsync(o->dBa, h, inBytes, hipMemcpyHostToDevice, nullptr));
-    uint8_t *d = o->dBa, *r = o->dBaOut;
+    HIP_TRY(hipMemcpyAsync(o->ba.arena.stage.d, h, inBytes, hipMemcpyHostToDevice, nullptr));
+    uint8_t *d = o->ba.arena.stage.d, *r = o->ba.arena.stageOut.p;
     RansacArgs A;
     A.n = n; A.nHyp = n_hyp; A.fixScale = fix_scale != 0;
     A.X1 = (const float *)(d + oX1); A.X2 = (const float *)(d + oX2); A.thr1 = (const float *)(d + oT1); A.thr2 = (const float *)(d + oT2);
@@ -109,13 +109,13 @@ extern "C" int rumi_sim3_ransac(RumiOptimizer *o, int32_t n, const float *X3Dc1,
     A.e1 = d + sE1; A.e2 = d + sE2; A.pairCnt = (int32_t *)(r + rC); A.comp = (double *)(r + rComp);
     hipLaunchKernelGGL(k_sim3_ransac, dim3(n_hyp), dim3(256), 0, nullptr, A);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(o->hBa, r, outBytes, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpyAsync(h, r, outBytes, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
-    std::memcpy(T12_out, o->hBa + rT, H * 64);
-    std::memcpy(n_inliers_out, o->hBa + rN, H * 4);
-    if (inlier_out) std::memcpy(inlier_out, o->hBa + rI, H * N);
+    std::memcpy(T12_out, h + rT, H * 64);
+    std::memcpy(n_inliers_out, h + rN, H * 4);
+    if (inlier_out) std::memcpy(inlier_out, h + rI, H * N);
     if (score) {                                                              // :643-662 per hypothesis
-        const int32_t *cnt = reinterpret_cast<const int32_t *>(o->hBa + rC);
+        const int32_t *cnt = reinterpret_cast<const int32_t *>(h + rC);
         std::vector<float> ratio(np);
         for (int hh = 0; hh < n_hyp; hh++) {
             for (int p = 0; p < np; p++) ratio[p] = (total > 0 && score->pair_denominator[p]) ? (float)cnt[(size_t)hh * np + p] / (float)score->pair_denominator[p] : 0.f;
@@ -145,8 +145,8 @@ extern "C" int rumi_optimize_sim3(RumiOptimizer *o, int32_t n, const int32_t *pa
     // result block: estimate, counters, status; scratch behind it
     const size_t rS = 0, rR = 64, rSt = 80, outBytes = al16(rSt + N), sC = outBytes, sX1 = al16(sC + NP * 30 * 64), sX2 = al16(sX1 + N * 8), sO1 = al16(sX2 + N * 8),
                  sO2 = al16(sO1 + N), scratchEnd = al16(sO2 + N);
-    if (inBytes > o->baStageCap || scratchEnd > o->baStageCap) { g_lastError = "rumi_optimize_sim3: more correspondences than the optimiser's arenas hold"; return RUMI_E_CAPACITY; }
-    uint8_t *h = o->hBa;
+    if (inBytes > o->ba.arena.stage.cap || scratchEnd > o->ba.arena.stage.cap) { g_lastError = "rumi_optimize_sim3: more correspondences than the optimiser's arenas hold"; return RUMI_E_CAPACITY; }
+    uint8_t *h = o->ba.arena.stage.h;
     std::memcpy(h + oS, S_io8, 64);
     if (world) { std::memcpy(h + oA, S_c1w, NP * 64); std::memcpy(h + oB, S_c2w, NP * 64); if (n) std::memcpy(h + oP, pair_of, N * 4); }
     std::memcpy(h + oK, K4_1, 16); std::memcpy(h + oK + 16, K4_2, 16);
@@ -156,8 +156,8 @@ extern "C" int rumi_optimize_sim3(RumiOptimizer *o, int32_t n, const int32_t *pa
         if (skip12) std::memcpy(h + oE1, skip12, N); else std::memset(h + oE1, 0, N);
         if (skip21) std::memcpy(h + oE2, skip21, N); else std::memset(h + oE2, 0, N);
     }
-    HIP_TRY(hipMemcpyAsync(o->dBa, h, inBytes, hipMemcpyHostToDevice, nullptr));
-    uint8_t *d = o->dBa, *r = o->dBaOut;
+    HIP_TRY(hipMemcpyAsync(o->ba.arena.stage.d, h, inBytes, hipMemcpyHostToDevice, nullptr));
+    uint8_t *d = o->ba.arena.stage.d, *r = o->ba.arena.stageOut.p;
     Sim3Args A;
     A.n = n; A.nPairs = n_pairs; A.world = world; A.fixScale = fix_scale != 0; A.robustFirst = robust_first_pass != 0; A.th2 = th2;
     A.pairOf = world ? (const int32_t *)(d + oP) : nullptr;
@@ -169,10 +169,10 @@ extern "C" int rumi_optimize_sim3(RumiOptimizer *o, int32_t n, const int32_t *pa
     A.comp = (double *)(r + sC); A.chi12 = (double *)(r + sX1); A.chi21 = (double *)(r + sX2); A.on12 = r + sO1; A.on21 = r + sO2;
     hipLaunchKernelGGL(k_sim3_opt, dim3(1), dim3(256), 0, nullptr, A);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(o->hBa, r, outBytes, hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(hipMemcpyAsync(h, r, outBytes, hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
-    std::memcpy(S_io8, o->hBa + rS, 64);
-    std::memcpy(result3, o->hBa + rR, 12);
-    if (n) std::memcpy(status_out, o->hBa + rSt, N);
+    std::memcpy(S_io8, h + rS, 64);
+    std::memcpy(result3, h + rR, 12);
+    if (n) std::memcpy(status_out, h + rSt, N);
     return RUMI_OK;
 }

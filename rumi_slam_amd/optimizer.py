@@ -13,9 +13,7 @@ class RumiSim3ScoreSet(C.Structure):
                                                                    "X1", "X2", "kp1", "kp2", "sigma2_1", "sigma2_2", "edge1", "edge2")]
 
 
-OPT_SYMBOLS = ["rumi_opt_create", "rumi_opt_destroy", "rumi_pose_optimization", "rumi_pose_optimization_batch", "rumi_local_ba", "rumi_merge_ba", "rumi_bundle_adjustment", "rumi_sim3_inliers",
-               "rumi_optimize_sim3", "rumi_sim3_ransac", "rumi_opt_stage_ms", "rumi_opt_set_profiling", "rumi_opt_kernel_ms",
-               "rumi_essential_graph", "rumi_sim3_correct_points"]
+OPT_SYMBOLS = capi.OPT_SYMBOLS          # one list: every entry of include/rumi_opt.h
 
 
 def _lib():
@@ -36,6 +34,7 @@ def _lib():
     L.rumi_opt_stage_ms.argtypes = [vp, vp]
     L.rumi_opt_set_profiling.argtypes = [vp, i32]
     L.rumi_opt_kernel_ms.argtypes = [vp, vp]
+    L.rumi_opt_footprint.argtypes = [vp, vp]
     L.rumi_sim3_ransac.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.rumi_optimize_sim3.argtypes = [vp, i32, vp, i32] + [vp] * 12 + [C.c_float, i32, i32, vp, vp, vp]
     L.rumi_essential_graph.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]
@@ -244,6 +243,12 @@ class Optimizer:
         ms = np.zeros(4, np.float32)
         capi.check(self._lib.rumi_opt_kernel_ms(self._h, capi.ptr(ms)))
         return dict(hpp=float(ms[0]), syrk=float(ms[1]), solve=float(ms[2]), trials=int(ms[3]))
+
+    def footprint(self):
+        """(device bytes, pinned host bytes) the handle owns right now: the sum over its buffers (include/rumi_opt.h states the expressions)."""
+        out = np.zeros(2, np.int64)
+        capi.check(self._lib.rumi_opt_footprint(self._h, capi.ptr(out)))
+        return int(out[0]), int(out[1])
 
     def stage_ms(self):
         ms = np.zeros(8, np.float32)

@@ -148,7 +148,7 @@ def test_kfdb_query_batches(tmp_path):
     voc.close()
 
 
-# ---- batched local BA: groupOut ----
+# ---- batched local BA: one batch arena, then four, then one again ----
 def test_local_ba_batch_windows():
     from rumi_slam_amd.optimizer import Optimizer
     probs = [ba_problem(seed=600, n_opt=3, n_fixed=2, n_points=100)] + [ba_problem(seed=601 + i, n_opt=8, n_fixed=2, n_points=300) for i in range(4)]
@@ -160,4 +160,112 @@ def test_local_ba_batch_windows():
         assert len(got) == len(s)
         for i, (a, b) in enumerate(zip(s, got)):
             assert all(np.array_equal(a[j], b[j]) for j in range(4)), (name, i)
+    o.close()
+
+
+# ---- the optimiser's parts (csrc/opt.hip: pose blocks, arenas, runners, worker contexts): what the handle owns, every route on one handle ----
+OPT_SIZES = dict(max_pose_edges=4096, max_pose_batch=4, max_kf=32, max_mp=512, max_edges=8192)
+
+
+def opt_parts(max_pose_edges, max_pose_batch, max_kf, max_mp, max_edges):
+    """(device, pinned) bytes of every part, transcribed from the allocation paragraph of include/rumi_opt.h."""
+    PE, PB, K, M, E = max_pose_edges, max_pose_batch, max_kf, max_mp, max_edges
+    r16, r256 = (lambda x: (x + 15) // 16 * 16), (lambda x: (x + 255) // 256 * 256)
+    NP = min(r16(6 * K + 1), 256)
+    S = 48 * E + 32 * M + 80 * K + 1024
+    runner = 15616 + 32 * r256(r16(r16(r16(64 * K) + 24 * M) + E) + 16)
+    parts = dict(pose=(34 * PE + 64 * PB + 532, 25 * PE + 64 * PB + 532),
+                 W=(233 * E + 232 * M + 672 * K + 2560, S + 64),
+                 H=(144 * E + (120 + 24 * NP) * M + 8 * NP * NP + 8 * (6 * K + 2) ** 2 + 96 * K + 64, 128),
+                 X=(26088000 + 16 * max(192, (M + 31) // 32) + 2 * r256(4 * M + 4) + 6 * r256(4 * E) + r256(8 * E) + r256(E) + r256(128 * (M // 16 + 2)), 24),
+                 R=(runner, runner))
+    return {k: np.array(v, np.int64) for k, v in parts.items()}
+
+
+def ba_window(**cfg):
+    b = ba_problem(**cfg)
+    return (b["kf_pose"], b["kf_fixed"], b["mp_pos"], b["e_mp"], b["e_kf"], b["e_obs"], b["e_w"], b["K"])
+
+
+def eligible_windows(n, seed=700):
+    """Windows the window-batched kernels take, within OPT_SIZES."""
+    return [ba_window(seed=seed + i, n_opt=3 + i % 6, n_fixed=2, n_points=100 + 10 * (i % 11)) for i in range(n)]
+
+
+def same_bytes(a, b):
+    flat = lambda r: [np.asarray(x).tobytes() for x in (r if isinstance(r, (tuple, list)) else [r])]
+    if isinstance(a, list):
+        return len(a) == len(b) and all(same_bytes(x, y) for x, y in zip(a, b))
+    return flat(a) == flat(b)
+
+
+def test_optimizer_footprint_follows_the_header():
+    from rumi_slam_amd.optimizer import Optimizer
+    p = opt_parts(**OPT_SIZES)
+    o = Optimizer(**OPT_SIZES)
+    created = np.array(o.footprint())
+    assert (created == p["pose"] + p["W"] + p["H"] + p["R"]).all(), (created, p)
+    twelve = eligible_windows(12)                                    # the first count that runs as three launch groups
+    o.LocalBundleAdjustmentBatch(twelve, 1)
+    batch = np.array(o.footprint())
+    assert (batch - created == 12 * (p["W"] + p["X"]) + 2 * p["R"]).all(), (batch - created, p)
+    o.LocalBundleAdjustmentBatch(twelve, 1)
+    assert (np.array(o.footprint()) == batch).all(), "the same batch again"
+    o.LocalBundleAdjustmentBatch(twelve[:3], 1)
+    assert (np.array(o.footprint()) == batch).all(), "a smaller batch"
+    o.LocalBundleAdjustmentBatch([ba_window(seed=720, n_opt=30, n_fixed=2, n_points=200)], 2)      # 30 optimised key-frames: ba_run's host loop
+    assert (np.array(o.footprint()) - batch == p["W"] + p["H"] + p["R"]).all(), "one worker context"
+    o.close()
+
+
+def test_optimizer_every_route_on_one_handle():
+    """Batch arenas, a worker context, the handle's own window with its batch extras, the pose blocks, Sim3 and the essential graph in turn on ONE
+    handle: no route may find a block that another one left in a state it cannot use.  Every result of a route with a fixed summation order is
+    held to the bytes a fresh handle returns for that input alone; the window of 30 key-frames (f64 atomics) to the oracle."""
+    from ba_scene import pose_problem
+    from rumi_slam_amd.optimizer import Optimizer
+    from sim3_scene import sim3_pair_problem
+    from test_optimizer_gpu import _check_local_ba
+    nine, two, big = eligible_windows(9, 730), eligible_windows(2, 750), ba_window(seed=760, n_opt=30, n_fixed=2, n_points=200)
+    single, merge, gba = eligible_windows(3, 770)
+    poses = [pose_problem(40 + i, 150 + 37 * i, 0.15) for i in range(3)]
+    start = np.cumsum([0] + [len(q["inv_sigma2"]) for q in poses]).astype(np.int32)
+    pose_args = (start, np.concatenate([q["Xw"] for q in poses]), np.concatenate([q["obs"] for q in poses]), np.concatenate([q["inv_sigma2"] for q in poses]),
+                 poses[0]["K"], np.stack([q["T0"] for q in poses]))
+    s = sim3_pair_problem(seed=6, n=60)
+    sim3_args = (s["S0"], s["P1c"], s["P2c"], s["obs1"], s["obs2"], s["w1"], s["w2"], s["K"], s["K"])
+    eg, eg_it = es.scene("two_free"), es.SCENES["two_free"]["n_it"]
+    routes = [("batch of 9", lambda h: h.LocalBundleAdjustmentBatch(nine, 1)),
+              ("mixed batch", lambda h: h.LocalBundleAdjustmentBatch(two + [big], 2)),
+              ("local BA", lambda h: h.LocalBundleAdjustment(*single)),
+              ("merge BA", lambda h: h.MergeBundleAdjustment(*merge)),
+              ("global BA", lambda h: h.BundleAdjustment(*gba)),
+              ("pose batch", lambda h: h.PoseOptimizationBatch(*pose_args)),
+              ("Sim3", lambda h: h.OptimizeSim3(*sim3_args)),
+              ("essential graph", lambda h: h.essential_graph(*eg.args(), n_iterations=eg_it)),
+              ("batch of 9 again", lambda h: h.LocalBundleAdjustmentBatch(nine, 1))]
+    o = Optimizer(**OPT_SIZES)
+    for name, call in routes:
+        got = call(o)
+        fresh = Optimizer(**OPT_SIZES)
+        want = call(fresh)
+        fresh.close()
+        if name == "mixed batch":
+            _check_local_ba(dict(kf_pose=big[0], kf_fixed=big[1]), got[2], O.local_ba(*big))
+            got, want = got[:2], want[:2]
+        assert same_bytes(got, want), name
+    o.close()
+
+
+def test_optimizer_destroyed_after_a_batch_and_created_again():
+    from rumi_slam_amd.optimizer import Optimizer
+    w = eligible_windows(1, 780)[0]
+    fresh = Optimizer(**OPT_SIZES)
+    want = fresh.LocalBundleAdjustment(*w)
+    fresh.close()
+    o = Optimizer(**OPT_SIZES)
+    o.LocalBundleAdjustmentBatch(eligible_windows(12, 790) + [ba_window(seed=760, n_opt=30, n_fixed=2, n_points=200)], 2)   # arenas, runners and a worker context to release
+    o.close()
+    o = Optimizer(**OPT_SIZES)
+    assert same_bytes(o.LocalBundleAdjustment(*w), want)
     o.close()
