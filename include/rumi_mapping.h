@@ -157,6 +157,43 @@ int rumi_search_in_neighbors_resident(RumiMatcher *m, RumiCovis *c, int32_t cur_
 /* The last call on this matcher, in ms: validation + table | upload, kernels, download | write-out. */
 int rumi_search_in_neighbors_stage_ms(const RumiMatcher *m, float *out3);
 
+/* ---- The searches of LoopClosing::SearchAndFuse (R/lib_src/LoopClosing.cc:1996-2065) for every corrected key-frame in one call, over
+ * key-frames and points resident in a covisibility store.  The member calls ORBmatcher::Fuse(pKF, Scw, vpPoints, 4, vpReplacePoint)
+ * (ORBmatcher.cc:1182-1291) once per key-frame: the search of a (key-frame, point) pair reads the point's position, normal, distance range
+ * and descriptor and the key-frame's pose, key-points, descriptors, scale table and bounds; it has no reprojection gate.  AddObservation /
+ * AddMapPoint happen inside Fuse, Replace after each key-frame (:2017-2023).  The gates (isBad, spAlreadyFound) only ever close during the
+ * member, so the device answers every pair from the store as it stands and the caller replays the mutations key-frame by key-frame,
+ * re-evaluating each gate and reading GetMapPoint(bestIdx) live at its turn.
+ * WHAT THE CALLER MUST DO BESIDES: Replace ends with ComputeDistinctiveDescriptors() on the survivor, here always the loop point
+ * (MapPoint.cc:321).  Compare its GetDescriptor() before and after; a loop point whose descriptor changed no longer has valid answers for the
+ * key-frames that follow: search it again for each of them (rumi_fuse_candidates, check_reprojection = 0, live descriptor) before its turn.
+ * facade/LoopClosingStep.h SearchAndFuseResident does all of this.  Monocular.
+ *
+ * kfs[k]: Tcw7 and Ow as ORBmatcher.cc:1190-1191 derives them from Scw -- SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()) and its
+ * inverse's translation -- formed by the caller; no Sim3 arithmetic crosses this boundary.  bounds and log_scale_factor: the key-frame's own.
+ * For key-frame k and list entry i the best feature is best_idx of rumi_fuse_candidates(..., check_reprojection = 0) on that key-frame's
+ * resident features and K4, that pose, and the stored attributes of point_ids[i], byte for byte; -1 where point_ids[i] < 0, where the point is
+ * bad in the store, where its observer row lists kf_slots[k], or where the search finds nothing within TH_LOW.  Duplicate ids are answered
+ * independently.
+ * hits [hit_cap]: only the pairs whose best feature is >= 0, in ascending (kf, point) order; kf and point index the call's lists, feature is
+ * the best index, occupant the id in entry `feature` of that key-frame's map-point row at the call or -1 (a preview of GetMapPoint(bestIdx),
+ * :1278; the caller re-reads the live object).  per_kf [n_kfs]: hits per key-frame; *n_hits their total.  hit_cap < *n_hits: RUMI_E_CAPACITY,
+ * *n_hits and per_kf valid, the first hit_cap hits written.  The dense answer (n_kfs * n_points words) never leaves the device.
+ * Host to device per call: the store's staged edits and staged features, n_kfs records of 60 bytes and 4 * n_points bytes of ids.  A query:
+ * the store is not changed.  Integer atomics only: two calls on the same state return the same bytes.
+ * RUMI_E_INVALID, nothing written: a missing argument; th <= 0; a pose, centre, bound or scale factor that is not finite, or empty bounds; a
+ * slot that is not live or holds no features; a slot named twice; a slot whose feature count differs from the length of its map-point row;
+ * matcher and store on different devices; an id at or above the store's point capacity; a list entry that would be searched and whose point
+ * has no attributes (found on the device; the message names how many entries).  RUMI_E_CAPACITY, nothing written: n_kfs >
+ * RUMI_FUSE_MAX_TARGETS; a key-frame above the matcher's max_features; n_kfs * n_points >= 2^31 (more pairs than a work item addresses).
+ * n_kfs == 0 or n_points == 0: RUMI_OK, *n_hits = 0 (per_kf zeroed), no device call. */
+typedef struct RumiFuseHit { int32_t kf, point, feature, occupant; } RumiFuseHit;
+int rumi_search_and_fuse_resident(RumiMatcher *m, RumiCovis *c, const int32_t *kf_slots, const RumiFuseKF *kfs, int32_t n_kfs,
+                                  const int32_t *point_ids, int32_t n_points, float th, RumiFuseHit *hits, int32_t hit_cap, int32_t *n_hits,
+                                  int32_t *per_kf /* [n_kfs] */);
+/* The last call on this matcher, in ms: validation + table | upload, kernels, download | write-out. */
+int rumi_search_and_fuse_stage_ms(const RumiMatcher *m, float *out3);
+
 /* ---- MapPoint::ComputeDistinctiveDescriptors (R/lib_src/MapPoint.cc:353-427) and MapPoint::UpdateNormalAndDepth (:450-518) for a batch of
  * points.  Neither member reads another MapPoint: a point's result depends on its own observation list, its position and reference
  * key-frame, and the observing key-frames' descriptors, camera centres, bad flags and scale tables.  So the per-point calls a map-changing

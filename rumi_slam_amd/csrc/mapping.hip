@@ -9,7 +9,8 @@
 //   replay       for k = 0, 1, ...: baseline skip; the pairs whose i1 is still free; the rotation histogram over exactly those; survivors
 //                with gate == 0 create a point and take i1 out.
 //
-// The searches of LocalMapping::SearchInNeighbors over the same store: search_in_neighbors.inc, included at the end of this file.
+// The searches of LocalMapping::SearchInNeighbors over the same store: search_in_neighbors.inc, included at the end of this file; those of
+// LoopClosing::SearchAndFuse: search_and_fuse.inc, after it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -468,6 +469,8 @@ __global__ __launch_bounds__(256) void k_newpts_gather(const ResKF *__restrict__
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
 struct SinState;                                             // the blocks of rumi_search_in_neighbors_resident (search_in_neighbors.inc)
 static void sin_destroy(SinState *s);
+struct SafState;                                             // the blocks of rumi_search_and_fuse_resident (search_and_fuse.inc)
+static void saf_destroy(SafState *s);
 
 struct NewPtsState {
     MirrorBuf<uint8_t> blk, res;                             // the upload block; the result block, a NewPtsResult and its points
@@ -476,12 +479,14 @@ struct NewPtsState {
     int lastNeigh = 0, lastN1 = 0, lastOri = 0;              // the last block call, whose device state rumi_hook_newpts_matches replays
     StageClock clock;
     float stageMs[3] = {0.f, 0.f, 0.f};
-    SinState *sin = nullptr;                                 // with the first SearchInNeighbors call
+    SinState *sin = nullptr;                                 // with the first SearchInNeighbors or SearchAndFuse call (the stamped tables)
+    SafState *saf = nullptr;                                 // with the first SearchAndFuse call
 };
 
 static void newpts_destroy(void *p) {                        // rumi_match_destroy has made the matcher's device current
     NewPtsState *s = static_cast<NewPtsState *>(p);
     if (s->sin) sin_destroy(s->sin);
+    if (s->saf) saf_destroy(s->saf);
     delete s;
 }
 
@@ -720,3 +725,4 @@ extern "C" int rumi_hook_newpts_matches(RumiMatcher *m, int32_t n_neigh, int32_t
 }
 
 #include "search_in_neighbors.inc"
+#include "search_and_fuse.inc"

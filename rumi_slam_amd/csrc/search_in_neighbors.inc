@@ -185,10 +185,70 @@ __global__ __launch_bounds__(256) void k_sin_fwd_gate(SinArgs a) {
     sin_push(a, q.valid != 0, q, (uint32_t)at);
 }
 
-// ORBmatcher.cc:1114-1161 for the pairs of the work list, kSinLanes lanes each: the candidates of Frame::GetFeaturesInArea in its order (cell
-// column, cell row, ascending feature index), the level window [level - 1, level], the monocular reprojection gate (5.99) and the strict
-// `dist < bestDist`: the key (distance << 16 | place in the walk) has one minimum, the earliest of the nearest.  The tests are those of
-// candidates_walk (match_candidates.inc, MODE_FUSE), expression for expression.
+// The window walk of one work item, kSinLanes lanes each: the candidates of Frame::GetFeaturesInArea (Frame.cc:695-750) in its order (cell
+// column, cell row, ascending feature index), the level window [level - 1, level] and the strict `dist < bestDist`: the key
+// (distance << 16 | place in the walk) has one minimum, the earliest of the nearest.  REPROJ: the monocular reprojection gate (5.99) of
+// ORBmatcher.cc:1138-1145, which Fuse(KF, MapPoints) has and Fuse(KF, Scw, MapPoints) (:1258-1274, search_and_fuse.inc) has not.  The tests are
+// those of candidates_walk (match_candidates.inc, MODE_FUSE), expression for expression.  One body for k_sin_search and k_saf_search.
+template <bool REPROJ>
+__device__ __forceinline__ void sin_walk(const SinArgs &a, int k, int p, const uint4 &item, int sub, uint32_t &bestKey, int &bestIdx) {
+    const SinKF &F = a.tab[k];
+    const uint8_t *R8 = a.feat + F.block;
+    const CovisFeatRec *R = reinterpret_cast<const CovisFeatRec *>(R8);
+    const RumiKeyPoint *keys = reinterpret_cast<const RumiKeyPoint *>(R8 + R->keys);
+    const uint8_t *desc = R8 + R->desc;
+    const float *scale = reinterpret_cast<const float *>(R8 + R->scale);
+    const uint16_t *S = a.sorted + F.sortedOff;
+    const int32_t *CS = a.cellStart + (size_t)k * (kGridCells + 1);
+    const uint4 q0 = ld16_dword(a.attr + (size_t)p * kCovisAttrWords + 8), q1 = ld16_dword(a.attr + (size_t)p * kCovisAttrWords + 12);
+    const float u = __uint_as_float(item.x), v = __uint_as_float(item.y);
+    const int maxLevel = (int)item.w, minLevel = maxLevel - 1;
+    const float r = a.th * scale[maxLevel];
+    // Frame::GetFeaturesInArea (Frame.cc:695-750)
+    const int nMinCellX = max(0, (int)floorf((u - F.bounds[0] - r) * F.wInv));
+    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((u - F.bounds[0] + r) * F.wInv));
+    const int nMinCellY = max(0, (int)floorf((v - F.bounds[1] - r) * F.hInv));
+    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((v - F.bounds[1] + r) * F.hInv));
+    if (nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0 && nMaxCellY >= nMinCellY) {
+        int order = 0;
+        for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
+            const int p0 = CS[ix * kGridRows + nMinCellY], p1 = CS[ix * kGridRows + nMaxCellY + 1];
+            for (int base = p0; base < p1; base += kSinLanes, order += kSinLanes) {
+                const int c = base + sub;
+                if (c >= p1) continue;
+                const int idx = S[c];
+                const RumiKeyPoint kp = keys[idx];
+                const int oct = kp.octave;
+                if (oct < minLevel || oct > maxLevel) continue;
+                const float dx = kp.x - u, dy = kp.y - v;
+                if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
+                if (REPROJ) {
+                    const float ex = u - kp.x, ey = v - kp.y;           // mono reprojection gate, ORBmatcher.cc:1138-1145
+                    const float e2 = ex * ex + ey * ey;
+                    const float s2 = scale[oct] * scale[oct];           // mvLevelSigma2; mvInvLevelSigma2 = 1.0f / it
+                    if ((double)(e2 * (1.0f / s2)) > 5.99) continue;
+                }
+                const uint4 d0 = ld16_dword(desc + (size_t)idx * 32), d1 = ld16_dword(desc + (size_t)idx * 32 + 16);
+                const int d = __popc(q0.x ^ d0.x) + __popc(q0.y ^ d0.y) + __popc(q0.z ^ d0.z) + __popc(q0.w ^ d0.w) +
+                              __popc(q1.x ^ d1.x) + __popc(q1.y ^ d1.y) + __popc(q1.z ^ d1.z) + __popc(q1.w ^ d1.w);
+                const uint32_t key = ((uint32_t)d << 16) | (uint32_t)(order + sub);
+                if (key < bestKey) { bestKey = key; bestIdx = idx; }
+            }
+        }
+    }
+}
+
+// The minimum of a group's kSinLanes keys; all 64 lanes are here, a group's lanes exchange among themselves only.
+__device__ __forceinline__ void sin_group_min(uint32_t &bestKey, int &bestIdx) {
+#pragma unroll
+    for (int m = 1; m < kSinLanes; m <<= 1) {
+        const uint32_t ok = (uint32_t)__shfl_xor((int)bestKey, m);
+        const int oi = __shfl_xor(bestIdx, m);
+        if (ok < bestKey) { bestKey = ok; bestIdx = oi; }
+    }
+}
+
+// ORBmatcher.cc:1114-1161 for the pairs of the work list: sin_walk with the reprojection gate.
 __global__ __launch_bounds__(256) void k_sin_search(SinArgs a) {
     const int sub = threadIdx.x & (kSinLanes - 1), perBlock = 256 / kSinLanes;
     const int count = a.head[SIN_WORK];
@@ -202,55 +262,9 @@ __global__ __launch_bounds__(256) void k_sin_search(SinArgs a) {
             int k, p;
             if (item.z & kSinRevBit) { const int j = (int)(item.z & ~kSinRevBit); k = 0; p = a.revPoint[j]; out = a.revBest + j; }
             else { const int t = (int)(item.z / (uint32_t)a.nCur), i = (int)(item.z - (uint32_t)t * (uint32_t)a.nCur); k = 1 + t; p = a.rows[a.tab[0].mpOff + i]; out = a.fwd + item.z; }
-            const SinKF &F = a.tab[k];
-            const uint8_t *R8 = a.feat + F.block;
-            const CovisFeatRec *R = reinterpret_cast<const CovisFeatRec *>(R8);
-            const RumiKeyPoint *keys = reinterpret_cast<const RumiKeyPoint *>(R8 + R->keys);
-            const uint8_t *desc = R8 + R->desc;
-            const float *scale = reinterpret_cast<const float *>(R8 + R->scale);
-            const uint16_t *S = a.sorted + F.sortedOff;
-            const int32_t *CS = a.cellStart + (size_t)k * (kGridCells + 1);
-            const uint4 q0 = ld16_dword(a.attr + (size_t)p * kCovisAttrWords + 8), q1 = ld16_dword(a.attr + (size_t)p * kCovisAttrWords + 12);
-            const float u = __uint_as_float(item.x), v = __uint_as_float(item.y);
-            const int maxLevel = (int)item.w, minLevel = maxLevel - 1;
-            const float r = a.th * scale[maxLevel];
-            // Frame::GetFeaturesInArea (Frame.cc:695-750)
-            const int nMinCellX = max(0, (int)floorf((u - F.bounds[0] - r) * F.wInv));
-            const int nMaxCellX = min(kGridCols - 1, (int)ceilf((u - F.bounds[0] + r) * F.wInv));
-            const int nMinCellY = max(0, (int)floorf((v - F.bounds[1] - r) * F.hInv));
-            const int nMaxCellY = min(kGridRows - 1, (int)ceilf((v - F.bounds[1] + r) * F.hInv));
-            if (nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0 && nMaxCellY >= nMinCellY) {
-                int order = 0;
-                for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-                    const int p0 = CS[ix * kGridRows + nMinCellY], p1 = CS[ix * kGridRows + nMaxCellY + 1];
-                    for (int base = p0; base < p1; base += kSinLanes, order += kSinLanes) {
-                        const int c = base + sub;
-                        if (c >= p1) continue;
-                        const int idx = S[c];
-                        const RumiKeyPoint kp = keys[idx];
-                        const int oct = kp.octave;
-                        if (oct < minLevel || oct > maxLevel) continue;
-                        const float dx = kp.x - u, dy = kp.y - v;
-                        if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
-                        const float ex = u - kp.x, ey = v - kp.y;           // mono reprojection gate, ORBmatcher.cc:1138-1145
-                        const float e2 = ex * ex + ey * ey;
-                        const float s2 = scale[oct] * scale[oct];           // mvLevelSigma2; mvInvLevelSigma2 = 1.0f / it
-                        if ((double)(e2 * (1.0f / s2)) > 5.99) continue;
-                        const uint4 d0 = ld16_dword(desc + (size_t)idx * 32), d1 = ld16_dword(desc + (size_t)idx * 32 + 16);
-                        const int d = __popc(q0.x ^ d0.x) + __popc(q0.y ^ d0.y) + __popc(q0.z ^ d0.z) + __popc(q0.w ^ d0.w) +
-                                      __popc(q1.x ^ d1.x) + __popc(q1.y ^ d1.y) + __popc(q1.z ^ d1.z) + __popc(q1.w ^ d1.w);
-                        const uint32_t key = ((uint32_t)d << 16) | (uint32_t)(order + sub);
-                        if (key < bestKey) { bestKey = key; bestIdx = idx; }
-                    }
-                }
-            }
+            sin_walk<true>(a, k, p, item, sub, bestKey, bestIdx);
         }
-#pragma unroll
-        for (int m = 1; m < kSinLanes; m <<= 1) {            // all 64 lanes are here; a group's lanes exchange among themselves only
-            const uint32_t ok = (uint32_t)__shfl_xor((int)bestKey, m);
-            const int oi = __shfl_xor(bestIdx, m);
-            if (ok < bestKey) { bestKey = ok; bestIdx = oi; }
-        }
+        sin_group_min(bestKey, bestIdx);
         if (out && sub == 0) *out = (int)(bestKey >> 16) <= RUMI_TH_LOW ? bestIdx : -1;      // :1161; no candidate: 0xFFFF
     }
 }
@@ -275,6 +289,21 @@ static bool sin_finite(const RumiFuseKF &k) {
     const float *f = reinterpret_cast<const float *>(&k);
     for (size_t i = 0; i < sizeof(RumiFuseKF) / 4; i++) if (!std::isfinite(f[i])) return false;
     return true;
+}
+
+// The two stamped tables: a value of another epoch reads as "not of this call"; a new or outgrown table, or a wrapped epoch, starts from zero.
+// Shared with rumi_search_and_fuse_resident (search_and_fuse.inc), whose calls take their epochs from the same counter.
+static int sin_next_epoch(rumi::SinState *s, const rumi::CovisFeatureView &fv) {
+    int rc;
+    const bool fresh = (size_t)fv.maxKf > s->slotTag.cap || (size_t)fv.maxPoints > s->claim.cap || s->epoch >= (1u << 22) - 1;
+    if ((rc = s->slotTag.reserve((size_t)fv.maxKf, (size_t)fv.maxKf)) != RUMI_OK || (rc = s->claim.reserve((size_t)fv.maxPoints, (size_t)fv.maxPoints)) != RUMI_OK) return rc;
+    if (fresh) {
+        HIP_TRY(hipMemsetAsync(s->slotTag.p, 0, s->slotTag.cap * sizeof(uint32_t), nullptr));
+        HIP_TRY(hipMemsetAsync(s->claim.p, 0, s->claim.cap * sizeof(unsigned long long), nullptr));
+        s->epoch = 0;
+    }
+    s->epoch++;
+    return RUMI_OK;
 }
 
 extern "C" int rumi_search_in_neighbors_resident(RumiMatcher *m, RumiCovis *c, int32_t cur_slot, const RumiFuseKF *cur, const int32_t *target_slots,
@@ -336,15 +365,7 @@ extern "C" int rumi_search_in_neighbors_resident(RumiMatcher *m, RumiCovis *c, i
     CovisFeatureView fv;
     s->clock.mark();
     if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
-    // the two stamped tables: a value of another epoch reads as "not of this call"; a new or outgrown table, or a wrapped epoch, starts from zero
-    const bool fresh = (size_t)fv.maxKf > s->slotTag.cap || (size_t)fv.maxPoints > s->claim.cap || s->epoch >= (1u << 22) - 1;
-    if ((rc = s->slotTag.reserve((size_t)fv.maxKf, (size_t)fv.maxKf)) != RUMI_OK || (rc = s->claim.reserve((size_t)fv.maxPoints, (size_t)fv.maxPoints)) != RUMI_OK) return rc;
-    if (fresh) {
-        HIP_TRY(hipMemsetAsync(s->slotTag.p, 0, s->slotTag.cap * sizeof(uint32_t), nullptr));
-        HIP_TRY(hipMemsetAsync(s->claim.p, 0, s->claim.cap * sizeof(unsigned long long), nullptr));
-        s->epoch = 0;
-    }
-    s->epoch++;
+    if ((rc = sin_next_epoch(s, fv)) != RUMI_OK) return rc;
 
     SinKF *tab = reinterpret_cast<SinKF *>(s->tab.h);
     int32_t sortedOff = 0;

@@ -182,6 +182,8 @@ template <class KeyFrameT, class MapPointT> class CovisibilityGraph {
     int PointCount() const { return (int)pts_.size(); }
     KeyFrameT *KeyFrameAt(int slot) const { return kfs_[slot]; }
     MapPointT *PointAt(int id) const { return pts_[id]; }
+    // has the store seen the point?  (IdOf below stages a point it has not)
+    bool HasPoint(MapPointT *pMP) const { return id_.count(pMP) > 0; }
     // the id of a point, staging it first when the store has not seen it (-1 on failure)
     int IdOf(MapPointT *pMP) {
         auto it = id_.find(pMP);

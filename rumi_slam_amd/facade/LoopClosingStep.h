@@ -7,6 +7,12 @@
 //
 // Templated on the key-frame, map-point and matcher types, so that it instantiates against the reference's classes and against the stand-ins of
 // tests/cpp.  Mono key-frames only.
+//
+// With RUMI_HAVE_SOPHUS, LoopClosing::SearchAndFuse (R/lib_src/LoopClosing.cc:1996-2065) over a CovisibilityGraph that holds the map becomes
+//     rumi::LoopClosingStep step;                                    // = ORBmatcher matcher(0.8)
+//     step.SearchAndFuseResident(graph, poses, vpMapPoints);         // poses: (KeyFrame *, Sophus::Sim3f) in CorrectedPosesMap's order
+//     step.SearchAndFuseResident(graph, vConectedKFs, vpMapPoints);  // the overload that searches under GetPose(), scale 1
+// (at the end of this header).
 #pragma once
 #include <cstdint>
 #include <set>
@@ -171,3 +177,181 @@ int CommonRegionsBoWStage(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> 
 }
 
 }  // namespace rumi_facade
+
+#ifdef RUMI_HAVE_SOPHUS
+#include <cstring>
+#include <mutex>
+#include <type_traits>
+#include <utility>
+
+#include "ORBmatcher.h"
+#include "rumi_mapping.h"
+
+namespace RUMI_FACADE_NAMESPACE {
+
+// LoopClosing::SearchAndFuse (R/lib_src/LoopClosing.cc:1996-2028 and :2030-2065) over a CovisibilityGraph that holds the map: graph.FlushDirty();
+// ONE device call answers every (key-frame, loop point) search from the store as it stands (rumi_search_and_fuse_resident, include/rumi_mapping.h);
+// then the reference's own objects replay :2003-2026 key-frame by key-frame.  At a key-frame's turn spAlreadyFound is taken, isBad() is asked
+// per point, GetMapPoint(bestIdx) is read live (a point added earlier in the same key-frame is the occupant), AddObservation / AddMapPoint
+// happen at once, vpReplacePoints is filled and the Replace loop runs after the key-frame under the map's update mutex.
+// Replace ends with ComputeDistinctiveDescriptors() on the survivor, always the loop point here (MapPoint.cc:321): a loop point whose
+// GetDescriptor() a Replace changed is searched again, on its live descriptor, for every key-frame that follows, before its turn (one small
+// rumi_fuse_candidates call per such key-frame, without the reprojection gate; *nSearchedAgain counts the pairs).  DESIGN.md 4v has the
+// argument why nothing else the device read can change.  The touched key-frames and points are staged again (Sync, MarkDirty), so the graph
+// is current when the member returns.
+// Returns the key-frames' nFused together, or -1 with a report and nothing mutated: NLeft != -1 on any key-frame, a key-frame or point the
+// graph has never seen, a key-frame without resident features or a searched point without attributes, more key-frames than
+// RUMI_FUSE_MAX_TARGETS, a failed device call.  The caller keeps the reference's member for those.  (A second search that fails ends the
+// member with -1 after the key-frames replayed so far, which stay, staged.)
+class LoopClosingStep : public ORBmatcher {
+public:
+    LoopClosingStep() : ORBmatcher(0.8f, true) {}            // `ORBmatcher matcher(0.8)`, LoopClosing.cc:1997
+
+    // kfs: an ordered range of (KeyFrameT *, Sophus::Sim3f) -- CorrectedPosesMap with its g2o::Sim3 through Converter::toSophus, in the order the
+    // map iterates (:2003-2009) -- or a std::vector<KeyFrameT *>, each searched under `Sim3f(GetPose().unit_quaternion(), GetPose().translation())`
+    // with scale 1 (:2041-2043).  Sim3T is Sophus::Sim3f; a parameter so that tests/cpp's stand-in, which lacks that constructor, can stand in.
+    template <class Sim3T = Sophus::Sim3f, class GraphT, class RangeT, class MapPointT>
+    int SearchAndFuseResident(GraphT &graph, const RangeT &kfs, std::vector<MapPointT *> &vpMapPoints, int *nSearchedAgain = nullptr) {
+        return saf_dispatch<Sim3T>(graph, kfs, vpMapPoints, nSearchedAgain, typename std::is_pointer<typename RangeT::value_type>::type());
+    }
+
+protected:
+    template <class Sim3T, class GraphT, class KeyFrameT, class MapPointT>
+    int saf_dispatch(GraphT &graph, const std::vector<KeyFrameT *> &vConectedKFs, std::vector<MapPointT *> &vpMapPoints, int *nSearchedAgain, std::true_type) {
+        std::vector<std::pair<KeyFrameT *, Sim3T>> poses;
+        for (KeyFrameT *pKF : vConectedKFs) {
+            const Sophus::SE3f Tcw = pKF->GetPose();
+            Sim3T Scw(Tcw.unit_quaternion(), Tcw.translation());
+            Scw.setScale(1.f);
+            poses.emplace_back(pKF, Scw);
+        }
+        return saf_dispatch<Sim3T>(graph, poses, vpMapPoints, nSearchedAgain, std::false_type());
+    }
+
+    template <class Sim3T, class GraphT, class PosesT, class MapPointT>
+    int saf_dispatch(GraphT &graph, const PosesT &poses, std::vector<MapPointT *> &vpMapPoints, int *nSearchedAgain, std::false_type) {
+        using KeyFrameT = typename std::remove_pointer<typename std::decay<decltype(poses.begin()->first)>::type>::type;
+        static const char *where = "LoopClosingStep::SearchAndFuseResident";
+        if (nSearchedAgain) *nSearchedAgain = 0;
+        if (!graph.ok()) { rumi_facade::report(where, RUMI_E_INVALID, "no store; nothing was fused"); return -1; }
+        // ---- 1. what can refuse, before anything is touched
+        std::vector<KeyFrameT *> vpKFs;
+        std::vector<int32_t> slots;
+        std::vector<RumiFuseKF> rec;
+        for (const auto &kv : poses) {
+            KeyFrameT *pKF = kv.first;
+            if (pKF->NLeft != -1) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a key-frame with NLeft != -1: only the monocular Fuse is built; nothing was fused");
+                return -1;
+            }
+            if (graph.SlotOf(pKF) < 0 || !graph.HasFeatures(pKF)) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a key-frame the graph has never seen or without resident features (graph.Sync, graph.SyncFeatures); nothing was uploaded, nothing was fused");
+                return -1;
+            }
+            auto Scw = kv.second;                                                   // ORBmatcher.cc:1190-1191, as Fuse (ORBmatcher.h) forms them
+            const Sophus::SE3f Tcw = Sophus::SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale());
+            const Eigen::Vector3f Ow = Tcw.inverse().translation();
+            const auto q = Tcw.unit_quaternion();
+            RumiFuseKF r;
+            r.Tcw7[0] = q.x(); r.Tcw7[1] = q.y(); r.Tcw7[2] = q.z(); r.Tcw7[3] = q.w();
+            for (int c = 0; c < 3; c++) { r.Tcw7[4 + c] = Tcw.translation()(c); r.Ow[c] = Ow(c); }
+            r.bounds[0] = pKF->mnMinX; r.bounds[1] = pKF->mnMinY; r.bounds[2] = pKF->mnMaxX; r.bounds[3] = pKF->mnMaxY;
+            r.log_scale_factor = pKF->mfLogScaleFactor;
+            vpKFs.push_back(pKF); slots.push_back(graph.SlotOf(pKF)); rec.push_back(r);
+        }
+        const int nK = (int)vpKFs.size(), nP = (int)vpMapPoints.size();
+        if (nK > RUMI_FUSE_MAX_TARGETS) { rumi_facade::report(where, RUMI_E_INVALID, "more key-frames than RUMI_FUSE_MAX_TARGETS; nothing was fused"); return -1; }
+        std::vector<int32_t> ids((size_t)nP + 1, -1);
+        for (int i = 0; i < nP; i++) {
+            MapPointT *pMP = vpMapPoints[i];
+            if (!pMP) continue;
+            if (!graph.HasPoint(pMP)) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a loop point the graph has never seen (graph.Sync, graph.SyncAttributes); nothing was uploaded, nothing was fused");
+                return -1;
+            }
+            ids[i] = graph.IdOf(pMP);
+        }
+        if (nK == 0 || nP == 0) return 0;
+        // ---- 2. one call
+        if (graph.FlushDirty() != RUMI_OK) return -1;
+        const float th = 4.0f;                                                      // :2012, :2049
+        std::vector<RumiFuseHit> hits((size_t)(nP > 1024 ? nP : 1024));
+        std::vector<int32_t> per(nK);
+        int32_t nHits = 0;
+        if (!arena()) return -1;                                                    // reported by arena()
+        auto grow = [&]() {                                                         // a hit list that was too short is not the arena's fault
+            if ((size_t)nHits > hits.size()) { hits.resize((size_t)nHits); return true; }
+            return ORBmatcher::grow_arena();
+        };
+        if (RUMI_GUARDED("LoopClosingStep / rumi_search_and_fuse_resident", grow,
+                         rumi_search_and_fuse_resident(arena(), graph.handle(), slots.data(), rec.data(), nK, ids.data(), nP, th, hits.data(), (int32_t)hits.size(),
+                                                       &nHits, per.data())) != RUMI_OK)
+            return -1;
+        // ---- 3. the replay of :2003-2026
+        std::set<KeyFrameT *> touchedKFs;
+        std::set<MapPointT *> touchedPts, changed;
+        auto stage = [&]() {
+            for (KeyFrameT *k : touchedKFs) graph.Sync(k);
+            for (MapPointT *p : touchedPts) graph.Sync(p);
+            for (MapPointT *p : changed) graph.MarkDirty(p);
+        };
+        int nFused = 0;
+        size_t h0 = 0;
+        for (int kk = 0; kk < nK; kk++) {
+            KeyFrameT *pKF = vpKFs[kk];
+            std::vector<int32_t> best((size_t)nP, -1);
+            for (size_t h = h0; h < h0 + (size_t)per[kk]; h++) best[hits[h].point] = hits[h].feature;
+            h0 += (size_t)per[kk];
+            const auto spAlreadyFound = pKF->GetMapPoints();                        // ORBmatcher.cc:1194, at the key-frame's turn
+            if (!changed.empty()) {                                                 // loop points whose descriptor a Replace changed: their answers are stale
+                std::vector<int> at;
+                std::vector<MapPointT *> again;
+                for (int i = 0; i < nP; i++) {
+                    MapPointT *p = vpMapPoints[i];
+                    if (p && changed.count(p) && !p->isBad() && !spAlreadyFound.count(p)) { at.push_back(i); again.push_back(p); }
+                }
+                if (!again.empty()) {
+                    std::vector<int32_t> sub;
+                    if (!fuse_search(pKF, rec[kk].Tcw7, rec[kk].Ow, again, [](MapPointT *) { return false; }, th, 0, sub)) { stage(); return -1; }
+                    for (size_t j = 0; j < at.size(); j++) best[at[j]] = sub[j];
+                    if (nSearchedAgain) *nSearchedAgain += (int)at.size();
+                }
+            }
+            std::vector<MapPointT *> vpReplacePoints((size_t)nP, static_cast<MapPointT *>(nullptr));
+            for (int iMP = 0; iMP < nP; iMP++) {                                    // ORBmatcher.cc:1201-1288
+                MapPointT *pMP = vpMapPoints[iMP];
+                if (!pMP) continue;
+                if (pMP->isBad() || spAlreadyFound.count(pMP)) continue;
+                if (best[iMP] < 0) continue;
+                MapPointT *pMPinKF = pKF->GetMapPoint(best[iMP]);
+                if (pMPinKF) {
+                    if (!pMPinKF->isBad()) vpReplacePoints[iMP] = pMPinKF;
+                } else {
+                    pMP->AddObservation(pKF, best[iMP]);
+                    pKF->AddMapPoint(pMP, best[iMP]);
+                    touchedKFs.insert(pKF); touchedPts.insert(pMP);
+                }
+                nFused++;
+            }
+            std::unique_lock<std::mutex> lock(pKF->GetMap()->mMutexMapUpdate);      // LoopClosing.cc:2015-2023
+            for (int i = 0; i < nP; i++) {
+                MapPointT *pRep = vpReplacePoints[i];
+                if (!pRep) continue;
+                MapPointT *stays = vpMapPoints[i];
+                for (const auto &o : pRep->GetObservations()) touchedKFs.insert(o.first);
+                const cv::Mat before = stays->GetDescriptor().clone();
+                pRep->Replace(stays);
+                const cv::Mat after = stays->GetDescriptor();
+                if (std::memcmp(before.ptr(0), after.ptr(0), 32) != 0) changed.insert(stays);
+                touchedPts.insert(pRep); touchedPts.insert(stays);
+            }
+        }
+        stage();
+        return nFused;
+    }
+};
+
+}  // namespace RUMI_FACADE_NAMESPACE
+
+namespace rumi { using LoopClosingStep = RUMI_FACADE_NAMESPACE::LoopClosingStep; }
+#endif  // RUMI_HAVE_SOPHUS

@@ -384,7 +384,7 @@ public:
         const auto q = Tcw.unit_quaternion();
         const float T7[7] = {q.x(), q.y(), q.z(), q.w(), Tcw.translation()(0), Tcw.translation()(1), Tcw.translation()(2)};
         const float Ow[3] = {Owv(0), Owv(1), Owv(2)};
-        const std::set<MapPointT *> spAlreadyFound = pKF->GetMapPoints();
+        const auto spAlreadyFound = pKF->GetMapPoints();                       // std::set<MapPoint *>; `auto`: a data model may return the set of a base type
         std::vector<int32_t> best;
         if (!fuse_search(pKF, T7, Ow, vpPoints, [&](MapPointT *p) { return p->isBad() || spAlreadyFound.count(p) > 0; }, th, 0, best)) return -1;
         int nFused = 0;

@@ -2,7 +2,8 @@
 include/rumi_mapping.h: one call for the current key-frame and all of its neighbours; of the map-point refresh
 (``MapPoint::ComputeDistinctiveDescriptors`` / ``UpdateNormalAndDepth``, R/lib_src/MapPoint.cc:353-427, 450-518) for a batch of points; and of
 ``LocalMapping::KeyFrameCulling`` / ``CloudKeyFrameCulling`` (R/lib_src/LocalMapping.cc:953-1079, 820-951) for the whole covisible list; and of
-the searches of ``LocalMapping::SearchInNeighbors`` (R/lib_src/LocalMapping.cc:649-743) for every target key-frame in one call."""
+the searches of ``LocalMapping::SearchInNeighbors`` (R/lib_src/LocalMapping.cc:649-743) for every target key-frame in one call; and of those of
+``LoopClosing::SearchAndFuse`` (R/lib_src/LoopClosing.cc:1996-2065) for every corrected key-frame in one call."""
 import ctypes as C
 
 import numpy as np
@@ -37,6 +38,8 @@ def _lib():
     L.rumi_newpts_stage_ms.argtypes = [vp, vp]
     L.rumi_search_in_neighbors_resident.argtypes = [vp, vp, i32, vp, vp, vp, i32, C.c_float, vp, vp, vp, i32, C.POINTER(i32)]
     L.rumi_search_in_neighbors_stage_ms.argtypes = [vp, vp]
+    L.rumi_search_and_fuse_resident.argtypes = [vp, vp, vp, vp, i32, vp, i32, C.c_float, vp, i32, C.POINTER(i32), vp]
+    L.rumi_search_and_fuse_stage_ms.argtypes = [vp, vp]
     L.rumi_hook_newpts_matches.argtypes = [vp, i32, i32, vp]
     L.rumi_refresh_create.argtypes = [i32, C.POINTER(vp)]
     L.rumi_refresh_destroy.argtypes = [vp]
@@ -217,6 +220,44 @@ def search_in_neighbors_stage_ms(matcher):
     """(validation + table, upload + kernels + download, write-out) of the matcher's last SearchInNeighborsResident call, ms."""
     out = np.zeros(3, np.float32)
     capi.check(_lib().rumi_search_in_neighbors_stage_ms(matcher._h, capi.ptr(out)))
+    return out
+
+
+# ---- SearchAndFuse ----
+FUSE_HIT_DTYPE = np.dtype([("kf", "<i4"), ("point", "<i4"), ("feature", "<i4"), ("occupant", "<i4")])
+assert FUSE_HIT_DTYPE.itemsize == 16
+
+
+def SearchAndFuseResident(matcher, store, kf_slots, kfs, point_ids, th=4.0, hit_cap=None):
+    """The searches of LoopClosing::SearchAndFuse over key-frames and points resident in ``store``: one device call for every corrected key-frame.
+    ``kfs``: one RumiFuseKF per slot (see ``fuse_kf``) carrying the pose derived from the corrected Sim3, ORBmatcher.cc:1190-1191; ``point_ids``:
+    the loop points (an id < 0 is passed over).  Returns (hits as FUSE_HIT_DTYPE in ascending (kf, point) order, hits per key-frame): only the
+    pairs that found a feature travel back.  ``hit_cap``: first size of the hit list (default: 4 hits per list entry, 1024 at least); when the
+    call answers RUMI_E_CAPACITY the list is grown once to the count it reported and the call is made again."""
+    L = _lib()
+    n = len(kf_slots)
+    assert len(kfs) == n
+    slots = np.ascontiguousarray(kf_slots, np.int32).reshape(-1)
+    ids = np.ascontiguousarray(point_ids, np.int32).reshape(-1)
+    arr = (RumiFuseKF * max(n, 1))(*kfs)
+    cap = max(1024, 4 * len(ids)) if hit_cap is None else int(hit_cap)
+    per = np.zeros(max(n, 1), np.int32)
+    n_hits = C.c_int32()
+    for attempt in range(2):
+        hits = np.zeros(max(cap, 1), FUSE_HIT_DTYPE)
+        rc = L.rumi_search_and_fuse_resident(matcher._h, store._h, capi.ptr(slots) if n else None, C.byref(arr) if n else None, n,
+                                             capi.ptr(ids) if len(ids) else None, len(ids), float(th), capi.ptr(hits), cap, C.byref(n_hits), capi.ptr(per))
+        if rc != capi.RUMI_E_CAPACITY or attempt or n_hits.value <= cap:
+            break
+        cap = n_hits.value
+    capi.check(rc)
+    return hits[:n_hits.value], per[:n]
+
+
+def search_and_fuse_stage_ms(matcher):
+    """(validation + table, upload + kernels + download, write-out) of the matcher's last SearchAndFuseResident call, ms."""
+    out = np.zeros(3, np.float32)
+    capi.check(_lib().rumi_search_and_fuse_stage_ms(matcher._h, capi.ptr(out)))
     return out
 
 
