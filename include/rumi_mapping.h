@@ -194,6 +194,50 @@ int rumi_search_and_fuse_resident(RumiMatcher *m, RumiCovis *c, const int32_t *k
 /* The last call on this matcher, in ms: validation + table | upload, kernels, download | write-out. */
 int rumi_search_and_fuse_stage_ms(const RumiMatcher *m, float *out3);
 
+/* ---- ORBmatcher::SearchByProjection(KeyFrame*, Sim3f&, points, ...) (R/lib_src/ORBmatcher.cc:372-471, :473-579) for every job of a
+ * place-recognition stage in one call, over key-frames and points resident in a covisibility store.  The member is what
+ * DetectCommonRegionsFromBoW / DetectCommonRegionsFromLastKF / DetectAndReffineSim3FromLastKF call between the Sim3 estimates
+ * (LoopClosing.cc:716, :738, :773-795 through FindMatchesByProjection :868-914, :503-540; CloudMerging.cc has the same text).  A job is one
+ * call of the member.  Inside a job the loop is sequential -- `vpMatched[bestIdx] = pMP` (:465, :573) hides the feature from every later
+ * entry -- and the device reproduces exactly that order; jobs are independent of one another, also on the same slot.  Every call site hands
+ * the member a fresh all-NULL vpMatched, so no feature is taken at entry; a caller that needs a pre-filled vector keeps
+ * rumi_search_by_projection_sim3 (include/rumi_match.h).  Monocular.
+ *
+ * For job j and feature f, matched[matched_start[j] + f] is the POSITION inside job j's list of the point the loop leaves in vpMatched[f], or
+ * -1; nmatches[j] the loop's return value: byte for byte what rumi_search_by_projection_sim3 returns for that key-frame's resident features
+ * and K4, that pose, skip[i] = the point is bad in the store or the id is < 0, the stored attributes of the listed points and matched all -1.
+ * A key-frame that already lists a point is NOT a gate (the member does not test it).  An id that appears twice in a list is two independent
+ * entries in order, and both may match.  matched_start [n_jobs + 1]: the rows are concatenated, each the feature count of its job's slot.
+ * Host to device per call: the store's staged edits and staged features, 128 bytes a job, 112 bytes a distinct slot and 4 bytes a list entry.
+ * Device to host: 4 bytes a feature a job and 8 bytes a job, one blocking copy.  A query: the store is not changed.  Integer atomics only: two
+ * calls on the same state return the same bytes.
+ * RUMI_E_INVALID, nothing written: a missing argument; th <= 0, ratio_hamming not finite or <= 0; a pose, centre, bound or scale factor that
+ * is not finite, or empty bounds; a slot that is not live or holds no features, or whose feature count differs from the length of its
+ * map-point row; a list range outside [0, n_points]; an id at or above the store's point capacity; matcher and store on different devices; a
+ * list entry that would be searched and whose point has no attributes (found on the device; the message names how many entries).
+ * RUMI_E_CAPACITY, nothing written: n_jobs > RUMI_FUSE_MAX_TARGETS; a key-frame above the matcher's max_features; 2^31 or more (job, entry)
+ * pairs (more than a work item addresses); matched_cap below the sum of the rows -- then, and only then, matched_start IS written, so that the
+ * caller can size `matched` and call again.  n_jobs == 0, or every list empty: RUMI_OK, the rows all -1, the counts zero, no device call. */
+typedef struct RumiSim3ProjJob {
+    int32_t   kf_slot;                   /* key-frame searched; the same slot may appear in many jobs */
+    RumiFuseKF kf;                       /* Tcw7 and Ow as ORBmatcher.cc:380-381 derive them from Scw (formed by the caller), bounds, mfLogScaleFactor */
+    int32_t   point_start, point_count;  /* this job's list = point_ids[point_start .. +point_count); ranges of different jobs may coincide or overlap */
+    int32_t   th;                        /* 8, 5, 3 upstream */
+    float     ratio_hamming;             /* match iff bestDist <= TH_LOW * ratio_hamming, compared in float as :464 does */
+    int32_t   explicit_invz;             /* 0 = :372-471 (mpCamera->project), 1 = :473-579 (u = fx * (x * (1/z)) + cx) */
+} RumiSim3ProjJob;
+
+int rumi_search_by_projection_sim3_resident(RumiMatcher *m, RumiCovis *c, const RumiSim3ProjJob *jobs, int32_t n_jobs,
+                                            const int32_t *point_ids, int32_t n_points,
+                                            int32_t *matched /* concatenated per job, feature count of its slot each */,
+                                            int32_t *matched_start /* [n_jobs + 1] out */, int32_t matched_cap,
+                                            int32_t *nmatches /* [n_jobs] */);
+/* The last call on this matcher, in ms: validation + table | upload, kernels, download | write-out. */
+int rumi_search_by_projection_sim3_stage_ms(const RumiMatcher *m, float *out3);
+/* The rounds the ordered resolve of each job of the last call took (1: no entry lost a feature to an earlier one; 0 for every job of a call
+ * that made no device call, whose stage times are 0 too).  n_jobs must be that call's. */
+int rumi_search_by_projection_sim3_rounds(const RumiMatcher *m, int32_t *rounds, int32_t n_jobs);
+
 /* ---- MapPoint::ComputeDistinctiveDescriptors (R/lib_src/MapPoint.cc:353-427) and MapPoint::UpdateNormalAndDepth (:450-518) for a batch of
  * points.  Neither member reads another MapPoint: a point's result depends on its own observation list, its position and reference
  * key-frame, and the observing key-frames' descriptors, camera centres, bad flags and scale tables.  So the per-point calls a map-changing

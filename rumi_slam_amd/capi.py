@@ -121,7 +121,8 @@ QUEUE_SYMBOLS = ["rumi_queue_create", "rumi_queue_destroy", "rumi_queue_shards",
 KFDB_SYMBOLS = ["rumi_kfdb_create", "rumi_kfdb_destroy", "rumi_kfdb_clear", "rumi_kfdb_size", "rumi_kfdb_next_seq", "rumi_kfdb_max_batch", "rumi_kfdb_add",
                 "rumi_kfdb_add_batch_device", "rumi_kfdb_bow", "rumi_kfdb_erase", "rumi_kfdb_clear_map", "rumi_kfdb_set_map_bad", "rumi_kfdb_set_maps",
                 "rumi_kfdb_set_bad", "rumi_kfdb_set_covisibles", "rumi_kfdb_score", "rumi_kfdb_scored", "rumi_kfdb_select_reloc", "rumi_kfdb_select_nbest"]
-MAPPING_SYMBOLS = ["rumi_create_new_map_points", "rumi_create_new_map_points_resident", "rumi_newpts_stage_ms", "rumi_search_in_neighbors_resident", "rumi_search_in_neighbors_stage_ms", "rumi_search_and_fuse_resident", "rumi_search_and_fuse_stage_ms", "rumi_refresh_create", "rumi_refresh_destroy", "rumi_refresh_map_points", "rumi_refresh_stage_ms", "rumi_refresh_map_points_resident", "rumi_refresh_last_launches",
+MAPPING_SYMBOLS = ["rumi_create_new_map_points", "rumi_create_new_map_points_resident", "rumi_newpts_stage_ms", "rumi_search_in_neighbors_resident", "rumi_search_in_neighbors_stage_ms", "rumi_search_and_fuse_resident", "rumi_search_and_fuse_stage_ms",
+                   "rumi_search_by_projection_sim3_resident", "rumi_search_by_projection_sim3_stage_ms", "rumi_search_by_projection_sim3_rounds", "rumi_refresh_create", "rumi_refresh_destroy", "rumi_refresh_map_points", "rumi_refresh_stage_ms", "rumi_refresh_map_points_resident", "rumi_refresh_last_launches",
                    "rumi_cull_create", "rumi_cull_destroy", "rumi_keyframe_culling", "rumi_keyframe_culling_resident", "rumi_cull_stage_ms"]
 COVIS_SYMBOLS = ["rumi_covis_create", "rumi_covis_destroy", "rumi_covis_set_keyframes", "rumi_covis_set_points", "rumi_covis_set_point_observations",
                  "rumi_covis_set_point_attributes", "rumi_covis_set_keyframe_centres", "rumi_covis_set_point_reference",

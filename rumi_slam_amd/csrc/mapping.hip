@@ -471,6 +471,8 @@ struct SinState;                                             // the blocks of ru
 static void sin_destroy(SinState *s);
 struct SafState;                                             // the blocks of rumi_search_and_fuse_resident (search_and_fuse.inc)
 static void saf_destroy(SafState *s);
+struct S3pState;                                             // the blocks of rumi_search_by_projection_sim3_resident (sim3_projection_batch.inc)
+static void s3p_destroy(S3pState *s);
 
 struct NewPtsState {
     MirrorBuf<uint8_t> blk, res;                             // the upload block; the result block, a NewPtsResult and its points
@@ -481,12 +483,14 @@ struct NewPtsState {
     float stageMs[3] = {0.f, 0.f, 0.f};
     SinState *sin = nullptr;                                 // with the first SearchInNeighbors or SearchAndFuse call (the stamped tables)
     SafState *saf = nullptr;                                 // with the first SearchAndFuse call
+    S3pState *s3p = nullptr;                                 // with the first resident Sim3 projection search
 };
 
 static void newpts_destroy(void *p) {                        // rumi_match_destroy has made the matcher's device current
     NewPtsState *s = static_cast<NewPtsState *>(p);
     if (s->sin) sin_destroy(s->sin);
     if (s->saf) saf_destroy(s->saf);
+    if (s->s3p) s3p_destroy(s->s3p);
     delete s;
 }
 
@@ -726,3 +730,4 @@ extern "C" int rumi_hook_newpts_matches(RumiMatcher *m, int32_t n_neigh, int32_t
 
 #include "search_in_neighbors.inc"
 #include "search_and_fuse.inc"
+#include "sim3_projection_batch.inc"

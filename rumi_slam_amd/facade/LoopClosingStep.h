@@ -3,7 +3,7 @@
 // with SearchByBoW(KF, KF) and the match vectors are folded into vpMatchedPoints / vpKeyFrameMatchedMP.  All candidates, all members and the folds
 // go to the GPU in one call (include/rumi_match.h: rumi_common_regions_bow); this side applies the checks that need no device, marshals the
 // key-frames and hands back, per candidate, what the loop body from :655 on reads.  That body (the Sim3 solver, the two SearchByProjection passes,
-// OptimizeSim3, the covisible check) stays where it is and runs through the entries it already has.
+// OptimizeSim3, the covisible check) stays where it is; its SearchByProjection passes and the covisible check have one-call members below.
 //
 // Templated on the key-frame, map-point and matcher types, so that it instantiates against the reference's classes and against the stand-ins of
 // tests/cpp.  Mono key-frames only.
@@ -12,6 +12,9 @@
 //     rumi::LoopClosingStep step;                                    // = ORBmatcher matcher(0.8)
 //     step.SearchAndFuseResident(graph, poses, vpMapPoints);         // poses: (KeyFrame *, Sophus::Sim3f) in CorrectedPosesMap's order
 //     step.SearchAndFuseResident(graph, vConectedKFs, vpMapPoints);  // the overload that searches under GetPose(), scale 1
+// and the SearchByProjection(KF, Scw, ...) searches of DetectCommonRegionsFromBoW (:716, :738, the covisible check :773-795) become
+//     step.SearchByProjectionResident(graph, jobs);                  // one Sim3ProjectionJob per call of the reference's member
+//     step.CovisibleCheckResident(graph, pCurrentKF, pMostBoWMatchesKF, gScw, vpCurrentCovKFs, vpMapPoints, &nNumKFs, Converter::toSophus);
 // (at the end of this header).
 #pragma once
 #include <cstdint>
@@ -213,6 +216,157 @@ public:
     template <class Sim3T = Sophus::Sim3f, class GraphT, class RangeT, class MapPointT>
     int SearchAndFuseResident(GraphT &graph, const RangeT &kfs, std::vector<MapPointT *> &vpMapPoints, int *nSearchedAgain = nullptr) {
         return saf_dispatch<Sim3T>(graph, kfs, vpMapPoints, nSearchedAgain, typename std::is_pointer<typename RangeT::value_type>::type());
+    }
+
+    // ---- The SearchByProjection(KeyFrame*, Sim3f&, points, ...) searches of DetectCommonRegionsFromBoW (LoopClosing.cc:716, :738, :773-795;
+    // CloudMerging.cc:1157, 1179, 1226 are the same text) over a CovisibilityGraph that holds the map: the jobs of a stage in ONE device call
+    // (rumi_search_by_projection_sim3_resident, include/rumi_mapping.h).  The member changes no map, so there is no replay.
+    // One call of the reference's member.  vpPointsKFs / vpMatchedKF: both set for the overload of ORBmatcher.cc:473-579, both null for
+    // :372-471.  *vpMatched (and *vpMatchedKF) are what the call sites hand over: all NULL; the member sizes them to the key-frame's
+    // features and fills them as the overload would have.  A point list that several jobs name is sent once.
+    template <class KeyFrameT, class MapPointT> struct Sim3ProjectionJob {
+        KeyFrameT *pKF;
+        Sophus::Sim3f Scw;
+        const std::vector<MapPointT *> *vpPoints;
+        const std::vector<KeyFrameT *> *vpPointsKFs;
+        int th;
+        float ratioHamming;
+        std::vector<MapPointT *> *vpMatched;
+        std::vector<KeyFrameT *> *vpMatchedKF;
+        int *nmatches;
+    };
+
+    // Serves :716 and :738 across all candidates that reached those lines.  Returns the number of jobs, or -1 with a report and nothing
+    // written: NLeft != -1, a key-frame the graph has never seen or without SyncFeatures, a point the graph has never seen, a searched point
+    // without attributes (found by the device call), a failed device call (more jobs than RUMI_FUSE_MAX_TARGETS among them).
+    template <class GraphT, class KeyFrameT, class MapPointT>
+    int SearchByProjectionResident(GraphT &graph, const std::vector<Sim3ProjectionJob<KeyFrameT, MapPointT>> &jobs) {
+        static const char *where = "LoopClosingStep::SearchByProjectionResident";
+        if (!graph.ok()) { rumi_facade::report(where, RUMI_E_INVALID, "no store; nothing was searched"); return -1; }
+        std::vector<RumiSim3ProjJob> rec;
+        std::vector<int32_t> ids;
+        std::vector<std::pair<const std::vector<MapPointT *> *, int32_t>> sent;      // a list and where it starts in ids
+        size_t rows = 0;
+        for (const auto &J : jobs) {
+            KeyFrameT *pKF = J.pKF;
+            if (pKF->NLeft != -1) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a key-frame with NLeft != -1: only the monocular SearchByProjection is built; nothing was searched");
+                return -1;
+            }
+            if (graph.SlotOf(pKF) < 0 || !graph.HasFeatures(pKF)) {
+                rumi_facade::report(where, RUMI_E_INVALID, "a key-frame the graph has never seen or without resident features (graph.Sync, graph.SyncFeatures); nothing was uploaded, nothing was searched");
+                return -1;
+            }
+            int32_t start = -1;
+            for (const auto &s : sent) if (s.first == J.vpPoints) start = s.second;
+            if (start < 0) {
+                start = (int32_t)ids.size();
+                for (MapPointT *pMP : *J.vpPoints) {
+                    if (!pMP) { ids.push_back(-1); continue; }
+                    if (!graph.HasPoint(pMP)) {
+                        rumi_facade::report(where, RUMI_E_INVALID, "a point the graph has never seen (graph.Sync, graph.SyncAttributes); nothing was uploaded, nothing was searched");
+                        return -1;
+                    }
+                    ids.push_back(graph.IdOf(pMP));
+                }
+                sent.emplace_back(J.vpPoints, start);
+            }
+            Sophus::Sim3f Scw = J.Scw;                                              // ORBmatcher.cc:380-381 / :481-482, as searchSim3 (ORBmatcher.h) forms them
+            const Sophus::SE3f Tcw = Sophus::SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale());
+            const Eigen::Vector3f Ow = Tcw.inverse().translation();
+            const auto q = Tcw.unit_quaternion();
+            RumiSim3ProjJob r;
+            r.kf_slot = graph.SlotOf(pKF);
+            r.kf.Tcw7[0] = q.x(); r.kf.Tcw7[1] = q.y(); r.kf.Tcw7[2] = q.z(); r.kf.Tcw7[3] = q.w();
+            for (int c = 0; c < 3; c++) { r.kf.Tcw7[4 + c] = Tcw.translation()(c); r.kf.Ow[c] = Ow(c); }
+            r.kf.bounds[0] = pKF->mnMinX; r.kf.bounds[1] = pKF->mnMinY; r.kf.bounds[2] = pKF->mnMaxX; r.kf.bounds[3] = pKF->mnMaxY;
+            r.kf.log_scale_factor = pKF->mfLogScaleFactor;
+            r.point_start = start; r.point_count = (int32_t)J.vpPoints->size();
+            r.th = J.th; r.ratio_hamming = J.ratioHamming; r.explicit_invz = J.vpPointsKFs ? 1 : 0;
+            rec.push_back(r);
+            rows += (size_t)pKF->N;
+        }
+        if (jobs.empty()) return 0;
+        if (graph.FlushDirty() != RUMI_OK) return -1;
+        const int nJ = (int)jobs.size();
+        std::vector<int32_t> matched(rows + 1), start((size_t)nJ + 1), nm((size_t)nJ);
+        ids.push_back(-1);                                                          // (never an empty array)
+        if (!arena()) return -1;                                                    // reported by arena()
+        if (RUMI_GUARDED("LoopClosingStep / rumi_search_by_projection_sim3_resident", &ORBmatcher::grow_arena,
+                         rumi_search_by_projection_sim3_resident(arena(), graph.handle(), rec.data(), nJ, ids.data(), (int32_t)ids.size() - 1, matched.data(),
+                                                                 start.data(), (int32_t)rows, nm.data())) != RUMI_OK)
+            return -1;
+        for (int j = 0; j < nJ; j++) {                                              // :465 / :573-574 from the returned positions
+            const auto &J = jobs[j];
+            const int N = J.pKF->N;
+            J.vpMatched->assign((size_t)N, static_cast<MapPointT *>(nullptr));
+            if (J.vpMatchedKF) J.vpMatchedKF->assign((size_t)N, static_cast<KeyFrameT *>(nullptr));
+            for (int f = 0; f < N; f++) {
+                const int i = matched[(size_t)start[j] + f];
+                if (i < 0) continue;
+                (*J.vpMatched)[f] = (*J.vpPoints)[i];
+                if (J.vpMatchedKF && J.vpPointsKFs) (*J.vpMatchedKF)[f] = (*J.vpPointsKFs)[i];
+            }
+            if (J.nmatches) *J.nmatches = nm[j];
+        }
+        return nJ;
+    }
+
+    // The loop :773-795 for one candidate: `while (nNumKFs < 3 && j < vpCurrentCovKFs.size())` over DetectCommonRegionsFromLastKF (:855-866)
+    // -> FindMatchesByProjection (:868-914).  The list of :871-905 is built ONCE: it depends on the matched key-frame alone (spCheckKFs and
+    // spCurrentCovisbles, the only things the covisible enters, reach nothing that leaves the function).  gSjw is formed per covisible as
+    // :779-781 do and every covisible is searched in one call (th 3, ratio 1.5, :911); then the while loop is replayed over the counts with
+    // the threshold 30 of :860-861.  The covisibles after the third valid one are searched SPECULATIVELY and passed over: the reference would
+    // not have searched them, and nothing of their answers leaves this member.  vpMapPoints is left as the member leaves it, cleared and
+    // refilled through the reference parameter (:893-905); with no covisible it is untouched, as in the reference.
+    // toSophus: Converter::toSophus (g2o::Sim3 -> Sophus::Sim3f).  Returns the covisibles the loop visited, or -1 with a report, nNumKFs and
+    // vpMapPoints untouched (the refusals of SearchByProjectionResident).
+    template <class GraphT, class KeyFrameT, class MapPointT, class G2oSim3T, class ToSophusT>
+    int CovisibleCheckResident(GraphT &graph, KeyFrameT *pCurrentKF, KeyFrameT *pMostBoWMatchesKF, const G2oSim3T &gScw,
+                               const std::vector<KeyFrameT *> &vpCurrentCovKFs, std::vector<MapPointT *> &vpMapPoints, int *nNumKFs, ToSophusT toSophus) {
+        if (vpCurrentCovKFs.empty()) return 0;
+        std::vector<MapPointT *> vpList;                                            // :871-905
+        {
+            int nNumCovisibles = 10;
+            std::vector<KeyFrameT *> vpCovKFm = pMostBoWMatchesKF->GetBestCovisibilityKeyFrames(nNumCovisibles);
+            int nInitialCov = vpCovKFm.size();
+            vpCovKFm.push_back(pMostBoWMatchesKF);
+            if (nInitialCov < nNumCovisibles) {
+                for (int i = 0; i < nInitialCov; ++i) {
+                    std::vector<KeyFrameT *> vpKFs = vpCovKFm[i]->GetBestCovisibilityKeyFrames(nNumCovisibles);
+                    vpCovKFm.insert(vpCovKFm.end(), vpKFs.begin(), vpKFs.end());
+                }
+            }
+            std::set<MapPointT *> spMapPoints;
+            for (KeyFrameT *pKFi : vpCovKFm) {
+                for (MapPointT *pMPij : pKFi->GetMapPointMatches()) {
+                    if (!pMPij || pMPij->isBad()) continue;
+                    if (spMapPoints.find(pMPij) == spMapPoints.end()) { spMapPoints.insert(pMPij); vpList.push_back(pMPij); }
+                }
+            }
+        }
+        const size_t nC = vpCurrentCovKFs.size();
+        std::vector<std::vector<MapPointT *>> vvpMatched(nC);
+        std::vector<int> num(nC, 0);
+        std::vector<Sim3ProjectionJob<KeyFrameT, MapPointT>> jobs;
+        for (size_t j = 0; j < nC; j++) {
+            KeyFrameT *pKFj = vpCurrentCovKFs[j];
+            const Sophus::SE3f Tjc = pKFj->GetPose() * pCurrentKF->GetPoseInverse();         // :779: .cast<double>() widens each component
+            const auto q = Tjc.unit_quaternion(); const auto t = Tjc.translation();
+            G2oSim3T gSjc(Eigen::Quaterniond((double)q.w(), (double)q.x(), (double)q.y(), (double)q.z()), Eigen::Vector3d((double)t(0), (double)t(1), (double)t(2)), 1.0);
+            G2oSim3T gSjw = gSjc * gScw;
+            jobs.push_back(Sim3ProjectionJob<KeyFrameT, MapPointT>{pKFj, toSophus(gSjw), &vpList, nullptr, 3, 1.5f, &vvpMatched[j], nullptr, &num[j]});
+        }
+        if (SearchByProjectionResident(graph, jobs) < 0) return -1;
+        size_t j = 0;                                                               // :775-795 over the counts
+        int n = *nNumKFs;
+        while (n < 3 && j < nC) {
+            if (num[j] >= 30) n++;                                                  // :860-863
+            j++;
+        }
+        if (j > 0) vpMapPoints = vpList;                                            // every visited covisible leaves the same list
+        *nNumKFs = n;
+        return (int)j;
     }
 
 protected:

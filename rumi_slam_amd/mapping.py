@@ -40,6 +40,9 @@ def _lib():
     L.rumi_search_in_neighbors_stage_ms.argtypes = [vp, vp]
     L.rumi_search_and_fuse_resident.argtypes = [vp, vp, vp, vp, i32, vp, i32, C.c_float, vp, i32, C.POINTER(i32), vp]
     L.rumi_search_and_fuse_stage_ms.argtypes = [vp, vp]
+    L.rumi_search_by_projection_sim3_resident.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, i32, vp]
+    L.rumi_search_by_projection_sim3_stage_ms.argtypes = [vp, vp]
+    L.rumi_search_by_projection_sim3_rounds.argtypes = [vp, vp, i32]
     L.rumi_hook_newpts_matches.argtypes = [vp, i32, i32, vp]
     L.rumi_refresh_create.argtypes = [i32, C.POINTER(vp)]
     L.rumi_refresh_destroy.argtypes = [vp]
@@ -259,6 +262,59 @@ def search_and_fuse_stage_ms(matcher):
     out = np.zeros(3, np.float32)
     capi.check(_lib().rumi_search_and_fuse_stage_ms(matcher._h, capi.ptr(out)))
     return out
+
+
+# ---- SearchByProjection(KeyFrame*, Sim3f&, points, ...) of place recognition ----
+SIM3_PROJ_JOB_DTYPE = np.dtype([("kf_slot", "<i4"), ("Tcw7", "<f4", 7), ("Ow", "<f4", 3), ("bounds", "<f4", 4), ("log_scale_factor", "<f4"),
+                                ("point_start", "<i4"), ("point_count", "<i4"), ("th", "<i4"), ("ratio_hamming", "<f4"), ("explicit_invz", "<i4")])
+assert SIM3_PROJ_JOB_DTYPE.itemsize == 84          # RumiSim3ProjJob
+
+
+def sim3_proj_job(kf_slot, Tcw7, Ow, bounds, log_sf, point_start, point_count, th, ratio_hamming, explicit_invz=False):
+    """One RumiSim3ProjJob as a record of SIM3_PROJ_JOB_DTYPE: the key-frame's slot, the pose derived from Scw (ORBmatcher.cc:380-381), its bounds and
+    mfLogScaleFactor, the job's range of the call's point ids, th, the Hamming ratio and which overload's projection to use."""
+    j = np.zeros((), SIM3_PROJ_JOB_DTYPE)
+    j["kf_slot"], j["Tcw7"], j["Ow"], j["bounds"], j["log_scale_factor"] = kf_slot, np.float32(Tcw7), np.float32(Ow), np.float32(bounds), log_sf
+    j["point_start"], j["point_count"], j["th"], j["ratio_hamming"], j["explicit_invz"] = point_start, point_count, th, ratio_hamming, int(explicit_invz)
+    return j
+
+
+def SearchByProjectionSim3Resident(matcher, store, jobs, point_ids):
+    """Every SearchByProjection(KeyFrame*, Sim3f&, ...) call of a place-recognition stage over key-frames and points resident in ``store``: one
+    device call.  ``jobs``: a structured array of SIM3_PROJ_JOB_DTYPE (see ``sim3_proj_job``); ``point_ids``: the ids the jobs' ranges index.
+    Returns (matched_rows, nmatches): matched_rows[j][f] is the position inside job j's list of the point left in vpMatched[f], or -1; every job
+    starts from an all-NULL vpMatched."""
+    L = _lib()
+    jobs = np.ascontiguousarray(jobs, SIM3_PROJ_JOB_DTYPE).reshape(-1)
+    ids = np.ascontiguousarray(point_ids, np.int32).reshape(-1)
+    n = len(jobs)
+    start = np.zeros(n + 1, np.int32)
+    nm = np.zeros(max(n, 1), np.int32)
+    lengths = [store.row_length(int(s)) for s in jobs["kf_slot"]]
+    cap = sum(max(x, 0) for x in lengths)
+    for attempt in range(2):
+        rows = np.full(max(cap, 1), -1, np.int32)
+        rc = L.rumi_search_by_projection_sim3_resident(matcher._h, store._h, capi.ptr(jobs) if n else None, n, capi.ptr(ids) if len(ids) else None,
+                                                       len(ids), capi.ptr(rows), capi.ptr(start), cap, capi.ptr(nm))
+        if rc != capi.RUMI_E_CAPACITY or attempt or int(start[n]) <= cap:
+            break
+        cap = int(start[n])
+    capi.check(rc)
+    return [rows[start[j]:start[j + 1]] for j in range(n)], nm[:n]
+
+
+def search_by_projection_sim3_stage_ms(matcher):
+    """(validation + table, upload + kernels + download, write-out) of the matcher's last SearchByProjectionSim3Resident call, ms."""
+    out = np.zeros(3, np.float32)
+    capi.check(_lib().rumi_search_by_projection_sim3_stage_ms(matcher._h, capi.ptr(out)))
+    return out
+
+
+def search_by_projection_sim3_rounds(matcher, n_jobs):
+    """Rounds the ordered resolve took for each job of the matcher's last SearchByProjectionSim3Resident call."""
+    out = np.zeros(max(int(n_jobs), 1), np.int32)
+    capi.check(_lib().rumi_search_by_projection_sim3_rounds(matcher._h, capi.ptr(out), int(n_jobs)))
+    return out[:int(n_jobs)]
 
 
 # ---- map-point refresh ----
