@@ -213,6 +213,54 @@ int rumi_optimize_sim3(RumiOptimizer *o, int32_t n, const int32_t *pair_of, int3
                        const float *inv_sigma2_2, const uint8_t *skip12, const uint8_t *skip21, const float *K4_1, const float *K4_2, float th2,
                        int32_t fix_scale, int32_t robust_first_pass, double *S_io8, uint8_t *status_out, int32_t *result3);
 
+/* Sim3Solver::iterate(nIterations, bNoMore, vbInliers, nInliers, bConverge) — R/lib_src/Sim3Solver.cc:222-290 — of the J solvers that
+ * DetectCommonRegionsFromBoW runs one after the other (LoopClosing.cc:655-676, CloudMerging.cc:1019 ff.), in one call.  The solvers share the
+ * process-wide rand() and every iteration consumes exactly three draws (:249-259), so iteration g of the stream uses the same three numbers
+ * whichever solver runs it; only the mapping to indices depends on the solver's N.  The caller takes a window of `window` iterations of the
+ * stream and draws it once per solver with that solver's N: triples [J][window][3], indices relative to the solver's `first`.  The device
+ * evaluates every (solver, iteration) — ComputeSim3 and CheckInliers exactly as rumi_sim3_ransac — and then applies the sequential rule in
+ * solver order with pos = 0: solver j returns at the first h in [pos, min(pos + its_left, window)) that is valid and has more than min_inliers
+ * inliers (upstream's ">= mnBestInliers" cannot fail there: an earlier iteration with as many would itself have returned; a degenerate set
+ * keeps the previous, non-returning, count).
+ *   RUMI_SIM3_CONVERGED     its = h - pos + 1, pos <- h + 1; hyp = h, n_inliers, T12 = that iteration's T12_out record, mask in inlier_out
+ *   RUMI_SIM3_EXHAUSTED     no such h and pos + its_left <= window: its = its_left (the solver's bNoMore), pos <- pos + its_left
+ *   RUMI_SIM3_WINDOW_ENDED  no such h and pos + its_left > window: its = window - pos; every later solver is RUMI_SIM3_NOT_REACHED, its = 0
+ * The caller advances rand() by 3 * (sum of its) and calls again with what is left (rumi_slam_amd.sim3solver.Sim3SolverBatch,
+ * facade/PlaceRecognitionStages.h).  Solvers with fewer correspondences than min_inliers draw nothing upstream (:228-231) and are not sent.
+ * Correspondences are concatenated over the solvers (n_total entries; the ranges [first, first + n) ascend without overlap); K4_1 / K4_2 are
+ * {fx fy cx cy} of the two key-frames.  inlier_out [n_total]: the mask of a converged solver in its range, 0 elsewhere.  n_inliers_all
+ * [J][window] and T12_all [J][window][16] (both may be NULL): every hypothesis as rumi_sim3_ransac returns it for that solver and triple,
+ * byte for byte.  RUMI_E_INVALID (n < 3, a triple index outside [0, n), its_left < 1, window < 1, ranges out of order) and RUMI_E_CAPACITY
+ * (the staging does not fit the handle's arena) leave every output untouched. */
+enum { RUMI_SIM3_NOT_REACHED = 0, RUMI_SIM3_CONVERGED = 1, RUMI_SIM3_EXHAUSTED = 2, RUMI_SIM3_WINDOW_ENDED = 3 };
+typedef struct RumiSim3RansacSolver {
+    int32_t first, n;            /* the solver's correspondences in the concatenated arrays, n >= 3 */
+    int32_t min_inliers;         /* mRansacMinInliers */
+    int32_t its_left;            /* mRansacMaxIts - mnIterations, >= 1 */
+    int32_t fix_scale;
+    float K4_1[4], K4_2[4];
+} RumiSim3RansacSolver;
+typedef struct RumiSim3RansacResult {
+    int32_t state, its, hyp, n_inliers;
+    float T12[16];
+} RumiSim3RansacResult;
+int rumi_sim3_ransac_batch(RumiOptimizer *o, int32_t n_solvers, const RumiSim3RansacSolver *solvers, int32_t n_total, const float *X3Dc1,
+                           const float *X3Dc2, const float *sigma2_1, const float *sigma2_2, int32_t window, const int32_t *triples,
+                           RumiSim3RansacResult *results, uint8_t *inlier_out, int32_t *n_inliers_all, float *T12_all);
+
+/* Optimizer::OptimizeSim3 (the pair form of rumi_optimize_sim3: S_c1w == NULL, no skip flags) of J candidates in one call, one workgroup
+ * per problem.  Correspondences are concatenated as above; per problem the bytes rumi_optimize_sim3 returns: S_io8 [J][8] in / out,
+ * status_out [n_total], result3 [J][3].  n = 0 and "n - nBad < 10" behave as there. */
+typedef struct RumiSim3OptProblem {
+    int32_t first, n;
+    float th2;
+    int32_t fix_scale, robust_first_pass;
+    float K4_1[4], K4_2[4];
+} RumiSim3OptProblem;
+int rumi_optimize_sim3_batch(RumiOptimizer *o, int32_t n_problems, const RumiSim3OptProblem *problems, int32_t n_total, const float *P1c,
+                             const float *P2c, const float *obs1, const float *obs2, const float *inv_sigma2_1, const float *inv_sigma2_2,
+                             double *S_io8, uint8_t *status_out, int32_t *result3);
+
 /* Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale) —
  * R/lib_src/Optimizer.cc:1357-1623 (LoopClosing::CorrectLoop) and its merge overload (pCurKF, vpFixedKFs, vpFixedCorrectedKFs, vpNonFixedKFs,
  * vpNonCorrectedMPs) — :1625-1918: the Sim3 pose graph, Levenberg-Marquardt with setUserLambdaInit(1e-16) over g2o::VertexSim3Expmap vertices

@@ -110,7 +110,7 @@ MATCH_SYMBOLS = ["rumi_descriptor_distance", "rumi_match_create", "rumi_match_de
 
 OPT_SYMBOLS = ["rumi_opt_create", "rumi_opt_destroy", "rumi_pose_optimization", "rumi_pose_optimization_batch", "rumi_local_ba", "rumi_local_ba_batch", "rumi_merge_ba", "rumi_bundle_adjustment", "rumi_sim3_inliers",
                "rumi_optimize_sim3", "rumi_sim3_ransac", "rumi_opt_stage_ms", "rumi_opt_set_profiling", "rumi_opt_kernel_ms", "rumi_opt_footprint",
-               "rumi_essential_graph", "rumi_sim3_correct_points"]
+               "rumi_essential_graph", "rumi_sim3_correct_points", "rumi_sim3_ransac_batch", "rumi_optimize_sim3_batch"]
 
 VOC_SYMBOLS = ["rumi_voc_create", "rumi_voc_load_text", "rumi_voc_destroy", "rumi_voc_words", "rumi_voc_levels", "rumi_voc_set_levels", "rumi_voc_assemble", "rumi_voc_transform_features",
                "rumi_voc_transform_batch_device", "rumi_voc_transform"]

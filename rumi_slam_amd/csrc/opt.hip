@@ -44,6 +44,7 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 #include "ba_big.inc"
 #include "chol_blocked.inc"
 #include "sim3.inc"
+#include "sim3_batch.inc"
 #include "ba_windows.inc"
 #include "essential.inc"
 
@@ -259,3 +260,4 @@ static int fetch_published_scalars(BaArena::HostLoop &s, hipStream_t st) {
 
 #include "ba_single_host.inc"
 #include "sim3_host.inc"
+#include "sim3_batch_host.inc"

@@ -1,5 +1,5 @@
 // sim3.inc -- the three Sim3 kernels with their argument blocks: ComputeInliersNum, the RANSAC hypotheses, OptimizeSim3 (host side: sim3_host.inc).
-// Included by opt.hip inside namespace rumi.
+// Included by opt.hip inside namespace rumi.  sim3_batch.inc runs the same per-hypothesis and per-problem device functions over several candidates.
 
 // Sim3Solver::ComputeInliersNum (R/lib_src/Sim3Solver.cc:564-664): one lane per matched key-point pair.
 // g2o::Sim3::map = s * (r * xyz) + t in double (G/types/sim3.h:144-146), Pinhole::project(Vector3d) in double then .cast<float>()
@@ -70,77 +70,103 @@ __device__ inline void sym4_dominant_eigenvector(double a[4][4], double q[4]) {
     for (int k = 0; k < 4; k++) q[k] = v[k][best];
 }
 
+// ComputeSim3 (:437-540) of one minimal set: the three correspondences tri[0..2] of X1 / X2.  Writes the rows of [sR | t] of T12 and T21 (what
+// CheckInliers multiplies with), the 16-float record of rumi_sim3_ransac's T12_out, and hands R, t, s back for the rumination overload.
+// One thread; k_sim3_ransac (lane 0 of a workgroup) and k_s3b_hyp (one lane per hypothesis) both call it, so both round alike.
+__device__ __forceinline__ void sim3_minimal_solve(const float *X1, const float *X2, const int32_t *tri, int fixScale, float *sT12, float *sT21, float *Tout,
+                                                   float (&R)[3][3], float (&t12)[3], float &s12) {
+    float P1[3][3], P2[3][3];                                  // column i = correspondence i (:185-188)
+    for (int i = 0; i < 3; i++) {
+        const int idx = tri[i];
+        for (int r = 0; r < 3; r++) { P1[r][i] = X1[idx * 3 + r]; P2[r][i] = X2[idx * 3 + r]; }
+    }
+    float O1[3], O2[3], Pr1[3][3], Pr2[3][3];                  // ComputeCentroid :430-435
+    for (int r = 0; r < 3; r++) {
+        O1[r] = ((P1[r][0] + P1[r][1]) + P1[r][2]) / 3.f;
+        O2[r] = ((P2[r][0] + P2[r][1]) + P2[r][2]) / 3.f;
+        for (int i = 0; i < 3; i++) { Pr1[r][i] = P1[r][i] - O1[r]; Pr2[r][i] = P2[r][i] - O2[r]; }
+    }
+    float M[3][3];                                             // Pr2 * Pr1^T :453
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) M[r][c] = (Pr2[r][0] * Pr1[c][0] + Pr2[r][1] * Pr1[c][1]) + Pr2[r][2] * Pr1[c][2];
+    const double N11 = M[0][0] + M[1][1] + M[2][2], N12 = M[1][2] - M[2][1], N13 = M[2][0] - M[0][2], N14 = M[0][1] - M[1][0],
+                 N22 = M[0][0] - M[1][1] - M[2][2], N23 = M[0][1] + M[1][0], N24 = M[2][0] + M[0][2], N33 = -M[0][0] + M[1][1] - M[2][2],
+                 N34 = M[1][2] + M[2][1], N44 = -M[0][0] - M[1][1] + M[2][2];
+    // upstream stores N in a Matrix4f: the solver sees the float-rounded entries
+    double Nm[4][4] = {{(float)N11, (float)N12, (float)N13, (float)N14}, {(float)N12, (float)N22, (float)N23, (float)N24},
+                       {(float)N13, (float)N23, (float)N33, (float)N34}, {(float)N14, (float)N24, (float)N34, (float)N44}};
+    double q[4];
+    sym4_dominant_eigenvector(Nm, q);
+    const float e0 = (float)q[0];
+    float vec[3] = {(float)q[1], (float)q[2], (float)q[3]};
+    const float nrm = sqrtf((vec[0] * vec[0] + vec[1] * vec[1]) + vec[2] * vec[2]);
+    int valid = !(vec[0] == 0 && vec[1] == 0 && vec[2] == 0);   // :493-494 upstream keeps the previous iteration's transform
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R[r][c] = r == c ? 1.f : 0.f; t12[r] = 0.f; }
+    s12 = 1.f;
+    if (valid) {
+        const double ang = atan2((double)nrm, (double)e0);
+        const float f = (float)(2 * ang);
+        for (int k = 0; k < 3; k++) vec[k] = vec[k] * f / nrm;   // angle-axis; the quaternion angle is the half
+        // Sophus::SO3f::exp(vec).matrix()
+        const float th2 = (vec[0] * vec[0] + vec[1] * vec[1]) + vec[2] * vec[2], th = sqrtf(th2), half = 0.5f * th;
+        float im, re;
+        if (th < 1e-5f) { const float th4 = th2 * th2; im = 0.5f - (1.f / 48.f) * th2 + (1.f / 3840.f) * th4; re = 1.f - (1.f / 8.f) * th2 + (1.f / 384.f) * th4; }
+        else { im = sinf(half) / th; re = cosf(half); }
+        const float qx = im * vec[0], qy = im * vec[1], qz = im * vec[2], qw = re;
+        const float tx = 2 * qx, ty = 2 * qy, tz = 2 * qz, twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx,
+                    tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
+        R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
+        R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
+        R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
+        if (!fixScale) {                                      // :503-520
+            double nom = 0, den = 0;
+            float P3[3][3];
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) P3[r][c] = (R[r][0] * Pr2[0][c] + R[r][1] * Pr2[1][c]) + R[r][2] * Pr2[2][c];
+            float fn = 0, fd = 0;                               // Eigen's float array sums, column-major order
+            for (int c = 0; c < 3; c++) for (int r = 0; r < 3; r++) { fn += Pr1[r][c] * P3[r][c]; fd += P3[r][c] * P3[r][c]; }
+            nom = fn; den = fd;
+            s12 = (float)(nom / den);
+        }
+        for (int r = 0; r < 3; r++) {                           // mt12i = O1 - ms12i * mR12i * O2
+            const float ro = ((s12 * R[r][0]) * O2[0] + (s12 * R[r][1]) * O2[1]) + (s12 * R[r][2]) * O2[2];
+            t12[r] = O1[r] - ro;
+        }
+    }
+    const float sinv = (float)(1.0 / s12);
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) { sT12[r * 4 + c] = s12 * R[r][c]; sT21[r * 4 + c] = sinv * R[c][r]; }
+        sT12[r * 4 + 3] = t12[r];
+    }
+    for (int r = 0; r < 3; r++) sT21[r * 4 + 3] = -((sT21[r * 4 + 0] * t12[0] + sT21[r * 4 + 1] * t12[1]) + sT21[r * 4 + 2] * t12[2]);
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Tout[r * 3 + c] = R[r][c];
+    Tout[9] = t12[0]; Tout[10] = t12[1]; Tout[11] = t12[2]; Tout[12] = s12; Tout[13] = (float)valid; Tout[14] = 0; Tout[15] = 0;
+}
+
+// CheckInliers :542-562 of one correspondence (float, as upstream): a = point 1 in camera 1, b = point 2 in camera 2, K = {fx fy cx cy}
+__device__ __forceinline__ bool sim3_check_inlier(const float *K1, const float *K2, const float *sT12, const float *sT21, const float *a, const float *b,
+                                                  float thr1, float thr2) {
+    const float fx1 = K1[0], fy1 = K1[1], cx1 = K1[2], cy1 = K1[3], fx2 = K2[0], fy2 = K2[1], cx2 = K2[2], cy2 = K2[3];
+    const float u1 = fx1 * a[0] / a[2] + cx1, v1 = fy1 * a[1] / a[2] + cy1;            // mvP1im1
+    const float u2 = fx2 * b[0] / b[2] + cx2, v2 = fy2 * b[1] / b[2] + cy2;            // mvP2im2
+    float p[3], r[3];
+    for (int k = 0; k < 3; k++) {
+        p[k] = ((sT12[k * 4] * b[0] + sT12[k * 4 + 1] * b[1]) + sT12[k * 4 + 2] * b[2]) + sT12[k * 4 + 3];   // point 2 in camera 1
+        r[k] = ((sT21[k * 4] * a[0] + sT21[k * 4 + 1] * a[1]) + sT21[k * 4 + 2] * a[2]) + sT21[k * 4 + 3];   // point 1 in camera 2
+    }
+    const float d1x = u1 - (fx1 * p[0] / p[2] + cx1), d1y = v1 - (fy1 * p[1] / p[2] + cy1);
+    const float d2x = (fx2 * r[0] / r[2] + cx2) - u2, d2y = (fy2 * r[1] / r[2] + cy2) - v2;
+    const float err1 = d1x * d1x + d1y * d1y, err2 = d2x * d2x + d2y * d2y;
+    return err1 < thr1 && err2 < thr2;
+}
+
 __global__ __launch_bounds__(256) void k_sim3_ransac(RansacArgs A) {
     __shared__ float sT12[12], sT21[12];      // rows of [sR | t]
     __shared__ int sCnt;
     __shared__ DSim3 sSw1w2;
     const int h = blockIdx.x, tid = threadIdx.x;
-    float *Tout = A.T12 + (size_t)h * 16;
     if (tid == 0) {
         sCnt = 0;
-        float P1[3][3], P2[3][3];                                  // column i = correspondence i (:185-188)
-        for (int i = 0; i < 3; i++) {
-            const int idx = A.tri[h * 3 + i];
-            for (int r = 0; r < 3; r++) { P1[r][i] = A.X1[idx * 3 + r]; P2[r][i] = A.X2[idx * 3 + r]; }
-        }
-        float O1[3], O2[3], Pr1[3][3], Pr2[3][3];                  // ComputeCentroid :430-435
-        for (int r = 0; r < 3; r++) {
-            O1[r] = ((P1[r][0] + P1[r][1]) + P1[r][2]) / 3.f;
-            O2[r] = ((P2[r][0] + P2[r][1]) + P2[r][2]) / 3.f;
-            for (int i = 0; i < 3; i++) { Pr1[r][i] = P1[r][i] - O1[r]; Pr2[r][i] = P2[r][i] - O2[r]; }
-        }
-        float M[3][3];                                             // Pr2 * Pr1^T :453
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) M[r][c] = (Pr2[r][0] * Pr1[c][0] + Pr2[r][1] * Pr1[c][1]) + Pr2[r][2] * Pr1[c][2];
-        const double N11 = M[0][0] + M[1][1] + M[2][2], N12 = M[1][2] - M[2][1], N13 = M[2][0] - M[0][2], N14 = M[0][1] - M[1][0],
-                     N22 = M[0][0] - M[1][1] - M[2][2], N23 = M[0][1] + M[1][0], N24 = M[2][0] + M[0][2], N33 = -M[0][0] + M[1][1] - M[2][2],
-                     N34 = M[1][2] + M[2][1], N44 = -M[0][0] - M[1][1] + M[2][2];
-        // upstream stores N in a Matrix4f: the solver sees the float-rounded entries
-        double Nm[4][4] = {{(float)N11, (float)N12, (float)N13, (float)N14}, {(float)N12, (float)N22, (float)N23, (float)N24},
-                           {(float)N13, (float)N23, (float)N33, (float)N34}, {(float)N14, (float)N24, (float)N34, (float)N44}};
-        double q[4];
-        sym4_dominant_eigenvector(Nm, q);
-        const float e0 = (float)q[0];
-        float vec[3] = {(float)q[1], (float)q[2], (float)q[3]};
-        const float nrm = sqrtf((vec[0] * vec[0] + vec[1] * vec[1]) + vec[2] * vec[2]);
-        int valid = !(vec[0] == 0 && vec[1] == 0 && vec[2] == 0);   // :493-494 upstream keeps the previous iteration's transform
-        float R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, s12 = 1.f, t12[3] = {0, 0, 0};
-        if (valid) {
-            const double ang = atan2((double)nrm, (double)e0);
-            const float f = (float)(2 * ang);
-            for (int k = 0; k < 3; k++) vec[k] = vec[k] * f / nrm;   // angle-axis; the quaternion angle is the half
-            // Sophus::SO3f::exp(vec).matrix()
-            const float th2 = (vec[0] * vec[0] + vec[1] * vec[1]) + vec[2] * vec[2], th = sqrtf(th2), half = 0.5f * th;
-            float im, re;
-            if (th < 1e-5f) { const float th4 = th2 * th2; im = 0.5f - (1.f / 48.f) * th2 + (1.f / 3840.f) * th4; re = 1.f - (1.f / 8.f) * th2 + (1.f / 384.f) * th4; }
-            else { im = sinf(half) / th; re = cosf(half); }
-            const float qx = im * vec[0], qy = im * vec[1], qz = im * vec[2], qw = re;
-            const float tx = 2 * qx, ty = 2 * qy, tz = 2 * qz, twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx,
-                        tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
-            R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
-            R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
-            R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
-            if (!A.fixScale) {                                      // :503-520
-                double nom = 0, den = 0;
-                float P3[3][3];
-                for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) P3[r][c] = (R[r][0] * Pr2[0][c] + R[r][1] * Pr2[1][c]) + R[r][2] * Pr2[2][c];
-                float fn = 0, fd = 0;                               // Eigen's float array sums, column-major order
-                for (int c = 0; c < 3; c++) for (int r = 0; r < 3; r++) { fn += Pr1[r][c] * P3[r][c]; fd += P3[r][c] * P3[r][c]; }
-                nom = fn; den = fd;
-                s12 = (float)(nom / den);
-            }
-            for (int r = 0; r < 3; r++) {                           // mt12i = O1 - ms12i * mR12i * O2
-                const float ro = ((s12 * R[r][0]) * O2[0] + (s12 * R[r][1]) * O2[1]) + (s12 * R[r][2]) * O2[2];
-                t12[r] = O1[r] - ro;
-            }
-        }
-        const float sinv = (float)(1.0 / s12);
-        for (int r = 0; r < 3; r++) {
-            for (int c = 0; c < 3; c++) { sT12[r * 4 + c] = s12 * R[r][c]; sT21[r * 4 + c] = sinv * R[c][r]; }
-            sT12[r * 4 + 3] = t12[r];
-        }
-        for (int r = 0; r < 3; r++) sT21[r * 4 + 3] = -((sT21[r * 4 + 0] * t12[0] + sT21[r * 4 + 1] * t12[1]) + sT21[r * 4 + 2] * t12[2]);
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Tout[r * 3 + c] = R[r][c];
-        Tout[9] = t12[0]; Tout[10] = t12[1]; Tout[11] = t12[2]; Tout[12] = s12; Tout[13] = (float)valid; Tout[14] = 0; Tout[15] = 0;
+        float R[3][3], t12[3], s12;
+        sim3_minimal_solve(A.X1, A.X2, A.tri + h * 3, A.fixScale, sT12, sT21, A.T12 + (size_t)h * 16, R, t12, s12);
         if (A.total > 0) {                                          // :338-347
             double Rd[3][3];
             for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Rd[r][c] = (double)R[r][c];
@@ -149,22 +175,9 @@ __global__ __launch_bounds__(256) void k_sim3_ransac(RansacArgs A) {
         }
     }
     __syncthreads();
-    // CheckInliers :542-562 (float, as upstream)
-    const float fx1 = A.K1[0], fy1 = A.K1[1], cx1 = A.K1[2], cy1 = A.K1[3], fx2 = A.K2[0], fy2 = A.K2[1], cx2 = A.K2[2], cy2 = A.K2[3];
     int mine = 0;
     for (int i = tid; i < A.n; i += 256) {
-        const float *a = A.X1 + (size_t)i * 3, *b = A.X2 + (size_t)i * 3;
-        const float u1 = fx1 * a[0] / a[2] + cx1, v1 = fy1 * a[1] / a[2] + cy1;            // mvP1im1
-        const float u2 = fx2 * b[0] / b[2] + cx2, v2 = fy2 * b[1] / b[2] + cy2;            // mvP2im2
-        float p[3], r[3];
-        for (int k = 0; k < 3; k++) {
-            p[k] = ((sT12[k * 4] * b[0] + sT12[k * 4 + 1] * b[1]) + sT12[k * 4 + 2] * b[2]) + sT12[k * 4 + 3];   // point 2 in camera 1
-            r[k] = ((sT21[k * 4] * a[0] + sT21[k * 4 + 1] * a[1]) + sT21[k * 4 + 2] * a[2]) + sT21[k * 4 + 3];   // point 1 in camera 2
-        }
-        const float d1x = u1 - (fx1 * p[0] / p[2] + cx1), d1y = v1 - (fy1 * p[1] / p[2] + cy1);
-        const float d2x = (fx2 * r[0] / r[2] + cx2) - u2, d2y = (fy2 * r[1] / r[2] + cy2) - v2;
-        const float err1 = d1x * d1x + d1y * d1y, err2 = d2x * d2x + d2y * d2y;
-        const bool in = err1 < A.thr1[i] && err2 < A.thr2[i];
+        const bool in = sim3_check_inlier(A.K1, A.K2, sT12, sT21, A.X1 + (size_t)i * 3, A.X2 + (size_t)i * 3, A.thr1[i], A.thr2[i]);
         if (A.inl) A.inl[(size_t)h * A.n + i] = in;
         mine += in;
     }
@@ -212,7 +225,9 @@ struct Sim3Args {
     double *comp, *chi12, *chi21; uint8_t *on12, *on21;   // scratch
 };
 
-__global__ __launch_bounds__(256) void k_sim3_opt(Sim3Args A) {
+// The whole optimisation of one problem by one 256-thread workgroup: k_sim3_opt hands it the kernel's own argument block, k_sim3_opt_batch
+// (sim3_batch.inc) the entry of its problem table.  Same text, same order of every sum, same bytes.
+__device__ __forceinline__ void sim3_opt_run(const Sim3Args &A) {
     __shared__ double red[5 * 64];
     const int tid = threadIdx.x, n = A.n, np = A.world ? A.nPairs : 1;
     const DCam cam1{A.K1[0], A.K1[1], A.K1[2], A.K1[3]}, cam2{A.K2[0], A.K2[1], A.K2[2], A.K2[3]};
@@ -400,3 +415,5 @@ __global__ __launch_bounds__(256) void k_sim3_opt(Sim3Args A) {
     block_sum<1>(in, red);
     if (tid == 0) { sim3_to8(est, A.Sout); A.res[0] = (int)in[0]; A.res[1] = nBad; A.res[2] = 0; }
 }
+
+__global__ __launch_bounds__(256) void k_sim3_opt(Sim3Args A) { sim3_opt_run(A); }

@@ -3,7 +3,8 @@
 // with SearchByBoW(KF, KF) and the match vectors are folded into vpMatchedPoints / vpKeyFrameMatchedMP.  All candidates, all members and the folds
 // go to the GPU in one call (include/rumi_match.h: rumi_common_regions_bow); this side applies the checks that need no device, marshals the
 // key-frames and hands back, per candidate, what the loop body from :655 on reads.  That body (the Sim3 solver, the two SearchByProjection passes,
-// OptimizeSim3, the covisible check) stays where it is; its SearchByProjection passes and the covisible check have one-call members below.
+// OptimizeSim3, the covisible check) stays where it is; its SearchByProjection passes and the covisible check have one-call members below, the
+// Sim3 solvers and OptimizeSim3 of all candidates in PlaceRecognitionStages.h (Sim3RansacStage, OptimizeSim3Stage).
 //
 // Templated on the key-frame, map-point and matcher types, so that it instantiates against the reference's classes and against the stand-ins of
 // tests/cpp.  Mono key-frames only.
@@ -15,6 +16,8 @@
 // and the SearchByProjection(KF, Scw, ...) searches of DetectCommonRegionsFromBoW (:716, :738, the covisible check :773-795) become
 //     step.SearchByProjectionResident(graph, jobs);                  // one Sim3ProjectionJob per call of the reference's member
 //     step.CovisibleCheckResident(graph, pCurrentKF, pMostBoWMatchesKF, gScw, vpCurrentCovKFs, vpMapPoints, &nNumKFs, Converter::toSophus);
+//     step.CovisibleCheckResident(graph, pCurrentKF, candidates, vpCurrentCovKFs, Converter::toSophus);   // several candidates, one call
+//     step.DetectCommonRegionsFromBoWResident(graph, pCurrentKF, vpBowCand, spConnectedKeyFrames, matcherBoW, mbFixScale, false, thresholds, ...);   // the whole function
 // (at the end of this header).
 #pragma once
 #include <cstdint>
@@ -58,13 +61,13 @@ template <class FeatVecT> inline void csr(const FeatVecT &fv, Member &m) {      
 // matcherBoW: the caller's ORBmatcher(0.9, true) (:555, facade/ORBmatcher.h): its ratio and orientation flag are read through NNRatio() /
 // CheckOrientation(), and the call runs on its per-thread arena (the call's own blocks grow on demand; should a member's FeatureVector node exceed what
 // the batch kernel holds, the library runs single searches on that arena, which grows as for ORBmatcher's own calls).
+// spConnectedKeyFrames: mpCurrentKF->GetConnectedKeyFrames() as :551 takes it once for the whole function; the overload without it asks the key-frame.
 template <class KeyFrameT, class MapPointT, class MatcherT>
-int CommonRegionsBoWStage(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpBowCand, int nNumCovisibles, const MatcherT &matcherBoW,
-                          std::vector<BowStageResult<KeyFrameT, MapPointT>> &out) {
+int CommonRegionsBoWStage(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpBowCand, const std::set<KeyFrameT *> &spConnectedKeyFrames, int nNumCovisibles,
+                          const MatcherT &matcherBoW, std::vector<BowStageResult<KeyFrameT, MapPointT>> &out) {
     namespace D = loopclosing_detail;
     static const char *where = "LoopClosingStep::CommonRegionsBoWStage / rumi_common_regions_bow";
     out.clear();
-    const std::set<KeyFrameT *> spConnectedKeyFrames = pCurrentKF->GetConnectedKeyFrames();
     const std::vector<MapPointT *> vpCurrentMPs = pCurrentKF->GetMapPointMatches();
     bool twoCameras = pCurrentKF->NLeft != -1;
 
@@ -178,6 +181,12 @@ int CommonRegionsBoWStage(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> 
     }
     return (int)out.size();
 }
+template <class KeyFrameT, class MapPointT, class MatcherT>
+int CommonRegionsBoWStage(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpBowCand, int nNumCovisibles, const MatcherT &matcherBoW,
+                          std::vector<BowStageResult<KeyFrameT, MapPointT>> &out) {
+    const std::set<KeyFrameT *> spConnectedKeyFrames = pCurrentKF->GetConnectedKeyFrames();
+    return CommonRegionsBoWStage(pCurrentKF, vpBowCand, spConnectedKeyFrames, nNumCovisibles, matcherBoW, out);
+}
 
 }  // namespace rumi_facade
 
@@ -188,6 +197,7 @@ int CommonRegionsBoWStage(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> 
 #include <utility>
 
 #include "ORBmatcher.h"
+#include "PlaceRecognitionStages.h"
 #include "rumi_mapping.h"
 
 namespace RUMI_FACADE_NAMESPACE {
@@ -324,9 +334,35 @@ public:
     template <class GraphT, class KeyFrameT, class MapPointT, class G2oSim3T, class ToSophusT>
     int CovisibleCheckResident(GraphT &graph, KeyFrameT *pCurrentKF, KeyFrameT *pMostBoWMatchesKF, const G2oSim3T &gScw,
                                const std::vector<KeyFrameT *> &vpCurrentCovKFs, std::vector<MapPointT *> &vpMapPoints, int *nNumKFs, ToSophusT toSophus) {
-        if (vpCurrentCovKFs.empty()) return 0;
-        std::vector<MapPointT *> vpList;                                            // :871-905
-        {
+        std::vector<CovisibleCheckCandidate<KeyFrameT, MapPointT, G2oSim3T>> one(1, CovisibleCheckCandidate<KeyFrameT, MapPointT, G2oSim3T>{pMostBoWMatchesKF, gScw, &vpMapPoints, nNumKFs, 0});
+        if (CovisibleCheckResident(graph, pCurrentKF, one, vpCurrentCovKFs, toSophus) < 0) return -1;
+        return one[0].visited;
+    }
+
+    // The same loop for SEVERAL candidates that reached :768 (each with its own pMostBoWMatchesKF and gScw): the covisibles of the current key-frame
+    // are the same for all of them, so every (candidate, covisible) search is a job of ONE device call, each candidate's list sent once; then
+    // `nNumKFs < 3` is replayed per candidate over its counts.  Per candidate what the single member leaves: *vpMapPoints, *nNumKFs, and `visited`
+    // = the covisibles its loop visited.  A candidate that arrives with nNumKFs >= 3 visits nothing: no list is built and nothing is searched for
+    // it.  Returns the number of candidates, or -1 with a report and every candidate untouched (`visited` included).
+    template <class KeyFrameT, class MapPointT, class G2oSim3T> struct CovisibleCheckCandidate {
+        KeyFrameT *pMostBoWMatchesKF;
+        G2oSim3T gScw;
+        std::vector<MapPointT *> *vpMapPoints;
+        int *nNumKFs;
+        int visited;
+    };
+    template <class GraphT, class KeyFrameT, class MapPointT, class G2oSim3T, class ToSophusT>
+    int CovisibleCheckResident(GraphT &graph, KeyFrameT *pCurrentKF, std::vector<CovisibleCheckCandidate<KeyFrameT, MapPointT, G2oSim3T>> &candidates,
+                               const std::vector<KeyFrameT *> &vpCurrentCovKFs, ToSophusT toSophus) {
+        const size_t nK = candidates.size(), nC = vpCurrentCovKFs.size();
+        std::vector<uint8_t> runs(nK, 0);                                            // the candidates whose loop has anything to visit
+        bool any = false;
+        for (size_t k = 0; k < nK; k++) { runs[k] = nC > 0 && *candidates[k].nNumKFs < 3; any = any || runs[k]; }
+        if (!any) { for (auto &c : candidates) c.visited = 0; return (int)nK; }
+        std::vector<std::vector<MapPointT *>> vpLists(nK);                           // :871-905 per candidate
+        for (size_t k = 0; k < nK; k++) {
+            if (!runs[k]) continue;
+            KeyFrameT *pMostBoWMatchesKF = candidates[k].pMostBoWMatchesKF;
             int nNumCovisibles = 10;
             std::vector<KeyFrameT *> vpCovKFm = pMostBoWMatchesKF->GetBestCovisibilityKeyFrames(nNumCovisibles);
             int nInitialCov = vpCovKFm.size();
@@ -341,35 +377,136 @@ public:
             for (KeyFrameT *pKFi : vpCovKFm) {
                 for (MapPointT *pMPij : pKFi->GetMapPointMatches()) {
                     if (!pMPij || pMPij->isBad()) continue;
-                    if (spMapPoints.find(pMPij) == spMapPoints.end()) { spMapPoints.insert(pMPij); vpList.push_back(pMPij); }
+                    if (spMapPoints.find(pMPij) == spMapPoints.end()) { spMapPoints.insert(pMPij); vpLists[k].push_back(pMPij); }
                 }
             }
         }
-        const size_t nC = vpCurrentCovKFs.size();
-        std::vector<std::vector<MapPointT *>> vvpMatched(nC);
-        std::vector<int> num(nC, 0);
+        std::vector<std::vector<MapPointT *>> vvpMatched(nK * nC);
+        std::vector<int> num(nK * nC, 0);
         std::vector<Sim3ProjectionJob<KeyFrameT, MapPointT>> jobs;
-        for (size_t j = 0; j < nC; j++) {
-            KeyFrameT *pKFj = vpCurrentCovKFs[j];
-            const Sophus::SE3f Tjc = pKFj->GetPose() * pCurrentKF->GetPoseInverse();         // :779: .cast<double>() widens each component
-            const auto q = Tjc.unit_quaternion(); const auto t = Tjc.translation();
-            G2oSim3T gSjc(Eigen::Quaterniond((double)q.w(), (double)q.x(), (double)q.y(), (double)q.z()), Eigen::Vector3d((double)t(0), (double)t(1), (double)t(2)), 1.0);
-            G2oSim3T gSjw = gSjc * gScw;
-            jobs.push_back(Sim3ProjectionJob<KeyFrameT, MapPointT>{pKFj, toSophus(gSjw), &vpList, nullptr, 3, 1.5f, &vvpMatched[j], nullptr, &num[j]});
-        }
+        for (size_t k = 0; k < nK; k++)
+            for (size_t j = 0; runs[k] && j < nC; j++) {
+                KeyFrameT *pKFj = vpCurrentCovKFs[j];
+                const Sophus::SE3f Tjc = pKFj->GetPose() * pCurrentKF->GetPoseInverse();     // :779: .cast<double>() widens each component
+                const auto q = Tjc.unit_quaternion(); const auto t = Tjc.translation();
+                G2oSim3T gSjc(Eigen::Quaterniond((double)q.w(), (double)q.x(), (double)q.y(), (double)q.z()), Eigen::Vector3d((double)t(0), (double)t(1), (double)t(2)), 1.0);
+                G2oSim3T gSjw = gSjc * candidates[k].gScw;
+                jobs.push_back(Sim3ProjectionJob<KeyFrameT, MapPointT>{pKFj, toSophus(gSjw), &vpLists[k], nullptr, 3, 1.5f, &vvpMatched[k * nC + j], nullptr, &num[k * nC + j]});
+            }
         if (SearchByProjectionResident(graph, jobs) < 0) return -1;
-        size_t j = 0;                                                               // :775-795 over the counts
-        int n = *nNumKFs;
-        while (n < 3 && j < nC) {
-            if (num[j] >= 30) n++;                                                  // :860-863
-            j++;
+        for (size_t k = 0; k < nK; k++) {
+            if (!runs[k]) { candidates[k].visited = 0; continue; }
+            size_t j = 0;                                                           // :775-795 over the counts
+            int n = *candidates[k].nNumKFs;
+            while (n < 3 && j < nC) {
+                if (num[k * nC + j] >= 30) n++;                                     // :860-863
+                j++;
+            }
+            if (j > 0) *candidates[k].vpMapPoints = vpLists[k];                     // every visited covisible leaves the same list
+            *candidates[k].nNumKFs = n;
+            candidates[k].visited = (int)j;
         }
-        if (j > 0) vpMapPoints = vpList;                                            // every visited covisible leaves the same list
-        *nNumKFs = n;
-        return (int)j;
+        return (int)nK;
+    }
+
+    // ---- LoopClosing::DetectCommonRegionsFromBoW (LoopClosing.cc:542-853; CloudMerging.cc:1019 ff. is the same text) stage by stage over the members
+    // above and PlaceRecognitionStages.h: (1) CommonRegionsBoWStage, (2) Sim3RansacStage, (3) :716 of every candidate whose solver converged,
+    // (4) OptimizeSim3Stage for numProjMatches >= nProjMatches, (5) :738 for numOptMatches >= nSim3Inliers, (6) the covisible check of every
+    // candidate with numProjOptMatches >= nProjOptMatches, (7) the replay of :802-810 in candidate order (strict `<`: the first candidate wins a
+    // tie) and :824-841 with SetNotErase().  Six device calls (more only when the RANSAC needs another round) whatever the number of candidates;
+    // they are separate calls, not a fused kernel.  The outputs are the reference's reference parameters and are written at :824-841 only.
+    // bInertialWithoutBA2: `mpTracker->mSensor == System::IMU_MONOCULAR && !GetIniertialBA2()` of :659 / :724 -- not built: refused.
+    // Returns 1 / 0 = the function's true / false, or -1 with a report and every output untouched: that case, NLeft != -1, the refusals of the
+    // members it calls.  (rand() has moved by then if the RANSAC stage ran.)
+    struct PlaceRecognitionThresholds { int nBoWMatches = 20, nBoWInliers = 15, nSim3Inliers = 20, nProjMatches = 50, nProjOptMatches = 80, nNumCovisibles = 10; };
+    template <class GraphT, class KeyFrameT, class MapPointT, class MatcherT, class G2oSim3T, class ToSophusT>
+    int DetectCommonRegionsFromBoWResident(GraphT &graph, KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpBowCand, const std::set<KeyFrameT *> &spConnectedKeyFrames,
+                                           const MatcherT &matcherBoW, bool mbFixScale, bool bInertialWithoutBA2, const PlaceRecognitionThresholds &th,
+                                           KeyFrameT *&pMatchedKF2, KeyFrameT *&pLastCurrentKF, G2oSim3T &g2oScw, int &nNumCoincidences, std::vector<MapPointT *> &vpMPs,
+                                           std::vector<MapPointT *> &vpMatchedMPs, ToSophusT toSophus) {
+        static const char *where = "LoopClosingStep::DetectCommonRegionsFromBoWResident";
+        if (bInertialWithoutBA2) { rumi_facade::report(where, RUMI_E_INVALID, "IMU_MONOCULAR before the second inertial BA is not built; nothing was searched"); return -1; }
+        if (pCurrentKF->NLeft != -1) { rumi_facade::report(where, RUMI_E_INVALID, "a key-frame with NLeft != -1: only the monocular path is built; nothing was searched"); return -1; }
+        std::vector<rumi_facade::BowStageResult<KeyFrameT, MapPointT>> bow;                            // (1) :576-651
+        if (rumi_facade::CommonRegionsBoWStage(pCurrentKF, vpBowCand, spConnectedKeyFrames, th.nNumCovisibles, matcherBoW, bow) < 0) return -1;
+        std::vector<rumi_facade::Sim3RansacOutcome> ransac;                                            // (2) :655-676
+        if (rumi_facade::Sim3RansacStage(pCurrentKF, bow, mbFixScale, th.nBoWMatches, th.nBoWInliers, ransac) < 0) return -1;
+        struct Cand {
+            KeyFrameT *pKFi;
+            G2oSim3T gScm, gScw;
+            std::vector<MapPointT *> vpMapPoints, vpMatchedMP, vpMatchedMP2;
+            std::vector<KeyFrameT *> vpKeyFrames, vpMatchedKF;
+            int numProjMatches = 0, numOptMatches = 0, numProjOptMatches = 0, nNumKFs = 0;
+        };
+        std::vector<Cand> cs;
+        cs.reserve(bow.size());                                                                        // the jobs below point into it
+        using Job = Sim3ProjectionJob<KeyFrameT, MapPointT>;
+        std::vector<Job> jobs;
+        for (size_t k = 0; k < bow.size(); k++) {                                                      // :676-716
+            if (!ransac[k].bConverge) continue;
+            cs.emplace_back();
+            Cand &c = cs.back();
+            c.pKFi = bow[k].pKFi;
+            KeyFrameT *pMostBoWMatchesKF = c.pKFi;
+            std::vector<KeyFrameT *> vpCovKFi = pMostBoWMatchesKF->GetBestCovisibilityKeyFrames(th.nNumCovisibles);
+            vpCovKFi.push_back(pMostBoWMatchesKF);
+            std::set<MapPointT *> spMapPoints;
+            for (KeyFrameT *pCovKFi : vpCovKFi)
+                for (MapPointT *pCovMPij : pCovKFi->GetMapPointMatches()) {
+                    if (!pCovMPij || pCovMPij->isBad()) continue;
+                    if (spMapPoints.find(pCovMPij) == spMapPoints.end()) { spMapPoints.insert(pCovMPij); c.vpMapPoints.push_back(pCovMPij); c.vpKeyFrames.push_back(pCovKFi); }
+                }
+            Eigen::Matrix3f R; Eigen::Vector3f t;
+            for (int r = 0; r < 3; r++) { for (int q = 0; q < 3; q++) R(r, q) = ransac[k].R[r * 3 + q]; t(r) = ransac[k].t[r]; }
+            c.gScm = G2oSim3T(R.template cast<double>(), t.template cast<double>(), (double)ransac[k].s);                                        // :706-708
+            const G2oSim3T gSmw(pMostBoWMatchesKF->GetRotation().template cast<double>(), pMostBoWMatchesKF->GetTranslation().template cast<double>(), 1.0);
+            c.gScw = c.gScm * gSmw;
+            jobs.push_back(Job{pCurrentKF, toSophus(c.gScw), &c.vpMapPoints, &c.vpKeyFrames, 8, 1.5f, &c.vpMatchedMP, &c.vpMatchedKF, &c.numProjMatches});
+        }
+        if (SearchByProjectionResident(graph, jobs) < 0) return -1;                                    // (3) :716
+        std::vector<rumi_facade::OptimizeSim3Job<KeyFrameT, MapPointT, G2oSim3T>> opt;
+        for (Cand &c : cs)
+            if (c.numProjMatches >= th.nProjMatches) opt.push_back(rumi_facade::OptimizeSim3Job<KeyFrameT, MapPointT, G2oSim3T>{pCurrentKF, c.pKFi, &c.vpMatchedMP, &c.gScm, 10.f, mbFixScale, true, &c.numOptMatches});
+        if (rumi_facade::OptimizeSim3Stage(opt) < 0) return -1;                                        // (4) :728
+        jobs.clear();
+        for (Cand &c : cs) {
+            if (c.numProjMatches < th.nProjMatches || c.numOptMatches < th.nSim3Inliers) continue;
+            const G2oSim3T gSmw(c.pKFi->GetRotation().template cast<double>(), c.pKFi->GetTranslation().template cast<double>(), 1.0);                    // :731-733
+            c.gScw = c.gScm * gSmw;
+            jobs.push_back(Job{pCurrentKF, toSophus(c.gScw), &c.vpMapPoints, nullptr, 5, 1.0f, &c.vpMatchedMP2, nullptr, &c.numProjOptMatches});
+        }
+        if (SearchByProjectionResident(graph, jobs) < 0) return -1;                                    // (5) :738
+        std::vector<CovisibleCheckCandidate<KeyFrameT, MapPointT, G2oSim3T>> covis;
+        std::vector<Cand *> reached;
+        for (Cand &c : cs)
+            if (c.numProjMatches >= th.nProjMatches && c.numOptMatches >= th.nSim3Inliers && c.numProjOptMatches >= th.nProjOptMatches) {
+                covis.push_back(CovisibleCheckCandidate<KeyFrameT, MapPointT, G2oSim3T>{c.pKFi, c.gScw, &c.vpMapPoints, &c.nNumKFs, 0});
+                reached.push_back(&c);
+            }
+        const std::vector<KeyFrameT *> vpCurrentCovKFs = pCurrentKF->GetBestCovisibilityKeyFrames(th.nNumCovisibles);                                   // :773
+        if (CovisibleCheckResident(graph, pCurrentKF, covis, vpCurrentCovKFs, toSophus) < 0) return -1;                                                // (6) :775-795
+        int nBestMatchesReproj = 0, nBestNumCoindicendes = 0;                                          // (7) :802-810
+        Cand *best = nullptr;
+        for (Cand *c : reached)
+            if (nBestMatchesReproj < c->numProjOptMatches) { nBestMatchesReproj = c->numProjOptMatches; nBestNumCoindicendes = c->nNumKFs; best = c; }
+        if (nBestMatchesReproj > 0) {                                                                  // :824-841
+            pLastCurrentKF = pCurrentKF;
+            nNumCoincidences = nBestNumCoindicendes;
+            pMatchedKF2 = best->pKFi;
+            set_not_erase(pMatchedKF2, 0);
+            g2oScw = best->gScw;
+            vpMPs = best->vpMapPoints;
+            vpMatchedMPs = best->vpMatchedMP2;
+            return nNumCoincidences >= 3 ? 1 : 0;
+        }
+        return 0;
     }
 
 protected:
+    // pKF->SetNotErase() where the data model has the member (the reference's KeyFrame does), else its flag
+    template <class K> static auto set_not_erase(K *k, int) -> decltype(k->SetNotErase(), void()) { k->SetNotErase(); }
+    template <class K> static void set_not_erase(K *k, long) { k->mbNotErase = true; }
+
     template <class Sim3T, class GraphT, class KeyFrameT, class MapPointT>
     int saf_dispatch(GraphT &graph, const std::vector<KeyFrameT *> &vConectedKFs, std::vector<MapPointT *> &vpMapPoints, int *nSearchedAgain, std::true_type) {
         std::vector<std::pair<KeyFrameT *, Sim3T>> poses;

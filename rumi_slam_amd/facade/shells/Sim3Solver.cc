@@ -24,26 +24,13 @@
 #define RUMI_FACADE_NAMESPACE rumi_facade_impl
 #endif
 #include "../Sim3Scoring.h"      // rumi_facade::ComputeInliersNum + the optimiser arena (this repository)
+#include "../RandLookahead.h"
+#include "../Sim3SolverGather.h"
 
 namespace ORB_SLAM3 {
 
 namespace {
-// glibc's process-wide generator, copied: random_r on the copy gives the values rand() is about to give
-struct RandLookahead {
-    int32_t table[32];
-    char scratch[128], dummy[128];
-    struct random_data rd;
-    RandLookahead() {
-        char *prev = initstate(1u, scratch, sizeof scratch);      // the global generator moves onto `scratch`; glibc returns its own state array,
-        std::memcpy(table, prev, sizeof table);                    // word 0 of which now encodes the position it had reached
-        setstate(prev);                                            // ... and resumes exactly there
-        std::memset(&rd, 0, sizeof rd);
-        initstate_r(1u, dummy, sizeof dummy, &rd);
-        setstate_r(reinterpret_cast<char *>(table), &rd);
-    }
-    int next() { int32_t v = 0; random_r(&rd, &v); return (int)v; }
-    int RandomInt(int min, int max) { const int d = max - min + 1; return int(((double)next() / ((double)RAND_MAX + 1.0)) * d) + min; }   // DUtils/Random.cpp:47-50
-};
+using rumi_facade::RandLookahead;   // glibc's process-wide generator, copied (../RandLookahead.h, shared with Sim3RansacStage)
 
 inline size_t float_bits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return (size_t)u; }
 inline float bits_float(size_t s) { const uint32_t u = (uint32_t)s; float f; std::memcpy(&f, &u, 4); return f; }
@@ -65,38 +52,23 @@ Sim3Solver::Sim3Solver() {}
 Sim3Solver::Sim3Solver(KeyFrame *pKF1, KeyFrame *pKF2, const std::vector<MapPoint *> &vpMatched12, const bool bFixScale,
                        std::vector<KeyFrame *> vpKeyFrameMatchedMP)
     : mnIterations(0), mnBestInliers(0), mbFixScale(bFixScale), pCamera1(pKF1->mpCamera), pCamera2(pKF2->mpCamera) {
-    bool bDifferentKFs = true;
-    if (vpKeyFrameMatchedMP.empty()) { bDifferentKFs = false; vpKeyFrameMatchedMP = std::vector<KeyFrame *>(vpMatched12.size(), pKF2); }
     mpKF1 = pKF1; mpKF2 = pKF2;
     const std::vector<MapPoint *> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
-    mN1 = (int)vpMatched12.size();
     mvpMatches12 = vpMatched12;
-    const Eigen::Matrix3f Rcw1 = pKF1->GetRotation(), Rcw2 = pKF2->GetRotation();
-    const Eigen::Vector3f tcw1 = pKF1->GetTranslation(), tcw2 = pKF2->GetTranslation();
-    size_t idx = 0;
-    KeyFrame *pKFm = pKF2;
-    for (int i1 = 0; i1 < mN1; i1++) {                               // :78-126
-        if (!vpMatched12[i1]) continue;
-        MapPoint *pMP1 = vpKeyFrameMP1[i1], *pMP2 = vpMatched12[i1];
-        if (!pMP1) continue;
-        if (pMP1->isBad() || pMP2->isBad()) continue;
-        if (bDifferentKFs) pKFm = vpKeyFrameMatchedMP[i1];
-        const int indexKF1 = std::get<0>(pMP1->GetIndexInKeyFrame(pKF1)), indexKF2 = std::get<0>(pMP2->GetIndexInKeyFrame(pKFm));
-        if (indexKF1 < 0 || indexKF2 < 0) continue;
-        const cv::KeyPoint &kp1 = pKF1->mvKeysUn[indexKF1];
-        const cv::KeyPoint &kp2 = pKFm->mvKeysUn[indexKF2];
-        const float sigmaSquare1 = pKF1->mvLevelSigma2[kp1.octave], sigmaSquare2 = pKFm->mvLevelSigma2[kp2.octave];
-        mvnMaxError1.push_back(9.210 * sigmaSquare1);
-        mvnMaxError2.push_back(9.210 * sigmaSquare2);
-        mvSigmaSquare1.push_back(float_bits(sigmaSquare1));           // (declared by the reference, unused there: holds the float's bits for the device call)
-        mvSigmaSquare2.push_back(float_bits(sigmaSquare2));
-        mvpMapPoints1.push_back(pMP1); mvpMapPoints2.push_back(pMP2);
+    rumi_facade::Sim3Correspondences c;                              // :78-126 (../Sim3SolverGather.h, shared with Sim3RansacStage)
+    rumi_facade::sim3_solver_gather(pKF1, pKF2, vpMatched12, vpKeyFrameMatchedMP, c);
+    mN1 = c.mN1;
+    for (size_t k = 0; k < c.indices1.size(); k++) {
+        const size_t i1 = c.indices1[k];
+        mvnMaxError1.push_back(9.210 * c.sigma2_1[k]);
+        mvnMaxError2.push_back(9.210 * c.sigma2_2[k]);
+        mvSigmaSquare1.push_back(float_bits(c.sigma2_1[k]));         // (declared by the reference, unused there: holds the float's bits for the device call)
+        mvSigmaSquare2.push_back(float_bits(c.sigma2_2[k]));
+        mvpMapPoints1.push_back(vpKeyFrameMP1[i1]); mvpMapPoints2.push_back(vpMatched12[i1]);
         mvnIndices1.push_back(i1);
-        const Eigen::Vector3f X3D1w = pMP1->GetWorldPos(), X3D2w = pMP2->GetWorldPos();
-        mvX3Dc1.push_back(Rcw1 * X3D1w + tcw1);
-        mvX3Dc2.push_back(Rcw2 * X3D2w + tcw2);
-        mvAllIndices.push_back(idx);
-        idx++;
+        mvX3Dc1.push_back(Eigen::Vector3f(c.X1[3 * k], c.X1[3 * k + 1], c.X1[3 * k + 2]));
+        mvX3Dc2.push_back(Eigen::Vector3f(c.X2[3 * k], c.X2[3 * k + 1], c.X2[3 * k + 2]));
+        mvAllIndices.push_back(k);
     }
     // mvP1im1 / mvP2im2 (:128-129) are re-projected on the device by every launch
     SetRansacParameters();
@@ -183,7 +155,7 @@ Eigen::Matrix4f Sim3Solver::iterate(int nIterations, bool &bNoMore, std::vector<
     }
     for (int h = 0; h < count; h++) {
         mnIterations++;
-        for (int k = 0; k < 3; k++) (void)rand();                     // the real generator follows, three draws per iteration upstream really runs
+        rumi_facade::rand_advance(1);                                 // the real generator follows, three draws per iteration upstream really runs
         RUMI_TAKE_HYPOTHESIS(B, h);
         if (mnInliersi >= mnBestInliers) {
             RUMI_TAKE_BEST();
@@ -212,7 +184,7 @@ Eigen::Matrix4f Sim3Solver::iterate(int nIterations, bool &bNoMore, std::vector<
     Eigen::Matrix4f bestSim3 = Eigen::Matrix4f::Identity();           // (upstream returns an uninitialised matrix when no iteration improved)
     for (int h = 0; h < count; h++) {
         mnIterations++;
-        for (int k = 0; k < 3; k++) (void)rand();
+        rumi_facade::rand_advance(1);
         RUMI_TAKE_HYPOTHESIS(B, h);
         if (mnInliersi >= mnBestInliers) {
             RUMI_TAKE_BEST();
@@ -279,7 +251,7 @@ Eigen::Matrix4f Sim3Solver::iterate(int nIterations, bool &bNoMore, std::vector<
     Eigen::Matrix4f bestSim3 = Eigen::Matrix4f::Identity();
     for (int h = 0; h < count; h++) {
         mnIterations++;
-        for (int k = 0; k < 3; k++) (void)rand();
+        rumi_facade::rand_advance(1);
         RUMI_TAKE_HYPOTHESIS(B, h);
         const float InliersRatio = denom.empty() ? 0.f : B.median[h];   // ComputeInliersNum returns 0 without key-frame pairs
         if (InliersRatio >= bestRatio && mnInliersi >= mnBestInliers) {

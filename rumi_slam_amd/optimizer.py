@@ -15,6 +15,15 @@ class RumiSim3ScoreSet(C.Structure):
 
 OPT_SYMBOLS = capi.OPT_SYMBOLS          # one list: every entry of include/rumi_opt.h
 
+# include/rumi_opt.h: RumiSim3RansacSolver, RumiSim3RansacResult, RumiSim3OptProblem
+SIM3_RANSAC_SOLVER_DTYPE = np.dtype([("first", "<i4"), ("n", "<i4"), ("min_inliers", "<i4"), ("its_left", "<i4"), ("fix_scale", "<i4"),
+                                     ("K4_1", "<f4", 4), ("K4_2", "<f4", 4)])
+SIM3_RANSAC_RESULT_DTYPE = np.dtype([("state", "<i4"), ("its", "<i4"), ("hyp", "<i4"), ("n_inliers", "<i4"), ("T12", "<f4", 16)])
+SIM3_OPT_PROBLEM_DTYPE = np.dtype([("first", "<i4"), ("n", "<i4"), ("th2", "<f4"), ("fix_scale", "<i4"), ("robust_first_pass", "<i4"),
+                                   ("K4_1", "<f4", 4), ("K4_2", "<f4", 4)])
+assert SIM3_RANSAC_SOLVER_DTYPE.itemsize == 52 and SIM3_RANSAC_RESULT_DTYPE.itemsize == 80 and SIM3_OPT_PROBLEM_DTYPE.itemsize == 52
+SIM3_NOT_REACHED, SIM3_CONVERGED, SIM3_EXHAUSTED, SIM3_WINDOW_ENDED = 0, 1, 2, 3
+
 
 def _lib():
     L = capi.lib()
@@ -39,6 +48,8 @@ def _lib():
     L.rumi_optimize_sim3.argtypes = [vp, i32, vp, i32] + [vp] * 12 + [C.c_float, i32, i32, vp, vp, vp]
     L.rumi_essential_graph.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]
     L.rumi_sim3_correct_points.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp]
+    L.rumi_sim3_ransac_batch.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.rumi_optimize_sim3_batch.argtypes = [vp, i32, vp, i32] + [vp] * 9
     L._opt_ready = True
     return L
 
@@ -207,6 +218,48 @@ class Optimizer:
         capi.check(self._lib.rumi_optimize_sim3(self._h, n, P(po), len(A) if world else 0, P(A), P(B), P(P1c), P(P2c), P(obs1), P(obs2), P(w1), P(w2),
                                                 P(s12), P(s21), P(K1), P(K2), float(th2), int(fix_scale), int(robust_first_pass), P(S), P(status), P(res)))
         return int(res[0]), int(res[1]), bool(res[2]), S, status[:n]
+
+    def Sim3RansacBatch(self, solvers, X3Dc1, X3Dc2, sigma2_1, sigma2_2, triples, want_all=False):
+        """One window of the shared iteration stream over J solvers of Sim3Solver::iterate(..., bConverge) (include/rumi_opt.h,
+        rumi_sim3_ransac_batch).  solvers: records of SIM3_RANSAC_SOLVER_DTYPE over the concatenated correspondences; triples [J, R, 3] = the
+        window drawn with every solver's own N (GlibcRand.draw_window), indices relative to the solver's first.
+        Returns dict(state [J], its [J], hyp [J], n_inliers [J], T12 [J,16], inliers [n_total] bool, and with want_all n_inliers_all [J,R],
+        T12_all [J,R,16])."""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        sol = np.ascontiguousarray(solvers, SIM3_RANSAC_SOLVER_DTYPE)
+        X1, X2, s1, s2 = f32(X3Dc1).reshape(-1, 3), f32(X3Dc2).reshape(-1, 3), f32(sigma2_1), f32(sigma2_2)
+        J, n = len(sol), len(X1)
+        tri = np.ascontiguousarray(triples, np.int32).reshape(J, -1, 3)
+        R = tri.shape[1]
+        if not (len(X2) == len(s1) == len(s2) == n):
+            raise ValueError("Sim3RansacBatch: array lengths disagree")
+        res = np.zeros(max(J, 1), SIM3_RANSAC_RESULT_DTYPE); inl = np.zeros(max(n, 1), np.uint8)
+        nall = np.zeros((max(J, 1), max(R, 1)), np.int32) if want_all else None
+        Tall = np.zeros((max(J, 1), max(R, 1), 16), np.float32) if want_all else None
+        P = lambda a: None if a is None else capi.ptr(a)
+        capi.check(self._lib.rumi_sim3_ransac_batch(self._h, J, P(sol), n, P(X1), P(X2), P(s1), P(s2), R, P(tri), P(res), P(inl), P(nall), P(Tall)))
+        res = res[:J]
+        out = dict(state=res["state"].copy(), its=res["its"].copy(), hyp=res["hyp"].copy(), n_inliers=res["n_inliers"].copy(), T12=res["T12"].copy(),
+                   inliers=inl[:n].astype(bool))
+        if want_all:
+            out.update(n_inliers_all=nall[:J, :R], T12_all=Tall[:J, :R])
+        return out
+
+    def OptimizeSim3Batch(self, problems, S8, P1c, P2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2):
+        """Optimizer::OptimizeSim3 of J candidates in one call (include/rumi_opt.h, rumi_optimize_sim3_batch).  problems: records of
+        SIM3_OPT_PROBLEM_DTYPE over the concatenated correspondences; S8 [J,8] the initial estimates.
+        Returns (result3 [J,3] = nIn, nBad, early; S8 [J,8]; status [n_total])."""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        pr = np.ascontiguousarray(problems, SIM3_OPT_PROBLEM_DTYPE)
+        P1c, P2c, obs1, obs2, w1, w2 = f32(P1c).reshape(-1, 3), f32(P2c).reshape(-1, 3), f32(obs1).reshape(-1, 2), f32(obs2).reshape(-1, 2), f32(inv_sigma2_1), f32(inv_sigma2_2)
+        J, n = len(pr), len(w1)
+        S = np.ascontiguousarray(S8, np.float64).reshape(-1, 8).copy()
+        if len(S) != J or not (len(P1c) == len(P2c) == len(obs1) == len(obs2) == len(w2) == n):
+            raise ValueError("OptimizeSim3Batch: array lengths disagree")
+        status = np.zeros(max(n, 1), np.uint8); res = np.zeros((max(J, 1), 3), np.int32)
+        P = capi.ptr
+        capi.check(self._lib.rumi_optimize_sim3_batch(self._h, J, P(pr), n, P(P1c), P(P2c), P(obs1), P(obs2), P(w1), P(w2), P(S), P(status), P(res)))
+        return res[:J], S, status[:n]
 
     def essential_graph(self, S8, fixed, fix_scale, e_v0, e_v1, meas8, n_iterations=20, stop_flag=None):
         """Optimizer::OptimizeEssentialGraph on the flattened Sim3 pose graph (include/rumi_opt.h, rumi_essential_graph).

@@ -57,6 +57,26 @@ class GlibcRand:
         d = hi - lo + 1
         return int((float(self.rand()) / (2147483647.0 + 1.0)) * d) + lo
 
+    def draw_window(self, N, R):
+        """The minimal sets of the next R iterations as a solver with N correspondences draws them (:249-259), without advancing the
+        generator: every iteration is one whole triple of the stream, so solvers with different N read the same window differently."""
+        saved = self.state()
+        tri = np.zeros((R, 3), np.int32)
+        for h in range(R):
+            avail = list(range(N))
+            for i in range(3):
+                r = self.RandomInt(0, len(avail) - 1)
+                tri[h, i] = avail[r]
+                avail[r] = avail[-1]
+                avail.pop()
+        self.set_state(saved)
+        return tri
+
+    def advance(self, iterations):
+        """Skip the draws of `iterations` iterations (three each)."""
+        for _ in range(3 * int(iterations)):
+            self._next_word()
+
 
 class Sim3Solver:
     """Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale, vpKeyFrameMatchedMP) on flat arrays: one entry per correspondence the constructor
@@ -207,3 +227,64 @@ class Sim3Solver:
 
     def GetEstimatedScale(self):
         return float(self.mBestScale)
+
+
+class Sim3SolverBatch:
+    """The solvers of one DetectCommonRegionsFromBoW call (LoopClosing.cc:655-676: per candidate ``while (!bConverge && !bNoMore)
+    iterate(20, ...)``) run together over ``rumi_sim3_ransac_batch``.  ``solvers``: mirror ``Sim3Solver`` objects in candidate order with their
+    RANSAC parameters set; ``rng``: the generator they share.  A round takes a window of the iteration stream, lets every unfinished solver
+    evaluate all of it with its own N and applies the sequential rule on the device; the generator then moves on by three draws per iteration
+    consumed.  Because convergence is local (the first valid iteration above mRansacMinInliers returns) and a solver that never converges uses
+    exactly its mRansacMaxIts iterations, the result does not depend on the window.
+
+    Default window: 20 iterations for every solver still running, so that each can take one block of the reference in sequence.  The device
+    entry alone is faster with a window that needs one round, but the host draws J x window minimal sets a round and that cost
+    has not been measured, so the default stays."""
+
+    def __init__(self, optimizer, solvers, rng):
+        self._opt, self.solvers, self.rng = optimizer, list(solvers), rng
+
+    def run(self, window=None):
+        """Returns (per solver (converged, T12, vbInliers over mN1, nInliers, iterations), rounds used).  T12 is the 4x4 [sR | t] of the
+        converged solver, else the identity as upstream's iterate returns it."""
+        from .optimizer import SIM3_CONVERGED, SIM3_EXHAUSTED, SIM3_RANSAC_SOLVER_DTYPE
+        out = [None] * len(self.solvers)
+        pending = []
+        for k, s in enumerate(self.solvers):
+            if s.N < s.mRansacMinInliers or s.mnIterations >= s.mRansacMaxIts:       # :228-231: bNoMore at once, nothing drawn
+                out[k] = (False, np.eye(4, dtype=np.float32), np.zeros(s.mN1, bool), 0, 0)
+            else:
+                pending.append(k)
+        used = {k: 0 for k in pending}
+        rounds = 0
+        while pending:
+            R = int(window) if window is not None else 20 * len(pending)
+            sol = np.zeros(len(pending), SIM3_RANSAC_SOLVER_DTYPE)
+            first = 0
+            for rec, k in zip(sol, pending):
+                s = self.solvers[k]
+                rec["first"], rec["n"], rec["min_inliers"], rec["its_left"] = first, s.N, s.mRansacMinInliers, s.mRansacMaxIts - s.mnIterations
+                rec["fix_scale"], rec["K4_1"], rec["K4_2"] = int(s.fix_scale), s.K1, s.K2
+                first += s.N
+            cat = lambda name: np.concatenate([getattr(self.solvers[k], name) for k in pending])
+            tri = np.stack([self.rng.draw_window(self.solvers[k].N, R) for k in pending])
+            res = self._opt.Sim3RansacBatch(sol, cat("X1"), cat("X2"), cat("s1"), cat("s2"), tri)
+            rounds += 1
+            still = []
+            for j, k in enumerate(pending):
+                s = self.solvers[k]
+                its = int(res["its"][j])
+                s.mnIterations += its
+                used[k] += its
+                if res["state"][j] == SIM3_CONVERGED:
+                    T = res["T12"][j]
+                    inl = res["inliers"][sol["first"][j]:sol["first"][j] + s.N]
+                    s._take_best(dict(inl=inl, n=int(res["n_inliers"][j]), R=T[:9].reshape(3, 3), t=T[9:12], s=T[12]))
+                    out[k] = (True, s._T12(), s._vb(inl), int(res["n_inliers"][j]), used[k])
+                elif res["state"][j] == SIM3_EXHAUSTED:
+                    out[k] = (False, np.eye(4, dtype=np.float32), np.zeros(s.mN1, bool), 0, used[k])
+                else:
+                    still.append(k)
+            self.rng.advance(int(res["its"].sum()))
+            pending = still
+        return out, rounds
