@@ -357,14 +357,15 @@ def SearchByProjection_Reloc(m, Cur, log_sf, Tcw7, Ow3, K4, kf_keys, kf_mp, pts,
     return nm.value, cur_mp
 
 
-def isInFrustum(m, Rcw9, tcw3, Ow3, K4, w, h, log_sf, nlevels, cos_limit, pts):
-    """Frame::isInFrustum for all points; returns the dict SearchByProjection_MapPoints takes (without desc / obs / is_bad)."""
+def isInFrustum(m, Rcw9, tcw3, Ow3, K4, w, h, log_sf, nlevels, cos_limit, pts, min_x=0.0, min_y=0.0):
+    """Frame::isInFrustum for all points; returns the dict SearchByProjection_MapPoints takes (without desc / obs / is_bad).
+    The image rectangle is [min_x, w] x [min_y, h] (mnMinX .. mnMaxY: w and h are the upper bounds, not sizes, when the minima are not 0)."""
     n = len(pts["max_dist"])
     R, t, O, K = _f32(Rcw9), _f32(tcw3), _f32(Ow3), _f32(K4)
     a = dict(pos=_f32(pts["pos"]), normal=_f32(pts["normal"]), mn=_f32(pts["min_dist"]), mx=_f32(pts["max_dist"]))
     out = dict(track_in_view=np.zeros(n, np.uint8), proj_x=np.zeros(n, np.float32), proj_y=np.zeros(n, np.float32),
                scale_level=np.zeros(n, np.int32), view_cos=np.zeros(n, np.float32), track_depth=np.zeros(n, np.float32))
-    capi.check(m._lib.rumi_frame_is_in_frustum(m._h, capi.ptr(R), capi.ptr(t), capi.ptr(O), capi.ptr(K), 0.0, 0.0, float(w), float(h), float(log_sf),
+    capi.check(m._lib.rumi_frame_is_in_frustum(m._h, capi.ptr(R), capi.ptr(t), capi.ptr(O), capi.ptr(K), float(min_x), float(min_y), float(w), float(h), float(log_sf),
                                                int(nlevels), float(cos_limit), n, capi.ptr(a["pos"]), capi.ptr(a["normal"]), capi.ptr(a["mn"]),
                                                capi.ptr(a["mx"]), capi.ptr(out["track_in_view"]), capi.ptr(out["proj_x"]), capi.ptr(out["proj_y"]),
                                                capi.ptr(out["scale_level"]), capi.ptr(out["view_cos"]), capi.ptr(out["track_depth"])))

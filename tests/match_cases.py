@@ -119,9 +119,11 @@ class Proj:
         self.f.append((np.float32(x), np.float32(y), self.level if octave is None else octave, angle, np.asarray(desc, np.uint8)))
         return len(self.f) - 1
 
-    def query(self, u, v, desc, angle=0.0, level=None, kind="ok", octave1=None):
+    def query(self, u, v, desc, angle=0.0, level=None, kind="ok", octave1=None, pos=None, normal=None, min_dist=None, max_dist=None):
+        """pos / normal / min_dist / max_dist: the point's attributes as given (float32 values) instead of the ones derived from (u, v, level);
+        (u, v) then only places the query's own key-point."""
         self.q.append(dict(u=u, v=v, desc=np.asarray(desc, np.uint8), angle=angle, level=self.level if level is None else level, kind=kind,
-                           octave1=octave1))
+                           octave1=octave1, pos=pos, normal=normal, min_dist=min_dist, max_dist=max_dist))
         return len(self.q) - 1
 
     def arrays(self):
@@ -135,8 +137,14 @@ class Proj:
                 p[2] = -Z
             if q["kind"] == "z0":
                 p = np.array([1.0, 1.0, 0.0])
+            if q["pos"] is not None:
+                p = np.asarray(q["pos"], np.float64)
             pos[i] = p
-            assert np.array_equal(pos[i].astype(np.float64), p), "camera-frame coordinates must be exact in float32"
+            assert pos[i].astype(np.float64).tobytes() == p.tobytes(), "camera-frame coordinates must be exact in float32"
+            if q["pos"] is not None:                            # a constructed point states all four attributes itself
+                mx[i], mn[i], nrm[i], lev[i] = q["max_dist"], q["min_dist"], q["normal"], q["level"]
+                assert float(mx[i]) == q["max_dist"] and float(mn[i]) == q["min_dist"] and np.array_equal(nrm[i].astype(np.float64), np.asarray(q["normal"], np.float64))
+                continue
             dist = float(np.linalg.norm(p))
             mx[i] = dist * 1.2 ** (q["level"] - 0.5)           # PredictScale = ceil(level - 0.5) = level, half a level clear of both neighbours
             mn[i] = 0.1
@@ -231,17 +239,17 @@ def call_oracle(O, c):
     obs = _mp_fields(i)[0]["obs"]
     if m == "LAST":
         pts = _pts(i, tot)
-        return O.search_by_projection_frame(i["keys"], i["desc"], i["w"], i["h"], SF, IDENT7, K4, i["qkeys"], np.arange(i["nq"], dtype=np.int32),
+        return O.search_by_projection_frame(i["keys"], i["desc"], i["w"], i["h"], SF, i.get("Tcw7", IDENT7), K4, i["qkeys"], np.arange(i["nq"], dtype=np.int32),
                                             np.zeros(i["nq"], np.uint8), pts["pos"], pts["desc"], obs, _state(i, n), float(i["R"]), c.ori)
     if m == "RELOC":
         pts = dict(_pts(i, tot), skip=np.zeros(tot, np.uint8))
-        return O.search_by_projection_reloc(i["keys"], i["desc"], i["w"], i["h"], SF, LOG_SF, IDENT7, np.zeros(3, np.float32), K4, i["qkeys"],
+        return O.search_by_projection_reloc(i["keys"], i["desc"], i["w"], i["h"], SF, LOG_SF, i.get("Tcw7", IDENT7), i.get("Ow", np.zeros(3, np.float32)), K4, i["qkeys"],
                                             np.arange(i["nq"], dtype=np.int32), pts, _state(i, n), float(i["R"]), i["orb_dist"], c.ori)
     if m == "SIM3P":
-        return O.search_by_projection_sim3(i["keys"], i["desc"], i["w"], i["h"], SF, LOG_SF, IDENT7, np.zeros(3, np.float32), K4, _pts(i, i["nq"]),
+        return O.search_by_projection_sim3(i["keys"], i["desc"], i["w"], i["h"], SF, LOG_SF, i.get("Tcw7", IDENT7), i.get("Ow", np.zeros(3, np.float32)), K4, _pts(i, i["nq"]),
                                            _state(i, n, -2), i["R"], i["ratio_hamming"], i["variant"])
     if m == "FUSE":
-        r = O.fuse_candidates(i["keys"], i["desc"], i["w"], i["h"], SF, LOG_SF, IDENT7, np.zeros(3, np.float32), K4, _pts(i, i["nq"]), float(i["R"]), i["reproj"])
+        r = O.fuse_candidates(i["keys"], i["desc"], i["w"], i["h"], SF, LOG_SF, i.get("Tcw7", IDENT7), i.get("Ow", np.zeros(3, np.float32)), K4, _pts(i, i["nq"]), float(i["R"]), i["reproj"])
         return int(np.count_nonzero(r >= 0)), r
     if m == "SIM3":
         s1, s2 = _sim3_sides(i)
@@ -261,21 +269,21 @@ def call_gpu(M, h, c):
     F = M.FrameView(i["keys"], i["desc"], i["w"], i["h"], SF)
     tot = i["nq"] + len(i["occ"])
     obs = _mp_fields(i)[0]["obs"]
-    Ow = np.zeros(3, np.float32)
+    Ow, T7 = i.get("Ow", np.zeros(3, np.float32)), i.get("Tcw7", IDENT7)
     if m == "MP":
         mp, _ = _mp_fields(i)
         return h.SearchByProjection_MapPoints(F, mp, _state(i, n), i["R"] / 4.0)
     if m == "LAST":
         pts = _pts(i, tot)
-        return h.SearchByProjection_Frame(F, IDENT7, K4, i["qkeys"], np.arange(i["nq"], dtype=np.int32), np.zeros(i["nq"], np.uint8), pts["pos"], pts["desc"],
+        return h.SearchByProjection_Frame(F, T7, K4, i["qkeys"], np.arange(i["nq"], dtype=np.int32), np.zeros(i["nq"], np.uint8), pts["pos"], pts["desc"],
                                           obs, _state(i, n), float(i["R"]))
     if m == "RELOC":
         pts = dict(_pts(i, tot), skip=np.zeros(tot, np.uint8))
-        return M.SearchByProjection_Reloc(h, F, LOG_SF, IDENT7, Ow, K4, i["qkeys"], np.arange(i["nq"], dtype=np.int32), pts, _state(i, n), float(i["R"]), i["orb_dist"])
+        return M.SearchByProjection_Reloc(h, F, LOG_SF, T7, Ow, K4, i["qkeys"], np.arange(i["nq"], dtype=np.int32), pts, _state(i, n), float(i["R"]), i["orb_dist"])
     if m == "SIM3P":
-        return M.SearchByProjection_Sim3(h, F, LOG_SF, IDENT7, Ow, K4, _pts(i, i["nq"]), _state(i, n, -2), i["R"], i["ratio_hamming"], bool(i["variant"]))
+        return M.SearchByProjection_Sim3(h, F, LOG_SF, T7, Ow, K4, _pts(i, i["nq"]), _state(i, n, -2), i["R"], i["ratio_hamming"], bool(i["variant"]))
     if m == "FUSE":
-        r = M.FuseCandidates(h, F, LOG_SF, IDENT7, Ow, K4, _pts(i, i["nq"]), float(i["R"]), bool(i["reproj"]))
+        r = M.FuseCandidates(h, F, LOG_SF, T7, Ow, K4, _pts(i, i["nq"]), float(i["R"]), bool(i["reproj"]))
         return int(np.count_nonzero(r >= 0)), r
     if m == "SIM3":
         s1, s2 = _sim3_sides(i)
@@ -292,8 +300,9 @@ def call_gpu_fused(M, h, c):
     F = M.FrameView(i["keys"], i["desc"], i["w"], i["h"], SF)
     mp, tot = _mp_fields(i)
     pts = dict(_pts(i, tot), obs=mp["obs"])
-    nto, nm, fm, _ = h.SearchLocalPoints(F, np.eye(3, dtype=np.float32).ravel(), np.zeros(3, np.float32), np.zeros(3, np.float32), K4, LOG_SF, 8, pts,
-                                         _state(i, len(i["keys"])), i["R"] / 4.0)
+    nto, nm, fm, _ = h.SearchLocalPoints(F, i.get("Rcw", np.eye(3, dtype=np.float32)).ravel(), i.get("tcw", np.zeros(3, np.float32)),
+                                         i.get("Ow", np.zeros(3, np.float32)), K4, LOG_SF, 8, pts, _state(i, len(i["keys"])), i["R"] / 4.0,
+                                         i.get("far", False), i.get("th_far", 50.0))
     return nm, fm
 
 
