@@ -168,6 +168,65 @@ int rumi_track_undistorted(RumiTracker *t, RumiKeyPoint *keys_un_out, int32_t ca
  * searched at these values (RumiTrackPoints.stale_proj).  One more device-to-host copy; valid until the next rumi_track_* call on the tracker. */
 int rumi_track_last_projections(RumiTracker *t, int32_t n_points, float *proj5_out);
 
+/* ---- Tracking::Relocalization, the refine chain (R/lib_src/Tracking.cc:3287-3345) of every pose hypothesis of a round in ONE call ----------
+ * The frame is the one rumi_track_extract left resident.  rumi_track_reloc_begin uploads, once per Relocalization call, what every round
+ * reads: the candidates' key-points, their map-point rows and BoW matches, and one point table shared by all candidates (pos, min_dist,
+ * max_dist, desc, bad of RumiTrackPoints are read).  rumi_track_reloc_refine then takes only the hypotheses of a round (candidate, pose,
+ * vbInliers) and returns, per hypothesis, the state the body of `for (i ...)` leaves behind when it starts from that hypothesis:
+ *   seed mvpMapPoints from matches and inliers, sFound from the inliers (:3296-3302) -> PoseOptimization -> `nGood < min_good: continue` ->
+ *   nulling loop (:3309) -> nGood < enough: SearchByProjection(F, pKF, sFound, th_coarse, dist_coarse) -> nGood + nadditional >= enough:
+ *   PoseOptimization -> retry_above < nGood < enough: sFound rebuilt from every non-NULL slot, SearchByProjection(th_fine, dist_fine) ->
+ *   (P2's) nGood + nadditional >= enough: PoseOptimization and the nulling loop (:3333).
+ * Every step is the arithmetic of rumi_pose_optimization / rumi_search_by_projection_reloc; the decisions are taken on the device and the
+ * number of kernel launches does not depend on the number of hypotheses.  The entry decides nothing about bMatch: read ngood_final. */
+#define RUMI_RELOC_MAX_HYPOTHESES 256      /* per rumi_track_reloc_refine call; more: RUMI_E_CAPACITY */
+
+typedef struct RumiRelocCandidate {      /* host pointers, read by begin only */
+    int32_t nkf;
+    const RumiKeyPoint *kf_keys;         /* pKF->mvKeysUn (octave is read, ORBmatcher.cc:1685-1793) */
+    const int32_t *kf_mp;                /* [nkf] GetMapPointMatches() as ids into pts, -1 NULL */
+    const int32_t *matches;              /* [n]  vvpMapPointMatches[i] as ids into pts, -1 NULL (from the BoW walk) */
+} RumiRelocCandidate;
+
+typedef struct RumiRelocParams {         /* the literals of Tracking.cc:3306-3342; rumi_reloc_default_params() fills them */
+    int32_t min_good;      /* 10 */
+    int32_t enough;        /* 50 */
+    int32_t retry_above;   /* 30 */
+    float th_coarse;       /* 10 */
+    int32_t dist_coarse;   /* 100 */
+    float th_fine;         /* 3 */
+    int32_t dist_fine;     /* 64 */
+    int32_t check_orientation; /* 1: ORBmatcher matcher2(0.9, true) */
+} RumiRelocParams;
+
+typedef struct RumiRelocHypothesis {
+    int32_t cand;                        /* index into the candidates of begin */
+    float Tcw7[7];                       /* Sophus::SE3f(eigTcw) as [qx qy qz qw tx ty tz] */
+    const uint8_t *inliers;              /* [n] vbInliers */
+} RumiRelocHypothesis;
+
+typedef struct RumiRelocResult {
+    int32_t ran;            /* bit 0 P1, 1 outliers nulled (:3309), 2 S1 (:3315), 3 P2 (:3318), 4 S2 (:3327), 5 P3 + nulling (:3331-3335) */
+    int32_t ngood[3];       /* return values of the PoseOptimizations that ran (0 otherwise) */
+    int32_t nadditional[2]; /* of the two searches */
+    int32_t ngood_final;    /* nGood as :3342 tests it; -1 when :3307 `continue`d */
+    float Tcw[7];           /* mCurrentFrame.GetPose() when the hypothesis' body ends */
+} RumiRelocResult;
+
+void rumi_reloc_default_params(RumiRelocParams *p);
+
+/* K4: fx fy cx cy of the frame.  cands [K]; pts: the table every kf_mp / matches id indexes.  RUMI_E_INVALID: no frame resident, a missing
+ * array, an id outside the table; RUMI_E_CAPACITY: pts->n above the tracker's max_points.  A refused begin leaves an earlier session as it was. */
+int rumi_track_reloc_begin(RumiTracker *t, const float *K4, int32_t K, const RumiRelocCandidate *cands, const RumiTrackPoints *pts);
+
+/* p == NULL: the defaults.  hyp [H].  Outputs: frame_mp [H][cap] = mvpMapPoints as table ids (the first n of each row are written),
+ * outlier_last [H][cap]: what the hypothesis' last PoseOptimization that had a point at the feature wrote into mvbOutlier there (0 / 1; 255:
+ * never written), res [H].  cap = nfeatures + 4 nlevels + 64 as everywhere in this header.  H == 0 returns RUMI_OK.
+ * RUMI_E_INVALID: no begin precedes on this frame (a new rumi_track_extract ends the session), cand outside [0, K), inliers NULL;
+ * RUMI_E_CAPACITY: H above RUMI_RELOC_MAX_HYPOTHESES.  Refusals precede any device work, write no output and leave the handle usable. */
+int rumi_track_reloc_refine(RumiTracker *t, const RumiRelocParams *p, int32_t H, const RumiRelocHypothesis *hyp, int32_t *frame_mp,
+                            uint8_t *outlier_last, RumiRelocResult *res);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@
 //   match_queries.inc     k_queries_mappoints / frame / bow / sim3 / campoints / reloc / init, k_is_in_frustum
 //   match_candidates.inc  k_candidates<0 | 1 | 2> (candidates_walk, wave_bitonic_store, offsets_of), k_scan
 //   match_resolve.inc     k_resolve (ResolveArgs, match_host.h), k_resolve_init (InitArgs)
+//   match_reloc_batch.inc  k_reloc_walk<count | fill>, k_reloc_resolve: the relocalisation searches of every pose hypothesis (launch_reloc_search)
 //   match_search.inc      host: build_lists, the list / resolve / retry loop, run_search; the rumi_search_* entries built on them,
 //                         rumi_fuse_candidates, rumi_frame_is_in_frustum
 //   match_tri.inc         k_tri_match, k_tri_filter (TriArgs) and rumi_search_for_triangulation
@@ -125,6 +126,7 @@ __global__ __launch_bounds__(256) void k_scatter(const uint8_t *__restrict__ mir
 #include "match_queries.inc"
 #include "match_candidates.inc"
 #include "match_resolve.inc"
+#include "match_reloc_batch.inc"
 
 }  // namespace rumi
 
@@ -268,6 +270,12 @@ void launch_queries_bow(RumiMatcher *m, int nEntries, int nnKF, int nnF, const i
 }
 void launch_resolve(const ResolveArgs &A, hipStream_t st) {
     hipLaunchKernelGGL(k_resolve, dim3(1), dim3(1024), (size_t)std::max(A.nfeat, 1) * sizeof(int32_t), st, A);
+}
+void launch_reloc_search(const RelocSearchArgs &A, hipStream_t st) {
+    const dim3 gWalk((std::max(A.maxNkf, 1) + 3) / 4, A.H);
+    hipLaunchKernelGGL(k_reloc_walk<false>, gWalk, dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_reloc_walk<true>, gWalk, dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_reloc_resolve, dim3(A.H), dim3(kRelocResolveThreads), (size_t)std::max(A.nfeat, 1) * sizeof(int32_t), st, A);
 }
 
 }  // namespace rumi

@@ -189,4 +189,39 @@ void launch_queries_frame(RumiMatcher *m, const FrameDev &fd, int nlast, float t
 void launch_queries_bow(RumiMatcher *m, int nEntries, int nnKF, int nnF, const int32_t *nnFdev, hipStream_t st);
 void launch_resolve(const ResolveArgs &A, hipStream_t st);
 
+// ---- rumi_track_reloc_refine: what its stage kernels in track.hip (track_reloc.inc) and match.hip (match_reloc_batch.inc) share ----
+enum { RELOC_LIVE_S1 = 1, RELOC_LIVE_P2 = 2, RELOC_LIVE_S2 = 4, RELOC_LIVE_P3 = 8 };     // RelocHyp.live: the stage still has this hypothesis to do
+struct RelocHyp {                        // one hypothesis on the device; its first 14 words are RumiRelocResult
+    int32_t ran, ngood[3], nadd[2], ngoodFinal;
+    float T[7];
+    int32_t cand, live;
+};
+static_assert(sizeof(RelocHyp) == 64, "a record of the result block");
+struct RelocCand { int32_t nkf, keyOff; };               // a candidate's key-points and map-point row inside the session's concatenated arrays
+// One SearchByProjection(F, pKF, sFound, th, ORBdist) stage for every hypothesis whose live bit is set (stage 0: S1, 1: S2): queries and
+// candidate count, fill, one ordered resolve per hypothesis, which also takes the stage's decision (`nGood + nadditional >= enough`).
+struct RelocSearchArgs {
+    int H, nfeat, words, maxNkf, stage;
+    RelocHyp *hyp;
+    const RelocCand *cands;
+    const RumiKeyPoint *kfKeys;          // all candidates' key-points, a candidate's at keyOff
+    const int32_t *kfMp;                 // likewise their rows
+    const float *pos, *minD, *maxD;      // the point table
+    const uint8_t *desc, *bad;
+    const uint32_t *found;               // [H][words] sFound as a bitmap over table ids
+    const float *T;                      // [H][7] the current poses
+    float K[4];
+    FrameDev fd;
+    int nLevels;
+    float logSf, th;
+    int orbDist, checkOri, enough;
+    Query *q;                            // [H][maxNkf]
+    int32_t *pairCount, *pairBase, *asg; // [H][maxNkf] candidates of a pair, where its list starts, the feature it holds
+    int32_t *head;                       // [0 / 1] candidates of S1 / S2 in all
+    uint2 *lists;
+    int listCap;
+    int32_t *featMp;                     // [H][nfeat]
+};
+void launch_reloc_search(const RelocSearchArgs &A, hipStream_t st);
+
 }  // namespace rumi

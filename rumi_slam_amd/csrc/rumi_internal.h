@@ -116,9 +116,11 @@ constexpr int kPoseLdsEdges = 1152;
 // Optimizer::PoseOptimization of ONE frame whose correspondences already lie on the device (opt.hip, k_pose_opt): dStart = {0, n} (n read by the
 // kernel, not by the host), Xw [n][3], obs [n][2], w [n] (invLevelSigma2), K4, Tin [7] -> Tout [7], outlier [n], nGood [1].  dActive [cap] and
 // dLastChi2 [cap] are scratch for frames of more than 1024 correspondences; fitsLds: the caller knows the count is at most 1024 (the second
-// instantiation is then not launched).  Enqueues on `st`, does not synchronise.
+// instantiation is then not launched).  Enqueues on `st`, does not synchronise.  nbatch > 1 (rumi_track_reloc_refine): dStart [nbatch + 1],
+// problem b's correspondences at dStart[b] .. dStart[b + 1], Tin / Tout [nbatch][7], nGood [nbatch], one workgroup each; fitsLds must then
+// hold for every problem.
 int pose_opt_device(const int32_t *dStart, const float *dXw, const float *dObs, const float *dW, const float *dK4, const float *dTin, float *dTout,
-                    uint8_t *dOutlier, int32_t *dNGood, uint8_t *dActive, double *dLastChi2, bool fitsLds, hipStream_t st);
+                    uint8_t *dOutlier, int32_t *dNGood, uint8_t *dActive, double *dLastChi2, bool fitsLds, hipStream_t st, int nbatch = 1);
 
 // Device, word count and the header's weighting / scoring types of a vocabulary (voc.hip), for the key-frame database (kfdb.hip).
 void voc_params(const RumiVocabulary *v, int *device, int *nWords, int *weighting, int *scoring);

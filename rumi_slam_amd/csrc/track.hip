@@ -3,7 +3,8 @@
 // costs about 4.5 us on the device whatever it does, so the step is built from as few as the data flow allows: no device-to-device copies (the
 // matcher reads the extractor's record in place, results are produced inside the block that travels back), fills and bookkeeping folded into
 // neighbouring kernels.  The matcher is driven through match_host.h (upload queue and stagers, the frustum result block, run_search); its kernels are
-// launched by match.hip's launchers.
+// launched by match.hip's launchers.  track_reloc.inc (included at the end): Tracking::Relocalization's refine chain for every pose hypothesis of a
+// round in one call (rumi_track_reloc_begin / rumi_track_reloc_refine).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -275,6 +276,8 @@ struct TrackViews {                      // the arrays behind the TrackBlock hea
     int32_t *tableIds;                   // rumi_track_local_map: the point id of every table row, behind the record
 };
 
+namespace rumi { struct RelocState; void reloc_release(RelocState *s); }      // track_reloc.inc
+
 struct RumiTracker {
     int device = 0, cap = 0, maxPts = 0, nlevels = 0;
     RumiOrbConfig cfg{};
@@ -305,11 +308,15 @@ struct RumiTracker {
     // the frame's BoW transform: one block [weight f64 x cap | word u32 x cap | node u32 x cap] and its pinned mirror (one copy back)
     uint8_t *dBow = nullptr, *hBow = nullptr;
     uint32_t *dWord = nullptr, *dNode = nullptr; double *dWeight = nullptr; int32_t *dNN = nullptr;
+    // rumi_track_reloc_begin / _refine (track_reloc.inc): the session's blocks; frameSerial counts the frames that became resident
+    uint32_t frameSerial = 0;
+    rumi::RelocState *reloc = nullptr;
 };
 
 extern "C" void rumi_track_destroy(RumiTracker *t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
+    rumi::reloc_release(t->reloc);
     rumi_orb_destroy(t->ext);
     rumi_match_destroy(t->m);
     void *p[] = {t->dImage, t->dBlk, t->dInvSigma2, t->dXw, t->dObs, t->dW, t->dIdx, t->dOutC, t->dActive, t->dSeen, t->dBad, t->dLocal, t->dChi, t->dBow, t->dNN, t->dStaleIn, t->dStaleProj, t->dKeysUn};
@@ -656,6 +663,7 @@ extern "C" int rumi_track_frame(RumiTracker *t, const uint8_t *img, int32_t w, i
         n = counts[0];
         res->n = n; res->mono_index = counts[1];
         t->curN = n; t->curW = w; t->curH = h; t->curMono = counts[1];      // the frame is resident for the step-wise entries too
+        t->frameSerial++;
         fd.n = n; m->gridN = n;
     };
     if (!canSpec) {
@@ -758,6 +766,7 @@ extern "C" int rumi_track_extract(RumiTracker *t, const uint8_t *img, int32_t w,
         std::memcpy(desc_out, t->h.record + t->oDesc, (size_t)n * 32);
     }
     t->curN = n; t->curW = w; t->curH = h; t->curMono = counts[1];
+    t->frameSerial++;
     { RumiFrameFeatures Fb{}; track_bounds(t, w, h, &Fb); }    // mnMinX .. mnMaxY of this frame (rumi_track_undistorted)
     *n_out = n; *mono_out = counts[1];
     return RUMI_OK;
@@ -1019,3 +1028,5 @@ extern "C" int rumi_track_undistorted(RumiTracker *t, RumiKeyPoint *keys_un_out,
     }
     return RUMI_OK;
 }
+
+#include "track_reloc.inc"

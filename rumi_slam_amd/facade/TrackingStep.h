@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "ORBextractor.h"
+#include "ORBmatcher.h"
 #include "ORBVocabulary.h"
 #include "rumi_status.h"
 #include "rumi_track.h"
@@ -48,6 +49,9 @@ struct TrackStep {
     bool okMotion = false;                  // what TrackWithMotionModel / TrackReferenceKeyFrame returned (the last one that ran)
     bool ranLocal = false;                  // TrackLocalMap's data path has run (TrackFrame only runs it when okMotion)
     float TcwMotion[7] = {0, 0, 0, 1, 0, 0, 0}, Tcw[7] = {0, 0, 0, 1, 0, 0, 0};
+    // Relocalization: live candidates after the BoW stage, rounds of the RANSAC loop, rumi_track_reloc_refine calls, hypotheses refined, the
+    // winning candidate (-1: none) and nGood as Tracking.cc:3342 tested it for the last hypothesis that was replayed
+    int relocCandidates = 0, relocRounds = 0, relocRefines = 0, relocHypotheses = 0, relocWinner = -1, relocGood = -1;
 };
 
 // per thread and extractor configuration: the tracker owns an extractor handle, a matcher arena and the result block
@@ -548,6 +552,120 @@ int TrackFrame(FrameT &Cur, const cv::Mat &im, ExtractorT &extractor, const floa
     std::memcpy(st.TcwMotion, r.Tcw_motion, 28); std::memcpy(st.Tcw, r.Tcw, 28);
     if (out) *out = st;
     return r.mono_index;
+}
+
+// Tracking::Relocalization (Tracking.cc:3212-3357) from `vpCandidateKFs` on, on the frame ExtractFrame left resident (F.mFeatVec computed:
+// Frame::ComputeBoW).  :3226-3259 with the existing pieces -- isBad, the batched SearchByBoW (ORBmatcher.h, nnratio 0.75), `nmatches < 15`, and
+// make(F, vvpMapPointMatches[i]), through which the CALLER constructs and configures its solver (this header names no solver type; the
+// reference's is `new MLPnPsolver(...)` + SetRansacParameters(0.99, 10, 300, 6, 0.5, 5.991)) -- then ONE rumi_track_reloc_begin, and per round of
+// :3266-3348 step(solver_i, bNoMore, vbInliers, nInliers, Tcw7) -> bTcw for every live candidate in order (the reference's
+// `pSolver->iterate(5, ...)`, Tcw7 = Sophus::SE3f(eigTcw) as [qx qy qz qw tx ty tz]; vbInliers covers the frame), ONE rumi_track_reloc_refine
+// for the round's hypotheses, and the replay in candidate order up to and including the first hypothesis that wins (`ran & 2` and
+// ngood_final >= 50): mvbOutlier takes every replayed hypothesis' layer (PoseOptimization writes it only where a point is), mvpMapPoints and
+// the pose are the last replayed hypothesis'.  Returns bMatch; mnLastRelocFrameId is the caller's.  Without a winner the frame is left as the
+// last hypothesis that ran left it, as in the reference.
+// speculateRound = true: the candidates behind the winner in the winning round have iterated once more than in the reference, so a solver that
+// draws from the process-wide rand() (DUtils::Random, shared with Sim3Solver) leaves that stream further advanced.  speculateRound = false
+// refines one hypothesis a call in the reference's order and makes exactly the reference's solver calls.  Both leave the same frame.
+template <class FrameT, class KeyFrameT, class MakeSolver, class SolverStep>
+bool Relocalization(FrameT &F, const std::vector<KeyFrameT *> &vpCandidateKFs, MakeSolver make, SolverStep step, TrackStep *out, bool speculateRound = true) {
+    using MapPointT = typename std::remove_pointer<typename std::decay<decltype(F.mvpMapPoints[0])>::type>::type;
+    TrackStep st = out ? *out : TrackStep();
+    st.relocCandidates = st.relocRounds = st.relocRefines = st.relocHypotheses = 0; st.relocWinner = -1; st.relocGood = -1;
+    auto leave = [&](bool r) { if (out) *out = st; return r; };
+    RumiTracker *t = tracker_slot();
+    if (!t) { report("Relocalization: ExtractFrame has not run on this thread", RUMI_E_INVALID); return leave(false); }
+    const int nKFs = (int)vpCandidateKFs.size();
+    if (nKFs == 0) return leave(false);                                                      // :3221
+    RUMI_FACADE_NAMESPACE::ORBmatcher matcher(0.75f, true);                                            // :3230
+    std::vector<std::vector<MapPointT *>> vvpMapPointMatches;
+    const std::vector<int> nmatches = matcher.SearchByBoW(vpCandidateKFs, F, vvpMapPointMatches);
+    using SolverT = decltype(make(F, vvpMapPointMatches[0]));
+    std::vector<SolverT> vpSolvers(nKFs);
+    std::vector<bool> vbDiscarded(nKFs, false);
+    std::vector<int> sessionOf(nKFs, -1);
+    int nCandidates = 0;
+    // the session: the live candidates' key-points, rows and matches over one point table
+    track_detail::PointTable<MapPointT> tab;
+    std::vector<std::vector<int32_t>> rows, matchIds;
+    std::vector<RumiRelocCandidate> cands;
+    for (int i = 0; i < nKFs; i++) {
+        KeyFrameT *pKF = vpCandidateKFs[i];
+        if (!pKF || pKF->isBad() || nmatches[i] < 15) { vbDiscarded[i] = true; continue; }  // :3245-3251
+        vpSolvers[i] = make(F, vvpMapPointMatches[i]);                                       // :3253-3255
+        sessionOf[i] = nCandidates++;
+        const std::vector<MapPointT *> vpMPs = pKF->GetMapPointMatches();
+        rows.emplace_back(vpMPs.size(), -1); matchIds.emplace_back((size_t)(F.N > 0 ? F.N : 1), -1);
+        for (size_t j = 0; j < vpMPs.size(); j++) if (vpMPs[j]) rows.back()[j] = tab.id_of(vpMPs[j]);
+        for (int f = 0; f < F.N; f++) if (vvpMapPointMatches[i][f]) matchIds.back()[f] = tab.id_of(vvpMapPointMatches[i][f]);
+    }
+    st.relocCandidates = nCandidates;
+    if (nCandidates == 0) return leave(false);
+    for (int i = 0, k = 0; i < nKFs; i++) {
+        if (vbDiscarded[i]) continue;
+        cands.push_back(RumiRelocCandidate{(int32_t)rows[k].size(), reinterpret_cast<const RumiKeyPoint *>(vpCandidateKFs[i]->mvKeysUn.data()), rows[k].data(), matchIds[k].data()});
+        k++;
+    }
+    tab.fill(0);
+    if (!track_detail::table_fits((int)tab.byId.size(), "Relocalization: more points than the tracker holds (ExtractFrame's maxPoints)")) return leave(false);
+    const float K4[4] = {F.fx, F.fy, F.cx, F.cy};
+    const RumiTrackPoints P = tab.view();
+    int rc = rumi_track_reloc_begin(t, K4, nCandidates, cands.data(), &P);
+    if (rc != RUMI_OK) { report("Relocalization: rumi_track_reloc_begin", rc); return leave(false); }
+    RumiRelocParams prm;
+    rumi_reloc_default_params(&prm);
+    const size_t cap = (size_t)tracker_cfg().nfeatures + 4 * tracker_cfg().nlevels + 64;
+    struct Hyp { int i; float T[7]; std::vector<uint8_t> inl; };
+    std::vector<int32_t> mp;
+    std::vector<uint8_t> ol;
+    std::vector<RumiRelocResult> res;
+    bool failed = false;
+    // one refine call for `hyps`, then the replay of :3287-3345's effect on the frame in order; true when one of them wins
+    auto refine = [&](const std::vector<Hyp> &hyps) {
+        const int H = (int)hyps.size();
+        std::vector<RumiRelocHypothesis> hv(H);
+        for (int h = 0; h < H; h++) { hv[h].cand = sessionOf[hyps[h].i]; std::memcpy(hv[h].Tcw7, hyps[h].T, 28); hv[h].inliers = hyps[h].inl.data(); }
+        mp.assign((size_t)H * cap, -1); ol.assign((size_t)H * cap, 255); res.assign(H, RumiRelocResult());
+        rc = rumi_track_reloc_refine(t, &prm, H, hv.data(), mp.data(), ol.data(), res.data());
+        if (rc != RUMI_OK) { report("Relocalization: rumi_track_reloc_refine", rc); failed = true; return false; }
+        st.relocRefines++; st.relocHypotheses += H;
+        for (int h = 0; h < H; h++) {
+            const uint8_t *o = &ol[(size_t)h * cap];
+            for (int f = 0; f < F.N; f++) if (o[f] != 255) F.mvbOutlier[f] = o[f] != 0;
+            const bool wins = (res[h].ran & 2) && res[h].ngood_final >= prm.enough;         // :3342
+            if (wins || h == H - 1) {
+                const int32_t *m = &mp[(size_t)h * cap];
+                for (int f = 0; f < F.N; f++) F.mvpMapPoints[f] = m[f] >= 0 ? tab.byId[m[f]] : nullptr;
+                track_detail::set_pose(F, res[h].Tcw);
+                std::memcpy(st.Tcw, res[h].Tcw, 28);
+                st.relocGood = res[h].ngood_final;
+            }
+            if (wins) { st.relocWinner = hyps[h].i; return true; }
+        }
+        return false;
+    };
+    bool bMatch = false;
+    while (nCandidates > 0 && !bMatch && !failed) {                                          // :3266
+        st.relocRounds++;
+        std::vector<Hyp> hyps;
+        for (int i = 0; i < nKFs && !bMatch && !failed; i++) {
+            if (vbDiscarded[i]) continue;
+            std::vector<bool> vbInliers;
+            int nInliers = 0;
+            bool bNoMore = false;
+            Hyp hy;
+            hy.i = i;
+            const bool bTcw = step(vpSolvers[i], bNoMore, vbInliers, nInliers, hy.T);          // :3278
+            if (bNoMore) { vbDiscarded[i] = true; nCandidates--; }                           // :3281-3284
+            if (!bTcw) continue;
+            hy.inl.assign((size_t)(F.N > 0 ? F.N : 1), 0);
+            for (size_t j = 0; j < vbInliers.size() && j < (size_t)F.N; j++) hy.inl[j] = vbInliers[j] ? 1 : 0;
+            hyps.push_back(std::move(hy));
+            if (!speculateRound) { bMatch = refine(hyps); hyps.clear(); }
+        }
+        if (speculateRound && !hyps.empty()) bMatch = refine(hyps);
+    }
+    return leave(bMatch);
 }
 
 }  // namespace rumi_facade

@@ -33,6 +33,28 @@ class RumiTrackResult(C.Structure):
                 ("Ow", C.c_float * 3)]
 
 
+class RumiRelocCandidate(C.Structure):
+    _fields_ = [("nkf", C.c_int32), ("kf_keys", C.c_void_p), ("kf_mp", C.c_void_p), ("matches", C.c_void_p)]
+
+
+class RumiRelocParams(C.Structure):
+    _fields_ = [("min_good", C.c_int32), ("enough", C.c_int32), ("retry_above", C.c_int32), ("th_coarse", C.c_float), ("dist_coarse", C.c_int32),
+                ("th_fine", C.c_float), ("dist_fine", C.c_int32), ("check_orientation", C.c_int32)]
+
+
+class RumiRelocHypothesis(C.Structure):
+    _fields_ = [("cand", C.c_int32), ("Tcw7", C.c_float * 7), ("inliers", C.c_void_p)]
+
+
+class RumiRelocResult(C.Structure):
+    _fields_ = [("ran", C.c_int32), ("ngood", C.c_int32 * 3), ("nadditional", C.c_int32 * 2), ("ngood_final", C.c_int32), ("Tcw", C.c_float * 7)]
+
+
+RELOC_MAX_HYPOTHESES = 256          # RUMI_RELOC_MAX_HYPOTHESES of include/rumi_track.h
+RELOC_RESULT_DTYPE = np.dtype([("ran", "<i4"), ("ngood", "<i4", 3), ("nadditional", "<i4", 2), ("ngood_final", "<i4"), ("Tcw", "<f4", 7)])
+assert RELOC_RESULT_DTYPE.itemsize == C.sizeof(RumiRelocResult)
+
+
 def _bind(L):
     if getattr(L, "_track_ready", False):
         return L
@@ -53,6 +75,11 @@ def _bind(L):
     L.rumi_track_set_distortion.argtypes = [vp, vp, vp]
     L.rumi_track_undistorted.argtypes = [vp, vp, i32, vp]
     L.rumi_track_image_buffer.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(i32)]
+    L.rumi_reloc_default_params.argtypes = [C.POINTER(RumiRelocParams)]
+    L.rumi_reloc_default_params.restype = None
+    L.rumi_track_reloc_begin.argtypes = [vp, vp, i32, vp, C.POINTER(RumiTrackPoints)]
+    L.rumi_track_reloc_refine.argtypes = [vp, C.POINTER(RumiRelocParams), i32, vp, vp, vp, vp]
+    L.rumi_track_reloc_attempts.argtypes = [vp, C.POINTER(i32)]
     L._track_ready = True
     return L
 
@@ -255,3 +282,134 @@ class Tracker:
                    local_points=o["table_ids"][:nl].copy(), table_ids=o["table_ids"][:nt], frame_mp=o["frame_mp"][:res.n], outlier=o["outlier"][:res.n],
                    in_view=o["in_view"][:nt])
         return out
+
+    # ---- Tracking::Relocalization: the refine chain of every pose hypothesis of a round in one call (include/rumi_track.h) ----
+    def reloc_default_params(self):
+        p = RumiRelocParams()
+        self._lib.rumi_reloc_default_params(C.byref(p))
+        return p
+
+    def reloc_begin_status(self, K4, cands, pts):
+        """The raw rumi_track_reloc_begin call: its status code.  cands: list of dicts kf_keys (KP_DTYPE [nkf]), kf_mp [nkf], matches [n]
+        (ids into pts, -1 NULL); pts: dict pos, min_dist, max_dist, desc, bad."""
+        K4 = np.ascontiguousarray(K4, np.float32)
+        keep = []
+        arr = (RumiRelocCandidate * max(len(cands), 1))()
+        for k, c in enumerate(cands):
+            kk = np.ascontiguousarray(c["kf_keys"], KP_DTYPE); km = np.ascontiguousarray(c["kf_mp"], np.int32); mt = np.ascontiguousarray(c["matches"], np.int32)
+            assert len(km) == len(kk) and len(mt) >= getattr(self, "_n", 0), "kf_mp covers the key-frame, matches the resident frame"
+            keep += [kk, km, mt]
+            arr[k] = RumiRelocCandidate(len(kk), capi.ptr(kk), capi.ptr(km), capi.ptr(mt))
+        n = len(pts["bad"])
+        a = dict(pos=np.ascontiguousarray(pts["pos"], np.float32).reshape(-1, 3), mn=np.ascontiguousarray(pts["min_dist"], np.float32),
+                 mx=np.ascontiguousarray(pts["max_dist"], np.float32), desc=np.ascontiguousarray(pts["desc"], np.uint8).reshape(-1, 32),
+                 bad=np.ascontiguousarray(pts["bad"], np.uint8))
+        assert len(a["pos"]) == len(a["mn"]) == len(a["mx"]) == len(a["desc"]) == n
+        P = RumiTrackPoints(n, capi.ptr(a["pos"]), None, capi.ptr(a["mn"]), capi.ptr(a["mx"]), capi.ptr(a["desc"]), None, capi.ptr(a["bad"]), None, None, None)
+        rc = self._lib.rumi_track_reloc_begin(self._h, capi.ptr(K4), len(cands), C.cast(arr, C.c_void_p), C.byref(P))
+        if rc == 0:
+            self._reloc_K = len(cands)
+        return rc
+
+    def reloc_begin(self, K4, cands, pts):
+        capi.check(self.reloc_begin_status(K4, cands, pts))
+
+    def reloc_refine_into(self, hyps, params, frame_mp, outlier_last, results):
+        """The raw rumi_track_reloc_refine call: its status code; outputs written in place.  hyps: list of (cand, Tcw7, inliers [n] u8; None = NULL)."""
+        H = len(hyps)
+        arr = (RumiRelocHypothesis * max(H, 1))()
+        keep = []
+        for h, (cand, T, inl) in enumerate(hyps):
+            if inl is not None:
+                inl = np.ascontiguousarray(inl, np.uint8)
+                assert len(inl) >= getattr(self, "_n", 0), "vbInliers covers the resident frame"
+                keep.append(inl)
+            arr[h] = RumiRelocHypothesis(int(cand), (C.c_float * 7)(*[float(x) for x in np.asarray(T, np.float32)]), capi.ptr(inl) if inl is not None else None)
+        return self._lib.rumi_track_reloc_refine(self._h, C.byref(params) if params is not None else None, H, C.cast(arr, C.c_void_p), capi.ptr(frame_mp),
+                                                 capi.ptr(outlier_last), capi.ptr(results))
+
+    def reloc_refine(self, hyps, params=None):
+        """rumi_track_reloc_refine -> (frame_mp [H, n] i32, outlier_last [H, n] u8 (255: never written), results [H] RELOC_RESULT_DTYPE)."""
+        H = len(hyps)
+        mp = np.full((max(H, 1), self.cap), -1, np.int32); ol = np.full((max(H, 1), self.cap), 255, np.uint8)
+        res = np.zeros(max(H, 1), RELOC_RESULT_DTYPE)
+        capi.check(self.reloc_refine_into(hyps, params, mp, ol, res))
+        n = self._n
+        return mp[:H, :n].copy(), ol[:H, :n].copy(), res[:H].copy()
+
+    def reloc_attempts(self):
+        """How often the last reloc_refine ran its chain (1: the candidate lists fitted their arena at once)."""
+        a = C.c_int32()
+        capi.check(self._lib.rumi_track_reloc_attempts(self._h, C.byref(a)))
+        return a.value
+
+
+def relocalize(tracker, cands, pts, solver_step, speculate_round=True, K4=None, params=None, frame_mp=None, outlier=None, Tcw=None):
+    """The round loop of Tracking::Relocalization (R/lib_src/Tracking.cc:3266-3348) over tracker.reloc_refine.  cands [K]: the candidates of
+    reloc_begin, None for one that is discarded from the start (isBad, or fewer than 15 BoW matches); with K4 the session is begun here,
+    otherwise the caller has begun it.  solver_step(i) -> (bTcw, bNoMore, inliers, Tcw7) is one `pSolver->iterate(5, ...)` of candidate i.
+    frame_mp / outlier / Tcw: the frame's mvpMapPoints, mvbOutlier and pose before the call (None: all NULL / false / None).
+
+    speculate_round: every live candidate of a round iterates, the round's hypotheses go to the device in ONE refine call, and the results are
+    replayed in candidate order up to and including the first that wins (ran & 2 and ngood_final >= enough) -- the reference's sequential rule;
+    the candidates behind the winner have then iterated once more than in the reference.  False: one hypothesis a call in the reference's
+    order, exactly its solver calls.  Both leave the same frame.
+    -> dict(matched, frame_mp, outlier, Tcw, winner (candidate or -1), rounds, steps [K] solver calls, refines)."""
+    K = len(cands)
+    if K4 is not None:
+        tracker.reloc_begin(K4, [c if c is not None else dict(kf_keys=np.zeros(0, KP_DTYPE), kf_mp=[], matches=np.full(getattr(tracker, "_n", 0), -1, np.int32))
+                                 for c in cands], pts)
+    enough = params.enough if params is not None else 50
+    discarded = [c is None for c in cands]
+    n_cand = discarded.count(False)
+    st = dict(matched=False, frame_mp=None if frame_mp is None else np.array(frame_mp, np.int32), outlier=None if outlier is None else np.array(outlier, np.uint8),
+              Tcw=None if Tcw is None else np.array(Tcw, np.float32), winner=-1, rounds=0, steps=[0] * K, refines=0)
+
+    def replay(cand, mp, ol, r):
+        """What the body of `for (i ...)` leaves in the frame for one hypothesis; True when it wins (:3342)."""
+        if st["outlier"] is None:
+            st["outlier"] = np.zeros(len(ol), np.uint8)
+        w = ol != 255
+        st["outlier"][w] = ol[w]
+        st["frame_mp"] = mp.copy(); st["Tcw"] = np.array(r["Tcw"], np.float32)
+        if (int(r["ran"]) & 2) and int(r["ngood_final"]) >= enough:
+            st["matched"] = True; st["winner"] = cand
+            return True
+        return False
+
+    def step(i):
+        st["steps"][i] += 1
+        b_tcw, b_no_more, inl, T = solver_step(i)
+        return b_tcw, b_no_more, inl, T
+
+    while n_cand > 0 and not st["matched"]:
+        st["rounds"] += 1
+        if speculate_round:
+            hyps = []
+            for i in range(K):
+                if discarded[i]:
+                    continue
+                b_tcw, b_no_more, inl, T = step(i)
+                if b_no_more:
+                    discarded[i] = True; n_cand -= 1
+                if b_tcw:
+                    hyps.append((i, T, inl))
+            if hyps:
+                mp, ol, res = tracker.reloc_refine(hyps, params)
+                st["refines"] += 1
+                for h, (i, _, _) in enumerate(hyps):
+                    if replay(i, mp[h], ol[h], res[h]):
+                        break
+        else:
+            for i in range(K):
+                if discarded[i]:
+                    continue
+                b_tcw, b_no_more, inl, T = step(i)
+                if b_no_more:
+                    discarded[i] = True; n_cand -= 1
+                if b_tcw:
+                    mp, ol, res = tracker.reloc_refine([(i, T, inl)], params)
+                    st["refines"] += 1
+                    if replay(i, mp[0], ol[0], res[0]):
+                        break
+    return st
