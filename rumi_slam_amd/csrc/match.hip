@@ -17,7 +17,8 @@
 //                    Then the rotation histogram / ComputeThreeMaxima filter and the result arrays.
 //   k_bruteforce_mfma  all-pairs best / second-best as an FP4 GEMM on the matrix cores.
 //
-//   match_queries.inc     k_queries_mappoints / frame / bow / sim3 / campoints / reloc / init, k_is_in_frustum
+//   match_queries.inc     k_queries_mappoints / frame / bow / sim3 / campoints / reloc / init, k_is_in_frustum (gates with one caller are written
+//                         out here; the shared ones are match_device.h's)
 //   match_candidates.inc  k_candidates<0 | 1 | 2> (candidates_walk, wave_bitonic_store, offsets_of), k_scan
 //   match_resolve.inc     k_resolve (ResolveArgs, match_host.h), k_resolve_init (InitArgs)
 //   match_reloc_batch.inc  k_reloc_walk<count | fill>, k_reloc_resolve: the relocalisation searches of every pose hypothesis (launch_reloc_search)
@@ -30,7 +31,10 @@
 //   match_bow_batch.inc   k_bow_batch_match, k_bow_batch_finish (BowKF, BowBatch) and rumi_search_by_bow_batch
 //   match_bow_kf_batch.inc  k_crb_match, k_crb_finish, k_crb_union (CrKF, CrArgs) and rumi_common_regions_bow
 //   match_submap.inc      k_grid_batch, k_submap_match, k_submap_compact (SubFrame, SubPair) and rumi_submap_match
-//   match_grid.h          grid_build_xy, the one-workgroup grid of k_grid_batch (shared with mapping.hip's k_sin_grid)
+//   match_device.h        what the kernels of match.hip, track.hip and mapping.hip share: Query, hamming256, the wave scans, rot_bin, and one body per
+//                         projection gate that has more than one caller (sim3_query, reloc_query, frustum_gate; se3f_camera_centre, pose_matrices19)
+//   match_grid.h          grid_build_xy, the one-workgroup grid of k_grid_batch (shared with mapping.hip's k_sin_grid); the GetFeaturesInArea window of
+//                         every walk: cell_window, window_gate, reproj_gate, and walk_window (16 lanes an item: mapping.hip's searches)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

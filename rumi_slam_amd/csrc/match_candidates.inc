@@ -33,15 +33,11 @@ __device__ __forceinline__ int candidates_walk(int mode, const Query &Q, const F
         }
         return Q.c1 - Q.c0;
     }
-    // Frame::GetFeaturesInArea (Frame.cc:695-750)
-    const int nMinCellX = max(0, (int)floorf((Q.u - F.minX - Q.r) * F.wInv));
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((Q.u - F.minX + Q.r) * F.wInv));
-    const int nMinCellY = max(0, (int)floorf((Q.v - F.minY - Q.r) * F.hInv));
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((Q.v - F.minY + Q.r) * F.hInv));
-    if (nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0) {
+    const CellWindow W = cell_window(Q.u, Q.v, Q.r, F.minX, F.minY, F.wInv, F.hInv);       // Frame::GetFeaturesInArea (Frame.cc:695-750)
+    if (W.any) {
         const bool checkLevels = Q.minLevel > 0 || Q.maxLevel >= 0;
-        for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-            const int p0 = F.cellStart[ix * kGridRows + nMinCellY], p1 = F.cellStart[ix * kGridRows + nMaxCellY + 1];
+        for (int ix = W.x0; ix <= W.x1; ix++) {
+            const int p0 = F.cellStart[ix * kGridRows + W.y0], p1 = F.cellStart[ix * kGridRows + W.y1 + 1];
             for (int base = p0; base < p1; base += 64) {
                 const int p = base + lane;
                 bool pass = false;
@@ -55,14 +51,8 @@ __device__ __forceinline__ int candidates_walk(int mode, const Query &Q, const F
                         if (oct < Q.minLevel) pass = false;
                         if (Q.maxLevel >= 0 && oct > Q.maxLevel) pass = false;
                     }
-                    const float dx = kp.x - Q.u, dy = kp.y - Q.v;
-                    if (!(fabsf(dx) < Q.r && fabsf(dy) < Q.r)) pass = false;
-                    if (mode == MODE_FUSE && Q.c0 && pass) {                        // mono reprojection gate, ORBmatcher.cc:1138-1145
-                        const float ex = Q.u - kp.x, ey = Q.v - kp.y;
-                        const float e2 = ex * ex + ey * ey;
-                        const float s2 = F.scale[oct] * F.scale[oct];              // mvLevelSigma2; mvInvLevelSigma2 = 1.0f / it
-                        if ((double)(e2 * (1.0f / s2)) > 5.99) pass = false;
-                    }
+                    if (!window_gate(kp.x, kp.y, Q.u, Q.v, Q.r)) pass = false;
+                    if (mode == MODE_FUSE && Q.c0 && pass && !reproj_gate(kp, Q.u, Q.v, F.scale)) pass = false;
                 }
                 const unsigned long long b = __ballot(pass);
                 if (FILL && pass) {
@@ -131,17 +121,13 @@ __global__ __launch_bounds__(256) void k_candidates(int mode, int nq, const Quer
         // instead of two walks of four loads per column: the cell ranges of all columns at once (one lane each), the window's
         // feature slots flat over the lanes (slot -> column by the prefix of the range lengths: the reference's candidate order),
         // key-point and descriptor of every slot fetched together, and up to 64 candidates ranked in registers.
-        const int nMinCellX = max(0, (int)floorf((Q.u - F.minX - Q.r) * F.wInv));
-        const int nMaxCellX = min(kGridCols - 1, (int)ceilf((Q.u - F.minX + Q.r) * F.wInv));
-        const int nMinCellY = max(0, (int)floorf((Q.v - F.minY - Q.r) * F.hInv));
-        const int nMaxCellY = min(kGridRows - 1, (int)ceilf((Q.v - F.minY + Q.r) * F.hInv));
-        int ncol = 0;
-        if (nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0 && nMaxCellY >= nMinCellY) ncol = max(0, nMaxCellX - nMinCellX + 1);
+        const CellWindow W = cell_window(Q.u, Q.v, Q.r, F.minX, F.minY, F.wInv, F.hInv);
+        const int ncol = W.any ? max(0, W.x1 - W.x0 + 1) : 0;
         int c0 = 0, len = 0;
         if (lane < ncol) {
-            const int cell = (nMinCellX + lane) * kGridRows;
-            c0 = F.cellStart[cell + nMinCellY];
-            len = F.cellStart[cell + nMaxCellY + 1] - c0;
+            const int cell = (W.x0 + lane) * kGridRows;
+            c0 = F.cellStart[cell + W.y0];
+            len = F.cellStart[cell + W.y1 + 1] - c0;
         }
         const uint32_t qmine = reinterpret_cast<const uint32_t *>(qDesc + (size_t)Q.descId * 32)[lane & 7];
         const int incl = wave_scan_incl_i32(len);
@@ -174,16 +160,9 @@ __global__ __launch_bounds__(256) void k_candidates(int mode, int nq, const Quer
                         if (oct < Q.minLevel) pass = false;
                         if (Q.maxLevel >= 0 && oct > Q.maxLevel) pass = false;
                     }
-                    const float dx = kp.x - Q.u, dy = kp.y - Q.v;
-                    if (!(fabsf(dx) < Q.r && fabsf(dy) < Q.r)) pass = false;
-                    if (mode == MODE_FUSE && Q.c0 && pass) {                        // mono reprojection gate, ORBmatcher.cc:1138-1145
-                        const float ex = Q.u - kp.x, ey = Q.v - kp.y;
-                        const float e2 = ex * ex + ey * ey;
-                        const float s2 = F.scale[oct] * F.scale[oct];              // mvLevelSigma2; mvInvLevelSigma2 = 1.0f / it
-                        if ((double)(e2 * (1.0f / s2)) > 5.99) pass = false;
-                    }
-                    d = __popc(qd[0] ^ d0.x) + __popc(qd[1] ^ d0.y) + __popc(qd[2] ^ d0.z) + __popc(qd[3] ^ d0.w) +
-                        __popc(qd[4] ^ d1.x) + __popc(qd[5] ^ d1.y) + __popc(qd[6] ^ d1.z) + __popc(qd[7] ^ d1.w);
+                    if (!window_gate(kp.x, kp.y, Q.u, Q.v, Q.r)) pass = false;
+                    if (mode == MODE_FUSE && Q.c0 && pass && !reproj_gate(kp, Q.u, Q.v, F.scale)) pass = false;
+                    d = hamming256(make_uint4(qd[0], qd[1], qd[2], qd[3]), make_uint4(qd[4], qd[5], qd[6], qd[7]), d0, d1);
                 }
                 b = __ballot(pass);
                 if (pass) {

@@ -1,5 +1,5 @@
-// Device helpers the matcher kernels (match.hip and its match_*.inc parts: queries, candidates, resolve, tri, bow_batch), the Tracking step (track.hip)
-// and the mapping kernels (mapping.hip) share.
+// Device helpers the matcher kernels (match.hip and its match_*.inc parts: queries, candidates, resolve, tri, bow_batch, reloc_batch), the Tracking
+// step (track.hip) and the mapping kernels (mapping.hip) share, among them the one body of every projection gate that has more than one caller.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -13,6 +13,10 @@ __device__ __forceinline__ int hamming256(const uint32_t q[8], const uint32_t *d
 #pragma unroll
     for (int k = 0; k < 8; k++) s += __popc(q[k] ^ d[k]);
     return s;
+}
+__device__ __forceinline__ int hamming256(const uint4 &q0, const uint4 &q1, const uint4 &d0, const uint4 &d1) {   // two rows held as 16-byte halves
+    return __popc(q0.x ^ d0.x) + __popc(q0.y ^ d0.y) + __popc(q0.z ^ d0.z) + __popc(q0.w ^ d0.w) +
+           __popc(q1.x ^ d1.x) + __popc(q1.y ^ d1.y) + __popc(q1.z ^ d1.z) + __popc(q1.w ^ d1.w);
 }
 
 // inclusive prefix sum over the lanes of a wave by DPP (row prefix, row_bcast:15, row_bcast:31); lane 63 holds the total
@@ -115,6 +119,46 @@ __device__ __forceinline__ Query sim3_query(const float *p3Dw, const float *Pn, 
     return o;
 }
 
+// Sophus::SE3f::inverse().translation(): conj(q) * (-t) by the quaternion's _transformVector, for Frame::UpdatePoseMatrices (pose_matrices19) and
+// for a pose hypothesis of the relocalisation walk (match_reloc_batch.inc), which the facade forms with the same expression.
+__device__ __forceinline__ void se3f_camera_centre(const float *T7, float *Ow) {
+    const float qx = -T7[0], qy = -T7[1], qz = -T7[2], qw = T7[3];
+    const float v0 = T7[4] * -1.f, v1 = T7[5] * -1.f, v2 = T7[6] * -1.f;
+    float u0 = qy * v2 - qz * v1, u1 = qz * v0 - qx * v2, u2 = qx * v1 - qy * v0;
+    u0 += u0; u1 += u1; u2 += u2;
+    const float c0 = qy * u2 - qz * u1, c1 = qz * u0 - qx * u2, c2 = qx * u1 - qy * u0;
+    Ow[0] = (v0 + qw * u0) + c0; Ow[1] = (v1 + qw * u1) + c1; Ow[2] = (v2 + qw * u2) + c2;
+}
+
+// The query of one key-frame feature for SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:1700-1733): no depth
+// test, the closed rectangle that lets a NaN projection through, the distance on xw - Ow, levels [L - 1, L + 1].  One body for k_queries_reloc
+// (match_queries.inc) and k_reloc_walk<false> (match_reloc_batch.inc).  mp: the feature's map point (< 0: none); skip: the caller's
+// "bad or already found", read only where mp >= 0.  The angle is the key-frame feature's, kept whether or not the point is searched.
+__device__ __forceinline__ Query reloc_query(int mp, bool skip, const float *mpPos, const float *mpMinDist, const float *mpMaxDist, const float *Tcw,
+                                             const float *K, const float *Ow, const float *scaleFactors, int nLevels, float logScaleFactor, float th,
+                                             float minX, float minY, float maxX, float maxY, float angle) {
+    Query o{};
+    if (mp >= 0 && !skip) {
+        const float *xw = mpPos + (size_t)mp * 3;
+        float pc[3];
+        se3f_mul(Tcw, xw, pc);
+        const float u = K[0] * pc[0] / pc[2] + K[2], v = K[1] * pc[1] / pc[2] + K[3];
+        if (!(u < minX || u > maxX) && !(v < minY || v > maxY)) {
+            const float P0 = xw[0] - Ow[0], P1 = xw[1] - Ow[1], P2 = xw[2] - Ow[2];
+            const float dist3D = sqrtf((P0 * P0 + P1 * P1) + P2 * P2);
+            const float maxD = 1.2f * mpMaxDist[mp], minD = 0.8f * mpMinDist[mp];
+            if (!(dist3D < minD || dist3D > maxD)) {
+                const int lvl = predict_scale(mpMaxDist[mp], dist3D, logScaleFactor, nLevels);
+                o.valid = 1; o.u = u; o.v = v; o.r = th * scaleFactors[lvl];
+                o.minLevel = lvl - 1; o.maxLevel = lvl + 1;
+            }
+        }
+        o.descId = mp; o.mpId = mp; o.blocks = 1;
+    }
+    o.angle = angle;
+    return o;
+}
+
 // A 16-byte load that asks for 4-byte alignment only (the extractor's descriptor kernel loads its rows the same way, orb_orient_desc.inc):
 // one wide instruction where the address happens to be aligned, never a fault where a row is not.
 struct __attribute__((packed, aligned(4))) Dword4 { uint32_t x, y, z, w; };
@@ -152,7 +196,7 @@ __device__ __forceinline__ void gather_correspondences(int n, const RumiKeyPoint
 }
 
 // Frame::UpdatePoseMatrices (Frame.cc:522-528) in Sophus' / Eigen's float arithmetic: Rcw = q.toRotationMatrix(), tcw, Ow = conj(q) * (-tcw)
-// (quaternion _transformVector), as [Rcw9 | tcw3 | Ow3 | K4] for the frustum test.
+// (se3f_camera_centre), as [Rcw9 | tcw3 | Ow3 | K4] for the frustum test.
 __device__ __forceinline__ void pose_matrices19(const float *Tcw7, const float *K4, float *pose19) {
     const float x = Tcw7[0], y = Tcw7[1], z = Tcw7[2], w = Tcw7[3];
     const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z;
@@ -162,12 +206,41 @@ __device__ __forceinline__ void pose_matrices19(const float *Tcw7, const float *
     pose19[6] = txz - twy; pose19[7] = tyz + twx; pose19[8] = 1.f - (txx + tyy);
     const float t0 = Tcw7[4], t1 = Tcw7[5], t2 = Tcw7[6];
     pose19[9] = t0; pose19[10] = t1; pose19[11] = t2;
-    const float qx = -x, qy = -y, qz = -z, v0 = t0 * -1.f, v1 = t1 * -1.f, v2 = t2 * -1.f;
-    float u0 = qy * v2 - qz * v1, u1 = qz * v0 - qx * v2, u2 = qx * v1 - qy * v0;
-    u0 += u0; u1 += u1; u2 += u2;
-    const float c0 = qy * u2 - qz * u1, c1 = qz * u0 - qx * u2, c2 = qx * u1 - qy * u0;
-    pose19[12] = (v0 + w * u0) + c0; pose19[13] = (v1 + w * u1) + c1; pose19[14] = (v2 + w * u2) + c2;
+    se3f_camera_centre(Tcw7, pose19 + 12);
     pose19[15] = K4[0]; pose19[16] = K4[1]; pose19[17] = K4[2]; pose19[18] = K4[3];
+}
+
+// Frame::isInFrustum (Frame.cc:558-617, mono) of one map point against [Rcw9 | tcw3 | Ow3 | K4]: depth sign, the closed image rectangle, the
+// distance range, the viewing cosine, PredictScale.  One body for k_is_in_frustum (match_queries.inc) and the tracker's fused form (frustum_body,
+// track.hip).  px, py stand once the rectangle passes; lvl, viewCos and depth (|Pc|) only for a point in view.  The distances and the normal are read
+// where the chain reaches them, hence the pointers.
+struct FrustumResult { uint8_t in; float px, py; int lvl; float viewCos, depth; };
+__device__ __forceinline__ FrustumResult frustum_gate(const float *P, const float *Pn, const float *minDist, const float *maxDist, const float *pose19,
+                                                      float minX, float minY, float maxX, float maxY, float logScaleFactor, int nLevels,
+                                                      float viewingCosLimit) {
+    const float *R = pose19, *t = pose19 + 9, *Ow = pose19 + 12, *K = pose19 + 15;
+    FrustumResult o{0, -1, -1, 0, 0, 0};
+    float Pc[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++) Pc[r] = ((R[r * 3] * P[0] + R[r * 3 + 1] * P[1]) + R[r * 3 + 2] * P[2]) + t[r];
+    const float Pc_dist = sqrtf((Pc[0] * Pc[0] + Pc[1] * Pc[1]) + Pc[2] * Pc[2]);
+    if (!(Pc[2] < 0.0f)) {
+        const float u = K[0] * Pc[0] / Pc[2] + K[2], v = K[1] * Pc[1] / Pc[2] + K[3];
+        if (!(u < minX || u > maxX) && !(v < minY || v > maxY)) {
+            o.px = u; o.py = v;
+            const float maxD = 1.2f * *maxDist, minD = 0.8f * *minDist;
+            const float P0 = P[0] - Ow[0], P1 = P[1] - Ow[1], P2 = P[2] - Ow[2];
+            const float dist = sqrtf((P0 * P0 + P1 * P1) + P2 * P2);
+            if (!(dist < minD || dist > maxD)) {
+                const float viewCos = ((P0 * Pn[0] + P1 * Pn[1]) + P2 * Pn[2]) / dist;
+                if (!(viewCos < viewingCosLimit)) {
+                    o.lvl = predict_scale(*maxDist, dist, logScaleFactor, nLevels);
+                    o.in = 1; o.depth = Pc_dist; o.viewCos = viewCos;
+                }
+            }
+        }
+    }
+    return o;
 }
 
 }  // namespace rumi

@@ -1,4 +1,5 @@
-// The 64 x 48 grid of one frame by one workgroup, for the kernels that build many grids in one launch (match.hip, mapping.hip).
+// The 64 x 48 grid of one frame by one workgroup, for the kernels that build many grids in one launch, and the window every search walks in
+// such a grid (match.hip, mapping.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -71,6 +72,65 @@ __device__ __forceinline__ void grid_build_xy(int n, const float *__restrict__ x
     }
     __syncthreads();
     for (int i = tid; i < total; i += 1024) sortedIdx[i] = sOut[i];
+}
+
+// ---- the window of Frame::GetFeaturesInArea (Frame.cc:695-750; KeyFrame.cc:887-925) and its per-candidate tests --------------------------------
+// The cell range of the window (u, v) +- r, clamped, and whether the member gets past its early returns.  `any` also asks for y1 >= y0, which the
+// reference does not test: cellStart is a non-decreasing prefix over column-major cells, so y1 < y0 makes a column's range [cellStart[ix * rows + y0],
+// cellStart[ix * rows + y1 + 1]) end at or before its start and every walk of it empty, as the reference's two nested cell loops are.  A walk may
+// therefore test it or not; the fast path of k_candidates takes the LENGTH of that range and needs it, so the one form tests it everywhere.
+struct CellWindow { int x0, x1, y0, y1; bool any; };
+__device__ __forceinline__ CellWindow cell_window(float u, float v, float r, float minX, float minY, float wInv, float hInv) {
+    CellWindow w;
+    w.x0 = max(0, (int)floorf((u - minX - r) * wInv));
+    w.x1 = min(kGridCols - 1, (int)ceilf((u - minX + r) * wInv));
+    w.y0 = max(0, (int)floorf((v - minY - r) * hInv));
+    w.y1 = min(kGridRows - 1, (int)ceilf((v - minY + r) * hInv));
+    w.any = w.x0 < kGridCols && w.x1 >= 0 && w.y0 < kGridRows && w.y1 >= 0 && w.y1 >= w.y0;
+    return w;
+}
+
+// the member's own test of a candidate against the window (the cells overhang it), and with the level range of the members that have one
+__device__ __forceinline__ bool window_gate(float x, float y, float u, float v, float r) {
+    const float dx = x - u, dy = y - v;
+    return fabsf(dx) < r && fabsf(dy) < r;
+}
+__device__ __forceinline__ bool window_gate(const RumiKeyPoint &kp, float u, float v, float r, int minLevel, int maxLevel) {
+    return !(kp.octave < minLevel) && !(kp.octave > maxLevel) && window_gate(kp.x, kp.y, u, v, r);
+}
+
+// the monocular reprojection gate of Fuse (ORBmatcher.cc:1138-1145): chi2 at the candidate's level against 5.99, in the reference's types
+__device__ __forceinline__ bool reproj_gate(const RumiKeyPoint &kp, float u, float v, const float *scale) {
+    const float ex = u - kp.x, ey = v - kp.y;
+    const float e2 = ex * ex + ey * ey;
+    const float s2 = scale[kp.octave] * scale[kp.octave];                  // mvLevelSigma2; mvInvLevelSigma2 = 1.0f / it
+    return !((double)(e2 * (1.0f / s2)) > 5.99);
+}
+
+// One frame's grid as a walk reads it.
+struct GridView {
+    const RumiKeyPoint *keys; const uint16_t *sorted; const int32_t *cellStart;
+    float minX, minY, wInv, hInv;
+};
+
+// The window walk by LANES lanes per item (sub: this lane's place among them): the candidates in the member's order (cell column, cell row, ascending
+// feature index) that pass window_gate, each handed to visit(feature, key-point, place in the walk).  The place grows along the walk (a column's
+// range rounded up to whole trips of LANES), so it orders the candidates as the reference meets them, whichever lane sees which.
+template <int LANES, class Visit>
+__device__ __forceinline__ void walk_window(const GridView &G, float u, float v, float r, int minLevel, int maxLevel, int sub, Visit &&visit) {
+    const CellWindow W = cell_window(u, v, r, G.minX, G.minY, G.wInv, G.hInv);
+    if (!W.any) return;
+    int order = 0;
+    for (int ix = W.x0; ix <= W.x1; ix++) {
+        const int p0 = G.cellStart[ix * kGridRows + W.y0], p1 = G.cellStart[ix * kGridRows + W.y1 + 1];
+        for (int base = p0; base < p1; base += LANES, order += LANES) {
+            const int c = base + sub;
+            if (c >= p1) continue;
+            const int idx = G.sorted[c];
+            const RumiKeyPoint kp = G.keys[idx];
+            if (window_gate(kp, u, v, r, minLevel, maxLevel)) visit(idx, kp, order + sub);
+        }
+    }
 }
 
 }  // namespace rumi

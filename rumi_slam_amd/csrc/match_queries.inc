@@ -110,34 +110,15 @@ __global__ void k_queries_campoints(int n, const uint8_t *skip, const float *pc,
     q[i] = o;
 }
 
-// SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist): ORBmatcher.cc:1700-1733
+// SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist): ORBmatcher.cc:1700-1733; the gate is reloc_query (match_device.h)
 __global__ void k_queries_reloc(int nkf, const RumiKeyPoint *kfKeys, const int32_t *kfMp, const uint8_t *skip, const float *mpPos,
                                 const float *mpMinDist, const float *mpMaxDist, const float *pose, const float *scaleFactors, int nLevels,
                                 float logScaleFactor, float th, float minX, float minY, float maxX, float maxY, Query *q) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nkf) return;
-    Query o{};
     const int mp = kfMp[i];
-    const float *Tcw = pose, *K = pose + 7, *Ow = pose + 11;
-    if (mp >= 0 && !skip[mp]) {
-        const float *xw = mpPos + (size_t)mp * 3;
-        float pc[3];
-        se3f_mul(Tcw, xw, pc);
-        const float u = K[0] * pc[0] / pc[2] + K[2], v = K[1] * pc[1] / pc[2] + K[3];
-        if (!(u < minX || u > maxX) && !(v < minY || v > maxY)) {
-            const float P0 = xw[0] - Ow[0], P1 = xw[1] - Ow[1], P2 = xw[2] - Ow[2];
-            const float dist3D = sqrtf((P0 * P0 + P1 * P1) + P2 * P2);
-            const float maxD = 1.2f * mpMaxDist[mp], minD = 0.8f * mpMinDist[mp];
-            if (!(dist3D < minD || dist3D > maxD)) {
-                const int lvl = predict_scale(mpMaxDist[mp], dist3D, logScaleFactor, nLevels);
-                o.valid = 1; o.u = u; o.v = v; o.r = th * scaleFactors[lvl];
-                o.minLevel = lvl - 1; o.maxLevel = lvl + 1;
-            }
-        }
-        o.descId = mp; o.mpId = mp; o.blocks = 1;
-    }
-    o.angle = kfKeys[i].angle;
-    q[i] = o;
+    q[i] = reloc_query(mp, mp >= 0 && skip[mp], mpPos, mpMinDist, mpMaxDist, pose, pose + 7, pose + 11, scaleFactors, nLevels, logScaleFactor, th,
+                       minX, minY, maxX, maxY, kfKeys[i].angle);
 }
 
 // SearchForInitialization: level-0 key-points of F1, window around vbPrevMatched (ORBmatcher.cc:593-602)
@@ -152,7 +133,7 @@ __global__ void k_queries_init(int n1, const RumiKeyPoint *keys1, const float *p
     q[i] = o;
 }
 
-// Frame::isInFrustum (Frame.cc:558-617, mono): one lane per map point
+// Frame::isInFrustum (Frame.cc:558-617, mono): one lane per map point; the chain is frustum_gate (match_device.h)
 __global__ void k_is_in_frustum(int nmp, const float *pose /*Rcw9 tcw3 Ow3 K4*/, float minX, float minY, float maxX, float maxY,
                                 float logScaleFactor, int nLevels, float viewingCosLimit, const float *mpPos, const float *mpNormal,
                                 const float *mpMinDist, const float *mpMaxDist, uint8_t *inView, float *projX, float *projY,
@@ -163,31 +144,7 @@ __global__ void k_is_in_frustum(int nmp, const float *pose /*Rcw9 tcw3 Ow3 K4*/,
         inView[i] = 0; projX[i] = -1; projY[i] = -1; scaleLevel[i] = 0; viewCosOut[i] = 0; trackDepth[i] = 0;
         return;
     }
-    const float *R = pose, *t = pose + 9, *Ow = pose + 12, *K = pose + 15;
-    const float *P = mpPos + (size_t)i * 3;
-    uint8_t in = 0;
-    float px = -1, py = -1, vc = 0, depth = 0;
-    int lvl = 0;
-    float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) Pc[r] = ((R[r * 3] * P[0] + R[r * 3 + 1] * P[1]) + R[r * 3 + 2] * P[2]) + t[r];
-    const float Pc_dist = sqrtf((Pc[0] * Pc[0] + Pc[1] * Pc[1]) + Pc[2] * Pc[2]);
-    if (!(Pc[2] < 0.0f)) {
-        const float u = K[0] * Pc[0] / Pc[2] + K[2], v = K[1] * Pc[1] / Pc[2] + K[3];
-        if (!(u < minX || u > maxX) && !(v < minY || v > maxY)) {
-            px = u; py = v;
-            const float maxD = 1.2f * mpMaxDist[i], minD = 0.8f * mpMinDist[i];
-            const float P0 = P[0] - Ow[0], P1 = P[1] - Ow[1], P2 = P[2] - Ow[2];
-            const float dist = sqrtf((P0 * P0 + P1 * P1) + P2 * P2);
-            if (!(dist < minD || dist > maxD)) {
-                const float *Pn = mpNormal + (size_t)i * 3;
-                const float viewCos = ((P0 * Pn[0] + P1 * Pn[1]) + P2 * Pn[2]) / dist;
-                if (!(viewCos < viewingCosLimit)) {
-                    lvl = predict_scale(mpMaxDist[i], dist, logScaleFactor, nLevels);
-                    in = 1; depth = Pc_dist; vc = viewCos;
-                }
-            }
-        }
-    }
-    inView[i] = in; projX[i] = px; projY[i] = py; scaleLevel[i] = lvl; viewCosOut[i] = vc; trackDepth[i] = depth;
+    const FrustumResult f = frustum_gate(mpPos + (size_t)i * 3, mpNormal + (size_t)i * 3, mpMinDist + i, mpMaxDist + i, pose, minX, minY, maxX, maxY,
+                                         logScaleFactor, nLevels, viewingCosLimit);
+    inView[i] = f.in; projX[i] = f.px; projY[i] = f.py; scaleLevel[i] = f.lvl; viewCosOut[i] = f.viewCos; trackDepth[i] = f.depth;
 }

@@ -3,10 +3,10 @@
 // launch_reloc_search (match_host.h) from track.hip.  The shape is sim3_projection_batch.inc's: a wave per (hypothesis, key-frame feature), count /
 // allocate / fill, one ordered fix-point resolve per hypothesis.
 //
-//   k_reloc_walk<false>  the gate of k_queries_reloc (its arithmetic restated operation by operation: the single entry keeps its own kernel) with
-//                        skip = bad | sFound bitmap and the hypothesis' own pose and camera centre, the query kept for the later passes; then the
-//                        window walk of candidates_walk in GetFeaturesInArea order, COUNTING the candidates within ORBdist; lane 0 takes the list
-//                        space with one atomicAdd on the stage's total.
+//   k_reloc_walk<false>  the gate of k_queries_reloc (reloc_query, match_device.h: one body for both; the single entry keeps its own kernel) with
+//                        skip = bad | sFound bitmap and the hypothesis' own pose and camera centre (se3f_camera_centre), the query kept for the
+//                        later passes; then the window walk of candidates_walk in GetFeaturesInArea order (cell_window, window_gate: match_grid.h),
+//                        COUNTING the candidates within ORBdist; lane 0 takes the list space with one atomicAdd on the stage's total.
 //   k_reloc_walk<true>   the same walk FILLS (distance << 20 | place among the kept, feature).  Exact for any list length.
 //   k_reloc_resolve      k_resolve's MODE_RELOC body, one workgroup per hypothesis: blockedFrom[nfeat] in LDS seeded from featMp[h][f] >= 0,
 //                        the fix point, the rotation histogram and ComputeThreeMaxima, the frame's vector; thread 0 then decides the next stage.
@@ -15,15 +15,6 @@
 // minimum key.  A hypothesis whose live bit is clear costs one wave-uniform load per workgroup.  Integer atomics only; where a list lies depends
 // on arrival, no result does.  When the lists outgrow the arena the fill and the resolve do nothing and the host repeats the whole refine with
 // a larger one.
-
-__device__ __forceinline__ void reloc_camera_centre(const float *T7, float *Ow) {       // Sophus::SE3f::inverse().translation(), as the facade forms it
-    const float qx = -T7[0], qy = -T7[1], qz = -T7[2], qw = T7[3];
-    const float p[3] = {T7[4] * -1.f, T7[5] * -1.f, T7[6] * -1.f};
-    float u0 = qy * p[2] - qz * p[1], u1 = qz * p[0] - qx * p[2], u2 = qx * p[1] - qy * p[0];
-    u0 += u0; u1 += u1; u2 += u2;
-    const float c0 = qy * u2 - qz * u1, c1 = qz * u0 - qx * u2, c2 = qx * u1 - qy * u0;
-    Ow[0] = (p[0] + qw * u0) + c0; Ow[1] = (p[1] + qw * u1) + c1; Ow[2] = (p[2] + qw * u2) + c2;
-}
 
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_reloc_walk(RelocSearchArgs A) {
@@ -40,27 +31,11 @@ __global__ __launch_bounds__(256) void k_reloc_walk(RelocSearchArgs A) {
     Query Q{};
     if (!FILL) {                                            // ORBmatcher.cc:1700-1733
         const int mp = A.kfMp[C.keyOff + i];
-        const float *Tcw = A.T + (size_t)h * 7, *K = A.K;
+        const float *Tcw = A.T + (size_t)h * 7;
         float Ow[3];
-        reloc_camera_centre(Tcw, Ow);
-        if (mp >= 0 && !(A.bad[mp] | ((A.found[(size_t)h * A.words + (mp >> 5)] >> (mp & 31)) & 1u))) {
-            const float *xw = A.pos + (size_t)mp * 3;
-            float pc[3];
-            se3f_mul(Tcw, xw, pc);
-            const float u = K[0] * pc[0] / pc[2] + K[2], v = K[1] * pc[1] / pc[2] + K[3];
-            if (!(u < F.minX || u > F.maxX) && !(v < F.minY || v > F.maxY)) {
-                const float P0 = xw[0] - Ow[0], P1 = xw[1] - Ow[1], P2 = xw[2] - Ow[2];
-                const float dist3D = sqrtf((P0 * P0 + P1 * P1) + P2 * P2);
-                const float maxD = 1.2f * A.maxD[mp], minD = 0.8f * A.minD[mp];
-                if (!(dist3D < minD || dist3D > maxD)) {
-                    const int lvl = predict_scale(A.maxD[mp], dist3D, A.logSf, A.nLevels);
-                    Q.valid = 1; Q.u = u; Q.v = v; Q.r = A.th * F.scale[lvl];
-                    Q.minLevel = lvl - 1; Q.maxLevel = lvl + 1;
-                }
-            }
-            Q.descId = mp; Q.mpId = mp; Q.blocks = 1;
-        }
-        Q.angle = A.kfKeys[C.keyOff + i].angle;
+        se3f_camera_centre(Tcw, Ow);
+        Q = reloc_query(mp, mp >= 0 && (A.bad[mp] | ((A.found[(size_t)h * A.words + (mp >> 5)] >> (mp & 31)) & 1u)), A.pos, A.minD, A.maxD, Tcw, A.K, Ow,
+                        F.scale, A.nLevels, A.logSf, A.th, F.minX, F.minY, F.maxX, F.maxY, A.kfKeys[C.keyOff + i].angle);
         if (lane == 0) A.q[pair] = Q;
     } else Q = A.q[pair];
     if (!Q.valid) {
@@ -76,13 +51,10 @@ __global__ __launch_bounds__(256) void k_reloc_walk(RelocSearchArgs A) {
     const int listAt = FILL ? A.pairBase[pair] : 0, listLen = FILL ? A.pairCount[pair] : 0;
     int count = 0;
     // Frame::GetFeaturesInArea (Frame.cc:695-750), as candidates_walk visits it
-    const int nMinCellX = max(0, (int)floorf((Q.u - F.minX - Q.r) * F.wInv));
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((Q.u - F.minX + Q.r) * F.wInv));
-    const int nMinCellY = max(0, (int)floorf((Q.v - F.minY - Q.r) * F.hInv));
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((Q.v - F.minY + Q.r) * F.hInv));
-    if (nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0) {
-        for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-            const int p0 = F.cellStart[ix * kGridRows + nMinCellY], p1 = F.cellStart[ix * kGridRows + nMaxCellY + 1];
+    const CellWindow W = cell_window(Q.u, Q.v, Q.r, F.minX, F.minY, F.wInv, F.hInv);
+    if (W.any) {
+        for (int ix = W.x0; ix <= W.x1; ix++) {
+            const int p0 = F.cellStart[ix * kGridRows + W.y0], p1 = F.cellStart[ix * kGridRows + W.y1 + 1];
             for (int base = p0; base < p1; base += 64) {
                 const int p = base + lane;
                 bool pass = false;
@@ -90,10 +62,7 @@ __global__ __launch_bounds__(256) void k_reloc_walk(RelocSearchArgs A) {
                 if (p < p1) {
                     idx = F.sortedIdx[p];
                     const RumiKeyPoint kp = F.keys[idx];
-                    const int oct = kp.octave;
-                    pass = !(oct < Q.minLevel) && !(oct > Q.maxLevel);          // (maxLevel >= 1 here: the level test always applies)
-                    const float dx = kp.x - Q.u, dy = kp.y - Q.v;
-                    if (!(fabsf(dx) < Q.r && fabsf(dy) < Q.r)) pass = false;
+                    pass = window_gate(kp, Q.u, Q.v, Q.r, Q.minLevel, Q.maxLevel);    // (maxLevel >= 1 here: the level test always applies)
                     if (pass && (uint32_t)idx < (uint32_t)A.nfeat) {
                         d = hamming256(qd, reinterpret_cast<const uint32_t *>(F.desc + (size_t)idx * 32));
                         if (d > A.orbDist) pass = false;                        // the cut (above)

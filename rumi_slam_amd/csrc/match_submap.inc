@@ -50,21 +50,17 @@ __global__ __launch_bounds__(256) void k_submap_match(const SubFrame *__restrict
     if (i1 < A.n && A.hasMp[i1]) {            // a query without a map point keeps nothing, whatever its candidates are (:532)
         const float u = A.keys[2 * i1], v = A.keys[2 * i1 + 1];
         // KeyFrame::GetFeaturesInArea(u, v, r), KeyFrame.cc:894-908, with its four early returns
-        const int nMinCellX = max(0, (int)floorf((u - B.minX - r) * B.wInv));
-        const int nMaxCellX = min(kGridCols - 1, (int)ceilf((u - B.minX + r) * B.wInv));
-        const int nMinCellY = max(0, (int)floorf((v - B.minY - r) * B.hInv));
-        const int nMaxCellY = min(kGridRows - 1, (int)ceilf((v - B.minY + r) * B.hInv));
-        if (nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0) {
+        const CellWindow W = cell_window(u, v, r, B.minX, B.minY, B.wInv, B.hInv);
+        if (W.any) {
             const uint16_t *S = sorted + B.sortedOff;
             const int32_t *CS = cellStart + (size_t)B.grid * (kGridCells + 1);
             float bestDist = r;
-            for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
+            for (int ix = W.x0; ix <= W.x1; ix++) {
                 // the cells of one column lie one behind the other, each in ascending key-point index: the reference's candidate order
-                const int p0 = CS[ix * kGridRows + nMinCellY], p1 = CS[ix * kGridRows + nMaxCellY + 1];
+                const int p0 = CS[ix * kGridRows + W.y0], p1 = CS[ix * kGridRows + W.y1 + 1];
                 for (int p = p0; p < p1; p++) {
                     const int i2 = S[p];
-                    const float dx = B.keysUn[2 * i2] - u, dy = B.keysUn[2 * i2 + 1] - v;     // the gate: mvKeysUn of key-frame 2 against mvKeys of 1
-                    if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
+                    if (!window_gate(B.keysUn[2 * i2], B.keysUn[2 * i2 + 1], u, v, r)) continue;     // the gate: mvKeysUn of key-frame 2 against mvKeys of 1
                     // (float)sqrt(pow(u1 - u2, 2) + pow(v1 - v2, 2)), :531: float differences of the two mvKeys, the rest in double
                     const double ex = (double)(u - B.keys[2 * i2]), ey = (double)(v - B.keys[2 * i2 + 1]);
                     const float d = (float)sqrt(ex * ex + ey * ey);

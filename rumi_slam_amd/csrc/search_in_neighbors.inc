@@ -185,57 +185,29 @@ __global__ __launch_bounds__(256) void k_sin_fwd_gate(SinArgs a) {
     sin_push(a, q.valid != 0, q, (uint32_t)at);
 }
 
-// The window walk of one work item, kSinLanes lanes each: the candidates of Frame::GetFeaturesInArea (Frame.cc:695-750) in its order (cell
-// column, cell row, ascending feature index), the level window [level - 1, level] and the strict `dist < bestDist`: the key
-// (distance << 16 | place in the walk) has one minimum, the earliest of the nearest.  REPROJ: the monocular reprojection gate (5.99) of
-// ORBmatcher.cc:1138-1145, which Fuse(KF, MapPoints) has and Fuse(KF, Scw, MapPoints) (:1258-1274, search_and_fuse.inc) has not.  The tests are
-// those of candidates_walk (match_candidates.inc, MODE_FUSE), expression for expression.  One body for k_sin_search and k_saf_search.
+// The window walk of one work item, kSinLanes lanes each (walk_window, match_grid.h): the candidates of Frame::GetFeaturesInArea (Frame.cc:695-750)
+// in its order, the level window [level - 1, level] and the strict `dist < bestDist`: the key (distance << 16 | place in the walk) has one
+// minimum, the earliest of the nearest.  REPROJ: the monocular reprojection gate (5.99) of ORBmatcher.cc:1138-1145 (reproj_gate, the one
+// candidates_walk applies in MODE_FUSE), which Fuse(KF, MapPoints) has and Fuse(KF, Scw, MapPoints) (:1258-1274, search_and_fuse.inc) has not.
+// One body for k_sin_search and k_saf_search.
 template <bool REPROJ>
 __device__ __forceinline__ void sin_walk(const SinArgs &a, int k, int p, const uint4 &item, int sub, uint32_t &bestKey, int &bestIdx) {
     const SinKF &F = a.tab[k];
     const uint8_t *R8 = a.feat + F.block;
     const CovisFeatRec *R = reinterpret_cast<const CovisFeatRec *>(R8);
-    const RumiKeyPoint *keys = reinterpret_cast<const RumiKeyPoint *>(R8 + R->keys);
     const uint8_t *desc = R8 + R->desc;
     const float *scale = reinterpret_cast<const float *>(R8 + R->scale);
-    const uint16_t *S = a.sorted + F.sortedOff;
-    const int32_t *CS = a.cellStart + (size_t)k * (kGridCells + 1);
+    const GridView G{reinterpret_cast<const RumiKeyPoint *>(R8 + R->keys), a.sorted + F.sortedOff, a.cellStart + (size_t)k * (kGridCells + 1),
+                     F.bounds[0], F.bounds[1], F.wInv, F.hInv};
     const uint4 q0 = ld16_dword(a.attr + (size_t)p * kCovisAttrWords + 8), q1 = ld16_dword(a.attr + (size_t)p * kCovisAttrWords + 12);
     const float u = __uint_as_float(item.x), v = __uint_as_float(item.y);
-    const int maxLevel = (int)item.w, minLevel = maxLevel - 1;
-    const float r = a.th * scale[maxLevel];
-    // Frame::GetFeaturesInArea (Frame.cc:695-750)
-    const int nMinCellX = max(0, (int)floorf((u - F.bounds[0] - r) * F.wInv));
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((u - F.bounds[0] + r) * F.wInv));
-    const int nMinCellY = max(0, (int)floorf((v - F.bounds[1] - r) * F.hInv));
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((v - F.bounds[1] + r) * F.hInv));
-    if (nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0 && nMaxCellY >= nMinCellY) {
-        int order = 0;
-        for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-            const int p0 = CS[ix * kGridRows + nMinCellY], p1 = CS[ix * kGridRows + nMaxCellY + 1];
-            for (int base = p0; base < p1; base += kSinLanes, order += kSinLanes) {
-                const int c = base + sub;
-                if (c >= p1) continue;
-                const int idx = S[c];
-                const RumiKeyPoint kp = keys[idx];
-                const int oct = kp.octave;
-                if (oct < minLevel || oct > maxLevel) continue;
-                const float dx = kp.x - u, dy = kp.y - v;
-                if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
-                if (REPROJ) {
-                    const float ex = u - kp.x, ey = v - kp.y;           // mono reprojection gate, ORBmatcher.cc:1138-1145
-                    const float e2 = ex * ex + ey * ey;
-                    const float s2 = scale[oct] * scale[oct];           // mvLevelSigma2; mvInvLevelSigma2 = 1.0f / it
-                    if ((double)(e2 * (1.0f / s2)) > 5.99) continue;
-                }
-                const uint4 d0 = ld16_dword(desc + (size_t)idx * 32), d1 = ld16_dword(desc + (size_t)idx * 32 + 16);
-                const int d = __popc(q0.x ^ d0.x) + __popc(q0.y ^ d0.y) + __popc(q0.z ^ d0.z) + __popc(q0.w ^ d0.w) +
-                              __popc(q1.x ^ d1.x) + __popc(q1.y ^ d1.y) + __popc(q1.z ^ d1.z) + __popc(q1.w ^ d1.w);
-                const uint32_t key = ((uint32_t)d << 16) | (uint32_t)(order + sub);
-                if (key < bestKey) { bestKey = key; bestIdx = idx; }
-            }
-        }
-    }
+    const int maxLevel = (int)item.w;
+    walk_window<kSinLanes>(G, u, v, a.th * scale[maxLevel], maxLevel - 1, maxLevel, sub, [&](int idx, const RumiKeyPoint &kp, int place) {
+        if (REPROJ && !reproj_gate(kp, u, v, scale)) return;
+        const int d = hamming256(q0, q1, ld16_dword(desc + (size_t)idx * 32), ld16_dword(desc + (size_t)idx * 32 + 16));
+        const uint32_t key = ((uint32_t)d << 16) | (uint32_t)place;
+        if (key < bestKey) { bestKey = key; bestIdx = idx; }
+    });
 }
 
 // The minimum of a group's kSinLanes keys; all 64 lanes are here, a group's lanes exchange among themselves only.

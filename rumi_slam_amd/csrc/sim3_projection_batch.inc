@@ -14,8 +14,8 @@
 //   k_s3p_gate     one lane per (job, entry), entries the fast index: a wave's lanes share the job; id < 0, bad, then sim3_query with the job's
 //                  th and projection; survivors to the work list with projection, level and job.  An entry that would be searched and whose
 //                  point has no attributes is counted.
-//   k_s3p_walk<0>  16 lanes per surviving pair walk the window in GetFeaturesInArea order over levels [level - 1, level] (sin_walk's traversal,
-//                  restated here because it indexes the grid through the job and emits every candidate instead of the nearest) and COUNT the
+//   k_s3p_walk<0>  16 lanes per surviving pair walk the window in GetFeaturesInArea order over levels [level - 1, level] (walk_window,
+//                  match_grid.h: sin_walk's traversal, here keeping every candidate instead of the nearest) and COUNT the
 //                  candidates within the job's threshold; a wave then takes the list space of its four pairs with one atomicAdd on the total.
 //                  (A scan of the counts over all pairs would give the same disjoint ranges in pair order; one workgroup took 215 us for it at
 //                  120 000 pairs, two thirds of the call.  Where a list lies reaches no result.)
@@ -98,45 +98,22 @@ __global__ __launch_bounds__(256) void k_s3p_walk(S3pArgs a) {
             const int p = a.ids[J.pointStart + (int)(pair - (uint32_t)J.pairBase)];
             const uint8_t *R8 = a.s.feat + J.block;
             const CovisFeatRec *R = reinterpret_cast<const CovisFeatRec *>(R8);
-            const RumiKeyPoint *keys = reinterpret_cast<const RumiKeyPoint *>(R8 + R->keys);
             const uint8_t *desc = R8 + R->desc;
-            const uint16_t *S = a.s.sorted + J.sortedOff;
-            const int32_t *CS = a.s.cellStart + (size_t)J.grid * (kGridCells + 1);
+            const GridView G{reinterpret_cast<const RumiKeyPoint *>(R8 + R->keys), a.s.sorted + J.sortedOff, a.s.cellStart + (size_t)J.grid * (kGridCells + 1),
+                             J.bounds[0], J.bounds[1], J.wInv, J.hInv};
             const uint4 q0 = ld16_dword(a.s.attr + (size_t)p * kCovisAttrWords + 8), q1 = ld16_dword(a.s.attr + (size_t)p * kCovisAttrWords + 12);
-            const float u = __uint_as_float(item.x), v = __uint_as_float(item.y);
-            const int maxLevel = (int)(item.w & 255u), minLevel = maxLevel - 1;
-            const float r = J.th * reinterpret_cast<const float *>(R8 + R->scale)[maxLevel];
+            const int maxLevel = (int)(item.w & 255u);
             const int listAt = FILL ? a.s.blockBase[pair] : 0, listLen = FILL ? a.s.blockCount[pair] : 0;
-            // Frame::GetFeaturesInArea (Frame.cc:695-750)
-            const int nMinCellX = max(0, (int)floorf((u - J.bounds[0] - r) * J.wInv));
-            const int nMaxCellX = min(kGridCols - 1, (int)ceilf((u - J.bounds[0] + r) * J.wInv));
-            const int nMinCellY = max(0, (int)floorf((v - J.bounds[1] - r) * J.hInv));
-            const int nMaxCellY = min(kGridRows - 1, (int)ceilf((v - J.bounds[1] + r) * J.hInv));
-            if (nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0 && nMaxCellY >= nMinCellY) {
-                int order = 0;
-                for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-                    const int p0 = CS[ix * kGridRows + nMinCellY], p1 = CS[ix * kGridRows + nMaxCellY + 1];
-                    for (int base = p0; base < p1; base += kSinLanes, order += kSinLanes) {
-                        const int c = base + sub;
-                        if (c >= p1) continue;
-                        const int idx = S[c];
-                        const RumiKeyPoint kp = keys[idx];
-                        const int oct = kp.octave;
-                        if (oct < minLevel || oct > maxLevel) continue;
-                        const float dx = kp.x - u, dy = kp.y - v;
-                        if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
-                        const uint4 d0 = ld16_dword(desc + (size_t)idx * 32), d1 = ld16_dword(desc + (size_t)idx * 32 + 16);
-                        const int d = __popc(q0.x ^ d0.x) + __popc(q0.y ^ d0.y) + __popc(q0.z ^ d0.z) + __popc(q0.w ^ d0.w) +
-                                      __popc(q1.x ^ d1.x) + __popc(q1.y ^ d1.y) + __popc(q1.z ^ d1.z) + __popc(q1.w ^ d1.w);
-                        if (!((float)d <= J.thrF)) continue;                        // the cut (above)
-                        if (FILL) {
-                            const int at = atomicAdd(&a.cursor[pair], 1);
-                            if (at < listLen && (uint32_t)(listAt + at) < (uint32_t)a.listCap)
-                                a.lists[listAt + at] = make_uint2(((uint32_t)d << 16) | (uint32_t)(order + sub), (uint32_t)idx);
-                        } else found++;
-                    }
-                }
-            }
+            walk_window<kSinLanes>(G, __uint_as_float(item.x), __uint_as_float(item.y), J.th * reinterpret_cast<const float *>(R8 + R->scale)[maxLevel],
+                                   maxLevel - 1, maxLevel, sub, [&](int idx, const RumiKeyPoint &, int place) {
+                const int d = hamming256(q0, q1, ld16_dword(desc + (size_t)idx * 32), ld16_dword(desc + (size_t)idx * 32 + 16));
+                if (!((float)d <= J.thrF)) return;                                  // the cut (above)
+                if (FILL) {
+                    const int at = atomicAdd(&a.cursor[pair], 1);
+                    if (at < listLen && (uint32_t)(listAt + at) < (uint32_t)a.listCap)
+                        a.lists[listAt + at] = make_uint2(((uint32_t)d << 16) | (uint32_t)place, (uint32_t)idx);
+                } else found++;
+            });
         }
         if (!FILL) {                                         // all 64 lanes are here: a wave's four pairs take their list space with one atomic
             static_assert(kSinLanes == 16, "four pairs a wave");

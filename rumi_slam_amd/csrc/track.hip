@@ -188,34 +188,10 @@ __device__ __forceinline__ void frustum_body(int i, const FrustumArgs &F) {
         F.q[i] = mappoint_query(i, false, -1.f, -1.f, 0, 0.f, 0.f, true, F.mpObs[i], F.scaleFactors, F.th, F.farPoints, F.thFar);
         return;
     }
-    const float *R = F.pose, *t = F.pose + 9, *Ow = F.pose + 12, *K = F.pose + 15;
-    const float *P = F.mpPos + (size_t)i * 3;
-    uint8_t in = 0;
-    float px = -1, py = -1, vc = 0, depth = 0;
-    int lvl = 0;
-    float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) Pc[r] = ((R[r * 3] * P[0] + R[r * 3 + 1] * P[1]) + R[r * 3 + 2] * P[2]) + t[r];
-    const float Pc_dist = sqrtf((Pc[0] * Pc[0] + Pc[1] * Pc[1]) + Pc[2] * Pc[2]);
-    if (!(Pc[2] < 0.0f)) {
-        const float u = K[0] * Pc[0] / Pc[2] + K[2], v = K[1] * Pc[1] / Pc[2] + K[3];
-        if (!(u < F.minX || u > F.maxX) && !(v < F.minY || v > F.maxY)) {
-            px = u; py = v;
-            const float maxD = 1.2f * F.mpMaxDist[i], minD = 0.8f * F.mpMinDist[i];
-            const float P0 = P[0] - Ow[0], P1 = P[1] - Ow[1], P2 = P[2] - Ow[2];
-            const float dist = sqrtf((P0 * P0 + P1 * P1) + P2 * P2);
-            if (!(dist < minD || dist > maxD)) {
-                const float *Pn = F.mpNormal + (size_t)i * 3;
-                const float viewCos = ((P0 * Pn[0] + P1 * Pn[1]) + P2 * Pn[2]) / dist;
-                if (!(viewCos < F.viewingCosLimit)) {
-                    lvl = predict_scale(F.mpMaxDist[i], dist, F.logScaleFactor, F.nLevels);
-                    in = 1; depth = Pc_dist; vc = viewCos;
-                }
-            }
-        }
-    }
-    F.inView[i] = in; F.projX[i] = px; F.projY[i] = py; F.scaleLevel[i] = lvl; F.viewCosOut[i] = vc; F.trackDepth[i] = depth;
-    F.q[i] = mappoint_query(i, in != 0, px, py, lvl, vc, depth, false, F.mpObs[i], F.scaleFactors, F.th, F.farPoints, F.thFar);
+    const FrustumResult f = frustum_gate(F.mpPos + (size_t)i * 3, F.mpNormal + (size_t)i * 3, F.mpMinDist + i, F.mpMaxDist + i, F.pose, F.minX, F.minY, F.maxX,
+                                         F.maxY, F.logScaleFactor, F.nLevels, F.viewingCosLimit);
+    F.inView[i] = f.in; F.projX[i] = f.px; F.projY[i] = f.py; F.scaleLevel[i] = f.lvl; F.viewCosOut[i] = f.viewCos; F.trackDepth[i] = f.depth;
+    F.q[i] = mappoint_query(i, f.in != 0, f.px, f.py, f.lvl, f.viewCos, f.depth, false, F.mpObs[i], F.scaleFactors, F.th, F.farPoints, F.thFar);
 }
 
 __global__ void k_track_frustum(FrustumArgs F) { frustum_body(blockIdx.x * blockDim.x + threadIdx.x, F); }

@@ -1,7 +1,8 @@
 """The projecting kernels against the constructed gate cases of gate_cases.py: every entry that evaluates the gate chain equals the hand-written
-expectation and the oracle.  Frustum cases run through k_is_in_frustum (matcher.isInFrustum, ORBmatcher.SearchLocalPoints) and its twin
-frustum_body (Tracker.local + last_projections); search cases through every member's query builder; the sim3_query cases also through the
-resident one-call entry."""
+expectation and the oracle.  Frustum cases run through the two callers of frustum_gate: k_is_in_frustum (matcher.isInFrustum,
+ORBmatcher.SearchLocalPoints) and the tracker's frustum_body (Tracker.local + last_projections), each with its own skip branches and outputs;
+search cases through every member's query builder (the RELOC member's gate, reloc_query, is also the relocalisation walk's); the sim3_query
+cases also through the resident one-call entry."""
 import numpy as np
 import pytest
 
@@ -85,7 +86,7 @@ def tracker_case(trackers, c):
 
 @pytest.mark.parametrize("family", sorted({c.family for c in FRUSTUM}))
 def test_tracker_frustum_equals_expected(trackers, family):
-    """frustum_body, the twin of k_is_in_frustum: the fields through rumi_track_last_projections, the flags and n_to_match through rumi_track_local."""
+    """frustum_body, the tracker's caller of frustum_gate: the fields through rumi_track_last_projections, the flags and n_to_match through rumi_track_local."""
     cases = [c for c in G.tracker_cases() if c.family == family]
     assert cases
     for c in cases:
