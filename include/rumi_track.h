@@ -227,6 +227,42 @@ int rumi_track_reloc_begin(RumiTracker *t, const float *K4, int32_t K, const Rum
 int rumi_track_reloc_refine(RumiTracker *t, const RumiRelocParams *p, int32_t H, const RumiRelocHypothesis *hyp, int32_t *frame_mp,
                             uint8_t *outlier_last, RumiRelocResult *res);
 
+/* ---- Tracking::Relocalization by slot: the frame's BoW, the BoW walk over the candidates and the refine session read the covisibility
+ * store (rumi_covis.h) where it lies.  A Relocalization call then sends slot numbers and pose hypotheses, nothing else. ------------------- */
+
+/* Frame::ComputeBoW (Frame.cc:763-768) on the frame rumi_track_extract left resident: the tree descent of every descriptor and the
+ * FeatureVector, both on the device.  word_id / word_weight / node_id [cap]: the per-feature transform, byte for byte what
+ * rumi_track_reference_keyframe writes for the same frame and vocabulary; rumi_voc_assemble gives mBowVec and mFeatVec from them.  The
+ * frame's FeatureVector stays in device buffers the tracker owns, valid until the next rumi_track_extract / rumi_track_frame whatever
+ * matcher calls come in between.  A frame without features: RUMI_OK, nothing written.  RUMI_E_INVALID: no frame resident, a NULL argument. */
+int rumi_track_compute_bow(RumiTracker *t, RumiVocabulary *voc, int32_t levelsup, uint32_t *word_id, double *word_weight, uint32_t *node_id);
+
+/* ORBmatcher(nnratio, check_orientation).SearchByBoW(pKF_k, mCurrentFrame, vvpMapPointMatches[k]) (ORBmatcher.cc:198-370, Tracking.cc:3243-3252)
+ * for the key-frames in slots [K] of store c.  Key-frame side: the slot's features (rumi_covis_set_keyframe_features), its map-point row
+ * and the points' bad bits, as the store holds them after its staged edits, which the call sends first; frame side: the resident frame and
+ * the FeatureVector of rumi_track_compute_bow.  matches [K][n] (n = the frame's feature count): store point ids, -1 = NULL; nmatches_out [K]:
+ * the return values.  A slot whose key-frame is bad is not searched (:3245): its row is all -1 and its count -1.  A live slot's row and
+ * count are rumi_search_by_bow's on the same data by host pointers; a FeatureVector node of any size is searched on the device.  The match
+ * rows stay on the device for rumi_track_reloc_begin_resident.
+ * RUMI_E_INVALID, before any device work, nothing written, the handle usable: no frame resident; no rumi_track_compute_bow on this frame;
+ * K < 1; a slot outside the store, not live, named twice, or -- unless its key-frame is bad -- without features or with a row whose length
+ * is not its feature count; store and tracker on different devices. */
+int rumi_track_reloc_bow(RumiTracker *t, RumiCovis *c, int32_t K, const int32_t *slots, float nnratio, int32_t check_orientation, int32_t *matches,
+                         int32_t *nmatches_out);
+
+/* Opens the session of rumi_track_reloc_refine from the store: what rumi_track_reloc_begin uploads, kernels gather here.  cand [Kc]: indices
+ * into the slots of the preceding rumi_track_reloc_bow on this frame and store -- the candidates that are kept, in the caller's order;
+ * hypothesis.cand of refine then indexes cand.  The point table has one row per distinct point id of the candidates' map-point rows, in
+ * order of first appearance over (candidate order, feature order); position, distances and descriptor come from the attribute records
+ * (rumi_covis_set_point_attributes), bad from the point flags.  table_ids [table_cap]: the store id of every row, *n_table of them;
+ * frame_mp of refine holds table rows.
+ * RUMI_E_INVALID, no output written: no rumi_track_reloc_bow on this frame and store (a new rumi_track_extract ends it); cand outside [0, K),
+ * naming a bad slot or the same slot twice; a row point without attributes (counted on the device, the message names how many).
+ * RUMI_E_CAPACITY: the table has more rows than table_cap or the tracker's max_points.  The last two are found after the session block has
+ * been written: an earlier session is then closed. */
+int rumi_track_reloc_begin_resident(RumiTracker *t, RumiCovis *c, const float *K4, int32_t Kc, const int32_t *cand, int32_t *table_ids,
+                                    int32_t table_cap, int32_t *n_table);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,7 +116,8 @@ VOC_SYMBOLS = ["rumi_voc_create", "rumi_voc_load_text", "rumi_voc_destroy", "rum
                "rumi_voc_transform_batch_device", "rumi_voc_transform"]
 TRACK_SYMBOLS = ["rumi_track_create", "rumi_track_destroy", "rumi_track_frame", "rumi_track_extract", "rumi_track_motion",
                  "rumi_track_reference_keyframe", "rumi_track_local", "rumi_track_local_map", "rumi_track_image_buffer", "rumi_track_last_projections", "rumi_track_set_distortion", "rumi_track_undistorted",
-                 "rumi_reloc_default_params", "rumi_track_reloc_begin", "rumi_track_reloc_refine", "rumi_track_reloc_attempts"]
+                 "rumi_reloc_default_params", "rumi_track_reloc_begin", "rumi_track_reloc_refine", "rumi_track_reloc_attempts",
+                 "rumi_track_compute_bow", "rumi_track_reloc_bow", "rumi_track_reloc_begin_resident"]
 QUEUE_SYMBOLS = ["rumi_queue_create", "rumi_queue_destroy", "rumi_queue_shards", "rumi_queue_record_bytes", "rumi_queue_block_capacity", "rumi_queue_row",
                  "rumi_queue_uses_rccl", "rumi_queue_extract", "rumi_queue_last_ms"]
 KFDB_SYMBOLS = ["rumi_kfdb_create", "rumi_kfdb_destroy", "rumi_kfdb_clear", "rumi_kfdb_size", "rumi_kfdb_next_seq", "rumi_kfdb_max_batch", "rumi_kfdb_add",

@@ -253,6 +253,7 @@ struct TrackViews {                      // the arrays behind the TrackBlock hea
 };
 
 namespace rumi { struct RelocState; void reloc_release(RelocState *s); }      // track_reloc.inc
+namespace rumi { struct RelocResident; void reloc_resident_release(RelocResident *r); }      // track_reloc_resident.inc
 
 struct RumiTracker {
     int device = 0, cap = 0, maxPts = 0, nlevels = 0;
@@ -287,12 +288,15 @@ struct RumiTracker {
     // rumi_track_reloc_begin / _refine (track_reloc.inc): the session's blocks; frameSerial counts the frames that became resident
     uint32_t frameSerial = 0;
     rumi::RelocState *reloc = nullptr;
+    // rumi_track_compute_bow / _reloc_bow / _reloc_begin_resident (track_reloc_resident.inc): the frame's FeatureVector, the BoW walk's matches
+    rumi::RelocResident *rres = nullptr;
 };
 
 extern "C" void rumi_track_destroy(RumiTracker *t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
     rumi::reloc_release(t->reloc);
+    rumi::reloc_resident_release(t->rres);
     rumi_orb_destroy(t->ext);
     rumi_match_destroy(t->m);
     void *p[] = {t->dImage, t->dBlk, t->dInvSigma2, t->dXw, t->dObs, t->dW, t->dIdx, t->dOutC, t->dActive, t->dSeen, t->dBad, t->dLocal, t->dChi, t->dBow, t->dNN, t->dStaleIn, t->dStaleProj, t->dKeysUn};
@@ -1006,3 +1010,4 @@ extern "C" int rumi_track_undistorted(RumiTracker *t, RumiKeyPoint *keys_un_out,
 }
 
 #include "track_reloc.inc"
+#include "track_reloc_resident.inc"

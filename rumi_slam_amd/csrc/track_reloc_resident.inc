@@ -1,0 +1,499 @@
+// Tracking::Relocalization by slot (R/lib_src/Tracking.cc:3212-3357), behind rumi_track_compute_bow / rumi_track_reloc_bow /
+// rumi_track_reloc_begin_resident (include/rumi_track.h, DESIGN.md 4z).  Included at the end of track.hip, behind track_reloc.inc, whose
+// session block (RelocState) and refine chain it feeds unchanged.  The key-frame side is read where the covisibility store keeps it: the
+// CovisFeatRec block of a slot (key-points, descriptors, mFeatVec as CSR), its map-point row in the row arena, the bad bits and the 64-byte
+// attribute records of the points.  A call sends slot numbers and a few words per candidate, nothing else.
+//
+//   k_rbow_match     SearchByBoW of every (candidate, key-frame node) pair, 16 lanes each: k_bow_batch_match's walk and tie rules.  A lane's
+//                    `taken` flags lie in LDS words of its own (word w of thread t at sTaken[w * 256 + t]; bit j of the lane's private mask is
+//                    position lane + 16 j of the node), as many words as the frame's feature count asks for: no node size is refused, and no
+//                    lane reads another lane's word, so there is nothing to synchronise.
+//   k_rbow_finish    ComputeThreeMaxima and the count of every candidate (k_bow_batch_finish's body); a bad slot's count is -1.
+//   k_rtab_claim     a lane per (candidate, key-frame feature): atomicMax of its claim u = place in (candidate order, feature order) on the
+//                    point's stamp: the lowest u wins (track_local_map.inc's scheme, a map and an epoch counter of the session's own).
+//   k_rtab_order     ONE workgroup: the winners in order of u by a ballot prefix, their rows, the ids of the rows, the rows without attributes.
+//   k_rtab_gather    a lane per row for position, distances and bad, eight lanes per row for the descriptor, into the session block.
+//   k_rsess_fill     key-points out of the feature arena, map-point rows and BoW matches rewritten from point ids to table rows, the
+//                    RelocCand records and K4.
+// Integer atomics only (atomicOr / atomicAdd / atomicMax on integers): no result depends on the order anything arrives in.
+
+namespace rumi {
+
+struct RbowCand { long long block; int32_t mpOff, nkf, nn, bad; };     // one candidate slot: its CovisFeatRec (bytes into the feature arena), its row
+static_assert(sizeof(RbowCand) == 24, "the candidate table as uploaded");
+
+struct RbowArgs {
+    const RbowCand *cands;
+    const uint8_t *feat;                 // the feature arena
+    const int32_t *rows, *pt;            // the row arena, the point records
+    const RumiKeyPoint *fKeys;           // the resident frame
+    const uint32_t *fDesc;
+    const uint32_t *fNodes, *fIdx;       // its FeatureVector (rumi_track_compute_bow)
+    const int32_t *fOff, *fNN;
+    int K, nf, words;                    // words: LDS words of `taken` flags a lane owns
+    int32_t *matches;                    // [K][nf] point ids, -1 none
+    int8_t *rotBin;                      // [K][nf]
+    int32_t *hist;                       // [K][32]
+    int32_t *nmatch;                     // [K]
+    float nnratio;
+    int checkOri;
+};
+
+template <class T> __device__ __forceinline__ const T *rec_arr(const CovisFeatRec *r, uint32_t o) {
+    return reinterpret_cast<const T *>(reinterpret_cast<const uint8_t *>(r) + o);
+}
+
+__global__ __launch_bounds__(256) void k_rbow_match(RbowArgs B) {
+    extern __shared__ uint32_t sTaken[];                      // [words][256]
+    const int k = blockIdx.y, lane = threadIdx.x & 15, a = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const RbowCand C = B.cands[k];
+    if (C.bad || a >= C.nn) return;
+    const CovisFeatRec *R = reinterpret_cast<const CovisFeatRec *>(B.feat + C.block);
+    const uint32_t *kfNodes = rec_arr<uint32_t>(R, R->nodes);
+    const uint32_t node = kfNodes[a];
+    const int nnF = B.fNN[0];
+    int lo = 0, hi = nnF;                                    // first frame node >= node (std::map order: ascending ids)
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (B.fNodes[mid] < node) lo = mid + 1; else hi = mid; }
+    if (lo >= nnF || B.fNodes[lo] != node) return;
+    const int c0 = B.fOff[lo], nc = B.fOff[lo + 1] - c0;
+    const int32_t *kOff = rec_arr<int32_t>(R, R->off);
+    const uint32_t *fIdx = B.fIdx + c0, *kIdx = rec_arr<uint32_t>(R, R->idx), *kDesc = rec_arr<uint32_t>(R, R->desc);
+    const RumiKeyPoint *kKeys = rec_arr<RumiKeyPoint>(R, R->keys);
+    const int32_t *kMp = B.rows + C.mpOff;
+    uint32_t *taken = sTaken + threadIdx.x;                  // word w at taken[w * 256]; bit j & 31 of word j >> 5: my position lane + 16 j holds a map point
+    const int myWords = ((nc + 15) / 16 + 31) / 32;          // (<= B.words: a node holds at most nf features)
+    for (int w = 0; w < myWords; w++) taken[w * 256] = 0;
+    for (int p = kOff[a]; p < kOff[a + 1]; p++) {
+        const int iKF = (int)kIdx[p];
+        const int mp = kMp[iKF];
+        if (mp < 0 || (B.pt[(size_t)mp * kCovisPointWords + 2] & 1)) continue;      // no map point, or a bad one (:238-243)
+        uint32_t q[8];
+#pragma unroll
+        for (int w = 0; w < 8; w++) q[w] = kDesc[(size_t)iKF * 8 + w];
+        uint32_t best = (256u << 16) | 0xFFFFu, second = 256u;
+        for (int j = 0, pos = lane; pos < nc; j++, pos += 16) {
+            if ((taken[(j >> 5) * 256] >> (j & 31)) & 1u) continue;
+            const uint32_t *d = B.fDesc + (size_t)fIdx[pos] * 8;
+            uint32_t dist = 0;
+#pragma unroll
+            for (int w = 0; w < 8; w++) dist += __popc(q[w] ^ d[w]);
+            const uint32_t key = (dist << 16) | (uint32_t)pos;
+            if (key < best) { second = best >> 16; best = key; }       // a strictly smaller distance, or the same at an earlier position
+            else if (dist < second) second = dist;
+        }
+        // 16-lane reduction: best = smallest key; second = second smallest distance of the union
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) {
+            const uint32_t ob = __shfl_xor(best, o, 16), os = __shfl_xor(second, o, 16);
+            const uint32_t loser = max(best, ob) >> 16;
+            best = min(best, ob);
+            second = min(min(second, os), loser);
+        }
+        const int bestDist1 = (int)(best >> 16), bestDist2 = (int)second;
+        if (bestDist1 <= RUMI_TH_LOW && (float)bestDist1 < B.nnratio * (float)bestDist2) {
+            const int pos = (int)(best & 0xFFFFu), f = (int)fIdx[pos];
+            if (lane == (pos & 15)) { const int j = pos >> 4; taken[(j >> 5) * 256] |= 1u << (j & 31); }
+            if (lane == 0) {
+                B.matches[(size_t)k * B.nf + f] = mp;
+                if (B.checkOri) {
+                    const int bin = rot_bin(kKeys[iKF].angle, B.fKeys[f].angle);
+                    B.rotBin[(size_t)k * B.nf + f] = (int8_t)bin;
+                    atomicAdd(&B.hist[k * 32 + bin], 1);
+                }
+            }
+        }
+    }
+}
+
+// rotation-histogram filter (ComputeThreeMaxima, ORBmatcher.cc:1795-1826) and the match count of every candidate; -1 for a bad slot (Tracking.cc:3245)
+__global__ __launch_bounds__(256) void k_rbow_finish(RbowArgs B) {
+    __shared__ int sKeep[32], sCount;
+    const int k = blockIdx.x, tid = threadIdx.x;
+    if (B.cands[k].bad) { if (tid == 0) B.nmatch[k] = -1; return; }
+    if (tid == 0) {
+        sCount = 0;
+        for (int i = 0; i < 32; i++) sKeep[i] = 1;
+        if (B.checkOri) {
+            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) {
+                const int s = B.hist[k * 32 + i];
+                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+                else if (s > max3) { max3 = s; ind3 = i; }
+            }
+            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+            else if (max3 < 0.1f * (float)max1) ind3 = -1;
+            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) sKeep[i] = (i == ind1 || i == ind2 || i == ind3);
+        }
+    }
+    __syncthreads();
+    int local = 0;
+    for (int f = tid; f < B.nf; f += 256) {
+        int32_t &m = B.matches[(size_t)k * B.nf + f];
+        if (m < 0) continue;
+        if (B.checkOri && !sKeep[B.rotBin[(size_t)k * B.nf + f] & 31]) m = -1; else local++;
+    }
+    atomicAdd(&sCount, local);
+    __syncthreads();
+    if (tid == 0) B.nmatch[k] = sCount;
+}
+
+// ---- the session's point table and block ------------------------------------------------------------------------------------------------
+struct RsessCand { long long block; int32_t mpOff, nkf, keyOff, matchRow; };      // keyOff: features of the candidates before it; matchRow: its row of the BoW matches
+static_assert(sizeof(RsessCand) == 24, "the candidate table as uploaded");
+
+struct RsessArgs {
+    const RsessCand *cands;
+    int Kc, n, rowCap;
+    uint32_t epoch;
+    const uint8_t *feat;
+    const int32_t *rows, *pt, *attr;
+    unsigned long long *rowOf;           // [max_points] (epoch << 32) | value, as track_local_map.inc
+    int32_t *head;                       // {n_table, rows without attributes, -, -}
+    int32_t *tableIds;                   // [rowCap]
+    const int32_t *bowMatches;           // [K][n] point ids
+    // the session block (RelocState::sess)
+    RelocCand *outCands;
+    RumiKeyPoint *outKeys;
+    int32_t *outRows, *outMatch;
+    float *pos, *minD, *maxD, *k4Out;
+    uint8_t *bad;
+    uint32_t *desc;
+    float K4[4];
+};
+
+__device__ __forceinline__ unsigned long long rsess_stamp(const RsessArgs &a, uint32_t value) { return ((unsigned long long)a.epoch << 32) | value; }
+__device__ __forceinline__ int rsess_row_of(const RsessArgs &a, int p) {
+    const unsigned long long s = a.rowOf[p];
+    return ((uint32_t)(s >> 32) == a.epoch && ((uint32_t)s & kRowBit)) ? (int)((uint32_t)s & ~kRowBit) : -1;
+}
+
+__global__ __launch_bounds__(256) void k_rtab_claim(RsessArgs a) {
+    const RsessCand C = a.cands[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= C.nkf) return;
+    const int p = a.rows[C.mpOff + i];
+    if (p >= 0) atomicMax(&a.rowOf[p], rsess_stamp(a, 0x7FFFFFFFu - (uint32_t)(C.keyOff + i)));
+}
+
+__global__ __launch_bounds__(kTableThreads) void k_rtab_order(RsessArgs a) {
+    __shared__ int sCnt[kTableThreads / 64], sBase, sMissing;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) { sBase = 0; sMissing = 0; }
+    __syncthreads();
+    for (int k = 0; k < a.Kc; k++) {
+        const RsessCand C = a.cands[k];
+        for (int c0 = 0; c0 < C.nkf; c0 += kTableThreads) {
+            const int i = c0 + tid;
+            const int p = i < C.nkf ? a.rows[C.mpOff + i] : -1;
+            const bool win = p >= 0 && a.rowOf[p] == rsess_stamp(a, 0x7FFFFFFFu - (uint32_t)(C.keyOff + i));
+            const unsigned long long b = __ballot(win);
+            if (lane == 0) sCnt[wave] = __popcll(b);
+            __syncthreads();
+            if (win) {
+                int off = sBase;
+                for (int w = 0; w < wave; w++) off += sCnt[w];
+                const int row = off + __popcll(b & ((1ull << lane) - 1ull));
+                a.rowOf[p] = rsess_stamp(a, kRowBit | (uint32_t)row);
+                if (row < a.rowCap) a.tableIds[row] = p;
+                if (!a.attr || !a.pt[(size_t)p * kCovisPointWords + 3]) atomicAdd(&sMissing, 1);
+            }
+            __syncthreads();
+            if (tid == 0) { int t = sBase; for (int w = 0; w < kTableThreads / 64; w++) t += sCnt[w]; sBase = t; }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) { a.head[0] = sBase; a.head[1] = sMissing; }
+}
+
+__global__ __launch_bounds__(256) void k_rtab_gather(RsessArgs a) {
+    __shared__ int sId[256];
+    const int tid = threadIdx.x, nTable = min(a.head[0], a.rowCap);
+    for (int base = blockIdx.x * 256; base < nTable; base += gridDim.x * 256) {
+        const int row = base + tid;
+        int id = -1;
+        if (row < nTable) {
+            const int p = a.tableIds[row];
+            const int4 P = *reinterpret_cast<const int4 *>(a.pt + (size_t)p * kCovisPointWords);
+            float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+            if (a.attr && P.w) {
+                id = p;
+                const float4 *A = reinterpret_cast<const float4 *>(a.attr + (size_t)p * kCovisAttrWords);
+                lo = A[0]; hi = A[1];
+            }
+            a.pos[(size_t)row * 3] = lo.x; a.pos[(size_t)row * 3 + 1] = lo.y; a.pos[(size_t)row * 3 + 2] = lo.z;
+            a.minD[row] = hi.z; a.maxD[row] = hi.w;
+            a.bad[row] = (uint8_t)(P.z & 1);
+        }
+        sId[tid] = id;                                       // -1: a row without attributes reads as zeros (the host refuses such a call)
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < 8; it++) {
+            const int r = it * 32 + (tid >> 3), w = tid & 7;
+            if (base + r < nTable) {
+                const int p = sId[r];
+                a.desc[(size_t)(base + r) * 8 + w] = p >= 0 ? (uint32_t)a.attr[(size_t)p * kCovisAttrWords + 8 + w] : 0u;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// grid (x, Kc): candidate blockIdx.y's key-points and row, then its matches; block (0, 0) also writes K4
+__global__ __launch_bounds__(256) void k_rsess_fill(RsessArgs a) {
+    const int k = blockIdx.y;
+    const RsessCand C = a.cands[k];
+    const int step = gridDim.x * 256, t0 = blockIdx.x * 256 + threadIdx.x;
+    if (t0 == 0) a.outCands[k] = RelocCand{C.nkf, C.keyOff};
+    if (k == 0 && t0 < 4) a.k4Out[t0] = a.K4[t0];
+    const RumiKeyPoint *keys = reinterpret_cast<const RumiKeyPoint *>(a.feat + C.block + kCovisFeatKeysOffset);
+    for (int i = t0; i < C.nkf; i += step) {
+        a.outKeys[C.keyOff + i] = keys[i];
+        const int p = a.rows[C.mpOff + i];
+        int row = p >= 0 ? rsess_row_of(a, p) : -1;
+        if (row >= a.rowCap) row = -1;                       // (the host refuses such a call: nothing of it is read)
+        a.outRows[C.keyOff + i] = row;
+    }
+    for (int f = t0; f < a.n; f += step) {
+        const int p = a.bowMatches[(size_t)C.matchRow * a.n + f];
+        int row = p >= 0 ? rsess_row_of(a, p) : -1;
+        if (row >= a.rowCap) row = -1;
+        a.outMatch[(size_t)k * a.n + f] = row;
+    }
+}
+
+// What rumi_track_compute_bow and rumi_track_reloc_bow leave on the device for the calls that follow on the same frame.
+struct RelocResident {
+    // the frame's FeatureVector, tracker-owned: valid while bowSerial == frameSerial
+    DevBuf<uint32_t> fvNodes, fvIdx;
+    DevBuf<int32_t> fvOff, fvNN;
+    uint32_t bowSerial = 0;
+    bool haveBow = false;
+    // the BoW walk: valid while walkSerial == frameSerial
+    bool haveWalk = false;
+    uint32_t walkSerial = 0;
+    const RumiCovis *store = nullptr;
+    std::vector<int32_t> slots;
+    std::vector<uint8_t> slotBad;
+    MirrorBuf<uint8_t> tab;              // the candidate table of either entry
+    MirrorBuf<uint8_t> out;              // [matches K n | nmatch K | hist K 32 | rotBin K n]
+    // the session's id -> row map
+    DevBuf<unsigned long long> rowOf;
+    uint32_t epoch = 0;
+    MirrorBuf<int32_t> ids;              // [head 4 | table ids rowCap]
+};
+void reloc_resident_release(RelocResident *r) { delete r; }
+
+static RelocResident *resident_of(RumiTracker *t) {
+    if (!t->rres) t->rres = new RelocResident();
+    return t->rres;
+}
+
+}  // namespace rumi
+
+extern "C" int rumi_track_compute_bow(RumiTracker *t, RumiVocabulary *voc, int32_t levelsup, uint32_t *word_id, double *word_weight, uint32_t *node_id) {
+    static const char *entry = "rumi_track_compute_bow";
+    if (!t || !voc || !word_id || !word_weight || !node_id) { g_lastError = std::string(entry) + ": missing argument"; return RUMI_E_INVALID; }
+    if (t->curN < 0) { g_lastError = std::string(entry) + ": no frame is resident (rumi_track_extract first)"; return RUMI_E_INVALID; }
+    HIP_TRY(hipSetDevice(t->device));
+    RelocResident *r = resident_of(t);
+    r->haveBow = false; r->haveWalk = false;
+    const int n = t->curN;
+    const size_t C = (size_t)t->cap;
+    int rc;
+    if ((rc = r->fvNodes.reserve(C + 1, C + 1)) != RUMI_OK || (rc = r->fvIdx.reserve(C + 1, C + 1)) != RUMI_OK || (rc = r->fvOff.reserve(C + 2, C + 2)) != RUMI_OK ||
+        (rc = r->fvNN.reserve(4, 4)) != RUMI_OK)
+        return rc;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(r->fvNN.p, 0, 16, nullptr));
+        HIP_TRY(hipMemsetAsync(r->fvOff.p, 0, 8, nullptr));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        r->bowSerial = t->frameSerial; r->haveBow = true;
+        return RUMI_OK;
+    }
+    // Frame::ComputeBoW (Frame.cc:763-768): the two steps of rumi_track_reference_keyframe, the FeatureVector into the tracker's own arrays
+    if ((rc = rumi_voc_transform_batch_device(voc, t->d.record + t->oDesc, t->d.record, 1, t->cap, levelsup, t->dWord, t->dWeight, t->dNode, nullptr)) != RUMI_OK) return rc;
+    int npad = 1;
+    while (npad < n) npad <<= 1;
+    const size_t fvLds = (size_t)npad * sizeof(unsigned long long);
+    if (fvLds > 64 * 1024) HIP_TRY(raise_lds_limit(reinterpret_cast<const void *>(k_fv_build), fvLds));
+    hipLaunchKernelGGL(k_fv_build, dim3(1), dim3(kFvThreads), fvLds, nullptr, n, npad, t->dNode, t->dWeight, r->fvNodes.p, r->fvOff.p, r->fvIdx.p, r->fvNN.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(t->hBow, t->dBow, C * 16, hipMemcpyDeviceToHost));
+    std::memcpy(word_weight, t->hBow, (size_t)n * 8); std::memcpy(word_id, t->hBow + C * 8, (size_t)n * 4); std::memcpy(node_id, t->hBow + C * 12, (size_t)n * 4);
+    r->bowSerial = t->frameSerial; r->haveBow = true;
+    return RUMI_OK;
+}
+
+extern "C" int rumi_track_reloc_bow(RumiTracker *t, RumiCovis *c, int32_t K, const int32_t *slots, float nnratio, int32_t check_orientation, int32_t *matches,
+                                    int32_t *nmatches_out) {
+    static const char *entry = "rumi_track_reloc_bow";
+    if (!t || !c || !slots || !nmatches_out) { g_lastError = std::string(entry) + ": missing argument"; return RUMI_E_INVALID; }
+    if (t->curN < 0) { g_lastError = std::string(entry) + ": no frame is resident (rumi_track_extract first)"; return RUMI_E_INVALID; }
+    RelocResident *r = t->rres;
+    if (!r || !r->haveBow || r->bowSerial != t->frameSerial) { g_lastError = std::string(entry) + ": no rumi_track_compute_bow precedes on the resident frame"; return RUMI_E_INVALID; }
+    const int n = t->curN;
+    if (K < 1 || (n > 0 && !matches)) { g_lastError = std::string(entry) + ": K < 1 or a missing output"; return RUMI_E_INVALID; }
+    // ---- the slots: a bad key-frame is named but not searched; every other one must hold features that fit its row
+    std::vector<int32_t> live, sorted(slots, slots + K);
+    std::vector<uint8_t> bad((size_t)K, 0);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { g_lastError = std::string(entry) + ": a slot named twice"; return RUMI_E_INVALID; }
+    for (int k = 0; k < K; k++) {
+        CovisCullSlot cs;
+        covis_cull_slot(c, slots[k], &cs);
+        if (!cs.live) { g_lastError = std::string(entry) + ": a slot outside the store or not live"; return RUMI_E_INVALID; }
+        bad[(size_t)k] = cs.bad ? 1 : 0;
+        if (!cs.bad) live.push_back(slots[k]);
+    }
+    std::vector<CovisSlotFeatures> info(live.size() + 1);
+    int rc;
+    if ((rc = covis_features_check(c, (int)live.size(), live.data(), t->device, entry, info.data())) != RUMI_OK) return rc;
+    // ---- device work from here on
+    HIP_TRY(hipSetDevice(t->device));
+    r->haveWalk = false;
+    const size_t Kn = (size_t)K * n;
+    const size_t oCnt = Kn * 4, oHist = oCnt + (size_t)K * 4, oBin = oHist + (size_t)K * 128, outBytes = oBin + Kn;
+    if ((rc = r->tab.reserve((size_t)K * sizeof(RbowCand), (size_t)K * sizeof(RbowCand) * 2)) != RUMI_OK || (rc = r->out.reserve(outBytes, outBytes + outBytes / 2)) != RUMI_OK)
+        return rc;
+    RbowCand *hc = reinterpret_cast<RbowCand *>(r->tab.h);
+    int maxNodes = 0;
+    for (int k = 0, l = 0; k < K; k++) {
+        if (bad[(size_t)k]) { hc[k] = RbowCand{0, 0, 0, 0, 1}; continue; }
+        const CovisSlotFeatures &I = info[(size_t)l++];
+        hc[k] = RbowCand{(long long)I.block, I.mpOff, I.n, I.nn, 0};
+        maxNodes = std::max(maxNodes, I.nn);
+    }
+    CovisFeatureView fv;
+    if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(r->tab.d, r->tab.h, (size_t)K * sizeof(RbowCand), hipMemcpyHostToDevice, nullptr));
+    if (Kn) HIP_TRY(hipMemsetAsync(r->out.d, 0xFF, Kn * 4, nullptr));                       // matches = -1
+    HIP_TRY(hipMemsetAsync(r->out.d + oCnt, 0, oBin - oCnt, nullptr));                      // counts and histograms
+    RbowArgs B{};
+    B.cands = reinterpret_cast<const RbowCand *>(r->tab.d);
+    B.feat = fv.feat; B.rows = fv.rows; B.pt = fv.pt;
+    B.fKeys = resident_keys(t); B.fDesc = reinterpret_cast<const uint32_t *>(t->d.record + t->oDesc);
+    B.fNodes = r->fvNodes.p; B.fIdx = r->fvIdx.p; B.fOff = r->fvOff.p; B.fNN = r->fvNN.p;
+    B.K = K; B.nf = n; B.words = std::max(1, ((n + 15) / 16 + 31) / 32);
+    B.matches = reinterpret_cast<int32_t *>(r->out.d); B.nmatch = reinterpret_cast<int32_t *>(r->out.d + oCnt);
+    B.hist = reinterpret_cast<int32_t *>(r->out.d + oHist); B.rotBin = reinterpret_cast<int8_t *>(r->out.d + oBin);
+    B.nnratio = nnratio; B.checkOri = check_orientation;
+    const size_t lds = (size_t)B.words * 256 * 4;
+    if (lds > 64 * 1024) HIP_TRY(raise_lds_limit(reinterpret_cast<const void *>(k_rbow_match), lds));
+    if (maxNodes > 0 && n > 0) hipLaunchKernelGGL(k_rbow_match, dim3((maxNodes + 15) / 16, K), dim3(256), lds, nullptr, B);
+    hipLaunchKernelGGL(k_rbow_finish, dim3(K), dim3(256), 0, nullptr, B);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(r->out.h, r->out.d, oHist, hipMemcpyDeviceToHost));                    // matches and counts: the call's one synchronisation
+    if (Kn) std::memcpy(matches, r->out.h, Kn * 4);
+    std::memcpy(nmatches_out, r->out.h + oCnt, (size_t)K * 4);
+    r->store = c; r->slots.assign(slots, slots + K); r->slotBad = bad;
+    r->walkSerial = t->frameSerial; r->haveWalk = true;
+    return RUMI_OK;
+}
+
+extern "C" int rumi_track_reloc_begin_resident(RumiTracker *t, RumiCovis *c, const float *K4, int32_t Kc, const int32_t *cand, int32_t *table_ids,
+                                               int32_t table_cap, int32_t *n_table) {
+    static const char *entry = "rumi_track_reloc_begin_resident";
+    if (!t || !c || !K4 || Kc < 0 || (Kc > 0 && !cand) || table_cap < 0 || (table_cap > 0 && !table_ids) || !n_table) {
+        g_lastError = std::string(entry) + ": missing argument or negative count";
+        return RUMI_E_INVALID;
+    }
+    if (t->curN < 0) { g_lastError = std::string(entry) + ": no frame is resident (rumi_track_extract first)"; return RUMI_E_INVALID; }
+    RelocResident *r = t->rres;
+    if (!r || !r->haveWalk || r->walkSerial != t->frameSerial || r->store != c) {
+        g_lastError = std::string(entry) + ": no rumi_track_reloc_bow on this store precedes on the resident frame";
+        return RUMI_E_INVALID;
+    }
+    const int n = t->curN, K = (int)r->slots.size();
+    std::vector<int32_t> sel((size_t)Kc);
+    for (int k = 0; k < Kc; k++) {
+        if (cand[k] < 0 || cand[k] >= K || r->slotBad[(size_t)cand[k]]) { g_lastError = std::string(entry) + ": a candidate outside [0, K) or naming a bad slot"; return RUMI_E_INVALID; }
+        sel[(size_t)k] = r->slots[(size_t)cand[k]];
+    }
+    std::vector<CovisSlotFeatures> info((size_t)Kc + 1);
+    int rc;
+    if ((rc = covis_features_check(c, Kc, sel.data(), t->device, entry, info.data())) != RUMI_OK) return rc;     // (also: a candidate named twice)
+    size_t keysAll = 0;
+    int maxNkf = 0;
+    for (int k = 0; k < Kc; k++) { keysAll += (size_t)info[(size_t)k].n; maxNkf = std::max(maxNkf, info[(size_t)k].n); }
+    if (keysAll > 0x7FFFFFFF / sizeof(RumiKeyPoint)) { g_lastError = std::string(entry) + ": the candidates' key-points exceed a 31-bit offset"; return RUMI_E_CAPACITY; }
+    // ---- device work from here on
+    HIP_TRY(hipSetDevice(t->device));
+    if (!t->reloc) t->reloc = new RelocState();
+    RelocState *s = t->reloc;
+    s->open = false;
+    const int rowCap = (int)std::min<size_t>(std::min(t->maxPts, table_cap), keysAll);      // a table has at most one row per key-frame feature
+    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    s->oKeys = al((size_t)Kc * sizeof(RelocCand)); s->oRows = al(s->oKeys + keysAll * sizeof(RumiKeyPoint)); s->oMatch = al(s->oRows + keysAll * 4);
+    s->oPos = al(s->oMatch + (size_t)Kc * n * 4); s->oMin = al(s->oPos + (size_t)rowCap * 12); s->oMax = al(s->oMin + (size_t)rowCap * 4);
+    s->oBad = al(s->oMax + (size_t)rowCap * 4); s->oDesc = al(s->oBad + (size_t)rowCap); s->oK4 = al(s->oDesc + (size_t)rowCap * 32);
+    const size_t bytes = s->oK4 + 16;
+    if ((rc = s->sess.reserve(bytes, bytes + bytes / 4)) != RUMI_OK) return rc;
+    if ((rc = r->tab.reserve((size_t)std::max(Kc, 1) * sizeof(RsessCand), (size_t)std::max(Kc, 1) * sizeof(RsessCand) * 2)) != RUMI_OK ||
+        (rc = r->ids.reserve(4 + (size_t)rowCap, 4 + (size_t)rowCap + (size_t)rowCap / 2)) != RUMI_OK)
+        return rc;
+    CovisFeatureView fv;
+    if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
+    if (r->rowOf.cap < (size_t)fv.maxPoints || r->epoch == 0xFFFFFFFFu) {
+        if ((rc = r->rowOf.reserve((size_t)fv.maxPoints, (size_t)fv.maxPoints)) != RUMI_OK) return rc;
+        HIP_TRY(hipMemsetAsync(r->rowOf.p, 0, r->rowOf.cap * 8, nullptr));
+        r->epoch = 0;
+    }
+    RsessCand *hc = reinterpret_cast<RsessCand *>(r->tab.h);
+    s->nkf.resize((size_t)Kc);
+    size_t at = 0;
+    for (int k = 0; k < Kc; k++) {
+        const CovisSlotFeatures &I = info[(size_t)k];
+        hc[k] = RsessCand{(long long)I.block, I.mpOff, I.n, (int32_t)at, cand[k]};
+        s->nkf[(size_t)k] = I.n;
+        at += (size_t)I.n;
+    }
+    if (Kc > 0) HIP_TRY(hipMemcpyAsync(r->tab.d, r->tab.h, (size_t)Kc * sizeof(RsessCand), hipMemcpyHostToDevice, nullptr));
+    uint8_t *ds = s->sess.d;
+    RsessArgs A{};
+    A.cands = reinterpret_cast<const RsessCand *>(r->tab.d);
+    A.Kc = Kc; A.n = n; A.rowCap = rowCap; A.epoch = ++r->epoch;
+    A.feat = fv.feat; A.rows = fv.rows; A.pt = fv.pt; A.attr = fv.attr;
+    A.rowOf = r->rowOf.p; A.head = r->ids.d; A.tableIds = r->ids.d + 4;
+    A.bowMatches = reinterpret_cast<const int32_t *>(r->out.d);
+    A.outCands = reinterpret_cast<RelocCand *>(ds); A.outKeys = reinterpret_cast<RumiKeyPoint *>(ds + s->oKeys);
+    A.outRows = reinterpret_cast<int32_t *>(ds + s->oRows); A.outMatch = reinterpret_cast<int32_t *>(ds + s->oMatch);
+    A.pos = reinterpret_cast<float *>(ds + s->oPos); A.minD = reinterpret_cast<float *>(ds + s->oMin); A.maxD = reinterpret_cast<float *>(ds + s->oMax);
+    A.bad = ds + s->oBad; A.desc = reinterpret_cast<uint32_t *>(ds + s->oDesc); A.k4Out = reinterpret_cast<float *>(ds + s->oK4);
+    std::memcpy(A.K4, K4, 16);
+    HIP_TRY(hipMemsetAsync(r->ids.d, 0, 16, nullptr));
+    if (Kc > 0) {
+        const int gx = std::max(1, (maxNkf + 255) / 256);
+        if (maxNkf > 0) hipLaunchKernelGGL(k_rtab_claim, dim3(gx, Kc), dim3(256), 0, nullptr, A);
+        hipLaunchKernelGGL(k_rtab_order, dim3(1), dim3(kTableThreads), 0, nullptr, A);
+        hipLaunchKernelGGL(k_rtab_gather, dim3(std::min(std::max((rowCap + 255) / 256, 1), 256)), dim3(256), 0, nullptr, A);
+        hipLaunchKernelGGL(k_rsess_fill, dim3(std::max(1, (std::max(maxNkf, n) + 255) / 256), Kc), dim3(256), 0, nullptr, A);
+        HIP_TRY(hipGetLastError());
+    } else HIP_TRY(hipMemcpyAsync(ds + s->oK4, K4, 16, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemcpy(r->ids.h, r->ids.d, 16, hipMemcpyDeviceToHost));
+    const int nmp = r->ids.h[0], nMissing = r->ids.h[1];
+    if (nMissing > 0) {
+        g_lastError = std::string(entry) + ": " + std::to_string(nMissing) + " row point(s) without attributes (rumi_covis_set_point_attributes)";
+        return RUMI_E_INVALID;
+    }
+    if (nmp > table_cap || nmp > t->maxPts) {
+        g_lastError = std::string(entry) + ": table_cap or the tracker's max_points is too small for the point table";
+        return RUMI_E_CAPACITY;
+    }
+    if (nmp > 0) HIP_TRY(hipMemcpyAsync(r->ids.h + 4, r->ids.d + 4, (size_t)nmp * 4, hipMemcpyDeviceToHost, nullptr));
+    // the resident frame as the matcher's kernels address it, and its grid (one for all hypotheses): as rumi_track_reloc_begin
+    t->projN = 0;
+    FrameDev fd;
+    if ((rc = track_frame_dev(t, &fd)) != RUMI_OK) return rc;
+    RumiMatcher *m = t->m;
+    FLUSH(m);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    s->fd = fd; s->K = Kc; s->nmp = nmp; s->maxNkf = maxNkf; s->words = (nmp + 31) / 32 + 1; s->n = n;
+    std::memcpy(s->K4, K4, 16);
+    s->serial = t->frameSerial;
+    s->open = true;
+    if (nmp > 0) std::memcpy(table_ids, r->ids.h + 4, (size_t)nmp * 4);
+    *n_table = nmp;
+    return RUMI_OK;
+}

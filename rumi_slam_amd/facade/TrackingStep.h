@@ -554,6 +554,12 @@ int TrackFrame(FrameT &Cur, const cv::Mat &im, ExtractorT &extractor, const floa
     return r.mono_index;
 }
 
+namespace track_detail {
+template <class FrameT, class SolverT, class SolverStep, class PointOf>
+bool reloc_rounds(FrameT &F, RumiTracker *t, std::vector<bool> &vbDiscarded, const std::vector<int> &sessionOf, int nCandidates, std::vector<SolverT> &vpSolvers,
+                  SolverStep step, PointOf pointOf, TrackStep &st, bool speculateRound);
+}
+
 // Tracking::Relocalization (Tracking.cc:3212-3357) from `vpCandidateKFs` on, on the frame ExtractFrame left resident (F.mFeatVec computed:
 // Frame::ComputeBoW).  :3226-3259 with the existing pieces -- isBad, the batched SearchByBoW (ORBmatcher.h, nnratio 0.75), `nmatches < 15`, and
 // make(F, vvpMapPointMatches[i]), through which the CALLER constructs and configures its solver (this header names no solver type; the
@@ -612,6 +618,18 @@ bool Relocalization(FrameT &F, const std::vector<KeyFrameT *> &vpCandidateKFs, M
     const RumiTrackPoints P = tab.view();
     int rc = rumi_track_reloc_begin(t, K4, nCandidates, cands.data(), &P);
     if (rc != RUMI_OK) { report("Relocalization: rumi_track_reloc_begin", rc); return leave(false); }
+    return leave(track_detail::reloc_rounds(F, t, vbDiscarded, sessionOf, nCandidates, vpSolvers, step, [&](int32_t row) { return tab.byId[row]; }, st, speculateRound));
+}
+
+namespace track_detail {
+// The rounds of Tracking.cc:3266-3348 on an open session, for Relocalization and RelocalizationResident: step() for every live candidate in
+// order, one rumi_track_reloc_refine for the round's hypotheses (speculateRound) or one a hypothesis, and the replay.  sessionOf[i]: candidate
+// i's index in the session; pointOf(row): the MapPoint of a table row.
+template <class FrameT, class SolverT, class SolverStep, class PointOf>
+bool reloc_rounds(FrameT &F, RumiTracker *t, std::vector<bool> &vbDiscarded, const std::vector<int> &sessionOf, int nCandidates, std::vector<SolverT> &vpSolvers,
+                  SolverStep step, PointOf pointOf, TrackStep &st, bool speculateRound) {
+    const int nKFs = (int)vbDiscarded.size();
+    int rc;
     RumiRelocParams prm;
     rumi_reloc_default_params(&prm);
     const size_t cap = (size_t)tracker_cfg().nfeatures + 4 * tracker_cfg().nlevels + 64;
@@ -635,7 +653,7 @@ bool Relocalization(FrameT &F, const std::vector<KeyFrameT *> &vpCandidateKFs, M
             const bool wins = (res[h].ran & 2) && res[h].ngood_final >= prm.enough;         // :3342
             if (wins || h == H - 1) {
                 const int32_t *m = &mp[(size_t)h * cap];
-                for (int f = 0; f < F.N; f++) F.mvpMapPoints[f] = m[f] >= 0 ? tab.byId[m[f]] : nullptr;
+                for (int f = 0; f < F.N; f++) F.mvpMapPoints[f] = m[f] >= 0 ? pointOf(m[f]) : nullptr;
                 track_detail::set_pose(F, res[h].Tcw);
                 std::memcpy(st.Tcw, res[h].Tcw, 28);
                 st.relocGood = res[h].ngood_final;
@@ -665,7 +683,101 @@ bool Relocalization(FrameT &F, const std::vector<KeyFrameT *> &vpCandidateKFs, M
         }
         if (speculateRound && !hyps.empty()) bMatch = refine(hyps);
     }
-    return leave(bMatch);
+    return bMatch;
+}
+}  // namespace track_detail
+
+// Frame::ComputeBoW (Frame.cc:763-768) on the frame ExtractFrame left resident (rumi_track_compute_bow): F.mFeatVec, and F.mBowVec where the
+// frame type has one (RUMI_TRACK_FRAME_HAS_BOWVEC, as TrackReferenceKeyFrame), through rumi_voc_assemble; the frame's FeatureVector also
+// stays on the device, where RelocalizationResident reads it.  False: refused or failed, reported, the frame untouched.
+template <class FrameT> bool ComputeBoWResident(FrameT &F, const ORBVocabulary &voc, int levelsup = 4) {
+    RumiTracker *t = tracker_slot();
+    if (!t) { report("ComputeBoWResident: ExtractFrame has not run on this thread", RUMI_E_INVALID); return false; }
+    const size_t capN = (size_t)tracker_cfg().nfeatures + 4 * tracker_cfg().nlevels + 64;
+    std::vector<uint32_t> word(capN), node(capN);
+    std::vector<double> wgt(capN);
+    int rc = rumi_track_compute_bow(t, voc.handle(), levelsup, word.data(), wgt.data(), node.data());
+    if (rc != RUMI_OK) { report("ComputeBoWResident: rumi_track_compute_bow", rc); return false; }
+    const int n = F.N;
+    std::vector<uint32_t> bowIds(n > 0 ? n : 1), fvNodes(n > 0 ? n : 1), fvIdx(n > 0 ? n : 1);
+    std::vector<double> bowVals(n > 0 ? n : 1);
+    std::vector<int32_t> fvOff(n + 1);
+    int32_t nWords = 0, nNodes = 0;
+    rc = rumi_voc_assemble(voc.handle(), n, word.data(), wgt.data(), node.data(), bowIds.data(), bowVals.data(), &nWords, fvNodes.data(), fvOff.data(), fvIdx.data(), &nNodes);
+    if (rc != RUMI_OK) { report("ComputeBoWResident: rumi_voc_assemble", rc); return false; }
+    F.mFeatVec.clear();
+    for (int a = 0; a < nNodes; a++) {
+        auto it = F.mFeatVec.insert(F.mFeatVec.end(), typename decltype(F.mFeatVec)::value_type(fvNodes[a], typename decltype(F.mFeatVec)::mapped_type()));
+        it->second.assign(fvIdx.begin() + fvOff[a], fvIdx.begin() + fvOff[a + 1]);
+    }
+#ifdef RUMI_TRACK_FRAME_HAS_BOWVEC
+    F.mBowVec.clear();
+    for (int k = 0; k < nWords; k++) F.mBowVec.insert(F.mBowVec.end(), typename decltype(F.mBowVec)::value_type(bowIds[k], bowVals[k]));
+#endif
+    return true;
+}
+
+// Relocalization by slot, after ComputeBoWResident on this frame: the candidates are slots of a CovisibilityGraph (CovisibilityGraph.h) whose
+// key-frames carry their features (SyncFeatures) and whose points carry their attributes (SyncAttributes / MarkDirty).  graph.FlushDirty(),
+// ONE rumi_track_reloc_bow over the candidates that are not bad, make(F, vvpMapPointMatches[i]) with the matches as MapPoint*, ONE
+// rumi_track_reloc_begin_resident over those that keep 15 matches, then the rounds and the replay of Relocalization.  Returns 1 / 0 for the
+// reference's true / false, and -1 when the call is refused -- a candidate the graph has never seen or without features, a stereo
+// key-frame (NLeft != -1), a point without attributes, a failed device call before the first round: reported, the frame untouched (make may
+// have run); the caller then runs Relocalization.
+template <class GraphT, class FrameT, class KeyFrameT, class MakeSolver, class SolverStep>
+int RelocalizationResident(GraphT &graph, FrameT &F, const std::vector<KeyFrameT *> &vpCandidateKFs, MakeSolver make, SolverStep step, TrackStep *out,
+                           bool speculateRound = true) {
+    using MapPointT = typename std::remove_pointer<typename std::decay<decltype(F.mvpMapPoints[0])>::type>::type;
+    const char *where = "RelocalizationResident";
+    TrackStep st = out ? *out : TrackStep();
+    st.relocCandidates = st.relocRounds = st.relocRefines = st.relocHypotheses = 0; st.relocWinner = -1; st.relocGood = -1;
+    auto leave = [&](int r) { if (out) *out = st; return r; };
+    RumiTracker *t = tracker_slot();
+    if (!t || !graph.ok()) { report("RelocalizationResident: ExtractFrame has not run on this thread, or no store", RUMI_E_INVALID); return leave(-1); }
+    const int nKFs = (int)vpCandidateKFs.size();
+    if (nKFs == 0) return leave(0);                                                          // :3221
+    if (graph.FlushDirty() != RUMI_OK) return leave(-1);
+    std::vector<int32_t> slots;
+    std::vector<int> sentOf(nKFs, -1);                                                       // candidate -> its place among the slots sent
+    for (int i = 0; i < nKFs; i++) {
+        KeyFrameT *pKF = vpCandidateKFs[i];
+        if (!pKF || pKF->isBad()) continue;                                                  // :3245
+        if (pKF->NLeft != -1) { report(where, RUMI_E_INVALID, "a stereo key-frame (NLeft != -1): only the monocular path is built"); return leave(-1); }
+        if (graph.SlotOf(pKF) < 0 || !graph.HasFeatures(pKF)) { report(where, RUMI_E_INVALID, "a candidate the graph has not seen, or without SyncFeatures"); return leave(-1); }
+        sentOf[i] = (int)slots.size();
+        slots.push_back(graph.SlotOf(pKF));
+    }
+    std::vector<bool> vbDiscarded(nKFs, true);
+    std::vector<int> sessionOf(nKFs, -1);
+    std::vector<std::vector<MapPointT *>> vvpMapPointMatches(nKFs, std::vector<MapPointT *>((size_t)(F.N > 0 ? F.N : 1), nullptr));
+    using SolverT = decltype(make(F, vvpMapPointMatches[0]));
+    std::vector<SolverT> vpSolvers(nKFs);
+    if (slots.empty()) return leave(0);
+    const int K = (int)slots.size(), n = F.N;
+    std::vector<int32_t> matches((size_t)K * (n > 0 ? n : 1), -1), nm(K, 0), cand;
+    int rc = rumi_track_reloc_bow(t, graph.handle(), K, slots.data(), 0.75f, 1, matches.data(), nm.data());      // :3230, :3248
+    if (rc != RUMI_OK) { report("RelocalizationResident: rumi_track_reloc_bow", rc); return leave(-1); }
+    int nCandidates = 0;
+    for (int i = 0; i < nKFs; i++) {
+        if (sentOf[i] < 0 || nm[sentOf[i]] < 15) continue;                                   // :3249-3251
+        const int32_t *m = &matches[(size_t)sentOf[i] * n];
+        for (int f = 0; f < n; f++) if (m[f] >= 0) vvpMapPointMatches[i][f] = graph.PointAt(m[f]);
+        vpSolvers[i] = make(F, vvpMapPointMatches[i]);                                       // :3253-3255
+        vbDiscarded[i] = false;
+        sessionOf[i] = nCandidates++;
+        cand.push_back(sentOf[i]);
+    }
+    st.relocCandidates = nCandidates;
+    if (nCandidates == 0) return leave(0);
+    const int cap = std::min(graph.PointCount() + 1, tracker_points());
+    std::vector<int32_t> ids(cap > 0 ? cap : 1, -1);
+    int32_t nTable = 0;
+    const float K4[4] = {F.fx, F.fy, F.cx, F.cy};
+    rc = rumi_track_reloc_begin_resident(t, graph.handle(), K4, nCandidates, cand.data(), ids.data(), cap, &nTable);
+    if (rc != RUMI_OK) { report("RelocalizationResident: rumi_track_reloc_begin_resident", rc); return leave(-1); }
+    const bool bMatch = track_detail::reloc_rounds(F, t, vbDiscarded, sessionOf, nCandidates, vpSolvers, step, [&](int32_t row) { return graph.PointAt(ids[row]); }, st,
+                                                   speculateRound);
+    return leave(bMatch ? 1 : 0);
 }
 
 }  // namespace rumi_facade

@@ -80,6 +80,9 @@ def _bind(L):
     L.rumi_track_reloc_begin.argtypes = [vp, vp, i32, vp, C.POINTER(RumiTrackPoints)]
     L.rumi_track_reloc_refine.argtypes = [vp, C.POINTER(RumiRelocParams), i32, vp, vp, vp, vp]
     L.rumi_track_reloc_attempts.argtypes = [vp, C.POINTER(i32)]
+    L.rumi_track_compute_bow.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.rumi_track_reloc_bow.argtypes = [vp, vp, i32, vp, f32, i32, vp, vp]
+    L.rumi_track_reloc_begin_resident.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp]
     L._track_ready = True
     return L
 
@@ -343,6 +346,53 @@ class Tracker:
         capi.check(self._lib.rumi_track_reloc_attempts(self._h, C.byref(a)))
         return a.value
 
+    # ---- Tracking::Relocalization by slot: the BoW walk and the refine session read the covisibility store (include/rumi_track.h) ----
+    def compute_bow_into(self, voc, levelsup, word, wgt, node):
+        """The raw rumi_track_compute_bow call: its status code.  voc None / an output None goes in as NULL."""
+        return self._lib.rumi_track_compute_bow(self._h, voc._h if voc is not None else None, int(levelsup), capi.ptr(word) if word is not None else None,
+                                                capi.ptr(wgt) if wgt is not None else None, capi.ptr(node) if node is not None else None)
+
+    def compute_bow(self, voc, levelsup=4):
+        """rumi_track_compute_bow: Frame::ComputeBoW on the resident frame -> dict word_id, word_weight, node_id [n] (the per-feature transform,
+        for Vocabulary.assemble); the frame's FeatureVector stays on the device for reloc_bow."""
+        word = np.zeros(self.cap, np.uint32); node = np.zeros(self.cap, np.uint32); wgt = np.zeros(self.cap, np.float64)
+        t0 = time.perf_counter()
+        rc = self.compute_bow_into(voc, levelsup, word, wgt, node)
+        self.last_call_s = time.perf_counter() - t0
+        capi.check(rc)
+        n = self._n
+        return dict(word_id=word[:n].copy(), word_weight=wgt[:n].copy(), node_id=node[:n].copy())
+
+    def reloc_bow_into(self, cov, slots, nnratio, check_orientation, matches, nmatches):
+        """The raw rumi_track_reloc_bow call: its status code; outputs written in place (matches [K, n] i32, nmatches [K] i32)."""
+        s = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        return self._lib.rumi_track_reloc_bow(self._h, cov._h, len(s), capi.ptr(s) if len(s) else None, float(nnratio), int(check_orientation),
+                                              capi.ptr(matches) if matches is not None and matches.size else None, capi.ptr(nmatches))
+
+    def reloc_bow(self, cov, slots, nnratio=0.75, check_orientation=True):
+        """rumi_track_reloc_bow: SearchByBoW of the key-frames in `slots` of the covisibility store `cov` against the resident frame (after
+        compute_bow) -> (nmatches [K] (-1: a bad key-frame, not searched), matches [K, n] store point ids, -1 = NULL)."""
+        K = len(slots)
+        matches = np.full((K, self._n), -1, np.int32); nm = np.zeros(max(K, 1), np.int32)
+        capi.check(self.reloc_bow_into(cov, slots, nnratio, check_orientation, matches, nm))
+        return nm[:K].copy(), matches
+
+    def reloc_begin_resident_into(self, cov, K4, cand, table_ids, table_cap, n_table):
+        """The raw rumi_track_reloc_begin_resident call: its status code; table_ids [table_cap] i32 and n_table [1] i32 written in place."""
+        K4 = np.ascontiguousarray(K4, np.float32)
+        cd = np.ascontiguousarray(cand, np.int32).reshape(-1)
+        return self._lib.rumi_track_reloc_begin_resident(self._h, cov._h, capi.ptr(K4), len(cd), capi.ptr(cd) if len(cd) else None, capi.ptr(table_ids),
+                                                         int(table_cap), capi.ptr(n_table))
+
+    def reloc_begin_resident(self, cov, K4, cand, table_cap=None):
+        """rumi_track_reloc_begin_resident: the session of reloc_refine from the store, for the candidates `cand` (indices into the slots of the
+        preceding reloc_bow) -> table_ids [n_table]: the store point id of every table row (reloc_refine's frame_mp holds rows)."""
+        table_cap = min(cov.max_points, self.max_points) if table_cap is None else int(table_cap)
+        ids = np.full(max(table_cap, 1), -1, np.int32); nt = np.zeros(1, np.int32)
+        capi.check(self.reloc_begin_resident_into(cov, K4, cand, ids, table_cap, nt))
+        self._reloc_K = len(cand)
+        return ids[:int(nt[0])].copy()
+
 
 def relocalize(tracker, cands, pts, solver_step, speculate_round=True, K4=None, params=None, frame_mp=None, outlier=None, Tcw=None):
     """The round loop of Tracking::Relocalization (R/lib_src/Tracking.cc:3266-3348) over tracker.reloc_refine.  cands [K]: the candidates of
@@ -359,8 +409,15 @@ def relocalize(tracker, cands, pts, solver_step, speculate_round=True, K4=None, 
     if K4 is not None:
         tracker.reloc_begin(K4, [c if c is not None else dict(kf_keys=np.zeros(0, KP_DTYPE), kf_mp=[], matches=np.full(getattr(tracker, "_n", 0), -1, np.int32))
                                  for c in cands], pts)
+    return _relocalize_rounds(tracker, [c is None for c in cands], lambda i: i, lambda mp: mp.copy(), solver_step, speculate_round, params, frame_mp, outlier, Tcw)
+
+
+def _relocalize_rounds(tracker, discarded, cand_of, map_mp, solver_step, speculate_round, params, frame_mp, outlier, Tcw):
+    """The rounds of relocalize / relocalize_resident on an open session.  discarded [K]: the candidates that are out from the start;
+    cand_of(i): candidate i's index in the session; map_mp(row): a hypothesis' frame_mp as the caller numbers its points."""
+    K = len(discarded)
+    discarded = list(discarded)
     enough = params.enough if params is not None else 50
-    discarded = [c is None for c in cands]
     n_cand = discarded.count(False)
     st = dict(matched=False, frame_mp=None if frame_mp is None else np.array(frame_mp, np.int32), outlier=None if outlier is None else np.array(outlier, np.uint8),
               Tcw=None if Tcw is None else np.array(Tcw, np.float32), winner=-1, rounds=0, steps=[0] * K, refines=0)
@@ -371,7 +428,7 @@ def relocalize(tracker, cands, pts, solver_step, speculate_round=True, K4=None, 
             st["outlier"] = np.zeros(len(ol), np.uint8)
         w = ol != 255
         st["outlier"][w] = ol[w]
-        st["frame_mp"] = mp.copy(); st["Tcw"] = np.array(r["Tcw"], np.float32)
+        st["frame_mp"] = map_mp(mp); st["Tcw"] = np.array(r["Tcw"], np.float32)
         if (int(r["ran"]) & 2) and int(r["ngood_final"]) >= enough:
             st["matched"] = True; st["winner"] = cand
             return True
@@ -395,7 +452,7 @@ def relocalize(tracker, cands, pts, solver_step, speculate_round=True, K4=None, 
                 if b_tcw:
                     hyps.append((i, T, inl))
             if hyps:
-                mp, ol, res = tracker.reloc_refine(hyps, params)
+                mp, ol, res = tracker.reloc_refine([(cand_of(i), T, inl) for i, T, inl in hyps], params)
                 st["refines"] += 1
                 for h, (i, _, _) in enumerate(hyps):
                     if replay(i, mp[h], ol[h], res[h]):
@@ -408,8 +465,35 @@ def relocalize(tracker, cands, pts, solver_step, speculate_round=True, K4=None, 
                 if b_no_more:
                     discarded[i] = True; n_cand -= 1
                 if b_tcw:
-                    mp, ol, res = tracker.reloc_refine([(i, T, inl)], params)
+                    mp, ol, res = tracker.reloc_refine([(cand_of(i), T, inl)], params)
                     st["refines"] += 1
                     if replay(i, mp[0], ol[0], res[0]):
                         break
     return st
+
+
+def relocalize_resident(tracker, cov, slots, solver_step, K4, make=None, nnratio=0.75, check_orientation=True, min_matches=15, speculate_round=True, params=None,
+                        frame_mp=None, outlier=None, Tcw=None):
+    """Tracking::Relocalization (R/lib_src/Tracking.cc:3226-3348) by slot, after tracker.compute_bow on the resident frame: one reloc_bow over
+    the candidate slots of the covisibility store `cov`, make(k, matches_k) for every candidate that keeps at least min_matches (:3253: the
+    caller sets up its solver from the matches, store point ids), one reloc_begin_resident over those, then the rounds of relocalize.
+    solver_step(k) as in relocalize, k an index into `slots`.  -> the dict of relocalize, frame_mp in store point ids, plus nmatches [K],
+    matches [K, n] and table_ids."""
+    nm, matches = tracker.reloc_bow(cov, slots, nnratio, check_orientation)
+    keep = [k for k in range(len(slots)) if nm[k] >= min_matches]
+    if make is not None:
+        for k in keep:
+            make(k, matches[k])
+    ids = tracker.reloc_begin_resident(cov, K4, keep)
+    place = {k: j for j, k in enumerate(keep)}
+    st = _relocalize_rounds(tracker, [k not in place for k in range(len(slots))], lambda k: place[k], lambda mp: rows_to_ids(mp, ids), solver_step, speculate_round,
+                            params, frame_mp, outlier, Tcw)
+    st.update(nmatches=nm, matches=matches, table_ids=ids)
+    return st
+
+
+def rows_to_ids(rows, table_ids):
+    """Table rows (-1 = NULL) as the store's point ids."""
+    rows = np.asarray(rows, np.int32)
+    ids = np.asarray(table_ids, np.int32)
+    return np.where(rows >= 0, ids[np.clip(rows, 0, max(len(ids) - 1, 0))] if len(ids) else -1, -1).astype(np.int32)
