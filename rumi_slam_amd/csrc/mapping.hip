@@ -26,6 +26,7 @@
 #include "keyframe_features.h"
 #include "match_host.h"
 #include "match_grid.h"
+#include "match_bow.h"
 
 namespace rumi {
 
@@ -124,11 +125,8 @@ template <class View> __global__ __launch_bounds__(256) void k_newpts_match(cons
     const typename View::KF C = view.kf(0), N = view.kf(1 + k);
     const int nn1 = C.nn(), nn2 = N.nn(), n1 = C.n();
     if (a >= nn1) return;
-    const uint32_t *nodes2 = N.nodes();
-    const uint32_t id = C.nodes()[a];
-    int lo = 0, hi = nn2;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (nodes2[mid] < id) lo = mid + 1; else hi = mid; }
-    if (lo >= nn2 || nodes2[lo] != id) return;
+    const int lo = fv_find_node(N.nodes(), nn2, C.nodes()[a]);
+    if (lo < 0) return;
     const int32_t *off1 = C.off(), *off2 = N.off(), *mp1 = C.mp(), *mp2 = N.mp();
     const uint32_t *idx1 = C.idx(), *idx2 = N.idx();
     const RumiKeyPoint *keys1 = C.keys(), *keys2 = N.keys();
@@ -368,7 +366,7 @@ struct NewPtsResult {
 };
 
 // One workgroup walks the neighbours in order.  Feature i belongs to thread i % 1024 in every pass, so a free flag is only ever touched by
-// its own thread; the histogram uses integer LDS atomics (order-free), the emission is an ordered compaction (ballot, wave totals, running base).
+// its own thread; the histogram uses integer LDS atomics (order-free), the emission is an ordered compaction (block_ordered_slot).
 // matched (may be null: only rumi_hook_newpts_matches passes it) receives stages 1 + 3 per neighbour.
 template <class View>
 __global__ __launch_bounds__(1024) void k_newpts_replay(const View view, int nNeigh, int checkOri, const int32_t *__restrict__ cand,
@@ -377,7 +375,7 @@ __global__ __launch_bounds__(1024) void k_newpts_replay(const View view, int nNe
     __shared__ uint8_t sFree[kMaxCur];
     __shared__ int sHist[RUMI_HISTO_LENGTH], sKeep[RUMI_HISTO_LENGTH], sWave[16], sBase;
     const typename View::KF C = view.kf(0);
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), n1 = C.n();
+    const int tid = threadIdx.x, n1 = C.n();
     const RumiKeyPoint *keys1 = C.keys();
     const int32_t *mp1 = C.mp();
     for (int i = tid; i < n1; i += 1024) sFree[i] = mp1[i] < 0;
@@ -401,18 +399,7 @@ __global__ __launch_bounds__(1024) void k_newpts_replay(const View view, int nNe
                 if (f >= 0) atomicAdd(&sHist[rot_bin(keys1[i].angle, keys2[f].angle)], 1);
             }
             __syncthreads();
-            if (tid == 0) {                                  // ComputeThreeMaxima, as k_tri_filter has it
-                int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-                for (int i = 0; i < RUMI_HISTO_LENGTH; i++) {
-                    const int s = sHist[i];
-                    if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                    else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                    else if (s > max3) { max3 = s; ind3 = i; }
-                }
-                if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-                else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
-                for (int i = 0; i < RUMI_HISTO_LENGTH; i++) sKeep[i] = (i == ind1 || i == ind2 || i == ind3);
-            }
+            if (tid == 0) three_maxima_keep(sHist, sKeep);
             __syncthreads();
         }
         for (int c0 = 0; c0 < n1; c0 += 1024) {
@@ -424,22 +411,13 @@ __global__ __launch_bounds__(1024) void k_newpts_replay(const View view, int nNe
                 if (f >= 0 && (!checkOri || sKeep[rot_bin(keys1[i].angle, keys2[f].angle)])) { idx2 = f; emit = gate[(size_t)k * n1 + i] == GATE_OK; }
                 if (matched) matchedK[i] = idx2;
             }
-            const unsigned long long b = __ballot(emit);
-            if (lane == 0) sWave[wave] = __popcll(b);
-            __syncthreads();
-            int off = sBase;
-            for (int w = 0; w < wave; w++) off += sWave[w];
-            if (emit) {
-                const int c = off + __popcll(b & ((1ull << lane) - 1));
+            block_ordered_slot(emit, sWave, &sBase, [&](int c) {
                 const float *x = x3D + 3 * ((size_t)k * n1 + i);
                 RumiNewPoint P;
                 P.neigh = k; P.idx1 = i; P.idx2 = idx2; P.x3D[0] = x[0]; P.x3D[1] = x[1]; P.x3D[2] = x[2];
                 res->pts[c] = P;
                 sFree[i] = 0;                                // mpCurrentKeyFrame->AddMapPoint(pMP, idx1), :636
-            }
-            __syncthreads();
-            if (tid == 0) { int t = sBase; for (int w = 0; w < 16; w++) t += sWave[w]; sBase = t; }
-            __syncthreads();
+            });
         }
         if (tid == 0) res->perNeigh[k] = sBase - before;
     }

@@ -28,10 +28,8 @@ __global__ __launch_bounds__(256) void k_bow_batch_match(BowBatch B) {
     const BowKF *T = reinterpret_cast<const BowKF *>(B.blk + B.kfTable) + k;
     if (a >= T->nn) return;
     const uint32_t *kfNodes = B.blk + T->nodes, *fNodes = B.blk + B.fNodes;
-    const uint32_t node = kfNodes[a];
-    int lo = 0, hi = B.nnF;                                  // first frame node >= node (std::map order: ascending ids)
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (fNodes[mid] < node) lo = mid + 1; else hi = mid; }
-    if (lo >= B.nnF || fNodes[lo] != node) return;
+    const int lo = fv_find_node(fNodes, B.nnF, kfNodes[a]);
+    if (lo < 0) return;
     const int32_t *fOff = reinterpret_cast<const int32_t *>(B.blk + B.fOff), *kOff = reinterpret_cast<const int32_t *>(B.blk + T->off);
     const int c0 = fOff[lo], nc = fOff[lo + 1] - c0;
     if (nc > 512) { if (lane == 0) atomicOr(B.err, 1); return; }
@@ -40,78 +38,23 @@ __global__ __launch_bounds__(256) void k_bow_batch_match(BowBatch B) {
     const float *fAngle = reinterpret_cast<const float *>(B.blk + B.fAngle), *kAngle = reinterpret_cast<const float *>(B.blk + T->angle);
     const int32_t *kMp = reinterpret_cast<const int32_t *>(B.blk + T->mp);
     const uint8_t *kGood = reinterpret_cast<const uint8_t *>(B.blk + T->good);
-    uint32_t taken = 0;                                      // bit j: my candidate lane + 16 j already holds a map point
-    for (int p = kOff[a]; p < kOff[a + 1]; p++) {
-        const int iKF = (int)kIdx[p];
-        if (!kGood[iKF]) continue;                           // no map point, or a bad one (:238-243)
-        uint32_t q[8];
-#pragma unroll
-        for (int w = 0; w < 8; w++) q[w] = kDesc[(size_t)iKF * 8 + w];
-        uint32_t best = (256u << 16) | 0xFFFFu, second = 256u;
-        for (int j = 0, pos = lane; pos < nc; j++, pos += 16) {
-            if ((taken >> j) & 1u) continue;
-            const uint32_t *d = fDesc + (size_t)fIdx[pos] * 8;
-            uint32_t dist = 0;
-#pragma unroll
-            for (int w = 0; w < 8; w++) dist += __popc(q[w] ^ d[w]);
-            const uint32_t key = (dist << 16) | (uint32_t)pos;
-            if (key < best) { second = best >> 16; best = key; }       // a strictly smaller distance, or the same at an earlier position
-            else if (dist < second) second = dist;
-        }
-        // 16-lane reduction: best = smallest key; second = second smallest distance of the union
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {
-            const uint32_t ob = __shfl_xor(best, o, 16), os = __shfl_xor(second, o, 16);
-            const uint32_t loser = max(best, ob) >> 16;
-            best = min(best, ob);
-            second = min(min(second, os), loser);
-        }
-        const int bestDist1 = (int)(best >> 16), bestDist2 = (int)second;
-        if (bestDist1 <= RUMI_TH_LOW && (float)bestDist1 < B.nnratio * (float)bestDist2) {
-            const int pos = (int)(best & 0xFFFFu), f = (int)fIdx[pos];
-            if (lane == (pos & 15)) taken |= 1u << (pos >> 4);
-            if (lane == 0) {
-                B.matches[(size_t)k * B.nf + f] = kMp[iKF];
-                if (B.checkOri) {
-                    const int bin = rot_bin(kAngle[iKF], fAngle[f]);
-                    B.rotBin[(size_t)k * B.nf + f] = (int8_t)bin;
-                    atomicAdd(&B.hist[k * 32 + bin], 1);
-                }
-            }
-        }
-    }
+    TakenMask taken;                                         // a frame feature that already holds a map point
+    bow_node_walk<false>(lane, kIdx, kOff[a], kOff[a + 1], kDesc, fIdx, nc, fDesc, B.nnratio, taken,
+                         [&](int iKF) { return kGood[iKF] != 0; },                          // no map point, or a bad one (:238-243)
+                         [&](int iKF, int f) {
+                             B.matches[(size_t)k * B.nf + f] = kMp[iKF];
+                             if (B.checkOri) {
+                                 const int bin = rot_bin(kAngle[iKF], fAngle[f]);
+                                 B.rotBin[(size_t)k * B.nf + f] = (int8_t)bin;
+                                 atomicAdd(&B.hist[k * 32 + bin], 1);
+                             }
+                         });
 }
 
 // rotation-histogram filter (ComputeThreeMaxima, ORBmatcher.cc:1795-1826) and the match count of every key-frame
 __global__ __launch_bounds__(256) void k_bow_batch_finish(BowBatch B) {
-    __shared__ int sKeep[RUMI_HISTO_LENGTH], sCount;
-    const int k = blockIdx.x, tid = threadIdx.x;
-    if (tid == 0) {
-        sCount = 0;
-        for (int i = 0; i < RUMI_HISTO_LENGTH; i++) sKeep[i] = 1;
-        if (B.checkOri) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) {
-                const int s = B.hist[k * 32 + i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) ind3 = -1;
-            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) sKeep[i] = (i == ind1 || i == ind2 || i == ind3);
-        }
-    }
-    __syncthreads();
-    int local = 0;
-    for (int f = tid; f < B.nf; f += 256) {
-        int32_t &m = B.matches[(size_t)k * B.nf + f];
-        if (m < 0) continue;
-        if (B.checkOri && !sKeep[B.rotBin[(size_t)k * B.nf + f]]) m = -1; else local++;
-    }
-    atomicAdd(&sCount, local);
-    __syncthreads();
-    if (tid == 0) B.nmatch[k] = sCount;
+    const int k = blockIdx.x;
+    bow_finish(B.matches + (size_t)k * B.nf, B.rotBin + (size_t)k * B.nf, B.hist + k * 32, B.nf, B.checkOri, &B.nmatch[k]);
 }
 
 // ---- host side: layout, pack, launch, unpack or fallback ----

@@ -8,7 +8,7 @@ namespace rumi {
 // search starts from an empty vbMatched2, so the searches are independent; inside one search "a member feature is taken by the first query that wins it"
 // never leaves a FeatureVector node (a feature lies in exactly one node).  So: grid over (node of the current key-frame, member), 16 lanes per pair;
 // the current key-frame's features of the node run in list order, the lanes share out the member's features of the node and reduce (best, second)
-// with the (dist << 16 | position) key, as k_bow_batch_match does with the roles swapped.  Differences to that kernel: the query side is the one
+// with the (dist << 16 | position) key: bow_node_walk (match_bow.h), which k_bow_batch_match calls with the roles swapped.  What this caller passes: the query side is the one
 // current key-frame, BOTH sides carry a "holds a good map point" gate (ORBmatcher.cc:717-721, :736-742), acceptance is bestDist1 < TH_LOW (strict,
 // :757) and the output is the member's FEATURE index.
 // ------------------------------------------------------------------------------------------------
@@ -37,10 +37,8 @@ __global__ __launch_bounds__(256) void k_crb_match(CrArgs A) {
     if (a >= A.nnC) return;
     const CrKF *T = reinterpret_cast<const CrKF *>(A.blk + A.kfTable) + reinterpret_cast<const int32_t *>(A.blk + A.memKf)[mem];
     const uint32_t *kNodes = A.blk + T->nodes;
-    const uint32_t node = (A.blk + A.cNodes)[a];
-    int lo = 0, hi = T->nn;                                  // first member node >= node (std::map order: ascending ids)
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (kNodes[mid] < node) lo = mid + 1; else hi = mid; }
-    if (lo >= T->nn || kNodes[lo] != node) return;
+    const int lo = fv_find_node(kNodes, T->nn, (A.blk + A.cNodes)[a]);
+    if (lo < 0) return;
     const int32_t *cOff = reinterpret_cast<const int32_t *>(A.blk + A.cOff), *kOff = reinterpret_cast<const int32_t *>(A.blk + T->off);
     const int c0 = kOff[lo], nc = kOff[lo + 1] - c0;
     if (nc > 512) { if (lane == 0) atomicOr(A.err, 1); return; }
@@ -48,82 +46,27 @@ __global__ __launch_bounds__(256) void k_crb_match(CrArgs A) {
     const uint32_t *kDesc = A.blk + T->desc, *cDesc = A.blk + A.cDesc;
     const float *kAngle = reinterpret_cast<const float *>(A.blk + T->angle), *cAngle = reinterpret_cast<const float *>(A.blk + A.cAngle);
     const uint8_t *kGood = reinterpret_cast<const uint8_t *>(A.blk + T->good), *cGood = reinterpret_cast<const uint8_t *>(A.blk + A.cGood);
-    uint32_t taken = 0;                                      // bit j: my candidate lane + 16 j is matched already, or holds no good map point (:738-742)
+    TakenMask taken;                                         // a member feature that is matched already, or holds no good map point (:738-742)
     for (int j = 0, pos = lane; pos < nc; j++, pos += 16)
-        if (!kGood[kIdx[pos]]) taken |= 1u << j;
-    for (int p = cOff[a]; p < cOff[a + 1]; p++) {
-        const int iC = (int)cIdx[p];
-        if (!cGood[iC]) continue;                            // no map point, or a bad one (:717-721); uniform over the 16 lanes
-        uint32_t q[8];
-#pragma unroll
-        for (int w = 0; w < 8; w++) q[w] = cDesc[(size_t)iC * 8 + w];
-        uint32_t best = (256u << 16) | 0xFFFFu, second = 256u;
-        for (int j = 0, pos = lane; pos < nc; j++, pos += 16) {
-            if ((taken >> j) & 1u) continue;
-            const uint32_t *d = kDesc + (size_t)kIdx[pos] * 8;
-            uint32_t dist = 0;
-#pragma unroll
-            for (int w = 0; w < 8; w++) dist += __popc(q[w] ^ d[w]);
-            const uint32_t key = (dist << 16) | (uint32_t)pos;
-            if (key < best) { second = best >> 16; best = key; }       // a strictly smaller distance (positions ascend inside a lane)
-            else if (dist < second) second = dist;
-        }
-        // 16-lane reduction: best = smallest key (equal distances: the earlier list entry, :748); second = second smallest distance of the union
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {
-            const uint32_t ob = __shfl_xor(best, o, 16), os = __shfl_xor(second, o, 16);
-            const uint32_t loser = max(best, ob) >> 16;
-            best = min(best, ob);
-            second = min(min(second, os), loser);
-        }
-        const int bestDist1 = (int)(best >> 16), bestDist2 = (int)second;
-        if (bestDist1 < RUMI_TH_LOW && (float)bestDist1 < A.nnratio * (float)bestDist2) {      // :757-758
-            const int pos = (int)(best & 0xFFFFu), f = (int)kIdx[pos];
-            if (lane == (pos & 15)) taken |= 1u << (pos >> 4);
-            if (lane == 0) {
-                A.matches[(size_t)mem * A.n + iC] = f;
-                if (A.checkOri) {
-                    // (angles of real key-points give bins 0..12; the clamp keeps a malformed angle inside the histogram)
-                    const int bin = min(max(rot_bin(cAngle[iC], kAngle[f]), 0), RUMI_HISTO_LENGTH - 1);
-                    A.rotBin[(size_t)mem * A.n + iC] = (int8_t)bin;
-                    atomicAdd(&A.hist[mem * 32 + bin], 1);
-                }
-            }
-        }
-    }
+        if (!kGood[kIdx[pos]]) taken.set(j);
+    bow_node_walk<true>(lane, cIdx, cOff[a], cOff[a + 1], cDesc, kIdx, nc, kDesc, A.nnratio, taken,            // strict: :757-758
+                        [&](int iC) { return cGood[iC] != 0; },                             // no map point, or a bad one (:717-721)
+                        [&](int iC, int f) {
+                            A.matches[(size_t)mem * A.n + iC] = f;
+                            if (A.checkOri) {
+                                // (angles of real key-points give bins 0..12; the clamp keeps a malformed angle inside the histogram)
+                                const int bin = min(max(rot_bin(cAngle[iC], kAngle[f]), 0), RUMI_HISTO_LENGTH - 1);
+                                A.rotBin[(size_t)mem * A.n + iC] = (int8_t)bin;
+                                atomicAdd(&A.hist[mem * 32 + bin], 1);
+                            }
+                        });
 }
 
 // rotation-histogram filter (ComputeThreeMaxima, ORBmatcher.cc:1795-1826) and the match count of every member.  A match the histogram removes has
 // kept its member feature taken during the search, as in the reference, where the filter runs after the walk (:786-801).
 __global__ __launch_bounds__(256) void k_crb_finish(CrArgs A) {
-    __shared__ int sKeep[RUMI_HISTO_LENGTH], sCount;
-    const int mem = blockIdx.x, tid = threadIdx.x;
-    if (tid == 0) {
-        sCount = 0;
-        for (int i = 0; i < RUMI_HISTO_LENGTH; i++) sKeep[i] = 1;
-        if (A.checkOri) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) {
-                const int s = A.hist[mem * 32 + i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
-            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) sKeep[i] = (i == ind1 || i == ind2 || i == ind3);
-        }
-    }
-    __syncthreads();
-    int local = 0;
-    for (int k = tid; k < A.n; k += 256) {
-        int32_t &f = A.matches[(size_t)mem * A.n + k];
-        if (f < 0) continue;
-        if (A.checkOri && !sKeep[A.rotBin[(size_t)mem * A.n + k]]) f = -1; else local++;
-    }
-    if (local) atomicAdd(&sCount, local);
-    __syncthreads();
-    if (tid == 0) A.nmatch[mem] = sCount;
+    const int mem = blockIdx.x;
+    bow_finish(A.matches + (size_t)mem * A.n, A.rotBin + (size_t)mem * A.n, A.hist + mem * 32, A.n, A.checkOri, &A.nmatch[mem]);
 }
 
 // The union of one group (LoopClosing.cc:635-651 walks j ascending, then k ascending): one workgroup per group, integer atomics only, so the

@@ -1,5 +1,6 @@
 // Device helpers the matcher kernels (match.hip and its match_*.inc parts: queries, candidates, resolve, tri, bow_batch, reloc_batch), the Tracking
-// step (track.hip) and the mapping kernels (mapping.hip) share, among them the one body of every projection gate that has more than one caller.
+// step (track.hip) and the mapping kernels (mapping.hip) share, among them the one body of every projection gate that has more than one caller, of
+// ComputeThreeMaxima in its serial and its one-wave form, of the finish of a batched SearchByBoW, and of the ordered compaction of a workgroup.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -46,6 +47,84 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 __device__ __forceinline__ int wave_sum_i32(int v) { return __builtin_amdgcn_readlane(wave_scan_incl_i32(v), 63); }
+
+// ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:1795-1826) and the filter around it, in its two forms.  Neither is converted into the other: one
+// thread against one wave is a speed choice of the kernel that calls it.
+// Serial form, called by ONE thread: the scan of the 30 bins with its strict comparisons, the two 0.1f cuts in float, keep[bin] = bin is one of the three.
+__device__ __forceinline__ void three_maxima_keep(const int *hist, int *keep) {
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int i = 0; i < RUMI_HISTO_LENGTH; i++) {
+        const int s = hist[i];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+        else if (s > max3) { max3 = s; ind3 = i; }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
+    for (int i = 0; i < RUMI_HISTO_LENGTH; i++) keep[i] = (i == ind1 || i == ind2 || i == ind3);
+}
+// One-wave form, called by the first wave of a workgroup with s = its lane's bin count (0 from lane 30 on): the scan keeps the three largest counts
+// ordered by (count descending, bin ascending) and empty bins never enter, which is three maxima of (count << 6 | 63 - bin).  Returns the lane's
+// keep flag; *removed: the entries of the bins that go.  Without useHist every bin stays.
+__device__ __forceinline__ int three_maxima_wave(int s, bool useHist, int *removed) {
+    const int lane = threadIdx.x;
+    int keep = 1;
+    *removed = 0;
+    if (useHist) {
+        uint32_t key = s > 0 ? ((uint32_t)s << 6) | (uint32_t)(63 - lane) : 0u;
+        const uint32_t k1 = wave_max_u32(key);
+        if (key == k1) key = 0;
+        const uint32_t k2 = wave_max_u32(key);
+        if (key == k2) key = 0;
+        const uint32_t k3 = wave_max_u32(key);
+        const int max1 = (int)(k1 >> 6), max2 = (int)(k2 >> 6), max3 = (int)(k3 >> 6);
+        int ind1 = k1 ? 63 - (int)(k1 & 63) : -1, ind2 = k2 ? 63 - (int)(k2 & 63) : -1, ind3 = k3 ? 63 - (int)(k3 & 63) : -1;
+        if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+        else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
+        keep = (lane == ind1 || lane == ind2 || lane == ind3);
+        *removed = wave_sum_i32(keep ? 0 : s);
+    }
+    return keep;
+}
+// The end of a batched SearchByBoW, one workgroup of 256 per row of a [rows][n] match matrix: the matches whose rotBin the row's histogram rejects
+// become -1, the others are counted.  (32 keep flags read with & 31: a bin is 0..29 for every finite angle, and no byte indexes past the array.)
+__device__ __forceinline__ void bow_finish(int32_t *matches, const int8_t *rotBin, const int32_t *hist, int n, int checkOri, int32_t *count) {
+    __shared__ int sKeep[32], sCount;
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        sCount = 0;
+        for (int i = 0; i < 32; i++) sKeep[i] = 1;
+        if (checkOri) three_maxima_keep(hist, sKeep);
+    }
+    __syncthreads();
+    int local = 0;
+    for (int f = tid; f < n; f += 256) {
+        if (matches[f] < 0) continue;
+        if (checkOri && !sKeep[rotBin[f] & 31]) matches[f] = -1; else local++;
+    }
+    if (local) atomicAdd(&sCount, local);
+    __syncthreads();
+    if (tid == 0) *count = sCount;
+}
+
+// One chunk of an ordered compaction by a workgroup of 1024: every thread brings a flag, the flagged ones get consecutive slots in thread order behind
+// *sBase and call emit(slot), then *sBase advances by their number.  Three barriers: the wave counts; every slot taken (the emits run between the
+// first two, where the sites had their stores) before thread 0 moves the base; the new base.
+template <class Emit>
+__device__ __forceinline__ void block_ordered_slot(bool flag, int *sCnt /* [16] */, int *sBase, Emit emit) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned long long b = __ballot(flag);
+    if (lane == 0) sCnt[wave] = __popcll(b);
+    __syncthreads();
+    if (flag) {
+        int slot = *sBase;
+        for (int k = 0; k < wave; k++) slot += sCnt[k];
+        emit(slot + __popcll(b & ((1ull << lane) - 1ull)));
+    }
+    __syncthreads();
+    if (tid == 0) { int t = *sBase; for (int k = 0; k < 16; k++) t += sCnt[k]; *sBase = t; }
+    __syncthreads();
+}
 
 struct Query {           // 48 bytes
     float u, v, r;       // window centre / half-size (MODE_BOW: unused)
@@ -165,32 +244,26 @@ struct __attribute__((packed, aligned(4))) Dword4 { uint32_t x, y, z, w; };
 __device__ __forceinline__ uint4 ld16_dword(const void *q) { const Dword4 t = *reinterpret_cast<const Dword4 *>(q); return make_uint4(t.x, t.y, t.z, t.w); }
 
 // Correspondences of Optimizer::PoseOptimization(Frame*) (Optimizer.cc:749-815, mono): the features with a map point, in feature order.
-// One workgroup of 1024 threads, ordered compaction (ballot + wave offsets through LDS, chunks of 1024 features).
+// One workgroup of 1024 threads, ordered compaction (block_ordered_slot, chunks of 1024 features).  correspondence_store: feature i with point mp
+// as correspondence c, also for the relocalisation's gather (track_reloc.inc).
+__device__ __forceinline__ void correspondence_store(int c, int i, int mp, const RumiKeyPoint *__restrict__ keys, const float *__restrict__ mpPos,
+                                                     const float *__restrict__ invSigma2, float *Xw, float *obs, float *w, int32_t *idx) {
+    Xw[3 * c] = mpPos[3 * mp]; Xw[3 * c + 1] = mpPos[3 * mp + 1]; Xw[3 * c + 2] = mpPos[3 * mp + 2];
+    obs[2 * c] = keys[i].x; obs[2 * c + 1] = keys[i].y;
+    w[c] = invSigma2[keys[i].octave];
+    idx[c] = i;
+}
 __device__ __forceinline__ void gather_correspondences(int n, const RumiKeyPoint *__restrict__ keys, const int32_t *featMp, const float *__restrict__ mpPos,
                                                        const float *__restrict__ invSigma2, float *Xw, float *obs, float *w, int32_t *idx, int32_t *start,
                                                        int32_t *snapshot, int *sWave /* [16] */, int *sBase) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tid = threadIdx.x;
     if (tid == 0) *sBase = 0;
     __syncthreads();
     for (int c0 = 0; c0 < n; c0 += 1024) {
         const int i = c0 + tid;
         const int mp = i < n ? featMp[i] : -1;
         if (snapshot && i < n) snapshot[i] = mp;            // the frame's map-point vector as the search left it (the optimisation's outliers leave it next)
-        const unsigned long long b = __ballot(mp >= 0);
-        if (lane == 0) sWave[wave] = __popcll(b);
-        __syncthreads();
-        int off = *sBase;
-        for (int k = 0; k < wave; k++) off += sWave[k];
-        if (mp >= 0) {
-            const int c = off + __popcll(b & ((1ull << lane) - 1));
-            Xw[3 * c] = mpPos[3 * mp]; Xw[3 * c + 1] = mpPos[3 * mp + 1]; Xw[3 * c + 2] = mpPos[3 * mp + 2];
-            obs[2 * c] = keys[i].x; obs[2 * c + 1] = keys[i].y;
-            w[c] = invSigma2[keys[i].octave];
-            idx[c] = i;
-        }
-        __syncthreads();
-        if (tid == 0) { int t = *sBase; for (int k = 0; k < 16; k++) t += sWave[k]; *sBase = t; }
-        __syncthreads();
+        block_ordered_slot(mp >= 0, sWave, sBase, [&](int c) { correspondence_store(c, i, mp, keys, mpPos, invSigma2, Xw, obs, w, idx); });
     }
     if (tid == 0) { start[0] = 0; start[1] = *sBase; }
 }

@@ -53,10 +53,8 @@ __global__ void k_queries_bow(int nnKF, const uint32_t *kfNodes, const int32_t *
     int a = 0, ahi = nnKF;                                  // the node that holds entry p: last a with kfOff[a] <= p
     while (ahi - a > 1) { const int mid = (a + ahi) >> 1; if (kfOff[mid] <= p) a = mid; else ahi = mid; }
     // the merge-walk of the two ordered maps visits exactly the node ids present in both
-    int lo = 0, hi = nnF;
-    const uint32_t id = kfNodes[a];
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (fNodes[mid] < id) lo = mid + 1; else hi = mid; }
-    const bool hit = lo < nnF && fNodes[lo] == id;
+    const int lo = fv_find_node(fNodes, nnF, kfNodes[a]);
+    const bool hit = lo >= 0;
     Query o{};
     const int feat = (int)kfIdx[p];
     const int mp = kfMp[feat];

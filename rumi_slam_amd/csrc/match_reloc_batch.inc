@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kRelocResolveThreads) void k_reloc_resolve(RelocSea
         if (!any) break;
         for (int f = tid; f < nfeat; f += nt) sBlockedFrom[f] = featMp[f] >= 0 ? -1 : kFree;
     }
-    // rotation histogram and ComputeThreeMaxima as k_resolve runs them (ORBmatcher.cc:1759-1790, :1795-1826)
+    // rotation histogram and ComputeThreeMaxima in the one-wave form (ORBmatcher.cc:1759-1790, :1795-1826)
     __syncthreads();
     const RumiKeyPoint *featKeys = A.fd.keys;
     int local = 0;
@@ -149,22 +149,8 @@ __global__ __launch_bounds__(kRelocResolveThreads) void k_reloc_resolve(RelocSea
     if (local) atomicAdd(&sCount, local);
     __syncthreads();
     if (tid < 64) {
-        const int s = tid < RUMI_HISTO_LENGTH ? sHist[tid] : 0;
-        int keep = 1, removed = 0;
-        if (A.checkOri) {
-            uint32_t key = s > 0 ? ((uint32_t)s << 6) | (uint32_t)(63 - tid) : 0u;
-            const uint32_t k1 = wave_max_u32(key);
-            if (key == k1) key = 0;
-            const uint32_t k2 = wave_max_u32(key);
-            if (key == k2) key = 0;
-            const uint32_t k3 = wave_max_u32(key);
-            const int max1 = (int)(k1 >> 6), max2 = (int)(k2 >> 6), max3 = (int)(k3 >> 6);
-            int ind1 = k1 ? 63 - (int)(k1 & 63) : -1, ind2 = k2 ? 63 - (int)(k2 & 63) : -1, ind3 = k3 ? 63 - (int)(k3 & 63) : -1;
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
-            keep = (tid == ind1 || tid == ind2 || tid == ind3);
-            removed = wave_sum_i32(keep ? 0 : s);
-        }
+        int removed;
+        const int keep = three_maxima_wave(tid < RUMI_HISTO_LENGTH ? sHist[tid] : 0, A.checkOri, &removed);
         if (tid < RUMI_HISTO_LENGTH) sKeep[tid] = keep;
         if (tid == 0) {
             // the stage's decision: Tracking.cc:3317 (S1, with P1's nGood) / :3330 (S2, with P2's)

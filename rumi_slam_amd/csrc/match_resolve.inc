@@ -127,24 +127,9 @@ __global__ __launch_bounds__(1024) void k_resolve(ResolveArgs A) {
     }
     if (local) atomicAdd(&sCount, local);
     __syncthreads();
-    if (tid < 64) {                                                      // ComputeThreeMaxima, ORBmatcher.cc:1795-1826, by the lanes of one wave:
-        // the scan with its strict comparisons keeps the three largest counts ordered by (count descending, bin ascending); empty bins never enter
-        const int s = tid < RUMI_HISTO_LENGTH ? sHist[tid] : 0;
-        int keep = 1, removed = 0;
-        if (useHist) {
-            uint32_t key = s > 0 ? ((uint32_t)s << 6) | (uint32_t)(63 - tid) : 0u;
-            const uint32_t k1 = wave_max_u32(key);
-            if (key == k1) key = 0;
-            const uint32_t k2 = wave_max_u32(key);
-            if (key == k2) key = 0;
-            const uint32_t k3 = wave_max_u32(key);
-            const int max1 = (int)(k1 >> 6), max2 = (int)(k2 >> 6), max3 = (int)(k3 >> 6);
-            int ind1 = k1 ? 63 - (int)(k1 & 63) : -1, ind2 = k2 ? 63 - (int)(k2 & 63) : -1, ind3 = k3 ? 63 - (int)(k3 & 63) : -1;
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
-            keep = (tid == ind1 || tid == ind2 || tid == ind3);
-            removed = wave_sum_i32(keep ? 0 : s);
-        }
+    if (tid < 64) {                                                      // ComputeThreeMaxima by the lanes of one wave
+        int removed;
+        const int keep = three_maxima_wave(tid < RUMI_HISTO_LENGTH ? sHist[tid] : 0, useHist, &removed);
         if (tid < RUMI_HISTO_LENGTH) sKeep[tid] = keep;
         if (tid == 0) *A.nmatches = sCount - removed;
     }
@@ -237,18 +222,7 @@ __global__ __launch_bounds__(64) void k_resolve_init(InitArgs A) {
     __syncthreads();
     if (lane == 0) {
         for (int i = 0; i < RUMI_HISTO_LENGTH; i++) sKeep[i] = 1;
-        if (A.checkOri) {                                                   // ComputeThreeMaxima over ALL accepted (also stolen) entries
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) {
-                const int s = sHist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
-            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) sKeep[i] = (i == ind1 || i == ind2 || i == ind3);
-        }
+        if (A.checkOri) three_maxima_keep(sHist, sKeep);                    // over ALL accepted (also stolen) entries
     }
     __syncthreads();
     // a surviving match keeps the bin it was accepted with (its feature never changes afterwards): :661-677

@@ -20,10 +20,8 @@ struct TriArgs {
 __global__ void k_tri_match(TriArgs A) {
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= A.nn1) return;
-    int lo = 0, hi = A.nn2;
-    const uint32_t id = A.nodes1[a];
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (A.nodes2[mid] < id) lo = mid + 1; else hi = mid; }
-    const bool hit = lo < A.nn2 && A.nodes2[lo] == id;
+    const int lo = fv_find_node(A.nodes2, A.nn2, A.nodes1[a]);
+    const bool hit = lo >= 0;
     const float *F = A.geom;
     const float epx = A.geom[9], epy = A.geom[10];
     for (int p = A.off1[a]; p < A.off1[a + 1]; p++) {
@@ -76,18 +74,7 @@ __global__ __launch_bounds__(256) void k_tri_filter(int nq, const uint32_t *idx1
             if (f >= 0) atomicAdd(&sHist[rot_bin(keys1[idx1[p]].angle, keys2[f].angle)], 1);
         }
         __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) {
-                const int s = sHist[i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
-            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) sKeep[i] = (i == ind1 || i == ind2 || i == ind3);
-        }
+        if (tid == 0) three_maxima_keep(sHist, sKeep);
         __syncthreads();
     }
     int local = 0;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "match_host.h"
+#include "match_bow.h"
 #include "rumi_orb.h"
 #include "rumi_track.h"
 #include "rumi_voc.h"
@@ -102,23 +103,14 @@ __global__ __launch_bounds__(kFvThreads) void k_fv_build(int n, int npad, const 
         }
     if (tid == 0) { sBase = 0; sValid = 0; }
     __syncthreads();
-    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (int c0 = 0; c0 < npad; c0 += kFvThreads) {
         const int i = c0 + tid;
         const unsigned long long key = i < npad ? fvKey[i] : ~0ull;
         const bool valid = key != ~0ull;
         const bool first = valid && (i == 0 || (uint32_t)(fvKey[i - 1] >> 32) != (uint32_t)(key >> 32));
         if (valid) fvIdx[i] = (uint32_t)key;
-        const unsigned long long b = __ballot(first);
-        if (lane == 0) sCnt[wave] = __popcll(b);
-        if (valid) atomicMax(&sValid, i + 1);
-        __syncthreads();
-        int off = sBase;
-        for (int k = 0; k < wave; k++) off += sCnt[k];
-        if (first) { const int a = off + __popcll(b & ((1ull << lane) - 1)); fvNodes[a] = (uint32_t)(key >> 32); fvOff[a] = i; }
-        __syncthreads();
-        if (tid == 0) { int t = sBase; for (int k = 0; k < kFvThreads / 64; k++) t += sCnt[k]; sBase = t; }
-        __syncthreads();
+        if (valid) atomicMax(&sValid, i + 1);                // (ahead of the step's first barrier; read behind its last)
+        block_ordered_slot(first, sCnt, &sBase, [&](int a) { fvNodes[a] = (uint32_t)(key >> 32); fvOff[a] = i; });
     }
     if (tid == 0) { fvOff[sBase] = sValid; *nnOut = sBase; }
 }

@@ -6,7 +6,7 @@
 // No host read between the seed and the one copy back.
 //
 //   k_reloc_seed    mvpMapPoints from matches[cand] and vbInliers, sFound as a bitmap by atomicOr, outlier_last = 255, the record; then P1's
-//                   correspondences in feature order by ballot prefix (k_track_gather's compaction) at start[h].  start[h] is the number of
+//                   correspondences in feature order (block_ordered_slot, as gather_correspondences) at start[h].  start[h] is the number of
 //                   correspondences of the hypotheses before h, which the workgroup counts itself: no scan launch.
 //   k_reloc_gather  the same gather from featMp[h] for P2 / P3 (count 0 for a hypothesis that does not run it: k_pose_opt then leaves its pose).
 //   k_reloc_after   outlier_last from the optimisation's flags, the nulling loops (:3309, :3333), the count compares (:3306, :3314, :3322), and
@@ -40,7 +40,7 @@ struct RelocArgs {
 template <class Before, class Mp>
 __device__ __forceinline__ void reloc_gather(const RelocArgs &A, int h, Before before, Mp mpOf) {
     __shared__ int sWave[16], sBase;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tid = threadIdx.x;
     if (tid == 0) sBase = 0;
     __syncthreads();
     int mine = 0;
@@ -52,21 +52,7 @@ __device__ __forceinline__ void reloc_gather(const RelocArgs &A, int h, Before b
     for (int c0 = 0; c0 < A.n; c0 += 1024) {
         const int i = c0 + tid;
         const int mp = i < A.n ? mpOf(i) : -1;
-        const unsigned long long b = __ballot(mp >= 0);
-        if (lane == 0) sWave[wave] = __popcll(b);
-        __syncthreads();
-        int off = sBase;
-        for (int k = 0; k < wave; k++) off += sWave[k];
-        if (mp >= 0) {
-            const int c = off + __popcll(b & ((1ull << lane) - 1));
-            A.Xw[3 * c] = A.pos[3 * mp]; A.Xw[3 * c + 1] = A.pos[3 * mp + 1]; A.Xw[3 * c + 2] = A.pos[3 * mp + 2];
-            A.obs[2 * c] = A.keys[i].x; A.obs[2 * c + 1] = A.keys[i].y;
-            A.w[c] = A.invSigma2[A.keys[i].octave];
-            A.idx[c] = i;
-        }
-        __syncthreads();
-        if (tid == 0) { int t = sBase; for (int k = 0; k < 16; k++) t += sWave[k]; sBase = t; }
-        __syncthreads();
+        block_ordered_slot(mp >= 0, sWave, &sBase, [&](int c) { correspondence_store(c, i, mp, A.keys, A.pos, A.invSigma2, A.Xw, A.obs, A.w, A.idx); });
     }
     if (tid == 0) { A.start[h] = base; if (h == A.H - 1) A.start[A.H] = sBase; }
 }

@@ -4,15 +4,16 @@
 // CovisFeatRec block of a slot (key-points, descriptors, mFeatVec as CSR), its map-point row in the row arena, the bad bits and the 64-byte
 // attribute records of the points.  A call sends slot numbers and a few words per candidate, nothing else.
 //
-//   k_rbow_match     SearchByBoW of every (candidate, key-frame node) pair, 16 lanes each: k_bow_batch_match's walk and tie rules.  A lane's
+//   k_rbow_match     SearchByBoW of every (candidate, key-frame node) pair, 16 lanes each: bow_node_walk (match_bow.h) over TakenLds.  A lane's
 //                    `taken` flags lie in LDS words of its own (word w of thread t at sTaken[w * 256 + t]; bit j of the lane's private mask is
 //                    position lane + 16 j of the node), as many words as the frame's feature count asks for: no node size is refused, and no
 //                    lane reads another lane's word, so there is nothing to synchronise.
-//   k_rbow_finish    ComputeThreeMaxima and the count of every candidate (k_bow_batch_finish's body); a bad slot's count is -1.
+//   k_rbow_finish    ComputeThreeMaxima and the count of every candidate (bow_finish, match_device.h); a bad slot's count is -1.
 //   k_rtab_claim     a lane per (candidate, key-frame feature): atomicMax of its claim u = place in (candidate order, feature order) on the
-//                    point's stamp: the lowest u wins (track_local_map.inc's scheme, a map and an epoch counter of the session's own).
-//   k_rtab_order     ONE workgroup: the winners in order of u by a ballot prefix, their rows, the ids of the rows, the rows without attributes.
-//   k_rtab_gather    a lane per row for position, distances and bad, eight lanes per row for the descriptor, into the session block.
+//                    point's stamp: the lowest u wins (the stamps of track_local_map.inc: table_claim, table_row, table_row_of; the map and the
+//                    epoch counter are the session's own).
+//   k_rtab_order     ONE workgroup: the winners in order of u (block_ordered_slot), their rows, the ids of the rows, the rows without attributes.
+//   k_rtab_gather    table_gather_rows without normal, obs and local: position, distances, bad and descriptor into the session block.
 //   k_rsess_fill     key-points out of the feature arena, map-point rows and BoW matches rewritten from point ids to table rows, the
 //                    RelocCand records and K4.
 // Integer atomics only (atomicOr / atomicAdd / atomicMax on integers): no result depends on the order anything arrives in.
@@ -49,93 +50,34 @@ __global__ __launch_bounds__(256) void k_rbow_match(RbowArgs B) {
     const RbowCand C = B.cands[k];
     if (C.bad || a >= C.nn) return;
     const CovisFeatRec *R = reinterpret_cast<const CovisFeatRec *>(B.feat + C.block);
-    const uint32_t *kfNodes = rec_arr<uint32_t>(R, R->nodes);
-    const uint32_t node = kfNodes[a];
-    const int nnF = B.fNN[0];
-    int lo = 0, hi = nnF;                                    // first frame node >= node (std::map order: ascending ids)
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (B.fNodes[mid] < node) lo = mid + 1; else hi = mid; }
-    if (lo >= nnF || B.fNodes[lo] != node) return;
+    const int lo = fv_find_node(B.fNodes, B.fNN[0], rec_arr<uint32_t>(R, R->nodes)[a]);
+    if (lo < 0) return;
     const int c0 = B.fOff[lo], nc = B.fOff[lo + 1] - c0;
     const int32_t *kOff = rec_arr<int32_t>(R, R->off);
     const uint32_t *fIdx = B.fIdx + c0, *kIdx = rec_arr<uint32_t>(R, R->idx), *kDesc = rec_arr<uint32_t>(R, R->desc);
     const RumiKeyPoint *kKeys = rec_arr<RumiKeyPoint>(R, R->keys);
     const int32_t *kMp = B.rows + C.mpOff;
-    uint32_t *taken = sTaken + threadIdx.x;                  // word w at taken[w * 256]; bit j & 31 of word j >> 5: my position lane + 16 j holds a map point
+    TakenLds taken{sTaken + threadIdx.x};                    // a frame feature that already holds a map point
     const int myWords = ((nc + 15) / 16 + 31) / 32;          // (<= B.words: a node holds at most nf features)
-    for (int w = 0; w < myWords; w++) taken[w * 256] = 0;
-    for (int p = kOff[a]; p < kOff[a + 1]; p++) {
-        const int iKF = (int)kIdx[p];
-        const int mp = kMp[iKF];
-        if (mp < 0 || (B.pt[(size_t)mp * kCovisPointWords + 2] & 1)) continue;      // no map point, or a bad one (:238-243)
-        uint32_t q[8];
-#pragma unroll
-        for (int w = 0; w < 8; w++) q[w] = kDesc[(size_t)iKF * 8 + w];
-        uint32_t best = (256u << 16) | 0xFFFFu, second = 256u;
-        for (int j = 0, pos = lane; pos < nc; j++, pos += 16) {
-            if ((taken[(j >> 5) * 256] >> (j & 31)) & 1u) continue;
-            const uint32_t *d = B.fDesc + (size_t)fIdx[pos] * 8;
-            uint32_t dist = 0;
-#pragma unroll
-            for (int w = 0; w < 8; w++) dist += __popc(q[w] ^ d[w]);
-            const uint32_t key = (dist << 16) | (uint32_t)pos;
-            if (key < best) { second = best >> 16; best = key; }       // a strictly smaller distance, or the same at an earlier position
-            else if (dist < second) second = dist;
-        }
-        // 16-lane reduction: best = smallest key; second = second smallest distance of the union
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {
-            const uint32_t ob = __shfl_xor(best, o, 16), os = __shfl_xor(second, o, 16);
-            const uint32_t loser = max(best, ob) >> 16;
-            best = min(best, ob);
-            second = min(min(second, os), loser);
-        }
-        const int bestDist1 = (int)(best >> 16), bestDist2 = (int)second;
-        if (bestDist1 <= RUMI_TH_LOW && (float)bestDist1 < B.nnratio * (float)bestDist2) {
-            const int pos = (int)(best & 0xFFFFu), f = (int)fIdx[pos];
-            if (lane == (pos & 15)) { const int j = pos >> 4; taken[(j >> 5) * 256] |= 1u << (j & 31); }
-            if (lane == 0) {
-                B.matches[(size_t)k * B.nf + f] = mp;
-                if (B.checkOri) {
-                    const int bin = rot_bin(kKeys[iKF].angle, B.fKeys[f].angle);
-                    B.rotBin[(size_t)k * B.nf + f] = (int8_t)bin;
-                    atomicAdd(&B.hist[k * 32 + bin], 1);
-                }
-            }
-        }
-    }
+    for (int w = 0; w < myWords; w++) taken.w[w * 256] = 0;
+    int mp = -1;                                             // the current query's point: the gate reads it, the match writes it
+    bow_node_walk<false>(lane, kIdx, kOff[a], kOff[a + 1], kDesc, fIdx, nc, B.fDesc, B.nnratio, taken,
+                         [&](int iKF) { mp = kMp[iKF]; return !(mp < 0 || (B.pt[(size_t)mp * kCovisPointWords + 2] & 1)); },   // no map point, or a bad one (:238-243)
+                         [&](int iKF, int f) {
+                             B.matches[(size_t)k * B.nf + f] = mp;
+                             if (B.checkOri) {
+                                 const int bin = rot_bin(kKeys[iKF].angle, B.fKeys[f].angle);
+                                 B.rotBin[(size_t)k * B.nf + f] = (int8_t)bin;
+                                 atomicAdd(&B.hist[k * 32 + bin], 1);
+                             }
+                         });
 }
 
 // rotation-histogram filter (ComputeThreeMaxima, ORBmatcher.cc:1795-1826) and the match count of every candidate; -1 for a bad slot (Tracking.cc:3245)
 __global__ __launch_bounds__(256) void k_rbow_finish(RbowArgs B) {
-    __shared__ int sKeep[32], sCount;
-    const int k = blockIdx.x, tid = threadIdx.x;
-    if (B.cands[k].bad) { if (tid == 0) B.nmatch[k] = -1; return; }
-    if (tid == 0) {
-        sCount = 0;
-        for (int i = 0; i < 32; i++) sKeep[i] = 1;
-        if (B.checkOri) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) {
-                const int s = B.hist[k * 32 + i];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-                else if (s > max3) { max3 = s; ind3 = i; }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) ind3 = -1;
-            for (int i = 0; i < RUMI_HISTO_LENGTH; i++) sKeep[i] = (i == ind1 || i == ind2 || i == ind3);
-        }
-    }
-    __syncthreads();
-    int local = 0;
-    for (int f = tid; f < B.nf; f += 256) {
-        int32_t &m = B.matches[(size_t)k * B.nf + f];
-        if (m < 0) continue;
-        if (B.checkOri && !sKeep[B.rotBin[(size_t)k * B.nf + f] & 31]) m = -1; else local++;
-    }
-    atomicAdd(&sCount, local);
-    __syncthreads();
-    if (tid == 0) B.nmatch[k] = sCount;
+    const int k = blockIdx.x;
+    if (B.cands[k].bad) { if (threadIdx.x == 0) B.nmatch[k] = -1; return; }
+    bow_finish(B.matches + (size_t)k * B.nf, B.rotBin + (size_t)k * B.nf, B.hist + k * 32, B.nf, B.checkOri, &B.nmatch[k]);
 }
 
 // ---- the session's point table and block ------------------------------------------------------------------------------------------------
@@ -162,23 +104,17 @@ struct RsessArgs {
     float K4[4];
 };
 
-__device__ __forceinline__ unsigned long long rsess_stamp(const RsessArgs &a, uint32_t value) { return ((unsigned long long)a.epoch << 32) | value; }
-__device__ __forceinline__ int rsess_row_of(const RsessArgs &a, int p) {
-    const unsigned long long s = a.rowOf[p];
-    return ((uint32_t)(s >> 32) == a.epoch && ((uint32_t)s & kRowBit)) ? (int)((uint32_t)s & ~kRowBit) : -1;
-}
-
 __global__ __launch_bounds__(256) void k_rtab_claim(RsessArgs a) {
     const RsessCand C = a.cands[blockIdx.y];
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= C.nkf) return;
     const int p = a.rows[C.mpOff + i];
-    if (p >= 0) atomicMax(&a.rowOf[p], rsess_stamp(a, 0x7FFFFFFFu - (uint32_t)(C.keyOff + i)));
+    if (p >= 0) atomicMax(&a.rowOf[p], table_claim(a.epoch, C.keyOff + i));
 }
 
 __global__ __launch_bounds__(kTableThreads) void k_rtab_order(RsessArgs a) {
     __shared__ int sCnt[kTableThreads / 64], sBase, sMissing;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) { sBase = 0; sMissing = 0; }
     __syncthreads();
     for (int k = 0; k < a.Kc; k++) {
@@ -186,57 +122,19 @@ __global__ __launch_bounds__(kTableThreads) void k_rtab_order(RsessArgs a) {
         for (int c0 = 0; c0 < C.nkf; c0 += kTableThreads) {
             const int i = c0 + tid;
             const int p = i < C.nkf ? a.rows[C.mpOff + i] : -1;
-            const bool win = p >= 0 && a.rowOf[p] == rsess_stamp(a, 0x7FFFFFFFu - (uint32_t)(C.keyOff + i));
-            const unsigned long long b = __ballot(win);
-            if (lane == 0) sCnt[wave] = __popcll(b);
-            __syncthreads();
-            if (win) {
-                int off = sBase;
-                for (int w = 0; w < wave; w++) off += sCnt[w];
-                const int row = off + __popcll(b & ((1ull << lane) - 1ull));
-                a.rowOf[p] = rsess_stamp(a, kRowBit | (uint32_t)row);
+            const bool win = p >= 0 && a.rowOf[p] == table_claim(a.epoch, C.keyOff + i);
+            block_ordered_slot(win, sCnt, &sBase, [&](int row) {
+                a.rowOf[p] = table_row(a.epoch, row);
                 if (row < a.rowCap) a.tableIds[row] = p;
                 if (!a.attr || !a.pt[(size_t)p * kCovisPointWords + 3]) atomicAdd(&sMissing, 1);
-            }
-            __syncthreads();
-            if (tid == 0) { int t = sBase; for (int w = 0; w < kTableThreads / 64; w++) t += sCnt[w]; sBase = t; }
-            __syncthreads();
+            });
         }
     }
     if (tid == 0) { a.head[0] = sBase; a.head[1] = sMissing; }
 }
 
-__global__ __launch_bounds__(256) void k_rtab_gather(RsessArgs a) {
-    __shared__ int sId[256];
-    const int tid = threadIdx.x, nTable = min(a.head[0], a.rowCap);
-    for (int base = blockIdx.x * 256; base < nTable; base += gridDim.x * 256) {
-        const int row = base + tid;
-        int id = -1;
-        if (row < nTable) {
-            const int p = a.tableIds[row];
-            const int4 P = *reinterpret_cast<const int4 *>(a.pt + (size_t)p * kCovisPointWords);
-            float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-            if (a.attr && P.w) {
-                id = p;
-                const float4 *A = reinterpret_cast<const float4 *>(a.attr + (size_t)p * kCovisAttrWords);
-                lo = A[0]; hi = A[1];
-            }
-            a.pos[(size_t)row * 3] = lo.x; a.pos[(size_t)row * 3 + 1] = lo.y; a.pos[(size_t)row * 3 + 2] = lo.z;
-            a.minD[row] = hi.z; a.maxD[row] = hi.w;
-            a.bad[row] = (uint8_t)(P.z & 1);
-        }
-        sId[tid] = id;                                       // -1: a row without attributes reads as zeros (the host refuses such a call)
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < 8; it++) {
-            const int r = it * 32 + (tid >> 3), w = tid & 7;
-            if (base + r < nTable) {
-                const int p = sId[r];
-                a.desc[(size_t)(base + r) * 8 + w] = p >= 0 ? (uint32_t)a.attr[(size_t)p * kCovisAttrWords + 8 + w] : 0u;
-            }
-        }
-        __syncthreads();
-    }
+__global__ __launch_bounds__(256) void k_rtab_gather(RsessArgs a) {       // (the host refuses a call that has a row without attributes)
+    table_gather_rows<false>(a.pt, a.attr, a.tableIds, min(a.head[0], a.rowCap), 0, TableRows{a.pos, nullptr, a.minD, a.maxD, nullptr, a.desc, a.bad, nullptr});
 }
 
 // grid (x, Kc): candidate blockIdx.y's key-points and row, then its matches; block (0, 0) also writes K4
@@ -250,13 +148,13 @@ __global__ __launch_bounds__(256) void k_rsess_fill(RsessArgs a) {
     for (int i = t0; i < C.nkf; i += step) {
         a.outKeys[C.keyOff + i] = keys[i];
         const int p = a.rows[C.mpOff + i];
-        int row = p >= 0 ? rsess_row_of(a, p) : -1;
+        int row = p >= 0 ? table_row_of(a.rowOf, a.epoch, p) : -1;
         if (row >= a.rowCap) row = -1;                       // (the host refuses such a call: nothing of it is read)
         a.outRows[C.keyOff + i] = row;
     }
     for (int f = t0; f < a.n; f += step) {
         const int p = a.bowMatches[(size_t)C.matchRow * a.n + f];
-        int row = p >= 0 ? rsess_row_of(a, p) : -1;
+        int row = p >= 0 ? table_row_of(a.rowOf, a.epoch, p) : -1;
         if (row >= a.rowCap) row = -1;
         a.outMatch[(size_t)k * a.n + f] = row;
     }

@@ -159,6 +159,32 @@ class NewPointsScene:
         return self.neigh[:n]
 
 
+# The rotation histogram ON its first cut: one neighbour, one FeatureVector node of at most 40 features a side.  13 of the pairs the search finds
+# (distinct features on both sides) get the angles of match_cases.HISTOGRAMS["cut_kept"], bins 2 / 5 / 8 / 10 with 10 / 1 / 1 / 1 pairs; the
+# other features of the current key-frame receive a map point and leave the search (the queries are independent: vbMatched2 is never set).
+# 1 < 0.1f * 10 is false in float, so bins 5 and 8 stay and bin 10 goes for being the fourth.
+CUT_KEPT = [(60.0, 0.0, 2)] * 10 + [(155.0, 5.0, 5), (250.0, 10.0, 8), (300.0, 0.0, 10)]
+
+
+def cut_kept_scene(L):
+    """-> (scene, pairs [13, 2], bins [13]) with the pairs in CUT_KEPT's order."""
+    s = NewPointsScene(70, 1, 40, mp_frac_cur=0.0, mp_frac_neigh=0.3, levelsup=3)
+    cur, nb = s.views[0], s.views[1]
+    assert len(cur["fv"][0]) == 1 and len(nb["fv"][0]) == 1 and len(cur["keys"]) <= 40 and len(nb["keys"]) <= 40
+    m = run_oracle(L, s.cur, s.neigh, params(0, 0, 0, TH_FAR))["matches"][0]
+    pairs, used = [], set()
+    for i1 in np.nonzero(m >= 0)[0]:
+        if int(m[i1]) not in used and len(pairs) < len(CUT_KEPT):
+            used.add(int(m[i1])); pairs.append((int(i1), int(m[i1])))
+    assert len(pairs) == len(CUT_KEPT), "the scene's search finds too few pairs"
+    cur["kf_mp"][:] = cur["land"]
+    for (i1, i2), (a1, a2, _) in zip(pairs, CUT_KEPT):
+        cur["kf_mp"][i1] = -1
+        cur["keys"]["angle"][i1] = a1; nb["keys"]["angle"][i2] = a2
+    s.cur, s.neigh = s._view(cur, False), [s._view(nb, True)]
+    return s, np.array(pairs, np.int32), np.array([b for _, _, b in CUT_KEPT])
+
+
 # ---- the C++ oracle ----
 def build_oracle(out_dir):
     O.lib()                                                    # builds oracle/liboracle.so when it is missing

@@ -14,8 +14,10 @@ candidate   what it carries (all under nnratio = 0.75, check_orientation = true 
   0 edges     best distance exactly TH_LOW (accepted), TH_LOW + 1 (refused); bestDist1 == nnratio * bestDist2 exactly in float, 30 against 40
               (refused); a NULL row entry and a bad point (skipped); a key-frame node the frame does not have; plain matches
   1 order     two frame features of one node at equal distance (refused at 0.75 whatever the order; at nnratio = 1.25 the earlier position
-              wins); two key-frame features contending for one frame feature: the first takes it, the second takes its runner-up, or nothing;
-              in the root setting with the contended feature in each 512-position stretch of the node
+              wins), once anywhere in a node and once 16 or 32 positions apart, where one lane of a 16-lane walk meets both; two key-frame features contending for one frame feature: the first takes it, the second takes its runner-up, or nothing;
+              in the root setting with the contended feature in each 512-position stretch of the node; its matches in four rotation bins,
+              30 / 3 / 3 / 3 (the cut_kept histogram of match_cases.py three times over): 3 < 0.1f * 30 is false in float, so the second and
+              the third bin stay and the fourth goes for being the fourth
   2 rotation  matches in four rotation bins, 12 / 8 / 6 / 3: ComputeThreeMaxima drops the fourth
   3 bad       a key-frame whose bad bit is set: not searched, count -1
   4 shared    29 against 39, one bit nearer than 30 against 40 (accepted); the points of candidate 0's plain matches again: one table row each
@@ -41,6 +43,7 @@ K = 6
 SLOTS = [3, 7, 1, 9, 4, 6]              # the store slot of candidate k: not its index
 EDGES, ORDER, ROTATION, BAD, SHARED, SIZES = range(K)
 ROT_BINS = ((0, 12), (3, 8), (6, 6), (9, 3))
+CUT_BINS = ((0, 30), (3, 3), (6, 3), (9, 3))      # candidate ORDER's histogram
 N_PLAIN = 20
 
 
@@ -170,6 +173,7 @@ class _Builder:
         self.claimed = [set() for _ in range(K)]          # the frame features a candidate's gadgets rely on
         self.expect = [dict() for _ in range(K)]          # frame feature -> point id or -1, nnratio 0.75 with the orientation check
         self.expect_ties = [dict() for _ in range(K)]     # the same at nnratio 1.25, for the features of the tie gadgets only
+        self.expect_ties_lane = [dict() for _ in range(K)]   # ... and of the tie that lies in one lane
         self.gadgets = []                                 # (name, candidate, key-frame features, frame features)
         self.rng = np.random.default_rng(11)
 
@@ -251,10 +255,14 @@ class _Builder:
             return
         raise AssertionError(f"no pair of frame features for {best} against {second}")
 
-    def tie(self, k):
-        """f before g in one node, both at distance D / 2 of the key-frame feature, everything else farther."""
-        for f, g, D in self.pairs(k, lambda D: D % 2 == 0 and 2 <= D <= 60):
-            q = flipped(self.desc[f], self.rng.choice(bits_of(self.desc[f], self.desc[g], True), D // 2, replace=False))
+    def tie(self, k, same_lane=False):
+        """f before g in one node, both at distance D / 2 of the key-frame feature, everything else farther.  same_lane: g a multiple of 16 positions
+        behind f (up to TH_LOW away: such pairs are few), drawn from a generator of its own so that the other gadgets stay what they were."""
+        rng = np.random.default_rng(12) if same_lane else self.rng
+        for f, g, D in self.pairs(k, lambda D: D % 2 == 0 and 2 <= D <= (2 * TH_LOW if same_lane else 60)):
+            if same_lane and (self.pos_of[g] - self.pos_of[f]) % 16:
+                continue
+            q = flipped(self.desc[f], rng.choice(bits_of(self.desc[f], self.desc[g], True), D // 2, replace=False))
             assert ham(q, self.desc[[f, g]]).tolist() == [D // 2, D // 2]
             o = self.others(q, f, g)
             if len(o) and o.min() <= D // 2:
@@ -263,8 +271,9 @@ class _Builder:
             i = self.kfs[k].add(self.key(f), q, self.node_of[f], p, "tie")
             self.claimed[k].update((f, g))
             self.expect[k][f] = self.expect[k][g] = -1                 # d < 0.75 d never holds
-            self.expect_ties[k][f] = p; self.expect_ties[k][g] = -1    # d < 1.25 d: the earlier position
-            self.gadgets.append(("tie", k, [i], [f, g]))
+            ties = self.expect_ties_lane if same_lane else self.expect_ties
+            ties[k][f] = p; ties[k][g] = -1                            # d < 1.25 d: the earlier position
+            self.gadgets.append(("tie_same_lane" if same_lane else "tie", k, [i], [f, g]))
             return
         raise AssertionError("no pair of frame features for a tie")
 
@@ -344,12 +353,14 @@ def build(setting):
             B.contend(ORDER, False, lambda f: B.pos_of[f] >= 16)
     for f in B.free(ORDER)[:N_PLAIN]:
         B.plain(ORDER, f)
-    # 2 rotation
-    for bin_, cnt in ROT_BINS:
-        for f in B.free(ROTATION)[:cnt]:
-            B.plain(ROTATION, f, bin_, tag=f"bin{bin_}")
-            if bin_ == ROT_BINS[-1][0]:
-                B.expect[ROTATION][f] = -1
+    B.tie(ORDER, same_lane=True)
+    have = sum(p >= 0 for p in B.expect[ORDER].values())              # every match so far votes for bin 0
+    for k, bins in ((ORDER, ((0, CUT_BINS[0][1] - have),) + CUT_BINS[1:]), (ROTATION, ROT_BINS)):       # 2 rotation
+        for bin_, cnt in bins:
+            for f in B.free(k)[:cnt]:
+                B.plain(k, f, bin_, tag=f"bin{bin_}")
+                if bin_ == bins[-1][0]:
+                    B.expect[k][f] = -1
     # 3 bad slot
     for f in B.free(BAD)[:N_PLAIN]:
         B.plain(BAD, f)
@@ -376,7 +387,7 @@ def build(setting):
     counts = [(int((expect[k] >= 0).sum()) if k != BAD else -1) for k in range(K)]
     expect[BAD] = -1
     S = dict(setting=setting, levelsup=SETTINGS[setting], fv=B.fv, kfs=kfs, bad_slot=[k == BAD for k in range(K)], points=pts, expect=expect, counts=counts,
-             expect_ties=B.expect_ties, gadgets=B.gadgets, sizes=sorted({int(B.size_of[f]) for k in range(K) for f in B.claimed[k]}),
+             expect_ties=B.expect_ties, expect_ties_lane=B.expect_ties_lane, gadgets=B.gadgets, sizes=sorted({int(B.size_of[f]) for k in range(K) for f in B.claimed[k]}),
              n=B.n, pos_of=B.pos_of, size_of=B.size_of)
     _assert_conditions(S)
     return S
@@ -406,9 +417,11 @@ def _assert_conditions(S):
         elif name == "ratio29_39":
             best, second, f, ok = tr[kf_feats[0]]
             assert (best, second) == (29, 39) and ok and f == f_feats[0]
-        elif name == "tie":
+        elif name in ("tie", "tie_same_lane"):
             best, second, f, ok = tr[kf_feats[0]]
             assert best == second and best > 0 and not ok and f == f_feats[0] and f_feats[0] < f_feats[1]
+            if name == "tie_same_lane":
+                assert S["pos_of"][f_feats[1]] > S["pos_of"][f_feats[0]] and (S["pos_of"][f_feats[1]] - S["pos_of"][f_feats[0]]) % 16 == 0
             best, second, f, ok = trace_of(S, k, NNRATIO_TIES)[2][kf_feats[0]]
             assert best == second and ok and f == f_feats[0]
         elif name == "contend_runner_up":
@@ -420,10 +433,13 @@ def _assert_conditions(S):
             assert b1 == 0 and ok1 and f1 == f_feats[0] and not ok2 and b2 > TH_LOW
         elif name in ("null", "bad_point", "absent_node"):
             assert kf_feats[0] not in tr
-    assert seen >= {f"th{TH_LOW}", f"th{TH_LOW + 1}", "ratio30_40", "ratio29_39", "tie", "contend_runner_up", "contend_nothing", "null", "bad_point", "absent_node"}
+    assert seen >= {f"th{TH_LOW}", f"th{TH_LOW + 1}", "ratio30_40", "ratio29_39", "tie", "tie_same_lane", "contend_runner_up", "contend_nothing", "null", "bad_point", "absent_node"}
     hist = traces[ROTATION][3]
     assert sorted(hist[hist > 0].tolist(), reverse=True) == [c for _, c in ROT_BINS] and all(hist[b] == c for b, c in ROT_BINS)
     assert ROT_BINS[-1][1] >= 0.1 * ROT_BINS[0][1], "the fourth bin is dropped for being the fourth, not for being small"
+    hist = traces[ORDER][3]
+    assert all(hist[b] == c for b, c in CUT_BINS) and hist.sum() == sum(c for _, c in CUT_BINS)
+    assert not np.float32(CUT_BINS[1][1]) < np.float32(0.1) * np.float32(CUT_BINS[0][1]) and S["counts"][ORDER] == hist.sum() - CUT_BINS[-1][1]
     rows0 = set(S["kfs"][EDGES]["mp"][S["kfs"][EDGES]["mp"] >= 0].tolist()) & set(S["kfs"][SHARED]["mp"].tolist())
     assert len(rows0) >= 10, "candidates 0 and 4 share points"
     if S["setting"] == "root":

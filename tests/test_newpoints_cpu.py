@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from newpoints_scene import GATES, K_TUM3, SCENES, SF, TH_FAR, NewPointsScene, build_oracle, median_depth, params, run_oracle
+from newpoints_scene import GATES, K_TUM3, SCENES, SF, TH_FAR, NewPointsScene, build_oracle, cut_kept_scene, median_depth, params, run_oracle
 
 SEPARATION = 1e-3
 NULLVEC_MEASURED = 5.9e-8
@@ -199,6 +199,18 @@ def test_histogram_removes_pairs(runs):
         else:
             assert r["hist_removed"].sum() == 0
     assert hit >= 2
+
+
+def test_histogram_on_its_first_cut(oracle):
+    """10 / 1 / 1 / 1 pairs in bins 2 / 5 / 8 / 10: the oracle keeps the second and third bin (1 < 0.1f * 10 is false) and drops the fourth."""
+    s, pairs, bins = cut_kept_scene(oracle)
+    off = run_oracle(oracle, s.cur, s.neigh, params(0, 0, 0, TH_FAR))
+    on = run_oracle(oracle, s.cur, s.neigh, params(0, 1, 0, TH_FAR))
+    want = np.full(s.cur.frame.n, -1, np.int32)
+    want[pairs[:, 0]] = pairs[:, 1]
+    assert not on["skipped"][0] and np.array_equal(off["matches"][0], want), "the 13 constructed pairs are what the search finds"
+    want[pairs[bins == 10, 0]] = -1
+    assert np.array_equal(on["matches"][0], want) and on["hist_removed"][0] == 1 and (on["matches"][0] >= 0).sum() == 12
 
 
 def test_empty_neighbour_and_no_neighbours(oracle):

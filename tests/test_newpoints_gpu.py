@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from newpoints_scene import SCENES, SF, TH_FAR, NewPointsScene, build_oracle, params, run_oracle
+from newpoints_scene import SCENES, SF, TH_FAR, NewPointsScene, build_oracle, cut_kept_scene, params, run_oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -82,6 +82,19 @@ def test_nodes_of_more_than_64_features(oracle):
         m = matcher(ori)
         assert_same(gpu_call(m, s, s.neigh, coarse, 0), want)
         m.close()
+
+
+def test_histogram_on_its_first_cut(oracle):
+    """newpoints_scene.cut_kept_scene: 10 / 1 / 1 / 1 pairs in four rotation bins.  The pairs of the second and third bin stay, the fourth goes."""
+    from rumi_slam_amd.mapping import last_matches
+    s, pairs, bins = cut_kept_scene(oracle)
+    want = run_oracle(oracle, s.cur, s.neigh, params(0, 1, 0, TH_FAR))
+    m = matcher(1)
+    assert_same(gpu_call(m, s, s.neigh, 0, 0), want)
+    got = last_matches(m, 1, s.cur.frame.n)
+    assert np.array_equal(got, want["matches"])
+    assert np.array_equal(got[0][pairs[:, 0]], np.where(bins == 10, -1, pairs[:, 1]))
+    m.close()
 
 
 def test_more_than_2048_features(oracle):

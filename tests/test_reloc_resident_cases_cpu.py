@@ -44,8 +44,13 @@ def test_oracle_ties_and_rotation(setting):
     n, row = _oracle(scene, S.ORDER, S.NNRATIO_TIES)
     ties = scene["expect_ties"][S.ORDER]
     assert len(ties) == 2 and sorted(ties.values())[0] == -1 and sorted(ties.values())[1] >= 0
-    for f, p in ties.items():
+    lane = scene["expect_ties_lane"][S.ORDER]
+    assert len(lane) == 2 and sorted(lane.values())[0] == -1 and sorted(lane.values())[1] >= 0
+    for f, p in list(ties.items()) + list(lane.items()):
         assert row[f] == p, (f, p, row[f])
+    n_on, row_on = _oracle(scene, S.ORDER)
+    n_off, row_off = _oracle(scene, S.ORDER, check_ori=False)
+    assert n_off == sum(c for _, c in S.CUT_BINS) and n_on == n_off - S.CUT_BINS[-1][1], "the second and third bin stand ON the 0.1f cut and stay"
     n_off, row_off = _oracle(scene, S.ROTATION, check_ori=False)
     n_on, row_on = _oracle(scene, S.ROTATION)
     assert n_off == sum(c for _, c in S.ROT_BINS) and n_on == n_off - S.ROT_BINS[-1][1]
