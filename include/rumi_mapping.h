@@ -238,6 +238,41 @@ int rumi_search_by_projection_sim3_stage_ms(const RumiMatcher *m, float *out3);
  * that made no device call, whose stage times are 0 too).  n_jobs must be that call's. */
 int rumi_search_by_projection_sim3_rounds(const RumiMatcher *m, int32_t *rounds, int32_t n_jobs);
 
+/* ---- The BoW stage of LoopClosing::DetectCommonRegionsFromBoW (R/lib_src/LoopClosing.cc:576-651; CloudMerging.cc:1019-1094) by slot: what
+ * rumi_common_regions_bow (include/rumi_match.h) answers from host pointers, answered from a covisibility store.  cur_slot is the current
+ * key-frame; group g (one per BoW candidate) is member_slot[group_start[g] .. group_start[g + 1]), slots in vpCovKFi order.  A slot may appear
+ * in several groups (and be the current key-frame's) and is read where it lies: key-points, descriptors and mFeatVec in its feature block,
+ * its map points in its row, isBad() in the point records.  Both gates of ORBmatcher.cc:717-721 / :736-742 are read there -- row entry >= 0
+ * and the point's bad bit clear, on the current side and on the member side -- so there is no cur_good and no mp_bad argument.
+ *
+ * Outputs, with n = the current slot's feature count, M = group_start[n_groups], G = n_groups: matches12 [M][n] (member feature index, -1),
+ * nmatches [M], matched_point [G][n] (STORE point ids, -1), matched_member [G][n] (position j inside the group, -1), num_bow_matches [G],
+ * most_matches [G][2] = (j, count), strictly greater so the first j wins a tie, (0, 0) when nothing matched.  Every array equals, byte for
+ * byte, what rumi_common_regions_bow returns for the same key-frames, rows and bad bits by host pointers with the store's point ids as the
+ * shared numbering.  matches12 may be NULL: the rows then stay on the device and are not copied back; the other five arrays do not change.
+ * A member slot whose key-frame bad bit is set is named but not searched (as rumi_track_reloc_bow): its row is -1, its count -1, it takes no
+ * part in the union or in most_matches, and the members behind it keep their j (the current slot's own bad bit is not read: the loop does
+ * not ask it either).  A member FeatureVector node of any size is searched on the
+ * device (the `taken` flags lie in LDS, sized by the largest member of the call): there is no host fallback.
+ * Host to device per call: the store's staged edits and staged features, 24 bytes a member, 4 bytes a group.  Device to host: one blocking
+ * copy of the counts and rows.  A query: the store is not changed.  Integer atomics only: two calls on the same state return the same bytes.
+ * Memory the handle keeps for the union: a stamped table of 8 bytes x max_points x (the largest n_groups of any call so far), never cleared
+ * between calls (a per-call epoch in the high word makes older stamps lose); clears per call are 4 bytes x (M x n + G x n + 33 M) and do not grow
+ * with max_points.
+ * RUMI_E_INVALID, before any device work, nothing written: a NULL handle, store or array (matches12 excepted); n_groups < 0; group_start not
+ * ascending from 0; more than 65535 members; a slot outside the store or not live; the current slot or a member that is not bad without
+ * features, or whose feature count differs from the length of its row; (largest group) x n above 2^31 - 1 (the union's key j * n + k);
+ * matcher and store on different devices.  RUMI_E_CAPACITY, likewise before any device work: a member above 65535 features; a union table above 2 GiB.
+ * An empty group, n_groups == 0 and n == 0 are valid: rows -1, counts 0 (-1 for a bad member), most_matches (0, 0); with n == 0 or M == 0
+ * there is no device call. */
+int rumi_common_regions_bow_resident(RumiMatcher *m, RumiCovis *c, int32_t cur_slot, int32_t n_groups, const int32_t *group_start /* [n_groups + 1] */,
+                                     const int32_t *member_slot /* [M] */, float nnratio, int32_t check_orientation,
+                                     int32_t *matches12 /* [M][n], may be NULL */, int32_t *nmatches /* [M] */, int32_t *matched_point /* [G][n] */,
+                                     int32_t *matched_member /* [G][n] */, int32_t *num_bow_matches /* [G] */, int32_t *most_matches /* [G][2] */);
+/* The last call on this matcher, in ms: validation + table | store flush, upload, kernels, download | write-out (all 0 after a call
+ * that made no device call). */
+int rumi_common_regions_bow_resident_stage_ms(const RumiMatcher *m, float *out3);
+
 /* ---- MapPoint::ComputeDistinctiveDescriptors (R/lib_src/MapPoint.cc:353-427) and MapPoint::UpdateNormalAndDepth (:450-518) for a batch of
  * points.  Neither member reads another MapPoint: a point's result depends on its own observation list, its position and reference
  * key-frame, and the observing key-frames' descriptors, camera centres, bad flags and scale tables.  So the per-point calls a map-changing

@@ -78,6 +78,11 @@ int rumi_hook_newpts_matches(struct RumiMatcher *m, int32_t n_neigh, int32_t n1,
 struct RumiCovis;
 int rumi_hook_covis_read_attributes(struct RumiCovis *c, int32_t n, const int32_t *ids, uint8_t *out, int32_t from_device);
 
+/* What the host mirror of a covisibility store holds for a live slot, staged edits included: its map-point row (row_length entries, cap at least
+ * that), per entry the bad bit of its point (0 for a NULL entry) and the key-frame's bad bit.  Uploads nothing.  For the tests that fill a store
+ * from a scene (rumi_common_regions_bow_resident). */
+int rumi_hook_covis_read_row(struct RumiCovis *c, int32_t slot, int32_t cap, int32_t *row, uint8_t *point_bad, int32_t *kf_bad);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,7 +124,7 @@ KFDB_SYMBOLS = ["rumi_kfdb_create", "rumi_kfdb_destroy", "rumi_kfdb_clear", "rum
                 "rumi_kfdb_add_batch_device", "rumi_kfdb_bow", "rumi_kfdb_erase", "rumi_kfdb_clear_map", "rumi_kfdb_set_map_bad", "rumi_kfdb_set_maps",
                 "rumi_kfdb_set_bad", "rumi_kfdb_set_covisibles", "rumi_kfdb_score", "rumi_kfdb_scored", "rumi_kfdb_select_reloc", "rumi_kfdb_select_nbest"]
 MAPPING_SYMBOLS = ["rumi_create_new_map_points", "rumi_create_new_map_points_resident", "rumi_newpts_stage_ms", "rumi_search_in_neighbors_resident", "rumi_search_in_neighbors_stage_ms", "rumi_search_and_fuse_resident", "rumi_search_and_fuse_stage_ms",
-                   "rumi_search_by_projection_sim3_resident", "rumi_search_by_projection_sim3_stage_ms", "rumi_search_by_projection_sim3_rounds", "rumi_refresh_create", "rumi_refresh_destroy", "rumi_refresh_map_points", "rumi_refresh_stage_ms", "rumi_refresh_map_points_resident", "rumi_refresh_last_launches",
+                   "rumi_search_by_projection_sim3_resident", "rumi_search_by_projection_sim3_stage_ms", "rumi_search_by_projection_sim3_rounds", "rumi_common_regions_bow_resident", "rumi_common_regions_bow_resident_stage_ms", "rumi_refresh_create", "rumi_refresh_destroy", "rumi_refresh_map_points", "rumi_refresh_stage_ms", "rumi_refresh_map_points_resident", "rumi_refresh_last_launches",
                    "rumi_cull_create", "rumi_cull_destroy", "rumi_keyframe_culling", "rumi_keyframe_culling_resident", "rumi_cull_stage_ms"]
 COVIS_SYMBOLS = ["rumi_covis_create", "rumi_covis_destroy", "rumi_covis_set_keyframes", "rumi_covis_set_points", "rumi_covis_set_point_observations",
                  "rumi_covis_set_point_attributes", "rumi_covis_set_keyframe_centres", "rumi_covis_set_point_reference",
@@ -220,7 +220,7 @@ def covis_lib():
 
 HOOK_SYMBOLS = ["rumi_hook_sort_like_std", "rumi_hook_sort_device", "rumi_hook_std_sort", "rumi_hook_quadtree", "rumi_hook_sinf", "rumi_hook_cosf",
                 "rumi_hook_fast_atan2", "rumi_hook_cv_round", "rumi_hook_magic_div", "rumi_hook_newpts_matches", "rumi_hook_lane_packing", "rumi_hook_disc_moments",
-                "rumi_hook_stream_plan", "rumi_hook_parse_hw_queues", "rumi_hook_octree_bins", "rumi_hook_compact_hist_lds", "rumi_hook_covis_read_attributes"]
+                "rumi_hook_stream_plan", "rumi_hook_parse_hw_queues", "rumi_hook_octree_bins", "rumi_hook_compact_hist_lds", "rumi_hook_covis_read_attributes", "rumi_hook_covis_read_row"]
 
 
 def hooks():
@@ -247,5 +247,6 @@ def hooks():
     L.rumi_hook_octree_bins.argtypes = [i32, i32, i32, C.c_float, i32, i32, vp, vp, i32, C.POINTER(i32)]
     L.rumi_hook_compact_hist_lds.argtypes = [i32, i32, i32, C.c_float, i32, vp]
     L.rumi_hook_covis_read_attributes.argtypes = [vp, i32, vp, vp, i32]
+    L.rumi_hook_covis_read_row.argtypes = [vp, i32, i32, vp, vp, vp]
     L._hooks_ready = True
     return L

@@ -107,6 +107,13 @@ class Covisibility:
             return out
         return rc, out
 
+    def read_row(self, slot):
+        """Test hook: what the host mirror holds for a live slot -> (map-point row, bad bit of each entry's point, the key-frame's bad bit)."""
+        n = max(self.row_length(slot), 0)
+        row, bad, kf = np.zeros(max(n, 1), _i32), np.zeros(max(n, 1), _u8), np.zeros(1, _i32)
+        capi.check(capi.hooks().rumi_hook_covis_read_row(self._h, int(slot), n, _p(row), _p(bad), _p(kf)))
+        return row[:n], bad[:n], int(kf[0])
+
     def set_bad(self, kf_slots=(), kf_bad=(), pt_ids=(), pt_bad=(), check=True):
         ks = np.ascontiguousarray(kf_slots, _i32); kb = np.ascontiguousarray(kf_bad, _u8)
         ps = np.ascontiguousarray(pt_ids, _i32); pb = np.ascontiguousarray(pt_bad, _u8)

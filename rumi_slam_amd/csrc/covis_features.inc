@@ -277,6 +277,8 @@ int rumi::covis_features_check(RumiCovis *h, int n, const int32_t *slots, int wa
     return RUMI_OK;
 }
 
+int rumi::covis_max_points(const RumiCovis *h) { return h->maxPts; }
+
 int rumi::covis_features_flush(RumiCovis *h, CovisFeatureView *view) {
     int rc;
     uint8_t *unused = nullptr;

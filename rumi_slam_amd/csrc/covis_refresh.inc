@@ -137,3 +137,17 @@ extern "C" int rumi_hook_covis_read_attributes(RumiCovis *h, int32_t n, const in
     }
     return RUMI_OK;
 }
+
+extern "C" int rumi_hook_covis_read_row(RumiCovis *h, int32_t slot, int32_t cap, int32_t *row, uint8_t *point_bad, int32_t *kf_bad) {
+    if (!h || cap < 0 || !row || !point_bad || !kf_bad) { g_lastError = "rumi_hook_covis_read_row: missing argument or negative cap"; return RUMI_E_INVALID; }
+    if (!is_live(h, slot)) { g_lastError = "rumi_hook_covis_read_row: a slot that is not live"; return RUMI_E_INVALID; }
+    const int32_t *K = h->kf.data() + (size_t)slot * KFW;
+    if (K[K_MPLEN] > cap) { g_lastError = "rumi_hook_covis_read_row: the row is longer than cap"; return RUMI_E_CAPACITY; }
+    for (int i = 0; i < K[K_MPLEN]; i++) {
+        const int32_t p = h->arena[(size_t)K[K_MPOFF] + i];
+        row[i] = p;
+        point_bad[i] = p >= 0 ? (uint8_t)(h->pt[(size_t)p * PTW + 2] & 1) : 0;
+    }
+    *kf_bad = K[K_FLAGS] & 1;
+    return RUMI_OK;
+}

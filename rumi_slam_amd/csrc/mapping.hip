@@ -451,6 +451,8 @@ struct SafState;                                             // the blocks of ru
 static void saf_destroy(SafState *s);
 struct S3pState;                                             // the blocks of rumi_search_by_projection_sim3_resident (sim3_projection_batch.inc)
 static void s3p_destroy(S3pState *s);
+struct CrrState;                                             // the blocks of rumi_common_regions_bow_resident (common_regions_resident.inc)
+static void crr_destroy(CrrState *s);
 
 struct NewPtsState {
     MirrorBuf<uint8_t> blk, res;                             // the upload block; the result block, a NewPtsResult and its points
@@ -462,6 +464,7 @@ struct NewPtsState {
     SinState *sin = nullptr;                                 // with the first SearchInNeighbors or SearchAndFuse call (the stamped tables)
     SafState *saf = nullptr;                                 // with the first SearchAndFuse call
     S3pState *s3p = nullptr;                                 // with the first resident Sim3 projection search
+    CrrState *crr = nullptr;                                 // with the first resident common-regions BoW call
 };
 
 static void newpts_destroy(void *p) {                        // rumi_match_destroy has made the matcher's device current
@@ -469,6 +472,7 @@ static void newpts_destroy(void *p) {                        // rumi_match_destr
     if (s->sin) sin_destroy(s->sin);
     if (s->saf) saf_destroy(s->saf);
     if (s->s3p) s3p_destroy(s->s3p);
+    if (s->crr) crr_destroy(s->crr);
     delete s;
 }
 
@@ -709,3 +713,4 @@ extern "C" int rumi_hook_newpts_matches(RumiMatcher *m, int32_t n_neigh, int32_t
 #include "search_in_neighbors.inc"
 #include "search_and_fuse.inc"
 #include "sim3_projection_batch.inc"
+#include "common_regions_resident.inc"

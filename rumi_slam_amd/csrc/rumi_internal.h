@@ -61,6 +61,8 @@ struct CovisFeatureView {
 // Host only: every slot live, with features, named once, feature count == length of its mp row; with wantDevice >= 0 the store on that
 // device (a store without a device yet takes it).  Refused with RUMI_E_INVALID and the message set.
 int covis_features_check(RumiCovis *c, int n, const int32_t *slots, int wantDevice, const char *entry, CovisSlotFeatures *info);
+// Host only: the point ids the store's tables hold (max_points of rumi_covis_create).
+int covis_max_points(const RumiCovis *c);
 // Sends the staged edits and the staged features; where the tables lie afterwards.  Enqueues on the null stream, does not synchronise.
 int covis_features_flush(RumiCovis *c, CovisFeatureView *view);
 

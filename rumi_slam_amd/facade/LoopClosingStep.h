@@ -2,7 +2,8 @@
 // (R/lib_src/CloudMerging.cc:1019-1094): for every BoW candidate, the candidate and its best covisibles are matched against the current key-frame
 // with SearchByBoW(KF, KF) and the match vectors are folded into vpMatchedPoints / vpKeyFrameMatchedMP.  All candidates, all members and the folds
 // go to the GPU in one call (include/rumi_match.h: rumi_common_regions_bow); this side applies the checks that need no device, marshals the
-// key-frames and hands back, per candidate, what the loop body from :655 on reads.  That body (the Sim3 solver, the two SearchByProjection passes,
+// key-frames and hands back, per candidate, what the loop body from :655 on reads (CommonRegionsBoWStageResident: the same over a
+// CovisibilityGraph that holds the map, by slot -- include/rumi_mapping.h: rumi_common_regions_bow_resident -- with nothing to marshal).  That body (the Sim3 solver, the two SearchByProjection passes,
 // OptimizeSim3, the covisible check) stays where it is; its SearchByProjection passes and the covisible check have one-call members below, the
 // Sim3 solvers and OptimizeSim3 of all candidates in PlaceRecognitionStages.h (Sim3RansacStage, OptimizeSim3Stage).
 //
@@ -25,6 +26,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "rumi_mapping.h"
 #include "rumi_match.h"
 #include "rumi_status.h"
 
@@ -53,6 +55,46 @@ template <class FeatVecT> inline void csr(const FeatVecT &fv, Member &m) {      
         m.off.push_back((int32_t)m.idx.size());
     }
 }
+// :576-605 and :623 for every candidate, the part of the stage that needs no device and is the same by host pointers and by slot: the skips, the
+// displaced covisible, the abort by a connected key-frame, bad and NULL members left out.  `out` gets one entry per surviving candidate with its
+// vectors sized; member / groupStart: the key-frames that are searched, group after group; memberPos[g]: their positions in vpCovKFi.
+template <class KeyFrameT, class MapPointT> struct BowGroups {
+    std::vector<int32_t> groupStart = std::vector<int32_t>(1, 0);
+    std::vector<KeyFrameT *> member;
+    std::vector<std::vector<int>> memberPos;
+    bool twoCameras = false;
+};
+template <class KeyFrameT, class MapPointT>
+inline void bow_groups(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpBowCand, const std::set<KeyFrameT *> &spConnectedKeyFrames, int nNumCovisibles,
+                       size_t nSlots, std::vector<BowStageResult<KeyFrameT, MapPointT>> &out, BowGroups<KeyFrameT, MapPointT> &G) {
+    G.twoCameras = pCurrentKF->NLeft != -1;
+    for (KeyFrameT *pKFi : vpBowCand) {
+        if (!pKFi || pKFi->isBad()) continue;
+        BowStageResult<KeyFrameT, MapPointT> r;
+        r.pKFi = pKFi;
+        r.vpCovKFi = pKFi->GetBestCovisibilityKeyFrames(nNumCovisibles);
+        if (r.vpCovKFi.empty()) r.vpCovKFi.push_back(pKFi);
+        else { r.vpCovKFi.push_back(r.vpCovKFi[0]); r.vpCovKFi[0] = pKFi; }
+        bool bAbortByNearKF = false;
+        for (KeyFrameT *pKFj : r.vpCovKFi)
+            if (spConnectedKeyFrames.count(pKFj)) { bAbortByNearKF = true; break; }
+        if (bAbortByNearKF) continue;
+        std::vector<int> pos;
+        for (size_t j = 0; j < r.vpCovKFi.size(); j++) {
+            KeyFrameT *pKFj = r.vpCovKFi[j];
+            if (!pKFj || pKFj->isBad()) continue;
+            G.twoCameras = G.twoCameras || pKFj->NLeft != -1;
+            G.member.push_back(pKFj);
+            pos.push_back((int)j);
+        }
+        G.groupStart.push_back((int32_t)G.member.size());
+        G.memberPos.push_back(pos);
+        r.vvpMatchedMPs.resize(r.vpCovKFi.size());
+        r.vpMatchedPoints.assign(nSlots, static_cast<MapPointT *>(nullptr));
+        r.vpKeyFrameMatchedMP.assign(nSlots, static_cast<KeyFrameT *>(nullptr));
+        out.push_back(r);
+    }
+}
 }  // namespace loopclosing_detail
 
 // Runs :576-651 for every candidate of vpBowCand.  `out` receives one entry per candidate that is neither skipped (NULL or bad, :577) nor aborted
@@ -69,40 +111,19 @@ int CommonRegionsBoWStage(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> 
     static const char *where = "LoopClosingStep::CommonRegionsBoWStage / rumi_common_regions_bow";
     out.clear();
     const std::vector<MapPointT *> vpCurrentMPs = pCurrentKF->GetMapPointMatches();
-    bool twoCameras = pCurrentKF->NLeft != -1;
-
     // ---- the groups: what needs no device ----
+    D::BowGroups<KeyFrameT, MapPointT> groups;
+    D::bow_groups(pCurrentKF, vpBowCand, spConnectedKeyFrames, nNumCovisibles, vpCurrentMPs.size(), out, groups);
+    const bool twoCameras = groups.twoCameras;
+    const std::vector<int32_t> &groupStart = groups.groupStart;
+    const std::vector<std::vector<int>> &memberPos = groups.memberPos;
     std::unordered_map<KeyFrameT *, int> tableIndex;
-    std::vector<KeyFrameT *> table;
-    std::vector<int32_t> groupStart(1, 0), memberKf;
-    std::vector<std::vector<int>> memberPos;                  // per result: the vpCovKFi position of every member that was sent
-    for (KeyFrameT *pKFi : vpBowCand) {
-        if (!pKFi || pKFi->isBad()) continue;
-        BowStageResult<KeyFrameT, MapPointT> r;
-        r.pKFi = pKFi;
-        r.vpCovKFi = pKFi->GetBestCovisibilityKeyFrames(nNumCovisibles);
-        if (r.vpCovKFi.empty()) r.vpCovKFi.push_back(pKFi);
-        else { r.vpCovKFi.push_back(r.vpCovKFi[0]); r.vpCovKFi[0] = pKFi; }
-        bool bAbortByNearKF = false;
-        for (KeyFrameT *pKFj : r.vpCovKFi)
-            if (spConnectedKeyFrames.count(pKFj)) { bAbortByNearKF = true; break; }
-        if (bAbortByNearKF) continue;
-        std::vector<int> pos;
-        for (size_t j = 0; j < r.vpCovKFi.size(); j++) {
-            KeyFrameT *pKFj = r.vpCovKFi[j];
-            if (!pKFj || pKFj->isBad()) continue;
-            twoCameras = twoCameras || pKFj->NLeft != -1;
-            auto it = tableIndex.find(pKFj);
-            if (it == tableIndex.end()) { it = tableIndex.emplace(pKFj, (int)table.size()).first; table.push_back(pKFj); }
-            memberKf.push_back(it->second);
-            pos.push_back((int)j);
-        }
-        groupStart.push_back((int32_t)memberKf.size());
-        memberPos.push_back(pos);
-        r.vvpMatchedMPs.resize(r.vpCovKFi.size());
-        r.vpMatchedPoints.assign(vpCurrentMPs.size(), static_cast<MapPointT *>(nullptr));
-        r.vpKeyFrameMatchedMP.assign(vpCurrentMPs.size(), static_cast<KeyFrameT *>(nullptr));
-        out.push_back(r);
+    std::vector<KeyFrameT *> table;                          // every distinct member once
+    std::vector<int32_t> memberKf;
+    for (KeyFrameT *pKFj : groups.member) {
+        auto it = tableIndex.find(pKFj);
+        if (it == tableIndex.end()) { it = tableIndex.emplace(pKFj, (int)table.size()).first; table.push_back(pKFj); }
+        memberKf.push_back(it->second);
     }
     if (twoCameras) {
         // (the reason travels in the call site's name: the status did not come from the library, so its error string says nothing here)
@@ -186,6 +207,92 @@ int CommonRegionsBoWStage(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> 
                           std::vector<BowStageResult<KeyFrameT, MapPointT>> &out) {
     const std::set<KeyFrameT *> spConnectedKeyFrames = pCurrentKF->GetConnectedKeyFrames();
     return CommonRegionsBoWStage(pCurrentKF, vpBowCand, spConnectedKeyFrames, nNumCovisibles, matcherBoW, out);
+}
+
+// The same stage over a CovisibilityGraph that holds the map (rumi_common_regions_bow_resident, include/rumi_mapping.h): the host
+// logic above, then graph.FlushDirty(), key-frames to slots and ONE call that sends slot numbers and nothing else of a key-frame -- no walk over
+// mFeatVec or GetMapPointMatches() of the members, no renumbering of their points; the device reads features, rows and bad bits in the store,
+// and the matched point ids come back to MapPoint* through the graph's own map.  Every field of BowStageResult is filled as the stage above fills
+// it, for a graph that is current (rows and bad bits staged: graph.Sync); vvpMatchedMPs[j] is filled only with wantMemberMatches (nothing after
+// the union reads it, LoopClosing.cc:608-638, and without it the [members][slots] block stays on the device), else every vvpMatchedMPs[j] is empty.
+// GraphT: CovisibilityGraph, or anything with its ok / SlotOf / HasFeatures / FlushDirty / handle / PointAt.
+// Returns out.size(), or -1 with `out` cleared and a report: NLeft != -1 on a key-frame, no store, the current key-frame or a member the graph
+// has never seen or without SyncFeatures, a current key-frame whose N is not the length of its row in the store, a failed call.  With notResident the third case is not reported: *notResident is set instead, for a
+// caller that then takes the stage above (DetectCommonRegionsFromBoWResident).
+template <class GraphT, class KeyFrameT, class MapPointT, class MatcherT>
+int CommonRegionsBoWStageResident(GraphT &graph, KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpBowCand, const std::set<KeyFrameT *> &spConnectedKeyFrames,
+                                  int nNumCovisibles, const MatcherT &matcherBoW, std::vector<BowStageResult<KeyFrameT, MapPointT>> &out, bool wantMemberMatches,
+                                  bool *notResident = nullptr) {
+    namespace D = loopclosing_detail;
+    static const char *where = "LoopClosingStep::CommonRegionsBoWStageResident / rumi_common_regions_bow_resident";
+    out.clear();
+    if (notResident) *notResident = false;
+    const size_t nSlots = pCurrentKF->GetMapPointMatches().size();
+    D::BowGroups<KeyFrameT, MapPointT> groups;
+    D::bow_groups(pCurrentKF, vpBowCand, spConnectedKeyFrames, nNumCovisibles, nSlots, out, groups);
+    if (groups.twoCameras) {
+        RUMI_GUARDED("LoopClosingStep::CommonRegionsBoWStageResident: a key-frame with NLeft != -1 (only the monocular SearchByBoW is built; no candidate was matched)",
+                     &no_growth, RUMI_E_INVALID);
+        out.clear();
+        return -1;
+    }
+    if (out.empty()) return 0;
+    if (!graph.ok()) { report(where, RUMI_E_INVALID, "no store; no candidate was matched"); out.clear(); return -1; }
+    std::vector<int32_t> memberSlot;
+    bool resident = graph.SlotOf(pCurrentKF) >= 0 && graph.HasFeatures(pCurrentKF);
+    for (KeyFrameT *pKFj : groups.member) {
+        resident = resident && graph.SlotOf(pKFj) >= 0 && graph.HasFeatures(pKFj);
+        memberSlot.push_back(graph.SlotOf(pKFj));
+    }
+    if (!resident) {
+        if (notResident) *notResident = true;
+        else report(where, RUMI_E_INVALID, "a key-frame the graph has never seen or without resident features (graph.Sync, graph.SyncFeatures); nothing was uploaded, no candidate was matched");
+        out.clear();
+        return -1;
+    }
+    // the entry writes rows of the store's feature count for the current slot: the buffers below are sized by N, so the two must agree
+    if (rumi_covis_row_length(graph.handle(), graph.SlotOf(pCurrentKF)) != (int32_t)pCurrentKF->N) {
+        report(where, RUMI_E_INVALID, "the current key-frame's N differs from the row the store holds for it (graph.Sync after the key-frame changed); no candidate was matched");
+        out.clear();
+        return -1;
+    }
+    if (graph.FlushDirty() != RUMI_OK) { out.clear(); return -1; }
+    const size_t n = (size_t)pCurrentKF->N, G = out.size(), M = memberSlot.size();
+    memberSlot.push_back(-1);                                // (never an empty array)
+    std::vector<int32_t> matches12(wantMemberMatches ? M * n + 1 : 0), nmatches(M + 1), matchedPoint(G * n + 1), matchedMember(G * n + 1), numBow(G + 1), most(2 * G + 2);
+    if (!MatcherT::arena()) { out.clear(); return -1; }      // reported by arena()
+    if (RUMI_GUARDED(where, &MatcherT::grow_arena,
+                     rumi_common_regions_bow_resident(MatcherT::arena(), graph.handle(), graph.SlotOf(pCurrentKF), (int32_t)G, groups.groupStart.data(), memberSlot.data(),
+                                                      matcherBoW.NNRatio(), matcherBoW.CheckOrientation(), wantMemberMatches ? matches12.data() : nullptr,
+                                                      nmatches.data(), matchedPoint.data(), matchedMember.data(), numBow.data(), most.data())) != RUMI_OK) {
+        out.clear();
+        return -1;
+    }
+    // ---- back to pointers; a member's position inside its group becomes its position in vpCovKFi ----
+    for (size_t g = 0; g < G; g++) {
+        BowStageResult<KeyFrameT, MapPointT> &r = out[g];
+        const std::vector<int> &pos = groups.memberPos[g];
+        for (size_t jj = 0; wantMemberMatches && jj < pos.size(); jj++) {
+            const size_t mem = (size_t)groups.groupStart[g] + jj;
+            const std::vector<MapPointT *> s2 = groups.member[mem]->GetMapPointMatches();
+            std::vector<MapPointT *> &v = r.vvpMatchedMPs[pos[jj]];
+            v.assign(nSlots, static_cast<MapPointT *>(nullptr));
+            for (size_t k = 0; k < n && k < v.size(); k++) {
+                const int f = matches12[mem * n + k];
+                if (f >= 0 && (size_t)f < s2.size()) v[k] = s2[f];
+            }
+        }
+        for (size_t k = 0; k < n && k < r.vpMatchedPoints.size(); k++) {
+            const int id = matchedPoint[g * n + k], jj = matchedMember[g * n + k];
+            if (id < 0) continue;
+            r.vpMatchedPoints[k] = graph.PointAt(id);
+            r.vpKeyFrameMatchedMP[k] = r.vpCovKFi[pos[jj]];
+        }
+        r.numBoWMatches = numBow[g];
+        r.nMostBoWNumMatches = most[2 * g + 1];
+        r.nIndexMostBoWMatchesKF = pos.empty() ? 0 : pos[most[2 * g]];
+    }
+    return (int)out.size();
 }
 
 }  // namespace rumi_facade
@@ -410,7 +517,7 @@ public:
     }
 
     // ---- LoopClosing::DetectCommonRegionsFromBoW (LoopClosing.cc:542-853; CloudMerging.cc:1019 ff. is the same text) stage by stage over the members
-    // above and PlaceRecognitionStages.h: (1) CommonRegionsBoWStage, (2) Sim3RansacStage, (3) :716 of every candidate whose solver converged,
+    // above and PlaceRecognitionStages.h: (1) CommonRegionsBoWStageResident (CommonRegionsBoWStage by host pointers when a key-frame it searches is not resident), (2) Sim3RansacStage, (3) :716 of every candidate whose solver converged,
     // (4) OptimizeSim3Stage for numProjMatches >= nProjMatches, (5) :738 for numOptMatches >= nSim3Inliers, (6) the covisible check of every
     // candidate with numProjOptMatches >= nProjOptMatches, (7) the replay of :802-810 in candidate order (strict `<`: the first candidate wins a
     // tie) and :824-841 with SetNotErase().  Six device calls (more only when the RANSAC needs another round) whatever the number of candidates;
@@ -428,7 +535,10 @@ public:
         if (bInertialWithoutBA2) { rumi_facade::report(where, RUMI_E_INVALID, "IMU_MONOCULAR before the second inertial BA is not built; nothing was searched"); return -1; }
         if (pCurrentKF->NLeft != -1) { rumi_facade::report(where, RUMI_E_INVALID, "a key-frame with NLeft != -1: only the monocular path is built; nothing was searched"); return -1; }
         std::vector<rumi_facade::BowStageResult<KeyFrameT, MapPointT>> bow;                            // (1) :576-651
-        if (rumi_facade::CommonRegionsBoWStage(pCurrentKF, vpBowCand, spConnectedKeyFrames, th.nNumCovisibles, matcherBoW, bow) < 0) return -1;
+        bool notResident = false;                                                                      // by slot when the graph holds the features of every key-frame searched
+        int nBow = rumi_facade::CommonRegionsBoWStageResident(graph, pCurrentKF, vpBowCand, spConnectedKeyFrames, th.nNumCovisibles, matcherBoW, bow, false, &notResident);
+        if (nBow < 0 && notResident) nBow = rumi_facade::CommonRegionsBoWStage(pCurrentKF, vpBowCand, spConnectedKeyFrames, th.nNumCovisibles, matcherBoW, bow);
+        if (nBow < 0) return -1;
         std::vector<rumi_facade::Sim3RansacOutcome> ransac;                                            // (2) :655-676
         if (rumi_facade::Sim3RansacStage(pCurrentKF, bow, mbFixScale, th.nBoWMatches, th.nBoWInliers, ransac) < 0) return -1;
         struct Cand {

@@ -43,6 +43,8 @@ def _lib():
     L.rumi_search_by_projection_sim3_resident.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, i32, vp]
     L.rumi_search_by_projection_sim3_stage_ms.argtypes = [vp, vp]
     L.rumi_search_by_projection_sim3_rounds.argtypes = [vp, vp, i32]
+    L.rumi_common_regions_bow_resident.argtypes = [vp, vp, i32, i32, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp]
+    L.rumi_common_regions_bow_resident_stage_ms.argtypes = [vp, vp]
     L.rumi_hook_newpts_matches.argtypes = [vp, i32, i32, vp]
     L.rumi_refresh_create.argtypes = [i32, C.POINTER(vp)]
     L.rumi_refresh_destroy.argtypes = [vp]
@@ -315,6 +317,54 @@ def search_by_projection_sim3_rounds(matcher, n_jobs):
     out = np.zeros(max(int(n_jobs), 1), np.int32)
     capi.check(_lib().rumi_search_by_projection_sim3_rounds(matcher._h, capi.ptr(out), int(n_jobs)))
     return out[:int(n_jobs)]
+
+
+# ---- the BoW stage of DetectCommonRegionsFromBoW by slot ----
+def CommonRegionsBoWResident_status(matcher, store, cur_slot, groups, nnratio=None, check_ori=None, want_matches12=True, fill=-1, n=None, null_out=None):
+    """``rumi_common_regions_bow_resident`` with its status code instead of an exception.  matcher / store may be None (a NULL handle);
+    ``groups``: one list of slots per candidate, None (a NULL group_start), or a tuple (group_start, member_slot) that goes in as given, for a
+    caller that wants them malformed.  The outputs start out filled with ``fill``; ``n``: the row width when the current slot cannot tell;
+    ``null_out``: which of the six outputs goes in as NULL (1 .. 5; 0 is want_matches12=False).
+    Returns (rc, matches12 or None, nmatches, matched_point, matched_member, num_bow_matches, most_matches)."""
+    L = _lib()
+    if n is None:
+        n = max(store.row_length(int(cur_slot)), 0) if store is not None else 0
+    start = member = None
+    if groups is not None:
+        if isinstance(groups, tuple):
+            start = np.ascontiguousarray(groups[0], np.int32)
+            member = None if groups[1] is None else np.ascontiguousarray(groups[1], np.int32)
+        else:
+            start = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int32)
+            member = np.array([k for g in groups for k in g], np.int32)
+    G = 0 if start is None else len(start) - 1
+    M = 0 if member is None else len(member)
+    out = [np.full((M, n), fill, np.int32) if want_matches12 else None, np.full(M, fill, np.int32), np.full((G, n), fill, np.int32),
+           np.full((G, n), fill, np.int32), np.full(G, fill, np.int32), np.full((G, 2), fill, np.int32)]
+    p = lambda a: None if a is None else capi.ptr(a)
+    ratio = nnratio if nnratio is not None else (matcher.mfNNratio if matcher is not None else 0.9)
+    ori = check_ori if check_ori is not None else (matcher.mbCheckOrientation if matcher is not None else True)
+    rc = L.rumi_common_regions_bow_resident(matcher._h if matcher is not None else None, store._h if store is not None else None, int(cur_slot), G, p(start),
+                                            p(member), float(ratio), int(ori),
+                                            *[None if i == null_out else p(a) for i, a in enumerate(out)])
+    return (rc, *out)
+
+
+def CommonRegionsBoWResident(matcher, store, cur_slot, groups, nnratio=None, check_ori=None, want_matches12=False):
+    """The BoW stage of LoopClosing::DetectCommonRegionsFromBoW (LoopClosing.cc:576-651) for every candidate in one call, over key-frames
+    resident in ``store`` (a covis.Covisibility): the current key-frame's slot and one list of member slots per candidate, in vpCovKFi order.
+    nnratio / check_ori default to the handle's.  Returns (matches12 [M, n] or None when not asked for, nmatches [M], matched_point [G, n] as
+    store point ids, matched_member [G, n], num_bow_matches [G], most_matches [G, 2])."""
+    r = CommonRegionsBoWResident_status(matcher, store, cur_slot, groups, nnratio, check_ori, want_matches12)
+    capi.check(r[0])
+    return r[1:]
+
+
+def common_regions_bow_resident_stage_ms(matcher):
+    """(validation + table, store flush + upload + kernels + download, write-out) of the matcher's last CommonRegionsBoWResident call, ms."""
+    out = np.zeros(3, np.float32)
+    capi.check(_lib().rumi_common_regions_bow_resident_stage_ms(matcher._h, capi.ptr(out)))
+    return out
 
 
 # ---- map-point refresh ----

@@ -14,6 +14,12 @@ key-frames, about 40 distinct member key-frames (covisibles shared between candi
            copy back; taken in calls of their own, not in the timed rounds
   --trace  only runs both paths a few times (for a separate rocprofv3 --kernel-trace --stats pass; nothing is timed or written)
 
+  --resident  rumi_common_regions_bow_resident against rumi_common_regions_bow in the same process: the workload above
+           and 1 group x 1 member, both put into a covisibility store; the two entries alternate call by call (arguments marshalled once,
+           outside the clock), medians of --repeats calls in each of --rounds rounds, the six arrays compared before a time counts.  Rows: the
+           by-slot entry with matches12 = NULL (as the facade calls it), with matches12 copied back, and with 50 point edits staged before
+           each call (set_bad outside the clock, their flush inside).  The gate of the section is evaluated and written into the record.
+
 Both paths must return the same six arrays before anything is timed.  Needs a GPU: there is no fallback."""
 import argparse
 import ctypes as C
@@ -106,14 +112,140 @@ def host_union(n, groups, kfs, m12, nm):
     return point, member, num, most
 
 
+def resident(a):
+    """The --resident mode: one record per workload."""
+    import torch
+    from rumi_slam_amd import capi, mapping as MP
+    from rumi_slam_amd.covis import Covisibility
+    M, cur, cur_good, kfs, mp_bad, groups_full = workload()
+    h = M.ORBmatcher(0.9, True)
+    L, LM = h._lib, MP._lib()
+    n, nmp = cur[0].n, len(mp_bad)
+    # the store: the current key-frame in slot 0, table entry k in slot k + 1; a good current feature holds a fresh point, the others none
+    cov = Covisibility(len(kfs) + 1, nmp + n)
+    cur_row = np.where(cur_good != 0, nmp + np.arange(n), -1).astype(np.int32)
+    slots = list(range(len(kfs) + 1))
+    cov.set_keyframes(slots, [100 + s for s in slots], [0] * len(slots), [0] * len(slots), [cur_row] + [k[2] for k in kfs], [[]] * len(slots), [-1] * len(slots),
+                      [[]] * len(slots))
+    cov.set_points(np.arange(nmp + n, dtype=np.int32), np.concatenate([mp_bad, np.zeros(n, np.uint8)]), [[]] * (nmp + n))
+    for s_, (F, fv) in zip(slots, [cur] + [(k[0], k[1]) for k in kfs]):
+        cov.set_keyframe_features(s_, F, fv, [500.0, 500.0, 320.0, 240.0])
+    dev = torch.cuda.get_device_name(0)
+    edit_ids = np.arange(50, dtype=np.int32) * 7
+    edit_bad = mp_bad[edit_ids].copy()                                   # the values they have: staged edits that change no result
+    for name, groups in (("6x11", groups_full), ("1x1", [[0]])):
+        G, members = len(groups), [k for g in groups for k in g]
+        start = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int32)
+        used = sorted(set(members))                                      # the host-pointer entry gets the key-frames of this workload only
+        table = (M.RumiBowKeyFrame * len(used))()
+        for t, k in zip(table, used):
+            t.feat, t.fv, t.mp = kfs[k][0].c, kfs[k][1].c, kfs[k][2].ctypes.data
+        member = np.array([used.index(k) for k in members], np.int32)
+        member_slot = np.array(members, np.int32) + 1
+        shapes = [(len(members), n), (len(members),), (G, n), (G, n), (G,), (G, 2)]
+        outP, outS = [np.zeros(sh, np.int32) for sh in shapes], [np.zeros(sh, np.int32) for sh in shapes]
+        argsP = (h._h, C.addressof(cur[0].c), C.addressof(cur[1].c), capi.ptr(cur_good), len(used), C.addressof(table), nmp, capi.ptr(mp_bad), G, capi.ptr(start),
+                 capi.ptr(member), 0.9, 1, *[capi.ptr(o) for o in outP])
+        argsS = (h._h, cov._h, 0, G, capi.ptr(start), capi.ptr(member_slot), 0.9, 1, *[capi.ptr(o) for o in outS])
+        argsN = argsS[:8] + (None,) + argsS[9:]
+
+        def timed(fn, args):
+            t0 = time.perf_counter()
+            rc = fn(*args)
+            t = time.perf_counter() - t0
+            assert rc == 0, capi.lib().rumi_last_error()
+            return t * 1e3
+
+        def same():
+            return all(np.array_equal(x, y) for x, y in zip(outP, outS))
+
+        for o in outS:
+            o[...] = -9
+        timed(L.rumi_common_regions_bow, argsP); timed(LM.rumi_common_regions_bow_resident, argsS)
+        assert same(), "the by-slot entry differs from the host-pointer entry"
+        keep = outS[0].copy()
+        timed(LM.rumi_common_regions_bow_resident, argsN)
+        assert same() and np.array_equal(keep, outS[0]), "matches12 = NULL changed another array"
+        for _ in range(5):
+            timed(L.rumi_common_regions_bow, argsP); timed(LM.rumi_common_regions_bow_resident, argsS); timed(LM.rumi_common_regions_bow_resident, argsN)
+        rounds = {"pointer": [], "slot_null": [], "slot_rows": [], "slot_null_50_edits": []}
+        for _ in range(a.rounds):
+            t = {k: [] for k in rounds}
+            for _ in range(a.repeats):
+                t["pointer"].append(timed(L.rumi_common_regions_bow, argsP))
+                t["slot_null"].append(timed(LM.rumi_common_regions_bow_resident, argsN))
+                t["slot_rows"].append(timed(LM.rumi_common_regions_bow_resident, argsS))
+                cov.set_bad(pt_ids=edit_ids, pt_bad=edit_bad)
+                t["slot_null_50_edits"].append(timed(LM.rumi_common_regions_bow_resident, argsN))
+                assert same(), "results changed inside the timed rounds"
+            for k in rounds:
+                rounds[k].append(float(np.median(t[k])))
+        med = {k: float(np.median(v)) for k, v in rounds.items()}
+        spread = {k: max(v) - min(v) for k, v in rounds.items()}           # ms, of the round medians
+        gate = {}
+        for k in ("slot_null", "slot_rows"):
+            if name == "1x1":
+                gate[k] = med[k] <= med["pointer"]
+            else:
+                gate[k] = med["pointer"] - med[k] > max(spread[k], spread["pointer"])
+        rec = {"device": dev, "probe": "common_regions_resident", "workload": name, "groups": G, "members": len(members), "distinct_keyframes": len(used), "features": n,
+               "repeats": a.repeats, "rounds": a.rounds, "num_bow_matches": outS[4].tolist(),
+               "rumi_common_regions_bow_ms": stats(rounds["pointer"]), "resident_matches12_null_ms": stats(rounds["slot_null"]),
+               "resident_matches12_back_ms": stats(rounds["slot_rows"]), "resident_null_after_50_staged_edits_ms": stats(rounds["slot_null_50_edits"]),
+               "spread_of_round_medians_ms": {k: round(v, 4) for k, v in spread.items()},
+               "resident_stage_ms_last_call": [round(float(x), 4) for x in MP.common_regions_bow_resident_stage_ms(h)],
+               "gate": ("not above the host-pointer entry" if name == "1x1" else "below the host-pointer entry by more than the larger spread of the round medians"),
+               "gate_held": gate}
+        recs = [rec]
+        if name == "6x11":
+            recs.append(dict(device=dev, **facade_stages(a, M, cur, cur_good, kfs, mp_bad, groups)))
+        for r_ in recs:
+            line = json.dumps(r_)
+            print(line, flush=True)
+            if a.out:
+                with open(a.out, "a") as f:
+                    f.write(line + "\n")
+
+
+def facade_stages(a, M, cur, cur_good, kfs, mp_bad, groups):
+    """The two facade stages over the same workload (tests/cpp/test_common_regions_resident_facade.cc, mode lc with repeats and rounds): the
+    whole stage by the wall clock, marshalling included.  The binary is built into a temporary directory."""
+    import subprocess
+    import tempfile
+    from common_regions_scene import KF, Scene
+    from test_common_regions_facade_gpu import write_scene
+    from test_common_regions_resident_facade_gpu import build_facade_test
+    as_kf = lambda F, fv, mp=None: KF(F.keys["angle"], F.desc, (fv.node_ids, fv.offsets, fv.indices), mp)
+    scene = Scene("probe", as_kf(*cur), cur_good, [as_kf(*k) for k in kfs], mp_bad, groups, 0.9, True)
+    cov = {k: [] for k in range(len(kfs) + 1)}
+    for g in groups:                                                     # the candidate, then its covisibles: vpCovKFi has the group's members
+        cov[g[0] + 1] = [k + 1 for k in g[1:]]
+    with tempfile.TemporaryDirectory() as tmp:
+        exe, path = os.path.join(tmp, "facade"), os.path.join(tmp, "scene.bin")
+        build_facade_test(exe)
+        write_scene(path, scene, [g[0] + 1 for g in groups], cov, [], set())
+        r = subprocess.run([exe, "lc", path, "-1", str(a.repeats), str(a.rounds)], capture_output=True, text=True, env=dict(os.environ, RUMI_NO_TORCH="1"), timeout=600)
+    assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-2000:]
+    lines = [l.split() for l in r.stdout.splitlines()]
+    assert lines[0] == ["E", "with", "equal"] and lines[1] == ["E", "without", "equal"], lines[:2]
+    t = {l[1]: [float(x) for x in l[2:]] for l in lines if l[0] == "T"}
+    return {"probe": "common_regions_resident_facade", "workload": f"{len(groups)}x{len(groups[0])}", "repeats": a.repeats, "rounds": a.rounds,
+            "CommonRegionsBoWStage_ms": stats(t["pointer"]), "CommonRegionsBoWStageResident_ms": stats(t["slot"]),
+            "spread_of_round_medians_ms": {k: round(max(v) - min(v), 4) for k, v in t.items()},
+            "note": "whole stage by the wall clock: groups, marshalling, the C entry, back to pointers; the by-slot stage without member matches"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
+    ap.add_argument("--resident", action="store_true")
     ap.add_argument("--repeats", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--trace", action="store_true")
     a = ap.parse_args()
     assert a.repeats >= 20
+    if a.resident:
+        return resident(a)
     import torch
     from rumi_slam_amd import capi
     M, cur, cur_good, kfs, mp_bad, groups = workload()
