@@ -282,11 +282,11 @@ typedef struct RumiBowKeyFrame {
  *   matched_member [G][n]   vpKeyFrameMatchedMP as the member's position j inside its group, -1 NULL
  *   num_bow_matches [G]     numBoWMatches
  *   most_matches [G][2]     nIndexMostBoWMatchesKF, nMostBoWNumMatches (strictly greater, :628: the first j wins a tie; 0, 0 without matches)
- * Exact: every result equals the literal loop's.  A member FeatureVector node with more than 512 features does not fit the batch kernel; the entry then
- * runs rumi_search_by_bow_kf member by member and the union on the host for that call, with the same results (the handle's max_features /
- * max_queries then apply).  RUMI_E_INVALID, with nothing written and no device work: a NULL array, group_start not ascending from 0, a member
- * index outside the table, a map-point id >= nmp, a FeatureVector whose offsets descend, whose node ids do not ascend or that names a feature
- * outside its key-frame. */
+ * Exact: every result equals the literal loop's, whatever the size of a member's FeatureVector nodes (above 512 features a node the kernel keeps
+ * its `taken` flags in LDS instead of a register).  RUMI_E_INVALID, with nothing written and no device work: a NULL array, group_start not
+ * ascending from 0, a member index outside the table, a map-point id >= nmp, a FeatureVector whose offsets descend, whose node ids do not ascend or
+ * that names a feature outside its key-frame.  RUMI_E_CAPACITY, likewise: a member node above 65535 features (the search key holds a node position
+ * in 16 bits; rumi_search_by_bow_batch refuses such a node of the frame in the same way). */
 int rumi_common_regions_bow(RumiMatcher *m, const RumiFrameFeatures *Cur, const RumiFeatureVector *cur_fv, const uint8_t *cur_good, int32_t n_kfs,
                             const RumiBowKeyFrame *kfs, int32_t nmp, const uint8_t *mp_bad, int32_t n_groups, const int32_t *group_start,
                             const int32_t *member_kf, float nnratio, int32_t check_orientation, int32_t *matches12, int32_t *nmatches,

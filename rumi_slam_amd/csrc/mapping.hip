@@ -26,7 +26,7 @@
 #include "keyframe_features.h"
 #include "match_host.h"
 #include "match_grid.h"
-#include "match_bow.h"
+#include "match_bow_stage.h"
 
 namespace rumi {
 
@@ -89,7 +89,7 @@ struct ResidentView {
     const ResKF *tab; const uint8_t *feat; const int32_t *rows; const float *pos;
     struct KF {
         const ResKF *p; const CovisFeatRec *r; const int32_t *row; const float *xyz;
-        template <class T> __device__ __forceinline__ const T *arr(uint32_t o) const { return reinterpret_cast<const T *>(reinterpret_cast<const uint8_t *>(r) + o); }
+        template <class T> __device__ __forceinline__ const T *arr(uint32_t o) const { return rec_arr<T>(r, o); }
         __device__ __forceinline__ int n() const { return r->n; }
         __device__ __forceinline__ int nn() const { return r->nn; }
         __device__ __forceinline__ const RumiKeyPoint *keys() const { return arr<RumiKeyPoint>(r->keys); }

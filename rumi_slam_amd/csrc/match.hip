@@ -28,13 +28,16 @@
 //   match_bruteforce.inc  k_bruteforce_mfma with its derivation, launch_bruteforce, rumi_match_bruteforce_*
 //   match_bruteforce_pair.inc  k_bruteforce_pair (one pair, train rows split over workgroups, last-arriver merge), launch_bruteforce_pair,
 //                         rumi_match_bruteforce_pair_*
-//   match_bow_batch.inc   k_bow_batch_match, k_bow_batch_finish (BowKF, BowBatch; callers of bow_node_walk and bow_finish) and rumi_search_by_bow_batch
-//   match_bow_kf_batch.inc  k_crb_match, k_crb_finish, k_crb_union (CrKF, CrArgs) and rumi_common_regions_bow
+//   match_bow_batch.inc   rumi_search_by_bow_batch: k_bowf_match and k_bow_rows_finish over the packed view
+//   match_bow_kf_batch.inc  rumi_common_regions_bow: k_cr_match, k_bow_rows_finish and k_cr_union over the packed view, `first` cleared per call
 //   match_submap.inc      k_grid_batch, k_submap_match, k_submap_compact (SubFrame, SubPair) and rumi_submap_match
 //   match_device.h        what the kernels of match.hip, track.hip and mapping.hip share: Query, hamming256, the wave scans, rot_bin, one body per
 //                         projection gate that has more than one caller (sim3_query, reloc_query, frustum_gate; se3f_camera_centre, pose_matrices19),
 //                         ComputeThreeMaxima (three_maxima_keep by one thread, three_maxima_wave by one wave), bow_finish, block_ordered_slot
 //   match_bow.h           the FeatureVector side of SearchByBoW: fv_find_node, bow_reduce16, bow_node_walk over a TakenMask or TakenLds
+//   match_bow_stage.h     the two BoW batch stages, one body each for the host-pointer and the by-slot entries (track.hip, mapping.hip): the key-frame
+//                         views, k_bowf_match, k_cr_match, k_bow_rows_finish, k_cr_union with its two `first` tables, and the host staging the two
+//                         common-regions entries share
 //   match_grid.h          grid_build_xy, the one-workgroup grid of k_grid_batch (shared with mapping.hip's k_sin_grid); the GetFeaturesInArea window of
 //                         every walk: cell_window, window_gate, reproj_gate, and walk_window (16 lanes an item: mapping.hip's searches)
 #include <hip/hip_runtime.h>
@@ -48,7 +51,7 @@
 
 #include "match_host.h"
 #include "match_grid.h"
-#include "match_bow.h"
+#include "match_bow_stage.h"
 
 namespace rumi {
 

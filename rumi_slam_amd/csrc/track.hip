@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "match_host.h"
-#include "match_bow.h"
+#include "match_bow_stage.h"
 #include "rumi_orb.h"
 #include "rumi_track.h"
 #include "rumi_voc.h"

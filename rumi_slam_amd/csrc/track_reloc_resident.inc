@@ -4,11 +4,9 @@
 // CovisFeatRec block of a slot (key-points, descriptors, mFeatVec as CSR), its map-point row in the row arena, the bad bits and the 64-byte
 // attribute records of the points.  A call sends slot numbers and a few words per candidate, nothing else.
 //
-//   k_rbow_match     SearchByBoW of every (candidate, key-frame node) pair, 16 lanes each: bow_node_walk (match_bow.h) over TakenLds.  A lane's
-//                    `taken` flags lie in LDS words of its own (word w of thread t at sTaken[w * 256 + t]; bit j of the lane's private mask is
-//                    position lane + 16 j of the node), as many words as the frame's feature count asks for: no node size is refused, and no
-//                    lane reads another lane's word, so there is nothing to synchronise.
-//   k_rbow_finish    ComputeThreeMaxima and the count of every candidate (bow_finish, match_device.h); a bad slot's count is -1.
+//   k_bowf_match<SlotView, ResidentFrame, TakenLds>   (match_bow_stage.h) SearchByBoW of every (candidate, key-frame node) pair, 16 lanes each.  A
+//                    lane's `taken` flags lie in LDS words of its own, as many as the frame's feature count asks for: no node size is refused.
+//   k_bow_rows_finish<SlotView>   ComputeThreeMaxima and the count of every candidate; a bad slot's count is -1.
 //   k_rtab_claim     a lane per (candidate, key-frame feature): atomicMax of its claim u = place in (candidate order, feature order) on the
 //                    point's stamp: the lowest u wins (the stamps of track_local_map.inc: table_claim, table_row, table_row_of; the map and the
 //                    epoch counter are the session's own).
@@ -19,66 +17,6 @@
 // Integer atomics only (atomicOr / atomicAdd / atomicMax on integers): no result depends on the order anything arrives in.
 
 namespace rumi {
-
-struct RbowCand { long long block; int32_t mpOff, nkf, nn, bad; };     // one candidate slot: its CovisFeatRec (bytes into the feature arena), its row
-static_assert(sizeof(RbowCand) == 24, "the candidate table as uploaded");
-
-struct RbowArgs {
-    const RbowCand *cands;
-    const uint8_t *feat;                 // the feature arena
-    const int32_t *rows, *pt;            // the row arena, the point records
-    const RumiKeyPoint *fKeys;           // the resident frame
-    const uint32_t *fDesc;
-    const uint32_t *fNodes, *fIdx;       // its FeatureVector (rumi_track_compute_bow)
-    const int32_t *fOff, *fNN;
-    int K, nf, words;                    // words: LDS words of `taken` flags a lane owns
-    int32_t *matches;                    // [K][nf] point ids, -1 none
-    int8_t *rotBin;                      // [K][nf]
-    int32_t *hist;                       // [K][32]
-    int32_t *nmatch;                     // [K]
-    float nnratio;
-    int checkOri;
-};
-
-template <class T> __device__ __forceinline__ const T *rec_arr(const CovisFeatRec *r, uint32_t o) {
-    return reinterpret_cast<const T *>(reinterpret_cast<const uint8_t *>(r) + o);
-}
-
-__global__ __launch_bounds__(256) void k_rbow_match(RbowArgs B) {
-    extern __shared__ uint32_t sTaken[];                      // [words][256]
-    const int k = blockIdx.y, lane = threadIdx.x & 15, a = blockIdx.x * 16 + (threadIdx.x >> 4);
-    const RbowCand C = B.cands[k];
-    if (C.bad || a >= C.nn) return;
-    const CovisFeatRec *R = reinterpret_cast<const CovisFeatRec *>(B.feat + C.block);
-    const int lo = fv_find_node(B.fNodes, B.fNN[0], rec_arr<uint32_t>(R, R->nodes)[a]);
-    if (lo < 0) return;
-    const int c0 = B.fOff[lo], nc = B.fOff[lo + 1] - c0;
-    const int32_t *kOff = rec_arr<int32_t>(R, R->off);
-    const uint32_t *fIdx = B.fIdx + c0, *kIdx = rec_arr<uint32_t>(R, R->idx), *kDesc = rec_arr<uint32_t>(R, R->desc);
-    const RumiKeyPoint *kKeys = rec_arr<RumiKeyPoint>(R, R->keys);
-    const int32_t *kMp = B.rows + C.mpOff;
-    TakenLds taken{sTaken + threadIdx.x};                    // a frame feature that already holds a map point
-    const int myWords = ((nc + 15) / 16 + 31) / 32;          // (<= B.words: a node holds at most nf features)
-    for (int w = 0; w < myWords; w++) taken.w[w * 256] = 0;
-    int mp = -1;                                             // the current query's point: the gate reads it, the match writes it
-    bow_node_walk<false>(lane, kIdx, kOff[a], kOff[a + 1], kDesc, fIdx, nc, B.fDesc, B.nnratio, taken,
-                         [&](int iKF) { mp = kMp[iKF]; return !(mp < 0 || (B.pt[(size_t)mp * kCovisPointWords + 2] & 1)); },   // no map point, or a bad one (:238-243)
-                         [&](int iKF, int f) {
-                             B.matches[(size_t)k * B.nf + f] = mp;
-                             if (B.checkOri) {
-                                 const int bin = rot_bin(kKeys[iKF].angle, B.fKeys[f].angle);
-                                 B.rotBin[(size_t)k * B.nf + f] = (int8_t)bin;
-                                 atomicAdd(&B.hist[k * 32 + bin], 1);
-                             }
-                         });
-}
-
-// rotation-histogram filter (ComputeThreeMaxima, ORBmatcher.cc:1795-1826) and the match count of every candidate; -1 for a bad slot (Tracking.cc:3245)
-__global__ __launch_bounds__(256) void k_rbow_finish(RbowArgs B) {
-    const int k = blockIdx.x;
-    if (B.cands[k].bad) { if (threadIdx.x == 0) B.nmatch[k] = -1; return; }
-    bow_finish(B.matches + (size_t)k * B.nf, B.rotBin + (size_t)k * B.nf, B.hist + k * 32, B.nf, B.checkOri, &B.nmatch[k]);
-}
 
 // ---- the session's point table and block ------------------------------------------------------------------------------------------------
 struct RsessCand { long long block; int32_t mpOff, nkf, keyOff, matchRow; };      // keyOff: features of the candidates before it; matchRow: its row of the BoW matches
@@ -252,34 +190,31 @@ extern "C" int rumi_track_reloc_bow(RumiTracker *t, RumiCovis *c, int32_t K, con
     r->haveWalk = false;
     const size_t Kn = (size_t)K * n;
     const size_t oCnt = Kn * 4, oHist = oCnt + (size_t)K * 4, oBin = oHist + (size_t)K * 128, outBytes = oBin + Kn;
-    if ((rc = r->tab.reserve((size_t)K * sizeof(RbowCand), (size_t)K * sizeof(RbowCand) * 2)) != RUMI_OK || (rc = r->out.reserve(outBytes, outBytes + outBytes / 2)) != RUMI_OK)
+    if ((rc = r->tab.reserve((size_t)K * sizeof(BowSlotKF), (size_t)K * sizeof(BowSlotKF) * 2)) != RUMI_OK || (rc = r->out.reserve(outBytes, outBytes + outBytes / 2)) != RUMI_OK)
         return rc;
-    RbowCand *hc = reinterpret_cast<RbowCand *>(r->tab.h);
+    BowSlotKF *hc = reinterpret_cast<BowSlotKF *>(r->tab.h);
     int maxNodes = 0;
     for (int k = 0, l = 0; k < K; k++) {
-        if (bad[(size_t)k]) { hc[k] = RbowCand{0, 0, 0, 0, 1}; continue; }
+        if (bad[(size_t)k]) { hc[k] = BowSlotKF{0, 0, 0, 0, 1}; continue; }
         const CovisSlotFeatures &I = info[(size_t)l++];
-        hc[k] = RbowCand{(long long)I.block, I.mpOff, I.n, I.nn, 0};
+        hc[k] = BowSlotKF{(long long)I.block, I.mpOff, I.n, I.nn, 0};
         maxNodes = std::max(maxNodes, I.nn);
     }
     CovisFeatureView fv;
     if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(r->tab.d, r->tab.h, (size_t)K * sizeof(RbowCand), hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(r->tab.d, r->tab.h, (size_t)K * sizeof(BowSlotKF), hipMemcpyHostToDevice, nullptr));
     if (Kn) HIP_TRY(hipMemsetAsync(r->out.d, 0xFF, Kn * 4, nullptr));                       // matches = -1
     HIP_TRY(hipMemsetAsync(r->out.d + oCnt, 0, oBin - oCnt, nullptr));                      // counts and histograms
-    RbowArgs B{};
-    B.cands = reinterpret_cast<const RbowCand *>(r->tab.d);
-    B.feat = fv.feat; B.rows = fv.rows; B.pt = fv.pt;
-    B.fKeys = resident_keys(t); B.fDesc = reinterpret_cast<const uint32_t *>(t->d.record + t->oDesc);
-    B.fNodes = r->fvNodes.p; B.fIdx = r->fvIdx.p; B.fOff = r->fvOff.p; B.fNN = r->fvNN.p;
-    B.K = K; B.nf = n; B.words = std::max(1, ((n + 15) / 16 + 31) / 32);
-    B.matches = reinterpret_cast<int32_t *>(r->out.d); B.nmatch = reinterpret_cast<int32_t *>(r->out.d + oCnt);
-    B.hist = reinterpret_cast<int32_t *>(r->out.d + oHist); B.rotBin = reinterpret_cast<int8_t *>(r->out.d + oBin);
-    B.nnratio = nnratio; B.checkOri = check_orientation;
-    const size_t lds = (size_t)B.words * 256 * 4;
-    if (lds > 64 * 1024) HIP_TRY(raise_lds_limit(reinterpret_cast<const void *>(k_rbow_match), lds));
-    if (maxNodes > 0 && n > 0) hipLaunchKernelGGL(k_rbow_match, dim3((maxNodes + 15) / 16, K), dim3(256), lds, nullptr, B);
-    hipLaunchKernelGGL(k_rbow_finish, dim3(K), dim3(256), 0, nullptr, B);
+    SlotView V{reinterpret_cast<const BowSlotKF *>(r->tab.d), fv.feat, fv.rows, fv.pt};
+    ResidentFrame F{resident_keys(t), reinterpret_cast<const uint32_t *>(t->d.record + t->oDesc), r->fvNodes.p, r->fvIdx.p, r->fvOff.p, r->fvNN.p};
+    BowRows R;
+    R.matches = reinterpret_cast<int32_t *>(r->out.d); R.nmatch = reinterpret_cast<int32_t *>(r->out.d + oCnt);
+    R.hist = reinterpret_cast<int32_t *>(r->out.d + oHist); R.rotBin = reinterpret_cast<int8_t *>(r->out.d + oBin);
+    R.n = n; R.nnratio = nnratio; R.checkOri = check_orientation;
+    const size_t lds = taken_lds_bytes(n);                   // (a node holds at most n features)
+    if (lds > 64 * 1024) HIP_TRY(raise_lds_limit(reinterpret_cast<const void *>(k_bowf_match<SlotView, ResidentFrame, TakenLds>), lds));
+    if (maxNodes > 0 && n > 0) hipLaunchKernelGGL((k_bowf_match<SlotView, ResidentFrame, TakenLds>), dim3((maxNodes + 15) / 16, K), dim3(256), lds, nullptr, V, F, R);
+    hipLaunchKernelGGL(k_bow_rows_finish<SlotView>, dim3(K), dim3(256), 0, nullptr, V, R);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(r->out.h, r->out.d, oHist, hipMemcpyDeviceToHost));                    // matches and counts: the call's one synchronisation
     if (Kn) std::memcpy(matches, r->out.h, Kn * 4);

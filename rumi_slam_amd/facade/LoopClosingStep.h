@@ -101,8 +101,8 @@ inline void bow_groups(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vp
 // (one of its members is connected to the current key-frame, :593-605), in vpBowCand's order.  Returns out.size(), or -1 with `out` empty and a
 // report through rumi_status.h: a key-frame with NLeft != -1 (the two-camera branches of SearchByBoW are not built), or a failed device call.
 // matcherBoW: the caller's ORBmatcher(0.9, true) (:555, facade/ORBmatcher.h): its ratio and orientation flag are read through NNRatio() /
-// CheckOrientation(), and the call runs on its per-thread arena (the call's own blocks grow on demand; should a member's FeatureVector node exceed what
-// the batch kernel holds, the library runs single searches on that arena, which grows as for ORBmatcher's own calls).
+// CheckOrientation(), and the call runs on its per-thread arena (the call's own blocks grow on demand; a member's FeatureVector node of any size up to
+// 65535 features is searched in the same launch).
 // spConnectedKeyFrames: mpCurrentKF->GetConnectedKeyFrames() as :551 takes it once for the whole function; the overload without it asks the key-frame.
 template <class KeyFrameT, class MapPointT, class MatcherT>
 int CommonRegionsBoWStage(KeyFrameT *pCurrentKF, const std::vector<KeyFrameT *> &vpBowCand, const std::set<KeyFrameT *> &spConnectedKeyFrames, int nNumCovisibles,

@@ -101,11 +101,13 @@ RES_NODE_SIZES = [0, 1, 15, 16, 17, 512, 513]
 WHOLE_MEMBER = 1100
 
 
-def contended_node_scene(size, name=None):
+def contended_node_scene(size, name=None, lead_nodes=0):
     """One shared node; the member holds ``size`` features in it, list order against feature order.  In every 512-position stretch of the list
     two current features want the member feature at the stretch's LAST position (3 and 4 bits away): the first takes it, the second must find it
     taken and settles for the feature at the stretch's FIRST position (20 bits away) or, in a stretch of one, for nothing.  A lane that lost its
-    `taken` bit past position 511 would hand the same feature out twice.  One member feature in ten holds no point, point 2 is bad."""
+    `taken` bit past position 511 would hand the same feature out twice.  One member feature in ten holds no point, point 2 is bad.
+    lead_nodes (at most 9): empty nodes with lower ids ahead of the shared one in the current key-frame's FeatureVector, so that the node pair falls
+    to sixteen-lane group ``lead_nodes`` of its workgroup of sixteen."""
     s = Build(300 + size)
     rows = [[s.base(), (-1 if p % 10 == 7 else p)] for p in range(size)]
     for s0 in range(0, size, 512):
@@ -118,7 +120,7 @@ def contended_node_scene(size, name=None):
     s.cur(s.base(), 11)                                              # a node the member lacks
     for p in reversed(range(size)):                                  # feature index size - 1 - p sits at list position p
         s.feat(0, rows[p][0], None, rows[p][1])
-    sc = s.scene(name or f"contended_{size}", [[0]], max(size, 1), bad=[2] if size > 2 else [], nnratio=0.9)
+    sc = s.scene(name or f"contended_{size}", [[0]], max(size, 1), bad=[2] if size > 2 else [], nnratio=0.9, extra_nodes={-1: range(lead_nodes)})
     sc.kfs[0].fv = csr({9: [size - 1 - p for p in range(size)], 13: []})
     return sc
 

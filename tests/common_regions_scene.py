@@ -262,7 +262,17 @@ def expect_tuple(e):
             np.array(e["num"], np.int32), np.array(e["most"], np.int32).reshape(-1, 2))
 
 
-NODE_SIZES = [0, 1, 15, 16, 17, 33, 512, 513]
+NODE_SIZES = [0, 1, 15, 16, 17, 33, 512, 513, 1024, 1025, 1100]      # above 512 a lane's `taken` flags lie in LDS words: 1024 is the last size of two, 1025 the first of three
+CONTENDED_NODE = 1100
+
+
+def contended_scene():
+    """The 1100-feature node with two current features contending for one member feature in every 512-position stretch of the node (the helper
+    of the by-slot suite, whose module imports this one: hence the import here).  Nine empty nodes lead the current key-frame's FeatureVector:
+    the node pair is searched by the tenth sixteen-lane group of its workgroup, whose third LDS word lies 2624 bytes into the block -- past what a
+    launch with one word too few would get (2048 bytes, which the hardware rounds up to 2560)."""
+    from common_regions_resident_scene import contended_node_scene
+    return contended_node_scene(CONTENDED_NODE, lead_nodes=9)
 
 
 def node_size_scene(size):

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from common_regions_scene import (NODE_SIZES, SEEDS, Scene, cur_size_scene, empty_member_scene, expect_tuple, expected, from_case, hand_cases, mixed_groups,
+from common_regions_scene import (CONTENDED_NODE, NODE_SIZES, SEEDS, Scene, contended_scene, cur_size_scene, empty_member_scene, expect_tuple, expected, from_case, hand_cases, mixed_groups,
                                   most_matches, node_size_scene, same, describe, seeded_scene, union)
 from match_cases import all_cases
 
@@ -82,6 +82,20 @@ def test_node_size_scenes_match_where_they_should():
             assert m12[0][0] == 0, size                                 # the twin at the LAST list position holds feature index 0
         if size >= 15:
             assert m12[0][1] == size - 1 and m12[0][2] == size - 1 - 5, size          # the tie goes to the earlier list entry; the NULL best is passed over
+
+
+def test_contended_scene_contends():
+    """In every 512-position stretch of the 1100-feature node the first of the two current features takes the stretch's last position and the
+    second the stretch's first."""
+    size, s = CONTENDED_NODE, contended_scene()
+    K = s.kfs[0]
+    a = list(K.fv[0]).index(9)
+    assert K.n == size and K.fv[1][a + 1] - K.fv[1][a] == size
+    m12, nm, *_ = expected(O, s)
+    for i, s0 in enumerate(range(0, size, 512)):
+        last = min(s0 + 511, size - 1)
+        assert m12[0][2 * i] == size - 1 - last and m12[0][2 * i + 1] == size - 1 - s0, (size, s0)
+    assert nm[0] == 2 * len(range(0, size, 512))
 
 
 def test_size_scenes():

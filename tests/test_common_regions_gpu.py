@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from common_regions_scene import (NODE_SIZES, SEEDS, cur_size_scene, describe, empty_member_scene, expect_tuple, expected, from_case, gpu_pair, hand_cases,
+from common_regions_scene import (CONTENDED_NODE, NODE_SIZES, SEEDS, contended_scene, cur_size_scene, describe, empty_member_scene, expect_tuple, expected, from_case, gpu_pair, hand_cases,
                                   mixed_groups, node_size_scene, run_gpu, same, seeded_scene, views)
 from match_cases import all_cases
 
@@ -61,8 +61,35 @@ def test_hand_written_scenes(M, h, case):
 
 @pytest.mark.parametrize("size", NODE_SIZES)
 def test_member_node_sizes(M, h, size):
-    """0, 1, 15, 16, 17, 33 and 512 features in the member's node; 513 does not fit the batch kernel and takes the single-call path: same results."""
+    """0, 1, 15, 16, 17, 33 and 512 features in the member's node keep a lane's `taken` flags in a register; from 513 on they lie in LDS words
+    (1024: the last size of two words a lane, 1025: the first of three).  No size leaves the device: same results."""
     check(M, h, node_size_scene(size))
+
+
+def test_contended_node_above_512(M, h):
+    """A member node of 1100 features in which, in every 512-position stretch, two current features want the member feature at the stretch's last
+    position: the first takes it, the second must find it taken and settles for the stretch's first.  A lane that lost a `taken` bit past
+    position 511 would hand the same feature out twice."""
+    size = CONTENDED_NODE
+    m12 = check(M, h, contended_scene())[0]
+    for i, s0 in enumerate(range(0, size, 512)):
+        last = min(s0 + 511, size - 1)
+        assert m12[0][2 * i] == size - 1 - last and m12[0][2 * i + 1] == (size - 1 - s0 if last != s0 else -1), (size, s0)
+
+
+def test_malformed_angle_stays_inside_the_histogram(M, h):
+    """An angle no key-point has (930 degrees against 0: round(930 / 30) = 31, past the 30 bins) is counted in the last bin, 29, where the entry
+    keeps it: eleven matches in bin 2 and this one in bin 29, 1 < 0.1f * 11 drops it (ORBmatcher.cc:1820).  The reference indexes past rotHist
+    here, so the expectation is written down by hand, not asked of the oracle."""
+    from common_regions_scene import Build
+    from match_cases import desc_at
+    s = Build(6)
+    for k, a1 in enumerate([60.0] * 11 + [930.0]):
+        b = s.base()
+        s.cur(b, 3 + 2 * k, angle=a1); s.feat(0, desc_at(b, 3, s.rng), 3 + 2 * k, k, angle=0.0)
+    keep = list(range(11)) + [-1]
+    e = dict(matches12=[keep], nmatches=[11], matched_point=[keep], matched_member=[[0] * 11 + [-1]], num=[11], most=[[0, 11]])
+    check(M, h, s.scene("angle_930", [[0]], 12, ori=True), expect_tuple(e))
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65])
@@ -140,7 +167,7 @@ def test_handle_reuse_and_buffer_growth(M, seeded):
     assert same(check(M, h, small, want_small), first)
     check(M, h, big, seeded[SEEDS[0]][1])
     assert same(check(M, h, small, want_small), first)
-    # a fallback call (513) between two batch calls leaves the handle as it was
+    # a call that keeps its `taken` flags in LDS (513) between two calls that keep them in a register leaves the handle as it was
     check(M, h, node_size_scene(513))
     assert same(check(M, h, small, want_small), first)
     h.close()

@@ -92,12 +92,29 @@ def test_search_by_bow(matcher, seed, nn):
 def test_search_by_bow_batch_matches_single_calls(matcher, K, nodes):
     """rumi_search_by_bow_batch: K candidate key-frames against one frame in one launch == K single SearchByBoW calls == the oracle, per
     candidate; `nodes` small puts dozens of features into every FeatureVector node (long sequential chains inside a node); nodes = 1 puts ALL
-    of the frame's features into one node -- more than the 512 the batch kernel holds per node, so the entry answers with K single searches."""
+    of the frame's features into one node -- more than the 512 a lane's `taken` register covers, so the launch keeps the flags in LDS words."""
+    bow_batch_against_single_calls(matcher, K, nodes)
+
+
+@pytest.mark.parametrize("nf", [512, 513])
+def test_search_by_bow_batch_frame_node_of_512_and_513(matcher, nf):
+    """The frame cut to nf features, all in one node: 512 is the largest node searched with the `taken` flags in a register, 513 the smallest
+    with the flags in LDS."""
+    bow_batch_against_single_calls(matcher, 3, 1, nf)
+
+
+def bow_batch_against_single_calls(matcher, K, nodes, nf=None):
+    """nf: the frame's first nf features only."""
     from rumi_slam_amd.matcher import FrameView, SearchByBoW_batch
     scenes = [TrackingScene(40 + k) for k in range(K)]
     base = scenes[0]
-    F = FrameView(base.cur_keys, base.cur_desc, base.w, base.h, base.sf)
     _, fv_f0 = base.feature_vectors(nodes)
+    if nf is not None:
+        assert len(base.cur_keys) > nf
+        base.cur_keys, base.cur_desc = base.cur_keys[:nf], base.cur_desc[:nf]
+        fv_f0 = {nd: [i for i in idxs if i < nf] for nd, idxs in fv_f0.items()}
+        assert [len(v) for v in fv_f0.values()] == [nf]
+    F = FrameView(base.cur_keys, base.cur_desc, base.w, base.h, base.sf)
     b = _fv(fv_f0)
     KFs, fvs, mps, bads = [], [], [], []
     for k, s in enumerate(scenes):
