@@ -262,7 +262,8 @@ int rumi_search_by_projection_sim3_rounds(const RumiMatcher *m, int32_t *rounds,
  * RUMI_E_INVALID, before any device work, nothing written: a NULL handle, store or array (matches12 excepted); n_groups < 0; group_start not
  * ascending from 0; more than 65535 members; a slot outside the store or not live; the current slot or a member that is not bad without
  * features, or whose feature count differs from the length of its row; (largest group) x n above 2^31 - 1 (the union's key j * n + k);
- * matcher and store on different devices.  RUMI_E_CAPACITY, likewise before any device work: a member above 65535 features; a union table above 2 GiB.
+ * matcher and store on different devices (the store is not bound first: neither handle makes a device call before this refusal, as in every
+ * by-slot entry of this header).  RUMI_E_CAPACITY, likewise before any device work: a member above 65535 features; a union table above 2 GiB.
  * An empty group, n_groups == 0 and n == 0 are valid: rows -1, counts 0 (-1 for a bad member), most_matches (0, 0); with n == 0 or M == 0
  * there is no device call. */
 int rumi_common_regions_bow_resident(RumiMatcher *m, RumiCovis *c, int32_t cur_slot, int32_t n_groups, const int32_t *group_start /* [n_groups + 1] */,
@@ -364,8 +365,8 @@ int rumi_refresh_map_points(RumiRefresh *r, const RumiRefreshKF *kf, int32_t n_k
  * the kernels, so the write-back wins over an older staged value.
  *
  * RUMI_E_INVALID, nothing written (neither the outputs nor the store), on the host before any device call: a missing argument; an unknown
- * `what` or `flags` bit, or no mode; an id outside the store or named twice; the handle and the store on different devices (a handle created
- * with device < 0 learns its device by asking for the current one, which is then the only device call made before this refusal); a point with
+ * `what` or `flags` bit, or no mode; an id outside the store or named twice; the handle and the store on different devices (before any device work: neither is
+ * bound first; a handle created with device < 0 learns its device by binding, which is then the only device work before this refusal); a point with
  * observers but without observation features; a point without attributes when RUMI_REFRESH_NORMAL_DEPTH or the write-back is asked for.
  * RUMI_E_INVALID, nothing written, counted on the device among what the call reads, the counts in the message (the store is legitimately
  * inconsistent between two staged edits, so the check is at the query): an observer slot without resident features (descriptor mode, good
@@ -473,7 +474,8 @@ int rumi_keyframe_culling(RumiCull *c, const RumiCullKF *kfs, int32_t n_kf, cons
  * changed.  The caller applies SetBadFlag() in the returned order and stages its edits for the next call.
  * RUMI_E_INVALID, nothing written: a missing argument or unknown flag; a candidate slot that is not live; a candidate that will be
  * evaluated and holds no features, or whose feature count differs from the length of its row; a point in such a row without observation
- * features (checked on the store's host mirror, with the count); the handle and the store on different devices; and, counted on the device
+ * features (checked on the store's host mirror, with the count); the handle and the store on different devices (on the host, before either
+ * binds: before any device work; a handle created with device < 0 learns its device by binding first); and, counted on the device
  * among the rows of the evaluated candidates, their points and those points' observers: an observer slot without resident features, an
  * observation (k, f) with f outside k's row or row_k[f] != p, a candidate slot i holding p where p does not list (candidate, i).  The check
  * happens at the query because the store is legitimately inconsistent between two staged edits.  RUMI_E_CAPACITY, nothing written: a point

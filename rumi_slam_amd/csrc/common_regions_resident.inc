@@ -16,27 +16,7 @@
 namespace rumi {
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-struct CrrState {
-    MirrorBuf<uint8_t> up;                                   // [BowSlotKF nM | group starts nG + 1]
-    MirrorBuf<int32_t> res;                                  // CrResultLayout
-    DevBuf<int8_t> rotBin;                                   // [nM][n]
-    DevBuf<unsigned long long> first;                        // [groups][max_points], stamped
-    size_t firstGroups = 0, firstPoints = 0;                 // the shape `first` was allocated for
-    uint32_t epoch = 0;
-    StageClock clock;
-    float stageMs[3] = {0.f, 0.f, 0.f};
-};
 constexpr size_t kCrrFirstMaxBytes = (size_t)1 << 31;        // the `first` table is refused above 2 GiB (groups x max_points x 8 bytes)
-
-static void crr_destroy(CrrState *s) { delete s; }
-
-static CrrState *crr_state(RumiMatcher *m) {
-    MatcherExt *ext = &m->ext;
-    if (!ext->state) { ext->state = new NewPtsState(); ext->destroy = newpts_destroy; }
-    NewPtsState *np = static_cast<NewPtsState *>(ext->state);
-    if (!np->crr) np->crr = new CrrState();
-    return np->crr;
-}
 
 }  // namespace rumi
 
@@ -69,7 +49,7 @@ extern "C" int rumi_common_regions_bow_resident(RumiMatcher *m, RumiCovis *c, in
     auto place = [&](int32_t slot) { return (size_t)(std::lower_bound(distinct.begin(), distinct.end(), slot) - distinct.begin()); };
     std::vector<CovisSlotFeatures> info(distinct.size());
     int rc;
-    if ((rc = covis_features_check(c, (int)distinct.size(), distinct.data(), -1, entry, info.data())) != RUMI_OK) return rc;
+    if ((rc = covis_features_check(c, (int)distinct.size(), distinct.data(), entry, info.data())) != RUMI_OK) return rc;
     const size_t curAt = place(cur_slot);
     const int n = info[curAt].n, nnC = info[curAt].nn;
     int maxN = 0;                                            // over the members that are searched, the current key-frame among them when it is named
@@ -86,17 +66,17 @@ extern "C" int rumi_common_regions_bow_resident(RumiMatcher *m, RumiCovis *c, in
     const size_t G = (size_t)n_groups, Mn = (size_t)nM * n;
     const CrOutputs out{matches12, nmatches, matched_point, matched_member, num_bow_matches, most_matches};
     if (n == 0 || nM == 0) {                                 // nothing to search: the literal loop leaves every vector NULL.  No device call.
-        CrrState *s0 = crr_state(m);
+        CrrState *s0 = made(newpts_state(m)->crr);
         s0->stageMs[0] = s0->stageMs[1] = s0->stageMs[2] = 0.f;
         cr_fill_nothing(n, nM, n_groups, bad.data(), out);
         return RUMI_OK;
     }
     // with work to do: the device both handles live on (a store without a device takes the matcher's)
-    if ((rc = covis_features_check(c, (int)distinct.size(), distinct.data(), m->device, entry, info.data())) != RUMI_OK) return rc;
+    if ((rc = covis_same_device(c, m->device, entry)) != RUMI_OK) return rc;
 #undef CRR_REFUSE
     // ---- device work from here on
     HIP_TRY(hipSetDevice(m->device));
-    CrrState *s = crr_state(m);
+    CrrState *s = made(newpts_state(m)->crr);
     s->clock.start(); s->clock.t[0] = t0;
     const size_t memBytes = (size_t)nM * sizeof(BowSlotKF), upBytes = memBytes + (G + 1) * 4;
     const CrResultLayout L(nM, n_groups, n);
@@ -105,14 +85,13 @@ extern "C" int rumi_common_regions_bow_resident(RumiMatcher *m, RumiCovis *c, in
         return rc;
     BowSlotKF *hm = reinterpret_cast<BowSlotKF *>(s->up.h);
     for (int i = 0; i < nM; i++) {
-        if (bad[(size_t)i]) { hm[i] = BowSlotKF{0, 0, 0, 0, 1}; continue; }
-        const CovisSlotFeatures &I = info[(size_t)at[(size_t)i]];
-        hm[i] = BowSlotKF{(long long)I.block, I.mpOff, I.n, I.nn, 0};
+        if (bad[(size_t)i]) hm[i] = BowSlotKF{{}, 1};
+        else hm[i] = BowSlotKF{covis_slot_ref(info[(size_t)at[(size_t)i]]), 0};
     }
     std::memcpy(s->up.h + memBytes, group_start, (G + 1) * 4);
     s->clock.mark();
-    CovisFeatureView fv;
-    if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
+    CovisView fv;
+    if ((rc = covis_view(c, 0, &fv)) != RUMI_OK) return rc;
     // the stamped table: one row of max_points words a group.  A new block, or a wrapped counter, starts from zeroed stamps and epoch 1.
     if (G > s->firstGroups || P > s->firstPoints || s->epoch == 0xFFFFFFFFu) {
         // (a handle that has served a larger store or more groups keeps the larger shape; capped so that the bound above stays the bound)
@@ -127,8 +106,8 @@ extern "C" int rumi_common_regions_bow_resident(RumiMatcher *m, RumiCovis *c, in
     HIP_TRY(L.clear(dRes));
     SlotCrView V;
     V.tab = reinterpret_cast<const BowSlotKF *>(s->up.d); V.groupStart = reinterpret_cast<const int32_t *>(s->up.d + memBytes);
-    V.feat = fv.feat; V.rows = fv.rows; V.pt = fv.pt;
-    V.curKf = BowSlotKF{(long long)info[curAt].block, info[curAt].mpOff, n, nnC, 0};
+    V.s = fv;
+    V.curKf = BowSlotKF{covis_slot_ref(info[curAt]), 0};
     BowRows R;
     CrGroups U;
     L.bind(dRes, &R, &U);
@@ -149,10 +128,10 @@ extern "C" int rumi_common_regions_bow_resident(RumiMatcher *m, RumiCovis *c, in
 }
 
 extern "C" int rumi_common_regions_bow_resident_stage_ms(const RumiMatcher *m, float *out3) {
-    if (!m || !out3 || !m->ext.state || !static_cast<const NewPtsState *>(m->ext.state)->crr) {
+    if (!out3 || !newpts_peek(m) || !newpts_peek(m)->crr) {
         g_lastError = "rumi_common_regions_bow_resident_stage_ms: no resident common-regions call precedes on this matcher";
         return RUMI_E_INVALID;
     }
-    std::memcpy(out3, static_cast<const NewPtsState *>(m->ext.state)->crr->stageMs, 12);
+    std::memcpy(out3, newpts_peek(m)->crr->stageMs, 12);
     return RUMI_OK;
 }

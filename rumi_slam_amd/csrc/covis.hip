@@ -1,25 +1,17 @@
 // The covisibility store (include/rumi_covis.h): KeyFrame::UpdateConnections for a batch of key-frames (R/lib_src/KeyFrame.cc:487-574) and
 // Tracking::UpdateLocalKeyFrames + UpdateLocalPoints for one frame (R/lib_src/Tracking.cc:3067-3210), over tables that stay on the device.
 //
-// Resident state, all of it 32-bit words so that one scatter kernel applies every staged edit:
-//   kf     [max_kf][20]     mp row (offset, length), children row (offset, length), flags (bit 0 bad, bit 1 live), map, parent, -, order_key
-//                           (two words), best[10]
-//   pt     [max_points][4]  observer row (offset, length), flags (bit 0 bad, bit 1 has observation features), has attributes.  An observer
-//                           entry is slot | feature << 13 (kCovisObsSlotMask): the feature index GetObservations() holds, 0 where the
-//                           point was set without them (rumi_covis_set_points)
-//   attr   [max_points][16] position, normal, mfMinDistance, mfMaxDistance (eight floats), then the 32 descriptor bytes: a 64-byte record whose
-//                           two halves are 16-byte aligned, so a gather may read either as two uint4 or as eight dwords over eight lanes.
-//                           Allocated with the first rumi_covis_set_point_attributes; the tracker's table gather reads it (track_local_map.inc)
-//   arena                   every row: mp rows, children rows, observer rows.  A row that outgrows its place moves to the tail; a full arena is
-//                           rebuilt on the host (compacted, and doubled when the live rows fill more than three quarters of it) and sent whole.
-//   tag    [max_points]     64-bit stamps of the local-point selection, (call epoch << 32) | priority
-//   rowOf  [max_points]     64-bit stamps of the same epoch for rumi_track_local_map's id -> table row map (allocated with its first call)
-//   feat                    the key-frames' constant part, a byte arena of its own with no host mirror (covis_features.inc)
-//   centre [max_kf][4]      GetCameraCenter() and a "has centre" word (rumi_covis_set_keyframe_centres); allocated with the first such call
-//   ref    [max_points]     GetReferenceKeyFrame() as slot + 1, 0 = none (rumi_covis_set_point_reference); allocated with the first such call.
-//                           Both are read by rumi_refresh_map_points_resident (refresh_resident.inc) and by nothing else
-//   featTab [max_kf][4]     where a slot's key-points lie in feat (64-bit byte offset, -1: no features), its feature count, -: what a kernel
-//                           needs to read the octave of an observation it meets in an observer row (culling.hip)
+// Resident state, all of it 32-bit words so that one scatter kernel applies every staged edit.  The record layout of kf, pt, attr, the row
+// arena, featTab, centre and ref is covis_view.h's; what that header does not say:
+//   attr   allocated with the first rumi_covis_set_point_attributes; the tracker's table gather reads it (track_local_map.inc)
+//   arena  a row that outgrows its place moves to the tail; a full arena is rebuilt on the host (compacted, and doubled when the live rows
+//          fill more than three quarters of it) and sent whole.  An observer entry holds the feature index GetObservations() holds, 0 where
+//          the point was set without them (rumi_covis_set_points)
+//   tag    [max_points]  64-bit stamps of the local-point selection, (call epoch << 32) | priority
+//   rowOf  [max_points]  64-bit stamps of the same epoch for rumi_track_local_map's id -> table row map (allocated with its first call)
+//   feat   the key-frames' constant part, a byte arena of its own with no host mirror (covis_features.inc)
+//   centre, ref  allocated with the first rumi_covis_set_keyframe_centres / rumi_covis_set_point_reference; read by
+//          rumi_refresh_map_points_resident (refresh_resident.inc) and by nothing else
 // The host keeps a mirror of kf, pt, attr and the arena; an edit writes the mirror and notes (table, offset, words).  The next query packs the noted
 // ranges and its own input into one pinned block, sends it with one copy, and k_covis_apply scatters it.
 //
@@ -40,25 +32,23 @@
 
 #include "rumi_common.h"
 #include "rumi_covis.h"
-#include "rumi_internal.h"
+#include "covis_view.h"
 #include "keyframe_features.h"
 
 namespace rumi {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int KFW = 20, PTW = kCovisPointWords, ATW = kCovisAttrWords;     // words per key-frame / point / attribute record
-constexpr int K_MPOFF = 0, K_MPLEN = 1, K_CHOFF = 2, K_CHLEN = 3, K_FLAGS = 4, K_MAP = 5, K_PARENT = 6, K_KEY = 8, K_BEST = 10;
+// short names of covis_view.h's layout for the kernels and the mirror code of this file
+constexpr int KFW = kCovisKfWords, PTW = kCovisPointWords, ATW = kCovisAttrWords, CTW = kCovisCentreWords, FTW = kCovisFeatTabWords;
+constexpr int K_MPOFF = kCovisKfMpOff, K_MPLEN = kCovisKfMpLen, K_CHOFF = kCovisKfChOff, K_CHLEN = kCovisKfChLen, K_FLAGS = kCovisKfFlags,
+              K_MAP = kCovisKfMap, K_PARENT = kCovisKfParent, K_KEY = kCovisKfKey, K_BEST = kCovisKfBest;
 constexpr int T_KF = 0, T_PT = 1, T_ARENA = 2, T_ATTR = 3, T_FEAT = 4, T_CENTRE = 5, T_REF = 6, kTables = 7;
-constexpr int CTW = kCovisCentreWords;
-constexpr int FTW = kCovisFeatTabWords;
 constexpr uint16_t kNone = 0xFFFF;                     // sorts last; slots stay below RUMI_COVIS_MAX_KEYFRAMES
 constexpr int kPosBits = 13;
 static_assert((1 << kPosBits) == RUMI_COVIS_MAX_KEYFRAMES, "position bits of the packed maximum");
 static_assert((1 << kCovisObsSlotBits) == RUMI_COVIS_MAX_KEYFRAMES && ((int64_t)RUMI_COVIS_MAX_FEATURES << kCovisObsSlotBits) <= (1ll << 31),
               "slot | feature << 13 is a non-negative 32-bit word");
-static_assert(KFW == kCovisKfWords && K_MPOFF == kCovisKfMpOff && K_MPLEN == kCovisKfMpLen, "the kf record as culling.hip reads it");
-static_assert(K_FLAGS == kCovisKfFlags, "the kf record as refresh_resident.inc reads it");
 static_assert((int64_t)RUMI_COVIS_MAX_FEATURES << kPosBits < (1ll << 31), "count << 13 | position fits 32 bits");
 static_assert((int64_t)RUMI_COVIS_MAX_KEYFRAMES * RUMI_COVIS_MAX_FEATURES <= (1ll << 32), "rank * features + feature fits 32 bits");
 
@@ -152,7 +142,7 @@ template <bool VOTE> __global__ __launch_bounds__(kThreads) void k_covis_count(C
             if (P.z & 1) bad = 1;
             else
                 for (int o = P.x, e = P.x + P.y; o < e; o++) {
-                    const int k = arena[o] & kCovisObsSlotMask;
+                    const int k = covis_obs_slot(arena[o]);
                     if (!VOTE) {
                         if (k == self) continue;
                         const int32_t *O = kf + k * KFW;
@@ -377,7 +367,6 @@ struct RumiCovis {
 namespace {
 
 inline int32_t row_cap(int32_t n) { return n + (n >> 2) + 2; }
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 void note(RumiCovis *h, int table, int64_t off, int64_t words) {
     if (words > 0 && !h->full[table]) h->recs.push_back(make_int4(table, (int)off, 0, (int)words));
@@ -500,7 +489,13 @@ int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) 
     return RUMI_OK;
 }
 
-inline bool is_live(const RumiCovis *h, int32_t s) { return s >= 0 && s < h->maxKf && (h->kf[(size_t)s * KFW + K_FLAGS] & 2); }
+inline bool is_live(const RumiCovis *h, int32_t s) { return s >= 0 && s < h->maxKf && (h->kf[(size_t)s * KFW + K_FLAGS] & kCovisKfLive); }
+
+// Where the tables lie right now (after flush and feat_flush).
+void fill_view(const RumiCovis *h, CovisView *v) {
+    *v = CovisView{h->dKf.p, h->dPt.p, h->dArena.p, h->dAttr.p, h->dFeatTab.p, h->feat.arena.p, h->dCentre.p, h->dRef.p,
+                   h->feat.oct.p, h->feat.octStride, h->maxKf, h->maxPts, h->dev.device};
+}
 
 }  // namespace
 
@@ -856,11 +851,7 @@ int rumi::covis_local_map_launch(RumiCovis *h, int n, const int32_t *frame_point
         }
     }
     int rc;
-    if ((rc = bind_device(h)) != RUMI_OK) return rc;
-    if (wantDevice >= 0 && h->dev.device != wantDevice) {
-        g_lastError = std::string(entry) + ": the store and the tracker are on different devices";
-        return RUMI_E_INVALID;
-    }
+    if ((rc = covis_same_device(h, wantDevice, entry)) != RUMI_OK) return rc;
     // the input block: frame points | discarded ids | their mbTrackInView | their projections, each part 16-byte aligned
     const size_t offIds = up16((size_t)n * 4), offIn = offIds + up16((size_t)nd * 4), offProj = offIn + up16(stale ? (size_t)nd : 0),
                  inBytes = d ? offProj + (stale ? (size_t)nd * 20 : 0) : (size_t)n * 4;
@@ -914,8 +905,9 @@ int rumi::covis_local_map_launch(RumiCovis *h, int n, const int32_t *frame_point
     HIP_TRY(hipGetLastError());
     CovisLocalView &v = *view;
     v = CovisLocalView{};
-    v.device = h->dev.device; v.maxPoints = h->maxPts; v.nFrame = n; v.nDiscarded = nd; v.epoch = h->epoch;
-    v.pt = h->dPt.p; v.attr = h->dAttr.p; v.rowOf = h->dRowOf.p;
+    fill_view(h, &v.t);
+    v.nFrame = n; v.nDiscarded = nd; v.epoch = h->epoch;
+    v.rowOf = h->dRowOf.p;
     v.head = reinterpret_cast<int32_t *>(h->out.d);
     v.localPts = reinterpret_cast<const int32_t *>(h->out.d + offPts);
     v.framePts = reinterpret_cast<const int32_t *>(dFrame);

@@ -23,12 +23,11 @@ constexpr int64_t kFeatLimit = 1ll << 38;              // far above any device; 
 
 // Slot `slot0 + blockIdx.y` of the octave table, from its key-points where they lie.  One slot (slot0 = the slot, gridDim.y = 1) or every slot
 // below gridDim.y; a slot without features is left alone.
-__global__ __launch_bounds__(256) void k_covis_octaves(const int32_t *featTab, const uint8_t *feat, uint8_t *oct, int stride, int slot0) {
+__global__ __launch_bounds__(256) void k_covis_octaves(CovisView v, uint8_t *oct, int slot0) {
     const int s = slot0 + (int)blockIdx.y, i = (int)blockIdx.x * 256 + (int)threadIdx.x;
-    const int32_t *T = featTab + s * FTW;
-    const long long keys = *reinterpret_cast<const long long *>(T);
-    if (keys < 0 || i >= T[2] || i >= stride) return;
-    oct[(size_t)s * stride + i] = (uint8_t)reinterpret_cast<const RumiKeyPoint *>(feat + keys)[i].octave;
+    const long long keys = v.feat_keys(s);
+    if (keys < 0 || i >= v.feat_count(s) || i >= v.octStride) return;
+    oct[(size_t)s * v.octStride + i] = (uint8_t)v.keys_at(keys)[i].octave;
 }
 
 // Brings the octave table up to date with the arena and featTab on the device (both flushed before): the pending slots one launch each,
@@ -47,10 +46,12 @@ int oct_flush(RumiCovis *h) {
     }
     if (F.arena.p && h->hiSlot > 0) {
         const int gx = (F.octStride + 255) / 256;
-        if (all) hipLaunchKernelGGL(k_covis_octaves, dim3(gx, h->hiSlot), dim3(256), 0, nullptr, h->dFeatTab.p, F.arena.p, F.oct.p, F.octStride, 0);
+        CovisView v;
+        fill_view(h, &v);
+        if (all) hipLaunchKernelGGL(k_covis_octaves, dim3(gx, h->hiSlot), dim3(256), 0, nullptr, v, F.oct.p, 0);
         else
             for (int32_t s : F.octPending)
-                hipLaunchKernelGGL(k_covis_octaves, dim3(gx, 1), dim3(256), 0, nullptr, h->dFeatTab.p, F.arena.p, F.oct.p, F.octStride, s);
+                hipLaunchKernelGGL(k_covis_octaves, dim3(gx, 1), dim3(256), 0, nullptr, v, F.oct.p, s);
         HIP_TRY(hipGetLastError());
     }
     F.octPending.clear();
@@ -58,7 +59,7 @@ int oct_flush(RumiCovis *h) {
 }
 
 // The record of a validated key-frame; false when the block would pass 2 GiB (the record's 32-bit offsets), or if the key-points did not
-// follow the record at once (kCovisFeatKeysOffset, rumi_internal.h).
+// follow the record at once (kCovisFeatKeysOffset, covis_view.h).
 bool feat_layout(const RumiFrameFeatures &f, const RumiFeatureVector &v, const float *K4, CovisFeatRec *r) {
     const uint64_t n = (uint64_t)f.n, nn = (uint64_t)v.n_nodes, ne = nn ? (uint64_t)v.offsets[nn] : 0;
     uint64_t at = sizeof(CovisFeatRec);                // the key-points follow the record at once: refresh_resident.inc finds the record from featTab's offset
@@ -245,7 +246,14 @@ extern "C" int rumi_covis_feature_stats(const RumiCovis *h, int64_t *out6) {
     return RUMI_OK;
 }
 
-int rumi::covis_features_check(RumiCovis *h, int n, const int32_t *slots, int wantDevice, const char *entry, CovisSlotFeatures *info) {
+int rumi::covis_same_device(RumiCovis *h, int wantDevice, const char *entry) {
+    if (wantDevice < 0) return RUMI_OK;
+    if (!h->dev.bound && h->dev.device < 0) h->dev.device = wantDevice;
+    if (h->dev.device != wantDevice) { g_lastError = std::string(entry) + ": the store and the handle that reads it are on different devices"; return RUMI_E_INVALID; }
+    return RUMI_OK;
+}
+
+int rumi::covis_features_check(RumiCovis *h, int n, const int32_t *slots, const char *entry, CovisSlotFeatures *info) {
     const FeatureStore &F = h->feat;
     if (h->stampKf > INT32_MAX - 4) { std::fill(h->kfStamp.begin(), h->kfStamp.end(), 0); h->stampKf = 0; }
     const int32_t inCall = ++h->stampKf;
@@ -263,12 +271,6 @@ int rumi::covis_features_check(RumiCovis *h, int n, const int32_t *slots, int wa
             return RUMI_E_INVALID;
         }
     }
-    if (wantDevice >= 0) {
-        if (!h->dev.bound && h->dev.device < 0) h->dev.device = wantDevice;      // a store without a device takes the consumer's
-        const int rc = bind_device(h);
-        if (rc != RUMI_OK) return rc;
-        if (h->dev.device != wantDevice) { g_lastError = std::string(entry) + ": the store and the matcher are on different devices"; return RUMI_E_INVALID; }
-    }
     for (int i = 0; i < n; i++) {                        // rows move when an edit is staged (set_row), never in a query
         const FeatPlace &P = F.place[slots[i]];
         const int32_t *K = h->kf.data() + (size_t)slots[i] * KFW;
@@ -279,11 +281,12 @@ int rumi::covis_features_check(RumiCovis *h, int n, const int32_t *slots, int wa
 
 int rumi::covis_max_points(const RumiCovis *h) { return h->maxPts; }
 
-int rumi::covis_features_flush(RumiCovis *h, CovisFeatureView *view) {
+int rumi::covis_view(RumiCovis *h, int want, CovisView *view) {
     int rc;
     uint8_t *unused = nullptr;
-    if ((rc = flush(h, nullptr, 0, &unused)) != RUMI_OK || (rc = feat_flush(h)) != RUMI_OK) return rc;
-    *view = CovisFeatureView{h->dArena.p, h->dPt.p, h->dAttr.p, h->feat.arena.p, h->maxKf, h->maxPts};
+    if ((rc = flush(h, nullptr, 0, &unused)) != RUMI_OK || (rc = feat_flush(h)) != RUMI_OK) return rc;      // flush binds the store
+    if ((want & kCovisWantOctaves) && (rc = oct_flush(h)) != RUMI_OK) return rc;
+    fill_view(h, view);
     return RUMI_OK;
 }
 
@@ -305,15 +308,4 @@ void rumi::covis_cull_row_points(const RumiCovis *h, int32_t mpOff, int32_t mpLe
         l = std::max(l, P[1]);
     }
     *without = w; *longest = l;
-}
-
-int rumi::covis_cull_flush(RumiCovis *h, int wantDevice, const char *entry, CovisCullView *view) {
-    if (!h->dev.bound && h->dev.device < 0) h->dev.device = wantDevice;          // a store without a device takes the consumer's
-    int rc = bind_device(h);
-    if (rc != RUMI_OK) return rc;
-    if (h->dev.device != wantDevice) { g_lastError = std::string(entry) + ": the handle and the store are on different devices"; return RUMI_E_INVALID; }
-    uint8_t *unused = nullptr;
-    if ((rc = flush(h, nullptr, 0, &unused)) != RUMI_OK || (rc = feat_flush(h)) != RUMI_OK || (rc = oct_flush(h)) != RUMI_OK) return rc;
-    *view = CovisCullView{h->dKf.p, h->dPt.p, h->dArena.p, h->dFeatTab.p, h->feat.oct.p, h->feat.octStride, h->maxKf, h->maxPts, h->dev.device};
-    return RUMI_OK;
 }

@@ -64,7 +64,7 @@ extern "C" int rumi_covis_set_point_reference(RumiCovis *h, int32_t n, const int
     return RUMI_OK;
 }
 
-int rumi::covis_refresh_check(RumiCovis *h, int n, const int32_t *ids, bool needAttr, int wantDevice, const char *entry, int32_t *rowLen) {
+int rumi::covis_refresh_check(RumiCovis *h, int n, const int32_t *ids, bool needAttr, const char *entry, int32_t *rowLen) {
     if (h->stampPt > INT32_MAX - 4) { std::fill(h->ptStamp.begin(), h->ptStamp.end(), 0); h->stampPt = 0; }
     const int32_t inCall = ++h->stampPt;
     for (int i = 0; i < n; i++) {
@@ -89,24 +89,6 @@ int rumi::covis_refresh_check(RumiCovis *h, int n, const int32_t *ids, bool need
         g_lastError = std::string(entry) + ": " + std::to_string(noAttr) + " points have no attributes (rumi_covis_set_point_attributes): the position is read there, and the write-back goes there";
         return RUMI_E_INVALID;
     }
-    if (wantDevice >= 0 && h->dev.device >= 0 && h->dev.device != wantDevice) {
-        g_lastError = std::string(entry) + ": the handle and the store are on different devices";
-        return RUMI_E_INVALID;
-    }
-    return RUMI_OK;
-}
-
-int rumi::covis_refresh_flush(RumiCovis *h, int wantDevice, const char *entry, CovisRefreshView *view) {
-    if (!h->dev.bound && h->dev.device < 0) h->dev.device = wantDevice;          // a store without a device takes the consumer's
-    if (h->dev.device != wantDevice) {                                            // before the store makes a device call
-        g_lastError = std::string(entry) + ": the handle and the store are on different devices";
-        return RUMI_E_INVALID;
-    }
-    int rc = bind_device(h);
-    if (rc != RUMI_OK) return rc;
-    uint8_t *unused = nullptr;
-    if ((rc = flush(h, nullptr, 0, &unused)) != RUMI_OK || (rc = feat_flush(h)) != RUMI_OK) return rc;
-    *view = CovisRefreshView{h->dKf.p, h->dPt.p, h->dArena.p, h->dFeatTab.p, h->dCentre.p, h->dRef.p, h->dAttr.p, h->feat.arena.p, h->dev.device};
     return RUMI_OK;
 }
 

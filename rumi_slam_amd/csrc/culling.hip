@@ -28,7 +28,7 @@
 #include <vector>
 
 #include "rumi_common.h"
-#include "rumi_internal.h"
+#include "covis_view.h"
 #include "rumi_mapping.h"
 
 namespace rumi {
@@ -71,21 +71,18 @@ struct BlockView {
 // ResidentView: the covisibility store's own tables (covis.hip), read in place.  Observations() is the length of the observer row; the
 // culled-observer count is a word per point owned by the RumiCull handle, (call epoch << 8) | count, never cleared between calls.
 struct ResidentView {
-    const int32_t *kf, *pt, *arena, *featTab;
-    const uint8_t *oct;                                             // the store's octave table: keys[f].octave of slot k at k * octStride + f
-    int octStride;
+    CovisView s;                                                    // read through: point, kf_row, the observer words, featTab, the octave table
     uint32_t *goneOf;
     uint32_t epoch;
     __device__ __forceinline__ int gone(int p) const { const uint32_t w = goneOf[p]; return (w >> 8) == epoch ? (int)(w & 255u) : 0; }
     __device__ __forceinline__ void add_gone(int p) const { const uint32_t w = goneOf[p]; goneOf[p] = (w >> 8) == epoch ? w + 1u : (epoch << 8) | 1u; }
     __device__ __forceinline__ CullPoint point(int p) const {
-        const int4 P = *reinterpret_cast<const int4 *>(pt + (size_t)p * kCovisPointWords);
-        return CullPoint{P.x, P.y, P.y, P.z & 1, gone(p)};
+        const CovisPoint P = s.point(p);
+        return CullPoint{P.obs_off(), P.obs_len(), P.obs_len(), P.bad(), gone(p)};
     }
-    __device__ __forceinline__ const int32_t *row(const int4 &cd) const { return arena + kf[cd.x * kCovisKfWords + kCovisKfMpOff]; }
-    __device__ __forceinline__ int2 obs(int o) const { const int w = arena[o]; return make_int2(w & kCovisObsSlotMask, w >> kCovisObsSlotBits); }
-    __device__ __forceinline__ long long keys_of(int k) const { return *reinterpret_cast<const long long *>(featTab + k * kCovisFeatTabWords); }
-    __device__ __forceinline__ int octave(int k, int f) const { return (int)oct[(size_t)k * octStride + f]; }
+    __device__ __forceinline__ const int32_t *row(const int4 &cd) const { return s.kf_row(cd.x); }
+    __device__ __forceinline__ int2 obs(int o) const { const int w = s.rows[o]; return make_int2(covis_obs_slot(w), covis_obs_feature(w)); }
+    __device__ __forceinline__ int octave(int k, int f) const { return s.octave(k, f); }
 };
 
 // One slot of key-frame `own` (octave ownOct) holding point p: bit 0 counted in nMPs (:1000-1006), bit 1 redundant (:1007-1038).
@@ -117,15 +114,14 @@ __global__ __launch_bounds__(kFirstThreads) void k_cull_check(ResidentView v, Cu
     if ((cd.w & 0xff) != 0 || i >= cd.z) return;
     const int p = v.row(cd)[i];
     if (p < 0) return;
-    const int4 P = *reinterpret_cast<const int4 *>(v.pt + (size_t)p * kCovisPointWords);
+    const CovisPoint P = v.s.point(p);
     int noFeat = 0, dangling = 0;
     bool listed = false;
-    for (int o = P.x, e = P.x + P.y; o < e; o++) {
+    for (int o = P.obs_off(), e = P.obs_off() + P.obs_len(); o < e; o++) {
         const int2 kfq = v.obs(o);
         const int k = kfq.x, f = kfq.y;
-        if (v.keys_of(k) < 0) { noFeat++; continue; }
-        const int32_t *K = v.kf + k * kCovisKfWords;
-        if (f >= v.featTab[k * kCovisFeatTabWords + 2] || f >= K[kCovisKfMpLen] || v.arena[K[kCovisKfMpOff] + f] != p) dangling++;
+        if (v.s.feat_keys(k) < 0) { noFeat++; continue; }
+        if (f >= v.s.feat_count(k) || f >= v.s.kf_row_len(k) || v.s.kf_row_entry(k, f) != p) dangling++;
         listed = listed || (k == cd.x && f == i);
     }
     if (noFeat) atomicAdd(&defects[0], noFeat);
@@ -327,11 +323,10 @@ extern "C" int rumi_keyframe_culling(RumiCull *h, const RumiCullKF *kfs, int32_t
     const int nUp = (int)h->cands.size();
 
     // ---- one block: points | candidates | first-pass counts | octave offsets | rows | observations | octaves || (device only) first-pass bits
-    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t offPts = 0, offCand = up((size_t)n_pts * 16), offCount = offCand + (size_t)nUp * 16, offOctOff = offCount + up((size_t)nUp * 8),
-                 offRows = offOctOff + up(((size_t)n_kf + 1) * 4), offObsKf = offRows + up(nRows * 4), offObsF = offObsKf + up((size_t)n_obs * 4),
-                 offOct = offObsF + up((size_t)n_obs * 4), upBytes = offOct + up((size_t)nOct), blkBytes = upBytes + up(nRows);
-    const size_t outBytes = ((size_t)nUp + 1) * 16 + up((size_t)nUp * 4);
+    const size_t offPts = 0, offCand = up16((size_t)n_pts * 16), offCount = offCand + (size_t)nUp * 16, offOctOff = offCount + up16((size_t)nUp * 8),
+                 offRows = offOctOff + up16(((size_t)n_kf + 1) * 4), offObsKf = offRows + up16(nRows * 4), offObsF = offObsKf + up16((size_t)n_obs * 4),
+                 offOct = offObsF + up16((size_t)n_obs * 4), upBytes = offOct + up16((size_t)nOct), blkBytes = upBytes + up16(nRows);
+    const size_t outBytes = ((size_t)nUp + 1) * 16 + up16((size_t)nUp * 4);
     if ((rc = h->dev.bind()) != RUMI_OK || (rc = h->blk.reserve(blkBytes, blkBytes + blkBytes / 4)) != RUMI_OK ||
         (rc = h->out.reserve(outBytes, outBytes + outBytes / 4)) != RUMI_OK)
         return rc;
@@ -443,11 +438,12 @@ extern "C" int rumi_keyframe_culling_resident(RumiCull *h, RumiCovis *c, const R
 
     // ---- the staged edits of the store, then one small block: candidates | first-pass counts | defect counts || (device only) first-pass bits
     int rc;
-    CovisCullView cv;
-    if ((rc = h->dev.bind()) != RUMI_OK || (rc = covis_cull_flush(c, h->dev.device, E, &cv)) != RUMI_OK) return rc;
-    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t offCount = (size_t)nUp * 16, offDefect = offCount + up((size_t)nUp * 8), upBytes = offDefect + 16, blkBytes = upBytes + up(nRows);
-    const size_t outBytes = ((size_t)nUp + 1) * 16 + up((size_t)nUp * 4);
+    CovisView cv;
+    const bool named = h->dev.device >= 0;                   // a handle created without a device learns it when it binds: the rule is asked again then
+    if ((rc = covis_same_device(c, h->dev.device, E)) != RUMI_OK || (rc = h->dev.bind()) != RUMI_OK) return rc;
+    if ((!named && (rc = covis_same_device(c, h->dev.device, E)) != RUMI_OK) || (rc = covis_view(c, kCovisWantOctaves, &cv)) != RUMI_OK) return rc;
+    const size_t offCount = (size_t)nUp * 16, offDefect = offCount + up16((size_t)nUp * 8), upBytes = offDefect + 16, blkBytes = upBytes + up16(nRows);
+    const size_t outBytes = ((size_t)nUp + 1) * 16 + up16((size_t)nUp * 4);
     if ((rc = h->blk.reserve(blkBytes, blkBytes + blkBytes / 4)) != RUMI_OK || (rc = h->out.reserve(outBytes, outBytes + outBytes / 4)) != RUMI_OK) return rc;
     if (h->gone.cap < (size_t)cv.maxPoints || h->epoch >= (1u << 24) - 1) {          // a new block, or the stamp's 24 bits are used up
         if ((rc = h->gone.reserve((size_t)cv.maxPoints, (size_t)cv.maxPoints)) != RUMI_OK) return rc;
@@ -460,7 +456,7 @@ extern "C" int rumi_keyframe_culling_resident(RumiCull *h, RumiCovis *c, const R
     clock.mark();
     HIP_TRY(hipMemcpyAsync(h->blk.d, h->blk.h, upBytes, hipMemcpyHostToDevice, nullptr));
 
-    ResidentView v{cv.kf, cv.pt, cv.rows, cv.featTab, cv.oct, cv.octStride, h->gone.p, h->epoch};
+    ResidentView v{cv, h->gone.p, h->epoch};
     CullArgs a;
     a.cands = reinterpret_cast<const int4 *>(h->blk.d);
     a.counts = reinterpret_cast<int2 *>(h->blk.d + offCount);

@@ -17,6 +17,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -50,8 +51,8 @@ template <class T> __device__ __forceinline__ const T *at(const uint8_t *blk, ui
 // The four kernels below read a key-frame through a view: view.kf(i) is key-frame i of the call (0 = the current one), and what it returns
 // names every array and small matrix.  The kernels hold the arithmetic once; the two entries differ only in where the bytes lie.
 //   BlockView     rumi_create_new_map_points: everything inside the call's upload block, arrays at blk + offset.
-//   ResidentView  rumi_create_new_map_points_resident: features in the store's feature arena (a CovisFeatRec and its arrays), the map-point
-//                 row where the covisibility store keeps it, positions in the scratch k_newpts_gather filled, poses in the call's table.
+//   ResidentView  rumi_create_new_map_points_resident: a CovisKeyFrame of the covisibility store (covis_view.h), positions in the scratch
+//                 k_newpts_gather filled, poses in the call's table.
 struct BlockView {
     const uint8_t *blk;
     struct KF {
@@ -76,31 +77,17 @@ struct BlockView {
 };
 
 // One key-frame of a resident call: where its block, its row and its positions lie, and the pose by value.
-struct ResKF {
-    int64_t block;                     // byte offset of the CovisFeatRec in the feature arena
-    int32_t mpOff;                     // first entry of the mp row in the row arena
+struct ResKF : CovisSlotRef {
     uint32_t posOff;                   // first float of its positions in the gather scratch (neighbours)
     float T[12], Ow[3], F12[9], ep[2];
-    int32_t pad[2];
 };
 static_assert(sizeof(ResKF) == 128, "a pose record");
 
 struct ResidentView {
-    const ResKF *tab; const uint8_t *feat; const int32_t *rows; const float *pos;
-    struct KF {
-        const ResKF *p; const CovisFeatRec *r; const int32_t *row; const float *xyz;
-        template <class T> __device__ __forceinline__ const T *arr(uint32_t o) const { return rec_arr<T>(r, o); }
-        __device__ __forceinline__ int n() const { return r->n; }
-        __device__ __forceinline__ int nn() const { return r->nn; }
-        __device__ __forceinline__ const RumiKeyPoint *keys() const { return arr<RumiKeyPoint>(r->keys); }
-        __device__ __forceinline__ const uint8_t *desc() const { return arr<uint8_t>(r->desc); }
-        __device__ __forceinline__ const float *scale() const { return arr<float>(r->scale); }
-        __device__ __forceinline__ const uint32_t *nodes() const { return arr<uint32_t>(r->nodes); }
-        __device__ __forceinline__ const int32_t *off() const { return arr<int32_t>(r->off); }
-        __device__ __forceinline__ const uint32_t *idx() const { return arr<uint32_t>(r->idx); }
-        __device__ __forceinline__ const int32_t *mp() const { return row; }
+    const ResKF *tab; CovisView s; const float *pos;
+    struct KF : CovisKeyFrame {
+        const ResKF *p; const float *xyz;
         __device__ __forceinline__ const float *pos() const { return xyz; }
-        __device__ __forceinline__ const float *K() const { return r->K; }
         __device__ __forceinline__ const float *T() const { return p->T; }
         __device__ __forceinline__ const float *Ow() const { return p->Ow; }
         __device__ __forceinline__ const float *F12() const { return p->F12; }
@@ -108,7 +95,7 @@ struct ResidentView {
     };
     __device__ __forceinline__ KF kf(int i) const {
         const ResKF *p = tab + i;
-        return KF{p, reinterpret_cast<const CovisFeatRec *>(feat + p->block), rows + p->mpOff, pos + p->posOff};
+        return KF{s.key_frame(*p), p, pos + p->posOff};
     }
 };
 
@@ -430,29 +417,62 @@ __global__ __launch_bounds__(1024) void k_newpts_replay(const View view, int nNe
 // point's 64-byte attribute record (covis.hip) into pos[posOff + 3 i]: what the block entry gets as mp_pos.  An entry whose point has no
 // attributes is counted (integer atomic; the order does not matter) and the host refuses the call.  The current key-frame's positions
 // are not read, as with mp_pos == NULL.
-__global__ __launch_bounds__(256) void k_newpts_gather(const ResKF *__restrict__ tab, const uint8_t *__restrict__ feat, const int32_t *__restrict__ rows,
-                                                       const int32_t *__restrict__ pt, const int32_t *__restrict__ attr, int32_t *__restrict__ pos,
-                                                       int32_t *__restrict__ missing) {
+__global__ __launch_bounds__(256) void k_newpts_gather(const ResKF *__restrict__ tab, CovisView s, int32_t *__restrict__ pos, int32_t *__restrict__ missing) {
     const ResKF &N = tab[1 + blockIdx.y];
-    const int n = reinterpret_cast<const CovisFeatRec *>(feat + N.block)->n, i = blockIdx.x * 256 + threadIdx.x;
+    const int n = s.rec(N.block)->n, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int p = rows[N.mpOff + i];
+    const int p = s.mp_row(N)[i];
     if (p < 0) return;
-    if (!attr || !pt[(size_t)p * kCovisPointWords + 3]) { atomicAdd(missing, 1); return; }
-    const int32_t *A = attr + (size_t)p * kCovisAttrWords;
+    if (!s.has_attr(p)) { atomicAdd(missing, 1); return; }
+    const int32_t *A = s.attr_rec(p);
     int32_t *o = pos + N.posOff + 3 * (size_t)i;
     o[0] = A[0]; o[1] = A[1]; o[2] = A[2];
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-struct SinState;                                             // the blocks of rumi_search_in_neighbors_resident (search_in_neighbors.inc)
-static void sin_destroy(SinState *s);
-struct SafState;                                             // the blocks of rumi_search_and_fuse_resident (search_and_fuse.inc)
-static void saf_destroy(SafState *s);
-struct S3pState;                                             // the blocks of rumi_search_by_projection_sim3_resident (sim3_projection_batch.inc)
-static void s3p_destroy(S3pState *s);
-struct CrrState;                                             // the blocks of rumi_common_regions_bow_resident (common_regions_resident.inc)
-static void crr_destroy(CrrState *s);
+// What the entries of this file keep on a RumiMatcher (MatcherExt, rumi_internal.h): one NewPtsState, made by the first call of any of them, so that
+// the blocks live and die with the handle.  Each by-slot search owns a part of it that is made by ITS first call: that is how its *_stage_ms
+// knows that no call precedes.
+struct SinState {                                            // rumi_search_in_neighbors_resident (search_in_neighbors.inc)
+    MirrorBuf<uint8_t> tab;                                  // the table of SinKF
+    MirrorBuf<int32_t> res;                                  // [head SIN_HEAD][fwd nT * nCur][revPoint E][revBest E], E = the targets' row entries
+    DevBuf<uint16_t> sorted; DevBuf<int32_t> cellStart, blocks;
+    DevBuf<uint32_t> slotTag; DevBuf<unsigned long long> claim;      // the stamped tables, which SearchAndFuse and the Sim3 projection search share
+    DevBuf<uint4> work;
+    uint32_t epoch = 0;
+    StageClock clock;
+    float stageMs[3] = {0.f, 0.f, 0.f};
+};
+struct SafState {                                            // rumi_search_and_fuse_resident (search_and_fuse.inc)
+    MirrorBuf<uint8_t> up;                                   // the table of SinKF, then the ids
+    MirrorBuf<int32_t> res;                                  // [head SIN_HEAD][per_kf nK][hits: 4 words each]
+    DevBuf<int32_t> dense, cellStart, blocks;                // [nK][nP] best index per pair; the grids; block counts and bases
+    DevBuf<uint16_t> sorted;
+    DevBuf<uint4> work;
+    StageClock clock;
+    float stageMs[3] = {0.f, 0.f, 0.f};
+};
+struct S3pState {                                            // rumi_search_by_projection_sim3_resident (sim3_projection_batch.inc)
+    MirrorBuf<uint8_t> up;                                   // the grids' SinKF, the jobs' S3pJob, the ids
+    MirrorBuf<int32_t> res;                                  // [head SIN_HEAD][nmatches nJ][rounds nJ][rows]
+    DevBuf<int32_t> pair, cellStart;                         // [4][pairs] counts, cursors, list starts, held features; the grids
+    DevBuf<uint16_t> sorted;
+    DevBuf<uint4> work;
+    DevBuf<uint2> lists;
+    std::vector<int32_t> rounds;                             // of the last call, per job
+    StageClock clock;
+    float stageMs[3] = {0.f, 0.f, 0.f};
+};
+struct CrrState {                                            // rumi_common_regions_bow_resident (common_regions_resident.inc)
+    MirrorBuf<uint8_t> up;                                   // [BowSlotKF nM | group starts nG + 1]
+    MirrorBuf<int32_t> res;                                  // CrResultLayout
+    DevBuf<int8_t> rotBin;                                   // [nM][n]
+    DevBuf<unsigned long long> first;                        // [groups][max_points], stamped
+    size_t firstGroups = 0, firstPoints = 0;                 // the shape `first` was allocated for
+    uint32_t epoch = 0;
+    StageClock clock;
+    float stageMs[3] = {0.f, 0.f, 0.f};
+};
 
 struct NewPtsState {
     MirrorBuf<uint8_t> blk, res;                             // the upload block; the result block, a NewPtsResult and its points
@@ -461,20 +481,25 @@ struct NewPtsState {
     int lastNeigh = 0, lastN1 = 0, lastOri = 0;              // the last block call, whose device state rumi_hook_newpts_matches replays
     StageClock clock;
     float stageMs[3] = {0.f, 0.f, 0.f};
-    SinState *sin = nullptr;                                 // with the first SearchInNeighbors or SearchAndFuse call (the stamped tables)
-    SafState *saf = nullptr;                                 // with the first SearchAndFuse call
-    S3pState *s3p = nullptr;                                 // with the first resident Sim3 projection search
-    CrrState *crr = nullptr;                                 // with the first resident common-regions BoW call
+    std::unique_ptr<SinState> sin;                           // with the first SearchInNeighbors, SearchAndFuse or Sim3 projection call (the stamped tables)
+    std::unique_ptr<SafState> saf;
+    std::unique_ptr<S3pState> s3p;
+    std::unique_ptr<CrrState> crr;
 };
 
-static void newpts_destroy(void *p) {                        // rumi_match_destroy has made the matcher's device current
-    NewPtsState *s = static_cast<NewPtsState *>(p);
-    if (s->sin) sin_destroy(s->sin);
-    if (s->saf) saf_destroy(s->saf);
-    if (s->s3p) s3p_destroy(s->s3p);
-    if (s->crr) crr_destroy(s->crr);
-    delete s;
+static void newpts_destroy(void *p) { delete static_cast<NewPtsState *>(p); }       // rumi_match_destroy has made the matcher's device current
+
+// This matcher's state, and a part of it, each made on first use.
+static NewPtsState *newpts_state(RumiMatcher *m) {
+    if (!m->ext.state) { m->ext.state = new NewPtsState(); m->ext.destroy = newpts_destroy; }
+    return static_cast<NewPtsState *>(m->ext.state);
 }
+template <class T> static T *made(std::unique_ptr<T> &part) {
+    if (!part) part.reset(new T());
+    return part.get();
+}
+// What a *_stage_ms entry reads: the part if its entry has been called on this matcher, else null.
+static const NewPtsState *newpts_peek(const RumiMatcher *m) { return m ? static_cast<const NewPtsState *>(m->ext.state) : nullptr; }
 
 static bool kf_valid(const RumiNewPointsKF &k, bool neighbour, const char **why) {
     *why = "key-frame features: bad sizes or missing arrays";
@@ -484,8 +509,7 @@ static bool kf_valid(const RumiNewPointsKF &k, bool neighbour, const char **why)
 
 static size_t kf_bytes(const RumiNewPointsKF &k) {
     const size_t n = k.feat.n, nn = k.fv.n_nodes, ne = nn ? k.fv.offsets[nn] : 0;
-    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    return up(n * sizeof(RumiKeyPoint)) + up(n * 32) + up(k.feat.nlevels * 4) + up(nn * 4) + up((nn + 1) * 4) + up(ne * 4) + up(n * 4) + up(n * 12);
+    return up16(n * sizeof(RumiKeyPoint)) + up16(n * 32) + up16(k.feat.nlevels * 4) + up16(nn * 4) + up16((nn + 1) * 4) + up16(ne * 4) + up16(n * 4) + up16(n * 12);
 }
 
 static void kf_pack(const RumiNewPointsKF &k, bool neighbour, uint8_t *blk, size_t *used, KFDev *d) {
@@ -573,7 +597,6 @@ extern "C" int rumi_create_new_map_points(RumiMatcher *m, const RumiNewPointsKF 
     if (!kf_valid(*cur, false, &why)) { g_lastError = why; return RUMI_E_INVALID; }
     for (int k = 0; k < n_neigh; k++) if (!kf_valid(neigh[k], true, &why)) { g_lastError = why; return RUMI_E_INVALID; }
     const int maxFeat = m->maxFeat, maxQ = m->maxQ;
-    MatcherExt *ext = &m->ext;
     const int n1 = cur->feat.n;
     auto entries = [](const RumiNewPointsKF &k) { return k.fv.n_nodes ? k.fv.offsets[k.fv.n_nodes] : 0; };
     bool fits = n1 <= std::min(std::min(maxFeat, maxQ), kMaxCur) && entries(*cur) <= std::min(maxFeat, maxQ) && cur->fv.n_nodes <= std::min(maxFeat, maxQ);
@@ -590,8 +613,7 @@ extern "C" int rumi_create_new_map_points(RumiMatcher *m, const RumiNewPointsKF 
     for (int k = 0; k < n_neigh; k++) { per_neigh_out[k] = 0; neigh_skipped_out[k] = 0; }
     if (n_neigh == 0) return RUMI_OK;
     HIP_TRY(hipSetDevice(m->device));
-    if (!ext->state) { ext->state = new NewPtsState(); ext->destroy = newpts_destroy; }
-    NewPtsState *s = static_cast<NewPtsState *>(ext->state);
+    NewPtsState *s = newpts_state(m);
     s->lastNeigh = 0; s->lastN1 = 0;
     s->clock.start(); s->clock.t[0] = t0;                    // the validation above belongs to the host stage
 
@@ -629,7 +651,7 @@ extern "C" int rumi_create_new_map_points_resident(RumiMatcher *m, RumiCovis *c,
     slots[0] = cur_slot;
     for (int k = 0; k < n_neigh; k++) slots[1 + k] = neigh_slots[k];
     int rc;
-    if ((rc = covis_features_check(c, n_neigh + 1, slots, n_neigh > 0 ? m->device : -1, entry, info)) != RUMI_OK) return rc;
+    if ((rc = covis_features_check(c, n_neigh + 1, slots, entry, info)) != RUMI_OK || (n_neigh > 0 && (rc = covis_same_device(c, m->device, entry)) != RUMI_OK)) return rc;
     const int lim = std::min(m->maxFeat, m->maxQ), n1 = info[0].n;
     bool fits = n1 <= std::min(lim, kMaxCur) && info[0].ne <= lim && info[0].nn <= lim;
     int maxN2 = 1;
@@ -645,9 +667,7 @@ extern "C" int rumi_create_new_map_points_resident(RumiMatcher *m, RumiCovis *c,
     }
     if (n_neigh == 0) { *n_out = 0; return RUMI_OK; }
     HIP_TRY(hipSetDevice(m->device));
-    MatcherExt *ext = &m->ext;
-    if (!ext->state) { ext->state = new NewPtsState(); ext->destroy = newpts_destroy; }
-    NewPtsState *s = static_cast<NewPtsState *>(ext->state);
+    NewPtsState *s = newpts_state(m);
     s->lastNeigh = 0; s->lastN1 = 0;                         // the hook replays the block path's state, which this call overwrites
     s->clock.start(); s->clock.t[0] = t0;
 
@@ -661,21 +681,19 @@ extern "C" int rumi_create_new_map_points_resident(RumiMatcher *m, RumiCovis *c,
     for (int k = 0; k <= n_neigh; k++) {
         const RumiNewPointsPose &P = k ? neigh_pose[k - 1] : *cur_pose;
         ResKF &R = tab[k];
-        R.block = info[k].block; R.mpOff = info[k].mpOff; R.posOff = k ? posOff : 0;
+        static_cast<CovisSlotRef &>(R) = covis_slot_ref(info[k]); R.posOff = k ? posOff : 0;
         std::memcpy(R.T, P.Tcw, 48); std::memcpy(R.Ow, P.Ow, 12); std::memcpy(R.F12, P.F12, 36); std::memcpy(R.ep, P.epipole2, 8);
-        R.pad[0] = R.pad[1] = 0;
         if (k) posOff += 3u * (uint32_t)info[k].n;
     }
     s->clock.mark();
-    CovisFeatureView fv;
-    if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
+    CovisView fv;
+    if ((rc = covis_view(c, 0, &fv)) != RUMI_OK) return rc;
     HIP_TRY(hipMemcpyAsync(s->tab.d, s->tab.h, tabBytes, hipMemcpyHostToDevice, nullptr));
     NewPtsResult *dRes = reinterpret_cast<NewPtsResult *>(s->res.d);
     HIP_TRY(hipMemsetAsync(dRes, 0, sizeof(NewPtsResult), nullptr));
     const ResKF *dTab = reinterpret_cast<const ResKF *>(s->tab.d);
-    hipLaunchKernelGGL(k_newpts_gather, dim3((maxN2 + 255) / 256, n_neigh), dim3(256), 0, nullptr, dTab, fv.feat, fv.rows, fv.pt, fv.attr, s->pos.p,
-                       &dRes->pad[0]);
-    if ((rc = newpts_run(s, ResidentView{dTab, fv.feat, fv.rows, reinterpret_cast<const float *>(s->pos.p)}, n_neigh, n1, info[0].nn, maxN2, p)) != RUMI_OK)
+    hipLaunchKernelGGL(k_newpts_gather, dim3((maxN2 + 255) / 256, n_neigh), dim3(256), 0, nullptr, dTab, fv, s->pos.p, &dRes->pad[0]);
+    if ((rc = newpts_run(s, ResidentView{dTab, fv, reinterpret_cast<const float *>(s->pos.p)}, n_neigh, n1, info[0].nn, maxN2, p)) != RUMI_OK)
         return rc;
     const int missing = reinterpret_cast<const NewPtsResult *>(s->res.h)->pad[0];
     if (missing) {
@@ -686,8 +704,8 @@ extern "C" int rumi_create_new_map_points_resident(RumiMatcher *m, RumiCovis *c,
 }
 
 extern "C" int rumi_newpts_stage_ms(const RumiMatcher *m, float *out3) {
-    if (!m || !out3 || !m->ext.state) { g_lastError = "rumi_newpts_stage_ms: no CreateNewMapPoints call precedes on this matcher"; return RUMI_E_INVALID; }
-    std::memcpy(out3, static_cast<const NewPtsState *>(m->ext.state)->stageMs, 12);
+    if (!out3 || !newpts_peek(m)) { g_lastError = "rumi_newpts_stage_ms: no CreateNewMapPoints call precedes on this matcher"; return RUMI_E_INVALID; }
+    std::memcpy(out3, newpts_peek(m)->stageMs, 12);
     return RUMI_OK;
 }
 

@@ -18,26 +18,22 @@
 
 #include "match_bow.h"
 #include "rumi_common.h"
-#include "rumi_internal.h"
+#include "covis_view.h"
 
 namespace rumi {
 
 // ---- key-frame views ----------------------------------------------------------------------------------------------------------------------
 struct BowPackedKF { int32_t n, nn, angle, desc, mp, good, nodes, off, idx, pad; };      // sizes and dword offsets of one key-frame's arrays in the block
-struct BowSlotKF { long long block; int32_t mpOff, n, nn, bad; };      // one row: its CovisFeatRec (bytes into the feature arena), its map-point row; bad: named, not searched
+struct BowSlotKF : CovisSlotRef { int32_t bad; };            // one row; bad: named, not searched
 static_assert(sizeof(BowSlotKF) == 24, "the slot table as uploaded");
-
-template <class T> __device__ __forceinline__ const T *rec_arr(const CovisFeatRec *r, uint32_t o) {
-    return reinterpret_cast<const T *>(reinterpret_cast<const uint8_t *>(r) + o);
-}
 
 // angle of feature i / "feature i holds a map point that is not bad" (ORBmatcher.cc:238-243, :717-721, :738-742), as either side keeps them
 struct PackedAngles { const float *p; __device__ __forceinline__ float operator[](int i) const { return p[i]; } };
 struct PackedGood { const uint8_t *p; __device__ __forceinline__ bool operator[](int i) const { return p[i] != 0; } };
 struct SlotAngles { const RumiKeyPoint *p; __device__ __forceinline__ float operator[](int i) const { return p[i].angle; } };
 struct SlotGood {                                            // read in the store: row entry >= 0 and the point's bad bit clear
-    const int32_t *row, *pt;
-    __device__ __forceinline__ bool operator[](int i) const { const int p = row[i]; return p >= 0 && !(pt[(size_t)p * kCovisPointWords + 2] & 1); }
+    const int32_t *row; CovisView s;
+    __device__ __forceinline__ bool operator[](int i) const { const int p = row[i]; return p >= 0 && !s.point_bad(p); }
 };
 
 struct PackedKF {
@@ -53,17 +49,13 @@ struct PackedKF {
     __device__ __forceinline__ PackedGood good() const { return PackedGood{reinterpret_cast<const uint8_t *>(blk + t->good)}; }
     __device__ __forceinline__ bool bad() const { return false; }
 };
-struct SlotKF {                                              // (nothing behind r is read before bad() has said no)
-    const CovisFeatRec *r; const int32_t *row, *pt; int32_t n_, nn_, bad_;
+struct SlotKF : CovisKeyFrame {                              // sizes from the table row: nothing behind r is read before bad() has said no
+    CovisView s; int32_t n_, nn_, bad_;
     __device__ __forceinline__ int n() const { return n_; }
     __device__ __forceinline__ int nn() const { return nn_; }
-    __device__ __forceinline__ const uint32_t *nodes() const { return rec_arr<uint32_t>(r, r->nodes); }
-    __device__ __forceinline__ const int32_t *off() const { return rec_arr<int32_t>(r, r->off); }
-    __device__ __forceinline__ const uint32_t *idx() const { return rec_arr<uint32_t>(r, r->idx); }
     __device__ __forceinline__ const uint32_t *desc() const { return rec_arr<uint32_t>(r, r->desc); }
-    __device__ __forceinline__ const int32_t *mp() const { return row; }
-    __device__ __forceinline__ SlotAngles angles() const { return SlotAngles{rec_arr<RumiKeyPoint>(r, r->keys)}; }
-    __device__ __forceinline__ SlotGood good() const { return SlotGood{row, pt}; }
+    __device__ __forceinline__ SlotAngles angles() const { return SlotAngles{keys()}; }
+    __device__ __forceinline__ SlotGood good() const { return SlotGood{row, s}; }
     __device__ __forceinline__ bool bad() const { return bad_ != 0; }
 };
 
@@ -83,9 +75,8 @@ struct PackedCrView : PackedView {                           // row = member: th
 struct SlotView {
     using KF = SlotKF;
     const BowSlotKF *tab;         // [rows]
-    const uint8_t *feat;          // the feature arena
-    const int32_t *rows, *pt;     // the row arena, the point records
-    __device__ __forceinline__ KF of(const BowSlotKF &T) const { return KF{reinterpret_cast<const CovisFeatRec *>(feat + T.block), rows + T.mpOff, pt, T.n, T.nn, T.bad}; }
+    CovisView s;                  // read through: key_frame, point_bad
+    __device__ __forceinline__ KF of(const BowSlotKF &T) const { return KF{s.key_frame(T), s, T.n, T.nn, T.bad}; }
     __device__ __forceinline__ KF kf(int k) const { return of(tab[k]); }
 };
 struct SlotCrView : SlotView {

@@ -238,11 +238,6 @@ __device__ __forceinline__ Query reloc_query(int mp, bool skip, const float *mpP
     return o;
 }
 
-// A 16-byte load that asks for 4-byte alignment only (the extractor's descriptor kernel loads its rows the same way, orb_orient_desc.inc):
-// one wide instruction where the address happens to be aligned, never a fault where a row is not.
-struct __attribute__((packed, aligned(4))) Dword4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ uint4 ld16_dword(const void *q) { const Dword4 t = *reinterpret_cast<const Dword4 *>(q); return make_uint4(t.x, t.y, t.z, t.w); }
-
 // Correspondences of Optimizer::PoseOptimization(Frame*) (Optimizer.cc:749-815, mono): the features with a map point, in feature order.
 // One workgroup of 1024 threads, ordered compaction (block_ordered_slot, chunks of 1024 features).  correspondence_store: feature i with point mp
 // as correspondence c, also for the relocalisation's gather (track_reloc.inc).

@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "rumi_common.h"
-#include "rumi_internal.h"
+#include "covis_view.h"
 #include "rumi_mapping.h"
 
 namespace rumi {
@@ -276,9 +276,8 @@ extern "C" int rumi_refresh_map_points(RumiRefresh *r, const RumiRefreshKF *kf, 
     std::stable_sort(r->bins[3].begin(), r->bins[3].end(), [&](int a, int b) { return r->pt[a].nGood > r->pt[b].nGood; });
 
     // ---- one block: points | camera centres | key-frame index of every observation | bin lists | position of every gathered row | rows
-    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t offPts = 0, offOw = up((size_t)n_pts * sizeof(PtDev)), offObs = offOw + up((size_t)n_kf * 12),
-                 offList = offObs + up(wantNormal ? (size_t)n_obs * 4 : 0), offPos = offList + up(nBinned * 4), offDesc = offPos + up(nGoodAll * 4),
+    const size_t offPts = 0, offOw = up16((size_t)n_pts * sizeof(PtDev)), offObs = offOw + up16((size_t)n_kf * 12),
+                 offList = offObs + up16(wantNormal ? (size_t)n_obs * 4 : 0), offPos = offList + up16(nBinned * 4), offDesc = offPos + up16(nGoodAll * 4),
                  blkBytes = offDesc + nGoodAll * 32;
     const size_t outBytes = (size_t)n_pts * sizeof(OutDev);
     if ((rc = r->dev.bind()) != RUMI_OK || (rc = r->blk.reserve(blkBytes, blkBytes + blkBytes / 4)) != RUMI_OK ||

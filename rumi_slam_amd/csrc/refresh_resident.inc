@@ -25,26 +25,21 @@ constexpr size_t kViolBytes = 64;                      // the counts lie before 
 static_assert(kViolations * 4 <= kViolBytes, "the counts fit their block");
 
 struct ResArgs {
-    CovisRefreshView v;
+    CovisView v;
     const int32_t *ids;            // [n]
     CovisRefreshOut *out;          // [n]
     int32_t *viol;                 // [kViolations]
     int what;
 };
 
-__device__ __forceinline__ const CovisFeatRec *res_block(const ResArgs &a, long long keys) {
-    return reinterpret_cast<const CovisFeatRec *>(a.v.feat + keys - (long long)kCovisFeatKeysOffset);   // feat_layout keeps the key-points there
-}
-
 // The descriptor row of (slot, feature) where it lies; zero, and counted, when the store does not hold it.
 __device__ __forceinline__ void res_fetch_desc(const ResArgs &a, int slot, int feature, uint4 &r0, uint4 &r1) {
     r0 = r1 = make_uint4(0, 0, 0, 0);
-    const int32_t *T = a.v.featTab + slot * kCovisFeatTabWords;
-    const long long keys = *reinterpret_cast<const long long *>(T);
+    const long long keys = a.v.feat_keys(slot);
     if (keys < 0) { atomicAdd(&a.viol[V_NO_FEATURES], 1); return; }
-    if (feature >= T[2]) { atomicAdd(&a.viol[V_FEATURE_RANGE], 1); return; }
-    const CovisFeatRec *R = res_block(a, keys);
-    const uint4 *d = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(R) + R->desc) + 2 * (size_t)feature;
+    if (feature >= a.v.feat_count(slot)) { atomicAdd(&a.viol[V_FEATURE_RANGE], 1); return; }
+    const CovisFeatRec *R = a.v.rec_of_keys(keys);
+    const uint4 *d = rec_arr<uint4>(R, R->desc) + 2 * (size_t)feature;
     r0 = d[0]; r1 = d[1];
 }
 
@@ -52,14 +47,13 @@ __device__ __forceinline__ void res_fetch_desc(const ResArgs &a, int slot, int f
 __device__ __forceinline__ bool res_reference(const ResArgs &a, int ref, int refFeature, float &scaleRef, float &scaleLast) {
     scaleRef = scaleLast = 1.f;
     if (ref < 0) { atomicAdd(&a.viol[V_NO_REFERENCE], 1); return false; }
-    const int32_t *T = a.v.featTab + ref * kCovisFeatTabWords;
-    const long long keys = *reinterpret_cast<const long long *>(T);
+    const long long keys = a.v.feat_keys(ref);
     if (keys < 0) { atomicAdd(&a.viol[V_REF_NO_FEATURES], 1); return false; }
-    if (refFeature >= T[2]) { atomicAdd(&a.viol[V_FEATURE_RANGE], 1); return false; }
-    const CovisFeatRec *R = res_block(a, keys);
-    const int oct = reinterpret_cast<const RumiKeyPoint *>(a.v.feat + keys)[refFeature].octave;
+    if (refFeature >= a.v.feat_count(ref)) { atomicAdd(&a.viol[V_FEATURE_RANGE], 1); return false; }
+    const CovisFeatRec *R = a.v.rec_of_keys(keys);
+    const int oct = a.v.keys_at(keys)[refFeature].octave;
     if (oct < 0 || oct >= R->nlevels) { atomicAdd(&a.viol[V_REF_OCTAVE], 1); return false; }
-    const float *scale = reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(R) + R->scale);
+    const float *scale = rec_arr<float>(R, R->scale);
     scaleRef = scale[oct]; scaleLast = scale[R->nlevels - 1];
     return true;
 }
@@ -67,7 +61,7 @@ __device__ __forceinline__ bool res_reference(const ResArgs &a, int ref, int ref
 // GetCameraCenter() of a slot; zero, and counted, when it was never set.
 __device__ __forceinline__ float4 res_centre(const ResArgs &a, int slot) {
     if (a.v.centre) {
-        const float4 c = *reinterpret_cast<const float4 *>(a.v.centre + slot * kCovisCentreWords);
+        const float4 c = a.v.centre_of(slot);
         if (__float_as_int(c.w) != 0) return c;
     }
     atomicAdd(&a.viol[V_NO_CENTRE], 1);
@@ -104,15 +98,15 @@ __global__ __launch_bounds__(256) void k_refresh_res_group(ResArgs a, const int3
     const int i = live ? list[g] : 0;
     const int p = live ? a.ids[i] : 0;
     int off = 0, L = 0;
-    if (live) { const int2 R = *reinterpret_cast<const int2 *>(a.v.pt + (size_t)p * kCovisPointWords); off = R.x; L = min(R.y, G); }
+    if (live) { const int2 R = a.v.point_obs(p); off = R.x; L = min(R.y, G); }
     const bool has = sub < L, mine = live && sub == 0 && L > 0;  // mine: the point's lane
     const int word = has ? a.v.rows[off + sub] : 0;
-    const int slot = word & kCovisObsSlotMask, feature = word >> kCovisObsSlotBits;
+    const int slot = covis_obs_slot(word), feature = covis_obs_feature(word);
     const int gbase = lane & ~(G - 1);
     const unsigned long long gmask = G == 64 ? ~0ull : (1ull << (G & 63)) - 1;
 
     // ---- the reference key-frame: `observations[pRefKF]` (:495)
-    const int ref = live && a.v.ref ? a.v.ref[p] - 1 : -1;
+    const int ref = live ? a.v.ref_slot(p) : -1;
     const unsigned long long isRef = (__ballot(has && slot == ref) >> gbase) & gmask;        // a row lists a slot at most once
     const int refLane = isRef ? __ffsll((long long)isRef) - 1 : 0;
     const int refLaneFeature = __shfl(feature, gbase + refLane);
@@ -125,7 +119,7 @@ __global__ __launch_bounds__(256) void k_refresh_res_group(ResArgs a, const int3
         float *sU = reinterpret_cast<float *>(sRow);             // [3][256]
         float pos[3] = {0.f, 0.f, 0.f};
         if (live && L > 0) {
-            const float *A = reinterpret_cast<const float *>(a.v.attr + (size_t)p * kCovisAttrWords);
+            const float *A = a.v.attr_pos(p);
             pos[0] = A[0]; pos[1] = A[1]; pos[2] = A[2];
         }
         if (has) {                                               // bad key-frames included (:471-490)
@@ -144,7 +138,7 @@ __global__ __launch_bounds__(256) void k_refresh_res_group(ResArgs a, const int3
     }
 
     if (a.what & RUMI_REFRESH_DESCRIPTOR) {
-        const bool good = has && !(a.v.kf[slot * kCovisKfWords + kCovisKfFlags] & 1);        // :376
+        const bool good = has && !a.v.kf_bad(slot);              // :376
         uint4 r0 = make_uint4(0, 0, 0, 0), r1 = r0;
         if (good) res_fetch_desc(a, slot, feature, r0, r1);
         const unsigned long long gm = (__ballot(good) >> gbase) & gmask;
@@ -178,18 +172,18 @@ __global__ __launch_bounds__(256) void k_refresh_res_block(ResArgs a, const int3
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = list[blockIdx.x];
     const int p = a.ids[i];
-    const int2 P = *reinterpret_cast<const int2 *>(a.v.pt + (size_t)p * kCovisPointWords);
+    const int2 P = a.v.point_obs(p);
     const int off = P.x, L = min(P.y, nAlloc);
     uint4 *sRow = smem;
     int *histAll = reinterpret_cast<int *>(smem + 2 * (size_t)nAlloc), *hist = histAll + wave * kHistStride;
     uint16_t *sPos = reinterpret_cast<uint16_t *>(histAll + 4 * kHistStride);
     const int32_t *row = a.v.rows + off;
 
-    const int ref = a.v.ref ? a.v.ref[p] - 1 : -1;
+    const int ref = a.v.ref_slot(p);
     if (tid == 0) sRefFeature = 0;
     __syncthreads();
     for (int k = tid; k < L; k += 256)
-        if ((row[k] & kCovisObsSlotMask) == ref) sRefFeature = row[k] >> kCovisObsSlotBits;  // at most one writer
+        if (covis_obs_slot(row[k]) == ref) sRefFeature = covis_obs_feature(row[k]);     // at most one writer
     __syncthreads();
     float scaleRef = 1.f, scaleLast = 1.f;
     bool refOk = false;
@@ -197,11 +191,11 @@ __global__ __launch_bounds__(256) void k_refresh_res_block(ResArgs a, const int3
 
     if (a.what & RUMI_REFRESH_NORMAL_DEPTH) {
         float *sU = reinterpret_cast<float *>(smem);             // [3][nAlloc]
-        const float *A = reinterpret_cast<const float *>(a.v.attr + (size_t)p * kCovisAttrWords);
+        const float *A = a.v.attr_pos(p);
         const float pos[3] = {A[0], A[1], A[2]};
         for (int k = tid; k < L; k += 256) {
             float ux, uy, uz;
-            res_unit(pos, res_centre(a, row[k] & kCovisObsSlotMask), ux, uy, uz);
+            res_unit(pos, res_centre(a, covis_obs_slot(row[k])), ux, uy, uz);
             sU[k] = ux; sU[nAlloc + k] = uy; sU[2 * nAlloc + k] = uz;
         }
         __syncthreads();
@@ -219,10 +213,10 @@ __global__ __launch_bounds__(256) void k_refresh_res_block(ResArgs a, const int3
         for (int k0 = 0; k0 < L; k0 += 256) {
             const int k = k0 + tid;
             const int word = k < L ? row[k] : 0;
-            const int slot = word & kCovisObsSlotMask;
-            const bool good = k < L && !(a.v.kf[slot * kCovisKfWords + kCovisKfFlags] & 1);
+            const int slot = covis_obs_slot(word);
+            const bool good = k < L && !a.v.kf_bad(slot);
             uint4 r0 = make_uint4(0, 0, 0, 0), r1 = r0;
-            if (good) res_fetch_desc(a, slot, word >> kCovisObsSlotBits, r0, r1);
+            if (good) res_fetch_desc(a, slot, covis_obs_feature(word), r0, r1);
             const unsigned long long m = __ballot(good);
             if (lane == 0) sCnt[wave] = __popcll(m);
             __syncthreads();
@@ -257,12 +251,12 @@ __global__ __launch_bounds__(256) void k_refresh_res_commit(ResArgs a, int n) {
     for (int v = 0; v < kViolations; v++)
         if (a.viol[v]) return;
     const int p = a.ids[i];
-    if (a.v.pt[(size_t)p * kCovisPointWords + 1] == 0) return;   // an empty row: both members return before they write
+    if (a.v.point_obs_len(p) == 0) return;                       // an empty row: both members return before they write
     const CovisRefreshOut &o = a.out[i];
-    int32_t *A = a.v.attr + (size_t)p * kCovisAttrWords;
+    int32_t *A = a.v.attr_rec(p);
     if ((a.what & RUMI_REFRESH_DESCRIPTOR) && o.bestObs >= 0) {
         const uint4 *D = reinterpret_cast<const uint4 *>(o.desc);
-        uint4 *dst = reinterpret_cast<uint4 *>(A + 8);
+        uint4 *dst = reinterpret_cast<uint4 *>(A + kCovisAttrDesc);
         dst[0] = D[0]; dst[1] = D[1];
     }
     if ((a.what & RUMI_REFRESH_NORMAL_DEPTH) && o.updated) {
@@ -288,8 +282,9 @@ extern "C" int rumi_refresh_map_points_resident(RumiRefresh *r, RumiCovis *c, co
     r->clock.start();
     // ---- the mirror: O(1) words a point, nothing per observation
     r->rowLen.resize((size_t)n_pts);
-    int rc = covis_refresh_check(c, n_pts, ids, wantNormal || writeBack, r->dev.device, E, r->rowLen.data());
-    if (rc != RUMI_OK) return rc;
+    int rc = covis_refresh_check(c, n_pts, ids, wantNormal || writeBack, E, r->rowLen.data());
+    const bool named = r->dev.device >= 0;                   // a handle created without a device learns it when it binds: the rule is asked again then
+    if (rc != RUMI_OK || (rc = covis_same_device(c, r->dev.device, E)) != RUMI_OK) return rc;
     for (auto &b : r->bins) b.clear();
     int maxLen = 0;
     for (int i = 0; i < n_pts; i++) {
@@ -308,10 +303,9 @@ extern "C" int rumi_refresh_map_points_resident(RumiRefresh *r, RumiCovis *c, co
     for (auto &b : r->bins) nBinned += b.size();
 
     // ---- the store's staged edits, then one small block: ids | bin lists
-    CovisRefreshView cv;
-    if ((rc = r->dev.bind()) != RUMI_OK || (rc = covis_refresh_flush(c, r->dev.device, E, &cv)) != RUMI_OK) return rc;
-    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t offList = up((size_t)n_pts * 4), blkBytes = offList + up(nBinned * 4);
+    CovisView cv;
+    if ((rc = r->dev.bind()) != RUMI_OK || (!named && (rc = covis_same_device(c, r->dev.device, E)) != RUMI_OK) || (rc = covis_view(c, 0, &cv)) != RUMI_OK) return rc;
+    const size_t offList = up16((size_t)n_pts * 4), blkBytes = offList + up16(nBinned * 4);
     const size_t outBytes = kViolBytes + (size_t)n_pts * sizeof(CovisRefreshOut);
     if ((rc = r->blk.reserve(blkBytes, blkBytes + blkBytes / 4)) != RUMI_OK || (rc = r->out.reserve(outBytes, outBytes + outBytes / 4)) != RUMI_OK) return rc;
     std::memcpy(r->blk.h, ids, (size_t)n_pts * 4);
@@ -340,7 +334,7 @@ extern "C" int rumi_refresh_map_points_resident(RumiRefresh *r, RumiCovis *c, co
     if (n1) { hipLaunchKernelGGL(k_refresh_res_group<32>, dim3((n1 + 7) / 8), dim3(256), 0, nullptr, a, dList + binOff[1], n1); launches++; }
     if (n2) { hipLaunchKernelGGL(k_refresh_res_group<64>, dim3((n2 + 3) / 4), dim3(256), 0, nullptr, a, dList + binOff[2], n2); launches++; }
     if (n3) {
-        const size_t lds = (size_t)maxLen * 32 + 4 * kHistStride * sizeof(int) + up((size_t)maxLen * 2);     // at most 64 KiB + 4224 + 4096 bytes
+        const size_t lds = (size_t)maxLen * 32 + 4 * kHistStride * sizeof(int) + up16((size_t)maxLen * 2);     // at most 64 KiB + 4224 + 4096 bytes
         if (lds > 64 * 1024) HIP_TRY(raise_lds_limit(reinterpret_cast<const void *>(k_refresh_res_block), lds));
         hipLaunchKernelGGL(k_refresh_res_block, dim3(n3), dim3(256), lds, nullptr, a, dList + binOff[3], maxLen);
         launches++;

@@ -71,6 +71,9 @@ inline int require_device(int *count = nullptr) {
     return RUMI_OK;
 }
 
+// The parts of an upload or result block start 16-byte aligned.
+inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
 // A device block grown on demand.  reserve(need, want): nothing when `need` elements fit, else the old block is released (its contents are not
 // kept) and `want` elements take its place.  After a failed allocation p is null and cap is 0, so the next call allocates again and nothing
 // writes through a stale block.  An empty buffer makes no HIP call, in release() or in the destructor.

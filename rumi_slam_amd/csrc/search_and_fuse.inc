@@ -35,18 +35,18 @@ __global__ __launch_bounds__(256) void k_saf_mark(SafArgs a) {
     if (i >= a.s.nCur) return;
     const int p = a.ids[i];
     if (p < 0) return;
-    const int4 P = *reinterpret_cast<const int4 *>(a.s.pt + (size_t)p * kCovisPointWords);
-    if (P.z & 1) return;                                     // pMP->isBad()
-    const int32_t *obs = a.s.rows + P.x;
+    const CovisPoint P = a.s.v.point(p);
+    if (P.bad()) return;                                     // pMP->isBad()
+    const int32_t *obs = a.s.v.rows + P.obs_off();
     int listed = 0;                                          // observers are distinct slots: each key-frame counts once
-    for (int j = 0; j < P.y; j++) {
-        const uint32_t tag = a.s.slotTag[obs[j] & kCovisObsSlotMask];
+    for (int j = 0; j < P.obs_len(); j++) {
+        const uint32_t tag = a.s.slotTag[covis_obs_slot(obs[j])];
         if ((tag >> 10) != a.s.epoch) continue;
         a.s.fwd[(size_t)(tag & 1023u) * a.s.nCur + i] = kSinListed;            // spAlreadyFound.count(pMP), ORBmatcher.cc:1205
         listed++;
     }
     // counted HERE for the whole call; k_saf_gate passes such pairs over in silence: keep the two in step
-    if (listed < a.s.nT && (!a.s.attr || !P.w)) atomicAdd(&a.s.head[SIN_MISSING], 1);
+    if (listed < a.s.nT && !a.s.v.has_attr(P)) atomicAdd(&a.s.head[SIN_MISSING], 1);
 }
 
 __global__ __launch_bounds__(256) void k_saf_gate(SafArgs a) {
@@ -58,8 +58,8 @@ __global__ __launch_bounds__(256) void k_saf_gate(SafArgs a) {
         const int p = a.ids[i];
         if (a.s.fwd[at] == kSinListed) a.s.fwd[at] = -1;
         else if (p >= 0) {
-            const int4 P = *reinterpret_cast<const int4 *>(a.s.pt + (size_t)p * kCovisPointWords);
-            if (!(P.z & 1) && a.s.attr && P.w) q = sin_query(a.s, k, p);
+            const CovisPoint P = a.s.v.point(p);
+            if (!P.bad() && a.s.v.has_attr(P)) q = sin_query(a.s, k, p);
         }
     }
     sin_push(a.s, q.valid != 0, q, (uint32_t)at);
@@ -105,23 +105,11 @@ __global__ __launch_bounds__(256) void k_saf_emit(SafArgs a) {
     const int first = a.s.blockBase[k * a.s.gx];             // the key-frame's blocks are consecutive in the scan
     int j = a.s.blockBase[k * a.s.gx + blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
     for (int w = 0; w < wave; w++) j += sWave[w];
-    if (f >= 0 && j < a.hitCap) a.hits[j] = make_int4(k, i, f, a.s.rows[a.s.tab[k].mpOff + f]);      // pKF->GetMapPoint(bestIdx) at the call
+    if (f >= 0 && j < a.hitCap) a.hits[j] = make_int4(k, i, f, a.s.v.mp_row(a.s.tab[k])[f]);      // pKF->GetMapPoint(bestIdx) at the call
     if (blockIdx.x == 0 && threadIdx.x == 0) a.perKf[k] = (k + 1 < a.s.nT ? a.s.blockBase[(k + 1) * a.s.gx] : a.s.head[SIN_NREV]) - first;
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-struct SafState {
-    MirrorBuf<uint8_t> up;                                   // the table of SinKF, then the ids
-    MirrorBuf<int32_t> res;                                  // [head SIN_HEAD][per_kf nK][hits: 4 words each]
-    DevBuf<int32_t> dense, cellStart, blocks;                // [nK][nP] best index per pair; the grids; block counts and bases
-    DevBuf<uint16_t> sorted;
-    DevBuf<uint4> work;
-    StageClock clock;
-    float stageMs[3] = {0.f, 0.f, 0.f};
-};
-
-static void saf_destroy(SafState *s) { delete s; }
-
 constexpr int kSafFirstHits = 2048;                          // hits that travel with the head; more take a second copy
 
 }  // namespace rumi
@@ -143,17 +131,13 @@ extern "C" int rumi_search_and_fuse_resident(RumiMatcher *m, RumiCovis *c, const
     if (pairs >= kSinRevBit) { g_lastError = std::string(entry) + ": more pairs than a work item addresses"; return RUMI_E_CAPACITY; }
     const auto t0 = std::chrono::steady_clock::now();
     if (!(th > 0.f) || !std::isfinite(th)) { g_lastError = std::string(entry) + ": th must be positive"; return RUMI_E_INVALID; }
-    bool finite = true;
-    for (int k = 0; k < n_kfs; k++) finite = finite && sin_finite(kfs[k]);
-    if (!finite) { g_lastError = std::string(entry) + ": a pose, camera centre, bound or scale factor that is not finite"; return RUMI_E_INVALID; }
-    for (int k = 0; k < n_kfs; k++)
-        if (!(kfs[k].bounds[2] > kfs[k].bounds[0]) || !(kfs[k].bounds[3] > kfs[k].bounds[1])) { g_lastError = std::string(entry) + ": empty image bounds"; return RUMI_E_INVALID; }
+    if (const char *why = fuse_kfs_check(n_kfs, [&](int k) -> const RumiFuseKF & { return kfs[k]; })) { g_lastError = std::string(entry) + ": " + why; return RUMI_E_INVALID; }
     std::vector<CovisSlotFeatures> info((size_t)n_kfs);
     const bool work = n_kfs > 0 && n_points > 0;
     int rc;
     // everything the host alone can refuse is refused before the matcher handle is read: the slots first, then the device both live on
-    if ((rc = covis_features_check(c, n_kfs, kf_slots, -1, entry, info.data())) != RUMI_OK) return rc;
-    if (work && (rc = covis_features_check(c, n_kfs, kf_slots, m->device, entry, info.data())) != RUMI_OK) return rc;
+    if ((rc = covis_features_check(c, n_kfs, kf_slots, entry, info.data())) != RUMI_OK) return rc;
+    if (work && (rc = covis_same_device(c, m->device, entry)) != RUMI_OK) return rc;
     size_t feats = 0;
     for (int k = 0; k < n_kfs; k++) {
         if (info[k].n > m->maxFeat) { g_lastError = std::string(entry) + ": a key-frame exceeds the matcher's max_features"; return RUMI_E_CAPACITY; }
@@ -165,12 +149,9 @@ extern "C" int rumi_search_and_fuse_resident(RumiMatcher *m, RumiCovis *c, const
         return RUMI_OK;
     }
     HIP_TRY(hipSetDevice(m->device));
-    MatcherExt *ext = &m->ext;
-    if (!ext->state) { ext->state = new NewPtsState(); ext->destroy = newpts_destroy; }
-    NewPtsState *np = static_cast<NewPtsState *>(ext->state);
-    if (!np->sin) np->sin = new SinState();
-    if (!np->saf) np->saf = new SafState();
-    SafState *s = np->saf;
+    NewPtsState *np = newpts_state(m);
+    SinState *sin = made(np->sin);                           // the stamped tables and their epoch
+    SafState *s = made(np->saf);
     s->clock.start(); s->clock.t[0] = t0;
 
     const size_t tabBytes = (size_t)n_kfs * sizeof(SinKF), upBytes = tabBytes + (size_t)n_points * 4;
@@ -182,24 +163,18 @@ extern "C" int rumi_search_and_fuse_resident(RumiMatcher *m, RumiCovis *c, const
         (rc = s->cellStart.reserve((size_t)n_kfs * (kGridCells + 1), (size_t)n_kfs * (kGridCells + 1))) != RUMI_OK ||
         (rc = s->blocks.reserve(2 * (size_t)nBlocks, 2 * (size_t)nBlocks)) != RUMI_OK || (rc = s->work.reserve(pairs + 1, pairs + pairs / 4 + 1)) != RUMI_OK)
         return rc;
-    CovisFeatureView fv;
+    CovisView fv;
     s->clock.mark();
-    if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
+    if ((rc = covis_view(c, 0, &fv)) != RUMI_OK) return rc;
     for (int i = 0; i < n_points; i++)
         if (point_ids[i] >= fv.maxPoints) { g_lastError = std::string(entry) + ": a point id at or above the store's point capacity"; return RUMI_E_INVALID; }
-    if ((rc = sin_next_epoch(np->sin, fv)) != RUMI_OK) return rc;
+    if ((rc = sin_next_epoch(sin, fv)) != RUMI_OK) return rc;
 
     SinKF *tab = reinterpret_cast<SinKF *>(s->up.h);
     int32_t sortedOff = 0;
     for (int k = 0; k < n_kfs; k++) {
-        const RumiFuseKF &P = kfs[k];
-        SinKF &R = tab[k];
-        std::memset(&R, 0, sizeof R);
-        R.block = info[k].block; R.mpOff = info[k].mpOff; R.n = info[k].n; R.sortedOff = sortedOff; R.slot = kf_slots[k];
-        std::memcpy(R.T, P.Tcw7, 28); std::memcpy(R.Ow, P.Ow, 12); std::memcpy(R.bounds, P.bounds, 16);
-        R.logSf = P.log_scale_factor;
-        R.wInv = (float)kGridCols / (float)(P.bounds[2] - P.bounds[0]);      // Frame.cc:322-323, as upload_frame forms them
-        R.hInv = (float)kGridRows / (float)(P.bounds[3] - P.bounds[1]);
+        sin_kf_grid(&tab[k], covis_slot_ref(info[k]), kf_slots[k], kfs[k].bounds, sortedOff);
+        sin_kf_pose(&tab[k], kfs[k]);
         sortedOff += info[k].n;
     }
     std::memcpy(s->up.h + tabBytes, point_ids, (size_t)n_points * 4);
@@ -208,9 +183,9 @@ extern "C" int rumi_search_and_fuse_resident(RumiMatcher *m, RumiCovis *c, const
     HIP_TRY(hipMemsetAsync(dRes, 0, SIN_HEAD * 4, nullptr));
     HIP_TRY(hipMemsetAsync(s->dense.p, 0xFF, pairs * 4, nullptr));
     SafArgs a{};
-    a.s.tab = reinterpret_cast<const SinKF *>(s->up.d); a.s.feat = fv.feat; a.s.rows = fv.rows; a.s.pt = fv.pt; a.s.attr = fv.attr;
-    a.s.nT = n_kfs; a.s.nCur = n_points; a.s.gx = gx; a.s.curSlot = -1; a.s.epoch = np->sin->epoch; a.s.th = th;
-    a.s.slotTag = np->sin->slotTag.p; a.s.claim = np->sin->claim.p; a.s.sorted = s->sorted.p; a.s.cellStart = s->cellStart.p;
+    a.s.tab = reinterpret_cast<const SinKF *>(s->up.d); a.s.v = fv;
+    a.s.nT = n_kfs; a.s.nCur = n_points; a.s.gx = gx; a.s.curSlot = -1; a.s.epoch = sin->epoch; a.s.th = th;
+    a.s.slotTag = sin->slotTag.p; a.s.claim = sin->claim.p; a.s.sorted = s->sorted.p; a.s.cellStart = s->cellStart.p;
     a.s.blockCount = s->blocks.p; a.s.blockBase = s->blocks.p + nBlocks; a.s.work = s->work.p;
     a.s.head = dRes; a.s.fwd = s->dense.p;
     a.ids = reinterpret_cast<const int32_t *>(s->up.d + tabBytes);
@@ -251,10 +226,10 @@ extern "C" int rumi_search_and_fuse_resident(RumiMatcher *m, RumiCovis *c, const
 }
 
 extern "C" int rumi_search_and_fuse_stage_ms(const RumiMatcher *m, float *out3) {
-    if (!m || !out3 || !m->ext.state || !static_cast<const NewPtsState *>(m->ext.state)->saf) {
+    if (!out3 || !newpts_peek(m) || !newpts_peek(m)->saf) {
         g_lastError = "rumi_search_and_fuse_stage_ms: no SearchAndFuse call precedes on this matcher";
         return RUMI_E_INVALID;
     }
-    std::memcpy(out3, static_cast<const NewPtsState *>(m->ext.state)->saf->stageMs, 12);
+    std::memcpy(out3, newpts_peek(m)->saf->stageMs, 12);
     return RUMI_OK;
 }

@@ -1,6 +1,6 @@
 // The search half of LocalMapping::SearchInNeighbors (R/lib_src/LocalMapping.cc:649-743) for every target key-frame in one call, behind
 // rumi_search_in_neighbors_resident (include/rumi_mapping.h).  Included at the end of mapping.hip; everything is read where the covisibility
-// store keeps it (ResidentView's sources: the feature arena, the row arena, the point and attribute records).
+// store keeps it, through a CovisView (covis_view.h).
 //
 // What the device computes is the search of ORBmatcher::Fuse (ORBmatcher.cc:1037-1174) on the map as it stands at the call: bestIdx for a
 // (key-frame, point) pair reads the point's position, normal, distance range and descriptor and the key-frame's pose, key-points,
@@ -26,12 +26,10 @@ namespace rumi {
 
 static_assert(sizeof(RumiKeyPoint) == 28, "k_sin_grid reads x, y seven floats apart");
 
-struct SinKF {                         // one key-frame of a call; entry 0 is the current one
-    int64_t block;                     // byte offset of its CovisFeatRec in the feature arena
-    int32_t mpOff, n;                  // its mp row in the row arena, its length (= feature count)
+struct SinKF : CovisSlotRef {          // one key-frame of a call; entry 0 is the current one
     int32_t sortedOff, slot;           // first entry of its sorted feature indices; its slot in the store
     float T[7], Ow[3], bounds[4], logSf, wInv, hInv;
-    float pad[5];
+    float pad[4];
 };
 static_assert(sizeof(SinKF) % 16 == 0, "a table entry");
 
@@ -41,7 +39,7 @@ constexpr int kSinLanes = 16;          // lanes per surviving pair in k_sin_sear
 constexpr uint32_t kSinRevBit = 0x80000000u;
 
 struct SinArgs {
-    const SinKF *tab; const uint8_t *feat; const int32_t *rows, *pt, *attr;
+    const SinKF *tab; CovisView v;
     int nT, nCur, gx, curSlot;
     uint32_t epoch;
     float th;
@@ -52,16 +50,14 @@ struct SinArgs {
     int32_t *head, *fwd, *revPoint, *revBest;
 };
 
-__device__ __forceinline__ const CovisFeatRec *sin_rec(const SinArgs &a, const SinKF &F) { return reinterpret_cast<const CovisFeatRec *>(a.feat + F.block); }
 __device__ __forceinline__ unsigned long long sin_claim(const SinArgs &a, int t, int i) {
     return ((unsigned long long)a.epoch << 32) | (0x7FFFFFFFu - (((uint32_t)t << 16) | (uint32_t)i));
 }
 
 __global__ __launch_bounds__(1024) void k_sin_grid(SinArgs a, uint16_t *__restrict__ sorted, int32_t *__restrict__ cellStart) {
     const SinKF F = a.tab[blockIdx.x];
-    const CovisFeatRec *R = sin_rec(a, F);
     if (threadIdx.x == 0) a.slotTag[F.slot] = (a.epoch << 10) | blockIdx.x;
-    grid_build_xy<7>(F.n, reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(R) + R->keys), F.bounds[0], F.bounds[1], F.wInv, F.hInv,
+    grid_build_xy<7>(F.n, reinterpret_cast<const float *>(a.v.key_frame(F).keys()), F.bounds[0], F.bounds[1], F.wInv, F.hInv,
                      sorted + F.sortedOff, cellStart + (size_t)blockIdx.x * (kGridCells + 1));
 }
 
@@ -69,15 +65,15 @@ __global__ __launch_bounds__(256) void k_sin_mark(SinArgs a) {
     const int k = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     const SinKF &F = a.tab[k];
     if (i >= F.n) return;
-    const int p = a.rows[F.mpOff + i];
+    const int p = a.v.mp_row(F)[i];
     if (p < 0) return;
-    const int4 P = *reinterpret_cast<const int4 *>(a.pt + (size_t)p * kCovisPointWords);
-    if (P.z & 1) return;                                     // pMP->isBad()
-    const int32_t *obs = a.rows + P.x;
+    const CovisPoint P = a.v.point(p);
+    if (P.bad()) return;                                     // pMP->isBad()
+    const int32_t *obs = a.v.rows + P.obs_off();
     if (k == 0) {
         int listed = 0;                                      // observers are distinct slots: each target counts once
-        for (int j = 0; j < P.y; j++) {
-            const uint32_t tag = a.slotTag[obs[j] & kCovisObsSlotMask];
+        for (int j = 0; j < P.obs_len(); j++) {
+            const uint32_t tag = a.slotTag[covis_obs_slot(obs[j])];
             if ((tag >> 10) != a.epoch || (tag & 1023u) == 0) continue;
             a.fwd[(size_t)((tag & 1023u) - 1) * a.nCur + i] = kSinListed;       // pMP->IsInKeyFrame(pKFi)
             listed++;
@@ -85,13 +81,13 @@ __global__ __launch_bounds__(256) void k_sin_mark(SinArgs a) {
         // A point that some target would search and that has no attributes is counted HERE for the forward pass (k_sin_fwd_gate passes such
         // pairs over in silence: keep the two in step), and the call is refused.  Its id is claimed above every reverse claim, so that a
         // store whose observer row does not (yet) list the current slot cannot have k_sin_rev_emit count the same point again.
-        if (listed < a.nT && (!a.attr || !P.w)) {
+        if (listed < a.nT && !a.v.has_attr(P)) {
             atomicAdd(&a.head[SIN_MISSING], 1);
             atomicMax(&a.claim[p], ((unsigned long long)a.epoch << 32) | 0xFFFFFFFFull);
         }
     } else {
         bool inCur = false;                                  // pMP->IsInKeyFrame(mpCurrentKeyFrame), ORBmatcher.cc:1054 in the reverse pass
-        for (int j = 0; j < P.y; j++) inCur = inCur || (obs[j] & kCovisObsSlotMask) == a.curSlot;
+        for (int j = 0; j < P.obs_len(); j++) inCur = inCur || covis_obs_slot(obs[j]) == a.curSlot;
         if (!inCur) atomicMax(&a.claim[p], sin_claim(a, k - 1, i));
     }
 }
@@ -100,7 +96,7 @@ __global__ __launch_bounds__(256) void k_sin_mark(SinArgs a) {
 __device__ __forceinline__ int sin_winner(const SinArgs &a, int t, int i) {
     const SinKF &F = a.tab[1 + t];
     if (i >= F.n) return -1;
-    const int p = a.rows[F.mpOff + i];
+    const int p = a.v.mp_row(F)[i];
     return p >= 0 && a.claim[p] == sin_claim(a, t, i) ? p : -1;
 }
 
@@ -143,12 +139,12 @@ __device__ __forceinline__ void sin_push(const SinArgs &a, bool valid, const Que
 
 __device__ __forceinline__ Query sin_query(const SinArgs &a, int k, int p) {
     const SinKF &F = a.tab[k];
-    const CovisFeatRec *R = sin_rec(a, F);
-    const float4 *A = reinterpret_cast<const float4 *>(a.attr + (size_t)p * kCovisAttrWords);
-    const float4 lo = A[0], hi = A[1];
-    const float pos[3] = {lo.x, lo.y, lo.z}, nrm[3] = {lo.w, hi.x, hi.y};
-    return sim3_query(pos, nrm, hi.z, hi.w, F.T, R->K, F.Ow, reinterpret_cast<const float *>(reinterpret_cast<const uint8_t *>(R) + R->scale), R->nlevels,
-                      F.logSf, a.th, 0, F.bounds[0], F.bounds[1], F.bounds[2], F.bounds[3]);
+    const CovisKeyFrame K = a.v.key_frame(F);
+    const CovisAttrGeom A = a.v.attr_geom(p);
+    float pos[3], nrm[3];
+    A.pos(pos); A.normal(nrm);
+    return sim3_query(pos, nrm, A.min_dist(), A.max_dist(), F.T, K.K(), F.Ow, K.scale(), K.nlevels(), F.logSf, a.th, 0, F.bounds[0], F.bounds[1], F.bounds[2],
+                      F.bounds[3]);
 }
 
 __global__ __launch_bounds__(256) void k_sin_rev_emit(SinArgs a) {
@@ -163,7 +159,7 @@ __global__ __launch_bounds__(256) void k_sin_rev_emit(SinArgs a) {
     Query q{};
     if (p >= 0) {
         a.revPoint[j] = p; a.revBest[j] = -1;
-        if (a.attr && a.pt[(size_t)p * kCovisPointWords + 3]) q = sin_query(a, 0, p);
+        if (a.v.has_attr(p)) q = sin_query(a, 0, p);
         else atomicAdd(&a.head[SIN_MISSING], 1);
     }
     sin_push(a, q.valid != 0, q, kSinRevBit | (uint32_t)j);
@@ -175,11 +171,11 @@ __global__ __launch_bounds__(256) void k_sin_fwd_gate(SinArgs a) {
     size_t at = 0;
     if (i < a.nCur) {
         at = (size_t)t * a.nCur + i;
-        const int p = a.rows[a.tab[0].mpOff + i];
+        const int p = a.v.mp_row(a.tab[0])[i];
         if (a.fwd[at] == kSinListed) a.fwd[at] = -1;
         else if (p >= 0) {
-            const int4 P = *reinterpret_cast<const int4 *>(a.pt + (size_t)p * kCovisPointWords);
-            if (!(P.z & 1) && a.attr && P.w) q = sin_query(a, 1 + t, p);
+            const CovisPoint P = a.v.point(p);
+            if (!P.bad() && a.v.has_attr(P)) q = sin_query(a, 1 + t, p);
         }
     }
     sin_push(a, q.valid != 0, q, (uint32_t)at);
@@ -193,13 +189,12 @@ __global__ __launch_bounds__(256) void k_sin_fwd_gate(SinArgs a) {
 template <bool REPROJ>
 __device__ __forceinline__ void sin_walk(const SinArgs &a, int k, int p, const uint4 &item, int sub, uint32_t &bestKey, int &bestIdx) {
     const SinKF &F = a.tab[k];
-    const uint8_t *R8 = a.feat + F.block;
-    const CovisFeatRec *R = reinterpret_cast<const CovisFeatRec *>(R8);
-    const uint8_t *desc = R8 + R->desc;
-    const float *scale = reinterpret_cast<const float *>(R8 + R->scale);
-    const GridView G{reinterpret_cast<const RumiKeyPoint *>(R8 + R->keys), a.sorted + F.sortedOff, a.cellStart + (size_t)k * (kGridCells + 1),
-                     F.bounds[0], F.bounds[1], F.wInv, F.hInv};
-    const uint4 q0 = ld16_dword(a.attr + (size_t)p * kCovisAttrWords + 8), q1 = ld16_dword(a.attr + (size_t)p * kCovisAttrWords + 12);
+    const CovisKeyFrame K = a.v.key_frame(F);
+    const uint8_t *desc = K.desc();
+    const float *scale = K.scale();
+    const GridView G{K.keys(), a.sorted + F.sortedOff, a.cellStart + (size_t)k * (kGridCells + 1), F.bounds[0], F.bounds[1], F.wInv, F.hInv};
+    uint4 q0, q1;
+    a.v.attr_desc(p, q0, q1);
     const float u = __uint_as_float(item.x), v = __uint_as_float(item.y);
     const int maxLevel = (int)item.w;
     walk_window<kSinLanes>(G, u, v, a.th * scale[maxLevel], maxLevel - 1, maxLevel, sub, [&](int idx, const RumiKeyPoint &kp, int place) {
@@ -233,7 +228,7 @@ __global__ __launch_bounds__(256) void k_sin_search(SinArgs a) {
             const uint4 item = a.work[w];
             int k, p;
             if (item.z & kSinRevBit) { const int j = (int)(item.z & ~kSinRevBit); k = 0; p = a.revPoint[j]; out = a.revBest + j; }
-            else { const int t = (int)(item.z / (uint32_t)a.nCur), i = (int)(item.z - (uint32_t)t * (uint32_t)a.nCur); k = 1 + t; p = a.rows[a.tab[0].mpOff + i]; out = a.fwd + item.z; }
+            else { const int t = (int)(item.z / (uint32_t)a.nCur), i = (int)(item.z - (uint32_t)t * (uint32_t)a.nCur); k = 1 + t; p = a.v.mp_row(a.tab[0])[i]; out = a.fwd + item.z; }
             sin_walk<true>(a, k, p, item, sub, bestKey, bestIdx);
         }
         sin_group_min(bestKey, bestIdx);
@@ -242,30 +237,38 @@ __global__ __launch_bounds__(256) void k_sin_search(SinArgs a) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-struct SinState {
-    MirrorBuf<uint8_t> tab;                                  // the table of SinKF
-    MirrorBuf<int32_t> res;                                  // [head SIN_HEAD][fwd nT * nCur][revPoint E][revBest E], E = the targets' row entries
-    DevBuf<uint16_t> sorted; DevBuf<int32_t> cellStart, blocks;
-    DevBuf<uint32_t> slotTag; DevBuf<unsigned long long> claim;
-    DevBuf<uint4> work;
-    uint32_t epoch = 0;
-    StageClock clock;
-    float stageMs[3] = {0.f, 0.f, 0.f};
-};
-
-static void sin_destroy(SinState *s) { delete s; }
-
 }  // namespace rumi
 
-static bool sin_finite(const RumiFuseKF &k) {
-    const float *f = reinterpret_cast<const float *>(&k);
-    for (size_t i = 0; i < sizeof(RumiFuseKF) / 4; i++) if (!std::isfinite(f[i])) return false;
-    return true;
+// The RumiFuseKF of a call, k = 0 .. n - 1 through at(k): every float finite, then image bounds that are not empty.  What is wrong, or nullptr.
+template <class At> static const char *fuse_kfs_check(int n, At at) {
+    for (int k = 0; k < n; k++) {
+        const float *f = reinterpret_cast<const float *>(&at(k));
+        for (size_t i = 0; i < sizeof(RumiFuseKF) / 4; i++) if (!std::isfinite(f[i])) return "a pose, camera centre, bound or scale factor that is not finite";
+    }
+    for (int k = 0; k < n; k++) {
+        const RumiFuseKF &P = at(k);
+        if (!(P.bounds[2] > P.bounds[0]) || !(P.bounds[3] > P.bounds[1])) return "empty image bounds";
+    }
+    return nullptr;
+}
+
+// The grid entry of a key-frame: its slot record, its bounds and the cell sizes as upload_frame forms them (Frame.cc:322-323); the rest zero.
+static void sin_kf_grid(rumi::SinKF *R, const rumi::CovisSlotRef &ref, int32_t slot, const float *bounds, int32_t sortedOff) {
+    std::memset(R, 0, sizeof *R);
+    static_cast<rumi::CovisSlotRef &>(*R) = ref; R->sortedOff = sortedOff; R->slot = slot;
+    std::memcpy(R->bounds, bounds, 16);
+    R->wInv = (float)rumi::kGridCols / (float)(bounds[2] - bounds[0]);
+    R->hInv = (float)rumi::kGridRows / (float)(bounds[3] - bounds[1]);
+}
+// ... and the pose it is searched under (SearchInNeighbors, SearchAndFuse; a Sim3 projection job carries its own).
+static void sin_kf_pose(rumi::SinKF *R, const RumiFuseKF &P) {
+    std::memcpy(R->T, P.Tcw7, 28); std::memcpy(R->Ow, P.Ow, 12);
+    R->logSf = P.log_scale_factor;
 }
 
 // The two stamped tables: a value of another epoch reads as "not of this call"; a new or outgrown table, or a wrapped epoch, starts from zero.
 // Shared with rumi_search_and_fuse_resident (search_and_fuse.inc), whose calls take their epochs from the same counter.
-static int sin_next_epoch(rumi::SinState *s, const rumi::CovisFeatureView &fv) {
+static int sin_next_epoch(rumi::SinState *s, const rumi::CovisView &fv) {
     int rc;
     const bool fresh = (size_t)fv.maxKf > s->slotTag.cap || (size_t)fv.maxPoints > s->claim.cap || s->epoch >= (1u << 22) - 1;
     if ((rc = s->slotTag.reserve((size_t)fv.maxKf, (size_t)fv.maxKf)) != RUMI_OK || (rc = s->claim.reserve((size_t)fv.maxPoints, (size_t)fv.maxPoints)) != RUMI_OK) return rc;
@@ -293,21 +296,16 @@ extern "C" int rumi_search_in_neighbors_resident(RumiMatcher *m, RumiCovis *c, i
     }
     const auto t0 = std::chrono::steady_clock::now();
     if (!(th > 0.f) || !std::isfinite(th)) { g_lastError = std::string(entry) + ": th must be positive"; return RUMI_E_INVALID; }
-    bool finite = sin_finite(*cur);
-    for (int k = 0; k < n_targets; k++) finite = finite && sin_finite(targets[k]);
-    if (!finite) { g_lastError = std::string(entry) + ": a pose, camera centre, bound or scale factor that is not finite"; return RUMI_E_INVALID; }
-    for (int k = 0; k <= n_targets; k++) {
-        const RumiFuseKF &P = k ? targets[k - 1] : *cur;
-        if (!(P.bounds[2] > P.bounds[0]) || !(P.bounds[3] > P.bounds[1])) { g_lastError = std::string(entry) + ": empty image bounds"; return RUMI_E_INVALID; }
-    }
+    const auto kfAt = [&](int k) -> const RumiFuseKF & { return k ? targets[k - 1] : *cur; };
+    if (const char *why = fuse_kfs_check(n_targets + 1, kfAt)) { g_lastError = std::string(entry) + ": " + why; return RUMI_E_INVALID; }
     std::vector<int32_t> slots((size_t)n_targets + 1);
     std::vector<CovisSlotFeatures> info((size_t)n_targets + 1);
     slots[0] = cur_slot;
     for (int k = 0; k < n_targets; k++) slots[1 + k] = target_slots[k];
     int rc;
     // everything the host alone can refuse is refused before the matcher handle is read: the slots first, then the device both live on
-    if ((rc = covis_features_check(c, n_targets + 1, slots.data(), -1, entry, info.data())) != RUMI_OK) return rc;
-    if (n_targets > 0 && (rc = covis_features_check(c, n_targets + 1, slots.data(), m->device, entry, info.data())) != RUMI_OK) return rc;
+    if ((rc = covis_features_check(c, n_targets + 1, slots.data(), entry, info.data())) != RUMI_OK) return rc;
+    if (n_targets > 0 && (rc = covis_same_device(c, m->device, entry)) != RUMI_OK) return rc;
     size_t E = 0, feats = 0;
     int maxN = 1;
     for (int k = 0; k <= n_targets; k++) {
@@ -320,11 +318,7 @@ extern "C" int rumi_search_in_neighbors_resident(RumiMatcher *m, RumiCovis *c, i
     const size_t pairs = (size_t)n_targets * nCur;
     if (pairs >= kSinRevBit || E >= kSinRevBit) { g_lastError = "SearchInNeighbors: more pairs than a work item addresses"; return RUMI_E_CAPACITY; }
     HIP_TRY(hipSetDevice(m->device));
-    MatcherExt *ext = &m->ext;
-    if (!ext->state) { ext->state = new NewPtsState(); ext->destroy = newpts_destroy; }
-    NewPtsState *np = static_cast<NewPtsState *>(ext->state);
-    if (!np->sin) np->sin = new SinState();
-    SinState *s = np->sin;
+    SinState *s = made(newpts_state(m)->sin);
     s->clock.start(); s->clock.t[0] = t0;
 
     const size_t tabBytes = (size_t)(n_targets + 1) * sizeof(SinKF), resWords = SIN_HEAD + pairs + 2 * E;
@@ -334,22 +328,16 @@ extern "C" int rumi_search_in_neighbors_resident(RumiMatcher *m, RumiCovis *c, i
         (rc = s->cellStart.reserve((size_t)(n_targets + 1) * (kGridCells + 1), (size_t)(n_targets + 1) * (kGridCells + 1))) != RUMI_OK ||
         (rc = s->blocks.reserve(2 * (size_t)nBlocks, 2 * (size_t)nBlocks)) != RUMI_OK || (rc = s->work.reserve(pairs + E + 1, pairs + E + (pairs + E) / 4 + 1)) != RUMI_OK)
         return rc;
-    CovisFeatureView fv;
+    CovisView fv;
     s->clock.mark();
-    if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
+    if ((rc = covis_view(c, 0, &fv)) != RUMI_OK) return rc;
     if ((rc = sin_next_epoch(s, fv)) != RUMI_OK) return rc;
 
     SinKF *tab = reinterpret_cast<SinKF *>(s->tab.h);
     int32_t sortedOff = 0;
     for (int k = 0; k <= n_targets; k++) {
-        const RumiFuseKF &P = k ? targets[k - 1] : *cur;
-        SinKF &R = tab[k];
-        std::memset(&R, 0, sizeof R);
-        R.block = info[k].block; R.mpOff = info[k].mpOff; R.n = info[k].n; R.sortedOff = sortedOff; R.slot = slots[k];
-        std::memcpy(R.T, P.Tcw7, 28); std::memcpy(R.Ow, P.Ow, 12); std::memcpy(R.bounds, P.bounds, 16);
-        R.logSf = P.log_scale_factor;
-        R.wInv = (float)kGridCols / (float)(P.bounds[2] - P.bounds[0]);      // Frame.cc:322-323, as upload_frame forms them
-        R.hInv = (float)kGridRows / (float)(P.bounds[3] - P.bounds[1]);
+        sin_kf_grid(&tab[k], covis_slot_ref(info[k]), slots[k], kfAt(k).bounds, sortedOff);
+        sin_kf_pose(&tab[k], kfAt(k));
         sortedOff += info[k].n;
     }
     HIP_TRY(hipMemcpyAsync(s->tab.d, s->tab.h, tabBytes, hipMemcpyHostToDevice, nullptr));
@@ -357,7 +345,7 @@ extern "C" int rumi_search_in_neighbors_resident(RumiMatcher *m, RumiCovis *c, i
     HIP_TRY(hipMemsetAsync(dRes, 0, SIN_HEAD * 4, nullptr));
     if (pairs) HIP_TRY(hipMemsetAsync(dRes + SIN_HEAD, 0xFF, pairs * 4, nullptr));
     SinArgs a{};
-    a.tab = reinterpret_cast<const SinKF *>(s->tab.d); a.feat = fv.feat; a.rows = fv.rows; a.pt = fv.pt; a.attr = fv.attr;
+    a.tab = reinterpret_cast<const SinKF *>(s->tab.d); a.v = fv;
     a.nT = n_targets; a.nCur = nCur; a.gx = gx; a.curSlot = cur_slot; a.epoch = s->epoch; a.th = th;
     a.slotTag = s->slotTag.p; a.claim = s->claim.p; a.sorted = s->sorted.p; a.cellStart = s->cellStart.p;
     a.blockCount = s->blocks.p; a.blockBase = s->blocks.p + nBlocks; a.work = s->work.p;
@@ -392,10 +380,10 @@ extern "C" int rumi_search_in_neighbors_resident(RumiMatcher *m, RumiCovis *c, i
 }
 
 extern "C" int rumi_search_in_neighbors_stage_ms(const RumiMatcher *m, float *out3) {
-    if (!m || !out3 || !m->ext.state || !static_cast<const NewPtsState *>(m->ext.state)->sin) {
+    if (!out3 || !newpts_peek(m) || !newpts_peek(m)->sin) {
         g_lastError = "rumi_search_in_neighbors_stage_ms: no SearchInNeighbors call precedes on this matcher";
         return RUMI_E_INVALID;
     }
-    std::memcpy(out3, static_cast<const NewPtsState *>(m->ext.state)->sin->stageMs, 12);
+    std::memcpy(out3, newpts_peek(m)->sin->stageMs, 12);
     return RUMI_OK;
 }

@@ -31,16 +31,15 @@
 
 namespace rumi {
 
-struct S3pJob {                        // one job of a call
-    int64_t block;                     // byte offset of the key-frame's CovisFeatRec in the feature arena
-    int32_t n, grid;                   // its feature count; which grid of the call is its
+struct S3pJob : CovisSlotRef {         // one job of a call: its key-frame, then
+    int32_t grid;                      // which grid of the call is its
     int32_t sortedOff;                 // first entry of that grid's sorted feature indices
     int32_t pointStart, pointCount;    // its list in the call's ids
     int32_t pairBase, rowStart;        // its first (job, entry) pair; its row in the matched block
     int32_t variant;                   // 0: mpCamera->project (:372-471), 1: explicit 1 / z (:473-579)
     float th, thrF;                    // window factor; TH_LOW * ratio, compared in float as :464 / :572 do
     float T[7], Ow[3], bounds[4], logSf, wInv, hInv;
-    float pad[3];
+    float pad[1];
 };
 static_assert(sizeof(S3pJob) % 16 == 0, "a table entry");
 
@@ -60,17 +59,16 @@ __global__ __launch_bounds__(256) void k_s3p_gate(S3pArgs a) {
     if (i < J.pointCount) {
         const int p = a.ids[J.pointStart + i];
         if (p >= 0) {
-            const int4 P = *reinterpret_cast<const int4 *>(a.s.pt + (size_t)p * kCovisPointWords);
-            if (!(P.z & 1)) {                                // pMP->isBad(), :396 / :498
-                if (!a.s.attr || !P.w) atomicAdd(&a.s.head[SIN_MISSING], 1);
+            const CovisPoint P = a.s.v.point(p);
+            if (!P.bad()) {                                  // pMP->isBad(), :396 / :498
+                if (!a.s.v.has_attr(P)) atomicAdd(&a.s.head[SIN_MISSING], 1);
                 else {
-                    const uint8_t *R8 = a.s.feat + J.block;
-                    const CovisFeatRec *R = reinterpret_cast<const CovisFeatRec *>(R8);
-                    const float4 *A = reinterpret_cast<const float4 *>(a.s.attr + (size_t)p * kCovisAttrWords);
-                    const float4 lo = A[0], hi = A[1];
-                    const float pos[3] = {lo.x, lo.y, lo.z}, nrm[3] = {lo.w, hi.x, hi.y};
-                    q = sim3_query(pos, nrm, hi.z, hi.w, J.T, R->K, J.Ow, reinterpret_cast<const float *>(R8 + R->scale), R->nlevels, J.logSf, J.th,
-                                   J.variant, J.bounds[0], J.bounds[1], J.bounds[2], J.bounds[3]);
+                    const CovisKeyFrame K = a.s.v.key_frame(J);
+                    const CovisAttrGeom A = a.s.v.attr_geom(p);
+                    float pos[3], nrm[3];
+                    A.pos(pos); A.normal(nrm);
+                    q = sim3_query(pos, nrm, A.min_dist(), A.max_dist(), J.T, K.K(), J.Ow, K.scale(), K.nlevels(), J.logSf, J.th, J.variant, J.bounds[0],
+                                   J.bounds[1], J.bounds[2], J.bounds[3]);
                     q.maxLevel |= (int)blockIdx.y << 8;      // the item's last word: level (predict_scale's bits) | job << 8
                 }
             }
@@ -96,15 +94,14 @@ __global__ __launch_bounds__(256) void k_s3p_walk(S3pArgs a) {
             pair = item.z;
             const S3pJob &J = a.jobs[item.w >> 8];
             const int p = a.ids[J.pointStart + (int)(pair - (uint32_t)J.pairBase)];
-            const uint8_t *R8 = a.s.feat + J.block;
-            const CovisFeatRec *R = reinterpret_cast<const CovisFeatRec *>(R8);
-            const uint8_t *desc = R8 + R->desc;
-            const GridView G{reinterpret_cast<const RumiKeyPoint *>(R8 + R->keys), a.s.sorted + J.sortedOff, a.s.cellStart + (size_t)J.grid * (kGridCells + 1),
-                             J.bounds[0], J.bounds[1], J.wInv, J.hInv};
-            const uint4 q0 = ld16_dword(a.s.attr + (size_t)p * kCovisAttrWords + 8), q1 = ld16_dword(a.s.attr + (size_t)p * kCovisAttrWords + 12);
+            const CovisKeyFrame K = a.s.v.key_frame(J);
+            const uint8_t *desc = K.desc();
+            const GridView G{K.keys(), a.s.sorted + J.sortedOff, a.s.cellStart + (size_t)J.grid * (kGridCells + 1), J.bounds[0], J.bounds[1], J.wInv, J.hInv};
+            uint4 q0, q1;
+            a.s.v.attr_desc(p, q0, q1);
             const int maxLevel = (int)(item.w & 255u);
             const int listAt = FILL ? a.s.blockBase[pair] : 0, listLen = FILL ? a.s.blockCount[pair] : 0;
-            walk_window<kSinLanes>(G, __uint_as_float(item.x), __uint_as_float(item.y), J.th * reinterpret_cast<const float *>(R8 + R->scale)[maxLevel],
+            walk_window<kSinLanes>(G, __uint_as_float(item.x), __uint_as_float(item.y), J.th * K.scale()[maxLevel],
                                    maxLevel - 1, maxLevel, sub, [&](int idx, const RumiKeyPoint &, int place) {
                 const int d = hamming256(q0, q1, ld16_dword(desc + (size_t)idx * 32), ld16_dword(desc + (size_t)idx * 32 + 16));
                 if (!((float)d <= J.thrF)) return;                                  // the cut (above)
@@ -195,19 +192,6 @@ __global__ __launch_bounds__(kS3pResolveThreads) void k_s3p_resolve(S3pArgs a) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-struct S3pState {
-    MirrorBuf<uint8_t> up;                                   // the grids' SinKF, the jobs' S3pJob, the ids
-    MirrorBuf<int32_t> res;                                  // [head SIN_HEAD][nmatches nJ][rounds nJ][rows]
-    DevBuf<int32_t> pair, cellStart;                         // [4][pairs] counts, cursors, list starts, held features; the grids
-    DevBuf<uint16_t> sorted;
-    DevBuf<uint4> work;
-    DevBuf<uint2> lists;
-    std::vector<int32_t> rounds;                             // of the last call, per job
-    StageClock clock;
-    float stageMs[3] = {0.f, 0.f, 0.f};
-};
-
-static void s3p_destroy(S3pState *s) { delete s; }
 
 }  // namespace rumi
 
@@ -232,8 +216,7 @@ extern "C" int rumi_search_by_projection_sim3_resident(RumiMatcher *m, RumiCovis
             g_lastError = std::string(entry) + ": th and ratio_hamming must be positive";
             return RUMI_E_INVALID;
         }
-        if (!sin_finite(J.kf)) { g_lastError = std::string(entry) + ": a pose, camera centre, bound or scale factor that is not finite"; return RUMI_E_INVALID; }
-        if (!(J.kf.bounds[2] > J.kf.bounds[0]) || !(J.kf.bounds[3] > J.kf.bounds[1])) { g_lastError = std::string(entry) + ": empty image bounds"; return RUMI_E_INVALID; }
+        if (const char *why = fuse_kfs_check(1, [&](int) -> const RumiFuseKF & { return J.kf; })) { g_lastError = std::string(entry) + ": " + why; return RUMI_E_INVALID; }
         if (J.point_start < 0 || J.point_count < 0 || (int64_t)J.point_start + J.point_count > n_points) {
             g_lastError = std::string(entry) + ": a list range outside [0, n_points]";
             return RUMI_E_INVALID;
@@ -260,7 +243,7 @@ extern "C" int rumi_search_by_projection_sim3_resident(RumiMatcher *m, RumiCovis
     const bool work = pairs > 0;
     int rc;
     // the slots first, then (with work to do) the device both handles live on
-    if ((rc = covis_features_check(c, nS, slots.data(), work ? m->device : -1, entry, info.data())) != RUMI_OK) return rc;
+    if ((rc = covis_features_check(c, nS, slots.data(), entry, info.data())) != RUMI_OK || (work && (rc = covis_same_device(c, m->device, entry)) != RUMI_OK)) return rc;
     for (int k = 0; k < nS; k++)
         if (info[k].n > m->maxFeat) { g_lastError = std::string(entry) + ": a key-frame exceeds the matcher's max_features"; return RUMI_E_CAPACITY; }
     size_t rowWords = 0, feats = 0;
@@ -274,24 +257,18 @@ extern "C" int rumi_search_by_projection_sim3_resident(RumiMatcher *m, RumiCovis
         return RUMI_E_CAPACITY;
     }
     if (!work) {                                             // also a call: its rounds (none) and stage times (none) replace the last call's
-        MatcherExt *e0 = &m->ext;
-        if (!e0->state) { e0->state = new NewPtsState(); e0->destroy = newpts_destroy; }
-        NewPtsState *n0 = static_cast<NewPtsState *>(e0->state);
-        if (!n0->s3p) n0->s3p = new S3pState();
-        n0->s3p->rounds.assign((size_t)n_jobs, 0);
-        n0->s3p->stageMs[0] = n0->s3p->stageMs[1] = n0->s3p->stageMs[2] = 0.f;
+        S3pState *s0 = made(newpts_state(m)->s3p);
+        s0->rounds.assign((size_t)n_jobs, 0);
+        s0->stageMs[0] = s0->stageMs[1] = s0->stageMs[2] = 0.f;
         std::memcpy(matched_start, rowStart.data(), ((size_t)n_jobs + 1) * 4);
         for (int j = 0; j < n_jobs; j++) nmatches[j] = 0;
         for (size_t f = 0; f < rowWords; f++) matched[f] = -1;
         return RUMI_OK;
     }
     HIP_TRY(hipSetDevice(m->device));
-    MatcherExt *ext = &m->ext;
-    if (!ext->state) { ext->state = new NewPtsState(); ext->destroy = newpts_destroy; }
-    NewPtsState *np = static_cast<NewPtsState *>(ext->state);
-    if (!np->sin) np->sin = new SinState();
-    if (!np->s3p) np->s3p = new S3pState();
-    S3pState *s = np->s3p;
+    NewPtsState *np = newpts_state(m);
+    SinState *sin = made(np->sin);                           // the stamped tables and their epoch
+    S3pState *s = made(np->s3p);
     s->clock.start(); s->clock.t[0] = t0;
 
     const size_t gridBytes = (size_t)nG * sizeof(SinKF), jobBytes = (size_t)n_jobs * sizeof(S3pJob), upBytes = gridBytes + jobBytes + (size_t)n_points * 4;
@@ -302,26 +279,19 @@ extern "C" int rumi_search_by_projection_sim3_resident(RumiMatcher *m, RumiCovis
         (rc = s->cellStart.reserve((size_t)nG * (kGridCells + 1), (size_t)nG * (kGridCells + 1))) != RUMI_OK ||
         (rc = s->work.reserve(pairs + 1, pairs + pairs / 4 + 1)) != RUMI_OK || (rc = s->lists.reserve(listFirst, listFirst)) != RUMI_OK)
         return rc;
-    CovisFeatureView fv;
+    CovisView fv;
     s->clock.mark();
-    if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
+    if ((rc = covis_view(c, 0, &fv)) != RUMI_OK) return rc;
     for (int i = 0; i < n_points; i++)
         if (point_ids[i] >= fv.maxPoints) { g_lastError = std::string(entry) + ": a point id at or above the store's point capacity"; return RUMI_E_INVALID; }
-    if ((rc = sin_next_epoch(np->sin, fv)) != RUMI_OK) return rc;
+    if ((rc = sin_next_epoch(sin, fv)) != RUMI_OK) return rc;
 
     SinKF *grids = reinterpret_cast<SinKF *>(s->up.h);
     S3pJob *tab = reinterpret_cast<S3pJob *>(s->up.h + gridBytes);
     int32_t sortedOff = 0;
     for (int g = 0; g < nG; g++) {
-        const RumiFuseKF &P = jobs[firstJob[g]].kf;
-        const CovisSlotFeatures &I = info[slotAt[g]];
-        SinKF &R = grids[g];
-        std::memset(&R, 0, sizeof R);
-        R.block = I.block; R.mpOff = I.mpOff; R.n = I.n; R.sortedOff = sortedOff; R.slot = slots[slotAt[g]];
-        std::memcpy(R.bounds, P.bounds, 16);
-        R.wInv = (float)kGridCols / (float)(P.bounds[2] - P.bounds[0]);      // Frame.cc:322-323, as upload_frame forms them
-        R.hInv = (float)kGridRows / (float)(P.bounds[3] - P.bounds[1]);
-        sortedOff += I.n;
+        sin_kf_grid(&grids[g], covis_slot_ref(info[slotAt[g]]), slots[slotAt[g]], jobs[firstJob[g]].kf.bounds, sortedOff);
+        sortedOff += grids[g].n;
     }
     int32_t pairBase = 0, maxCount = 0, maxN = 1;
     for (int j = 0; j < n_jobs; j++) {
@@ -329,7 +299,7 @@ extern "C" int rumi_search_by_projection_sim3_resident(RumiMatcher *m, RumiCovis
         const SinKF &G = grids[gridOf[j]];
         S3pJob &R = tab[j];
         std::memset(&R, 0, sizeof R);
-        R.block = G.block; R.n = G.n; R.grid = gridOf[j]; R.sortedOff = G.sortedOff;
+        static_cast<CovisSlotRef &>(R) = G; R.grid = gridOf[j]; R.sortedOff = G.sortedOff;
         R.pointStart = Q.point_start; R.pointCount = Q.point_count; R.pairBase = pairBase; R.rowStart = rowStart[j];
         R.variant = Q.explicit_invz != 0;
         R.th = (float)Q.th; R.thrF = (float)RUMI_TH_LOW * Q.ratio_hamming;
@@ -350,9 +320,9 @@ extern "C" int rumi_search_by_projection_sim3_resident(RumiMatcher *m, RumiCovis
         HIP_TRY(hipMemsetAsync(s->pair.p, 0, 2 * pairs * 4, nullptr));
         HIP_TRY(hipMemsetAsync(s->pair.p + 3 * pairs, 0xFF, pairs * 4, nullptr));
         S3pArgs a{};
-        a.s.tab = reinterpret_cast<const SinKF *>(s->up.d); a.s.feat = fv.feat; a.s.rows = fv.rows; a.s.pt = fv.pt; a.s.attr = fv.attr;
-        a.s.nT = nG; a.s.curSlot = -1; a.s.epoch = np->sin->epoch;
-        a.s.slotTag = np->sin->slotTag.p; a.s.claim = np->sin->claim.p; a.s.sorted = s->sorted.p; a.s.cellStart = s->cellStart.p;
+        a.s.tab = reinterpret_cast<const SinKF *>(s->up.d); a.s.v = fv;
+        a.s.nT = nG; a.s.curSlot = -1; a.s.epoch = sin->epoch;
+        a.s.slotTag = sin->slotTag.p; a.s.claim = sin->claim.p; a.s.sorted = s->sorted.p; a.s.cellStart = s->cellStart.p;
         a.s.blockCount = s->pair.p; a.s.blockBase = s->pair.p + 2 * pairs; a.s.work = s->work.p; a.s.head = dRes;
         a.jobs = reinterpret_cast<const S3pJob *>(s->up.d + gridBytes); a.ids = reinterpret_cast<const int32_t *>(s->up.d + gridBytes + jobBytes);
         a.cursor = s->pair.p + pairs; a.asg = s->pair.p + 3 * pairs;
@@ -384,16 +354,16 @@ extern "C" int rumi_search_by_projection_sim3_resident(RumiMatcher *m, RumiCovis
 }
 
 extern "C" int rumi_search_by_projection_sim3_stage_ms(const RumiMatcher *m, float *out3) {
-    if (!m || !out3 || !m->ext.state || !static_cast<const NewPtsState *>(m->ext.state)->s3p) {
+    if (!out3 || !newpts_peek(m) || !newpts_peek(m)->s3p) {
         g_lastError = "rumi_search_by_projection_sim3_stage_ms: no resident Sim3 projection search precedes on this matcher";
         return RUMI_E_INVALID;
     }
-    std::memcpy(out3, static_cast<const NewPtsState *>(m->ext.state)->s3p->stageMs, 12);
+    std::memcpy(out3, newpts_peek(m)->s3p->stageMs, 12);
     return RUMI_OK;
 }
 
 extern "C" int rumi_search_by_projection_sim3_rounds(const RumiMatcher *m, int32_t *rounds, int32_t n_jobs) {
-    const rumi::S3pState *s = m && m->ext.state ? static_cast<const NewPtsState *>(m->ext.state)->s3p : nullptr;
+    const rumi::S3pState *s = newpts_peek(m) ? newpts_peek(m)->s3p.get() : nullptr;
     if (!s || !rounds || n_jobs != (int32_t)s->rounds.size()) {
         g_lastError = "rumi_search_by_projection_sim3_rounds: no resident Sim3 projection search of n_jobs jobs precedes on this matcher";
         return RUMI_E_INVALID;

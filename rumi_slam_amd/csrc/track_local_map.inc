@@ -1,5 +1,5 @@
 // The point table of rumi_track_local_map, built on the device from the covisibility store's attribute records (included by track.hip; the
-// store's side is covis.hip, the view between them rumi_internal.h).  Rows 0 .. n_local_points) are mvpLocalMapPoints in their order, then the
+// store's side is covis.hip, the view between them covis_view.h).  Rows 0 .. n_local_points) are mvpLocalMapPoints in their order, then the
 // frame's other points in order of their first feature, then the discarded outliers that have no row yet, in list order.
 //
 // rowOf[point] is a 64-bit stamp (epoch << 32) | value; a value of another epoch reads as "no row".  Inside an epoch
@@ -43,7 +43,7 @@ __device__ __forceinline__ int table_row_of(const unsigned long long *rowOf, uin
 // 32-byte rows).  FULL: normal, obs and local (row < nLocal) as well, which only the local-map table has.  A row without attributes reads as zeros.
 struct TableRows { float *pos, *normal, *minDist, *maxDist; int32_t *obs; uint32_t *desc; uint8_t *bad, *local; };
 template <bool FULL>
-__device__ __forceinline__ void table_gather_rows(const int32_t *pt, const int32_t *attr, const int32_t *tableIds, int nTable, int nLocal, const TableRows &o) {
+__device__ __forceinline__ void table_gather_rows(const CovisView &v, const int32_t *tableIds, int nTable, int nLocal, const TableRows &o) {
     __shared__ int sId[256];
     const int tid = threadIdx.x;
     for (int base = blockIdx.x * 256; base < nTable; base += gridDim.x * 256) {
@@ -51,19 +51,15 @@ __device__ __forceinline__ void table_gather_rows(const int32_t *pt, const int32
         int id = -1;
         if (row < nTable) {
             const int p = tableIds[row];
-            const int4 P = *reinterpret_cast<const int4 *>(pt + (size_t)p * kCovisPointWords);
-            float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-            if (attr && P.w) {
-                id = p;
-                const float4 *A = reinterpret_cast<const float4 *>(attr + (size_t)p * kCovisAttrWords);
-                lo = A[0]; hi = A[1];
-            }
-            o.pos[(size_t)row * 3] = lo.x; o.pos[(size_t)row * 3 + 1] = lo.y; o.pos[(size_t)row * 3 + 2] = lo.z;
-            o.minDist[row] = hi.z; o.maxDist[row] = hi.w;
-            o.bad[row] = (uint8_t)(P.z & 1);
+            const CovisPoint P = v.point(p);
+            CovisAttrGeom A{make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+            if (v.has_attr(P)) { id = p; A = v.attr_geom(p); }
+            A.pos(o.pos + (size_t)row * 3);
+            o.minDist[row] = A.min_dist(); o.maxDist[row] = A.max_dist();
+            o.bad[row] = (uint8_t)P.bad();
             if (FULL) {
-                o.normal[(size_t)row * 3] = lo.w; o.normal[(size_t)row * 3 + 1] = hi.x; o.normal[(size_t)row * 3 + 2] = hi.y;
-                o.obs[row] = P.y;                            // Observations() of the monocular model: the length of the observer row
+                A.normal(o.normal + (size_t)row * 3);
+                o.obs[row] = P.obs_len();                    // Observations() of the monocular model: the length of the observer row
                 o.local[row] = row < nLocal;
             }
         }
@@ -74,7 +70,7 @@ __device__ __forceinline__ void table_gather_rows(const int32_t *pt, const int32
             const int r = it * 32 + (tid >> 3), w = tid & 7;
             if (base + r < nTable) {
                 const int p = sId[r];
-                o.desc[(size_t)(base + r) * 8 + w] = p >= 0 ? (uint32_t)attr[(size_t)p * kCovisAttrWords + 8 + w] : 0u;
+                o.desc[(size_t)(base + r) * 8 + w] = p >= 0 ? (uint32_t)v.attr_desc(p)[w] : 0u;
             }
         }
         __syncthreads();
@@ -85,7 +81,7 @@ __device__ __forceinline__ void table_gather_rows(const int32_t *pt, const int32
 __device__ __forceinline__ int table_candidate(const TableArgs &a, int u) {
     const int p = u < a.v.nFrame ? a.v.framePts[u] : a.v.discIds[u - a.v.nFrame];
     if (p < 0) return -1;
-    if (u < a.v.nFrame && (a.v.pt[p * kCovisPointWords + 2] & 1)) return -1;
+    if (u < a.v.nFrame && a.v.t.point_bad(p)) return -1;
     return p;
 }
 
@@ -95,7 +91,7 @@ __global__ __launch_bounds__(256) void k_table_mark(TableArgs a) {
         const int p = a.v.localPts[j];
         a.v.rowOf[p] = table_row(a.v.epoch, j);
         if (j < a.rowCap) { a.tableIds[j] = p; a.seen[j] = 0; }
-        if (!a.v.attr || !a.v.pt[p * kCovisPointWords + 3]) atomicAdd(&a.v.head[5], 1);
+        if (!a.v.t.has_attr(p)) atomicAdd(&a.v.head[5], 1);
     }
 }
 
@@ -120,7 +116,7 @@ __global__ __launch_bounds__(kTableThreads) void k_table_extras(TableArgs a) {
             const int row = nLocal + slot;
             a.v.rowOf[p] = table_row(a.v.epoch, row);
             if (row < a.rowCap) { a.tableIds[row] = p; a.seen[row] = 0; }
-            if (u < n && (!a.v.attr || !a.v.pt[p * kCovisPointWords + 3])) atomicAdd(&sMissing, 1);
+            if (u < n && !a.v.t.has_attr(p)) atomicAdd(&sMissing, 1);
         });
     }
     __threadfence_block();                                   // the rows written above are read below by other lanes of this workgroup
@@ -148,6 +144,6 @@ __global__ __launch_bounds__(kTableThreads) void k_table_extras(TableArgs a) {
 }
 
 __global__ __launch_bounds__(256) void k_table_gather(TableArgs a) {
-    table_gather_rows<true>(a.v.pt, a.v.attr, a.tableIds, min(a.v.head[4], a.rowCap), a.v.head[3],
+    table_gather_rows<true>(a.v.t, a.tableIds, min(a.v.head[4], a.rowCap), a.v.head[3],
                             TableRows{a.pos, a.normal, a.minDist, a.maxDist, a.obs, a.desc, a.bad, a.local});
 }

@@ -188,10 +188,9 @@ extern "C" int rumi_track_reloc_begin(RumiTracker *t, const float *K4, int32_t K
     if (!t->reloc) t->reloc = new RelocState();
     RelocState *s = t->reloc;
     s->open = false;
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    s->oKeys = al((size_t)K * sizeof(RelocCand)); s->oRows = al(s->oKeys + keysAll * sizeof(RumiKeyPoint)); s->oMatch = al(s->oRows + keysAll * 4);
-    s->oPos = al(s->oMatch + (size_t)K * n * 4); s->oMin = al(s->oPos + (size_t)nmp * 12); s->oMax = al(s->oMin + (size_t)nmp * 4);
-    s->oBad = al(s->oMax + (size_t)nmp * 4); s->oDesc = al(s->oBad + (size_t)nmp); s->oK4 = al(s->oDesc + (size_t)nmp * 32);
+    s->oKeys = up16((size_t)K * sizeof(RelocCand)); s->oRows = up16(s->oKeys + keysAll * sizeof(RumiKeyPoint)); s->oMatch = up16(s->oRows + keysAll * 4);
+    s->oPos = up16(s->oMatch + (size_t)K * n * 4); s->oMin = up16(s->oPos + (size_t)nmp * 12); s->oMax = up16(s->oMin + (size_t)nmp * 4);
+    s->oBad = up16(s->oMax + (size_t)nmp * 4); s->oDesc = up16(s->oBad + (size_t)nmp); s->oK4 = up16(s->oDesc + (size_t)nmp * 32);
     const size_t bytes = s->oK4 + 16;
     int rc;
     if ((rc = s->sess.reserve(bytes, bytes + bytes / 4)) != RUMI_OK) return rc;
@@ -252,9 +251,8 @@ extern "C" int rumi_track_reloc_refine(RumiTracker *t, const RumiRelocParams *p,
     if (p) P = *p; else rumi_reloc_default_params(&P);
     HIP_TRY(hipSetDevice(t->device));
     const size_t n = (size_t)s->n, Hn = (size_t)H * n, pairs = (size_t)H * (size_t)std::max(s->maxNkf, 1);
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t uT = al((size_t)H * sizeof(RelocHyp)), uInl = al(uT + (size_t)H * 28), upBytes = al(uInl + Hn);
-    const size_t rHyp = 16, rMp = al(rHyp + (size_t)H * sizeof(RelocHyp)), rOut = al(rMp + Hn * 4), resBytes = al(rOut + Hn);
+    const size_t uT = up16((size_t)H * sizeof(RelocHyp)), uInl = up16(uT + (size_t)H * 28), upBytes = up16(uInl + Hn);
+    const size_t rHyp = 16, rMp = up16(rHyp + (size_t)H * sizeof(RelocHyp)), rOut = up16(rMp + Hn * 4), resBytes = up16(rOut + Hn);
     const size_t fT = 0, fX = fT + (size_t)H * 8, fO = fX + Hn * 3, fW = fO + Hn * 2, flN = fW + Hn;
     const size_t iIdx = 0, iStart = iIdx + Hn, iGood = iStart + (size_t)H + 1, iCnt = iGood + 3 * (size_t)H, iBase = iCnt + pairs, iAsg = iBase + pairs, inN = iAsg + pairs;
     const size_t listFirst = std::min<size_t>(4 * pairs + 4096, 0x7FFFFFFF);

@@ -19,6 +19,7 @@
 namespace rumi {
 
 // ---- the session's point table and block ------------------------------------------------------------------------------------------------
+// A CovisSlotRef without nn, which the session does not read: with its own two words the record stays at 24 bytes.
 struct RsessCand { long long block; int32_t mpOff, nkf, keyOff, matchRow; };      // keyOff: features of the candidates before it; matchRow: its row of the BoW matches
 static_assert(sizeof(RsessCand) == 24, "the candidate table as uploaded");
 
@@ -26,8 +27,7 @@ struct RsessArgs {
     const RsessCand *cands;
     int Kc, n, rowCap;
     uint32_t epoch;
-    const uint8_t *feat;
-    const int32_t *rows, *pt, *attr;
+    CovisView v;
     unsigned long long *rowOf;           // [max_points] (epoch << 32) | value, as track_local_map.inc
     int32_t *head;                       // {n_table, rows without attributes, -, -}
     int32_t *tableIds;                   // [rowCap]
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void k_rtab_claim(RsessArgs a) {
     const RsessCand C = a.cands[blockIdx.y];
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= C.nkf) return;
-    const int p = a.rows[C.mpOff + i];
+    const int p = a.v.rows[C.mpOff + i];
     if (p >= 0) atomicMax(&a.rowOf[p], table_claim(a.epoch, C.keyOff + i));
 }
 
@@ -59,12 +59,12 @@ __global__ __launch_bounds__(kTableThreads) void k_rtab_order(RsessArgs a) {
         const RsessCand C = a.cands[k];
         for (int c0 = 0; c0 < C.nkf; c0 += kTableThreads) {
             const int i = c0 + tid;
-            const int p = i < C.nkf ? a.rows[C.mpOff + i] : -1;
+            const int p = i < C.nkf ? a.v.rows[C.mpOff + i] : -1;
             const bool win = p >= 0 && a.rowOf[p] == table_claim(a.epoch, C.keyOff + i);
             block_ordered_slot(win, sCnt, &sBase, [&](int row) {
                 a.rowOf[p] = table_row(a.epoch, row);
                 if (row < a.rowCap) a.tableIds[row] = p;
-                if (!a.attr || !a.pt[(size_t)p * kCovisPointWords + 3]) atomicAdd(&sMissing, 1);
+                if (!a.v.has_attr(p)) atomicAdd(&sMissing, 1);
             });
         }
     }
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kTableThreads) void k_rtab_order(RsessArgs a) {
 }
 
 __global__ __launch_bounds__(256) void k_rtab_gather(RsessArgs a) {       // (the host refuses a call that has a row without attributes)
-    table_gather_rows<false>(a.pt, a.attr, a.tableIds, min(a.head[0], a.rowCap), 0, TableRows{a.pos, nullptr, a.minD, a.maxD, nullptr, a.desc, a.bad, nullptr});
+    table_gather_rows<false>(a.v, a.tableIds, min(a.head[0], a.rowCap), 0, TableRows{a.pos, nullptr, a.minD, a.maxD, nullptr, a.desc, a.bad, nullptr});
 }
 
 // grid (x, Kc): candidate blockIdx.y's key-points and row, then its matches; block (0, 0) also writes K4
@@ -82,10 +82,10 @@ __global__ __launch_bounds__(256) void k_rsess_fill(RsessArgs a) {
     const int step = gridDim.x * 256, t0 = blockIdx.x * 256 + threadIdx.x;
     if (t0 == 0) a.outCands[k] = RelocCand{C.nkf, C.keyOff};
     if (k == 0 && t0 < 4) a.k4Out[t0] = a.K4[t0];
-    const RumiKeyPoint *keys = reinterpret_cast<const RumiKeyPoint *>(a.feat + C.block + kCovisFeatKeysOffset);
+    const RumiKeyPoint *keys = a.v.keys_at(C.block + kCovisFeatKeysOffset);
     for (int i = t0; i < C.nkf; i += step) {
         a.outKeys[C.keyOff + i] = keys[i];
-        const int p = a.rows[C.mpOff + i];
+        const int p = a.v.rows[C.mpOff + i];
         int row = p >= 0 ? table_row_of(a.rowOf, a.epoch, p) : -1;
         if (row >= a.rowCap) row = -1;                       // (the host refuses such a call: nothing of it is read)
         a.outRows[C.keyOff + i] = row;
@@ -184,7 +184,7 @@ extern "C" int rumi_track_reloc_bow(RumiTracker *t, RumiCovis *c, int32_t K, con
     }
     std::vector<CovisSlotFeatures> info(live.size() + 1);
     int rc;
-    if ((rc = covis_features_check(c, (int)live.size(), live.data(), t->device, entry, info.data())) != RUMI_OK) return rc;
+    if ((rc = covis_features_check(c, (int)live.size(), live.data(), entry, info.data())) != RUMI_OK || (rc = covis_same_device(c, t->device, entry)) != RUMI_OK) return rc;
     // ---- device work from here on
     HIP_TRY(hipSetDevice(t->device));
     r->haveWalk = false;
@@ -195,17 +195,16 @@ extern "C" int rumi_track_reloc_bow(RumiTracker *t, RumiCovis *c, int32_t K, con
     BowSlotKF *hc = reinterpret_cast<BowSlotKF *>(r->tab.h);
     int maxNodes = 0;
     for (int k = 0, l = 0; k < K; k++) {
-        if (bad[(size_t)k]) { hc[k] = BowSlotKF{0, 0, 0, 0, 1}; continue; }
-        const CovisSlotFeatures &I = info[(size_t)l++];
-        hc[k] = BowSlotKF{(long long)I.block, I.mpOff, I.n, I.nn, 0};
-        maxNodes = std::max(maxNodes, I.nn);
+        if (bad[(size_t)k]) { hc[k] = BowSlotKF{{}, 1}; continue; }
+        hc[k] = BowSlotKF{covis_slot_ref(info[(size_t)l++]), 0};
+        maxNodes = std::max(maxNodes, hc[k].nn);
     }
-    CovisFeatureView fv;
-    if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
+    CovisView fv;
+    if ((rc = covis_view(c, 0, &fv)) != RUMI_OK) return rc;
     HIP_TRY(hipMemcpyAsync(r->tab.d, r->tab.h, (size_t)K * sizeof(BowSlotKF), hipMemcpyHostToDevice, nullptr));
     if (Kn) HIP_TRY(hipMemsetAsync(r->out.d, 0xFF, Kn * 4, nullptr));                       // matches = -1
     HIP_TRY(hipMemsetAsync(r->out.d + oCnt, 0, oBin - oCnt, nullptr));                      // counts and histograms
-    SlotView V{reinterpret_cast<const BowSlotKF *>(r->tab.d), fv.feat, fv.rows, fv.pt};
+    SlotView V{reinterpret_cast<const BowSlotKF *>(r->tab.d), fv};
     ResidentFrame F{resident_keys(t), reinterpret_cast<const uint32_t *>(t->d.record + t->oDesc), r->fvNodes.p, r->fvIdx.p, r->fvOff.p, r->fvNN.p};
     BowRows R;
     R.matches = reinterpret_cast<int32_t *>(r->out.d); R.nmatch = reinterpret_cast<int32_t *>(r->out.d + oCnt);
@@ -245,7 +244,9 @@ extern "C" int rumi_track_reloc_begin_resident(RumiTracker *t, RumiCovis *c, con
     }
     std::vector<CovisSlotFeatures> info((size_t)Kc + 1);
     int rc;
-    if ((rc = covis_features_check(c, Kc, sel.data(), t->device, entry, info.data())) != RUMI_OK) return rc;     // (also: a candidate named twice)
+    if ((rc = covis_features_check(c, Kc, sel.data(), entry, info.data())) != RUMI_OK ||                         // (also: a candidate named twice)
+        (rc = covis_same_device(c, t->device, entry)) != RUMI_OK)
+        return rc;
     size_t keysAll = 0;
     int maxNkf = 0;
     for (int k = 0; k < Kc; k++) { keysAll += (size_t)info[(size_t)k].n; maxNkf = std::max(maxNkf, info[(size_t)k].n); }
@@ -256,17 +257,16 @@ extern "C" int rumi_track_reloc_begin_resident(RumiTracker *t, RumiCovis *c, con
     RelocState *s = t->reloc;
     s->open = false;
     const int rowCap = (int)std::min<size_t>(std::min(t->maxPts, table_cap), keysAll);      // a table has at most one row per key-frame feature
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    s->oKeys = al((size_t)Kc * sizeof(RelocCand)); s->oRows = al(s->oKeys + keysAll * sizeof(RumiKeyPoint)); s->oMatch = al(s->oRows + keysAll * 4);
-    s->oPos = al(s->oMatch + (size_t)Kc * n * 4); s->oMin = al(s->oPos + (size_t)rowCap * 12); s->oMax = al(s->oMin + (size_t)rowCap * 4);
-    s->oBad = al(s->oMax + (size_t)rowCap * 4); s->oDesc = al(s->oBad + (size_t)rowCap); s->oK4 = al(s->oDesc + (size_t)rowCap * 32);
+    s->oKeys = up16((size_t)Kc * sizeof(RelocCand)); s->oRows = up16(s->oKeys + keysAll * sizeof(RumiKeyPoint)); s->oMatch = up16(s->oRows + keysAll * 4);
+    s->oPos = up16(s->oMatch + (size_t)Kc * n * 4); s->oMin = up16(s->oPos + (size_t)rowCap * 12); s->oMax = up16(s->oMin + (size_t)rowCap * 4);
+    s->oBad = up16(s->oMax + (size_t)rowCap * 4); s->oDesc = up16(s->oBad + (size_t)rowCap); s->oK4 = up16(s->oDesc + (size_t)rowCap * 32);
     const size_t bytes = s->oK4 + 16;
     if ((rc = s->sess.reserve(bytes, bytes + bytes / 4)) != RUMI_OK) return rc;
     if ((rc = r->tab.reserve((size_t)std::max(Kc, 1) * sizeof(RsessCand), (size_t)std::max(Kc, 1) * sizeof(RsessCand) * 2)) != RUMI_OK ||
         (rc = r->ids.reserve(4 + (size_t)rowCap, 4 + (size_t)rowCap + (size_t)rowCap / 2)) != RUMI_OK)
         return rc;
-    CovisFeatureView fv;
-    if ((rc = covis_features_flush(c, &fv)) != RUMI_OK) return rc;
+    CovisView fv;
+    if ((rc = covis_view(c, 0, &fv)) != RUMI_OK) return rc;
     if (r->rowOf.cap < (size_t)fv.maxPoints || r->epoch == 0xFFFFFFFFu) {
         if ((rc = r->rowOf.reserve((size_t)fv.maxPoints, (size_t)fv.maxPoints)) != RUMI_OK) return rc;
         HIP_TRY(hipMemsetAsync(r->rowOf.p, 0, r->rowOf.cap * 8, nullptr));
@@ -286,7 +286,7 @@ extern "C" int rumi_track_reloc_begin_resident(RumiTracker *t, RumiCovis *c, con
     RsessArgs A{};
     A.cands = reinterpret_cast<const RsessCand *>(r->tab.d);
     A.Kc = Kc; A.n = n; A.rowCap = rowCap; A.epoch = ++r->epoch;
-    A.feat = fv.feat; A.rows = fv.rows; A.pt = fv.pt; A.attr = fv.attr;
+    A.v = fv;
     A.rowOf = r->rowOf.p; A.head = r->ids.d; A.tableIds = r->ids.d + 4;
     A.bowMatches = reinterpret_cast<const int32_t *>(r->out.d);
     A.outCands = reinterpret_cast<RelocCand *>(ds); A.outKeys = reinterpret_cast<RumiKeyPoint *>(ds + s->oKeys);

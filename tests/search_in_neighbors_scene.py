@@ -412,12 +412,15 @@ def tiny_map(points, targets, n_cur=None, extra_rows=None):
 class StoreScene:
     """A covisibility store holding a SinMap: rows, observers with feature indices, attributes, features."""
 
-    def __init__(self, m, max_points=None):
+    def __init__(self, m, max_points=None, arena_entries=0, reserve_features=None):
+        """arena_entries, reserve_features: first sizes of the row arena and the feature arena (the store's defaults when not given)."""
         from rumi_slam_amd.covis import Covisibility
         from rumi_slam_amd.matcher import FeatureVector, FrameView
         self.m = m
         nk = len(m.kfs)
-        self.store = Covisibility(slot_of(nk) + 4, (m.n_points + 64) if max_points is None else max_points)
+        self.store = Covisibility(slot_of(nk) + 4, (m.n_points + 64) if max_points is None else max_points, arena_entries=arena_entries)
+        if reserve_features is not None:
+            self.store.reserve_features(reserve_features)
         self.frames = [FrameView(kf.keys, kf.desc, W, H, SF) for kf in m.kfs]
         self.fv = FeatureVector({})
         order = list(range(nk))[::-1]

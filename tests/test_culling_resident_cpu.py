@@ -62,6 +62,31 @@ def test_a_later_list_differs_from_the_first():
         assert len({tuple(c) for c in lists}) == len(lists)
 
 
+def test_store_and_handle_on_different_devices_are_refused_before_either_binds():
+    """Known without asking either device: the refusal is RUMI_E_INVALID, not the missing device of a machine without one (the twin of
+    test_refresh_resident_cpu.test_resident_refusals_from_the_mirror's last case)."""
+    from rumi_slam_amd import capi
+    from rumi_slam_amd.covis import Covisibility
+    from rumi_slam_amd.mapping import KeyFrameCuller, cull_outputs
+
+    octv = np.zeros(3, np.int32)
+    mp = [np.array([0, 1, -1], np.int32), np.array([0, -1, 1], np.int32), np.array([-1, 0, 1], np.int32), np.array([0, -1, -1], np.int32)]
+    pts = [(False, 4, [(0, 0), (1, 0), (2, 1), (3, 0)]), (False, 3, [(0, 1), (1, 2), (2, 2)])]
+    m = rs.MapMirror([(octv, r, False, False, False, False) for r in mp], pts)
+    s = Covisibility(8, 16, arena_entries=256, device=1)
+    m.load(s)
+    cull = KeyFrameCuller(device=0)
+    cands = m.candidates([2, 0, 1])
+    out = cull_outputs(len(cands), 0x77)
+    before = s.stats()
+    rc = cull.status_resident(s, cands, 0, out)
+    msg = capi.lib().rumi_last_error().decode()
+    assert rc == capi.RUMI_E_INVALID and "different devices" in msg, (rc, msg)
+    assert all(a.tobytes() == bytes([0x77]) * a.nbytes for a in out.values()), "a refused call writes nothing"
+    assert s.stats() == before
+    cull.close(); s.close()
+
+
 def test_symbols_are_declared():
     from rumi_slam_amd import capi
     assert "rumi_keyframe_culling_resident" in capi.MAPPING_SYMBOLS and "rumi_covis_set_point_observations" in capi.COVIS_SYMBOLS

@@ -172,6 +172,36 @@ def test_a_target_whose_row_is_empty_gives_no_reverse_candidates(matcher):
     assert fwd[:, 0].tolist() == [0, 0, 0]
 
 
+def test_the_view_is_taken_per_call_and_survives_both_arenas_moving(matcher):
+    """Between two calls on one matcher the feature arena grows (a new device allocation) and the row arena is rebuilt (every row moves): the
+    second call reads the store where it lies then.  The smallest constructed scene, the current key-frame and two targets, in a store whose
+    arenas start as small as the entries admit."""
+    from rumi_slam_amd.matcher import FeatureVector, FrameView
+    a, b = D[12], D[13]
+    pts = [S.point_at(100.0, 100.0, 2, a), S.point_at(601.0, 440.0, 0, b), S.point_at(50.0, 50.0, 2, D[14])]
+    f = ([[100.5, 100.0], [400.0, 400.0]], [2, 2], [a, D[15]])
+    m = S.tiny_map(pts, [f, f], extra_rows=[[-1, 1], [2, 1]])
+    m.kfs[0].row[1] = m.kfs[0].row[2] = -1                        # points 1 and 2 live in the targets only
+    m.kfs[0].desc[0] = b                                          # and point 1 matches feature 0 of the current key-frame
+    sc = S.StoreScene(m, arena_entries=16, reserve_features=4096)
+    _, fwd, rp, rb = check(matcher, m, sc)
+    assert fwd[:, 0].tolist() == [0, 0] and rp.tolist() == [1, 2] and rb.tolist() == [0, -1]
+    # one more key-frame, which no point observes: more features than the feature arena has room left for, a row longer than the row arena
+    store, fs, rs = sc.store, sc.store.feature_stats(), sc.store.stats()
+    n = max(fs["capacity"] // 60, rs["capacity"]) + 8
+    rng = np.random.default_rng(9)
+    xy = np.stack([rng.uniform(20, 600, n), rng.uniform(20, 440, n)], 1)
+    slot = S.slot_of(len(m.kfs))
+    store.set_keyframes([slot], [9000 + 13 * slot], [0], [0], [np.full(n, -1, np.int32)], [[]], [-1], [[]])
+    store.set_keyframe_features(slot, FrameView(S.keypoints(xy, np.zeros(n, np.int32)), rng.integers(0, 256, (n, 32), dtype=np.uint8), S.W, S.H, S.SF),
+                                FeatureVector({}), S.K4)
+    fs2, rs2 = store.feature_stats(), store.stats()
+    assert fs2["growths"] > fs["growths"] and fs2["capacity"] > fs["capacity"]
+    assert rs2["growths"] + rs2["compactions"] > rs["growths"] + rs["compactions"]
+    _, fwd2, rp2, rb2 = check(matcher, m, sc)
+    assert fwd2.tobytes() == fwd.tobytes() and rp2.tobytes() == rp.tobytes() and rb2.tobytes() == rb.tobytes()
+
+
 @pytest.mark.parametrize("nt", [1, 65])
 def test_target_counts(matcher, nt):
     """One target, and more targets than a wave has lanes: 65 copies of a 64-feature key-frame under slots of their own."""
