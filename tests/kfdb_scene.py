@@ -2,7 +2,9 @@
 GPU database run.
 
 A script is a list of commands (tuples): ("A", id, map, words, vals), ("E", id), ("M", map), ("C",), ("B", map, bad), ("K", id, map),
-("D", id, bad), ("V", id, [covisible ids]), ("R", qid, map, words, vals), ("N", qid, map, n_cand, [connected ids], words, vals)."""
+("D", id, bad), ("V", id, [covisible ids]), ("R", qid, map, words, vals), ("N", qid, map, n_cand, [connected ids], words, vals).
+"R" and "N" may carry one more element: visible_below, as a number of adds counted from the start of the script; only run_gpu and kfdb_cases.PyDB
+read it (the oracle has no such argument, to_text leaves it out)."""
 import os
 import subprocess
 
@@ -141,6 +143,11 @@ def run_gpu(db, script, batch=True):
     kind (distinct ids) go in one batched call.  Returns the output lines in the oracle's format."""
     out = []
     i = 0
+    base = db.next_seq()
+
+    def bounds(qs, at):
+        return [base + q[at] if len(q) > at else (1 << 62) for q in qs] if any(len(q) > at for q in qs) else None
+
     while i < len(script):
         c = script[i]
         op = c[0]
@@ -157,11 +164,12 @@ def run_gpu(db, script, batch=True):
                 seen.add(script[j][1]); j += 1
             qs = script[i:j]
             if op == "R":
-                cands, scored = db.detect_relocalization_candidates([q[1] for q in qs], [q[2] for q in qs], [(q[3], q[4]) for q in qs], with_scored=True)
+                cands, scored = db.detect_relocalization_candidates([q[1] for q in qs], [q[2] for q in qs], [(q[3], q[4]) for q in qs], visible_below=bounds(qs, 5),
+                                                                      with_scored=True)
                 out += [format_reloc(q[1], s, cd) for q, s, cd in zip(qs, scored, cands)]
             else:
                 res, scored = db.detect_nbest_candidates([q[1] for q in qs], [q[2] for q in qs], [(q[5], q[6]) for q in qs], [q[4] for q in qs],
-                                                         [q[3] for q in qs], with_scored=True)
+                                                         [q[3] for q in qs], visible_below=bounds(qs, 7), with_scored=True)
                 out += [format_nbest(q[1], s, lp, mg) for q, s, (lp, mg) in zip(qs, scored, res)]
             i = j
             continue

@@ -1,125 +1,11 @@
-"""The C++ key-frame database oracle (tests/cpp/kfdb_oracle.cc) against a tiny pure-Python restatement of KeyFrameDatabase.cc's two queries,
+"""The C++ key-frame database oracle (tests/cpp/kfdb_oracle.cc) against a tiny pure-Python restatement of KeyFrameDatabase.cc's two queries
+(kfdb_cases.PyDB),
 on hand-built cases, and the scene generator of tests/kfdb_scene.py.  CPU only."""
 import numpy as np
 import pytest
 
+from kfdb_cases import PyDB
 from kfdb_scene import Scene, build_oracle, l1_normalise, run_oracle, to_text
-
-
-def f32(x):
-    return float(np.float32(x))
-
-
-def f32hex(x):
-    return "%08x" % int(np.float32(x).view(np.uint32))
-
-
-class PyDB:
-    """KeyFrameDatabase.cc:604-708 (N-best) and :733-843 (reloc), float arithmetic through numpy float32."""
-
-    def __init__(self):
-        self.kf, self.inv, self.indb, self.badmaps = {}, {}, set(), set()
-
-    def run(self, script):
-        out = []
-        for c in script:
-            op = c[0]
-            if op == "A":
-                k = self.kf.setdefault(c[1], dict(rq=0, rs=0.0, pq=0, ps=0.0))
-                k.update(map=c[2], bow=dict(zip((int(x) for x in c[3]), (float(x) for x in c[4]))), cov=[], bad=False)
-                for w in k["bow"]:
-                    self.inv.setdefault(w, []).append(c[1])
-                self.indb.add(c[1])
-            elif op == "E":
-                self._erase(c[1])
-            elif op == "M":
-                for i in [i for i in self.indb if self.kf[i]["map"] == c[1]]:
-                    self._erase(i)
-            elif op == "B":
-                (self.badmaps.add if c[2] else self.badmaps.discard)(c[1])
-            elif op == "V":
-                if c[1] in self.indb:
-                    self.kf[c[1]]["cov"] = [x for x in c[2] if x in self.indb]
-            elif op == "R":
-                out.append(self._query("R", c[1], c[2], set(), dict(zip((int(x) for x in c[3]), (float(x) for x in c[4]))), None))
-            elif op == "N":
-                out.append(self._query("N", c[1], c[2], set(c[4]), dict(zip((int(x) for x in c[5]), (float(x) for x in c[6]))), c[3]))
-        return out
-
-    def _erase(self, i):
-        if i not in self.indb:
-            return
-        for w in self.kf[i]["bow"]:
-            self.inv[w].remove(i)
-        self.indb.discard(i)
-        for k in self.kf.values():
-            if "cov" in k:
-                k["cov"] = [x for x in k["cov"] if x != i]
-
-    @staticmethod
-    def score(a, b):
-        s = 0.0
-        for w in sorted(set(a) & set(b)):
-            v, u = a[w], b[w]
-            s += abs(v - u) - abs(v) - abs(u)
-        return f32(-s / 2.0)
-
-    def _query(self, kind, qid, qmap, conn, bow, N):
-        q, sc = ("rq", "rs") if kind == "R" else ("pq", "ps")
-        listed, words = [], {}
-        for w in sorted(bow):
-            for i in self.inv.get(w, []):
-                k = self.kf[i]
-                if k[q] != qid:
-                    words[i] = 0
-                    if i not in conn:
-                        k[q] = qid
-                        listed.append(i)
-                words[i] = words.get(i, 0) + 1
-        line = f"{kind} {qid} |"
-        if not listed:
-            return line + (" |" if kind == "R" else " | |")
-        mx = max(words[i] for i in listed)
-        mn = int(f32(np.float32(mx) * np.float32(0.8)))
-        scored = []
-        for i in listed:
-            if words[i] > mn:
-                s = self.score(bow, self.kf[i]["bow"])
-                self.kf[i][sc] = s
-                scored.append((s, i))
-        line += "".join(f" {i}:{f32hex(s)}" for s, i in scored) + " |"
-        acc = []
-        best_acc = np.float32(0)
-        for s, i in scored:
-            a, b, bi = np.float32(s), np.float32(s), i
-            for x in self.kf[i]["cov"]:
-                if self.kf[x][q] != qid:
-                    continue
-                a = np.float32(a + np.float32(self.kf[x][sc]))
-                if np.float32(self.kf[x][sc]) > b:
-                    b, bi = np.float32(self.kf[x][sc]), x
-            acc.append((a, bi))
-            best_acc = max(best_acc, a)
-        if kind == "R":
-            th, seen, out = np.float32(0.75) * best_acc, set(), []
-            for a, i in acc:
-                if a > th and self.kf[i]["map"] == qmap and i not in seen:
-                    out.append(i); seen.add(i)
-            return line + "".join(f" {i}" for i in out)
-        acc = sorted(acc, key=lambda t: -t[0])        # stable, as std::list::sort
-        loop, merge, seen = [], [], set()
-        for a, i in acc:
-            if not (len(loop) < N or len(merge) < N):
-                break
-            if i in seen:
-                continue
-            m = self.kf[i]["map"]
-            if m == qmap and len(loop) < N:
-                loop.append(i)
-            elif m != qmap and len(merge) < N and m not in self.badmaps:
-                merge.append(i)
-            seen.add(i)
-        return line + "".join(f" {i}" for i in loop) + " |" + "".join(f" {i}" for i in merge)
 
 
 @pytest.fixture(scope="module")
