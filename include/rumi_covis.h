@@ -79,6 +79,16 @@ int rumi_covis_set_keyframe_centres(RumiCovis *c, int32_t n, const int32_t *slot
 /* GetReferenceKeyFrame() of n points as a live slot, -1 clears it; ids each at most once and inside 0..max_points-1.  To be called wherever
  * SetReferenceKeyFrame or EraseObservation changes mpRefKF.  Staged like every edit, one word a point. */
 int rumi_covis_set_point_reference(RumiCovis *c, int32_t n, const int32_t *ids, const int32_t *ref_slots);
+/* GetPose() of n live slots, each at most once, as qx qy qz qw tx ty tz, all finite.  To be called where the reference calls SetPose, beside
+ * rumi_covis_set_keyframe_centres.  The store keeps what the bundle adjustment makes of the seven floats before it uploads them (eight doubles,
+ * 64 bytes a key-frame: the normalised quaternion, the translation, a zero), converted here on the host by the same function, so that
+ * rumi_local_ba_resident (rumi_opt.h) reads the bytes rumi_local_ba would upload.  A slot set here "has a pose" from then on.  Staged like
+ * every edit; the table does not exist until the first call. */
+int rumi_covis_set_keyframe_poses(RumiCovis *c, int32_t n, const int32_t *slots, const float *pose7);
+/* MapPoint::GetMap() of n points in the numbering of the key-frames' map_id; ids each at most once and inside 0..max_points-1.  A point set
+ * here "has a map" from then on (rumi_covis_set_points keeps the bit).  Staged like every edit, one word a point.  Read by
+ * rumi_local_ba_resident (Optimizer.cc:1032 asks pMP->GetMap() == pCurrentMap) and by nothing else. */
+int rumi_covis_set_point_maps(RumiCovis *c, int32_t n, const int32_t *ids, const int32_t *map_ids);
 /* The length of a live slot's map-point row as the last rumi_covis_set_keyframes left it (host only, no device call); -1 for a slot that is
  * not live or a missing handle.  For callers that size an output by it (rumi_search_in_neighbors_resident, rumi_mapping.h). */
 int32_t rumi_covis_row_length(const RumiCovis *c, int32_t slot);
@@ -130,7 +140,7 @@ int rumi_covis_local_map(RumiCovis *c, int32_t n, const int32_t *frame_points, u
 /* The last query, in ms: validation + staging | upload, kernels, download | write-out. */
 int rumi_covis_stage_ms(const RumiCovis *c, float *out3);
 /* out7: arena capacity, tail, live entries (all in 32-bit entries), rows re-placed at the tail, compactions, growths, bytes of the last upload
- * (attribute, centre and reference edits included). */
+ * (attribute, centre, reference, pose and point-map edits included). */
 int rumi_covis_stats(const RumiCovis *c, int64_t *out7);
 
 #ifdef __cplusplus

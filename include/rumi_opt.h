@@ -59,6 +59,9 @@ typedef struct RumiOptimizer RumiOptimizer;
  *   rumi_local_ba / rumi_merge_ba / rumi_bundle_adjustment: X, the first time a window of up to 29 optimised key-frames (and at most 512
  *     key-frames, handle not profiled) runs; 148 E and the co-observation pair lists of the largest window seen (growing by a quarter), the first
  *     time a window of more than 42 optimised key-frames runs.
+ *   rumi_local_ba_resident: what the assembly of a window needs beyond W, growing with the store and the window: 8 bytes a point id of the
+ *     store (first-occurrence stamps), 20 E (observer word, point id and erase list per edge), the lists and counts of one call (4 bytes a
+ *     feature of the local rows, 16 a slot), and two small transfer blocks; the solve then takes X, or H's blocks, as rumi_local_ba does.
  *   rumi_essential_graph / rumi_sim3_correct_points: the dense matrix and one block for the rest, by problem size.
  *   rumi_local_ba_batch with n such small windows: batch arenas A = W + X, one per window of a launch wave: min(n, 32) of them (X when a
  *     window is first staged in the arena; a window that ends before staging leaves it at W); batch runners R: one per launch group after the
@@ -97,6 +100,42 @@ int rumi_pose_optimization_batch(RumiOptimizer *o, int32_t nbatch, const int32_t
 int rumi_local_ba(RumiOptimizer *o, int32_t nKF, float *kf_pose7, const uint8_t *kf_fixed, int32_t nMP, float *mp_pos3,
                   int32_t nE, const int32_t *e_mp, const int32_t *e_kf, const float *e_obs, const float *e_inv_sigma2,
                   const float *K4, const volatile uint8_t *stop_flag, uint8_t *erase_out, int32_t *stats);
+
+/* Optimizer::LocalBundleAdjustment with the window assembled on the device from the covisibility store (rumi_covis.h): the host names slots,
+ * nothing of the graph is uploaded.  For the same map state every output is, byte for byte, what rumi_local_ba returns on the graph that
+ * Optimizer.cc:1003-1271 builds (monocular branch).
+ *   cur_slot     pKF; K4 is its fx fy cx cy (rumi_covis_set_keyframe_features)
+ *   neigh_slots  pKF->GetVectorCovisibleKeyFrames() as slots, unfiltered and in that order (live, distinct, never cur_slot)
+ *   init_slot    pMap->GetInitKFid() as a slot, -1 none
+ * Read in the store: map-point rows, bad bits and maps of key-frames and points (rumi_covis_set_point_maps), observer rows with feature indices
+ * (rumi_covis_set_point_observations), order_key (the order of std::map<KeyFrame*, ..>), key-points, scale factors, poses
+ * (rumi_covis_set_keyframe_poses) and positions (rumi_covis_set_point_attributes).
+ * out: the caller sets the capacities and the pointers; the call writes
+ *   kf_slots [n_kf]        lLocalKeyFrames (num_OptKF of them, the current slot first), then lFixedCameras in order of first appearance
+ *   kf_pose7 [num_OptKF]   the new poses of the local key-frames (the initial key-frame keeps the floats it was set with)
+ *   mp_ids, mp_pos3 [num_MPs]   lLocalMapPoints and their new positions
+ *   erased [n_erased][3]   {key-frame slot, point id, feature} of the observations to erase, in edge order (Optimizer.cc:1285-1297)
+ *   num_fixedKF            lFixedCameras, plus one when init_slot is local;  num_edges;  stats[4] as rumi_local_ba
+ * Refused with RUMI_E_INVALID, counts from the device's check in the message, store and out untouched: a live point of a local row that was
+ * never given a map; an observation whose (slot, feature) disagrees with the slot's row; a key-frame of the window without pose or features;
+ * a listed point without attributes or observation features.  No fixed key-frame: RUMI_E_INVALID and rumi_local_ba's message.  Stop flag
+ * raised: stats[3] = 1, nothing else written.  RUMI_E_CAPACITY when a list does not fit out or the handle's arenas.
+ * One small block (counts and the key-frame list) is read back between assembly and solve.  A window the tile solver takes (at most 29
+ * optimised and 512 key-frames, handle not profiled) is solved from where the fill kernels left it; any other window is assembled on the
+ * device all the same, read back once and handed to the single-window host loop as rumi_local_ba does.
+ * After a run that was not aborted the store takes the results: positions into the attribute records (device and mirror), the new poses as
+ * rumi_covis_set_keyframe_poses of kf_pose7 would leave them (staged).  Camera centres stay the caller's rumi_covis_set_keyframe_centres. */
+typedef struct RumiLbaResidentOut {
+    int32_t kf_cap, mp_cap, erase_cap;             /* in: capacities of the arrays below, in entries */
+    int32_t *kf_slots; float *kf_pose7;            /* [kf_cap], [kf_cap][7] */
+    int32_t *mp_ids; float *mp_pos3;               /* [mp_cap], [mp_cap][3] */
+    int32_t *erased;                               /* [erase_cap][3] */
+    int32_t n_kf, num_OptKF, num_fixedKF, num_MPs, num_edges, n_erased;
+    int32_t stats[4];
+} RumiLbaResidentOut;
+struct RumiCovis;
+int rumi_local_ba_resident(RumiOptimizer *o, struct RumiCovis *c, int32_t cur_slot, const int32_t *neigh_slots, int32_t n_neigh, int32_t init_slot,
+                           const volatile uint8_t *stop_flag, RumiLbaResidentOut *out);
 
 /* R independent windows of Optimizer::LocalBundleAdjustment (Optimizer.cc:1003-1355) in one call.  A window does not shard over GPUs or
  * workgroups ("replicas only"), but windows are independent.  Windows of up to 29 optimised key-frames are a batch

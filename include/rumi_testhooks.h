@@ -83,6 +83,12 @@ int rumi_hook_covis_read_attributes(struct RumiCovis *c, int32_t n, const int32_
  * from a scene (rumi_common_regions_bow_resident). */
 int rumi_hook_covis_read_row(struct RumiCovis *c, int32_t slot, int32_t cap, int32_t *row, uint8_t *point_bad, int32_t *kf_bad);
 
+/* What a covisibility store holds of rumi_covis_set_keyframe_poses and rumi_covis_set_point_maps, from the device copy (from_device != 0; waits
+ * for the device) or from the host mirror, staged edits included there.  Uploads nothing.  pose8 [n_kf][8] doubles and has_pose [n_kf] of the
+ * slots (zeros where the table does not exist yet); map_id [n_pt] and has_map [n_pt] of the points.  For the tests of rumi_local_ba_resident. */
+int rumi_hook_covis_read_poses(struct RumiCovis *c, int32_t n_kf, const int32_t *slots, double *pose8, int32_t *has_pose, int32_t n_pt,
+                               const int32_t *ids, int32_t *map_id, int32_t *has_map, int32_t from_device);
+
 #ifdef __cplusplus
 }
 #endif

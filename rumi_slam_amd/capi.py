@@ -108,7 +108,7 @@ MATCH_SYMBOLS = ["rumi_descriptor_distance", "rumi_match_create", "rumi_match_de
                  "rumi_search_by_projection_reloc", "rumi_search_for_initialization", "rumi_search_for_triangulation", "rumi_fuse_candidates", "rumi_search_by_sim3", "rumi_frame_is_in_frustum", "rumi_search_local_points", "rumi_search_by_bow_batch", "rumi_common_regions_bow", "rumi_common_regions_bow_profile", "rumi_match_bruteforce_batch_device", "rumi_match_bruteforce_batch_device_strided", "rumi_match_bruteforce_ring_device", "rumi_match_bruteforce_shape", "rumi_submap_match",
                  "rumi_match_bruteforce_pair_scratch_bytes", "rumi_match_bruteforce_pair_shape", "rumi_match_bruteforce_pair_device"]
 
-OPT_SYMBOLS = ["rumi_opt_create", "rumi_opt_destroy", "rumi_pose_optimization", "rumi_pose_optimization_batch", "rumi_local_ba", "rumi_local_ba_batch", "rumi_merge_ba", "rumi_bundle_adjustment", "rumi_sim3_inliers",
+OPT_SYMBOLS = ["rumi_opt_create", "rumi_opt_destroy", "rumi_pose_optimization", "rumi_pose_optimization_batch", "rumi_local_ba", "rumi_local_ba_resident", "rumi_local_ba_batch", "rumi_merge_ba", "rumi_bundle_adjustment", "rumi_sim3_inliers",
                "rumi_optimize_sim3", "rumi_sim3_ransac", "rumi_opt_stage_ms", "rumi_opt_set_profiling", "rumi_opt_kernel_ms", "rumi_opt_footprint",
                "rumi_essential_graph", "rumi_sim3_correct_points", "rumi_sim3_ransac_batch", "rumi_optimize_sim3_batch"]
 
@@ -128,6 +128,7 @@ MAPPING_SYMBOLS = ["rumi_create_new_map_points", "rumi_create_new_map_points_res
                    "rumi_cull_create", "rumi_cull_destroy", "rumi_keyframe_culling", "rumi_keyframe_culling_resident", "rumi_cull_stage_ms"]
 COVIS_SYMBOLS = ["rumi_covis_create", "rumi_covis_destroy", "rumi_covis_set_keyframes", "rumi_covis_set_points", "rumi_covis_set_point_observations",
                  "rumi_covis_set_point_attributes", "rumi_covis_set_keyframe_centres", "rumi_covis_set_point_reference",
+                 "rumi_covis_set_keyframe_poses", "rumi_covis_set_point_maps",
                  "rumi_covis_set_bad", "rumi_covis_set_maps", "rumi_covis_set_keyframe_features", "rumi_covis_drop_keyframe_features",
                  "rumi_covis_reserve_features", "rumi_covis_feature_stats", "rumi_covis_row_length",
                  "rumi_covis_update_connections", "rumi_covis_local_map", "rumi_covis_stage_ms", "rumi_covis_stats"]
@@ -202,6 +203,8 @@ def covis_lib():
     L.rumi_covis_set_point_attributes.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.rumi_covis_set_keyframe_centres.argtypes = [vp, i32, vp, vp]
     L.rumi_covis_set_point_reference.argtypes = [vp, i32, vp, vp]
+    L.rumi_covis_set_keyframe_poses.argtypes = [vp, i32, vp, vp]
+    L.rumi_covis_set_point_maps.argtypes = [vp, i32, vp, vp]
     L.rumi_covis_set_bad.argtypes = [vp, i32, vp, vp, i32, vp, vp]
     L.rumi_covis_set_maps.argtypes = [vp, i32, vp, vp]
     L.rumi_covis_update_connections.argtypes = [vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64]
@@ -220,7 +223,7 @@ def covis_lib():
 
 HOOK_SYMBOLS = ["rumi_hook_sort_like_std", "rumi_hook_sort_device", "rumi_hook_std_sort", "rumi_hook_quadtree", "rumi_hook_sinf", "rumi_hook_cosf",
                 "rumi_hook_fast_atan2", "rumi_hook_cv_round", "rumi_hook_magic_div", "rumi_hook_newpts_matches", "rumi_hook_lane_packing", "rumi_hook_disc_moments",
-                "rumi_hook_stream_plan", "rumi_hook_parse_hw_queues", "rumi_hook_octree_bins", "rumi_hook_compact_hist_lds", "rumi_hook_covis_read_attributes", "rumi_hook_covis_read_row"]
+                "rumi_hook_stream_plan", "rumi_hook_parse_hw_queues", "rumi_hook_octree_bins", "rumi_hook_compact_hist_lds", "rumi_hook_covis_read_attributes", "rumi_hook_covis_read_row", "rumi_hook_covis_read_poses"]
 
 
 def hooks():
@@ -248,5 +251,6 @@ def hooks():
     L.rumi_hook_compact_hist_lds.argtypes = [i32, i32, i32, C.c_float, i32, vp]
     L.rumi_hook_covis_read_attributes.argtypes = [vp, i32, vp, vp, i32]
     L.rumi_hook_covis_read_row.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.rumi_hook_covis_read_poses.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32]
     L._hooks_ready = True
     return L

@@ -96,6 +96,19 @@ class Covisibility:
         assert len(ids) == len(ref)
         return self._ret(self._lib.rumi_covis_set_point_reference(self._h, len(ids), _p(ids), _p(ref)), check)
 
+    def set_keyframe_poses(self, slots, pose7, check=True):
+        """GetPose() [n, 7] (qx qy qz qw tx ty tz) of the live slots ``slots`` (where the reference calls SetPose, beside set_keyframe_centres);
+        read by optimizer.LocalBundleAdjustmentResident."""
+        s = np.ascontiguousarray(slots, _i32).reshape(-1)
+        T = np.ascontiguousarray(pose7, np.float32).reshape(len(s), 7)
+        return self._ret(self._lib.rumi_covis_set_keyframe_poses(self._h, len(s), _p(s), _p(T)), check)
+
+    def set_point_maps(self, ids, map_ids, check=True):
+        """MapPoint::GetMap() of the points ``ids`` in the key-frames' map_id numbering."""
+        ids = np.ascontiguousarray(ids, _i32).reshape(-1); m = np.ascontiguousarray(map_ids, _i32).reshape(-1)
+        assert len(ids) == len(m)
+        return self._ret(self._lib.rumi_covis_set_point_maps(self._h, len(ids), _p(ids), _p(m)), check)
+
     def read_attributes(self, ids, from_device=False, check=True):
         """Test hook: the 64-byte attribute records [n, 64] of ``ids`` from the device copy or the host mirror; uploads nothing.  With
         check=False -> (status, records)."""
@@ -106,6 +119,14 @@ class Covisibility:
             capi.check(rc)
             return out
         return rc, out
+
+    def read_poses(self, slots=(), ids=(), from_device=False):
+        """Test hook: (pose8 [n_kf, 8] float64, has_pose [n_kf], map_id [n_pt], has_map [n_pt]) from the device copy or the host mirror."""
+        s = np.ascontiguousarray(slots, _i32).reshape(-1); p = np.ascontiguousarray(ids, _i32).reshape(-1)
+        T, hp = np.zeros((max(len(s), 1), 8), np.float64), np.zeros(max(len(s), 1), _i32)
+        m, hm = np.zeros(max(len(p), 1), _i32), np.zeros(max(len(p), 1), _i32)
+        capi.check(capi.hooks().rumi_hook_covis_read_poses(self._h, len(s), _p(s), _p(T), _p(hp), len(p), _p(p), _p(m), _p(hm), int(bool(from_device))))
+        return T[:len(s)], hp[:len(s)], m[:len(p)], hm[:len(p)]
 
     def read_row(self, slot):
         """Test hook: what the host mirror holds for a live slot -> (map-point row, bad bit of each entry's point, the key-frame's bad bit)."""

@@ -8,7 +8,16 @@ struct BawArgs {                         // one window as the C ABI hands it ove
     int32_t nKF; float *kf_pose7; const uint8_t *kf_fixed; int32_t nMP; float *mp_pos3;
     int32_t nE; const int32_t *e_mp, *e_kf; const float *e_obs, *e_inv_sigma2; const float *K4;
     const volatile uint8_t *stop_flag; uint8_t *erase_out; int32_t *stats;
+    bool resident = false;               // the raw block already lies in the arena's stage.d (ba_resident_host.inc): mp_pos3 and the e_* arrays are not read
 };
+// Where the raw arrays of a window lie in the arena's upload block: poses as doubles, positions, column blocks, then the edges as they came.
+struct BawRawLayout { size_t oT, oX, oPC, oEM, oEK, oOb, oIn, upBytes; };
+static BawRawLayout baw_raw_layout(int nKF, int nMP, int nE) {
+    BawRawLayout r;
+    r.oT = 0; r.oX = al16(r.oT + (size_t)nKF * 64); r.oPC = al16(r.oX + (size_t)nMP * 12); r.oEM = al16(r.oPC + (size_t)nKF * 4); r.oEK = al16(r.oEM + (size_t)nE * 4);
+    r.oOb = al16(r.oEK + (size_t)nE * 4); r.oIn = al16(r.oOb + (size_t)nE * 8); r.upBytes = al16(r.oIn + (size_t)nE * 4);
+    return r;
+}
 struct BawPrep {                         // what staging a window leaves behind
     int nOpt = 0, n = 0, NP = 0, NT = 0;
     size_t rT = 0, rX = 0, rE = 0, rErr = 0, dnBytes = 0, outOff = 0;
@@ -34,22 +43,24 @@ static int baw_stage(BaArena *c, hipStream_t st, int mode, const BawArgs &a, int
     int nOpt = 0;
     for (int k = 0; k < nKF; k++) nOpt += a.kf_fixed[k] ? 0 : 1;
     const int n = 6 * nOpt;
-    // ONE pinned block up: the caller's arrays as they came (the structure -- g2o's buildStructure -- is derived on the device, k_baws_*), the
-    // initial poses as doubles, the column blocks
-    const size_t oT = 0, oX = al16(oT + (size_t)nKF * 64), oPC = al16(oX + (size_t)nMP * 12), oEM = al16(oPC + (size_t)nKF * 4), oEK = al16(oEM + (size_t)nE * 4),
-                 oOb = al16(oEK + (size_t)nE * 4), oIn = al16(oOb + (size_t)nE * 8), upBytes = al16(oIn + (size_t)nE * 4);
+    // The raw block: the caller's arrays as they came (the structure -- g2o's buildStructure -- is derived on the device, k_baws_*), the initial
+    // poses as doubles, the column blocks.  ONE pinned block up, or, for a resident window, what the fill kernels left there (ba_resident.inc).
+    const BawRawLayout rl = baw_raw_layout(nKF, nMP, nE);
+    const size_t oT = rl.oT, oX = rl.oX, oPC = rl.oPC, oEM = rl.oEM, oEK = rl.oEK, oOb = rl.oOb, oIn = rl.oIn, upBytes = rl.upBytes;
     if (upBytes > c->stage.cap) { g_lastError = "local BA: upload block larger than the optimiser's arenas"; return RUMI_E_CAPACITY; }
-    uint8_t *hs = c->stage.h;
-    ba_stage_poses(nKF, a.kf_pose7, reinterpret_cast<double *>(hs + oT));
-    {
-        int32_t *poseCol = reinterpret_cast<int32_t *>(hs + oPC);
-        int cc = 0;
-        for (int k = 0; k < nKF; k++) poseCol[k] = a.kf_fixed[k] ? -1 : cc++;
+    if (!a.resident) {
+        uint8_t *hs = c->stage.h;
+        ba_stage_poses(nKF, a.kf_pose7, reinterpret_cast<double *>(hs + oT));
+        {
+            int32_t *poseCol = reinterpret_cast<int32_t *>(hs + oPC);
+            int cc = 0;
+            for (int k = 0; k < nKF; k++) poseCol[k] = a.kf_fixed[k] ? -1 : cc++;
+        }
+        std::memcpy(hs + oX, a.mp_pos3, (size_t)nMP * 12);
+        std::memcpy(hs + oEM, a.e_mp, (size_t)nE * 4); std::memcpy(hs + oEK, a.e_kf, (size_t)nE * 4);
+        std::memcpy(hs + oOb, a.e_obs, (size_t)nE * 8); std::memcpy(hs + oIn, a.e_inv_sigma2, (size_t)nE * 4);
+        HIP_TRY(hipMemcpyAsync(c->stage.d, hs, upBytes, hipMemcpyHostToDevice, st));
     }
-    std::memcpy(hs + oX, a.mp_pos3, (size_t)nMP * 12);
-    std::memcpy(hs + oEM, a.e_mp, (size_t)nE * 4); std::memcpy(hs + oEK, a.e_kf, (size_t)nE * 4);
-    std::memcpy(hs + oOb, a.e_obs, (size_t)nE * 8); std::memcpy(hs + oIn, a.e_inv_sigma2, (size_t)nE * 4);
-    HIP_TRY(hipMemcpyAsync(c->stage.d, hs, upBytes, hipMemcpyHostToDevice, st));
     const int NP = (n + 1 + 15) / 16 * 16, NT = NP / 16;
     Wd = BAWin{};
     Wd.nKF = nKF; Wd.nMP = nMP; Wd.nE = nE; Wd.nOpt = nOpt; Wd.n = n; Wd.NP = NP; Wd.NT = NT; Wd.nT = NT * (NT + 1) / 2;

@@ -12,6 +12,8 @@
 //   feat   the key-frames' constant part, a byte arena of its own with no host mirror (covis_features.inc)
 //   centre, ref  allocated with the first rumi_covis_set_keyframe_centres / rumi_covis_set_point_reference; read by
 //          rumi_refresh_map_points_resident (refresh_resident.inc) and by nothing else
+//   pose, ptMap  allocated with the first rumi_covis_set_keyframe_poses / rumi_covis_set_point_maps (covis_lba.inc); read by
+//          rumi_local_ba_resident (ba_resident.inc) and by nothing else
 // The host keeps a mirror of kf, pt, attr and the arena; an edit writes the mirror and notes (table, offset, words).  The next query packs the noted
 // ranges and its own input into one pinned block, sends it with one copy, and k_covis_apply scatters it.
 //
@@ -34,16 +36,17 @@
 #include "rumi_covis.h"
 #include "covis_view.h"
 #include "keyframe_features.h"
+#include "opt_math.h"
 
 namespace rumi {
 namespace {
 
 constexpr int kThreads = 256;
 // short names of covis_view.h's layout for the kernels and the mirror code of this file
-constexpr int KFW = kCovisKfWords, PTW = kCovisPointWords, ATW = kCovisAttrWords, CTW = kCovisCentreWords, FTW = kCovisFeatTabWords;
+constexpr int KFW = kCovisKfWords, PTW = kCovisPointWords, ATW = kCovisAttrWords, CTW = kCovisCentreWords, FTW = kCovisFeatTabWords, PSW = kCovisPoseWords;
 constexpr int K_MPOFF = kCovisKfMpOff, K_MPLEN = kCovisKfMpLen, K_CHOFF = kCovisKfChOff, K_CHLEN = kCovisKfChLen, K_FLAGS = kCovisKfFlags,
               K_MAP = kCovisKfMap, K_PARENT = kCovisKfParent, K_KEY = kCovisKfKey, K_BEST = kCovisKfBest;
-constexpr int T_KF = 0, T_PT = 1, T_ARENA = 2, T_ATTR = 3, T_FEAT = 4, T_CENTRE = 5, T_REF = 6, kTables = 7;
+constexpr int T_KF = 0, T_PT = 1, T_ARENA = 2, T_ATTR = 3, T_FEAT = 4, T_CENTRE = 5, T_REF = 6, T_POSE = 7, T_PTMAP = 8, kTables = 9;
 constexpr uint16_t kNone = 0xFFFF;                     // sorts last; slots stay below RUMI_COVIS_MAX_KEYFRAMES
 constexpr int kPosBits = 13;
 static_assert((1 << kPosBits) == RUMI_COVIS_MAX_KEYFRAMES, "position bits of the packed maximum");
@@ -343,6 +346,9 @@ struct RumiCovis {
     std::vector<int32_t> featTab;                    // [max_kf][FTW]
     std::vector<int32_t> centre, ref;                // [max_kf][CTW], [max_points]: empty until their first edit
     int32_t hiRef = 0;                               // highest point id whose reference was ever set + 1
+    std::vector<int32_t> pose, ptMap;                // [max_kf][PSW] (eight doubles a slot), [max_points]: empty until their first edit
+    std::vector<float> pose7;                        // [max_kf][7] the floats the poses were staged from (host only)
+    int32_t hiMap = 0;                               // highest point id whose map was ever set + 1
     int32_t hiAttr = 0;                              // highest point id with attributes + 1
     std::vector<int32_t> capMp, capCh, capObs;       // places of the rows in the arena (entries); 0 = never placed
     int64_t tail = 0, live = 0;
@@ -353,9 +359,9 @@ struct RumiCovis {
     int32_t stampKf = 0, stampPt = 0;
     // staged edits
     std::vector<int4> recs;                          // table, first word, -, words
-    bool full[kTables] = {true, true, true, true, true, true, true};
+    bool full[kTables] = {true, true, true, true, true, true, true, true, true};
     // device
-    DevBuf<int32_t> dKf, dPt, dArena, dAttr, dFeatTab, dCentre, dRef;       // dKf, dPt, dTag: with the first bind; dAttr, dRowOf: with their first use; dArena follows the mirror
+    DevBuf<int32_t> dKf, dPt, dArena, dAttr, dFeatTab, dCentre, dRef, dPose, dPtMap;       // dKf, dPt, dTag: with the first bind; dAttr, dRowOf: with their first use; dArena follows the mirror
     DevBuf<unsigned long long> dTag, dRowOf;
     std::vector<uint8_t> extra;                      // the input block of rumi_track_local_map: frame points and the discarded outliers
     StageClock clock;                                // of the query in flight (the local-map query is launched and read in two calls)
@@ -456,8 +462,17 @@ int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) 
         HIP_TRY(hipMemsetAsync(h->dRef.p, 0, h->ref.size() * 4, nullptr));     // ids above hiRef: no reference
         h->full[T_REF] = true;
     }
-    int32_t *dBase[kTables] = {h->dKf.p, h->dPt.p, h->dArena.p, h->dAttr.p, h->dFeatTab.p, h->dCentre.p, h->dRef.p};
-    const std::vector<int32_t> *mirror[kTables] = {&h->kf, &h->pt, &h->arena, &h->attr, &h->featTab, &h->centre, &h->ref};
+    if (!h->pose.empty() && !h->dPose.p) {
+        if ((rc = h->dPose.reserve(h->pose.size(), h->pose.size())) != RUMI_OK) return rc;
+        h->full[T_POSE] = true;
+    }
+    if (!h->ptMap.empty() && !h->dPtMap.p) {
+        if ((rc = h->dPtMap.reserve(h->ptMap.size(), h->ptMap.size())) != RUMI_OK) return rc;
+        HIP_TRY(hipMemsetAsync(h->dPtMap.p, 0, h->ptMap.size() * 4, nullptr));     // ids above hiMap: never read (no "has map" bit)
+        h->full[T_PTMAP] = true;
+    }
+    int32_t *dBase[kTables] = {h->dKf.p, h->dPt.p, h->dArena.p, h->dAttr.p, h->dFeatTab.p, h->dCentre.p, h->dRef.p, h->dPose.p, h->dPtMap.p};
+    const std::vector<int32_t> *mirror[kTables] = {&h->kf, &h->pt, &h->arena, &h->attr, &h->featTab, &h->centre, &h->ref, &h->pose, &h->ptMap};
     size_t words = 0, nRec = 0;
     for (int4 &r : h->recs)
         if (!h->full[r.x]) { r.z = (int)words; words += (size_t)r.w; h->recs[nRec++] = r; }
@@ -467,7 +482,7 @@ int flush(RumiCovis *h, const void *extra, size_t extraBytes, uint8_t **dExtra) 
     h->lastUpload = (int64_t)bytes;
     for (int t = 0; t < kTables; t++)
         if (h->full[t]) {
-            const size_t n = t == T_ARENA ? (size_t)h->tail : t == T_ATTR ? (size_t)h->hiAttr * ATW : t == T_REF ? (size_t)h->hiRef : mirror[t]->size();
+            const size_t n = t == T_ARENA ? (size_t)h->tail : t == T_ATTR ? (size_t)h->hiAttr * ATW : t == T_REF ? (size_t)h->hiRef : t == T_PTMAP ? (size_t)h->hiMap : mirror[t]->size();
             if (n) HIP_TRY(hipMemcpyAsync(dBase[t], mirror[t]->data(), n * 4, hipMemcpyHostToDevice, nullptr));
             h->lastUpload += (int64_t)n * 4;
         }
@@ -494,7 +509,7 @@ inline bool is_live(const RumiCovis *h, int32_t s) { return s >= 0 && s < h->max
 // Where the tables lie right now (after flush and feat_flush).
 void fill_view(const RumiCovis *h, CovisView *v) {
     *v = CovisView{h->dKf.p, h->dPt.p, h->dArena.p, h->dAttr.p, h->dFeatTab.p, h->feat.arena.p, h->dCentre.p, h->dRef.p,
-                   h->feat.oct.p, h->feat.octStride, h->maxKf, h->maxPts, h->dev.device};
+                   h->feat.oct.p, h->feat.octStride, h->maxKf, h->maxPts, h->dev.device, reinterpret_cast<const double *>(h->dPose.p), h->dPtMap.p};
 }
 
 }  // namespace
@@ -672,7 +687,7 @@ static int set_points_impl(RumiCovis *h, const char *entry, int32_t n, const int
             src = packed.data();
         }
         set_row(h, h->pt[(size_t)p * PTW], h->pt[(size_t)p * PTW + 1], h->capObs[p], src, no);
-        h->pt[(size_t)p * PTW + 2] = (is_bad[i] ? 1 : 0) | (withFeatures ? kCovisPointHasObsFeatures : 0);
+        h->pt[(size_t)p * PTW + 2] = (is_bad[i] ? 1 : 0) | (withFeatures ? kCovisPointHasObsFeatures : 0) | (h->pt[(size_t)p * PTW + 2] & kCovisPointHasMap);
         note(h, T_PT, (int64_t)p * PTW, PTW);
     }
     return RUMI_OK;
@@ -961,6 +976,7 @@ extern "C" int rumi_covis_local_map(RumiCovis *h, int32_t n, const int32_t *fram
 
 #include "covis_features.inc"
 #include "covis_refresh.inc"
+#include "covis_lba.inc"
 
 extern "C" int rumi_covis_stage_ms(const RumiCovis *h, float *out3) {
     if (!h || !out3) return RUMI_E_INVALID;

@@ -12,7 +12,7 @@ typedef struct RumiCovis RumiCovis;
 namespace rumi {
 
 // ---- the records, all of 32-bit words ---------------------------------------------------------------------------------------------------
-//   kf      [max_kf][20]      mp row (offset, length), children row (offset, length), flags, map, parent, -, order_key (two words), best[10]
+//   kf      [max_kf][20]      mp row (offset, length), children row (offset, length), flags, map, parent, has pose, order_key (two words), best[10]
 //   pt      [max_points][4]   observer row (offset, length), flags, has attributes
 //   attr    [max_points][16]  position 3, normal 3, min distance, max distance (f32), descriptor 8 words: two 16-byte aligned halves
 //   rows                      the row arena: mp rows (point ids, -1 none), children rows, observer rows (observer words)
@@ -20,11 +20,14 @@ namespace rumi {
 //   centre  [max_kf][4]       GetCameraCenter() (3 x f32), has centre
 //   ref     [max_points]      GetReferenceKeyFrame() as slot + 1, 0: none
 //   oct     [max_kf][stride]  keys[i].octave of every slot that holds features (bytes)
-constexpr int kCovisKfWords = 20, kCovisPointWords = 4, kCovisAttrWords = 16, kCovisFeatTabWords = 4, kCovisCentreWords = 4;
+//   pose    [max_kf][16]      GetPose() as the bundle adjustment reads it: eight doubles (unit quaternion x y z w, translation, 0), what
+//                             ba_stage_poses makes of the caller's seven floats; "has pose" is word 7 of the kf record
+//   ptMap   [max_points]      MapPoint::GetMap() in the key-frames' map_id numbering; "has map" is a bit of the pt record's flags word
+constexpr int kCovisKfWords = 20, kCovisPointWords = 4, kCovisAttrWords = 16, kCovisFeatTabWords = 4, kCovisCentreWords = 4, kCovisPoseWords = 16;
 constexpr int kCovisKfMpOff = 0, kCovisKfMpLen = 1, kCovisKfChOff = 2, kCovisKfChLen = 3, kCovisKfFlags = 4, kCovisKfMap = 5, kCovisKfParent = 6,
-              kCovisKfKey = 8, kCovisKfBest = 10;
+              kCovisKfHasPose = 7, kCovisKfKey = 8, kCovisKfBest = 10;
 constexpr int kCovisKfBad = 1, kCovisKfLive = 2;                       // the kf record's flags word
-constexpr int kCovisPointBad = 1, kCovisPointHasObsFeatures = 2;       // the pt record's flags word
+constexpr int kCovisPointBad = 1, kCovisPointHasObsFeatures = 2, kCovisPointHasMap = 4;       // the pt record's flags word
 constexpr int kCovisAttrDesc = 8;                                      // first descriptor word of an attr record
 constexpr int kCovisObsSlotBits = 13, kCovisObsSlotMask = (1 << kCovisObsSlotBits) - 1;   // an observer word: slot | feature << 13
 
@@ -70,6 +73,7 @@ struct CovisPoint {
     __device__ __forceinline__ int obs_len() const { return w.y; }            // Observations() of the monocular model
     __device__ __forceinline__ bool bad() const { return (w.z & kCovisPointBad) != 0; }
     __device__ __forceinline__ bool has_obs_features() const { return (w.z & kCovisPointHasObsFeatures) != 0; }
+    __device__ __forceinline__ bool has_map() const { return (w.z & kCovisPointHasMap) != 0; }    // (the map itself: CovisView::point_map)
     __device__ __forceinline__ int has_attr() const { return w.w; }           // (the table itself may still be missing: CovisView::has_attr)
 };
 // The eight floats of an attribute record, read as two 16-byte loads.
@@ -98,7 +102,7 @@ struct CovisKeyFrame {
 
 // Where the store's tables lie on the device after covis_view; passed to kernels by value.  A pointer is null until the table exists: attr
 // (no point has attributes), centre and ref (never set), feat (no key-frame has features), oct (no covis_view with kCovisWantOctaves yet; up to
-// date only in a view that asked for it).
+// date only in a view that asked for it), pose and ptMap (never set).
 struct CovisView {
     const int32_t *kf, *pt, *rows;
     int32_t *attr;                     // written in place by the refresh entry's write-back only
@@ -107,6 +111,8 @@ struct CovisView {
     const int32_t *centre, *ref;
     const uint8_t *oct;
     int octStride, maxKf, maxPoints, device;
+    const double *pose;
+    const int32_t *ptMap;
 
     // point record
     __device__ __forceinline__ CovisPoint point(int p) const { return CovisPoint{*reinterpret_cast<const int4 *>(pt + (size_t)p * kCovisPointWords)}; }
@@ -126,6 +132,8 @@ struct CovisView {
     __device__ __forceinline__ int kf_row_entry(int slot, int f) const { return rows[kf[slot * kCovisKfWords + kCovisKfMpOff] + f]; }       // one index sum
     __device__ __forceinline__ int kf_row_len(int slot) const { return kf[slot * kCovisKfWords + kCovisKfMpLen]; }
     __device__ __forceinline__ bool kf_bad(int slot) const { return (kf[slot * kCovisKfWords + kCovisKfFlags] & kCovisKfBad) != 0; }
+    __device__ __forceinline__ int kf_map(int slot) const { return kf[slot * kCovisKfWords + kCovisKfMap]; }
+    __device__ __forceinline__ unsigned long long kf_key(int slot) const { return *reinterpret_cast<const unsigned long long *>(kf + slot * kCovisKfWords + kCovisKfKey); }
     // featTab
     __device__ __forceinline__ long long feat_keys(int slot) const { return *reinterpret_cast<const long long *>(featTab + slot * kCovisFeatTabWords); }     // < 0: none
     __device__ __forceinline__ int feat_count(int slot) const { return featTab[slot * kCovisFeatTabWords + 2]; }
@@ -136,6 +144,10 @@ struct CovisView {
     __device__ __forceinline__ const RumiKeyPoint *keys_of(const CovisSlotRef &s) const { return keys_at(s.block + kCovisFeatKeysOffset); }
     __device__ __forceinline__ const int32_t *mp_row(const CovisSlotRef &s) const { return rows + s.mpOff; }
     __device__ __forceinline__ CovisKeyFrame key_frame(const CovisSlotRef &s) const { return CovisKeyFrame{rec(s.block), mp_row(s)}; }
+    // pose (eight doubles), the point's map
+    __device__ __forceinline__ bool has_pose(int slot) const { return pose && kf[slot * kCovisKfWords + kCovisKfHasPose]; }
+    __device__ __forceinline__ const double *pose_of(int slot) const { return pose + (size_t)slot * (kCovisPoseWords / 2); }
+    __device__ __forceinline__ int point_map(int p) const { return ptMap[p]; }                    // meaningful where the point has_map()
     // centre, reference slot, octave
     __device__ __forceinline__ float4 centre_of(int slot) const { return *reinterpret_cast<const float4 *>(centre + slot * kCovisCentreWords); }   // w != 0: has centre
     __device__ __forceinline__ int ref_slot(int p) const { return ref ? ref[p] - 1 : -1; }
@@ -199,5 +211,18 @@ struct CovisLocalView {
 int covis_local_map_launch(RumiCovis *c, int n, const int32_t *frame_points, const CovisDiscarded *d, int wantDevice, const char *entry, CovisLocalView *view);
 // Both headers, the frame's bad flags [nFrame] and the local key-frames, as host pointers into the store's pinned block (synchronises).
 int covis_local_map_read(RumiCovis *c, const CovisLocalView &v, const int32_t **head8, const uint8_t **frameBad, const int32_t **localKf);
+
+// ---- the window of rumi_local_ba_resident (opt.hip, ba_resident_host.inc), host only, from the store's mirror ---------------------------
+// lLocalKeyFrames (Optimizer.cc:1007-1017): the current slot, then the neighbours that are not bad and share its map, in the caller's order.
+struct CovisLbaWindow { int32_t nLocal, initIdx, hiSlot, curMap, maxRow; int64_t sumRows; float K4[4]; };
+// Validates (cur live with features; neighbours live, distinct, never cur; init -1 or a slot), then fills locals [n_neigh + 1], role
+// [RUMI_COVIS_MAX_KEYFRAMES] (the index in locals, -1 for every other slot; hiSlot of them are meaningful.  A neighbour dropped as bad or of
+// another map needs no role of its own: the tests that dropped it keep it from being a fixed camera, Optimizer.cc:1050) and *w (initIdx: where init lies in locals or -1; maxRow / sumRows: the longest local
+// map-point row and their total; K4: the current slot's).  Refused with RUMI_E_INVALID and the message set.
+int covis_lba_window(RumiCovis *c, int32_t cur, const int32_t *neigh, int32_t nNeigh, int32_t init, const char *entry, int32_t *locals, int32_t *role, CovisLbaWindow *w);
+// The seven floats rumi_covis_set_keyframe_poses was given for the slot (zeros where it has none).
+void covis_lba_pose7(const RumiCovis *c, int32_t slot, float *pose7);
+// The mirror's half of the position write-back: attribute record of ids[i] takes pos3[i].  No edit is staged (the device half is the caller's kernel).
+void covis_lba_write_positions(RumiCovis *c, int32_t n, const int32_t *ids, const float *pos3);
 
 }  // namespace rumi

@@ -13,6 +13,7 @@
 //   sim3.inc            k_sim3_inliers / ransac / opt.  Host: sim3_host.inc
 //   ba_windows.inc      k_baw_* / k_baws_*: local BA with the window as a batch dimension.  Host: ba_windows_host.inc
 //   essential.inc       k_eg_*: OptimizeEssentialGraph.  Host: essential_host.inc
+//   ba_resident.inc     k_lba_*: the local window assembled from the covisibility store (rumi_local_ba_resident).  Host: ba_resident_host.inc
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +33,8 @@
 #include "rumi_internal.h"
 #include "rumi_common.h"
 #include "rumi_opt.h"
+#include "rumi_covis.h"
+#include "covis_view.h"
 
 namespace rumi {
 
@@ -47,6 +50,7 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 #include "sim3_batch.inc"
 #include "ba_windows.inc"
 #include "essential.inc"
+#include "ba_resident.inc"
 
 }  // namespace rumi
 
@@ -168,6 +172,17 @@ struct BaProfile {
     float kernelMs[4] = {0};          // hpp, syrk, solve (ms over the call), trials
 };
 
+// rumi_local_ba_resident (ba_resident_host.inc): what the assembly of a window needs beyond the handle's own arena, taken by the first call
+struct LbaResident {
+    MirrorBuf<uint8_t> in, out;      // locals and roles up; the head, the key-frame list, the point ids and the erase list back
+    DevBuf<uint8_t> work, edge;      // lists, counts and stamps of one call; per edge the observer word and the erase list
+    DevBuf<unsigned long long> ptTag;   // [max_points of the store] first-occurrence stamps, epoch << 32 | priority
+    EventHold ev;                    // the assembly (null stream) before the runner's stream
+    uint32_t epoch = 0;
+    std::vector<int32_t> locals, role;
+    void count(Footprint &f) const { f.add(in, out, work, edge, ptTag); }
+};
+
 constexpr int kBaMaxWorkers = 16;
 struct RumiOptimizer {
     int device = 0;
@@ -181,6 +196,7 @@ struct RumiOptimizer {
     BaContext workers[kBaMaxWorkers];
     // essential graph (essential_host.inc): the dense matrix and one block for the rest, taken by the first rumi_essential_graph call
     DevBuf<uint8_t> egA, eg;
+    LbaResident lba;
 };
 
 extern "C" void rumi_opt_destroy(RumiOptimizer *o) {
@@ -210,7 +226,7 @@ extern "C" int rumi_opt_create(int32_t max_pose_edges, int32_t max_pose_batch, i
 extern "C" int rumi_opt_footprint(const RumiOptimizer *o, int64_t out2[2]) {
     if (!o || !out2) return RUMI_E_INVALID;
     Footprint f;
-    o->pose.count(f); o->ba.count(f); f.add(o->egA, o->eg);
+    o->pose.count(f); o->ba.count(f); f.add(o->egA, o->eg); o->lba.count(f);
     for (const auto &a : o->batchArenas) a.count(f);
     for (const auto &r : o->batchRunners) r.count(f);
     for (const auto &w : o->workers) w.count(f);
@@ -261,3 +277,4 @@ static int fetch_published_scalars(BaArena::HostLoop &s, hipStream_t st) {
 #include "ba_single_host.inc"
 #include "sim3_host.inc"
 #include "sim3_batch_host.inc"
+#include "ba_resident_host.inc"

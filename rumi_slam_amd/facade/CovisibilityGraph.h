@@ -135,6 +135,46 @@ template <class KeyFrameT, class MapPointT> class CovisibilityGraph {
         return rc;
     }
 
+    // ---- what Optimizer::LocalBundleAdjustmentResident (Optimizer.h) reads beside rows, observers, features and attributes: GetPose() of the
+    // key-frames (rumi_covis_set_keyframe_poses; after SetPose, beside SyncCentres) and GetMap() of the points (rumi_covis_set_point_maps; where
+    // a point is created, and where a merge moves it to another map).  Objects the store has not seen are staged first.
+    int SyncPoses(const std::vector<KeyFrameT *> &vpKFs) {
+        if (!h_) return RUMI_E_INVALID;
+        std::vector<KeyFrameT *> unseen;
+        std::set<KeyFrameT *> in;
+        for (KeyFrameT *k : vpKFs)
+            if (k && in.insert(k).second && !slot_.count(k)) unseen.push_back(k);
+        int rc;
+        if (!unseen.empty() && (rc = sync_keyframes(unseen)) != RUMI_OK) return rc;
+        std::vector<int32_t> slots;
+        std::vector<float> T7;
+        for (KeyFrameT *k : in) {
+            slots.push_back(slot_[k]);
+            const auto T = k->GetPose(); const auto q = T.unit_quaternion(); const auto t = T.translation();
+            const float p[7] = {q.x(), q.y(), q.z(), q.w(), t(0), t(1), t(2)};
+            T7.insert(T7.end(), p, p + 7);
+        }
+        if (slots.empty()) return RUMI_OK;
+        rc = rumi_covis_set_keyframe_poses(h_, (int32_t)slots.size(), slots.data(), T7.data());
+        if (rc != RUMI_OK) rumi_facade::report("CovisibilityGraph::SyncPoses", rc);
+        return rc;
+    }
+    int SyncPointMaps(const std::vector<MapPointT *> &vpMPs) {
+        if (!h_) return RUMI_E_INVALID;
+        std::vector<MapPointT *> unseen;
+        std::set<MapPointT *> in;
+        for (MapPointT *p : vpMPs)
+            if (p && in.insert(p).second && !id_.count(p)) unseen.push_back(p);
+        int rc;
+        if (!unseen.empty() && (rc = sync_points(unseen)) != RUMI_OK) return rc;
+        std::vector<int32_t> ids, maps;
+        for (MapPointT *p : in) { ids.push_back(id_[p]); maps.push_back((int32_t)p->GetMap()->GetId()); }
+        if (ids.empty()) return RUMI_OK;
+        rc = rumi_covis_set_point_maps(h_, (int32_t)ids.size(), ids.data(), maps.data());
+        if (rc != RUMI_OK) rumi_facade::report("CovisibilityGraph::SyncPointMaps", rc);
+        return rc;
+    }
+
     // ---- the key-frame's constant part (mvKeysUn, mDescriptors, mvScaleFactors, mFeatVec, fx fy cx cy): rumi_covis_set_keyframe_features.
     // SyncFeatures is called once, where the key-frame enters the graph (after ComputeBoW: mFeatVec must be final); DropFeatures from
     // KeyFrame::SetBadFlag.  rumi::LocalMappingStep::CreateNewMapPointsResident then names slots instead of uploading key-frames.

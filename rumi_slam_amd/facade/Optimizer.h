@@ -15,6 +15,11 @@
 
 #include "rumi_opt.h"
 #include "rumi_status.h"
+#ifdef RUMI_HAVE_SOPHUS
+#include <cstring>
+#include <type_traits>
+#include "MapPointRefresh.h"     // LocalBundleAdjustmentResident hands UpdateNormalAndDepth of the window to RefreshMapPointsResident
+#endif
 
 // capacity of the per-thread optimiser arenas (key-frames incl. fixed ones, map points, observations of one call)
 #ifndef RUMI_OPT_MAX_KF
@@ -304,6 +309,83 @@ public:
     }
 
 #ifdef RUMI_HAVE_SOPHUS
+    // The same member over a CovisibilityGraph that holds the map (rumi_local_ba_resident, include/rumi_opt.h): the walk of the live objects
+    // above (:1003-1271) is replaced by one device call that names slots; the host replays :1327-1351 on the objects in the returned order.
+    // The store must be current for the window: Sync of its key-frames and points, SyncFeatures, SyncAttributes, SyncReferences, SyncCentres,
+    // SyncPoses and SyncPointMaps.  Afterwards the store is synced by what changed here (rows and observer rows of the erased
+    // observations, references, centres; positions and poses are already there), and UpdateNormalAndDepth of all window points goes as one
+    // RefreshMapPointsResident (normal and depth) instead of the per-point loop.  A raised stop flag returns before anything is written,
+    // the counters included.  Errors are reported (rumi_status.h) and nothing is written; no fixed key-frame returns silently as upstream.
+    template <class GraphT, class KeyFrameT, class MapT>
+    static void LocalBundleAdjustmentResident(GraphT &graph, KeyFrameT *pKF, bool *pbStopFlag, MapT *pMap, int &num_fixedKF, int &num_OptKF, int &num_MPs, int &num_edges) {
+        using MapPointT = typename std::remove_pointer<typename std::decay<decltype(pKF->GetMapPointMatches()[0])>::type>::type;
+        static const char *where = "Optimizer::LocalBundleAdjustmentResident";
+        const int32_t cur = graph.SlotOf(pKF);
+        std::vector<int32_t> neigh;
+        int32_t init = -1;
+        bool seen = cur >= 0;
+        if (seen && pKF->mnId == pMap->GetInitKFid()) init = cur;
+        for (KeyFrameT *pKFi : pKF->GetVectorCovisibleKeyFrames()) {
+            const int32_t s = graph.SlotOf(pKFi);
+            seen = seen && s >= 0;
+            neigh.push_back(s);
+            if (pKFi->mnId == pMap->GetInitKFid()) init = s;             // a local key-frame is a fixed vertex iff it is the initial one (:1094)
+        }
+        if (!seen) { rumi_facade::report(where, RUMI_E_INVALID, "the current key-frame or a covisible one has not been synced to the graph"); return; }
+        const int kfCap = graph.KeyFrameCount(), mpCap = graph.PointCount();
+        thread_local std::vector<int32_t> erased(3 << 12);
+        std::vector<int32_t> kfSlots(kfCap), mpIds(mpCap);
+        std::vector<float> kfPose((size_t)kfCap * 7), mpPos((size_t)mpCap * 3);
+        RumiLbaResidentOut out{};
+        int rc;
+        for (;;) {
+            out = RumiLbaResidentOut{};
+            out.kf_cap = kfCap; out.mp_cap = mpCap; out.erase_cap = (int32_t)(erased.size() / 3);
+            out.kf_slots = kfSlots.data(); out.kf_pose7 = kfPose.data(); out.mp_ids = mpIds.data(); out.mp_pos3 = mpPos.data(); out.erased = erased.data();
+            rc = rumi_local_ba_resident(arena(), graph.handle(), cur, neigh.data(), (int32_t)neigh.size(), init, reinterpret_cast<const volatile uint8_t *>(pbStopFlag), &out);
+            if (rc != RUMI_E_CAPACITY) break;
+            const char *msg = rumi_last_error();
+            if (msg && std::strstr(msg, "erase_cap")) { if (erased.size() > ((size_t)3 << 26)) break; erased.resize(erased.size() * 2); }   // nothing was written: solve again
+            else if (!grow_arena()) break;
+        }
+        if (rc == RUMI_E_INVALID && rumi_last_error() && std::strncmp(rumi_last_error(), "LM-LBA", 6) == 0) return;                 // :1057-1060
+        if (rc != RUMI_OK) { rumi_facade::report(where, rc); return; }
+        if (out.stats[3]) return;                                                            // :1274-1276
+        num_fixedKF = out.num_fixedKF; num_OptKF = out.num_OptKF; num_MPs = out.num_MPs; num_edges = out.num_edges;
+        std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                             // :1325
+        std::vector<KeyFrameT *> rowChanged, locals;
+        std::vector<MapPointT *> obsChanged, window;
+        std::set<KeyFrameT *> inK;
+        std::set<MapPointT *> inP;
+        for (int i = 0; i < out.n_erased; i++) {                                             // :1327-1334, in edge order
+            KeyFrameT *pKFi = graph.KeyFrameAt(erased[3 * i]);
+            MapPointT *pMPi = graph.PointAt(erased[3 * i + 1]);
+            if (pMPi->isBad()) continue;                                                     // went bad since the call (:1289)
+            pKFi->EraseMapPointMatch(pMPi);
+            pMPi->EraseObservation(pKFi);
+            if (inK.insert(pKFi).second) rowChanged.push_back(pKFi);
+            if (inP.insert(pMPi).second) obsChanged.push_back(pMPi);
+        }
+        for (int k = 0; k < out.num_OptKF; k++) {                                            // :1338-1344
+            const float *T7 = &kfPose[(size_t)k * 7];
+            KeyFrameT *pKFi = graph.KeyFrameAt(kfSlots[k]);
+            pKFi->SetPose(Sophus::SE3f(Eigen::Quaternionf(T7[3], T7[0], T7[1], T7[2]), Eigen::Vector3f(T7[4], T7[5], T7[6])));
+            locals.push_back(pKFi);
+        }
+        for (int p = 0; p < out.num_MPs; p++) {                                              // :1347-1350
+            MapPointT *pMP = graph.PointAt(mpIds[p]);
+            pMP->SetWorldPos(Eigen::Vector3f(mpPos[3 * p], mpPos[3 * p + 1], mpPos[3 * p + 2]));
+            window.push_back(pMP);
+        }
+        // the store, by what changed: the device call left positions and poses there already
+        bool ok = true;
+        for (KeyFrameT *k : rowChanged) ok = ok && graph.Sync(k) == RUMI_OK;
+        for (MapPointT *p : obsChanged) ok = ok && graph.Sync(p) == RUMI_OK;
+        ok = ok && graph.SyncReferences(obsChanged) == RUMI_OK && graph.SyncCentres(locals) == RUMI_OK;
+        if (ok) rumi_facade::RefreshMapPointsResident(graph, window, RUMI_REFRESH_NORMAL_DEPTH);   // :1351, every window point in one call
+        pMap->IncreaseChangeIndex();
+    }
+
     // void static BundleAdjustment(const vector<KeyFrame *> &vpKFs, const vector<MapPoint *> &vpMP, int nIterations = 5, bool *pbStopFlag = NULL,
     //                              const unsigned long nLoopKF = 0, const bool bRobust = true)                Optimizer.cc:54-351 (monocular edges)
     template <class KeyFrameT, class MapPointT>

@@ -25,6 +25,13 @@ assert SIM3_RANSAC_SOLVER_DTYPE.itemsize == 52 and SIM3_RANSAC_RESULT_DTYPE.item
 SIM3_NOT_REACHED, SIM3_CONVERGED, SIM3_EXHAUSTED, SIM3_WINDOW_ENDED = 0, 1, 2, 3
 
 
+class RumiLbaResidentOut(C.Structure):
+    """include/rumi_opt.h RumiLbaResidentOut"""
+    _fields_ = [("kf_cap", C.c_int32), ("mp_cap", C.c_int32), ("erase_cap", C.c_int32), ("kf_slots", C.c_void_p), ("kf_pose7", C.c_void_p),
+                ("mp_ids", C.c_void_p), ("mp_pos3", C.c_void_p), ("erased", C.c_void_p), ("n_kf", C.c_int32), ("num_OptKF", C.c_int32),
+                ("num_fixedKF", C.c_int32), ("num_MPs", C.c_int32), ("num_edges", C.c_int32), ("n_erased", C.c_int32), ("stats", C.c_int32 * 4)]
+
+
 def _lib():
     L = capi.lib()
     if getattr(L, "_opt_ready", False):
@@ -37,6 +44,7 @@ def _lib():
     L.rumi_pose_optimization_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rumi_local_ba.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rumi_local_ba_batch.argtypes = [vp, i32, vp, i32]
+    L.rumi_local_ba_resident.argtypes = [vp, vp, i32, vp, i32, i32, vp, C.POINTER(RumiLbaResidentOut)]
     L.rumi_bundle_adjustment.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp]
     L.rumi_sim3_inliers.argtypes = [vp, i32] + [vp] * 17
     L.rumi_merge_ba.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -113,6 +121,38 @@ class Optimizer:
         self.last_call_s = time.perf_counter() - t0
         capi.check(rc)
         return stats, kp, mp, erase[:len(em)]
+
+    def LocalBundleAdjustmentResident(self, covis, cur_slot, neigh_slots, init_slot, stop_flag=None, kf_cap=None, mp_cap=None, erase_cap=None,
+                                      fill=0, check=True):
+        """rumi_local_ba_resident: Optimizer::LocalBundleAdjustment with the window assembled on the device from the store ``covis``.
+        Returns dict(kf_slots [n_kf], num_OptKF, num_fixedKF, kf_pose7 [num_OptKF, 7], mp_ids [num_MPs], mp_pos3 [num_MPs, 3], num_edges,
+        erased [n_erased, 3] = (slot, point id, feature), stats [4], status, raw = the untrimmed output arrays).  The capacities default to
+        the store's and the handle's sizes; every output byte starts as ``fill``; with check=False a refusal comes back as status."""
+        neigh = np.ascontiguousarray(neigh_slots, np.int32).reshape(-1)
+        kf_cap = covis.max_kf if kf_cap is None else int(kf_cap)
+        mp_cap = covis.max_points if mp_cap is None else int(mp_cap)
+        erase_cap = (1 << 18) if erase_cap is None else int(erase_cap)
+        f = lambda n, dt: np.frombuffer(bytes([fill]) * (max(int(n), 1) * np.dtype(dt).itemsize), dt).copy()
+        raw = dict(kf_slots=f(kf_cap, np.int32), kf_pose7=f(kf_cap * 7, np.float32), mp_ids=f(mp_cap, np.int32), mp_pos3=f(mp_cap * 3, np.float32),
+                   erased=f(erase_cap * 3, np.int32))
+        out = RumiLbaResidentOut.from_buffer_copy(bytes([fill]) * C.sizeof(RumiLbaResidentOut))
+        out.kf_cap, out.mp_cap, out.erase_cap = kf_cap, mp_cap, erase_cap
+        for k, v in raw.items():
+            setattr(out, k, v.ctypes.data)
+        sp = capi.ptr(stop_flag) if stop_flag is not None else None
+        import time
+        t0 = time.perf_counter()
+        rc = self._lib.rumi_local_ba_resident(self._h, covis._h, int(cur_slot), capi.ptr(neigh), len(neigh), int(init_slot), sp, C.byref(out))
+        self.last_call_s = time.perf_counter() - t0
+        if check:
+            capi.check(rc)
+        res = dict(status=int(rc), raw=raw, stats=np.array(out.stats, np.int32), header=bytes(out))
+        if rc == capi.RUMI_OK and not res["stats"][3]:
+            nk, no, nm, ne = out.n_kf, out.num_OptKF, out.num_MPs, out.n_erased
+            res.update(kf_slots=raw["kf_slots"][:nk], num_OptKF=no, num_fixedKF=out.num_fixedKF, kf_pose7=raw["kf_pose7"][:no * 7].reshape(no, 7),
+                       mp_ids=raw["mp_ids"][:nm], mp_pos3=raw["mp_pos3"][:nm * 3].reshape(nm, 3), num_edges=out.num_edges,
+                       erased=raw["erased"][:ne * 3].reshape(ne, 3))
+        return res
 
     def LocalBundleAdjustmentBatch(self, windows, n_workers=4, return_status=False):
         """rumi_local_ba_batch: `windows` = list of (kf_pose, kf_fixed, mp_pos, e_mp, e_kf, e_obs, e_inv_sigma2, K4) tuples; returns one
