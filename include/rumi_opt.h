@@ -287,6 +287,60 @@ int rumi_sim3_ransac_batch(RumiOptimizer *o, int32_t n_solvers, const RumiSim3Ra
                            const float *X3Dc2, const float *sigma2_1, const float *sigma2_2, int32_t window, const int32_t *triples,
                            RumiSim3RansacResult *results, uint8_t *inlier_out, int32_t *n_inliers_all, float *T12_all);
 
+/* CloudMerging::ComputeSubmapSim3 -- R/lib_src/CloudMerging.cc:434-825 -- as a session over one resident score set: the set of
+ * Sim3Solver::ComputeInliersNum does not change during the function, so it is uploaded once (begin), scored for given transforms (score, :611, :748,
+ * :809) and used by the whole RANSAC loop of :643-741 in one call (ransac).  The session lives in the handle; its blocks grow on demand.
+ *   begin   validates as rumi_sim3_ransac does (n_pairs >= 1, ascending pair_start, non-NULL arrays when total > 0) and uploads the set; S_kf1w /
+ *           S_kf2w of the set are not read (every solver brings its own).  A second begin replaces the set, end drops it; every other entry
+ *           without a set returns RUMI_E_INVALID.  total == 0 and pairs with pair_denominator == 0 are legal: their ratios are 0 (Sim3Solver.cc:644-647).
+ *   score   ComputeInliersNum for n_S transforms: S_c1w2 / S_c2w1 [n_S][n_pairs][8] are the composed transforms the caller forms as for
+ *           rumi_sim3_inliers; per transform inlier_out [n_S][total] (may be NULL), ratio_out [n_S][n_pairs] (may be NULL) and median_out [n_S]
+ *           hold the bytes rumi_sim3_inliers returns for the same set. */
+int rumi_submap_sim3_begin(RumiOptimizer *o, const RumiSim3ScoreSet *set);
+int rumi_submap_sim3_end(RumiOptimizer *o);
+int rumi_submap_sim3_score(RumiOptimizer *o, int32_t n_S, const double *S_c1w2, const double *S_c2w1, uint8_t *inlier_out, float *ratio_out,
+                           float *median_out);
+
+/* The loop of CloudMerging.cc:643-741: one Sim3Solver per selected key-frame pair, each running the rumination overload of iterate
+ * (Sim3Solver.cc:292-404) in blocks of 20 until it converges or has used its mRansacMaxIts iterations; the first solver that converges ends the
+ * loop.  A solver that does not converge always uses all its iterations, so the iterations form one stream of the shared rand(): solver j runs
+ * the positions [sum of the its before it, + its_j).  triples [sum its][3] is flat in solver order, each solver's segment drawn with that
+ * solver's n exactly as :321-331, indices relative to its `first`; correspondences are concatenated as for rumi_sim3_ransac_batch.
+ * The device evaluates the stream in chunks (ComputeSim3, CheckInliers and ComputeInliersNum of every iteration as rumi_sim3_ransac with
+ * score = the resident set under this solver's S_kf) and applies the sequential rule in stream order: per solver mnBestInliers starts at 0,
+ * bestRatio starts at best_ratio_in and is shared by the solvers; an iteration is taken when ratio >= bestRatio && nIn >= mnBestInliers (of two
+ * equal ones the later is held); it converges when (double)ratio > 0.10 && nIn > min_inliers, which ends the call with the later solvers
+ * RUMI_SIM3_NOT_REACHED.  A degenerate minimal set (valid == 0) repeats the solver's last valid iteration; if the solver has none yet it counts
+ * 0 inliers under the ratio scored for its identity record, and later degenerate sets repeat that.
+ *   results[j]   state (CONVERGED / EXHAUSTED / NOT_REACHED), its = iterations it consumed, best_hyp = stream position of the iteration whose record is
+ *                held as mBest* (-1: none was taken; for a repeated degenerate set the position of the iteration it repeats), best_inliers =
+ *                mnBestInliers, best_ratio_after = the shared ratio when this solver ended (NOT_REACHED: when the call ended), T12 = that
+ *                iteration's record as rumi_sim3_ransac lays it out (zeros when best_hyp is -1)
+ *   its_consumed the iterations consumed in all: the caller advances rand() by three times that
+ *   n_inliers_all / median_all / T12_all  [sum its] / [sum its] / [sum its][16], each may be NULL: the first its_consumed entries are, per
+ *                iteration, the bytes rumi_sim3_ransac returns for that solver and triple; the entries after them are not written
+ * The rumination overload never fills vbInliers, so no mask comes back.  Results do not depend on the chunk length.  RUMI_E_INVALID (no set, n < 3,
+ * ranges out of order, a triple outside [0, n), its < 1) and RUMI_E_CAPACITY leave every output untouched. */
+typedef struct RumiSubmapSolver {
+    int32_t first, n;          /* its correspondences in the concatenated X3Dc arrays, n >= 3 */
+    int32_t min_inliers, its;  /* mRansacMinInliers; mRansacMaxIts after SetRansacParameters, >= 1 */
+    int32_t fix_scale;
+    float K4_1[4], K4_2[4];
+    double S_kf1w[8], S_kf2w[8];   /* g2o::Sim3(R, t, 1.0) of the solver's mpKF1 / mpKF2 (Sim3Solver.cc:347-348) */
+} RumiSubmapSolver;
+typedef struct RumiSubmapSolverResult {
+    int32_t state;             /* RUMI_SIM3_CONVERGED / _EXHAUSTED / _NOT_REACHED */
+    int32_t its;               /* iterations it consumed */
+    int32_t best_hyp;          /* stream position of the iteration held as mBest*, -1 if none was taken */
+    int32_t best_inliers;      /* mnBestInliers */
+    float best_ratio_after;    /* the shared bestInlierRatio when this solver ended */
+    float T12[16];             /* that iteration's record as rumi_sim3_ransac lays it out */
+} RumiSubmapSolverResult;
+int rumi_submap_sim3_ransac(RumiOptimizer *o, int32_t n_solvers, const RumiSubmapSolver *solvers, int32_t n_total, const float *X3Dc1,
+                            const float *X3Dc2, const float *sigma2_1, const float *sigma2_2, const int32_t *triples /*[sum its][3]*/,
+                            float best_ratio_in, RumiSubmapSolverResult *results, int32_t *its_consumed,
+                            int32_t *n_inliers_all, float *median_all, float *T12_all /* [sum its] each, may be NULL */);
+
 /* Optimizer::OptimizeSim3 (the pair form of rumi_optimize_sim3: S_c1w == NULL, no skip flags) of J candidates in one call, one workgroup
  * per problem.  Correspondences are concatenated as above; per problem the bytes rumi_optimize_sim3 returns: S_io8 [J][8] in / out,
  * status_out [n_total], result3 [J][3].  n = 0 and "n - nBad < 10" behave as there. */

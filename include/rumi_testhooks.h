@@ -89,6 +89,12 @@ int rumi_hook_covis_read_row(struct RumiCovis *c, int32_t slot, int32_t cap, int
 int rumi_hook_covis_read_poses(struct RumiCovis *c, int32_t n_kf, const int32_t *slots, double *pose8, int32_t *has_pose, int32_t n_pt,
                                const int32_t *ids, int32_t *map_id, int32_t *has_map, int32_t from_device);
 
+/* The chunk length of rumi_submap_sim3_ransac on this optimiser (rumi_opt.h): iterations of the stream enqueued between two read-backs of the
+ * rule's state.  0 = the library's default; a length at or above the sum of the solvers' iterations runs the call as one chunk.  Results do not
+ * depend on it; the tests put chunk edges on solver boundaries and on the converging iteration. */
+struct RumiOptimizer;
+int rumi_hook_submap_sim3_set_chunk(struct RumiOptimizer *o, int32_t chunk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,7 +110,8 @@ MATCH_SYMBOLS = ["rumi_descriptor_distance", "rumi_match_create", "rumi_match_de
 
 OPT_SYMBOLS = ["rumi_opt_create", "rumi_opt_destroy", "rumi_pose_optimization", "rumi_pose_optimization_batch", "rumi_local_ba", "rumi_local_ba_resident", "rumi_local_ba_batch", "rumi_merge_ba", "rumi_bundle_adjustment", "rumi_sim3_inliers",
                "rumi_optimize_sim3", "rumi_sim3_ransac", "rumi_opt_stage_ms", "rumi_opt_set_profiling", "rumi_opt_kernel_ms", "rumi_opt_footprint",
-               "rumi_essential_graph", "rumi_sim3_correct_points", "rumi_sim3_ransac_batch", "rumi_optimize_sim3_batch"]
+               "rumi_essential_graph", "rumi_sim3_correct_points", "rumi_sim3_ransac_batch", "rumi_optimize_sim3_batch",
+               "rumi_submap_sim3_begin", "rumi_submap_sim3_end", "rumi_submap_sim3_score", "rumi_submap_sim3_ransac"]
 
 VOC_SYMBOLS = ["rumi_voc_create", "rumi_voc_load_text", "rumi_voc_destroy", "rumi_voc_words", "rumi_voc_levels", "rumi_voc_set_levels", "rumi_voc_assemble", "rumi_voc_transform_features",
                "rumi_voc_transform_batch_device", "rumi_voc_transform"]
@@ -223,7 +224,8 @@ def covis_lib():
 
 HOOK_SYMBOLS = ["rumi_hook_sort_like_std", "rumi_hook_sort_device", "rumi_hook_std_sort", "rumi_hook_quadtree", "rumi_hook_sinf", "rumi_hook_cosf",
                 "rumi_hook_fast_atan2", "rumi_hook_cv_round", "rumi_hook_magic_div", "rumi_hook_newpts_matches", "rumi_hook_lane_packing", "rumi_hook_disc_moments",
-                "rumi_hook_stream_plan", "rumi_hook_parse_hw_queues", "rumi_hook_octree_bins", "rumi_hook_compact_hist_lds", "rumi_hook_covis_read_attributes", "rumi_hook_covis_read_row", "rumi_hook_covis_read_poses"]
+                "rumi_hook_stream_plan", "rumi_hook_parse_hw_queues", "rumi_hook_octree_bins", "rumi_hook_compact_hist_lds", "rumi_hook_covis_read_attributes", "rumi_hook_covis_read_row", "rumi_hook_covis_read_poses",
+                "rumi_hook_submap_sim3_set_chunk"]
 
 
 def hooks():
@@ -252,5 +254,6 @@ def hooks():
     L.rumi_hook_covis_read_attributes.argtypes = [vp, i32, vp, vp, i32]
     L.rumi_hook_covis_read_row.argtypes = [vp, i32, i32, vp, vp, vp]
     L.rumi_hook_covis_read_poses.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32]
+    L.rumi_hook_submap_sim3_set_chunk.argtypes = [vp, i32]
     L._hooks_ready = True
     return L

@@ -11,6 +11,7 @@
 //   ba_big.inc          k_big_init / w / schur: block-sparse Schur accumulation of a window of more than 255 unknowns
 //   chol_blocked.inc    k_chol_diag / trsm / syrk / backsub: multi-workgroup blocked Cholesky (large windows, essential graph)
 //   sim3.inc            k_sim3_inliers / ransac / opt.  Host: sim3_host.inc
+//   submap_sim3.inc     k_sms_*: the RANSAC of ComputeSubmapSim3 over a resident score set, every solver in one call.  Host: submap_sim3_host.inc
 //   ba_windows.inc      k_baw_* / k_baws_*: local BA with the window as a batch dimension.  Host: ba_windows_host.inc
 //   essential.inc       k_eg_*: OptimizeEssentialGraph.  Host: essential_host.inc
 //   ba_resident.inc     k_lba_*: the local window assembled from the covisibility store (rumi_local_ba_resident).  Host: ba_resident_host.inc
@@ -48,6 +49,7 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 #include "chol_blocked.inc"
 #include "sim3.inc"
 #include "sim3_batch.inc"
+#include "submap_sim3.inc"
 #include "ba_windows.inc"
 #include "essential.inc"
 #include "ba_resident.inc"
@@ -183,6 +185,17 @@ struct LbaResident {
     void count(Footprint &f) const { f.add(in, out, work, edge, ptTag); }
 };
 
+// The sub-map alignment session (submap_sim3_host.inc): the resident score set of rumi_submap_sim3_begin and the blocks of a call, all grown on demand
+struct SubmapSim3Part {
+    bool have = false;               // between begin and end
+    int chunk = 0;                   // iterations between two read-backs of the state; 0 = the growing default (rumi_hook_submap_sim3_set_chunk)
+    SmsSet view{};                   // where the parts of `set` lie on the device
+    MirrorBuf<uint8_t> set;          // the score set as begin laid it out
+    MirrorBuf<uint8_t> io, out;      // a call's upload with the state and result records; its per-iteration results
+    DevBuf<uint8_t> work;            // rows of [sR | t], gSw1w2 and its inverse, counts and ratios per (iteration, pair)
+    void count(Footprint &f) const { f.add(set, io, out, work); }
+};
+
 constexpr int kBaMaxWorkers = 16;
 struct RumiOptimizer {
     int device = 0;
@@ -197,6 +210,7 @@ struct RumiOptimizer {
     // essential graph (essential_host.inc): the dense matrix and one block for the rest, taken by the first rumi_essential_graph call
     DevBuf<uint8_t> egA, eg;
     LbaResident lba;
+    SubmapSim3Part sms;
 };
 
 extern "C" void rumi_opt_destroy(RumiOptimizer *o) {
@@ -226,7 +240,7 @@ extern "C" int rumi_opt_create(int32_t max_pose_edges, int32_t max_pose_batch, i
 extern "C" int rumi_opt_footprint(const RumiOptimizer *o, int64_t out2[2]) {
     if (!o || !out2) return RUMI_E_INVALID;
     Footprint f;
-    o->pose.count(f); o->ba.count(f); f.add(o->egA, o->eg); o->lba.count(f);
+    o->pose.count(f); o->ba.count(f); f.add(o->egA, o->eg); o->lba.count(f); o->sms.count(f);
     for (const auto &a : o->batchArenas) a.count(f);
     for (const auto &r : o->batchRunners) r.count(f);
     for (const auto &w : o->workers) w.count(f);
@@ -277,4 +291,5 @@ static int fetch_published_scalars(BaArena::HostLoop &s, hipStream_t st) {
 #include "ba_single_host.inc"
 #include "sim3_host.inc"
 #include "sim3_batch_host.inc"
+#include "submap_sim3_host.inc"
 #include "ba_resident_host.inc"

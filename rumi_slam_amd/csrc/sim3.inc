@@ -14,17 +14,23 @@ __device__ __forceinline__ float reproj2(const double *S, const float *K, const 
     const float dx = kp[0] - u, dy = kp[1] - v;
     return dx * dx + dy * dy;
 }
+// ComputeInliersNum's test of one matched key-point pair (:621-630) under the composites gSc1w2 / gSc2w1 of its key-frame pair
+__device__ __forceinline__ bool sim3_score_inlier(const double *Sc1w2, const double *Sc2w1, const float *K1, const float *K2, const float *X1, const float *X2,
+                                                  const float *kp1, const float *kp2, float sg1, float sg2, bool e1, bool e2) {
+    const float err1 = reproj2(Sc1w2, K1, X2, kp1);   // map-2 point into key-frame 1
+    const float err2 = reproj2(Sc2w1, K2, X1, kp2);   // map-1 point into key-frame 2
+    const bool ok1 = (double)err1 < 2 * 9.210 * (double)sg1 || e2;
+    const bool ok2 = (double)err2 < 2 * 9.210 * (double)sg2 || e1;
+    return ok1 && ok2;
+}
 __global__ void k_sim3_inliers(int total, const int32_t *pairOf, const double *Sc1w2, const double *Sc2w1, const float *K1, const float *K2,
                                const float *X1, const float *X2, const float *kp1, const float *kp2, const float *sigma1, const float *sigma2,
                                const uint8_t *edge1, const uint8_t *edge2, uint8_t *inlier) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     const int pr = pairOf[i];
-    const float err1 = reproj2(Sc1w2 + (size_t)pr * 8, K1, X2 + (size_t)i * 3, kp1 + (size_t)i * 2);   // map-2 point into key-frame 1
-    const float err2 = reproj2(Sc2w1 + (size_t)pr * 8, K2, X1 + (size_t)i * 3, kp2 + (size_t)i * 2);   // map-1 point into key-frame 2
-    const bool ok1 = (double)err1 < 2 * 9.210 * (double)sigma1[i] || edge2[i];
-    const bool ok2 = (double)err2 < 2 * 9.210 * (double)sigma2[i] || edge1[i];
-    inlier[i] = ok1 && ok2;
+    inlier[i] = sim3_score_inlier(Sc1w2 + (size_t)pr * 8, Sc2w1 + (size_t)pr * 8, K1, K2, X1 + (size_t)i * 3, X2 + (size_t)i * 3, kp1 + (size_t)i * 2,
+                                  kp2 + (size_t)i * 2, sigma1[i], sigma2[i], edge1[i] != 0, edge2[i] != 0);
 }
 
 
@@ -158,6 +164,15 @@ __device__ __forceinline__ bool sim3_check_inlier(const float *K1, const float *
     return err1 < thr1 && err2 < thr2;
 }
 
+// gSw1w2 = gSc1w^-1 * gSc1c2 * gSc2w (:338-347) of one hypothesis; Skf = g2o::Sim3(R, t, 1.0) of the solver's two key-frames, 2 x 8 doubles.
+// k_sim3_ransac and k_sms_hyp (submap_sim3.inc) both call it, so both round alike.
+__device__ __forceinline__ DSim3 sim3_hyp_world(const float (&R)[3][3], const float (&t12)[3], float s12, const double *Skf) {
+    double Rd[3][3];
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Rd[r][c] = (double)R[r][c];
+    const DSim3 Sc1c2{quat_from_matrix(Rd), {(double)t12[0], (double)t12[1], (double)t12[2]}, (double)s12};
+    return sim3_mul(sim3_mul(sim3_inverse(sim3_from8(Skf)), Sc1c2), sim3_from8(Skf + 8));
+}
+
 __global__ __launch_bounds__(256) void k_sim3_ransac(RansacArgs A) {
     __shared__ float sT12[12], sT21[12];      // rows of [sR | t]
     __shared__ int sCnt;
@@ -167,12 +182,7 @@ __global__ __launch_bounds__(256) void k_sim3_ransac(RansacArgs A) {
         sCnt = 0;
         float R[3][3], t12[3], s12;
         sim3_minimal_solve(A.X1, A.X2, A.tri + h * 3, A.fixScale, sT12, sT21, A.T12 + (size_t)h * 16, R, t12, s12);
-        if (A.total > 0) {                                          // :338-347
-            double Rd[3][3];
-            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Rd[r][c] = (double)R[r][c];
-            const DSim3 Sc1c2{quat_from_matrix(Rd), {(double)t12[0], (double)t12[1], (double)t12[2]}, (double)s12};
-            sSw1w2 = sim3_mul(sim3_mul(sim3_inverse(sim3_from8(A.Skf)), Sc1c2), sim3_from8(A.Skf + 8));
-        }
+        if (A.total > 0) sSw1w2 = sim3_hyp_world(R, t12, s12, A.Skf);
     }
     __syncthreads();
     int mine = 0;
@@ -197,11 +207,9 @@ __global__ __launch_bounds__(256) void k_sim3_ransac(RansacArgs A) {
     __syncthreads();
     for (int i = tid; i < A.total; i += 256) {
         const int pr = A.pairOf[i];
-        const float err1 = reproj2(comp + (size_t)pr * 16, A.sK1, A.sX2 + (size_t)i * 3, A.kp1 + (size_t)i * 2);
-        const float err2 = reproj2(comp + (size_t)pr * 16 + 8, A.sK2, A.sX1 + (size_t)i * 3, A.kp2 + (size_t)i * 2);
-        const bool ok1 = (double)err1 < 2 * 9.210 * (double)A.sg1[i] || A.e2[i];
-        const bool ok2 = (double)err2 < 2 * 9.210 * (double)A.sg2[i] || A.e1[i];
-        if (ok1 && ok2) atomicAdd(&cnt[pr], 1);
+        if (sim3_score_inlier(comp + (size_t)pr * 16, comp + (size_t)pr * 16 + 8, A.sK1, A.sK2, A.sX1 + (size_t)i * 3, A.sX2 + (size_t)i * 3, A.kp1 + (size_t)i * 2,
+                              A.kp2 + (size_t)i * 2, A.sg1[i], A.sg2[i], A.e1[i] != 0, A.e2[i] != 0))
+            atomicAdd(&cnt[pr], 1);
     }
 }
 

@@ -40,25 +40,32 @@ __global__ __launch_bounds__(256) void k_s3b_hyp(S3bArgs A) {
                        A.Tall + (size_t)g * 16, R, t12, s12);
 }
 
-// one wave per (solver, hypothesis), four to a workgroup: CheckInliers over the solver's correspondences, the count by ballot + popcount
+// CheckInliers of one hypothesis over the n correspondences of its solver by one wave: the count by ballot + popcount (the same in every lane), the
+// mask where the caller keeps one.  k_s3b_check and k_sms_check (submap_sim3.inc) both call it.
+__device__ __forceinline__ int sim3_check_wave(int lane, int n, const float *K1, const float *K2, const float *rows12, const float *rows21, const float *X1,
+                                               const float *X2, const float *thr1, const float *thr2, uint8_t *mask) {
+    float T12[12], T21[12];
+    for (int k = 0; k < 12; k++) { T12[k] = rows12[k]; T21[k] = rows21[k]; }
+    int cnt = 0;
+    for (int base = 0; base < n; base += 64) {
+        const int i = base + lane;
+        bool in = false;
+        if (i < n) {
+            in = sim3_check_inlier(K1, K2, T12, T21, X1 + (size_t)i * 3, X2 + (size_t)i * 3, thr1[i], thr2[i]);
+            if (mask) mask[i] = in;
+        }
+        cnt += __popcll(__ballot(in));
+    }
+    return cnt;
+}
+
+// one wave per (solver, hypothesis), four to a workgroup: CheckInliers over the solver's correspondences
 __global__ __launch_bounds__(256) void k_s3b_check(S3bArgs A) {
     const int lane = threadIdx.x & 63, g = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (g >= A.J * A.R) return;
     const S3bSolver &s = A.sol[g / A.R];
-    const float *X1 = A.X1 + (size_t)s.first * 3, *X2 = A.X2 + (size_t)s.first * 3, *thr1 = A.thr1 + s.first, *thr2 = A.thr2 + s.first;
-    float T12[12], T21[12];
-    for (int k = 0; k < 12; k++) { T12[k] = A.rows12[(size_t)g * 12 + k]; T21[k] = A.rows21[(size_t)g * 12 + k]; }
-    uint8_t *mask = A.mask + (size_t)g * A.nMax;
-    int cnt = 0;
-    for (int base = 0; base < s.n; base += 64) {
-        const int i = base + lane;
-        bool in = false;
-        if (i < s.n) {
-            in = sim3_check_inlier(s.K1, s.K2, T12, T21, X1 + (size_t)i * 3, X2 + (size_t)i * 3, thr1[i], thr2[i]);
-            mask[i] = in;
-        }
-        cnt += __popcll(__ballot(in));
-    }
+    const int cnt = sim3_check_wave(lane, s.n, s.K1, s.K2, A.rows12 + (size_t)g * 12, A.rows21 + (size_t)g * 12, A.X1 + (size_t)s.first * 3, A.X2 + (size_t)s.first * 3,
+                                    A.thr1 + s.first, A.thr2 + s.first, A.mask + (size_t)g * A.nMax);
     if (lane == 0) A.nInAll[g] = cnt;
 }
 
